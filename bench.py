@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the charging-hub step path at 65 536 parallel envs (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes what the last timed step computed
+(--dump-outputs DIR: obs / reward / done as DIR/<name>.npy, float32; the inputs are the same from run to run) and prints the line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...; `roofline` is null).  Everything else described below --
+the profiled days behind `roofline`, value_day_avg, `sustained`, `phases`, roofline_c5, packed_actions, dropin_single_env / roofline_compat
+and cpu_baseline -- runs with --full only (the --no-* options then leave parts of it out).
 
 Both forms work for N > 1.  Started WITHOUT a launcher (no WORLD_SIZE in the environment) `--gpus N` makes this process the
 launcher: it spawns N fresh rank processes (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_PORT and a private rendezvous directory in
@@ -274,6 +280,31 @@ def launch_ranks(args):
         shutil.rmtree(rdv, ignore_errors=True)
     sys.stdout.flush()
     raise SystemExit(rc)
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: at most this much in all; a larger output is written as a fixed, seeded sample of its envs
+
+
+def dump_outputs(out_dir, rows, D):
+    """--dump-outputs: what the timed path's last step handed its caller, from the packed [envs, D + 2] f32 block (obs, reward, done),
+    as out_dir/obs.npy [envs, D], reward.npy [envs], done.npy [envs] (float32).  Where the three would exceed DUMP_MAX_BYTES, the same
+    fixed, seeded sample of envs is written for all three and env_index.npy (float64) names the envs kept.  -> the names written"""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = rows.shape[0]
+    keep = max(1, DUMP_MAX_BYTES // ((D + 2) * 4 + 8))
+    out = {}
+    if n > keep:
+        idx = np.sort(np.random.RandomState(SEED).choice(n, size=keep, replace=False))
+        rows = rows[idx]
+        out["env_index"] = idx.astype(np.float64)
+    out["obs"] = np.ascontiguousarray(rows[:, :D], dtype=np.float32)
+    out["reward"] = np.ascontiguousarray(rows[:, D], dtype=np.float32)
+    out["done"] = np.ascontiguousarray(rows[:, D + 1], dtype=np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(out)
 
 
 PROFILE_DAYS = 5  # whole days stepped for the per-kernel timestamps, every PROFILE_DAYS-th step sampled
@@ -613,7 +644,18 @@ def main():
                     help="stop every rank before libchub is loaded and print who it is (launch plumbing check, runs without a GPU)")
     ap.add_argument("--dry-run-fail-rank", type=int, default=-1, help="(tests) with --dry-run: this rank exits with status 3")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="launcher: seconds before ranks still running are stopped")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline too: the profiled days behind `roofline`, the ten days behind value_day_avg, "
+                         "`sustained`, the per-rank `phases` (with a communicator), roofline_c5, packed_actions, dropin_single_env and "
+                         "cpu_baseline (the --no-* options leave parts of it out); without it a run sets up, warms up, times the steps, "
+                         "writes its outputs (--dump-outputs) and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (obs, reward, done of every env, float32) as "
+                         "DIR/<name>.npy (rank 0, all ranks' envs)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline alone
+        for k in ("no_cpu_baseline", "no_events", "no_day_avg", "no_sustained", "no_c5", "no_bits", "no_dropin"):
+            setattr(args, k, True)
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         launch_ranks(args)  # does not return
@@ -796,6 +838,8 @@ def main():
         assert np.isfinite(g).all()
         assert ((g[:, D + 1] > 0.5) == (((warmup + steps) % 96) == 0)).all(), "a shard's done flags are out of step"
         assert (np.abs(g[:, :D]).sum(axis=1) > 0).all(), "a shard's rows never arrived"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, g if use_comm else last, D)
 
     # ---- untimed: on to the next episode boundary, then whole days with per-kernel timestamps on every slot of the day once
     slot_us = env_us = 0.0
@@ -855,7 +899,7 @@ def main():
     # day averages above), the gather alone (HIP events around 100 of them back to back), the host's issue time per step in the
     # timed region, the rank's own wall clock per step -- gathered to rank 0 through the communicator
     phases = None
-    if comm is not None:
+    if comm is not None and args.full:
         # (a rank that fails in here leaves the others inside a collective that never completes: it says so and exits non-zero at once,
         # and the launcher -- this file's, or torch.distributed.run -- stops the rest instead of waiting for its timeout)
         try:

@@ -106,3 +106,27 @@ def test_reference_stations_rate_is_timed_where_the_reference_build_exists():
     # a hub with a station without piles times the other station alone
     r0 = b.reference_stations_rate(dict(station_list=[16, 0], station_type_list=["fast", "slow"], fcev_permeate=0.0), target_seconds=0.3)
     assert r0["value"] > r["value"]
+
+
+def test_dump_outputs_writes_the_last_step_as_float32_within_the_cap(tmp_path):
+    """--dump-outputs: obs / reward / done of the packed [envs, D + 2] block as float32; past the cap, one fixed, seeded sample of envs for
+    all three arrays, named by env_index.npy"""
+    import numpy as np
+    b = _bench()
+    rows = np.random.RandomState(3).uniform(-1, 1, size=(100, 15)).astype(np.float32)
+    assert b.dump_outputs(str(tmp_path / "all"), rows, 13) == ["done", "obs", "reward"]
+    got = {k: np.load(str(tmp_path / "all" / (k + ".npy"))) for k in ("obs", "reward", "done")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["obs"], rows[:, :13]) and np.array_equal(got["reward"], rows[:, 13]) and np.array_equal(got["done"], rows[:, 14])
+    cap = b.DUMP_MAX_BYTES
+    try:
+        b.DUMP_MAX_BYTES = 40 * (15 * 4 + 8)
+        for d in ("s1", "s2"):
+            assert b.dump_outputs(str(tmp_path / d), rows, 13) == ["done", "env_index", "obs", "reward"]
+    finally:
+        b.DUMP_MAX_BYTES = cap
+    idx = np.load(str(tmp_path / "s1" / "env_index.npy"))
+    assert idx.dtype == np.float64 and idx.size == 40 and (np.diff(idx) > 0).all()
+    assert np.array_equal(idx, np.load(str(tmp_path / "s2" / "env_index.npy")))
+    assert np.array_equal(np.load(str(tmp_path / "s1" / "obs.npy")), rows[idx.astype(np.int64), :13])
+    assert sum(os.path.getsize(str(tmp_path / "s1" / (k + ".npy"))) - 128 for k in ("obs", "reward", "done", "env_index")) <= 40 * (15 * 4 + 8)

@@ -24,7 +24,7 @@ def _bench(*flags):
 
 
 def test_bench_short_form_prints_the_contract_line():
-    d = _bench("--no-c5", "--no-cpu-baseline")
+    d = _bench("--full", "--no-c5", "--no-cpu-baseline")
     assert d["metric"].startswith("env-steps/sec") and d["unit"] == "env-steps/s" and d["n_gpus"] == 1
     assert d["steps"] == 20 and d["warmup"] == 5 and d["higher_is_better"] is True and d["vs_baseline"] is None
     assert d["dtype"] == "f64" and d["data"] == "synthetic" and "65536 envs x hub [20 fast, 25 slow]" in d["config"]["workload"]
@@ -53,12 +53,33 @@ def test_bench_short_form_prints_the_contract_line():
     assert abs(su["value"] / d["value_day_avg"] - 1) < 0.05
 
 
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """without --full: the timed steps and the line, nothing measured beside them; --dump-outputs writes what the last timed step computed,
+    the same arrays on every run with the same arguments"""
+    import numpy as np
+    outs = []
+    for name in ("a", "b"):
+        d = _bench("--dump-outputs", str(tmp_path / name))
+        assert d["steps"] == 20 and d["warmup"] == 5 and d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+        assert abs(d["value"] - 65536 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"] and d["value"] > 5e8
+        assert d["roofline"] is None
+        for k in ("day_avg", "value_day_avg", "sustained", "phases", "roofline_c5", "packed_actions", "dropin_single_env", "roofline_compat", "cpu_baseline"):
+            assert k not in d, k
+        outs.append({k: np.load(str(tmp_path / name / (k + ".npy"))) for k in ("obs", "reward", "done")})
+    o = outs[0]
+    assert o["obs"].shape == (65536, 13) and o["reward"].shape == (65536,) and o["done"].shape == (65536,)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in o.values())
+    assert (o["done"] == 0).all() and (np.abs(o["obs"]).sum(axis=1) > 0).all()  # step 24 of the day: no episode ends there
+    for k in o:
+        assert np.array_equal(o[k].view(np.uint32), outs[1][k].view(np.uint32)), k
+
+
 def test_bench_compat_block_carries_the_end_state_of_the_reference_exact_run():
     """`roofline_compat` (the reference-exact COMPAT mode at 65 536 envs: k_slot_walk2 + k_env) carries a digest of what its days left behind --
     observations, rewards, slot state, station records, the streams; the same days on the one-kernel-per-station form (the unit's first lane
     walks the env's two streams in the reference's consumption order, CHS.hpp:1272-1316 / 1583-1627; pinned to the reference's fixtures by
     test_compat_matches_reference_golden[*-4_per_station]) must leave the same digest: the rate the line prints is the rate of a correct run."""
-    d = _bench("--no-cpu-baseline", "--no-bits")
+    d = _bench("--full", "--no-cpu-baseline", "--no-bits")
     rc = d["roofline_compat"]
     assert rc["days_stepped"] == 8 and len(rc["end_state_digest"]) == 32 and 0.1 < rc["frac"] < 1.0
     assert "traffic" in rc and (rc["traffic"] is None or rc["traffic_over_algorithmic"] > 0.3)
@@ -74,7 +95,7 @@ def test_bench_compat_block_carries_the_end_state_of_the_reference_exact_run():
 
 
 def test_bench_multi_rank_path_on_a_world_of_one():
-    d = _bench("--force-comm", "--graph", "off", "--no-c5", "--no-cpu-baseline", "--no-events")
+    d = _bench("--full", "--force-comm", "--graph", "off", "--no-c5", "--no-cpu-baseline", "--no-events")
     assert d["n_ranks_seen"] == 1 and d["rccl_comm_count"] == 1 and len(d["ranks"]) == 1 and d["ranks"][0]["rank"] == 0
     assert "ncclSend/ncclRecv" in d["config"]["collective"] and d["value"] > 2e8
     assert d["roofline"] is None                  # --no-events: no per-kernel block, never a made-up one
@@ -85,7 +106,7 @@ def test_bench_multi_rank_path_on_a_world_of_one():
 
 
 def test_bench_multi_rank_path_reports_its_phases_with_kernel_times():
-    d = _bench("--force-comm", "--graph", "off", "--no-c5", "--no-cpu-baseline", "--envs", "8192")
+    d = _bench("--full", "--force-comm", "--graph", "off", "--no-c5", "--no-cpu-baseline", "--envs", "8192")
     r0 = d["phases"]["per_rank"][0]               # an 8-GPU shard's worth of envs: the single-launch step, priced as one kernel
     assert 3.0 < r0["slot_kernel_us"] + r0["env_kernel_us"] < 40.0 and 0.0 <= r0["gather_us"] < 200.0
     assert d["phases"]["expected_bound"] in ("gpu (kernels + gather)", "host issue (call by call)")
@@ -96,10 +117,10 @@ def test_bench_multi_rank_path_reports_its_phases_with_kernel_times():
 def test_bench_overlapped_gather_in_a_graph_on_a_world_of_one():
     """--graph on --overlap-gather: the N > 1 graph form with the gather on the communicator's own stream (graph edges); the line says so and
     its expectation is the larger of kernels and gather, not their sum"""
-    d = _bench("--force-comm", "--graph", "on", "--overlap-gather", "--no-c5", "--no-cpu-baseline", "--envs", "8192", "--steps", "192", "--warmup", "96")
+    d = _bench("--full", "--force-comm", "--graph", "on", "--overlap-gather", "--no-c5", "--no-cpu-baseline", "--envs", "8192", "--steps", "192", "--warmup", "96")
     assert "communicator's own stream" in d["config"]["collective"] and d["config"]["graph"] == "on"
     r0, ph = d["phases"]["per_rank"][0], d["phases"]
     assert ph["expected_bound"].startswith("gpu (the larger of kernels and gather")
     assert abs(ph["expected_ms_per_step"] * 1e3 - max(r0["slot_kernel_us"] + r0["env_kernel_us"], r0["gather_us"])) < 1e-6
-    s = _bench("--force-comm", "--graph", "on", "--no-c5", "--no-cpu-baseline", "--envs", "8192", "--steps", "192", "--warmup", "96")
+    s = _bench("--full", "--force-comm", "--graph", "on", "--no-c5", "--no-cpu-baseline", "--envs", "8192", "--steps", "192", "--warmup", "96")
     assert d["value"] > 0.7 * s["value"]          # measured 0.95 x the serial graph form on one GPU (the "gather" is a local copy that competes with the kernels)

@@ -5,12 +5,12 @@ TAG=${1:-vX}
 OUT=gpurun_out/round6_${TAG}_all_configs_1gpu.json
 : > $OUT
 for c in c2 c3 c4 c5; do
-  python3 bench.py --config $c --steps 1920 --warmup 384 --no-cpu-baseline --no-c5 2>/dev/null | tail -1 >> $OUT
+  python3 bench.py --full --config $c --steps 1920 --warmup 384 --no-cpu-baseline --no-c5 2>/dev/null | tail -1 >> $OUT
 done
 # the per-GPU share of the weak-scaling job (configs[4] over 8 GPUs: 32 768 envs x [32,32] per GPU)
-python3 bench.py --scaling weak --steps 1920 --warmup 384 --no-cpu-baseline 2>/dev/null | tail -1 >> $OUT
+python3 bench.py --full --scaling weak --steps 1920 --warmup 384 --no-cpu-baseline 2>/dev/null | tail -1 >> $OUT
 # the multi-GPU call pattern on one GPU: communicator of one rank, gather to itself
-python3 bench.py --force-comm --steps 1920 --warmup 384 --no-cpu-baseline --no-c5 2>/dev/null | tail -1 >> $OUT
+python3 bench.py --full --force-comm --steps 1920 --warmup 384 --no-cpu-baseline --no-c5 2>/dev/null | tail -1 >> $OUT
 python3 - $OUT <<'PY'
 import json, sys
 for line in open(sys.argv[1]):

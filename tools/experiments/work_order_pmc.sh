@@ -5,7 +5,7 @@
 OUT=${1:-gpurun_out/work_order_pmc}
 mkdir -p $OUT
 export TMPDIR=/tmp
-ARGS="--steps 96 --warmup 96 --no-cpu-baseline --no-events --no-c5 --no-bits --no-dropin"
+ARGS="--full --steps 96 --warmup 96 --no-cpu-baseline --no-events --no-c5 --no-bits --no-dropin"
 # (bench.py --no-events as the vehicle, as in tools/refresh_profiles.sh.  Round 5 had tools/ab_step_times.py here and lost two counter passes to a
 # run that never finished.  Round 6 looked for the cause (gpurun_out/r6e, r6f; tools/experiments/README.md): NOT an `env` hop in front of python --
 # the records show the profiled command was `python3 tools/ab_step_times.py` itself, variables exported by the shell, and the same command with

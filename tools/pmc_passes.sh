@@ -3,7 +3,7 @@
 OUT=${1:-gpurun_out/pmc}
 mkdir -p $OUT
 export TMPDIR=/tmp
-ARGS="--steps 96 --warmup 96 --no-cpu-baseline --no-events"
+ARGS="--full --steps 96 --warmup 96 --no-cpu-baseline --no-events"
 i=0
 while read -r set; do
   [ -z "$set" ] && continue
