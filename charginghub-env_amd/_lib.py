@@ -10,7 +10,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DATA_DIR = os.path.join(_HERE, "data")
 
 CHUB_FAST, CHUB_SLOW = 0, 1
-RNG_COMPAT, RNG_PHILOX = 0, 1
+RNG_COMPAT, RNG_PHILOX, RNG_PHILOX_CURVES = 0, 1, 2
+RNG_MODES = {"compat": RNG_COMPAT, "philox": RNG_PHILOX, "philox_curves": RNG_PHILOX_CURVES}
 T_COUNT = 38
 TELEMETRY_NAMES = ["hy_act", "hy_flow_speed", "all_power_second", "Store_SOC", "capacity", "total_mass_need", "hy_use",
                    "not_meet", "fc_power", "hy_to_use", "re_used_renew", "re_ev_power_0", "re_ev_power_1",

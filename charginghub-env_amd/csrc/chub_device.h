@@ -109,6 +109,9 @@ struct SlotArrays {          // index = base_k + env*S_k + slot  (station-major)
     CHUB_G(uint32_t) hot;    // COMPAT [NS][4], station-major; PHILOX [N][S0 + S1]: the 4-byte slot state described in
                              // chub_kernels.hip, hub-major (station 0's piles, then station 1's, like an action row)
     CHUB_G(uint8_t) stay8;   // PHILOX [N][S0 + S1]: Station::stay_time of the car in the slot (CHS.hpp:245), written when it is admitted
+    // PHILOX_CURVES (k_slot_curves in chub_kernels.hip): hot is [N][S0 + S1][2] f32 (power, t_soc), hub-major, and beside it
+    CHUB_G(uint32_t) wrd;    // [N][S0 + S1] the PHILOX state word with the class bits zero
+    CHUB_G(float) soc0;      // [N][S0 + S1] the car's arrival SoC, written when it is admitted (introspection only)
     CHUB_G(uint32_t) var[2]; // COMPAT, split step [N][S0 + S1][8], hub-major by admission rank, double-buffered by the parity of the step's tick: the r-th car
                              // a unit admits in that step AS add_car MAKES IT (CHS.hpp:864-877), evaluated by the stream walk where its variates are drawn
                              // (walk_rounds / compat_walk_env): ONE 32-byte record -- power, t_target, t_soc (f32 bits), stay | target level << 7 (the hot
@@ -231,6 +234,7 @@ struct HubParams {
     int32_t packed;          // PHILOX steps run k_slot_packed (any hub shape of up to 512 piles)
     int32_t compat_split;    // COMPAT resets / steps run empties -> walk (lane = env) -> slots instead of one kernel per station
     int32_t xcd;             // PHILOX packed kernels: tiles, tail and level workgroups in XCD-aware order (xcd_order in chub_kernels.hip)
+    int32_t soc_curves;      // CHUB_RNG_PHILOX_CURVES: a PHILOX handle (rng_mode) whose slots run k_slot_curves (continuous arrival SoC, curves on the device)
 };
 
 // Everything a kernel needs that does not change from step to step, kept in device memory and passed by pointer

@@ -2383,6 +2383,154 @@ __global__ __launch_bounds__(BLOCK, 7) void k_slot(const DevCtx *__restrict__ ct
     else slot_body_compat<1, RESET, BLOCK>(hp, sa, ctx->sl, ctx->st, ctx->cr, ctx->tb, k, bl, lds_f, lds_u);
 }
 
+// ---------------------------------------------------------------------------------------- k_slot_curves, PHILOX_CURVES
+// The third RNG mode (CHUB_RNG_PHILOX_CURVES): PHILOX's draws, keyed exactly as PHILOX keys them, with the reference's continuous arrival SoC
+// and car_step evaluated on the device along the curves (car_step_curves + soc_to_time, the arithmetic COMPAT is pinned with).  Internally the
+// handle is a PHILOX handle (hp.rng_mode = MODE_PHILOX: the station draws of k_draw_levels / k_reset_levels and the tail k_env<.., MODE_PHILOX>
+// are reused as they are) with hp.soc_curves = 1, which sends its slot launches here instead of to k_slot_packed / k_slot.
+//   slot state, hub-major [env][S0 + S1] like PHILOX's:
+//     SlotArrays::hot   [NS][2] f32: power, t_soc = soc_to_time(current SoC)   (8 B read + 8 B written per slot and step)
+//     SlotArrays::wrd   [NS]    u32: PHILOX's state word with the class bits zero: bits 0-4 stay left, bit 5 charging, bits 6-10 car_steps taken,
+//                                    bits 22-31 target level                     (4 B read + 4 B written)
+//     SlotArrays::soc0  [NS]    f32: the arrival SoC, written once at admission (introspection: init_soc, k_replay_soc), as stay8
+//   a new car: the PHILOX block px.block(SITE_SOC, hub slot, 0) -- word 0 -> soc_from_word (the continuous SoC; PHILOX's class is word 0 >> 21),
+//   word 1 % 1000 the target level, word 2 late_from_word.  Tape mode: car_tape's .x carries the f32 bits of the recorded arrival SoC.
+// Lane = slot, wave-local units of H = pow2 >= S_k lanes (slot_body_wave's shape), one station per workgroup and the station type a template
+// parameter, so the f64 branches of the curves are uniform per wave; sums as PHILOX's (integers of 2^-19 kW, DPP butterflies).
+template <int TYPE, bool RESET, int BLOCK>
+__device__ __forceinline__ void slot_body_curves(const HubParams &hp, const StepArgs &sa, const SlotArrays &sl, const StationArrays &st,
+                                                 const Tables &tb, const int k, const int64_t block_local) {
+    constexpr int WAVES = BLOCK / 64;
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int H = hp.H[k], S = hp.S[k], logH = hp.logH[k];
+    const int upw = 64 >> logH;
+    const int uiw = lane >> logH;
+    const int slot = lane & (H - 1);
+    const int64_t N = hp.n_envs;
+    const int env = (int) block_local * (WAVES * upw) + wave * upw + uiw;
+    const bool unit_ok = env < (int) N && in_group(sa, env);
+    const bool valid = unit_ok && slot < S;
+    const uint64_t unit_mask = (H == 64) ? ~0ull : (((1ull << H) - 1ull) << (uiw << logH));
+    const int hub_slot = (k ? hp.S[0] : 0) + slot;
+    const uint32_t idx = (uint32_t) env * (uint32_t) (hp.S[0] + hp.S[1]) + (uint32_t) hub_slot;
+    const uint32_t sidx = (uint32_t) k * (uint32_t) N + (uint32_t) env;
+    const bool cp = hp.constant_charging != 0;
+
+    uint32_t pk_in = 0, w0 = 0u;
+    float a = 0.0f;
+    f32x2 hv = {0.0f, 0.0f};
+    if (unit_ok) pk_in = st.pk[sa.tick & 1u][sidx];
+    if (!RESET && valid) {
+        w0 = sl.wrd[idx];
+        hv = *(CHUB_G(const f32x2)) ((CHUB_G(const float)) sl.hot + 2u * idx);
+        a = sa.actions[(uint32_t) env * (uint32_t) hp.act_dim + (uint32_t) hub_slot];
+    }
+    int tl = ps_tl(w0);
+    bool car = tl > 0;
+    float power = hv.x, t_soc = hv.y;
+    const float t_target = car ? tb.ttab[k][ps_lev(w0)] : 0.0f;
+    // ---- judge_feasibility + assign_on_off_piece (CHS.hpp:1404-1413, 1364-1373)
+    const bool on = car && (a >= kActOnThreshold || must_charge(t_target, t_soc, tl));
+    // ---- car_step along the curves (CHS.hpp:900-905 / 1065-1070); a car that leaves this step is wiped right after it (CHS.hpp:1196-1201)
+    if (on && tl > 1) {
+        float soc_new;
+        car_step_curves<TYPE>(__fadd_rn(t_soc, 1.0f), cp, hp.cc, soc_new, power);
+        t_soc = soc_to_time<TYPE>(soc_new, cp);
+        w0 += kPsStep;
+    }
+    w0 &= ~kPsChg;
+    if (car) {  // remove_car (CHS.hpp:912-923 / 1077-1088)
+        tl -= 1;
+        w0 -= 1u;
+        if (tl <= 0) {
+            car = false;
+            w0 = 0u;
+            power = t_soc = 0.0f;
+        }
+    }
+    const bool charge = on && car;
+    if (charge) w0 |= kPsChg;
+
+    // ---- receive_car (CHS.hpp:1272-1316 / 1583-1627): the unit's draws as PHILOX decodes them (draw_decoded_levels / k_reset_levels)
+    const bool empty = valid && !car;
+    const uint64_t be = __ballot(empty) & unit_mask;
+    const int empties = __popcll(be);
+    const int rank = prefix_count(be);
+    int line = 0, flow = 0, assign = 0;
+    if (unit_ok) {
+        int want;
+        if (RESET) {
+            flow = TYPE == 0 ? (int) (int16_t) (pk_in & 0xFFFFu) : (int) ((pk_in >> 16) & 0xFFFFu);
+            want = flow;
+        } else {
+            want = dk_want(pk_in);
+            flow = dk_flow(pk_in);
+        }
+        assign = want < empties ? want : empties;  // assign_car, CHS.hpp:417-430
+        line = want - assign;
+        line = line < kMaxLine ? line : kMaxLine;
+    }
+    float tgt = t_target;
+    if (empty && rank < assign) {  // add_car (CHS.hpp:864-877 / 1029-1042)
+        float soc;
+        uint32_t lev;
+        int late;
+        if (sa.car_tape) {
+            const uint32_t *tp = sa.car_tape + 2u * idx;
+            soc = __uint_as_float(tp[0]);
+            lev = tp[1] & 0xFFFFu;
+            late = (int) (tp[1] >> 16);
+        } else {
+            PhiloxCtx px{hp.key[0], hp.key[1], CHUB_TICK(hp, sa.tick), (uint32_t) (hp.env_id0 + env)};
+            const U4 o = px.block(SITE_SOC, (uint32_t) hub_slot, 0);
+            soc = soc_from_word(tb.soc_d_icdf, o.v[0]);
+            lev = o.v[1] % 1000u;
+            late = late_from_word(tb.late_thr, o.v[2]);
+        }
+        tgt = tb.ttab[k][lev];
+        t_soc = soc_to_time<TYPE>(soc, cp);
+        power = time_to_power<TYPE>(t_soc, cp);
+        int stay = (int) ceilf(__fsub_rn(tgt, t_soc)) + late;  // calculate_min_charging_time + mk_late_time
+        stay = stay > kMaxStay ? kMaxStay : stay;
+        tl = stay;
+        car = tl > 0;
+        w0 = car ? ps_make(stay, 0u, lev) : 0u;
+        sl.stay8[idx] = (uint8_t) stay;
+        sl.soc0[idx] = soc;
+    }
+
+    // ---- calculate_output (CHS.hpp:1233-1261 / 1544-1572): PHILOX's order-independent integer sums
+    const bool urgent = car && must_charge(tgt, t_soc, tl);
+    const int q = kw_to_fixed(power);
+    int i_min = urgent ? q : 0, i_max = car ? q : 0, i_chg = charge ? q : 0;
+    if (H > 1) { i_min += dppi_xor1(i_min); i_max += dppi_xor1(i_max); i_chg += dppi_xor1(i_chg); }
+    if (H > 2) { i_min += dppi_xor2(i_min); i_max += dppi_xor2(i_max); i_chg += dppi_xor2(i_chg); }
+    if (H > 4) { i_min += dppi_mirror8(i_min); i_max += dppi_mirror8(i_max); i_chg += dppi_mirror8(i_chg); }
+    if (H > 8) { i_min += dppi_mirror16(i_min); i_max += dppi_mirror16(i_max); i_chg += dppi_mirror16(i_chg); }
+    if (H > 16) { i_min += __shfl_xor(i_min, 16); i_max += __shfl_xor(i_max, 16); i_chg += __shfl_xor(i_chg, 16); }
+    if (H > 32) { i_min += __shfl_xor(i_min, 32); i_max += __shfl_xor(i_max, 32); i_chg += __shfl_xor(i_chg, 32); }
+    const int cars = __popcll(__ballot(car) & unit_mask);
+
+    if (valid) {
+        sl.wrd[idx] = w0;
+        const f32x2 out = {car ? power : 0.0f, car ? t_soc : 0.0f};
+        *(CHUB_G(f32x2)) ((CHUB_G(float)) sl.hot + 2u * idx) = out;
+    }
+    if (unit_ok && slot == 0) rec_store(st.rec, sidx, fixed_to_kw(i_min), fixed_to_kw(i_chg), fixed_to_kw(i_max), pkd_make(line, flow, cars));
+}
+
+template <bool RESET, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_slot_curves(const DevCtx *__restrict__ ctx, StepArgs sa, int64_t nb0) {
+    const HubParams &hp = ctx->hp;
+    const int64_t bid = blockIdx.x;
+    const int k = (bid >= nb0) ? 1 : 0;  // one station per workgroup: the type below is uniform over it
+    const int64_t bl = k ? bid - nb0 : bid;
+    if (hp.type[k] == 0) slot_body_curves<0, RESET, BLOCK>(hp, sa, ctx->sl, ctx->st, ctx->tb, k, bl);
+    else slot_body_curves<1, RESET, BLOCK>(hp, sa, ctx->sl, ctx->st, ctx->tb, k, bl);
+}
+
 // ---------------------------------------------------------------------------------------- COMPAT, the split step
 // One kernel per station with the unit's first lane walking the env's streams keeps 2 of a wave's 64 lanes busy through the longest
 // part of the step (every polar normal of the reference's std::normal_distribution costs a lane about a microsecond): 250 of the
@@ -4337,7 +4485,14 @@ __global__ void k_replay_soc(const DevCtx *__restrict__ ctx, float *out) {
     float soc = 0.0f;
     int n = 0;
     bool car;
-    if (hp.rng_mode == MODE_PHILOX) {  // arrival SoC of the slot's class, car_steps from the state word
+    if (hp.rng_mode == MODE_PHILOX && hp.soc_curves) {  // PHILOX_CURVES: the arrival SoC of the slot's cold array, car_steps from the state word
+        const uint32_t w0 = ctx->sl.wrd[idx];
+        car = ps_tl(w0) != 0;
+        if (car) {
+            soc = ctx->sl.soc0[idx];
+            n = (int) ps_n(w0);
+        }
+    } else if (hp.rng_mode == MODE_PHILOX) {  // arrival SoC of the slot's class, car_steps from the state word
         const uint32_t w0 = ctx->sl.hot[idx];
         car = ps_tl(w0) != 0;
         if (car) {
@@ -4514,6 +4669,15 @@ void launch_slot(bool reset, const HubParams &hp, const DevCtx *ctx, const StepA
                  const PackedPtrs &pp, hipEvent_t ev0, hipEvent_t ev1) {
     if (hp.rng_mode == MODE_PHILOX && !reset && (sa.fresh || sa.pk_tape))
         hipLaunchKernelGGL(k_draw_levels, dim3((unsigned) ((2 * ((int64_t) sa.env_hi - sa.env_lo + 1) + 255) / 256)), dim3(256), 0, stream, ctx, sa);
+    if (hp.rng_mode == MODE_PHILOX && hp.soc_curves) {  // PHILOX_CURVES (chub_create refuses stations of more than 64 piles and the scalar-load control)
+        if (reset && !sa.car_tape)  // (tape mode: the caller's occupancy draws are in pk already)
+            hipLaunchKernelGGL(k_reset_levels, dim3((unsigned) ((8 * ((int64_t) sa.env_hi - sa.env_lo + 1) + 255) / 256)), dim3(256), 0, stream, ctx, sa);
+        constexpr int BLOCK = 256;
+        const int64_t nb0 = blocks_for(hp.n_envs, hp.H[0], BLOCK), nb1 = blocks_for(hp.n_envs, hp.H[1], BLOCK);
+        if (reset) CHUB_LAUNCH((k_slot_curves<true, BLOCK>), dim3((unsigned) (nb0 + nb1)), dim3(BLOCK), stream, ev0, ev1, ctx, sa, nb0);
+        else CHUB_LAUNCH((k_slot_curves<false, BLOCK>), dim3((unsigned) (nb0 + nb1)), dim3(BLOCK), stream, ev0, ev1, ctx, sa, nb0);
+        return;
+    }
     if (hp.rng_mode == MODE_PHILOX) {
         if (hp.packed && !sa.load_mode) {
             if (reset && !sa.car_tape)  // (tape mode: the caller's occupancy draws are in pk already)

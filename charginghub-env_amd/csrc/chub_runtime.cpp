@@ -129,6 +129,7 @@ struct chub_env {
     double *d_telem = nullptr;
     int tape_classes;   // PHILOX tape mode: caller-registered arrival-SoC classes so far
     bool tape_stale = false;  // chub_tape_clear_soc since the last reset: the slots may hold cars of classes that are gone
+    int public_mode = 0;     // the rng_mode the handle was created with: CHUB_RNG_PHILOX_CURVES is hp.rng_mode = PHILOX + hp.soc_curves
     bool tape_only = false;  // ... and once there are any, the handle's class rows are the caller's: only tape resets / steps may admit cars
     uint32_t h_late8[8];
     double h_sin96[96];
@@ -403,7 +404,13 @@ int chub_create_ex(const chub_config *cfg, const char *data_dir, int64_t n_envs,
     if (n_envs <= 0) return fail(CHUB_ERR_ARG, "n_envs must be positive");
     if (n_envs * (int64_t) (cfg->station_list[0] + cfg->station_list[1] + 2) >= (int64_t) 1 << 31)
         return fail(CHUB_ERR_UNSUPPORTED, "n_envs * (piles + 2) must stay below 2^31 per handle (32-bit slot indices)");
-    if (rng_mode != CHUB_RNG_COMPAT && rng_mode != CHUB_RNG_PHILOX) return fail(CHUB_ERR_ARG, "unknown rng_mode");
+    if (rng_mode != CHUB_RNG_COMPAT && rng_mode != CHUB_RNG_PHILOX && rng_mode != CHUB_RNG_PHILOX_CURVES) return fail(CHUB_ERR_ARG, "unknown rng_mode");
+    // PHILOX_CURVES: PHILOX's draws and tail, the slots on k_slot_curves (chub_kernels.hip); a unit is one wave's lanes there
+    const bool soc_curves = rng_mode == CHUB_RNG_PHILOX_CURVES;
+    if (soc_curves && (cfg->station_list[0] > 64 || cfg->station_list[1] > 64))
+        return fail(CHUB_ERR_UNSUPPORTED, "rng_mode PHILOX_CURVES covers stations of at most 64 piles (its slot kernel keeps a station's unit inside one wave)");
+    const int public_mode = rng_mode;
+    if (soc_curves) rng_mode = CHUB_RNG_PHILOX;
     for (int k = 0; k < 2; k++) {
         if (cfg->station_list[k] < 0) return fail(CHUB_ERR_ARG, "station_list entries must be >= 0");
         // the production (PHILOX) kernel lays whole envs over a workgroup's 512 (2048) virtual lanes; the wave-local kernels keep a unit
@@ -421,6 +428,7 @@ int chub_create_ex(const chub_config *cfg, const char *data_dir, int64_t n_envs,
 
     chub_env *e = new chub_env();
     e->cfg = *cfg;
+    e->public_mode = public_mode;
     e->device = device;
     e->t = 0;
     e->price_count = 0;
@@ -532,6 +540,7 @@ int chub_create_ex(const chub_config *cfg, const char *data_dir, int64_t n_envs,
     hp.act_dim = hp.S[0] + hp.S[1] + 2;
     hp.constant_charging = cfg->constant_charging ? 1 : 0;
     hp.rng_mode = rng_mode;
+    hp.soc_curves = soc_curves ? 1 : 0;
     hp.telemetry = 0;
     hp.qcap = qcap;
     hp.hv_w = 1 + hv_max_arrive;
@@ -741,7 +750,7 @@ int chub_create_ex(const chub_config *cfg, const char *data_dir, int64_t n_envs,
             if ((((uint32_t) l * ((1u << 20) / (uint32_t) St + 1u)) >> 20) != (uint32_t) (l / St)) magic_ok = false;
         hp.packed = (rng_mode == CHUB_RNG_PHILOX && St >= 1 && St <= pb && magic_ok &&
                      (uint64_t) n_envs * (uint64_t) (St + 2) * 16u < ((uint64_t) 1 << 32) &&  // 32-bit byte offsets
-                     opt.slot_kernel != 1) ? 1 : 0;
+                     opt.slot_kernel != 1 && !soc_curves) ? 1 : 0;  // (PHILOX_CURVES: k_slot_curves whatever the options say)
     }
     {   // the whole step as one launch: where the two kernels are launch- and latency-bound and every workgroup finds room at once
         const int64_t nb = (n_envs + hp.epb - 1) / hp.epb;
@@ -815,11 +824,18 @@ int chub_create_ex(const chub_config *cfg, const char *data_dir, int64_t n_envs,
 #define ALLOC(ptr, count)                                        \
     if ((rc = dev_alloc(e, &(ptr), (count)))) return bail(rc)
     e->sl.stay8 = nullptr;
+    e->sl.wrd = nullptr;
+    e->sl.soc0 = nullptr;
     e->sl.var[0] = e->sl.var[1] = nullptr;
     e->st.empt = nullptr;
     e->st.fa[0] = e->st.fa[1] = nullptr;
     e->st.empt2[0] = e->st.empt2[1] = e->st.shrt[0] = e->st.shrt[1] = nullptr;
-    if (rng_mode == CHUB_RNG_PHILOX) {
+    if (soc_curves) {
+        ALLOC(e->sl.hot, 2 * NS);  // power, t_soc
+        ALLOC(e->sl.wrd, NS);      // the state word
+        ALLOC(e->sl.soc0, NS);     // arrival SoC (cold)
+        ALLOC(e->sl.stay8, NS);
+    } else if (rng_mode == CHUB_RNG_PHILOX) {
         ALLOC(e->sl.hot, NS);  // 4-byte slot state
         ALLOC(e->sl.stay8, NS);
     } else {
@@ -1393,6 +1409,8 @@ static int step_masked(chub_env *e, const uint8_t *mask, const float *d_actions,
         return fail(CHUB_ERR_ARG, "a handle with registered tape classes steps through chub_step_tape / chub_step_tape_env only (its class "
                                   "rows hold the caller's arrival SoCs: cars admitted by this build's own draws would be given them)");
     if (e->hp.rng_mode == CHUB_RNG_COMPAT && !d_exo_z) return fail(CHUB_ERR_ARG, "COMPAT mode needs exo_z");
+    if (load_mode && e->hp.soc_curves)
+        return fail(CHUB_ERR_UNSUPPORTED, "the scalar-load control (chub_step_load*) is not supported in rng_mode PHILOX_CURVES");
     HIP_TRY(hipSetDevice(e->device));
     (void) hipGetLastError();  // a stale error of an earlier, unrelated call must not be reported as this step's
     hipStream_t s = (hipStream_t) stream;
@@ -1944,6 +1962,8 @@ int chub_stream_sync(int device, void *stream) {
 int chub_tape_register_soc(chub_env *e, const float *soc, int32_t count, uint32_t *class_ids) {
     if (!e || !soc || !class_ids || count < 0) return fail(CHUB_ERR_ARG, "bad argument");
     if (e->hp.rng_mode != CHUB_RNG_PHILOX) return fail(CHUB_ERR_ARG, "tape mode needs a PHILOX handle");
+    if (e->hp.soc_curves)
+        return fail(CHUB_ERR_UNSUPPORTED, "rng_mode PHILOX_CURVES has no classes: its car tape carries each arrival SoC itself (f32 bits in .x)");
     if (e->tape_classes + count > kSocLevels) return fail(CHUB_ERR_UNSUPPORTED, "too many tape classes (chub_tape_clear_soc starts over)");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
@@ -1997,6 +2017,7 @@ int chub_tape_clear_soc(chub_env *e) {
 int chub_set_slots(chub_env *e, const int32_t *rows) {
     if (!e || !rows) return fail(CHUB_ERR_ARG, "null argument");
     if (e->hp.rng_mode != CHUB_RNG_PHILOX) return fail(CHUB_ERR_ARG, "chub_set_slots needs a PHILOX handle");
+    if (e->hp.soc_curves) return fail(CHUB_ERR_UNSUPPORTED, "chub_set_slots writes class-table slot states: not supported in rng_mode PHILOX_CURVES");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
     const HubParams &hp = e->hp;
@@ -2055,7 +2076,7 @@ int chub_step_tape(chub_env *e, const float *actions, const uint64_t *pk_tape, c
 int chub_step_tape_env(chub_env *e, const float *actions, const uint64_t *pk_tape, const uint32_t *car_tape, const double *exo_z,
                        const uint32_t *hv_tape, int32_t hv_w, float *obs, float *reward, uint8_t *done) {
     if (!e || !actions || !pk_tape || !car_tape || !obs || !reward || !done) return fail(CHUB_ERR_ARG, "null argument");
-    if (e->hp.rng_mode != CHUB_RNG_PHILOX || !e->hp.packed)
+    if (e->hp.rng_mode != CHUB_RNG_PHILOX || !(e->hp.packed || e->hp.soc_curves))
         return fail(CHUB_ERR_ARG, "tape mode drives the packed PHILOX slot kernel: the hub shape must be one it covers");
     if ((exo_z != nullptr) != (hv_tape != nullptr) || (hv_tape && hv_w < 1)) return fail(CHUB_ERR_ARG, "the tail's tape is exo_z [N][3] AND hv_tape [N][hv_w >= 1]");
     if (e->tape_stale) return fail(CHUB_ERR_ARG, "chub_tape_clear_soc was called: reset (chub_reset_tape) before the next tape step");
@@ -2132,7 +2153,7 @@ int chub_reset_tape_env(chub_env *e, const uint32_t *occ_tape, const uint32_t *c
         for (size_t i = 0; i < (size_t) e->hp.n_envs; i++)
             if (exo_days[2 * i] < 0 || exo_days[2 * i] >= 100 || exo_days[2 * i + 1] < 0 || exo_days[2 * i + 1] >= 150)
                 return fail(CHUB_ERR_ARG, "exo_days out of range");
-    if (e->hp.rng_mode != CHUB_RNG_PHILOX || !e->hp.packed)
+    if (e->hp.rng_mode != CHUB_RNG_PHILOX || !(e->hp.packed || e->hp.soc_curves))
         return fail(CHUB_ERR_ARG, "tape mode drives the packed PHILOX slot kernel: the hub shape must be one it covers");
     if (e->capturing) return fail(CHUB_ERR_ARG, "tape mode cannot be captured");
     HIP_TRY(hipSetDevice(e->device));
@@ -2196,8 +2217,12 @@ int chub_get_slots(chub_env *e, float *out) {
         if (rc) return rc;
     }
     std::vector<uint8_t> stay8;
-    if ((rc = fetch(hot, (const uint32_t *) e->sl.hot, (philox ? 1 : 4) * NS))) return rc;
+    std::vector<uint32_t> wrd;
+    std::vector<float> arr0;
+    const bool curves = hp.soc_curves != 0;
+    if ((rc = fetch(hot, (const uint32_t *) e->sl.hot, (curves ? 2 : philox ? 1 : 4) * NS))) return rc;
     if (philox && (rc = fetch(stay8, (const uint8_t *) e->sl.stay8, NS))) return rc;
+    if (curves && ((rc = fetch(wrd, (const uint32_t *) e->sl.wrd, NS)) || (rc = fetch(arr0, (const float *) e->sl.soc0, NS)))) return rc;
     for (size_t env = 0; env < N; env++) {
         float *o = out + env * 9 * S;
         for (int k = 0; k < 2; k++) {
@@ -2207,7 +2232,16 @@ int chub_get_slots(chub_env *e, float *out) {
                 float power = 0, t_target = 0, t_soc = 0, arrive = 0;
                 int left, stay, lev;
                 bool chg;
-                if (philox) {  // 4-byte state: everything else comes from the class row and the table of target times (see chub_kernels.hip)
+                if (curves) {  // PHILOX_CURVES: power and t_soc in the hot record, the state word beside it, the arrival SoC in its cold array
+                    const uint32_t w0 = wrd[idx];
+                    left = (int) (w0 & 31u); chg = (w0 & 32u) != 0; stay = (int) stay8[idx]; lev = (int) (w0 >> 22);
+                    if (left > 0) {
+                        memcpy(&power, &hot[2 * idx + 0], 4);
+                        memcpy(&t_soc, &hot[2 * idx + 1], 4);
+                        arrive = arr0[idx];
+                        t_target = ttab[k][(size_t) lev];
+                    }
+                } else if (philox) {  // 4-byte state: everything else comes from the class row and the table of target times (see chub_kernels.hip)
                     const uint32_t w0 = hot[idx];
                     left = (int) (w0 & 31u); chg = (w0 & 32u) != 0; stay = (int) stay8[idx]; lev = (int) (w0 >> 22);
                     if (left > 0) {
@@ -2529,7 +2563,7 @@ int chub_get_state(chub_env *e, void *buf, int64_t size) {
     h.n_envs = e->hp.n_envs;
     h.env_id0 = e->hp.env_id0;
     h.cfg = e->cfg;
-    h.rng_mode = e->hp.rng_mode;
+    h.rng_mode = e->public_mode;
     h.t = e->t;
     h.price_count = e->price_count;
     h.tick = e->tick;
@@ -2561,7 +2595,7 @@ int chub_set_state(chub_env *e, const void *buf, int64_t size) {
     if (size < (int64_t) sizeof h) return fail(CHUB_ERR_ARG, "snapshot truncated");
     memcpy(&h, buf, sizeof h);
     if (h.magic != kSnapMagic) return fail(CHUB_ERR_ARG, "not a chub snapshot");
-    if (h.n_envs != e->hp.n_envs || h.env_id0 != e->hp.env_id0 || h.rng_mode != e->hp.rng_mode ||
+    if (h.n_envs != e->hp.n_envs || h.env_id0 != e->hp.env_id0 || h.rng_mode != e->public_mode ||
         memcmp(&h.cfg, &e->cfg, sizeof h.cfg) != 0 || h.arena_used != e->arena_used || size < need)
         return fail(CHUB_ERR_ARG, "snapshot was taken from a handle with a different configuration");
     HIP_TRY(hipSetDevice(e->device));

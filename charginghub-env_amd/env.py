@@ -19,6 +19,11 @@ for this env -- glibc ``rand()`` + ``std::minstd_rand0`` on the device, while th
 the host exactly where the reference makes them: ``random.randint`` for the PV / wind day (REN:25,51-53) and
 ``np.random.normal()`` for the three OU processes (REN:73-74).  So ``random.seed(s); np.random.seed(s)``
 before construction means what it means for the reference.  ``rng='philox'`` uses the device generator.
+``rng='philox_curves'`` uses the same device generator with the reference's continuous EV arrival SoC and the charge curves
+evaluated on the device (a PHILOX arrival SoC is one of 2048 classes, its car_step a table read).
+
+Which to pick: ``'compat'`` to reproduce the reference seed for seed; ``'philox_curves'`` for the reference's laws (continuous
+arrival SoC, curves) without the serial streams; ``'philox'`` for the highest rate, with the arrival SoC quantised to 2048 classes.
 """
 import ctypes as C
 import os
@@ -168,6 +173,8 @@ class EvcsspManagerEnv_v6(object):
         the state of the reference's two process-global C++ streams in front of the constructor (default: what
         Change_Use_Seed(seed_rand) leaves, CHS.hpp:25-41)."""
         assert len(station_list) == len(station_type_list) == 2  # MGR:37
+        if rng not in _lib.RNG_MODES:
+            raise ValueError("rng must be 'compat', 'philox' or 'philox_curves'")
         self.fcev_permeate = fcev_permeate
         self.init_soc = init_soc
         self.price_fluctuate = price_fluctuate

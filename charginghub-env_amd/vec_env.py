@@ -58,9 +58,9 @@ class VecChargingHub(object):
         self._lib = load_library()
         self.cfg = make_config(station_list, station_type_list, **kwargs)
         self.n_envs = int(n_envs)
-        self.rng_mode = _lib.RNG_PHILOX if rng == "philox" else _lib.RNG_COMPAT
-        if rng not in ("philox", "compat"):
-            raise ValueError("rng must be 'philox' or 'compat'")
+        if rng not in _lib.RNG_MODES:
+            raise ValueError("rng must be 'philox', 'compat' or 'philox_curves'")
+        self.rng_mode = _lib.RNG_MODES[rng]
         h = C.c_void_p()
         opt = ChubOptions()
         opt.slot_kernel = _lib.SLOT_KERNELS[slot_kernel]

@@ -43,8 +43,25 @@ enum { CHUB_FAST = 0, CHUB_SLOW = 1 };
  * rand() TYPE_3 + std::minstd_rand0, CHS.hpp:23-45) in the reference's consumption order; exogenous
  * normals / day indices come from the caller (the reference draws them from numpy / random, REN:25,74).
  * PHILOX is the production mode: counter-based Philox4x32-10, key = seed, counter = (block,
- * site<<16|index, tick, global env id); results do not depend on how envs are sharded over GPUs. */
-enum { CHUB_RNG_COMPAT = 0, CHUB_RNG_PHILOX = 1 };
+ * site<<16|index, tick, global env id); results do not depend on how envs are sharded over GPUs.  Its EV
+ * arrival SoC takes one of 2048 equiprobable classes and car_step is read from per-class tables.
+ * PHILOX_CURVES: PHILOX's draws, keyed exactly as in PHILOX, with the reference's CONTINUOUS arrival SoC
+ * (CHS.hpp:803-814) and car_step evaluated on the device along the reference's curves (CHS.hpp:467-726, the
+ * arithmetic COMPAT is pinned with); station sums as in PHILOX (integers of 2^-19 kW, independent of order).
+ *   The draw contract: a car admitted into hub slot j of global env g at the launch's tick uses the SAME Philox
+ *   block as PHILOX, block(SITE_SOC = 5, j, 0) -- counter (0, 5 << 16 | j, tick, g), key = seed: word 1 % 1000 is
+ *   the target level and word 2 the extra stay, as in PHILOX; word 0 gives the arrival SoC by linear
+ *   interpolation of the 4097-node inverse CDF of clip(N(7,3),1,10) (12 bits pick the cell, 20 interpolate;
+ *   soc = 75 - 5 d), where PHILOX takes the class word 0 >> 21.  So on one seed the cars, targets and extra
+ *   stays at reset are those of PHILOX, each car's SoC lies inside its PHILOX class's cell of the table (nodes
+ *   2c .. 2c + 2), and trajectories part after the reset because a stay depends on the SoC.  Everything else
+ *   (arrival counts, renege / balk, evs_reset's occupancy, the forecourt, OU) draws PHILOX's counters.
+ *   Not in this mode (CHUB_ERR_UNSUPPORTED with a message): stations of more than 64 piles, the scalar-load
+ *   control (chub_step_load*), chub_tape_register_soc (the car tape's .x carries the f32 bits of each
+ *   recorded arrival SoC instead of a class id), chub_set_slots.  The chub_options that pick the packed /
+ *   one-launch / span kernels are accepted and have no effect: chub_uses_packed_kernel returns 0 and
+ *   chub_run_steps issues its steps one by one.  Snapshots of one mode are refused by a handle of another. */
+enum { CHUB_RNG_COMPAT = 0, CHUB_RNG_PHILOX = 1, CHUB_RNG_PHILOX_CURVES = 2 };
 
 /* Constructor kwargs of EvcsspManagerEnv_v6 (MGR:25-27), same names and meaning.  use_lagrange is
  * ignored by the reference (MGR:126) and has no field.  seed_rand maps to the seeds given at create. */
