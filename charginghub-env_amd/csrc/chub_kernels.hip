@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "chub_device.h"
+#include "chub_plan.h"
 
 namespace chub {
 
@@ -250,7 +251,7 @@ constexpr int MODE_COMPAT = 0, MODE_PHILOX = 1;
 // array (vector-TLB misses 954 -> 0 per launch); nothing stays in L2 across kernel boundaries (profiles/round5_work_order_pmc.txt).  Measured (round 5, A/B inside one call,
 // bit-identical; tiles, tail workgroups and level workgroups all in this order): cache-resident sizes gain 4-6 % of the step (C4 27.1 ->
 // 25.95 us, 32 768 envs 18.3 -> 17.1, 8192 envs 10.8 -> 10.3, 131 072 envs 44.8 -> 43.8); the HBM-resident C5 LOSES 1 % (contiguous eighths
-// concentrate each XCD's streams on fewer memory channels at a time), so handles of more than kXcdOrderSlots slots keep the dispatcher's
+// concentrate each XCD's streams on fewer memory channels at a time), so handles beyond cache-resident sizes (chub_plan.h) keep the dispatcher's
 // order (HubParams::xcd -> PackedArgs::xcd / TailArgs::xcd).
 __device__ __forceinline__ uint32_t xcd_order(uint32_t b, uint32_t nb, uint32_t on) {
     if (!on) return b;
@@ -2916,9 +2917,6 @@ __global__ __launch_bounds__(256) void k_compat_walk(const DevCtx *__restrict__ 
     compat_walk_block<RESET>(ctx, sa, blockIdx.x, s_ring, s_stage);
 }
 
-#ifndef CHUB_SPLIT2
-#define CHUB_SPLIT2 1  // the split step's slot pass with two slots per lane (slot_body_split2); 0: slot_body_compat<.., SPLIT> for every step
-#endif
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK, 7) void k_slot_split2(const DevCtx *__restrict__ ctx, StepArgs sa, int64_t nb0) {
     const HubParams &hp = ctx->hp;
@@ -2938,11 +2936,6 @@ __global__ __launch_bounds__(BLOCK, 7) void k_slot_split2(const DevCtx *__restri
 // and the streams continue from step i's shadow, which the slot pass beside it is committing (StepArgs::walk_far).  Workgroups
 // [0, nwalk): 64 (or 32) walks each, on one wave (8 KB of rings + 7 KB of staging in LDS: a larger area would cost the slot workgroups their occupancy),
 // at raised priority; the others: slot_body_split2.
-// Envs per walk workgroup of k_slot_walk2 (one wave walks them): 64, or -- batches of at most kWalk2HalfMaxEnvs envs -- 32: twice the walking
-// waves, each with half the cars to evaluate (all 64 lanes still evaluate).  A small batch's launch lasts as long as its longest walk
-// (4096 envs: 27.0 -> 22.3 us, 16 384: 31.1 -> 26.8, 32 768: 37.7 -> 33.2, 40 000: 40.4 -> 39.7); a large one is bound by instruction issue,
-// where the second set of serial phases costs more than the shorter chain gives (65 536 envs: 54.6 -> 59.1 us).
-constexpr int64_t kWalk2HalfMaxEnvs = 40000;
 #ifndef CHUB_WALK2_OCC
 #define CHUB_WALK2_OCC 7  // workgroups per CU of k_slot_walk2 (sets its register budget: 72 VGPRs at 7, 80 at 6, 96 at 5)
 #endif
@@ -4596,135 +4589,144 @@ static inline int64_t blocks_for_split2(int64_t n_envs, int U, int block) {
     return (n_envs + upb - 1) / upb;
 }
 
+// The launchers launch the forms chub_plan.h names (LaunchPlan per handle, CallPlan per call) and decide nothing themselves.
 // ev0 / ev1 (may be null): kernel start / stop timestamps of the dispatch itself (hipExtLaunchKernelGGL), what
 // chub_profile_* reports -- plain hipEventRecord pairs around a launch also count the gap in front of it
-template <bool RESET, int MODE>
-static void launch_slot_t(const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, hipEvent_t ev0,
-                          hipEvent_t ev1) {
-    constexpr int BLOCK = 256;
-    // (COMPAT units take exactly S lanes, the PHILOX wave-local kernel's the next power of two: its sums are DPP butterflies)
-    const int64_t nb0 = blocks_for(hp.n_envs, MODE == MODE_COMPAT ? hp.U[0] : hp.H[0], BLOCK), nb1 = blocks_for(hp.n_envs, MODE == MODE_COMPAT ? hp.U[1] : hp.H[1], BLOCK);
-    const bool big = hp.S[0] > 64 || hp.S[1] > 64;  // a unit of more than 64 piles is a workgroup of its own (k_slot_unit)
-    if (MODE == MODE_PHILOX && RESET) hipLaunchKernelGGL(k_reset_levels, dim3((unsigned) ((8 * ((int64_t) sa.env_hi - sa.env_lo + 1) + 255) / 256)), dim3(256), 0, stream, ctx, sa);
-    if (MODE == MODE_PHILOX && !big) {
-        CHUB_LAUNCH((k_slot<RESET, MODE, BLOCK>), dim3((unsigned) (nb0 + nb1)), dim3(BLOCK), stream, ev0, ev1, ctx, sa, nb0);
-    } else if (MODE == MODE_COMPAT && !big && hp.compat_split) {
-        // the split step: empties -> the stream walks, one env per lane -> the slots of both stations in one launch
-        const bool count_first = !RESET && sa.empt_fresh && !sa.walked;
-        if (count_first) {  // of every unit, whatever envs the call names: the counts are then good for whoever is stepped next
-            StepArgs all = sa;
-            all.env_mask = nullptr;
-            CHUB_LAUNCH((k_compat_empties<BLOCK>), dim3((unsigned) (nb0 + nb1)), dim3(BLOCK), stream, ev0, (hipEvent_t) nullptr, ctx, all, nb0);
-        }
-        const bool walk_now = RESET || !sa.walked;  // (otherwise the walk ran beside the previous step's tails, k_env_walk)
-        if (walk_now)
-            CHUB_LAUNCH((k_compat_walk<RESET>), dim3((unsigned) ((hp.n_envs + 255) / 256)), dim3(256), stream, count_first ? (hipEvent_t) nullptr : ev0, (hipEvent_t) nullptr, ctx, sa);
-        if (CHUB_SPLIT2 && !RESET && !sa.load_mode && hp.U[0] >= 8 && hp.U[1] >= 8) {  // two slots per lane (stations of 8 to 64 piles: at most 8 units per virtual wave)
-            const int64_t sb0 = blocks_for_split2(hp.n_envs, hp.U[0], BLOCK), sb1 = blocks_for_split2(hp.n_envs, hp.U[1], BLOCK);
-            CHUB_LAUNCH((k_slot_split2<BLOCK>), dim3((unsigned) (sb0 + sb1)), dim3(BLOCK), stream, walk_now ? (hipEvent_t) nullptr : ev0, ev1, ctx, sa, sb0);
-        } else
-            CHUB_LAUNCH((k_slot_split<RESET, BLOCK>), dim3((unsigned) (nb0 + nb1)), dim3(BLOCK), stream, walk_now ? (hipEvent_t) nullptr : ev0, ev1, ctx, sa, nb0);
-    } else {
-        for (int k = 0; k < 2; k++) {  // the reference streams are consumed station 0 first, then station 1
-            StepArgs s2 = sa;
-            s2.station_filter = k;
-            hipEvent_t e0 = k == 0 ? ev0 : nullptr, e1 = k == 1 ? ev1 : nullptr;
-            if (hp.S[k] > 256) CHUB_LAUNCH((k_slot_unit_any<RESET, MODE>), dim3((unsigned) hp.n_envs), dim3(256), stream, e0, e1, ctx, s2, k);
-            else if (hp.S[k] > 64) CHUB_LAUNCH((k_slot_unit<RESET, MODE>), dim3((unsigned) hp.n_envs), dim3(256), stream, e0, e1, ctx, s2, k);
-            else CHUB_LAUNCH((k_slot<RESET, MODE, BLOCK>), dim3((unsigned) (k ? nb1 : nb0)), dim3(BLOCK), stream, e0, e1, ctx, s2, nb0);
-        }
-    }
-}
-
-// COMPAT split step, lock-step steps of every env of a handle whose stations take the two-slots-per-lane pass: the slot pass of step i
-// (sa) beside the stream walks of step i + 1 (sw: walk_far), k_slot_walk2.  Step i's own walk first where it has not run (the first step
-// after a reset or anything else that voided it: near, from the committed streams), the empty-slot counts in front of it where they are
-// not the previous pass's.
-bool slot_walk2_covers(const HubParams &hp) { return CHUB_SPLIT2 && hp.compat_split && hp.S[0] <= 64 && hp.S[1] <= 64 && hp.U[0] >= 8 && hp.U[1] >= 8; }
-void launch_slot_walk2(const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, const StepArgs &sw, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
-    constexpr int BLOCK = 256;
-    const int64_t nb0 = blocks_for(hp.n_envs, hp.U[0], BLOCK), nb1 = blocks_for(hp.n_envs, hp.U[1], BLOCK);
-    const bool count_first = sa.empt_fresh && !sa.walked;
-    if (count_first) {
-        StepArgs all = sa;
-        all.env_mask = nullptr;
-        CHUB_LAUNCH((k_compat_empties<BLOCK>), dim3((unsigned) (nb0 + nb1)), dim3(BLOCK), stream, ev0, (hipEvent_t) nullptr, ctx, all, nb0);
-    }
-    const bool walk_now = !sa.walked;
-    if (walk_now)
-        CHUB_LAUNCH((k_compat_walk<false>), dim3((unsigned) ((hp.n_envs + 255) / 256)), dim3(256), stream, count_first ? (hipEvent_t) nullptr : ev0, (hipEvent_t) nullptr, ctx, sa);
-    const int64_t sb0 = blocks_for_split2(hp.n_envs, hp.U[0], BLOCK), sb1 = blocks_for_split2(hp.n_envs, hp.U[1], BLOCK);
-    if (hp.n_envs <= kWalk2HalfMaxEnvs) {
-        const int nwalk = (int) ((hp.n_envs + 31) / 32);
-        CHUB_LAUNCH((k_slot_walk2<BLOCK, 32>), dim3((unsigned) (nwalk + sb0 + sb1)), dim3(BLOCK), stream, walk_now ? (hipEvent_t) nullptr : ev0, ev1, ctx, sa, sw, sb0, nwalk);
-    } else {
-        const int nwalk = (int) ((hp.n_envs + 63) / 64);
-        CHUB_LAUNCH((k_slot_walk2<BLOCK, 64>), dim3((unsigned) (nwalk + sb0 + sb1)), dim3(BLOCK), stream, walk_now ? (hipEvent_t) nullptr : ev0, ev1, ctx, sa, sw, sb0, nwalk);
+static void launch_levels(LevelsForm lv, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream) {
+    const int64_t n = (int64_t) sa.env_hi - sa.env_lo + 1;
+    switch (lv) {
+    case LEVELS_NONE: break;
+    case LEVELS_DRAW: hipLaunchKernelGGL(k_draw_levels, dim3((unsigned) ((2 * n + 255) / 256)), dim3(256), 0, stream, ctx, sa); break;
+    case LEVELS_RESET: hipLaunchKernelGGL(k_reset_levels, dim3((unsigned) ((8 * n + 255) / 256)), dim3(256), 0, stream, ctx, sa); break;
     }
 }
 
 static PackedArgs make_packed_args(const HubParams &hp, const StepArgs &sa, const PackedPtrs &pp);
 
-void launch_slot(bool reset, const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream,
+template <bool TAPE, bool RESET, bool MASKED, bool BITS>
+static void launch_packed(const HubParams &hp, const LaunchPlan &lp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, const PackedPtrs &pp,
+                          hipEvent_t ev0, hipEvent_t ev1) {
+    const PackedArgs pa = make_packed_args(hp, sa, pp);
+    // every workgroup of the batch, or (a call on a subset of the envs) those of the range of envs it names
+    const uint32_t nb = MASKED ? (uint32_t) (sa.env_hi / hp.epb - sa.env_lo / hp.epb + 1) : (uint32_t) ((hp.n_envs + hp.epb - 1) / hp.epb);
+    switch ((PackedForm) lp.packed) {
+    case PACKED_SMALL:
+        CHUB_LAUNCH((k_slot_packed<kPackedBlock, kSlotsPerLane, TAPE, RESET, false, MASKED, BITS>), dim3(nb), dim3(kPackedBlock), stream, ev0, ev1, ctx, sa, pa);
+        break;
+    case PACKED_SMALL_WIDE:
+        CHUB_LAUNCH((k_slot_packed<kPackedBlock, kSlotsPerLane, TAPE, RESET, true, MASKED, BITS>), dim3(nb), dim3(kPackedBlock), stream, ev0, ev1, ctx, sa, pa);
+        break;
+    case PACKED_LARGE:
+        CHUB_LAUNCH((k_slot_packed<kBigBlock, kBigSlotsPerLane, TAPE, RESET, false, MASKED, BITS>), dim3(nb), dim3(kBigBlock), stream, ev0, ev1, ctx, sa, pa);
+        break;
+    case PACKED_LARGE_WIDE:
+        CHUB_LAUNCH((k_slot_packed<kBigBlock, kBigSlotsPerLane, TAPE, RESET, true, MASKED, BITS>), dim3(nb), dim3(kBigBlock), stream, ev0, ev1, ctx, sa, pa);
+        break;
+    case PACKED_NONE: break;
+    }
+}
+
+// one launch per station: the reference streams are consumed station 0 first, then station 1
+template <bool RESET, int MODE>
+static void launch_stations(const HubParams &hp, const LaunchPlan &lp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, hipEvent_t ev0,
+                            hipEvent_t ev1) {
+    constexpr int BLOCK = 256;
+    // (COMPAT units take exactly S lanes, the PHILOX wave-local kernel's the next power of two: its sums are DPP butterflies)
+    const int64_t nb0 = blocks_for(hp.n_envs, MODE == MODE_COMPAT ? hp.U[0] : hp.H[0], BLOCK), nb1 = blocks_for(hp.n_envs, MODE == MODE_COMPAT ? hp.U[1] : hp.H[1], BLOCK);
+    for (int k = 0; k < 2; k++) {
+        StepArgs s2 = sa;
+        s2.station_filter = k;
+        hipEvent_t e0 = k == 0 ? ev0 : nullptr, e1 = k == 1 ? ev1 : nullptr;
+        switch ((StationKernel) lp.station[k]) {
+        case STATION_UNIT_ANY: CHUB_LAUNCH((k_slot_unit_any<RESET, MODE>), dim3((unsigned) hp.n_envs), dim3(256), stream, e0, e1, ctx, s2, k); break;
+        case STATION_UNIT: CHUB_LAUNCH((k_slot_unit<RESET, MODE>), dim3((unsigned) hp.n_envs), dim3(256), stream, e0, e1, ctx, s2, k); break;
+        case STATION_WAVE:
+        case STATION_CURVES: CHUB_LAUNCH((k_slot<RESET, MODE, BLOCK>), dim3((unsigned) (k ? nb1 : nb0)), dim3(BLOCK), stream, e0, e1, ctx, s2, nb0); break;
+        }
+    }
+}
+
+// COMPAT split step, in front of its slot pass: the empty-slot counts of every unit, whatever envs the call names, where they are not
+// the previous pass's (they are then good for whoever is stepped next), and the step's own stream walks, one env per lane, where they
+// have not run beside the previous step's tails (k_env_walk).  Returns the start event the slot pass still has to take.
+static hipEvent_t launch_split_front(const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, hipEvent_t ev0) {
+    constexpr int BLOCK = 256;
+    if (sa.empt_fresh && !sa.walked) {
+        const int64_t nb0 = blocks_for(hp.n_envs, hp.U[0], BLOCK), nb1 = blocks_for(hp.n_envs, hp.U[1], BLOCK);
+        StepArgs all = sa;
+        all.env_mask = nullptr;
+        CHUB_LAUNCH((k_compat_empties<BLOCK>), dim3((unsigned) (nb0 + nb1)), dim3(BLOCK), stream, ev0, (hipEvent_t) nullptr, ctx, all, nb0);
+        ev0 = nullptr;
+    }
+    if (!sa.walked) {
+        CHUB_LAUNCH((k_compat_walk<false>), dim3((unsigned) ((hp.n_envs + 255) / 256)), dim3(256), stream, ev0, (hipEvent_t) nullptr, ctx, sa);
+        ev0 = nullptr;
+    }
+    return ev0;
+}
+
+template <bool RESET>
+void launch_slot(const CallPlan &cp, const HubParams &hp, const LaunchPlan &lp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream,
                  const PackedPtrs &pp, hipEvent_t ev0, hipEvent_t ev1) {
-    if (hp.rng_mode == MODE_PHILOX && !reset && (sa.fresh || sa.pk_tape))
-        hipLaunchKernelGGL(k_draw_levels, dim3((unsigned) ((2 * ((int64_t) sa.env_hi - sa.env_lo + 1) + 255) / 256)), dim3(256), 0, stream, ctx, sa);
-    if (hp.rng_mode == MODE_PHILOX && hp.soc_curves) {  // PHILOX_CURVES (chub_create refuses stations of more than 64 piles and the scalar-load control)
-        if (reset && !sa.car_tape)  // (tape mode: the caller's occupancy draws are in pk already)
-            hipLaunchKernelGGL(k_reset_levels, dim3((unsigned) ((8 * ((int64_t) sa.env_hi - sa.env_lo + 1) + 255) / 256)), dim3(256), 0, stream, ctx, sa);
-        constexpr int BLOCK = 256;
-        const int64_t nb0 = blocks_for(hp.n_envs, hp.H[0], BLOCK), nb1 = blocks_for(hp.n_envs, hp.H[1], BLOCK);
-        if (reset) CHUB_LAUNCH((k_slot_curves<true, BLOCK>), dim3((unsigned) (nb0 + nb1)), dim3(BLOCK), stream, ev0, ev1, ctx, sa, nb0);
-        else CHUB_LAUNCH((k_slot_curves<false, BLOCK>), dim3((unsigned) (nb0 + nb1)), dim3(BLOCK), stream, ev0, ev1, ctx, sa, nb0);
-        return;
+    constexpr int BLOCK = 256;
+    const int64_t nbh0 = blocks_for(hp.n_envs, hp.H[0], BLOCK), nbh1 = blocks_for(hp.n_envs, hp.H[1], BLOCK);
+    const int64_t nbu0 = blocks_for(hp.n_envs, hp.U[0], BLOCK), nbu1 = blocks_for(hp.n_envs, hp.U[1], BLOCK);
+    launch_levels(cp.levels, ctx, sa, stream);
+    switch (cp.slot) {
+    case SLOT_PACKED: launch_packed<false, RESET, false, false>(hp, lp, ctx, sa, stream, pp, ev0, ev1); break;
+    case SLOT_PACKED_MASKED: launch_packed<false, RESET, true, false>(hp, lp, ctx, sa, stream, pp, ev0, ev1); break;
+    case SLOT_PACKED_TAPE: launch_packed<true, RESET, false, false>(hp, lp, ctx, sa, stream, pp, ev0, ev1); break;  // (tape mode runs in lock-step)
+    case SLOT_PACKED_BITS:  // one bit per pile (lock-step steps only)
+        if constexpr (!RESET) launch_packed<false, false, false, true>(hp, lp, ctx, sa, stream, pp, ev0, ev1);
+        break;
+    case SLOT_CURVES: CHUB_LAUNCH((k_slot_curves<RESET, BLOCK>), dim3((unsigned) (nbh0 + nbh1)), dim3(BLOCK), stream, ev0, ev1, ctx, sa, nbh0); break;
+    case SLOT_WAVE: CHUB_LAUNCH((k_slot<RESET, MODE_PHILOX, BLOCK>), dim3((unsigned) (nbh0 + nbh1)), dim3(BLOCK), stream, ev0, ev1, ctx, sa, nbh0); break;
+    case SLOT_STATIONS: launch_stations<RESET, MODE_PHILOX>(hp, lp, ctx, sa, stream, ev0, ev1); break;
+    case SLOT_SPLIT:  // the split step: (empties ->) the stream walks, one env per lane -> the slots of both stations in one launch
+        if constexpr (RESET) {
+            CHUB_LAUNCH((k_compat_walk<true>), dim3((unsigned) ((hp.n_envs + 255) / 256)), dim3(256), stream, ev0, (hipEvent_t) nullptr, ctx, sa);
+            ev0 = nullptr;
+        } else {
+            ev0 = launch_split_front(hp, ctx, sa, stream, ev0);
+        }
+        CHUB_LAUNCH((k_slot_split<RESET, BLOCK>), dim3((unsigned) (nbu0 + nbu1)), dim3(BLOCK), stream, ev0, ev1, ctx, sa, nbu0);
+        break;
+    case SLOT_SPLIT2: {  // ... with two slots per lane (stations of 8 to 64 piles: at most 8 units per virtual wave)
+        ev0 = launch_split_front(hp, ctx, sa, stream, ev0);
+        const int64_t sb0 = blocks_for_split2(hp.n_envs, hp.U[0], BLOCK), sb1 = blocks_for_split2(hp.n_envs, hp.U[1], BLOCK);
+        CHUB_LAUNCH((k_slot_split2<BLOCK>), dim3((unsigned) (sb0 + sb1)), dim3(BLOCK), stream, ev0, ev1, ctx, sa, sb0);
+        break;
     }
-    if (hp.rng_mode == MODE_PHILOX) {
-        if (hp.packed && !sa.load_mode) {
-            if (reset && !sa.car_tape)  // (tape mode: the caller's occupancy draws are in pk already)
-                hipLaunchKernelGGL(k_reset_levels, dim3((unsigned) ((8 * ((int64_t) sa.env_hi - sa.env_lo + 1) + 255) / 256)), dim3(256), 0, stream, ctx, sa);
-            const PackedArgs pa = make_packed_args(hp, sa, pp);
-            // every workgroup of the batch, or (a call on a subset of the envs) those of the range of envs it names
-            const uint32_t nb = sa.env_mask ? (uint32_t) (sa.env_hi / hp.epb - sa.env_lo / hp.epb + 1) : (uint32_t) ((hp.n_envs + hp.epb - 1) / hp.epb);
-#define CHUB_PACKED2(TAPE_, RESET_, BIG_, MASKED_, BITS_) \
-    do {                                                                                                                              \
-        if (hp.pblock == kBigBlock)                                                                                                   \
-            CHUB_LAUNCH((k_slot_packed<kBigBlock, kBigSlotsPerLane, TAPE_, RESET_, BIG_, MASKED_, BITS_>), dim3(nb), dim3(kBigBlock), stream, ev0, ev1, ctx, sa, pa); \
-        else                                                                                                                          \
-            CHUB_LAUNCH((k_slot_packed<kPackedBlock, kSlotsPerLane, TAPE_, RESET_, BIG_, MASKED_, BITS_>), dim3(nb), dim3(kPackedBlock), stream, ev0, ev1, ctx, sa, pa); \
-    } while (0)
-#define CHUB_PACKED1(TAPE_, RESET_, BIG_, MASKED_) CHUB_PACKED2(TAPE_, RESET_, BIG_, MASKED_, false)
-#define CHUB_PACKED(TAPE_, RESET_, BIG_) \
-    do {                                                              \
-        if (sa.env_mask) CHUB_PACKED1(TAPE_, RESET_, BIG_, true);     \
-        else CHUB_PACKED1(TAPE_, RESET_, BIG_, false);                \
-    } while (0)
-            const bool big = hp.S[0] > 64 || hp.S[1] > 64;
-            if (reset && sa.car_tape) {  // tape mode runs in lock-step
-                if (big) CHUB_PACKED1(true, true, true, false);
-                else CHUB_PACKED1(true, true, false, false);
-            } else if (reset) {
-                if (big) CHUB_PACKED(false, true, true);
-                else CHUB_PACKED(false, true, false);
-            } else if (sa.car_tape) {
-                if (big) CHUB_PACKED1(true, false, true, false);
-                else CHUB_PACKED1(true, false, false, false);
-            } else if (sa.act_bits) {  // one bit per pile (lock-step entry points only: no mask)
-                if (big) CHUB_PACKED2(false, false, true, false, true);
-                else CHUB_PACKED2(false, false, false, false, true);
-            } else if (big) {
-                CHUB_PACKED(false, false, true);
-            } else {
-                CHUB_PACKED(false, false, false);
-            }
-#undef CHUB_PACKED
-#undef CHUB_PACKED1
-#undef CHUB_PACKED2
-        } else if (reset) launch_slot_t<true, MODE_PHILOX>(hp, ctx, sa, stream, ev0, ev1);
-        else launch_slot_t<false, MODE_PHILOX>(hp, ctx, sa, stream, ev0, ev1);
-        return;
+    case SLOT_COMPAT_STATIONS: launch_stations<RESET, MODE_COMPAT>(hp, lp, ctx, sa, stream, ev0, ev1); break;
     }
-    if (reset) launch_slot_t<true, MODE_COMPAT>(hp, ctx, sa, stream, ev0, ev1);
-    else launch_slot_t<false, MODE_COMPAT>(hp, ctx, sa, stream, ev0, ev1);
+}
+template void launch_slot<true>(const CallPlan &, const HubParams &, const LaunchPlan &, const DevCtx *, const StepArgs &, hipStream_t, const PackedPtrs &,
+                                hipEvent_t, hipEvent_t);
+template void launch_slot<false>(const CallPlan &, const HubParams &, const LaunchPlan &, const DevCtx *, const StepArgs &, hipStream_t, const PackedPtrs &,
+                                 hipEvent_t, hipEvent_t);
+
+// COMPAT split step, lock-step steps of every env of a handle whose stations take the two-slots-per-lane pass: the slot pass of step i
+// (sa) beside the stream walks of step i + 1 (sw: walk_far), k_slot_walk2.  Step i's own walk first where it has not run (the first step
+// after a reset or anything else that voided it: near, from the committed streams), the empty-slot counts in front of it where they are
+// not the previous pass's.
+void launch_slot_walk2(const LaunchPlan &lp, const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, const StepArgs &sw, hipStream_t stream,
+                       hipEvent_t ev0, hipEvent_t ev1) {
+    constexpr int BLOCK = 256;
+    ev0 = launch_split_front(hp, ctx, sa, stream, ev0);
+    const int64_t sb0 = blocks_for_split2(hp.n_envs, hp.U[0], BLOCK), sb1 = blocks_for_split2(hp.n_envs, hp.U[1], BLOCK);
+    switch ((CompatForm) lp.compat) {
+    case COMPAT_WALK2_32: {
+        const int nwalk = (int) ((hp.n_envs + 31) / 32);
+        CHUB_LAUNCH((k_slot_walk2<BLOCK, 32>), dim3((unsigned) (nwalk + sb0 + sb1)), dim3(BLOCK), stream, ev0, ev1, ctx, sa, sw, sb0, nwalk);
+        break;
+    }
+    case COMPAT_WALK2_64: {
+        const int nwalk = (int) ((hp.n_envs + 63) / 64);
+        CHUB_LAUNCH((k_slot_walk2<BLOCK, 64>), dim3((unsigned) (nwalk + sb0 + sb1)), dim3(BLOCK), stream, ev0, ev1, ctx, sa, sw, sb0, nwalk);
+        break;
+    }
+    default: break;
+    }
 }
 
 static PackedArgs make_packed_args(const HubParams &hp, const StepArgs &sa, const PackedPtrs &pp) {
@@ -4758,38 +4760,34 @@ static PackedArgs make_packed_args(const HubParams &hp, const StepArgs &sa, cons
     return pa;
 }
 
-// the whole PHILOX lock-step step as ONE launch (k_step_fused): the caller has checked that the hub shape and the call allow it
-void launch_step_fused(const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, const PackedPtrs &pp, hipEvent_t ev0,
-                       hipEvent_t ev1) {
-    if (sa.fresh || sa.pk_tape) hipLaunchKernelGGL(k_draw_levels, dim3((unsigned) ((2 * ((int64_t) sa.env_hi - sa.env_lo + 1) + 255) / 256)), dim3(256), 0, stream, ctx, sa);
+// the whole PHILOX lock-step step as ONE launch (k_step_fused / k_step_tailwave)
+void launch_step_fused(const CallPlan &cp, const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, const PackedPtrs &pp,
+                       hipEvent_t ev0, hipEvent_t ev1) {
+    launch_levels(cp.levels, ctx, sa, stream);
     const PackedArgs pa = make_packed_args(hp, sa, pp);
     TailArgs ta = make_tail_args(*pp.ev, *pp.st, hp, sa, pp, false);
+    // the tails read their two actions from the action rows (the workgroup has just had them in cache), or with one bit per pile from
+    // the caller's [N][2] array
+    ta.tail_act = (cp.one == ONE_FUSED_BITS || cp.one == ONE_TAILWAVE_BITS) ? (CHUB_G(const float)) sa.act_tail : nullptr;
     const uint32_t nb = (uint32_t) ((hp.n_envs + hp.epb - 1) / hp.epb);
-    if (sa.tail_tape) {  // tape mode (the caller has checked: station draws, car variates and the tail's variates all come from the tape)
-        ta.tail_act = nullptr;
+    switch (cp.one) {  // (the tail wave's lanes are the workgroup's envs)
+    case ONE_FUSED: CHUB_LAUNCH((k_step_fused<kPackedBlock, kSlotsPerLane>), dim3(nb), dim3(kPackedBlock), stream, ev0, ev1, ctx, sa, pa, ta); break;
+    case ONE_TAILWAVE: CHUB_LAUNCH((k_step_tailwave<kPackedBlock, kSlotsPerLane>), dim3(nb), dim3(kPackedBlock + 64), stream, ev0, ev1, ctx, sa, pa, ta); break;
+    case ONE_FUSED_BITS: CHUB_LAUNCH((k_step_fused<kPackedBlock, kSlotsPerLane, true>), dim3(nb), dim3(kPackedBlock), stream, ev0, ev1, ctx, sa, pa, ta); break;
+    case ONE_TAILWAVE_BITS:
+        CHUB_LAUNCH((k_step_tailwave<kPackedBlock, kSlotsPerLane, true>), dim3(nb), dim3(kPackedBlock + 64), stream, ev0, ev1, ctx, sa, pa, ta);
+        break;
+    case ONE_FUSED_TAPE:  // station draws, car variates and the tail's variates all come from the tape
         CHUB_LAUNCH((k_step_fused<kPackedBlock, kSlotsPerLane, false, true>), dim3(nb), dim3(kPackedBlock), stream, ev0, ev1, ctx, sa, pa, ta);
-        return;
+        break;
+    case ONE_NONE: break;
     }
-    if (sa.act_bits) {  // one bit per pile: the tails read their two actions from the caller's [N][2] array
-        ta.tail_act = (CHUB_G(const float)) sa.act_tail;
-        if (hp.epb <= 64)
-            CHUB_LAUNCH((k_step_tailwave<kPackedBlock, kSlotsPerLane, true>), dim3(nb), dim3(kPackedBlock + 64), stream, ev0, ev1, ctx, sa, pa, ta);
-        else
-            CHUB_LAUNCH((k_step_fused<kPackedBlock, kSlotsPerLane, true>), dim3(nb), dim3(kPackedBlock), stream, ev0, ev1, ctx, sa, pa, ta);
-        return;
-    }
-    ta.tail_act = nullptr;  // the tails read their two actions from the action rows (the workgroup has just had them in cache)
-    if (hp.epb <= 64)  // (the tail wave's lanes are the workgroup's envs)
-        CHUB_LAUNCH((k_step_tailwave<kPackedBlock, kSlotsPerLane>), dim3(nb), dim3(kPackedBlock + 64), stream, ev0, ev1, ctx, sa, pa, ta);
-    else
-        CHUB_LAUNCH((k_step_fused<kPackedBlock, kSlotsPerLane>), dim3(nb), dim3(kPackedBlock), stream, ev0, ev1, ctx, sa, pa, ta);
 }
 
-// COMPAT lock-step reset / step of a handle whose envs all fit one workgroup (the caller has checked): one launch
 // a span of n_steps lock-step steps from `sa` (the span's first step) in one launch: chub_run_steps, PHILOX handles on the one-launch step
-void launch_steps_fused(const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, const PackedPtrs &pp, int n_steps, int pc0,
-                        int64_t first, const float *const *batches, int n_batches, float *const *packed2, bool piped) {
-    if (sa.fresh) hipLaunchKernelGGL(k_draw_levels, dim3((unsigned) ((2 * ((int64_t) sa.env_hi - sa.env_lo + 1) + 255) / 256)), dim3(256), 0, stream, ctx, sa);
+void launch_steps_fused(const HubParams &hp, const LaunchPlan &lp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, const PackedPtrs &pp,
+                        int n_steps, int pc0, int64_t first, const float *const *batches, int n_batches, float *const *packed2) {
+    launch_levels(sa.fresh ? LEVELS_DRAW : LEVELS_NONE, ctx, sa, stream);
     const PackedArgs pa = make_packed_args(hp, sa, pp);
     TailArgs ta = make_tail_args(*pp.ev, *pp.st, hp, sa, pp, false);
     ta.tail_act = nullptr;  // (the tails read their two actions from the action rows, as in k_step_fused)
@@ -4812,21 +4810,25 @@ void launch_steps_fused(const HubParams &hp, const DevCtx *ctx, const StepArgs &
     sp.wdT = (CHUB_G(const double)) pp.tb->wdT;
     sp.sin96 = (CHUB_G(const double)) pp.tb->sin96;
     const uint32_t nb = (uint32_t) ((hp.n_envs + hp.epb - 1) / hp.epb);
-    if (piped)  // (the caller has checked: at most 64 envs per workgroup -- the tail wave's lanes are the workgroup's envs)
+    if (lp.span_piped)  // (the tail wave's lanes are the workgroup's envs)
         hipLaunchKernelGGL((k_steps_piped<kPackedBlock, kSlotsPerLane>), dim3(nb), dim3(kPackedBlock + 64), 0, stream, ctx, sa, pa, ta, sp);
     else
         hipLaunchKernelGGL((k_steps_fused<kPackedBlock, kSlotsPerLane>), dim3(nb), dim3(kPackedBlock), 0, stream, ctx, sa, pa, ta, sp);
 }
 
-void launch_compat_small(bool reset, const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, const PackedPtrs &pp) {
-    const TailArgs ta = make_tail_args(*pp.ev, *pp.st, hp, sa, pp, reset);
-    if (reset) hipLaunchKernelGGL(k_compat_small<true>, dim3(1), dim3(kCompatSmallBlock), 0, stream, ctx, sa, ta);
-    else hipLaunchKernelGGL(k_compat_small<false>, dim3(1), dim3(kCompatSmallBlock), 0, stream, ctx, sa, ta);
+// COMPAT lock-step reset / step of a handle whose envs all fit one workgroup: one launch
+template <bool RESET>
+void launch_compat_small(const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, const PackedPtrs &pp) {
+    const TailArgs ta = make_tail_args(*pp.ev, *pp.st, hp, sa, pp, RESET);
+    hipLaunchKernelGGL(k_compat_small<RESET>, dim3(1), dim3(kCompatSmallBlock), 0, stream, ctx, sa, ta);
 }
+template void launch_compat_small<true>(const HubParams &, const DevCtx *, const StepArgs &, hipStream_t, const PackedPtrs &);
+template void launch_compat_small<false>(const HubParams &, const DevCtx *, const StepArgs &, hipStream_t, const PackedPtrs &);
 
-void launch_env(bool reset, const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, hipEvent_t ev0,
-                hipEvent_t ev1, const PackedPtrs &pp) {
-    const TailArgs ta = make_tail_args(*pp.ev, *pp.st, hp, sa, pp, reset);
+template <bool RESET>
+void launch_env(EnvForm f, const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
+                const PackedPtrs &pp) {
+    const TailArgs ta = make_tail_args(*pp.ev, *pp.st, hp, sa, pp, RESET);
     // the tail blocks of every env, or (per-env clocks) of the range of envs the call names
     const int nb_env = sa.env_clk ? sa.env_hi / kEnvBlock - sa.env_lo / kEnvBlock + 1 : (int) ((hp.n_envs + kEnvBlock - 1) / kEnvBlock);
     if (sa.env_clk && sa.env_mask) {
@@ -4836,25 +4838,20 @@ void launch_env(bool reset, const HubParams &hp, const DevCtx *ctx, const StepAr
         hipLaunchKernelGGL(k_keep_clocks, dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, stream, sa.env_clk + (int64_t) ((sa.tick + 1u) & 1u) * N,
                            (const uint16_t *) sa.env_clk + (int64_t) (sa.tick & 1u) * N, N);
     }
-    if (hp.rng_mode == MODE_PHILOX) {
-        // + the level-draw workgroups: next step's state-independent variates (3 lanes per env: two stations, one env)
-        const unsigned nb = (unsigned) nb_env + (unsigned) ((3 * ((int64_t) sa.env_hi - sa.env_lo + 1) + kEnvBlock - 1) / kEnvBlock);
-        if (sa.tail_tape) {  // tape mode (lock-step): the tail's variates from the caller
-            if (reset) CHUB_LAUNCH((k_env<true, MODE_PHILOX, false, true>), dim3(nb), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env);
-            else CHUB_LAUNCH((k_env<false, MODE_PHILOX, false, true>), dim3(nb), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env);
-        } else if (sa.env_clk) {  // per-env clocks: its own instantiation
-            if (reset) CHUB_LAUNCH((k_env<true, MODE_PHILOX, true>), dim3(nb), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env);
-            else CHUB_LAUNCH((k_env<false, MODE_PHILOX, true>), dim3(nb), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env);
-        } else if (reset) CHUB_LAUNCH((k_env<true, MODE_PHILOX, false>), dim3(nb), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env);
-        else CHUB_LAUNCH((k_env<false, MODE_PHILOX, false>), dim3(nb), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env);
-    } else {
-        if (sa.env_clk) {  // per-env clocks
-            if (reset) CHUB_LAUNCH((k_env<true, MODE_COMPAT, true>), dim3((unsigned) nb_env), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env);
-            else CHUB_LAUNCH((k_env<false, MODE_COMPAT, true>), dim3((unsigned) nb_env), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env);
-        } else if (reset) CHUB_LAUNCH((k_env<true, MODE_COMPAT, false>), dim3((unsigned) nb_env), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env);
-        else CHUB_LAUNCH((k_env<false, MODE_COMPAT, false>), dim3((unsigned) nb_env), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env);
+    // PHILOX: + the level-draw workgroups: next step's state-independent variates (3 lanes per env: two stations, one env)
+    const unsigned nb = (unsigned) nb_env + (unsigned) ((3 * ((int64_t) sa.env_hi - sa.env_lo + 1) + kEnvBlock - 1) / kEnvBlock);
+    switch (f) {
+    case ENV_PHILOX: CHUB_LAUNCH((k_env<RESET, MODE_PHILOX, false>), dim3(nb), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env); break;
+    case ENV_PHILOX_CLOCKS: CHUB_LAUNCH((k_env<RESET, MODE_PHILOX, true>), dim3(nb), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env); break;
+    case ENV_PHILOX_TAPE:  // tape mode (lock-step): the tail's variates from the caller
+        CHUB_LAUNCH((k_env<RESET, MODE_PHILOX, false, true>), dim3(nb), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env);
+        break;
+    case ENV_COMPAT: CHUB_LAUNCH((k_env<RESET, MODE_COMPAT, false>), dim3((unsigned) nb_env), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env); break;
+    case ENV_COMPAT_CLOCKS: CHUB_LAUNCH((k_env<RESET, MODE_COMPAT, true>), dim3((unsigned) nb_env), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env); break;
     }
 }
+template void launch_env<true>(EnvForm, const HubParams &, const DevCtx *, const StepArgs &, hipStream_t, hipEvent_t, hipEvent_t, const PackedPtrs &);
+template void launch_env<false>(EnvForm, const HubParams &, const DevCtx *, const StepArgs &, hipStream_t, hipEvent_t, hipEvent_t, const PackedPtrs &);
 
 // COMPAT split step, lock-step: the tails of step `sa` + the walks of the step after it (`sw`: its clock and tick)
 void launch_env_walk(const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, const StepArgs &sw, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,

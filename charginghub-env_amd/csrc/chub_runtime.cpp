@@ -15,27 +15,31 @@
 
 #include "../../include/chub.h"
 #include "chub_device.h"
+#include "chub_plan.h"
 
 namespace chub {
-void launch_slot(bool reset, const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream,
+template <bool RESET>
+void launch_slot(const CallPlan &cp, const HubParams &hp, const LaunchPlan &lp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream,
                  const PackedPtrs &pp, hipEvent_t ev0, hipEvent_t ev1);
 void launch_replay_soc(const HubParams &hp, const DevCtx *ctx, float *d_out, hipStream_t stream);
 void launch_check_ttab(const DevCtx *ctx, uint32_t *d_mismatch, hipStream_t stream);
-void launch_env(bool reset, const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, hipEvent_t ev0,
-                hipEvent_t ev1, const PackedPtrs &pp);
+template <bool RESET>
+void launch_env(EnvForm f, const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
+                const PackedPtrs &pp);
 void launch_random_actions(const HubParams &hp, uint64_t key, uint32_t batch, float *d_actions, hipStream_t stream);
 void launch_compat_ctor_sweep(const HubParams &hp, const DevCtx *ctx, int rng_cur, hipStream_t stream);
 void launch_tick_advance(uint32_t *tick_base, uint32_t by, hipStream_t stream);
 void launch_fill_clocks(uint16_t *dst, int64_t n, uint16_t value, hipStream_t stream);
 void launch_keep_clocks(uint16_t *dst, const uint16_t *src, int64_t n, hipStream_t stream);
 void launch_expand_bits(const HubParams &hp, const uint64_t *d_bits, const float *d_tail, float *d_actions, hipStream_t stream);
-void launch_step_fused(const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, const PackedPtrs &pp, hipEvent_t ev0,
-                       hipEvent_t ev1);
-void launch_compat_small(bool reset, const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, const PackedPtrs &pp);
-void launch_steps_fused(const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, const PackedPtrs &pp, int n_steps, int pc0,
-                        int64_t first, const float *const *batches, int n_batches, float *const *packed2, bool piped);
-bool slot_walk2_covers(const HubParams &hp);
-void launch_slot_walk2(const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, const StepArgs &sw, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1);
+void launch_step_fused(const CallPlan &cp, const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, const PackedPtrs &pp,
+                       hipEvent_t ev0, hipEvent_t ev1);
+template <bool RESET>
+void launch_compat_small(const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, const PackedPtrs &pp);
+void launch_steps_fused(const HubParams &hp, const LaunchPlan &lp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, const PackedPtrs &pp,
+                        int n_steps, int pc0, int64_t first, const float *const *batches, int n_batches, float *const *packed2);
+void launch_slot_walk2(const LaunchPlan &lp, const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, const StepArgs &sw, hipStream_t stream,
+                       hipEvent_t ev0, hipEvent_t ev1);
 void launch_env_walk(const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, const StepArgs &sw, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
                      const PackedPtrs &pp);
 }  // namespace chub
@@ -67,15 +71,10 @@ struct chub_env {
     CompatRng cr;
     Tables tb;
     int device;
-    bool fused;         // PHILOX lock-step steps of this handle run as ONE launch (k_step_fused): small batches
-    bool span_size_ok = false;   // spans of steps in one launch: few enough workgroups (or the one-launch step forced: the measurements)
-    bool span_piped = false;     // ... with the tails on a wave of their own, a step behind (k_steps_piped; chub_options.span_tails)
-    int span_steps = 0;          // chub_options.span_steps: chub_run_steps's spans of steps in one launch (0: up to a day's rest; 1: never; n: at most n)
-    bool no_walk_ahead = false;  // chub_options.walk_ahead = 1: the split COMPAT step never walks ahead (A/B, parity cross-check)
+    LaunchPlan plan;           // the launch forms of this handle (chub_plan.h)
     int rng_cur = 0;           // COMPAT: which of CompatRng's three buffers holds the committed streams (moved on by every commit: chub_device.h)
     uint32_t walked_tick = 0;  // COMPAT split step: the tick whose stream walk has run already, beside the previous step's tails (0: none)
     uint32_t e2_tick = ~0u;    // ... and the tick of the pass after which StationArrays::empt2 holds every unit's count (what a walk two steps ahead needs)
-    bool compat_small;  // COMPAT: every env fits one workgroup for both stations: lock-step resets and steps are ONE launch (k_compat_small)
     bool empt_valid;    // COMPAT, split step: StationArrays::empt holds every unit's empty-slot count for the next step (left by the last split pass)
     DevCtx *d_ctx;      // device copy of {hp, sl, st, ev, cr, tb}
     bool ctx_dirty;
@@ -393,41 +392,21 @@ int chub_create_ex(const chub_config *cfg, const char *data_dir, int64_t n_envs,
     chub_options opt;
     memset(&opt, 0, sizeof opt);
     if (opt_in) opt = *opt_in;
-    if (opt.slot_kernel < 0 || opt.slot_kernel > 2) return fail(CHUB_ERR_ARG, "chub_options.slot_kernel must be 0, 1 or 2");
-    if (opt.fused_step < 0 || opt.fused_step > 2) return fail(CHUB_ERR_ARG, "chub_options.fused_step must be 0, 1 or 2");
-    if (opt.tile < 0 || opt.tile > 2) return fail(CHUB_ERR_ARG, "chub_options.tile must be 0, 1 or 2");
-    if (opt.walk_ahead < 0 || opt.walk_ahead > 1) return fail(CHUB_ERR_ARG, "chub_options.walk_ahead must be 0 or 1");
-    if (opt.work_order < 0 || opt.work_order > 1) return fail(CHUB_ERR_ARG, "chub_options.work_order must be 0 or 1");
-    if (opt.span_steps < 0 || opt.span_steps > 96) return fail(CHUB_ERR_ARG, "chub_options.span_steps must be 0 .. 96");
-    if (opt.span_tails < 0 || opt.span_tails > 2) return fail(CHUB_ERR_ARG, "chub_options.span_tails must be 0 (by size), 1 (on the last slot wave) or 2 (on a wave of their own)");
     *out = nullptr;
-    if (n_envs <= 0) return fail(CHUB_ERR_ARG, "n_envs must be positive");
-    if (n_envs * (int64_t) (cfg->station_list[0] + cfg->station_list[1] + 2) >= (int64_t) 1 << 31)
-        return fail(CHUB_ERR_UNSUPPORTED, "n_envs * (piles + 2) must stay below 2^31 per handle (32-bit slot indices)");
-    if (rng_mode != CHUB_RNG_COMPAT && rng_mode != CHUB_RNG_PHILOX && rng_mode != CHUB_RNG_PHILOX_CURVES) return fail(CHUB_ERR_ARG, "unknown rng_mode");
-    // PHILOX_CURVES: PHILOX's draws and tail, the slots on k_slot_curves (chub_kernels.hip); a unit is one wave's lanes there
+    LaunchPlan plan;
+    const char *msg = nullptr;
+    if (const int rc = plan_handle(cfg, n_envs, rng_mode, opt, plan, &msg)) return fail(rc, msg);
+    // PHILOX_CURVES: PHILOX's draws and tail, the slots on k_slot_curves (chub_kernels.hip)
     const bool soc_curves = rng_mode == CHUB_RNG_PHILOX_CURVES;
-    if (soc_curves && (cfg->station_list[0] > 64 || cfg->station_list[1] > 64))
-        return fail(CHUB_ERR_UNSUPPORTED, "rng_mode PHILOX_CURVES covers stations of at most 64 piles (its slot kernel keeps a station's unit inside one wave)");
     const int public_mode = rng_mode;
     if (soc_curves) rng_mode = CHUB_RNG_PHILOX;
-    for (int k = 0; k < 2; k++) {
-        if (cfg->station_list[k] < 0) return fail(CHUB_ERR_ARG, "station_list entries must be >= 0");
-        // the production (PHILOX) kernel lays whole envs over a workgroup's 512 (2048) virtual lanes; the wave-local kernels keep a unit
-        // of up to 64 piles inside a wave, give a larger one a workgroup of 256 lanes (k_slot_unit) and walk a unit of more than 256
-        // piles in chunks (k_slot_unit_any, whose scalar-load control ranks the whole unit in LDS: kMaxPiles)
-        if (cfg->station_list[k] > kMaxPiles) return fail(CHUB_ERR_UNSUPPORTED, "more than 4096 piles per station is not supported");
-        if (cfg->station_type_list[k] != CHUB_FAST && cfg->station_type_list[k] != CHUB_SLOW)
-            return fail(CHUB_ERR_ARG, "EVS type must be fast or slow");  // AGG:196
-    }
-    if (cfg->station_list[0] + cfg->station_list[1] < 1)
-        return fail(CHUB_ERR_ARG, "A station must have fast pile or slow pile!");  // MGR:336
     if (!(cfg->init_soc >= 0.1 && cfg->init_soc <= 1)) return fail(CHUB_ERR_ARG, "init_soc must be in [0.1, 1]");  // HYD:137
     if (!(cfg->hydro_prod_rate >= 0) || !(cfg->hydro_store_vlt > 0) || !(cfg->fc_max_power >= 0))
         return fail(CHUB_ERR_ARG, "hydrogen system sizes must be non-negative");
 
     chub_env *e = new chub_env();
     e->cfg = *cfg;
+    e->plan = plan;
     e->public_mode = public_mode;
     e->device = device;
     e->t = 0;
@@ -732,51 +711,12 @@ int chub_create_ex(const chub_config *cfg, const char *data_dir, int64_t n_envs,
     e->cur_tail = nullptr;
     e->capturing = false;
     e->graph_base = 0;
-    // packed slot kernel (k_slot_packed): the workgroup's virtual lanes laid over whole envs end to end
-    {
-        const int St = hp.S[0] + hp.S[1];
-        // the workgroup tile: the small one while state and action rows live in the caches, the large one once they stream from HBM
-        // (a hub too large for the small tile's 512 virtual lanes -- stations of several hundred piles -- still fits the large one's 2048)
-        const bool big_tile = opt.tile == 2 || (opt.tile == 0 && (n_envs * (int64_t) St >= kBigTileSlots || St > kPackedBlock * kSlotsPerLane));
-        hp.pblock = big_tile ? kBigBlock : kPackedBlock;
-        hp.pslots = big_tile ? kBigSlotsPerLane : kSlotsPerLane;
-        // ... and the work order: XCD-aware while the streams are cache-resident (measured: 4-6 % of the step; HBM-resident sizes lose 1 %)
-        hp.xcd = (opt.work_order == 0 && (!big_tile || CHUB_XCD_ANY_TILE) && n_envs * (int64_t) St <= kXcdOrderSlots) ? 1 : 0;
-        const int pb = hp.pblock * hp.pslots;
-        hp.epb = pb / St > 0 ? pb / St : 1;
-        if (hp.epb > pb / 4) hp.epb = pb / 4;  // the workgroup's per-unit LDS areas hold 2 * pb / 4 units: hubs of 1-3 piles leave lanes idle
-        bool magic_ok = true;  // the kernel divides lane numbers by S0 + S1 with a 20-bit reciprocal
-        for (int l = 0; l < pb && magic_ok; l++)
-            if ((((uint32_t) l * ((1u << 20) / (uint32_t) St + 1u)) >> 20) != (uint32_t) (l / St)) magic_ok = false;
-        hp.packed = (rng_mode == CHUB_RNG_PHILOX && St >= 1 && St <= pb && magic_ok &&
-                     (uint64_t) n_envs * (uint64_t) (St + 2) * 16u < ((uint64_t) 1 << 32) &&  // 32-bit byte offsets
-                     opt.slot_kernel != 1 && !soc_curves) ? 1 : 0;  // (PHILOX_CURVES: k_slot_curves whatever the options say)
-    }
-    {   // the whole step as one launch: where the two kernels are launch- and latency-bound and every workgroup finds room at once
-        const int64_t nb = (n_envs + hp.epb - 1) / hp.epb;
-        const bool can = hp.packed && hp.S[0] <= 64 && hp.S[1] <= 64 && hp.pblock == kPackedBlock;
-        e->fused = can && (opt.fused_step == 2 || (opt.fused_step == 0 && nb <= (hp.epb <= 64 ? kFusedMaxBlocksTailWave : kFusedMaxBlocks)));
-        e->span_size_ok = nb <= kSpanMaxBlocks || opt.fused_step == 2;
-        if (opt.fused_step == 2 && !can)
-            return bail(fail(CHUB_ERR_UNSUPPORTED, "fused_step = 2: the single-launch step covers PHILOX handles on the packed slot kernel with "
-                                                   "stations of at most 64 piles"));
-        // chub_run_steps's spans: the tails on a wave of their own, a step behind the slot waves (k_steps_piped) -- its 64 lanes are the workgroup's envs
-        const bool can_pipe = e->fused && hp.epb <= 64;
-        e->span_piped = can_pipe && (opt.span_tails == 2 || (opt.span_tails == 0 && nb <= kPipedMaxBlocks));
-        if (opt.span_tails == 2 && !can_pipe)
-            return bail(fail(CHUB_ERR_UNSUPPORTED, "span_tails = 2: the tail wave of a span covers handles on the one-launch step (fused_step) with at most 64 envs "
-                                                   "per workgroup (hubs of 8 piles and more)"));
-    }
-    {   // the reference-exact mode at a handful of envs (the drop-in class: one): both station passes and the tail in one launch
-        const int64_t fit = std::min<int64_t>(64, std::min<int64_t>(kCompatSmallWaves0 * (64 / hp.U[0]), kCompatSmallWaves1 * (64 / hp.U[1])));
-        e->no_walk_ahead = opt.walk_ahead == 1;
-        e->span_steps = opt.span_steps;
-        e->compat_small = rng_mode == CHUB_RNG_COMPAT && opt.fused_step != 1 && hp.S[0] <= 64 && hp.S[1] <= 64 && n_envs <= fit;
-        // ... and everything else as the split step (stream walks, one env per lane -> slots of both stations in one launch) unless
-        // slot_kernel = 1 asks for one kernel per station with the unit's first lane walking (the parity cross-check).  Measured, us per
-        // step, split vs per station: 47.1 vs 51.1 at 1024 envs, 49.7 vs 50.9 at 4096, 54 vs 70 at 8192, 100 vs 279 at 65 536 ([20, 25] hub)
-        hp.compat_split = (rng_mode == CHUB_RNG_COMPAT && hp.S[0] <= 64 && hp.S[1] <= 64 && opt.slot_kernel != 1) ? 1 : 0;
-    }
+    hp.packed = plan.packed != PACKED_NONE ? 1 : 0;
+    hp.pblock = plan.pblock;
+    hp.pslots = plan.pslots;
+    hp.epb = plan.epb;
+    hp.xcd = plan.xcd;
+    hp.compat_split = (plan.compat == COMPAT_SPLIT || plan.compat == COMPAT_WALK2_32 || plan.compat == COMPAT_WALK2_64) ? 1 : 0;
     build_hy_table(hp, e->hy_table);
     std::vector<double> hy_v(e->hy_table, e->hy_table + 102);
 
@@ -955,8 +895,22 @@ int chub_clock(const chub_env *e) {  // lock-step: the clock; per-env clocks: en
     return (int) (c & 127u);
 }
 int chub_uses_packed_kernel(const chub_env *e) { return e ? e->hp.packed : CHUB_ERR_ARG; }
-int chub_uses_xcd_order(const chub_env *e) { return e ? ((e->hp.packed && e->hp.xcd && !e->fused) ? 1 : 0) : CHUB_ERR_ARG; }  // (the single-launch step has one order only)
-int chub_uses_fused_step(const chub_env *e) { return e ? ((e->fused || e->compat_small) ? 1 : 0) : CHUB_ERR_ARG; }
+int chub_uses_xcd_order(const chub_env *e) {  // (the single-launch step has one order only)
+    return e ? ((e->hp.packed && e->hp.xcd && e->plan.one_launch == ONE_NONE) ? 1 : 0) : CHUB_ERR_ARG;
+}
+int chub_uses_fused_step(const chub_env *e) { return e ? ((e->plan.one_launch != ONE_NONE || e->plan.compat_small) ? 1 : 0) : CHUB_ERR_ARG; }
+
+int chub_launch_plan(const chub_config *cfg, int64_t n_envs, int rng_mode, const chub_options *opt_in, int32_t *out) {
+    if (!cfg || !out) return fail(CHUB_ERR_ARG, "null argument");
+    chub_options opt;
+    memset(&opt, 0, sizeof opt);
+    if (opt_in) opt = *opt_in;
+    LaunchPlan p;
+    const char *msg = nullptr;
+    if (const int rc = plan_handle(cfg, n_envs, rng_mode, opt, p, &msg)) return fail(rc, msg);
+    memcpy(out, &p, sizeof p);  // (LaunchPlan is the CHUB_PLAN_* list: chub_plan.h)
+    return CHUB_OK;
+}
 
 int chub_sync(chub_env *e) {
     if (!e) return fail(CHUB_ERR_ARG, "null handle");
@@ -1055,12 +1009,26 @@ static int note_served(chub_env *e, const uint8_t *mask, int served, hipStream_t
     return CHUB_OK;
 }
 
-// ONE launched reset: of every env (served = 2) or of the envs of the uploaded mask (served = 1)
 // COMPAT: the handle's lock-step steps of every env run the slot pass beside the NEXT step's stream walks (k_slot_walk2)
-static bool walks_two_ahead(const chub_env *e) {
-    return e->hp.rng_mode == CHUB_RNG_COMPAT && !e->compat_small && !e->no_walk_ahead && slot_walk2_covers(e->hp);
+static bool walks_two_ahead(const chub_env *e) { return e->plan.compat == COMPAT_WALK2_32 || e->plan.compat == COMPAT_WALK2_64; }
+
+// the launch forms of the reset / step in progress (chub_plan.h)
+static CallPlan plan_this_call(const chub_env *e, bool reset, int served, int load_mode, bool fresh) {
+    CallState c;
+    c.reset = reset;
+    c.load_mode = load_mode != 0;
+    c.per_env = e->per_env;
+    c.all_served = served == 2;
+    c.capturing = e->capturing;
+    c.car_tape = e->tape_car != nullptr;
+    c.pk_tape = !reset && e->tape_pk;
+    c.tail_tape = e->tape_tail;
+    c.bits = !reset && e->cur_bits;
+    c.fresh = fresh;
+    return plan_call(e->plan, c);
 }
 
+// ONE launched reset: of every env (served = 2) or of the envs of the uploaded mask (served = 1)
 static int run_reset(chub_env *e, int served, const int32_t *d_exo_days, const double *d_exo_z, float *d_obs, hipStream_t s) {
     e->tick += 1;
     StepArgs sa;
@@ -1076,8 +1044,9 @@ static int run_reset(chub_env *e, int served, const int32_t *d_exo_days, const d
     sa.obs_stride = e->hp.obs_dim;
     sa.car_tape = e->tape_car;  // chub_reset_tape: the unit's occupancy draws are in pk already, the cars' variates come from the tape
     sa.tail_tape = e->tape_tail ? 1 : 0;  // chub_reset_tape_env: the tail's days and normals from the caller as well
+    const CallPlan cp = plan_this_call(e, true, served, 0, false);
     // COMPAT split reset: the walk's draws are committed by the slot pass (k_compat_small walks the streams in place: nothing to commit)
-    sa.commit_rng = (e->hp.compat_split != 0 && !(e->compat_small && !e->per_env)) ? 1 : 0;
+    sa.commit_rng = (cp.call != CALL_COMPAT_SMALL && slot_form_split(cp.slot)) ? 1 : 0;
     sa.walk_short = walks_two_ahead(e) ? 1 : 0;  // (the reset's walk leaves its short stays for a walk two steps ahead, as every walk of such a handle)
     sa.rng_cur = e->rng_cur;
     e->walked_tick = 0;                   // (a walk that ran ahead for a step that now does not come: its shadow is simply overwritten)
@@ -1093,13 +1062,13 @@ static int run_reset(chub_env *e, int served, const int32_t *d_exo_days, const d
     }
     int rc_ = sync_ctx(e, s);
     if (rc_) return rc_;
-    if (e->compat_small && !e->per_env) {
-        launch_compat_small(true, e->hp, e->d_ctx, sa, s, packed_ptrs(e));
+    if (cp.call == CALL_COMPAT_SMALL) {
+        launch_compat_small<true>(e->hp, e->d_ctx, sa, s, packed_ptrs(e));
         e->empt_valid = true;  // (k_compat_small is the split step in one launch: its slot waves leave the counts)
     } else {
-        launch_slot(true, e->hp, e->d_ctx, sa, s, packed_ptrs(e), nullptr, nullptr);
+        launch_slot<true>(cp, e->hp, e->plan, e->d_ctx, sa, s, packed_ptrs(e), nullptr, nullptr);
         if (sa.commit_rng) sa.rng_cur = e->rng_cur = (e->rng_cur + 1) % 3;  // the commit: the walk's shadow is the streams' buffer from here on
-        launch_env(true, e->hp, e->d_ctx, sa, s, nullptr, nullptr, packed_ptrs(e));
+        launch_env<true>(cp.env, e->hp, e->d_ctx, sa, s, nullptr, nullptr, packed_ptrs(e));
         // (a split reset leaves the counts of the units it served; those of the others are as good as they were)
         e->empt_valid = e->hp.compat_split != 0 && (served == 2 || e->empt_valid) && !e->capturing;
         if (e->hp.compat_split != 0 && served == 2 && !e->capturing) e->e2_tick = e->tick;  // (... and every unit's empt2, at this tick's parity)
@@ -1182,7 +1151,7 @@ int chub_step_gather(chub_env *e, chub_comm *comm, const float *d_actions, float
 // (k_steps_fused: the workgroup that owns an env's slots, records and tail goes from step to step by itself).  Not while a tape is loaded,
 // on per-env clocks, with one bit per pile, under the per-kernel profiler or with chub_options.span_steps = 1.
 static bool span_ok(const chub_env *e, int n_batches) {
-    return e->fused && e->span_size_ok && e->span_steps != 1 && e->hp.rng_mode == CHUB_RNG_PHILOX && !e->per_env && !e->prof_on && !e->tape_pk && !e->tape_car &&
+    return e->plan.one_launch != ONE_NONE && e->plan.span_size_ok && e->plan.span_steps != 1 && !e->per_env && !e->prof_on && !e->tape_pk && !e->tape_car &&
            !e->tape_tail && !e->tape_only && !e->cur_bits && n_batches <= 8 && e->tick != 0 && !e->hp.telemetry;
 }
 
@@ -1215,7 +1184,7 @@ static int run_span(chub_env *e, const float *const *batches, int n_batches, flo
 #endif
     int rc = sync_ctx(e, s);
     if (rc) return rc;
-    launch_steps_fused(e->hp, e->d_ctx, sa, s, packed_ptrs(e), k, e->price_count, first, batches, n_batches, packed2, e->span_piped);
+    launch_steps_fused(e->hp, e->plan, e->d_ctx, sa, s, packed_ptrs(e), k, e->price_count, first, batches, n_batches, packed2);
     HIP_TRY(hipGetLastError());
     e->tick += (uint32_t) k;
     if (e->capturing) e->cap_full_rel = e->tick - e->graph_tick0;  // (note_served: which launch of the capture served every env last)
@@ -1241,7 +1210,7 @@ int chub_run_steps(chub_env *e, chub_comm *comm, const float *const *d_action_ba
             int64_t k = first_step + n_steps - i;
             k = k < 96 - i % 96 ? k : 96 - i % 96;
             k = k < 96 - e->t ? k : 96 - e->t;  // (the handle's own clock need not be i % 96: a caller may step on past `done` -- the span ends where the clock wraps)
-            if (e->span_steps > 1 && k > e->span_steps) k = e->span_steps;
+            if (e->plan.span_steps > 1 && k > e->plan.span_steps) k = e->plan.span_steps;
             if (k >= 2 && span_ok(e, n_batches)) {
                 if ((rc = run_span(e, d_action_batches, n_batches, d_packed2, i, (int) k, (hipStream_t) stream))) return rc;
                 i += k - 1;
@@ -1312,7 +1281,12 @@ static int run_step(chub_env *e, int served, const float *d_actions, const doubl
     sa.hv_tape = e->tape_hv;
     sa.hv_w = e->tape_hv_w;
     sa.tail_tape = e->tape_tail ? 1 : 0;
-    const bool split_step = e->hp.compat_split != 0 && !(e->compat_small && !load_mode && !e->per_env);
+    // the state-independent draws of this step: left by the previous launch's level blocks if that launch served every env
+    // (for the tick that is now this launch's), otherwise made by this launch itself (a graph's first step always makes its
+    // own: a replay must not depend on what ran before it)
+    sa.fresh = (!e->predrawn || (e->capturing && e->tick == e->graph_tick0 + 1u)) ? 1 : 0;
+    const CallPlan cp = plan_this_call(e, false, served, load_mode, sa.fresh != 0);
+    const bool split_step = cp.call != CALL_COMPAT_SMALL && slot_form_split(cp.slot);
     sa.rng_cur = e->rng_cur;
     if (split_step) {  // COMPAT split step: the slot pass commits the walk's draws, the tail reads the forecourt's from where the walk left them
         sa.commit_rng = 1;
@@ -1332,10 +1306,6 @@ static int run_step(chub_env *e, int served, const float *d_actions, const doubl
             sa.env_hi = (int32_t) e->mask_hi;
         }
     }
-    // the state-independent draws of this step: left by the previous launch's level blocks if that launch served every env
-    // (for the tick that is now this launch's), otherwise made by this launch itself (a graph's first step always makes its
-    // own: a replay must not depend on what ran before it)
-    sa.fresh = (!e->predrawn || (e->capturing && e->tick == e->graph_tick0 + 1u)) ? 1 : 0;
     int rc_ = sync_ctx(e, s);
     if (rc_) return rc_;
     bool prof = e->prof_on && e->prof_used < e->prof_cap;
@@ -1345,22 +1315,20 @@ static int run_step(chub_env *e, int served, const float *d_actions, const doubl
     }
     // four events per profiled step: start / stop of the slot kernel, start / stop of the tail kernel
     hipEvent_t *pe = prof ? &e->prof_events[4 * e->prof_used] : nullptr;
-    const bool small_step = e->compat_small && !load_mode && !e->per_env;
-    sa.empt_fresh = ((small_step || e->hp.compat_split) && (!e->empt_valid || e->capturing)) ? 1 : 0;
-    if (small_step) {
-        launch_compat_small(false, e->hp, e->d_ctx, sa, s, packed_ptrs(e));
+    sa.empt_fresh = ((cp.call == CALL_COMPAT_SMALL || e->hp.compat_split) && (!e->empt_valid || e->capturing)) ? 1 : 0;
+    if (cp.call == CALL_COMPAT_SMALL) {
+        launch_compat_small<false>(e->hp, e->d_ctx, sa, s, packed_ptrs(e));
         e->empt_valid = true;
         if (prof) {  // one kernel, no dispatch timestamps: the sample spans nothing
             for (int i = 0; i < 4; i++) HIP_TRY(hipEventRecord(pe[i], s));
         }
-    } else if (e->fused && !load_mode && !e->per_env && ((!sa.car_tape && !sa.pk_tape) || (sa.car_tape && sa.pk_tape && sa.tail_tape))) {
-        // (tape mode: the one-launch form replays only a complete tape -- station draws, car variates and the tail's variates)
-        launch_step_fused(e->hp, e->d_ctx, sa, s, packed_ptrs(e), prof ? pe[0] : nullptr, prof ? pe[1] : nullptr);
+    } else if (cp.call == CALL_ONE_LAUNCH) {
+        launch_step_fused(cp, e->hp, e->d_ctx, sa, s, packed_ptrs(e), prof ? pe[0] : nullptr, prof ? pe[1] : nullptr);
         if (prof) {  // one kernel: the whole step is on the first pair of timestamps, the second pair spans nothing
             HIP_TRY(hipEventRecord(pe[2], s));
             HIP_TRY(hipEventRecord(pe[3], s));
         }
-    } else if (split_step && served == 2 && !e->per_env && !load_mode && !e->capturing && walks_two_ahead(e)) {
+    } else if (cp.call == CALL_SLOT_WALK2) {
         // lock-step COMPAT steps of every env, stations of 8 to 64 piles: the slot pass of this step beside the stream walks of the NEXT one
         // (k_slot_walk2: the walk two steps ahead of the slots it draws for), then the tails alone -- if the next call is that step, its walk
         // has run; if it is anything else, the walk's shadow is never committed
@@ -1369,17 +1337,17 @@ static int run_step(chub_env *e, int served, const float *d_actions, const doubl
         sw.t = (e->t + 1) % 96;
         sw.tick = sa.tick + 1u;
         sw.walk_far = 1;  // (reads the buffer behind the committed one -- this step's shadow -- and writes the one behind that)
-        launch_slot_walk2(e->hp, e->d_ctx, sa, sw, s, prof ? pe[0] : nullptr, prof ? pe[1] : nullptr);
+        launch_slot_walk2(e->plan, e->hp, e->d_ctx, sa, sw, s, prof ? pe[0] : nullptr, prof ? pe[1] : nullptr);
         sa.rng_cur = e->rng_cur = (e->rng_cur + 1) % 3;  // the commit of this step's draws: its walk's shadow is the streams' buffer now
-        launch_env(false, e->hp, e->d_ctx, sa, s, prof ? pe[2] : nullptr, prof ? pe[3] : nullptr, packed_ptrs(e));
+        launch_env<false>(cp.env, e->hp, e->d_ctx, sa, s, prof ? pe[2] : nullptr, prof ? pe[3] : nullptr, packed_ptrs(e));
         e->walked_tick = e->tick + 1u;
         e->empt_valid = true;
         e->e2_tick = e->tick;
     } else {
-        launch_slot(false, e->hp, e->d_ctx, sa, s, packed_ptrs(e), prof ? pe[0] : nullptr, prof ? pe[1] : nullptr);
+        launch_slot<false>(cp, e->hp, e->plan, e->d_ctx, sa, s, packed_ptrs(e), prof ? pe[0] : nullptr, prof ? pe[1] : nullptr);
         if (sa.commit_rng) sa.rng_cur = e->rng_cur = (e->rng_cur + 1) % 3;  // the commit (as above)
         if (split_step && served == 2 && !e->per_env && !e->capturing) e->e2_tick = e->tick;  // (every unit's empt2, whichever pass it was)
-        if (split_step && served == 2 && !e->per_env && !e->no_walk_ahead) {
+        if (cp.call == CALL_SLOT_ENV_WALK) {
             // lock-step COMPAT steps of every env: the tails of this step and the stream walks of the NEXT one in one launch (k_env_walk) --
             // if the next call is that step, its walk has run; if it is anything else, the walk's shadow is never committed
             StepArgs sw = sa;  // (rng_cur: the buffer this step's slot pass has just made the committed one)
@@ -1388,7 +1356,7 @@ static int run_step(chub_env *e, int served, const float *d_actions, const doubl
             launch_env_walk(e->hp, e->d_ctx, sa, sw, s, prof ? pe[2] : nullptr, prof ? pe[3] : nullptr, packed_ptrs(e));
             e->walked_tick = e->tick + 1u;
         } else {
-            launch_env(false, e->hp, e->d_ctx, sa, s, prof ? pe[2] : nullptr, prof ? pe[3] : nullptr, packed_ptrs(e));
+            launch_env<false>(cp.env, e->hp, e->d_ctx, sa, s, prof ? pe[2] : nullptr, prof ? pe[3] : nullptr, packed_ptrs(e));
         }
         e->empt_valid = e->hp.compat_split != 0 && !e->capturing;  // (counted for every unit in front of the walk, or good already; the pass left the served units')
     }
@@ -2516,7 +2484,10 @@ int chub_compat_replay_constructor(chub_env *e) {
     sa.env_hi = (int32_t) (e->hp.n_envs - 1);
     sa.commit_rng = e->hp.compat_split;  // (the split form's walk leaves the streams' state in the shadow buffer: the commit moves rng_cur on)
     sa.rng_cur = e->rng_cur;
-    launch_slot(true, e->hp, e->d_ctx, sa, nullptr, packed_ptrs(e), nullptr, nullptr);
+    CallState c = {};
+    c.reset = c.all_served = true;
+    const CallPlan cp = {CALL_SLOT_ENV, ONE_NONE, slot_form(e->plan, c), LEVELS_NONE, ENV_COMPAT};
+    launch_slot<true>(cp, e->hp, e->plan, e->d_ctx, sa, nullptr, packed_ptrs(e), nullptr, nullptr);
     if (sa.commit_rng) e->rng_cur = (e->rng_cur + 1) % 3;
     e->empt_valid = e->hp.compat_split != 0;
     e->e2_tick = ~0u;  // (no pass has left empt2 for a walk two steps ahead: the first step counts for itself)

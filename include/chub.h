@@ -156,6 +156,31 @@ int chub_uses_packed_kernel(const chub_env *env); /* 1: PHILOX steps of this han
 int chub_uses_fused_step(const chub_env *env);    /* 1: its lock-step steps run as one launch (k_step_tailwave / k_step_fused / k_compat_small, small batches) */
 int chub_uses_xcd_order(const chub_env *env);     /* 1: its packed kernels' workgroups take their work in XCD-aware order (chub_options.work_order) */
 
+/* The launch forms chub_create_ex would choose for this hub shape, batch, RNG mode and options, without a device: out[CHUB_PLAN_COUNT], one
+ * value per CHUB_PLAN_* index.  Returns what chub_create_ex returns for arguments and combinations it refuses (same code, same message). */
+int chub_launch_plan(const chub_config *cfg, int64_t n_envs, int rng_mode, const chub_options *opt /* NULL = defaults */, int32_t *out);
+enum {
+    CHUB_PLAN_PACKED = 0,     /* PHILOX steps on k_slot_packed: 0 no, 1 small tile, 2 small tile with stations of more than 64 piles, 3 large tile, 4 large tile
+                                 with stations of more than 64 piles */
+    CHUB_PLAN_BIG_TILE,       /* 1: the packed kernel's large tile */
+    CHUB_PLAN_PBLOCK,         /* ... its workgroup size */
+    CHUB_PLAN_PSLOTS,         /* ... and slots per lane */
+    CHUB_PLAN_EPB,            /* whole envs per packed workgroup */
+    CHUB_PLAN_XCD,            /* 1: XCD-aware work order (what the kernels read; chub_uses_xcd_order: not where the step is one launch) */
+    CHUB_PLAN_ONE_LAUNCH,     /* lock-step steps as one launch: 0 no, 1 k_step_fused, 2 k_step_tailwave */
+    CHUB_PLAN_SPAN_SIZE_OK,   /* 1: chub_run_steps's spans of steps in one launch are allowed by size */
+    CHUB_PLAN_SPAN_PIPED,     /* ... as k_steps_piped (1) or k_steps_fused (0) */
+    CHUB_PLAN_SPAN_STEPS,     /* chub_options.span_steps */
+    CHUB_PLAN_COMPAT_SMALL,   /* 1: COMPAT lock-step resets and steps as one launch (k_compat_small) */
+    CHUB_PLAN_COMPAT,         /* COMPAT's other resets and steps: 0 (PHILOX), 1 one kernel per station, 2 the split form, 3 the split form walking two steps
+                                 ahead (k_slot_walk2, 32 envs per walk workgroup), 4 the same with 64 */
+    CHUB_PLAN_SPLIT2,         /* 1: the split form's steps take two slots per lane (k_slot_split2) */
+    CHUB_PLAN_WALK_AHEAD,     /* 1: lock-step split steps walk the next step's streams ahead (chub_options.walk_ahead) */
+    CHUB_PLAN_STATION0,       /* station 0's slot kernel where the packed one is not used: 0 k_slot, 1 k_slot_unit, 2 k_slot_unit_any, 3 k_slot_curves */
+    CHUB_PLAN_STATION1,
+    CHUB_PLAN_COUNT
+};
+
 /* ---- hot path ------------------------------------------------------------------------------
  * chub_reset replaces EvcsspManagerEnv_v6.reset (MGR:304-316 -> AGG:157-175 evs_reset main.cpp:199,251,
  * HYD:197-208, REN:51-53).  chub_step replaces EvcsspManagerEnv_v6.step (MGR:136-302 -> AGG:116-155
