@@ -47,6 +47,15 @@ class ChubConfig(C.Structure):
                 ("price_fluctuate", C.c_double), ("hydro_loss", C.c_double)]
 
 
+# the eight scalar constructor kwargs that may differ from env to env (chub_env_params, chub_create_params)
+ENV_PARAM_FIELDS = ("hydro_prod_rate", "hydro_store_vlt", "init_soc", "fc_max_power", "fcev_permeate", "renew_fluctuate", "price_fluctuate",
+                    "hydro_loss")
+
+
+class ChubEnvParams(C.Structure):
+    _fields_ = [(name, C.c_double) for name in ENV_PARAM_FIELDS]
+
+
 def lib_path():
     """libchub.so next to this file; CHUB_LIB names another build of it (compiler-flag experiments)"""
     return os.environ.get("CHUB_LIB") or os.path.join(_HERE, "libchub.so")
@@ -90,6 +99,9 @@ def load_library():
         "chub_destroy": (I, [P]),
         "chub_obs_dim": (I, [P]), "chub_act_dim": (I, [P]), "chub_num_envs": (L, [P]), "chub_clock": (I, [P]), "chub_uses_packed_kernel": (I, [P]), "chub_uses_fused_step": (I, [P]), "chub_uses_xcd_order": (I, [P]),
         "chub_launch_plan": (I, [C.POINTER(ChubConfig), L, I, C.POINTER(ChubOptions), P]),
+        "chub_launch_plan_params": (I, [C.POINTER(ChubConfig), L, I, C.POINTER(ChubOptions), P]),
+        "chub_create_params": (I, [C.POINTER(ChubConfig), C.c_char_p, L, L, I, C.c_uint64, I, C.POINTER(ChubOptions), P, C.POINTER(P)]),
+        "chub_set_env_params": (I, [P, P, P]), "chub_get_env_params": (I, [P, P]), "chub_has_env_params": (I, [P]),
         "chub_reset": (I, [P, P, P, P]),
         "chub_step": (I, [P, P, P, P, P, P]), "chub_host_actions": (I, [P, C.POINTER(P)]),
         "chub_step_bits": (I, [P, P, P, P, P, P, P]), "chub_host_bits": (I, [P, C.POINTER(P), C.POINTER(P)]),
@@ -144,7 +156,8 @@ def load_library():
     return lib
 
 
-EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "chub_act_dim", "chub_num_envs", "chub_clock", "chub_uses_packed_kernel", "chub_uses_fused_step", "chub_uses_xcd_order", "chub_launch_plan", "chub_reset",
+EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "chub_act_dim", "chub_num_envs", "chub_clock", "chub_uses_packed_kernel", "chub_uses_fused_step", "chub_uses_xcd_order", "chub_launch_plan", "chub_launch_plan_params",
+            "chub_create_params", "chub_set_env_params", "chub_get_env_params", "chub_has_env_params", "chub_reset",
             "chub_step", "chub_host_actions", "chub_step_bits", "chub_host_bits", "chub_step_bits_device", "chub_step_bits_device_packed", "chub_reset_device", "chub_step_device", "chub_step_device_packed", "chub_step_load", "chub_step_load_device", "chub_step_load_envs", "chub_step_load_envs_device", "chub_reset_envs", "chub_step_envs", "chub_reset_envs_device", "chub_step_envs_device",
             "chub_env_clocks", "chub_clock_groups", "chub_random_actions_device", "chub_sync", "chub_profile_begin", "chub_profile_end",
             "chub_get_slots", "chub_get_station_scalars", "chub_get_telemetry", "chub_get_obs_f64",

@@ -135,8 +135,9 @@ struct EnvArrays {           // index = env (or field*N + env)
                                  // HYD:270-276) and its entries are folded into q_fold / q_fold_cnt
     CHUB_G(double) q_fold;       // [N][2] folded list: sum of its times, sum of its masses, in the reference's left-to-right order
     CHUB_G(uint32_t) q_fold_cnt; // [N]    folded list: number of entries
-    CHUB_G(double) hy_env;       // [N][102] COMPAT only: per-env hy_power_speed_list (the reference builds it with live random
-                                 // FCEV demand at construction, HYD:154-157, so it depends on the env's streams)
+    CHUB_G(double) hy_env;       // [N][102] COMPAT: per-env hy_power_speed_list (the reference builds it with live random
+                                 // FCEV demand at construction, HYD:154-157, so it depends on the env's streams); PHILOX handles
+                                 // with per-env parameters (EnvParamArrays): each env's zero-demand table
     CHUB_G(uint32_t) drw[2];     // [N][4] PHILOX: a step's state-independent env draws, made one launch ahead (double-buffered by
                                  // tick parity): three OU normals (f32 bits: pv, wind, price) and the first FCEV arrival's SoC (f32 bits)
     CHUB_G(uint8_t) drw_cnt[2];  // [N]    ... and the FCEV arrival count
@@ -220,6 +221,18 @@ struct HubParams {
     int32_t soc_curves;      // CHUB_RNG_PHILOX_CURVES: a PHILOX handle (rng_mode) whose slots run k_slot_curves (continuous arrival SoC, curves on the device)
 };
 
+// Per-env hub parameters (chub_create_params): the HubParams constants that follow from the eight scalar constructor kwargs, one
+// value per env, derived by the same host code (derive_env_consts in chub_runtime.cpp).  Null on a homogeneous handle.
+enum EnvPrm {
+    PRM_V_H_MAX = 0, PRM_CELLS, PRM_RC_CELLS, PRM_CAP_MASS, PRM_RC_CAP_MASS, PRM_INIT_SOC, PRM_HYDRO_LOSS, PRM_FC_MAX_POWER,
+    PRM_RENEW_FLUCT1, PRM_PRICE_FLUCT1, PRM_COUNT
+};
+struct EnvParamArrays {
+    CHUB_G(const double) prm;        // [PRM_COUNT][N] f64, field-major
+    CHUB_G(const float) hv_rate;     // [N] f32(f32(0.3) * f32(permeate)) (the permeate > 1 -> 0.01 quirk applied)
+    CHUB_G(const uint16_t) hv_idx;   // [96][1000] the arrival index n[t][level] behind Tables::cnt_hv: arrivals = clamp(roundf(hv_rate * n), 0, 255)
+};
+
 // Everything a kernel needs that does not change from step to step, kept in device memory and passed by pointer
 // (as by-value kernel arguments these ~600 bytes were all loaded into SGPRs up front and spilled).
 struct DevCtx {
@@ -229,6 +242,7 @@ struct DevCtx {
     EnvArrays ev;
     CompatRng cr;
     Tables tb;
+    EnvParamArrays ep;  // (last: the offsets of everything above stay those of a homogeneous handle's kernels)
 };
 
 // host-side copies of the device pointers the packed slot kernel takes as kernel arguments (launch_slot)

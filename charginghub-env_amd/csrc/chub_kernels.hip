@@ -3085,7 +3085,16 @@ struct NoMid {
 // TAPE (the parity instrument of include/chub.h, PHILOX handles): the tail's variates come from the caller -- the exogenous normals
 // (sa.exo_z, f64 as the reference's numpy drew them), a reset's days (sa.exo_days), the forecourt's arrivals and their SoCs (sa.hv_tape) --
 // and everything else is the production tail, instruction for instruction.
-template <bool RESET, int MODE, bool MULTI, bool FUSED = false, typename Mid = NoMid, int EB = kEnvBlock, bool TAPE = false>
+// FCEV arrivals of env e at slot of day t and level `lev` on a handle with per-env hub parameters: the host's expression behind Tables::cnt_hv
+// (chub_create_ex) with the env's own rate -- the same f32 product and rounding, so the count is bit for bit the per-handle table's
+__device__ __forceinline__ uint32_t hv_count_env(const EnvParamArrays &ep, uint32_t e, int t, uint32_t lev) {
+    const int c = (int) roundf(ep.hv_rate[e] * (float) ep.hv_idx[(uint32_t) t * (uint32_t) kLevels + lev]);
+    return (uint32_t) (c < 0 ? 0 : (c > 255 ? 255 : c));
+}
+
+// EP (ENV_PARAMS, handles made by chub_create_params): the hydrogen, fuel-cell, fluctuation and FCEV constants are the env's own (DevCtx::ep, read
+// in the first load burst) and the electrolyser table is the env's row of EnvArrays::hy_env instead of the block's LDS copy
+template <bool RESET, int MODE, bool MULTI, bool FUSED = false, typename Mid = NoMid, int EB = kEnvBlock, bool TAPE = false, bool EP = false>
 __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const StepArgs &sa, const int env, const bool live,
                                          const double *s_pv, const double *s_wd, const double *s_pv_now, const double *s_wd_now,
                                          const double *s_hy, const uint8_t *s_hv, float *s_out, const int env_block, const TailArgs &ta,
@@ -3112,8 +3121,9 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
 #define TAB_WD(d) (multi ? tb.wdT[t_next * 150 + (d)] : s_wd[d])
 #define TAB_PV_NOW(d) (multi ? tb.pvT[t_now * 100 + (d)] : s_pv_now[d])
 #define TAB_WD_NOW(d) (multi ? tb.wdT[t_now * 150 + (d)] : s_wd_now[d])
-#define TAB_HY(i) (MODE == MODE_COMPAT ? hy_env[i] : s_hy[i])
-#define TAB_HV(l) (multi ? tb.cnt_hv[(uint32_t) t_now * (uint32_t) kLevels + (uint32_t) (l)] : s_hv[l])
+#define TAB_HY(i) ((MODE == MODE_COMPAT || EP) ? hy_env[i] : s_hy[i])
+#define HP_E(field, own) (EP ? (own) : hp.field)  // a hub constant: the handle's, or (EP) the env's
+#define TAB_HV(l) (EP ? hv_count_env(ctx->ep, e32, t_now, (uint32_t) (l)) : multi ? tb.cnt_hv[(uint32_t) t_now * (uint32_t) kLevels + (uint32_t) (l)] : s_hv[l])
     // ---- prefetch: every per-env input is requested before the table staging and its barrier, and the PHILOX
     // words that do not depend on state (FCEV arrival level, the three OU normals) are drawn here too, so the
     // memory latencies of this latency-bound kernel overlap instead of queueing behind one another.
@@ -3145,10 +3155,10 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
             }
         }
         if (!RESET) {
-            if (i < 102) st_hy = ta.hy_table[i];
+            if (!EP && i < 102) st_hy = ta.hy_table[i];
             // (the split step's tail does not look the forecourt's arrivals up -- the walk did: no table row, and no hop through the context
             // pointer for its address in front of the per-env loads)
-            if (MODE == MODE_COMPAT && !multi && !sa.hv_tape && i < kLevels / 4) st_hv = ((CHUB_G(const uint32_t)) tb.cnt_hv)[sa.t * (kLevels / 4) + i];
+            if (MODE == MODE_COMPAT && !EP && !multi && !sa.hv_tape && i < kLevels / 4) st_hv = ((CHUB_G(const uint32_t)) tb.cnt_hv)[sa.t * (kLevels / 4) + i];
         }
     }
     // The device-side tick offset of graph replays is a scalar load from DEVICE memory (a miss in the scalar cache of every CU at the start of a
@@ -3165,7 +3175,25 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
     u32x4 drw_raw = {0u, 0u, 0u, 0u};
     uint32_t drw_n = 0u, hvw0 = 0u, hvw1 = 0u;
     const bool have_pre = FUSED && use_pre;  // the env's own state came in ahead of time (tail_prefetch)
+    double p_v_h_max = 0.0, p_cells = 0.0, p_rc_cells = 0.0, p_cap_mass = 0.0, p_rc_cap_mass = 0.0, p_init_soc = 0.0, p_hydro_loss = 0.0;
+    double p_fc_max_power = 0.0, p_renew_fluct1 = 0.0, p_price_fluct1 = 0.0;
     if (live) {
+        if (EP) {  // the env's own constants, with its state
+            CHUB_G(const double) pr = ctx->ep.prm;
+            p_cap_mass = pr[PRM_CAP_MASS * n32 + e32];
+            p_renew_fluct1 = pr[PRM_RENEW_FLUCT1 * n32 + e32];
+            p_price_fluct1 = pr[PRM_PRICE_FLUCT1 * n32 + e32];
+            if (RESET) {
+                p_init_soc = pr[PRM_INIT_SOC * n32 + e32];
+            } else {
+                p_v_h_max = pr[PRM_V_H_MAX * n32 + e32];
+                p_cells = pr[PRM_CELLS * n32 + e32];
+                p_rc_cells = pr[PRM_RC_CELLS * n32 + e32];
+                p_rc_cap_mass = pr[PRM_RC_CAP_MASS * n32 + e32];
+                p_hydro_loss = pr[PRM_HYDRO_LOSS * n32 + e32];
+                p_fc_max_power = pr[PRM_FC_MAX_POWER * n32 + e32];
+            }
+        }
         if (have_pre) {
             ou_pv = pre.ou_pv; ou_wd = pre.ou_wd; ou_price = pre.ou_price; in_price_noise = pre.price_noise;
         } else {
@@ -3226,7 +3254,8 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
             if (!RESET) {
                 // the FCEV arrival level is state-independent: look its count up now, one byte straight from the table
                 hv_lev = (int) (px.block(SITE_HV, 0, 0).v[0] % 1000u);
-                hv_arrive = (int) tb.cnt_hv[(uint32_t) t_now * (uint32_t) kLevels + (uint32_t) hv_lev];
+                hv_arrive = EP ? (int) hv_count_env(ctx->ep, e32, t_now, (uint32_t) hv_lev)
+                               : (int) tb.cnt_hv[(uint32_t) t_now * (uint32_t) kLevels + (uint32_t) hv_lev];
             }
         } else {
             z_pv = sa.exo_z[e32 * 3u + 0u];
@@ -3251,8 +3280,8 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
         if (!RESET) {
             if (i < 100) ((double *) s_pv_now)[i] = st_pv_now;
             if (i < 150) ((double *) s_wd_now)[i] = st_wd_now;
-            if (i < 102) ((double *) s_hy)[i] = st_hy;
-            if (MODE == MODE_COMPAT && i < kLevels / 4) ((uint32_t *) s_hv)[i] = st_hv;
+            if (!EP && i < 102) ((double *) s_hy)[i] = st_hy;
+            if (MODE == MODE_COMPAT && !EP && i < kLevels / 4) ((uint32_t *) s_hv)[i] = st_hv;
         }
         __syncthreads();
     }
@@ -3304,17 +3333,17 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
         }
     };
     // what the first half hands to the second
-    const double *hy_env = MODE == MODE_COMPAT ? (const double *) ev.hy_env + (size_t) e32 * 102u : nullptr;
+    const double *hy_env = (MODE == MODE_COMPAT || EP) ? (const double *) ev.hy_env + (size_t) e32 * 102u : nullptr;
     (void) hy_env;
     // COMPAT: the env's own hy_power_speed_list entry the electrolyser clamp looks at first (MGR:160-180; its index follows from the action
     // alone) is requested HERE, in front of the first half, instead of as a round trip of its own in the second
     double hy_req_pre = 0.0;
-    if (MODE == MODE_COMPAT && !RESET && live) {
+    if ((MODE == MODE_COMPAT || EP) && !RESET && live) {
         int rq = (int) ceil((((double) a_el_f + 1) / 2) * 100);
         rq = rq < 0 ? 0 : (rq > 101 ? 101 : rq);
         hy_req_pre = hy_env[rq];
     }
-    const double cap_mass = hp.cap_mass;
+    const double cap_mass = HP_E(cap_mass, p_cap_mass);
     double store_soc = 0.0, reward = 0.0, in_re_pv = 0.0, in_re_wd = 0.0, in_price_next = 0.0, total_mass_need = 0.0;
     double re_pv = 0.0, re_wd = 0.0, price_next = 0.0;
     int arrive = 0;
@@ -3344,8 +3373,8 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
         ev.wd_day[e32] = (int16_t) wd_day;
         ev.q_len[e32] = 0;
         ev.hv_line[e32] = 0;
-        cap = hp.init_soc * cap_mass;
-        store_soc = hp.init_soc;
+        cap = HP_E(init_soc, p_init_soc) * cap_mass;
+        store_soc = HP_E(init_soc, p_init_soc);
         CHUB_TEL(4, cap);
     } else {
         // What the previous make_state (MGR:344-361: the end of the previous step, or reset) produced for THIS slot is not kept as
@@ -3353,10 +3382,10 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
         // the OU states as that make_state left them (the values loaded above), the price noise and the tariff it saw last.
         {
             double tp = TAB_PV_NOW(pv_day);
-            if (tp > 0 && (pv_day % 2) == 0) tp += ou_pv * hp.renew_fluct1;  // REN:38-43
+            if (tp > 0 && (pv_day % 2) == 0) tp += ou_pv * HP_E(renew_fluct1, p_renew_fluct1);  // REN:38-43
             in_re_pv = (tp > 0 ? tp : 0.0) * 5;
             double tw = TAB_WD_NOW(wd_day);
-            tw += ou_wd * hp.renew_fluct1;                                    // REN:45-49
+            tw += ou_wd * HP_E(renew_fluct1, p_renew_fluct1);                 // REN:45-49
             in_re_wd = (tw > 0 ? tw : 0.0) * 1;
         }
         in_price_next = price_prev + in_price_noise;            // MGR:354-359
@@ -3471,16 +3500,16 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
     {
         double temp = TAB_PV(pv_day);
         if (temp > 0 && (pv_day % 2) == 0) {  // REN:38-43
-            temp += ou_sample(ou_pv, .01, 1., z_pv) * hp.renew_fluct1;
+            temp += ou_sample(ou_pv, .01, 1., z_pv) * HP_E(renew_fluct1, p_renew_fluct1);
             ev.ou[e32] = ou_pv;
         }
         re_pv = (temp > 0 ? temp : 0.0) * 5;
         temp = TAB_WD(wd_day);
-        temp += ou_sample(ou_wd, .01, 1.5, z_wd) * hp.renew_fluct1;  // REN:45-49
+        temp += ou_sample(ou_wd, .01, 1.5, z_wd) * HP_E(renew_fluct1, p_renew_fluct1);  // REN:45-49
         ev.ou[n32 + e32] = ou_wd;
         re_wd = (temp > 0 ? temp : 0.0) * 1;
         if (draw_price) {  // MGR:354-357
-            price_next = ou_sample(ou_price, .1, 0.005, z_pr) * hp.price_fluct1;
+            price_next = ou_sample(ou_price, .1, 0.005, z_pr) * HP_E(price_fluct1, p_price_fluct1);
             ev.ou[2u * n32 + e32] = ou_price;
             ev.price_noise[e32] = price_next;
             price_next += price_last;
@@ -3515,7 +3544,7 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
         double act_el = a_el;
         int req = (int) ceil(a_el * 100);
         req = req < 0 ? 0 : (req > 101 ? 101 : req);  // actions outside [-1,1] would index out of the table
-        if ((MODE == MODE_COMPAT ? hy_req_pre : TAB_HY(req)) > hy_power_limit) {
+        if (((MODE == MODE_COMPAT || EP) ? hy_req_pre : TAB_HY(req)) > hy_power_limit) {
             int ind = 0;
             while (ind < 102 && !(TAB_HY(ind) >= hy_power_limit)) ind++;
             // hy_power_speed_list_input[ind - 1]; python index -1 wraps to the last entry (1.0)
@@ -3527,20 +3556,21 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
         must_chg = must_chg > 0 ? must_chg : 0.0;
         double upper_charge = cap_mass - cap;
         upper_charge = upper_charge > 0 ? upper_charge : 0.0;
-        double charge_temp = act_el * hp.v_h_max * (15 * 60);
+        const double v_h_max = HP_E(v_h_max, p_v_h_max), cells = HP_E(cells, p_cells);
+        double charge_temp = act_el * v_h_max * (15 * 60);
         charge_temp = charge_temp < upper_charge ? charge_temp : upper_charge;
         charge_temp = charge_temp > must_chg ? charge_temp : must_chg;
         double flow = DIV_K(charge_temp, 15 * 60);
-        flow = flow < hp.v_h_max ? flow : hp.v_h_max;
+        flow = flow < v_h_max ? flow : v_h_max;
         double ele_power = 0.0;
-        if (hp.cells != 0.0) {  // Electrolyser.get_power, HYD:38-48
-            const double v_H_mass = div_c(flow, hp.cells, hp.rc_cells);
+        if (cells != 0.0) {  // Electrolyser.get_power, HYD:38-48
+            const double v_H_mass = div_c(flow, cells, HP_E(rc_cells, p_rc_cells));
             const double v_H_mol = DIV_K(v_H_mass, 2.02);
             const double v_H_L = v_H_mol * hp.v_M;
             const double v_H = v_H_L * 1000 * 60;
             const double temp = div_c(v_H * 2 * 96487, hp.v_M * 1000 * 60, hp.rc_vm60k);
             double power = temp * temp * 0.326 + temp * 1.476;
-            ele_power = DIV_K(hp.cells * power, 1000);
+            ele_power = DIV_K(cells * power, 1000);
         }
         const double cpr_power = DIV_K(DIV_K(DIV_K(flow, 2.02) * hp.cpr_w12, 0.8), 1000);  // Compressor.generate_W, HYD:74-82
         // sty_step (HYD:104-126)
@@ -3550,8 +3580,8 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
         const double hy_use = total_mass_need < lower_change ? total_mass_need : lower_change;
         const double not_meet = total_mass_need - hy_use;
         cap -= hy_use;
-        cap -= cap * hp.hydro_loss;
-        store_soc = div_c(cap, cap_mass, hp.rc_cap_mass);
+        cap -= cap * HP_E(hydro_loss, p_hydro_loss);
+        store_soc = div_c(cap, cap_mass, HP_E(rc_cap_mass, p_rc_cap_mass));
         const double all_power_second = ele_power + cpr_power;
         const bool gen_hy = flow > 0.5;  // MGR:161,173-179
         mid.at2();
@@ -3582,8 +3612,9 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
         CHUB_TEL(11, e0);  // self.re_ev_power_list is taken before the fuel-cell rescale (MGR:212)
         CHUB_TEL(12, e1);
         // ---- fuel cell (MGR:215-227, HFC.use_cell HYD:409-430)
-        double fc_power = gen_hy ? 0.0 : hp.fc_max_power * a_fc;
-        if (fc_power > hp.fc_max_power) fc_power = hp.fc_max_power;
+        const double fc_max_power = HP_E(fc_max_power, p_fc_max_power);
+        double fc_power = gen_hy ? 0.0 : fc_max_power * a_fc;
+        if (fc_power > fc_max_power) fc_power = fc_max_power;
         else if (fc_power < 0) fc_power = 0.0;
         else if (fc_power > ev_power_sum) fc_power = ev_power_sum;
         double hy_to_use = DIV_K(fc_power * 1500, 119.6);
@@ -3692,10 +3723,11 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
 #undef TAB_WD_NOW
 #undef TAB_HY
 #undef TAB_HV
+#undef HP_E
 }
 
 // Next step's state-independent draws, lane u: [0, 2N) the station-level variates of unit u, [2N, 3N) the per-env draws
-template <bool RESET, bool MULTI>
+template <bool RESET, bool MULTI, bool EP = false>
 __device__ __forceinline__ void level_block(const DevCtx *__restrict__ ctx, const StepArgs &sa, const int64_t u, const int line_known = -1) {
     const HubParams &hp = ctx->hp;
     const int64_t N = hp.n_envs;
@@ -3721,14 +3753,14 @@ __device__ __forceinline__ void level_block(const DevCtx *__restrict__ ctx, cons
         d.x = __float_as_uint(normal_from_word(tb.normal_icdf, tb.normal_tail, ow.v[0]));
         d.y = __float_as_uint(normal_from_word(tb.normal_icdf, tb.normal_tail, ow.v[1]));
         d.z = __float_as_uint(normal_from_word(tb.normal_icdf, tb.normal_tail, ow.v[2]));
-        const uint32_t cnt = (uint32_t) tb.cnt_hv[(uint32_t) t_next * (uint32_t) kLevels + hv_lev];
+        const uint32_t cnt = EP ? hv_count_env(ctx->ep, e, t_next, hv_lev) : (uint32_t) tb.cnt_hv[(uint32_t) t_next * (uint32_t) kLevels + hv_lev];
         d.w = cnt != 0u ? __float_as_uint(soc_from_word(tb.soc_d_icdf, px.block(SITE_HVSOC, 0, 0).v[0])) : 0u;  // the first arrival's SoC
         ((CHUB_G(u32x4)) ctx->ev.drw[(sa.tick + 1u) & 1u])[e] = d;
         ctx->ev.drw_cnt[(sa.tick + 1u) & 1u][e] = (uint8_t) cnt;
     }
 }
 
-template <bool RESET, int MODE, bool MULTI, bool TAPE = false>
+template <bool RESET, int MODE, bool MULTI, bool TAPE = false, bool EP = false>
 __global__ __launch_bounds__(kEnvBlock) void k_env(const DevCtx *__restrict__ ctx, StepArgs sa, TailArgs ta, int nb_env) {
     __shared__ double s_pv[100], s_wd[150], s_pv_now[100], s_wd_now[150], s_hy[102];
     __shared__ __attribute__((aligned(16))) uint8_t s_hv[kLevels];
@@ -3755,7 +3787,7 @@ __global__ __launch_bounds__(kEnvBlock) void k_env(const DevCtx *__restrict__ ct
         } else {
             have = range_unit(sa, (int64_t) jb * kEnvBlock + threadIdx.x, 3, seg, env_);
         }
-        if (have) level_block<RESET, MULTI>(ctx, sa, (int64_t) seg * ctx->hp.n_envs + env_);
+        if (have) level_block<RESET, MULTI, EP>(ctx, sa, (int64_t) seg * ctx->hp.n_envs + env_);
 #if CHUB_TRACE
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         CHUB_STAMP_REAL(9);
@@ -3770,7 +3802,7 @@ __global__ __launch_bounds__(kEnvBlock) void k_env(const DevCtx *__restrict__ ct
     const int env = blk * kEnvBlock + (int) threadIdx.x;
     TailIn none;  // (the stand-alone tail loads its inputs itself)
     NoMid nomid;
-    env_tail<RESET, MODE, MULTI, false, NoMid, kEnvBlock, TAPE>(ctx, sa, env, env < (int) ta.n_envs && (!MULTI || in_group(sa, env)), s_pv, s_wd, s_pv_now,
+    env_tail<RESET, MODE, MULTI, false, NoMid, kEnvBlock, TAPE, EP>(ctx, sa, env, env < (int) ta.n_envs && (!MULTI || in_group(sa, env)), s_pv, s_wd, s_pv_now,
                                                                 s_wd_now, s_hy, s_hv, s_out, blk, ta, nullptr, 0, 0, 0, none, false, nomid);
 }
 
@@ -4339,26 +4371,33 @@ extern "C" int chub_debug_piped_stamps(unsigned long long *out) {
 // power at request 0.01 * i.  Then hy_reset().  One lane per env replays exactly that: the streams advance by what the
 // reference's constructor consumes and the table comes out as the reference's (it depends on the draws whenever a tank
 // clamp binds).  Same operations as the step's tail (env_tail), plain f64 divisions.
+// EP (handles with per-env hub parameters): the env's own constants and FCEV rate -- the reference's constructor with that env's kwargs.
+template <bool EP>
 __global__ void k_compat_ctor_sweep(const DevCtx *__restrict__ ctx, int rng_cur) {
     const HubParams &hp = ctx->hp;
     const EnvArrays &ev = ctx->ev;
     const Tables &tb = ctx->tb;
     const int64_t env = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (env >= hp.n_envs) return;
+    const uint32_t e32 = (uint32_t) env, n32 = (uint32_t) hp.n_envs;
+    (void) e32;
+    (void) n32;
+#define HP_E(field, f) (EP ? ctx->ep.prm[(f) * n32 + e32] : hp.field)
     CompatStream rs;
     rs.load(ctx->cr, rng_cur, env);
     const int qcap = hp.qcap;
     double *qt = (double *) ev.q_time + (size_t) env * (size_t) qcap, *qm = (double *) ev.q_mass + (size_t) env * (size_t) qcap;
     double *table = (double *) ev.hy_env + (size_t) env * 102u;
-    const double cap_mass = hp.cap_mass;
-    double cap = hp.init_soc * cap_mass;  // HyStore.__init__ (HYD:99-100)
+    const double cap_mass = HP_E(cap_mass, PRM_CAP_MASS);
+    double cap = HP_E(init_soc, PRM_INIT_SOC) * cap_mass;  // HyStore.__init__ (HYD:99-100)
+    const double v_h_max = HP_E(v_h_max, PRM_V_H_MAX), cells = HP_E(cells, PRM_CELLS), hydro_loss = HP_E(hydro_loss, PRM_HYDRO_LOSS);
     int q_len = 0;
     bool stuck = false;
     double fold_t = 0.0, fold_m = 0.0;
     for (int i = 0; i < 101; i++) {
         const int t = i % 96;  // sys_time (HYD:192-193)
         // hvs_step (HYD:253-285)
-        const int arrive = (int) tb.cnt_hv[t * kLevels + rs.level()];
+        const int arrive = EP ? (int) hv_count_env(ctx->ep, e32, t, (uint32_t) rs.level()) : (int) tb.cnt_hv[t * kLevels + rs.level()];
         double total_time = stuck ? fold_t : 0.0, total_mass = stuck ? fold_m : 0.0;
         for (int q = 0; q < q_len; q++) {
             total_time += qt[q];
@@ -4411,20 +4450,20 @@ __global__ void k_compat_ctor_sweep(const DevCtx *__restrict__ ctx, int rng_cur)
         must_chg = must_chg > 0 ? must_chg : 0.0;
         double upper_charge = cap_mass - cap;
         upper_charge = upper_charge > 0 ? upper_charge : 0.0;
-        double charge_temp = gen_speed * hp.v_h_max * (15 * 60);
+        double charge_temp = gen_speed * v_h_max * (15 * 60);
         charge_temp = charge_temp < upper_charge ? charge_temp : upper_charge;
         charge_temp = charge_temp > must_chg ? charge_temp : must_chg;
         double flow = charge_temp / (15 * 60);
-        flow = flow < hp.v_h_max ? flow : hp.v_h_max;
+        flow = flow < v_h_max ? flow : v_h_max;
         double ele_power = 0.0;
-        if (hp.cells != 0.0) {  // Electrolyser.get_power, HYD:38-48
-            const double v_H_mass = flow / hp.cells;
+        if (cells != 0.0) {  // Electrolyser.get_power, HYD:38-48
+            const double v_H_mass = flow / cells;
             const double v_H_mol = v_H_mass / 2.02;
             const double v_H_L = v_H_mol * hp.v_M;
             const double v_H = v_H_L * 1000 * 60;
             const double temp = v_H * 2 * 96487 / (hp.v_M * 1000 * 60);
             const double power = temp * temp * 0.326 + temp * 1.476;
-            ele_power = hp.cells * power / 1000;
+            ele_power = cells * power / 1000;
         }
         const double cpr_power = ((flow / 2.02) * hp.cpr_w12 / 0.8) / 1000;  // Compressor.generate_W, HYD:74-82
         // sty_step (HYD:104-126)
@@ -4433,16 +4472,18 @@ __global__ void k_compat_ctor_sweep(const DevCtx *__restrict__ ctx, int rng_cur)
         lower_change = lower_change > 0 ? lower_change : 0.0;
         const double hy_use = total_mass < lower_change ? total_mass : lower_change;
         cap -= hy_use;
-        cap -= cap * hp.hydro_loss;
+        cap -= cap * hydro_loss;
         table[i] = ele_power + cpr_power;
     }
     table[101] = table[100];
     rs.store(ctx->cr, rng_cur, env);
     // hy_reset (HYD:197-208): the step state is re-initialised by chub_reset; the FIFO arrays were scratch here
+#undef HP_E
 }
 
-void launch_compat_ctor_sweep(const HubParams &hp, const DevCtx *ctx, int rng_cur, hipStream_t stream) {
-    hipLaunchKernelGGL(k_compat_ctor_sweep, dim3((unsigned) ((hp.n_envs + 63) / 64)), dim3(64), 0, stream, ctx, rng_cur);
+void launch_compat_ctor_sweep(const HubParams &hp, const DevCtx *ctx, int rng_cur, hipStream_t stream, bool env_params) {
+    if (env_params) hipLaunchKernelGGL(k_compat_ctor_sweep<true>, dim3((unsigned) ((hp.n_envs + 63) / 64)), dim3(64), 0, stream, ctx, rng_cur);
+    else hipLaunchKernelGGL(k_compat_ctor_sweep<false>, dim3((unsigned) ((hp.n_envs + 63) / 64)), dim3(64), 0, stream, ctx, rng_cur);
 }
 
 // -------------------------------------------------------------------- random policy (bench / tests)
@@ -4848,6 +4889,18 @@ void launch_env(EnvForm f, const HubParams &hp, const DevCtx *ctx, const StepArg
         break;
     case ENV_COMPAT: CHUB_LAUNCH((k_env<RESET, MODE_COMPAT, false>), dim3((unsigned) nb_env), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env); break;
     case ENV_COMPAT_CLOCKS: CHUB_LAUNCH((k_env<RESET, MODE_COMPAT, true>), dim3((unsigned) nb_env), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env); break;
+    case ENV_PHILOX_PARAMS:  // per-env hub parameters (chub_create_params)
+        CHUB_LAUNCH((k_env<RESET, MODE_PHILOX, false, false, true>), dim3(nb), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env);
+        break;
+    case ENV_PHILOX_PARAMS_CLOCKS:
+        CHUB_LAUNCH((k_env<RESET, MODE_PHILOX, true, false, true>), dim3(nb), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env);
+        break;
+    case ENV_COMPAT_PARAMS:
+        CHUB_LAUNCH((k_env<RESET, MODE_COMPAT, false, false, true>), dim3((unsigned) nb_env), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env);
+        break;
+    case ENV_COMPAT_PARAMS_CLOCKS:
+        CHUB_LAUNCH((k_env<RESET, MODE_COMPAT, true, false, true>), dim3((unsigned) nb_env), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, nb_env);
+        break;
     }
 }
 template void launch_env<true>(EnvForm, const HubParams &, const DevCtx *, const StepArgs &, hipStream_t, hipEvent_t, hipEvent_t, const PackedPtrs &);

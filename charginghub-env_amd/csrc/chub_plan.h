@@ -173,6 +173,24 @@ inline int plan_handle(const chub_config *cfg, int64_t n_envs, int rng_mode, con
     return CHUB_OK;
 }
 
+// ... and what becomes of that plan on a handle with per-env hub parameters (chub_create_params).  The tail k_env<.., ENV_PARAMS> reads each
+// env's constants: the forms that carry a tail of their own (k_step_fused / k_step_tailwave, the spans of chub_run_steps, k_compat_small) are not
+// built for that, so such a handle runs the two-launch step whatever the options say.  COMPAT: one kernel per station, the unit's first lane
+// walking the streams and the tail drawing the forecourt, at every batch size (the split step's walks read the per-handle FCEV counts).
+inline int plan_params(LaunchPlan &p, int rng_mode, const char **msg) {
+    (void) msg;
+    if (rng_mode == CHUB_RNG_COMPAT) {
+        p.compat = COMPAT_STATIONS;
+        p.compat_small = 0;
+        p.split2 = 0;
+        p.walk_ahead = 0;
+    }
+    p.one_launch = ONE_NONE;
+    p.span_size_ok = 0;
+    p.span_piped = 0;
+    return CHUB_OK;
+}
+
 // ---- per call
 enum CallForm : int32_t {  // the kernel sequence of one reset / step
     CALL_COMPAT_SMALL,     // k_compat_small: both station passes and the tail
@@ -191,7 +209,8 @@ enum SlotForm : int32_t {  // what launch_slot runs
     SLOT_COMPAT_STATIONS   // COMPAT, one launch per station
 };
 enum LevelsForm : int32_t { LEVELS_NONE, LEVELS_DRAW, LEVELS_RESET };  // PHILOX station draws in front: k_draw_levels / k_reset_levels
-enum EnvForm : int32_t { ENV_PHILOX, ENV_PHILOX_CLOCKS, ENV_PHILOX_TAPE, ENV_COMPAT, ENV_COMPAT_CLOCKS };  // k_env: mode, per-env clocks, tail tape
+enum EnvForm : int32_t { ENV_PHILOX, ENV_PHILOX_CLOCKS, ENV_PHILOX_TAPE, ENV_COMPAT, ENV_COMPAT_CLOCKS,  // k_env: mode, per-env clocks, tail tape,
+                         ENV_PHILOX_PARAMS, ENV_PHILOX_PARAMS_CLOCKS, ENV_COMPAT_PARAMS, ENV_COMPAT_PARAMS_CLOCKS };  // per-env hub parameters
 
 struct CallState {
     bool reset, load_mode;
@@ -201,6 +220,7 @@ struct CallState {
     bool car_tape, pk_tape, tail_tape;
     bool bits;         // one bit per pile (chub_step_bits*)
     bool fresh;        // the call makes its own state-independent draws (StepArgs::fresh)
+    bool env_params;   // the handle has per-env hub parameters (plan_params)
 };
 struct CallPlan {
     CallForm call;
@@ -240,7 +260,9 @@ inline CallPlan plan_call(const LaunchPlan &p, const CallState &c) {
         return r;
     }
     r.slot = slot_form(p, c);
-    r.env = compat ? (c.per_env ? ENV_COMPAT_CLOCKS : ENV_COMPAT) : c.tail_tape ? ENV_PHILOX_TAPE : c.per_env ? ENV_PHILOX_CLOCKS : ENV_PHILOX;
+    r.env = compat ? (c.env_params ? (c.per_env ? ENV_COMPAT_PARAMS_CLOCKS : ENV_COMPAT_PARAMS) : c.per_env ? ENV_COMPAT_CLOCKS : ENV_COMPAT)
+          : c.tail_tape ? ENV_PHILOX_TAPE
+          : c.env_params ? (c.per_env ? ENV_PHILOX_PARAMS_CLOCKS : ENV_PHILOX_PARAMS) : c.per_env ? ENV_PHILOX_CLOCKS : ENV_PHILOX;
     // lock-step split steps of every env walk the next step's streams ahead: beside this step's slot pass (k_slot_walk2), or its tails
     const bool ahead = !c.reset && slot_form_split(r.slot) && c.all_served && !c.per_env;
     if (ahead && !c.load_mode && !c.capturing && (p.compat == COMPAT_WALK2_32 || p.compat == COMPAT_WALK2_64)) {

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -27,7 +28,7 @@ template <bool RESET>
 void launch_env(EnvForm f, const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
                 const PackedPtrs &pp);
 void launch_random_actions(const HubParams &hp, uint64_t key, uint32_t batch, float *d_actions, hipStream_t stream);
-void launch_compat_ctor_sweep(const HubParams &hp, const DevCtx *ctx, int rng_cur, hipStream_t stream);
+void launch_compat_ctor_sweep(const HubParams &hp, const DevCtx *ctx, int rng_cur, hipStream_t stream, bool env_params);
 void launch_tick_advance(uint32_t *tick_base, uint32_t by, hipStream_t stream);
 void launch_fill_clocks(uint16_t *dst, int64_t n, uint16_t value, hipStream_t stream);
 void launch_keep_clocks(uint16_t *dst, const uint16_t *src, int64_t n, hipStream_t stream);
@@ -51,6 +52,10 @@ static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) {
     g_err = msg;
     return code;
+}
+// an entry point that is not built for handles with per-env hub parameters (include/chub.h: chub_create_params)
+static int refuse_params(const char *what) {
+    return fail(CHUB_ERR_UNSUPPORTED, std::string(what) + " is not supported on a handle with per-env hub parameters (chub_create_params)");
 }
 // for the other translation units of the library (chub_comm.cpp); not part of the ABI
 extern "C" __attribute__((visibility("hidden"))) int chub_set_last_error_(int code, const char *msg) { return fail(code, msg); }
@@ -128,6 +133,12 @@ struct chub_env {
     double *d_telem = nullptr;
     int tape_classes;   // PHILOX tape mode: caller-registered arrival-SoC classes so far
     bool tape_stale = false;  // chub_tape_clear_soc since the last reset: the slots may hold cars of classes that are gone
+    // per-env hub parameters (chub_create_params): DevCtx::ep, EnvArrays::hy_env and the raw rows live in the arena (snapshots carry them)
+    bool env_params = false;
+    chub_env_params *d_rows = nullptr;  // [N] the rows as the caller gave them (chub_get_env_params)
+    int hv_max_arrive = 0;              // FCEV arrivals per step at most, over the rows at create: sizes qcap / hv_w (chub_set_env_params keeps below it)
+    int hv_top[96];                     // the largest arrival index of each slot of the day (what that bound is computed from)
+    EnvParamArrays ep = {nullptr, nullptr, nullptr};
     int public_mode = 0;     // the rng_mode the handle was created with: CHUB_RNG_PHILOX_CURVES is hp.rng_mode = PHILOX + hp.soc_curves
     bool tape_only = false;  // ... and once there are any, the handle's class rows are the caller's: only tape resets / steps may admit cars
     uint32_t h_late8[8];
@@ -269,6 +280,62 @@ static int pow2_ge(int v) {
     return p;
 }
 
+// The hub constants that follow from the eight scalar constructor kwargs (hydrogen system HYD:94-98, 144, 10-24, 57-72; fluctuations
+// REN:38-49, MGR:354-357): chub_create_ex derives the handle's with it, chub_create_params / chub_set_env_params each env's
+struct EnvConsts {
+    double v_h_max, cells, rc_cells, cap_mass, rc_cap_mass, init_soc, hydro_loss, fc_max_power, renew_fluct1, price_fluct1;
+    float hv_rate;  // f32(f32(0.3) * f32(permeate)), permeate > 1 -> 0.01 (the reference's quirk)
+};
+static double hub_v_M() { return 0.082 * (273 + 25) / 1; }
+static EnvConsts derive_env_consts(double hydro_prod_rate, double hydro_store_vlt, double init_soc, double fc_max_power, double fcev_permeate,
+                                   double renew_fluctuate, double price_fluctuate, double hydro_loss) {
+    EnvConsts k;
+    k.cap_mass = (0.089 * (200 / 1)) * (hydro_store_vlt * 1000);
+    k.v_h_max = 0.089 * hydro_prod_rate * 1000 / 3600;
+    k.init_soc = init_soc;
+    k.hydro_loss = hydro_loss;
+    k.fc_max_power = fc_max_power;
+    {
+        double v_H_L = (10.0 / 1000) / 60;
+        double v_H_mol = v_H_L / hub_v_M();
+        double v_H_mass = v_H_mol * 2.02;
+        k.cells = ceil(k.v_h_max / v_H_mass);
+    }
+    k.rc_cells = k.cells != 0.0 ? 1.0 / k.cells : 0.0;
+    k.rc_cap_mass = 1.0 / k.cap_mass;
+    k.renew_fluct1 = 1 + renew_fluctuate;
+    k.price_fluct1 = 1 + price_fluctuate;
+    float hv_pin = (float) 0.3, hv_perm = (float) fcev_permeate;
+    if (hv_perm > 1) hv_perm = (float) 0.01;
+    k.hv_rate = hv_pin * hv_perm;
+    return k;
+}
+static EnvConsts derive_env_consts(const chub_config &c) {
+    return derive_env_consts(c.hydro_prod_rate, c.hydro_store_vlt, c.init_soc, c.fc_max_power, c.fcev_permeate, c.renew_fluctuate, c.price_fluctuate,
+                             c.hydro_loss);
+}
+static EnvConsts derive_env_consts(const chub_env_params &r) {
+    return derive_env_consts(r.hydro_prod_rate, r.hydro_store_vlt, r.init_soc, r.fc_max_power, r.fcev_permeate, r.renew_fluctuate, r.price_fluctuate,
+                             r.hydro_loss);
+}
+// what chub_create_ex refuses of its eight scalars (HYD:137); `where` names the env of a per-env row
+static int check_scalars(double init_soc, double hydro_prod_rate, double hydro_store_vlt, double fc_max_power, const std::string &where) {
+    if (!(init_soc >= 0.1 && init_soc <= 1)) return fail(CHUB_ERR_ARG, "init_soc must be in [0.1, 1]" + where);
+    if (!(hydro_prod_rate >= 0) || !(hydro_store_vlt > 0) || !(fc_max_power >= 0))
+        return fail(CHUB_ERR_ARG, "hydrogen system sizes must be non-negative" + where);
+    return CHUB_OK;
+}
+// FCEV arrivals per step at most for a rate: the largest count the arrival table can give (the table is built from the same expression)
+static int hv_bound(const int *hv_top, float hv_rate) {
+    int m = 0;
+    for (int t = 0; t < 96; t++) {
+        int c = (int) roundf(hv_rate * (float) hv_top[t]);
+        c = c < 0 ? 0 : (c > 255 ? 255 : c);
+        m = c > m ? c : m;
+    }
+    return m;
+}
+
 // HySystem.__init__ sweep (HYD:154-158) with zero FCEV demand: electrolyser + compressor power of the
 // flow each request level yields while the tank integrates it (see chub_set_hy_table in chub.h).
 static void build_hy_table(const HubParams &hp, double *table) {
@@ -349,7 +416,7 @@ static PackedPtrs packed_ptrs(const chub_env *e) {
 static int sync_ctx(chub_env *e, hipStream_t s) {
     if (!e->ctx_dirty) return 0;
     DevCtx h;
-    h.hp = e->hp; h.sl = e->sl; h.st = e->st; h.ev = e->ev; h.cr = e->cr; h.tb = e->tb;
+    h.hp = e->hp; h.sl = e->sl; h.st = e->st; h.ev = e->ev; h.cr = e->cr; h.tb = e->tb; h.ep = e->ep;
     HIP_TRY(hipStreamSynchronize(s));
     HIP_TRY(hipMemcpy(e->d_ctx, &h, sizeof h, hipMemcpyHostToDevice));
     e->ctx_dirty = false;
@@ -381,31 +448,61 @@ int chub_device_info(int device, int32_t *out4) {
     return CHUB_OK;
 }
 
+static int write_env_params(chub_env *e, const uint8_t *mask, const chub_env_params *rows);
+static int create_impl(const chub_config *cfg_in, const char *data_dir, int64_t n_envs, int64_t env_id0, int device, uint64_t seed, int rng_mode,
+                       const chub_options *opt_in, const chub_env_params *rows, chub_env **out);
+
 int chub_create(const chub_config *cfg, const char *data_dir, int64_t n_envs, int64_t env_id0, int device,
                 uint64_t seed, int rng_mode, chub_env **out) {
     return chub_create_ex(cfg, data_dir, n_envs, env_id0, device, seed, rng_mode, nullptr, out);
 }
-
 int chub_create_ex(const chub_config *cfg, const char *data_dir, int64_t n_envs, int64_t env_id0, int device,
-                   uint64_t seed, int rng_mode, const chub_options *opt_in, chub_env **out) {
-    if (!cfg || !data_dir || !out) return fail(CHUB_ERR_ARG, "null argument");
+                   uint64_t seed, int rng_mode, const chub_options *opt, chub_env **out) {
+    return create_impl(cfg, data_dir, n_envs, env_id0, device, seed, rng_mode, opt, nullptr, out);
+}
+int chub_create_params(const chub_config *cfg, const char *data_dir, int64_t n_envs, int64_t env_id0, int device, uint64_t seed, int rng_mode,
+                       const chub_options *opt, const chub_env_params *rows, chub_env **out) {
+    if (!rows) return fail(CHUB_ERR_ARG, "null argument");
+    return create_impl(cfg, data_dir, n_envs, env_id0, device, seed, rng_mode, opt, rows, out);
+}
+
+
+// chub_create_ex, and (rows != null) chub_create_params: the handle's scalar kwargs are then each env's row; cfg_in's are ignored
+static int create_impl(const chub_config *cfg_in, const char *data_dir, int64_t n_envs, int64_t env_id0, int device, uint64_t seed, int rng_mode,
+                       const chub_options *opt_in, const chub_env_params *rows, chub_env **out) {
+    if (!cfg_in || !data_dir || !out) return fail(CHUB_ERR_ARG, "null argument");
     chub_options opt;
     memset(&opt, 0, sizeof opt);
     if (opt_in) opt = *opt_in;
     *out = nullptr;
     LaunchPlan plan;
     const char *msg = nullptr;
-    if (const int rc = plan_handle(cfg, n_envs, rng_mode, opt, plan, &msg)) return fail(rc, msg);
+    if (const int rc = plan_handle(cfg_in, n_envs, rng_mode, opt, plan, &msg)) return fail(rc, msg);
+    if (rows)
+        if (const int rc = plan_params(plan, rng_mode, &msg)) return fail(rc, msg);
     // PHILOX_CURVES: PHILOX's draws and tail, the slots on k_slot_curves (chub_kernels.hip)
     const bool soc_curves = rng_mode == CHUB_RNG_PHILOX_CURVES;
     const int public_mode = rng_mode;
     if (soc_curves) rng_mode = CHUB_RNG_PHILOX;
-    if (!(cfg->init_soc >= 0.1 && cfg->init_soc <= 1)) return fail(CHUB_ERR_ARG, "init_soc must be in [0.1, 1]");  // HYD:137
-    if (!(cfg->hydro_prod_rate >= 0) || !(cfg->hydro_store_vlt > 0) || !(cfg->fc_max_power >= 0))
-        return fail(CHUB_ERR_ARG, "hydrogen system sizes must be non-negative");
+    // a handle with rows takes the handle-wide constants (tables it keeps but its tails do not read) from env 0's row
+    chub_config cfg_eff = *cfg_in;
+    if (rows) {
+        for (int64_t i = 0; i < n_envs; i++) {
+            const chub_env_params &r = rows[i];
+            if (const int rc = check_scalars(r.init_soc, r.hydro_prod_rate, r.hydro_store_vlt, r.fc_max_power, " (env " + std::to_string(i) + ")")) return rc;
+        }
+        const chub_env_params &r = rows[0];
+        cfg_eff.hydro_prod_rate = r.hydro_prod_rate; cfg_eff.hydro_store_vlt = r.hydro_store_vlt; cfg_eff.init_soc = r.init_soc;
+        cfg_eff.fc_max_power = r.fc_max_power; cfg_eff.fcev_permeate = r.fcev_permeate; cfg_eff.renew_fluctuate = r.renew_fluctuate;
+        cfg_eff.price_fluctuate = r.price_fluctuate; cfg_eff.hydro_loss = r.hydro_loss;
+    } else if (const int rc = check_scalars(cfg_in->init_soc, cfg_in->hydro_prod_rate, cfg_in->hydro_store_vlt, cfg_in->fc_max_power, "")) {
+        return rc;  // HYD:137
+    }
+    const chub_config *cfg = &cfg_eff;
 
     chub_env *e = new chub_env();
-    e->cfg = *cfg;
+    e->cfg = *cfg_in;
+    e->env_params = rows != nullptr;
     e->plan = plan;
     e->public_mode = public_mode;
     e->device = device;
@@ -474,19 +571,27 @@ int chub_create_ex(const chub_config *cfg, const char *data_dir, int64_t n_envs,
                     n = j;
                     break;
                 }
+            e->hv_top[t] = n;
             int c = (int) roundf(hv_pin * hv_perm * (float) n);
             c = c < 0 ? 0 : (c > 255 ? 255 : c);
             hv_max_arrive = c > hv_max_arrive ? c : hv_max_arrive;
         }
     }
     if (hv_max_arrive > 127) return bail(fail(CHUB_ERR_UNSUPPORTED, "more than 127 FCEV arrivals per step"));
+    for (int64_t i = 0; rows && i < n_envs; i++) {  // (rows: the largest bound of any env sizes the waiting list)
+        const int m = hv_bound(e->hv_top, derive_env_consts(rows[i]).hv_rate);
+        if (m > 127) return bail(fail(CHUB_ERR_UNSUPPORTED, "more than 127 FCEV arrivals per step (env " + std::to_string(i) + ")"));
+        hv_max_arrive = m > hv_max_arrive ? m : hv_max_arrive;
+    }
+    e->hv_max_arrive = hv_max_arrive;
     const int qcap = hv_max_arrive > 0 ? 2 * hv_max_arrive - 1 : 1;
 
     {   // arena: generous upper bound of everything allocated below (telemetry buffers come later, separately)
         const size_t S_tot = (size_t) (cfg->station_list[0] + cfg->station_list[1]);
         const size_t per_env = S_tot * (rng_mode == CHUB_RNG_COMPAT ? 88 : 40) + 1024 + (size_t) qcap * 16 +  // (COMPAT: 16 + 4 + 2 * 32 bytes per slot)
                                (rng_mode == CHUB_RNG_COMPAT ? 102 * 8 + 3 * 33 * 4 + 2 * 4 * (size_t) (1 + hv_max_arrive) + 1024 + 64 : 0);
-        const size_t want = (size_t) n_envs * per_env + ((size_t) 8 << 20) +
+        const size_t per_env_rows = rows ? (size_t) PRM_COUNT * 8 + 4 + sizeof(chub_env_params) + (rng_mode == CHUB_RNG_COMPAT ? 0 : 102 * 8) : 0;  // + 256-B rounding: the 8 MB below
+        const size_t want = (size_t) n_envs * (per_env + per_env_rows) + ((size_t) 8 << 20) + (rows ? (size_t) 96 * kLevels * 2 : 0) +
                             (rng_mode == CHUB_RNG_PHILOX ? 2 * ((size_t) kSocLevels + 2) * (kClsRow * 8 + 4) : 0);
         void *q = nullptr;
         if (!opt.no_arena && hipMalloc(&q, want) == hipSuccess) {
@@ -527,17 +632,15 @@ int chub_create_ex(const chub_config *cfg, const char *data_dir, int64_t n_envs,
     hp.key[1] = (uint32_t) (seed >> 32);
     hp.cc = make_curve_consts();
     // hydrogen system (HYD:94-98, 144, 10-24, 57-72)
-    hp.cap_mass = (0.089 * (200 / 1)) * (cfg->hydro_store_vlt * 1000);
-    hp.v_h_max = 0.089 * cfg->hydro_prod_rate * 1000 / 3600;
-    hp.init_soc = cfg->init_soc;
-    hp.hydro_loss = cfg->hydro_loss;
-    hp.fc_max_power = cfg->fc_max_power;
-    hp.v_M = 0.082 * (273 + 25) / 1;
+    const EnvConsts k0 = derive_env_consts(*cfg);
+    hp.cap_mass = k0.cap_mass;
+    hp.v_h_max = k0.v_h_max;
+    hp.init_soc = k0.init_soc;
+    hp.hydro_loss = k0.hydro_loss;
+    hp.fc_max_power = k0.fc_max_power;
+    hp.v_M = hub_v_M();
+    hp.cells = k0.cells;
     {
-        double v_H_L = (10.0 / 1000) / 60;
-        double v_H_mol = v_H_L / hp.v_M;
-        double v_H_mass = v_H_mol * 2.02;
-        hp.cells = ceil(hp.v_h_max / v_H_mass);
         double alpha = 1.4, R = 0.082, T = 273 + 25, P_in = 1, P_out = 200;
         double P_a = sqrt(P_in * P_out);
         double part1 = alpha / (alpha - 1);
@@ -547,15 +650,15 @@ int chub_create_ex(const chub_config *cfg, const char *data_dir, int64_t n_envs,
         double W_2 = part2 * (-1 + pow(P_out / P_a, part3));
         hp.cpr_w12 = W_1 + W_2;
     }
-    hp.rc_cells = hp.cells != 0.0 ? 1.0 / hp.cells : 0.0;
-    hp.rc_cap_mass = 1.0 / hp.cap_mass;
+    hp.rc_cells = k0.rc_cells;
+    hp.rc_cap_mass = k0.rc_cap_mass;
     hp.rc_vm60k = 1.0 / (hp.v_M * 1000 * 60);
     for (int k = 0; k < 2; k++) {
         const double half_range = (double) hp.transformer_limit[k] / 2;
         hp.rc_half_range[k] = half_range != 0.0 ? 1.0 / half_range : 0.0;
     }
-    hp.renew_fluct1 = 1 + cfg->renew_fluctuate;
-    hp.price_fluct1 = 1 + cfg->price_fluctuate;
+    hp.renew_fluct1 = k0.renew_fluct1;
+    hp.price_fluct1 = k0.price_fluct1;
     {
         double mean = np_sum96(e->price) / 96;
         double dev[96];
@@ -571,6 +674,7 @@ int chub_create_ex(const chub_config *cfg, const char *data_dir, int64_t n_envs,
     // arrival index per (slot of day, level): first j with CDF[t][j] >= u_k, else 300 (CHS.hpp:731-743),
     // then the per-station-type scaling + std::round (CHS.hpp:751-780, HYD:247-251)
     std::vector<uint8_t> cnt[2], cnt_hv(96 * kLevels);
+    std::vector<uint16_t> hv_idx(96 * kLevels);  // (per-env parameters: the index itself, each env scales it by its own rate on the device)
     cnt[0].resize(96 * kLevels);
     cnt[1].resize(96 * kLevels);
     float hv_pin = (float) 0.3, hv_perm = (float) cfg->fcev_permeate;
@@ -594,6 +698,7 @@ int chub_create_ex(const chub_config *cfg, const char *data_dir, int64_t n_envs,
             }
             int c = (int) roundf(hv_pin * hv_perm * (float) n);
             cnt_hv[t * kLevels + k] = (uint8_t) (c < 0 ? 0 : (c > 255 ? 255 : c));
+            hv_idx[t * kLevels + k] = (uint16_t) n;
         }
     }
     if (rng_mode == CHUB_RNG_PHILOX) {
@@ -811,9 +916,24 @@ int chub_create_ex(const chub_config *cfg, const char *data_dir, int64_t n_envs,
     e->ctx_dirty = true;
     ALLOC(e->d_actions, N * (size_t) hp.act_dim); ALLOC(e->d_obs, N * (size_t) hp.obs_dim); ALLOC(e->d_reward, N);
     ALLOC(e->d_done, N); ALLOC(e->d_exo_z, N * 3); ALLOC(e->d_exo_days, N * 2);
+    if (rows) {
+        double *prm = nullptr;
+        float *hv_rate = nullptr;
+        ALLOC(prm, (size_t) PRM_COUNT * N); ALLOC(hv_rate, N); ALLOC(e->d_rows, N);
+        if (!e->ev.hy_env) ALLOC(e->ev.hy_env, N * 102);  // (COMPAT has one already)
+        e->ep.prm = prm;
+        e->ep.hv_rate = hv_rate;
+        if ((rc = dev_upload(e, &e->ep.hv_idx, hv_idx))) return bail(rc);
+    }
 #undef ALLOC
+    if (rows && (rc = write_env_params(e, nullptr, rows))) return bail(rc);
     {   // tank starts at init_soc (HyStore.__init__, HYD:99-100)
         std::vector<double> cap(N, hp.init_soc * hp.cap_mass), soc(N, hp.init_soc);
+        for (size_t i = 0; rows && i < N; i++) {
+            const EnvConsts k = derive_env_consts(rows[i]);
+            cap[i] = k.init_soc * k.cap_mass;
+            soc[i] = k.init_soc;
+        }
         HIP_TRY(hipMemcpy(e->ev.cap, cap.data(), N * sizeof(double), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(e->ev.store_soc, soc.data(), N * sizeof(double), hipMemcpyHostToDevice));
     }
@@ -909,6 +1029,19 @@ int chub_launch_plan(const chub_config *cfg, int64_t n_envs, int rng_mode, const
     const char *msg = nullptr;
     if (const int rc = plan_handle(cfg, n_envs, rng_mode, opt, p, &msg)) return fail(rc, msg);
     memcpy(out, &p, sizeof p);  // (LaunchPlan is the CHUB_PLAN_* list: chub_plan.h)
+    return CHUB_OK;
+}
+
+int chub_launch_plan_params(const chub_config *cfg, int64_t n_envs, int rng_mode, const chub_options *opt_in, int32_t *out) {
+    if (!cfg || !out) return fail(CHUB_ERR_ARG, "null argument");
+    chub_options opt;
+    memset(&opt, 0, sizeof opt);
+    if (opt_in) opt = *opt_in;
+    LaunchPlan p;
+    const char *msg = nullptr;
+    if (const int rc = plan_handle(cfg, n_envs, rng_mode, opt, p, &msg)) return fail(rc, msg);
+    if (const int rc = plan_params(p, rng_mode, &msg)) return fail(rc, msg);
+    memcpy(out, &p, sizeof p);
     return CHUB_OK;
 }
 
@@ -1025,6 +1158,7 @@ static CallPlan plan_this_call(const chub_env *e, bool reset, int served, int lo
     c.tail_tape = e->tape_tail;
     c.bits = !reset && e->cur_bits;
     c.fresh = fresh;
+    c.env_params = e->env_params;
     return plan_call(e->plan, c);
 }
 
@@ -1379,6 +1513,7 @@ static int step_masked(chub_env *e, const uint8_t *mask, const float *d_actions,
     if (e->hp.rng_mode == CHUB_RNG_COMPAT && !d_exo_z) return fail(CHUB_ERR_ARG, "COMPAT mode needs exo_z");
     if (load_mode && e->hp.soc_curves)
         return fail(CHUB_ERR_UNSUPPORTED, "the scalar-load control (chub_step_load*) is not supported in rng_mode PHILOX_CURVES");
+    if (load_mode && e->env_params) return refuse_params("the scalar-load control (chub_step_load*)");
     HIP_TRY(hipSetDevice(e->device));
     (void) hipGetLastError();  // a stale error of an earlier, unrelated call must not be reported as this step's
     hipStream_t s = (hipStream_t) stream;
@@ -1929,6 +2064,7 @@ int chub_stream_sync(int device, void *stream) {
 // ---- tape mode (parity instrument, PHILOX handles): recorded decisions replayed through the production kernels -------
 int chub_tape_register_soc(chub_env *e, const float *soc, int32_t count, uint32_t *class_ids) {
     if (!e || !soc || !class_ids || count < 0) return fail(CHUB_ERR_ARG, "bad argument");
+    if (e->env_params) return refuse_params("tape mode (chub_tape_register_soc)");
     if (e->hp.rng_mode != CHUB_RNG_PHILOX) return fail(CHUB_ERR_ARG, "tape mode needs a PHILOX handle");
     if (e->hp.soc_curves)
         return fail(CHUB_ERR_UNSUPPORTED, "rng_mode PHILOX_CURVES has no classes: its car tape carries each arrival SoC itself (f32 bits in .x)");
@@ -2044,6 +2180,7 @@ int chub_step_tape(chub_env *e, const float *actions, const uint64_t *pk_tape, c
 int chub_step_tape_env(chub_env *e, const float *actions, const uint64_t *pk_tape, const uint32_t *car_tape, const double *exo_z,
                        const uint32_t *hv_tape, int32_t hv_w, float *obs, float *reward, uint8_t *done) {
     if (!e || !actions || !pk_tape || !car_tape || !obs || !reward || !done) return fail(CHUB_ERR_ARG, "null argument");
+    if (e->env_params) return refuse_params("tape mode (chub_step_tape / chub_step_tape_env)");
     if (e->hp.rng_mode != CHUB_RNG_PHILOX || !(e->hp.packed || e->hp.soc_curves))
         return fail(CHUB_ERR_ARG, "tape mode drives the packed PHILOX slot kernel: the hub shape must be one it covers");
     if ((exo_z != nullptr) != (hv_tape != nullptr) || (hv_tape && hv_w < 1)) return fail(CHUB_ERR_ARG, "the tail's tape is exo_z [N][3] AND hv_tape [N][hv_w >= 1]");
@@ -2116,6 +2253,7 @@ int chub_reset_tape(chub_env *e, const uint32_t *occ_tape, const uint32_t *car_t
 // (MGR:344-361) from the caller
 int chub_reset_tape_env(chub_env *e, const uint32_t *occ_tape, const uint32_t *car_tape, const int32_t *exo_days, const double *exo_z, float *obs) {
     if (!e || !occ_tape || !car_tape || !obs) return fail(CHUB_ERR_ARG, "null argument");
+    if (e->env_params) return refuse_params("tape mode (chub_reset_tape / chub_reset_tape_env)");
     if ((exo_days != nullptr) != (exo_z != nullptr)) return fail(CHUB_ERR_ARG, "the tail's tape of a reset is exo_days [N][2] AND exo_z [N][3]");
     if (exo_days)
         for (size_t i = 0; i < (size_t) e->hp.n_envs; i++)
@@ -2493,7 +2631,7 @@ int chub_compat_replay_constructor(chub_env *e) {
     e->e2_tick = ~0u;  // (no pass has left empt2 for a walk two steps ahead: the first step counts for itself)
     // (2) HySystem.__init__: 101 hy_step()s with live FCEV arrivals (HYD:154-157,168,250-259) -> the streams advance and
     //     every env gets the hy_power_speed_list the reference would have built from its draws
-    launch_compat_ctor_sweep(e->hp, e->d_ctx, e->rng_cur, nullptr);
+    launch_compat_ctor_sweep(e->hp, e->d_ctx, e->rng_cur, nullptr, e->env_params);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     return CHUB_OK;
@@ -2511,7 +2649,8 @@ struct SnapshotHeader {
     double hy_table[102];
     // per-env clocks (the clocks themselves are in the arena); the blob ends with every env's last tick
     int32_t predrawn, per_env;
-    int32_t rng_cur, pad_;  // COMPAT: which of the arena's three stream buffers holds the committed streams
+    int32_t rng_cur;  // COMPAT: which of the arena's three stream buffers holds the committed streams
+    int32_t pad_;     // 1: taken from a handle with per-env hub parameters (0 otherwise: a homogeneous handle's blob is unchanged)
 };
 static const uint64_t kSnapMagic = 0x43485542534e4150ull;  // "CHUBSNAP"
 
@@ -2544,6 +2683,7 @@ int chub_get_state(chub_env *e, void *buf, int64_t size) {
     h.predrawn = e->predrawn ? 1 : 0;
     h.per_env = e->per_env ? 1 : 0;
     h.rng_cur = e->rng_cur;
+    h.pad_ = e->env_params ? 1 : 0;  // (the rows themselves are in the arena)
     memcpy(buf, &h, sizeof h);
     HIP_TRY(hipMemcpy((char *) buf + sizeof h, e->arena, e->arena_used, hipMemcpyDeviceToHost));
     {
@@ -2566,6 +2706,9 @@ int chub_set_state(chub_env *e, const void *buf, int64_t size) {
     if (size < (int64_t) sizeof h) return fail(CHUB_ERR_ARG, "snapshot truncated");
     memcpy(&h, buf, sizeof h);
     if (h.magic != kSnapMagic) return fail(CHUB_ERR_ARG, "not a chub snapshot");
+    if ((h.pad_ != 0) != e->env_params)
+        return fail(CHUB_ERR_ARG, e->env_params ? "snapshot was taken from a handle without per-env hub parameters"
+                                                : "snapshot was taken from a handle with per-env hub parameters (chub_create_params)");
     if (h.n_envs != e->hp.n_envs || h.env_id0 != e->hp.env_id0 || h.rng_mode != e->public_mode ||
         memcmp(&h.cfg, &e->cfg, sizeof h.cfg) != 0 || h.arena_used != e->arena_used || size < need)
         return fail(CHUB_ERR_ARG, "snapshot was taken from a handle with a different configuration");
@@ -2621,6 +2764,7 @@ int chub_set_ou_state(chub_env *e, const double *ou) {
 
 int chub_get_hy_table(const chub_env *e, double *out102) {
     if (!e || !out102) return fail(CHUB_ERR_ARG, "null argument");
+    if (e->env_params) return refuse_params("chub_get_hy_table (one table for every env; chub_get_hy_table_env gives env i's)");
     memcpy(out102, e->hy_table, sizeof e->hy_table);
     return CHUB_OK;
 }
@@ -2637,6 +2781,7 @@ int chub_get_hy_table_env(chub_env *e, int64_t env_index, double *out102) {
 
 int chub_set_hy_table(chub_env *e, const double *in102) {
     if (!e || !in102) return fail(CHUB_ERR_ARG, "null argument");
+    if (e->env_params) return refuse_params("chub_set_hy_table (one table for every env)");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
     memcpy(e->hy_table, in102, sizeof e->hy_table);
@@ -2649,5 +2794,83 @@ int chub_set_hy_table(chub_env *e, const double *in102) {
     }
     return CHUB_OK;
 }
+
+// ---- per-env hub parameters (include/chub.h) ----------------------------------------------------------------------------------
+// Rows -> DevCtx::ep (the derived constants, field-major, and the FCEV rate), EnvArrays::hy_env (each env's zero-demand electrolyser table,
+// built on the host by build_hy_table: glibc's pow(temp, 2) is not always temp * temp, so a device copy of the sweep would not be the
+// homogeneous handle's table) and the raw rows.  Only the envs the mask names are written; a table is built once per distinct tank /
+// electrolyser setting among them.
+static int write_env_params(chub_env *e, const uint8_t *mask, const chub_env_params *rows) {
+    const size_t N = (size_t) e->hp.n_envs;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());  // (launches in flight read these arrays)
+    std::vector<double> prm((size_t) PRM_COUNT * N), hy(N * 102);
+    std::vector<float> rate(N);
+    std::vector<chub_env_params> raw(N);
+    if (mask) {  // the envs the mask does not name keep what they have
+        int rc;
+        if ((rc = fetch(prm, (const double *) e->ep.prm, prm.size())) || (rc = fetch(rate, (const float *) e->ep.hv_rate, N)) ||
+            (rc = fetch(hy, (const double *) e->ev.hy_env, hy.size())) || (rc = fetch(raw, (const chub_env_params *) e->d_rows, N)))
+            return rc;
+    }
+    std::map<std::string, size_t> built;  // (init_soc, hydro_store_vlt, hydro_prod_rate, hydro_loss) -> an env whose table holds that sweep
+    HubParams hq = e->hp;
+    for (size_t i = 0; i < N; i++) {
+        if (mask && !mask[i]) continue;
+        const chub_env_params &r = rows[i];
+        raw[i] = r;
+        const EnvConsts k = derive_env_consts(r);
+        const double v[PRM_COUNT] = {k.v_h_max, k.cells, k.rc_cells, k.cap_mass, k.rc_cap_mass, k.init_soc, k.hydro_loss, k.fc_max_power,
+                                     k.renew_fluct1, k.price_fluct1};
+        for (int f = 0; f < PRM_COUNT; f++) prm[(size_t) f * N + i] = v[f];
+        rate[i] = k.hv_rate;
+        const double key[4] = {r.init_soc, r.hydro_store_vlt, r.hydro_prod_rate, r.hydro_loss};
+        const std::string ks((const char *) key, sizeof key);
+        const auto it = built.find(ks);
+        if (it != built.end()) {
+            memcpy(&hy[i * 102], &hy[it->second * 102], 102 * sizeof(double));
+        } else {
+            hq.init_soc = k.init_soc; hq.cap_mass = k.cap_mass; hq.v_h_max = k.v_h_max; hq.cells = k.cells; hq.hydro_loss = k.hydro_loss;
+            build_hy_table(hq, &hy[i * 102]);
+            built.emplace(ks, i);
+        }
+    }
+    HIP_TRY(hipMemcpy((void *) e->ep.prm, prm.data(), prm.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy((void *) e->ep.hv_rate, rate.data(), N * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->ev.hy_env, hy.data(), hy.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_rows, raw.data(), N * sizeof(chub_env_params), hipMemcpyHostToDevice));
+    // the next step's FCEV counts were drawn one launch ahead with the old rates: the next launch draws its own
+    e->predrawn = false;
+    return CHUB_OK;
+}
+
+int chub_set_env_params(chub_env *e, const uint8_t *mask, const chub_env_params *rows) {
+    if (!e || !rows) return fail(CHUB_ERR_ARG, "null argument");
+    if (!e->env_params) return fail(CHUB_ERR_ARG, "the handle has no per-env hub parameters: create it with chub_create_params");
+    if (e->capturing) return fail(CHUB_ERR_ARG, "chub_set_env_params inside a capture (call it between replays)");
+    for (int64_t i = 0; i < e->hp.n_envs; i++) {
+        if (mask && !mask[i]) continue;
+        const chub_env_params &r = rows[i];
+        const std::string where = " (env " + std::to_string(i) + ")";
+        if (const int rc = check_scalars(r.init_soc, r.hydro_prod_rate, r.hydro_store_vlt, r.fc_max_power, where)) return rc;
+        const int m = hv_bound(e->hv_top, derive_env_consts(r).hv_rate);
+        if (m > 127) return fail(CHUB_ERR_UNSUPPORTED, "more than 127 FCEV arrivals per step" + where);
+        if (m > e->hv_max_arrive)
+            return fail(CHUB_ERR_ARG, "fcev_permeate gives up to " + std::to_string(m) + " FCEV arrivals per step, more than the " +
+                                      std::to_string(e->hv_max_arrive) + " the handle's waiting list was sized for at create" + where);
+    }
+    return write_env_params(e, mask, rows);
+}
+
+int chub_get_env_params(chub_env *e, chub_env_params *rows) {
+    if (!e || !rows) return fail(CHUB_ERR_ARG, "null argument");
+    if (!e->env_params) return fail(CHUB_ERR_ARG, "the handle has no per-env hub parameters: create it with chub_create_params");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(rows, e->d_rows, (size_t) e->hp.n_envs * sizeof(chub_env_params), hipMemcpyDeviceToHost));
+    return CHUB_OK;
+}
+
+int chub_has_env_params(const chub_env *e) { return e ? (e->env_params ? 1 : 0) : CHUB_ERR_ARG; }
 
 }  // extern "C"

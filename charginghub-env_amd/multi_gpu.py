@@ -314,13 +314,16 @@ class NativeShardedHub(object):
 
     def __init__(self, total_envs, hub_kwargs, seed=0, comm=None, shard=None):
         from .sharded import shard_range
+        from .vec_env import slice_env_kwargs
 
         self.comm = comm if comm is not None else Comm()
         self.rank, self.world = self.comm.rank, self.comm.world
         self.total_envs = int(total_envs)
         self.env_id0, self.n_local = shard_range(self.total_envs, self.world, self.rank)
+        # per-env kwargs (one value per env of the whole batch): this rank's slice
+        self.hub_kwargs = slice_env_kwargs(hub_kwargs, self.total_envs, self.env_id0, self.n_local)
         if shard is None:
-            shard = HipShard(self.n_local, self.env_id0, self.comm.device, seed, hub_kwargs, self.total_envs, self.rank == 0)
+            shard = HipShard(self.n_local, self.env_id0, self.comm.device, seed, self.hub_kwargs, self.total_envs, self.rank == 0)
         elif callable(shard):
             shard = shard(self.n_local, self.env_id0, self.total_envs, self.rank == 0)
         self.shard = shard

@@ -55,15 +55,19 @@ class ShardedChargingHub(object):
         import torch
         import torch.distributed as dist
 
+        from .vec_env import slice_env_kwargs
+
         self.torch, self.dist = torch, dist
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         self.total_envs = int(total_envs)
         self.env_id0, self.n_local = shard_range(self.total_envs, self.world, self.rank)
+        # per-env kwargs (one value per env of the whole batch): this rank's slice
+        self.hub_kwargs = slice_env_kwargs(hub_kwargs, self.total_envs, self.env_id0, self.n_local)
         if engine == "hip":
             local_rank = int(os.environ.get("LOCAL_RANK", self.rank))
-            engine = HipEngine(self.n_local, self.env_id0, local_rank, seed, hub_kwargs)
+            engine = HipEngine(self.n_local, self.env_id0, local_rank, seed, self.hub_kwargs)
         elif callable(engine):
             engine = engine(self.n_local, self.env_id0)
         self.engine = engine

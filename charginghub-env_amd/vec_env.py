@@ -40,6 +40,53 @@ def make_config(station_list, station_type_list, constant_charging=False, hydro_
     return cfg
 
 
+_ENV_PARAM_DEFAULTS = {"hydro_prod_rate": 430.0, "hydro_store_vlt": 5000.0, "init_soc": 0.5, "fc_max_power": 100.0, "fcev_permeate": 0.01,
+                       "renew_fluctuate": 0.0, "price_fluctuate": 0.0, "hydro_loss": 0.0}  # make_config's defaults (None -> the reference's)
+
+
+def _is_sequence(v):
+    return v is not None and not isinstance(v, (str, bytes)) and np.ndim(v) > 0
+
+
+def _field_values(name, value, n_envs):
+    """one per-env kwarg -> float64 [n_envs]: a scalar broadcasts, a sequence must have one entry per env (None entries take the default)"""
+    if _is_sequence(value):
+        seq = list(np.asarray(value, dtype=object).ravel()) if np.ndim(value) == 1 else None
+        if seq is None or len(seq) != n_envs:
+            raise ValueError("%s: expected a scalar or a sequence of n_envs = %d values, got shape %s" % (name, n_envs, np.shape(value)))
+        return np.array([_ENV_PARAM_DEFAULTS[name] if v is None else float(v) for v in seq], dtype=np.float64)
+    return np.full(n_envs, _ENV_PARAM_DEFAULTS[name] if value is None else float(value), dtype=np.float64)
+
+
+def split_env_params(n_envs, kwargs):
+    """The hub kwargs with per-env sequences taken out: (scalar kwargs for make_config, rows) -- rows is None when every one of the
+    eight per-env kwargs (_lib.ENV_PARAM_FIELDS) is a scalar, else a [n_envs] array of chub_env_params (scalars broadcast)."""
+    if not any(_is_sequence(kwargs.get(f)) for f in _lib.ENV_PARAM_FIELDS):
+        return dict(kwargs), None
+    scalar = {k: v for k, v in kwargs.items() if k not in _lib.ENV_PARAM_FIELDS}
+    rows = np.zeros(n_envs, dtype=ENV_PARAMS_DTYPE)
+    for f in _lib.ENV_PARAM_FIELDS:
+        rows[f] = _field_values(f, kwargs.get(f), n_envs)
+    return scalar, rows
+
+
+def slice_env_kwargs(kwargs, total_envs, lo, n):
+    """the hub kwargs of a shard that holds envs lo .. lo + n - 1 of total_envs: per-env sequences (one value per env of the whole
+    batch) sliced, everything else as it is"""
+    out = {}
+    for k, v in kwargs.items():
+        if k in _lib.ENV_PARAM_FIELDS and _is_sequence(v):
+            seq = np.asarray(v, dtype=object).ravel()
+            if np.ndim(v) != 1 or seq.size != total_envs:
+                raise ValueError("%s: expected a scalar or a sequence of total_envs = %d values, got shape %s" % (k, total_envs, np.shape(v)))
+            v = list(seq[lo:lo + n])
+        out[k] = v
+    return out
+
+
+ENV_PARAMS_DTYPE = np.dtype([(f, np.float64) for f in _lib.ENV_PARAM_FIELDS])  # the layout of chub_env_params
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -56,8 +103,10 @@ class VecChargingHub(object):
         kwargs.pop("seed_rand", None)
         kwargs.pop("use_lagrange", None)  # ignored by the reference too (MGR:126)
         self._lib = load_library()
-        self.cfg = make_config(station_list, station_type_list, **kwargs)
         self.n_envs = int(n_envs)
+        # any of the eight hydrogen / FCEV / fluctuation kwargs may be a sequence of one value per env (chub_create_params)
+        scalar_kwargs, rows = split_env_params(self.n_envs, kwargs)
+        self.cfg = make_config(station_list, station_type_list, **scalar_kwargs)
         if rng not in _lib.RNG_MODES:
             raise ValueError("rng must be 'philox', 'compat' or 'philox_curves'")
         self.rng_mode = _lib.RNG_MODES[rng]
@@ -72,8 +121,13 @@ class VecChargingHub(object):
         opt.span_tails = {"auto": 0, "same_wave": 1, "own_wave": 2}[span_tails]  # ... and the wave a span's tails run on (own_wave: a step behind the slots)
         opt.work_order = _lib.WORK_ORDER[work_order]  # PHILOX packed kernels: "auto" (XCD-aware while the streams are cache-resident) or "dispatch"
         self._copy_outputs = bool(copy_outputs)
-        check(self._lib.chub_create_ex(C.byref(self.cfg), (data_dir or _lib.DATA_DIR).encode(), self.n_envs, int(env_id0),
-                                       int(device), int(seed) & 0xFFFFFFFFFFFFFFFF, self.rng_mode, C.byref(opt), C.byref(h)))
+        if rows is None:
+            check(self._lib.chub_create_ex(C.byref(self.cfg), (data_dir or _lib.DATA_DIR).encode(), self.n_envs, int(env_id0),
+                                           int(device), int(seed) & 0xFFFFFFFFFFFFFFFF, self.rng_mode, C.byref(opt), C.byref(h)))
+        else:
+            check(self._lib.chub_create_params(C.byref(self.cfg), (data_dir or _lib.DATA_DIR).encode(), self.n_envs, int(env_id0),
+                                               int(device), int(seed) & 0xFFFFFFFFFFFFFFFF, self.rng_mode, C.byref(opt), _ptr(rows),
+                                               C.byref(h)))
         self._h = h
         self.obs_dim = self._lib.chub_obs_dim(h)
         self.act_dim = self._lib.chub_act_dim(h)
@@ -449,6 +503,32 @@ class VecChargingHub(object):
         b = np.ascontiguousarray(blob, dtype=np.uint8)
         check(self._lib.chub_set_state(self._h, _ptr(b), b.size))
 
+    # ---- per-env hub parameters (chub_create_params)
+    @property
+    def has_env_params(self):
+        return self._lib.chub_has_env_params(self._h) == 1
+
+    def env_params(self):
+        """the eight per-env kwargs as {name: float64 [n_envs]} (a homogeneous handle: its config, broadcast)"""
+        if not self.has_env_params:
+            return {f: np.full(self.n_envs, getattr(self.cfg, f), dtype=np.float64) for f in _lib.ENV_PARAM_FIELDS}
+        rows = np.zeros(self.n_envs, dtype=ENV_PARAMS_DTYPE)
+        check(self._lib.chub_get_env_params(self._h, _ptr(rows)))
+        return {f: rows[f].copy() for f in _lib.ENV_PARAM_FIELDS}
+
+    def set_env_params(self, mask=None, **fields):
+        """overwrite the given fields (scalar or one value per env) of the envs `mask` names (None = all); the others keep theirs.  They
+        apply from the next call on; follow with reset_envs(mask) to start those envs afresh (domain randomisation)."""
+        unknown = set(fields) - set(_lib.ENV_PARAM_FIELDS)
+        if unknown:
+            raise TypeError("unknown per-env parameters: %s" % ", ".join(sorted(unknown)))
+        cur = self.env_params()
+        rows = np.zeros(self.n_envs, dtype=ENV_PARAMS_DTYPE)
+        for f in _lib.ENV_PARAM_FIELDS:
+            rows[f] = _field_values(f, fields[f], self.n_envs) if f in fields else cur[f]
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask, dtype=bool).reshape(self.n_envs), dtype=np.uint8)
+        check(self._lib.chub_set_env_params(self._h, _ptr(m), _ptr(rows)))
+
     def hy_table(self, env=None):
         """hy_power_speed_list (HYD:154-157): the handle's table, or env i's own (COMPAT after compat_replay_constructor)"""
         out = np.zeros(102, dtype=np.float64)
@@ -480,4 +560,4 @@ class VecChargingHub(object):
             pass
 
 
-__all__ = ["VecChargingHub", "make_config", "ChubError"]
+__all__ = ["VecChargingHub", "make_config", "ChubError", "split_env_params", "slice_env_kwargs"]

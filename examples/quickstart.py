@@ -58,6 +58,18 @@ def batched_host(n=4096):
     obs, reward, done, _ = hub.step(rs.uniform(-1, 1, (n, hub.act_dim)).astype(np.float32))
     print("   per-env clocks: slots of day now %s (%d clocks)" % (sorted(set(hub.env_clocks().tolist())), hub.clock_groups))
     hub.close()
+    # differently built hubs in one handle: any of the eight hydrogen / FCEV / fluctuation kwargs may be one value per env
+    kw = dict(HUB, hydro_store_vlt=rs.uniform(5, 400, n), init_soc=rs.uniform(0.1, 1, n))
+    hub = chub.VecChargingHub(n, seed=0, **kw)
+    hub.reset()
+    for t in range(48):
+        obs, reward, done, _ = hub.step(batches[t % 8])
+    redo = rs.uniform(size=n) < 0.25                          # domain randomisation: new tanks for a quarter of the envs ...
+    hub.set_env_params(mask=redo, hydro_store_vlt=rs.uniform(5, 400, n), renew_fluctuate=0.3)
+    obs = hub.reset_envs(redo)                                # ... which start a new day with them
+    print("   per-env parameters: tank sizes %.0f .. %.0f m^3, mean reward %.4f"
+          % (hub.env_params()["hydro_store_vlt"].min(), hub.env_params()["hydro_store_vlt"].max(), reward.mean()))
+    hub.close()
 
 
 def device_resident(n=65536):

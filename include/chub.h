@@ -148,6 +148,53 @@ int chub_create_ex(const chub_config *cfg, const char *data_dir, int64_t n_envs,
                    uint64_t seed, int rng_mode, const chub_options *opt /* NULL = defaults */, chub_env **out);
 int chub_destroy(chub_env *env);
 
+/* ---- per-env hub parameters ----------------------------------------------------------------------------------------------
+ * In the reference every EvcsspManagerEnv_v6 is its own object built from its own kwargs (MGR:25-27): a vector of them may mix
+ * electrolysers, tanks, fuel cells, FCEV traffic and fluctuations (domain randomisation).  A handle made by chub_create_params
+ * holds such a mix: station_list, station_type_list and constant_charging stay per handle (they set the slot layout), the eight
+ * scalars below are per env.  Each row has the chub_config field of the same name and meaning; an env computes exactly what a
+ * homogeneous handle built from a chub_config with its row computes (same seed, same global env id: bit for bit).
+ *   chub_create_params: as chub_create_ex; cfg's eight scalars are ignored in favour of rows [N].  Every row is validated as
+ *       chub_create validates its config (same codes and messages, with " (env i)" appended).  fcev_permeate > 1 counts as 0.01 per
+ *       env, as in the reference.  The FCEV waiting list is sized for the largest arrival bound of any row.
+ *   chub_set_env_params: overwrite the rows of the envs a host mask names (NULL = all; rows is [N], only the named rows are read).
+ *       The new rows apply from the next launch on, including to a captured graph's next replay (the arrays do not move; a graph's
+ *       first step draws its own state-independent variates, so no FCEV count drawn with the old rate is consumed).  The state
+ *       of an env is not touched -- its tank keeps its content until a reset starts it at the new init_soc -- so the domain-
+ *       randomisation pattern is chub_set_env_params(mask, rows) then chub_reset_envs(mask).  What survives that reset is what
+ *       survives any reset (the OU states, MGR:304-316) and does not depend on the rows.  A row whose FCEV arrival bound exceeds the
+ *       one the handle was created with is refused (CHUB_ERR_ARG): create with the largest fcev_permeate you will use.  COMPAT: the
+ *       named envs' hy_power_speed_list becomes the zero-demand sweep of their new row; chub_compat_replay_constructor rebuilds it.
+ *   chub_get_env_params: the rows, [N].  chub_has_env_params: 1 for a handle made by chub_create_params, else 0.
+ *   chub_launch_plan_params: chub_launch_plan for such a handle (CHUB_PLAN_* values).
+ * Modes and forms: all three RNG modes.  Steps run as two launches -- the slot kernel, then the tail k_env<.., ENV_PARAMS> -- lock-step
+ * or masked: the options that pick the one-launch step and chub_run_steps's spans are accepted and have no effect (chub_uses_fused_step
+ * returns 0, chub_run_steps issues its steps one by one).  COMPAT: the reference's sequence for N differently built envs is
+ * chub_create_params -> chub_set_rng_compat_seeds -> chub_compat_replay_constructor (each env the constructor with its own kwargs and
+ * streams; until then each env's table is the zero-demand sweep of its row) -> chub_reset.  Such a handle runs one COMPAT form at every
+ * batch size: one kernel per station with the unit's first lane walking the streams, the tail drawing the forecourt (the split step's
+ * walks and k_compat_small are not built for rows; chub_options.slot_kernel / walk_ahead have no effect).  Entry points not built for
+ * per-env rows return CHUB_ERR_UNSUPPORTED with a message: the scalar-load control (chub_step_load*), tape mode
+ * (chub_tape_register_soc, chub_step_tape*, chub_reset_tape*), chub_get_hy_table and chub_set_hy_table (one table for every env;
+ * chub_get_hy_table_env gives env i's).  Snapshots carry the rows; one taken from a handle with rows is refused by a handle without
+ * and the other way round. */
+typedef struct chub_env_params {
+    double hydro_prod_rate;
+    double hydro_store_vlt;
+    double init_soc;
+    double fc_max_power;
+    double fcev_permeate;
+    double renew_fluctuate;
+    double price_fluctuate;
+    double hydro_loss;
+} chub_env_params;
+int chub_create_params(const chub_config *cfg, const char *data_dir, int64_t n_envs, int64_t env_id0, int device, uint64_t seed, int rng_mode,
+                       const chub_options *opt /* NULL = defaults */, const chub_env_params *rows /* [N] */, chub_env **out);
+int chub_set_env_params(chub_env *env, const uint8_t *mask /* host, NULL = all */, const chub_env_params *rows /* [N] */);
+int chub_get_env_params(chub_env *env, chub_env_params *rows /* [N] */);
+int chub_has_env_params(const chub_env *env);
+int chub_launch_plan_params(const chub_config *cfg, int64_t n_envs, int rng_mode, const chub_options *opt /* NULL = defaults */, int32_t *out);
+
 int chub_obs_dim(const chub_env *env);  /* 2 + 4*(#stations with piles>0) + 3 (MGR:74-104) */
 int chub_act_dim(const chub_env *env);  /* S + 2 (MGR:108-113) */
 int64_t chub_num_envs(const chub_env *env);
@@ -466,7 +513,8 @@ int chub_set_state(chub_env *env, const void *buf, int64_t size);
  * with 101 real hy_step()s, i.e. with live random FCEV demand, which matters whenever a tank clamp binds during that
  * sweep.  COMPAT: chub_compat_replay_constructor computes exactly that table per env from the env's streams (until
  * then, and in PHILOX mode, the table is the zero-demand sweep, one per handle: the production mode's definition).
- * chub_get_hy_table_env returns env i's table (PHILOX: the handle's); chub_set_hy_table installs one for every env. */
+ * chub_get_hy_table_env returns env i's table (PHILOX: the handle's; a handle with per-env parameters: the zero-demand sweep of env
+ * i's row); chub_set_hy_table installs one for every env. */
 int chub_get_hy_table(const chub_env *env, double *out102);
 int chub_get_hy_table_env(chub_env *env, int64_t env_index, double *out102);
 int chub_set_hy_table(chub_env *env, const double *in102);
