@@ -67,6 +67,8 @@ extern "C" __attribute__((visibility("hidden"))) int chub_set_last_error_(int co
             return fail(CHUB_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));               \
     } while (0)
 
+// The handle holds what outlives a call: configuration, device state, clocks, staging.  What ONE reset or step was asked to do -- its mask,
+// actions or bits, variates, tapes, outputs -- travels as a StepCall (below), never as a field here.
 struct chub_env {
     chub_config cfg;
     HubParams hp;
@@ -95,8 +97,6 @@ struct chub_env {
     uint8_t *h_mask;                // [2][N] pinned staging for them
     hipEvent_t mask_done[2];        // recorded behind the launches that read d_mask[i]
     uint32_t mask_seq;
-    const uint8_t *cur_mask;        // device copy of the mask of the call in progress
-    int64_t mask_lo, mask_hi;       // ... and the first / last env it names
     // a capture on per-env clocks: every masked call gets a device mask of its own (owned by the graph: a replay reads no host
     // memory), and the capture notes which launch of it served each env last (chub_env_clocks after a replay)
     std::vector<void *> cap_masks;
@@ -151,13 +151,6 @@ struct chub_env {
     bool graph_predrawn0;
     bool capturing;
     chub_comm *cap_comm = nullptr;  // the communicator whose gathers the capture in progress holds (chub_step_gather)
-    const uint64_t *cur_bits;  // set for the duration of chub_step_bits_device on the packed slot kernel: the step reads the
-    const float *cur_tail;     //   decision bits and the tail actions themselves (no action rows)
-    const uint64_t *tape_pk;   // set for the duration of chub_step_tape
-    const uint32_t *tape_car;
-    const uint32_t *tape_hv = nullptr;  // ... and, with them, the tail's tape (chub_step_tape_env / chub_reset_tape_env): FCEV arrivals per env
-    int tape_hv_w = 0;
-    bool tape_tail = false;     // the tail of the call in flight takes its variates from the caller (exo_z, exo_days, tape_hv)
     // optional per-kernel timing with HIP events on the launch stream (chub_profile_*)
     std::vector<hipEvent_t> prof_events;
     size_t prof_used, prof_cap;
@@ -515,7 +508,6 @@ static int create_impl(const chub_config *cfg_in, const char *data_dir, int64_t 
     e->h_mask = nullptr;
     e->mask_done[0] = e->mask_done[1] = nullptr;
     e->mask_seq = 0;
-    e->cur_mask = nullptr;
     e->cap_full_rel = 0;
     e->graph_per_env0 = false;
     e->graph_full_tick0 = 0;
@@ -810,10 +802,6 @@ static int create_impl(const chub_config *cfg_in, const char *data_dir, int64_t 
         if (max_stay > 31) return bail(fail(CHUB_ERR_UNSUPPORTED, "charge curves yield stays longer than 31 slots (the 5-bit fields of the slot state)"));
     }
     e->tape_classes = 0;
-    e->tape_pk = nullptr;
-    e->tape_car = nullptr;
-    e->cur_bits = nullptr;
-    e->cur_tail = nullptr;
     e->capturing = false;
     e->graph_base = 0;
     hp.packed = plan.packed != PACKED_NONE ? 1 : 0;
@@ -1052,6 +1040,61 @@ int chub_sync(chub_env *e) {
     return CHUB_OK;
 }
 
+// ---- one call ---------------------------------------------------------------------------------------------------------------
+// What ONE reset or step was asked to do, as a value.  Every entry point of the C ABI fills one in and hands it to run_call (a span of
+// chub_run_steps: to run_span); nothing of a call is kept on the handle, so nothing of it can be left behind for the next one.
+
+// where a call's outputs go (StepArgs has the fields' meaning)
+struct OutSink {
+    float *obs, *reward;
+    int obs_stride, reward_stride;
+    uint8_t *done;
+    float *done_f32;
+};
+// three arrays: obs [N][D], reward [N], done [N] u8 (a reset: obs alone)
+static OutSink dense_out(const chub_env *e, float *obs, float *reward, uint8_t *done) { return {obs, reward, e->hp.obs_dim, 1, done, nullptr}; }
+// one block [N][D + 2] f32: obs, reward, done as 0 / 1
+static OutSink packed_out(const chub_env *e, float *packed) {
+    const int D = e->hp.obs_dim;
+    return {packed, packed + D, D + 2, D + 2, nullptr, packed + D + 1};
+}
+
+struct StepCall {
+    bool reset;
+    int load_mode;            // step: the scalar-load control (chub_step_load*)
+    const uint8_t *mask;      // HOST [N], non-zero = the call serves this env; null: every env.  Everything below is device memory
+    const float *actions;     // step: the action rows [N][A], or
+    const uint64_t *bits;     //   one decision bit per pile [N][ceil(S / 64)] and
+    const float *tail;        //   the two tail actions [N][2] (chub_step_bits*)
+    const int32_t *exo_days;  // reset: [N][2] or null
+    const double *exo_z;      // [N][3] or null
+    // tape mode (chub_step_tape* / chub_reset_tape*): the station draws of a step, the cars' variates, and (tail_tape: exo_z, exo_days and
+    // the FCEV arrivals hv_tape [N][hv_w]) the tail's variates come from the caller
+    const uint64_t *pk_tape;
+    const uint32_t *car_tape, *hv_tape;
+    int hv_w;
+    bool tail_tape;
+    OutSink out;
+};
+static StepCall reset_call(const chub_env *e, const uint8_t *mask, const int32_t *d_exo_days, const double *d_exo_z, float *d_obs) {
+    StepCall c = {};
+    c.reset = true;
+    c.mask = mask;
+    c.exo_days = d_exo_days;
+    c.exo_z = d_exo_z;
+    c.out = dense_out(e, d_obs, nullptr, nullptr);
+    return c;
+}
+static StepCall step_call(const uint8_t *mask, const float *d_actions, const double *d_exo_z, const OutSink &out, int load_mode) {
+    StepCall c = {};
+    c.load_mode = load_mode;
+    c.mask = mask;
+    c.actions = d_actions;
+    c.exo_z = d_exo_z;
+    c.out = out;
+    return c;
+}
+
 // ---- clocks -----------------------------------------------------------------------------------------------------------------
 // Every reference env owns its clock (MGR:137-140, 271-273, 299).  Lock-step (the usual case: everybody reset and stepped
 // together) is ONE clock on the host, passed to the kernels as an argument.  The first call that names a subset of the envs
@@ -1060,12 +1103,17 @@ int chub_sync(chub_env *e) {
 // any call is still ONE launch with one Philox tick, however many different clocks the envs show.  A reset of everybody
 // returns to the host clock.
 
+// the mask of one call as its launch sees it: the device copy (null: every env) and the first / last env it names
+struct MaskView {
+    const uint8_t *d_mask;
+    int64_t lo, hi;
+};
+
 // What one call serves: 0 nobody, 1 a subset (mask uploaded, per-env clocks on), 2 every env.
-static int serve_mask(chub_env *e, const uint8_t *mask, hipStream_t s, int &served) {
+static int serve_mask(chub_env *e, const uint8_t *mask, hipStream_t s, int &served, MaskView &mv) {
     const size_t N = (size_t) e->hp.n_envs;
     size_t n_masked = N;
-    e->mask_lo = 0;
-    e->mask_hi = (int64_t) N - 1;
+    mv = {nullptr, 0, (int64_t) N - 1};
     if (mask) {
         n_masked = 0;
         int64_t lo = -1, hi = -1;
@@ -1076,13 +1124,12 @@ static int serve_mask(chub_env *e, const uint8_t *mask, hipStream_t s, int &serv
                 hi = (int64_t) i;
             }
         if (n_masked) {
-            e->mask_lo = lo;
-            e->mask_hi = hi;
+            mv.lo = lo;
+            mv.hi = hi;
         }
     }
     served = n_masked == 0 ? 0 : (n_masked == N ? 2 : 1);
     if (served != 1) return CHUB_OK;
-    if (e->tape_pk) return fail(CHUB_ERR_ARG, "tape mode runs in lock-step");
     if (e->capturing) {
         // a replay must not read the caller's (or the handle's staging) memory: the mask of a captured call lives in a device
         // buffer of its own, filled now and freed with the graph.  The clocks are device state, so nothing of them is baked in.
@@ -1096,7 +1143,7 @@ static int serve_mask(chub_env *e, const uint8_t *mask, hipStream_t s, int &serv
         if (!e->upload_stream) HIP_TRY(hipStreamCreateWithFlags(&e->upload_stream, hipStreamNonBlocking));
         HIP_TRY(hipMemcpyAsync(d, mask, N, hipMemcpyHostToDevice, e->upload_stream));
         HIP_TRY(hipStreamSynchronize(e->upload_stream));
-        e->cur_mask = d;
+        mv.d_mask = d;
         return CHUB_OK;
     }
     if (!e->per_env) {  // every env starts from the lock-step clock, in the buffer the next launch reads
@@ -1115,7 +1162,7 @@ static int serve_mask(chub_env *e, const uint8_t *mask, hipStream_t s, int &serv
     if (e->mask_seq >= 2) HIP_TRY(hipEventSynchronize(e->mask_done[b]));
     memcpy(e->h_mask + (size_t) b * N, mask, N);
     HIP_TRY(hipMemcpyAsync(e->d_mask + (size_t) b * N, e->h_mask + (size_t) b * N, N, hipMemcpyHostToDevice, s));
-    e->cur_mask = e->d_mask + (size_t) b * N;
+    mv.d_mask = e->d_mask + (size_t) b * N;
     return CHUB_OK;
 }
 
@@ -1145,57 +1192,97 @@ static int note_served(chub_env *e, const uint8_t *mask, int served, hipStream_t
 // COMPAT: the handle's lock-step steps of every env run the slot pass beside the NEXT step's stream walks (k_slot_walk2)
 static bool walks_two_ahead(const chub_env *e) { return e->plan.compat == COMPAT_WALK2_32 || e->plan.compat == COMPAT_WALK2_64; }
 
-// the launch forms of the reset / step in progress (chub_plan.h)
-static CallPlan plan_this_call(const chub_env *e, bool reset, int served, int load_mode, bool fresh) {
+// the launch forms of a reset / step (chub_plan.h)
+static CallPlan plan_this_call(const chub_env *e, const StepCall &call, int served, bool fresh) {
     CallState c;
-    c.reset = reset;
-    c.load_mode = load_mode != 0;
+    c.reset = call.reset;
+    c.load_mode = call.load_mode != 0;
     c.per_env = e->per_env;
     c.all_served = served == 2;
     c.capturing = e->capturing;
-    c.car_tape = e->tape_car != nullptr;
-    c.pk_tape = !reset && e->tape_pk;
-    c.tail_tape = e->tape_tail;
-    c.bits = !reset && e->cur_bits;
+    c.car_tape = call.car_tape != nullptr;
+    c.pk_tape = !call.reset && call.pk_tape;
+    c.tail_tape = call.tail_tape;
+    c.bits = !call.reset && call.bits;
     c.fresh = fresh;
     c.env_params = e->env_params;
     return plan_call(e->plan, c);
 }
 
-// ONE launched reset: of every env (served = 2) or of the envs of the uploaded mask (served = 1)
-static int run_reset(chub_env *e, int served, const int32_t *d_exo_days, const double *d_exo_z, float *d_obs, hipStream_t s) {
-    e->tick += 1;
-    StepArgs sa;
+// The part of StepArgs that every launch of a call fills the same way, for the launch with Philox tick `tick`: the clock and the tariff, the
+// call's inputs, tapes and outputs, the envs it serves; then the device's copy of the handle's context is brought up to date
+static int fill_args(chub_env *e, const StepCall &c, int served, const MaskView &mv, uint32_t tick, hipStream_t s, StepArgs &sa) {
     memset(&sa, 0, sizeof sa);
-    sa.t = 0;
-    sa.tick = e->tick - e->graph_base;
+    sa.t = c.reset ? 0 : e->t;
+    sa.tick = tick - e->graph_base;
     sa.draw_price = (e->price_count % 4 == 0) ? 1 : 0;
     sa.station_filter = -1;
-    sa.price_last = e->price[95];  // AGG:171: price = [] + mean_for_MAD; price[-1]
-    sa.exo_days = d_exo_days;
-    sa.exo_z = d_exo_z;
-    sa.obs = d_obs;
-    sa.obs_stride = e->hp.obs_dim;
-    sa.car_tape = e->tape_car;  // chub_reset_tape: the unit's occupancy draws are in pk already, the cars' variates come from the tape
-    sa.tail_tape = e->tape_tail ? 1 : 0;  // chub_reset_tape_env: the tail's days and normals from the caller as well
-    const CallPlan cp = plan_this_call(e, true, served, 0, false);
-    // COMPAT split reset: the walk's draws are committed by the slot pass (k_compat_small walks the streams in place: nothing to commit)
-    sa.commit_rng = (cp.call != CALL_COMPAT_SMALL && slot_form_split(cp.slot)) ? 1 : 0;
-    sa.walk_short = walks_two_ahead(e) ? 1 : 0;  // (the reset's walk leaves its short stays for a walk two steps ahead, as every walk of such a handle)
+    if (c.reset) {
+        sa.price_last = e->price[95];  // AGG:171: price = [] + mean_for_MAD; price[-1]
+    } else {
+        sa.price_last = e->price[e->t];  // AGG:147
+        sa.price_prev = e->price[(e->t + 95) % 96];  // what the make_state before this step saw there (the reset: price[95], AGG:171)
+    }
+    sa.actions = c.actions;
+    sa.act_bits = c.bits;
+    sa.act_tail = c.tail;
+    sa.exo_days = c.exo_days;
+    sa.exo_z = c.exo_z;
+    sa.obs = c.out.obs;
+    sa.obs_stride = c.out.obs_stride;
+    sa.reward = c.out.reward;
+    sa.reward_stride = c.out.reward_stride;
+    sa.done = c.out.done;
+    sa.done_f32 = c.out.done_f32;
+    sa.load_mode = c.load_mode;
+    sa.pk_tape = c.pk_tape;
+    sa.car_tape = c.car_tape;  // (a tape reset: the units' occupancy draws are in pk already, the cars' variates come from the tape)
+    sa.hv_tape = c.hv_tape;
+    sa.hv_w = c.hv_w;
+    sa.tail_tape = c.tail_tape ? 1 : 0;
+    // the state-independent draws of a step: left by the previous launch's level blocks if that launch served every env
+    // (for the tick that is now this launch's), otherwise made by this launch itself (a graph's first step always makes its
+    // own: a replay must not depend on what ran before it)
+    sa.fresh = (!c.reset && (!e->predrawn || (e->capturing && tick == e->graph_tick0 + 1u))) ? 1 : 0;
     sa.rng_cur = e->rng_cur;
-    e->walked_tick = 0;                   // (a walk that ran ahead for a step that now does not come: its shadow is simply overwritten)
     sa.env_lo = 0;
     sa.env_hi = (int32_t) (e->hp.n_envs - 1);
     if (e->per_env) {
         sa.env_clk = e->d_env_clk;
-        sa.env_mask = served == 1 ? e->cur_mask : nullptr;
         if (served == 1) {
-            sa.env_lo = (int32_t) e->mask_lo;
-            sa.env_hi = (int32_t) e->mask_hi;
+            sa.env_mask = mv.d_mask;
+            sa.env_lo = (int32_t) mv.lo;
+            sa.env_hi = (int32_t) mv.hi;
         }
     }
-    int rc_ = sync_ctx(e, s);
-    if (rc_) return rc_;
+    return sync_ctx(e, s);
+}
+
+// the handle's clocks behind a launch that went out: a reset, or k steps
+static void advance_clocks(chub_env *e, const StepCall &c, int served, int k) {
+    e->predrawn = served == 2;  // the launch's level blocks left the next step's draws of every env it served
+    if (c.reset) {
+        if (served == 2) {  // everybody starts a new day: one clock again (the launch itself still ran on the envs' own clocks)
+            e->per_env = false;
+            e->t = 0;
+            e->price_count = 0;  // MGR:313 (after make_state)
+        }
+    } else if (!e->per_env) {
+        e->price_count += k;
+        e->t = (e->t + k) % 96;
+    }
+}
+
+// ONE launched reset: of every env (served = 2) or of the envs of the uploaded mask (served = 1)
+static int run_reset(chub_env *e, const StepCall &c, int served, const MaskView &mv, hipStream_t s) {
+    e->tick += 1;
+    e->walked_tick = 0;  // (a walk that ran ahead for a step that now does not come: its shadow is simply overwritten)
+    StepArgs sa;
+    if (const int rc = fill_args(e, c, served, mv, e->tick, s, sa)) return rc;
+    const CallPlan cp = plan_this_call(e, c, served, false);
+    // COMPAT split reset: the walk's draws are committed by the slot pass (k_compat_small walks the streams in place: nothing to commit)
+    sa.commit_rng = (cp.call != CALL_COMPAT_SMALL && slot_form_split(cp.slot)) ? 1 : 0;
+    sa.walk_short = walks_two_ahead(e) ? 1 : 0;  // (the reset's walk leaves its short stays for a walk two steps ahead, as every walk of such a handle)
     if (cp.call == CALL_COMPAT_SMALL) {
         launch_compat_small<true>(e->hp, e->d_ctx, sa, s, packed_ptrs(e));
         e->empt_valid = true;  // (k_compat_small is the split step in one launch: its slot waves leave the counts)
@@ -1208,240 +1295,30 @@ static int run_reset(chub_env *e, int served, const int32_t *d_exo_days, const d
         if (e->hp.compat_split != 0 && served == 2 && !e->capturing) e->e2_tick = e->tick;  // (... and every unit's empt2, at this tick's parity)
     }
     HIP_TRY(hipGetLastError());
-    e->predrawn = served == 2;  // the launch's level blocks left the next step's draws of every env it served
-    if (served == 2) {  // everybody starts a new day: one clock again (the launch itself still ran on the envs' own clocks)
-        e->per_env = false;
-        e->t = 0;
-        e->price_count = 0;  // MGR:313 (after make_state)
-    }
-    return CHUB_OK;
-}
-
-static int reset_masked(chub_env *e, const uint8_t *mask, const int32_t *d_exo_days, const double *d_exo_z, float *d_obs, void *stream) {
-    if (!e || !d_obs) return fail(CHUB_ERR_ARG, "null argument");
-    if (e->hp.rng_mode == CHUB_RNG_COMPAT && (!d_exo_days || !d_exo_z))
-        return fail(CHUB_ERR_ARG, "COMPAT mode needs exo_days and exo_z");
-    if (e->tape_only && !e->tape_car)
-        return fail(CHUB_ERR_ARG, "a handle with registered tape classes resets through chub_reset_tape / chub_reset_tape_env only");
-    HIP_TRY(hipSetDevice(e->device));
-    (void) hipGetLastError();  // a stale error of an earlier, unrelated call must not be reported as this step's
-    hipStream_t s = (hipStream_t) stream;
-    int served = 0;
-    const bool was_per_env = e->per_env;
-    int rc = serve_mask(e, mask, s, served);
-    if (rc || served == 0) return rc;
-    rc = run_reset(e, served, d_exo_days, d_exo_z, d_obs, s);
-    if (rc) {
-        e->per_env = was_per_env;  // nothing was launched: the handle stays on the clock(s) it was on
-        return rc;
-    }
-    return note_served(e, mask, served, s);
-}
-
-int chub_reset_device(chub_env *e, const int32_t *d_exo_days, const double *d_exo_z, float *d_obs, void *stream) {
-    return reset_masked(e, nullptr, d_exo_days, d_exo_z, d_obs, stream);
-}
-
-int chub_reset_envs_device(chub_env *e, const uint8_t *mask, const int32_t *d_exo_days, const double *d_exo_z, float *d_obs, void *stream) {
-    if (!mask) return fail(CHUB_ERR_ARG, "null argument");
-    return reset_masked(e, mask, d_exo_days, d_exo_z, d_obs, stream);
-}
-
-static int step_common(chub_env *e, const float *d_actions, const double *d_exo_z, float *d_obs, int obs_stride,
-                       float *d_reward, int reward_stride, uint8_t *d_done, float *d_done_f32, void *stream,
-                       int load_mode = 0);
-
-int chub_step_device(chub_env *e, const float *d_actions, const double *d_exo_z, float *d_obs, float *d_reward,
-                     uint8_t *d_done, void *stream) {
-    if (!e || !d_actions || !d_obs || !d_reward || !d_done) return fail(CHUB_ERR_ARG, "null argument");
-    return step_common(e, d_actions, d_exo_z, d_obs, e->hp.obs_dim, d_reward, 1, d_done, nullptr, stream);
-}
-
-int chub_step_device_packed(chub_env *e, const float *d_actions, const double *d_exo_z, float *d_packed, void *stream) {
-    if (!e || !d_actions || !d_packed) return fail(CHUB_ERR_ARG, "null argument");
-    const int D = e->hp.obs_dim;
-    return step_common(e, d_actions, d_exo_z, d_packed, D + 2, d_packed + D, D + 2, nullptr, d_packed + D + 1, stream);
-}
-
-int chub_step_gather(chub_env *e, chub_comm *comm, const float *d_actions, float *d_packed, float *d_gathered, void *stream) {
-    if (!e || !comm || !d_actions) return fail(CHUB_ERR_ARG, "null argument");
-    // (overlapped gathers, chub_comm_set_overlap: the gather that last sent this block must have left before the kernels overwrite it;
-    // a capture remembers the communicator so that chub_graph_end can join its stream)
-    // the ROOT's kernels write its packed block straight into the gathered buffer (its first n_envs rows): no copy of the root's own block, neither
-    // by a send to itself nor otherwise; d_packed is not touched there (may be null).  Every other rank steps into d_packed and sends it.
-    const bool root = chub_comm_rank(comm) == 0;
-    if (root && !d_gathered) return fail(CHUB_ERR_ARG, "rank 0 needs the gathered buffer");
-    if (!root && !d_packed) return fail(CHUB_ERR_ARG, "null argument");
-    float *out = root ? d_gathered : d_packed;
-    int rc = chub_comm_gather_begin(comm, out, stream);
-    if (rc) return rc;
-    if (e->capturing) e->cap_comm = comm;
-    rc = chub_step_device_packed(e, d_actions, nullptr, out, stream);
-    if (rc) return rc;
-    return chub_comm_gather(comm, out, d_gathered, e->hp.n_envs * (int64_t) (e->hp.obs_dim + 2) * (int64_t) sizeof(float), stream);
-}
-
-// chub_run_steps on a PHILOX handle that runs the one-launch step (k_step_fused): a span of lock-step steps goes out as ONE launch
-// (k_steps_fused: the workgroup that owns an env's slots, records and tail goes from step to step by itself).  Not while a tape is loaded,
-// on per-env clocks, with one bit per pile, under the per-kernel profiler or with chub_options.span_steps = 1.
-static bool span_ok(const chub_env *e, int n_batches) {
-    return e->plan.one_launch != ONE_NONE && e->plan.span_size_ok && e->plan.span_steps != 1 && !e->per_env && !e->prof_on && !e->tape_pk && !e->tape_car &&
-           !e->tape_tail && !e->tape_only && !e->cur_bits && n_batches <= 8 && e->tick != 0 && !e->hp.telemetry;
-}
-
-static int run_span(chub_env *e, const float *const *batches, int n_batches, float *const *packed2, int64_t first, int k, hipStream_t s) {
-    HIP_TRY(hipSetDevice(e->device));
-    (void) hipGetLastError();
-    if (e->t + k > 96) return fail(CHUB_ERR_ARG, "a span of steps ends at the day's end at the latest");
-    const int D = e->hp.obs_dim;
-    StepArgs sa;
-    memset(&sa, 0, sizeof sa);
-    sa.t = e->t;
-    sa.tick = e->tick + 1u - e->graph_base;
-    sa.draw_price = (e->price_count % 4 == 0) ? 1 : 0;
-    sa.station_filter = -1;
-    sa.price_last = e->price[e->t];
-    sa.price_prev = e->price[(e->t + 95) % 96];
-    sa.actions = batches[first % n_batches];
-    float *out = packed2[first & 1];
-    sa.obs = out;
-    sa.obs_stride = D + 2;
-    sa.reward = out + D;
-    sa.reward_stride = D + 2;
-    sa.done_f32 = out + D + 1;
-    sa.env_lo = 0;
-    sa.env_hi = (int32_t) (e->hp.n_envs - 1);
-    sa.fresh = (!e->predrawn || (e->capturing && e->tick == e->graph_tick0)) ? 1 : 0;  // (as run_step: a graph's first step makes its own draws)
-#if CHUB_TRACE
-    sa.stamps_slot = nullptr;
-    sa.stamps_env = nullptr;
-#endif
-    int rc = sync_ctx(e, s);
-    if (rc) return rc;
-    launch_steps_fused(e->hp, e->plan, e->d_ctx, sa, s, packed_ptrs(e), k, e->price_count, first, batches, n_batches, packed2);
-    HIP_TRY(hipGetLastError());
-    e->tick += (uint32_t) k;
-    if (e->capturing) e->cap_full_rel = e->tick - e->graph_tick0;  // (note_served: which launch of the capture served every env last)
-    else e->full_tick = e->tick;
-    e->predrawn = true;
-    e->price_count += k;
-    e->t = (e->t + k) % 96;
-    return CHUB_OK;
-}
-
-// A run of steps issued from C: what a host loop of chub_reset_device / chub_step_device_packed / chub_step_gather calls does, without
-// a trip through the host language per step (multi-GPU shards of a few thousand envs are otherwise bound by the host's issue rate)
-int chub_run_steps(chub_env *e, chub_comm *comm, const float *const *d_action_batches, int n_batches, float *const *d_packed2,
-                   float *const *d_gathered2, float *d_reset_obs, int64_t first_step, int64_t n_steps, void *stream) {
-    if (!e || !d_action_batches || n_batches <= 0 || !d_packed2 || !d_packed2[0] || !d_packed2[1] || !d_reset_obs || first_step < 0 ||
-        n_steps < 0)
-        return fail(CHUB_ERR_ARG, "bad argument");
-    for (int64_t i = first_step; i < first_step + n_steps; i++) {
-        int rc;
-        if (i % 96 == 0 && (rc = chub_reset_device(e, nullptr, nullptr, d_reset_obs, stream))) return rc;
-        // a SPAN of steps in ONE launch (k_steps_fused) where the handle runs the one-launch step anyway: up to the day's end or the call's
-        if (!comm) {
-            int64_t k = first_step + n_steps - i;
-            k = k < 96 - i % 96 ? k : 96 - i % 96;
-            k = k < 96 - e->t ? k : 96 - e->t;  // (the handle's own clock need not be i % 96: a caller may step on past `done` -- the span ends where the clock wraps)
-            if (e->plan.span_steps > 1 && k > e->plan.span_steps) k = e->plan.span_steps;
-            if (k >= 2 && span_ok(e, n_batches)) {
-                if ((rc = run_span(e, d_action_batches, n_batches, d_packed2, i, (int) k, (hipStream_t) stream))) return rc;
-                i += k - 1;
-                continue;
-            }
-        }
-        const float *act = d_action_batches[i % n_batches];
-        float *packed = d_packed2[i & 1];
-        if (comm) rc = chub_step_gather(e, comm, act, packed, d_gathered2 ? d_gathered2[i & 1] : nullptr, stream);
-        else rc = chub_step_device_packed(e, act, nullptr, packed, stream);
-        if (rc) return rc;
-    }
-    return CHUB_OK;
-}
-
-int chub_step_load_device(chub_env *e, const float *d_actions, const double *d_exo_z, float *d_obs, float *d_reward,
-                          uint8_t *d_done, void *stream) {
-    if (!e || !d_actions || !d_obs || !d_reward || !d_done) return fail(CHUB_ERR_ARG, "null argument");
-    return step_common(e, d_actions, d_exo_z, d_obs, e->hp.obs_dim, d_reward, 1, d_done, nullptr, stream, 1);
-}
-
-int chub_step_load(chub_env *e, const float *actions, const double *exo_z, float *obs, float *reward, uint8_t *done) {
-    if (!e || !actions || !obs || !reward || !done) return fail(CHUB_ERR_ARG, "null argument");
-    HIP_TRY(hipSetDevice(e->device));
-    const size_t N = (size_t) e->hp.n_envs;
-    HIP_TRY(hipMemcpy(e->d_actions, actions, N * (size_t) e->hp.act_dim * sizeof(float), hipMemcpyHostToDevice));
-    if (e->hp.rng_mode == CHUB_RNG_COMPAT) {
-        if (!exo_z) return fail(CHUB_ERR_ARG, "COMPAT mode needs exo_z");
-        HIP_TRY(hipMemcpy(e->d_exo_z, exo_z, N * 3 * sizeof(double), hipMemcpyHostToDevice));
-    }
-    int rc = chub_step_load_device(e, e->d_actions, e->d_exo_z, e->d_obs, e->d_reward, e->d_done, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(obs, e->d_obs, N * (size_t) e->hp.obs_dim * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(reward, e->d_reward, N * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(done, e->d_done, N, hipMemcpyDeviceToHost));
+    advance_clocks(e, c, served, 1);
     return CHUB_OK;
 }
 
 // ONE launched step: of every env (served = 2) or of the envs of the uploaded mask (served = 1)
-static int run_step(chub_env *e, int served, const float *d_actions, const double *d_exo_z, float *d_obs, int obs_stride,
-                    float *d_reward, int reward_stride, uint8_t *d_done, float *d_done_f32, hipStream_t s, int load_mode) {
+static int run_step(chub_env *e, const StepCall &c, int served, const MaskView &mv, hipStream_t s) {
     e->tick += 1;
+    const uint32_t walked_tick = e->walked_tick;
+    e->walked_tick = 0;
     StepArgs sa;
-    memset(&sa, 0, sizeof sa);
-    sa.t = e->t;
-    sa.tick = e->tick - e->graph_base;
-    sa.draw_price = (e->price_count % 4 == 0) ? 1 : 0;
-    sa.station_filter = -1;
-    sa.price_last = e->price[e->t];  // AGG:147
-    sa.price_prev = e->price[(e->t + 95) % 96];  // what the make_state before this step saw there (the reset: price[95], AGG:171)
-    sa.actions = d_actions;
-    sa.act_bits = e->cur_bits;
-    sa.act_tail = e->cur_tail;
-    sa.exo_z = d_exo_z;
-    sa.obs = d_obs;
-    sa.obs_stride = obs_stride;
-    sa.reward = d_reward;
-    sa.reward_stride = reward_stride;
-    sa.done = d_done;
-    sa.done_f32 = d_done_f32;
-    sa.load_mode = load_mode;
-    sa.pk_tape = e->tape_pk;
-    sa.car_tape = e->tape_car;
+    if (const int rc = fill_args(e, c, served, mv, e->tick, s, sa)) return rc;
 #if CHUB_TRACE
     sa.stamps_slot = (unsigned long long *) g_stamps_slot;
     sa.stamps_env = (unsigned long long *) g_stamps_env;
 #endif
-    sa.hv_tape = e->tape_hv;
-    sa.hv_w = e->tape_hv_w;
-    sa.tail_tape = e->tape_tail ? 1 : 0;
-    // the state-independent draws of this step: left by the previous launch's level blocks if that launch served every env
-    // (for the tick that is now this launch's), otherwise made by this launch itself (a graph's first step always makes its
-    // own: a replay must not depend on what ran before it)
-    sa.fresh = (!e->predrawn || (e->capturing && e->tick == e->graph_tick0 + 1u)) ? 1 : 0;
-    const CallPlan cp = plan_this_call(e, false, served, load_mode, sa.fresh != 0);
+    const CallPlan cp = plan_this_call(e, c, served, sa.fresh != 0);
     const bool split_step = cp.call != CALL_COMPAT_SMALL && slot_form_split(cp.slot);
-    sa.rng_cur = e->rng_cur;
     if (split_step) {  // COMPAT split step: the slot pass commits the walk's draws, the tail reads the forecourt's from where the walk left them
         sa.commit_rng = 1;
         sa.hv_tape = (const uint32_t *) e->ev.hv_pre[sa.tick & 1u];
         sa.hv_w = e->hp.hv_w;
-        sa.walked = (e->walked_tick == e->tick && served == 2 && !e->per_env) ? 1 : 0;
+        sa.walked = (walked_tick == e->tick && served == 2 && !e->per_env) ? 1 : 0;
         sa.walk_short = walks_two_ahead(e) ? 1 : 0;
     }
-    e->walked_tick = 0;
-    sa.env_lo = 0;
-    sa.env_hi = (int32_t) (e->hp.n_envs - 1);
-    if (e->per_env) {
-        sa.env_clk = e->d_env_clk;
-        sa.env_mask = served == 1 ? e->cur_mask : nullptr;
-        if (served == 1) {
-            sa.env_lo = (int32_t) e->mask_lo;
-            sa.env_hi = (int32_t) e->mask_hi;
-        }
-    }
-    int rc_ = sync_ctx(e, s);
-    if (rc_) return rc_;
     bool prof = e->prof_on && e->prof_used < e->prof_cap;
     if (prof) {
         prof = (e->prof_phase % e->prof_every) == 0;  // sample: the event records are not free
@@ -1496,113 +1373,171 @@ static int run_step(chub_env *e, int served, const float *d_actions, const doubl
     }
     if (prof) e->prof_used++;
     HIP_TRY(hipGetLastError());
-    e->predrawn = served == 2;
-    if (!e->per_env) {
-        e->price_count += 1;
-        e->t = (e->t + 1) % 96;
-    }
+    advance_clocks(e, c, served, 1);
     return CHUB_OK;
 }
 
-static int step_masked(chub_env *e, const uint8_t *mask, const float *d_actions, const double *d_exo_z, float *d_obs, int obs_stride,
-                       float *d_reward, int reward_stride, uint8_t *d_done, float *d_done_f32, void *stream, int load_mode) {
-    if (e->tick == 0) return fail(CHUB_ERR_ARG, "step() before reset()");
-    if (e->tape_only && !e->tape_pk)
-        return fail(CHUB_ERR_ARG, "a handle with registered tape classes steps through chub_step_tape / chub_step_tape_env only (its class "
-                                  "rows hold the caller's arrival SoCs: cars admitted by this build's own draws would be given them)");
-    if (e->hp.rng_mode == CHUB_RNG_COMPAT && !d_exo_z) return fail(CHUB_ERR_ARG, "COMPAT mode needs exo_z");
-    if (load_mode && e->hp.soc_curves)
-        return fail(CHUB_ERR_UNSUPPORTED, "the scalar-load control (chub_step_load*) is not supported in rng_mode PHILOX_CURVES");
-    if (load_mode && e->env_params) return refuse_params("the scalar-load control (chub_step_load*)");
+// the precondition of a COMPAT handle's calls: the caller brings the variates the reference's numpy would have drawn
+static int check_compat_variates(const chub_env *e, bool reset, const int32_t *exo_days, const double *exo_z) {
+    if (e->hp.rng_mode != CHUB_RNG_COMPAT) return CHUB_OK;
+    if (reset && (!exo_days || !exo_z)) return fail(CHUB_ERR_ARG, "COMPAT mode needs exo_days and exo_z");
+    if (!reset && !exo_z) return fail(CHUB_ERR_ARG, "COMPAT mode needs exo_z");
+    return CHUB_OK;
+}
+
+// ONE reset or step, from the checks that depend on the call to the handle's bookkeeping behind the launch
+static int run_call(chub_env *e, const StepCall &call, hipStream_t s) {
+    if (call.reset) {
+        if (const int rc = check_compat_variates(e, true, call.exo_days, call.exo_z)) return rc;
+        if (e->tape_only && !call.car_tape)
+            return fail(CHUB_ERR_ARG, "a handle with registered tape classes resets through chub_reset_tape / chub_reset_tape_env only");
+    } else {
+        if (e->tick == 0) return fail(CHUB_ERR_ARG, "step() before reset()");
+        if (e->tape_only && !call.pk_tape)
+            return fail(CHUB_ERR_ARG, "a handle with registered tape classes steps through chub_step_tape / chub_step_tape_env only (its class "
+                                      "rows hold the caller's arrival SoCs: cars admitted by this build's own draws would be given them)");
+        if (const int rc = check_compat_variates(e, false, nullptr, call.exo_z)) return rc;
+        if (call.load_mode && e->hp.soc_curves)
+            return fail(CHUB_ERR_UNSUPPORTED, "the scalar-load control (chub_step_load*) is not supported in rng_mode PHILOX_CURVES");
+        if (call.load_mode && e->env_params) return refuse_params("the scalar-load control (chub_step_load*)");
+    }
     HIP_TRY(hipSetDevice(e->device));
-    (void) hipGetLastError();  // a stale error of an earlier, unrelated call must not be reported as this step's
-    hipStream_t s = (hipStream_t) stream;
+    StepCall c = call;
+    if (c.bits && !(e->hp.packed && e->hp.rng_mode == CHUB_RNG_PHILOX)) {
+        // only the packed PHILOX slot kernel reads the bits themselves (8 bytes per env and word instead of a row of floats); for every other
+        // kernel they are expanded on the device into the action rows it reads
+        launch_expand_bits(e->hp, c.bits, c.tail, e->d_actions, s);
+        HIP_TRY(hipGetLastError());
+        c.actions = e->d_actions;
+        c.bits = nullptr;
+        c.tail = nullptr;
+    }
+    (void) hipGetLastError();  // a stale error of an earlier, unrelated call must not be reported as this call's
     int served = 0;
+    MaskView mv;
     const bool was_per_env = e->per_env;
-    int rc = serve_mask(e, mask, s, served);
+    int rc = serve_mask(e, c.mask, s, served, mv);
     if (rc || served == 0) return rc;
-    rc = run_step(e, served, d_actions, d_exo_z, d_obs, obs_stride, d_reward, reward_stride, d_done, d_done_f32, s, load_mode);
+    rc = c.reset ? run_reset(e, c, served, mv, s) : run_step(e, c, served, mv, s);
     if (rc) {
         e->per_env = was_per_env;  // nothing was launched: the handle stays on the clock(s) it was on
         return rc;
     }
-    return note_served(e, mask, served, s);
+    return note_served(e, c.mask, served, s);
 }
 
-static int step_common(chub_env *e, const float *d_actions, const double *d_exo_z, float *d_obs, int obs_stride,
-                       float *d_reward, int reward_stride, uint8_t *d_done, float *d_done_f32, void *stream,
-                       int load_mode) {
-    return step_masked(e, nullptr, d_actions, d_exo_z, d_obs, obs_stride, d_reward, reward_stride, d_done, d_done_f32, stream, load_mode);
+int chub_reset_device(chub_env *e, const int32_t *d_exo_days, const double *d_exo_z, float *d_obs, void *stream) {
+    if (!e || !d_obs) return fail(CHUB_ERR_ARG, "null argument");
+    return run_call(e, reset_call(e, nullptr, d_exo_days, d_exo_z, d_obs), (hipStream_t) stream);
+}
+
+int chub_reset_envs_device(chub_env *e, const uint8_t *mask, const int32_t *d_exo_days, const double *d_exo_z, float *d_obs, void *stream) {
+    if (!e || !mask || !d_obs) return fail(CHUB_ERR_ARG, "null argument");
+    return run_call(e, reset_call(e, mask, d_exo_days, d_exo_z, d_obs), (hipStream_t) stream);
+}
+
+int chub_step_device(chub_env *e, const float *d_actions, const double *d_exo_z, float *d_obs, float *d_reward,
+                     uint8_t *d_done, void *stream) {
+    if (!e || !d_actions || !d_obs || !d_reward || !d_done) return fail(CHUB_ERR_ARG, "null argument");
+    return run_call(e, step_call(nullptr, d_actions, d_exo_z, dense_out(e, d_obs, d_reward, d_done), 0), (hipStream_t) stream);
+}
+
+int chub_step_device_packed(chub_env *e, const float *d_actions, const double *d_exo_z, float *d_packed, void *stream) {
+    if (!e || !d_actions || !d_packed) return fail(CHUB_ERR_ARG, "null argument");
+    return run_call(e, step_call(nullptr, d_actions, d_exo_z, packed_out(e, d_packed), 0), (hipStream_t) stream);
+}
+
+int chub_step_load_device(chub_env *e, const float *d_actions, const double *d_exo_z, float *d_obs, float *d_reward,
+                          uint8_t *d_done, void *stream) {
+    if (!e || !d_actions || !d_obs || !d_reward || !d_done) return fail(CHUB_ERR_ARG, "null argument");
+    return run_call(e, step_call(nullptr, d_actions, d_exo_z, dense_out(e, d_obs, d_reward, d_done), 1), (hipStream_t) stream);
 }
 
 int chub_step_envs_device(chub_env *e, const uint8_t *mask, const float *d_actions, const double *d_exo_z, float *d_obs, float *d_reward,
                           uint8_t *d_done, void *stream) {
     if (!e || !mask || !d_actions || !d_obs || !d_reward || !d_done) return fail(CHUB_ERR_ARG, "null argument");
-    return step_masked(e, mask, d_actions, d_exo_z, d_obs, e->hp.obs_dim, d_reward, 1, d_done, nullptr, stream, 0);
+    return run_call(e, step_call(mask, d_actions, d_exo_z, dense_out(e, d_obs, d_reward, d_done), 0), (hipStream_t) stream);
 }
 
 // the scalar-load step on a subset of the envs (every reference env can take evs_step(float) on its own, CHS.hpp:1169-1186 / 1480-1497)
 int chub_step_load_envs_device(chub_env *e, const uint8_t *mask, const float *d_actions, const double *d_exo_z, float *d_obs, float *d_reward,
                                uint8_t *d_done, void *stream) {
     if (!e || !mask || !d_actions || !d_obs || !d_reward || !d_done) return fail(CHUB_ERR_ARG, "null argument");
-    return step_masked(e, mask, d_actions, d_exo_z, d_obs, e->hp.obs_dim, d_reward, 1, d_done, nullptr, stream, 1);
+    return run_call(e, step_call(mask, d_actions, d_exo_z, dense_out(e, d_obs, d_reward, d_done), 1), (hipStream_t) stream);
 }
 
-// host-pointer forms: full-size arrays, only the rows of the named envs are read and written
-int chub_reset_envs(chub_env *e, const uint8_t *mask, const int32_t *exo_days, const double *exo_z, float *obs) {
-    if (!e || !mask || !obs) return fail(CHUB_ERR_ARG, "null argument");
-    HIP_TRY(hipSetDevice(e->device));
-    const size_t N = (size_t) e->hp.n_envs, D = (size_t) e->hp.obs_dim;
-    if (e->hp.rng_mode == CHUB_RNG_COMPAT) {  // as chub_reset: the values of the envs outside the mask are not looked at
-        if (!exo_days || !exo_z) return fail(CHUB_ERR_ARG, "COMPAT mode needs exo_days and exo_z");
-        for (size_t i = 0; i < N; i++)
-            if (mask[i] && (exo_days[2 * i] < 0 || exo_days[2 * i] >= 100 || exo_days[2 * i + 1] < 0 || exo_days[2 * i + 1] >= 150))
-                return fail(CHUB_ERR_ARG, "exo_days out of range");
-        HIP_TRY(hipMemcpy(e->d_exo_days, exo_days, N * 2 * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(e->d_exo_z, exo_z, N * 3 * sizeof(double), hipMemcpyHostToDevice));
-    }
-    int rc = chub_reset_envs_device(e, mask, e->d_exo_days, e->d_exo_z, e->d_obs, nullptr);
+int chub_step_gather(chub_env *e, chub_comm *comm, const float *d_actions, float *d_packed, float *d_gathered, void *stream) {
+    if (!e || !comm || !d_actions) return fail(CHUB_ERR_ARG, "null argument");
+    // (overlapped gathers, chub_comm_set_overlap: the gather that last sent this block must have left before the kernels overwrite it;
+    // a capture remembers the communicator so that chub_graph_end can join its stream)
+    // the ROOT's kernels write its packed block straight into the gathered buffer (its first n_envs rows): no copy of the root's own block, neither
+    // by a send to itself nor otherwise; d_packed is not touched there (may be null).  Every other rank steps into d_packed and sends it.
+    const bool root = chub_comm_rank(comm) == 0;
+    if (root && !d_gathered) return fail(CHUB_ERR_ARG, "rank 0 needs the gathered buffer");
+    if (!root && !d_packed) return fail(CHUB_ERR_ARG, "null argument");
+    float *out = root ? d_gathered : d_packed;
+    int rc = chub_comm_gather_begin(comm, out, stream);
     if (rc) return rc;
-    std::vector<float> o(N * D);
-    HIP_TRY(hipMemcpy(o.data(), e->d_obs, o.size() * sizeof(float), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < N; i++)
-        if (mask[i]) memcpy(obs + i * D, &o[i * D], D * sizeof(float));
-    return CHUB_OK;
+    if (e->capturing) e->cap_comm = comm;
+    rc = chub_step_device_packed(e, d_actions, nullptr, out, stream);
+    if (rc) return rc;
+    return chub_comm_gather(comm, out, d_gathered, e->hp.n_envs * (int64_t) (e->hp.obs_dim + 2) * (int64_t) sizeof(float), stream);
 }
 
-static int step_envs_host(chub_env *e, const uint8_t *mask, const float *actions, const double *exo_z, float *obs, float *reward, uint8_t *done,
-                          int load_mode) {
-    if (!e || !mask || !actions || !obs || !reward || !done) return fail(CHUB_ERR_ARG, "null argument");
+// chub_run_steps on a PHILOX handle that runs the one-launch step (k_step_fused): a span of lock-step steps goes out as ONE launch
+// (k_steps_fused: the workgroup that owns an env's slots, records and tail goes from step to step by itself).  Not on a tape handle,
+// on per-env clocks, under the per-kernel profiler or with chub_options.span_steps = 1.  (The steps of chub_run_steps are row steps
+// into the packed block: no tape and no decision bits to look for.)
+static bool span_ok(const chub_env *e, int n_batches) {
+    return e->plan.one_launch != ONE_NONE && e->plan.span_size_ok && e->plan.span_steps != 1 && !e->per_env && !e->prof_on && !e->tape_only &&
+           n_batches <= 8 && e->tick != 0 && !e->hp.telemetry;
+}
+
+static int run_span(chub_env *e, const float *const *batches, int n_batches, float *const *packed2, int64_t first, int k, hipStream_t s) {
     HIP_TRY(hipSetDevice(e->device));
-    const size_t N = (size_t) e->hp.n_envs, A = (size_t) e->hp.act_dim, D = (size_t) e->hp.obs_dim;
-    HIP_TRY(hipMemcpy(e->d_actions, actions, N * A * sizeof(float), hipMemcpyHostToDevice));
-    if (e->hp.rng_mode == CHUB_RNG_COMPAT) {
-        if (!exo_z) return fail(CHUB_ERR_ARG, "COMPAT mode needs exo_z");
-        HIP_TRY(hipMemcpy(e->d_exo_z, exo_z, N * 3 * sizeof(double), hipMemcpyHostToDevice));
-    }
-    int rc = load_mode ? chub_step_load_envs_device(e, mask, e->d_actions, e->d_exo_z, e->d_obs, e->d_reward, e->d_done, nullptr)
-                       : chub_step_envs_device(e, mask, e->d_actions, e->d_exo_z, e->d_obs, e->d_reward, e->d_done, nullptr);
-    if (rc) return rc;
-    std::vector<float> o(N * D), r(N);
-    std::vector<uint8_t> d(N);
-    HIP_TRY(hipMemcpy(o.data(), e->d_obs, o.size() * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(r.data(), e->d_reward, N * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(d.data(), e->d_done, N, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < N; i++)
-        if (mask[i]) {
-            memcpy(obs + i * D, &o[i * D], D * sizeof(float));
-            reward[i] = r[i];
-            done[i] = d[i];
+    (void) hipGetLastError();
+    if (e->t + k > 96) return fail(CHUB_ERR_ARG, "a span of steps ends at the day's end at the latest");
+    // the span's first step, as chub_step_device_packed would be asked for it; the kernel moves on through the batches and the two blocks
+    const StepCall c = step_call(nullptr, batches[first % n_batches], nullptr, packed_out(e, packed2[first & 1]), 0);
+    const MaskView all = {nullptr, 0, e->hp.n_envs - 1};
+    StepArgs sa;
+    if (const int rc = fill_args(e, c, 2, all, e->tick + 1u, s, sa)) return rc;
+    launch_steps_fused(e->hp, e->plan, e->d_ctx, sa, s, packed_ptrs(e), k, e->price_count, first, batches, n_batches, packed2);
+    HIP_TRY(hipGetLastError());
+    e->tick += (uint32_t) k;
+    advance_clocks(e, c, 2, k);
+    return note_served(e, nullptr, 2, s);
+}
+
+// A run of steps issued from C: what a host loop of chub_reset_device / chub_step_device_packed / chub_step_gather calls does, without
+// a trip through the host language per step (multi-GPU shards of a few thousand envs are otherwise bound by the host's issue rate)
+int chub_run_steps(chub_env *e, chub_comm *comm, const float *const *d_action_batches, int n_batches, float *const *d_packed2,
+                   float *const *d_gathered2, float *d_reset_obs, int64_t first_step, int64_t n_steps, void *stream) {
+    if (!e || !d_action_batches || n_batches <= 0 || !d_packed2 || !d_packed2[0] || !d_packed2[1] || !d_reset_obs || first_step < 0 ||
+        n_steps < 0)
+        return fail(CHUB_ERR_ARG, "bad argument");
+    for (int64_t i = first_step; i < first_step + n_steps; i++) {
+        int rc;
+        if (i % 96 == 0 && (rc = chub_reset_device(e, nullptr, nullptr, d_reset_obs, stream))) return rc;
+        // a SPAN of steps in ONE launch (k_steps_fused) where the handle runs the one-launch step anyway: up to the day's end or the call's
+        if (!comm) {
+            int64_t k = first_step + n_steps - i;
+            k = k < 96 - i % 96 ? k : 96 - i % 96;
+            k = k < 96 - e->t ? k : 96 - e->t;  // (the handle's own clock need not be i % 96: a caller may step on past `done` -- the span ends where the clock wraps)
+            if (e->plan.span_steps > 1 && k > e->plan.span_steps) k = e->plan.span_steps;
+            if (k >= 2 && span_ok(e, n_batches)) {
+                if ((rc = run_span(e, d_action_batches, n_batches, d_packed2, i, (int) k, (hipStream_t) stream))) return rc;
+                i += k - 1;
+                continue;
+            }
         }
+        const float *act = d_action_batches[i % n_batches];
+        float *packed = d_packed2[i & 1];
+        if (comm) rc = chub_step_gather(e, comm, act, packed, d_gathered2 ? d_gathered2[i & 1] : nullptr, stream);
+        else rc = chub_step_device_packed(e, act, nullptr, packed, stream);
+        if (rc) return rc;
+    }
     return CHUB_OK;
-}
-
-int chub_step_envs(chub_env *e, const uint8_t *mask, const float *actions, const double *exo_z, float *obs, float *reward, uint8_t *done) {
-    return step_envs_host(e, mask, actions, exo_z, obs, reward, done, 0);
-}
-
-int chub_step_load_envs(chub_env *e, const uint8_t *mask, const float *actions, const double *exo_z, float *obs, float *reward, uint8_t *done) {
-    return step_envs_host(e, mask, actions, exo_z, obs, reward, done, 1);
 }
 
 // slot of day (and, if asked, the Philox tick of the last launch) of every env
@@ -1639,24 +1574,6 @@ int chub_clock_groups(chub_env *e) {  // number of distinct clocks among the env
     return (int) (std::unique(c.begin(), c.end()) - c.begin());
 }
 
-int chub_reset(chub_env *e, const int32_t *exo_days, const double *exo_z, float *obs) {
-    if (!e || !obs) return fail(CHUB_ERR_ARG, "null argument");
-    HIP_TRY(hipSetDevice(e->device));
-    const size_t N = (size_t) e->hp.n_envs;
-    if (e->hp.rng_mode == CHUB_RNG_COMPAT) {
-        if (!exo_days || !exo_z) return fail(CHUB_ERR_ARG, "COMPAT mode needs exo_days and exo_z");
-        for (size_t i = 0; i < N; i++)
-            if (exo_days[2 * i] < 0 || exo_days[2 * i] >= 100 || exo_days[2 * i + 1] < 0 || exo_days[2 * i + 1] >= 150)
-                return fail(CHUB_ERR_ARG, "exo_days out of range");
-        HIP_TRY(hipMemcpy(e->d_exo_days, exo_days, N * 2 * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(e->d_exo_z, exo_z, N * 3 * sizeof(double), hipMemcpyHostToDevice));
-    }
-    int rc = chub_reset_device(e, e->d_exo_days, e->d_exo_z, e->d_obs, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(obs, e->d_obs, N * (size_t) e->hp.obs_dim * sizeof(float), hipMemcpyDeviceToHost));
-    return CHUB_OK;
-}
-
 // The output arrays of a host-pointer step, as the device sees them: pinned host memory (hipHostMalloc: chub_alloc_host, what
 // VecChargingHub hands in) is mapped into the device's address space, so the tail kernel can store its rows straight into the
 // caller's arrays -- they cross PCIe as posted writes while the kernel runs instead of in a copy phase of their own behind it.
@@ -1671,10 +1588,10 @@ static bool device_view(void *host, void **dev) {
     return true;
 }
 
-// Host-pointer step: the reference-shaped API (numpy in / numpy out), bounded by PCIe: (A + D + 2) * 4 bytes per env and
-// step.  A private stream; the actions go up from the handle's pinned buffer when the caller filled that one
-// (chub_host_actions: one DMA, no staging copy), otherwise through the runtime's pageable-copy path; outputs come back
-// into the caller's arrays.
+// ---- host-pointer entry points: the reference-shaped API (numpy in / numpy out), bounded by PCIe: (A + D + 2) * 4 bytes per env and
+// step.  Each stages its arrays with the helpers below and goes through run_call.  chub_step and chub_step_bits work on a private
+// stream with async copies; every other one on the null stream with blocking copies.
+
 static int host_path_init(chub_env *e) {
     if (e->host_stream) return CHUB_OK;
     const size_t N = (size_t) e->hp.n_envs, A = (size_t) e->hp.act_dim;
@@ -1692,43 +1609,135 @@ int chub_host_actions(chub_env *e, float **out) {
     return CHUB_OK;
 }
 
-int chub_step(chub_env *e, const float *actions, const double *exo_z, float *obs, float *reward, uint8_t *done) {
-    if (!e || !actions || !obs || !reward || !done) return fail(CHUB_ERR_ARG, "null argument");
+// One input array on its way to the device.  s null: a blocking copy into the handle's staging `d_stage`; otherwise an async copy on s --
+// from the handle's pinned buffers (chub_host_actions, chub_host_bits) one DMA, any other host pointer is staged by the HIP runtime.
+// in_place: pinned host memory is not copied at all, the kernels READ it where it is.  d_in: what the kernels are given
+static int upload(void *d_stage, const void *host, size_t bytes, hipStream_t s, bool in_place, const void **d_in) {
+    void *v = nullptr;
+    if (in_place && device_view((void *) host, &v)) {
+        *d_in = v;
+        return CHUB_OK;
+    }
+    if (s) HIP_TRY(hipMemcpyAsync(d_stage, host, bytes, hipMemcpyHostToDevice, s));
+    else HIP_TRY(hipMemcpy(d_stage, host, bytes, hipMemcpyHostToDevice));
+    *d_in = d_stage;
+    return CHUB_OK;
+}
+
+// Where a host-pointer step stores: pinned output arrays (try_direct, see device_view) are written by the tail kernel itself;
+// any other host memory gets the handle's device staging and fetch_out behind the launch
+static OutSink host_out(const chub_env *e, float *obs, float *reward, uint8_t *done, bool try_direct, bool &direct) {
+    void *v_obs = nullptr, *v_rew = nullptr, *v_done = nullptr;
+    direct = try_direct && device_view(obs, &v_obs) && device_view(reward, &v_rew) && device_view(done, &v_done);
+    return direct ? dense_out(e, (float *) v_obs, (float *) v_rew, (uint8_t *) v_done) : dense_out(e, e->d_obs, e->d_reward, e->d_done);
+}
+
+// ... the copy back from that staging (on s, or blocking: as upload).  mask: only the rows of the envs it names are written;
+// reward and done null: a reset's obs alone
+static int fetch_out(chub_env *e, const uint8_t *mask, float *obs, float *reward, uint8_t *done, hipStream_t s) {
+    const size_t N = (size_t) e->hp.n_envs, D = (size_t) e->hp.obs_dim;
+    auto back = [s](void *dst, const void *src, size_t bytes) {
+        return s ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
+    };
+    if (!mask) {
+        HIP_TRY(back(obs, e->d_obs, N * D * sizeof(float)));
+        if (reward) HIP_TRY(back(reward, e->d_reward, N * sizeof(float)));
+        if (done) HIP_TRY(back(done, e->d_done, N));
+        return CHUB_OK;
+    }
+    std::vector<float> o(N * D), r(N);
+    std::vector<uint8_t> d(N);
+    HIP_TRY(hipMemcpy(o.data(), e->d_obs, N * D * sizeof(float), hipMemcpyDeviceToHost));
+    if (reward) HIP_TRY(hipMemcpy(r.data(), e->d_reward, N * sizeof(float), hipMemcpyDeviceToHost));
+    if (done) HIP_TRY(hipMemcpy(d.data(), e->d_done, N, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < N; i++)
+        if (mask[i]) {
+            memcpy(obs + i * D, &o[i * D], D * sizeof(float));
+            if (reward) reward[i] = r[i];
+            if (done) done[i] = d[i];
+        }
+    return CHUB_OK;
+}
+
+// a reset's PV / wind days (REN:51-53) index the 100 x 96 and 150 x 96 tables; mask: the values of the envs outside it are not looked at
+static int check_exo_days(const chub_env *e, const uint8_t *mask, const int32_t *exo_days) {
+    for (size_t i = 0; i < (size_t) e->hp.n_envs; i++)
+        if ((!mask || mask[i]) && (exo_days[2 * i] < 0 || exo_days[2 * i] >= 100 || exo_days[2 * i + 1] < 0 || exo_days[2 * i + 1] >= 150))
+            return fail(CHUB_ERR_ARG, "exo_days out of range");
+    return CHUB_OK;
+}
+
+// chub_reset (mask null) and chub_reset_envs: full-size arrays, only the rows of the named envs are read and written
+static int reset_host(chub_env *e, const uint8_t *mask, const int32_t *exo_days, const double *exo_z, float *obs) {
     HIP_TRY(hipSetDevice(e->device));
-    int rc = host_path_init(e);
+    const size_t N = (size_t) e->hp.n_envs;
+    int rc = check_compat_variates(e, true, exo_days, exo_z);
     if (rc) return rc;
-    const size_t N = (size_t) e->hp.n_envs, A = (size_t) e->hp.act_dim, D = (size_t) e->hp.obs_dim;
-    hipStream_t s = e->host_stream;
+    const void *d_days = e->d_exo_days, *d_z = e->d_exo_z;
+    if (e->hp.rng_mode == CHUB_RNG_COMPAT) {
+        if ((rc = check_exo_days(e, mask, exo_days))) return rc;
+        if ((rc = upload(e->d_exo_days, exo_days, N * 2 * sizeof(int32_t), nullptr, false, &d_days))) return rc;
+        if ((rc = upload(e->d_exo_z, exo_z, N * 3 * sizeof(double), nullptr, false, &d_z))) return rc;
+    }
+    if ((rc = run_call(e, reset_call(e, mask, (const int32_t *) d_days, (const double *) d_z, e->d_obs), nullptr))) return rc;
+    return fetch_out(e, mask, obs, nullptr, nullptr, nullptr);
+}
+
+int chub_reset(chub_env *e, const int32_t *exo_days, const double *exo_z, float *obs) {
+    if (!e || !obs) return fail(CHUB_ERR_ARG, "null argument");
+    return reset_host(e, nullptr, exo_days, exo_z, obs);
+}
+
+int chub_reset_envs(chub_env *e, const uint8_t *mask, const int32_t *exo_days, const double *exo_z, float *obs) {
+    if (!e || !mask || !obs) return fail(CHUB_ERR_ARG, "null argument");
+    return reset_host(e, mask, exo_days, exo_z, obs);
+}
+
+// The host-pointer step on rows of actions.  s: the handle's private stream (chub_step: async copies, pinned arrays used where they are, one
+// stream synchronisation at the end) or null (blocking copies through the staging)
+static int step_host(chub_env *e, const uint8_t *mask, const float *actions, const double *exo_z, float *obs, float *reward, uint8_t *done,
+                     int load_mode, hipStream_t s) {
+    int rc = check_compat_variates(e, false, nullptr, exo_z);
+    if (rc) return rc;
+    const size_t N = (size_t) e->hp.n_envs, A = (size_t) e->hp.act_dim;
     // A handful of envs (the drop-in class: one): inputs that sit in pinned host memory are READ BY THE KERNELS where they are -- a
     // few hundred bytes over PCIe -- instead of going through a copy engine first: the step is then one launch set and one
     // stream synchronisation, no copy in either direction.  Larger batches and pageable memory take the DMA as before.
-    const bool tiny = N * A * sizeof(float) <= 16384;
-    const double *d_z = e->d_exo_z;
-    if (e->hp.rng_mode == CHUB_RNG_COMPAT) {
-        if (!exo_z) return fail(CHUB_ERR_ARG, "COMPAT mode needs exo_z");
-        void *vz = nullptr;
-        if (tiny && device_view((void *) exo_z, &vz)) d_z = (const double *) vz;
-        else HIP_TRY(hipMemcpyAsync(e->d_exo_z, exo_z, N * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    }
-    const float *d_act = e->d_actions;
-    void *va = nullptr;
-    if (tiny && device_view((void *) actions, &va)) d_act = (const float *) va;
-    else  // from the handle's pinned buffer (chub_host_actions) this is one DMA; any other host pointer is staged by the HIP runtime
-        HIP_TRY(hipMemcpyAsync(e->d_actions, actions, N * A * sizeof(float), hipMemcpyHostToDevice, s));
-    void *v_obs = nullptr, *v_rew = nullptr, *v_done = nullptr;
-    if (device_view(obs, &v_obs) && device_view(reward, &v_rew) && device_view(done, &v_done)) {
-        // pinned output arrays: the tail kernel stores into them directly (see device_view)
-        rc = chub_step_device(e, d_act, d_z, (float *) v_obs, (float *) v_rew, (uint8_t *) v_done, s);
-        if (rc) return rc;
-    } else {
-        rc = chub_step_device(e, d_act, d_z, e->d_obs, e->d_reward, e->d_done, s);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(obs, e->d_obs, N * D * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(reward, e->d_reward, N * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(done, e->d_done, N, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
+    const bool tiny = s && N * A * sizeof(float) <= 16384;
+    const void *d_z = e->d_exo_z, *d_act = nullptr;
+    if (e->hp.rng_mode == CHUB_RNG_COMPAT && (rc = upload(e->d_exo_z, exo_z, N * 3 * sizeof(double), s, tiny, &d_z))) return rc;
+    if ((rc = upload(e->d_actions, actions, N * A * sizeof(float), s, tiny, &d_act))) return rc;
+    bool direct = false;
+    const OutSink out = host_out(e, obs, reward, done, s != nullptr, direct);
+    if ((rc = run_call(e, step_call(mask, (const float *) d_act, (const double *) d_z, out, load_mode), s))) return rc;
+    if (!direct && (rc = fetch_out(e, mask, obs, reward, done, s))) return rc;
+    if (s) HIP_TRY(hipStreamSynchronize(s));
     return CHUB_OK;
+}
+
+int chub_step(chub_env *e, const float *actions, const double *exo_z, float *obs, float *reward, uint8_t *done) {
+    if (!e || !actions || !obs || !reward || !done) return fail(CHUB_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(e->device));
+    if (const int rc = host_path_init(e)) return rc;
+    return step_host(e, nullptr, actions, exo_z, obs, reward, done, 0, e->host_stream);
+}
+
+int chub_step_load(chub_env *e, const float *actions, const double *exo_z, float *obs, float *reward, uint8_t *done) {
+    if (!e || !actions || !obs || !reward || !done) return fail(CHUB_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(e->device));
+    return step_host(e, nullptr, actions, exo_z, obs, reward, done, 1, nullptr);
+}
+
+int chub_step_envs(chub_env *e, const uint8_t *mask, const float *actions, const double *exo_z, float *obs, float *reward, uint8_t *done) {
+    if (!e || !mask || !actions || !obs || !reward || !done) return fail(CHUB_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(e->device));
+    return step_host(e, mask, actions, exo_z, obs, reward, done, 0, nullptr);
+}
+
+int chub_step_load_envs(chub_env *e, const uint8_t *mask, const float *actions, const double *exo_z, float *obs, float *reward, uint8_t *done) {
+    if (!e || !mask || !actions || !obs || !reward || !done) return fail(CHUB_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(e->device));
+    return step_host(e, mask, actions, exo_z, obs, reward, done, 1, nullptr);
 }
 
 // ---- packed-action form of the host-pointer step: one bit per pile + the two tail floats (16 bytes per env for hubs of up to
@@ -1757,42 +1766,23 @@ int chub_host_bits(chub_env *e, uint64_t **bits_out, float **tail_out) {
     return CHUB_OK;
 }
 
-// dense outputs (d_reward, d_done) or the packed block (d_packed: obs at stride D + 2, reward and done as floats behind each row)
-static int step_bits_device(chub_env *e, const uint64_t *d_pile_bits, const float *d_tail, const double *d_exo_z, float *d_obs,
-                            float *d_reward, uint8_t *d_done, float *d_packed, void *stream) {
-    if (e->tick == 0) return fail(CHUB_ERR_ARG, "step() before reset()");
-    if (e->tape_only && !e->tape_pk)
-        return fail(CHUB_ERR_ARG, "a handle with registered tape classes steps through chub_step_tape / chub_step_tape_env only (its class "
-                                  "rows hold the caller's arrival SoCs: cars admitted by this build's own draws would be given them)");
-    HIP_TRY(hipSetDevice(e->device));
-    const int D = e->hp.obs_dim;
-    const float *rows = nullptr;
-    if (e->hp.packed && e->hp.rng_mode == CHUB_RNG_PHILOX && !e->tape_pk) {
-        // the production kernel reads the bits themselves: 8 bytes per env and word instead of a row of floats (and no expansion)
-        e->cur_bits = d_pile_bits;
-        e->cur_tail = d_tail;
-    } else {
-        launch_expand_bits(e->hp, d_pile_bits, d_tail, e->d_actions, (hipStream_t) stream);
-        HIP_TRY(hipGetLastError());
-        rows = e->d_actions;
-    }
-    const int rc = d_packed ? step_common(e, rows, d_exo_z, d_packed, D + 2, d_packed + D, D + 2, nullptr, d_packed + D + 1, stream)
-                            : step_common(e, rows, d_exo_z, d_obs, D, d_reward, 1, d_done, nullptr, stream);
-    e->cur_bits = nullptr;
-    e->cur_tail = nullptr;
-    return rc;
+static StepCall bits_call(const uint64_t *d_pile_bits, const float *d_tail, const double *d_exo_z, const OutSink &out) {
+    StepCall c = step_call(nullptr, nullptr, d_exo_z, out, 0);
+    c.bits = d_pile_bits;
+    c.tail = d_tail;
+    return c;
 }
 
 int chub_step_bits_device(chub_env *e, const uint64_t *d_pile_bits, const float *d_tail, const double *d_exo_z, float *d_obs,
                           float *d_reward, uint8_t *d_done, void *stream) {
     if (!e || !d_pile_bits || !d_tail || !d_obs || !d_reward || !d_done) return fail(CHUB_ERR_ARG, "null argument");
-    return step_bits_device(e, d_pile_bits, d_tail, d_exo_z, d_obs, d_reward, d_done, nullptr, stream);
+    return run_call(e, bits_call(d_pile_bits, d_tail, d_exo_z, dense_out(e, d_obs, d_reward, d_done)), (hipStream_t) stream);
 }
 
 int chub_step_bits_device_packed(chub_env *e, const uint64_t *d_pile_bits, const float *d_tail, const double *d_exo_z, float *d_packed,
                                  void *stream) {
     if (!e || !d_pile_bits || !d_tail || !d_packed) return fail(CHUB_ERR_ARG, "null argument");
-    return step_bits_device(e, d_pile_bits, d_tail, d_exo_z, nullptr, nullptr, nullptr, d_packed, stream);
+    return run_call(e, bits_call(d_pile_bits, d_tail, d_exo_z, packed_out(e, d_packed)), (hipStream_t) stream);
 }
 
 int chub_step_bits(chub_env *e, const uint64_t *pile_bits, const float *tail, const double *exo_z, float *obs, float *reward,
@@ -1801,31 +1791,20 @@ int chub_step_bits(chub_env *e, const uint64_t *pile_bits, const float *tail, co
     HIP_TRY(hipSetDevice(e->device));
     int rc = bits_path_init(e);
     if (rc) return rc;
-    const size_t N = (size_t) e->hp.n_envs, D = (size_t) e->hp.obs_dim, W = (size_t) ((e->hp.S[0] + e->hp.S[1] + 63) / 64);
+    if ((rc = check_compat_variates(e, false, nullptr, exo_z))) return rc;
+    const size_t N = (size_t) e->hp.n_envs, W = (size_t) ((e->hp.S[0] + e->hp.S[1] + 63) / 64);
+    const size_t n_bits = N * W * sizeof(uint64_t), n_tail = N * 2 * sizeof(float);
     hipStream_t s = e->host_stream;
-    if (e->hp.rng_mode == CHUB_RNG_COMPAT) {
-        if (!exo_z) return fail(CHUB_ERR_ARG, "COMPAT mode needs exo_z");
-        HIP_TRY(hipMemcpyAsync(e->d_exo_z, exo_z, N * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    }
-    // from the handle's pinned block (chub_host_bits) this is ONE DMA; any other host pointers are staged by the HIP runtime
-    if (pile_bits == e->h_bits && tail == e->h_tail) {
-        HIP_TRY(hipMemcpyAsync(e->d_bits, pile_bits, N * W * sizeof(uint64_t) + N * 2 * sizeof(float), hipMemcpyHostToDevice, s));
-    } else {
-        HIP_TRY(hipMemcpyAsync(e->d_bits, pile_bits, N * W * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(e->d_tail, tail, N * 2 * sizeof(float), hipMemcpyHostToDevice, s));
-    }
-    void *v_obs = nullptr, *v_rew = nullptr, *v_done = nullptr;
-    const bool direct = device_view(obs, &v_obs) && device_view(reward, &v_rew) && device_view(done, &v_done);
-    if (direct) {
-        rc = chub_step_bits_device(e, e->d_bits, e->d_tail, e->d_exo_z, (float *) v_obs, (float *) v_rew, (uint8_t *) v_done, s);
-        if (rc) return rc;
-    } else {
-        rc = chub_step_bits_device(e, e->d_bits, e->d_tail, e->d_exo_z, e->d_obs, e->d_reward, e->d_done, s);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(obs, e->d_obs, N * D * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(reward, e->d_reward, N * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(done, e->d_done, N, hipMemcpyDeviceToHost, s));
-    }
+    const void *d_z = e->d_exo_z, *d_bits = nullptr, *d_tail = e->d_tail;
+    if (e->hp.rng_mode == CHUB_RNG_COMPAT && (rc = upload(e->d_exo_z, exo_z, N * 3 * sizeof(double), s, false, &d_z))) return rc;
+    // from the handle's pinned block (chub_host_bits) bits and tail go up in ONE DMA
+    const bool one_block = pile_bits == e->h_bits && tail == e->h_tail;
+    if ((rc = upload(e->d_bits, pile_bits, one_block ? n_bits + n_tail : n_bits, s, false, &d_bits))) return rc;
+    if (!one_block && (rc = upload(e->d_tail, tail, n_tail, s, false, &d_tail))) return rc;
+    bool direct = false;
+    const OutSink out = host_out(e, obs, reward, done, true, direct);
+    if ((rc = run_call(e, bits_call((const uint64_t *) d_bits, (const float *) d_tail, (const double *) d_z, out), s))) return rc;
+    if (!direct && (rc = fetch_out(e, nullptr, obs, reward, done, s))) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return CHUB_OK;
 }
@@ -2170,6 +2149,27 @@ int chub_set_station_queue(chub_env *e, const int32_t *line) {
     return CHUB_OK;
 }
 
+// the temporary device buffers of one tape call: freed when the call returns, once everything that may still read them has run
+namespace {
+struct TapeBuffers {
+    std::vector<void *> held;
+    ~TapeBuffers() {
+        if (held.empty()) return;
+        (void) hipDeviceSynchronize();
+        for (void *p : held) (void) hipFree(p);
+    }
+    // a device copy of `bytes` of host memory
+    int put(const void *host, size_t bytes, const void **d_out) {
+        void *d = nullptr;
+        HIP_TRY(hipMalloc(&d, bytes));
+        held.push_back(d);
+        HIP_TRY(hipMemcpy(d, host, bytes, hipMemcpyHostToDevice));
+        *d_out = d;
+        return CHUB_OK;
+    }
+};
+}  // namespace
+
 int chub_step_tape(chub_env *e, const float *actions, const uint64_t *pk_tape, const uint32_t *car_tape, float *obs, float *reward,
                    uint8_t *done) {
     return chub_step_tape_env(e, actions, pk_tape, car_tape, nullptr, nullptr, 0, obs, reward, done);
@@ -2187,7 +2187,9 @@ int chub_step_tape_env(chub_env *e, const float *actions, const uint64_t *pk_tap
     if (e->tape_stale) return fail(CHUB_ERR_ARG, "chub_tape_clear_soc was called: reset (chub_reset_tape) before the next tape step");
     HIP_TRY(hipSetDevice(e->device));
     const size_t N = (size_t) e->hp.n_envs, S = (size_t) (e->hp.S[0] + e->hp.S[1]);
-    uint32_t *d_hv = nullptr;
+    TapeBuffers tb;
+    int rc;
+    const void *d_hv = nullptr, *d_z = nullptr, *d_pk = nullptr, *d_ct = nullptr, *d_act = nullptr;
     if (hv_tape) {
         // at most as many arrivals per step as the handle's forecourt can see from its own tables (the waiting list's explicit entries
         // are sized for that, chub_create), each with its SoC on the tape
@@ -2195,54 +2197,21 @@ int chub_step_tape_env(chub_env *e, const float *actions, const uint64_t *pk_tap
         for (size_t i = 0; i < N; i++)
             if (hv_tape[i * (size_t) hv_w] > most || hv_tape[i * (size_t) hv_w] > (uint32_t) (hv_w - 1))
                 return fail(CHUB_ERR_ARG, "hv_tape: more FCEV arrivals in one step than the handle's forecourt (or the tape's width) takes");
-        HIP_TRY(hipMalloc((void **) &d_hv, N * (size_t) hv_w * sizeof(uint32_t)));
-        hipError_t he1 = hipMemcpy(d_hv, hv_tape, N * (size_t) hv_w * sizeof(uint32_t), hipMemcpyHostToDevice);
-        if (he1 == hipSuccess) he1 = hipMemcpy(e->d_exo_z, exo_z, N * 3 * sizeof(double), hipMemcpyHostToDevice);
-        if (he1 != hipSuccess) {
-            (void) hipFree(d_hv);
-            return fail(CHUB_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(he1));
-        }
+        if ((rc = tb.put(hv_tape, N * (size_t) hv_w * sizeof(uint32_t), &d_hv))) return rc;
+        if ((rc = upload(e->d_exo_z, exo_z, N * 3 * sizeof(double), nullptr, false, &d_z))) return rc;
     }
     // the car tape is in hub order [N][S][2] (station 0's slots first), which is the kernel's own slot order
-    const std::vector<uint32_t> ct(car_tape, car_tape + 2 * N * S);
-    uint64_t *d_pk = nullptr;
-    uint32_t *d_ct = nullptr;
-    hipError_t he = hipMalloc((void **) &d_pk, 2 * N * sizeof(uint64_t));
-    if (he == hipSuccess) he = hipMalloc((void **) &d_ct, ct.size() * sizeof(uint32_t));
-    if (he != hipSuccess) {
-        (void) hipFree(d_pk);
-        (void) hipFree(d_hv);
-        return fail(CHUB_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(he));
-    }
-    int rc = CHUB_OK;
-    auto done_ = [&](int code) {
-        (void) hipDeviceSynchronize();
-        (void) hipFree(d_pk);
-        (void) hipFree(d_ct);
-        (void) hipFree(d_hv);
-        return code;
-    };
-    if (hipMemcpy(d_pk, pk_tape, 2 * N * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_ct, ct.data(), ct.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(e->d_actions, actions, N * (size_t) e->hp.act_dim * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-        return done_(fail(CHUB_ERR_HIP, "hipMemcpy failed"));
-    e->tape_pk = d_pk;
-    e->tape_car = d_ct;
-    e->tape_hv = d_hv;
-    e->tape_hv_w = hv_w;
-    e->tape_tail = d_hv != nullptr;
-    rc = chub_step_device(e, e->d_actions, d_hv ? e->d_exo_z : nullptr, e->d_obs, e->d_reward, e->d_done, nullptr);
-    e->tape_pk = nullptr;
-    e->tape_car = nullptr;
-    e->tape_hv = nullptr;
-    e->tape_hv_w = 0;
-    e->tape_tail = false;
-    if (rc) return done_(rc);
-    if (hipMemcpy(obs, e->d_obs, N * (size_t) e->hp.obs_dim * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(reward, e->d_reward, N * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(done, e->d_done, N, hipMemcpyDeviceToHost) != hipSuccess)
-        return done_(fail(CHUB_ERR_HIP, "hipMemcpy failed"));
-    return done_(CHUB_OK);
+    if ((rc = tb.put(pk_tape, 2 * N * sizeof(uint64_t), &d_pk))) return rc;
+    if ((rc = tb.put(car_tape, 2 * N * S * sizeof(uint32_t), &d_ct))) return rc;
+    if ((rc = upload(e->d_actions, actions, N * (size_t) e->hp.act_dim * sizeof(float), nullptr, false, &d_act))) return rc;
+    StepCall c = step_call(nullptr, (const float *) d_act, (const double *) d_z, dense_out(e, e->d_obs, e->d_reward, e->d_done), 0);
+    c.pk_tape = (const uint64_t *) d_pk;
+    c.car_tape = (const uint32_t *) d_ct;
+    c.hv_tape = (const uint32_t *) d_hv;
+    c.hv_w = hv_w;
+    c.tail_tape = d_hv != nullptr;
+    if ((rc = run_call(e, c, nullptr))) return rc;
+    return fetch_out(e, nullptr, obs, reward, done, nullptr);
 }
 
 int chub_reset_tape(chub_env *e, const uint32_t *occ_tape, const uint32_t *car_tape, float *obs) {
@@ -2255,42 +2224,31 @@ int chub_reset_tape_env(chub_env *e, const uint32_t *occ_tape, const uint32_t *c
     if (!e || !occ_tape || !car_tape || !obs) return fail(CHUB_ERR_ARG, "null argument");
     if (e->env_params) return refuse_params("tape mode (chub_reset_tape / chub_reset_tape_env)");
     if ((exo_days != nullptr) != (exo_z != nullptr)) return fail(CHUB_ERR_ARG, "the tail's tape of a reset is exo_days [N][2] AND exo_z [N][3]");
-    if (exo_days)
-        for (size_t i = 0; i < (size_t) e->hp.n_envs; i++)
-            if (exo_days[2 * i] < 0 || exo_days[2 * i] >= 100 || exo_days[2 * i + 1] < 0 || exo_days[2 * i + 1] >= 150)
-                return fail(CHUB_ERR_ARG, "exo_days out of range");
+    int rc;
+    if (exo_days && (rc = check_exo_days(e, nullptr, exo_days))) return rc;
     if (e->hp.rng_mode != CHUB_RNG_PHILOX || !(e->hp.packed || e->hp.soc_curves))
         return fail(CHUB_ERR_ARG, "tape mode drives the packed PHILOX slot kernel: the hub shape must be one it covers");
     if (e->capturing) return fail(CHUB_ERR_ARG, "tape mode cannot be captured");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
     const size_t N = (size_t) e->hp.n_envs, S = (size_t) (e->hp.S[0] + e->hp.S[1]);
-    uint32_t *d_ct = nullptr;
-    HIP_TRY(hipMalloc((void **) &d_ct, 2 * N * S * sizeof(uint32_t)));
-    auto done_ = [&](int code) {
-        (void) hipDeviceSynchronize();
-        (void) hipFree(d_ct);
-        return code;
-    };
+    TapeBuffers tb;
+    const void *d_ct = nullptr, *d_days = nullptr, *d_z = nullptr;
+    if ((rc = tb.put(car_tape, 2 * N * S * sizeof(uint32_t), &d_ct))) return rc;
     // the reset is the launch with argument tick + 1 - base: its slot kernel reads the units' occupancy draws from pk[that & 1],
     // where k_reset_levels would have left this build's own
     const uint32_t arg = e->tick + 1u - e->graph_base;
-    if (hipMemcpy((void *) e->st.pk[arg & 1u], occ_tape, 2 * N * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_ct, car_tape, 2 * N * S * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
-        return done_(fail(CHUB_ERR_HIP, "hipMemcpy failed"));
-    if (exo_days && (hipMemcpy(e->d_exo_days, exo_days, 2 * N * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
-                     hipMemcpy(e->d_exo_z, exo_z, 3 * N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess))
-        return done_(fail(CHUB_ERR_HIP, "hipMemcpy failed"));
-    e->tape_car = d_ct;
-    e->tape_tail = exo_days != nullptr;
-    int rc = chub_reset_device(e, exo_days ? e->d_exo_days : nullptr, exo_days ? e->d_exo_z : nullptr, e->d_obs, nullptr);
-    e->tape_car = nullptr;
-    e->tape_tail = false;
-    if (rc) return done_(rc);
+    HIP_TRY(hipMemcpy((void *) e->st.pk[arg & 1u], occ_tape, 2 * N * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (exo_days) {
+        if ((rc = upload(e->d_exo_days, exo_days, 2 * N * sizeof(int32_t), nullptr, false, &d_days))) return rc;
+        if ((rc = upload(e->d_exo_z, exo_z, 3 * N * sizeof(double), nullptr, false, &d_z))) return rc;
+    }
+    StepCall c = reset_call(e, nullptr, (const int32_t *) d_days, (const double *) d_z, e->d_obs);
+    c.car_tape = (const uint32_t *) d_ct;
+    c.tail_tape = exo_days != nullptr;
+    if ((rc = run_call(e, c, nullptr))) return rc;
     e->tape_stale = false;  // evs_reset has wiped every slot
-    if (hipMemcpy(obs, e->d_obs, N * (size_t) e->hp.obs_dim * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
-        return done_(fail(CHUB_ERR_HIP, "hipMemcpy failed"));
-    return done_(CHUB_OK);
+    return fetch_out(e, nullptr, obs, nullptr, nullptr, nullptr);
 }
 
 int chub_random_actions_device(chub_env *e, uint64_t key, uint32_t batch, float *d_actions, void *stream) {

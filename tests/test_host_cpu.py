@@ -232,3 +232,79 @@ def test_canonical_division_by_the_constant_is_the_division_itself():
     also exercised on 4e8 dividends of the walk's own shape, incl. the smallest and largest second draws."""
     import orclib
     assert orclib.orc.orc_check_canon_division(400_000_000, 20260105) == 0
+
+
+# every reset / step entry point of include/chub.h: (name, arguments in order).  "h" the handle, "p" a pointer the call requires,
+# "o" a pointer it may do without, "c" the communicator, "i32" / "i64" integers
+_RESET_STEP_ENTRY_POINTS = [
+    ("chub_reset", "h o o p"),
+    ("chub_step", "h p o p p p"),
+    ("chub_step_bits", "h p p o p p p"),
+    ("chub_step_bits_device", "h p p o p p p o"),
+    ("chub_step_bits_device_packed", "h p p o p o"),
+    ("chub_reset_device", "h o o p o"),
+    ("chub_step_device", "h p o p p p o"),
+    ("chub_reset_envs", "h p o o p"),
+    ("chub_step_envs", "h p p o p p p"),
+    ("chub_reset_envs_device", "h p o o p o"),
+    ("chub_step_envs_device", "h p p o p p p o"),
+    ("chub_step_load", "h p o p p p"),
+    ("chub_step_load_device", "h p o p p p o"),
+    ("chub_step_load_envs", "h p p o p p p"),
+    ("chub_step_load_envs_device", "h p p o p p p o"),
+    ("chub_step_device_packed", "h p o p o"),
+    ("chub_step_gather", "h c p o o o"),
+    ("chub_step_tape", "h p p p p p p"),
+    ("chub_reset_tape", "h p p p"),
+    ("chub_step_tape_env", "h p p p o o i32 p p p"),
+    ("chub_reset_tape_env", "h p p o o p"),
+]
+
+
+def test_reset_and_step_entry_points_refuse_null_arguments():
+    """every reset and step entry point answers a null handle, and a null pointer it requires, with CHUB_ERR_ARG and the text
+    "null argument", before it looks at the handle (chub_run_steps, which checks its counts in the same breath: "bad argument")"""
+    m = chub()
+    lib = C.CDLL(m.lib_path())
+    lib.chub_last_error.restype = C.c_char_p
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "chub.h")).read(), flags=re.S)
+    in_header = set(re.findall(r"\b(chub_(?:reset|step|run_steps)[a-z0-9_]*)\s*\(", hdr))
+    assert in_header == {n for n, _ in _RESET_STEP_ENTRY_POINTS} | {"chub_run_steps"}
+    # stand-ins that are never read: a call that is refused for a null argument returns before it touches any of them
+    block = C.create_string_buffer(1 << 16)
+    live = C.addressof(block)
+    ctype = {"h": C.c_void_p, "p": C.c_void_p, "o": C.c_void_p, "c": C.c_void_p, "i32": C.c_int32, "i64": C.c_int64}
+
+    def refused(fn, args, text=b"null argument"):
+        rc = fn(*args)
+        return rc == -1 and lib.chub_last_error() == text
+
+    for name, spec in _RESET_STEP_ENTRY_POINTS:
+        kinds = spec.split()
+        fn = getattr(lib, name)
+        fn.restype = C.c_int
+        fn.argtypes = [ctype[k] for k in kinds]
+        full = [1 if k in ("i32", "i64") else (None if k == "o" else live) for k in kinds]
+        for i, k in enumerate(kinds):
+            if k not in ("h", "p", "c"):
+                continue
+            args = list(full)
+            args[i] = None
+            assert refused(fn, args), "%s with argument %d null: %r" % (name, i, lib.chub_last_error())
+        # ... and with every optional pointer given, the answer to a null handle is the same
+        args = [1 if k in ("i32", "i64") else live for k in kinds]
+        args[0] = None
+        assert refused(fn, args), name
+    fn = lib.chub_run_steps
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+    two = (C.c_void_p * 2)(live, live)
+    good = [live, None, C.addressof(two), 2, C.addressof(two), None, live, 0, 4, None]
+    for i, bad in ((0, None), (2, None), (3, 0), (4, None), (6, None), (7, -1), (8, -1)):
+        args = list(good)
+        args[i] = bad
+        assert refused(fn, args, b"bad argument"), "chub_run_steps with argument %d = %r" % (i, bad)
+    one_null = (C.c_void_p * 2)(live, None)
+    args = list(good)
+    args[4] = C.addressof(one_null)
+    assert refused(fn, args, b"bad argument")
