@@ -68,8 +68,9 @@ CHUB_HD float slow_c_hole(float x, const CurveConsts &cc) {  // CHS.hpp:568-578
     else if ((double) x <= 3.67 * 4) return slow_c_part2(x / 4.0f);
     else return cc.slow_c2_end;
 }
+constexpr float kSlowConstantPower = (float) 5.254973139368931;  // constant_power of the slow curve, CHS.hpp:495-511
 CHUB_HD float slow_time_to_power(float t, bool cp) {  // CHS.hpp:495-511
-    if (cp) return (14.68 >= (double) t && t >= 0) ? (float) 5.254973139368931 : 0.0f;
+    if (cp) return (14.68 >= (double) t && t >= 0) ? kSlowConstantPower : 0.0f;
     if ((double) t < 2.33 * 4) return slow_b_part1(t / 4.0f);
     else if ((double) t < 3.67 * 4) return slow_b_part2(t / 4.0f);
     return 0.0f;
@@ -118,8 +119,9 @@ CHUB_HD float fast_aa_part2(float xf, float aa2_c) {  // CHS.hpp:697-704
     return (float) ((0.0002253 / 5) * x5 - (0.03572 / 4) * x4 + (2.016 / 3) * x3 - (48.76 / 2) * x2 + 457.7 * x +
                     (double) aa2_c);
 }
+constexpr float kFastConstantPower = (float) 36.44764034125146;  // constant_power of the fast curve, CHS.hpp:621-637
 CHUB_HD float fast_time_to_power(float t, bool cp) {  // CHS.hpp:621-637
-    if (cp) return (3.4133333333333336 >= (double) t && t >= 0) ? (float) 36.44764034125146 : 0.0f;
+    if (cp) return (3.4133333333333336 >= (double) t && t >= 0) ? kFastConstantPower : 0.0f;
     if (t >= 0 && (double) t < (28.7 / 15)) return fast_a_part1(t * 15.0f);
     else if (t >= 0 && (double) t < (51.2 / 15)) return fast_a_part2(t * 15.0f);
     return 0.0f;

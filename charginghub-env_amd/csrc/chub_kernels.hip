@@ -483,7 +483,33 @@ __device__ __forceinline__ void car_step_curves(float tt, bool cp, const CurveCo
 // 4-byte store per new car was a read-modify-write of a whole sector).  soc_to_time(target) is one of 1000 values per station -- the target is
 // level l of uniform_rand(80, 100) -- read from Tables::ttab[k] by the level kept in the record's word; chub_create checks once, on the device, that
 // the table's entries are the bits the device's own soc_to_time gives (k_check_ttab): the table may then stand in for the function.
+// The record's fourth word: bits 0-6 stay_time - already_stay_time (0 = empty), bit 7 charging this step, and above the flag the car's meta
+// bits: stay_time (7 bits) | target level << 7 | car_steps taken << 17 (its SoC is replayed from them on demand).  The layout is written
+// here: hot_tl / hot_level / kMetaStep for those who look at the word alone, CompatSlot for the whole record.  Two places spell it out
+// beside these: slot_body_split2 packs the word itself (through CompatSlot k_slot_walk2 spilt one more VGPR) and k_compat_empties masks the
+// stay itself (noted there); the walks' var[] records carry the meta bits alone (stay | level << 7).  The host reads the same word
+// (chub_runtime.cpp, introspection).
+__device__ __forceinline__ int hot_tl(uint32_t w) { return (int) (w & 127u); }
 __device__ __forceinline__ int hot_level(uint32_t w) { return (int) ((w >> 15) & 1023u); }
+constexpr int kMetaStep = 1 << 17;  // one more car_step on the car's account
+struct CompatSlot {
+    float power, arr_soc, t_soc;
+    int tl;       // stay left
+    bool charge;  // charging this step
+    int meta;
+    static __device__ __forceinline__ CompatSlot unpack(const u32x4 h) {
+        CompatSlot s;
+        s.power = __uint_as_float(h.x); s.arr_soc = __uint_as_float(h.y); s.t_soc = __uint_as_float(h.z);
+        s.tl = hot_tl(h.w);
+        s.charge = (h.w & 128u) != 0u;
+        s.meta = (int) (h.w >> 8);
+        return s;
+    }
+    __device__ __forceinline__ u32x4 pack() const {
+        return u32x4{__float_as_uint(power), __float_as_uint(arr_soc), __float_as_uint(t_soc),
+                     (uint32_t) tl | (charge ? 128u : 0u) | ((uint32_t) meta << 8)};
+    }
+};
 
 // What add_car (CHS.hpp:864-877 / 1029-1042) produces for one admitted slot.
 struct NewCar {
@@ -505,6 +531,254 @@ __device__ __forceinline__ NewCar make_car(float arrive_soc, int lev, float t_ta
     return c;
 }
 
+// ------------------------------------------------------------------------------- the phases of the station step
+// The reference's station step (CHS.hpp:1188-1207 / 1499-1518), one definition per phase.  The kernel forms below (wave-local units, a
+// workgroup per unit, a unit in chunks, the split step and its walks) differ in how lanes map onto slots and in where a unit's state lives;
+// the arithmetic of a phase is what stands here, and "the same draws in the same order, the same arithmetic: the same bits" holds
+// between the forms because they call the same function.  (The packed production body, slot_body_packed, is a form of its own.)
+
+// receive_car (CHS.hpp:1272-1316 / 1583-1627) ends in assign_car (CHS.hpp:417-430): of the `want` cars at the door (the queue that stayed +
+// the arrivals recorded) as many as there are empty slots are admitted, the others queue up to max_line.  flow and assign may be negative
+// right after the reset of a small fast station (CHS.hpp:1617): nobody is admitted then; a caller that stores assign clamps it itself.
+struct Received {
+    int flow, assign, line;  // flow_in_number.back(), cars admitted, Station::line
+};
+__device__ __forceinline__ Received assign_car(const int want, const int flow, const int empties) {
+    Received r;
+    r.flow = flow;
+    r.assign = want < empties ? want : empties;
+    const int line = want - r.assign;
+    r.line = line < kMaxLine ? line : kMaxLine;
+    return r;
+}
+// ... on the COMPAT streams, in the reference's consumption order: the initial occupancy (RESET: init_station_car_number, CHS.hpp:832-842) or
+// the arrival count of the env's own slot of day, the renege pass over the queue, the balk pass over the arrivals.  line: the queue coming in
+template <bool RESET, typename Stream>
+__device__ __forceinline__ Received receive_car_streams(Stream &rs, const HubParams &hp, const StepArgs &sa, const Tables &tb, const int k,
+                                                        const int env, const bool fast, const int line, const int empties) {
+    const int S = hp.S[k], mu = S / 2;  // round(charge_number / 2) on ints, CHS.hpp:1276
+    int n_in;
+    if (RESET) {
+        const int temp = (int) roundf(rs.normal_f((float) mu, 1.0f));
+        n_in = temp > mu + 3 ? mu + 3 : (temp < mu - 3 ? mu - 3 : temp);
+    } else {
+        const int t_env = sa.env_clk ? clk_t(env_clk(sa, hp.n_envs, env)) : sa.t;  // per-env clocks: the env's own slot of day
+        n_in = (int) tb.cnt[k][t_env * kLevels + rs.level()];
+    }
+    int stay_q = 0;
+    for (int w = 0; w < line; w++) stay_q += (rs.level() >= (int) tb.thr_renege[w]) ? 1 : 0;
+    int true_in = 0;
+    for (int j = 0; j < n_in; j++) {
+        const int m = stay_q + j;
+        const int thr = (int) tb.thr_balk[m < kBalkTab ? m : kBalkTab - 1];
+        true_in += (rs.level() <= thr && j <= S) ? 1 : 0;
+    }
+    const int flow = fast ? n_in : true_in;  // the fast station records the un-thinned count, CHS.hpp:1617 / 1306
+    return assign_car(stay_q + flow, flow, empties);
+}
+// ... from PHILOX's station word: the unit's draws were made and decoded one launch ahead (draw_decoded_levels; RESET: the raw
+// initial-occupancy draws of k_reset_levels, arrivals | arrivals that stay << 16)
+template <bool RESET>
+__device__ __forceinline__ Received receive_car_word(const uint32_t pk, const bool fast, const int empties) {
+    if (RESET) {
+        const int flow = fast ? (int) (int16_t) (pk & 0xFFFFu) : (int) ((pk >> 16) & 0xFFFFu);
+        return assign_car(flow, flow, empties);
+    }
+    return assign_car(dk_want(pk), dk_flow(pk), empties);
+}
+
+// A new car's three variates from the COMPAT streams, in the reference's consumption order: mk_soc (CHS.hpp:804-814), the target level
+// (CHS.hpp:35-44), mk_late_time("slow") (CHS.hpp:816-830)
+struct CarDraw {
+    float soc;
+    int lev, late;
+};
+template <typename Stream>
+__device__ __forceinline__ CarDraw draw_car_streams(Stream &rs) {
+    CarDraw d;
+    d.soc = arrive_soc_from(rs.normal_d(7.0, 3.0));
+    d.lev = rs.level();
+    const int late = (int) roundf(rs.normal_f(2.0f, 2.0f));
+    d.late = late < 0 ? 0 : late;
+    return d;
+}
+// ... and add_car (CHS.hpp:864-877 / 1029-1042) on the curves from them
+__device__ __forceinline__ NewCar add_car_compat(const bool fast, const float soc, const int lev, const int late, const bool cp) {
+    const float target = uniform_level(lev, 80.0f, 100.0f);
+    NewCar nc;
+    if (fast) nc = make_car<0>(soc, lev, soc_to_time<0>(target, cp), late, cp);
+    else nc = make_car<1>(soc, lev, soc_to_time<1>(target, cp), late, cp);
+    return nc;
+}
+__device__ __forceinline__ CompatSlot compat_slot_of(const NewCar &nc) {  // the hot record of a car that has just arrived
+    CompatSlot s;
+    s.power = nc.power; s.arr_soc = nc.soc; s.t_soc = nc.t_soc;
+    s.tl = nc.stay;
+    s.charge = false;
+    s.meta = nc.stay | (nc.lev << 7);
+    return s;
+}
+
+// PHILOX add_car (CHS.hpp:864-877 / 1029-1042): one Philox block per new car, keyed by (env, hub slot, tick) -- word 0 the SoC, word 1 the
+// target level, word 2 the extra stay
+__device__ __forceinline__ U4 car_block(const HubParams &hp, const StepArgs &sa, const int env, const int hub_slot) {
+    PhiloxCtx px{hp.key[0], hp.key[1], CHUB_TICK(hp, sa.tick), (uint32_t) (hp.env_id0 + env)};
+    return px.block(SITE_SOC, (uint32_t) hub_slot, 0);
+}
+struct PhiloxCar {
+    float power, t_soc, t_target;
+    int stay;
+    uint32_t word;  // the slot's new state word (0: the car does not stay)
+};
+__device__ __forceinline__ PhiloxCar add_car_philox(const HubParams &hp, const StepArgs &sa, const Tables &tb, const int k, const int env,
+                                                    const int hub_slot) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const U4 o = car_block(hp, sa, env, hub_slot);
+    const uint32_t c = o.v[0] >> kSocLevelShift, lev = o.v[1] % 1000u;
+    const f32x2 e0 = *(CHUB_G(const f32x2)) ((CHUB_G(const char)) tb.cls[k] + (size_t) c * (kClsRow * 8u));  // the class row's first entry
+    PhiloxCar n;
+    n.t_target = tb.ttab[k][lev];
+    const int late = late_from_word(tb.late_thr, o.v[2]);
+    const int stay = (int) ceilf(__fsub_rn(n.t_target, e0.y)) + late;  // calculate_min_charging_time + mk_late_time
+    n.stay = stay > kMaxStay ? kMaxStay : stay;
+    n.power = e0.x;
+    n.t_soc = e0.y;
+    n.word = n.stay > 0 ? ps_make(n.stay, c, lev) : 0u;
+    return n;
+}
+
+// car_step (CHS.hpp:900-905 / 1065-1070) of a COMPAT slot that is on: one slot further along the curves
+__device__ __forceinline__ void car_step_compat(CompatSlot &s, const bool fast, const bool cp, const CurveConsts &cc) {
+    s.meta += kMetaStep;
+    float soc_new;
+    const float tt = __fadd_rn(s.t_soc, 1.0f);
+    if (fast) {
+        car_step_curves<0>(tt, cp, cc, soc_new, s.power);
+        s.t_soc = soc_to_time<0>(soc_new, cp);
+    } else {
+        car_step_curves<1>(tt, cp, cc, soc_new, s.power);
+        s.t_soc = soc_to_time<1>(soc_new, cp);
+    }
+}
+// remove_car (CHS.hpp:912-923 / 1077-1088) of a COMPAT slot: one slot of stay less; a car whose stay is over leaves (returns true) and the
+// record is wiped.  The charging flag is that of a car that is on AND stays.
+__device__ __forceinline__ bool remove_car_compat(CompatSlot &s, const bool on) {
+    bool leave = false;
+    if (s.tl > 0) {
+        s.tl -= 1;
+        if (s.tl <= 0) {
+            leave = true;
+            s.tl = 0;
+            s.power = s.t_soc = s.arr_soc = 0.0f;
+            s.meta = 0;
+        }
+    }
+    s.charge = on && s.tl > 0;
+    return leave;
+}
+// car_step + remove_car on the PHILOX state word.  A car_step is one more entry along the class row, taken only by a car that stays: one
+// that leaves this step is wiped right after its car_step (CHS.hpp:1196-1201).  The word's part alone (returns whether the car took the
+// step) is all k_slot_unit_any's first pass needs; car_step_philox moves the slot's power and t_soc along with it and returns whether
+// the car left, like remove_car_compat.
+struct PhiloxWord {
+    uint32_t w;
+    int tl;       // stay left
+    bool charge;  // charging this step
+};
+struct PhiloxSlot : PhiloxWord {
+    float power, t_soc;
+};
+__device__ __forceinline__ bool car_step_word(PhiloxWord &s, const bool on) {
+    const bool step = on && s.tl > 1;
+    if (step) s.w += kPsStep;
+    s.w &= ~kPsChg;
+    if (s.tl > 0) {  // remove_car
+        s.tl -= 1;
+        s.w -= 1u;
+        if (s.tl <= 0) {
+            s.tl = 0;
+            s.w = 0u;
+        }
+    }
+    s.charge = on && s.tl > 0;
+    if (s.charge) s.w |= kPsChg;
+    return step;
+}
+__device__ __forceinline__ bool car_step_philox(PhiloxSlot &s, const bool on, const float next_power, const float next_t_soc) {
+    const bool car = s.tl > 0;
+    if (car_step_word(s, on)) {
+        s.power = next_power;
+        s.t_soc = next_t_soc;
+    }
+    const bool leave = car && s.tl == 0;
+    if (leave) s.power = s.t_soc = 0.0f;
+    return leave;
+}
+__device__ __forceinline__ PhiloxSlot philox_slot_of(const PhiloxCar &nc) {  // the slot of a car that has just arrived
+    PhiloxSlot s;
+    s.w = nc.word; s.tl = nc.stay; s.charge = false;
+    s.power = nc.power; s.t_soc = nc.t_soc;
+    return s;
+}
+// the slot value of a kernel that serves either state layout (both have power, t_soc, tl, charge)
+template <int MODE> struct SlotOf { typedef CompatSlot type; };
+template <> struct SlotOf<MODE_PHILOX> { typedef PhiloxSlot type; };
+
+// Scalar-load control, evs_step(float) (CHS.hpp:1169-1186 / 1480-1497).  catch_load (CHS.hpp:358-366): the station's kW target, clamped to
+// [min_power, max_power] of the previous calculate_output
+__device__ __forceinline__ float catch_load(const HubParams &hp, const StepArgs &sa, const StationArrays &st, const int k, const int env,
+                                            const uint32_t sidx) {
+    const StationRec pr = rec_load(st.rec, sidx);
+    float load = sa.actions[(uint32_t) env * (uint32_t) hp.act_dim + (uint32_t) (k ? hp.S[0] : 0)];
+    if (load > pr.mx) load = pr.mx;
+    else if (load < pr.mn) load = pr.mn;
+    return load;
+}
+// ... and whether it switches on a car (assign_on_off, CHS.hpp:1318-1362 / 1629-1674) that has `mine_before` cars in front of it in urgency
+// order and the cumulative power `mine` up to and including itself (rank_power_add, CHS.hpp:1375-1402): a constant-power fleet takes the
+// first round(load / constant_power) cars, the others as many as the target covers
+__device__ __forceinline__ bool load_says_on(const bool cp, const bool fast, const float load, const float mine, const int mine_before) {
+    if (cp) {
+        const int n_on = (int) roundf(__fdiv_rn(load, fast ? kFastConstantPower : kSlowConstantPower));
+        return mine_before < n_on;
+    }
+    return (double) load + 0.0001 >= (double) mine;
+}
+
+// calculate_output (CHS.hpp:1233-1261 / 1544-1572), PHILOX: integer butterfly over a wave-local unit's H lanes (order-independent sums of
+// slot powers in units of 2^-19 kW: kw_to_fixed)
+__device__ __forceinline__ void unit_sums_dpp(const int H, int &i_min, int &i_max, int &i_chg) {
+    if (H > 1) { i_min += dppi_xor1(i_min); i_max += dppi_xor1(i_max); i_chg += dppi_xor1(i_chg); }
+    if (H > 2) { i_min += dppi_xor2(i_min); i_max += dppi_xor2(i_max); i_chg += dppi_xor2(i_chg); }
+    if (H > 4) { i_min += dppi_mirror8(i_min); i_max += dppi_mirror8(i_max); i_chg += dppi_mirror8(i_chg); }
+    if (H > 8) { i_min += dppi_mirror16(i_min); i_max += dppi_mirror16(i_max); i_chg += dppi_mirror16(i_chg); }
+    if (H > 16) { i_min += __shfl_xor(i_min, 16); i_max += __shfl_xor(i_max, 16); i_chg += __shfl_xor(i_chg, 16); }
+    if (H > 32) { i_min += __shfl_xor(i_min, 32); i_max += __shfl_xor(i_max, 32); i_chg += __shfl_xor(i_chg, 32); }
+}
+// ... one lane adding n slots' terms in LDS to its running sums, in slot order.  COMPAT: the reference's sequential f32 sums
+// (CHS.hpp:1244-1255), same order, same roundings; PHILOX: 64-bit integers, one rounding to f32 at the end (fixed64_to_kw)
+struct SumsF32 {
+    float mn, chg, mx;
+    __device__ __forceinline__ void add(const float *t_min, const float *t_chg, const float *t_max, const int n) {
+        for (int i = 0; i < n; i++) {
+            mx = __fadd_rn(mx, t_max[i]);
+            mn = __fadd_rn(mn, t_min[i]);
+            chg = __fadd_rn(chg, t_chg[i]);
+        }
+    }
+};
+struct SumsI64 {
+    long long mn, chg, mx;
+    __device__ __forceinline__ void add(const uint32_t *t_min, const uint32_t *t_chg, const uint32_t *t_max, const int n) {
+        for (int i = 0; i < n; i++) {
+            mn += (long long) (int) t_min[i];
+            chg += (long long) (int) t_chg[i];
+            mx += (long long) (int) t_max[i];
+        }
+    }
+};
+__device__ __forceinline__ float fixed64_to_kw(long long v) { return (float) v * (1.0f / 524288.0f); }
+
 // ---- scalar-load control mode, evs_step(float) (CHS.hpp:1169-1186 / 1480-1497): one kW target per station; the piles are
 // switched on in urgency order until the target is met (assign_on_off, CHS.hpp:1318-1362 / 1629-1674).  Wave-local units
 // (H = pow2 >= S lanes).  Returns this lane's on / off decision.
@@ -516,14 +790,7 @@ __device__ __forceinline__ bool load_mode_on(const HubParams &hp, const StepArgs
     const int S = hp.S[k];
     const uint32_t sidx = (uint32_t) k * (uint32_t) hp.n_envs + (uint32_t) env;
     const bool cp = hp.constant_charging != 0;
-    // catch_load (CHS.hpp:358-366): clamp to [min_power, max_power] of the previous calculate_output
-    float load = 0.0f;
-    if (unit_ok) {
-        const StationRec pr = rec_load(st.rec, sidx);
-        load = sa.actions[(uint32_t) env * (uint32_t) hp.act_dim + (uint32_t) (k ? hp.S[0] : 0)];
-        if (load > pr.mx) load = pr.mx;
-        else if (load < pr.mn) load = pr.mn;
-    }
+    const float load = unit_ok ? catch_load(hp, sa, st, k, env, sidx) : 0.0f;
     // std::multimap keyed by -emergency (CHS.hpp:1324-1336): emergency descending, ties by slot index (ubase: the unit's first lane)
     int rk = 0;
     for (int j = 0; j < S; j++) {
@@ -548,14 +815,7 @@ __device__ __forceinline__ bool load_mode_on(const HubParams &hp, const StepArgs
         cars_before += valid ? (int) car_by_rank[q] : 0;
         if (q == rk) mine = cum;
     }
-    bool chg;
-    if (cp) {  // constant-power fleet: the first round(load / constant_power) cars in order
-        const float constant_power = hp.type[k] == 0 ? (float) 36.44764034125146 : (float) 5.254973139368931;
-        const int n_on = (int) roundf(__fdiv_rn(load, constant_power));
-        chg = car0 && mine_before < n_on;
-    } else {
-        chg = car0 && ((double) load + 0.0001 >= (double) mine);
-    }
+    const bool chg = car0 && load_says_on(cp, hp.type[k] == 0, load, mine, mine_before);
     __builtin_amdgcn_wave_barrier();
     __syncthreads();  // the scratch areas are reused below
     return chg;
@@ -568,7 +828,7 @@ __device__ __forceinline__ bool load_mode_on(const HubParams &hp, const StepArgs
 // trajectories (tests/golden).
 // SPLIT (the split step of large batches): the walk was done by k_compat_walk, one ENV per lane (here one lane per UNIT walks while
 // the other lanes of the wave idle); this body then only fetches what it came to -- flow, cars admitted, queue -- and the admitted
-// lanes their car's variates.  Same draws in the same order, same arithmetic: bit-identical.
+// lanes their car's variates (the phases: receive_car_streams, draw_car_streams, add_car_compat above).
 // wave0 / mid (k_compat_small): the station's units start at workgroup wave `wave0`, and mid() is called by every lane in front of the
 // first look at what the walk came to (there: the workgroup barrier behind which the walker wave's results are in).
 struct NoSlotMid {
@@ -609,42 +869,26 @@ __device__ __forceinline__ void slot_body_compat(const HubParams &hp, const Step
         hot = ((CHUB_G(u32x4)) sl.hot)[idx];
         a = sa.actions[(uint32_t) env * (uint32_t) hp.act_dim + (uint32_t) hub_slot];
     }
-    float power = __uint_as_float(hot.x), arr_soc = __uint_as_float(hot.y), t_soc = __uint_as_float(hot.z);
-    int tl = (int) (hot.w & 127u);
-    int meta = (int) (hot.w >> 8);  // all of the meta bits above the flag: stay_time | target level << 7 | car_steps << 17
-    bool car = tl > 0, leave = false;
-    float t_target = car ? tb.ttab[k][hot_level(hot.w)] : 0.0f;  // soc_to_time(target) of the car's level (hot_level above)
+    CompatSlot s = CompatSlot::unpack(hot);
+    bool car = s.tl > 0;
+    float t_target = car ? tb.ttab[k][hot_level(hot.w)] : 0.0f;  // soc_to_time(target) of the car's level
     int on_override = -1;
     if (!RESET && sa.load_mode)
-        on_override = load_mode_on<BLOCK>(hp, sa, st, k, env, unit_ok, valid, slot, car, power,
-                                          car ? emergency_of(t_target, t_soc, tl) : 0.0f, lds_f, lds_u, leader) ? 1 : 0;
+        on_override = load_mode_on<BLOCK>(hp, sa, st, k, env, unit_ok, valid, slot, car, s.power,
+                                          car ? emergency_of(t_target, s.t_soc, s.tl) : 0.0f, lds_f, lds_u, leader) ? 1 : 0;
     // judge_feasibility + assign_on_off_piece (CHS.hpp:1404-1413, 1364-1373); action_to_real (MGR:384-393)
-    const bool on = on_override >= 0 ? (car && on_override != 0) : (car && (a >= kActOnThreshold || must_charge(t_target, t_soc, tl)));
-    if (on) {  // car_step (CHS.hpp:900-905 / 1065-1070)
-        meta += 1 << 17;  // one more car_step on this car's account (its SoC is replayed from it on demand)
-        float soc_new;
-        car_step_curves<TYPE>(__fadd_rn(t_soc, 1.0f), cp, hp.cc, soc_new, power);
-        t_soc = soc_to_time<TYPE>(soc_new, cp);
-    }
-    if (car) {  // remove_car (CHS.hpp:912-923 / 1077-1088)
-        tl -= 1;
-        if (tl <= 0) {
-            car = false;
-            leave = true;
-            tl = 0;
-            power = t_target = t_soc = arr_soc = 0.0f;
-            meta = 0;
-        }
-    }
-    const bool charge = on && car;
+    const bool on = on_override >= 0 ? (car && on_override != 0) : (car && (a >= kActOnThreshold || must_charge(t_target, s.t_soc, s.tl)));
+    if (on) car_step_compat(s, TYPE == 0, cp, hp.cc);
+    const bool leave = remove_car_compat(s, on);
+    if (leave) t_target = 0.0f;
+    car = s.tl > 0;
 
-    // ---- receive_car (CHS.hpp:1272-1316 / 1583-1627): arrivals, renege, balk, admission
+    // ---- receive_car: arrivals, renege, balk, admission
     const bool empty = valid && !car;
     const uint64_t be = __ballot(empty) & unit_mask;
     const int empties = __popcll(be);
     const int rank = prefix_count(be);
     int line = pkd_line(line_in);
-    const int mu = S / 2;  // round(charge_number / 2) on ints, CHS.hpp:1276
     // the unit's first lane walks the two reference streams in the reference's order and parks the per-admission
     // variates in LDS, indexed by admission rank
     float *lds_soc = lds_f;
@@ -662,37 +906,16 @@ __device__ __forceinline__ void slot_body_compat(const HubParams &hp, const Step
     } else if (unit_ok && slot == 0) {
         CompatStream rs;
         rs.load(cr, sa.rng_cur, env);
-        int n_in;
-        if (RESET) {
-            const float cn = rs.normal_f((float) mu, 1.0f);
-            int temp = (int) roundf(cn);
-            temp = temp > mu + 3 ? mu + 3 : (temp < mu - 3 ? mu - 3 : temp);
-            n_in = temp;
-        } else {
-            const int t_env = sa.env_clk ? clk_t(env_clk(sa, N, env)) : sa.t;  // per-env clocks: the env's own slot of day
-            n_in = (int) tb.cnt[k][t_env * kLevels + rs.level()];
-        }
-        int tline = 0;
-        for (int w = 0; w < line; w++) tline += (rs.level() >= (int) tb.thr_renege[w]) ? 1 : 0;
-        new_line = tline;
-        int true_in = 0;
-        for (int j = 0; j < n_in; j++) {
-            const int m = new_line + j;
-            const int thr = (int) tb.thr_balk[m < kBalkTab ? m : kBalkTab - 1];
-            true_in += (rs.level() <= thr && j <= S) ? 1 : 0;
-        }
-        const int fl = (TYPE == 0) ? n_in : true_in;
-        int as = (new_line + fl) < empties ? (new_line + fl) : empties;
-        new_line = new_line + fl - as;
-        new_line = new_line < kMaxLine ? new_line : kMaxLine;
-        for (int rr = 0; rr < as; rr++) {  // ascending slot order == ascending rank
-            lds_soc[lbase + rr] = arrive_soc_from(rs.normal_d(7.0, 3.0));
-            lds_lev[lbase + rr] = (uint32_t) rs.level();
-            int late = (int) roundf(rs.normal_f(2.0f, 2.0f));  // mk_late_time("slow"), CHS.hpp:816-830
-            lds_late[lbase + rr] = (uint32_t) (late < 0 ? 0 : late);
+        const Received rc = receive_car_streams<RESET>(rs, hp, sa, tb, k, env, TYPE == 0, line, empties);
+        new_line = rc.line;
+        for (int rr = 0; rr < rc.assign; rr++) {  // ascending slot order == ascending rank
+            const CarDraw d = draw_car_streams(rs);
+            lds_soc[lbase + rr] = d.soc;
+            lds_lev[lbase + rr] = (uint32_t) d.lev;
+            lds_late[lbase + rr] = (uint32_t) d.late;
         }
         rs.store(cr, sa.rng_cur, env);
-        fa = make_int2(fl, as);
+        fa = make_int2(rc.flow, rc.assign);
     }
     const int flow = __shfl(fa.x, leader);
     const int assign = __shfl(fa.y, leader);
@@ -701,39 +924,30 @@ __device__ __forceinline__ void slot_body_compat(const HubParams &hp, const Step
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     const bool adm = empty && rank < assign;
-    float nc_soc = 0.0f;
     if (adm && SPLIT) {  // the car as the walk made it (compat_walk_env: add_car there, one record per admission rank)
         const uint32_t vi = (uint32_t) env * (uint32_t) (hp.S[0] + hp.S[1]) + (uint32_t) (k ? hp.S[0] : 0) + (uint32_t) rank;
         const u32x4 vv = ((CHUB_G(const u32x4)) sl.var[sa.tick & 1u])[2u * vi];
-        nc_soc = __uint_as_float(sl.var[sa.tick & 1u][8u * vi + 4u]);
-        power = __uint_as_float(vv.x);
+        s.arr_soc = __uint_as_float(sl.var[sa.tick & 1u][8u * vi + 4u]);
+        s.power = __uint_as_float(vv.x);
         t_target = __uint_as_float(vv.y);
-        t_soc = __uint_as_float(vv.z);
-        tl = (int) (vv.w & 127u);
-        car = tl > 0;
-        meta = (int) vv.w;
+        s.t_soc = __uint_as_float(vv.z);
+        s.tl = (int) (vv.w & 127u);
+        s.meta = (int) vv.w;
     } else if (adm) {
-        const int lev = (int) lds_lev[lbase + rank];
-        const float target = uniform_level(lev, 80.0f, 100.0f);
-        const NewCar nc = make_car<TYPE>(lds_soc[lbase + rank], lev, soc_to_time<TYPE>(target, cp), (int) lds_late[lbase + rank], cp);
-        nc_soc = nc.soc;
+        const NewCar nc = add_car_compat(TYPE == 0, lds_soc[lbase + rank], (int) lds_lev[lbase + rank], (int) lds_late[lbase + rank], cp);
         t_target = nc.t_target;
-        t_soc = nc.t_soc;
-        tl = nc.stay;
-        power = nc.power;
-        car = tl > 0;
-        meta = nc.stay | (nc.lev << 7);
+        s = compat_slot_of(nc);
     } else if (leave || RESET) {
-        meta = 0;
+        s.meta = 0;
     }
+    car = s.tl > 0;
 
-    // ---- calculate_output (CHS.hpp:1233-1261 / 1544-1572): the reference adds slot powers sequentially in f32
-    // (CHS.hpp:1244-1255): same order, same roundings
-    const bool urgent = car && must_charge(t_target, t_soc, tl);
-    const float v_min = urgent ? power : 0.0f, v_max = car ? power : 0.0f, v_chg = charge ? power : 0.0f;
+    // ---- calculate_output (CHS.hpp:1233-1261 / 1544-1572): SumsF32
+    const bool urgent = car && must_charge(t_target, s.t_soc, s.tl);
+    const float v_min = urgent ? s.power : 0.0f, v_max = car ? s.power : 0.0f, v_chg = s.charge ? s.power : 0.0f;
     // every lane parks its three terms in the wave's own scratch area and the unit's first lane -- the only one that needs the sums --
     // adds them up in slot order (each lane fetching its S neighbours' terms by cross-lane reads cost 3 S of those per wave)
-    float r_min = 0.0f, r_max = 0.0f, r_chg = 0.0f;
+    SumsF32 r = {0.0f, 0.0f, 0.0f};
     {
         __builtin_amdgcn_wave_barrier();  // (the admitted lanes' reads of the walk's variates above are done)
         float *t_max = lds_f + wave_abs * 64, *t_min = (float *) lds_u + wave_abs * 64, *t_chg = (float *) lds_u + BLOCK + wave_abs * 64;
@@ -743,29 +957,16 @@ __device__ __forceinline__ void slot_body_compat(const HubParams &hp, const Step
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (unit_ok && slot == 0) {
-            for (int i = 0; i < S; i++) {
-                r_max = __fadd_rn(r_max, t_max[leader + i]);
-                r_min = __fadd_rn(r_min, t_min[leader + i]);
-                r_chg = __fadd_rn(r_chg, t_chg[leader + i]);
-            }
-        }
+        if (unit_ok && slot == 0) r.add(t_min + leader, t_chg + leader, t_max + leader, S);
     }
     const int cars = __popcll(__ballot(car) & unit_mask);
 
-    if (valid) {
-        u32x4 h2;
-        h2.x = __float_as_uint(power);
-        h2.y = __float_as_uint(adm ? nc_soc : arr_soc);  // the arrival SoC (current SoC and target SoC are derived from it and the word on demand)
-        h2.z = __float_as_uint(t_soc);
-        h2.w = (uint32_t) tl | (charge ? 128u : 0u) | ((uint32_t) meta << 8);
-        ((CHUB_G(u32x4)) sl.hot)[idx] = h2;
-    }
+    if (valid) ((CHUB_G(u32x4)) sl.hot)[idx] = s.pack();
     if (unit_ok && slot == 0) {
-        rec_store(st.rec, sidx, r_min, r_chg, r_max, pkd_make(line, flow, cars));
+        rec_store(st.rec, sidx, r.mn, r.chg, r.mx, pkd_make(line, flow, cars));
     }
     if (SPLIT) {  // what the next step's walk needs of the slots: a slot is empty after remove_car iff it has at most one slot of stay left
-        const int n_empty = __popcll(__ballot(valid && tl <= 1) & unit_mask), n_empty2 = __popcll(__ballot(valid && tl <= 2) & unit_mask);
+        const int n_empty = __popcll(__ballot(valid && s.tl <= 1) & unit_mask), n_empty2 = __popcll(__ballot(valid && s.tl <= 2) & unit_mask);
         if (unit_ok && slot == 0) {
             st.empt[sidx] = (uint8_t) n_empty;
             st.empt2[sa.tick & 1u][sidx] = (uint8_t) n_empty2;
@@ -852,7 +1053,7 @@ __device__ __forceinline__ void slot_body_split2(const HubParams &hp, const Step
         power[j] = __uint_as_float(hot[j].x);
         arr_soc[j] = __uint_as_float(hot[j].y);
         t_soc[j] = __uint_as_float(hot[j].z);
-        tl[j] = (int) (hot[j].w & 127u);
+        tl[j] = hot_tl(hot[j].w);
         meta[j] = (int) (hot[j].w >> 8);
         car[j] = tl[j] > 0;
         t_target[j] = car[j] ? ttab_k[hot_level(hot[j].w)] : 0.0f;  // soc_to_time(target) of the car's level (hot_level)
@@ -934,7 +1135,7 @@ __device__ __forceinline__ void slot_body_split2(const HubParams &hp, const Step
     }
 #pragma unroll
     for (int j = 0; j < 2; j++) {
-        if (on[j]) meta[j] += 1 << 17;  // one more car_step on this car's account (its SoC is replayed from it on demand)
+        if (on[j]) meta[j] += kMetaStep;  // one more car_step on this car's account (its SoC is replayed from it on demand)
         if (car[j]) {  // remove_car (CHS.hpp:912-923 / 1077-1088)
             tl[j] -= 1;
             if (tl[j] <= 0) {
@@ -1047,7 +1248,6 @@ __device__ void slot_body_wave(const HubParams &hp, const StepArgs &sa, const Sl
     const uint32_t sidx = (uint32_t) k * (uint32_t) N + (uint32_t) env;
     const bool fast = hp.type[k] == 0;
     typedef float f32x4 __attribute__((ext_vector_type(4)));
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
     CHUB_G(const float) cls = tb.cls[k];
 
     uint32_t pk_in = 0;
@@ -1058,97 +1258,51 @@ __device__ void slot_body_wave(const HubParams &hp, const StepArgs &sa, const Sl
         w0 = sl.hot[idx];
         a = sa.actions[(uint32_t) env * (uint32_t) hp.act_dim + (uint32_t) hub_slot];
     }
-    int tl = ps_tl(w0);
-    bool car = tl > 0;
+    PhiloxSlot s = {{w0, ps_tl(w0), false}, 0.0f, 0.0f};
+    bool car = s.tl > 0;
     f32x4 row = {0.0f, 0.0f, 0.0f, 0.0f};
     float t_target = 0.0f;
     if (car) {
         row = *(CHUB_G(const f32x4)) ((CHUB_G(const char)) cls + ((size_t) ps_cls(w0) * (kClsRow * 8u) + ps_n(w0) * 8u));
         t_target = tb.ttab[k][ps_lev(w0)];
     }
-    float power = row.x, t_soc = row.y;
+    s.power = row.x;
+    s.t_soc = row.y;
     int on_override = -1;
     if (!RESET && sa.load_mode)
-        on_override = load_mode_on<BLOCK>(hp, sa, st, k, env, unit_ok, valid, slot, car, power,
-                                          car ? emergency_of(t_target, t_soc, tl) : 0.0f, lds_f, lds_u, uiw << logH) ? 1 : 0;
-    const bool on = on_override >= 0 ? (car && on_override != 0) : (car && (a >= kActOnThreshold || must_charge(t_target, t_soc, tl)));
-    const bool step = on && tl > 1;  // a car that leaves this step is wiped right after its car_step (CHS.hpp:1196-1201)
-    if (step) {  // car_step (CHS.hpp:900-905 / 1065-1070) = the next entry of the class row
-        power = row.z;
-        t_soc = row.w;
-        w0 += kPsStep;
-    }
-    w0 &= ~kPsChg;
-    if (car) {  // remove_car (CHS.hpp:912-923 / 1077-1088)
-        tl -= 1;
-        w0 -= 1u;
-        if (tl <= 0) {
-            car = false;
-            w0 = 0u;
-            power = t_target = t_soc = 0.0f;
-        }
-    }
-    const bool charge = on && car;
-    if (charge) w0 |= kPsChg;
-    if (RESET) w0 = 0u;
+        on_override = load_mode_on<BLOCK>(hp, sa, st, k, env, unit_ok, valid, slot, car, s.power,
+                                          car ? emergency_of(t_target, s.t_soc, s.tl) : 0.0f, lds_f, lds_u, uiw << logH) ? 1 : 0;
+    const bool on = on_override >= 0 ? (car && on_override != 0) : (car && (a >= kActOnThreshold || must_charge(t_target, s.t_soc, s.tl)));
+    if (car_step_philox(s, on, row.z, row.w)) t_target = 0.0f;
+    if (RESET) s.w = 0u;
+    car = s.tl > 0;
 
-    // ---- receive_car (CHS.hpp:1272-1316 / 1583-1627): arrivals, renege, balk, admission
+    // ---- receive_car: arrivals, renege, balk, admission
     const bool empty = valid && !car;
     const uint64_t be = __ballot(empty) & unit_mask;
     const int empties = __popcll(be);
     const int rank = prefix_count(be);
-    int line = 0, flow = 0, assign = 0;
-    if (unit_ok) {
-        int want;
-        if (RESET) {
-            // evs_reset: the unit's initial occupancy was drawn by k_reset_levels, one lane per unit, just before.  The fast
-            // station records the raw draw, which is negative for small stations (mu - 3 < 0, CHS.hpp:1617, 832-842):
-            // assign_car then admits nobody and the queue stays empty
-            flow = fast ? (int) (int16_t) (pk_in & 0xFFFFu) : (int) ((pk_in >> 16) & 0xFFFFu);
-            want = flow;
-        } else {
-            // this step's station-level draws were made and decoded one launch ahead (draw_decoded_levels)
-            want = dk_want(pk_in);
-            flow = dk_flow(pk_in);
-        }
-        assign = want < empties ? want : empties;  // assign_car, CHS.hpp:417-430
-        line = want - assign;
-        line = line < kMaxLine ? line : kMaxLine;
-    }
-    const bool adm = empty && rank < assign;
-    if (adm) {  // add_car (CHS.hpp:864-877 / 1029-1042): one Philox block per new car, word 0 SoC class, 1 target level, 2 extra stay
-        PhiloxCtx px{hp.key[0], hp.key[1], CHUB_TICK(hp, sa.tick), (uint32_t) (hp.env_id0 + env)};
-        const U4 o = px.block(SITE_SOC, (uint32_t) hub_slot, 0);
-        const uint32_t c = o.v[0] >> kSocLevelShift, lev = o.v[1] % 1000u;
-        const f32x2 e0 = *(CHUB_G(const f32x2)) ((CHUB_G(const char)) cls + (size_t) c * (kClsRow * 8u));
-        t_target = tb.ttab[k][lev];
-        const int late = late_from_word(tb.late_thr, o.v[2]);
-        int stay = (int) ceilf(__fsub_rn(t_target, e0.y)) + late;  // calculate_min_charging_time + mk_late_time
-        stay = stay > kMaxStay ? kMaxStay : stay;
-        power = e0.x;
-        t_soc = e0.y;
-        tl = stay;
-        car = tl > 0;
-        w0 = car ? ps_make(stay, c, lev) : 0u;
-        sl.stay8[idx] = (uint8_t) stay;
+    Received rc = {0, 0, 0};
+    if (unit_ok) rc = receive_car_word<RESET>(pk_in, fast, empties);
+    if (empty && rank < rc.assign) {
+        const PhiloxCar nc = add_car_philox(hp, sa, tb, k, env, hub_slot);
+        t_target = nc.t_target;
+        s = philox_slot_of(nc);
+        car = s.tl > 0;
+        sl.stay8[idx] = (uint8_t) nc.stay;
     }
 
     // ---- calculate_output (CHS.hpp:1233-1261 / 1544-1572): order-independent sums -- every slot power rounded to the nearest
     // multiple of 2^-19 kW, integer butterfly over the unit's H lanes, one rounding to f32
-    const bool urgent = car && must_charge(t_target, t_soc, tl);
-    const int q = kw_to_fixed(power);
-    int i_min = urgent ? q : 0, i_max = car ? q : 0, i_chg = charge ? q : 0;
-    if (H > 1) { i_min += dppi_xor1(i_min); i_max += dppi_xor1(i_max); i_chg += dppi_xor1(i_chg); }
-    if (H > 2) { i_min += dppi_xor2(i_min); i_max += dppi_xor2(i_max); i_chg += dppi_xor2(i_chg); }
-    if (H > 4) { i_min += dppi_mirror8(i_min); i_max += dppi_mirror8(i_max); i_chg += dppi_mirror8(i_chg); }
-    if (H > 8) { i_min += dppi_mirror16(i_min); i_max += dppi_mirror16(i_max); i_chg += dppi_mirror16(i_chg); }
-    if (H > 16) { i_min += __shfl_xor(i_min, 16); i_max += __shfl_xor(i_max, 16); i_chg += __shfl_xor(i_chg, 16); }
-    if (H > 32) { i_min += __shfl_xor(i_min, 32); i_max += __shfl_xor(i_max, 32); i_chg += __shfl_xor(i_chg, 32); }
+    const bool urgent = car && must_charge(t_target, s.t_soc, s.tl);
+    const int q = kw_to_fixed(s.power);
+    int i_min = urgent ? q : 0, i_max = car ? q : 0, i_chg = s.charge ? q : 0;
+    unit_sums_dpp(H, i_min, i_max, i_chg);
     const int cars = __popcll(__ballot(car) & unit_mask);
 
-    if (valid) sl.hot[idx] = w0;
+    if (valid) sl.hot[idx] = s.w;
     if (unit_ok && slot == 0) {
-        rec_store(st.rec, sidx, fixed_to_kw(i_min), fixed_to_kw(i_chg), fixed_to_kw(i_max), pkd_make(line, flow, cars));
+        rec_store(st.rec, sidx, fixed_to_kw(i_min), fixed_to_kw(i_chg), fixed_to_kw(i_max), pkd_make(rc.line, rc.flow, cars));
     }
 }
 
@@ -1162,7 +1316,6 @@ __device__ void slot_body_wave(const HubParams &hp, const StepArgs &sa, const Sl
 template <bool RESET, int MODE>
 __global__ __launch_bounds__(256) void k_slot_unit(const DevCtx *__restrict__ ctx, StepArgs sa, int k) {
     typedef float f32x4 __attribute__((ext_vector_type(4)));
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
     const HubParams &hp = ctx->hp;
     const SlotArrays &sl = ctx->sl;
     const StationArrays &st = ctx->st;
@@ -1186,34 +1339,31 @@ __global__ __launch_bounds__(256) void k_slot_unit(const DevCtx *__restrict__ ct
     CHUB_G(const float) cls = tb.cls[k];
 
     // ---- the slot as the previous step left it
-    float power = 0.0f, t_target = 0.0f, t_soc = 0.0f, arr_soc = 0.0f, a = 0.0f, next_power = 0.0f, next_t_soc = 0.0f;
-    int tl = 0, meta = 0;
-    uint32_t w0 = 0u;
+    typename SlotOf<MODE>::type s = {};  // the mode's slot value, empty
+    float t_target = 0.0f, a = 0.0f, next_power = 0.0f, next_t_soc = 0.0f;
     if (!RESET && valid) {
         a = sa.actions[(uint32_t) env * (uint32_t) hp.act_dim + (uint32_t) hub_slot];
-        if (MODE == MODE_COMPAT) {
+        if constexpr (MODE == MODE_COMPAT) {
             const u32x4 hot = ((CHUB_G(u32x4)) sl.hot)[idx];
-            power = __uint_as_float(hot.x); arr_soc = __uint_as_float(hot.y); t_soc = __uint_as_float(hot.z);
-            tl = (int) (hot.w & 127u);
-            meta = (int) (hot.w >> 8);
-            if (tl > 0) t_target = tb.ttab[k][hot_level(hot.w)];  // (hot_level: the record keeps the arrival SoC, the target's time is a table entry)
+            s = CompatSlot::unpack(hot);
+            if (s.tl > 0) t_target = tb.ttab[k][hot_level(hot.w)];  // (the record keeps the arrival SoC, the target's time is a table entry)
         } else {
-            w0 = sl.hot[idx];
-            tl = ps_tl(w0);
-            if (tl > 0) {
-                const f32x4 row = *(CHUB_G(const f32x4)) ((CHUB_G(const char)) cls + ((size_t) ps_cls(w0) * (kClsRow * 8u) + ps_n(w0) * 8u));
-                power = row.x; t_soc = row.y; next_power = row.z; next_t_soc = row.w;
-                t_target = tb.ttab[k][ps_lev(w0)];
+            s.w = sl.hot[idx];
+            s.tl = ps_tl(s.w);
+            if (s.tl > 0) {
+                const f32x4 row = *(CHUB_G(const f32x4)) ((CHUB_G(const char)) cls + ((size_t) ps_cls(s.w) * (kClsRow * 8u) + ps_n(s.w) * 8u));
+                s.power = row.x; s.t_soc = row.y; next_power = row.z; next_t_soc = row.w;
+                t_target = tb.ttab[k][ps_lev(s.w)];
             }
         }
     }
-    bool car = tl > 0, leave = false;
+    bool car = s.tl > 0, leave;
 
     // ---- on / off: judge_feasibility + assign_on_off_piece (CHS.hpp:1404-1413, 1364-1373), or the scalar-load control
     // (assign_on_off, CHS.hpp:1318-1362 / 1629-1674: the piles in urgency order, std::multimap keyed by -emergency)
     bool on;
     if (!RESET && sa.load_mode) {
-        const float em0 = car ? emergency_of(t_target, t_soc, tl) : 0.0f;
+        const float em0 = car ? emergency_of(t_target, s.t_soc, s.tl) : 0.0f;
         s_a[tid] = em0;
         __syncthreads();
         int rk = 0;
@@ -1222,15 +1372,12 @@ __global__ __launch_bounds__(256) void k_slot_unit(const DevCtx *__restrict__ ct
             rk += (ej > em0 || (ej == em0 && j < slot)) ? 1 : 0;
         }
         if (valid) {
-            s_c[rk] = car ? power : 0.0f;
+            s_c[rk] = car ? s.power : 0.0f;
             s_u[rk] = car ? 1u : 0u;
         }
         __syncthreads();
-        // catch_load (CHS.hpp:358-366) against the previous calculate_output; rank_power_add (CHS.hpp:1375-1402): sequential f32
-        const StationRec pr = rec_load(st.rec, sidx);
-        float load = sa.actions[(uint32_t) env * (uint32_t) hp.act_dim + (uint32_t) (k ? hp.S[0] : 0)];
-        if (load > pr.mx) load = pr.mx;
-        else if (load < pr.mn) load = pr.mn;
+        // catch_load against the previous calculate_output; rank_power_add (CHS.hpp:1375-1402): sequential f32
+        const float load = catch_load(hp, sa, st, k, env, sidx);
         float cum = 0.0f, mine = 0.0f;
         int cars_before = 0, mine_before = 0;
         for (int q = 0; q < S; q++) {
@@ -1239,62 +1386,24 @@ __global__ __launch_bounds__(256) void k_slot_unit(const DevCtx *__restrict__ ct
             cars_before += (int) s_u[q];
             if (q == rk) mine = cum;
         }
-        if (cp) {
-            const float constant_power = fast ? (float) 36.44764034125146 : (float) 5.254973139368931;
-            const int n_on = (int) roundf(__fdiv_rn(load, constant_power));
-            on = car && mine_before < n_on;
-        } else {
-            on = car && ((double) load + 0.0001 >= (double) mine);
-        }
+        on = car && load_says_on(cp, fast, load, mine, mine_before);
         __syncthreads();
     } else {
-        on = car && (a >= kActOnThreshold || must_charge(t_target, t_soc, tl));
+        on = car && (a >= kActOnThreshold || must_charge(t_target, s.t_soc, s.tl));
     }
 
-    // ---- car_step (CHS.hpp:900-905 / 1065-1070), remove_car (CHS.hpp:912-923 / 1077-1088)
-    if (MODE == MODE_COMPAT) {
-        if (on) {
-            meta += 1 << 17;
-            float soc_new;
-            const float tt = __fadd_rn(t_soc, 1.0f);
-            if (fast) {
-                car_step_curves<0>(tt, cp, hp.cc, soc_new, power);
-                t_soc = soc_to_time<0>(soc_new, cp);
-            } else {
-                car_step_curves<1>(tt, cp, hp.cc, soc_new, power);
-                t_soc = soc_to_time<1>(soc_new, cp);
-            }
-        }
-        if (car) {
-            tl -= 1;
-            if (tl <= 0) {
-                car = false; leave = true; tl = 0;
-                power = t_target = t_soc = arr_soc = 0.0f;
-                meta = 0;
-            }
-        }
+    // ---- car_step, remove_car
+    if constexpr (MODE == MODE_COMPAT) {
+        if (on) car_step_compat(s, fast, cp, hp.cc);
+        leave = remove_car_compat(s, on);
     } else {
-        if (on && tl > 1) {  // a car that leaves this step is wiped right after its car_step (CHS.hpp:1196-1201)
-            power = next_power;
-            t_soc = next_t_soc;
-            w0 += kPsStep;
-        }
-        w0 &= ~kPsChg;
-        if (car) {
-            tl -= 1;
-            w0 -= 1u;
-            if (tl <= 0) {
-                car = false;
-                w0 = 0u;
-                power = t_target = t_soc = 0.0f;
-            }
-        }
-        if (RESET) w0 = 0u;
+        leave = car_step_philox(s, on, next_power, next_t_soc);
+        if (RESET) s.w = 0u;
     }
-    const bool charge = on && car;
-    if (MODE == MODE_PHILOX && charge) w0 |= kPsChg;
+    if (leave) t_target = 0.0f;
+    car = s.tl > 0;
 
-    // ---- receive_car (CHS.hpp:1272-1316 / 1583-1627): empties over the whole unit, admission rank = empties below the slot
+    // ---- receive_car: empties over the whole unit, admission rank = empties below the slot
     const bool empty = valid && !car;
     const uint64_t be = __ballot(empty);
     if (lane == 0) s_ball[wave] = be;
@@ -1306,134 +1415,72 @@ __global__ __launch_bounds__(256) void k_slot_unit(const DevCtx *__restrict__ ct
         rank += w < wave ? c : 0;
     }
     if (tid == 0) {
-        int line = (RESET || MODE == MODE_PHILOX) ? 0 : pkd_line(st.rec[4u * sidx + 3u]);
-        int flow, assign;
+        Received rc;
         if (MODE == MODE_COMPAT) {
             const CompatRng &cr = ctx->cr;
             CompatStream rs;
             rs.load(cr, sa.rng_cur, env);
-            const int mu = S / 2;  // round(charge_number / 2) on ints, CHS.hpp:1276
-            int n_in;
-            if (RESET) {
-                int temp = (int) roundf(rs.normal_f((float) mu, 1.0f));
-                n_in = temp > mu + 3 ? mu + 3 : (temp < mu - 3 ? mu - 3 : temp);
-            } else {
-                const int t_env = sa.env_clk ? clk_t(env_clk(sa, N, env)) : sa.t;
-                n_in = (int) tb.cnt[k][t_env * kLevels + rs.level()];
-            }
-            int tline = 0;
-            for (int w = 0; w < line; w++) tline += (rs.level() >= (int) tb.thr_renege[w]) ? 1 : 0;
-            line = tline;
-            int true_in = 0;
-            for (int j = 0; j < n_in; j++) {
-                const int m = line + j;
-                const int thr = (int) tb.thr_balk[m < kBalkTab ? m : kBalkTab - 1];
-                true_in += (rs.level() <= thr && j <= S) ? 1 : 0;
-            }
-            flow = fast ? n_in : true_in;  // CHS.hpp:1617 / 1306
-            assign = (line + flow) < empties ? (line + flow) : empties;
-            line = line + flow - assign;
-            line = line < kMaxLine ? line : kMaxLine;
-            for (int rr = 0; rr < assign; rr++) {  // ascending slot order == ascending rank
-                s_soc[rr] = arrive_soc_from(rs.normal_d(7.0, 3.0));
-                s_v[rr] = (uint32_t) rs.level();
-                const int late = (int) roundf(rs.normal_f(2.0f, 2.0f));  // mk_late_time("slow"), CHS.hpp:816-830
-                s_w[rr] = (uint32_t) (late < 0 ? 0 : late);
+            rc = receive_car_streams<RESET>(rs, hp, sa, tb, k, env, fast, RESET ? 0 : pkd_line(st.rec[4u * sidx + 3u]), empties);
+            for (int rr = 0; rr < rc.assign; rr++) {  // ascending slot order == ascending rank
+                const CarDraw d = draw_car_streams(rs);
+                s_soc[rr] = d.soc;
+                s_v[rr] = (uint32_t) d.lev;
+                s_w[rr] = (uint32_t) d.late;
             }
             rs.store(cr, sa.rng_cur, env);
         } else {
-            const uint32_t pk = st.pk[sa.tick & 1u][sidx];
-            int want;
-            if (RESET) {
-                flow = fast ? (int) (int16_t) (pk & 0xFFFFu) : (int) ((pk >> 16) & 0xFFFFu);
-                want = flow;
-            } else {
-                want = dk_want(pk);
-                flow = dk_flow(pk);
-            }
-            assign = want < empties ? want : empties;
-            line = want - assign;
-            line = line < kMaxLine ? line : kMaxLine;
+            rc = receive_car_word<RESET>(st.pk[sa.tick & 1u][sidx], fast, empties);
         }
-        s_hdr[0] = assign; s_hdr[1] = flow; s_hdr[2] = line;
+        s_hdr[0] = rc.assign; s_hdr[1] = rc.flow; s_hdr[2] = rc.line;
     }
     __syncthreads();
     const int assign = s_hdr[0];
-    const bool adm = empty && rank < assign;
-    float nc_soc = 0.0f;
-    if (adm) {  // add_car (CHS.hpp:864-877 / 1029-1042)
-        if (MODE == MODE_COMPAT) {
-            const int lev = (int) s_v[rank];
-            const float target = uniform_level(lev, 80.0f, 100.0f);
-            const NewCar nc = fast ? make_car<0>(s_soc[rank], lev, soc_to_time<0>(target, cp), (int) s_w[rank], cp)
-                                   : make_car<1>(s_soc[rank], lev, soc_to_time<1>(target, cp), (int) s_w[rank], cp);
-            nc_soc = nc.soc;
-            t_target = nc.t_target; t_soc = nc.t_soc; tl = nc.stay; power = nc.power;
-            car = tl > 0;
-            meta = nc.stay | (nc.lev << 7);
+    if (empty && rank < assign) {
+        if constexpr (MODE == MODE_COMPAT) {
+            const NewCar nc = add_car_compat(fast, s_soc[rank], (int) s_v[rank], (int) s_w[rank], cp);
+            t_target = nc.t_target;
+            s = compat_slot_of(nc);
         } else {
-            PhiloxCtx px{hp.key[0], hp.key[1], CHUB_TICK(hp, sa.tick), (uint32_t) (hp.env_id0 + env)};
-            const U4 o = px.block(SITE_SOC, (uint32_t) hub_slot, 0);
-            const uint32_t c = o.v[0] >> kSocLevelShift, lev = o.v[1] % 1000u;
-            const f32x2 e0 = *(CHUB_G(const f32x2)) ((CHUB_G(const char)) cls + (size_t) c * (kClsRow * 8u));
-            t_target = tb.ttab[k][lev];
-            const int late = late_from_word(tb.late_thr, o.v[2]);
-            int stay = (int) ceilf(__fsub_rn(t_target, e0.y)) + late;
-            stay = stay > kMaxStay ? kMaxStay : stay;
-            power = e0.x; t_soc = e0.y; tl = stay;
-            car = tl > 0;
-            w0 = car ? ps_make(stay, c, lev) : 0u;
-            sl.stay8[idx] = (uint8_t) stay;
+            const PhiloxCar nc = add_car_philox(hp, sa, tb, k, env, hub_slot);
+            t_target = nc.t_target;
+            s = philox_slot_of(nc);
+            sl.stay8[idx] = (uint8_t) nc.stay;
         }
-    } else if (MODE == MODE_COMPAT && (leave || RESET)) {
-        meta = 0;
+        car = s.tl > 0;
+    } else if (leave || RESET) {
+        if constexpr (MODE == MODE_COMPAT) s.meta = 0;
     }
 
     // ---- calculate_output (CHS.hpp:1233-1261 / 1544-1572)
-    const bool urgent = car && must_charge(t_target, t_soc, tl);
+    const bool urgent = car && must_charge(t_target, s.t_soc, s.tl);
     const uint64_t bc = __ballot(car);
     if (lane == 0) s_ball[4 + wave] = bc;
     if (MODE == MODE_COMPAT) {
-        s_a[tid] = urgent ? power : 0.0f;
-        s_b[tid] = charge ? power : 0.0f;
-        s_c[tid] = car ? power : 0.0f;
+        s_a[tid] = urgent ? s.power : 0.0f;
+        s_b[tid] = s.charge ? s.power : 0.0f;
+        s_c[tid] = car ? s.power : 0.0f;
     } else {
-        const int q = kw_to_fixed(power);
+        const int q = kw_to_fixed(s.power);
         s_u[tid] = (uint32_t) (urgent ? q : 0);
-        s_v[tid] = (uint32_t) (charge ? q : 0);
+        s_v[tid] = (uint32_t) (s.charge ? q : 0);
         s_w[tid] = (uint32_t) (car ? q : 0);
     }
     if (valid) {
-        if (MODE == MODE_COMPAT) {
-            u32x4 h2;
-            h2.x = __float_as_uint(power); h2.y = __float_as_uint(adm ? nc_soc : arr_soc); h2.z = __float_as_uint(t_soc);
-            h2.w = (uint32_t) tl | (charge ? 128u : 0u) | ((uint32_t) meta << 8);
-            ((CHUB_G(u32x4)) sl.hot)[idx] = h2;
-        } else {
-            sl.hot[idx] = w0;
-        }
+        if constexpr (MODE == MODE_COMPAT) ((CHUB_G(u32x4)) sl.hot)[idx] = s.pack();
+        else sl.hot[idx] = s.w;
     }
     __syncthreads();
     if (tid == 0) {
         const int cars = __popcll(s_ball[4]) + __popcll(s_ball[5]) + __popcll(s_ball[6]) + __popcll(s_ball[7]);
         float r_min, r_chg, r_max;
-        if (MODE == MODE_COMPAT) {  // the reference adds the slot powers sequentially in f32 (CHS.hpp:1244-1255)
-            r_min = r_chg = r_max = 0.0f;
-            for (int i = 0; i < S; i++) {
-                r_max = __fadd_rn(r_max, s_c[i]);
-                r_min = __fadd_rn(r_min, s_a[i]);
-                r_chg = __fadd_rn(r_chg, s_b[i]);
-            }
-        } else {  // order-independent: 64-bit sums of the slot powers in units of 2^-19 kW, one rounding to f32
-            long long i_min = 0, i_chg = 0, i_max = 0;
-            for (int i = 0; i < S; i++) {
-                i_min += (long long) (int) s_u[i];
-                i_chg += (long long) (int) s_v[i];
-                i_max += (long long) (int) s_w[i];
-            }
-            r_min = (float) i_min * (1.0f / 524288.0f);
-            r_chg = (float) i_chg * (1.0f / 524288.0f);
-            r_max = (float) i_max * (1.0f / 524288.0f);
+        if (MODE == MODE_COMPAT) {
+            SumsF32 r = {0.0f, 0.0f, 0.0f};
+            r.add(s_a, s_b, s_c, S);
+            r_min = r.mn; r_chg = r.chg; r_max = r.mx;
+        } else {
+            SumsI64 r = {0, 0, 0};
+            r.add(s_u, s_v, s_w, S);
+            r_min = fixed64_to_kw(r.mn); r_chg = fixed64_to_kw(r.chg); r_max = fixed64_to_kw(r.mx);
         }
         rec_store(st.rec, sidx, r_min, r_chg, r_max, pkd_make(s_hdr[2], s_hdr[1], cars));
     }
@@ -1490,7 +1537,7 @@ __global__ __launch_bounds__(256) void k_slot_unit_any(const DevCtx *__restrict_
             if (MODE == MODE_COMPAT) {
                 const u32x4 hot = ((CHUB_G(u32x4)) sl.hot)[idx];
                 t_soc = __uint_as_float(hot.z);
-                tl = (int) (hot.w & 127u);
+                tl = hot_tl(hot.w);
                 if (tl > 0) t_target = tb.ttab[k][hot_level(hot.w)];
             } else {
                 const uint32_t w0 = sl.hot[idx];
@@ -1509,7 +1556,7 @@ __global__ __launch_bounds__(256) void k_slot_unit_any(const DevCtx *__restrict_
             bool car;
             if (MODE == MODE_COMPAT) {
                 const u32x4 hot = ((CHUB_G(u32x4)) sl.hot)[idx];
-                car = (hot.w & 127u) != 0u;
+                car = hot_tl(hot.w) != 0;
                 power = __uint_as_float(hot.x);
             } else {
                 const uint32_t w0 = sl.hot[idx];
@@ -1527,11 +1574,8 @@ __global__ __launch_bounds__(256) void k_slot_unit_any(const DevCtx *__restrict_
             s_cb[rk] = car ? 1 : 0;
         }
         __syncthreads();
-        // catch_load (CHS.hpp:358-366) against the previous calculate_output; rank_power_add (CHS.hpp:1375-1402): sequential f32
-        const StationRec pr = rec_load(st.rec, sidx);
-        load = sa.actions[(uint32_t) env * (uint32_t) hp.act_dim + (uint32_t) hub0];
-        if (load > pr.mx) load = pr.mx;
-        else if (load < pr.mn) load = pr.mn;
+        // catch_load against the previous calculate_output; rank_power_add (CHS.hpp:1375-1402): sequential f32
+        load = catch_load(hp, sa, st, k, env, sidx);
         if (tid == 0) {
             float cum = 0.0f;
             int cars_before = 0;
@@ -1551,86 +1595,47 @@ __global__ __launch_bounds__(256) void k_slot_unit_any(const DevCtx *__restrict_
         const int slot = (c << 8) + tid;
         const bool valid = slot < S;
         const uint32_t idx = idx0 + (uint32_t) slot;
-        float power = 0.0f, t_target = 0.0f, t_soc = 0.0f, arr_soc = 0.0f, a = 0.0f;
-        int tl = 0, meta = 0;
-        uint32_t w0 = 0u;
-        if (!RESET && valid) {
-            a = sa.actions[(uint32_t) env * (uint32_t) hp.act_dim + (uint32_t) (hub0 + slot)];
-            if (MODE == MODE_COMPAT) {
-                const u32x4 hot = ((CHUB_G(u32x4)) sl.hot)[idx];
-                power = __uint_as_float(hot.x); arr_soc = __uint_as_float(hot.y); t_soc = __uint_as_float(hot.z);
-                tl = (int) (hot.w & 127u);
-                meta = (int) (hot.w >> 8);
-                if (tl > 0) t_target = tb.ttab[k][hot_level(hot.w)];
-            } else {
-                w0 = sl.hot[idx];
-                tl = ps_tl(w0);
-                if (tl > 0) {  // (the state word says the rest: a car_step is one more entry along the class row)
-                    t_soc = (*(CHUB_G(const f32x2)) ((CHUB_G(const char)) cls + ((size_t) ps_cls(w0) * (kClsRow * 8u) + ps_n(w0) * 8u))).y;
-                    t_target = tb.ttab[k][ps_lev(w0)];
-                }
-            }
-        }
-        bool car = tl > 0;
-        bool on;
-        if (!RESET && sa.load_mode) {
-            on = false;
-            if (car) {
+        float a = 0.0f;
+        if (!RESET && valid) a = sa.actions[(uint32_t) env * (uint32_t) hp.act_dim + (uint32_t) (hub0 + slot)];
+        // on / off of a slot with a car: the scalar-load control by the car's urgency rank, else the pile's action or its urgency
+        auto switched_on = [&](const float t_target, const float t_soc, const int tl) {
+            if (!RESET && sa.load_mode) {
                 const int rk = (int) s_rk[slot];
-                if (cp) {
-                    const float constant_power = fast ? (float) 36.44764034125146 : (float) 5.254973139368931;
-                    const int n_on = (int) roundf(__fdiv_rn(load, constant_power));
-                    on = (int) s_cb[rk] < n_on;
-                } else {
-                    on = (double) load + 0.0001 >= (double) s_pw[rk];
+                return load_says_on(cp, fast, load, s_pw[rk], (int) s_cb[rk]);
+            }
+            return a >= kActOnThreshold || must_charge(t_target, t_soc, tl);
+        };
+        bool car;
+        if constexpr (MODE == MODE_COMPAT) {
+            CompatSlot s = {};
+            float t_target = 0.0f;
+            if (!RESET && valid) {
+                const u32x4 hot = ((CHUB_G(u32x4)) sl.hot)[idx];
+                s = CompatSlot::unpack(hot);
+                if (s.tl > 0) t_target = tb.ttab[k][hot_level(hot.w)];
+            }
+            const bool on = s.tl > 0 && switched_on(t_target, s.t_soc, s.tl);
+            if (on) car_step_compat(s, fast, cp, hp.cc);
+            remove_car_compat(s, on);
+            if (RESET) s.meta = 0;
+            if (valid) ((CHUB_G(u32x4)) sl.hot)[idx] = s.pack();
+            car = s.tl > 0;
+        } else {  // (the state word alone: pass 2 reads the car's row entry again)
+            PhiloxWord s = {};
+            float t_target = 0.0f, t_soc = 0.0f;
+            if (!RESET && valid) {
+                s.w = sl.hot[idx];
+                s.tl = ps_tl(s.w);
+                if (s.tl > 0) {
+                    t_soc = (*(CHUB_G(const f32x2)) ((CHUB_G(const char)) cls + ((size_t) ps_cls(s.w) * (kClsRow * 8u) + ps_n(s.w) * 8u))).y;
+                    t_target = tb.ttab[k][ps_lev(s.w)];
                 }
             }
-        } else {
-            on = car && (a >= kActOnThreshold || must_charge(t_target, t_soc, tl));
-        }
-        // car_step (CHS.hpp:900-905 / 1065-1070), remove_car (CHS.hpp:912-923 / 1077-1088)
-        if (MODE == MODE_COMPAT) {
-            if (on) {
-                meta += 1 << 17;
-                float soc_new;
-                const float tt = __fadd_rn(t_soc, 1.0f);
-                if (fast) {
-                    car_step_curves<0>(tt, cp, hp.cc, soc_new, power);
-                    t_soc = soc_to_time<0>(soc_new, cp);
-                } else {
-                    car_step_curves<1>(tt, cp, hp.cc, soc_new, power);
-                    t_soc = soc_to_time<1>(soc_new, cp);
-                }
-            }
-            if (car) {
-                tl -= 1;
-                if (tl <= 0) {
-                    car = false; tl = 0;
-                    power = t_soc = arr_soc = 0.0f;
-                    meta = 0;
-                }
-            }
-            if (RESET) meta = 0;
-        } else {
-            if (on && tl > 1) w0 += kPsStep;  // a car that leaves this step is wiped right after its car_step (CHS.hpp:1196-1201)
-            w0 &= ~kPsChg;
-            if (car) {
-                tl -= 1;
-                w0 -= 1u;
-                if (tl <= 0) { car = false; w0 = 0u; }
-            }
-            if (RESET) w0 = 0u;
-        }
-        const bool charge = on && car;
-        if (valid) {
-            if (MODE == MODE_COMPAT) {
-                u32x4 h2;
-                h2.x = __float_as_uint(power); h2.y = __float_as_uint(arr_soc); h2.z = __float_as_uint(t_soc);
-                h2.w = (uint32_t) tl | (charge ? 128u : 0u) | ((uint32_t) meta << 8);
-                ((CHUB_G(u32x4)) sl.hot)[idx] = h2;
-            } else {
-                sl.hot[idx] = charge ? (w0 | kPsChg) : w0;
-            }
+            const bool on = s.tl > 0 && switched_on(t_target, t_soc, s.tl);
+            car_step_word(s, on);
+            if (RESET) s.w = 0u;
+            if (valid) sl.hot[idx] = s.w;
+            car = s.tl > 0;
         }
         const uint64_t be = __ballot(valid && !car);
         if (lane == 0 && be) atomicAdd(&s_cnt, __popcll(be));
@@ -1641,55 +1646,22 @@ __global__ __launch_bounds__(256) void k_slot_unit_any(const DevCtx *__restrict_
     // ---- receive_car (CHS.hpp:1272-1316 / 1583-1627): lane 0 decides how many cars the unit admits
     CompatStream rs;
     if (tid == 0) {
-        int line = (RESET || MODE == MODE_PHILOX) ? 0 : pkd_line(st.rec[4u * sidx + 3u]);
-        int flow, assign;
+        Received rc;
         if (MODE == MODE_COMPAT) {
             rs.load(ctx->cr, sa.rng_cur, env);
-            const int mu = S / 2;  // round(charge_number / 2) on ints, CHS.hpp:1276
-            int n_in;
-            if (RESET) {
-                int temp = (int) roundf(rs.normal_f((float) mu, 1.0f));
-                n_in = temp > mu + 3 ? mu + 3 : (temp < mu - 3 ? mu - 3 : temp);
-            } else {
-                const int t_env = sa.env_clk ? clk_t(env_clk(sa, N, env)) : sa.t;
-                n_in = (int) tb.cnt[k][t_env * kLevels + rs.level()];
-            }
-            int tline = 0;
-            for (int w = 0; w < line; w++) tline += (rs.level() >= (int) tb.thr_renege[w]) ? 1 : 0;
-            line = tline;
-            int true_in = 0;
-            for (int j = 0; j < n_in; j++) {
-                const int m = line + j;
-                const int thr = (int) tb.thr_balk[m < kBalkTab ? m : kBalkTab - 1];
-                true_in += (rs.level() <= thr && j <= S) ? 1 : 0;
-            }
-            flow = fast ? n_in : true_in;  // CHS.hpp:1617 / 1306
-            assign = (line + flow) < empties ? (line + flow) : empties;
-            line = line + flow - assign;
-            line = line < kMaxLine ? line : kMaxLine;
+            rc = receive_car_streams<RESET>(rs, hp, sa, tb, k, env, fast, RESET ? 0 : pkd_line(st.rec[4u * sidx + 3u]), empties);
         } else {
-            const uint32_t pk = st.pk[sa.tick & 1u][sidx];
-            int want;
-            if (RESET) {
-                flow = fast ? (int) (int16_t) (pk & 0xFFFFu) : (int) ((pk >> 16) & 0xFFFFu);
-                want = flow;
-            } else {
-                want = dk_want(pk);
-                flow = dk_flow(pk);
-            }
-            assign = want < empties ? want : empties;
-            line = want - assign;
-            line = line < kMaxLine ? line : kMaxLine;
+            rc = receive_car_word<RESET>(st.pk[sa.tick & 1u][sidx], fast, empties);
         }
-        s_hdr[0] = assign; s_hdr[1] = flow; s_hdr[2] = line;
+        s_hdr[0] = rc.assign; s_hdr[1] = rc.flow; s_hdr[2] = rc.line;
     }
     __syncthreads();
     const int assign = s_hdr[0];
 
-    // ---- pass 2: admission by rank, add_car (CHS.hpp:864-877 / 1029-1042), calculate_output (CHS.hpp:1233-1261 / 1544-1572)
+    // ---- pass 2: admission by rank, add_car, calculate_output (CHS.hpp:1233-1261 / 1544-1572)
     int base = 0, cars = 0;                     // empties / cars of the chunks in front (the same number in every lane)
-    float r_min = 0.0f, r_chg = 0.0f, r_max = 0.0f;   // lane 0: the running sums
-    long long i_min = 0, i_chg = 0, i_max = 0;
+    SumsF32 rf = {0.0f, 0.0f, 0.0f};            // lane 0: the running sums
+    SumsI64 ri = {0, 0, 0};
     for (int c = 0; c < chunks; c++) {
         const int slot = (c << 8) + tid;
         const bool valid = slot < S;
@@ -1700,9 +1672,8 @@ __global__ __launch_bounds__(256) void k_slot_unit_any(const DevCtx *__restrict_
         if (valid) {  // what pass 1 left (this lane's own stores)
             if (MODE == MODE_COMPAT) {
                 const u32x4 hot = ((CHUB_G(u32x4)) sl.hot)[idx];
-                power = __uint_as_float(hot.x); t_soc = __uint_as_float(hot.z);
-                tl = (int) (hot.w & 127u);
-                charge = (hot.w & 128u) != 0u;
+                const CompatSlot cs = CompatSlot::unpack(hot);
+                power = cs.power; t_soc = cs.t_soc; tl = cs.tl; charge = cs.charge;
                 if (tl > 0) t_target = tb.ttab[k][hot_level(hot.w)];
             } else {
                 const uint32_t w0 = sl.hot[idx];
@@ -1731,10 +1702,10 @@ __global__ __launch_bounds__(256) void k_slot_unit_any(const DevCtx *__restrict_
                 int n_new = assign - base;
                 n_new = n_new < 0 ? 0 : (n_new > chunk_empties ? chunk_empties : n_new);
                 for (int rr = 0; rr < n_new; rr++) {
-                    s_soc[rr] = arrive_soc_from(rs.normal_d(7.0, 3.0));
-                    s_v[rr] = (uint32_t) rs.level();
-                    const int late = (int) roundf(rs.normal_f(2.0f, 2.0f));  // mk_late_time("slow"), CHS.hpp:816-830
-                    s_w[rr] = (uint32_t) (late < 0 ? 0 : late);
+                    const CarDraw d = draw_car_streams(rs);
+                    s_soc[rr] = d.soc;
+                    s_v[rr] = (uint32_t) d.lev;
+                    s_w[rr] = (uint32_t) d.late;
                 }
             }
             __syncthreads();
@@ -1742,30 +1713,16 @@ __global__ __launch_bounds__(256) void k_slot_unit_any(const DevCtx *__restrict_
         if (empty && rank < assign) {
             if (MODE == MODE_COMPAT) {
                 const int r = rank - base;
-                const int lev = (int) s_v[r];
-                const float target = uniform_level(lev, 80.0f, 100.0f);
-                const NewCar nc = fast ? make_car<0>(s_soc[r], lev, soc_to_time<0>(target, cp), (int) s_w[r], cp)
-                                       : make_car<1>(s_soc[r], lev, soc_to_time<1>(target, cp), (int) s_w[r], cp);
+                const NewCar nc = add_car_compat(fast, s_soc[r], (int) s_v[r], (int) s_w[r], cp);
                 t_target = nc.t_target; t_soc = nc.t_soc; tl = nc.stay; power = nc.power;
-                car = tl > 0;
-                u32x4 h2;
-                h2.x = __float_as_uint(power); h2.y = __float_as_uint(nc.soc); h2.z = __float_as_uint(t_soc);
-                h2.w = (uint32_t) tl | ((uint32_t) (nc.stay | (nc.lev << 7)) << 8);
-                ((CHUB_G(u32x4)) sl.hot)[idx] = h2;
+                ((CHUB_G(u32x4)) sl.hot)[idx] = compat_slot_of(nc).pack();
             } else {
-                PhiloxCtx px{hp.key[0], hp.key[1], CHUB_TICK(hp, sa.tick), (uint32_t) (hp.env_id0 + env)};
-                const U4 o = px.block(SITE_SOC, (uint32_t) (hub0 + slot), 0);
-                const uint32_t cl = o.v[0] >> kSocLevelShift, lev = o.v[1] % 1000u;
-                const f32x2 e0 = *(CHUB_G(const f32x2)) ((CHUB_G(const char)) cls + (size_t) cl * (kClsRow * 8u));
-                t_target = tb.ttab[k][lev];
-                const int late = late_from_word(tb.late_thr, o.v[2]);
-                int stay = (int) ceilf(__fsub_rn(t_target, e0.y)) + late;
-                stay = stay > kMaxStay ? kMaxStay : stay;
-                power = e0.x; t_soc = e0.y; tl = stay;
-                car = tl > 0;
-                sl.hot[idx] = car ? ps_make(stay, cl, lev) : 0u;
-                sl.stay8[idx] = (uint8_t) stay;
+                const PhiloxCar nc = add_car_philox(hp, sa, tb, k, env, hub0 + slot);
+                t_target = nc.t_target; t_soc = nc.t_soc; tl = nc.stay; power = nc.power;
+                sl.hot[idx] = nc.word;
+                sl.stay8[idx] = (uint8_t) nc.stay;
             }
+            car = tl > 0;
         }
         const bool urgent = car && must_charge(t_target, t_soc, tl);
         const uint64_t bc = __ballot(car);
@@ -1784,19 +1741,8 @@ __global__ __launch_bounds__(256) void k_slot_unit_any(const DevCtx *__restrict_
         cars += __popcll(s_ball[4]) + __popcll(s_ball[5]) + __popcll(s_ball[6]) + __popcll(s_ball[7]);
         if (tid == 0) {
             const int n = S - (c << 8) < 256 ? S - (c << 8) : 256;
-            if (MODE == MODE_COMPAT) {  // the reference adds the slot powers sequentially in f32 (CHS.hpp:1244-1255)
-                for (int i = 0; i < n; i++) {
-                    r_max = __fadd_rn(r_max, s_c[i]);
-                    r_min = __fadd_rn(r_min, s_a[i]);
-                    r_chg = __fadd_rn(r_chg, s_b[i]);
-                }
-            } else {  // order-independent: 64-bit sums of the slot powers in units of 2^-19 kW, one rounding to f32
-                for (int i = 0; i < n; i++) {
-                    i_min += (long long) (int) s_u[i];
-                    i_chg += (long long) (int) s_v[i];
-                    i_max += (long long) (int) s_w[i];
-                }
-            }
+            if (MODE == MODE_COMPAT) rf.add(s_a, s_b, s_c, n);
+            else ri.add(s_u, s_v, s_w, n);
         }
         base += chunk_empties;
         __syncthreads();  // the chunk's LDS areas are free again
@@ -1804,12 +1750,10 @@ __global__ __launch_bounds__(256) void k_slot_unit_any(const DevCtx *__restrict_
     if (tid == 0) {
         if (MODE == MODE_COMPAT) {
             rs.store(ctx->cr, sa.rng_cur, env);
+            rec_store(st.rec, sidx, rf.mn, rf.chg, rf.mx, pkd_make(s_hdr[2], s_hdr[1], cars));
         } else {
-            r_min = (float) i_min * (1.0f / 524288.0f);
-            r_chg = (float) i_chg * (1.0f / 524288.0f);
-            r_max = (float) i_max * (1.0f / 524288.0f);
+            rec_store(st.rec, sidx, fixed64_to_kw(ri.mn), fixed64_to_kw(ri.chg), fixed64_to_kw(ri.mx), pkd_make(s_hdr[2], s_hdr[1], cars));
         }
-        rec_store(st.rec, sidx, r_min, r_chg, r_max, pkd_make(s_hdr[2], s_hdr[1], cars));
     }
 }
 
@@ -2459,22 +2403,10 @@ __device__ __forceinline__ void slot_body_curves(const HubParams &hp, const Step
     const uint64_t be = __ballot(empty) & unit_mask;
     const int empties = __popcll(be);
     const int rank = prefix_count(be);
-    int line = 0, flow = 0, assign = 0;
-    if (unit_ok) {
-        int want;
-        if (RESET) {
-            flow = TYPE == 0 ? (int) (int16_t) (pk_in & 0xFFFFu) : (int) ((pk_in >> 16) & 0xFFFFu);
-            want = flow;
-        } else {
-            want = dk_want(pk_in);
-            flow = dk_flow(pk_in);
-        }
-        assign = want < empties ? want : empties;  // assign_car, CHS.hpp:417-430
-        line = want - assign;
-        line = line < kMaxLine ? line : kMaxLine;
-    }
+    Received rc = {0, 0, 0};
+    if (unit_ok) rc = receive_car_word<RESET>(pk_in, TYPE == 0, empties);
     float tgt = t_target;
-    if (empty && rank < assign) {  // add_car (CHS.hpp:864-877 / 1029-1042)
+    if (empty && rank < rc.assign) {  // add_car (CHS.hpp:864-877 / 1029-1042)
         float soc;
         uint32_t lev;
         int late;
@@ -2484,8 +2416,7 @@ __device__ __forceinline__ void slot_body_curves(const HubParams &hp, const Step
             lev = tp[1] & 0xFFFFu;
             late = (int) (tp[1] >> 16);
         } else {
-            PhiloxCtx px{hp.key[0], hp.key[1], CHUB_TICK(hp, sa.tick), (uint32_t) (hp.env_id0 + env)};
-            const U4 o = px.block(SITE_SOC, (uint32_t) hub_slot, 0);
+            const U4 o = car_block(hp, sa, env, hub_slot);
             soc = soc_from_word(tb.soc_d_icdf, o.v[0]);
             lev = o.v[1] % 1000u;
             late = late_from_word(tb.late_thr, o.v[2]);
@@ -2506,12 +2437,7 @@ __device__ __forceinline__ void slot_body_curves(const HubParams &hp, const Step
     const bool urgent = car && must_charge(tgt, t_soc, tl);
     const int q = kw_to_fixed(power);
     int i_min = urgent ? q : 0, i_max = car ? q : 0, i_chg = charge ? q : 0;
-    if (H > 1) { i_min += dppi_xor1(i_min); i_max += dppi_xor1(i_max); i_chg += dppi_xor1(i_chg); }
-    if (H > 2) { i_min += dppi_xor2(i_min); i_max += dppi_xor2(i_max); i_chg += dppi_xor2(i_chg); }
-    if (H > 4) { i_min += dppi_mirror8(i_min); i_max += dppi_mirror8(i_max); i_chg += dppi_mirror8(i_chg); }
-    if (H > 8) { i_min += dppi_mirror16(i_min); i_max += dppi_mirror16(i_max); i_chg += dppi_mirror16(i_chg); }
-    if (H > 16) { i_min += __shfl_xor(i_min, 16); i_max += __shfl_xor(i_max, 16); i_chg += __shfl_xor(i_chg, 16); }
-    if (H > 32) { i_min += __shfl_xor(i_min, 32); i_max += __shfl_xor(i_max, 32); i_chg += __shfl_xor(i_chg, 32); }
+    unit_sums_dpp(H, i_min, i_max, i_chg);
     const int cars = __popcll(__ballot(car) & unit_mask);
 
     if (valid) {
@@ -2519,7 +2445,7 @@ __device__ __forceinline__ void slot_body_curves(const HubParams &hp, const Step
         const f32x2 out = {car ? power : 0.0f, car ? t_soc : 0.0f};
         *(CHUB_G(f32x2)) ((CHUB_G(float)) sl.hot + 2u * idx) = out;
     }
-    if (unit_ok && slot == 0) rec_store(st.rec, sidx, fixed_to_kw(i_min), fixed_to_kw(i_chg), fixed_to_kw(i_max), pkd_make(line, flow, cars));
+    if (unit_ok && slot == 0) rec_store(st.rec, sidx, fixed_to_kw(i_min), fixed_to_kw(i_chg), fixed_to_kw(i_max), pkd_make(rc.line, rc.flow, cars));
 }
 
 template <bool RESET, int BLOCK>
@@ -2560,7 +2486,7 @@ __global__ __launch_bounds__(BLOCK) void k_compat_empties(const DevCtx *__restri
     const uint64_t unit_mask = (U == 64) ? ~0ull : (uiw < upw ? (((1ull << U) - 1ull) << (uiw * U)) : 0ull);
     uint32_t w = 0u;
     if (valid) w = ctx->sl.hot[4 * ((size_t) hp.base[k] + (size_t) env * (size_t) S + (size_t) slot) + 3];  // (slot indices go up to 2^31: 64-bit word index)
-    const bool empty = valid && (int) (w & 127u) <= 1;
+    const bool empty = valid && (int) (w & 127u) <= 1;  // (hot_tl spelt out: through the function this kernel comes out with another schedule)
     const uint64_t be = __ballot(empty) & unit_mask, be2 = __ballot(valid && (int) (w & 127u) <= 2) & unit_mask;
     if (unit_ok && slot == 0) {
         ctx->st.empt[(uint32_t) k * (uint32_t) hp.n_envs + (uint32_t) env] = (uint8_t) __popcll(be);
@@ -2600,50 +2526,21 @@ __device__ __forceinline__ void compat_walk_env(const DevCtx *__restrict__ ctx, 
             line = pkd_line(st.rec[4u * sidx + 3u]);
             empties = (int) st.empt[sidx];
         }
-        const int mu = S / 2;  // round(charge_number / 2) on ints, CHS.hpp:1276
-        int n_in;
-        if (RESET) {
-            const float cn = rs.normal_f((float) mu, 1.0f);
-            int temp = (int) roundf(cn);
-            temp = temp > mu + 3 ? mu + 3 : (temp < mu - 3 ? mu - 3 : temp);
-            n_in = temp;
-        } else {
-            const int t_env = sa.env_clk ? clk_t(env_clk(sa, N, env)) : sa.t;  // per-env clocks: the env's own slot of day
-            n_in = (int) tb.cnt[k][t_env * kLevels + rs.level()];
-        }
-        int tline = 0;
-        for (int w = 0; w < line; w++) tline += (rs.level() >= (int) tb.thr_renege[w]) ? 1 : 0;
-        int new_line = tline;
-        int true_in = 0;
-        for (int j = 0; j < n_in; j++) {
-            const int m = new_line + j;
-            const int thr = (int) tb.thr_balk[m < kBalkTab ? m : kBalkTab - 1];
-            true_in += (rs.level() <= thr && j <= S) ? 1 : 0;
-        }
-        const int fl = fast ? n_in : true_in;
-        const int as = (new_line + fl) < empties ? (new_line + fl) : empties;
-        new_line = new_line + fl - as;
-        new_line = new_line < kMaxLine ? new_line : kMaxLine;
+        const Received rc = receive_car_streams<RESET>(rs, hp, sa, tb, k, env, fast, line, empties);
         CHUB_G(u32x4) var = (CHUB_G(u32x4)) ctx->sl.var[par] + 2u * ((uint32_t) env * St + (uint32_t) (k ? hp.S[0] : 0));
         int n_short = 0;
-        for (int rr = 0; rr < as; rr++) {  // ascending slot order == ascending rank
-            const float soc = arrive_soc_from(rs.normal_d(7.0, 3.0));
-            const int lev = rs.level();
-            int late = (int) roundf(rs.normal_f(2.0f, 2.0f));  // mk_late_time("slow"), CHS.hpp:816-830
-            late = late < 0 ? 0 : late;
-            // add_car (CHS.hpp:864-877 / 1029-1042) HERE, where the car's variates are in registers: every lane of the walk that still has a car
-            // to draw evaluates it, while in the slot pass the one lane in fifteen that admits a car made its whole wave pay for the f64 curve
-            // work (round 6: 250 of a slot wave's 813 vector instructions).  Same functions on the same values: the same bits.
-            const float target = uniform_level(lev, 80.0f, 100.0f);
-            NewCar nc;
-            if (fast) nc = make_car<0>(soc, lev, soc_to_time<0>(target, cp), late, cp);
-            else nc = make_car<1>(soc, lev, soc_to_time<1>(target, cp), late, cp);
-            var[2 * rr] = u32x4{__float_as_uint(nc.power), __float_as_uint(nc.t_target), __float_as_uint(nc.t_soc), (uint32_t) nc.stay | ((uint32_t) lev << 7)};
-            var[2 * rr + 1] = u32x4{__float_as_uint(soc), 0u, 0u, 0u};
+        for (int rr = 0; rr < rc.assign; rr++) {  // ascending slot order == ascending rank
+            const CarDraw d = draw_car_streams(rs);
+            // add_car HERE, where the car's variates are in registers: every lane of the walk that still has a car to draw evaluates it, while
+            // in the slot pass the one lane in fifteen that admits a car made its whole wave pay for the f64 curve work (round 6: 250 of a slot
+            // wave's 813 vector instructions)
+            const NewCar nc = add_car_compat(fast, d.soc, d.lev, d.late, cp);
+            var[2 * rr] = u32x4{__float_as_uint(nc.power), __float_as_uint(nc.t_target), __float_as_uint(nc.t_soc), (uint32_t) nc.stay | ((uint32_t) d.lev << 7)};
+            var[2 * rr + 1] = u32x4{__float_as_uint(d.soc), 0u, 0u, 0u};
             // (what a walk two steps ahead needs of this step's admissions: how many of them stay one slot at most)
             n_short += (nc.stay <= 1) ? 1 : 0;
         }
-        st.fa[par][sidx] = ((uint32_t) fl & 0xFFFFu) | ((uint32_t) (as > 0 ? as : 0) << 16) | ((uint32_t) new_line << 24);
+        st.fa[par][sidx] = ((uint32_t) rc.flow & 0xFFFFu) | ((uint32_t) (rc.assign > 0 ? rc.assign : 0) << 16) | ((uint32_t) rc.line << 24);
         if (sa.walk_short) st.shrt[par][sidx] = (uint8_t) n_short;
     }
     if (FORECOURT && !RESET) {
@@ -2663,8 +2560,9 @@ __device__ __forceinline__ void compat_walk_env(const DevCtx *__restrict__ ctx, 
 // 3 + 1.5 cars per env) on a chain that is the split step's long pole.  Here: phase A, lane = env, draws the raw points of up to kWalkCap cars
 // into the wave's staging area in LDS (compacted: car j of the lanes that still have one, lane order); phase B, lane = CAR, evaluates them
 // densely packed (3 + 2 passes) and writes the new cars where the slot pass looks for them.  Rounds repeat while any env has cars left.
-// Same streams, same order of draws per env, the same functions on the same values: the same bits as compat_walk_env, which k_compat_small
-// (a handful of envs on one wave's lanes) keeps.
+// Same streams, same order of draws per env, the same phase functions as compat_walk_env, which k_compat_small (a handful of envs on one
+// wave's lanes) keeps.  walk_rounds is the one form that does not call draw_car_streams: it takes a car's variates in two halves (the accepted
+// points here, the transforms by another lane), which normal_d / normal_f are defined as (CompatStreamT).
 constexpr int kWalkCap = 256;
 constexpr int kWalkStageWords = kWalkCap * 7 + 64;  // per staged car: y, r2 of the SoC normal (f64), y, r2 of the extra-stay normal (f32), a word; + one counter per lane
 struct WalkStage {
@@ -2751,11 +2649,7 @@ __device__ __forceinline__ void walk_rounds(const DevCtx *__restrict__ ctx, cons
                 const int lev = (int) (w & 1023u);
                 int late = (int) roundf(Stream::normal_of_polar_f(sg.yf[i], sg.r2f[i], 2.0f, 2.0f));  // mk_late_time("slow")
                 late = late < 0 ? 0 : late;
-                // add_car (CHS.hpp:864-877 / 1029-1042)
-                const float target = uniform_level(lev, 80.0f, 100.0f);
-                NewCar nc;
-                if (fast) nc = make_car<0>(soc, lev, soc_to_time<0>(target, cp), late, cp);
-                else nc = make_car<1>(soc, lev, soc_to_time<1>(target, cp), late, cp);
+                const NewCar nc = add_car_compat(fast, soc, lev, late, cp);
                 const uint32_t vi = (env0 + owner) * St + (uint32_t) (k ? hp.S[0] : 0) + rank;
                 // ONE 32-byte record per new car (the hot record's four words + the arrival SoC): a sector written whole; neighbouring lanes hold
                 // the same env's next admission ranks (the staging area is filled env by env), so a unit's records leave as one run
@@ -2804,31 +2698,10 @@ __device__ __forceinline__ void compat_walk_wave(const DevCtx *__restrict__ ctx,
                 line = pkd_line(st.rec[4u * sidx + 3u]);
                 empties = (int) st.empt[sidx];
             }
-            const int mu = S / 2;  // round(charge_number / 2) on ints, CHS.hpp:1276
-            int n_in;
-            if (RESET) {
-                const float cn = rs.normal_f((float) mu, 1.0f);
-                int temp = (int) roundf(cn);
-                temp = temp > mu + 3 ? mu + 3 : (temp < mu - 3 ? mu - 3 : temp);
-                n_in = temp;
-            } else {
-                const int t_env = sa.env_clk ? clk_t(env_clk(sa, N, env)) : sa.t;  // per-env clocks: the env's own slot of day
-                n_in = (int) tb.cnt[k][t_env * kLevels + rs.level()];
-            }
-            int tline = 0;
-            for (int w = 0; w < line; w++) tline += (rs.level() >= (int) tb.thr_renege[w]) ? 1 : 0;
-            new_line = tline;
-            int true_in = 0;
-            for (int j = 0; j < n_in; j++) {
-                const int m = new_line + j;
-                const int thr = (int) tb.thr_balk[m < kBalkTab ? m : kBalkTab - 1];
-                true_in += (rs.level() <= thr && j <= S) ? 1 : 0;
-            }
-            fl = fast ? n_in : true_in;
-            as = (new_line + fl) < empties ? (new_line + fl) : empties;
-            new_line = new_line + fl - as;
-            new_line = new_line < kMaxLine ? new_line : kMaxLine;
-            as = as > 0 ? as : 0;
+            const Received rc = receive_car_streams<RESET>(rs, hp, sa, tb, k, env, fast, line, empties);
+            fl = rc.flow;
+            new_line = rc.line;
+            as = rc.assign > 0 ? rc.assign : 0;
         }
         walk_rounds<0>(ctx, sa, rs, sg, lane, env0, as, k, fast);
         if (live) {
@@ -3873,7 +3746,7 @@ __global__ __launch_bounds__(kCompatSmallBlock) void k_compat_small(const DevCtx
             const uint64_t unit_mask = (U == 64) ? ~0ull : (uiw < upw ? (((1ull << U) - 1ull) << (uiw * U)) : 0ull);
             uint32_t w = 0u;
             if (valid) w = ctx->sl.hot[4 * ((size_t) hp.base[k] + (size_t) env * (size_t) S + (size_t) slot) + 3];
-            const uint64_t be = __ballot(valid && (int) (w & 127u) <= 1) & unit_mask;
+            const uint64_t be = __ballot(valid && hot_tl(w) <= 1) & unit_mask;
             if (unit_ok && slot == 0) ctx->st.empt[(uint32_t) k * (uint32_t) hp.n_envs + (uint32_t) env] = (uint8_t) __popcll(be);
         }
         mid();
@@ -4535,7 +4408,7 @@ __global__ void k_replay_soc(const DevCtx *__restrict__ ctx, float *out) {
         }
     } else {
         const uint32_t w = ctx->sl.hot[4 * idx + 3];
-        car = (w & 127u) != 0u;
+        car = hot_tl(w) != 0;
         if (car) {
             soc = __uint_as_float(ctx->sl.hot[4 * idx + 1]);  // the record's second word: the arrival SoC
             n = (int) (w >> 25);

@@ -607,7 +607,7 @@ static int create_impl(const chub_config *cfg_in, const char *data_dir, int64_t 
         hp.U[k] = hp.S[k] > 0 ? (hp.S[k] < 64 ? hp.S[k] : 64) : 1;  // COMPAT wave-local kernels: units of exactly S lanes
         active += hp.S[k] > 0;
         // transformer_limit = constant_power * charge_number in f32 (CHS.hpp:1133-1134, 1443-1444)
-        float constant_power = hp.type[k] == CHUB_FAST ? (float) 36.44764034125146 : (float) 5.254973139368931;
+        float constant_power = hp.type[k] == CHUB_FAST ? kFastConstantPower : kSlowConstantPower;
         hp.transformer_limit[k] = constant_power * (float) hp.S[k];
     }
     hp.base[0] = 0;
