@@ -2425,7 +2425,7 @@ __device__ __forceinline__ void slot_body_curves(const HubParams &hp, const Step
         t_soc = soc_to_time<TYPE>(soc, cp);
         power = time_to_power<TYPE>(t_soc, cp);
         int stay = (int) ceilf(__fsub_rn(tgt, t_soc)) + late;  // calculate_min_charging_time + mk_late_time
-        stay = stay > kMaxStay ? kMaxStay : stay;
+        stay = stay > kMaxStay ? kMaxStay : stay;  // (never binds on the mode's own draws: chub_create refuses curves whose stays could pass kMaxStay, chub.h; a car tape may carry any extra stay)
         tl = stay;
         car = tl > 0;
         w0 = car ? ps_make(stay, 0u, lev) : 0u;

@@ -60,7 +60,10 @@ enum { CHUB_FAST = 0, CHUB_SLOW = 1 };
  *   control (chub_step_load*), chub_tape_register_soc (the car tape's .x carries the f32 bits of each
  *   recorded arrival SoC instead of a class id), chub_set_slots.  The chub_options that pick the packed /
  *   one-launch / span kernels are accepted and have no effect: chub_uses_packed_kernel returns 0 and
- *   chub_run_steps issues its steps one by one.  Snapshots of one mode are refused by a handle of another. */
+ *   chub_run_steps issues its steps one by one.  Snapshots of one mode are refused by a handle of another.
+ *   Stays: a stay is ceil(needed slots) + the extra stay, as in PHILOX, and is kept in five bits; chub_create refuses curves on which
+ *   one could exceed 31, so no stay of this mode is ever clamped (the oracle's back-end of this mode does not clamp either: it raises
+ *   orc_station.stay_overflow, which the tests assert stays 0). */
 enum { CHUB_RNG_COMPAT = 0, CHUB_RNG_PHILOX = 1, CHUB_RNG_PHILOX_CURVES = 2 };
 
 /* Constructor kwargs of EvcsspManagerEnv_v6 (MGR:25-27), same names and meaning.  use_lagrange is

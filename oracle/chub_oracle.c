@@ -204,6 +204,12 @@ void orc_rng_seed_philox(orc_rng *r, uint64_t seed, uint32_t env_id) {
     r->tick = 0;
 }
 
+/* PHILOX_CURVES (include/chub.h): the same generator, keys and counters; only add_car reads its word 0 differently */
+void orc_rng_seed_philox_curves(orc_rng *r, uint64_t seed, uint32_t env_id) {
+    orc_rng_seed_philox(r, seed, env_id);
+    r->mode = ORC_RNG_PHILOX_CURVES;
+}
+
 static void philox_block(const orc_rng *r, int tag, int index, uint32_t block, uint32_t out[4]) {
     uint32_t ctr[4] = {block, ((uint32_t) tag << 16) | (uint32_t) index, r->tick, r->env_id};
     orc_philox4x32_10(ctr, r->key, out);
@@ -636,34 +642,51 @@ static void remove_car(orc_station *s, int i) {
     if (time_left <= 0) reset_position(s, i);
 }
 
-/* CHS:864-877 / 1029-1042 add_car (+ calculate_min_charging_time CHS:933-937 / 1098-1102) */
-static void add_car(orc_station *s, orc_rng *r, const orc_tables *t, int i) {
+/* CHS:864-877 / 1029-1042 add_car (+ calculate_min_charging_time CHS:933-937 / 1098-1102), the part behind the draws */
+static void place_car(orc_station *s, int i, float arrive_soc, float target_soc, int late, int curves_mode) {
     int cc = s->constant_charging;
-    int slot = s->slot_base + i;
-    int late;
-    if (r->mode == ORC_RNG_COMPAT) {
-        s->p_arrive_soc[i] = orc_mk_soc(r);
-        s->p_current_soc[i] = s->p_arrive_soc[i];
-        s->p_target_soc[i] = orc_uniform_level((int) (orc_glibc_rand(r) % 1000u), 80, 100);
-    } else {
-        /* PHILOX: one block per admitted slot -- word 0 arrival SoC, word 1 target level, word 2 extra stay */
-        uint32_t o[4];
-        philox_block(r, ORC_PU_SOC, slot, 0, o);
-        s->p_arrive_soc[i] = orc_soc_level_from_word(t, o[0]);
-        s->p_current_soc[i] = s->p_arrive_soc[i];
-        s->p_target_soc[i] = orc_uniform_level((int) (o[1] % 1000u), 80, 100);
-        late = orc_late_from_word(t, o[2]);
-    }
+    s->p_arrive_soc[i] = arrive_soc;
+    s->p_current_soc[i] = s->p_arrive_soc[i];
+    s->p_target_soc[i] = target_soc;
     float needed_time = soc_to_time(s->type, s->p_target_soc[i], cc) - soc_to_time(s->type, s->p_current_soc[i], cc);
     int must_needed = (int) ceilf(needed_time);
-    if (r->mode == ORC_RNG_COMPAT) late = orc_mk_late_time(r);
     s->stay_time[i] = must_needed + late;
+    /* PHILOX_CURVES: an implementation may keep a stay in five bits; chub.h promises that no stay of this mode passes
+     * ORC_MAX_STAY_CURVES, so nothing is clamped here -- a longer one is flagged and the tests assert the flag stays 0 */
+    if (curves_mode && s->stay_time[i] > ORC_MAX_STAY_CURVES) s->stay_overflow = 1;
     s->already[i] = 0;
     s->car[i] = 1; /* occupy_position CHS:314-317 */
     s->assign[i] = 0;
     s->power[i] = time_to_power(s->type, soc_to_time(s->type, s->p_current_soc[i], cc), cc);
     s->init_soc[i] = s->p_arrive_soc[i];
     s->target_soc[i] = s->p_target_soc[i];
+}
+
+/* ... and the draws, in the reference's order: arrival SoC, target level, then (after the needed time is known) the extra stay */
+static void add_car(orc_station *s, orc_rng *r, const orc_tables *t, int i) {
+    int slot = s->slot_base + i;
+    float soc, target;
+    int late;
+    if (r->mode == ORC_RNG_COMPAT) {
+        soc = orc_mk_soc(r);
+        target = orc_uniform_level((int) (orc_glibc_rand(r) % 1000u), 80, 100);
+        late = orc_mk_late_time(r); /* (drawn after the needed time is computed, CHS:869: the computation draws nothing) */
+    } else {
+        /* PHILOX: one block per admitted slot -- word 0 arrival SoC, word 1 target level, word 2 extra stay.
+         * PHILOX takes word 0's class (its top 11 bits), PHILOX_CURVES the continuous variate of the whole word */
+        uint32_t o[4];
+        philox_block(r, ORC_PU_SOC, slot, 0, o);
+        if (r->mode == ORC_RNG_PHILOX_CURVES) soc = orc_soc_from_word(t, o[0]);
+        else soc = orc_soc_level_from_word(t, o[0]);
+        target = orc_uniform_level((int) (o[1] % 1000u), 80, 100);
+        late = orc_late_from_word(t, o[2]);
+    }
+    place_car(s, i, soc, target, late, r->mode == ORC_RNG_PHILOX_CURVES);
+}
+
+/* tests: a given car into pile i, as add_car would place it (what a car tape does on the device) */
+void orc_station_put_car(orc_station *s, int i, float arrive_soc, float target_soc, int late) {
+    place_car(s, i, arrive_soc, target_soc, late, 1);
 }
 
 /* CHS:442-451 find_empty */
@@ -1295,7 +1318,8 @@ orc_vec *orc_vec_create(const orc_config *cfg, const orc_tables *t, long n_envs,
             /* per-env seeds of the two reference streams: srand(seed + 2*id + 1), e.seed(seed + 2*id + 2) */
             orc_rng_seed_compat(&v->envs[i].rng, (uint32_t) seed + 2u * id + 1u, (uint32_t) seed + 2u * id + 2u);
         } else {
-            orc_rng_seed_philox(&v->envs[i].rng, seed, id);
+            if (rng_mode == ORC_RNG_PHILOX_CURVES) orc_rng_seed_philox_curves(&v->envs[i].rng, seed, id);
+            else orc_rng_seed_philox(&v->envs[i].rng, seed, id);
             v->envs[i].st[0].exact_sums = 1;
             v->envs[i].st[1].exact_sums = 1;
         }
@@ -1434,11 +1458,30 @@ void orc_station_slots(const orc_station *s, float *out) {
     }
 }
 
+/* whole-batch forms of the two accessors above (tests that compare tens of thousands of envs at once) */
+void orc_vec_slots(orc_vec *v, int k, float *out) {
+    for (long i = 0; i < v->n; i++) orc_station_slots(&v->envs[i].st[k], out + (long) 9 * v->envs[i].st[k].n * i);
+}
+void orc_vec_station_scalars(orc_vec *v, double *out) {
+    for (long i = 0; i < v->n; i++)
+        for (int k = 0; k < 2; k++) orc_station_scalars(&v->envs[i].st[k], out + 16 * i + 8 * k);
+}
+void orc_vec_telemetry(orc_vec *v, double *out) {
+    for (long i = 0; i < v->n; i++) orc_env_telemetry(&v->envs[i], out + 38 * i);
+}
+int orc_vec_overflow(orc_vec *v) {
+    int any = 0;
+    for (long i = 0; i < v->n; i++) any |= v->envs[i].q_overflow | orc_env_stay_overflow(&v->envs[i]);
+    return any;
+}
+
 orc_env *orc_env_alloc(void) { return (orc_env *) calloc(1, sizeof(orc_env)); }
 void orc_env_free(orc_env *e) { free(e); }
 orc_station *orc_env_station(orc_env *e, int k) { return &e->st[k]; }
 orc_rng *orc_env_rng(orc_env *e) { return &e->rng; }
 int orc_env_q_overflow(const orc_env *e) { return e->q_overflow; }
+int orc_station_stay_overflow(const orc_station *s) { return s->stay_overflow; }
+int orc_env_stay_overflow(const orc_env *e) { return e->st[0].stay_overflow | e->st[1].stay_overflow; }
 void orc_env_hy_table(const orc_env *e, double *out102) { memcpy(out102, e->hy_table, sizeof e->hy_table); }
 
 /* telemetry named after the reference attributes (MGR:183-297, HYD) */

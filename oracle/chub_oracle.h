@@ -34,7 +34,12 @@ extern "C" {
 #define ORC_QCAP 1024 /* FCEV waiting list: the reference list is unbounded (HYD:264-265); this plain array is long enough for every test (saturating, flagged in q_overflow: tests assert the flag stays 0) */
 
 enum { ORC_FAST = 0, ORC_SLOW = 1 };
-enum { ORC_RNG_COMPAT = 0, ORC_RNG_PHILOX = 1 };
+/* ORC_RNG_PHILOX_CURVES (include/chub.h, the PHILOX_CURVES paragraph): every draw keyed and decoded as in ORC_RNG_PHILOX -- arrival
+ * counts, renege / balk, evs_reset's occupancy, target level, extra stay, forecourt, OU, days -- and the order-independent integer sums;
+ * the one difference is add_car's arrival SoC, the continuous orc_soc_from_word(word 0) where ORC_RNG_PHILOX takes the class
+ * orc_soc_level_from_word(word 0).  car_step runs along the curves in both. */
+enum { ORC_RNG_COMPAT = 0, ORC_RNG_PHILOX = 1, ORC_RNG_PHILOX_CURVES = 2 };
+#define ORC_MAX_STAY_CURVES 31 /* PHILOX_CURVES: chub.h promises no stay is longer (five bits on the device); not clamped here, flagged in orc_station.stay_overflow: tests assert the flag stays 0 */
 
 /* draw-site tags (Philox counter word 1 = tag << 16 | index); compat mode ignores them */
 enum {
@@ -71,6 +76,7 @@ typedef struct {
     float constant_power, transformer_limit;
     int slot_base; /* hub-global index of slot 0 (Philox tags) */
     int index;     /* 0/1 within the hub */
+    int stay_overflow; /* PHILOX_CURVES: 1 once add_car gave a stay above ORC_MAX_STAY_CURVES */
     int exact_sums; /* 0: reference's sequential f32 sums (CHS:1244-1255); 1: order-independent integer sums in 2^-19 kW (PHILOX mode) */
 } orc_station;
 
@@ -144,6 +150,7 @@ float orc_uniform_level(int k, float a, float b);                      /* CHS:35
 /* ---- RNG ---- */
 void orc_rng_seed_compat(orc_rng *r, uint32_t glibc_seed, uint32_t minstd_seed);
 void orc_rng_seed_philox(orc_rng *r, uint64_t seed, uint32_t env_id);
+void orc_rng_seed_philox_curves(orc_rng *r, uint64_t seed, uint32_t env_id);
 uint32_t orc_glibc_rand(orc_rng *r);
 uint32_t orc_minstd_next(orc_rng *r);
 void orc_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
@@ -168,6 +175,7 @@ void orc_station_init(orc_station *s, int type, int piles, int wait, int constan
 void orc_station_reset(orc_station *s, orc_rng *r, const orc_tables *t);
 void orc_station_step(orc_station *s, orc_rng *r, const orc_tables *t, const float *actions);
 void orc_station_step_load(orc_station *s, orc_rng *r, const orc_tables *t, float load);
+void orc_station_put_car(orc_station *s, int i, float arrive_soc, float target_soc, int late); /* tests: add_car with the draws given */
 
 /* ---- H2 pieces (HYD) ---- */
 double orc_j2601_target_pressure(double p0);                           /* HYD:338-388 */
@@ -195,6 +203,10 @@ void orc_vec_step(orc_vec *v, const float *actions, const double *exo_z, double 
                   unsigned char *done, int n_threads);
 void orc_vec_step_load(orc_vec *v, const float *actions, const double *exo_z, double *obs, double *reward,
                        unsigned char *done, int n_threads);
+void orc_vec_slots(orc_vec *v, int k, float *out /* [n][9][piles[k]] */);      /* orc_station_slots of station k of every env */
+void orc_vec_station_scalars(orc_vec *v, double *out /* [n][2][8] */);          /* orc_station_scalars of both stations of every env */
+void orc_vec_telemetry(orc_vec *v, double *out /* [n][38] */);                  /* orc_env_telemetry of every env */
+int orc_vec_overflow(orc_vec *v);                                               /* q_overflow | stay_overflow of any env */
 long orc_sizeof_env(void);
 long orc_check_canon_division(long n, unsigned long long seed); /* see chub_oracle.c */
 
@@ -216,6 +228,8 @@ orc_rng *orc_env_rng(orc_env *e);
 void orc_env_hy_table(const orc_env *e, double *out102);
 int orc_env_telemetry(const orc_env *e, double *out24);
 int orc_env_q_overflow(const orc_env *e); /* 1 once the FCEV waiting list outgrew ORC_QCAP */
+int orc_station_stay_overflow(const orc_station *s); /* PHILOX_CURVES: 1 once a stay passed ORC_MAX_STAY_CURVES */
+int orc_env_stay_overflow(const orc_env *e);
 void orc_env_set_hy_table(orc_env *e, const double *in102);
 void orc_env_init_compat_ctor(orc_env *e, const orc_config *cfg, const orc_tables *t, uint32_t glibc_seed,
                               uint32_t minstd_seed);

@@ -22,13 +22,13 @@ KW = dict(station_list=[20, 25], station_type_list=["fast", "slow"], hydro_prod_
 class Pair(object):
     """the library handle and the oracle's envs, driven with the same calls"""
 
-    def __init__(self, kw, n, slot_kernel="auto"):
+    def __init__(self, kw, n, slot_kernel="auto", rng="philox"):
         chub = hub()
-        self.n, self.kw, self.slot_kernel = n, kw, slot_kernel
+        self.n, self.kw, self.slot_kernel, self.rng = n, kw, slot_kernel, rng
         seed, env_id0 = 0xFEED5EED, 4000
-        self.v = chub.VecChargingHub(n, seed=seed, rng="philox", env_id0=env_id0, slot_kernel=slot_kernel, **kw)
+        self.v = chub.VecChargingHub(n, seed=seed, rng=rng, env_id0=env_id0, slot_kernel=slot_kernel, **kw)
         self.v.set_telemetry(True)
-        self.cfg, self.h = _oracle_vec(kw, n, env_id0, seed)
+        self.cfg, self.h = _oracle_vec(kw, n, env_id0, seed, rng=rng)
         self.D, self.A = self.v.obs_dim, self.v.act_dim
         self.o_obs = np.zeros((n, self.D))
         self.o_rew = np.zeros(n)
@@ -96,7 +96,7 @@ class Pair(object):
         same arguments, restore -- the oracle's envs run on uninterrupted"""
         chub = hub()
         snap = self.v.get_state()
-        args = dict(seed=0xFEED5EED, rng="philox", env_id0=4000, slot_kernel=self.slot_kernel)
+        args = dict(seed=0xFEED5EED, rng=self.rng, env_id0=4000, slot_kernel=self.slot_kernel)
         self.v.close()
         self.v = chub.VecChargingHub(self.n, **args, **self.kw)
         self.v.set_telemetry(True)  # same arena layout as the handle the snapshot came from
@@ -119,8 +119,12 @@ SHAPES = {
 @pytest.mark.parametrize("shape", sorted(SHAPES))
 def test_subset_resets_and_steps_match_the_oracle(shape):
     kw, slot_kernel = SHAPES[shape]
-    n = 44
-    p = Pair(kw, n, slot_kernel)
+    subset_resets_and_steps(Pair(kw, 44, slot_kernel))
+
+
+def subset_resets_and_steps(p):
+    """the body of the test above, for any Pair (tests/test_gpu_soc_curves_oracle.py runs it on PHILOX_CURVES handles)"""
+    n = p.n
     idx = np.arange(n)
     p.reset(label="all")
     for i in range(6):
@@ -150,6 +154,7 @@ def test_subset_resets_and_steps_match_the_oracle(shape):
     assert p.v.clock_groups == 1
     for i in range(4):
         p.step(label=("lock-step again", i))  # the first of these makes its own draws, the others find them left by the launch before
+    assert orc.orc_vec_overflow(p.h) == 0
     p.close()
 
 
@@ -222,8 +227,12 @@ def test_restore_into_a_fresh_handle_continues_the_oracle_run(shape):
     state is taken out of the handle, the handle is destroyed, a fresh handle is created and restored, and the run goes on
     against the oracle's uninterrupted envs: slot state and station records bit for bit, f64 observation / reward to 1e-9."""
     kw, slot_kernel = SHAPES[shape]
-    n = 36
-    p = Pair(kw, n, slot_kernel)
+    restore_into_a_fresh_handle(Pair(kw, 36, slot_kernel))
+
+
+def restore_into_a_fresh_handle(p):
+    """the body of the test above, for any Pair"""
+    n = p.n
     idx = np.arange(n)
     p.reset(label="all")
     for i in range(10):
@@ -254,6 +263,7 @@ def test_restore_into_a_fresh_handle_continues_the_oracle_run(shape):
     assert p.v.clock_groups == 1
     for i in range(4):
         p.step(label=("lock-step again", i))
+    assert orc.orc_vec_overflow(p.h) == 0
     p.close()
 
 
@@ -601,8 +611,12 @@ def test_masked_scalar_load_steps_match_the_oracle(shape):
 def test_random_sequences_of_masked_calls_match_the_oracle(seed):
     """300 calls drawn at random -- resets and steps of random subsets (sparse, dense, single envs, everybody, nobody) --
     against the oracle's separate env objects"""
-    n = 48
-    p = Pair(KW, n)
+    random_sequences_of_masked_calls(Pair(KW, 48), seed)
+
+
+def random_sequences_of_masked_calls(p, seed):
+    """the body of the test above, for any Pair"""
+    n = p.n
     rs = np.random.RandomState(seed)
     p.reset(label="all")
     for i in range(300):
@@ -621,4 +635,5 @@ def test_random_sequences_of_masked_calls_match_the_oracle(seed):
         else:
             p.step(mask if kind != 0 else None, ("fuzz step", i))
     assert np.array_equal(p.v.env_clocks(), p.t)
+    assert orc.orc_vec_overflow(p.h) == 0
     p.close()

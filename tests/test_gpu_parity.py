@@ -126,10 +126,13 @@ def test_compat_matches_reference_golden(name, n_envs, migrate):
     v.close()
 
 
-def _oracle_vec(cfg_kw, n, env_id0, seed, tables=None):
+ORACLE_RNG = {"philox": orclib.PHILOX, "philox_curves": orclib.PHILOX_CURVES}  # the oracle back-end that specifies each library mode
+
+
+def _oracle_vec(cfg_kw, n, env_id0, seed, tables=None, rng="philox"):
     cfg = orclib.make_config(piles=cfg_kw["station_list"], types=cfg_kw["station_type_list"],
                              **{k: cfg_kw[k] for k in cfg_kw if k not in ("station_list", "station_type_list")})
-    h = orc.orc_vec_create(C.byref(cfg), tables or orclib.tables(), n, env_id0, orclib.PHILOX, seed)
+    h = orc.orc_vec_create(C.byref(cfg), tables or orclib.tables(), n, env_id0, ORACLE_RNG[rng], seed)
     return cfg, h
 
 
@@ -354,6 +357,10 @@ def test_packed_kernel_shape_sweep(piles, types):
 
 def test_philox_user_series(tmp_path):
     """user-supplied arrival CDFs / price / PV / wind through a data directory: same parity bar"""
+    _user_series_parity(tmp_path)
+
+
+def _user_series_parity(tmp_path, rng="philox"):
     from charginghub_env_amd import data_io
     rs = np.random.RandomState(11)
     rates = 45 + 35 * np.sin(np.arange(96) * 2 * np.pi / 96 + 1.0)
@@ -365,20 +372,20 @@ def test_philox_user_series(tmp_path):
     assert tables
     kw = dict(station_list=[12, 20], station_type_list=["fast", "slow"], hydro_prod_rate=100.0, hydro_store_vlt=25.0,
               init_soc=0.2, fc_max_power=100.0, fcev_permeate=0.02, renew_fluctuate=0.2, price_fluctuate=0.1)
-    _philox_parity("user_series", kw, 96, data_dir=d, tables=tables, plan=[96, 20])
+    _philox_parity("user_series", kw, 96, data_dir=d, tables=tables, plan=[96, 20], rng=rng)
 
 
-def _philox_parity(label, kw, n, data_dir=None, tables=None, plan=(96, 96, 10, 30), slot_kernel="auto", fused_step="auto"):
+def _philox_parity(label, kw, n, data_dir=None, tables=None, plan=(96, 96, 10, 30), slot_kernel="auto", fused_step="auto", rng="philox"):
     chub = hub()
     kw = dict(kw)
     for k, d in (("constant_charging", False), ("renew_fluctuate", 0.0), ("price_fluctuate", 0.0), ("hydro_loss", 0.0)):
         kw.setdefault(k, d)
     seed, env_id0 = 0xC0FFEE12345, 1000
-    v = chub.VecChargingHub(n, seed=seed, rng="philox", env_id0=env_id0, data_dir=data_dir, slot_kernel=slot_kernel, fused_step=fused_step, **kw)
+    v = chub.VecChargingHub(n, seed=seed, rng=rng, env_id0=env_id0, data_dir=data_dir, slot_kernel=slot_kernel, fused_step=fused_step, **kw)
     if fused_step != "auto":
         assert v.uses_fused_step == (fused_step == "on")
     v.set_telemetry(True)
-    cfg, h = _oracle_vec(kw, n, env_id0, seed, tables)
+    cfg, h = _oracle_vec(kw, n, env_id0, seed, tables, rng)
     D, A = v.obs_dim, v.act_dim
     S0, S1 = kw["station_list"]
     rs = np.random.RandomState(7)
@@ -420,6 +427,7 @@ def _philox_parity(label, kw, n, data_dir=None, tables=None, plan=(96, 96, 10, 3
                 close(tel[e, 24:28], wt[24:28], (label, "telemetry (after the fuel cell)", ep, t, e), rtol=TIGHT, atol=1e-7)
                 assert np.array_equal(tel[e, 28:38], wt[28:38]), (label, "telemetry (station scalars)", ep, t, e, tel[e, 28:38], wt[28:38])
                 assert orc.orc_env_q_overflow(env) == 0
+                assert rng == "philox" or orc.orc_env_stay_overflow(env) == 0  # (PHILOX_CURVES: no stay beyond the device's five bits)
             assert np.array_equal(done, o_done.astype(bool))
             close(v.obs_f64(), o_obs, (label, "obs", ep, t), rtol=TIGHT, atol=TIGHT)
             close(obs, o_obs, (label, "obs f32", ep, t), atol=1e-6)

@@ -3,7 +3,12 @@ evaluated on the device along the reference's curves (CHS.hpp:467-726) -- k_slot
 
 What is pinned here: the reference's fixtures through the new slot kernel in tape mode; the draw contract of chub.h against the oracle's
 Philox; every car's (power, SoC) against the host's f32 curve chain; the law of the arrival SoC; the whole process against COMPAT (the
-reference's own streams) with k-SE bounds; the launch forms bit for bit; and what the mode refuses."""
+reference's own streams) with k-SE bounds; the launch forms bit for bit; and what the mode refuses.
+
+What is NOT pinned here -- every check above is either piecewise (new cars only; the curve chain given the device's OWN charging flag;
+two envs in tape mode) or the kernel against itself: the free-running mode step for step against an independent implementation (the
+on / off decision, countdown and departures, admission ranks in every unit of a workgroup, station sums and records, the tail, masked
+calls, restores) lives in tests/test_gpu_soc_curves_oracle.py, against the oracle's ORC_RNG_PHILOX_CURVES back-end."""
 import ctypes as C
 import math
 
