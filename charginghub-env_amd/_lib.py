@@ -121,6 +121,7 @@ def load_library():
         "chub_telemetry_host": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P)]),
         "chub_set_rng_compat_seeds": (I, [P, P]), "chub_set_rng_compat_state": (I, [P, P]),
         "chub_get_rng_compat_state": (I, [P, P]), "chub_compat_replay_constructor": (I, [P]), "chub_set_ou_state": (I, [P, P]),
+        "chub_copy_envs": (I, [P, P, P, P, L]), "chub_copy_envs_device": (I, [P, P, P, P, L, P]),
         "chub_state_size": (L, [P]), "chub_get_state": (I, [P, P, L]), "chub_set_state": (I, [P, P, L]),
         "chub_get_hy_table": (I, [P, P]), "chub_get_hy_table_env": (I, [P, L, P]), "chub_set_hy_table": (I, [P, P]),
         "chub_last_error": (C.c_char_p, []), "chub_device_count": (I, []), "chub_build_id": (C.c_char_p, []),
@@ -162,7 +163,7 @@ EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "ch
             "chub_env_clocks", "chub_clock_groups", "chub_random_actions_device", "chub_sync", "chub_profile_begin", "chub_profile_end",
             "chub_get_slots", "chub_get_station_scalars", "chub_get_telemetry", "chub_get_obs_f64",
             "chub_get_reward_f64", "chub_set_telemetry", "chub_fcev_stuck_count", "chub_set_rng_compat_seeds", "chub_set_rng_compat_state", "chub_get_rng_compat_state", "chub_compat_replay_constructor", "chub_set_ou_state",
-            "chub_state_size", "chub_get_state", "chub_set_state", "chub_get_hy_table", "chub_get_hy_table_env", "chub_set_hy_table", "chub_last_error", "chub_device_count", "chub_build_id",
+            "chub_copy_envs", "chub_copy_envs_device", "chub_state_size", "chub_get_state", "chub_set_state", "chub_get_hy_table", "chub_get_hy_table_env", "chub_set_hy_table", "chub_last_error", "chub_device_count", "chub_build_id",
             "chub_comm_unique_id", "chub_comm_create", "chub_comm_destroy", "chub_comm_world", "chub_comm_rank", "chub_comm_gather", "chub_comm_gather_timed",
             "chub_comm_max_f64", "chub_comm_barrier", "chub_comm_ranks_seen", "chub_comm_set_overlap", "chub_comm_gather_begin", "chub_comm_join", "chub_device_info", "chub_step_gather", "chub_run_steps", "chub_tape_register_soc", "chub_set_slots",
             "chub_set_station_queue", "chub_step_tape", "chub_reset_tape", "chub_tape_clear_soc", "chub_step_tape_env", "chub_reset_tape_env", "chub_telemetry_host", "chub_graph_begin", "chub_graph_end", "chub_graph_launch", "chub_graph_destroy",

@@ -245,6 +245,26 @@ struct DevCtx {
     EnvParamArrays ep;  // (last: the offsets of everything above stay those of a homogeneous handle's kernels)
 };
 
+// chub_copy_envs: env dst_idx[i] of `dst` becomes a clone of env src_idx[i] of `src` (k_copy_envs; one wave per pair).  The two contexts may
+// be the same handle's.  The clock of an env is not in DevCtx: lock-step handles keep it on the host (src_clk null: src_clk_value holds for
+// every source env; dst_clk null: the host has checked that no clock changes and none is written), handles on per-env clocks in
+// StepArgs::env_clk -- the pointers below name the buffer the handle's NEXT launch reads.
+struct CopyArgs {
+    const DevCtx *src;
+    const DevCtx *dst;
+    CHUB_G(const int64_t) src_idx;   // [count] device memory; a pair with an index out of range is skipped
+    CHUB_G(const int64_t) dst_idx;
+    int64_t count;
+    CHUB_G(const uint16_t) src_clk;
+    CHUB_G(uint16_t) dst_clk;
+    uint32_t src_clk_value;
+    int32_t src_rng, dst_rng;        // COMPAT: the buffer of CompatRng that holds each handle's committed streams
+    CHUB_G(const double) src_rows;   // per-env hub parameters: the raw rows [N][8] f64 (chub_env_params), or null
+    CHUB_G(double) dst_rows;
+};
+
+enum { COPY_PHILOX = 0, COPY_CURVES = 1, COPY_COMPAT = 2 };  // k_copy_envs: the slot layouts (SlotArrays)
+
 // host-side copies of the device pointers the packed slot kernel takes as kernel arguments (launch_slot)
 struct PackedPtrs {
     const EnvArrays *ev;      // host copies of the array tables (launch_env / k_step build TailArgs from them)

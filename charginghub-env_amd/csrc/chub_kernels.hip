@@ -4830,6 +4830,113 @@ void launch_tick_advance(uint32_t *tick_base, uint32_t by, hipStream_t stream) {
     hipLaunchKernelGGL(k_tick_advance, dim3(1), dim3(1), 0, stream, tick_base, by);
 }
 
+// ---- chub_copy_envs: env d of one handle becomes a clone of env s of another (or the same) handle, by index, on the device
+// One wave per (s, d) pair, four pairs per workgroup.  What moves is the env's simulation state and nothing else: its slot rows, both
+// station records, the tank, OU and forecourt words, its days and clock, the committed COMPAT streams, its electrolyser table and (handles
+// with per-env hub parameters) its row.  What a launch made AHEAD of the next step from the old state -- pk, and the COMPAT walk's shadow
+// streams, var, fa, empt*, shrt, hv_pre -- is not touched: the host marks it void (chub_runtime.cpp: copy_launch) and the next launch
+// makes its own, as after a masked call.  drw / drw_cnt (state-independent, keyed by the destination's own counters) stay as they are.
+//
+// The bulk is the slot rows (4 .. 16 bytes per slot): a row is contiguous per env (hub-major layouts) or per env and station (COMPAT),
+// so the wave's lanes take consecutive 16-byte pieces of it where both ends are 16-byte aligned (COMPAT's records always are, hub-major
+// rows whenever 4 S is a multiple of 16), consecutive words otherwise: one fully coalesced request per 1 KiB / 256 bytes either way.
+// The ~30 scalars go one per lane.
+__device__ __forceinline__ void copy_span(CHUB_G(uint8_t) d, CHUB_G(const uint8_t) s, uint32_t n, uint32_t lane) {
+    const uint32_t al = (uint32_t) (uintptr_t) d | (uint32_t) (uintptr_t) s;
+    uint32_t done = 0u;
+    if ((al & 15u) == 0u) {
+        const uint32_t nv = n >> 4;
+        for (uint32_t i = lane; i < nv; i += 64u) ((CHUB_G(u32x4)) d)[i] = ((CHUB_G(const u32x4)) s)[i];
+        done = nv << 4;
+    }
+    if ((al & 3u) == 0u) {
+        const uint32_t nw = (n - done) >> 2;
+        for (uint32_t i = lane; i < nw; i += 64u) ((CHUB_G(uint32_t)) (d + done))[i] = ((CHUB_G(const uint32_t)) (s + done))[i];
+        done += nw << 2;
+    }
+    for (uint32_t i = done + lane; i < n; i += 64u) d[i] = s[i];
+}
+template <typename T>
+__device__ __forceinline__ void copy_rows(CHUB_G(T) d, int64_t d_off, CHUB_G(const T) s, int64_t s_off, uint32_t count, uint32_t lane) {
+    copy_span((CHUB_G(uint8_t)) (d + d_off), (CHUB_G(const uint8_t)) (s + s_off), count * (uint32_t) sizeof(T), lane);
+}
+
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void k_copy_envs(CopyArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const int64_t pair = (int64_t) blockIdx.x * 4 + (int64_t) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+    if (pair >= a.count) return;
+    const int64_t s = a.src_idx[pair], d = a.dst_idx[pair];
+    const HubParams &hs = a.src->hp;
+    const HubParams &hd = a.dst->hp;
+    const int64_t Ns = hs.n_envs, Nd = hd.n_envs;
+    if (s < 0 || s >= Ns || d < 0 || d >= Nd) return;
+    const EnvArrays &es = a.src->ev;
+    const EnvArrays &ed = a.dst->ev;
+    // (the device form cannot refuse: a waiting list longer than the destination handle's rows can hold leaves the pair alone)
+    const uint32_t qcap = (uint32_t) (hs.qcap < hd.qcap ? hs.qcap : hd.qcap);
+    if ((uint32_t) es.q_len[s] > qcap) return;
+    const uint32_t S0 = (uint32_t) hd.S[0], S1 = (uint32_t) hd.S[1], S = S0 + S1;  // (the same in both handles)
+
+    // ---- slot rows
+    if (LAYOUT == COPY_COMPAT) {
+        copy_rows<uint32_t>(a.dst->sl.hot, 4 * (hd.base[0] + d * (int64_t) S0), a.src->sl.hot, 4 * (hs.base[0] + s * (int64_t) S0), 4u * S0, lane);
+        copy_rows<uint32_t>(a.dst->sl.hot, 4 * (hd.base[1] + d * (int64_t) S1), a.src->sl.hot, 4 * (hs.base[1] + s * (int64_t) S1), 4u * S1, lane);
+    } else if (LAYOUT == COPY_CURVES) {
+        copy_rows<uint32_t>(a.dst->sl.hot, 2 * d * (int64_t) S, a.src->sl.hot, 2 * s * (int64_t) S, 2u * S, lane);
+        copy_rows<uint32_t>(a.dst->sl.wrd, d * (int64_t) S, a.src->sl.wrd, s * (int64_t) S, S, lane);
+        copy_rows<float>(a.dst->sl.soc0, d * (int64_t) S, a.src->sl.soc0, s * (int64_t) S, S, lane);
+        copy_rows<uint8_t>(a.dst->sl.stay8, d * (int64_t) S, a.src->sl.stay8, s * (int64_t) S, S, lane);
+    } else {
+        copy_rows<uint32_t>(a.dst->sl.hot, d * (int64_t) S, a.src->sl.hot, s * (int64_t) S, S, lane);
+        copy_rows<uint8_t>(a.dst->sl.stay8, d * (int64_t) S, a.src->sl.stay8, s * (int64_t) S, S, lane);
+    }
+
+    // ---- the forecourt list, the electrolyser table, the committed streams
+    copy_rows<double>(ed.q_time, d * (int64_t) hd.qcap, es.q_time, s * (int64_t) hs.qcap, qcap, lane);
+    copy_rows<double>(ed.q_mass, d * (int64_t) hd.qcap, es.q_mass, s * (int64_t) hs.qcap, qcap, lane);
+    if (es.hy_env && ed.hy_env) copy_rows<double>(ed.hy_env, d * 102, es.hy_env, s * 102, 102u, lane);
+    if (LAYOUT == COPY_COMPAT) copy_rows<uint32_t>(a.dst->cr.g3[a.dst_rng], d * 32, a.src->cr.g3[a.src_rng], s * 32, 32u, lane);
+
+    // ---- the scalars, one per lane
+    const bool rows = a.src->ep.prm && a.dst->ep.prm && a.src_rows && a.dst_rows;
+    switch (lane) {
+    case 0: ed.cap[d] = es.cap[s]; break;
+    case 1: ed.store_soc[d] = es.store_soc[s]; break;
+    case 2: case 3: case 4: ed.ou[(int64_t) (lane - 2u) * Nd + d] = es.ou[(int64_t) (lane - 2u) * Ns + s]; break;
+    case 5: ed.price_noise[d] = es.price_noise[s]; break;
+    case 6: ed.pv_day[d] = es.pv_day[s]; break;
+    case 7: ed.wd_day[d] = es.wd_day[s]; break;
+    case 8: ed.q_len[d] = es.q_len[s]; break;
+    case 9: ed.hv_line[d] = es.hv_line[s]; break;
+    case 10: case 11: ed.q_fold[2 * d + (int64_t) (lane - 10u)] = es.q_fold[2 * s + (int64_t) (lane - 10u)]; break;
+    case 12: ed.q_fold_cnt[d] = es.q_fold_cnt[s]; break;
+    case 13: if (a.dst_clk) a.dst_clk[d] = a.src_clk ? a.src_clk[s] : (uint16_t) a.src_clk_value; break;
+    case 14: case 15: {  // the station records, 16 bytes each (unit u = k N + env)
+        const int64_t k = (int64_t) (lane - 14u);
+        ((CHUB_G(u32x4)) a.dst->st.rec)[k * Nd + d] = ((CHUB_G(const u32x4)) a.src->st.rec)[k * Ns + s];
+        break;
+    }
+    case 16: if (LAYOUT == COPY_COMPAT) a.dst->cr.minstd3[a.dst_rng][d] = a.src->cr.minstd3[a.src_rng][s]; break;
+    case 17: if (rows) ((CHUB_G(float)) a.dst->ep.hv_rate)[d] = a.src->ep.hv_rate[s]; break;
+    default:
+        if (rows && lane >= 32u && lane < 32u + (uint32_t) PRM_COUNT)
+            ((CHUB_G(double)) a.dst->ep.prm)[(int64_t) (lane - 32u) * Nd + d] = a.src->ep.prm[(int64_t) (lane - 32u) * Ns + s];
+        else if (rows && lane >= 48u && lane < 56u)
+            a.dst_rows[8 * d + (int64_t) (lane - 48u)] = a.src_rows[8 * s + (int64_t) (lane - 48u)];
+        break;
+    }
+}
+
+void launch_copy_envs(int layout, const CopyArgs &a, hipStream_t stream) {
+    const dim3 grid((unsigned) ((a.count + 3) / 4)), block(256);
+    switch (layout) {
+    case COPY_COMPAT: hipLaunchKernelGGL(k_copy_envs<COPY_COMPAT>, grid, block, 0, stream, a); break;
+    case COPY_CURVES: hipLaunchKernelGGL(k_copy_envs<COPY_CURVES>, grid, block, 0, stream, a); break;
+    default: hipLaunchKernelGGL(k_copy_envs<COPY_PHILOX>, grid, block, 0, stream, a); break;
+    }
+}
+
 // chub_create, COMPAT handles: every entry of Tables::ttab against the device's own soc_to_time(uniform_level(l, 80, 100)) -- the expression
 // add_car evaluates (make_car's callers) -- bit for bit; *mismatch counts the entries that differ
 __global__ void k_check_ttab(const DevCtx *__restrict__ ctx, uint32_t *mismatch) {

@@ -33,6 +33,7 @@ void launch_tick_advance(uint32_t *tick_base, uint32_t by, hipStream_t stream);
 void launch_fill_clocks(uint16_t *dst, int64_t n, uint16_t value, hipStream_t stream);
 void launch_keep_clocks(uint16_t *dst, const uint16_t *src, int64_t n, hipStream_t stream);
 void launch_expand_bits(const HubParams &hp, const uint64_t *d_bits, const float *d_tail, float *d_actions, hipStream_t stream);
+void launch_copy_envs(int layout, const CopyArgs &a, hipStream_t stream);
 void launch_step_fused(const CallPlan &cp, const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, const PackedPtrs &pp,
                        hipEvent_t ev0, hipEvent_t ev1);
 template <bool RESET>
@@ -1572,6 +1573,132 @@ int chub_clock_groups(chub_env *e) {  // number of distinct clocks among the env
     if (rc) return rc;
     std::sort(c.begin(), c.end());
     return (int) (std::unique(c.begin(), c.end()) - c.begin());
+}
+
+// ---- chub_copy_envs: env dst_idx[i] of `dst` becomes a clone of env src_idx[i] of `src`, on the device (k_copy_envs) ------------------------
+// The kernel moves the state; what the handle keeps on the host ABOUT that state is settled here, exactly as after a masked call or a
+// restored snapshot: the draws a launch made ahead for the next step (pk; the COMPAT walk's shadow, var, fa, hv_pre) and the counts a pass
+// left (empt, empt2, shrt) belong to the destination's old state, so the next launch makes and counts its own (StepArgs::fresh,
+// empt_fresh; a walk that ran ahead is void).  Nothing of them is reused and nothing is copied approximately.
+
+static const char *copy_refuse_handle(const chub_env *e) {
+    if (e->tape_only) return "chub_copy_envs is not supported on a tape handle (chub_tape_register_soc)";
+    if (e->capturing) return "chub_copy_envs between chub_graph_begin and chub_graph_end (a copy cannot be recorded: call it between replays)";
+    return nullptr;
+}
+
+static int copy_check_handles(const chub_env *dst, const chub_env *src) {
+    for (const chub_env *e : {dst, src})
+        if (const char *why = copy_refuse_handle(e)) return fail(CHUB_ERR_UNSUPPORTED, why);
+    if (src == dst) return CHUB_OK;
+    if (src->device != dst->device) return fail(CHUB_ERR_ARG, "chub_copy_envs: the two handles live on different devices");
+    if (src->public_mode != dst->public_mode) return fail(CHUB_ERR_ARG, "chub_copy_envs: the two handles have different RNG modes");
+    const chub_config &a = src->cfg, &b = dst->cfg;
+    if (a.station_list[0] != b.station_list[0] || a.station_list[1] != b.station_list[1] || a.station_type_list[0] != b.station_type_list[0] ||
+        a.station_type_list[1] != b.station_type_list[1] || (a.constant_charging != 0) != (b.constant_charging != 0))
+        return fail(CHUB_ERR_ARG, "chub_copy_envs: the two handles differ in station_list, station_type_list or constant_charging");
+    if (src->env_params != dst->env_params)
+        return fail(CHUB_ERR_ARG, "chub_copy_envs: one handle has per-env hub parameters (chub_create_params) and the other has none");
+    if (!src->env_params &&
+        (a.hydro_prod_rate != b.hydro_prod_rate || a.hydro_store_vlt != b.hydro_store_vlt || a.init_soc != b.init_soc || a.fc_max_power != b.fc_max_power ||
+         a.fcev_permeate != b.fcev_permeate || a.renew_fluctuate != b.renew_fluctuate || a.price_fluctuate != b.price_fluctuate || a.hydro_loss != b.hydro_loss))
+        return fail(CHUB_ERR_ARG, "chub_copy_envs: the two handles were created with different chub_config scalars (a clone must be the same hub)");
+    return CHUB_OK;
+}
+
+static uint16_t lock_step_clock(const chub_env *e) { return (uint16_t) ((uint32_t) e->t | (((uint32_t) e->price_count & 3u) << 8)); }
+
+// the launch and the handle's bookkeeping behind it.  keep_clocks: the caller has shown that no destination's clock changes (both handles
+// in lock-step on equal clocks): the destination stays in lock-step; otherwise it goes onto per-env clocks as a masked call does
+static int copy_launch(chub_env *dst, chub_env *src, const int64_t *d_src_idx, const int64_t *d_dst_idx, int64_t count, hipStream_t s, bool keep_clocks) {
+    HIP_TRY(hipSetDevice(dst->device));
+    (void) hipGetLastError();
+    if (const int rc = sync_ctx(src, s)) return rc;
+    if (const int rc = sync_ctx(dst, s)) return rc;
+    const size_t Nd = (size_t) dst->hp.n_envs, Ns = (size_t) src->hp.n_envs;
+    if (!keep_clocks && !dst->per_env) {  // (as serve_mask: every env starts from the lock-step clock, in the buffer the next launch reads)
+        launch_fill_clocks(dst->d_env_clk + (size_t) ((dst->tick + 1u - dst->graph_base) & 1u) * Nd, (int64_t) Nd, lock_step_clock(dst), s);
+        dst->per_env = true;
+        if (dst->h_tick.size() != Nd) dst->h_tick.assign(Nd, 0u);
+    }
+    CopyArgs a;
+    memset(&a, 0, sizeof a);
+    a.src = src->d_ctx;
+    a.dst = dst->d_ctx;
+    a.src_idx = d_src_idx;
+    a.dst_idx = d_dst_idx;
+    a.count = count;
+    a.src_clk = src->per_env ? src->d_env_clk + (size_t) ((src->tick + 1u - src->graph_base) & 1u) * Ns : nullptr;
+    a.dst_clk = keep_clocks ? nullptr : dst->d_env_clk + (size_t) ((dst->tick + 1u - dst->graph_base) & 1u) * Nd;
+    a.src_clk_value = lock_step_clock(src);
+    a.src_rng = src->rng_cur;
+    a.dst_rng = dst->rng_cur;
+    a.src_rows = (const double *) src->d_rows;
+    a.dst_rows = (double *) dst->d_rows;
+    launch_copy_envs(dst->hp.rng_mode == CHUB_RNG_COMPAT ? COPY_COMPAT : dst->hp.soc_curves ? COPY_CURVES : COPY_PHILOX, a, s);
+    HIP_TRY(hipGetLastError());
+    dst->predrawn = false;   // pk was decoded against the old queues (and a row may have come along): the next launch draws its own
+    dst->walked_tick = 0;    // COMPAT: a walk that ran ahead of its step walked the old state
+    dst->empt_valid = false; // ... and the counts the last pass left are the old slots'
+    dst->e2_tick = ~0u;
+    return CHUB_OK;
+}
+
+int chub_copy_envs_device(chub_env *dst, chub_env *src, const int64_t *d_src_idx, const int64_t *d_dst_idx, int64_t count, void *stream) {
+    if (!dst || !src || !d_src_idx || !d_dst_idx) return fail(CHUB_ERR_ARG, "null argument");
+    if (count < 0) return fail(CHUB_ERR_ARG, "count < 0");
+    if (const int rc = copy_check_handles(dst, src)) return rc;
+    if (count == 0) return CHUB_OK;
+    return copy_launch(dst, src, d_src_idx, d_dst_idx, count, (hipStream_t) stream, false);
+}
+
+int chub_copy_envs(chub_env *dst, chub_env *src, const int64_t *src_idx, const int64_t *dst_idx, int64_t count) {
+    if (!dst || !src || !src_idx || !dst_idx) return fail(CHUB_ERR_ARG, "null argument");
+    if (count < 0) return fail(CHUB_ERR_ARG, "count < 0");
+    if (const int rc = copy_check_handles(dst, src)) return rc;
+    if (count == 0) return CHUB_OK;
+    const int64_t Ns = src->hp.n_envs, Nd = dst->hp.n_envs;
+    std::vector<uint8_t> is_dst((size_t) Nd, 0);
+    for (int64_t i = 0; i < count; i++) {
+        const std::string at = "[" + std::to_string(i) + "] = ";
+        if (src_idx[i] < 0 || src_idx[i] >= Ns)
+            return fail(CHUB_ERR_ARG, "src_idx" + at + std::to_string(src_idx[i]) + " is out of range (the source handle has " + std::to_string(Ns) + " envs)");
+        if (dst_idx[i] < 0 || dst_idx[i] >= Nd)
+            return fail(CHUB_ERR_ARG, "dst_idx" + at + std::to_string(dst_idx[i]) + " is out of range (the destination handle has " + std::to_string(Nd) + " envs)");
+        if (is_dst[(size_t) dst_idx[i]])
+            return fail(CHUB_ERR_ARG, "dst_idx" + at + std::to_string(dst_idx[i]) + " names a destination a second time");
+        is_dst[(size_t) dst_idx[i]] = 1;
+    }
+    for (int64_t i = 0; src == dst && i < count; i++)
+        if (is_dst[(size_t) src_idx[i]])
+            return fail(CHUB_ERR_ARG, "src_idx[" + std::to_string(i) + "] = " + std::to_string(src_idx[i]) +
+                                          " is also a destination (within one handle no env may be both)");
+    HIP_TRY(hipSetDevice(dst->device));
+    HIP_TRY(hipDeviceSynchronize());  // (launches in flight on any stream read or write these arrays: as the other host-form mutators)
+    if (src != dst && src->env_params) {  // the rows come along: each must fit the waiting list `dst` was created with (as chub_set_env_params)
+        std::vector<chub_env_params> rows;
+        if (const int rc = fetch(rows, (const chub_env_params *) src->d_rows, (size_t) Ns)) return rc;
+        for (int64_t i = 0; i < count; i++) {
+            const int m = hv_bound(dst->hv_top, derive_env_consts(rows[(size_t) src_idx[i]]).hv_rate);
+            if (m > dst->hv_max_arrive)
+                return fail(CHUB_ERR_ARG, "src_idx[" + std::to_string(i) + "] = " + std::to_string(src_idx[i]) + ": its fcev_permeate gives up to " +
+                                              std::to_string(m) + " FCEV arrivals per step, more than the " + std::to_string(dst->hv_max_arrive) +
+                                              " the destination handle's waiting list was sized for at create");
+        }
+    }
+    // both handles in lock-step on equal clocks: no clock changes, the destination stays in lock-step
+    const bool keep_clocks = !dst->per_env && !src->per_env && lock_step_clock(src) == lock_step_clock(dst);
+    int64_t *d_idx = nullptr;
+    HIP_TRY(hipMalloc((void **) &d_idx, 2 * (size_t) count * sizeof(int64_t)));
+    int rc = CHUB_OK;
+    if (hipMemcpy(d_idx, src_idx, (size_t) count * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_idx + count, dst_idx, (size_t) count * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess)
+        rc = fail(CHUB_ERR_HIP, "chub_copy_envs: the indices could not be uploaded");
+    if (!rc) rc = copy_launch(dst, src, d_idx, d_idx + count, count, nullptr, keep_clocks);
+    const hipError_t he = hipDeviceSynchronize();
+    (void) hipFree(d_idx);
+    if (!rc && he != hipSuccess) rc = fail(CHUB_ERR_HIP, std::string("chub_copy_envs: ") + hipGetErrorString(he));
+    return rc;
 }
 
 // The output arrays of a host-pointer step, as the device sees them: pinned host memory (hipHostMalloc: chub_alloc_host, what

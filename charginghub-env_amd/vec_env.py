@@ -349,6 +349,28 @@ class VecChargingHub(object):
         """number of distinct env clocks right now (1 = lock-step)"""
         return self._lib.chub_clock_groups(self._h)
 
+    # ---- copying envs on the device (chub_copy_envs): env dst_idx[i] becomes a clone of env src_idx[i] of `source` (default: this handle)
+    def copy_envs(self, src_idx, dst_idx, source=None):
+        """Clone envs by index without leaving the device: population-based training (the worst k become copies of the best k), planners
+        (fan real envs out into a scratch handle), restarts from archived states.  The whole simulation state of the env is copied; in
+        the Philox modes the clone keeps drawing from its OWN counters (this handle's seed and tick, its own env id), so it parts from
+        its source at the next step.  Destinations must be distinct and, within one handle, no env both source and destination.  This
+        handle's cached observation rows follow (the clone's current observation is its source's)."""
+        src = self if source is None else source
+        s = np.ascontiguousarray(np.asarray(src_idx).ravel(), dtype=np.int64)
+        d = np.ascontiguousarray(np.asarray(dst_idx).ravel(), dtype=np.int64)
+        if s.shape != d.shape:
+            raise AssertionError("src_idx and dst_idx must have the same length")
+        check(self._lib.chub_copy_envs(self._h, src._h, _ptr(s), _ptr(d), int(s.size)))
+        if s.size and src.obs_dim == self.obs_dim:
+            self._obs[d] = src._obs[s]
+
+    def copy_envs_device(self, d_src_idx, d_dst_idx, count, source=None, stream=0):
+        """copy_envs with the index arrays (int64) in device memory, enqueued on `stream`: no host synchronisation and no validation of
+        the indices (see chub_copy_envs_device for the caller's obligations); this handle runs on per-env clocks afterwards"""
+        src = self if source is None else source
+        check(self._lib.chub_copy_envs_device(self._h, src._h, d_src_idx, d_dst_idx, int(count), stream or None))
+
     # ---- device-pointer path (ints are raw device addresses, e.g. torch.Tensor.data_ptr())
     def reset_device(self, d_obs, d_exo_days=0, d_exo_z=0, stream=0):
         check(self._lib.chub_reset_device(self._h, d_exo_days or None, d_exo_z or None, d_obs, stream or None))

@@ -258,6 +258,7 @@ class TorchHubVecEnv(object):
         self._packed = torch.empty((self.num_envs, self.obs_dim + 2), dtype=torch.float32, device=self.device)
         self._obs0 = torch.empty((self.num_envs, self.obs_dim), dtype=torch.float32, device=self.device)
         self.last_obs = None
+        self._cur_obs = None  # the observation rows the last reset / step returned
         self._t = 0
 
     def _stream(self):
@@ -266,6 +267,7 @@ class TorchHubVecEnv(object):
     def reset(self):
         self.vec.reset_device(self._obs0.data_ptr(), stream=self._stream())
         self._t = 0
+        self._cur_obs = self._obs0
         return self._obs0
 
     def step(self, actions):
@@ -280,6 +282,7 @@ class TorchHubVecEnv(object):
     def _after_step(self):
         D = self.obs_dim
         obs, reward, done = self._packed[:, :D], self._packed[:, D], self._packed[:, D + 1] > 0.5
+        self._cur_obs = obs
         self._t += 1
         if self.autoreset and self._t % 96 == 0:  # lock-step clock: done fires for every env in this step (MGR:271-273)
             self.last_obs = obs.clone()
@@ -309,6 +312,25 @@ class TorchHubVecEnv(object):
             raise AssertionError("pile_bits must be a contiguous int64 CUDA tensor of shape (%d, %d), tail float32 (%d, 2)" % (N, W, N))
         self.vec.step_bits_device_packed(pile_bits.data_ptr(), tail.data_ptr(), self._packed.data_ptr(), stream=self._stream())
         return self._after_step()
+
+    def copy_envs(self, src_idx, dst_idx, source=None):
+        """env dst_idx[i] becomes a clone of env src_idx[i] of `source` (another TorchHubVecEnv; default: this one), on torch's current
+        stream and without a host read: the indices are int64 CUDA tensors as torch.topk returns them (chub_copy_envs_device: distinct
+        destinations, within one adapter no env both source and destination -- e.g. the top k and the bottom k of one ranking, 2 k <= N).
+        The cached observation rows are copied along, so the rows the last reset / step returned stay the envs' current observations.
+        Copy between adapters that are at the same step of the day: autoreset counts one clock for the whole batch."""
+        torch = self.torch
+        src = self if source is None else source
+        for name, t in (("src_idx", src_idx), ("dst_idx", dst_idx)):
+            if not (t.is_cuda and t.dtype == torch.int64 and t.dim() == 1):
+                raise AssertionError("%s must be a 1-d int64 CUDA tensor" % name)
+        if src_idx.numel() != dst_idx.numel():
+            raise AssertionError("src_idx and dst_idx must have the same length")
+        s, d = src_idx.contiguous(), dst_idx.contiguous()
+        self.vec.copy_envs_device(s.data_ptr(), d.data_ptr(), s.numel(), source=src.vec, stream=self._stream())
+        if self._cur_obs is not None and src._cur_obs is not None:
+            self._cur_obs.index_copy_(0, d, src._cur_obs.index_select(0, s))
+        return self._cur_obs
 
     def close(self):
         self.vec.close()

@@ -100,6 +100,13 @@ def device_resident(n=65536):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print("   the same decisions as bits: %.0f M env-steps/s" % (n * steps / dt / 1e6))
+    # population-based selection without leaving the device: the worst tenth becomes a copy of the best tenth (each clone keeps its own
+    # random streams, so it parts from its source at the next step)
+    k = max(1, n // 10)
+    best, worst = torch.topk(reward, k).indices, torch.topk(reward, k, largest=False).indices
+    env.copy_envs(best, worst)
+    obs, reward, done, _ = env.step(actions)
+    print("   best %d copied over worst %d: mean reward of the next step %.4f" % (k, k, float(reward.mean())))
     env.close()
 
 

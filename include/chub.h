@@ -512,6 +512,39 @@ int64_t chub_state_size(const chub_env *env);
 int chub_get_state(chub_env *env, void *buf, int64_t size);
 int chub_set_state(chub_env *env, const void *buf, int64_t size);
 
+/* ---- copying envs on the device: branch, clone and seed envs by index -------------------------------------------------------------
+ * Env dst_idx[i] of `dst` becomes a clone of env src_idx[i] of `src`, i = 0 .. count - 1, without leaving the device: what a deep copy of
+ * the reference object gives (population-based training: the worst k envs become copies of the best k; planners: N real envs fanned out
+ * into K branches each in a scratch handle; restarts from archived states).  `src` may be `dst`; one source may be named many times.
+ *   Copied: everything chub_get_state counts as simulation state of that env -- every slot of both stations, the station records and
+ *       queues, tank, capacity, OU states, price noise, PV / wind day, the forecourt list (its folded form included), the env's slot of day
+ *       (and price-noise phase), in COMPAT the committed streams and the env's hy_power_speed_list; on handles made by chub_create_params the
+ *       env's parameter row and its table: the destination becomes the same hub as the source.
+ *   Not copied: the stream identity in PHILOX / PHILOX_CURVES -- the destination keeps drawing from its own counters (dst's seed, dst's
+ *       tick, its own global env id), so a clone parts from its source at the next launch, and a scratch handle with another seed samples
+ *       other futures.  (In COMPAT the streams ARE state: a clone given its source's actions and exo_z stays bit-identical to it.)  Draws
+ *       made one launch ahead of the next step are neither copied nor reused: the destination handle's next launch makes its own, as after
+ *       a call on a subset of the envs.  Telemetry, obs64 and reward64 of the last step are left alone, and the call writes no observation:
+ *       the destination's current observation is the source's last observation row (it is a function of the copied state only).
+ *   Clocks: a copy may give the destination another slot of day than its neighbours, so `dst` goes onto per-env clocks as after a masked
+ *       call (chub_clock_groups / chub_env_clocks report the truth; chub_reset of everybody returns to one clock).  chub_copy_envs keeps
+ *       `dst` in lock-step when both handles are in lock-step on the same slot of day and price phase.
+ *   Handle pairs: same device, same RNG mode, same station_list / station_type_list / constant_charging, both with or both without per-env
+ *       rows; without rows equal chub_config scalars; n_envs, env_id0, seed and chub_options may differ.  A scratch handle must have been
+ *       reset once before it is stepped.
+ *   chub_copy_envs (host index arrays) validates, uploads the indices, runs the device form and synchronises.  CHUB_ERR_ARG, with a message
+ *       naming the offending position and nothing written: null arguments, count < 0, an index out of range, a destination named twice,
+ *       within one handle an env that is both source and destination, incompatible handles, a source row whose FCEV arrival bound exceeds
+ *       the one `dst` was created with (as chub_set_env_params).  CHUB_ERR_UNSUPPORTED: tape handles, a handle between chub_graph_begin and
+ *       chub_graph_end.  count == 0 succeeds and does nothing.
+ *   chub_copy_envs_device (index arrays in device memory, e.g. what a top-k on the device left) returns after enqueueing ONE gather /
+ *       scatter launch on `stream`: no host synchronisation, no device read.  It checks the handles but cannot check the indices: the caller
+ *       guarantees distinct destinations, within one handle no env both source and destination, and rows that fit `dst`.  A pair with an
+ *       index out of range (or a source whose waiting list is longer than `dst` can hold) is skipped; destinations named twice or envs
+ *       that are both end with unspecified contents, and no other env is affected.  `dst` is on per-env clocks afterwards. */
+int chub_copy_envs(chub_env *dst, chub_env *src, const int64_t *src_idx, const int64_t *dst_idx, int64_t count);
+int chub_copy_envs_device(chub_env *dst, chub_env *src, const int64_t *d_src_idx, const int64_t *d_dst_idx, int64_t count, void *stream);
+
 /* electrolyser action->power table hy_power_speed_list[102] (HYD:154-157).  The reference builds it at construction
  * with 101 real hy_step()s, i.e. with live random FCEV demand, which matters whenever a tank clamp binds during that
  * sweep.  COMPAT: chub_compat_replay_constructor computes exactly that table per env from the env's streams (until
