@@ -111,6 +111,9 @@ def load_library():
         "chub_step_device_packed": (I, [P, P, P, P, P]),
         "chub_reset_envs": (I, [P, P, P, P, P]), "chub_step_envs": (I, [P, P, P, P, P, P, P]), "chub_reset_envs_device": (I, [P, P, P, P, P, P]),
         "chub_step_envs_device": (I, [P, P, P, P, P, P, P, P]), "chub_env_clocks": (I, [P, P, P]), "chub_clock_groups": (I, [P]),
+        "chub_dmask_reset_envs_device": (I, [P, P, P, P, P, P]), "chub_dmask_step_envs_device": (I, [P, P, P, P, P, P, P, P]),
+        "chub_autoreset_step_device": (I, [P, P, P, P, P, P, P, P]),
+        "chub_call_plan": (I, [C.POINTER(ChubConfig), L, I, C.POINTER(ChubOptions), I, C.c_uint32, P]),
         "chub_step_load": (I, [P, P, P, P, P, P]), "chub_step_load_device": (I, [P, P, P, P, P, P, P]),
         "chub_step_load_envs": (I, [P, P, P, P, P, P, P]), "chub_step_load_envs_device": (I, [P, P, P, P, P, P, P, P]),
         "chub_random_actions_device": (I, [P, C.c_uint64, C.c_uint32, P, P]),
@@ -160,7 +163,7 @@ def load_library():
 EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "chub_act_dim", "chub_num_envs", "chub_clock", "chub_uses_packed_kernel", "chub_uses_fused_step", "chub_uses_xcd_order", "chub_launch_plan", "chub_launch_plan_params",
             "chub_create_params", "chub_set_env_params", "chub_get_env_params", "chub_has_env_params", "chub_reset",
             "chub_step", "chub_host_actions", "chub_step_bits", "chub_host_bits", "chub_step_bits_device", "chub_step_bits_device_packed", "chub_reset_device", "chub_step_device", "chub_step_device_packed", "chub_step_load", "chub_step_load_device", "chub_step_load_envs", "chub_step_load_envs_device", "chub_reset_envs", "chub_step_envs", "chub_reset_envs_device", "chub_step_envs_device",
-            "chub_env_clocks", "chub_clock_groups", "chub_random_actions_device", "chub_sync", "chub_profile_begin", "chub_profile_end",
+            "chub_env_clocks", "chub_clock_groups", "chub_dmask_reset_envs_device", "chub_dmask_step_envs_device", "chub_autoreset_step_device", "chub_call_plan", "chub_random_actions_device", "chub_sync", "chub_profile_begin", "chub_profile_end",
             "chub_get_slots", "chub_get_station_scalars", "chub_get_telemetry", "chub_get_obs_f64",
             "chub_get_reward_f64", "chub_set_telemetry", "chub_fcev_stuck_count", "chub_set_rng_compat_seeds", "chub_set_rng_compat_state", "chub_get_rng_compat_state", "chub_compat_replay_constructor", "chub_set_ou_state",
             "chub_copy_envs", "chub_copy_envs_device", "chub_state_size", "chub_get_state", "chub_set_state", "chub_get_hy_table", "chub_get_hy_table_env", "chub_set_hy_table", "chub_last_error", "chub_device_count", "chub_build_id",

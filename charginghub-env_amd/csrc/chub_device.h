@@ -330,6 +330,14 @@ struct StepArgs {
     // and the empty slots as empt2 - cars admitted by that walk + those of them that stay one slot at most.  walk_short: the walk leaves
     // that count (StationArrays::shrt) for the walk behind it
     int32_t walk_far, walk_short;
+    // device masks and auto-reset (chub_dmask_*_device, chub_autoreset_step_device).  Read by the per-env-clock instantiations only: the
+    // lock-step kernels carry none of this.
+    uint32_t *tick_note;         // [N] or null: the tail notes the launch's true tick (CHUB_TICK) for every env it serves -- what the host
+                                 // cannot know of a mask it never sees (chub_env_clocks folds it into its record)
+    uint8_t *done_mask;          // step: [N] or null: every env's done byte of this step (0 for an env the launch does not serve), and
+    uint32_t *done_count;        //   the number of envs whose done fired, added to this counter (one vector atomic per wave)
+    const uint32_t *skip_count;  // masked reset: when given and its value is 0 the mask names nobody and every workgroup returns at entry
+    float *final_obs;            // masked reset: [N][D] or null: a served env's current row of the output buffer goes there first
 #if CHUB_TRACE
     // measurement builds only (make KFLAGS=-DCHUB_TRACE=1, tools/experiments/phase_stamps.py): s_memtime stamps at the phase boundaries of
     // the packed slot kernel and of the tail kernel (16 words per workgroup each); null: none taken

@@ -1795,6 +1795,9 @@ struct PackedArgs {
 
 typedef const uint32_t __attribute__((address_space(4))) *chub_sptr;  // constant address space: scalar loads
 __device__ __forceinline__ uint32_t sload_u32(const void *p, int i) { return ((chub_sptr) (uintptr_t) p)[i]; }
+// A masked reset behind a step that counted its done envs on the device (StepArgs::skip_count, chub_autoreset_step_device): the count is 0
+// on most calls and the mask then names nobody.  The count was written by an earlier launch of the stream, so a uniform load reads it.
+__device__ __forceinline__ bool mask_is_empty(const StepArgs &sa) { return sa.skip_count != nullptr && sload_u32(sa.skip_count, 0) == 0u; }
 
 // RESET: evs_reset (CHS.hpp:1209-1231 / 1520-1542) on the same layout: no state comes in, the unit's initial occupancy was drawn
 // by k_reset_levels, every wave helps with the (many) new cars.  BIG: a station with more than 64 piles -- a unit then spans
@@ -2235,6 +2238,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK <= 256 ? 8 : 2048 / BLOCK)) void k_sl
     __shared__ __attribute__((aligned(16))) int s_acc[2 * BLOCK * T * kAccCopies];  // 2 epb <= BLOCK * T / 2 units x {min, charge, max power, cars} (BIG: as 64-bit sums, few units)
     __shared__ uint32_t s_unit[BLOCK * T / 2];                        // per unit: line | flow << 8
     __shared__ uint32_t s_uinfo[BLOCK * T / 2];                       // per unit: where its empties are (the admission's unit pass)
+    if (RESET && MASKED && mask_is_empty(sa)) return;  // (a masked reset of nobody: chub_autoreset_step_device on most calls)
     // all kernel arguments this wave needs, requested in ONE batch of scalar loads at its very start (the single asm
     // statement makes every one of them live here), instead of in a chain of dependent loads in front of the first
     // vector load
@@ -3570,6 +3574,9 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
             if (sa.done) sa.done[e32] = (uint8_t) (dn ? 1 : 0);
             if (sa.done_f32) sa.done_f32[(size_t) e32 * sa.reward_stride] = dn ? 1.0f : 0.0f;
         }
+    } else if (MULTI && sa.done_f32) {  // a masked reset into packed rows (auto-reset): the step's reward and done stay in the env's row
+        obs[n] = sa.reward[(size_t) e32 * sa.reward_stride];
+        obs[n + 1] = sa.done_f32[(size_t) e32 * sa.reward_stride];
     }
     if (tel_on) {
         ev.reward64[e32] = reward;
@@ -3582,6 +3589,20 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
     } while (0);
     CHUB_STAMP(5);  // second half (clamp, hydrogen step, netting, fuel cell, money, observation) done
     mid.at3();
+    if (MULTI) {  // device masks and auto-reset (every lane is here: the do / while above)
+        if (RESET && sa.final_obs && live) {  // the row the reset is about to replace: the terminal observation
+            const float *row = sa.obs + (size_t) e32 * (size_t) row_w;
+            float *fin = sa.final_obs + (size_t) e32 * (size_t) hp.obs_dim;
+            for (int j = 0; j < hp.obs_dim; j++) fin[j] = row[j];
+        }
+        if (sa.tick_note && live) sa.tick_note[e32] = CHUB_TICK(hp, sa.tick);
+        if (!RESET && sa.done_mask) {
+            const bool dn = live && (t_now + 1) >= 96;
+            if (env < (int) N) sa.done_mask[e32] = (uint8_t) (dn ? 1 : 0);
+            const unsigned long long fired = __ballot(dn);
+            if ((threadIdx.x & 63u) == 0u && fired != 0ull) atomicAdd(sa.done_count, (uint32_t) __popcll(fired));
+        }
+    }
     flush_rows();
 #if CHUB_TRACE
     CHUB_STAMP(6);  // rows flushed
@@ -3638,6 +3659,9 @@ __global__ __launch_bounds__(kEnvBlock) void k_env(const DevCtx *__restrict__ ct
     __shared__ double s_pv[100], s_wd[150], s_pv_now[100], s_wd_now[150], s_hy[102];
     __shared__ __attribute__((aligned(16))) uint8_t s_hv[kLevels];
     __shared__ __attribute__((aligned(16))) float s_out[kEnvBlock * 16];  // output rows: obs_dim + 2 <= 15 floats
+    // a masked reset whose mask was counted on the device (auto-reset: the envs the step in front found done) and names nobody: nothing to
+    // do, tails and level workgroups alike -- one uniform load.  (Every env's clock has been carried to the other buffer by k_keep_clocks.)
+    if (RESET && MULTI && mask_is_empty(sa)) return;
     if (MODE == MODE_PHILOX && (int) blockIdx.x >= nb_env) {
         // the last blocks of the grid: next step's station-level draws, one lane per (station, env).
         // They are pure VALU work and fill the issue slots the latency-bound tail waves leave empty.
@@ -4425,7 +4449,7 @@ __global__ void k_replay_soc(const DevCtx *__restrict__ ctx, float *out) {
 // PHILOX reset: evs_reset's initial occupancy per (station, env) unit -- init_station_car_number(mu, 3) (CHS.hpp:832-842)
 // thinned by the balk test of an empty queue -- drawn once per unit here (every lane of the unit used to redo it),
 // handed to k_slot<RESET> through this tick's pk word: arrivals | arrivals that stay << 8.
-__global__ void k_reset_levels(const DevCtx *__restrict__ ctx, StepArgs sa) {
+__device__ __forceinline__ void reset_levels_body(const DevCtx *__restrict__ ctx, const StepArgs &sa) {
     // four lanes per unit: lane q takes the Philox blocks q, q + 4, ... of the unit's arrival words (four arrivals each), the
     // quad adds up.  (One lane per unit walking all its arrivals was a 15-iteration dependent chain at two waves per SIMD:
     // 20 us per reset.)
@@ -4461,6 +4485,12 @@ __global__ void k_reset_levels(const DevCtx *__restrict__ ctx, StepArgs sa) {
     true_in += __shfl_xor(true_in, 2);
     if (served && q == 0)
         ctx->st.pk[tick & 1u][u] = ((uint32_t) n_in & 0xFFFFu) | ((uint32_t) true_in << 16);  // n_in: signed 16 bits
+}
+__global__ void k_reset_levels(const DevCtx *__restrict__ ctx, StepArgs sa) { reset_levels_body(ctx, sa); }
+// ... in front of the masked reset of an auto-reset call, whose mask may name nobody (every workgroup then returns at entry)
+__global__ void k_reset_levels_gated(const DevCtx *__restrict__ ctx, StepArgs sa) {
+    if (mask_is_empty(sa)) return;
+    reset_levels_body(ctx, sa);
 }
 
 // fresh launches (StepArgs::fresh): this step's station-level draws, made right in front of the slot kernel -- what the
@@ -4511,7 +4541,10 @@ static void launch_levels(LevelsForm lv, const DevCtx *ctx, const StepArgs &sa, 
     switch (lv) {
     case LEVELS_NONE: break;
     case LEVELS_DRAW: hipLaunchKernelGGL(k_draw_levels, dim3((unsigned) ((2 * n + 255) / 256)), dim3(256), 0, stream, ctx, sa); break;
-    case LEVELS_RESET: hipLaunchKernelGGL(k_reset_levels, dim3((unsigned) ((8 * n + 255) / 256)), dim3(256), 0, stream, ctx, sa); break;
+    case LEVELS_RESET:
+        if (sa.skip_count) hipLaunchKernelGGL(k_reset_levels_gated, dim3((unsigned) ((8 * n + 255) / 256)), dim3(256), 0, stream, ctx, sa);
+        else hipLaunchKernelGGL(k_reset_levels, dim3((unsigned) ((8 * n + 255) / 256)), dim3(256), 0, stream, ctx, sa);
+        break;
     }
 }
 

@@ -221,6 +221,8 @@ struct CallState {
     bool bits;         // one bit per pile (chub_step_bits*)
     bool fresh;        // the call makes its own state-independent draws (StepArgs::fresh)
     bool env_params;   // the handle has per-env hub parameters (plan_params)
+    bool dev_mask;     // the call's mask lives in device memory and the host never sees it (chub_dmask_*_device, the reset of
+                       // chub_autoreset_step_device): per-env clocks and the masked forms whatever the mask holds, over the whole env range
 };
 struct CallPlan {
     CallForm call;
@@ -245,7 +247,12 @@ inline SlotForm slot_form(const LaunchPlan &p, const CallState &c) {
 }
 
 // CallPlan::slot, levels and env are those of the CALL_SLOT_* forms
-inline CallPlan plan_call(const LaunchPlan &p, const CallState &c) {
+inline CallPlan plan_call(const LaunchPlan &p, const CallState &c_in) {
+    CallState c = c_in;
+    if (c.dev_mask) {  // nobody knows whether the mask names everybody: it never does, as far as the forms go
+        c.per_env = true;
+        c.all_served = false;
+    }
     CallPlan r = {CALL_SLOT_ENV, ONE_NONE, SLOT_WAVE, LEVELS_NONE, ENV_PHILOX};
     const bool compat = p.compat != COMPAT_NONE, lock_step = !c.load_mode && !c.per_env;
     if (p.compat_small && !c.per_env && (c.reset || !c.load_mode)) {

@@ -98,6 +98,12 @@ struct chub_env {
     uint8_t *h_mask;                // [2][N] pinned staging for them
     hipEvent_t mask_done[2];        // recorded behind the launches that read d_mask[i]
     uint32_t mask_seq;
+    // device masks and auto-reset (chub_dmask_*_device, chub_autoreset_step_device): the host never sees such a mask, so the launches note on
+    // the device whom they served; chub_env_clocks and chub_get_state (which synchronise anyway) fold that into h_tick
+    uint32_t *d_tick_note = nullptr;   // [N], in the arena: the true tick of the last device-mask launch that served the env (0: none)
+    uint8_t *d_done_mask = nullptr;    // [2][N], in the arena: the done masks of the last two auto-reset calls (the reset launches read them)
+    uint32_t *d_done_count = nullptr;  // [2][16]: how many envs each of them names
+    uint32_t done_seq = 0;
     // a capture on per-env clocks: every masked call gets a device mask of its own (owned by the graph: a replay reads no host
     // memory), and the capture notes which launch of it served each env last (chub_env_clocks after a replay)
     std::vector<void *> cap_masks;
@@ -899,6 +905,7 @@ static int create_impl(const chub_config *cfg_in, const char *data_dir, int64_t 
         HIP_TRY(hipMemcpy(e->ev.hy_env, rep.data(), rep.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     ALLOC(e->d_env_clk, 2 * N); ALLOC(e->d_mask, 2 * N);
+    ALLOC(e->d_tick_note, N); ALLOC(e->d_done_mask, 2 * N); ALLOC(e->d_done_count, 32);
     ALLOC(e->d_tick_base, 64);
     e->hp.tick_base = e->d_tick_base;
     ALLOC(e->d_ctx, 1);
@@ -1064,6 +1071,12 @@ struct StepCall {
     bool reset;
     int load_mode;            // step: the scalar-load control (chub_step_load*)
     const uint8_t *mask;      // HOST [N], non-zero = the call serves this env; null: every env.  Everything below is device memory
+    const uint8_t *dmask;     // or the mask in DEVICE memory, read by the launch alone (chub_dmask_*_device, the reset of an auto-reset call)
+    // auto-reset (chub_autoreset_step_device): its step leaves the done mask and its count, its reset reads them and saves the terminal rows
+    uint8_t *done_mask;
+    uint32_t *done_count;
+    const uint32_t *skip_count;
+    float *final_obs;
     const float *actions;     // step: the action rows [N][A], or
     const uint64_t *bits;     //   one decision bit per pile [N][ceil(S / 64)] and
     const float *tail;        //   the two tail actions [N][2] (chub_step_bits*)
@@ -1110,6 +1123,29 @@ struct MaskView {
     int64_t lo, hi;
 };
 
+// onto per-env clocks: every env starts from the lock-step clock, in the buffer the next launch reads
+static void enter_per_env(chub_env *e, hipStream_t s) {
+    const size_t N = (size_t) e->hp.n_envs;
+    const uint16_t c = (uint16_t) ((uint32_t) e->t | (((uint32_t) e->price_count & 3u) << 8));
+    launch_fill_clocks(e->d_env_clk + (size_t) ((e->tick + 1u - e->graph_base) & 1u) * N, (int64_t) N, c, s);
+    e->per_env = true;
+    if (e->h_tick.size() != N) e->h_tick.assign(N, 0u);
+}
+static const char *const kCaptureNeedsClocks = "a capture that names subsets of the envs must start on per-env clocks: make the first call "
+                                               "on a subset before chub_graph_begin (it fills the per-env clocks from the handle's clock)";
+
+// A mask in device memory: the host does not know whom it names, so the call is a masked one over the whole range of envs whatever it
+// holds -- no count, no staging, no copy, no wait; a captured call re-reads the caller's buffer on every replay.
+static int serve_dmask(chub_env *e, const uint8_t *d_mask, hipStream_t s, int &served, MaskView &mv) {
+    if (!e->per_env) {
+        if (e->capturing) return fail(CHUB_ERR_ARG, kCaptureNeedsClocks);
+        enter_per_env(e, s);
+    }
+    mv = {d_mask, 0, e->hp.n_envs - 1};
+    served = 1;
+    return CHUB_OK;
+}
+
 // What one call serves: 0 nobody, 1 a subset (mask uploaded, per-env clocks on), 2 every env.
 static int serve_mask(chub_env *e, const uint8_t *mask, hipStream_t s, int &served, MaskView &mv) {
     const size_t N = (size_t) e->hp.n_envs;
@@ -1134,9 +1170,7 @@ static int serve_mask(chub_env *e, const uint8_t *mask, hipStream_t s, int &serv
     if (e->capturing) {
         // a replay must not read the caller's (or the handle's staging) memory: the mask of a captured call lives in a device
         // buffer of its own, filled now and freed with the graph.  The clocks are device state, so nothing of them is baked in.
-        if (!e->per_env)
-            return fail(CHUB_ERR_ARG, "a capture that names subsets of the envs must start on per-env clocks: make the first call "
-                                      "on a subset before chub_graph_begin (it fills the per-env clocks from the handle's clock)");
+        if (!e->per_env) return fail(CHUB_ERR_ARG, kCaptureNeedsClocks);
         uint8_t *d = nullptr;
         HIP_TRY(hipMalloc((void **) &d, N));
         e->cap_masks.push_back(d);
@@ -1147,12 +1181,7 @@ static int serve_mask(chub_env *e, const uint8_t *mask, hipStream_t s, int &serv
         mv.d_mask = d;
         return CHUB_OK;
     }
-    if (!e->per_env) {  // every env starts from the lock-step clock, in the buffer the next launch reads
-        const uint16_t c = (uint16_t) ((uint32_t) e->t | (((uint32_t) e->price_count & 3u) << 8));
-        launch_fill_clocks(e->d_env_clk + (size_t) ((e->tick + 1u - e->graph_base) & 1u) * N, (int64_t) N, c, s);
-        e->per_env = true;
-        if (e->h_tick.size() != N) e->h_tick.assign(N, 0u);
-    }
+    if (!e->per_env) enter_per_env(e, s);
     // the mask of this call: the caller's array is only borrowed for the duration of the call, so it goes through one of two
     // pinned staging buffers; a buffer is reused once the launches that read its device copy are done (two masked calls ago)
     if (!e->h_mask) {
@@ -1207,6 +1236,7 @@ static CallPlan plan_this_call(const chub_env *e, const StepCall &call, int serv
     c.bits = !call.reset && call.bits;
     c.fresh = fresh;
     c.env_params = e->env_params;
+    c.dev_mask = call.dmask != nullptr;
     return plan_call(e->plan, c);
 }
 
@@ -1256,6 +1286,11 @@ static int fill_args(chub_env *e, const StepCall &c, int served, const MaskView 
             sa.env_hi = (int32_t) mv.hi;
         }
     }
+    if (c.dmask) sa.tick_note = e->d_tick_note;  // (whom the launch served: only the device knows)
+    sa.done_mask = c.done_mask;
+    sa.done_count = c.done_count;
+    sa.skip_count = c.skip_count;
+    sa.final_obs = c.final_obs;
     return sync_ctx(e, s);
 }
 
@@ -1417,13 +1452,14 @@ static int run_call(chub_env *e, const StepCall &call, hipStream_t s) {
     int served = 0;
     MaskView mv;
     const bool was_per_env = e->per_env;
-    int rc = serve_mask(e, c.mask, s, served, mv);
+    int rc = c.dmask ? serve_dmask(e, c.dmask, s, served, mv) : serve_mask(e, c.mask, s, served, mv);
     if (rc || served == 0) return rc;
     rc = c.reset ? run_reset(e, c, served, mv, s) : run_step(e, c, served, mv, s);
     if (rc) {
         e->per_env = was_per_env;  // nothing was launched: the handle stays on the clock(s) it was on
         return rc;
     }
+    if (c.dmask) return CHUB_OK;  // (the launch itself notes whom it served: StepArgs::tick_note)
     return note_served(e, c.mask, served, s);
 }
 
@@ -1458,6 +1494,105 @@ int chub_step_envs_device(chub_env *e, const uint8_t *mask, const float *d_actio
                           uint8_t *d_done, void *stream) {
     if (!e || !mask || !d_actions || !d_obs || !d_reward || !d_done) return fail(CHUB_ERR_ARG, "null argument");
     return run_call(e, step_call(mask, d_actions, d_exo_z, dense_out(e, d_obs, d_reward, d_done), 0), (hipStream_t) stream);
+}
+
+// ---- masks in device memory, and the step that resets whoever finished (include/chub.h) ---------------------------------------------------
+static int refuse_tape_dmask(const chub_env *e, const char *what) {
+    if (!e->tape_only) return CHUB_OK;
+    return fail(CHUB_ERR_UNSUPPORTED, std::string(what) + " is not supported on a tape handle (chub_tape_register_soc)");
+}
+
+int chub_dmask_reset_envs_device(chub_env *e, const uint8_t *d_mask, const int32_t *d_exo_days, const double *d_exo_z, float *d_obs, void *stream) {
+    if (!e || !d_mask || !d_obs) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = refuse_tape_dmask(e, "chub_dmask_reset_envs_device")) return rc;
+    StepCall c = reset_call(e, nullptr, d_exo_days, d_exo_z, d_obs);
+    c.dmask = d_mask;
+    return run_call(e, c, (hipStream_t) stream);
+}
+
+int chub_dmask_step_envs_device(chub_env *e, const uint8_t *d_mask, const float *d_actions, const double *d_exo_z, float *d_obs, float *d_reward,
+                                uint8_t *d_done, void *stream) {
+    if (!e || !d_mask || !d_actions || !d_obs || !d_reward || !d_done) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = refuse_tape_dmask(e, "chub_dmask_step_envs_device")) return rc;
+    StepCall c = step_call(nullptr, d_actions, d_exo_z, dense_out(e, d_obs, d_reward, d_done), 0);
+    c.dmask = d_mask;
+    return run_call(e, c, (hipStream_t) stream);
+}
+
+// Two launches, two ticks, whoever is done: the step of every env on its own clock (tick T), which leaves each env's done byte and their
+// count in the handle's buffers, then the masked reset of exactly those envs (tick T + 1), whose workgroups return at entry while the count
+// is 0.  Both go into the packed block: a reset env's row keeps the step's reward and done = 1 and takes the new episode's first observation.
+int chub_autoreset_step_device(chub_env *e, const float *d_actions, const double *d_exo_z, const int32_t *d_reset_exo_days,
+                               const double *d_reset_exo_z, float *d_packed, float *d_final_obs, void *stream) {
+    if (!e || !d_actions || !d_packed) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = refuse_tape_dmask(e, "chub_autoreset_step_device")) return rc;
+    if (e->tick == 0) return fail(CHUB_ERR_ARG, "step() before reset()");
+    if (const int rc = check_compat_variates(e, false, nullptr, d_exo_z)) return rc;
+    if (e->hp.rng_mode == CHUB_RNG_COMPAT && (!d_reset_exo_days || !d_reset_exo_z))
+        return fail(CHUB_ERR_ARG, "COMPAT mode needs d_reset_exo_days and d_reset_exo_z (the rows of the envs that finish are read)");
+    hipStream_t s = (hipStream_t) stream;
+    HIP_TRY(hipSetDevice(e->device));
+    // Everything a caller can get wrong has been refused above: from here on only the HIP runtime can fail.  If it does before the step is
+    // launched the handle is left as it was found (clocks, draws, mask buffer); if it does between the two launches the step HAS run -- one
+    // tick is consumed, the done mask is on the device and nobody has been reset -- and the error is returned as it is: the caller's stream
+    // is in a state only it can judge (the same holds for any call whose second kernel fails to launch).
+    const bool was_per_env = e->per_env, was_predrawn = e->predrawn;
+    if (!e->per_env) {
+        if (e->capturing) return fail(CHUB_ERR_ARG, kCaptureNeedsClocks);
+        enter_per_env(e, s);
+        e->predrawn = false;  // (the step below makes its own draws, as after any call that changed how the envs are served)
+    }
+    const size_t N = (size_t) e->hp.n_envs;
+    const uint32_t b = e->done_seq & 1u;
+    uint8_t *mask = e->d_done_mask + (size_t) b * N;
+    uint32_t *count = e->d_done_count + (size_t) b * 16;
+    StepCall st = step_call(nullptr, d_actions, d_exo_z, packed_out(e, d_packed), 0);
+    st.done_mask = mask;
+    st.done_count = count;
+    int rc = hipMemsetAsync(count, 0, sizeof(uint32_t), s) == hipSuccess ? CHUB_OK : fail(CHUB_ERR_HIP, "hipMemsetAsync of the done count failed");
+    if (!rc) rc = run_call(e, st, s);
+    if (rc) {  // nothing was launched
+        e->per_env = was_per_env;
+        e->predrawn = was_predrawn;
+        return rc;
+    }
+    e->done_seq += 1;
+    StepCall rs = reset_call(e, nullptr, d_reset_exo_days, d_reset_exo_z, d_packed);
+    rs.out = packed_out(e, d_packed);
+    rs.dmask = mask;
+    rs.skip_count = count;
+    rs.final_obs = d_final_obs;
+    return run_call(e, rs, s);
+}
+
+// the launch forms of one reset / step (plan_call of chub_plan.h) for a handle of this shape, without a device
+int chub_call_plan(const chub_config *cfg, int64_t n_envs, int rng_mode, const chub_options *opt_in, int env_params, uint32_t flags, int32_t *out) {
+    if (!cfg || !out) return fail(CHUB_ERR_ARG, "null argument");
+    chub_options opt;
+    memset(&opt, 0, sizeof opt);
+    if (opt_in) opt = *opt_in;
+    LaunchPlan p;
+    const char *msg = nullptr;
+    if (const int rc = plan_handle(cfg, n_envs, rng_mode, opt, p, &msg)) return fail(rc, msg);
+    if (env_params)
+        if (const int rc = plan_params(p, rng_mode, &msg)) return fail(rc, msg);
+    CallState c = {};
+    c.reset = (flags & CHUB_CALL_RESET) != 0;
+    c.per_env = (flags & CHUB_CALL_PER_ENV) != 0;
+    c.all_served = (flags & CHUB_CALL_ALL_SERVED) != 0;
+    c.dev_mask = (flags & CHUB_CALL_DEV_MASK) != 0;
+    c.fresh = (flags & CHUB_CALL_FRESH) != 0;
+    c.bits = (flags & CHUB_CALL_BITS) != 0;
+    c.load_mode = (flags & CHUB_CALL_LOAD) != 0;
+    c.capturing = (flags & CHUB_CALL_CAPTURING) != 0;
+    c.env_params = env_params != 0;
+    const CallPlan r = plan_call(p, c);
+    out[CHUB_CALLPLAN_CALL] = r.call;
+    out[CHUB_CALLPLAN_ONE] = r.one;
+    out[CHUB_CALLPLAN_SLOT] = r.slot;
+    out[CHUB_CALLPLAN_LEVELS] = r.levels;
+    out[CHUB_CALLPLAN_ENV] = r.env;
+    return CHUB_OK;
 }
 
 // the scalar-load step on a subset of the envs (every reference env can take evs_step(float) on its own, CHS.hpp:1169-1186 / 1480-1497)
@@ -1559,6 +1694,13 @@ int chub_env_clocks(chub_env *e, int32_t *t_out, uint32_t *tick_out) {
     std::vector<uint16_t> c;
     int rc = fetch_clocks(e, c);
     if (rc) return rc;
+    if (e->per_env && tick_out) {  // what the device-mask launches noted of whom they served (the device is idle: fetch_clocks synchronised)
+        std::vector<uint32_t> note(N);
+        HIP_TRY(hipMemcpy(note.data(), e->d_tick_note, N * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (e->h_tick.size() != N) e->h_tick.assign(N, 0u);
+        for (size_t i = 0; i < N; i++)
+            if (note[i] > e->h_tick[i]) e->h_tick[i] = note[i];
+    }
     for (size_t i = 0; i < N; i++) {
         t_out[i] = (int32_t) (c[i] & 127u);
         if (tick_out) tick_out[i] = (e->h_tick.size() == N && e->h_tick[i] > e->full_tick) ? e->h_tick[i] : e->full_tick;

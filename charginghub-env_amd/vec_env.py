@@ -390,6 +390,23 @@ class VecChargingHub(object):
     def step_bits_device_packed(self, d_pile_bits, d_tail, d_packed, d_exo_z=0, stream=0):
         check(self._lib.chub_step_bits_device_packed(self._h, d_pile_bits, d_tail, d_exo_z or None, d_packed, stream or None))
 
+    # ---- masks in device memory and the step that resets whoever finished: the host never looks at a mask (include/chub.h)
+    def reset_envs_dmask_device(self, d_mask, d_obs, d_exo_days=0, d_exo_z=0, stream=0):
+        """reset_envs with the mask ([N] uint8) in device memory, enqueued on `stream`: one launch, one tick, no host wait; the
+        handle runs on per-env clocks afterwards and stays there whatever the mask holds"""
+        check(self._lib.chub_dmask_reset_envs_device(self._h, d_mask, d_exo_days or None, d_exo_z or None, d_obs, stream or None))
+
+    def step_envs_dmask_device(self, d_mask, d_actions, d_obs, d_reward, d_done, d_exo_z=0, stream=0):
+        """step_envs with the mask ([N] uint8) in device memory (as reset_envs_dmask_device); only the named envs' rows are written"""
+        check(self._lib.chub_dmask_step_envs_device(self._h, d_mask, d_actions, d_exo_z or None, d_obs, d_reward, d_done, stream or None))
+
+    def step_autoreset_device(self, d_actions, d_packed, d_final_obs=0, d_exo_z=0, d_reset_exo_days=0, d_reset_exo_z=0, stream=0):
+        """every env takes one step on its own clock and every env whose done fired is reset in the same call (always two ticks):
+        d_packed [N, D + 2] carries, for a reset env, the step's reward, done = 1 and the first observation of the new episode;
+        d_final_obs [N, D] (optional) receives the terminal observation rows of the reset envs"""
+        check(self._lib.chub_autoreset_step_device(self._h, d_actions, d_exo_z or None, d_reset_exo_days or None, d_reset_exo_z or None,
+                                                   d_packed, d_final_obs or None, stream or None))
+
     def random_actions_device(self, d_actions, key, batch, stream=0):
         check(self._lib.chub_random_actions_device(self._h, int(key), int(batch), d_actions, stream or None))
 

@@ -243,26 +243,44 @@ class TorchHubVecEnv(object):
     (the host-pointer ``VecChargingHub.step`` moves 47 + 15 floats per env over PCIe, about 3x the device time at 65 536
     envs).  ``step`` returns views of ONE packed [N, D + 2] output buffer (what ``chub_step_device_packed`` writes);
     with ``autoreset`` the envs are reset in the step that ends the episode and the returned observation is the first
-    of the next one (``last_obs`` keeps the terminal one).  torch is imported here, not by the package."""
+    of the next one (``last_obs`` keeps the terminal one).  torch is imported here, not by the package.
+
+    ``autoreset=True`` counts ONE clock for the whole batch on the host (every env ends its day in the same step).
+    ``autoreset="per_env"`` keeps no clock at all: every ``step`` is one ``chub_autoreset_step_device`` -- each env steps on its
+    own clock and whoever finishes is reset on the device, in the same call -- so ``done`` is the per-env flag, ``last_obs`` is a
+    fixed [N, D] buffer whose rows are valid where ``done`` (the terminal observations), and envs cloned in from an adapter at
+    another time of day (``copy_envs``) simply keep their own days.  Nothing in that path reads the device or waits for it.
+    ``step_bits`` is refused in this mode (the auto-reset call takes action rows).  ``device`` is a CUDA ordinal or a ``torch.device``."""
 
     def __init__(self, n_envs, station_list, station_type_list, seed=0, device=0, autoreset=True, **hub_kwargs):
         import torch  # before libchub is loaded by VecChargingHub: both must share one HIP runtime
 
+        if not (autoreset is True or autoreset is False or autoreset == "per_env"):
+            raise ValueError("autoreset must be True, False or 'per_env', not %r" % (autoreset,))
         self.torch = torch
-        self.device = torch.device("cuda", int(device))
-        torch.cuda.set_device(self.device)
-        self.vec = VecChargingHub(n_envs, station_list, station_type_list, seed=seed, rng="philox", device=int(device),
+        self.device = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
+        if self.device.type == "cuda":
+            torch.cuda.set_device(self.device)
+        self.vec = VecChargingHub(n_envs, station_list, station_type_list, seed=seed, rng="philox", device=int(self.device.index or 0),
                                   **hub_kwargs)
         self.num_envs, self.obs_dim, self.act_dim = self.vec.n_envs, self.vec.obs_dim, self.vec.act_dim
+        self.per_env = autoreset == "per_env"
         self.autoreset = bool(autoreset)
         self._packed = torch.empty((self.num_envs, self.obs_dim + 2), dtype=torch.float32, device=self.device)
         self._obs0 = torch.empty((self.num_envs, self.obs_dim), dtype=torch.float32, device=self.device)
         self.last_obs = None
+        if self.per_env:  # the terminal rows land here on the device: rows valid where the step's done is set
+            self.last_obs = torch.zeros((self.num_envs, self.obs_dim), dtype=torch.float32, device=self.device)
         self._cur_obs = None  # the observation rows the last reset / step returned
         self._t = 0
 
     def _stream(self):
+        if self.device.type != "cuda":
+            return 0
         return self.torch.cuda.current_stream(self.device).cuda_stream
+
+    def _on_device(self, t):
+        return t.device.type == self.device.type
 
     def reset(self):
         self.vec.reset_device(self._obs0.data_ptr(), stream=self._stream())
@@ -272,10 +290,15 @@ class TorchHubVecEnv(object):
 
     def step(self, actions):
         a = actions
-        if not (a.is_cuda and a.dtype == self.torch.float32 and a.is_contiguous()
+        if not (self._on_device(a) and a.dtype == self.torch.float32 and a.is_contiguous()
                 and tuple(a.shape) == (self.num_envs, self.act_dim)):
-            raise AssertionError("actions must be a contiguous float32 CUDA tensor of shape (%d, %d)"
-                                 % (self.num_envs, self.act_dim))
+            raise AssertionError("actions must be a contiguous float32 tensor on %s of shape (%d, %d)"
+                                 % (self.device, self.num_envs, self.act_dim))
+        if self.per_env:  # step + reset of whoever is done, on the device: no clock here, nothing read back
+            self.vec.step_autoreset_device(a.data_ptr(), self._packed.data_ptr(), self.last_obs.data_ptr(), stream=self._stream())
+            D = self.obs_dim
+            self._cur_obs = self._packed[:, :D]
+            return self._cur_obs, self._packed[:, D], self._packed[:, D + 1] > 0.5, {}
         self.vec.step_device_packed(a.data_ptr(), self._packed.data_ptr(), stream=self._stream())
         return self._after_step()
 
@@ -307,9 +330,11 @@ class TorchHubVecEnv(object):
         """step() fed one bit per pile + the two tail floats (pack_bits' layout) instead of action rows: 8 W + 8 bytes of action input
         per env instead of 4 (S + 2); on the packed slot kernel the step reads the bits themselves"""
         torch, N, W = self.torch, self.num_envs, self.vec.bit_words
-        if not (pile_bits.is_cuda and pile_bits.dtype == torch.int64 and pile_bits.is_contiguous() and tuple(pile_bits.shape) == (N, W)
-                and tail.is_cuda and tail.dtype == torch.float32 and tail.is_contiguous() and tuple(tail.shape) == (N, 2)):
-            raise AssertionError("pile_bits must be a contiguous int64 CUDA tensor of shape (%d, %d), tail float32 (%d, 2)" % (N, W, N))
+        if self.per_env:
+            raise RuntimeError("step_bits is not available with autoreset='per_env' (chub_autoreset_step_device takes action rows)")
+        if not (self._on_device(pile_bits) and pile_bits.dtype == torch.int64 and pile_bits.is_contiguous() and tuple(pile_bits.shape) == (N, W)
+                and self._on_device(tail) and tail.dtype == torch.float32 and tail.is_contiguous() and tuple(tail.shape) == (N, 2)):
+            raise AssertionError("pile_bits must be a contiguous int64 tensor on %s of shape (%d, %d), tail float32 (%d, 2)" % (self.device, N, W, N))
         self.vec.step_bits_device_packed(pile_bits.data_ptr(), tail.data_ptr(), self._packed.data_ptr(), stream=self._stream())
         return self._after_step()
 
@@ -318,12 +343,14 @@ class TorchHubVecEnv(object):
         stream and without a host read: the indices are int64 CUDA tensors as torch.topk returns them (chub_copy_envs_device: distinct
         destinations, within one adapter no env both source and destination -- e.g. the top k and the bottom k of one ranking, 2 k <= N).
         The cached observation rows are copied along, so the rows the last reset / step returned stay the envs' current observations.
-        Copy between adapters that are at the same step of the day: autoreset counts one clock for the whole batch."""
+        With ``autoreset=True`` copy between adapters that are at the same step of the day (that mode counts one clock for the whole
+        batch); with ``autoreset="per_env"`` the adapters may be at any times of day: a clone keeps its source's clock and ends its
+        day when that clock does."""
         torch = self.torch
         src = self if source is None else source
         for name, t in (("src_idx", src_idx), ("dst_idx", dst_idx)):
-            if not (t.is_cuda and t.dtype == torch.int64 and t.dim() == 1):
-                raise AssertionError("%s must be a 1-d int64 CUDA tensor" % name)
+            if not (self._on_device(t) and t.dtype == torch.int64 and t.dim() == 1):
+                raise AssertionError("%s must be a 1-d int64 tensor on %s" % (name, self.device))
         if src_idx.numel() != dst_idx.numel():
             raise AssertionError("src_idx and dst_idx must have the same length")
         s, d = src_idx.contiguous(), dst_idx.contiguous()

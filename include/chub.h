@@ -288,6 +288,58 @@ int chub_step_envs_device(chub_env *env, const uint8_t *mask /* host */, const f
 int chub_env_clocks(chub_env *env, int32_t *t_out, uint32_t *tick_out);
 int chub_clock_groups(chub_env *env);
 
+/* Masks in device memory, and the step that resets whoever finished.  Which envs finished a step is known on the device only; a trainer
+ * whose episodes are staggered (clones from an archive or another handle, chub_copy_envs_device) would otherwise read `done` back,
+ * synchronise, build a host mask and call chub_reset_envs_device -- a device read and a stream wait per step.  On these entry points the
+ * host never looks at a mask.
+ *   chub_dmask_reset_envs_device / chub_dmask_step_envs_device: chub_reset_envs_device / chub_step_envs_device with d_mask [N] u8 in DEVICE
+ *       memory (the caller's buffer, read by the launch in stream order).  The call returns after enqueueing: no synchronisation, no staging
+ *       copy, no allocation.  It always takes exactly one Philox tick and always launches, over the whole range of envs; the handle goes onto
+ *       per-env clocks as after a host-mask call and STAYS there -- a device mask that happens to name everybody cannot return it to lock-step
+ *       (chub_reset of everybody still does) -- and the next launch makes its own state-independent draws, as after any call on a subset.
+ *       For a mask that is neither empty nor full: state, outputs and ticks are bit for bit those of the host-mask call with the same mask.
+ *       An all-zero mask changes no env state and writes no output row; it still consumes its tick.  All three RNG modes, with and without
+ *       per-env parameter rows.  CHUB_ERR_UNSUPPORTED with a message: tape handles.  (Scalar-load and bits forms take host masks only.)
+ *   chub_autoreset_step_device: every env takes one step on its own clock, and every env whose `done` fired in that step is then reset, in
+ *       the same call on the same stream.  ALWAYS two ticks: T for the step, T + 1 for the reset launch, whether or not anybody was done (the
+ *       streams then depend on nothing the host cannot know, and results stay independent of sharding).  Results: those of
+ *       chub_step_device_packed of everybody followed by a masked reset with mask = that step's done.  d_packed [N, D + 2]: for a reset env
+ *       the step's reward, done = 1 and the FIRST OBSERVATION OF THE NEW EPISODE; d_final_obs [N, D] (may be NULL) receives the terminal
+ *       observation rows of the reset envs, rows of other envs are left alone.  Valid on a lock-step handle (it moves to per-env clocks
+ *       first).  COMPAT: the step reads d_exo_z as chub_step_device does; the reset reads the rows of the reset envs of d_reset_exo_days
+ *       [N, 2] / d_reset_exo_z [N, 3] (ignored, may be NULL, in the Philox modes).  While nobody is done the reset launch's workgroups
+ *       return at entry: the handle counts the done envs on the device.
+ *   Ticks: chub_env_clocks(.., tick_out) stays truthful -- the launches note on the device whom they served, and chub_env_clocks /
+ *       chub_get_state (which synchronise anyway) fold that into the host's record; snapshots taken after such calls restore and continue
+ *       bit-identically.
+ *   Graphs: all three are recordable between chub_graph_begin and chub_graph_end under the rule that such a capture starts on per-env
+ *       clocks.  A device mask is the caller's buffer and is re-read on every replay (no per-call copy); a captured auto-reset call is two
+ *       launches (k calls: 2k, always even).  Such a graph may be replayed indefinitely whatever the envs' clocks are. */
+int chub_dmask_reset_envs_device(chub_env *env, const uint8_t *d_mask, const int32_t *d_exo_days, const double *d_exo_z, float *d_obs,
+                                 void *stream);
+int chub_dmask_step_envs_device(chub_env *env, const uint8_t *d_mask, const float *d_actions, const double *d_exo_z, float *d_obs,
+                                float *d_reward, uint8_t *d_done, void *stream);
+int chub_autoreset_step_device(chub_env *env, const float *d_actions, const double *d_exo_z, const int32_t *d_reset_exo_days,
+                               const double *d_reset_exo_z, float *d_packed /* [N, D + 2] */, float *d_final_obs /* [N, D], may be NULL */,
+                               void *stream);
+
+/* The launch forms ONE reset / step takes on a handle of this shape (chub_launch_plan's per-call half), without a device: flags describe the
+ * call and the handle's state, out[CHUB_CALLPLAN_COUNT] receives the forms (values in the order of the enums of csrc/chub_plan.h: CallForm,
+ * OneLaunch, SlotForm, LevelsForm, EnvForm).  env_params != 0: a handle made by chub_create_params. */
+enum {
+    CHUB_CALL_RESET = 1,       /* a reset (else a step) */
+    CHUB_CALL_PER_ENV = 2,     /* the handle is on per-env clocks */
+    CHUB_CALL_ALL_SERVED = 4,  /* the call serves every env (no mask) */
+    CHUB_CALL_DEV_MASK = 8,    /* the mask is in device memory: the masked forms and per-env clocks whatever else is set */
+    CHUB_CALL_FRESH = 16,      /* the launch makes its own state-independent draws */
+    CHUB_CALL_BITS = 32,       /* one bit per pile (chub_step_bits*) */
+    CHUB_CALL_LOAD = 64,       /* the scalar-load control */
+    CHUB_CALL_CAPTURING = 128  /* between chub_graph_begin and chub_graph_end */
+};
+enum { CHUB_CALLPLAN_CALL = 0, CHUB_CALLPLAN_ONE, CHUB_CALLPLAN_SLOT, CHUB_CALLPLAN_LEVELS, CHUB_CALLPLAN_ENV, CHUB_CALLPLAN_COUNT };
+int chub_call_plan(const chub_config *cfg, int64_t n_envs, int rng_mode, const chub_options *opt /* NULL = defaults */, int env_params,
+                   uint32_t flags, int32_t *out);
+
 /* Scalar-load control mode: replaces EvcsspManagerEnv-level use of Fast/SlowChargeStation.evs_step(float)
  * (CHS.hpp:1169-1186 / 1480-1497, bound at main.cpp:196-197,248-249): one kW target per station instead of one bit per
  * pile; the piles are switched on in urgency order until the (clamped) target is met.  Same array layout as chub_step,
