@@ -21,6 +21,10 @@ TELEMETRY_NAMES = ["hy_act", "hy_flow_speed", "all_power_second", "Store_SOC", "
                    "min_power_0", "charge_power_0", "max_power_0", "line_0", "flow_in_0",
                    "min_power_1", "charge_power_1", "max_power_1", "line_1", "flow_in_1"]
 T = {name: i for i, name in enumerate(TELEMETRY_NAMES)}
+# the columns of the per-episode ledger (the CHUB_EP_* enum of include/chub.h, in order)
+EPISODE_NAMES = ["return", "income", "draw_ele", "length", "deviation", "test_penalty", "end_soc"]
+EP_COUNT = len(EPISODE_NAMES)
+EP = {name: i for i, name in enumerate(EPISODE_NAMES)}
 
 
 class ChubOptions(C.Structure):
@@ -122,6 +126,9 @@ def load_library():
         "chub_get_slots": (I, [P, P]), "chub_get_station_scalars": (I, [P, P]), "chub_get_telemetry": (I, [P, P]),
         "chub_get_obs_f64": (I, [P, P]), "chub_get_reward_f64": (I, [P, P]), "chub_set_telemetry": (I, [P, I]), "chub_fcev_stuck_count": (I, [P, P]),
         "chub_telemetry_host": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P)]),
+        "chub_set_episode_stats": (I, [P, I]), "chub_has_episode_stats": (I, [P]), "chub_get_episode_stats": (I, [P, I, P]),
+        "chub_get_episode_counts": (I, [P, P]), "chub_episode_stats_device": (I, [P, I, P, P, P]),
+        "chub_episode_summary_device": (I, [P, P, I, P]), "chub_episode_summary": (I, [P, P, I]),
         "chub_set_rng_compat_seeds": (I, [P, P]), "chub_set_rng_compat_state": (I, [P, P]),
         "chub_get_rng_compat_state": (I, [P, P]), "chub_compat_replay_constructor": (I, [P]), "chub_set_ou_state": (I, [P, P]),
         "chub_copy_envs": (I, [P, P, P, P, L]), "chub_copy_envs_device": (I, [P, P, P, P, L, P]),
@@ -171,7 +178,9 @@ EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "ch
             "chub_comm_max_f64", "chub_comm_barrier", "chub_comm_ranks_seen", "chub_comm_set_overlap", "chub_comm_gather_begin", "chub_comm_join", "chub_device_info", "chub_step_gather", "chub_run_steps", "chub_tape_register_soc", "chub_set_slots",
             "chub_set_station_queue", "chub_step_tape", "chub_reset_tape", "chub_tape_clear_soc", "chub_step_tape_env", "chub_reset_tape_env", "chub_telemetry_host", "chub_graph_begin", "chub_graph_end", "chub_graph_launch", "chub_graph_destroy",
             "chub_malloc_device", "chub_free_device", "chub_copy_to_host", "chub_copy_to_device", "chub_alloc_host", "chub_free_host", "chub_stream_create",
-            "chub_stream_destroy", "chub_stream_sync"]
+            "chub_stream_destroy", "chub_stream_sync",
+            "chub_set_episode_stats", "chub_has_episode_stats", "chub_get_episode_stats", "chub_get_episode_counts", "chub_episode_stats_device",
+            "chub_episode_summary_device", "chub_episode_summary"]
 
 
 def check(rc):

@@ -57,6 +57,10 @@ constexpr int kSlotsPerLane = CHUB_SLOTS_PER_LANE;  // packed slot kernel: slots
 constexpr int kBigBlock = CHUB_BIG_BLOCK, kBigSlotsPerLane = CHUB_BIG_SLOTS_PER_LANE;
 constexpr int kClsRow = 32;        // PHILOX: entries (power, t_soc) per arrival-SoC class = car_steps a car can take (stay_time <= 27 here)
 constexpr int kTelemCount = 38;
+constexpr int kEpCount = 7;        // columns of the per-episode ledger (the CHUB_EP_* enum of include/chub.h)
+constexpr int kEpSumBlock = 256;   // k_episode_summary: lanes per workgroup, ...
+constexpr int kEpSumMaxBlocks = 64;   // ... workgroups at most (each walks the envs with the grid's stride), and
+constexpr int kEpSumWords = 1 + 4 * kEpCount;  // f64 per partial and per result: count, then per column sum, sum of squares, min, max
 constexpr int kCompatSmallBlock = 512;  // k_compat_small: wave 0 walks the envs' streams, ...
 constexpr int kCompatSmallWaves0 = 3, kCompatSmallWaves1 = 4;  // ... these many waves hold station 0's / station 1's units
 
@@ -196,7 +200,7 @@ struct HubParams {
     int32_t obs_dim, act_dim;
     int32_t constant_charging;
     int32_t rng_mode;
-    int32_t telemetry;
+    int32_t telemetry;       // bit 0: the tail stores the telemetry block; bit 1: it keeps the per-episode ledger (EpisodeArrays::on)
     uint32_t key[2];
     CHUB_G(const uint32_t) tick_base;  // PHILOX: added to every launch's host tick (moves only when a captured graph of steps replays)
     CurveConsts cc;
@@ -233,6 +237,18 @@ struct EnvParamArrays {
     CHUB_G(const uint16_t) hv_idx;   // [96][1000] the arrival index n[t][level] behind Tables::cnt_hv: arrivals = clamp(roundf(hv_rate * n), 0, 255)
 };
 
+// The per-episode ledger (chub_set_episode_stats; null / 0 until it is first switched on).  Columns in the order of the CHUB_EP_* enum:
+// return, income, draw_ele, length (sums since the env's reset), deviation, test_penalty, end_soc (of the env's last step: MGR:275-297).
+enum EpCol { EPC_RETURN = 0, EPC_INCOME, EPC_DRAW_ELE, EPC_LENGTH, EPC_DEVIATION, EPC_TEST_PENALTY, EPC_END_SOC };
+struct EpisodeArrays {
+    int32_t on;                  // the ledger is kept (mirrored into bit 1 of HubParams::telemetry: the tail reads that word anyway)
+    int32_t pad_;
+    CHUB_G(double) live;         // [kEpCount][N] "as if the episode ended now": updated by every step, zeroed by whatever resets the env
+    CHUB_G(double) fin;          // [kEpCount][N] the live columns as the step whose `done` fired left them; no reset touches it
+    CHUB_G(uint32_t) episodes;   // [N] how many such steps the env has seen
+    CHUB_G(uint8_t) pending;     // [N] set with fin, cleared only by a draining summary (k_episode_summary)
+};
+
 // Everything a kernel needs that does not change from step to step, kept in device memory and passed by pointer
 // (as by-value kernel arguments these ~600 bytes were all loaded into SGPRs up front and spilled).
 struct DevCtx {
@@ -242,7 +258,8 @@ struct DevCtx {
     EnvArrays ev;
     CompatRng cr;
     Tables tb;
-    EnvParamArrays ep;  // (last: the offsets of everything above stay those of a homogeneous handle's kernels)
+    EnvParamArrays ep;  // (behind the rest: the offsets of everything above stay those of a homogeneous handle's kernels)
+    EpisodeArrays es;   // (... and behind ep for the same reason)
 };
 
 // chub_copy_envs: env dst_idx[i] of `dst` becomes a clone of env src_idx[i] of `src` (k_copy_envs; one wave per pair).  The two contexts may

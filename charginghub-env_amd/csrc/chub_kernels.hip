@@ -3020,7 +3020,12 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
     double st_pv = 0.0, st_wd = 0.0, st_hy = 0.0, st_pv_now = 0.0, st_wd_now = 0.0;
     uint32_t st_hv = 0;
     const double sin_t = multi ? tb.sin96[t_next] : ta.sin_t;  // the observation's time feature
-    const bool tel_on = hp.telemetry != 0;
+    // bit 0: telemetry; bit 1: the per-episode ledger (chub_set_episode_stats) -- EpisodeArrays::on, mirrored into this word so that the tail
+    // learns both from ONE scalar load in a cache line it reads anyway, not from a load of its own at the far end of the context in front
+    // of the per-env burst (the two compared: DESIGN 6.9)
+    const int32_t tel_word = hp.telemetry;
+    const bool tel_on = (tel_word & 1) != 0;
+    const bool ep_on = (tel_word & 2) != 0;
     if (!FUSED) {
         const int i = threadIdx.x;
         if (!multi) {  // lock-step: the rows of the launch's slot of the day
@@ -3253,6 +3258,11 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
         cap = HP_E(init_soc, p_init_soc) * cap_mass;
         store_soc = HP_E(init_soc, p_init_soc);
         CHUB_TEL(4, cap);
+        if (ep_on) {  // a new episode: the live block starts over (MGR:305-306); the finished block, the counter and the flag stay
+            CHUB_G(double) lv = ctx->es.live;
+#pragma unroll
+            for (int c = 0; c < kEpCount; c++) lv[(size_t) c * n32 + e32] = c == EPC_END_SOC ? store_soc : 0.0;
+        }
     } else {
         // What the previous make_state (MGR:344-361: the end of the previous step, or reset) produced for THIS slot is not kept as
         // state but re-derived, operation for operation, from what it was computed from: the table rows of this slot of the day,
@@ -3527,6 +3537,32 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
             // ev_power_list / ev_power_sum as the incomes and cumulated_draw_ele see them, after the fuel-cell rescale (MGR:219-224, 262)
             CHUB_TEL(24, e0); CHUB_TEL(25, e1); CHUB_TEL(26, ev_power_sum);
             CHUB_TEL(27, in_price_next);  // real_state[1] as this step found it: what real_price_dollar is a quarter of (MGR:234)
+        }
+        if (ep_on) {
+            // the episode ledger: cumulated_income / cumulated_draw_ele (MGR:259-262), acumulate_reward (MGR:269), deviation (MGR:297) and what
+            // the end-of-day block derives from it (MGR:275-290) "as if the episode ended now".  Plain divisions: the sums are held bit for bit
+            // to the same additions made on the host.  Where `done` fires (the expression further down) the step's live columns are the record
+            // of the finished episode.  An env stepped on past `done` keeps adding, as the reference object does.
+            CHUB_G(double) lv = ctx->es.live;
+            const size_t nn = n32, ee = e32;
+            const double init_soc = EP ? ctx->ep.prm[PRM_INIT_SOC * n32 + e32] : hp.init_soc;
+            double col[kEpCount];
+            col[EPC_RETURN] = lv[EPC_RETURN * nn + ee] + reward;
+            col[EPC_INCOME] = lv[EPC_INCOME * nn + ee] + (income_hys + income_evs + income_evs_serve + hy_cost);
+            col[EPC_DRAW_ELE] = lv[EPC_DRAW_ELE * nn + ee] + ((e0 + e1) + hydrogen_power);
+            col[EPC_LENGTH] = lv[EPC_LENGTH * nn + ee] + 1.0;
+            col[EPC_DEVIATION] = fabs(store_soc - init_soc);
+            col[EPC_TEST_PENALTY] = fabs(col[EPC_DEVIATION] * cap_mass / 1000 / 0.2);
+            col[EPC_END_SOC] = store_soc;
+#pragma unroll
+            for (int c = 0; c < kEpCount; c++) lv[c * nn + ee] = col[c];
+            if ((t_now + 1) >= 96) {
+                CHUB_G(double) fin = ctx->es.fin;
+#pragma unroll
+                for (int c = 0; c < kEpCount; c++) fin[c * nn + ee] = col[c];
+                ctx->es.episodes[ee] += 1u;
+                ctx->es.pending[ee] = 1;
+            }
         }
         }
     }
@@ -4933,6 +4969,8 @@ __global__ __launch_bounds__(256) void k_copy_envs(CopyArgs a) {
 
     // ---- the scalars, one per lane
     const bool rows = a.src->ep.prm && a.dst->ep.prm && a.src_rows && a.dst_rows;
+    const bool ledger = a.src->es.on && a.dst->es.on;
+    static_assert(kEpCount == 7 && PRM_COUNT <= 10, "k_copy_envs: lanes 18-24 / 25-31 take the ledger's columns, 32-41 the parameter row");
     switch (lane) {
     case 0: ed.cap[d] = es.cap[s]; break;
     case 1: ed.store_soc[d] = es.store_soc[s]; break;
@@ -4952,6 +4990,14 @@ __global__ __launch_bounds__(256) void k_copy_envs(CopyArgs a) {
     }
     case 16: if (LAYOUT == COPY_COMPAT) a.dst->cr.minstd3[a.dst_rng][d] = a.src->cr.minstd3[a.src_rng][s]; break;
     case 17: if (rows) ((CHUB_G(float)) a.dst->ep.hv_rate)[d] = a.src->ep.hv_rate[s]; break;
+    case 18: case 19: case 20: case 21: case 22: case 23: case 24:  // the episode ledger (the host has checked: on in both handles or in neither)
+        if (ledger) a.dst->es.live[(int64_t) (lane - 18u) * Nd + d] = a.src->es.live[(int64_t) (lane - 18u) * Ns + s];
+        break;
+    case 25: case 26: case 27: case 28: case 29: case 30: case 31:
+        if (ledger) a.dst->es.fin[(int64_t) (lane - 25u) * Nd + d] = a.src->es.fin[(int64_t) (lane - 25u) * Ns + s];
+        break;
+    case 42: if (ledger) a.dst->es.episodes[d] = a.src->es.episodes[s]; break;
+    case 43: if (ledger) a.dst->es.pending[d] = a.src->es.pending[s]; break;
     default:
         if (rows && lane >= 32u && lane < 32u + (uint32_t) PRM_COUNT)
             ((CHUB_G(double)) a.dst->ep.prm)[(int64_t) (lane - 32u) * Nd + d] = a.src->ep.prm[(int64_t) (lane - 32u) * Ns + s];
@@ -4968,6 +5014,113 @@ void launch_copy_envs(int layout, const CopyArgs &a, hipStream_t stream) {
     case COPY_CURVES: hipLaunchKernelGGL(k_copy_envs<COPY_CURVES>, grid, block, 0, stream, a); break;
     default: hipLaunchKernelGGL(k_copy_envs<COPY_PHILOX>, grid, block, 0, stream, a); break;
     }
+}
+
+// ---- chub_episode_summary: the finished episodes nobody has looked at yet, reduced on the device
+// k_episode_summary walks the envs (lane i of the grid takes envs i, i + lanes, ...: a fixed assignment), and for the envs whose pending flag is
+// set adds up the count and per column of the finished block the sum, the sum of squares, min and max; a wave combines its lanes with __shfl_down,
+// the workgroup its waves through LDS in wave order, and the workgroup's kEpSumWords partials go to the handle's buffer.
+// k_episode_summary_combine (one wave, a launch of its own behind it: a kernel boundary is the one hand-off between workgroups that needs no
+// fence) takes one partial per lane and combines them with the same tree.  No atomics anywhere and every order fixed: two calls on one state give the same bits.
+__device__ __forceinline__ void ep_sum_merge(double &cnt, double *v, double o_cnt, const double *o) {
+    cnt += o_cnt;
+#pragma unroll
+    for (int c = 0; c < kEpCount; c++) {
+        v[4 * c] += o[4 * c];
+        v[4 * c + 1] += o[4 * c + 1];
+        v[4 * c + 2] = o[4 * c + 2] < v[4 * c + 2] ? o[4 * c + 2] : v[4 * c + 2];
+        v[4 * c + 3] = o[4 * c + 3] > v[4 * c + 3] ? o[4 * c + 3] : v[4 * c + 3];
+    }
+}
+// lane l takes lane l + off, off = 32 .. 1: a fixed tree, after which lane 0 holds the wave's values
+__device__ __forceinline__ void ep_sum_wave(double &cnt, double *v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        double o[4 * kEpCount];
+        const double o_cnt = __shfl_down(cnt, off);
+#pragma unroll
+        for (int j = 0; j < 4 * kEpCount; j++) o[j] = __shfl_down(v[j], off);
+        ep_sum_merge(cnt, v, o_cnt, o);
+    }
+}
+__global__ __launch_bounds__(kEpSumBlock) void k_episode_summary(const DevCtx *__restrict__ ctx, double *__restrict__ partials, int drain) {
+    __shared__ double s_part[kEpSumBlock / 64][kEpSumWords];
+    const EpisodeArrays &es = ctx->es;
+    const int64_t N = ctx->hp.n_envs;
+    double cnt = 0.0, v[4 * kEpCount];
+#pragma unroll
+    for (int c = 0; c < kEpCount; c++) {
+        v[4 * c] = 0.0;
+        v[4 * c + 1] = 0.0;
+        v[4 * c + 2] = __builtin_huge_val();
+        v[4 * c + 3] = -__builtin_huge_val();
+    }
+    for (int64_t i = (int64_t) blockIdx.x * kEpSumBlock + threadIdx.x; i < N; i += (int64_t) gridDim.x * kEpSumBlock) {
+        if (!es.pending[i]) continue;
+        if (drain) es.pending[i] = 0;  // (the flag this lane has just read: nobody else looks at env i)
+        double x[4 * kEpCount];
+#pragma unroll
+        for (int c = 0; c < kEpCount; c++) {
+            const double f = es.fin[(int64_t) c * N + i];
+            x[4 * c] = f;
+            x[4 * c + 1] = f * f;
+            x[4 * c + 2] = f;
+            x[4 * c + 3] = f;
+        }
+        ep_sum_merge(cnt, v, 1.0, x);
+    }
+    ep_sum_wave(cnt, v);
+    const int wave = (int) (threadIdx.x >> 6);
+    if ((threadIdx.x & 63u) == 0u) {
+        s_part[wave][0] = cnt;
+#pragma unroll
+        for (int j = 0; j < 4 * kEpCount; j++) s_part[wave][1 + j] = v[j];
+    }
+    __syncthreads();
+    const int j = (int) threadIdx.x;
+    if (j < kEpSumWords) {  // word j of the workgroup's partial: the waves in order
+        const int kind = j == 0 ? 0 : (j - 1) & 3;
+        double r = s_part[0][j];
+        for (int w = 1; w < kEpSumBlock / 64; w++) {
+            const double o = s_part[w][j];
+            r = kind < 2 ? r + o : (kind == 2 ? (o < r ? o : r) : (o > r ? o : r));
+        }
+        partials[(size_t) blockIdx.x * kEpSumWords + j] = r;
+    }
+}
+// one wave: lane b holds workgroup b's partial (the identity beyond the grid), all its words requested at once, then the same fixed tree
+__global__ __launch_bounds__(64) void k_episode_summary_combine(const double *__restrict__ partials, int n_blocks, double *__restrict__ out) {
+    static_assert(kEpSumMaxBlocks <= 64, "k_episode_summary_combine: one lane per partial");
+    const int b = (int) threadIdx.x;
+    double cnt = 0.0, v[4 * kEpCount];
+#pragma unroll
+    for (int c = 0; c < kEpCount; c++) {
+        v[4 * c] = 0.0;
+        v[4 * c + 1] = 0.0;
+        v[4 * c + 2] = __builtin_huge_val();
+        v[4 * c + 3] = -__builtin_huge_val();
+    }
+    if (b < n_blocks) {
+        const double *p = partials + (size_t) b * kEpSumWords;
+        cnt = p[0];
+#pragma unroll
+        for (int j = 0; j < 4 * kEpCount; j++) v[j] = p[1 + j];
+    }
+    ep_sum_wave(cnt, v);
+    if (b == 0) {
+        out[0] = cnt;
+#pragma unroll
+        for (int j = 0; j < 4 * kEpCount; j++) out[1 + j] = v[j];
+    }
+}
+int episode_summary_blocks(int64_t n_envs) {
+    const int64_t nb = (n_envs + kEpSumBlock - 1) / kEpSumBlock;
+    return (int) (nb < 1 ? 1 : (nb > kEpSumMaxBlocks ? kEpSumMaxBlocks : nb));
+}
+void launch_episode_summary(const HubParams &hp, const DevCtx *ctx, double *d_partials, double *d_out, int drain, hipStream_t stream) {
+    const int nb = episode_summary_blocks(hp.n_envs);
+    hipLaunchKernelGGL(k_episode_summary, dim3((unsigned) nb), dim3(kEpSumBlock), 0, stream, ctx, d_partials, drain);
+    hipLaunchKernelGGL(k_episode_summary_combine, dim3(1), dim3(64), 0, stream, (const double *) d_partials, nb, d_out);
 }
 
 // chub_create, COMPAT handles: every entry of Tables::ttab against the device's own soc_to_time(uniform_level(l, 80, 100)) -- the expression

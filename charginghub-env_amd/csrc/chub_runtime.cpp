@@ -34,6 +34,7 @@ void launch_fill_clocks(uint16_t *dst, int64_t n, uint16_t value, hipStream_t st
 void launch_keep_clocks(uint16_t *dst, const uint16_t *src, int64_t n, hipStream_t stream);
 void launch_expand_bits(const HubParams &hp, const uint64_t *d_bits, const float *d_tail, float *d_actions, hipStream_t stream);
 void launch_copy_envs(int layout, const CopyArgs &a, hipStream_t stream);
+void launch_episode_summary(const HubParams &hp, const DevCtx *ctx, double *d_partials, double *d_out, int drain, hipStream_t stream);
 void launch_step_fused(const CallPlan &cp, const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, const PackedPtrs &pp,
                        hipEvent_t ev0, hipEvent_t ev1);
 template <bool RESET>
@@ -146,6 +147,11 @@ struct chub_env {
     int hv_max_arrive = 0;              // FCEV arrivals per step at most, over the rows at create: sizes qcap / hv_w (chub_set_env_params keeps below it)
     int hv_top[96];                     // the largest arrival index of each slot of the day (what that bound is computed from)
     EnvParamArrays ep = {nullptr, nullptr, nullptr};
+    // the per-episode ledger (chub_set_episode_stats): DevCtx::es points into ONE block outside the arena, allocated when the ledger is first
+    // switched on -- live [kEpCount][N] f64, finished [kEpCount][N] f64, episodes [N] u32, pending [N] u8 -- which snapshots carry behind the arena
+    EpisodeArrays es = {0, 0, nullptr, nullptr, nullptr, nullptr};
+    char *d_ledger = nullptr;
+    double *d_ep_sum = nullptr;  // k_episode_summary's partials [kEpSumMaxBlocks][kEpSumWords], then the host form's result [kEpSumWords]
     int public_mode = 0;     // the rng_mode the handle was created with: CHUB_RNG_PHILOX_CURVES is hp.rng_mode = PHILOX + hp.soc_curves
     bool tape_only = false;  // ... and once there are any, the handle's class rows are the caller's: only tape resets / steps may admit cars
     uint32_t h_late8[8];
@@ -416,7 +422,7 @@ static PackedPtrs packed_ptrs(const chub_env *e) {
 static int sync_ctx(chub_env *e, hipStream_t s) {
     if (!e->ctx_dirty) return 0;
     DevCtx h;
-    h.hp = e->hp; h.sl = e->sl; h.st = e->st; h.ev = e->ev; h.cr = e->cr; h.tb = e->tb; h.ep = e->ep;
+    h.hp = e->hp; h.sl = e->sl; h.st = e->st; h.ev = e->ev; h.cr = e->cr; h.tb = e->tb; h.ep = e->ep; h.es = e->es;
     HIP_TRY(hipStreamSynchronize(s));
     HIP_TRY(hipMemcpy(e->d_ctx, &h, sizeof h, hipMemcpyHostToDevice));
     e->ctx_dirty = false;
@@ -987,6 +993,8 @@ int chub_destroy(chub_env *e) {
         if (e->h_packed) (void) hipHostFree(e->h_packed);
         if (e->h_telem) (void) hipHostFree(e->h_telem);
         if (e->d_telem) (void) hipFree(e->d_telem);
+        if (e->d_ledger) (void) hipFree(e->d_ledger);
+        if (e->d_ep_sum) (void) hipFree(e->d_ep_sum);
         if (e->h_bits) (void) hipHostFree(e->h_bits);  // h_tail / d_tail are the ends of the same blocks
         if (e->d_bits) (void) hipFree(e->d_bits);
         if (e->d_packed) (void) hipFree(e->d_packed);
@@ -1626,7 +1634,7 @@ int chub_step_gather(chub_env *e, chub_comm *comm, const float *d_actions, float
 // into the packed block: no tape and no decision bits to look for.)
 static bool span_ok(const chub_env *e, int n_batches) {
     return e->plan.one_launch != ONE_NONE && e->plan.span_size_ok && e->plan.span_steps != 1 && !e->per_env && !e->prof_on && !e->tape_only &&
-           n_batches <= 8 && e->tick != 0 && !e->hp.telemetry;
+           n_batches <= 8 && e->tick != 0 && !e->hp.telemetry && !e->es.on;
 }
 
 static int run_span(chub_env *e, const float *const *batches, int n_batches, float *const *packed2, int64_t first, int k, hipStream_t s) {
@@ -1741,6 +1749,8 @@ static int copy_check_handles(const chub_env *dst, const chub_env *src) {
         return fail(CHUB_ERR_ARG, "chub_copy_envs: the two handles differ in station_list, station_type_list or constant_charging");
     if (src->env_params != dst->env_params)
         return fail(CHUB_ERR_ARG, "chub_copy_envs: one handle has per-env hub parameters (chub_create_params) and the other has none");
+    if ((src->es.on != 0) != (dst->es.on != 0))
+        return fail(CHUB_ERR_ARG, "chub_copy_envs: one handle keeps the episode ledger (chub_set_episode_stats) and the other does not");
     if (!src->env_params &&
         (a.hydro_prod_rate != b.hydro_prod_rate || a.hydro_store_vlt != b.hydro_store_vlt || a.init_soc != b.init_soc || a.fc_max_power != b.fc_max_power ||
          a.fcev_permeate != b.fcev_permeate || a.renew_fluctuate != b.renew_fluctuate || a.price_fluctuate != b.price_fluctuate || a.hydro_loss != b.hydro_loss))
@@ -2313,6 +2323,8 @@ int chub_stream_sync(int device, void *stream) {
 int chub_tape_register_soc(chub_env *e, const float *soc, int32_t count, uint32_t *class_ids) {
     if (!e || !soc || !class_ids || count < 0) return fail(CHUB_ERR_ARG, "bad argument");
     if (e->env_params) return refuse_params("tape mode (chub_tape_register_soc)");
+    if (e->es.on)  // (chub_set_episode_stats refuses a tape handle; a handle that keeps the ledger does not become one either)
+        return fail(CHUB_ERR_UNSUPPORTED, "tape mode on a handle that keeps the episode ledger: call chub_set_episode_stats(env, 0) first");
     if (e->hp.rng_mode != CHUB_RNG_PHILOX) return fail(CHUB_ERR_ARG, "tape mode needs a PHILOX handle");
     if (e->hp.soc_curves)
         return fail(CHUB_ERR_UNSUPPORTED, "rng_mode PHILOX_CURVES has no classes: its car tape carries each arrival SoC itself (f32 bits in .x)");
@@ -2674,7 +2686,7 @@ int chub_set_telemetry(chub_env *e, int enabled) {
         e->ev.obs64 = e->ev.telem + N * (size_t) kTelemCount;
         e->ev.reward64 = e->ev.obs64 + N * D;
     }
-    e->hp.telemetry = enabled ? 1 : 0;
+    e->hp.telemetry = (e->hp.telemetry & ~1) | (enabled ? 1 : 0);  // (bit 1 is the episode ledger's)
     e->ctx_dirty = true;
     return CHUB_OK;
 }
@@ -2730,6 +2742,93 @@ int chub_get_reward_f64(chub_env *e, double *out) {
     if (!e || !out) return fail(CHUB_ERR_ARG, "null argument");
     const size_t N = (size_t) e->hp.n_envs;
     return telem_fetch(e, N * (size_t) kTelemCount + N * (size_t) e->hp.obs_dim, N, out);
+}
+
+// ---- the per-episode ledger (include/chub.h: chub_set_episode_stats) ---------------------------------------------------------------------
+static size_t ledger_bytes(const chub_env *e) {
+    return (size_t) e->hp.n_envs * (2 * (size_t) kEpCount * sizeof(double) + sizeof(uint32_t) + sizeof(uint8_t));
+}
+int chub_set_episode_stats(chub_env *e, int enabled) {
+    if (!e) return fail(CHUB_ERR_ARG, "null handle");
+    if (e->tape_only) return fail(CHUB_ERR_UNSUPPORTED, "chub_set_episode_stats is not supported on a tape handle (chub_tape_register_soc)");
+    if (e->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_set_episode_stats between chub_graph_begin and chub_graph_end (call it between replays)");
+    HIP_TRY(hipSetDevice(e->device));
+    if (enabled && !e->es.on) {
+        const size_t N = (size_t) e->hp.n_envs;
+        if (!e->d_ep_sum) HIP_TRY(hipMalloc((void **) &e->d_ep_sum, ((size_t) kEpSumMaxBlocks + 1) * kEpSumWords * sizeof(double)));
+        if (!e->d_ledger) HIP_TRY(hipMalloc((void **) &e->d_ledger, ledger_bytes(e)));
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemset(e->d_ledger, 0, ledger_bytes(e)));  // counting starts with the next call
+        e->es.live = (double *) e->d_ledger;
+        e->es.fin = e->es.live + (size_t) kEpCount * N;
+        e->es.episodes = (uint32_t *) (e->es.fin + (size_t) kEpCount * N);
+        e->es.pending = (uint8_t *) (e->es.episodes + N);
+    }
+    e->es.on = enabled ? 1 : 0;
+    e->hp.telemetry = (e->hp.telemetry & ~2) | (enabled ? 2 : 0);  // what the tail reads: one word for both flags
+    e->ctx_dirty = true;
+    return CHUB_OK;
+}
+
+int chub_has_episode_stats(const chub_env *e) { return e ? e->es.on : CHUB_ERR_ARG; }
+
+static int need_ledger(const chub_env *e) {
+    if (!e->es.on) return fail(CHUB_ERR_ARG, "the episode ledger is off: call chub_set_episode_stats(env, 1) first");
+    return 0;
+}
+
+int chub_get_episode_stats(chub_env *e, int finished, double *out) {
+    if (!e || !out) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = need_ledger(e)) return rc;
+    const size_t N = (size_t) e->hp.n_envs;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<double> t;
+    if (const int rc = fetch(t, (const double *) (finished ? e->es.fin : e->es.live), (size_t) kEpCount * N)) return rc;
+    for (size_t env = 0; env < N; env++)
+        for (int c = 0; c < kEpCount; c++) out[env * kEpCount + c] = t[(size_t) c * N + env];
+    return CHUB_OK;
+}
+
+int chub_get_episode_counts(chub_env *e, uint32_t *out) {
+    if (!e || !out) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = need_ledger(e)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, e->es.episodes, (size_t) e->hp.n_envs * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return CHUB_OK;
+}
+
+int chub_episode_stats_device(chub_env *e, int finished, double *d_out, uint32_t *d_counts, void *stream) {
+    if (!e || !d_out) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = need_ledger(e)) return rc;
+    const size_t N = (size_t) e->hp.n_envs;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMemcpyAsync(d_out, finished ? e->es.fin : e->es.live, (size_t) kEpCount * N * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t) stream));
+    if (d_counts) HIP_TRY(hipMemcpyAsync(d_counts, e->es.episodes, N * sizeof(uint32_t), hipMemcpyDeviceToDevice, (hipStream_t) stream));
+    return CHUB_OK;
+}
+
+int chub_episode_summary_device(chub_env *e, double *d_out, int drain, void *stream) {
+    if (!e || !d_out) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = need_ledger(e)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    if (const int rc = sync_ctx(e, (hipStream_t) stream)) return rc;
+    launch_episode_summary(e->hp, e->d_ctx, e->d_ep_sum, d_out, drain, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_episode_summary(chub_env *e, double *out, int drain) {
+    if (!e || !out) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = need_ledger(e)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());  // (steps in flight on any stream write the ledger)
+    double *d_res = e->d_ep_sum + (size_t) kEpSumMaxBlocks * kEpSumWords;
+    if (const int rc = chub_episode_summary_device(e, d_res, drain, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(out, d_res, kEpSumWords * sizeof(double), hipMemcpyDeviceToHost));
+    return CHUB_OK;
 }
 
 int chub_set_rng_compat_seeds(chub_env *e, const uint32_t *seeds) {
@@ -2877,14 +2976,15 @@ struct SnapshotHeader {
     // per-env clocks (the clocks themselves are in the arena); the blob ends with every env's last tick
     int32_t predrawn, per_env;
     int32_t rng_cur;  // COMPAT: which of the arena's three stream buffers holds the committed streams
-    int32_t pad_;     // 1: taken from a handle with per-env hub parameters (0 otherwise: a homogeneous handle's blob is unchanged)
+    int32_t pad_;     // bit 0: taken from a handle with per-env hub parameters, bit 1: with the episode ledger on -- its block then ends the blob
+                      // (0 otherwise: the blob of a homogeneous handle without the ledger is unchanged)
 };
 static const uint64_t kSnapMagic = 0x43485542534e4150ull;  // "CHUBSNAP"
 
 int64_t chub_state_size(const chub_env *e) {
     if (!e) return fail(CHUB_ERR_ARG, "null handle");
     if (!e->arena) return fail(CHUB_ERR_UNSUPPORTED, "snapshot needs the single-arena allocation (CHUB_NO_ARENA is set)");
-    return (int64_t) (sizeof(SnapshotHeader) + e->arena_used + (size_t) e->hp.n_envs * sizeof(uint32_t));
+    return (int64_t) (sizeof(SnapshotHeader) + e->arena_used + (size_t) e->hp.n_envs * sizeof(uint32_t) + (e->es.on ? ledger_bytes(e) : 0));
 }
 
 int chub_get_state(chub_env *e, void *buf, int64_t size) {
@@ -2910,7 +3010,7 @@ int chub_get_state(chub_env *e, void *buf, int64_t size) {
     h.predrawn = e->predrawn ? 1 : 0;
     h.per_env = e->per_env ? 1 : 0;
     h.rng_cur = e->rng_cur;
-    h.pad_ = e->env_params ? 1 : 0;  // (the rows themselves are in the arena)
+    h.pad_ = (e->env_params ? 1 : 0) | (e->es.on ? 2 : 0);  // (the rows themselves are in the arena)
     memcpy(buf, &h, sizeof h);
     HIP_TRY(hipMemcpy((char *) buf + sizeof h, e->arena, e->arena_used, hipMemcpyDeviceToHost));
     {
@@ -2920,6 +3020,8 @@ int chub_get_state(chub_env *e, void *buf, int64_t size) {
         int rc = chub_env_clocks(e, t.data(), tk.data());
         if (rc) return rc;
         memcpy((char *) buf + sizeof h + e->arena_used, tk.data(), N * sizeof(uint32_t));
+        if (e->es.on)
+            HIP_TRY(hipMemcpy((char *) buf + sizeof h + e->arena_used + N * sizeof(uint32_t), e->d_ledger, ledger_bytes(e), hipMemcpyDeviceToHost));
     }
     return CHUB_OK;
 }
@@ -2933,12 +3035,16 @@ int chub_set_state(chub_env *e, const void *buf, int64_t size) {
     if (size < (int64_t) sizeof h) return fail(CHUB_ERR_ARG, "snapshot truncated");
     memcpy(&h, buf, sizeof h);
     if (h.magic != kSnapMagic) return fail(CHUB_ERR_ARG, "not a chub snapshot");
-    if ((h.pad_ != 0) != e->env_params)
+    if (((h.pad_ & 1) != 0) != e->env_params)
         return fail(CHUB_ERR_ARG, e->env_params ? "snapshot was taken from a handle without per-env hub parameters"
                                                 : "snapshot was taken from a handle with per-env hub parameters (chub_create_params)");
+    if (((h.pad_ & 2) != 0) != (e->es.on != 0))
+        return fail(CHUB_ERR_ARG, e->es.on ? "snapshot was taken from a handle without the episode ledger (chub_set_episode_stats)"
+                                           : "snapshot was taken from a handle with the episode ledger on (chub_set_episode_stats)");
     if (h.n_envs != e->hp.n_envs || h.env_id0 != e->hp.env_id0 || h.rng_mode != e->public_mode ||
         memcmp(&h.cfg, &e->cfg, sizeof h.cfg) != 0 || h.arena_used != e->arena_used || size < need)
         return fail(CHUB_ERR_ARG, "snapshot was taken from a handle with a different configuration");
+    if (h.rng_cur < 0 || h.rng_cur > 2) return fail(CHUB_ERR_ARG, "snapshot header is corrupt");  // (every header check comes before the first write)
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
     // device pointers inside the arena are position-dependent: restore only into the handle's own layout, which the
@@ -2946,7 +3052,6 @@ int chub_set_state(chub_env *e, const void *buf, int64_t size) {
     HIP_TRY(hipMemcpy(e->arena, (const char *) buf + sizeof h, e->arena_used, hipMemcpyHostToDevice));
     e->empt_valid = false;  // (the restored slot state has not been counted)
     e->e2_tick = ~0u;       // (... nor has any pass left empt2 for a walk two steps ahead)
-    if (h.rng_cur < 0 || h.rng_cur > 2) return fail(CHUB_ERR_ARG, "snapshot header is corrupt");
     e->rng_cur = h.rng_cur;
     e->t = h.t;
     e->price_count = h.price_count;
@@ -2960,6 +3065,8 @@ int chub_set_state(chub_env *e, const void *buf, int64_t size) {
         e->per_env = h.per_env != 0;
         e->h_tick.resize(N);
         memcpy(e->h_tick.data(), (const char *) buf + sizeof h + e->arena_used, N * sizeof(uint32_t));
+        if (e->es.on)
+            HIP_TRY(hipMemcpy(e->d_ledger, (const char *) buf + sizeof h + e->arena_used + N * sizeof(uint32_t), ledger_bytes(e), hipMemcpyHostToDevice));
         e->full_tick = 0;  // per env, from the blob
     }
     return CHUB_OK;

@@ -91,6 +91,19 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def summary_dict(raw):
+    """chub_episode_summary's [1 + 4 * EP_COUNT] doubles -> {"count": n, name: {"mean", "std", "min", "max"}}"""
+    raw = np.asarray(raw, dtype=np.float64)
+    n = int(raw[0])
+    out = {"count": n}
+    for i, name in enumerate(_lib.EPISODE_NAMES):
+        s, ss, lo, hi = (float(v) for v in raw[1 + 4 * i:5 + 4 * i])
+        mean = s / n if n else float("nan")
+        var = max(ss / n - mean * mean, 0.0) if n else float("nan")
+        out[name] = {"mean": mean, "std": var ** 0.5, "min": lo, "max": hi}
+    return out
+
+
 class VecChargingHub(object):
     def __init__(self, n_envs, station_list, station_type_list, seed=0, rng="philox", device=0, env_id0=0,
                  data_dir=None, slot_kernel="auto", no_arena=False, copy_outputs=True, fused_step="auto", tile="auto", walk_ahead="auto",
@@ -501,6 +514,51 @@ class VecChargingHub(object):
         out = np.zeros(self.n_envs, dtype=np.float64)
         check(self._lib.chub_get_reward_f64(self._h, _ptr(out)))
         return out
+
+    # ---- per-episode accounting on the device (chub_set_episode_stats): the reference's end-of-day ledger (MGR:259-297), one per env
+    def set_episode_stats(self, on=True):
+        """keep the per-episode ledger: return, income, electricity drawn, length, and the tank's deviation / test_penalty / SOC as of the
+        env's last step (_lib.EPISODE_NAMES).  Off by default; switching on zeroes everything and counting starts with the next call."""
+        check(self._lib.chub_set_episode_stats(self._h, int(bool(on))))
+
+    @property
+    def has_episode_stats(self):
+        return self._lib.chub_has_episode_stats(self._h) == 1
+
+    def episode_stats(self, finished=False):
+        """{name: float64 [n_envs]} over _lib.EPISODE_NAMES: the running episode of every env ("as if it ended now"), or with finished=True
+        the record of the env's last finished episode (zeros until it has finished one: see episode_counts()).  Synchronises."""
+        out = np.zeros((self.n_envs, _lib.EP_COUNT), dtype=np.float64)
+        check(self._lib.chub_get_episode_stats(self._h, int(bool(finished)), _ptr(out)))
+        return {name: out[:, i].copy() for i, name in enumerate(_lib.EPISODE_NAMES)}
+
+    def episode_counts(self):
+        """uint32 [n_envs]: the episodes every env has finished since the ledger was switched on"""
+        out = np.zeros(self.n_envs, dtype=np.uint32)
+        check(self._lib.chub_get_episode_counts(self._h, _ptr(out)))
+        return out
+
+    def episode_stats_device(self, d_out, d_counts=0, finished=True, stream=0):
+        """the live / finished block into device memory, d_out [EP_COUNT, N] f64 (column-major, as stored) and optionally d_counts [N] u32:
+        device-to-device copies on `stream`, no synchronisation, recordable into a graph"""
+        check(self._lib.chub_episode_stats_device(self._h, int(bool(finished)), d_out, d_counts or None, stream or None))
+
+    def episode_summary_device(self, d_out, drain=True, stream=0):
+        """the finished episodes nobody has looked at yet (the envs whose pending flag is set), reduced on the device into d_out
+        [1 + 4 * EP_COUNT] f64: count, then per column sum, sum of squares, min, max; drain clears the flags.  No synchronisation."""
+        check(self._lib.chub_episode_summary_device(self._h, d_out, int(bool(drain)), stream or None))
+
+    def episode_summary_raw(self, drain=True):
+        """episode_summary_device into host memory: float64 [1 + 4 * EP_COUNT].  Synchronises."""
+        out = np.zeros(1 + 4 * _lib.EP_COUNT, dtype=np.float64)
+        check(self._lib.chub_episode_summary(self._h, _ptr(out), int(bool(drain))))
+        return out
+
+    def episode_summary(self, drain=True):
+        """{"count": n, name: {"mean", "std", "min", "max"}} over the episodes that ended since the last draining call (what a trainer logs):
+        29 doubles cross the bus instead of a [N, EP_COUNT] block.  mean and std (population) are computed here from sum and sum of squares;
+        with count 0 they are NaN, min +inf and max -inf."""
+        return summary_dict(self.episode_summary_raw(drain))
 
     def fcev_stuck_count(self):
         """envs whose FCEV forecourt is stuck: no prefix of its waiting list fits into 15 minutes any more, so -- as in the

@@ -115,7 +115,7 @@ def _spaces(vec, data_dir=None):
 class _HubBatch(object):
     """shared by the two vector conventions: owns (or borrows) a VecChargingHub, counts steps, applies the limit"""
 
-    def __init__(self, vec=None, n_envs=None, max_episode_steps=None, telemetry=False, data_dir=None, **hub_kwargs):
+    def __init__(self, vec=None, n_envs=None, max_episode_steps=None, telemetry=False, data_dir=None, episode_stats=False, **hub_kwargs):
         if vec is None:
             if n_envs is None:
                 raise ValueError("give either vec= or n_envs= and the hub kwargs")
@@ -128,6 +128,9 @@ class _HubBatch(object):
         self.telemetry = bool(telemetry)
         if self.telemetry:
             vec.set_telemetry(True)
+        self.episode_stats = bool(episode_stats)
+        if self.episode_stats:  # the per-episode ledger on the device (chub_set_episode_stats)
+            vec.set_episode_stats(True)
         self._elapsed = 0
         self.metadata = EvcsspManagerEnv_v6.metadata
         self.reward_range = (-float("inf"), float("inf"))
@@ -159,10 +162,14 @@ class HubVecEnv(_HubBatch):
     ``step_wait`` returns ``(obs, rewards, dones, infos)``; when the episode ends (all envs at once) the envs are reset,
     the returned ``obs`` is the first observation of the next episode and ``infos[i]['terminal_observation']`` holds the
     last one of the finished episode; ``infos[i]['TimeLimit.truncated']`` marks an end forced by ``max_episode_steps``.
+    ``episode_stats=True`` (off by default: the infos are then exactly the above) switches the hub's per-episode ledger on, and the
+    ``infos[i]`` of an env whose episode ended carries ``episode = {"r": return, "l": length, "income", "draw_ele", "test_penalty",
+    "end_soc"}`` (``r`` and ``l`` as stable-baselines' ``Monitor`` writes them; the others the reference's end-of-day ledger,
+    MGR:275-297) -- read from the hub's live block before the reset, so an episode the time limit cut short reports what it had.
     """
 
-    def __init__(self, vec=None, n_envs=None, max_episode_steps=None, telemetry=False, **hub_kwargs):
-        _HubBatch.__init__(self, vec, n_envs, max_episode_steps, telemetry, **hub_kwargs)
+    def __init__(self, vec=None, n_envs=None, max_episode_steps=None, telemetry=False, episode_stats=False, **hub_kwargs):
+        _HubBatch.__init__(self, vec, n_envs, max_episode_steps, telemetry, episode_stats=episode_stats, **hub_kwargs)
         self._pending = None
 
     def reset(self):
@@ -182,9 +189,14 @@ class HubVecEnv(_HubBatch):
                     infos[i][name] = col[i]
         if dones.any():
             # lock-step clock: the episode ends for every env in the same step
+            ep = self.vec.episode_stats(finished=False) if self.episode_stats else None
             for i in range(self.num_envs):
                 infos[i]["terminal_observation"] = obs[i]
                 infos[i]["TimeLimit.truncated"] = bool(truncated[i])
+                if ep is not None:
+                    infos[i]["episode"] = {"r": float(ep["return"][i]), "l": int(ep["length"][i]), "income": float(ep["income"][i]),
+                                           "draw_ele": float(ep["draw_ele"][i]), "test_penalty": float(ep["test_penalty"][i]),
+                                           "end_soc": float(ep["end_soc"][i])}
             obs = self._reset()
             dones = np.ones(self.num_envs, dtype=bool)
         return obs, reward, dones, infos
@@ -250,9 +262,13 @@ class TorchHubVecEnv(object):
     own clock and whoever finishes is reset on the device, in the same call -- so ``done`` is the per-env flag, ``last_obs`` is a
     fixed [N, D] buffer whose rows are valid where ``done`` (the terminal observations), and envs cloned in from an adapter at
     another time of day (``copy_envs``) simply keep their own days.  Nothing in that path reads the device or waits for it.
-    ``step_bits`` is refused in this mode (the auto-reset call takes action rows).  ``device`` is a CUDA ordinal or a ``torch.device``."""
+    ``step_bits`` is refused in this mode (the auto-reset call takes action rows).  ``device`` is a CUDA ordinal or a ``torch.device``.
 
-    def __init__(self, n_envs, station_list, station_type_list, seed=0, device=0, autoreset=True, **hub_kwargs):
+    ``episode_stats=True`` switches the hub's per-episode ledger on (chub_set_episode_stats): ``episode_stats()`` and
+    ``episode_summary()`` then give every env's finished-episode record, or its reduction over the episodes that ended since the last
+    look, as CUDA tensors filled on torch's stream -- no device read, no wait, whatever the envs' clocks are."""
+
+    def __init__(self, n_envs, station_list, station_type_list, seed=0, device=0, autoreset=True, episode_stats=False, **hub_kwargs):
         import torch  # before libchub is loaded by VecChargingHub: both must share one HIP runtime
 
         if not (autoreset is True or autoreset is False or autoreset == "per_env"):
@@ -273,6 +289,34 @@ class TorchHubVecEnv(object):
             self.last_obs = torch.zeros((self.num_envs, self.obs_dim), dtype=torch.float32, device=self.device)
         self._cur_obs = None  # the observation rows the last reset / step returned
         self._t = 0
+        self._ep_block = self._ep_counts = self._ep_summary = None
+        if episode_stats:
+            self.vec.set_episode_stats(True)
+            self._ep_block = torch.zeros((_lib.EP_COUNT, self.num_envs), dtype=torch.float64, device=self.device)
+            self._ep_counts = torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device)  # (the handle's u32 words)
+            self._ep_summary = torch.zeros((1 + 4 * _lib.EP_COUNT,), dtype=torch.float64, device=self.device)
+
+    def _need_episode_stats(self):
+        if self._ep_block is None:
+            raise RuntimeError("the episode ledger is off: construct with episode_stats=True")
+
+    def episode_stats(self, finished=True):
+        """{name: float64 [N] CUDA tensor} over _lib.EPISODE_NAMES plus "episodes" (int32 [N]: finished episodes per env): the record of
+        every env's last finished episode (finished=False: its running one), copied on the device on torch's current stream.  The tensors
+        are views of one buffer the next call overwrites."""
+        self._need_episode_stats()
+        self.vec.episode_stats_device(self._ep_block.data_ptr(), self._ep_counts.data_ptr(), finished=finished, stream=self._stream())
+        out = {name: self._ep_block[i] for i, name in enumerate(_lib.EPISODE_NAMES)}
+        out["episodes"] = self._ep_counts
+        return out
+
+    def episode_summary(self, drain=True):
+        """float64 [1 + 4 * EP_COUNT] CUDA tensor over the episodes that ended since the last draining call: their count, then per column
+        of _lib.EPISODE_NAMES sum, sum of squares, min, max -- reduced on the device on torch's current stream, without waiting
+        (charginghub_env_amd.vec_env.summary_dict turns its host copy into means and deviations).  The next call overwrites it."""
+        self._need_episode_stats()
+        self.vec.episode_summary_device(self._ep_summary.data_ptr(), drain=drain, stream=self._stream())
+        return self._ep_summary
 
     def _stream(self):
         if self.device.type != "cuda":

@@ -428,7 +428,8 @@ int chub_step_gather(chub_env *env, chub_comm *comm, const float *d_actions, flo
  * runs the one-launch step (chub_uses_fused_step: small batches) and with at most 8 action batches, consecutive lock-step steps go out as
  * ONE launch per span (k_steps_piped / k_steps_fused; chub_options.span_steps, span_tails) -- a span ends where the call does, at a reset and where the handle's clock
  * wraps; only the span's last two packed blocks exist afterwards, as after the same steps issued one by one.  Not under the per-kernel
- * profiler, with telemetry on, with a tape loaded or on per-env clocks: every step is then a launch of its own. */
+ * profiler, with telemetry on, with the episode ledger on (chub_set_episode_stats), with a tape loaded or on per-env clocks: every step is
+ * then a launch of its own. */
 int chub_run_steps(chub_env *env, chub_comm *comm, const float *const *d_action_batches, int n_batches, float *const *d_packed2,
                    float *const *d_gathered2, float *d_reset_obs, int64_t first_step, int64_t n_steps, void *stream);
 
@@ -462,6 +463,59 @@ int chub_set_telemetry(chub_env *env, int enabled); /* off by default: the hot p
  * device-pointer call: chub_sync / a stream synchronise).  This is how EvcsspManagerEnv_v6.step() reads everything the reference
  * class exposes after a step (MGR:183-297, 364-372) without one device read. */
 int chub_telemetry_host(chub_env *env, double **telem, double **obs64, double **reward64);
+
+/* ---- per-episode accounting on the device ---------------------------------------------------------------------------------------
+ * The reference keeps a ledger per episode: cumulated_income and cumulated_draw_ele are zeroed in reset() (MGR:305-306) and added to in
+ * every step() (MGR:259-262), acumulate_reward runs over the steps (MGR:269), deviation is the tank's distance from init_soc after every
+ * step (MGR:297), and the step that ends the day derives test_penalty from it (MGR:275-290).  With the ledger on, the step's per-env tail
+ * keeps the same columns per env in device memory -- in every launch form, in all three RNG modes, lock-step, masked or auto-reset:
+ *   CHUB_EP_RETURN        += the step's reward in f64, before the f32 narrowing (CHUB_T_REWARD)                     0 at reset
+ *   CHUB_EP_INCOME        += CHUB_T_INCOME                                                                         0 at reset
+ *   CHUB_EP_DRAW_ELE      += (CHUB_T_EV0_NET + CHUB_T_EV1_NET) + CHUB_T_HYDROGEN_POWER (MGR:262)                   0 at reset
+ *   CHUB_EP_LENGTH        += 1                                                                                     0 at reset
+ *   CHUB_EP_DEVIATION     abs(Store_SOC - init_soc) of the last step (CHUB_T_STORE_SOC: stale after the fuel cell) 0 at reset
+ *   CHUB_EP_TEST_PENALTY  abs(abs(Store_SOC - init_soc) * capacity_mass / 1000 / 0.2) of the last step             0 at reset
+ *   CHUB_EP_END_SOC       Store_SOC of the last step                                                               the reset's SOC
+ * (init_soc and capacity_mass are the env's own on a handle made by chub_create_params).  Two blocks and two per-env words:
+ *   live      the columns above, "as if the episode ended now"; zeroed by whatever resets the env (chub_reset*, masked and device-mask
+ *             resets, the reset half of chub_autoreset_step_device).  An env stepped on past `done` without a reset keeps accumulating, as
+ *             the reference object does.  A masked call updates only the envs it serves.
+ *   finished  a copy of the env's live columns taken in the step whose `done` fired; no reset touches it
+ *   episodes  u32: how many such steps the env has seen
+ *   pending   u8: set with the finished block, cleared only by a draining summary call
+ * The additions are IEEE f64 in step order: the sums equal, bit for bit, what a host gets by adding the same handle's telemetry columns.
+ *   chub_set_episode_stats: off by default -- a handle that never asks pays one uniform branch per tail.  Switching on allocates (outside the
+ *       arena) and zeroes everything; counting starts with the next call.  CHUB_ERR_UNSUPPORTED on tape handles and between chub_graph_begin
+ *       and chub_graph_end; it takes effect for a captured graph's next replay, as chub_set_telemetry does.  With the ledger on chub_run_steps
+ *       issues its steps one by one (as with telemetry on); single one-launch steps keep their form.  While the ledger is on
+ *       chub_tape_register_soc is CHUB_ERR_UNSUPPORTED too (switch it off first): no handle is a tape handle and keeps the ledger.
+ *   chub_get_episode_stats: host memory, out [N][CHUB_EP_COUNT]; finished = 0 selects the live block, 1 the finished one.  Synchronises.
+ *   chub_get_episode_counts: host memory, out [N].  Synchronises.
+ *   chub_episode_stats_device: d_out [CHUB_EP_COUNT][N] (column-major, as stored), d_counts [N] or NULL: device-to-device copies enqueued on
+ *       `stream`.  Recordable into a graph; no synchronisation.
+ *   chub_episode_summary_device: over the envs whose pending flag is set, d_out [1 + 4 * CHUB_EP_COUNT] f64 in the caller's device memory:
+ *       their count, then per column of the finished block sum, sum of squares, min, max (count 0: sums 0, min +inf, max -inf).  drain != 0
+ *       clears the flags it read.  Two launches on `stream` (per-workgroup partials, then their sum in workgroup order): no atomics, every
+ *       order fixed, so two calls on one state give identical bits.  Recordable into a graph; no synchronisation.  The partials live in ONE
+ *       buffer owned by the handle (the host form uses it too): summary calls on one handle must be ordered against each other -- the same
+ *       stream, or an event between them -- as they must be against the steps that write the ledger.  Two of them in flight on different
+ *       streams race on that buffer.
+ *   chub_episode_summary: the same into host memory.  Synchronises.
+ * All of them but the first two return CHUB_ERR_ARG with a message while the ledger is off.  Snapshots carry the four arrays when the ledger
+ * is on (chub_state_size grows by exactly their bytes); one taken with the ledger on is refused by a handle with it off and the other way
+ * round, with nothing written.  chub_copy_envs* copies an env's live block, finished block, count and flag with the rest of its state; a copy
+ * between a handle with the ledger on and one with it off is CHUB_ERR_ARG. */
+enum {
+    CHUB_EP_RETURN = 0, CHUB_EP_INCOME, CHUB_EP_DRAW_ELE, CHUB_EP_LENGTH, CHUB_EP_DEVIATION, CHUB_EP_TEST_PENALTY, CHUB_EP_END_SOC,
+    CHUB_EP_COUNT
+};
+int chub_set_episode_stats(chub_env *env, int enabled);
+int chub_has_episode_stats(const chub_env *env);
+int chub_get_episode_stats(chub_env *env, int finished, double *out);
+int chub_get_episode_counts(chub_env *env, uint32_t *out);
+int chub_episode_stats_device(chub_env *env, int finished, double *d_out, uint32_t *d_counts, void *stream);
+int chub_episode_summary_device(chub_env *env, double *d_out, int drain, void *stream);
+int chub_episode_summary(chub_env *env, double *out, int drain);
 
 /* The FCEV waiting list is unbounded as in the reference (HYD:264-265): the entries a list that still gets served can
  * hold are kept one by one, and once no prefix of it fits into 15 minutes any more (HYD:270-276: nobody is served again
