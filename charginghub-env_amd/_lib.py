@@ -25,6 +25,36 @@ T = {name: i for i, name in enumerate(TELEMETRY_NAMES)}
 EPISODE_NAMES = ["return", "income", "draw_ele", "length", "deviation", "test_penalty", "end_soc"]
 EP_COUNT = len(EPISODE_NAMES)
 EP = {name: i for i, name in enumerate(EPISODE_NAMES)}
+# the per-pile columns of chub_pile_obs_device (the CHUB_PILE_* enum of include/chub.h, in order: chub_get_slots' nine fields)
+PILE_NAMES = ("car", "charge", "emergency", "power", "soc", "init_soc", "target_soc", "stay_time", "already_stay_time")
+PILE_COUNT = len(PILE_NAMES)
+PILE = {name: i for i, name in enumerate(PILE_NAMES)}
+
+
+def pile_fields_mask(fields=None):
+    """a field set of chub_pile_obs_device as its bit mask: None = all nine, an int = the mask itself, else a sequence of PILE_NAMES"""
+    if fields is None:
+        return (1 << PILE_COUNT) - 1
+    if hasattr(fields, "__index__"):  # (an int of any kind)
+        fields = fields.__index__()
+        if fields <= 0 or fields >> PILE_COUNT:
+            raise ValueError("fields: a non-empty mask over the %d per-pile fields, got %#x" % (PILE_COUNT, fields))
+        return fields
+    if isinstance(fields, str):
+        fields = (fields,)
+    mask = 0
+    for name in fields:
+        if name not in PILE:
+            raise ValueError("unknown per-pile field %r (one of %s)" % (name, ", ".join(PILE_NAMES)))
+        mask |= 1 << PILE[name]
+    if not mask:
+        raise ValueError("fields: at least one per-pile field")
+    return mask
+
+
+def pile_fields_names(mask):
+    """the columns a mask selects, in the order they come out (ascending field order)"""
+    return tuple(name for i, name in enumerate(PILE_NAMES) if mask >> i & 1)
 
 
 class ChubOptions(C.Structure):
@@ -129,6 +159,7 @@ def load_library():
         "chub_set_episode_stats": (I, [P, I]), "chub_has_episode_stats": (I, [P]), "chub_get_episode_stats": (I, [P, I, P]),
         "chub_get_episode_counts": (I, [P, P]), "chub_episode_stats_device": (I, [P, I, P, P, P]),
         "chub_episode_summary_device": (I, [P, P, I, P]), "chub_episode_summary": (I, [P, P, I]),
+        "chub_pile_obs_columns": (I, [C.c_uint32]), "chub_pile_obs_device": (I, [P, C.c_uint32, P, P, P]),
         "chub_set_rng_compat_seeds": (I, [P, P]), "chub_set_rng_compat_state": (I, [P, P]),
         "chub_get_rng_compat_state": (I, [P, P]), "chub_compat_replay_constructor": (I, [P]), "chub_set_ou_state": (I, [P, P]),
         "chub_copy_envs": (I, [P, P, P, P, L]), "chub_copy_envs_device": (I, [P, P, P, P, L, P]),
@@ -180,7 +211,7 @@ EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "ch
             "chub_malloc_device", "chub_free_device", "chub_copy_to_host", "chub_copy_to_device", "chub_alloc_host", "chub_free_host", "chub_stream_create",
             "chub_stream_destroy", "chub_stream_sync",
             "chub_set_episode_stats", "chub_has_episode_stats", "chub_get_episode_stats", "chub_get_episode_counts", "chub_episode_stats_device",
-            "chub_episode_summary_device", "chub_episode_summary"]
+            "chub_episode_summary_device", "chub_episode_summary", "chub_pile_obs_columns", "chub_pile_obs_device"]
 
 
 def check(rc):

@@ -4441,6 +4441,15 @@ __global__ void k_random_actions(int64_t n_envs, int64_t env_id0, int act_dim, u
 // (hot.w bits 25-31) instead of storing the SoC every step: the SoC after n steps is the same deterministic chain
 // soc -> soc_to_time -> +1 slot -> time_to_soc the step evaluated (CHS.hpp:900-905 / 1065-1070), replayed here with the
 // same device functions, so the value is bit for bit the one the step produced.
+__device__ __forceinline__ float replay_soc_steps(const HubParams &hp, int k, float soc, int n) {
+    const bool cp = hp.constant_charging != 0;
+    for (int i = 0; i < n; i++) {
+        float pw;
+        if (hp.type[k] == 0) car_step_curves<0>(__fadd_rn(soc_to_time<0>(soc, cp), 1.0f), cp, hp.cc, soc, pw);
+        else car_step_curves<1>(__fadd_rn(soc_to_time<1>(soc, cp), 1.0f), cp, hp.cc, soc, pw);
+    }
+    return soc;
+}
 __global__ void k_replay_soc(const DevCtx *__restrict__ ctx, float *out) {
     const HubParams &hp = ctx->hp;
     const int64_t NS = hp.n_envs * (int64_t) (hp.S[0] + hp.S[1]);
@@ -4448,7 +4457,6 @@ __global__ void k_replay_soc(const DevCtx *__restrict__ ctx, float *out) {
     if (idx >= NS) return;
     const int St = hp.S[0] + hp.S[1];
     const int k = hp.rng_mode == MODE_PHILOX ? ((int) (idx % St) >= hp.S[0] ? 1 : 0) : (idx >= hp.base[1] ? 1 : 0);
-    const bool cp = hp.constant_charging != 0;
     float soc = 0.0f;
     int n = 0;
     bool car;
@@ -4474,12 +4482,120 @@ __global__ void k_replay_soc(const DevCtx *__restrict__ ctx, float *out) {
             n = (int) (w >> 25);
         }
     }
-    for (int i = 0; i < n; i++) {
-        float pw;
-        if (hp.type[k] == 0) car_step_curves<0>(__fadd_rn(soc_to_time<0>(soc, cp), 1.0f), cp, hp.cc, soc, pw);
-        else car_step_curves<1>(__fadd_rn(soc_to_time<1>(soc, cp), 1.0f), cp, hp.cc, soc, pw);
+    out[idx] = replay_soc_steps(hp, k, soc, n);
+}
+
+// -------------------------------------------------------------------- per-pile observations (chub_pile_obs_device)
+// Tables of the PHILOX SoC column, [2][kSocLevels][kClsRow] f32: the class's arrival SoC after n = 0 .. kClsRow-1 car_steps, i.e. what
+// k_replay_soc gives a slot of that class and count, written once per handle BY THE SAME CHAIN ON THE DEVICE (replay_soc_steps: entry n is
+// the chain's value after n steps, so every prefix is the replay's own result).  One lane per (station, class).
+__global__ void k_build_cls_soc(const DevCtx *__restrict__ ctx, float *out) {
+    const HubParams &hp = ctx->hp;
+    const int i = (int) (blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= 2 * kSocLevels) return;
+    const int k = i / kSocLevels, c = i - k * kSocLevels;
+    float soc = ctx->tb.cls_soc0[k][c];
+    float *row = out + (size_t) i * kClsRow;
+    row[0] = soc;
+    for (int n = 1; n < kClsRow; n++) {
+        soc = replay_soc_steps(hp, k, soc, 1);
+        row[n] = soc;
     }
-    out[idx] = soc;
+}
+void launch_build_cls_soc(const DevCtx *ctx, float *d_out, hipStream_t stream) {
+    hipLaunchKernelGGL(k_build_cls_soc, dim3((2 * kSocLevels + 255) / 256), dim3(256), 0, stream, ctx, d_out);
+}
+
+// Station::situation (CHS.hpp:204-231) and the two stay counters (CHS.hpp:245-246) of every pile as columns: out[env][column][hub slot],
+// the columns of the field mask in ascending order, every value the bits chub_get_slots reports for that pile and field.  Lane = (env, hub
+// slot) of a flat range, so a wave's stores of one column are runs of consecutive floats; no lane talks to another (a unit is not a wave
+// here), so stations of any size take the same path.  LAYOUT: the handle's slot arrays (SlotArrays) -- the output is the same for all three.
+// What a field set does not ask for is not loaded: the state word alone gives car, charge and already_stay_time's `left`; the class row /
+// hot record only power, emergency (with Tables::ttab) and init_soc; stay8 only the two counters; the SoC only the SoC column -- PHILOX reads
+// it from k_build_cls_soc's table, the other two replay the car's steps as k_replay_soc does.
+struct PileObsArgs {
+    const DevCtx *ctx;
+    const uint8_t *mask;   // [N] or null: rows of envs whose byte is 0 are not written
+    const float *cls_soc;  // PHILOX: k_build_cls_soc's tables
+    float *out;            // [N][columns][S0 + S1]
+    uint32_t fields;       // bits of the CHUB_PILE_* enum
+};
+enum PileField : uint32_t { PF_CAR = 1u, PF_CHARGE = 2u, PF_EMERGENCY = 4u, PF_POWER = 8u, PF_SOC = 16u, PF_INIT_SOC = 32u, PF_TARGET_SOC = 64u,
+                            PF_STAY_TIME = 128u, PF_ALREADY_STAY = 256u };
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void k_pile_obs(const PileObsArgs a) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const DevCtx *__restrict__ ctx = a.ctx;
+    const HubParams &hp = ctx->hp;
+    const Tables &tb = ctx->tb;
+    const uint32_t fields = a.fields;
+    const int S0 = hp.S[0], S = S0 + hp.S[1], C = __popc(fields);
+    const int64_t NS = hp.n_envs * (int64_t) S;
+    const bool want_row = (fields & (PF_EMERGENCY | PF_POWER)) != 0u;  // (power, t_soc) of the car's point on its curve
+    const bool small = NS <= 0xFFFFFFFFll;
+    for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; i < NS; i += (int64_t) gridDim.x * blockDim.x) {
+        const int64_t env = small ? (int64_t) ((uint32_t) i / (uint32_t) S) : i / S;  // (a 64-bit division costs more than the rest of a lane's work)
+        if (a.mask && !a.mask[env]) continue;
+        const int slot = (int) (i - env * S);
+        const int k = slot >= S0 ? 1 : 0;
+        int left, stay = 0, lev, n;
+        bool chg;
+        float power = 0.0f, t_soc = 0.0f, arrive = 0.0f, soc = 0.0f;
+        if (LAYOUT == COPY_COMPAT) {  // station-major 16-byte records; the fourth word alone when nothing else is asked for
+            const int64_t idx = hp.base[k] + env * hp.S[k] + (slot - (k ? S0 : 0));
+            u32x4 h = {0u, 0u, 0u, 0u};
+            if (want_row || (fields & (PF_SOC | PF_INIT_SOC))) h = *(CHUB_G(const u32x4)) (ctx->sl.hot + 4 * idx);
+            else h.w = ctx->sl.hot[4 * idx + 3];
+            const CompatSlot s = CompatSlot::unpack(h);
+            left = s.tl; chg = s.charge; stay = s.meta & 127; lev = hot_level(h.w); n = (int) (h.w >> 25);
+            power = s.power; t_soc = s.t_soc; arrive = s.arr_soc;
+            if (left > 0 && (fields & PF_SOC)) soc = replay_soc_steps(hp, k, arrive, n);
+        } else {
+            const uint32_t w0 = LAYOUT == COPY_CURVES ? ctx->sl.wrd[i] : ctx->sl.hot[i];
+            left = ps_tl(w0); chg = (w0 & kPsChg) != 0u; lev = (int) ps_lev(w0); n = (int) ps_n(w0);
+            if (left > 0) {
+                if (LAYOUT == COPY_CURVES) {
+                    if (want_row) {
+                        const f32x2 hv = *(CHUB_G(const f32x2)) ((CHUB_G(const float)) ctx->sl.hot + 2 * i);
+                        power = hv.x; t_soc = hv.y;
+                    }
+                    if (fields & (PF_SOC | PF_INIT_SOC)) arrive = ctx->sl.soc0[i];
+                    if (fields & PF_SOC) soc = replay_soc_steps(hp, k, arrive, n);
+                } else {
+                    const uint32_t c = ps_cls(w0);
+                    if (want_row) {
+                        const f32x2 row = *(CHUB_G(const f32x2)) ((CHUB_G(const char)) tb.cls[k] + ((size_t) c * (kClsRow * 8u) + (uint32_t) n * 8u));
+                        power = row.x; t_soc = row.y;
+                    }
+                    if (fields & PF_INIT_SOC) arrive = tb.cls_soc0[k][c];
+                    if (fields & PF_SOC) soc = a.cls_soc[((size_t) k * kSocLevels + c) * kClsRow + (uint32_t) n];
+                }
+            }
+            if (fields & (PF_STAY_TIME | PF_ALREADY_STAY)) stay = (int) ctx->sl.stay8[i];
+        }
+        const bool car = left > 0;
+        float *o = a.out + ((int64_t) env * C * S + slot);  // column c of this pile: o[c * S]
+        if (fields & PF_CAR) { *o = car ? 1.0f : 0.0f; o += S; }
+        if (fields & PF_CHARGE) { *o = chg ? 1.0f : 0.0f; o += S; }
+        if (fields & PF_EMERGENCY) { *o = car ? emergency_of(tb.ttab[k][lev], t_soc, left) : 0.0f; o += S; }
+        if (fields & PF_POWER) { *o = car ? power : 0.0f; o += S; }
+        if (fields & PF_SOC) { *o = car ? soc : 0.0f; o += S; }
+        if (fields & PF_INIT_SOC) { *o = car ? arrive : 0.0f; o += S; }
+        if (fields & PF_TARGET_SOC) { *o = car ? uniform_level(lev, 80.0f, 100.0f) : 0.0f; o += S; }
+        if (fields & PF_STAY_TIME) { *o = car ? (float) stay : -1.0f; o += S; }
+        if (fields & PF_ALREADY_STAY) { *o = car ? (float) (stay - left) : -1.0f; }
+    }
+}
+void launch_pile_obs(const HubParams &hp, const DevCtx *ctx, uint32_t fields, const uint8_t *d_mask, const float *d_cls_soc, float *d_out,
+                     hipStream_t stream) {
+    const int64_t NS = hp.n_envs * (int64_t) (hp.S[0] + hp.S[1]);
+    if (NS <= 0) return;
+    int64_t nb = (NS + 255) / 256;
+    if (nb > (1 << 20)) nb = 1 << 20;  // (beyond 2^28 piles the lanes stride)
+    const PileObsArgs a = {ctx, d_mask, d_cls_soc, d_out, fields};
+    if (hp.rng_mode != MODE_PHILOX) hipLaunchKernelGGL(k_pile_obs<COPY_COMPAT>, dim3((unsigned) nb), dim3(256), 0, stream, a);
+    else if (hp.soc_curves) hipLaunchKernelGGL(k_pile_obs<COPY_CURVES>, dim3((unsigned) nb), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(k_pile_obs<COPY_PHILOX>, dim3((unsigned) nb), dim3(256), 0, stream, a);
 }
 
 // PHILOX reset: evs_reset's initial occupancy per (station, env) unit -- init_station_car_number(mu, 3) (CHS.hpp:832-842)

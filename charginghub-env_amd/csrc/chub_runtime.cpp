@@ -24,6 +24,9 @@ void launch_slot(const CallPlan &cp, const HubParams &hp, const LaunchPlan &lp, 
                  const PackedPtrs &pp, hipEvent_t ev0, hipEvent_t ev1);
 void launch_replay_soc(const HubParams &hp, const DevCtx *ctx, float *d_out, hipStream_t stream);
 void launch_check_ttab(const DevCtx *ctx, uint32_t *d_mismatch, hipStream_t stream);
+void launch_build_cls_soc(const DevCtx *ctx, float *d_out, hipStream_t stream);
+void launch_pile_obs(const HubParams &hp, const DevCtx *ctx, uint32_t fields, const uint8_t *d_mask, const float *d_cls_soc, float *d_out,
+                     hipStream_t stream);
 template <bool RESET>
 void launch_env(EnvForm f, const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
                 const PackedPtrs &pp);
@@ -151,6 +154,9 @@ struct chub_env {
     // switched on -- live [kEpCount][N] f64, finished [kEpCount][N] f64, episodes [N] u32, pending [N] u8 -- which snapshots carry behind the arena
     EpisodeArrays es = {0, 0, nullptr, nullptr, nullptr, nullptr};
     char *d_ledger = nullptr;
+    // chub_pile_obs_device, PHILOX: [2][kSocLevels][kClsRow] f32, a class's SoC after n car_steps (k_build_cls_soc, once at create).  Derived
+    // data outside the arena: no snapshot carries it, no copy moves it
+    float *d_cls_soc = nullptr;
     double *d_ep_sum = nullptr;  // k_episode_summary's partials [kEpSumMaxBlocks][kEpSumWords], then the host form's result [kEpSumWords]
     int public_mode = 0;     // the rng_mode the handle was created with: CHUB_RNG_PHILOX_CURVES is hp.rng_mode = PHILOX + hp.soc_curves
     bool tape_only = false;  // ... and once there are any, the handle's class rows are the caller's: only tape resets / steps may admit cars
@@ -975,6 +981,18 @@ static int create_impl(const chub_config *cfg_in, const char *data_dir, int64_t 
                                               : "the device's soc_to_time differs from the host-built table of target times"));
         }
     }
+    if (rng_mode == CHUB_RNG_PHILOX && !soc_curves) {
+        // the SoC column of chub_pile_obs_device: the class rows' SoC, by the device's own replay of the curve (the chain k_replay_soc runs
+        // per slot for chub_get_slots), so that the table's entries are that replay's bits whatever the host's libm makes of the same chain
+        if (hipMalloc((void **) &e->d_cls_soc, (size_t) 2 * kSocLevels * kClsRow * sizeof(float)) != hipSuccess) {
+            e->d_cls_soc = nullptr;
+            return bail(fail(CHUB_ERR_HIP, "hipMalloc failed"));
+        }
+        if ((rc = sync_ctx(e, nullptr))) return bail(rc);
+        launch_build_cls_soc(e->d_ctx, e->d_cls_soc, nullptr);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess)
+            return bail(fail(CHUB_ERR_HIP, "the SoC table of the arrival classes could not be built on the device"));
+    }
     *out = e;
     return CHUB_OK;
 }
@@ -994,6 +1012,7 @@ int chub_destroy(chub_env *e) {
         if (e->h_telem) (void) hipHostFree(e->h_telem);
         if (e->d_telem) (void) hipFree(e->d_telem);
         if (e->d_ledger) (void) hipFree(e->d_ledger);
+        if (e->d_cls_soc) (void) hipFree(e->d_cls_soc);
         if (e->d_ep_sum) (void) hipFree(e->d_ep_sum);
         if (e->h_bits) (void) hipHostFree(e->h_bits);  // h_tail / d_tail are the ends of the same blocks
         if (e->d_bits) (void) hipFree(e->d_bits);
@@ -2623,6 +2642,24 @@ int chub_get_slots(chub_env *e, float *out) {
             o += 9 * n;
         }
     }
+    return CHUB_OK;
+}
+
+int chub_pile_obs_columns(uint32_t fields) {
+    if (fields == 0u || (fields >> CHUB_PILE_COUNT) != 0u) return fail(CHUB_ERR_ARG, "fields: a non-empty mask over the CHUB_PILE_* fields");
+    return __builtin_popcount(fields);
+}
+
+int chub_pile_obs_device(chub_env *e, uint32_t fields, const uint8_t *d_mask, float *d_out, void *stream) {
+    if (!e || !d_out) return fail(CHUB_ERR_ARG, "null argument");
+    if (chub_pile_obs_columns(fields) < 0) return CHUB_ERR_ARG;
+    if (e->tape_only)
+        return fail(CHUB_ERR_UNSUPPORTED, "chub_pile_obs_device is not supported on a tape handle (chub_tape_register_soc rewrites the class tables)");
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    if (const int rc = sync_ctx(e, (hipStream_t) stream)) return rc;  // (nothing to do inside a capture: chub_graph_begin has done it)
+    launch_pile_obs(e->hp, e->d_ctx, fields, d_mask, e->d_cls_soc, d_out, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
     return CHUB_OK;
 }
 

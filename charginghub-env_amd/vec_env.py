@@ -495,6 +495,30 @@ class VecChargingHub(object):
         b = out[:, 9 * s0:].reshape(self.n_envs, 9, self.piles[1])
         return [a, b]
 
+    # ---- per-pile observations on the device (chub_pile_obs_device): Station::situation and the stay counters as columns
+    def pile_obs_device(self, d_out, fields=None, d_mask=0, stream=0):
+        """the per-pile columns into device memory, d_out [N, C, n_slots] f32: env, then the C fields asked for in the order of
+        _lib.PILE_NAMES, then hub slot (station 0's piles first, as in an action row) -- every value the bits slots() reports, in another
+        layout.  fields: names, a bit mask, or None for all nine; d_mask [N] u8 in device memory: only the rows of the envs it names are
+        written.  One launch on `stream`: no synchronisation, nothing of the simulation changes, recordable into a graph."""
+        check(self._lib.chub_pile_obs_device(self._h, _lib.pile_fields_mask(fields), d_mask or None, d_out, stream or None))
+
+    def pile_obs(self, fields=None):
+        """pile_obs_device into host memory: float32 [N, C, n_slots] (the convenience form: it allocates, synchronises and copies)"""
+        mask = _lib.pile_fields_mask(fields)
+        out = np.zeros((self.n_envs, len(_lib.pile_fields_names(mask)), self.n_slots), dtype=np.float32)
+        if out.size == 0:
+            return out
+        d = C.c_void_p()
+        check(self._lib.chub_malloc_device(self._device, out.nbytes, C.byref(d)))
+        try:
+            check(self._lib.chub_sync(self._h))  # (calls in flight on any stream write the state)
+            check(self._lib.chub_pile_obs_device(self._h, mask, None, d, None))
+            check(self._lib.chub_copy_to_host(self._device, _ptr(out), d, out.nbytes, None))
+        finally:
+            self._lib.chub_free_device(self._device, d)
+        return out
+
     def station_scalars(self):
         out = np.zeros((self.n_envs, 2, 8), dtype=np.float64)
         check(self._lib.chub_get_station_scalars(self._h, _ptr(out)))

@@ -266,13 +266,19 @@ class TorchHubVecEnv(object):
 
     ``episode_stats=True`` switches the hub's per-episode ledger on (chub_set_episode_stats): ``episode_stats()`` and
     ``episode_summary()`` then give every env's finished-episode record, or its reduction over the episodes that ended since the last
-    look, as CUDA tensors filled on torch's stream -- no device read, no wait, whatever the envs' clocks are."""
+    look, as CUDA tensors filled on torch's stream -- no device read, no wait, whatever the envs' clocks are.
 
-    def __init__(self, n_envs, station_list, station_type_list, seed=0, device=0, autoreset=True, episode_stats=False, **hub_kwargs):
+    ``pile_obs=("car", "emergency", "soc")`` (any of _lib.PILE_NAMES; None: off) makes ``pile_obs()`` available: the per-pile columns
+    the reference keeps in Station::situation, as one [N, C, S] CUDA tensor (chub_pile_obs_device); ``pile_names`` is the column order."""
+
+    def __init__(self, n_envs, station_list, station_type_list, seed=0, device=0, autoreset=True, episode_stats=False, pile_obs=None,
+                 **hub_kwargs):
         import torch  # before libchub is loaded by VecChargingHub: both must share one HIP runtime
 
         if not (autoreset is True or autoreset is False or autoreset == "per_env"):
             raise ValueError("autoreset must be True, False or 'per_env', not %r" % (autoreset,))
+        self._pile_mask = None if pile_obs is None else _lib.pile_fields_mask(pile_obs)  # (ValueError for an unknown name, before anything is built)
+        self.pile_names = () if pile_obs is None else _lib.pile_fields_names(self._pile_mask)
         self.torch = torch
         self.device = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
         if self.device.type == "cuda":
@@ -295,6 +301,18 @@ class TorchHubVecEnv(object):
             self._ep_block = torch.zeros((_lib.EP_COUNT, self.num_envs), dtype=torch.float64, device=self.device)
             self._ep_counts = torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device)  # (the handle's u32 words)
             self._ep_summary = torch.zeros((1 + 4 * _lib.EP_COUNT,), dtype=torch.float64, device=self.device)
+        self._pile_buf = None
+        if self._pile_mask is not None:
+            self._pile_buf = torch.zeros((self.num_envs, len(self.pile_names), self.vec.n_slots), dtype=torch.float32, device=self.device)
+
+    def pile_obs(self):
+        """float32 [N, C, S] CUDA tensor: for every env the columns of ``pile_names`` over its S piles in hub-slot order (station 0's
+        first, as in an action row), as the piles stand after the last reset / step -- an env the step has just re-started shows its new
+        episode's piles.  Filled by one launch on torch's current stream, without a wait; it is ONE buffer, overwritten by the next call."""
+        if self._pile_buf is None:
+            raise RuntimeError("per-pile observations are off: construct with pile_obs=(names of _lib.PILE_NAMES)")
+        self.vec.pile_obs_device(self._pile_buf.data_ptr(), self._pile_mask, stream=self._stream())
+        return self._pile_buf
 
     def _need_episode_stats(self):
         if self._ep_block is None:

@@ -79,7 +79,7 @@ def device_resident(n=65536):
         print("3. skipped: torch is not installed")
         return
 
-    env = chub.TorchHubVecEnv(n, seed=0, **HUB)
+    env = chub.TorchHubVecEnv(n, seed=0, pile_obs=("car", "emergency"), **HUB)
     obs = env.reset()
     actions = torch.rand((n, env.act_dim), device="cuda") * 2 - 1
     for _ in range(96):
@@ -100,6 +100,14 @@ def device_resident(n=65536):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print("   the same decisions as bits: %.0f M env-steps/s" % (n * steps / dt / 1e6))
+    # a per-pile policy sees every pile (Station::situation): [n, columns, piles] on the device, here "charge whoever is urgent"
+    piles = env.pile_obs()
+    car, emergency = piles[:, 0], piles[:, 1]
+    urgent = actions.clone()
+    urgent[:, :env.act_dim - 2] = torch.where((car > 0) & (emergency >= 0.25), 1.0, -1.0)
+    obs, reward, done, _ = env.step(urgent)
+    print("   per-pile columns %s: %.1f cars per env, %.1f of them urgent" % (env.pile_names, float(car.sum(1).mean()),
+                                                                             float(((car > 0) & (emergency >= 0.25)).sum(1).float().mean())))
     # population-based selection without leaving the device: the worst tenth becomes a copy of the best tenth (each clone keeps its own
     # random streams, so it parts from its source at the next step)
     k = max(1, n // 10)

@@ -517,6 +517,39 @@ int chub_episode_stats_device(chub_env *env, int finished, double *d_out, uint32
 int chub_episode_summary_device(chub_env *env, double *d_out, int drain, void *stream);
 int chub_episode_summary(chub_env *env, double *out, int drain);
 
+/* ---- per-pile observations on the device -----------------------------------------------------------------------------------------
+ * A policy sets one bit per pile, and the reference shows it every pile: Station::situation (CHS.hpp:204-231) holds car, charge, emergency,
+ * power, soc, init_soc and target_soc per pile, the two stay counters sit beside it (CHS.hpp:245-246).  chub_get_slots reports these nine
+ * fields through the host (it synchronises, allocates and decodes in a host loop: a parity instrument); chub_pile_obs_device writes them as
+ * columns into the caller's device memory in ONE launch on `stream`, for a policy or a heuristic that never leaves the device:
+ *   fields  a bit mask over the CHUB_PILE_* enum (bit f = field f; the enum has chub_get_slots' nine fields in its order); C = its popcount
+ *           columns come out, in ascending field order.  chub_pile_obs_columns gives C for a valid mask (it needs no device).
+ *   d_out   [N][C][S] f32, S = piles[0] + piles[1]: env-major, then column, then HUB SLOT -- station 0's piles first, as in an action row
+ *           (a station of 0 piles contributes no slots), so that a wave stores runs of consecutive floats.  NOT chub_get_slots' layout: that
+ *           one is [N][station][9][piles[k]], per-station blocks.  Every value is, bit for bit, what chub_get_slots reports for that pile
+ *           and field at the same moment, the defaults of an empty pile included (0, and -1 for the two counters).
+ *   d_mask  [N] u8 in device memory or NULL: with a mask only the rows of the envs whose byte is non-zero are written, every other row of
+ *           d_out is left alone (an all-zero mask writes nothing).
+ * It reads simulation state and writes d_out, nothing else: no tick, no clock, no draw -- the handle computes what it would have computed
+ * without the call.  It returns after enqueueing: no synchronisation, no allocation, no staging copy; order it against the calls that
+ * write the state as any other call on the handle (the same stream, or an event).  Valid at any point after the first reset: after resets
+ * and steps of every form (masked, device-mask, auto-reset: a re-started env shows its new episode's piles), chub_copy_envs* and
+ * chub_set_state; on lock-step and per-env clocks, with or without per-env parameter rows, telemetry or the ledger; in all three RNG
+ * modes and for every hub shape the handle can be created with.  Recordable between chub_graph_begin and chub_graph_end, where it does
+ * not count towards the even number of resets + steps a graph must cover.
+ * Cost follows the field set: the state word alone gives car and charge; power, emergency and init_soc add the pile's record (PHILOX: its
+ * class row), the counters one byte, and the SoC -- which no mode stores -- is a read of a per-class table in PHILOX (derived data built on
+ * the device when the handle is created: not snapshot state, chub_state_size is unchanged) and a replay of the car's steps along the
+ * curve in COMPAT and PHILOX_CURVES, as in chub_get_slots.  A field that is not asked for costs none of this.
+ * CHUB_ERR_ARG: null handle, null d_out, fields 0 or with bits from CHUB_PILE_COUNT up.  CHUB_ERR_UNSUPPORTED with a message: tape handles
+ * (chub_tape_register_soc rewrites the class tables the columns are read from). */
+enum {
+    CHUB_PILE_CAR = 0, CHUB_PILE_CHARGE, CHUB_PILE_EMERGENCY, CHUB_PILE_POWER, CHUB_PILE_SOC, CHUB_PILE_INIT_SOC, CHUB_PILE_TARGET_SOC,
+    CHUB_PILE_STAY_TIME, CHUB_PILE_ALREADY_STAY, CHUB_PILE_COUNT
+};
+int chub_pile_obs_columns(uint32_t fields);
+int chub_pile_obs_device(chub_env *env, uint32_t fields, const uint8_t *d_mask, float *d_out, void *stream);
+
 /* The FCEV waiting list is unbounded as in the reference (HYD:264-265): the entries a list that still gets served can
  * hold are kept one by one, and once no prefix of it fits into 15 minutes any more (HYD:270-276: nobody is served again
  * until reset and the list only grows) its entries are folded into their count and running sums, which is all the
