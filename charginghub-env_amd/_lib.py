@@ -57,6 +57,38 @@ def pile_fields_names(mask):
     return tuple(name for i, name in enumerate(PILE_NAMES) if mask >> i & 1)
 
 
+
+# the columns of chub_station_profile_device (the CHUB_SP_* enum of include/chub.h, in order)
+SP_NAMES = ("cars", "charging", "must_charge", "power", "power_charging", "emergency", "soc_gap")
+SP_COUNT = len(SP_NAMES)
+SP = {name: i for i, name in enumerate(SP_NAMES)}
+
+
+def sp_fields_mask(fields=None):
+    """a field set of chub_station_profile_device as its bit mask: None = all seven, an int = the mask itself, else a sequence of SP_NAMES"""
+    if fields is None:
+        return (1 << SP_COUNT) - 1
+    if hasattr(fields, "__index__"):  # (an int of any kind)
+        fields = fields.__index__()
+        if fields <= 0 or fields >> SP_COUNT:
+            raise ValueError("fields: a non-empty mask over the %d station-profile fields, got %#x" % (SP_COUNT, fields))
+        return fields
+    if isinstance(fields, str):
+        fields = (fields,)
+    mask = 0
+    for name in fields:
+        if name not in SP:
+            raise ValueError("unknown station-profile field %r (one of %s)" % (name, ", ".join(SP_NAMES)))
+        mask |= 1 << SP[name]
+    if not mask:
+        raise ValueError("fields: at least one station-profile field")
+    return mask
+
+
+def sp_fields_names(mask):
+    """the columns a mask selects, in the order they come out (ascending field order)"""
+    return tuple(name for i, name in enumerate(SP_NAMES) if mask >> i & 1)
+
 class ChubOptions(C.Structure):
     """chub_options of include/chub.h (all zero = defaults; the library reads no environment variables)"""
     _fields_ = [("slot_kernel", C.c_int32), ("no_arena", C.c_int32), ("fused_step", C.c_int32), ("tile", C.c_int32), ("walk_ahead", C.c_int32), ("work_order", C.c_int32), ("span_steps", C.c_int32), ("span_tails", C.c_int32)]
@@ -160,6 +192,7 @@ def load_library():
         "chub_get_episode_counts": (I, [P, P]), "chub_episode_stats_device": (I, [P, I, P, P, P]),
         "chub_episode_summary_device": (I, [P, P, I, P]), "chub_episode_summary": (I, [P, P, I]),
         "chub_pile_obs_columns": (I, [C.c_uint32]), "chub_pile_obs_device": (I, [P, C.c_uint32, P, P, P]),
+        "chub_station_profile_size": (I, [C.c_uint32, C.c_int32]), "chub_station_profile_device": (I, [P, C.c_uint32, C.c_int32, P, P, P]),
         "chub_set_rng_compat_seeds": (I, [P, P]), "chub_set_rng_compat_state": (I, [P, P]),
         "chub_get_rng_compat_state": (I, [P, P]), "chub_compat_replay_constructor": (I, [P]), "chub_set_ou_state": (I, [P, P]),
         "chub_copy_envs": (I, [P, P, P, P, L]), "chub_copy_envs_device": (I, [P, P, P, P, L, P]),
@@ -211,7 +244,8 @@ EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "ch
             "chub_malloc_device", "chub_free_device", "chub_copy_to_host", "chub_copy_to_device", "chub_alloc_host", "chub_free_host", "chub_stream_create",
             "chub_stream_destroy", "chub_stream_sync",
             "chub_set_episode_stats", "chub_has_episode_stats", "chub_get_episode_stats", "chub_get_episode_counts", "chub_episode_stats_device",
-            "chub_episode_summary_device", "chub_episode_summary", "chub_pile_obs_columns", "chub_pile_obs_device"]
+            "chub_episode_summary_device", "chub_episode_summary", "chub_pile_obs_columns", "chub_pile_obs_device",
+            "chub_station_profile_size", "chub_station_profile_device"]
 
 
 def check(rc):

@@ -4522,57 +4522,77 @@ struct PileObsArgs {
 };
 enum PileField : uint32_t { PF_CAR = 1u, PF_CHARGE = 2u, PF_EMERGENCY = 4u, PF_POWER = 8u, PF_SOC = 16u, PF_INIT_SOC = 32u, PF_TARGET_SOC = 64u,
                             PF_STAY_TIME = 128u, PF_ALREADY_STAY = 256u };
+// One pile's decode, shared by k_pile_obs and k_station_profile (the profile's bins are sums over exactly these values): what `fields`
+// (PF_* bits) does not ask for is not loaded and stays 0.  i = env * S + slot, the pile's index in the slot-major PHILOX arrays.
+struct PileVals {
+    int left, stay, lev;
+    bool chg;
+    float power, t_soc, arrive, soc;
+};
+template <int LAYOUT>
+__device__ __forceinline__ PileVals pile_decode(const DevCtx *__restrict__ ctx, const float *cls_soc, uint32_t fields, int64_t env, int slot,
+                                                int64_t i) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const HubParams &hp = ctx->hp;
+    const Tables &tb = ctx->tb;
+    const int S0 = hp.S[0];
+    const bool want_row = (fields & (PF_EMERGENCY | PF_POWER)) != 0u;  // (power, t_soc) of the car's point on its curve
+    const int k = slot >= S0 ? 1 : 0;
+    int left, stay = 0, lev, n;
+    bool chg;
+    float power = 0.0f, t_soc = 0.0f, arrive = 0.0f, soc = 0.0f;
+    if (LAYOUT == COPY_COMPAT) {  // station-major 16-byte records; the fourth word alone when nothing else is asked for
+        const int64_t idx = hp.base[k] + env * hp.S[k] + (slot - (k ? S0 : 0));
+        u32x4 h = {0u, 0u, 0u, 0u};
+        if (want_row || (fields & (PF_SOC | PF_INIT_SOC))) h = *(CHUB_G(const u32x4)) (ctx->sl.hot + 4 * idx);
+        else h.w = ctx->sl.hot[4 * idx + 3];
+        const CompatSlot s = CompatSlot::unpack(h);
+        left = s.tl; chg = s.charge; stay = s.meta & 127; lev = hot_level(h.w); n = (int) (h.w >> 25);
+        power = s.power; t_soc = s.t_soc; arrive = s.arr_soc;
+        if (left > 0 && (fields & PF_SOC)) soc = replay_soc_steps(hp, k, arrive, n);
+    } else {
+        const uint32_t w0 = LAYOUT == COPY_CURVES ? ctx->sl.wrd[i] : ctx->sl.hot[i];
+        left = ps_tl(w0); chg = (w0 & kPsChg) != 0u; lev = (int) ps_lev(w0); n = (int) ps_n(w0);
+        if (left > 0) {
+            if (LAYOUT == COPY_CURVES) {
+                if (want_row) {
+                    const f32x2 hv = *(CHUB_G(const f32x2)) ((CHUB_G(const float)) ctx->sl.hot + 2 * i);
+                    power = hv.x; t_soc = hv.y;
+                }
+                if (fields & (PF_SOC | PF_INIT_SOC)) arrive = ctx->sl.soc0[i];
+                if (fields & PF_SOC) soc = replay_soc_steps(hp, k, arrive, n);
+            } else {
+                const uint32_t c = ps_cls(w0);
+                if (want_row) {
+                    const f32x2 row = *(CHUB_G(const f32x2)) ((CHUB_G(const char)) tb.cls[k] + ((size_t) c * (kClsRow * 8u) + (uint32_t) n * 8u));
+                    power = row.x; t_soc = row.y;
+                }
+                if (fields & PF_INIT_SOC) arrive = tb.cls_soc0[k][c];
+                if (fields & PF_SOC) soc = cls_soc[((size_t) k * kSocLevels + c) * kClsRow + (uint32_t) n];
+            }
+        }
+        if (fields & (PF_STAY_TIME | PF_ALREADY_STAY)) stay = (int) ctx->sl.stay8[i];
+    }
+    return {left, stay, lev, chg, power, t_soc, arrive, soc};
+}
 template <int LAYOUT>
 __global__ __launch_bounds__(256) void k_pile_obs(const PileObsArgs a) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
     const DevCtx *__restrict__ ctx = a.ctx;
     const HubParams &hp = ctx->hp;
     const Tables &tb = ctx->tb;
     const uint32_t fields = a.fields;
     const int S0 = hp.S[0], S = S0 + hp.S[1], C = __popc(fields);
     const int64_t NS = hp.n_envs * (int64_t) S;
-    const bool want_row = (fields & (PF_EMERGENCY | PF_POWER)) != 0u;  // (power, t_soc) of the car's point on its curve
     const bool small = NS <= 0xFFFFFFFFll;
     for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; i < NS; i += (int64_t) gridDim.x * blockDim.x) {
         const int64_t env = small ? (int64_t) ((uint32_t) i / (uint32_t) S) : i / S;  // (a 64-bit division costs more than the rest of a lane's work)
         if (a.mask && !a.mask[env]) continue;
         const int slot = (int) (i - env * S);
         const int k = slot >= S0 ? 1 : 0;
-        int left, stay = 0, lev, n;
-        bool chg;
-        float power = 0.0f, t_soc = 0.0f, arrive = 0.0f, soc = 0.0f;
-        if (LAYOUT == COPY_COMPAT) {  // station-major 16-byte records; the fourth word alone when nothing else is asked for
-            const int64_t idx = hp.base[k] + env * hp.S[k] + (slot - (k ? S0 : 0));
-            u32x4 h = {0u, 0u, 0u, 0u};
-            if (want_row || (fields & (PF_SOC | PF_INIT_SOC))) h = *(CHUB_G(const u32x4)) (ctx->sl.hot + 4 * idx);
-            else h.w = ctx->sl.hot[4 * idx + 3];
-            const CompatSlot s = CompatSlot::unpack(h);
-            left = s.tl; chg = s.charge; stay = s.meta & 127; lev = hot_level(h.w); n = (int) (h.w >> 25);
-            power = s.power; t_soc = s.t_soc; arrive = s.arr_soc;
-            if (left > 0 && (fields & PF_SOC)) soc = replay_soc_steps(hp, k, arrive, n);
-        } else {
-            const uint32_t w0 = LAYOUT == COPY_CURVES ? ctx->sl.wrd[i] : ctx->sl.hot[i];
-            left = ps_tl(w0); chg = (w0 & kPsChg) != 0u; lev = (int) ps_lev(w0); n = (int) ps_n(w0);
-            if (left > 0) {
-                if (LAYOUT == COPY_CURVES) {
-                    if (want_row) {
-                        const f32x2 hv = *(CHUB_G(const f32x2)) ((CHUB_G(const float)) ctx->sl.hot + 2 * i);
-                        power = hv.x; t_soc = hv.y;
-                    }
-                    if (fields & (PF_SOC | PF_INIT_SOC)) arrive = ctx->sl.soc0[i];
-                    if (fields & PF_SOC) soc = replay_soc_steps(hp, k, arrive, n);
-                } else {
-                    const uint32_t c = ps_cls(w0);
-                    if (want_row) {
-                        const f32x2 row = *(CHUB_G(const f32x2)) ((CHUB_G(const char)) tb.cls[k] + ((size_t) c * (kClsRow * 8u) + (uint32_t) n * 8u));
-                        power = row.x; t_soc = row.y;
-                    }
-                    if (fields & PF_INIT_SOC) arrive = tb.cls_soc0[k][c];
-                    if (fields & PF_SOC) soc = a.cls_soc[((size_t) k * kSocLevels + c) * kClsRow + (uint32_t) n];
-                }
-            }
-            if (fields & (PF_STAY_TIME | PF_ALREADY_STAY)) stay = (int) ctx->sl.stay8[i];
-        }
+        const PileVals p = pile_decode<LAYOUT>(ctx, a.cls_soc, fields, env, slot, i);
+        const int left = p.left, stay = p.stay, lev = p.lev;
+        const bool chg = p.chg;
+        const float power = p.power, t_soc = p.t_soc, arrive = p.arrive, soc = p.soc;
         const bool car = left > 0;
         float *o = a.out + ((int64_t) env * C * S + slot);  // column c of this pile: o[c * S]
         if (fields & PF_CAR) { *o = car ? 1.0f : 0.0f; o += S; }
@@ -4596,6 +4616,94 @@ void launch_pile_obs(const HubParams &hp, const DevCtx *ctx, uint32_t fields, co
     if (hp.rng_mode != MODE_PHILOX) hipLaunchKernelGGL(k_pile_obs<COPY_COMPAT>, dim3((unsigned) nb), dim3(256), 0, stream, a);
     else if (hp.soc_curves) hipLaunchKernelGGL(k_pile_obs<COPY_CURVES>, dim3((unsigned) nb), dim3(256), 0, stream, a);
     else hipLaunchKernelGGL(k_pile_obs<COPY_PHILOX>, dim3((unsigned) nb), dim3(256), 0, stream, a);
+}
+
+// -------------------------------------------------------------------- per-station deadline profiles (chub_station_profile_device)
+// A station's cars binned by the time they have left: out[env][station][column][bucket], the columns of the field mask in ascending order,
+// a car with `left` slots to go in bucket min(left, B) - 1.  The per-pile values are pile_decode's, i.e. k_pile_obs' columns; new here is the
+// reduction of a station's 1 .. 4096 piles into C x B bins.  A workgroup owns whole envs: `group` of them at a time (the host picks it so that
+// the group's piles fill the 256 lanes and its bins fit kSpBins), an env of more piles than lanes is walked in chunks of 256.  Every bin is
+// one 8-byte word of LDS: a count takes 32-bit adds on its low half, a sum 64-bit adds of llrint(x * 2^q) -- integer adds commute, so the
+// result does not depend on lane order, group size or grid -- and the group's blocks leave as one run of consecutive floats.  Three
+// barriers per group, each reached by every lane (the mask and the empty piles skip inside the lane loops, never around a barrier).
+// What a field set does not ask for is not loaded: cars and charging need the state word alone, must_charge / power* / emergency the
+// class row or hot record, soc_gap alone the SoC (PHILOX: k_build_cls_soc's table; the other two replay the car's steps).
+struct StationProfileArgs {
+    const DevCtx *ctx;
+    const uint8_t *mask;   // [N] or null: blocks of envs whose byte is 0 are not written
+    const float *cls_soc;  // PHILOX: k_build_cls_soc's tables
+    float *out;            // [N][2][columns][buckets]
+    uint32_t fields;       // bits of the CHUB_SP_* enum
+    int buckets;           // 1 .. 32
+    int group;             // envs a workgroup takes at a time: group * 2 * columns * buckets <= kSpBins
+};
+enum ProfileField : uint32_t { SPF_CARS = 1u, SPF_CHARGING = 2u, SPF_MUST_CHARGE = 4u, SPF_POWER = 8u, SPF_POWER_CHARGING = 16u, SPF_EMERGENCY = 32u,
+                               SPF_SOC_GAP = 64u };
+constexpr int kSpBins = 2048;  // 16 KB of LDS; one env of all seven fields and 32 buckets takes 448
+__device__ __forceinline__ unsigned long long sp_term(float x, double scale) { return (unsigned long long) __double2ll_rn((double) x * scale); }
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void k_station_profile(const StationProfileArgs a) {
+    __shared__ unsigned long long bins[kSpBins];
+    const DevCtx *__restrict__ ctx = a.ctx;
+    const HubParams &hp = ctx->hp;
+    const Tables &tb = ctx->tb;
+    const uint32_t fields = a.fields;
+    const int B = a.buckets, CB = __popc(fields) * B, per_env = 2 * CB, G = a.group;
+    const int S0 = hp.S[0], S = S0 + hp.S[1];
+    const int64_t N = hp.n_envs;
+    const int tid = (int) threadIdx.x;
+    uint32_t pf = 0u;  // the pile fields behind the profile's
+    if (fields & (SPF_MUST_CHARGE | SPF_EMERGENCY)) pf |= PF_EMERGENCY;
+    if (fields & (SPF_POWER | SPF_POWER_CHARGING)) pf |= PF_POWER;
+    if (fields & SPF_SOC_GAP) pf |= PF_SOC;
+    for (int64_t env0 = (int64_t) blockIdx.x * G; env0 < N; env0 += (int64_t) gridDim.x * G) {
+        const int ng = (int) (N - env0 < (int64_t) G ? N - env0 : (int64_t) G);
+        const int n_bins = ng * per_env, n_piles = ng * S;
+        for (int j = tid; j < n_bins; j += 256) bins[j] = 0ull;
+        __syncthreads();
+        for (int j = tid; j < n_piles; j += 256) {
+            const int e = j / S, slot = j - e * S;
+            const int64_t env = env0 + e;
+            if (a.mask && !a.mask[env]) continue;
+            const PileVals p = pile_decode<LAYOUT>(ctx, a.cls_soc, pf, env, slot, env * S + slot);
+            if (p.left <= 0) continue;
+            const int k = slot >= S0 ? 1 : 0;
+            unsigned long long *col = bins + ((e * 2 + k) * CB + (p.left < B ? p.left : B) - 1);
+            const float em = (pf & PF_EMERGENCY) ? emergency_of(tb.ttab[k][p.lev], p.t_soc, p.left) : 0.0f;
+            if (fields & SPF_CARS) { atomicAdd((unsigned int *) col, 1u); col += B; }
+            if (fields & SPF_CHARGING) { if (p.chg) atomicAdd((unsigned int *) col, 1u); col += B; }
+            if (fields & SPF_MUST_CHARGE) { if (em == 10.0f) atomicAdd((unsigned int *) col, 1u); col += B; }
+            if (fields & SPF_POWER) { atomicAdd(col, sp_term(p.power, 524288.0)); col += B; }
+            if (fields & SPF_POWER_CHARGING) { if (p.chg) atomicAdd(col, sp_term(p.power, 524288.0)); col += B; }
+            if (fields & SPF_EMERGENCY) { atomicAdd(col, sp_term(em, 1048576.0)); col += B; }
+            if (fields & SPF_SOC_GAP) atomicAdd(col, sp_term(__fsub_rn(uniform_level(p.lev, 80.0f, 100.0f), p.soc), 65536.0));
+        }
+        __syncthreads();
+        for (int j = tid; j < n_bins; j += 256) {
+            const int e = j / per_env;
+            if (a.mask && !a.mask[env0 + e]) continue;
+            int c = (j - e * per_env) % CB / B, f = 0;  // column c is the c-th set bit of the mask
+            for (uint32_t m = fields; c > 0 || !(m & 1u); m >>= 1, f++) c -= (int) (m & 1u);
+            const uint32_t bit = 1u << f;
+            const float unit = (bit & (SPF_POWER | SPF_POWER_CHARGING)) ? 0x1p-19f : bit == SPF_EMERGENCY ? 0x1p-20f : bit == SPF_SOC_GAP ? 0x1p-16f : 1.0f;
+            a.out[env0 * per_env + j] = __fmul_rn((float) (long long) bins[j], unit);
+        }
+        __syncthreads();  // (the next group zeroes the bins)
+    }
+}
+void launch_station_profile(const HubParams &hp, const DevCtx *ctx, uint32_t fields, int buckets, const uint8_t *d_mask, const float *d_cls_soc,
+                            float *d_out, hipStream_t stream) {
+    const int S = hp.S[0] + hp.S[1];
+    if (hp.n_envs <= 0) return;
+    int group = S > 0 ? 256 / S : 256;  // envs whose piles fill the workgroup's lanes ...
+    const int fit = kSpBins / (2 * __builtin_popcount(fields) * buckets);  // ... as far as their bins fit (>= 4)
+    group = group < 1 ? 1 : (group > fit ? fit : group);
+    int64_t nb = (hp.n_envs + group - 1) / group;
+    if (nb > (1 << 20)) nb = 1 << 20;  // (beyond that the workgroups stride)
+    const StationProfileArgs a = {ctx, d_mask, d_cls_soc, d_out, fields, buckets, group};
+    if (hp.rng_mode != MODE_PHILOX) hipLaunchKernelGGL(k_station_profile<COPY_COMPAT>, dim3((unsigned) nb), dim3(256), 0, stream, a);
+    else if (hp.soc_curves) hipLaunchKernelGGL(k_station_profile<COPY_CURVES>, dim3((unsigned) nb), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(k_station_profile<COPY_PHILOX>, dim3((unsigned) nb), dim3(256), 0, stream, a);
 }
 
 // PHILOX reset: evs_reset's initial occupancy per (station, env) unit -- init_station_car_number(mu, 3) (CHS.hpp:832-842)

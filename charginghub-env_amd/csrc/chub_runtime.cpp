@@ -27,6 +27,8 @@ void launch_check_ttab(const DevCtx *ctx, uint32_t *d_mismatch, hipStream_t stre
 void launch_build_cls_soc(const DevCtx *ctx, float *d_out, hipStream_t stream);
 void launch_pile_obs(const HubParams &hp, const DevCtx *ctx, uint32_t fields, const uint8_t *d_mask, const float *d_cls_soc, float *d_out,
                      hipStream_t stream);
+void launch_station_profile(const HubParams &hp, const DevCtx *ctx, uint32_t fields, int buckets, const uint8_t *d_mask, const float *d_cls_soc,
+                            float *d_out, hipStream_t stream);
 template <bool RESET>
 void launch_env(EnvForm f, const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
                 const PackedPtrs &pp);
@@ -2659,6 +2661,26 @@ int chub_pile_obs_device(chub_env *e, uint32_t fields, const uint8_t *d_mask, fl
     (void) hipGetLastError();
     if (const int rc = sync_ctx(e, (hipStream_t) stream)) return rc;  // (nothing to do inside a capture: chub_graph_begin has done it)
     launch_pile_obs(e->hp, e->d_ctx, fields, d_mask, e->d_cls_soc, d_out, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_station_profile_size(uint32_t fields, int32_t buckets) {
+    if (fields == 0u || (fields >> CHUB_SP_COUNT) != 0u) return fail(CHUB_ERR_ARG, "fields: a non-empty mask over the CHUB_SP_* fields");
+    if (buckets < 1 || buckets > 32) return fail(CHUB_ERR_ARG, "buckets: 1 .. 32");
+    return 2 * __builtin_popcount(fields) * buckets;
+}
+
+int chub_station_profile_device(chub_env *e, uint32_t fields, int32_t buckets, const uint8_t *d_mask, float *d_out, void *stream) {
+    if (!e || !d_out) return fail(CHUB_ERR_ARG, "null argument");
+    if (chub_station_profile_size(fields, buckets) < 0) return CHUB_ERR_ARG;
+    if (e->tape_only)
+        return fail(CHUB_ERR_UNSUPPORTED,
+                    "chub_station_profile_device is not supported on a tape handle (chub_tape_register_soc rewrites the class tables)");
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    if (const int rc = sync_ctx(e, (hipStream_t) stream)) return rc;  // (nothing to do inside a capture: chub_graph_begin has done it)
+    launch_station_profile(e->hp, e->d_ctx, fields, buckets, d_mask, e->d_cls_soc, d_out, (hipStream_t) stream);
     HIP_TRY(hipGetLastError());
     return CHUB_OK;
 }

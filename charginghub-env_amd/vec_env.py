@@ -519,6 +519,29 @@ class VecChargingHub(object):
             self._lib.chub_free_device(self._device, d)
         return out
 
+    # ---- per-station deadline profiles on the device (chub_station_profile_device): who is due by when
+    def station_profile_device(self, d_out, fields=None, buckets=8, d_mask=0, stream=0):
+        """the stations' cars binned by the time they have left, into device memory: d_out [N, 2, C, B] f32 -- env, station, the C fields
+        asked for in the order of _lib.SP_NAMES, then bucket min(left, B) - 1.  fields: names, a bit mask, or None for all seven; d_mask
+        [N] u8 in device memory: only the blocks of the envs it names are written.  The shape does not depend on the hub.  One launch on
+        `stream`: no synchronisation, nothing of the simulation changes, recordable into a graph."""
+        check(self._lib.chub_station_profile_device(self._h, _lib.sp_fields_mask(fields), int(buckets), d_mask or None, d_out, stream or None))
+
+    def station_profile(self, fields=None, buckets=8):
+        """station_profile_device into host memory: float32 [N, 2, C, B] (the convenience form: it allocates, synchronises and copies)"""
+        mask = _lib.sp_fields_mask(fields)
+        check(min(self._lib.chub_station_profile_size(mask, int(buckets)), 0))
+        out = np.zeros((self.n_envs, 2, len(_lib.sp_fields_names(mask)), int(buckets)), dtype=np.float32)
+        d = C.c_void_p()
+        check(self._lib.chub_malloc_device(self._device, out.nbytes, C.byref(d)))
+        try:
+            check(self._lib.chub_sync(self._h))  # (calls in flight on any stream write the state)
+            check(self._lib.chub_station_profile_device(self._h, mask, int(buckets), None, d, None))
+            check(self._lib.chub_copy_to_host(self._device, _ptr(out), d, out.nbytes, None))
+        finally:
+            self._lib.chub_free_device(self._device, d)
+        return out
+
     def station_scalars(self):
         out = np.zeros((self.n_envs, 2, 8), dtype=np.float64)
         check(self._lib.chub_get_station_scalars(self._h, _ptr(out)))

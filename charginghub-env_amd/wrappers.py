@@ -269,16 +269,29 @@ class TorchHubVecEnv(object):
     look, as CUDA tensors filled on torch's stream -- no device read, no wait, whatever the envs' clocks are.
 
     ``pile_obs=("car", "emergency", "soc")`` (any of _lib.PILE_NAMES; None: off) makes ``pile_obs()`` available: the per-pile columns
-    the reference keeps in Station::situation, as one [N, C, S] CUDA tensor (chub_pile_obs_device); ``pile_names`` is the column order."""
+    the reference keeps in Station::situation, as one [N, C, S] CUDA tensor (chub_pile_obs_device); ``pile_names`` is the column order.
+
+    ``station_profile=dict(fields=("cars", "must_charge", "power"), buckets=8)`` (fields: any of _lib.SP_NAMES, None for all; None: off)
+    makes ``station_profile()`` available: each station's cars binned by the time they have left, as one [N, 2, C, B] CUDA tensor whose
+    shape does not depend on the hub (chub_station_profile_device); ``profile_names`` is the column order."""
 
     def __init__(self, n_envs, station_list, station_type_list, seed=0, device=0, autoreset=True, episode_stats=False, pile_obs=None,
-                 **hub_kwargs):
+                 station_profile=None, **hub_kwargs):
         import torch  # before libchub is loaded by VecChargingHub: both must share one HIP runtime
 
         if not (autoreset is True or autoreset is False or autoreset == "per_env"):
             raise ValueError("autoreset must be True, False or 'per_env', not %r" % (autoreset,))
         self._pile_mask = None if pile_obs is None else _lib.pile_fields_mask(pile_obs)  # (ValueError for an unknown name, before anything is built)
         self.pile_names = () if pile_obs is None else _lib.pile_fields_names(self._pile_mask)
+        self._sp_mask = self._sp_buckets = None
+        if station_profile is not None:  # (ValueError for an unknown name or key, before anything is built)
+            unknown = set(station_profile) - {"fields", "buckets"}
+            if unknown:
+                raise ValueError("station_profile: a dict of fields and buckets, not %s" % sorted(unknown))
+            self._sp_mask, self._sp_buckets = _lib.sp_fields_mask(station_profile.get("fields")), int(station_profile.get("buckets", 8))
+            if not 1 <= self._sp_buckets <= 32:
+                raise ValueError("station_profile: buckets 1 .. 32, not %d" % self._sp_buckets)
+        self.profile_names = () if self._sp_mask is None else _lib.sp_fields_names(self._sp_mask)
         self.torch = torch
         self.device = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
         if self.device.type == "cuda":
@@ -304,6 +317,19 @@ class TorchHubVecEnv(object):
         self._pile_buf = None
         if self._pile_mask is not None:
             self._pile_buf = torch.zeros((self.num_envs, len(self.pile_names), self.vec.n_slots), dtype=torch.float32, device=self.device)
+
+        self._sp_buf = None
+        if self._sp_mask is not None:
+            self._sp_buf = torch.zeros((self.num_envs, 2, len(self.profile_names), self._sp_buckets), dtype=torch.float32, device=self.device)
+
+    def station_profile(self):
+        """float32 [N, 2, C, B] CUDA tensor: for every env and station the columns of ``profile_names`` over the B buckets of time left, as
+        the piles stand after the last reset / step.  Filled by one launch on torch's current stream, without a wait; it is ONE buffer,
+        overwritten by the next call."""
+        if self._sp_buf is None:
+            raise RuntimeError("station profiles are off: construct with station_profile=dict(fields=(names of _lib.SP_NAMES), buckets=B)")
+        self.vec.station_profile_device(self._sp_buf.data_ptr(), self._sp_mask, self._sp_buckets, stream=self._stream())
+        return self._sp_buf
 
     def pile_obs(self):
         """float32 [N, C, S] CUDA tensor: for every env the columns of ``pile_names`` over its S piles in hub-slot order (station 0's

@@ -79,7 +79,7 @@ def device_resident(n=65536):
         print("3. skipped: torch is not installed")
         return
 
-    env = chub.TorchHubVecEnv(n, seed=0, pile_obs=("car", "emergency"), **HUB)
+    env = chub.TorchHubVecEnv(n, seed=0, pile_obs=("car", "emergency"), station_profile=dict(fields=("cars", "power"), buckets=8), **HUB)
     obs = env.reset()
     actions = torch.rand((n, env.act_dim), device="cuda") * 2 - 1
     for _ in range(96):
@@ -108,6 +108,10 @@ def device_resident(n=65536):
     obs, reward, done, _ = env.step(urgent)
     print("   per-pile columns %s: %.1f cars per env, %.1f of them urgent" % (env.pile_names, float(car.sum(1).mean()),
                                                                              float(((car > 0) & (emergency >= 0.25)).sum(1).float().mean())))
+    # a station-level policy sees who is due by when, [n, 2, columns, buckets] whatever the hub's size; here the kW of the cars due within
+    # two slots, per station: an action row of the scalar-load control (VecChargingHub.step_load*)
+    load = env.station_profile()[:, :, 1, :2].sum(-1)
+    print("   station profiles %s: %.1f kW per station due within two slots" % (env.profile_names, float(load.mean())))
     # population-based selection without leaving the device: the worst tenth becomes a copy of the best tenth (each clone keeps its own
     # random streams, so it parts from its source at the next step)
     k = max(1, n // 10)

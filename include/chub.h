@@ -550,6 +550,42 @@ enum {
 int chub_pile_obs_columns(uint32_t fields);
 int chub_pile_obs_device(chub_env *env, uint32_t fields, const uint8_t *d_mask, float *d_out, void *stream);
 
+/* ---- per-station deadline profiles on the device -------------------------------------------------------------------------------------
+ * A policy that sets a station's load (chub_step_load*) must know how much charging falls due by when: the station's cars binned by the
+ * time they have left, with what they still need.  chub_station_profile_device writes that histogram for every env and both stations into
+ * the caller's device memory in ONE launch on `stream`; its shape depends on (fields, buckets) alone, never on the hub, so one policy
+ * serves hubs of 2 piles and of 8192.
+ *   fields   a bit mask over the CHUB_SP_* enum (bit f = field f); C = its popcount columns come out, in ascending field order
+ *   buckets  B, 1 .. 32.  With left = stay_time - already_stay_time as chub_get_slots reports it, a pile with a car falls into bucket
+ *            min(left, B) - 1: B = 1 gives plain station totals, the last bucket collects every longer stay (a COMPAT stay may exceed 31)
+ *   d_out    [N][2][C][B] f32: env, station, column, bucket.  chub_station_profile_size gives the floats per env, 2 * C * B, for valid
+ *            arguments (it needs no device).  A station of 0 piles gives a block of zeros.
+ *   d_mask   [N] u8 in device memory or NULL: with a mask only the blocks of the envs whose byte is non-zero are written.
+ * Every value is defined on what chub_get_slots / chub_pile_obs_device report for the station's piles with car == 1 at the same moment,
+ * over the cars of the bucket:
+ *   CARS            number of cars                      CHARGING        cars with charge == 1
+ *   MUST_CHARGE     cars with emergency == 10 (the step's must_charge predicate: judge_feasibility forces these on)
+ *   POWER           sum of power, in units of 2^-19 kW  POWER_CHARGING  the same over the cars with charge == 1
+ *   EMERGENCY       sum of emergency, units of 2^-20    SOC_GAP         sum of f32(target_soc - soc), units of 2^-16 %
+ * The four sums are integer sums (the convention of the PHILOX station sums): each term is llrint((double) x * 2^q), round-half-even, the
+ * terms are added as signed 64-bit integers and the result is (float) sum * 2^-q -- independent of lane order, workgroup shape and launch
+ * form, so two calls on one state give identical bits.  Counts are exact.
+ * Manners are chub_pile_obs_device's: it reads simulation state and writes d_out, nothing else (no tick, no clock, no draw); it returns
+ * after enqueueing (no synchronisation, no allocation, no staging copy); valid at any point after the first reset, after resets and steps
+ * of every form, chub_copy_envs* and chub_set_state, on lock-step and per-env clocks, with or without per-env parameter rows, telemetry
+ * or the ledger, in all three RNG modes and for every hub shape; recordable between chub_graph_begin and chub_graph_end, where it does
+ * not count towards the even number of resets + steps.  Cost follows the field set: CARS and CHARGING need the state word alone,
+ * MUST_CHARGE, POWER* and EMERGENCY add the class row or hot record, SOC_GAP alone the SoC (a table read in PHILOX, a replay of the
+ * car's steps in COMPAT and PHILOX_CURVES).
+ * CHUB_ERR_ARG: null handle, null d_out, fields 0 or with bits from CHUB_SP_COUNT up, buckets outside 1 .. 32 (chub_station_profile_size
+ * returns the same code).  CHUB_ERR_UNSUPPORTED with a message: tape handles, as for chub_pile_obs_device. */
+enum {
+    CHUB_SP_CARS = 0, CHUB_SP_CHARGING, CHUB_SP_MUST_CHARGE, CHUB_SP_POWER, CHUB_SP_POWER_CHARGING, CHUB_SP_EMERGENCY, CHUB_SP_SOC_GAP,
+    CHUB_SP_COUNT
+};
+int chub_station_profile_size(uint32_t fields, int32_t buckets);
+int chub_station_profile_device(chub_env *env, uint32_t fields, int32_t buckets, const uint8_t *d_mask, float *d_out, void *stream);
+
 /* The FCEV waiting list is unbounded as in the reference (HYD:264-265): the entries a list that still gets served can
  * hold are kept one by one, and once no prefix of it fits into 15 minutes any more (HYD:270-276: nobody is served again
  * until reset and the list only grows) its entries are folded into their count and running sums, which is all the
