@@ -85,11 +85,52 @@ CHUB_HD int pkd_line(uint32_t w) { return (int) (w & 15u); }
 CHUB_HD int pkd_flow(uint32_t w) { return ((int) (w << 16)) >> 20; }
 CHUB_HD int pkd_cars(uint32_t w) { return (int) (w >> 16); }
 
+// ---------------------------------------------------------------------------------------- slot state
+// COMPAT keeps, per slot, the 16-byte hot record of SlotArrays (power, arrival SoC, t_soc, meta) and evaluates the charge
+// curves in the step (the reference's streams make the arrival SoC a continuous value).
+//
+// PHILOX keeps FOUR bytes per slot and no curve is evaluated in the step at all.  The arrival SoC takes one of kSocLevels
+// classes, and a car's whole charging history is the deterministic chain soc -> soc_to_time -> +1 slot -> time_to_soc /
+// time_to_power (car_step, CHS.hpp:900-905 / 1065-1070) from that class: Tables::cls[k] holds, per class, (power, t_soc)
+// after n = 0 .. kClsRow-1 car_steps, built once on the host with the same curve functions (chub_curves.h).  The slot keeps ONE word:
+//   bits 0-4   stay_time - already_stay_time (0 = empty)        bit 5      charging this step
+//   bits 6-10  n = car_steps taken since arrival                 bits 11-21 arrival-SoC class
+//   bits 22-31 target-SoC level l (target = 80 + 20 * l / 999, CHS.hpp:35-44)
+// and everything the step needs follows from two reads issued together once the word is there: one 16-byte row read (entries n
+// and n + 1: where the car is on its curve and where one more car_step takes it) and soc_to_time(target) = Tables::ttab2[k][l], 4
+// bytes of a 4 KB table that lives in every CU's vector L1.  Round 3 kept that f32 in a second state word (8 bytes per slot, 12 B
+// read + 4 B written per slot and step); now a step reads 4 B and writes 4 B of state per slot.  stay_time itself (introspection
+// only: Station::stay_time, CHS.hpp:245) goes to a cold byte array when the car is admitted.
+CHUB_HD int ps_tl(uint32_t w) { return (int) (w & 31u); }
+CHUB_HD uint32_t ps_n(uint32_t w) { return (w >> 6) & 31u; }
+CHUB_HD uint32_t ps_cls(uint32_t w) { return (w >> 11) & 2047u; }
+CHUB_HD uint32_t ps_lev(uint32_t w) { return w >> 22; }
+CHUB_HD uint32_t ps_make(int stay, uint32_t cls, uint32_t lev) {  // a car that has just arrived
+    return (uint32_t) stay | (cls << 11) | (lev << 22);
+}
+constexpr uint32_t kPsChg = 32u, kPsStep = 64u;  // the charging flag; one more car_step
+static_assert(kSocLevels <= (1 << 11) && kLevels <= (1 << 10) && kClsRow <= 32, "field widths of the state word");
+constexpr int kMaxStay = 31;  // 5-bit fields; chub_create refuses curves whose stays could exceed it
+
+// COMPAT hot record, word y: the car's ARRIVAL SoC (round 6; until then soc_to_time(target), with the arrival SoC in a cold array of its own whose
+// 4-byte store per new car was a read-modify-write of a whole sector).  soc_to_time(target) is one of 1000 values per station -- the target is
+// level l of uniform_rand(80, 100) -- read from Tables::ttab[k] by the level kept in the record's word; chub_create checks once, on the device, that
+// the table's entries are the bits the device's own soc_to_time gives (k_check_ttab): the table may then stand in for the function.
+// The record's fourth word: bits 0-6 stay_time - already_stay_time (0 = empty), bit 7 charging this step, and above the flag the car's meta
+// bits: stay_time (7 bits) | target level << 7 | car_steps taken << 17 (its SoC is replayed from them on demand).  The layout is written
+// here: hot_tl / hot_level / kMetaStep for those who look at the word alone, CompatSlot (chub_kernels.hip) for the whole record.  Two places
+// spell it out beside these: slot_body_split2 packs the word itself (through CompatSlot k_slot_walk2 spilt one more VGPR) and k_compat_empties
+// masks the stay itself (noted there); the walks' var[] records carry the meta bits alone (stay | level << 7).  The host never reads the word:
+// introspection decodes a pile on the device (pile_decode, chub_kernels.hip).
+CHUB_HD int hot_tl(uint32_t w) { return (int) (w & 127u); }
+CHUB_HD int hot_level(uint32_t w) { return (int) ((w >> 15) & 1023u); }
+constexpr int kMetaStep = 1 << 17;  // one more car_step on the car's account
+
 struct SlotArrays {          // index = base_k + env*S_k + slot  (station-major)
     // the COMPAT hot record, one 16-byte load and one 16-byte store per slot and step:
     //   .x power      kW at the car's current point of the curve (Station::situation["power"])
     //   .y arrive_soc the car's arrival SoC (Station::situation["init_soc"]): its current SoC = this advanced by the recorded number of car_steps
-    //                 (k_replay_soc, on demand).  soc_to_time(target) is NOT kept: it is Tables::ttab[k][level] (checked at create: k_check_ttab)
+    //                 (replay_soc_steps, on demand).  soc_to_time(target) is NOT kept: it is Tables::ttab[k][level] (checked at create: k_check_ttab)
     //   .z t_soc      soc_to_time(soc)      -- cached, what car_step and calculate_needed both need
     //   .w bits 0-6 stay_time - already_stay_time (0 = empty), bit 7 charging this step, bits 8-14 stay_time,
     //      bits 15-24 target-SoC level l (target = 80 + 20 * l / 999, CHS.hpp:35-44), bits 25-31 car_steps taken since arrival
@@ -225,6 +266,11 @@ struct HubParams {
     int32_t soc_curves;      // CHUB_RNG_PHILOX_CURVES: a PHILOX handle (rng_mode) whose slots run k_slot_curves (continuous arrival SoC, curves on the device)
 };
 
+// The slot layouts (SlotArrays) and the one a handle keeps: what k_pile_obs, k_station_profile and k_copy_envs are instantiated over
+enum { LAYOUT_PHILOX = 0, LAYOUT_CURVES = 1, LAYOUT_COMPAT = 2 };
+constexpr int MODE_COMPAT = 0, MODE_PHILOX = 1;  // HubParams::rng_mode
+CHUB_HD int slot_layout(const HubParams &hp) { return hp.rng_mode != MODE_PHILOX ? LAYOUT_COMPAT : hp.soc_curves ? LAYOUT_CURVES : LAYOUT_PHILOX; }
+
 // Per-env hub parameters (chub_create_params): the HubParams constants that follow from the eight scalar constructor kwargs, one
 // value per env, derived by the same host code (derive_env_consts in chub_runtime.cpp).  Null on a homogeneous handle.
 enum EnvPrm {
@@ -279,8 +325,6 @@ struct CopyArgs {
     CHUB_G(const double) src_rows;   // per-env hub parameters: the raw rows [N][8] f64 (chub_env_params), or null
     CHUB_G(double) dst_rows;
 };
-
-enum { COPY_PHILOX = 0, COPY_CURVES = 1, COPY_COMPAT = 2 };  // k_copy_envs: the slot layouts (SlotArrays)
 
 // host-side copies of the device pointers the packed slot kernel takes as kernel arguments (launch_slot)
 struct PackedPtrs {

@@ -13,9 +13,11 @@
 //           reward, done, exogenous update (PV / wind / price OU) and the normalised observation.  The J2601 breakpoints
 //           are immediates; the PV and wind rows of the current slot and the electrolyser action->power table are staged
 //           in LDS; its last workgroups draw the next step's state-independent variates.  MULTI: per-env clocks.
-//   k_reset_levels, k_draw_levels, k_compat_ctor_sweep, k_replay_soc, k_random_actions, k_tick_advance, k_fill_clocks: small
-//           helpers (reset draws, a step's own station draws, COMPAT constructor replay, SoC introspection, bench policy,
+//   k_reset_levels, k_draw_levels, k_compat_ctor_sweep, k_random_actions, k_tick_advance, k_fill_clocks: small
+//           helpers (reset draws, a step's own station draws, COMPAT constructor replay, bench policy,
 //           graph replays, per-env clocks).
+//   k_pile_obs, k_station_profile: every pile's Station::situation values by ONE decode (pile_decode), as columns and as
+//           per-station bins; chub_get_slots is k_pile_obs with every field.
 //
 // No MFMA: there is no dense contraction anywhere in this path.  By bytes it is HBM-bound; measured VALU
 // issue, the vector L1's access rate and HBM streaming are each more than half used.
@@ -243,8 +245,6 @@ __device__ __forceinline__ int prefix_count(uint64_t m) {
     return (int) __builtin_amdgcn_mbcnt_hi((uint32_t) (m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m, 0u));
 }
 
-constexpr int MODE_COMPAT = 0, MODE_PHILOX = 1;
-
 // XCD-aware work order.  The dispatcher hands workgroup b of a launch to XCD b % 8 (each XCD has its own L2); with this mapping XCD x works
 // on ONE contiguous eighth of the launch's tiles (its b / 8-th) instead of on every eighth tile, so that neighbouring tiles -- which share
 // cache lines at their borders -- share an L2 (slot kernel: L2 misses - 14 %, fabric writes - 11.5 %) and a CU touches one eighth of every
@@ -400,31 +400,7 @@ __device__ __forceinline__ int dk_want(uint32_t dk) { return (int) (dk & 255u); 
 __device__ __forceinline__ int dk_flow(uint32_t dk) { return (int) ((dk >> 8) & 255u); }
 
 // ---------------------------------------------------------------------------------------- slot state
-// COMPAT keeps, per slot, the 16-byte hot record of SlotArrays (power, t_target, t_soc, meta) and evaluates the charge
-// curves in the step (the reference's streams make the arrival SoC a continuous value).
-//
-// PHILOX keeps FOUR bytes per slot and no curve is evaluated in the step at all.  The arrival SoC takes one of kSocLevels
-// classes, and a car's whole charging history is the deterministic chain soc -> soc_to_time -> +1 slot -> time_to_soc /
-// time_to_power (car_step, CHS.hpp:900-905 / 1065-1070) from that class: Tables::cls[k] holds, per class, (power, t_soc)
-// after n = 0 .. kClsRow-1 car_steps, built once on the host with the same curve functions (chub_curves.h).  The slot keeps ONE word:
-//   bits 0-4   stay_time - already_stay_time (0 = empty)        bit 5      charging this step
-//   bits 6-10  n = car_steps taken since arrival                 bits 11-21 arrival-SoC class
-//   bits 22-31 target-SoC level l (target = 80 + 20 * l / 999, CHS.hpp:35-44)
-// and everything the step needs follows from two reads issued together once the word is there: one 16-byte row read (entries n
-// and n + 1: where the car is on its curve and where one more car_step takes it) and soc_to_time(target) = Tables::ttab2[k][l], 4
-// bytes of a 4 KB table that lives in every CU's vector L1.  Round 3 kept that f32 in a second state word (8 bytes per slot, 12 B
-// read + 4 B written per slot and step); now a step reads 4 B and writes 4 B of state per slot.  stay_time itself (introspection
-// only: Station::stay_time, CHS.hpp:245) goes to a cold byte array when the car is admitted.
-__device__ __forceinline__ int ps_tl(uint32_t w) { return (int) (w & 31u); }
-__device__ __forceinline__ uint32_t ps_n(uint32_t w) { return (w >> 6) & 31u; }
-__device__ __forceinline__ uint32_t ps_cls(uint32_t w) { return (w >> 11) & 2047u; }
-__device__ __forceinline__ uint32_t ps_lev(uint32_t w) { return w >> 22; }
-__device__ __forceinline__ uint32_t ps_make(int stay, uint32_t cls, uint32_t lev) {  // a car that has just arrived
-    return (uint32_t) stay | (cls << 11) | (lev << 22);
-}
-constexpr uint32_t kPsChg = 32u, kPsStep = 64u;  // the charging flag; one more car_step
-static_assert(kSocLevels <= (1 << 11) && kLevels <= (1 << 10) && kClsRow <= 32, "field widths of the state word");
-constexpr int kMaxStay = 31;  // 5-bit fields; chub_create refuses curves whose stays could exceed it
+// The PHILOX state word (ps_*) and the COMPAT hot record's fourth word (hot_*) are laid out in chub_device.h.
 
 // car_step (CHS.hpp:900-905 / 1065-1070): soc and power one slot further along the curve, evaluated together.  Same
 // expressions as time_to_soc / time_to_power (chub_curves.h), but the powers of x are shared between the two
@@ -479,19 +455,7 @@ __device__ __forceinline__ void car_step_curves(float tt, bool cp, const CurveCo
     }
 }
 
-// COMPAT hot record, word y: the car's ARRIVAL SoC (round 6; until then soc_to_time(target), with the arrival SoC in a cold array of its own whose
-// 4-byte store per new car was a read-modify-write of a whole sector).  soc_to_time(target) is one of 1000 values per station -- the target is
-// level l of uniform_rand(80, 100) -- read from Tables::ttab[k] by the level kept in the record's word; chub_create checks once, on the device, that
-// the table's entries are the bits the device's own soc_to_time gives (k_check_ttab): the table may then stand in for the function.
-// The record's fourth word: bits 0-6 stay_time - already_stay_time (0 = empty), bit 7 charging this step, and above the flag the car's meta
-// bits: stay_time (7 bits) | target level << 7 | car_steps taken << 17 (its SoC is replayed from them on demand).  The layout is written
-// here: hot_tl / hot_level / kMetaStep for those who look at the word alone, CompatSlot for the whole record.  Two places spell it out
-// beside these: slot_body_split2 packs the word itself (through CompatSlot k_slot_walk2 spilt one more VGPR) and k_compat_empties masks the
-// stay itself (noted there); the walks' var[] records carry the meta bits alone (stay | level << 7).  The host reads the same word
-// (chub_runtime.cpp, introspection).
-__device__ __forceinline__ int hot_tl(uint32_t w) { return (int) (w & 127u); }
-__device__ __forceinline__ int hot_level(uint32_t w) { return (int) ((w >> 15) & 1023u); }
-constexpr int kMetaStep = 1 << 17;  // one more car_step on the car's account
+// The COMPAT hot record as a whole (its words and the fourth word's bits: chub_device.h)
 struct CompatSlot {
     float power, arr_soc, t_soc;
     int tl;       // stay left
@@ -2341,7 +2305,7 @@ __global__ __launch_bounds__(BLOCK, 7) void k_slot(const DevCtx *__restrict__ ct
 //     SlotArrays::hot   [NS][2] f32: power, t_soc = soc_to_time(current SoC)   (8 B read + 8 B written per slot and step)
 //     SlotArrays::wrd   [NS]    u32: PHILOX's state word with the class bits zero: bits 0-4 stay left, bit 5 charging, bits 6-10 car_steps taken,
 //                                    bits 22-31 target level                     (4 B read + 4 B written)
-//     SlotArrays::soc0  [NS]    f32: the arrival SoC, written once at admission (introspection: init_soc, k_replay_soc), as stay8
+//     SlotArrays::soc0  [NS]    f32: the arrival SoC, written once at admission (introspection: init_soc, the SoC's replay), as stay8
 //   a new car: the PHILOX block px.block(SITE_SOC, hub slot, 0) -- word 0 -> soc_from_word (the continuous SoC; PHILOX's class is word 0 >> 21),
 //   word 1 % 1000 the target level, word 2 late_from_word.  Tape mode: car_tape's .x carries the f32 bits of the recorded arrival SoC.
 // Lane = slot, wave-local units of H = pow2 >= S_k lanes (slot_body_wave's shape), one station per workgroup and the station type a template
@@ -4450,45 +4414,12 @@ __device__ __forceinline__ float replay_soc_steps(const HubParams &hp, int k, fl
     }
     return soc;
 }
-__global__ void k_replay_soc(const DevCtx *__restrict__ ctx, float *out) {
-    const HubParams &hp = ctx->hp;
-    const int64_t NS = hp.n_envs * (int64_t) (hp.S[0] + hp.S[1]);
-    const int64_t idx = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= NS) return;
-    const int St = hp.S[0] + hp.S[1];
-    const int k = hp.rng_mode == MODE_PHILOX ? ((int) (idx % St) >= hp.S[0] ? 1 : 0) : (idx >= hp.base[1] ? 1 : 0);
-    float soc = 0.0f;
-    int n = 0;
-    bool car;
-    if (hp.rng_mode == MODE_PHILOX && hp.soc_curves) {  // PHILOX_CURVES: the arrival SoC of the slot's cold array, car_steps from the state word
-        const uint32_t w0 = ctx->sl.wrd[idx];
-        car = ps_tl(w0) != 0;
-        if (car) {
-            soc = ctx->sl.soc0[idx];
-            n = (int) ps_n(w0);
-        }
-    } else if (hp.rng_mode == MODE_PHILOX) {  // arrival SoC of the slot's class, car_steps from the state word
-        const uint32_t w0 = ctx->sl.hot[idx];
-        car = ps_tl(w0) != 0;
-        if (car) {
-            soc = ctx->tb.cls_soc0[k][ps_cls(w0)];
-            n = (int) ps_n(w0);
-        }
-    } else {
-        const uint32_t w = ctx->sl.hot[4 * idx + 3];
-        car = hot_tl(w) != 0;
-        if (car) {
-            soc = __uint_as_float(ctx->sl.hot[4 * idx + 1]);  // the record's second word: the arrival SoC
-            n = (int) (w >> 25);
-        }
-    }
-    out[idx] = replay_soc_steps(hp, k, soc, n);
-}
 
 // -------------------------------------------------------------------- per-pile observations (chub_pile_obs_device)
 // Tables of the PHILOX SoC column, [2][kSocLevels][kClsRow] f32: the class's arrival SoC after n = 0 .. kClsRow-1 car_steps, i.e. what
-// k_replay_soc gives a slot of that class and count, written once per handle BY THE SAME CHAIN ON THE DEVICE (replay_soc_steps: entry n is
-// the chain's value after n steps, so every prefix is the replay's own result).  One lane per (station, class).
+// replay_soc_steps gives a slot of that class and count, written BY THE SAME CHAIN ON THE DEVICE (entry n is the chain's value after n
+// steps, so every prefix is the replay's own result) when the handle is created and whenever a tape rewrites class rows.  One lane per
+// (station, class).
 __global__ void k_build_cls_soc(const DevCtx *__restrict__ ctx, float *out) {
     const HubParams &hp = ctx->hp;
     const int i = (int) (blockIdx.x * blockDim.x + threadIdx.x);
@@ -4507,12 +4438,12 @@ void launch_build_cls_soc(const DevCtx *ctx, float *d_out, hipStream_t stream) {
 }
 
 // Station::situation (CHS.hpp:204-231) and the two stay counters (CHS.hpp:245-246) of every pile as columns: out[env][column][hub slot],
-// the columns of the field mask in ascending order, every value the bits chub_get_slots reports for that pile and field.  Lane = (env, hub
+// the columns of the field mask in ascending order, every value the f32 Station::situation holds for that pile.  Lane = (env, hub
 // slot) of a flat range, so a wave's stores of one column are runs of consecutive floats; no lane talks to another (a unit is not a wave
 // here), so stations of any size take the same path.  LAYOUT: the handle's slot arrays (SlotArrays) -- the output is the same for all three.
 // What a field set does not ask for is not loaded: the state word alone gives car, charge and already_stay_time's `left`; the class row /
 // hot record only power, emergency (with Tables::ttab) and init_soc; stay8 only the two counters; the SoC only the SoC column -- PHILOX reads
-// it from k_build_cls_soc's table, the other two replay the car's steps as k_replay_soc does.
+// it from k_build_cls_soc's table, the other two replay the car's steps (replay_soc_steps).
 struct PileObsArgs {
     const DevCtx *ctx;
     const uint8_t *mask;   // [N] or null: rows of envs whose byte is 0 are not written
@@ -4522,8 +4453,9 @@ struct PileObsArgs {
 };
 enum PileField : uint32_t { PF_CAR = 1u, PF_CHARGE = 2u, PF_EMERGENCY = 4u, PF_POWER = 8u, PF_SOC = 16u, PF_INIT_SOC = 32u, PF_TARGET_SOC = 64u,
                             PF_STAY_TIME = 128u, PF_ALREADY_STAY = 256u };
-// One pile's decode, shared by k_pile_obs and k_station_profile (the profile's bins are sums over exactly these values): what `fields`
-// (PF_* bits) does not ask for is not loaded and stays 0.  i = env * S + slot, the pile's index in the slot-major PHILOX arrays.
+// One pile's decode, THE reader of all three slot layouts: k_pile_obs (and through it chub_get_slots) and k_station_profile (whose bins are
+// sums over exactly these values).  What `fields` (PF_* bits) does not ask for is not loaded and stays 0.  i = env * S + slot, the pile's
+// index in the slot-major PHILOX arrays.  cls_soc (PHILOX): k_build_cls_soc's tables, rebuilt whenever the class rows change.
 struct PileVals {
     int left, stay, lev;
     bool chg;
@@ -4541,7 +4473,7 @@ __device__ __forceinline__ PileVals pile_decode(const DevCtx *__restrict__ ctx, 
     int left, stay = 0, lev, n;
     bool chg;
     float power = 0.0f, t_soc = 0.0f, arrive = 0.0f, soc = 0.0f;
-    if (LAYOUT == COPY_COMPAT) {  // station-major 16-byte records; the fourth word alone when nothing else is asked for
+    if (LAYOUT == LAYOUT_COMPAT) {  // station-major 16-byte records; the fourth word alone when nothing else is asked for
         const int64_t idx = hp.base[k] + env * hp.S[k] + (slot - (k ? S0 : 0));
         u32x4 h = {0u, 0u, 0u, 0u};
         if (want_row || (fields & (PF_SOC | PF_INIT_SOC))) h = *(CHUB_G(const u32x4)) (ctx->sl.hot + 4 * idx);
@@ -4551,10 +4483,10 @@ __device__ __forceinline__ PileVals pile_decode(const DevCtx *__restrict__ ctx, 
         power = s.power; t_soc = s.t_soc; arrive = s.arr_soc;
         if (left > 0 && (fields & PF_SOC)) soc = replay_soc_steps(hp, k, arrive, n);
     } else {
-        const uint32_t w0 = LAYOUT == COPY_CURVES ? ctx->sl.wrd[i] : ctx->sl.hot[i];
+        const uint32_t w0 = LAYOUT == LAYOUT_CURVES ? ctx->sl.wrd[i] : ctx->sl.hot[i];
         left = ps_tl(w0); chg = (w0 & kPsChg) != 0u; lev = (int) ps_lev(w0); n = (int) ps_n(w0);
         if (left > 0) {
-            if (LAYOUT == COPY_CURVES) {
+            if (LAYOUT == LAYOUT_CURVES) {
                 if (want_row) {
                     const f32x2 hv = *(CHUB_G(const f32x2)) ((CHUB_G(const float)) ctx->sl.hot + 2 * i);
                     power = hv.x; t_soc = hv.y;
@@ -4590,20 +4522,17 @@ __global__ __launch_bounds__(256) void k_pile_obs(const PileObsArgs a) {
         const int slot = (int) (i - env * S);
         const int k = slot >= S0 ? 1 : 0;
         const PileVals p = pile_decode<LAYOUT>(ctx, a.cls_soc, fields, env, slot, i);
-        const int left = p.left, stay = p.stay, lev = p.lev;
-        const bool chg = p.chg;
-        const float power = p.power, t_soc = p.t_soc, arrive = p.arrive, soc = p.soc;
-        const bool car = left > 0;
+        const bool car = p.left > 0;
         float *o = a.out + ((int64_t) env * C * S + slot);  // column c of this pile: o[c * S]
         if (fields & PF_CAR) { *o = car ? 1.0f : 0.0f; o += S; }
-        if (fields & PF_CHARGE) { *o = chg ? 1.0f : 0.0f; o += S; }
-        if (fields & PF_EMERGENCY) { *o = car ? emergency_of(tb.ttab[k][lev], t_soc, left) : 0.0f; o += S; }
-        if (fields & PF_POWER) { *o = car ? power : 0.0f; o += S; }
-        if (fields & PF_SOC) { *o = car ? soc : 0.0f; o += S; }
-        if (fields & PF_INIT_SOC) { *o = car ? arrive : 0.0f; o += S; }
-        if (fields & PF_TARGET_SOC) { *o = car ? uniform_level(lev, 80.0f, 100.0f) : 0.0f; o += S; }
-        if (fields & PF_STAY_TIME) { *o = car ? (float) stay : -1.0f; o += S; }
-        if (fields & PF_ALREADY_STAY) { *o = car ? (float) (stay - left) : -1.0f; }
+        if (fields & PF_CHARGE) { *o = p.chg ? 1.0f : 0.0f; o += S; }
+        if (fields & PF_EMERGENCY) { *o = car ? emergency_of(tb.ttab[k][p.lev], p.t_soc, p.left) : 0.0f; o += S; }
+        if (fields & PF_POWER) { *o = car ? p.power : 0.0f; o += S; }
+        if (fields & PF_SOC) { *o = car ? p.soc : 0.0f; o += S; }
+        if (fields & PF_INIT_SOC) { *o = car ? p.arrive : 0.0f; o += S; }
+        if (fields & PF_TARGET_SOC) { *o = car ? uniform_level(p.lev, 80.0f, 100.0f) : 0.0f; o += S; }
+        if (fields & PF_STAY_TIME) { *o = car ? (float) p.stay : -1.0f; o += S; }
+        if (fields & PF_ALREADY_STAY) { *o = car ? (float) (p.stay - p.left) : -1.0f; }
     }
 }
 void launch_pile_obs(const HubParams &hp, const DevCtx *ctx, uint32_t fields, const uint8_t *d_mask, const float *d_cls_soc, float *d_out,
@@ -4613,9 +4542,11 @@ void launch_pile_obs(const HubParams &hp, const DevCtx *ctx, uint32_t fields, co
     int64_t nb = (NS + 255) / 256;
     if (nb > (1 << 20)) nb = 1 << 20;  // (beyond 2^28 piles the lanes stride)
     const PileObsArgs a = {ctx, d_mask, d_cls_soc, d_out, fields};
-    if (hp.rng_mode != MODE_PHILOX) hipLaunchKernelGGL(k_pile_obs<COPY_COMPAT>, dim3((unsigned) nb), dim3(256), 0, stream, a);
-    else if (hp.soc_curves) hipLaunchKernelGGL(k_pile_obs<COPY_CURVES>, dim3((unsigned) nb), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(k_pile_obs<COPY_PHILOX>, dim3((unsigned) nb), dim3(256), 0, stream, a);
+    switch (slot_layout(hp)) {
+    case LAYOUT_COMPAT: hipLaunchKernelGGL(k_pile_obs<LAYOUT_COMPAT>, dim3((unsigned) nb), dim3(256), 0, stream, a); break;
+    case LAYOUT_CURVES: hipLaunchKernelGGL(k_pile_obs<LAYOUT_CURVES>, dim3((unsigned) nb), dim3(256), 0, stream, a); break;
+    default: hipLaunchKernelGGL(k_pile_obs<LAYOUT_PHILOX>, dim3((unsigned) nb), dim3(256), 0, stream, a); break;
+    }
 }
 
 // -------------------------------------------------------------------- per-station deadline profiles (chub_station_profile_device)
@@ -4701,9 +4632,11 @@ void launch_station_profile(const HubParams &hp, const DevCtx *ctx, uint32_t fie
     int64_t nb = (hp.n_envs + group - 1) / group;
     if (nb > (1 << 20)) nb = 1 << 20;  // (beyond that the workgroups stride)
     const StationProfileArgs a = {ctx, d_mask, d_cls_soc, d_out, fields, buckets, group};
-    if (hp.rng_mode != MODE_PHILOX) hipLaunchKernelGGL(k_station_profile<COPY_COMPAT>, dim3((unsigned) nb), dim3(256), 0, stream, a);
-    else if (hp.soc_curves) hipLaunchKernelGGL(k_station_profile<COPY_CURVES>, dim3((unsigned) nb), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(k_station_profile<COPY_PHILOX>, dim3((unsigned) nb), dim3(256), 0, stream, a);
+    switch (slot_layout(hp)) {
+    case LAYOUT_COMPAT: hipLaunchKernelGGL(k_station_profile<LAYOUT_COMPAT>, dim3((unsigned) nb), dim3(256), 0, stream, a); break;
+    case LAYOUT_CURVES: hipLaunchKernelGGL(k_station_profile<LAYOUT_CURVES>, dim3((unsigned) nb), dim3(256), 0, stream, a); break;
+    default: hipLaunchKernelGGL(k_station_profile<LAYOUT_PHILOX>, dim3((unsigned) nb), dim3(256), 0, stream, a); break;
+    }
 }
 
 // PHILOX reset: evs_reset's initial occupancy per (station, env) unit -- init_station_car_number(mu, 3) (CHS.hpp:832-842)
@@ -5172,10 +5105,10 @@ __global__ __launch_bounds__(256) void k_copy_envs(CopyArgs a) {
     const uint32_t S0 = (uint32_t) hd.S[0], S1 = (uint32_t) hd.S[1], S = S0 + S1;  // (the same in both handles)
 
     // ---- slot rows
-    if (LAYOUT == COPY_COMPAT) {
+    if (LAYOUT == LAYOUT_COMPAT) {
         copy_rows<uint32_t>(a.dst->sl.hot, 4 * (hd.base[0] + d * (int64_t) S0), a.src->sl.hot, 4 * (hs.base[0] + s * (int64_t) S0), 4u * S0, lane);
         copy_rows<uint32_t>(a.dst->sl.hot, 4 * (hd.base[1] + d * (int64_t) S1), a.src->sl.hot, 4 * (hs.base[1] + s * (int64_t) S1), 4u * S1, lane);
-    } else if (LAYOUT == COPY_CURVES) {
+    } else if (LAYOUT == LAYOUT_CURVES) {
         copy_rows<uint32_t>(a.dst->sl.hot, 2 * d * (int64_t) S, a.src->sl.hot, 2 * s * (int64_t) S, 2u * S, lane);
         copy_rows<uint32_t>(a.dst->sl.wrd, d * (int64_t) S, a.src->sl.wrd, s * (int64_t) S, S, lane);
         copy_rows<float>(a.dst->sl.soc0, d * (int64_t) S, a.src->sl.soc0, s * (int64_t) S, S, lane);
@@ -5189,7 +5122,7 @@ __global__ __launch_bounds__(256) void k_copy_envs(CopyArgs a) {
     copy_rows<double>(ed.q_time, d * (int64_t) hd.qcap, es.q_time, s * (int64_t) hs.qcap, qcap, lane);
     copy_rows<double>(ed.q_mass, d * (int64_t) hd.qcap, es.q_mass, s * (int64_t) hs.qcap, qcap, lane);
     if (es.hy_env && ed.hy_env) copy_rows<double>(ed.hy_env, d * 102, es.hy_env, s * 102, 102u, lane);
-    if (LAYOUT == COPY_COMPAT) copy_rows<uint32_t>(a.dst->cr.g3[a.dst_rng], d * 32, a.src->cr.g3[a.src_rng], s * 32, 32u, lane);
+    if (LAYOUT == LAYOUT_COMPAT) copy_rows<uint32_t>(a.dst->cr.g3[a.dst_rng], d * 32, a.src->cr.g3[a.src_rng], s * 32, 32u, lane);
 
     // ---- the scalars, one per lane
     const bool rows = a.src->ep.prm && a.dst->ep.prm && a.src_rows && a.dst_rows;
@@ -5212,7 +5145,7 @@ __global__ __launch_bounds__(256) void k_copy_envs(CopyArgs a) {
         ((CHUB_G(u32x4)) a.dst->st.rec)[k * Nd + d] = ((CHUB_G(const u32x4)) a.src->st.rec)[k * Ns + s];
         break;
     }
-    case 16: if (LAYOUT == COPY_COMPAT) a.dst->cr.minstd3[a.dst_rng][d] = a.src->cr.minstd3[a.src_rng][s]; break;
+    case 16: if (LAYOUT == LAYOUT_COMPAT) a.dst->cr.minstd3[a.dst_rng][d] = a.src->cr.minstd3[a.src_rng][s]; break;
     case 17: if (rows) ((CHUB_G(float)) a.dst->ep.hv_rate)[d] = a.src->ep.hv_rate[s]; break;
     case 18: case 19: case 20: case 21: case 22: case 23: case 24:  // the episode ledger (the host has checked: on in both handles or in neither)
         if (ledger) a.dst->es.live[(int64_t) (lane - 18u) * Nd + d] = a.src->es.live[(int64_t) (lane - 18u) * Ns + s];
@@ -5234,9 +5167,9 @@ __global__ __launch_bounds__(256) void k_copy_envs(CopyArgs a) {
 void launch_copy_envs(int layout, const CopyArgs &a, hipStream_t stream) {
     const dim3 grid((unsigned) ((a.count + 3) / 4)), block(256);
     switch (layout) {
-    case COPY_COMPAT: hipLaunchKernelGGL(k_copy_envs<COPY_COMPAT>, grid, block, 0, stream, a); break;
-    case COPY_CURVES: hipLaunchKernelGGL(k_copy_envs<COPY_CURVES>, grid, block, 0, stream, a); break;
-    default: hipLaunchKernelGGL(k_copy_envs<COPY_PHILOX>, grid, block, 0, stream, a); break;
+    case LAYOUT_COMPAT: hipLaunchKernelGGL(k_copy_envs<LAYOUT_COMPAT>, grid, block, 0, stream, a); break;
+    case LAYOUT_CURVES: hipLaunchKernelGGL(k_copy_envs<LAYOUT_CURVES>, grid, block, 0, stream, a); break;
+    default: hipLaunchKernelGGL(k_copy_envs<LAYOUT_PHILOX>, grid, block, 0, stream, a); break;
     }
 }
 
@@ -5360,11 +5293,6 @@ __global__ void k_check_ttab(const DevCtx *__restrict__ ctx, uint32_t *mismatch)
 }
 void launch_check_ttab(const DevCtx *ctx, uint32_t *d_mismatch, hipStream_t stream) {
     hipLaunchKernelGGL(k_check_ttab, dim3((2 * kLevels + 255) / 256), dim3(256), 0, stream, ctx, d_mismatch);
-}
-
-void launch_replay_soc(const HubParams &hp, const DevCtx *ctx, float *d_out, hipStream_t stream) {
-    const int64_t NS = hp.n_envs * (int64_t) (hp.S[0] + hp.S[1]);
-    hipLaunchKernelGGL(k_replay_soc, dim3((unsigned) ((NS + 255) / 256)), dim3(256), 0, stream, ctx, d_out);
 }
 
 void launch_random_actions(const HubParams &hp, uint64_t key, uint32_t batch, float *d_actions, hipStream_t stream) {

@@ -22,7 +22,6 @@ namespace chub {
 template <bool RESET>
 void launch_slot(const CallPlan &cp, const HubParams &hp, const LaunchPlan &lp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream,
                  const PackedPtrs &pp, hipEvent_t ev0, hipEvent_t ev1);
-void launch_replay_soc(const HubParams &hp, const DevCtx *ctx, float *d_out, hipStream_t stream);
 void launch_check_ttab(const DevCtx *ctx, uint32_t *d_mismatch, hipStream_t stream);
 void launch_build_cls_soc(const DevCtx *ctx, float *d_out, hipStream_t stream);
 void launch_pile_obs(const HubParams &hp, const DevCtx *ctx, uint32_t fields, const uint8_t *d_mask, const float *d_cls_soc, float *d_out,
@@ -156,15 +155,15 @@ struct chub_env {
     // switched on -- live [kEpCount][N] f64, finished [kEpCount][N] f64, episodes [N] u32, pending [N] u8 -- which snapshots carry behind the arena
     EpisodeArrays es = {0, 0, nullptr, nullptr, nullptr, nullptr};
     char *d_ledger = nullptr;
-    // chub_pile_obs_device, PHILOX: [2][kSocLevels][kClsRow] f32, a class's SoC after n car_steps (k_build_cls_soc, once at create).  Derived
-    // data outside the arena: no snapshot carries it, no copy moves it
+    // chub_pile_obs_device, PHILOX: [2][kSocLevels][kClsRow] f32, a class's SoC after n car_steps (k_build_cls_soc, at create and when a tape
+    // registers classes).  Derived data outside the arena: no snapshot carries it, no copy moves it
     float *d_cls_soc = nullptr;
     double *d_ep_sum = nullptr;  // k_episode_summary's partials [kEpSumMaxBlocks][kEpSumWords], then the host form's result [kEpSumWords]
     int public_mode = 0;     // the rng_mode the handle was created with: CHUB_RNG_PHILOX_CURVES is hp.rng_mode = PHILOX + hp.soc_curves
     bool tape_only = false;  // ... and once there are any, the handle's class rows are the caller's: only tape resets / steps may admit cars
     uint32_t h_late8[8];
     double h_sin96[96];
-    std::vector<float> h_cls[2], h_soc0[2], h_ttab[2];  // host copies of the class tables (introspection)
+    std::vector<float> h_ttab[2];  // host copy of Tables::ttab (chub_tape_register_soc: the longest target time)
     uint32_t *d_tick_base;     // see HubParams::tick_base
     uint32_t graph_base;       // host mirror of *d_tick_base: ticks covered by the graph replays so far
     uint32_t graph_tick0;      // host state at chub_graph_begin (restored at chub_graph_end: a capture runs nothing)
@@ -865,13 +864,10 @@ static int create_impl(const chub_config *cfg_in, const char *data_dir, int64_t 
         both.insert(both.end(), cls[1].begin(), cls[1].end());
         if ((rc = dev_upload(e, &e->tb.cls[0], both))) return bail(rc);
         e->tb.cls[1] = e->tb.cls[0] + cls[0].size();
-        for (int s = 0; s < 2; s++) {
+        for (int s = 0; s < 2; s++)
             if ((rc = dev_upload(e, &e->tb.cls_soc0[s], cls_soc0[s]))) return bail(rc);
-            e->h_cls[s] = cls[s];
-            e->h_soc0[s] = cls_soc0[s];
-        }
     }
-    for (int s = 0; s < 2; s++) e->h_ttab[s] = ttab[s];  // (both modes: introspection reads a car's target time from its level)
+    for (int s = 0; s < 2; s++) e->h_ttab[s] = ttab[s];
 
     // ---- state in HBM
     const size_t N = (size_t) n_envs, NS = N * (size_t) (hp.S[0] + hp.S[1]);
@@ -984,8 +980,8 @@ static int create_impl(const chub_config *cfg_in, const char *data_dir, int64_t 
         }
     }
     if (rng_mode == CHUB_RNG_PHILOX && !soc_curves) {
-        // the SoC column of chub_pile_obs_device: the class rows' SoC, by the device's own replay of the curve (the chain k_replay_soc runs
-        // per slot for chub_get_slots), so that the table's entries are that replay's bits whatever the host's libm makes of the same chain
+        // the SoC column of k_pile_obs / k_station_profile: the class rows' SoC, by the device's own replay of the curve (replay_soc_steps, the
+        // chain the other two layouts run per pile), so that the table's entries are that replay's bits whatever the host's libm makes of it
         if (hipMalloc((void **) &e->d_cls_soc, (size_t) 2 * kSocLevels * kClsRow * sizeof(float)) != hipSuccess) {
             e->d_cls_soc = nullptr;
             return bail(fail(CHUB_ERR_HIP, "hipMalloc failed"));
@@ -1808,7 +1804,7 @@ static int copy_launch(chub_env *dst, chub_env *src, const int64_t *d_src_idx, c
     a.dst_rng = dst->rng_cur;
     a.src_rows = (const double *) src->d_rows;
     a.dst_rows = (double *) dst->d_rows;
-    launch_copy_envs(dst->hp.rng_mode == CHUB_RNG_COMPAT ? COPY_COMPAT : dst->hp.soc_curves ? COPY_CURVES : COPY_PHILOX, a, s);
+    launch_copy_envs(slot_layout(dst->hp), a, s);
     HIP_TRY(hipGetLastError());
     dst->predrawn = false;   // pk was decoded against the old queues (and a row may have come along): the next launch draws its own
     dst->walked_tick = 0;    // COMPAT: a walk that ran ahead of its step walked the old state
@@ -2367,7 +2363,7 @@ int chub_tape_register_soc(chub_env *e, const float *soc, int32_t count, uint32_
             // chub_create checks for the build's own classes: an arrival SoC whose stay could not is refused, not clamped
             float row[kClsRow * 2];
             build_class_row(fast, cp, e->hp.cc, soc[i], row);
-            if (!(soc[i] >= 0.0f && soc[i] <= 100.0f) || (int) ceilf(tt_max - row[1]) + 15 > 31)
+            if (!(soc[i] >= 0.0f && soc[i] <= 100.0f) || (int) ceilf(tt_max - row[1]) + 15 > kMaxStay)
                 return fail(CHUB_ERR_ARG, "chub_tape_register_soc: an arrival SoC whose stay could exceed 31 slots (or outside 0 .. 100)");
         }
     }
@@ -2378,9 +2374,12 @@ int chub_tape_register_soc(chub_env *e, const float *soc, int32_t count, uint32_
         if (count) {
             HIP_TRY(hipMemcpy((void *) (e->tb.cls[k] + first * kClsRow * 2), rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
             HIP_TRY(hipMemcpy((void *) (e->tb.cls_soc0[k] + first), soc, (size_t) count * sizeof(float), hipMemcpyHostToDevice));
-            memcpy(&e->h_cls[k][first * kClsRow * 2], rows.data(), rows.size() * sizeof(float));
-            memcpy(&e->h_soc0[k][first], soc, (size_t) count * sizeof(float));
         }
+    }
+    if (count) {  // the SoC table follows the rows it is derived from (chub_get_slots reads it on this handle too)
+        if (const int rc = sync_ctx(e, nullptr)) return rc;
+        launch_build_cls_soc(e->d_ctx, e->d_cls_soc, nullptr);
+        HIP_TRY(hipGetLastError());
     }
     for (int i = 0; i < count; i++) class_ids[i] = (uint32_t) (first + (size_t) i);
     e->tape_classes += count;
@@ -2407,7 +2406,6 @@ int chub_set_slots(chub_env *e, const int32_t *rows) {
     HIP_TRY(hipDeviceSynchronize());
     const HubParams &hp = e->hp;
     const size_t N = (size_t) hp.n_envs, S = (size_t) (hp.S[0] + hp.S[1]);
-    const uint32_t n_classes = (uint32_t) kSocLevels;
     std::vector<uint32_t> st(N * S, 0u);
     std::vector<uint8_t> stay(N * S, 0);
     for (size_t env = 0; env < N; env++)
@@ -2416,12 +2414,12 @@ int chub_set_slots(chub_env *e, const int32_t *rows) {
                 const int32_t *r = rows + (env * S + (k ? (size_t) hp.S[0] : 0) + i) * 6;
                 if (r[0] < 0) continue;  // empty slot
                 const int left = r[2] - r[3];
-                if ((uint32_t) r[0] >= n_classes || r[1] < 0 || r[1] >= kLevels || r[2] < 1 || r[2] > 31 || left < 1 || r[4] < 0 ||
+                if ((uint32_t) r[0] >= (uint32_t) kSocLevels || r[1] < 0 || r[1] >= kLevels || r[2] < 1 || r[2] > kMaxStay || left < 1 || r[4] < 0 ||
                     r[4] >= kClsRow)
                     return fail(CHUB_ERR_ARG, "chub_set_slots: field out of range");
                 const size_t idx = env * S + (k ? (size_t) hp.S[0] : 0) + i;  // PHILOX state is hub-major
-                // the state word of chub_kernels.hip: what is left of the stay, charging flag, car_steps taken, class, target level
-                st[idx] = (uint32_t) left | (r[5] ? 32u : 0u) | ((uint32_t) r[4] << 6) | ((uint32_t) r[0] << 11) | ((uint32_t) r[1] << 22);
+                // the state word (chub_device.h): a car of that class and level with `left` to go, r[4] car_steps on, charging or not
+                st[idx] = ps_make(left, (uint32_t) r[0], (uint32_t) r[1]) | (uint32_t) r[4] * kPsStep | (r[5] ? kPsChg : 0u);
                 stay[idx] = (uint8_t) r[2];
             }
     HIP_TRY(hipMemcpy(e->sl.hot, st.data(), st.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -2567,81 +2565,24 @@ int chub_get_slots(chub_env *e, float *out) {
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
     const HubParams &hp = e->hp;
-    const size_t N = (size_t) hp.n_envs, S = (size_t) (hp.S[0] + hp.S[1]), NS = N * S;
-    const bool philox = hp.rng_mode == CHUB_RNG_PHILOX;
-    std::vector<float> soc;
-    const std::vector<float> *cls = e->h_cls, *soc0 = e->h_soc0, *ttab = e->h_ttab;
-    std::vector<uint32_t> hot;
+    const size_t N = (size_t) hp.n_envs, S = (size_t) (hp.S[0] + hp.S[1]), F = (size_t) CHUB_PILE_COUNT;
     int rc;
     if ((rc = sync_ctx(e, nullptr))) return rc;
-    {   // current SoC: the arrival SoC advanced by the recorded number of car_steps, on the device (k_replay_soc)
-        float *d_soc = nullptr;
-        HIP_TRY(hipMalloc((void **) &d_soc, NS * sizeof(float)));
-        launch_replay_soc(hp, e->d_ctx, d_soc, nullptr);
-        rc = fetch(soc, (const float *) d_soc, NS);
-        (void) hipFree(d_soc);
-        if (rc) return rc;
-    }
-    std::vector<uint8_t> stay8;
-    std::vector<uint32_t> wrd;
-    std::vector<float> arr0;
-    const bool curves = hp.soc_curves != 0;
-    if ((rc = fetch(hot, (const uint32_t *) e->sl.hot, (curves ? 2 : philox ? 1 : 4) * NS))) return rc;
-    if (philox && (rc = fetch(stay8, (const uint8_t *) e->sl.stay8, NS))) return rc;
-    if (curves && ((rc = fetch(wrd, (const uint32_t *) e->sl.wrd, NS)) || (rc = fetch(arr0, (const float *) e->sl.soc0, NS)))) return rc;
+    // every pile's nine values by the device's one decode: k_pile_obs with all fields, [N][9][S]
+    std::vector<float> cols;
+    float *d_cols = nullptr;
+    HIP_TRY(hipMalloc((void **) &d_cols, N * F * S * sizeof(float)));
+    launch_pile_obs(hp, e->d_ctx, (1u << CHUB_PILE_COUNT) - 1u, nullptr, e->d_cls_soc, d_cols, nullptr);
+    rc = hipGetLastError() != hipSuccess ? fail(CHUB_ERR_HIP, "the pile decode could not be launched") : fetch(cols, (const float *) d_cols, N * F * S);
+    (void) hipFree(d_cols);
+    if (rc) return rc;
+    // ... re-ordered into the per-station blocks: station k's piles are the hub slots from off_k on
     for (size_t env = 0; env < N; env++) {
-        float *o = out + env * 9 * S;
+        const float *c = cols.data() + env * F * S;
+        float *o = out + env * F * S;
         for (int k = 0; k < 2; k++) {
-            const size_t n = (size_t) hp.S[k];
-            for (size_t i = 0; i < n; i++) {
-                const size_t idx = philox ? env * S + (k ? (size_t) hp.S[0] : 0) + i : (size_t) hp.base[k] + env * n + i;
-                float power = 0, t_target = 0, t_soc = 0, arrive = 0;
-                int left, stay, lev;
-                bool chg;
-                if (curves) {  // PHILOX_CURVES: power and t_soc in the hot record, the state word beside it, the arrival SoC in its cold array
-                    const uint32_t w0 = wrd[idx];
-                    left = (int) (w0 & 31u); chg = (w0 & 32u) != 0; stay = (int) stay8[idx]; lev = (int) (w0 >> 22);
-                    if (left > 0) {
-                        memcpy(&power, &hot[2 * idx + 0], 4);
-                        memcpy(&t_soc, &hot[2 * idx + 1], 4);
-                        arrive = arr0[idx];
-                        t_target = ttab[k][(size_t) lev];
-                    }
-                } else if (philox) {  // 4-byte state: everything else comes from the class row and the table of target times (see chub_kernels.hip)
-                    const uint32_t w0 = hot[idx];
-                    left = (int) (w0 & 31u); chg = (w0 & 32u) != 0; stay = (int) stay8[idx]; lev = (int) (w0 >> 22);
-                    if (left > 0) {
-                        const size_t c = (size_t) ((w0 >> 11) & 2047u), at = (c * kClsRow + ((w0 >> 6) & 31u)) * 2;
-                        power = cls[k][at]; t_soc = cls[k][at + 1]; arrive = soc0[k][c];
-                        t_target = ttab[k][(size_t) lev];
-                    }
-                } else {
-                    memcpy(&power, &hot[4 * idx + 0], 4);
-                    memcpy(&arrive, &hot[4 * idx + 1], 4);  // (the record keeps the arrival SoC; the target's time is the level's table entry)
-                    memcpy(&t_soc, &hot[4 * idx + 2], 4);
-                    const uint32_t w = hot[4 * idx + 3];
-                    left = (int) (w & 127u); chg = (w & 128u) != 0; stay = (int) ((w >> 8) & 127u); lev = (int) ((w >> 15) & 1023u);
-                    if (left > 0) t_target = ttab[k][(size_t) lev];
-                }
-                const bool car = left > 0;
-                const float tr = (float) lev / 999.0f;
-                const float target = tr * (100.0f - 80.0f) + 80.0f;  // uniform_rand(80, 100) at level lev, CHS.hpp:35-44
-                float em = 0.0f;
-                if (car) {  // Station::situation["emergency"] as calculate_needed leaves it (CHS.hpp:879-898)
-                    float need = t_target - t_soc;
-                    if (need > 0) em = ((float) left <= ceilf(need)) ? 10.0f : (float) pow((double) (need / (float) left), 2);
-                }
-                o[0 * n + i] = car ? 1.0f : 0.0f;
-                o[1 * n + i] = chg ? 1.0f : 0.0f;
-                o[2 * n + i] = em;
-                o[3 * n + i] = car ? power : 0.0f;
-                o[4 * n + i] = car ? soc[idx] : 0.0f;
-                o[5 * n + i] = car ? arrive : 0.0f;
-                o[6 * n + i] = car ? target : 0.0f;
-                o[7 * n + i] = car ? (float) stay : -1.0f;
-                o[8 * n + i] = car ? (float) (stay - left) : -1.0f;
-            }
-            o += 9 * n;
+            const size_t n = (size_t) hp.S[k], off = k ? (size_t) hp.S[0] : 0;
+            for (size_t f = 0; f < F; f++, o += n) memcpy(o, c + f * S + off, n * sizeof(float));
         }
     }
     return CHUB_OK;

@@ -520,8 +520,9 @@ int chub_episode_summary(chub_env *env, double *out, int drain);
 /* ---- per-pile observations on the device -----------------------------------------------------------------------------------------
  * A policy sets one bit per pile, and the reference shows it every pile: Station::situation (CHS.hpp:204-231) holds car, charge, emergency,
  * power, soc, init_soc and target_soc per pile, the two stay counters sit beside it (CHS.hpp:245-246).  chub_get_slots reports these nine
- * fields through the host (it synchronises, allocates and decodes in a host loop: a parity instrument); chub_pile_obs_device writes them as
- * columns into the caller's device memory in ONE launch on `stream`, for a policy or a heuristic that never leaves the device:
+ * fields through the host (it synchronises, allocates, runs this launch with every field and re-orders in a host loop: a parity
+ * instrument); chub_pile_obs_device writes them as columns into the caller's device memory in ONE launch on `stream`, for a policy or a
+ * heuristic that never leaves the device:
  *   fields  a bit mask over the CHUB_PILE_* enum (bit f = field f; the enum has chub_get_slots' nine fields in its order); C = its popcount
  *           columns come out, in ascending field order.  chub_pile_obs_columns gives C for a valid mask (it needs no device).
  *   d_out   [N][C][S] f32, S = piles[0] + piles[1]: env-major, then column, then HUB SLOT -- station 0's piles first, as in an action row

@@ -74,6 +74,11 @@ SHAPES = [(rng, piles, False) for rng in MODES for piles in ([20, 25], [1, 1], [
 
 @pytest.mark.parametrize("rng,piles,cc", SHAPES, ids=lambda c: str(c).replace(" ", ""))
 def test_columns_equal_get_slots(rng, piles, cc):
+    """chub_get_slots is k_pile_obs with all nine fields, fetched and re-ordered on the host into per-station blocks: both sides of this bit
+    comparison come from the one device decode.  What it holds is that host re-ordering, in every mode and shape, and (with the field-subset
+    and mask tests below, which compare to the same form) the kernel's column subset / offset logic against the all-fields launch.  The
+    decode itself is held to the oracle and the reference's recordings: test_columns_equal_the_oracle, the COMPAT test behind it, and the
+    slots() comparisons of test_gpu_parity.py, test_gpu_big_stations.py, test_gpu_soc_curves_oracle.py and test_gpu_tape.py."""
     n = 67 if piles == [20, 25] else 5
     v = make(rng, piles, n, constant_charging=cc)
     S = piles[0] + piles[1]
@@ -101,37 +106,53 @@ def test_columns_equal_get_slots(rng, piles, cc):
     v.close()
 
 
-# ---- 2. against the oracle (Philox modes) and the reference's recording (COMPAT), not through the host decode
-@pytest.mark.parametrize("rng", ["philox", "philox_curves"])
-def test_columns_equal_the_oracle(rng):
-    """all nine columns bit for bit: tests/test_gpu_parity.py and tests/test_gpu_soc_curves_oracle.py hold chub_get_slots' power and emergency
-    to the oracle's by uint32 equality like the other seven, so the same holds here"""
+# ---- 2. against the oracle (Philox modes) and the reference's recording (COMPAT): the decode itself
+# (a PHILOX_CURVES handle takes stations of at most 64 piles: [65, 3] exists in PHILOX alone, as in SHAPES above)
+ORACLE_SHAPES = [(rng, piles) for rng in ("philox", "philox_curves") for piles in ([20, 25], [1, 1], [0, 7], [64, 64])] + [("philox", [65, 3])]
+
+
+@pytest.mark.parametrize("rng,piles", ORACLE_SHAPES, ids=lambda c: c if isinstance(c, str) else "%d,%d" % tuple(c))
+def test_columns_equal_the_oracle(rng, piles):
+    """all nine columns bit for bit, from chub_pile_obs_device and from chub_get_slots: tests/test_gpu_parity.py and
+    tests/test_gpu_soc_curves_oracle.py hold chub_get_slots' power and emergency to the oracle's by uint32 equality like the other seven, so
+    the same holds here.  The shapes are test_columns_equal_get_slots' within the plain oracle's 256 piles per station: one pile, a station
+    of none, a full wave per station and one pile more."""
     chub = hub()
-    kw = dict(BASE, station_list=[20, 25], constant_charging=False, renew_fluctuate=0.0, price_fluctuate=0.0, hydro_loss=0.0)
-    n, seed, env_id0 = 8, 0xC0FFEE12345, 1000
+    kw = dict(BASE, station_list=piles, constant_charging=False, renew_fluctuate=0.0, price_fluctuate=0.0, hydro_loss=0.0)
+    n, steps = (8, 30) if piles == [20, 25] else (5, 12)
+    seed, env_id0, S = 0xC0FFEE12345, 1000, sum(piles)
     v = chub.VecChargingHub(n, seed=seed, rng=rng, env_id0=env_id0, **kw)
     cfg, h = _oracle_vec(kw, n, env_id0, seed, rng=rng)
     o_obs, o_rew, o_done = np.zeros((n, v.obs_dim)), np.zeros(n), np.zeros(n, dtype=np.uint8)
 
     def oracle_form():
         out = []
-        for k, nk in ((0, 20), (1, 25)):
+        for k, nk in enumerate(piles):
             w = np.zeros((n, 9, nk), dtype=np.float32)
             orc.orc_vec_slots(h, k, ptr(w))
             out.append(w)
         return np.concatenate(out, axis=2)
 
+    def check(what):
+        want = oracle_form()
+        assert want.shape == (n, 9, S)
+        same(v.pile_obs(), want, (rng, piles, "pile_obs") + what)
+        same(host_form(v), want, (rng, piles, "slots") + what)
+
     rs = np.random.RandomState(7)
     v.reset()
     orc.orc_vec_reset(h, None, None, ptr(o_obs))
-    same(v.pile_obs(), oracle_form(), (rng, "reset"))
-    for t in range(30):
+    check(("reset",))
+    cars = 0
+    for t in range(steps):
         act = rs.uniform(-1, 1, size=(n, v.act_dim)).astype(np.float32)
         if t % 7 == 0:
-            act[:, :45] = 1.0
+            act[:, :S] = 1.0
         v.step(act)
         orc.orc_vec_step(h, ptr(act), None, ptr(o_obs), ptr(o_rew), ptr(o_done), 4)
-        same(v.pile_obs(), oracle_form(), (rng, "step", t))
+        check(("step", t))
+        cars += int(oracle_form()[:, 0].sum())
+    assert cars > 0  # (the comparison was not one of empty piles)
     orc.orc_vec_destroy(h)
     v.close()
 
