@@ -89,6 +89,23 @@ def sp_fields_names(mask):
     """the columns a mask selects, in the order they come out (ascending field order)"""
     return tuple(name for i, name in enumerate(SP_NAMES) if mask >> i & 1)
 
+
+# the units of chub_load_dispatch's station targets (CHUB_LOAD_KW / CHUB_LOAD_FRACTION of include/chub.h)
+LOAD_KW, LOAD_FRACTION = 0, 1
+LOAD_UNITS = {"kw": LOAD_KW, "fraction": LOAD_FRACTION}
+
+
+def load_units(units):
+    """the units of a station target as chub_load_dispatch's enum value: "kw", "fraction" or the value itself"""
+    if isinstance(units, str):
+        if units not in LOAD_UNITS:
+            raise ValueError("unknown load units %r (one of %s)" % (units, ", ".join(sorted(LOAD_UNITS))))
+        return LOAD_UNITS[units]
+    if units not in (LOAD_KW, LOAD_FRACTION):
+        raise ValueError("load units: 'kw' (%d) or 'fraction' (%d), got %r" % (LOAD_KW, LOAD_FRACTION, units))
+    return int(units)
+
+
 class ChubOptions(C.Structure):
     """chub_options of include/chub.h (all zero = defaults; the library reads no environment variables)"""
     _fields_ = [("slot_kernel", C.c_int32), ("no_arena", C.c_int32), ("fused_step", C.c_int32), ("tile", C.c_int32), ("walk_ahead", C.c_int32), ("work_order", C.c_int32), ("span_steps", C.c_int32), ("span_tails", C.c_int32)]
@@ -193,6 +210,7 @@ def load_library():
         "chub_episode_summary_device": (I, [P, P, I, P]), "chub_episode_summary": (I, [P, P, I]),
         "chub_pile_obs_columns": (I, [C.c_uint32]), "chub_pile_obs_device": (I, [P, C.c_uint32, P, P, P]),
         "chub_station_profile_size": (I, [C.c_uint32, C.c_int32]), "chub_station_profile_device": (I, [P, C.c_uint32, C.c_int32, P, P, P]),
+        "chub_load_dispatch_device": (I, [P, I, P, P, P, P, P, P]), "chub_load_dispatch": (I, [P, I, P, P, P, P]),
         "chub_set_rng_compat_seeds": (I, [P, P]), "chub_set_rng_compat_state": (I, [P, P]),
         "chub_get_rng_compat_state": (I, [P, P]), "chub_compat_replay_constructor": (I, [P]), "chub_set_ou_state": (I, [P, P]),
         "chub_copy_envs": (I, [P, P, P, P, L]), "chub_copy_envs_device": (I, [P, P, P, P, L, P]),
@@ -245,7 +263,7 @@ EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "ch
             "chub_stream_destroy", "chub_stream_sync",
             "chub_set_episode_stats", "chub_has_episode_stats", "chub_get_episode_stats", "chub_get_episode_counts", "chub_episode_stats_device",
             "chub_episode_summary_device", "chub_episode_summary", "chub_pile_obs_columns", "chub_pile_obs_device",
-            "chub_station_profile_size", "chub_station_profile_device"]
+            "chub_station_profile_size", "chub_station_profile_device", "chub_load_dispatch_device", "chub_load_dispatch"]
 
 
 def check(rc):

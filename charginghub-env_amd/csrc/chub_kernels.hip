@@ -4639,6 +4639,221 @@ void launch_station_profile(const HubParams &hp, const DevCtx *ctx, uint32_t fie
     }
 }
 
+// -------------------------------------------------------------------- station-level control (chub_load_dispatch_device)
+// evs_step(float)'s dispatch (catch_load, assign_on_off, rank_power_add: CHS.hpp:1169-1186 / 1480-1497) as a read-only launch in front of ANY
+// step form: one kW target (or a fraction of [min_power, max_power]) per station in, the pile decisions out -- as an action row (+1 / -1 and
+// the caller's two tail entries) and / or as chub_step_bits' words.  The per-pile values are pile_decode's, i.e. k_pile_obs' columns; the
+// target is clamped against the unit's record as catch_load does; the decision is load_says_on, the step's own, plus what judge_feasibility
+// forces on anyway (emergency == 10).  A workgroup owns whole envs, `group` at a time; a group's piles sit in LDS under their group-local
+// index j = e * Sp + slot.  The urgency order (emergency descending, ties by slot: the reference's multimap keyed by -emergency):
+//   BIG = false (stations of at most 64 piles): every pile counts the piles of its unit in front of it (O(S_k) LDS reads) and puts itself
+//       at that rank of its unit's range of s_ord;
+//   BIG = true: one bitonic sort of 64-bit keys over the whole group -- unit | inverted emergency bits (emergency is never negative, so its
+//       bits order as it does) | j | flags -- after which unit (e, k)'s piles are the run from e * Sp + (k ? S0 : 0) on.  A hub of more than
+//       kLdBig piles (group = 1) goes station by station: two passes.
+// Then ONE lane per unit walks its run, adding the cars' powers to the f32 running sum in that order (the sum is sequential in the
+// reference: rank_power_add), all units of the group side by side, and leaves +1 / -1 per pile where the pile's power was.  Every barrier
+// is reached by every lane: the mask, the empty piles and the absent stations skip inside the lane loops.  Rows leave as runs of
+// consecutive floats (lane = hub slot), bits as ballot words (a wave = one word).
+struct LoadDispatchArgs {
+    const DevCtx *ctx;
+    const uint8_t *mask;   // [N] or null: rows of envs whose byte is 0 are not written
+    const float *cls_soc;  // (pile_decode's argument; the SoC is not asked for)
+    const float *loads;    // [N][2] one target per station
+    const float *tail;     // [N][2] the two tail actions, copied into the rows (null without rows)
+    float *actions;        // [N][S + 2] or null
+    uint64_t *bits;        // [N][ceil(S / 64)] or null
+    int units;             // 0 kW, 1 fraction of [min_power, max_power]
+    int group;             // envs a workgroup takes at a time
+};
+constexpr int kLdSmall = 1024, kLdBig = 4096;  // piles a group holds in LDS: 12 KB / 48 KB
+constexpr int kLdWords = 128;                  // bit words of a group (a hub of 8192 piles has 128)
+template <int LAYOUT, bool BIG>
+__global__ __launch_bounds__(256) void k_load_dispatch(const LoadDispatchArgs a) {
+    __shared__ float s_pw[BIG ? kLdBig : kLdSmall];          // by j: the pile's power (0 without a car), then its decision (+1 / -1)
+    __shared__ unsigned long long s_key[BIG ? kLdBig : 1];   // BIG: the sort keys
+    __shared__ float s_em[BIG ? 1 : kLdSmall];               // small: by j, the pile's emergency
+    __shared__ uint32_t s_ord[BIG ? 1 : kLdSmall];           // small: by position in the urgency order, j << 2 | must charge << 1 | car
+    __shared__ unsigned long long s_bits[kLdWords];          // the group's bit words (a pass ORs its station in)
+    const DevCtx *__restrict__ ctx = a.ctx;
+    const HubParams &hp = ctx->hp;
+    const Tables &tb = ctx->tb;
+    const int S0 = hp.S[0], S = S0 + hp.S[1], A = S + 2, W = (S + 63) >> 6, G = a.group;
+    const int64_t N = hp.n_envs;
+    const int tid = (int) threadIdx.x;
+    const bool cp = hp.constant_charging != 0;
+    const int n_pass = (BIG && S > kLdBig) ? 2 : 1;  // (two passes: group is 1)
+    for (int64_t env0 = (int64_t) blockIdx.x * G; env0 < N; env0 += (int64_t) gridDim.x * G) {
+        const int ng = (int) (N - env0 < (int64_t) G ? N - env0 : (int64_t) G);
+        for (int pass = 0; pass < n_pass; pass++) {
+            const int lo = (n_pass == 2 && pass == 1) ? S0 : 0, hi = (n_pass == 2 && pass == 0) ? S0 : S;  // the pass's hub slots
+            const int Sp = hi - lo, n = ng * Sp;
+            int n_pad = 1;
+            if (BIG) while (n_pad < n) n_pad <<= 1;
+            // ---- every pile's car, emergency and power, as k_pile_obs reports them
+            for (int j = tid; j < (BIG ? n_pad : n); j += 256) {
+                float em = 0.0f, pw = 0.0f;
+                bool car = false;
+                int k = 0, e = 0;
+                if (j < n) {
+                    e = j / Sp;
+                    const int slot = lo + (j - e * Sp);
+                    const int64_t env = env0 + e;
+                    k = slot >= S0 ? 1 : 0;
+                    if (!(a.mask && !a.mask[env])) {
+                        const PileVals p = pile_decode<LAYOUT>(ctx, a.cls_soc, PF_EMERGENCY | PF_POWER, env, slot, env * S + slot);
+                        car = p.left > 0;
+                        if (car) { em = emergency_of(tb.ttab[k][p.lev], p.t_soc, p.left); pw = p.power; }
+                    }
+                }
+                if (j < n) s_pw[j] = pw;
+                const uint32_t flags = (car && em == 10.0f ? 2u : 0u) | (car ? 1u : 0u);
+                if (BIG) {
+                    const unsigned long long key = ((unsigned long long) (uint32_t) (e * 2 + k) << 46) |
+                                                   ((unsigned long long) (0x7FFFFFFFu - __float_as_uint(em)) << 15) |
+                                                   (unsigned long long) (((uint32_t) j << 2) | flags);
+                    s_key[j] = j < n ? key : ~0ull;
+                } else {
+                    s_em[j] = em;
+                    s_ord[j] = flags;  // (by j until the ranks are known)
+                }
+            }
+            __syncthreads();
+            // ---- the urgency order
+            if (BIG) {
+                for (int k2 = 2; k2 <= n_pad; k2 <<= 1)
+                    for (int j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
+                        for (int t = tid; t < (n_pad >> 1); t += 256) {
+                            const int i = ((t & ~(j2 - 1)) << 1) | (t & (j2 - 1)), p = i | j2;
+                            const unsigned long long x = s_key[i], y = s_key[p];
+                            if ((x > y) == ((i & k2) == 0)) { s_key[i] = y; s_key[p] = x; }
+                        }
+                        __syncthreads();
+                    }
+            } else {
+                uint32_t mine[(kLdSmall + 255) / 256];  // this lane's piles: position << 2 | flags
+#pragma unroll
+                for (int r = 0; r < (kLdSmall + 255) / 256; r++) {
+                    const int j = tid + 256 * r;
+                    mine[r] = 0u;
+                    if (j < n) {
+                        const int e = j / Sp, slot = j - e * Sp;
+                        const int k = slot >= S0 ? 1 : 0;
+                        const int ub = e * Sp + (k ? S0 : 0), Sk = hp.S[k];
+                        const float em0 = s_em[j];
+                        int rk = 0;
+                        for (int i = ub; i < ub + Sk; i++) {
+                            const float ei = s_em[i];
+                            rk += (ei > em0 || (ei == em0 && i < j)) ? 1 : 0;
+                        }
+                        mine[r] = ((uint32_t) (ub + rk) << 2) | s_ord[j];
+                    }
+                }
+                __syncthreads();
+#pragma unroll
+                for (int r = 0; r < (kLdSmall + 255) / 256; r++) {
+                    const int j = tid + 256 * r;
+                    if (j < n) s_ord[mine[r] >> 2] = ((uint32_t) j << 2) | (mine[r] & 3u);
+                }
+                __syncthreads();
+            }
+            // ---- one lane per unit: the target, then the running sum along the order
+            if (tid < 2 * ng) {
+                const int e = tid >> 1, k = tid & 1;
+                const int64_t env = env0 + e;
+                const int Sk = hp.S[k], off = k ? S0 : 0;
+                if (Sk > 0 && off >= lo && off + Sk <= hi && !(a.mask && !a.mask[env])) {
+                    const StationRec pr = rec_load(ctx->st.rec, (uint32_t) k * (uint32_t) N + (uint32_t) env);
+                    float load = a.loads[env * 2 + k];
+                    if (a.units == 1) {
+                        float f = __fmul_rn(__fadd_rn(load, 1.0f), 0.5f);
+                        f = f < 0.0f ? 0.0f : (f > 1.0f ? 1.0f : f);
+                        load = __fadd_rn(pr.mn, __fmul_rn(f, __fsub_rn(pr.mx, pr.mn)));
+                    }
+                    if (load > pr.mx) load = pr.mx;  // catch_load's clamp (CHS.hpp:358-366)
+                    else if (load < pr.mn) load = pr.mn;
+                    const bool fast = hp.type[k] == 0;
+                    const int base = e * Sp + (off - lo);
+                    float cum = 0.0f;
+                    int cars = 0;
+                    for (int q = 0; q < Sk; q++) {
+                        const uint32_t o = BIG ? ((uint32_t) s_key[base + q] & 0x7FFFu) : s_ord[base + q];
+                        const int j = (int) (o >> 2);
+                        bool on = false;
+                        if (o & 1u) {
+                            cum = __fadd_rn(cum, s_pw[j]);
+                            on = load_says_on(cp, fast, load, cum, cars) || (o & 2u) != 0u;
+                            cars++;
+                        }
+                        s_pw[j] = on ? 1.0f : -1.0f;
+                    }
+                }
+            }
+            __syncthreads();
+            // ---- rows: the pass's pile entries, lane = hub slot; the tail with the last pass
+            if (a.actions) {
+                for (int j = tid; j < n; j += 256) {
+                    const int e = j / Sp;
+                    const int64_t env = env0 + e;
+                    if (a.mask && !a.mask[env]) continue;
+                    a.actions[env * A + (lo + (j - e * Sp))] = s_pw[j];
+                }
+                if (pass == n_pass - 1)
+                    for (int j = tid; j < 2 * ng; j += 256) {
+                        const int64_t env = env0 + (j >> 1);
+                        if (a.mask && !a.mask[env]) continue;
+                        a.actions[env * A + S + (j & 1)] = a.tail[env * 2 + (j & 1)];
+                    }
+            }
+            // ---- bits: lane = bit of the group's words, a wave = one word (ng * W * 64 positions: whole waves)
+            if (a.bits) {
+                for (int b = tid; b < ng * W * 64; b += 256) {
+                    const int e = b / (W * 64), slot = b - e * (W * 64);
+                    const bool on = slot >= lo && slot < hi && s_pw[e * Sp + (slot - lo)] > 0.0f;
+                    const unsigned long long word = __ballot(on);
+                    if ((tid & 63) == 0) {
+                        const unsigned long long all = (pass ? s_bits[b >> 6] : 0ull) | word;
+                        s_bits[b >> 6] = all;
+                        const int64_t env = env0 + e;
+                        if (pass == n_pass - 1 && !(a.mask && !a.mask[env])) a.bits[env * W + (slot >> 6)] = all;
+                    }
+                }
+            }
+            __syncthreads();  // (the next pass / group overwrites the LDS arrays)
+        }
+    }
+}
+int load_dispatch_group(const HubParams &hp, bool big) {
+    const int S = hp.S[0] + hp.S[1];
+    const int cap = big ? kLdBig : kLdSmall;
+    int group = S > cap ? 1 : cap / S;
+    return group > 128 ? 128 : group;  // (two units per env, one lane each)
+}
+void launch_load_dispatch(const HubParams &hp, const DevCtx *ctx, int units, const uint8_t *d_mask, const float *d_cls_soc, const float *d_loads,
+                          const float *d_tail, float *d_actions, uint64_t *d_bits, hipStream_t stream) {
+    const int S = hp.S[0] + hp.S[1];
+    if (hp.n_envs <= 0 || S <= 0) return;
+    const bool big = hp.S[0] > 64 || hp.S[1] > 64;
+    const int group = load_dispatch_group(hp, big);
+    int64_t nb = (hp.n_envs + group - 1) / group;
+    if (nb > (1 << 20)) nb = 1 << 20;  // (beyond that the workgroups stride)
+    const LoadDispatchArgs a = {ctx, d_mask, d_cls_soc, d_loads, d_tail, d_actions, d_bits, units, group};
+    const dim3 grid((unsigned) nb), block(256);
+    switch (slot_layout(hp)) {
+    case LAYOUT_COMPAT:
+        if (big) hipLaunchKernelGGL((k_load_dispatch<LAYOUT_COMPAT, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((k_load_dispatch<LAYOUT_COMPAT, false>), grid, block, 0, stream, a);
+        break;
+    case LAYOUT_CURVES:  // (at most 64 piles per station in this mode)
+        hipLaunchKernelGGL((k_load_dispatch<LAYOUT_CURVES, false>), grid, block, 0, stream, a);
+        break;
+    default:
+        if (big) hipLaunchKernelGGL((k_load_dispatch<LAYOUT_PHILOX, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((k_load_dispatch<LAYOUT_PHILOX, false>), grid, block, 0, stream, a);
+        break;
+    }
+}
+
 // PHILOX reset: evs_reset's initial occupancy per (station, env) unit -- init_station_car_number(mu, 3) (CHS.hpp:832-842)
 // thinned by the balk test of an empty queue -- drawn once per unit here (every lane of the unit used to redo it),
 // handed to k_slot<RESET> through this tick's pk word: arrivals | arrivals that stay << 8.

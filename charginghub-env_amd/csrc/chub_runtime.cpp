@@ -28,6 +28,8 @@ void launch_pile_obs(const HubParams &hp, const DevCtx *ctx, uint32_t fields, co
                      hipStream_t stream);
 void launch_station_profile(const HubParams &hp, const DevCtx *ctx, uint32_t fields, int buckets, const uint8_t *d_mask, const float *d_cls_soc,
                             float *d_out, hipStream_t stream);
+void launch_load_dispatch(const HubParams &hp, const DevCtx *ctx, int units, const uint8_t *d_mask, const float *d_cls_soc, const float *d_loads,
+                          const float *d_tail, float *d_actions, uint64_t *d_bits, hipStream_t stream);
 template <bool RESET>
 void launch_env(EnvForm f, const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
                 const PackedPtrs &pp);
@@ -2624,6 +2626,47 @@ int chub_station_profile_device(chub_env *e, uint32_t fields, int32_t buckets, c
     launch_station_profile(e->hp, e->d_ctx, fields, buckets, d_mask, e->d_cls_soc, d_out, (hipStream_t) stream);
     HIP_TRY(hipGetLastError());
     return CHUB_OK;
+}
+
+// Station-level control: the dispatch of evs_step(float) as a read-only launch (k_load_dispatch) in front of any step form
+int chub_load_dispatch_device(chub_env *e, int units, const float *d_loads, const float *d_tail, const uint8_t *d_mask, float *d_actions,
+                              uint64_t *d_pile_bits, void *stream) {
+    if (!e || !d_loads) return fail(CHUB_ERR_ARG, "null argument");
+    if (!d_actions && !d_pile_bits) return fail(CHUB_ERR_ARG, "chub_load_dispatch: give d_actions, d_pile_bits or both");
+    if (d_actions && !d_tail) return fail(CHUB_ERR_ARG, "chub_load_dispatch: action rows need d_tail (their last two entries)");
+    if (units != CHUB_LOAD_KW && units != CHUB_LOAD_FRACTION) return fail(CHUB_ERR_ARG, "units: CHUB_LOAD_KW or CHUB_LOAD_FRACTION");
+    if (e->tape_only)
+        return fail(CHUB_ERR_UNSUPPORTED, "chub_load_dispatch is not supported on a tape handle (chub_tape_register_soc rewrites the class tables)");
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    if (const int rc = sync_ctx(e, (hipStream_t) stream)) return rc;  // (nothing to do inside a capture: chub_graph_begin has done it)
+    launch_load_dispatch(e->hp, e->d_ctx, units, d_mask, e->d_cls_soc, d_loads, d_tail, d_actions, d_pile_bits, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_load_dispatch(chub_env *e, int units, const float *loads, const float *tail, float *actions, uint64_t *pile_bits) {
+    if (!e || !loads) return fail(CHUB_ERR_ARG, "null argument");
+    if (!actions && !pile_bits) return fail(CHUB_ERR_ARG, "chub_load_dispatch: give actions, pile_bits or both");
+    if (actions && !tail) return fail(CHUB_ERR_ARG, "chub_load_dispatch: action rows need tail (their last two entries)");
+    if (units != CHUB_LOAD_KW && units != CHUB_LOAD_FRACTION) return fail(CHUB_ERR_ARG, "units: CHUB_LOAD_KW or CHUB_LOAD_FRACTION");
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t N = (size_t) e->hp.n_envs, S = (size_t) (e->hp.S[0] + e->hp.S[1]), W = (S + 63) / 64;
+    const size_t b_in = 2 * N * sizeof(float), b_act = actions ? N * (S + 2) * sizeof(float) : 0, b_bits = pile_bits ? N * W * sizeof(uint64_t) : 0;
+    char *d = nullptr;  // loads | tail | bits | rows, one allocation
+    HIP_TRY(hipMalloc((void **) &d, 2 * b_in + b_bits + b_act));
+    float *d_loads = (float *) d, *d_tail = tail ? (float *) (d + b_in) : nullptr;
+    uint64_t *d_bits = pile_bits ? (uint64_t *) (d + 2 * b_in) : nullptr;
+    float *d_act = actions ? (float *) (d + 2 * b_in + b_bits) : nullptr;
+    int rc = CHUB_OK;
+    if (hipMemcpy(d_loads, loads, b_in, hipMemcpyHostToDevice) != hipSuccess || (tail && hipMemcpy(d_tail, tail, b_in, hipMemcpyHostToDevice) != hipSuccess))
+        rc = fail(CHUB_ERR_HIP, "chub_load_dispatch: the inputs could not be copied to the device");
+    if (!rc) rc = chub_load_dispatch_device(e, units, d_loads, d_tail, nullptr, d_act, d_bits, nullptr);
+    if (!rc && (hipDeviceSynchronize() != hipSuccess || (actions && hipMemcpy(actions, d_act, b_act, hipMemcpyDeviceToHost) != hipSuccess) ||
+                (pile_bits && hipMemcpy(pile_bits, d_bits, b_bits, hipMemcpyDeviceToHost) != hipSuccess)))
+        rc = fail(CHUB_ERR_HIP, "chub_load_dispatch: the launch failed or its outputs could not be copied back");
+    (void) hipFree(d);
+    return rc;
 }
 
 int chub_get_station_scalars(chub_env *e, double *out) {

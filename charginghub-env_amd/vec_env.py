@@ -542,6 +542,34 @@ class VecChargingHub(object):
             self._lib.chub_free_device(self._device, d)
         return out
 
+    # ---- station-level control on the device (chub_load_dispatch_device): one target per station -> action rows / one bit per pile
+    def load_dispatch_device(self, d_loads, d_tail, d_actions=0, d_pile_bits=0, units="kw", d_mask=0, stream=0):
+        """the reference's evs_step(float) dispatch as one read-only launch on `stream`: d_loads [N, 2] f32 (one target per station: kW, or
+        with units="fraction" an action in [-1, 1] over the station's [min_power, max_power]) -> d_actions [N, A] f32 (pile entries +1 / -1,
+        then d_tail's [N, 2] entries) and / or d_pile_bits [N, bit_words] u64 (step_bits' layout), for ANY step form to take.  d_mask [N] u8
+        in device memory: only the rows of the envs it names are written.  No synchronisation, nothing of the simulation changes,
+        recordable into a graph."""
+        check(self._lib.chub_load_dispatch_device(self._h, _lib.load_units(units), d_loads, d_tail or None, d_mask or None, d_actions or None,
+                                                  d_pile_bits or None, stream or None))
+
+    def load_dispatch(self, loads, tail, units="kw"):
+        """load_dispatch_device through host memory: loads [N, 2], tail [N, 2] -> (actions float32 [N, A], pile_bits uint64 [N, bit_words])
+        (the convenience form: it allocates, synchronises and copies)"""
+        u = _lib.load_units(units)
+        ld = np.ascontiguousarray(loads, dtype=np.float32)
+        t = np.ascontiguousarray(tail, dtype=np.float32)
+        if ld.shape != (self.n_envs, 2) or t.shape != (self.n_envs, 2):
+            raise AssertionError("loads and tail must have shape (%d, 2)" % self.n_envs)
+        actions = np.zeros((self.n_envs, self.act_dim), dtype=np.float32)
+        bits = np.zeros((self.n_envs, self.bit_words), dtype=np.uint64)
+        check(self._lib.chub_sync(self._h))  # (calls in flight on any stream write the state)
+        check(self._lib.chub_load_dispatch(self._h, u, _ptr(ld), _ptr(t), _ptr(actions), _ptr(bits)))
+        return actions, bits
+
+    def step_load_device(self, d_actions, d_obs, d_reward, d_done, d_exo_z=0, stream=0):
+        """the device-pointer form of step_load (chub_step_load_device): d_actions [N, A] f32 in load_actions' layout"""
+        check(self._lib.chub_step_load_device(self._h, d_actions, d_exo_z or None, d_obs, d_reward, d_done, stream or None))
+
     def station_scalars(self):
         out = np.zeros((self.n_envs, 2, 8), dtype=np.float64)
         check(self._lib.chub_get_station_scalars(self._h, _ptr(out)))

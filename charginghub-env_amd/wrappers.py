@@ -273,14 +273,25 @@ class TorchHubVecEnv(object):
 
     ``station_profile=dict(fields=("cars", "must_charge", "power"), buckets=8)`` (fields: any of _lib.SP_NAMES, None for all; None: off)
     makes ``station_profile()`` available: each station's cars binned by the time they have left, as one [N, 2, C, B] CUDA tensor whose
-    shape does not depend on the hub (chub_station_profile_device); ``profile_names`` is the column order."""
+    shape does not depend on the hub (chub_station_profile_device); ``profile_names`` is the column order.
+
+    ``control="station"`` makes the policy set one load per station instead of one action per pile (the reference's evs_step(float)):
+    ``act_dim`` is 4 whatever the hub -- load of station 0, load of station 1, the two tail actions -- and every ``step`` first turns the
+    loads into an action row the adapter owns (chub_load_dispatch_device, one read-only launch on torch's stream), then takes the step
+    path of its ``autoreset`` mode, ``"per_env"`` included.  ``load_units="fraction"`` (the default) reads a load as an action in [-1, 1]
+    over the station's [min_power, max_power]; ``"kw"`` as kW.  ``step_bits`` is refused in this mode.  The default ``control="pile"``
+    is the adapter described above."""
 
     def __init__(self, n_envs, station_list, station_type_list, seed=0, device=0, autoreset=True, episode_stats=False, pile_obs=None,
-                 station_profile=None, **hub_kwargs):
+                 station_profile=None, control="pile", load_units="fraction", **hub_kwargs):
         import torch  # before libchub is loaded by VecChargingHub: both must share one HIP runtime
 
         if not (autoreset is True or autoreset is False or autoreset == "per_env"):
             raise ValueError("autoreset must be True, False or 'per_env', not %r" % (autoreset,))
+        if control not in ("pile", "station"):  # (ValueError before anything is built)
+            raise ValueError("control must be 'pile' or 'station', not %r" % (control,))
+        self.control = control
+        self._load_units = _lib.load_units(load_units)
         self._pile_mask = None if pile_obs is None else _lib.pile_fields_mask(pile_obs)  # (ValueError for an unknown name, before anything is built)
         self.pile_names = () if pile_obs is None else _lib.pile_fields_names(self._pile_mask)
         self._sp_mask = self._sp_buckets = None
@@ -299,6 +310,12 @@ class TorchHubVecEnv(object):
         self.vec = VecChargingHub(n_envs, station_list, station_type_list, seed=seed, rng="philox", device=int(self.device.index or 0),
                                   **hub_kwargs)
         self.num_envs, self.obs_dim, self.act_dim = self.vec.n_envs, self.vec.obs_dim, self.vec.act_dim
+        self._rows = None
+        if control == "station":  # the policy's row is (load 0, load 1, tail 0, tail 1); the dispatch fills the hub's own [N, A] rows
+            self._rows = torch.zeros((self.num_envs, self.vec.act_dim), dtype=torch.float32, device=self.device)
+            self._loads = torch.zeros((self.num_envs, 2), dtype=torch.float32, device=self.device)
+            self._tail = torch.zeros((self.num_envs, 2), dtype=torch.float32, device=self.device)
+            self.act_dim = 4
         self.per_env = autoreset == "per_env"
         self.autoreset = bool(autoreset)
         self._packed = torch.empty((self.num_envs, self.obs_dim + 2), dtype=torch.float32, device=self.device)
@@ -382,6 +399,12 @@ class TorchHubVecEnv(object):
                 and tuple(a.shape) == (self.num_envs, self.act_dim)):
             raise AssertionError("actions must be a contiguous float32 tensor on %s of shape (%d, %d)"
                                  % (self.device, self.num_envs, self.act_dim))
+        if self._rows is not None:  # station-level control: the loads become the hub's action rows, on the device
+            self._loads.copy_(a[:, :2])
+            self._tail.copy_(a[:, 2:])
+            self.vec.load_dispatch_device(self._loads.data_ptr(), self._tail.data_ptr(), d_actions=self._rows.data_ptr(), units=self._load_units,
+                                          stream=self._stream())
+            a = self._rows
         if self.per_env:  # step + reset of whoever is done, on the device: no clock here, nothing read back
             self.vec.step_autoreset_device(a.data_ptr(), self._packed.data_ptr(), self.last_obs.data_ptr(), stream=self._stream())
             D = self.obs_dim
@@ -418,6 +441,8 @@ class TorchHubVecEnv(object):
         """step() fed one bit per pile + the two tail floats (pack_bits' layout) instead of action rows: 8 W + 8 bytes of action input
         per env instead of 4 (S + 2); on the packed slot kernel the step reads the bits themselves"""
         torch, N, W = self.torch, self.num_envs, self.vec.bit_words
+        if self._rows is not None:
+            raise RuntimeError("step_bits is not available with control='station' (the adapter dispatches the loads into action rows)")
         if self.per_env:
             raise RuntimeError("step_bits is not available with autoreset='per_env' (chub_autoreset_step_device takes action rows)")
         if not (self._on_device(pile_bits) and pile_bits.dtype == torch.int64 and pile_bits.is_contiguous() and tuple(pile_bits.shape) == (N, W)

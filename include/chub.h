@@ -587,6 +587,43 @@ enum {
 int chub_station_profile_size(uint32_t fields, int32_t buckets);
 int chub_station_profile_device(chub_env *env, uint32_t fields, int32_t buckets, const uint8_t *d_mask, float *d_out, void *stream);
 
+/* ---- station-level control on the device: kW targets to pile actions ------------------------------------------------------------------
+ * The reference's station-level control, evs_step(float) (CHS.hpp:1169-1186 / 1480-1497: catch_load, assign_on_off, rank_power_add), takes
+ * one kW target per station and switches the piles on in urgency order until the target is met.  chub_step_load* runs it inside the
+ * wave-local step kernels (COMPAT and PHILOX, homogeneous handles, host masks).  chub_load_dispatch_device is the same dispatch as ONE
+ * read-only launch on `stream` that turns the targets into what EVERY step form takes -- an action row, or one bit per pile -- so that a
+ * policy which sets a station's load (its observations: chub_station_profile_device) runs in all three RNG modes, with per-env rows, under
+ * device masks, through chub_autoreset_step_device, chub_step_bits_device* and the packed kernels, and inside graphs.
+ *   units       CHUB_LOAD_KW: d_loads are kW.  CHUB_LOAD_FRACTION: d_loads are a in [-1, 1] like every other action; f = min(max((a + 1) / 2,
+ *               0), 1) and the target is min_power + f * (max_power - min_power), every operation rounded to f32 (no FMA).
+ *   d_loads     [N][2] f32: the target of station 0 and of station 1 (the entry of a station without piles is not read)
+ *   d_tail      [N][2] f32: the two tail actions, copied into the rows (required with d_actions; not read otherwise)
+ *   d_mask      [N] u8 in device memory or NULL: with a mask only the rows of the envs whose byte is non-zero are written
+ *   d_actions   [N][A] f32 or NULL: pile entries exactly +1.0f (on) or -1.0f (off), then the two tail entries
+ *   d_pile_bits [N][ceil(S / 64)] u64 or NULL: chub_step_bits' layout; bits from S up are zero.  Both outputs, if both are given, agree.
+ * Definition, per env and station k with piles: car, emergency and power of every pile are what chub_pile_obs_device reports; mn and mx are
+ * the f32 min_power and max_power of the unit's record (what chub_get_station_scalars shows).  The target is clamped as catch_load clamps
+ * it (if load > mx: mx, else if load < mn: mn).  The piles are ordered by emergency descending, ties by slot index (the reference's
+ * multimap keyed by -emergency); along that order the power of every pile with a car is added to ONE f32 running sum, sequentially
+ * (rank_power_add).  A car is on iff (double) load + 0.0001 >= (double) the sum up to and including itself; with constant charging iff
+ * fewer than roundf(load / constant_power) cars precede it.  In addition a car with emergency == 10 is on: judge_feasibility forces it on
+ * when the row is stepped, and the outputs say what the step will do.  Stepping the row (chub_step_device*) or the bits
+ * (chub_step_bits_device*) then computes, bit for bit, what chub_step_load_device computes from the same targets wherever no must-charge
+ * car lies beyond the target (the scalar-load step leaves such a car off; a stepped row cannot).
+ * Manners are chub_pile_obs_device's: it reads simulation state and writes its outputs, nothing else (no tick, no clock, no draw); it
+ * returns after enqueueing (no synchronisation, no allocation, no staging copy); valid at any point after the first reset, after resets
+ * and steps of every form, on lock-step and per-env clocks, with or without per-env parameter rows, telemetry or the ledger, in all three
+ * RNG modes and for every hub shape (stations of 0 to 4096 piles); recordable between chub_graph_begin and chub_graph_end, where it does
+ * not count towards the even number of resets + steps.
+ * chub_load_dispatch: the same through host memory, every env (it allocates, copies and synchronises: the convenience form).
+ * CHUB_ERR_ARG: null handle, null loads, both outputs null, d_actions without d_tail, unknown units.  CHUB_ERR_UNSUPPORTED with a message:
+ * tape handles, as for chub_pile_obs_device. */
+enum { CHUB_LOAD_KW = 0, CHUB_LOAD_FRACTION = 1 };
+int chub_load_dispatch_device(chub_env *env, int units, const float *d_loads /* [N,2] */, const float *d_tail /* [N,2] */,
+                              const uint8_t *d_mask /* [N] or NULL */, float *d_actions /* [N,A] or NULL */,
+                              uint64_t *d_pile_bits /* [N,W] or NULL */, void *stream);
+int chub_load_dispatch(chub_env *env, int units, const float *loads, const float *tail, float *actions, uint64_t *pile_bits);
+
 /* The FCEV waiting list is unbounded as in the reference (HYD:264-265): the entries a list that still gets served can
  * hold are kept one by one, and once no prefix of it fits into 15 minutes any more (HYD:270-276: nobody is served again
  * until reset and the list only grows) its entries are folded into their count and running sums, which is all the
