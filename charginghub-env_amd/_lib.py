@@ -90,6 +90,38 @@ def sp_fields_names(mask):
     return tuple(name for i, name in enumerate(SP_NAMES) if mask >> i & 1)
 
 
+# the columns of chub_forecast_device (the CHUB_FC_* enum of include/chub.h, in order)
+FC_NAMES = ("slot", "valid", "sin", "cos", "price", "pv", "wind", "arrivals0", "arrivals1", "fcev")
+FC_COUNT = len(FC_NAMES)
+FC = {name: i for i, name in enumerate(FC_NAMES)}
+
+
+def fc_fields_mask(fields=None):
+    """a field set of chub_forecast_device as its bit mask: None = all ten, an int = the mask itself, else a sequence of FC_NAMES"""
+    if fields is None:
+        return (1 << FC_COUNT) - 1
+    if hasattr(fields, "__index__"):  # (an int of any kind)
+        fields = fields.__index__()
+        if fields <= 0 or fields >> FC_COUNT:
+            raise ValueError("fields: a non-empty mask over the %d look-ahead fields, got %#x" % (FC_COUNT, fields))
+        return fields
+    if isinstance(fields, str):
+        fields = (fields,)
+    mask = 0
+    for name in fields:
+        if name not in FC:
+            raise ValueError("unknown look-ahead field %r (one of %s)" % (name, ", ".join(FC_NAMES)))
+        mask |= 1 << FC[name]
+    if not mask:
+        raise ValueError("fields: at least one look-ahead field")
+    return mask
+
+
+def fc_fields_names(mask):
+    """the columns a mask selects, in the order they come out (ascending field order)"""
+    return tuple(name for i, name in enumerate(FC_NAMES) if mask >> i & 1)
+
+
 # the units of chub_load_dispatch's station targets (CHUB_LOAD_KW / CHUB_LOAD_FRACTION of include/chub.h)
 LOAD_KW, LOAD_FRACTION = 0, 1
 LOAD_UNITS = {"kw": LOAD_KW, "fraction": LOAD_FRACTION}
@@ -211,6 +243,8 @@ def load_library():
         "chub_pile_obs_columns": (I, [C.c_uint32]), "chub_pile_obs_device": (I, [P, C.c_uint32, P, P, P]),
         "chub_station_profile_size": (I, [C.c_uint32, C.c_int32]), "chub_station_profile_device": (I, [P, C.c_uint32, C.c_int32, P, P, P]),
         "chub_load_dispatch_device": (I, [P, I, P, P, P, P, P, P]), "chub_load_dispatch": (I, [P, I, P, P, P, P]),
+        "chub_forecast_size": (I, [C.c_uint32, C.c_int32]), "chub_forecast_device": (I, [P, C.c_uint32, C.c_int32, P, P, P]),
+        "chub_forecast": (I, [P, C.c_uint32, C.c_int32, P]),
         "chub_set_rng_compat_seeds": (I, [P, P]), "chub_set_rng_compat_state": (I, [P, P]),
         "chub_get_rng_compat_state": (I, [P, P]), "chub_compat_replay_constructor": (I, [P]), "chub_set_ou_state": (I, [P, P]),
         "chub_copy_envs": (I, [P, P, P, P, L]), "chub_copy_envs_device": (I, [P, P, P, P, L, P]),
@@ -263,7 +297,8 @@ EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "ch
             "chub_stream_destroy", "chub_stream_sync",
             "chub_set_episode_stats", "chub_has_episode_stats", "chub_get_episode_stats", "chub_get_episode_counts", "chub_episode_stats_device",
             "chub_episode_summary_device", "chub_episode_summary", "chub_pile_obs_columns", "chub_pile_obs_device",
-            "chub_station_profile_size", "chub_station_profile_device", "chub_load_dispatch_device", "chub_load_dispatch"]
+            "chub_station_profile_size", "chub_station_profile_device", "chub_load_dispatch_device", "chub_load_dispatch",
+            "chub_forecast_size", "chub_forecast_device", "chub_forecast"]
 
 
 def check(rc):

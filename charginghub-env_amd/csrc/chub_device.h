@@ -295,6 +295,18 @@ struct EpisodeArrays {
     CHUB_G(uint8_t) pending;     // [N] set with fin, cleared only by a draining summary (k_episode_summary)
 };
 
+// The exogenous look-ahead (chub_forecast_device, k_forecast): its columns in the order of the CHUB_FC_* enum, and the derived tables it
+// reads beside Tables -- built once at create from cnt / cnt_hv / hv_idx, outside the arena: no snapshot carries them, no copy moves them
+enum FcField : uint32_t { FC_SLOT = 0, FC_VALID, FC_SIN, FC_COS, FC_PRICE, FC_PV, FC_WIND, FC_ARRIVALS0, FC_ARRIVALS1, FC_FCEV };
+constexpr int kFcCount = 10;
+constexpr int kFcHist = 301;  // arrival indices 0 .. 300 (CHS.hpp:731-743)
+struct ForecastTabs {
+    const float *mean;     // [3][96] mean arrival count over the 1000 levels per slot of day: Tables::cnt[0], cnt[1], cnt_hv
+    // per-env rows (else null): the histogram of EnvParamArrays::hv_idx over a slot's 1000 levels, its non-empty bins only, ascending:
+    const uint32_t *hist;      // [96][kFcHist] arrival index v | levels with that index << 16
+    const uint16_t *hist_len;  // [96] bins of the slot (1 .. kFcHist)
+};
+
 // Everything a kernel needs that does not change from step to step, kept in device memory and passed by pointer
 // (as by-value kernel arguments these ~600 bytes were all loaded into SGPRs up front and spilled).
 struct DevCtx {

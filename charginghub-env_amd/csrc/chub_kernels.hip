@@ -18,6 +18,7 @@
 //           graph replays, per-env clocks).
 //   k_pile_obs, k_station_profile: every pile's Station::situation values by ONE decode (pile_decode), as columns and as
 //           per-station bins; chub_get_slots is k_pile_obs with every field.
+//   k_forecast: the next H slots of what is deterministic about an env's day (time, tariff, PV / wind profiles, mean arrivals).
 //
 // No MFMA: there is no dense contraction anywhere in this path.  By bytes it is HBM-bound; measured VALU
 // issue, the vector L1's access rate and HBM streaming are each more than half used.
@@ -2928,9 +2929,12 @@ struct NoMid {
 // and everything else is the production tail, instruction for instruction.
 // FCEV arrivals of env e at slot of day t and level `lev` on a handle with per-env hub parameters: the host's expression behind Tables::cnt_hv
 // (chub_create_ex) with the env's own rate -- the same f32 product and rounding, so the count is bit for bit the per-handle table's
-__device__ __forceinline__ uint32_t hv_count_env(const EnvParamArrays &ep, uint32_t e, int t, uint32_t lev) {
-    const int c = (int) roundf(ep.hv_rate[e] * (float) ep.hv_idx[(uint32_t) t * (uint32_t) kLevels + lev]);
+__device__ __forceinline__ uint32_t hv_count_rate(float rate, uint32_t n) {  // ... of arrival index n at that rate (k_forecast sums over the indices)
+    const int c = (int) roundf(rate * (float) n);
     return (uint32_t) (c < 0 ? 0 : (c > 255 ? 255 : c));
+}
+__device__ __forceinline__ uint32_t hv_count_env(const EnvParamArrays &ep, uint32_t e, int t, uint32_t lev) {
+    return hv_count_rate(ep.hv_rate[e], (uint32_t) ep.hv_idx[(uint32_t) t * (uint32_t) kLevels + lev]);
 }
 
 // EP (ENV_PARAMS, handles made by chub_create_params): the hydrogen, fuel-cell, fluctuation and FCEV constants are the env's own (DevCtx::ep, read
@@ -4547,6 +4551,96 @@ void launch_pile_obs(const HubParams &hp, const DevCtx *ctx, uint32_t fields, co
     case LAYOUT_CURVES: hipLaunchKernelGGL(k_pile_obs<LAYOUT_CURVES>, dim3((unsigned) nb), dim3(256), 0, stream, a); break;
     default: hipLaunchKernelGGL(k_pile_obs<LAYOUT_PHILOX>, dim3((unsigned) nb), dim3(256), 0, stream, a); break;
     }
+}
+
+// -------------------------------------------------------------------- exogenous look-ahead (chub_forecast_device)
+// What is deterministic about the next H slots of an env's day, as columns: out[env][column][h], the columns of the field mask in ascending
+// order (FcField), h = 0 the slot the env's next step simulates.  Lane = one float of the flat [N][C][H] range, so a wave stores runs of
+// consecutive floats (k_pile_obs' pattern); no lane talks to another, no LDS.  The env's clock and days are the same address for every lane
+// of its block.  MULTI: the clock is the env's own (the buffer the handle's next launch reads); otherwise it is an argument and the slot,
+// time, tariff and arrival columns are wave-uniform.  EP (per-env rows): the FCEV mean is the sum over the arrival indices v of
+// hist[s][v] * hv_count_rate(rate of the env, v) over the slot's non-empty bins -- at most kFcHist terms (about 60 with the packaged
+// arrival table) instead of 1000 levels, with the tail's own rounding and clamp;
+// the homogeneous means are the host's (chub_create, beside cnt / cnt_hv).  The OU noise is not forecast: see include/chub.h.
+struct ForecastArgs {
+    const DevCtx *ctx;
+    const uint8_t *mask;   // [N] or null: blocks of envs whose byte is 0 are not written
+    const uint16_t *clk;   // MULTI: [N] the envs' clocks (StepArgs::env_clk's layout)
+    ForecastTabs ft;
+    float *out;            // [N][columns][horizon]
+    uint64_t colmap;       // 4 bits per column: its field
+    int32_t columns, horizon;
+    int32_t t;             // lock-step: the handle's clock
+};
+template <bool EP, bool MULTI>
+__global__ __launch_bounds__(256) void k_forecast(const ForecastArgs a) {
+    const DevCtx *__restrict__ ctx = a.ctx;
+    const Tables &tb = ctx->tb;
+    const uint32_t H = (uint32_t) a.horizon, CH = (uint32_t) a.columns * H;
+    const int64_t total = ctx->hp.n_envs * (int64_t) CH;
+    const bool small = total <= 0xFFFFFFFFll;
+    for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t) gridDim.x * blockDim.x) {
+        const int64_t env = small ? (int64_t) ((uint32_t) i / CH) : i / CH;
+        if (a.mask && !a.mask[env]) continue;
+        const uint32_t r = (uint32_t) (i - env * CH), c = r / H, h = r - c * H;
+        const uint32_t f = (uint32_t) (a.colmap >> (4u * c)) & 15u;
+        uint32_t t = MULTI ? (uint32_t) clk_t(a.clk[env]) : (uint32_t) a.t;
+        t = t > 95u ? 95u : t;  // (a clock is 0 .. 95; no table index below depends on that being so)
+        const uint32_t th = t + h, s = th >= 96u ? th - 96u : th;
+        float v;
+        switch (f) {
+        case FC_SLOT: v = (float) s; break;
+        case FC_VALID: v = th <= 95u ? 1.0f : 0.0f; break;
+        case FC_SIN: v = (float) tb.sin96[s]; break;
+        case FC_COS: v = (float) tb.sin96[s >= 72u ? s - 72u : s + 24u]; break;
+        case FC_PRICE: v = (float) tb.price[s == 0u ? 95u : s - 1u]; break;  // the tariff of the slot before: what the step of slot s finds in price[-1]
+        case FC_PV: {
+            const uint32_t d = (uint32_t) ctx->ev.pv_day[env];
+            const double x = tb.pvT[s * 100u + (d < 100u ? d : 99u)];
+            v = (float) ((x > 0 ? x : 0.0) * 5);  // REN:38-43, MGR:349 without the noise factor
+            break;
+        }
+        case FC_WIND: {
+            const uint32_t d = (uint32_t) ctx->ev.wd_day[env];
+            const double x = tb.wdT[s * 150u + (d < 150u ? d : 149u)];
+            v = (float) ((x > 0 ? x : 0.0) * 1);
+            break;
+        }
+        case FC_ARRIVALS0: v = a.ft.mean[s]; break;
+        case FC_ARRIVALS1: v = a.ft.mean[96u + s]; break;
+        default:  // FC_FCEV
+            if (EP) {
+                const float rate = ctx->ep.hv_rate[env];
+                const uint32_t *hist = a.ft.hist + s * (uint32_t) kFcHist;
+                const uint32_t bins = min((uint32_t) a.ft.hist_len[s], (uint32_t) kFcHist);
+                uint32_t sum = 0u;
+                for (uint32_t j = 0u; j < bins; j++) {
+                    const uint32_t b = hist[j];
+                    sum += (b >> 16) * hv_count_rate(rate, b & 0xFFFFu);
+                }
+                v = (float) sum / 1000.0f;
+            } else {
+                v = a.ft.mean[192u + s];
+            }
+            break;
+        }
+        a.out[i] = v;
+    }
+}
+void launch_forecast(const HubParams &hp, const DevCtx *ctx, const ForecastTabs &ft, uint32_t fields, int horizon, int t, const uint16_t *d_clk,
+                     const uint8_t *d_mask, float *d_out, hipStream_t stream) {
+    ForecastArgs a = {ctx, d_mask, d_clk, ft, d_out, 0ull, 0, horizon, t};
+    for (uint32_t f = 0; f < (uint32_t) kFcCount; f++)
+        if (fields >> f & 1u) a.colmap |= (uint64_t) f << (4 * a.columns++);
+    const int64_t total = hp.n_envs * (int64_t) a.columns * horizon;
+    if (total <= 0) return;
+    int64_t nb = (total + 255) / 256;
+    if (nb > (1 << 20)) nb = 1 << 20;  // (beyond 2^28 floats the lanes stride)
+    const bool ep = ft.hist != nullptr, multi = d_clk != nullptr;
+    if (ep && multi) hipLaunchKernelGGL((k_forecast<true, true>), dim3((unsigned) nb), dim3(256), 0, stream, a);
+    else if (ep) hipLaunchKernelGGL((k_forecast<true, false>), dim3((unsigned) nb), dim3(256), 0, stream, a);
+    else if (multi) hipLaunchKernelGGL((k_forecast<false, true>), dim3((unsigned) nb), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((k_forecast<false, false>), dim3((unsigned) nb), dim3(256), 0, stream, a);
 }
 
 // -------------------------------------------------------------------- per-station deadline profiles (chub_station_profile_device)

@@ -30,6 +30,8 @@ void launch_station_profile(const HubParams &hp, const DevCtx *ctx, uint32_t fie
                             float *d_out, hipStream_t stream);
 void launch_load_dispatch(const HubParams &hp, const DevCtx *ctx, int units, const uint8_t *d_mask, const float *d_cls_soc, const float *d_loads,
                           const float *d_tail, float *d_actions, uint64_t *d_bits, hipStream_t stream);
+void launch_forecast(const HubParams &hp, const DevCtx *ctx, const ForecastTabs &ft, uint32_t fields, int horizon, int t, const uint16_t *d_clk,
+                     const uint8_t *d_mask, float *d_out, hipStream_t stream);
 template <bool RESET>
 void launch_env(EnvForm f, const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
                 const PackedPtrs &pp);
@@ -160,6 +162,9 @@ struct chub_env {
     // chub_pile_obs_device, PHILOX: [2][kSocLevels][kClsRow] f32, a class's SoC after n car_steps (k_build_cls_soc, at create and when a tape
     // registers classes).  Derived data outside the arena: no snapshot carries it, no copy moves it
     float *d_cls_soc = nullptr;
+    // chub_forecast_device: the mean arrival counts per slot of day and, with per-env rows, the histogram of the FCEV arrival index (one block, built
+    // on the host at create beside cnt / cnt_hv / hv_idx).  Derived data outside the arena, as d_cls_soc
+    ForecastTabs fc = {nullptr, nullptr, nullptr};
     double *d_ep_sum = nullptr;  // k_episode_summary's partials [kEpSumMaxBlocks][kEpSumWords], then the host form's result [kEpSumWords]
     int public_mode = 0;     // the rng_mode the handle was created with: CHUB_RNG_PHILOX_CURVES is hp.rng_mode = PHILOX + hp.soc_curves
     bool tape_only = false;  // ... and once there are any, the handle's class rows are the caller's: only tape resets / steps may admit cars
@@ -715,6 +720,25 @@ static int create_impl(const chub_config *cfg_in, const char *data_dir, int64_t 
             hv_idx[t * kLevels + k] = (uint16_t) n;
         }
     }
+    // chub_forecast_device: the mean of each table over a slot's 1000 levels (an integer sum, narrowed and divided once), and for handles with
+    // per-env rows how often each arrival index occurs among them -- the device then sums at most kFcHist terms per (env, slot)
+    std::vector<float> fc_mean(3 * 96);
+    std::vector<uint32_t> fc_hist(rows ? 96 * kFcHist : 0, 0u);
+    std::vector<uint16_t> fc_hist_len(rows ? 96 : 0, (uint16_t) 0);
+    for (int t = 0; t < 96; t++) {
+        const uint8_t *tab[3] = {&cnt[0][t * kLevels], &cnt[1][t * kLevels], &cnt_hv[t * kLevels]};
+        for (int j = 0; j < 3; j++) {
+            uint32_t sum = 0;
+            for (int k = 0; k < kLevels; k++) sum += tab[j][k];
+            fc_mean[j * 96 + t] = (float) sum / 1000.0f;
+        }
+        if (rows) {
+            uint32_t levels[kFcHist] = {0u};
+            for (int k = 0; k < kLevels; k++) levels[hv_idx[t * kLevels + k]]++;
+            for (uint32_t v = 0; v < (uint32_t) kFcHist; v++)
+                if (levels[v]) fc_hist[t * kFcHist + fc_hist_len[t]++] = v | (levels[v] << 16);
+        }
+    }
     if (rng_mode == CHUB_RNG_PHILOX) {
         // the packed per-step station draws (draw_station_levels) hold up to 9 arrivals per station and step
         int top = 0;
@@ -981,6 +1005,20 @@ static int create_impl(const chub_config *cfg_in, const char *data_dir, int64_t 
                                               : "the device's soc_to_time differs from the host-built table of target times"));
         }
     }
+    {
+        const size_t b_mean = fc_mean.size() * sizeof(float), b_hist = fc_hist.size() * sizeof(uint32_t), b_len = fc_hist_len.size() * sizeof(uint16_t);
+        char *d = nullptr;
+        if (hipMalloc((void **) &d, b_mean + b_hist + b_len) != hipSuccess) return bail(fail(CHUB_ERR_HIP, "hipMalloc failed"));
+        e->fc.mean = (const float *) d;
+        if (b_hist) {
+            e->fc.hist = (const uint32_t *) (d + b_mean);
+            e->fc.hist_len = (const uint16_t *) (d + b_mean + b_hist);
+        }
+        if (hipMemcpy(d, fc_mean.data(), b_mean, hipMemcpyHostToDevice) != hipSuccess ||
+            (b_hist && (hipMemcpy(d + b_mean, fc_hist.data(), b_hist, hipMemcpyHostToDevice) != hipSuccess ||
+                        hipMemcpy(d + b_mean + b_hist, fc_hist_len.data(), b_len, hipMemcpyHostToDevice) != hipSuccess)))
+            return bail(fail(CHUB_ERR_HIP, "the look-ahead tables could not be uploaded"));
+    }
     if (rng_mode == CHUB_RNG_PHILOX && !soc_curves) {
         // the SoC column of k_pile_obs / k_station_profile: the class rows' SoC, by the device's own replay of the curve (replay_soc_steps, the
         // chain the other two layouts run per pile), so that the table's entries are that replay's bits whatever the host's libm makes of it
@@ -1013,6 +1051,7 @@ int chub_destroy(chub_env *e) {
         if (e->d_telem) (void) hipFree(e->d_telem);
         if (e->d_ledger) (void) hipFree(e->d_ledger);
         if (e->d_cls_soc) (void) hipFree(e->d_cls_soc);
+        if (e->fc.mean) (void) hipFree((void *) e->fc.mean);
         if (e->d_ep_sum) (void) hipFree(e->d_ep_sum);
         if (e->h_bits) (void) hipHostFree(e->h_bits);  // h_tail / d_tail are the ends of the same blocks
         if (e->d_bits) (void) hipFree(e->d_bits);
@@ -2626,6 +2665,44 @@ int chub_station_profile_device(chub_env *e, uint32_t fields, int32_t buckets, c
     launch_station_profile(e->hp, e->d_ctx, fields, buckets, d_mask, e->d_cls_soc, d_out, (hipStream_t) stream);
     HIP_TRY(hipGetLastError());
     return CHUB_OK;
+}
+
+// The exogenous look-ahead: what is deterministic about the next `horizon` slots of every env's day, as a read-only launch (k_forecast)
+static_assert((int) CHUB_FC_COUNT == kFcCount && (int) CHUB_FC_FCEV == (int) FC_FCEV, "FcField (chub_device.h) restates the CHUB_FC_* enum");
+int chub_forecast_size(uint32_t fields, int32_t horizon) {
+    if (fields == 0u || (fields >> CHUB_FC_COUNT) != 0u) return fail(CHUB_ERR_ARG, "fields: a non-empty mask over the CHUB_FC_* fields");
+    if (horizon < 1 || horizon > 96) return fail(CHUB_ERR_ARG, "horizon: 1 .. 96");
+    return __builtin_popcount(fields) * horizon;
+}
+
+int chub_forecast_device(chub_env *e, uint32_t fields, int32_t horizon, const uint8_t *d_mask, float *d_out, void *stream) {
+    if (!e || !d_out) return fail(CHUB_ERR_ARG, "null argument");
+    if (chub_forecast_size(fields, horizon) < 0) return CHUB_ERR_ARG;
+    if (e->tape_only) return fail(CHUB_ERR_UNSUPPORTED, "chub_forecast_device is not supported on a tape handle (its arrivals are the caller's)");
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    if (const int rc = sync_ctx(e, (hipStream_t) stream)) return rc;  // (nothing to do inside a capture: chub_graph_begin has done it)
+    // lock-step: the clock by value (a capture records it: a graph replays only from the clock it started at); per-env clocks: the buffer
+    // the handle's next launch reads (as copy_launch)
+    const uint16_t *d_clk = e->per_env ? e->d_env_clk + (size_t) ((e->tick + 1u - e->graph_base) & 1u) * (size_t) e->hp.n_envs : nullptr;
+    launch_forecast(e->hp, e->d_ctx, e->fc, fields, horizon, e->t, d_clk, d_mask, d_out, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_forecast(chub_env *e, uint32_t fields, int32_t horizon, float *out) {
+    if (!e || !out) return fail(CHUB_ERR_ARG, "null argument");
+    const int per_env = chub_forecast_size(fields, horizon);
+    if (per_env < 0) return CHUB_ERR_ARG;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t bytes = (size_t) e->hp.n_envs * (size_t) per_env * sizeof(float);
+    float *d = nullptr;
+    HIP_TRY(hipMalloc((void **) &d, bytes));
+    int rc = chub_forecast_device(e, fields, horizon, nullptr, d, nullptr);
+    if (!rc && hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(CHUB_ERR_HIP, "the forecast could not be copied to the host");
+    (void) hipFree(d);
+    return rc;
 }
 
 // Station-level control: the dispatch of evs_step(float) as a read-only launch (k_load_dispatch) in front of any step form

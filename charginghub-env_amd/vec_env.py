@@ -542,6 +542,23 @@ class VecChargingHub(object):
             self._lib.chub_free_device(self._device, d)
         return out
 
+    # ---- exogenous look-ahead on the device (chub_forecast_device): slot of day, tariff, renewables, mean arrivals
+    def forecast_device(self, d_out, fields=None, horizon=8, d_mask=0, stream=0):
+        """what is deterministic about the next `horizon` slots of every env's day, into device memory: d_out [N, C, H] f32 -- env, the C
+        fields asked for in the order of _lib.FC_NAMES, then look-ahead h (h = 0: the slot the env's next step simulates).  fields: names,
+        a bit mask, or None for all ten; d_mask [N] u8 in device memory: only the blocks of the envs it names are written.  The noise on
+        PV, wind and price is not forecast.  One launch on `stream`: no synchronisation, nothing of the simulation changes, recordable
+        into a graph."""
+        check(self._lib.chub_forecast_device(self._h, _lib.fc_fields_mask(fields), int(horizon), d_mask or None, d_out, stream or None))
+
+    def forecast(self, fields=None, horizon=8):
+        """forecast_device into host memory: float32 [N, C, H] (the convenience form: it allocates, synchronises and copies)"""
+        mask = _lib.fc_fields_mask(fields)
+        check(min(self._lib.chub_forecast_size(mask, int(horizon)), 0))
+        out = np.zeros((self.n_envs, len(_lib.fc_fields_names(mask)), int(horizon)), dtype=np.float32)
+        check(self._lib.chub_forecast(self._h, mask, int(horizon), _ptr(out)))
+        return out
+
     # ---- station-level control on the device (chub_load_dispatch_device): one target per station -> action rows / one bit per pile
     def load_dispatch_device(self, d_loads, d_tail, d_actions=0, d_pile_bits=0, units="kw", d_mask=0, stream=0):
         """the reference's evs_step(float) dispatch as one read-only launch on `stream`: d_loads [N, 2] f32 (one target per station: kW, or

@@ -275,6 +275,10 @@ class TorchHubVecEnv(object):
     makes ``station_profile()`` available: each station's cars binned by the time they have left, as one [N, 2, C, B] CUDA tensor whose
     shape does not depend on the hub (chub_station_profile_device); ``profile_names`` is the column order.
 
+    ``forecast=dict(fields=("valid", "cos", "price", "pv", "wind"), horizon=8)`` (fields: any of _lib.FC_NAMES, None for all; None: off)
+    makes ``forecast()`` available: what is deterministic about the next H slots of every env's day -- slot of day, tariff, the env's PV
+    and wind profiles, mean arrivals -- as one [N, C, H] CUDA tensor (chub_forecast_device); ``forecast_names`` is the column order.
+
     ``control="station"`` makes the policy set one load per station instead of one action per pile (the reference's evs_step(float)):
     ``act_dim`` is 4 whatever the hub -- load of station 0, load of station 1, the two tail actions -- and every ``step`` first turns the
     loads into an action row the adapter owns (chub_load_dispatch_device, one read-only launch on torch's stream), then takes the step
@@ -283,7 +287,7 @@ class TorchHubVecEnv(object):
     is the adapter described above."""
 
     def __init__(self, n_envs, station_list, station_type_list, seed=0, device=0, autoreset=True, episode_stats=False, pile_obs=None,
-                 station_profile=None, control="pile", load_units="fraction", **hub_kwargs):
+                 station_profile=None, control="pile", load_units="fraction", forecast=None, **hub_kwargs):
         import torch  # before libchub is loaded by VecChargingHub: both must share one HIP runtime
 
         if not (autoreset is True or autoreset is False or autoreset == "per_env"):
@@ -303,6 +307,15 @@ class TorchHubVecEnv(object):
             if not 1 <= self._sp_buckets <= 32:
                 raise ValueError("station_profile: buckets 1 .. 32, not %d" % self._sp_buckets)
         self.profile_names = () if self._sp_mask is None else _lib.sp_fields_names(self._sp_mask)
+        self._fc_mask = self._fc_horizon = None
+        if forecast is not None:  # (ValueError for an unknown name or key, before anything is built)
+            unknown = set(forecast) - {"fields", "horizon"}
+            if unknown:
+                raise ValueError("forecast: a dict of fields and horizon, not %s" % sorted(unknown))
+            self._fc_mask, self._fc_horizon = _lib.fc_fields_mask(forecast.get("fields")), int(forecast.get("horizon", 8))
+            if not 1 <= self._fc_horizon <= 96:
+                raise ValueError("forecast: horizon 1 .. 96, not %d" % self._fc_horizon)
+        self.forecast_names = () if self._fc_mask is None else _lib.fc_fields_names(self._fc_mask)
         self.torch = torch
         self.device = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
         if self.device.type == "cuda":
@@ -338,6 +351,19 @@ class TorchHubVecEnv(object):
         self._sp_buf = None
         if self._sp_mask is not None:
             self._sp_buf = torch.zeros((self.num_envs, 2, len(self.profile_names), self._sp_buckets), dtype=torch.float32, device=self.device)
+
+        self._fc_buf = None
+        if self._fc_mask is not None:
+            self._fc_buf = torch.zeros((self.num_envs, len(self.forecast_names), self._fc_horizon), dtype=torch.float32, device=self.device)
+
+    def forecast(self):
+        """float32 [N, C, H] CUDA tensor: for every env the columns of ``forecast_names`` over the next H slots of its day, h = 0 being the
+        slot its next step simulates -- an env the step has just re-started shows slot 0 and its new days.  Filled by one launch on torch's
+        current stream, without a wait; it is ONE buffer, overwritten by the next call."""
+        if self._fc_buf is None:
+            raise RuntimeError("the look-ahead is off: construct with forecast=dict(fields=(names of _lib.FC_NAMES), horizon=H)")
+        self.vec.forecast_device(self._fc_buf.data_ptr(), self._fc_mask, self._fc_horizon, stream=self._stream())
+        return self._fc_buf
 
     def station_profile(self):
         """float32 [N, 2, C, B] CUDA tensor: for every env and station the columns of ``profile_names`` over the B buckets of time left, as

@@ -587,6 +587,54 @@ enum {
 int chub_station_profile_size(uint32_t fields, int32_t buckets);
 int chub_station_profile_device(chub_env *env, uint32_t fields, int32_t buckets, const uint8_t *d_mask, float *d_out, void *stream);
 
+/* ---- exogenous look-ahead on the device: tariff, renewables, arrivals ------------------------------------------------------------------
+ * The reference's observation carries the time of day only as sin(2 pi t / 96) (MGR:319-320: slots t and 48 - t look alike), and the
+ * tariff, the PV / wind day profiles and the arrival law an energy-management policy plans against live inside the handle; on per-env
+ * clocks the slot of day itself is device state.  chub_forecast_device writes, per env, the next H slots of what is DETERMINISTIC about the
+ * exogenous world into the caller's device memory in ONE launch on `stream`:
+ *   fields   a bit mask over the CHUB_FC_* enum (bit f = field f); C = its popcount columns come out, in ascending field order
+ *   horizon  H, 1 .. 96
+ *   d_out    [N][C][H] f32: env, column, look-ahead h.  chub_forecast_size gives the floats per env, C * H, for valid arguments (it needs
+ *            no device).
+ *   d_mask   [N] u8 in device memory or NULL: with a mask only the blocks of the envs whose byte is non-zero are written, every other block
+ *            of d_out is left alone (an all-zero mask writes nothing).
+ * Per env let t be its slot of day, 0 .. 95: the slot its next step simulates, what chub_env_clocks reports (lock-step: the handle's
+ * clock); for h = 0 .. H - 1 let s = (t + h) % 96.  Every f64 expression is evaluated in f64 and narrowed once:
+ *   SLOT       (float) s
+ *   VALID      1 if t + h <= 95 (the slot lies inside the env's current day), else 0.  Beyond the day's end the other columns wrap with the
+ *              env's CURRENT PV / wind days: the next reset draws new ones, which nobody knows yet
+ *   SIN        (float) sin(2 pi s / 96) of the handle's table: at h = 0 the bits of observation column 0
+ *   COS        the same table at (s + 24) % 96
+ *   PRICE      (float) price[(s + 95) % 96]: the tariff part of real_state[1] as the step that simulates slot s finds it (make_state adds
+ *              price[-1], the tariff of the slot before, MGR:354-359; after a reset that is price[95], AGG:171)
+ *   PV         (float) (max(x, 0) * 5), x = the PV profile of the env's day at slot s: the noise-free part of re_pv_power (REN:38-43, MGR:349)
+ *   WIND       (float) (max(x, 0) * 1), x = the wind profile of the env's day at slot s
+ *   ARRIVALS0  (float) sum / 1000.0f, sum = the integer sum over the 1000 levels of uniform_rand of station 0's arrival count at slot s:
+ *   ARRIVALS1  the mean of what the station's draw of slot s can come to, before balking -- reported whatever the station's pile count
+ *   FCEV       the same over the FCEV arrival count the tail would read for THIS env: the handle's table, or with per-env rows
+ *              clamp(roundf(rate of the env * arrival index), 0, 255); it follows chub_set_env_params from the next call on
+ * The Ornstein-Uhlenbeck noise on PV, wind and price is deliberately NOT forecast (nor the env's price noise in PRICE): the observation
+ * already shows the current slot's noisy values, so a policy has the noise as observation minus column h = 0.
+ * Manners are chub_pile_obs_device's: it reads state and writes d_out, nothing else (no tick, no clock, no draw: the handle computes what
+ * it would have computed without the call); it returns after enqueueing (no synchronisation, no allocation, no staging copy); valid at
+ * any point after the first reset, after resets and steps of every form (masked, device-mask, auto-reset: a re-started env shows slot 0
+ * and its new days), chub_copy_envs* and chub_set_state; on lock-step and per-env clocks, with or without per-env parameter rows,
+ * telemetry or the ledger, in all three RNG modes (COMPAT's days are the caller's exo_days) and for every hub shape.  Recordable between
+ * chub_graph_begin and chub_graph_end, where it does not count towards the even number of resets + steps: a lock-step handle's clock is
+ * recorded by value (a graph replays only from the clock it started at), per-env clocks are read when the graph runs.
+ * The mean counts are derived tables built on the host when the handle is created (per-env rows: a histogram of the arrival index per
+ * slot, so that an env's FCEV mean is a sum of at most 301 terms): not snapshot state, chub_state_size is unchanged.
+ * chub_forecast: the same through host memory, every env (it allocates, copies and synchronises: the convenience form).
+ * CHUB_ERR_ARG: null handle, null d_out / out, fields 0 or with bits from CHUB_FC_COUNT up, horizon outside 1 .. 96 (chub_forecast_size
+ * returns the same code).  CHUB_ERR_UNSUPPORTED with a message: tape handles (their arrivals are the caller's). */
+enum {
+    CHUB_FC_SLOT = 0, CHUB_FC_VALID, CHUB_FC_SIN, CHUB_FC_COS, CHUB_FC_PRICE, CHUB_FC_PV, CHUB_FC_WIND, CHUB_FC_ARRIVALS0, CHUB_FC_ARRIVALS1,
+    CHUB_FC_FCEV, CHUB_FC_COUNT
+};
+int chub_forecast_size(uint32_t fields, int32_t horizon);
+int chub_forecast_device(chub_env *env, uint32_t fields, int32_t horizon, const uint8_t *d_mask, float *d_out, void *stream);
+int chub_forecast(chub_env *env, uint32_t fields, int32_t horizon, float *out);
+
 /* ---- station-level control on the device: kW targets to pile actions ------------------------------------------------------------------
  * The reference's station-level control, evs_step(float) (CHS.hpp:1169-1186 / 1480-1497: catch_load, assign_on_off, rank_power_add), takes
  * one kW target per station and switches the piles on in urgency order until the target is met.  chub_step_load* runs it inside the
