@@ -235,7 +235,8 @@ enum {
  * chub_reset replaces EvcsspManagerEnv_v6.reset (MGR:304-316 -> AGG:157-175 evs_reset main.cpp:199,251,
  * HYD:197-208, REN:51-53).  chub_step replaces EvcsspManagerEnv_v6.step (MGR:136-302 -> AGG:116-155
  * evs_step(Vector_float) main.cpp:198,250; hv_car_number_wrt_poisson / mk_soc main.cpp:151,163).
- *   actions  [N,A] f32 in [-1,1]; pile bit = ((a+1)/2 >= 0.5) in f32; tail is swapped as in MGR:395-403
+ *   actions  [N,A] f32 in [-1,1]; pile bit = ((a+1)/2 >= 0.5) in f32; tail is swapped as in MGR:395-403.  Tail actions outside
+ *            [-1,1] (NaN and infinities included) are the caller's error: the electrolyser's table index is clamped for memory safety only
  *   exo_days [N,2] i32 (pv_day, wd_day) -- required in COMPAT mode, ignored (may be NULL) in PHILOX
  *   exo_z    [N,3] f64 standard normals for the (pv, wd, price) OU updates (REN:71-76) -- COMPAT only
  *   obs      [N,D] f32, reward [N] f32, done [N] u8
