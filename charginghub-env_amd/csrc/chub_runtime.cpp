@@ -3097,8 +3097,13 @@ struct SnapshotHeader {
     int32_t predrawn, per_env;
     int32_t rng_cur;  // COMPAT: which of the arena's three stream buffers holds the committed streams
     int32_t pad_;     // bit 0: taken from a handle with per-env hub parameters, bit 1: with the episode ledger on -- its block then ends the blob
-                      // (0 otherwise: the blob of a homogeneous handle without the ledger is unchanged)
+                      // (0 otherwise: the blob of a homogeneous handle without the ledger is unchanged); bits 8 .. 15, with bit 0: the rows'
+                      // FCEV arrivals per step at most (hv_max_arrive <= 127), which sizes q_time / q_mass / hv_pre inside the arena -- two
+                      // capacities can round to one arena_used (every array is padded to 256 bytes), so the size alone does not tell them apart
+    uint32_t key[2];  // the source's Philox key (its seed): not state -- the target keeps its own -- but the draws made ahead carry it
 };
+static const char *const kSnapshotInCapture = "chub_get_state / chub_set_state between chub_graph_begin and chub_graph_end (a snapshot synchronises and "
+                                              "copies: call it between replays)";
 static const uint64_t kSnapMagic = 0x43485542534e4150ull;  // "CHUBSNAP"
 
 int64_t chub_state_size(const chub_env *e) {
@@ -3109,6 +3114,7 @@ int64_t chub_state_size(const chub_env *e) {
 
 int chub_get_state(chub_env *e, void *buf, int64_t size) {
     if (!e || !buf) return fail(CHUB_ERR_ARG, "null argument");
+    if (e->capturing) return fail(CHUB_ERR_UNSUPPORTED, kSnapshotInCapture);
     const int64_t need = chub_state_size(e);
     if (need < 0) return (int) need;
     if (size < need) return fail(CHUB_ERR_ARG, "buffer too small for the snapshot");
@@ -3130,7 +3136,9 @@ int chub_get_state(chub_env *e, void *buf, int64_t size) {
     h.predrawn = e->predrawn ? 1 : 0;
     h.per_env = e->per_env ? 1 : 0;
     h.rng_cur = e->rng_cur;
-    h.pad_ = (e->env_params ? 1 : 0) | (e->es.on ? 2 : 0);  // (the rows themselves are in the arena)
+    h.key[0] = e->hp.key[0];
+    h.key[1] = e->hp.key[1];
+    h.pad_ = (e->env_params ? 1 | (e->hv_max_arrive << 8) : 0) | (e->es.on ? 2 : 0);  // (the rows themselves are in the arena)
     memcpy(buf, &h, sizeof h);
     HIP_TRY(hipMemcpy((char *) buf + sizeof h, e->arena, e->arena_used, hipMemcpyDeviceToHost));
     {
@@ -3148,7 +3156,7 @@ int chub_get_state(chub_env *e, void *buf, int64_t size) {
 
 int chub_set_state(chub_env *e, const void *buf, int64_t size) {
     if (!e || !buf) return fail(CHUB_ERR_ARG, "null argument");
-    e->walked_tick = 0;  // (a walk that ran ahead of its step is void)
+    if (e->capturing) return fail(CHUB_ERR_UNSUPPORTED, kSnapshotInCapture);
     const int64_t need = chub_state_size(e);
     if (need < 0) return (int) need;
     SnapshotHeader h;
@@ -3164,7 +3172,11 @@ int chub_set_state(chub_env *e, const void *buf, int64_t size) {
     if (h.n_envs != e->hp.n_envs || h.env_id0 != e->hp.env_id0 || h.rng_mode != e->public_mode ||
         memcmp(&h.cfg, &e->cfg, sizeof h.cfg) != 0 || h.arena_used != e->arena_used || size < need)
         return fail(CHUB_ERR_ARG, "snapshot was taken from a handle with a different configuration");
+    if (e->env_params && ((h.pad_ >> 8) & 0xff) != e->hv_max_arrive)
+        return fail(CHUB_ERR_ARG, "snapshot was taken from a handle whose FCEV waiting list was sized for " + std::to_string((h.pad_ >> 8) & 0xff) +
+                                      " arrivals per step, this handle's for " + std::to_string(e->hv_max_arrive) + " (the largest fcev_permeate at create)");
     if (h.rng_cur < 0 || h.rng_cur > 2) return fail(CHUB_ERR_ARG, "snapshot header is corrupt");  // (every header check comes before the first write)
+    e->walked_tick = 0;  // (a walk that ran ahead of its step is void)
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
     // device pointers inside the arena are position-dependent: restore only into the handle's own layout, which the
@@ -3181,7 +3193,9 @@ int chub_set_state(chub_env *e, const void *buf, int64_t size) {
     e->ctx_dirty = true;
     {
         const size_t N = (size_t) e->hp.n_envs;
-        e->predrawn = h.predrawn != 0;
+        // (the draws made ahead are a function of key, tick, env id and the queues this blob restores: good in a handle of any launch form,
+        // void under another key)
+        e->predrawn = h.predrawn != 0 && h.key[0] == e->hp.key[0] && h.key[1] == e->hp.key[1];
         e->per_env = h.per_env != 0;
         e->h_tick.resize(N);
         memcpy(e->h_tick.data(), (const char *) buf + sizeof h + e->arena_used, N * sizeof(uint32_t));

@@ -769,7 +769,28 @@ int chub_reset_tape_env(chub_env *env, const uint32_t *occ_tape, const uint32_t 
 
 /* Snapshot / restore of the whole simulation state (clock, streams, every slot and env variable): checkpoint /
  * resume, planners that branch from a state.  The reference cannot do this (pickling disabled, main.cpp:234; raw
- * back-pointers, CHS.hpp:238).  A snapshot restores only into a handle created with the same arguments. */
+ * back-pointers, CHS.hpp:238).
+ *   The blob is a header, the handle's device arena, every env's last tick and, with the ledger on, its block.  The arena holds the
+ *       simulation state and, riding along, what the last launch made ahead of the next step: the station draws of the next tick (pk,
+ *       drw) and, in COMPAT, the shadow streams and counts of a walk that ran ahead.  The header says which of that is good: the draws are
+ *       reused by the first step after chub_set_state exactly when the snapshot's last launch served every env (they are a function of
+ *       the key, the tick, the env id and the queues the blob itself restores, not of the launch form that made them; redrawn, they come
+ *       out the same); a COMPAT walk that ran ahead and the counts of empty slots are void after every restore, and the next step makes
+ *       its own.  The continuation is bit-identical to the source handle's own, whichever launch forms the two handles run.
+ *   Target: the handle the blob was taken from, or one created with the same chub_config, n_envs, env_id0, RNG mode and data directory,
+ *       both with or both without per-env rows (then with the same waiting-list capacity: the largest fcev_permeate of the rows at
+ *       create) and both with the ledger on or off.  chub_options may differ (tile, slot_kernel, fused_step, walk_ahead, work_order,
+ *       span_*: the arena's layout does not depend on them; no_arena handles take no part).  The target need never have been reset and
+ *       may be anywhere in a day, on one clock or on per-env clocks: clocks, ticks and the graph tick base come from the blob.
+ *   Seed: the Philox key is the handle's, not state (as for chub_copy_envs).  A PHILOX / PHILOX_CURVES blob restored into a handle of
+ *       another seed gives the source's state exactly -- every reader returns the source's values -- and from the next launch on the
+ *       target draws with its OWN key: another future, the same for every such restore.  The draws that rode along were made with the
+ *       source's key (the header names it), so they are void there and the first step makes its own.
+ *   CHUB_ERR_ARG, with a message and nothing written (every check comes before the first write): null arguments, a buffer smaller than
+ *       chub_state_size / a truncated blob, not a snapshot, another n_envs, env_id0, chub_config, RNG mode, rows against no rows, another
+ *       waiting-list capacity of the rows, ledger against no ledger, a corrupt header.  CHUB_ERR_UNSUPPORTED, before any HIP call: a
+ *       no_arena handle; a handle between chub_graph_begin and chub_graph_end (a snapshot synchronises and copies: take and restore it
+ *       between replays; the capture goes on unharmed). */
 int64_t chub_state_size(const chub_env *env);
 int chub_get_state(chub_env *env, void *buf, int64_t size);
 int chub_set_state(chub_env *env, const void *buf, int64_t size);
