@@ -1395,6 +1395,61 @@ static void vec_step_impl(orc_vec *v, const float *actions, const double *exo_z,
     for (int k = 0; k < n_threads; k++) pthread_join(th[k], NULL);
 }
 
+/* ---- stations alone, from arrays (tests/class_grid_lib.py: designed populations of cars) ----
+ * orc_vec_fill_station: station k of every env emptied (reset_position) and filled from [n][piles[k]] arrays: late[e][i] < 0 leaves
+ * pile i of env e empty, otherwise the car place_car makes of (soc, target, late) -- what orc_station_put_car does, pile by pile.
+ * orc_vec_step_stations: orc_station_step of both stations of every env (one more tick first, as env_step_impl takes it), bits
+ * [n][piles[0] + piles[1]] f32 0 / 1 as action_to_real leaves them; nothing else of the env moves. */
+void orc_vec_fill_station(orc_vec *v, int k, const float *soc, const float *target, const int *late) {
+    for (long e = 0; e < v->n; e++) {
+        orc_station *s = &v->envs[e].st[k];
+        for (int i = 0; i < s->n; i++) {
+            long at = e * (long) s->n + i;
+            reset_position(s, i);
+            if (late[at] >= 0) place_car(s, i, soc[at], target[at], late[at], 1);
+        }
+    }
+}
+
+typedef struct {
+    orc_vec *v;
+    const float *bits;
+    long lo, hi;
+} stations_job;
+
+static void *stations_worker(void *p) {
+    stations_job *j = (stations_job *) p;
+    for (long e = j->lo; e < j->hi; e++) {
+        orc_env *env = &j->v->envs[e];
+        const float *b = j->bits + e * (long) (env->st[0].n + env->st[1].n);
+        env->rng.tick += 1;
+        orc_station_step(&env->st[0], &env->rng, env->tab, b);
+        orc_station_step(&env->st[1], &env->rng, env->tab, b + env->st[0].n);
+    }
+    return NULL;
+}
+
+void orc_vec_step_stations(orc_vec *v, const float *bits, int n_threads) {
+    if (n_threads < 1) n_threads = 1;
+    if (n_threads > 256) n_threads = 256;
+    if ((long) n_threads > v->n) n_threads = (int) (v->n > 0 ? v->n : 1);
+    stations_job jobs[256];
+    pthread_t th[256];
+    long chunk = (v->n + n_threads - 1) / n_threads;
+    for (int k = 0; k < n_threads; k++) {
+        long lo = chunk * k, hi = lo + chunk;
+        if (hi > v->n) hi = v->n;
+        if (lo > hi) lo = hi;
+        jobs[k] = (stations_job){v, bits, lo, hi};
+    }
+    if (n_threads == 1) {
+        stations_worker(&jobs[0]);
+        return;
+    }
+    for (int k = 0; k < n_threads; k++) pthread_create(&th[k], NULL, stations_worker, &jobs[k]);
+    for (int k = 0; k < n_threads; k++) pthread_join(th[k], NULL);
+}
+
 /* ============================================================== accessors for the ctypes tests */
 
 orc_tables *orc_tables_load(const char *data_dir) {

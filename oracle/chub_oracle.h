@@ -206,6 +206,9 @@ void orc_vec_step_load(orc_vec *v, const float *actions, const double *exo_z, do
 void orc_vec_slots(orc_vec *v, int k, float *out /* [n][9][piles[k]] */);      /* orc_station_slots of station k of every env */
 void orc_vec_station_scalars(orc_vec *v, double *out /* [n][2][8] */);          /* orc_station_scalars of both stations of every env */
 void orc_vec_telemetry(orc_vec *v, double *out /* [n][38] */);                  /* orc_env_telemetry of every env */
+/* stations alone, from arrays (designed populations of cars: tests/class_grid_lib.py) */
+void orc_vec_fill_station(orc_vec *v, int k, const float *soc, const float *target, const int *late /* each [n][piles[k]]; late < 0: empty */);
+void orc_vec_step_stations(orc_vec *v, const float *bits /* [n][piles[0] + piles[1]] 0 / 1 */, int n_threads);
 int orc_vec_overflow(orc_vec *v);                                               /* q_overflow | stay_overflow of any env */
 long orc_sizeof_env(void);
 long orc_check_canon_division(long n, unsigned long long seed); /* see chub_oracle.c */

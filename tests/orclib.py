@@ -128,6 +128,8 @@ def _load_oracle(name="liboracle.so"):
         "orc_vec_station_scalars": (None, [P, P]),
         "orc_vec_telemetry": (None, [P, P]),
         "orc_vec_overflow": (I, [P]),
+        "orc_vec_fill_station": (None, [P, I, P, P, P]),
+        "orc_vec_step_stations": (None, [P, P, I]),
         "orc_vec_reset": (None, [P, P, P, P]),
         "orc_vec_step": (None, [P, P, P, P, P, P, I]),
         "orc_vec_step_load": (None, [P, P, P, P, P, P, I]),
