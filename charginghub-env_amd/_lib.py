@@ -122,6 +122,40 @@ def fc_fields_names(mask):
     return tuple(name for i, name in enumerate(FC_NAMES) if mask >> i & 1)
 
 
+# the columns of chub_get_step_terms_device (the CHUB_ST_* enum of include/chub.h, in order)
+ST_NAMES = ("reward", "income", "income_evs0", "income_evs1", "cost_evs0", "cost_evs1", "income_serve", "income_hys", "hy_cost", "hy_loss",
+            "not_meet_loss", "grid_draw", "grid_excess", "used_renew", "fc_power", "hy_act", "gen_hy", "hy_gen", "hy_use", "not_meet",
+            "hy_for_fc", "mass_need", "fcev_arrive", "fcev_line", "fcev_queue", "soc_deviation", "soc_penalty")
+ST_COUNT = len(ST_NAMES)
+ST = {name: i for i, name in enumerate(ST_NAMES)}
+
+
+def st_fields_mask(fields=None):
+    """a field set of chub_get_step_terms_device as its bit mask: None = all 27, an int = the mask itself, else a sequence of ST_NAMES"""
+    if fields is None:
+        return (1 << ST_COUNT) - 1
+    if hasattr(fields, "__index__"):  # (an int of any kind)
+        fields = fields.__index__()
+        if fields <= 0 or fields >> ST_COUNT:
+            raise ValueError("fields: a non-empty mask over the %d step terms, got %#x" % (ST_COUNT, fields))
+        return fields
+    if isinstance(fields, str):
+        fields = (fields,)
+    mask = 0
+    for name in fields:
+        if name not in ST:
+            raise ValueError("unknown step term %r (one of %s)" % (name, ", ".join(ST_NAMES)))
+        mask |= 1 << ST[name]
+    if not mask:
+        raise ValueError("fields: at least one step term")
+    return mask
+
+
+def st_fields_names(mask):
+    """the columns a mask selects, in the order they come out (ascending field order)"""
+    return tuple(name for i, name in enumerate(ST_NAMES) if mask >> i & 1)
+
+
 # the units of chub_load_dispatch's station targets (CHUB_LOAD_KW / CHUB_LOAD_FRACTION of include/chub.h)
 LOAD_KW, LOAD_FRACTION = 0, 1
 LOAD_UNITS = {"kw": LOAD_KW, "fraction": LOAD_FRACTION}
@@ -245,6 +279,8 @@ def load_library():
         "chub_load_dispatch_device": (I, [P, I, P, P, P, P, P, P]), "chub_load_dispatch": (I, [P, I, P, P, P, P]),
         "chub_forecast_size": (I, [C.c_uint32, C.c_int32]), "chub_forecast_device": (I, [P, C.c_uint32, C.c_int32, P, P, P]),
         "chub_forecast": (I, [P, C.c_uint32, C.c_int32, P]),
+        "chub_get_step_terms_size": (I, [C.c_uint32]), "chub_get_step_terms_device": (I, [P, C.c_uint32, P, P, P]),
+        "chub_get_step_terms": (I, [P, C.c_uint32, P]), "chub_set_step_terms": (I, [P, C.c_uint32, P]), "chub_get_step_terms_attached": (I, [P]),
         "chub_set_rng_compat_seeds": (I, [P, P]), "chub_set_rng_compat_state": (I, [P, P]),
         "chub_get_rng_compat_state": (I, [P, P]), "chub_compat_replay_constructor": (I, [P]), "chub_set_ou_state": (I, [P, P]),
         "chub_copy_envs": (I, [P, P, P, P, L]), "chub_copy_envs_device": (I, [P, P, P, P, L, P]),
@@ -298,7 +334,8 @@ EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "ch
             "chub_set_episode_stats", "chub_has_episode_stats", "chub_get_episode_stats", "chub_get_episode_counts", "chub_episode_stats_device",
             "chub_episode_summary_device", "chub_episode_summary", "chub_pile_obs_columns", "chub_pile_obs_device",
             "chub_station_profile_size", "chub_station_profile_device", "chub_load_dispatch_device", "chub_load_dispatch",
-            "chub_forecast_size", "chub_forecast_device", "chub_forecast"]
+            "chub_forecast_size", "chub_forecast_device", "chub_forecast",
+            "chub_get_step_terms_size", "chub_get_step_terms_device", "chub_get_step_terms", "chub_set_step_terms", "chub_get_step_terms_attached"]
 
 
 def check(rc):

@@ -4643,6 +4643,138 @@ void launch_forecast(const HubParams &hp, const DevCtx *ctx, const ForecastTabs 
     else hipLaunchKernelGGL((k_forecast<false, false>), dim3((unsigned) nb), dim3(256), 0, stream, a);
 }
 
+// -------------------------------------------------------------------- step terms (chub_get_step_terms_device)
+// What the reward of an env's last step is made of and what a constrained learner penalises, as columns: out[env][column], the columns of the
+// field mask in ascending order of the CHUB_ST_* enum.  A pure function of the telemetry block [kTelemCount][N] the tail has written (in
+// whichever launch form and RNG mode) and of the hub's init_soc and capacity_mass -- the env's own with per-env rows, as the ledger takes
+// them; the expressions are include/chub.h's table, in f64 in the order written there, narrowed once by the store type.  Lane = env, so a
+// wave's load of one telemetry column is a run of consecutive doubles; of the 38 columns only those the field set reads are loaded (need:
+// the host's union over the fields, wave-uniform branches).  The rows go through LDS, as the tail's output rows do: the workgroup's
+// kStBlock rows are one contiguous run of out, stored with consecutive lanes on consecutive words.  With a mask only the rows of the envs it
+// names are written.  Reads telemetry (and ep.prm), writes out: nothing else.
+constexpr int kStBlock = 256;
+struct StepTermsArgs {
+    const DevCtx *ctx;
+    const uint8_t *mask;  // [N] or null: rows of envs whose byte is 0 are not written
+    void *out;            // [N][columns] f32 or f64
+    uint64_t need;        // bit c: some field asked for reads telemetry column c
+    uint32_t fields;      // bits of the CHUB_ST_* enum
+};
+// the telemetry columns field f reads
+static uint64_t step_term_reads(int f) {
+    auto b = [](int c) { return 1ull << c; };
+    const uint64_t price = b(CHUB_T_PRICE_NOW), draw = b(CHUB_T_EV0_NET) | b(CHUB_T_EV1_NET) | b(CHUB_T_HYDROGEN_POWER);
+    switch (f) {
+    case CHUB_ST_REWARD: return b(CHUB_T_REWARD);
+    case CHUB_ST_INCOME: return b(CHUB_T_INCOME);
+    case CHUB_ST_INCOME_EVS0: return b(CHUB_T_CHG0);
+    case CHUB_ST_INCOME_EVS1: return b(CHUB_T_CHG1);
+    case CHUB_ST_COST_EVS0: return price | b(CHUB_T_EV0_NET);
+    case CHUB_ST_COST_EVS1: return price | b(CHUB_T_EV1_NET);
+    case CHUB_ST_INCOME_SERVE: return b(CHUB_T_FLOW0) | b(CHUB_T_FLOW1);
+    case CHUB_ST_INCOME_HYS: case CHUB_ST_HY_USE: return b(CHUB_T_HY_USE);
+    case CHUB_ST_HY_COST: return price | b(CHUB_T_HYDROGEN_POWER);
+    case CHUB_ST_HY_LOSS: case CHUB_ST_HY_FOR_FC: return b(CHUB_T_HY_TO_USE);
+    case CHUB_ST_NOT_MEET_LOSS: case CHUB_ST_NOT_MEET: return b(CHUB_T_NOT_MEET);
+    case CHUB_ST_GRID_DRAW: case CHUB_ST_GRID_EXCESS: return draw;
+    case CHUB_ST_USED_RENEW: return b(CHUB_T_USED_RENEW);
+    case CHUB_ST_FC_POWER: return b(CHUB_T_FC_POWER);
+    case CHUB_ST_HY_ACT: return b(CHUB_T_HY_ACT);
+    case CHUB_ST_GEN_HY: case CHUB_ST_HY_GEN: return b(CHUB_T_HY_FLOW_SPEED);
+    case CHUB_ST_MASS_NEED: return b(CHUB_T_TOTAL_MASS_NEED);
+    case CHUB_ST_FCEV_ARRIVE: return b(CHUB_T_HV_ARRIVE);
+    case CHUB_ST_FCEV_LINE: return b(CHUB_T_HV_LINE);
+    case CHUB_ST_FCEV_QUEUE: return b(CHUB_T_QUEUE_LEN);
+    default: return b(CHUB_T_STORE_SOC);  // SOC_DEVIATION, SOC_PENALTY
+    }
+}
+template <typename OUT>
+__global__ __launch_bounds__(kStBlock) void k_step_terms(const StepTermsArgs a) {
+    __shared__ __attribute__((aligned(16))) OUT s_rows[kStBlock * CHUB_ST_COUNT];
+    const DevCtx *__restrict__ ctx = a.ctx;
+    const HubParams &hp = ctx->hp;
+    const int64_t N = hp.n_envs;
+    const uint32_t fields = a.fields;
+    const int C = __popc(fields);
+    const int64_t env0 = (int64_t) blockIdx.x * kStBlock, env = env0 + (int64_t) threadIdx.x;
+    const bool live = env < N && (!a.mask || a.mask[env] != 0);
+    if (live) {
+        CHUB_G(const double) tel = ctx->ev.telem;
+        // column c of this env, if any field asked for reads it
+#define ST_T(c) ((a.need >> (c) & 1ull) ? tel[(int64_t) (c) * N + env] : 0.0)
+        const double t_reward = ST_T(CHUB_T_REWARD), t_income = ST_T(CHUB_T_INCOME), chg0 = ST_T(CHUB_T_CHG0), chg1 = ST_T(CHUB_T_CHG1);
+        const double e0 = ST_T(CHUB_T_EV0_NET), e1 = ST_T(CHUB_T_EV1_NET), hydrogen_power = ST_T(CHUB_T_HYDROGEN_POWER);
+        const double flow0 = ST_T(CHUB_T_FLOW0), flow1 = ST_T(CHUB_T_FLOW1), hy_use = ST_T(CHUB_T_HY_USE), hy_to_use = ST_T(CHUB_T_HY_TO_USE);
+        const double not_meet = ST_T(CHUB_T_NOT_MEET), used_renew = ST_T(CHUB_T_USED_RENEW), fc_power = ST_T(CHUB_T_FC_POWER);
+        const double hy_act = ST_T(CHUB_T_HY_ACT), speed = ST_T(CHUB_T_HY_FLOW_SPEED), mass_need = ST_T(CHUB_T_TOTAL_MASS_NEED);
+        const double hv_arrive = ST_T(CHUB_T_HV_ARRIVE), hv_line = ST_T(CHUB_T_HV_LINE), queue = ST_T(CHUB_T_QUEUE_LEN);
+        const double store_soc = ST_T(CHUB_T_STORE_SOC);
+        const double p = ST_T(CHUB_T_PRICE_NOW) / 4;
+#undef ST_T
+        double init_soc = hp.init_soc, cap_mass = hp.cap_mass;
+        if (ctx->ep.prm && (fields & (1u << CHUB_ST_SOC_DEVIATION | 1u << CHUB_ST_SOC_PENALTY))) {  // per-env rows: the env's own, as the ledger's tail
+            init_soc = ctx->ep.prm[(int64_t) PRM_INIT_SOC * N + env];
+            cap_mass = ctx->ep.prm[(int64_t) PRM_CAP_MASS * N + env];
+        }
+        const double draw = (e0 + e1) + hydrogen_power;  // MGR:262
+        const double excess = draw - 2000;
+        const double deviation = fabs(store_soc - init_soc);  // MGR:297
+        OUT *row = s_rows + (int) threadIdx.x * C;
+        int n = 0;
+#define ST_OUT(f, v)                                    \
+    if (fields & (1u << (f))) row[n++] = (OUT) (v)
+        ST_OUT(CHUB_ST_REWARD, t_reward);
+        ST_OUT(CHUB_ST_INCOME, t_income);
+        ST_OUT(CHUB_ST_INCOME_EVS0, 0.42 / 4 * chg0);
+        ST_OUT(CHUB_ST_INCOME_EVS1, 0.21 / 4 * chg1);
+        ST_OUT(CHUB_ST_COST_EVS0, -p * e0);
+        ST_OUT(CHUB_ST_COST_EVS1, -p * e1);
+        ST_OUT(CHUB_ST_INCOME_SERVE, 0.8 * (flow0 + flow1));
+        ST_OUT(CHUB_ST_INCOME_HYS, 6 / 1000.0 * hy_use);
+        ST_OUT(CHUB_ST_HY_COST, -p * hydrogen_power);
+        ST_OUT(CHUB_ST_HY_LOSS, -6 / 1000.0 * hy_to_use);
+        ST_OUT(CHUB_ST_NOT_MEET_LOSS, -10 / 1000.0 * not_meet);
+        ST_OUT(CHUB_ST_GRID_DRAW, draw);
+        ST_OUT(CHUB_ST_GRID_EXCESS, excess > 0 ? excess : 0.0);  // beyond the 2000 kW of MGR:160
+        ST_OUT(CHUB_ST_USED_RENEW, used_renew);
+        ST_OUT(CHUB_ST_FC_POWER, fc_power);
+        ST_OUT(CHUB_ST_HY_ACT, hy_act);
+        ST_OUT(CHUB_ST_GEN_HY, speed > 0.5 ? 1.0 : 0.0);  // MGR:173-179
+        ST_OUT(CHUB_ST_HY_GEN, 15 * 60 * speed);
+        ST_OUT(CHUB_ST_HY_USE, hy_use);
+        ST_OUT(CHUB_ST_NOT_MEET, not_meet);
+        ST_OUT(CHUB_ST_HY_FOR_FC, hy_to_use);
+        ST_OUT(CHUB_ST_MASS_NEED, mass_need);
+        ST_OUT(CHUB_ST_FCEV_ARRIVE, hv_arrive);
+        ST_OUT(CHUB_ST_FCEV_LINE, hv_line);
+        ST_OUT(CHUB_ST_FCEV_QUEUE, queue);
+        ST_OUT(CHUB_ST_SOC_DEVIATION, deviation);
+        ST_OUT(CHUB_ST_SOC_PENALTY, fabs(deviation * cap_mass / 1000 / 0.2));  // MGR:277-290, as if the day ended now
+#undef ST_OUT
+    }
+    // the workgroup's rows as one run of out; under a mask that names only some of them, element by element
+    const bool whole = __syncthreads_and((live || env >= N) ? 1 : 0) != 0;
+    const int64_t left = N - env0;
+    const int total = (int) (left < kStBlock ? left : kStBlock) * C;
+    OUT *dst = (OUT *) a.out + env0 * C;
+    if (whole) {
+        for (int i = (int) threadIdx.x; i < total; i += kStBlock) dst[i] = s_rows[i];
+    } else {
+        for (int i = (int) threadIdx.x; i < total; i += kStBlock)
+            if (a.mask[env0 + i / C]) dst[i] = s_rows[i];
+    }
+}
+template <typename OUT>
+void launch_step_terms(const HubParams &hp, const DevCtx *ctx, uint32_t fields, const uint8_t *d_mask, OUT *d_out, hipStream_t stream) {
+    if (hp.n_envs <= 0) return;
+    StepTermsArgs a = {ctx, d_mask, d_out, 0ull, fields};
+    for (int f = 0; f < (int) CHUB_ST_COUNT; f++)
+        if (fields >> f & 1u) a.need |= step_term_reads(f);
+    hipLaunchKernelGGL(k_step_terms<OUT>, dim3((unsigned) ((hp.n_envs + kStBlock - 1) / kStBlock)), dim3(kStBlock), 0, stream, a);
+}
+template void launch_step_terms<float>(const HubParams &, const DevCtx *, uint32_t, const uint8_t *, float *, hipStream_t);
+template void launch_step_terms<double>(const HubParams &, const DevCtx *, uint32_t, const uint8_t *, double *, hipStream_t);
+
 // -------------------------------------------------------------------- per-station deadline profiles (chub_station_profile_device)
 // A station's cars binned by the time they have left: out[env][station][column][bucket], the columns of the field mask in ascending order,
 // a car with `left` slots to go in bucket min(left, B) - 1.  The per-pile values are pile_decode's, i.e. k_pile_obs' columns; new here is the

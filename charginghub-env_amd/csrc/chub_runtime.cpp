@@ -32,6 +32,8 @@ void launch_load_dispatch(const HubParams &hp, const DevCtx *ctx, int units, con
                           const float *d_tail, float *d_actions, uint64_t *d_bits, hipStream_t stream);
 void launch_forecast(const HubParams &hp, const DevCtx *ctx, const ForecastTabs &ft, uint32_t fields, int horizon, int t, const uint16_t *d_clk,
                      const uint8_t *d_mask, float *d_out, hipStream_t stream);
+template <typename OUT>
+void launch_step_terms(const HubParams &hp, const DevCtx *ctx, uint32_t fields, const uint8_t *d_mask, OUT *d_out, hipStream_t stream);
 template <bool RESET>
 void launch_env(EnvForm f, const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
                 const PackedPtrs &pp);
@@ -165,6 +167,9 @@ struct chub_env {
     // chub_forecast_device: the mean arrival counts per slot of day and, with per-env rows, the histogram of the FCEV arrival index (one block, built
     // on the host at create beside cnt / cnt_hv / hv_idx).  Derived data outside the arena, as d_cls_soc
     ForecastTabs fc = {nullptr, nullptr, nullptr};
+    // chub_set_step_terms: the caller's [N][C] f32 buffer every step call fills behind its kernels (run_call), and its field mask; null / 0: none
+    float *st_out = nullptr;
+    uint32_t st_fields = 0;
     double *d_ep_sum = nullptr;  // k_episode_summary's partials [kEpSumMaxBlocks][kEpSumWords], then the host form's result [kEpSumWords]
     int public_mode = 0;     // the rng_mode the handle was created with: CHUB_RNG_PHILOX_CURVES is hp.rng_mode = PHILOX + hp.soc_curves
     bool tape_only = false;  // ... and once there are any, the handle's class rows are the caller's: only tape resets / steps may admit cars
@@ -1525,8 +1530,16 @@ static int run_call(chub_env *e, const StepCall &call, hipStream_t s) {
         e->per_env = was_per_env;  // nothing was launched: the handle stays on the clock(s) it was on
         return rc;
     }
-    if (c.dmask) return CHUB_OK;  // (the launch itself notes whom it served: StepArgs::tick_note)
-    return note_served(e, c.mask, served, s);
+    // the attached step terms (chub_set_step_terms): the rows of the envs this step served, from the telemetry block its tail has just written --
+    // behind the step's kernels and, in an auto-reset call, in front of the reset that overwrites part of that block
+    hipError_t st_err = hipSuccess;
+    if (e->st_out && !c.reset) {
+        launch_step_terms<float>(e->hp, e->d_ctx, e->st_fields, mv.d_mask, e->st_out, s);
+        st_err = hipGetLastError();
+    }
+    if (!c.dmask) rc = note_served(e, c.mask, served, s);  // (a device mask: the launch itself notes whom it served, StepArgs::tick_note)
+    if (st_err != hipSuccess) return fail(CHUB_ERR_HIP, std::string("the step ran, its step terms could not be launched: ") + hipGetErrorString(st_err));
+    return rc;
 }
 
 int chub_reset_device(chub_env *e, const int32_t *d_exo_days, const double *d_exo_z, float *d_obs, void *stream) {
@@ -2705,6 +2718,67 @@ int chub_forecast(chub_env *e, uint32_t fields, int32_t horizon, float *out) {
     return rc;
 }
 
+// Step terms: what the last step's reward is made of and what a constrained learner penalises, as a read-only launch over the telemetry
+// block (k_step_terms); attached (chub_set_step_terms), run_call enqueues it behind every step
+static_assert((int) CHUB_ST_COUNT == 27 && (int) CHUB_ST_SOC_PENALTY == 26 && (int) CHUB_T_COUNT == kTelemCount, "k_step_terms reads CHUB_T_* columns into CHUB_ST_* fields");
+int chub_get_step_terms_size(uint32_t fields) {
+    if (fields == 0u || (fields >> CHUB_ST_COUNT) != 0u) return fail(CHUB_ERR_ARG, "fields: a non-empty mask over the CHUB_ST_* fields");
+    return __builtin_popcount(fields);
+}
+
+// what every step-terms entry point asks of its handle and mask
+static int check_step_terms(const chub_env *e, uint32_t fields, const void *out) {
+    if (!e || !out) return fail(CHUB_ERR_ARG, "null argument");
+    if (chub_get_step_terms_size(fields) < 0) return CHUB_ERR_ARG;
+    if (!(e->hp.telemetry & 1)) return fail(CHUB_ERR_ARG, "telemetry is off: the step terms are read from its block, call chub_set_telemetry(env, 1) first");
+    return CHUB_OK;
+}
+
+int chub_get_step_terms_device(chub_env *e, uint32_t fields, const uint8_t *d_mask, float *d_out, void *stream) {
+    if (const int rc = check_step_terms(e, fields, d_out)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    if (const int rc = sync_ctx(e, (hipStream_t) stream)) return rc;  // (nothing to do inside a capture: chub_graph_begin has done it)
+    launch_step_terms<float>(e->hp, e->d_ctx, fields, d_mask, d_out, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_get_step_terms(chub_env *e, uint32_t fields, double *out) {
+    if (const int rc = check_step_terms(e, fields, out)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t bytes = (size_t) e->hp.n_envs * (size_t) __builtin_popcount(fields) * sizeof(double);
+    double *d = nullptr;
+    HIP_TRY(hipMalloc((void **) &d, bytes));
+    int rc = sync_ctx(e, nullptr);
+    if (!rc) {
+        launch_step_terms<double>(e->hp, e->d_ctx, fields, nullptr, d, nullptr);
+        if (hipGetLastError() != hipSuccess || hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(CHUB_ERR_HIP, "the step terms could not be launched or copied to the host");
+    }
+    (void) hipFree(d);
+    return rc;
+}
+
+int chub_set_step_terms(chub_env *e, uint32_t fields, float *d_out) {
+    if (!e) return fail(CHUB_ERR_ARG, "null handle");
+    if (e->capturing)
+        return fail(CHUB_ERR_UNSUPPORTED, "chub_set_step_terms between chub_graph_begin and chub_graph_end (attach or detach between captures: "
+                                          "a recorded step keeps the launch it was recorded with)");
+    if (fields == 0u || !d_out) {  // detach
+        e->st_out = nullptr;
+        e->st_fields = 0u;
+        return CHUB_OK;
+    }
+    if (const int rc = check_step_terms(e, fields, d_out)) return rc;
+    e->st_out = d_out;
+    e->st_fields = fields;
+    return CHUB_OK;
+}
+
+int chub_get_step_terms_attached(const chub_env *e) { return e ? (int) e->st_fields : fail(CHUB_ERR_ARG, "null handle"); }
+
 // Station-level control: the dispatch of evs_step(float) as a read-only launch (k_load_dispatch) in front of any step form
 int chub_load_dispatch_device(chub_env *e, int units, const float *d_loads, const float *d_tail, const uint8_t *d_mask, float *d_actions,
                               uint64_t *d_pile_bits, void *stream) {
@@ -2772,6 +2846,8 @@ int chub_get_station_scalars(chub_env *e, double *out) {
 
 int chub_set_telemetry(chub_env *e, int enabled) {
     if (!e) return fail(CHUB_ERR_ARG, "null handle");
+    if (!enabled && e->st_out)
+        return fail(CHUB_ERR_ARG, "step terms are attached and read the telemetry block: detach first (chub_set_step_terms(env, 0, NULL))");
     HIP_TRY(hipSetDevice(e->device));
     if (enabled && !e->h_telem && !e->d_telem) {
         const size_t N = (size_t) e->hp.n_envs, D = (size_t) e->hp.obs_dim;

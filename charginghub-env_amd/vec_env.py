@@ -559,6 +559,39 @@ class VecChargingHub(object):
         check(self._lib.chub_forecast(self._h, mask, int(horizon), _ptr(out)))
         return out
 
+    # ---- step terms on the device (chub_get_step_terms_device): what the last step's reward is made of, the hydrogen side, constraint costs
+    def step_terms_device(self, d_out, fields=None, d_mask=0, stream=0):
+        """the terms of every env's last step into device memory, d_out [N, C] f32: env, then the C fields asked for in the order of
+        _lib.ST_NAMES -- each the f64 expression of include/chub.h over the telemetry block, narrowed once.  Needs set_telemetry(True).
+        fields: names, a bit mask, or None for all 27; d_mask [N] u8 in device memory: only the rows of the envs it names are written.
+        It reports the block as it stands (an env reset since its last step shows that step's hydrogen and money columns beside the new
+        episode's station columns).  One launch on `stream`: no synchronisation, nothing of the simulation changes, recordable into a
+        graph."""
+        check(self._lib.chub_get_step_terms_device(self._h, _lib.st_fields_mask(fields), d_mask or None, d_out, stream or None))
+
+    def step_terms(self, fields=None):
+        """the same for every env into host memory: float64 [N, C], the expressions before narrowing (the convenience form: it
+        allocates, synchronises and copies)"""
+        mask = _lib.st_fields_mask(fields)
+        out = np.zeros((self.n_envs, len(_lib.st_fields_names(mask))), dtype=np.float64)
+        check(self._lib.chub_get_step_terms(self._h, mask, _ptr(out)))
+        return out
+
+    def attach_step_terms(self, d_out, fields=None):
+        """from now on every step call of every form fills d_out [N, C] f32 (device memory that outlives the attachment) right behind its
+        kernels, on its own stream and with its own mask: only the rows of the envs a call served change, resets write nothing, and an
+        auto-reset step writes a restarted env's TERMINAL terms (chub_set_step_terms).  Needs set_telemetry(True); not between
+        graph_begin and graph_end."""
+        check(self._lib.chub_set_step_terms(self._h, _lib.st_fields_mask(fields), d_out))
+
+    def detach_step_terms(self):
+        check(self._lib.chub_set_step_terms(self._h, 0, None))
+
+    @property
+    def step_terms_attached(self):
+        """the attached field mask, or 0"""
+        return self._lib.chub_get_step_terms_attached(self._h)
+
     # ---- station-level control on the device (chub_load_dispatch_device): one target per station -> action rows / one bit per pile
     def load_dispatch_device(self, d_loads, d_tail, d_actions=0, d_pile_bits=0, units="kw", d_mask=0, stream=0):
         """the reference's evs_step(float) dispatch as one read-only launch on `stream`: d_loads [N, 2] f32 (one target per station: kW, or

@@ -279,6 +279,12 @@ class TorchHubVecEnv(object):
     makes ``forecast()`` available: what is deterministic about the next H slots of every env's day -- slot of day, tariff, the env's PV
     and wind profiles, mean arrivals -- as one [N, C, H] CUDA tensor (chub_forecast_device); ``forecast_names`` is the column order.
 
+    ``step_terms=("not_meet_loss", "grid_excess", "soc_penalty")`` (any of _lib.ST_NAMES; None: off) makes ``step_terms()`` available: what the
+    last step's reward is made of, the hydrogen side and the constraint costs a Lagrangian method penalises, as one float32 [N, C] CUDA
+    tensor; ``terms_names`` is the column order.  It switches the hub's telemetry on and attaches the buffer (chub_set_step_terms): every
+    step fills it behind its own kernels, so ``step_terms()`` launches nothing, and an env the step has just re-started (either autoreset
+    mode) shows the terms of its TERMINAL step -- the end-of-day ``soc_penalty`` included -- beside the new episode's first observation.
+
     ``control="station"`` makes the policy set one load per station instead of one action per pile (the reference's evs_step(float)):
     ``act_dim`` is 4 whatever the hub -- load of station 0, load of station 1, the two tail actions -- and every ``step`` first turns the
     loads into an action row the adapter owns (chub_load_dispatch_device, one read-only launch on torch's stream), then takes the step
@@ -287,7 +293,7 @@ class TorchHubVecEnv(object):
     is the adapter described above."""
 
     def __init__(self, n_envs, station_list, station_type_list, seed=0, device=0, autoreset=True, episode_stats=False, pile_obs=None,
-                 station_profile=None, control="pile", load_units="fraction", forecast=None, **hub_kwargs):
+                 station_profile=None, control="pile", load_units="fraction", forecast=None, step_terms=None, **hub_kwargs):
         import torch  # before libchub is loaded by VecChargingHub: both must share one HIP runtime
 
         if not (autoreset is True or autoreset is False or autoreset == "per_env"):
@@ -316,6 +322,8 @@ class TorchHubVecEnv(object):
             if not 1 <= self._fc_horizon <= 96:
                 raise ValueError("forecast: horizon 1 .. 96, not %d" % self._fc_horizon)
         self.forecast_names = () if self._fc_mask is None else _lib.fc_fields_names(self._fc_mask)
+        self._st_mask = None if step_terms is None else _lib.st_fields_mask(step_terms)  # (ValueError for an unknown name, before anything is built)
+        self.terms_names = () if step_terms is None else _lib.st_fields_names(self._st_mask)
         self.torch = torch
         self.device = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
         if self.device.type == "cuda":
@@ -355,6 +363,20 @@ class TorchHubVecEnv(object):
         self._fc_buf = None
         if self._fc_mask is not None:
             self._fc_buf = torch.zeros((self.num_envs, len(self.forecast_names), self._fc_horizon), dtype=torch.float32, device=self.device)
+
+        self._st_buf = None
+        if self._st_mask is not None:  # every step fills the buffer behind its own kernels, from the telemetry block its tail writes
+            self._st_buf = torch.zeros((self.num_envs, len(self.terms_names)), dtype=torch.float32, device=self.device)
+            self.vec.set_telemetry(True)
+            self.vec.attach_step_terms(self._st_buf.data_ptr(), self._st_mask)
+
+    def step_terms(self):
+        """float32 [N, C] CUDA tensor: for every env the columns of ``terms_names`` of its last step (zeros before the first).  Nothing is
+        launched here: the step itself filled the buffer, on the stream it ran on.  An env the step re-started keeps its terminal step's
+        terms; a reset writes nothing.  It is ONE buffer, overwritten by the next step."""
+        if self._st_buf is None:
+            raise RuntimeError("step terms are off: construct with step_terms=(names of _lib.ST_NAMES)")
+        return self._st_buf
 
     def forecast(self):
         """float32 [N, C, H] CUDA tensor: for every env the columns of ``forecast_names`` over the next H slots of its day, h = 0 being the

@@ -636,6 +636,71 @@ int chub_forecast_size(uint32_t fields, int32_t horizon);
 int chub_forecast_device(chub_env *env, uint32_t fields, int32_t horizon, const uint8_t *d_mask, float *d_out, void *stream);
 int chub_forecast(chub_env *env, uint32_t fields, int32_t horizon, float *out);
 
+/* ---- step terms on the device: reward parts, hydrogen side, constraint costs ----------------------------------------------------------
+ * What the reward of a step is made of, and what a constrained learner penalises: the reference keeps them as attributes after every step
+ * (re_income_*, re_hy_cost, hy_loss, not_meet_loss, cumulated_draw_ele's increment, the forecourt, the tank's distance from init_soc; its
+ * own use_lagrangian / test_penalty block is MGR:275-297).  Every one of them is a function of the telemetry block the step's tail writes
+ * in every launch form and RNG mode (CHUB_T_*), of init_soc and of capacity_mass; chub_get_step_terms_device evaluates that function for every
+ * env in ONE read-only launch on `stream` and writes the columns asked for into the caller's device memory.
+ * With T[x] = telemetry column CHUB_T_x of the env and p = T[PRICE_NOW] / 4, every expression evaluated in f64 in the order written
+ * (no contraction; constants folded as the reference's Python folds them):
+ *    0 REWARD         T[REWARD]                           (MGR:267)      14 FC_POWER       T[FC_POWER]
+ *    1 INCOME         T[INCOME]                           (MGR:259)      15 HY_ACT         T[HY_ACT]
+ *    2 INCOME_EVS0    0.42 / 4 * T[CHG0]      re_income_evs_list[0]      16 GEN_HY         T[HY_FLOW_SPEED] > 0.5 ? 1 : 0   (MGR:173-179)
+ *    3 INCOME_EVS1    0.21 / 4 * T[CHG1]      re_income_evs_list[1]      17 HY_GEN         15 * 60 * T[HY_FLOW_SPEED]           re_hy_gen
+ *    4 COST_EVS0      -p * T[EV0_NET]    re_income_evs_cost_list[0]      18 HY_USE         T[HY_USE]
+ *    5 COST_EVS1      -p * T[EV1_NET]    re_income_evs_cost_list[1]      19 NOT_MEET       T[NOT_MEET]
+ *    6 INCOME_SERVE   0.8 * (T[FLOW0] + T[FLOW1]) re_income_evs_serve    20 HY_FOR_FC      T[HY_TO_USE]                      re_hy_for_fc
+ *    7 INCOME_HYS     6 / 1000 * T[HY_USE]            re_income_hys      21 MASS_NEED      T[TOTAL_MASS_NEED]
+ *    8 HY_COST        -p * T[HYDROGEN_POWER]             re_hy_cost      22 FCEV_ARRIVE    T[HV_ARRIVE]
+ *    9 HY_LOSS        -6 / 1000 * T[HY_TO_USE]            (MGR:225)      23 FCEV_LINE      T[HV_LINE]
+ *   10 NOT_MEET_LOSS  -10 / 1000 * T[NOT_MEET]            (MGR:255)      24 FCEV_QUEUE     T[QUEUE_LEN]
+ *   11 GRID_DRAW      (T[EV0_NET] + T[EV1_NET]) + T[HYDROGEN_POWER]      25 SOC_DEVIATION  fabs(T[STORE_SOC] - init_soc)        (MGR:297)
+ *                     (MGR:262: the ledger's DRAW_ELE increment)         26 SOC_PENALTY    fabs(SOC_DEVIATION * capacity_mass / 1000 / 0.2)
+ *   12 GRID_EXCESS    max(GRID_DRAW - 2000, 0)  (the 2000 kW of MGR:160)                   (MGR:277-290, "as if the day ended now")
+ *   13 USED_RENEW     T[USED_RENEW]
+ * init_soc and capacity_mass are the handle's; on a handle made by chub_create_params the env's own row, exactly as the ledger takes them.
+ * So INCOME = (INCOME_HYS + ((INCOME_EVS0 + COST_EVS0) + (INCOME_EVS1 + COST_EVS1))) + INCOME_SERVE + HY_COST bit for bit (the tail's own
+ * expression), that sum + HY_LOSS + NOT_MEET_LOSS over 50 is REWARD within 1 ulp, and (float) REWARD is the step's reward output.
+ *   fields  a bit mask over the CHUB_ST_* enum (bit f = field f); C = its popcount columns come out, in ascending field order.
+ *           chub_get_step_terms_size gives C for a valid mask (it needs no device), CHUB_ERR_ARG for 0 or bits from CHUB_ST_COUNT up.
+ *   d_out   [N][C] f32, env-major; each value is the f64 expression narrowed once.
+ *   d_mask  [N] u8 in device memory or NULL: with a mask only the rows of the envs whose byte is non-zero are written, every other row of
+ *           d_out is left alone (an all-zero mask writes nothing).
+ * Manners are chub_pile_obs_device's: it reads the telemetry block and writes d_out, nothing else (no tick, no clock, no draw); it returns
+ * after enqueueing (no synchronisation, no allocation, no staging copy); recordable between chub_graph_begin and chub_graph_end, where it
+ * does not count towards the even number of resets + steps.  It works wherever telemetry works: all three RNG modes, every hub shape,
+ * per-env rows, tape handles, and both homes of the block (pinned host memory on handles of a few envs, device memory otherwise).
+ * It reports the block AS IT STANDS.  A reset rewrites the station columns, STORE_SOC, the exogenous columns and the days of the envs it
+ * restarts and leaves the rest: an env reset since its last step shows that step's hydrogen and money columns (REWARD, INCOME, COST_*,
+ * HY_*, GRID_*, FCEV_*, ...) beside the NEW episode's INCOME_EVS0/1, INCOME_SERVE and SOC_*.  Before the first step the block is zero.
+ *   chub_get_step_terms: the convenience form, every env, out [N][C] F64 in host memory: the expressions before narrowing, by the same kernel
+ *       with an f64 store.  It allocates, copies and synchronises.
+ *   chub_set_step_terms: attaches d_out [N][C] f32 (the caller's device memory, which must outlive the attachment).  From then on every STEP
+ *       call of every form -- lock-step, host-masked, device-masked, bits, load, packed, gather, tape, chub_run_steps and the step half of
+ *       chub_autoreset_step_device -- enqueues the launch on its own stream right behind the step's kernels, with that call's mask: only the
+ *       rows of the envs the call served change.  Resets never write d_out.  In chub_autoreset_step_device the launch goes BETWEEN the step
+ *       and the reset, so a restarted env's row holds its TERMINAL step's terms -- the end-of-day SOC_DEVIATION / SOC_PENALTY and station
+ *       incomes the reset is about to overwrite in the block -- beside the new episode's first observation in d_packed.  Inside a capture
+ *       the launch is one more node of the graph (not counted towards the even number of resets + steps).  fields == 0 or d_out == NULL
+ *       detaches.  CHUB_ERR_ARG when telemetry is off or the mask is bad; CHUB_ERR_UNSUPPORTED between chub_graph_begin and chub_graph_end
+ *       (a recorded step keeps the launch it was recorded with: a graph recorded while attached fills the buffer on every replay).  While
+ *       an output is attached chub_set_telemetry(env, 0) is CHUB_ERR_ARG: detach first.  With nothing attached a step costs one null
+ *       test on the host more than before.
+ *   chub_get_step_terms_attached: the attached mask, or 0.
+ * All of them: CHUB_ERR_ARG with a message for a null handle or null output, a bad mask, telemetry off. */
+enum {
+    CHUB_ST_REWARD = 0, CHUB_ST_INCOME, CHUB_ST_INCOME_EVS0, CHUB_ST_INCOME_EVS1, CHUB_ST_COST_EVS0, CHUB_ST_COST_EVS1, CHUB_ST_INCOME_SERVE,
+    CHUB_ST_INCOME_HYS, CHUB_ST_HY_COST, CHUB_ST_HY_LOSS, CHUB_ST_NOT_MEET_LOSS, CHUB_ST_GRID_DRAW, CHUB_ST_GRID_EXCESS, CHUB_ST_USED_RENEW,
+    CHUB_ST_FC_POWER, CHUB_ST_HY_ACT, CHUB_ST_GEN_HY, CHUB_ST_HY_GEN, CHUB_ST_HY_USE, CHUB_ST_NOT_MEET, CHUB_ST_HY_FOR_FC, CHUB_ST_MASS_NEED,
+    CHUB_ST_FCEV_ARRIVE, CHUB_ST_FCEV_LINE, CHUB_ST_FCEV_QUEUE, CHUB_ST_SOC_DEVIATION, CHUB_ST_SOC_PENALTY, CHUB_ST_COUNT
+};
+int chub_get_step_terms_size(uint32_t fields);
+int chub_get_step_terms_device(chub_env *env, uint32_t fields, const uint8_t *d_mask, float *d_out, void *stream);
+int chub_get_step_terms(chub_env *env, uint32_t fields, double *out);
+int chub_set_step_terms(chub_env *env, uint32_t fields, float *d_out);
+int chub_get_step_terms_attached(const chub_env *env);
+
 /* ---- station-level control on the device: kW targets to pile actions ------------------------------------------------------------------
  * The reference's station-level control, evs_step(float) (CHS.hpp:1169-1186 / 1480-1497: catch_load, assign_on_off, rank_power_add), takes
  * one kW target per station and switches the piles on in urgency order until the target is met.  chub_step_load* runs it inside the
