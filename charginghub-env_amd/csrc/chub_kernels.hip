@@ -1781,6 +1781,9 @@ __device__ __forceinline__ bool mask_is_empty(const StepArgs &sa) { return sa.sk
 #define CHUB_ACC_COPIES 2  // copies of a unit's LDS accumulators (lanes spread over them by lane number: fewer same-address atomics; 1 / 2 / 4: 21.28 / 20.95 / 21.12 us)
 #endif
 constexpr int kAccCopies = CHUB_ACC_COPIES;
+#ifndef CHUB_TAIL_PRE
+#define CHUB_TAIL_PRE 1  // 1: the tail actions packed_records hands over are requested with the workgroup's first loads; 0: where it stores them (A/B)
+#endif
 #ifndef CHUB_EPI_ALL
 #define CHUB_EPI_ALL 1  // 1: every wave of the workgroup takes its share of the new cars (a third barrier: -0.2 us at C4); 0: the last wave alone
 #endif
@@ -1788,7 +1791,8 @@ constexpr int kAccCopies = CHUB_ACC_COPIES;
 // barrier: every car's LDS atomics are in).  FUSED: also into s_rec, for the tails that follow in the same workgroup.
 #define CHUB_AT(T_, base, byte_off) (*(CHUB_G(T_)) ((CHUB_G(char)) (base) + (uint32_t) (byte_off)))
 template <int BLOCK, int T, bool RESET, bool BIG, bool MASKED, bool FUSED, bool BITS>
-__device__ __forceinline__ void packed_records(const PackedArgs &pa, const uint32_t block_local, int *s_acc, const uint32_t *s_unit, u32x4 *s_rec) {
+__device__ __forceinline__ void packed_records(const PackedArgs &pa, const uint32_t block_local, int *s_acc, const uint32_t *s_unit, u32x4 *s_rec,
+                                               const float *tail_pre = nullptr) {
     const int lane = threadIdx.x & 63;
     const int S0 = (int) pa.S[0], S1 = (int) pa.S[1], St = S0 + S1;
     const int epb = (int) pa.epb, N = (int) pa.n_envs;
@@ -1806,8 +1810,12 @@ __device__ __forceinline__ void packed_records(const PackedArgs &pa, const uint3
         const uint32_t su = (uint32_t) (k ? N : 0) + (uint32_t) env;
         if (!RESET && !FUSED && !BITS && k == 0) {  // the env's tail actions sit in the lines this workgroup has just read: hand them to the tail kernel packed
             typedef float f32x2_ __attribute__((ext_vector_type(2)));
+            // The first pass (unit i = lane: all there is for hubs of 16 piles and more, 32 envs per workgroup at most) has them in registers,
+            // requested with the workgroup's first loads (slot_body_packed); the passes behind it read them here.
             const uint32_t ai = ((uint32_t) env * (uint32_t) (St + 2) + (uint32_t) St) << 2;
-            const f32x2_ tv = {CHUB_AT(const float, pa.actions, ai), CHUB_AT(const float, pa.actions, ai + 4u)};
+            f32x2_ tv;
+            if (CHUB_TAIL_PRE && i < 64) tv = f32x2_{tail_pre[0], tail_pre[1]};
+            else tv = f32x2_{CHUB_AT(const float, pa.actions, ai), CHUB_AT(const float, pa.actions, ai + 4u)};
             CHUB_AT(f32x2_, pa.tail_act, (uint32_t) env << 3) = tv;
         }
         uint32_t lf = s_unit[i];
@@ -1886,8 +1894,15 @@ __device__ __forceinline__ int slot_body_packed(const HubParams &hp, const StepA
     // per lane: the loads and stores take the base from SGPRs and need no 64-bit address arithmetic
 #define CHUB_AT(T_, base, byte_off) (*(CHUB_G(T_)) ((CHUB_G(char)) (base) + (uint32_t) (byte_off)))
 
-    // phase A loads: slot state, action, the unit's queue length and packed draws.  No zero fill for the lanes without a slot:
-    // what they hold is never used (their occupancy is forced to 0 below).
+    // phase A loads: slot state, action, the unit's packed draws.  Steps on the small tile request the state words of all T slots FIRST and everything
+    // else behind them (the per-env clock byte, the draws, the action rows or bit words, the last wave's tail actions): vector loads
+    // return in order, and the class-row requests below wait for the state words alone -- the draws are not looked at before the
+    // admission, the actions not before the rows are in.  All of a step's requests sit in one basic block and are issued by every lane:
+    // a lane without a slot asks for the workgroup's first slot / env (env_first < N in every launch), and what it gets is never used
+    // (its occupancy is forced to 0 below).  One block, because behind exec-predicated blocks the wait in front of the class rows
+    // comes out as vmcnt(0).  Two forms keep the slot-by-slot order: the large tile, whose streams come from HBM (state words first cost it
+    // 1.4 % of the C5 step), and the one-launch kernels (FUSED: 0.4-1 % of the C2 step; they compile to what they were) -- docs/LAB_NOTEBOOK.md, Part I.
+    constexpr bool STATE_FIRST = !RESET && !FUSED && BLOCK <= 256;
     int e_[T], k_[T], slot[T];
     bool valid[T];
     uint32_t sidx[T];
@@ -1896,6 +1911,12 @@ __device__ __forceinline__ int slot_body_packed(const HubParams &hp, const StepA
     u32x2 actw[T];  // BITS: the word of the env's decision bits this slot's bit sits in
     int hs_[T];
     uint32_t pk_in[T];
+    uint32_t served[T];  // per-env clocks: is the env served by this launch?  Requested right behind the state, looked at with it
+    // The env's two tail actions sit in the lines this workgroup reads anyway: the lane of the last wave that will write env lane / 2's
+    // records (packed_records, its first pass) asks for them here and hands them to the tail kernel from registers, not behind a
+    // round trip of its own at the end of the workgroup's life.
+    constexpr bool HOIST_TAIL = CHUB_TAIL_PRE && !RESET && !FUSED && !BITS;
+    float tail_pre[2];
 #pragma unroll
     for (int j = 0; j < T; j++) {
         const int v = tid + j * BLOCK;
@@ -1908,23 +1929,57 @@ __device__ __forceinline__ int slot_body_packed(const HubParams &hp, const StepA
         slot[j] = hs - (k_[j] ? S0 : 0);
         const int env = env_first + e_[j];
         valid[j] = e_[j] < epb && env < N;
-        uint32_t served = 1u;  // per-env clocks: is the env served by this launch?  Requested with the state, looked at after it
-        if (MASKED && valid[j]) served = pa.env_mask[env];
+        served[j] = 1u;
         sidx[j] = (uint32_t) (k_[j] ? N : 0) + (uint32_t) env;
         asm volatile("" : "=v"(s2[j]), "=v"(act[j]), "=v"(pk_in[j]), "=v"(actw[j]));
-        if (RESET) {
-            s2[j] = 0u;
-            act[j] = 0.0f;
-        }
-        if (valid[j]) {
-            if (!RESET) {
-                s2[j] = CHUB_AT(uint32_t, pa.state, (idx0 + (uint32_t) v) << 2);
-                if (BITS) actw[j] = CHUB_AT(const u32x2, pa.actions, ((uint32_t) env * (((uint32_t) St + 63u) >> 6) + ((uint32_t) hs >> 6)) << 3);
-                else act[j] = CHUB_ACT_LOAD((CHUB_G(const float)) ((CHUB_G(const char)) pa.actions + (uint32_t) ((idx0 + (uint32_t) v + 2u * (uint32_t) env) << 2)));  // row stride S0 + S1 + 2
+        if (!STATE_FIRST) {  // slot by slot, the lanes that have one: clock byte, state, action, draws
+            if (RESET) {
+                s2[j] = 0u;
+                act[j] = 0.0f;
             }
-            pk_in[j] = CHUB_AT(const uint32_t, pa.pk, sidx[j] << 2);
+            if (MASKED && valid[j]) served[j] = pa.env_mask[env];
+            if (valid[j]) {
+                if (!RESET) {
+                    s2[j] = CHUB_AT(uint32_t, pa.state, (idx0 + (uint32_t) v) << 2);
+                    if (BITS) actw[j] = CHUB_AT(const u32x2, pa.actions, ((uint32_t) env * (((uint32_t) St + 63u) >> 6) + ((uint32_t) hs >> 6)) << 3);
+                    else act[j] = CHUB_ACT_LOAD((CHUB_G(const float)) ((CHUB_G(const char)) pa.actions + (uint32_t) ((idx0 + (uint32_t) v + 2u * (uint32_t) env) << 2)));  // row stride S0 + S1 + 2
+                }
+                pk_in[j] = CHUB_AT(const uint32_t, pa.pk, sidx[j] << 2);
+            }
         }
-        if (MASKED && valid[j]) valid[j] = served != 0u;
+    }
+    if (STATE_FIRST) {
+        uint32_t vc[T], envc[T];  // the lane's slot and env, or the workgroup's first
+#pragma unroll
+        for (int j = 0; j < T; j++) {
+            vc[j] = valid[j] ? (uint32_t) (tid + j * BLOCK) : 0u;
+            envc[j] = valid[j] ? (uint32_t) (env_first + e_[j]) : (uint32_t) env_first;
+        }
+#pragma unroll
+        for (int j = 0; j < T; j++) s2[j] = CHUB_AT(uint32_t, pa.state, (idx0 + vc[j]) << 2);
+        asm volatile("" ::: "memory");  // (the compiler keeps the requests of one block in this order)
+        if (MASKED) {
+#pragma unroll
+            for (int j = 0; j < T; j++) served[j] = CHUB_AT(const uint8_t, pa.env_mask, envc[j]);
+            asm volatile("" ::: "memory");
+        }
+#pragma unroll
+        for (int j = 0; j < T; j++) pk_in[j] = CHUB_AT(const uint32_t, pa.pk, (valid[j] ? sidx[j] : (uint32_t) env_first) << 2);
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int j = 0; j < T; j++) {
+            if (BITS) actw[j] = CHUB_AT(const u32x2, pa.actions, (envc[j] * (((uint32_t) St + 63u) >> 6) + (valid[j] ? (uint32_t) hs_[j] >> 6 : 0u)) << 3);
+            else act[j] = CHUB_ACT_LOAD((CHUB_G(const float)) ((CHUB_G(const char)) pa.actions + (uint32_t) ((idx0 + vc[j] + 2u * envc[j]) << 2)));  // row stride S0 + S1 + 2
+        }
+    }
+    if (HOIST_TAIL) asm volatile("" : "=v"(tail_pre[0]), "=v"(tail_pre[1]));
+    if (HOIST_TAIL && wave == WAVES - 1) {  // behind everything else: the other waves' wait for the state words then leaves them in flight as well
+        asm volatile("" ::: "memory");
+        const int te = env_first + (lane >> 1);
+        const uint32_t tenv = (uint32_t) ((lane >> 1) < epb && te < N ? te : env_first);
+        const uint32_t ai = (tenv * (uint32_t) (St + 2) + (uint32_t) St) << 2;
+        tail_pre[0] = CHUB_AT(const float, pa.actions, ai);
+        tail_pre[1] = CHUB_AT(const float, pa.actions, ai + 4u);
     }
     if (!TAPE) {  // the new cars' Philox inputs: scalar registers from here on, requested behind the first loads
         pa.tick += sload_u32(pa.tick_base, 0);  // CHUB_TICK
@@ -1946,9 +2001,22 @@ __device__ __forceinline__ int slot_body_packed(const HubParams &hp, const StepA
     bool stays[T];
     f32x4 row[T];
     float ttg[T];
+    // (every state word waited for in front of the first request: a wait behind slot 0's requests could not leave them in flight
+    // without leaving the draws and actions, which are older, behind)
+    if (!FUSED) {
+#pragma unroll
+        for (int j = 0; j < T; j++) asm volatile("" : "+v"(s2[j]));
+    }
+    if (MASKED) {  // ... and the clock bytes, which were requested right behind them: an env the launch does not serve has no slots here
+#pragma unroll
+        for (int j = 0; j < T; j++) {
+            asm volatile("" : "+v"(served[j]));
+            valid[j] = valid[j] && served[j] != 0u;
+        }
+    }
 #pragma unroll
     for (int j = 0; j < T; j++) {
-        asm volatile("" : "+v"(s2[j]));
+        if (FUSED) asm volatile("" : "+v"(s2[j]));  // (the one-launch kernels: slot by slot, as their loads)
         w0[j] = valid[j] ? s2[j] : 0u;
         tl[j] = ps_tl(w0[j]);
         stays[j] = tl[j] > 1;
@@ -2185,7 +2253,7 @@ __device__ __forceinline__ int slot_body_packed(const HubParams &hp, const StepA
 #endif
         if (wave != WAVES - 1) return 0;
     }
-    packed_records<BLOCK, T, RESET, BIG, MASKED, false, BITS>(pa, block_local, s_acc, s_unit, nullptr);
+    packed_records<BLOCK, T, RESET, BIG, MASKED, false, BITS>(pa, block_local, s_acc, s_unit, nullptr, tail_pre);
 #if CHUB_TRACE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     CHUB_STAMP(11);  // records stored: the workgroup is done
