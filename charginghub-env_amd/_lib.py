@@ -172,6 +172,80 @@ def load_units(units):
     return int(units)
 
 
+# an actor on the device (chub_policy_*): the CHUB_PIN_* / CHUB_PACT_* / CHUB_PHEAD_* / CHUB_PSQ_* / CHUB_PRUN_* enums of include/chub.h, in order
+PIN_NAMES = ("obs", "pile_obs", "station_profile", "forecast")
+PACT_NAMES = ("tanh", "relu")
+PHEAD_NAMES = ("piles", "loads")
+PSQ_NAMES = ("tanh", "clip")
+PRUN_NAMES = ("lockstep", "autoreset")
+PIN = {name: i for i, name in enumerate(PIN_NAMES)}
+PACT = {name: i for i, name in enumerate(PACT_NAMES)}
+PHEAD = {name: i for i, name in enumerate(PHEAD_NAMES)}
+PSQ = {name: i for i, name in enumerate(PSQ_NAMES)}
+PRUN = {name: i for i, name in enumerate(PRUN_NAMES)}
+POLICY_MAX_INPUTS = POLICY_MAX_LAYERS = 4
+
+
+class ChubPolicyInput(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("fields", C.c_int32), ("param", C.c_int32)]
+
+
+class ChubPolicySpec(C.Structure):
+    """chub_policy_spec of include/chub.h"""
+    _fields_ = [("n_inputs", C.c_int32), ("inputs", ChubPolicyInput * 4), ("n_layers", C.c_int32), ("width", C.c_int32 * 4),
+                ("hidden_act", C.c_int32), ("head", C.c_int32), ("squash", C.c_int32), ("normalize", C.c_int32), ("clip", C.c_float)]
+
+
+def _enum_value(table, value, what):
+    if isinstance(value, str):
+        if value not in table:
+            raise ValueError("unknown %s %r (one of %s)" % (what, value, ", ".join(table)))
+        return table[value]
+    return int(value)
+
+
+def policy_inputs(inputs):
+    """the input blocks of a policy as (kind, fields mask, param) triples.  An entry is a kind name ("obs"; the feature blocks with every
+    field and 8 buckets / slots of look-ahead), or a tuple (kind, fields[, param]) with fields as the feature call takes them"""
+    if isinstance(inputs, str):
+        inputs = (inputs,)
+    out = []
+    for entry in inputs:
+        kind, fields, param = (entry, None, None) if isinstance(entry, (str, int)) else (tuple(entry) + (None, None))[:3]
+        kind = _enum_value(PIN, kind, "policy input")
+        if kind == PIN["obs"]:
+            out.append((kind, 0, 0))
+        elif kind == PIN["pile_obs"]:
+            out.append((kind, pile_fields_mask(fields), 0))
+        elif kind == PIN["station_profile"]:
+            out.append((kind, sp_fields_mask(fields), 8 if param is None else int(param)))
+        elif kind == PIN["forecast"]:
+            out.append((kind, fc_fields_mask(fields), 8 if param is None else int(param)))
+        else:
+            out.append((kind, int(fields or 0), int(param or 0)))  # (the library refuses it with its own message)
+    return out
+
+
+def policy_spec(widths, inputs=("obs",), head="piles", hidden_act="tanh", squash="tanh", normalize=False, clip=0.0):
+    """a chub_policy_spec from Python values: widths = the outputs of every layer (the last one the head's), inputs as policy_inputs takes
+    them.  Counts beyond the struct's four slots are passed on as they are: the library refuses them"""
+    spec = ChubPolicySpec()
+    blocks = policy_inputs(inputs)
+    spec.n_inputs = len(blocks)
+    for i, (kind, fields, param) in enumerate(blocks[:POLICY_MAX_INPUTS]):
+        spec.inputs[i].kind, spec.inputs[i].fields, spec.inputs[i].param = kind, fields, param
+    widths = [int(w) for w in widths]
+    spec.n_layers = len(widths)
+    for l, w in enumerate(widths[:POLICY_MAX_LAYERS]):
+        spec.width[l] = w
+    spec.hidden_act = _enum_value(PACT, hidden_act, "hidden activation")
+    spec.head = _enum_value(PHEAD, head, "policy head")
+    spec.squash = _enum_value(PSQ, squash, "squash")
+    spec.normalize = int(bool(normalize))
+    spec.clip = float(clip)
+    return spec
+
+
 class ChubOptions(C.Structure):
     """chub_options of include/chub.h (all zero = defaults; the library reads no environment variables)"""
     _fields_ = [("slot_kernel", C.c_int32), ("no_arena", C.c_int32), ("fused_step", C.c_int32), ("tile", C.c_int32), ("walk_ahead", C.c_int32), ("work_order", C.c_int32), ("span_steps", C.c_int32), ("span_tails", C.c_int32)]
@@ -216,7 +290,7 @@ def source_hash():
 
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
-    for name in ("chub_kernels.hip", "chub_runtime.cpp", "chub_comm.cpp", "chub_device.h", "chub_curves.h", "chub_plan.h"):
+    for name in ("chub_kernels.hip", "chub_policy.hip", "chub_runtime.cpp", "chub_comm.cpp", "chub_device.h", "chub_curves.h", "chub_plan.h", "chub_policy.h"):
         h.update(open(os.path.join(csrc, name), "rb").read())
     h.update(open(os.path.join(os.path.dirname(_HERE), "include", "chub.h"), "rb").read())
     return h.hexdigest()[:16]
@@ -302,6 +376,11 @@ def load_library():
         "chub_malloc_device": (I, [I, L, C.POINTER(P)]), "chub_free_device": (I, [I, P]), "chub_copy_to_host": (I, [I, P, P, L, P]),
         "chub_copy_to_device": (I, [I, P, P, L, P]), "chub_alloc_host": (I, [I, L, C.POINTER(P)]), "chub_free_host": (I, [I, P]), "chub_stream_create": (I, [I, C.POINTER(P)]), "chub_stream_destroy": (I, [I, P]),
         "chub_stream_sync": (I, [I, P]),
+        "chub_policy_input_width": (I, [C.POINTER(ChubConfig), C.POINTER(ChubPolicySpec), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "chub_policy_create": (I, [P, C.POINTER(ChubPolicySpec), P, P, P, P, C.POINTER(P)]), "chub_policy_destroy": (I, [P]),
+        "chub_policy_set_weights": (I, [P, C.c_int32, P, P]), "chub_policy_set_weights_device": (I, [P, C.c_int32, P, P, P]),
+        "chub_policy_act_device": (I, [P, P, P, L, P, P, P, P, P]), "chub_policy_act": (I, [P, P, P, P]),
+        "chub_policy_run_steps": (I, [P, P, I, P, P, P, L, L, P]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -335,7 +414,9 @@ EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "ch
             "chub_episode_summary_device", "chub_episode_summary", "chub_pile_obs_columns", "chub_pile_obs_device",
             "chub_station_profile_size", "chub_station_profile_device", "chub_load_dispatch_device", "chub_load_dispatch",
             "chub_forecast_size", "chub_forecast_device", "chub_forecast",
-            "chub_get_step_terms_size", "chub_get_step_terms_device", "chub_get_step_terms", "chub_set_step_terms", "chub_get_step_terms_attached"]
+            "chub_get_step_terms_size", "chub_get_step_terms_device", "chub_get_step_terms", "chub_set_step_terms", "chub_get_step_terms_attached",
+            "chub_policy_input_width", "chub_policy_create", "chub_policy_destroy", "chub_policy_set_weights", "chub_policy_set_weights_device",
+            "chub_policy_act_device", "chub_policy_act", "chub_policy_run_steps"]
 
 
 def check(rc):

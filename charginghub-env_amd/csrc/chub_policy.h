@@ -1,0 +1,66 @@
+// chub_policy.h -- what the actor kernel (chub_policy.hip) and the host (chub_runtime.cpp) share: the kernel's argument block, the
+// device weight layout and the enums of include/chub.h's section "an actor on the device", restated for device code.
+#ifndef CHUB_POLICY_H
+#define CHUB_POLICY_H
+
+#include <stdint.h>
+
+#include <hip/hip_runtime.h>
+
+namespace chub {
+
+// the CHUB_PIN_* / CHUB_PACT_* / CHUB_PHEAD_* / CHUB_PSQ_* / CHUB_PRUN_* enums of include/chub.h (chub_runtime.cpp asserts the two agree)
+enum PolicyInput { PIN_OBS = 0, PIN_PILE_OBS, PIN_STATION_PROFILE, PIN_FORECAST, PIN_COUNT };
+enum PolicyAct { PACT_TANH = 0, PACT_RELU, PACT_COUNT };
+enum PolicyHead { PHEAD_PILES = 0, PHEAD_LOADS, PHEAD_COUNT };
+enum PolicySquash { PSQ_TANH = 0, PSQ_CLIP, PSQ_COUNT };
+enum PolicyRun { PRUN_LOCKSTEP = 0, PRUN_AUTORESET, PRUN_COUNT };
+
+constexpr int kPolicyMaxInputs = 4, kPolicyMaxLayers = 4, kPolicyMaxHidden = 256;
+constexpr int kPolicyEnvTile = 32;    // envs per workgroup: the column count of v_mfma_f32_32x32x2_f32
+constexpr int kPolicyOutTile = 32;    // outputs per accumulator tile: its row count
+constexpr int kPolicyMaxWaves = 4;    // waves per workgroup at most (one output tile per wave and round)
+// The activations of a tile live in two LDS images, [row][32 envs] f32: P holds the feature row and the outputs of the odd layers, Q the
+// outputs of the even layers.  Together at most 512 rows (64 KiB, what a launch gets without asking for more).
+constexpr int kPolicyLdsRows = 512;
+
+// Device weight layout of one layer (built by k_policy_relayout from the trainer's row-major [out][in]): per tile of 32 outputs the
+// transposed block [k_pad][32], zero beyond `in` and `out` -- lane l of a wave reads element 64 s + l of a tile at k-step s, which is
+// W[32 tile + (l & 31)][2 s + (l >> 5)]: the A operand of the f32-input MFMA.  Biases are [32 tiles] with zeros beyond `out`.
+struct PolicyLayer {
+    const float *w;   // [tiles][k_pad][32]
+    const float *b;   // [tiles * 32]
+    int32_t k_pad;    // inputs, rounded up to the MFMA's k step (2); the LDS rows beyond `in` hold zeros
+    int32_t tiles;    // output tiles of 32
+};
+
+struct PolicyBlock {
+    const float *p;   // [N] rows of `width` floats with row stride ld
+    int64_t ld;
+    int32_t width;
+    int32_t pad_;
+};
+
+struct PolicyArgs {
+    int64_t n_envs;
+    PolicyBlock in[kPolicyMaxInputs];
+    PolicyLayer layer[kPolicyMaxLayers];
+    const float *mean, *inv_std;  // [F], read when normalize != 0
+    const uint8_t *mask;          // [N] or null
+    float *actions;               // [N][A] or null (PILES)
+    uint32_t *bits;               // [N][2 W] u32 = [N][W] u64, little-endian halves, or null (PILES)
+    float *tail;                  // [N][2] or null: outputs S, S + 1 (PILES) / 2, 3 (LOADS)
+    float *loads;                 // [N][2] (LOADS): outputs 0, 1
+    float clip;
+    int32_t n_inputs, n_layers, F, f_pad;
+    int32_t q_row0;               // first row of the Q image
+    int32_t hidden_act, squash, normalize, head;
+    int32_t S, A, W;              // piles, outputs of the head, u64 words per env
+};
+
+void launch_policy(const PolicyArgs &a, int waves, hipStream_t stream);
+// W [out][in] row-major and b [out] in device memory -> the layout above
+void launch_policy_relayout(const float *d_W, const float *d_b, float *d_w, float *d_bias, int out, int in, int k_pad, int tiles, hipStream_t stream);
+
+}  // namespace chub
+#endif

@@ -17,6 +17,7 @@
 #include "../../include/chub.h"
 #include "chub_device.h"
 #include "chub_plan.h"
+#include "chub_policy.h"
 
 namespace chub {
 template <bool RESET>
@@ -170,6 +171,8 @@ struct chub_env {
     // chub_set_step_terms: the caller's [N][C] f32 buffer every step call fills behind its kernels (run_call), and its field mask; null / 0: none
     float *st_out = nullptr;
     uint32_t st_fields = 0;
+    // the actors made for this handle (chub_policy_create): destroyed before it.  Everything they own lies outside the arena
+    std::vector<chub_policy *> policies;
     double *d_ep_sum = nullptr;  // k_episode_summary's partials [kEpSumMaxBlocks][kEpSumWords], then the host form's result [kEpSumWords]
     int public_mode = 0;     // the rng_mode the handle was created with: CHUB_RNG_PHILOX_CURVES is hp.rng_mode = PHILOX + hp.soc_curves
     bool tape_only = false;  // ... and once there are any, the handle's class rows are the caller's: only tape resets / steps may admit cars
@@ -1040,8 +1043,11 @@ static int create_impl(const chub_config *cfg_in, const char *data_dir, int64_t 
     return CHUB_OK;
 }
 
+static void policy_free(chub_policy *pol);
+
 int chub_destroy(chub_env *e) {
     if (!e) return CHUB_OK;
+    while (!e->policies.empty()) policy_free(e->policies.back());  // (each takes itself off the list)
     if (!e->allocs.empty() || !e->prof_events.empty()) {  // a handle that never reached the device owns nothing there
         (void) hipSetDevice(e->device);
         (void) hipDeviceSynchronize();
@@ -3416,5 +3422,358 @@ int chub_get_env_params(chub_env *e, chub_env_params *rows) {
 }
 
 int chub_has_env_params(const chub_env *e) { return e ? (e->env_params ? 1 : 0) : CHUB_ERR_ARG; }
+
+// ---- an actor on the device (include/chub.h): an MLP from the feature row to the action row / pile bits, and the closed loop issued from C.
+// The kernel and the device weight layout are chub_policy.hip / chub_policy.h; here: validation, ownership, and the calls' order.
+static_assert((int) CHUB_PIN_COUNT == PIN_COUNT && (int) CHUB_PIN_FORECAST == PIN_FORECAST && (int) CHUB_PACT_COUNT == PACT_COUNT &&
+                  (int) CHUB_PACT_RELU == PACT_RELU && (int) CHUB_PHEAD_COUNT == PHEAD_COUNT && (int) CHUB_PHEAD_LOADS == PHEAD_LOADS &&
+                  (int) CHUB_PSQ_COUNT == PSQ_COUNT && (int) CHUB_PSQ_CLIP == PSQ_CLIP && (int) CHUB_PRUN_COUNT == PRUN_COUNT &&
+                  (int) CHUB_PRUN_AUTORESET == PRUN_AUTORESET,
+              "chub_policy.h restates the CHUB_PIN_* / PACT / PHEAD / PSQ / PRUN enums");
+}  // extern "C"
+
+struct chub_policy {
+    chub_env *env;
+    chub_policy_spec spec;
+    int32_t F, A_out, waves;
+    int32_t in_dim[kPolicyMaxLayers];       // inputs of layer l
+    PolicyArgs pa;                          // everything that does not change from call to call
+    float *d_w[kPolicyMaxLayers], *d_b[kPolicyMaxLayers];  // the layers in the kernel's layout (never move)
+    float *d_norm;                          // mean [F] | inv_std [F]
+    float *d_stage;                         // the host form of set_weights: W | b of the largest layer, in the trainer's layout
+    float *d_scratch[kPolicyMaxInputs];     // [N][width] of every non-OBS block
+    float *d_loads, *d_tail;                // [N][2] each: the LOADS head's outputs; the run loop's tail pair
+    uint64_t *d_bits;                       // [N][W]: the run loop's pile bits
+    float *d_rows;                          // [N][S + 2]: the run loop's action rows (CHUB_PRUN_AUTORESET)
+    std::vector<void *> allocs;
+};
+
+extern "C" {
+
+// what a spec comes to on a hub of this shape: the feature row's blocks, F, the head's output count and the LDS rows the kernel needs
+struct PolicyShape {
+    int32_t width[kPolicyMaxInputs];
+    int32_t F, A_out, p_rows, q_rows;
+};
+
+static int policy_shape(const int32_t piles[2], const chub_policy_spec *sp, PolicyShape &ps) {
+    if (piles[0] < 0 || piles[1] < 0 || piles[0] + piles[1] <= 0 || piles[0] > 4096 || piles[1] > 4096)
+        return fail(CHUB_ERR_ARG, "station_list: 0 .. 4096 piles per station, at least one pile");
+    const int S = piles[0] + piles[1], D = 2 + 4 * ((piles[0] > 0) + (piles[1] > 0)) + 3;
+    if (sp->n_inputs < 1 || sp->n_inputs > kPolicyMaxInputs) return fail(CHUB_ERR_ARG, "n_inputs: 1 .. 4");
+    if (sp->n_layers < 1 || sp->n_layers > kPolicyMaxLayers) return fail(CHUB_ERR_ARG, "n_layers: 1 .. 4");
+    int64_t F = 0;
+    for (int i = 0; i < sp->n_inputs; i++) {
+        const chub_policy_input &in = sp->inputs[i];
+        int w;
+        switch (in.kind) {
+        case CHUB_PIN_OBS: w = D; break;
+        case CHUB_PIN_PILE_OBS:
+            if ((w = chub_pile_obs_columns((uint32_t) in.fields)) < 0) return CHUB_ERR_ARG;  // (that call's message)
+            w *= S;
+            break;
+        case CHUB_PIN_STATION_PROFILE:
+            if ((w = chub_station_profile_size((uint32_t) in.fields, in.param)) < 0) return CHUB_ERR_ARG;
+            break;
+        case CHUB_PIN_FORECAST:
+            if ((w = chub_forecast_size((uint32_t) in.fields, in.param)) < 0) return CHUB_ERR_ARG;
+            break;
+        default: return fail(CHUB_ERR_ARG, "inputs[" + std::to_string(i) + "].kind: one of the CHUB_PIN_* kinds");
+        }
+        ps.width[i] = w;
+        F += w;
+    }
+    if (sp->hidden_act < 0 || sp->hidden_act >= CHUB_PACT_COUNT) return fail(CHUB_ERR_ARG, "hidden_act: CHUB_PACT_TANH or CHUB_PACT_RELU");
+    if (sp->head < 0 || sp->head >= CHUB_PHEAD_COUNT) return fail(CHUB_ERR_ARG, "head: CHUB_PHEAD_PILES or CHUB_PHEAD_LOADS");
+    if (sp->squash < 0 || sp->squash >= CHUB_PSQ_COUNT) return fail(CHUB_ERR_ARG, "squash: CHUB_PSQ_TANH or CHUB_PSQ_CLIP");
+    if (sp->normalize != 0 && sp->normalize != 1) return fail(CHUB_ERR_ARG, "normalize: 0 or 1");
+    const int A_out = sp->head == CHUB_PHEAD_PILES ? S + 2 : 4;
+    for (int l = 0; l + 1 < sp->n_layers; l++)
+        if (sp->width[l] < 1 || sp->width[l] > kPolicyMaxHidden)
+            return fail(CHUB_ERR_ARG, "width[" + std::to_string(l) + "]: hidden widths are 1 .. 256");
+    if (sp->width[sp->n_layers - 1] != A_out)
+        return fail(CHUB_ERR_ARG, "width[n_layers - 1] must be the head's output count, " + std::to_string(A_out));
+    if (sp->normalize && !(sp->clip > 0.0f)) return fail(CHUB_ERR_ARG, "clip must be > 0 with normalize");
+    // the two LDS images: P the feature row and the outputs of the odd layers, Q the outputs of the even layers (hidden layers only)
+    int64_t p_rows = (F + 1) & ~(int64_t) 1, q_rows = 0;
+    for (int l = 0; l + 1 < sp->n_layers; l++) {
+        const int64_t rows = (int64_t) ((sp->width[l] + kPolicyOutTile - 1) / kPolicyOutTile) * kPolicyOutTile;
+        if (l & 1) p_rows = rows > p_rows ? rows : p_rows;
+        else q_rows = rows > q_rows ? rows : q_rows;
+    }
+    if (p_rows + q_rows > kPolicyLdsRows)
+        return fail(CHUB_ERR_UNSUPPORTED, "a feature row of " + std::to_string(F) + " floats and these hidden widths need " + std::to_string(p_rows + q_rows) +
+                                              " rows of LDS: at most " + std::to_string(kPolicyLdsRows) + " (F <= 256 always fits)");
+    ps.F = (int32_t) F;
+    ps.A_out = A_out;
+    ps.p_rows = (int32_t) p_rows;
+    ps.q_rows = (int32_t) q_rows;
+    return CHUB_OK;
+}
+
+int chub_policy_input_width(const chub_config *cfg, const chub_policy_spec *spec, int32_t *F_out, int32_t *A_out) {
+    if (!cfg || !spec || !F_out || !A_out) return fail(CHUB_ERR_ARG, "null argument");
+    PolicyShape ps;
+    if (const int rc = policy_shape(cfg->station_list, spec, ps)) return rc;
+    *F_out = ps.F;
+    *A_out = ps.A_out;
+    return CHUB_OK;
+}
+
+static void policy_free(chub_policy *pol) {
+    chub_env *e = pol->env;
+    (void) hipSetDevice(e->device);
+    (void) hipDeviceSynchronize();  // (a launch still in flight reads the weights and the scratch)
+    for (void *p : pol->allocs) (void) hipFree(p);
+    e->policies.erase(std::remove(e->policies.begin(), e->policies.end(), pol), e->policies.end());
+    delete pol;
+}
+
+static int policy_alloc_bytes(chub_policy *pol, void **p, size_t bytes) {
+    void *d = nullptr;
+    if (!bytes) bytes = 4;
+    if (hipMalloc(&d, bytes) != hipSuccess) return fail(CHUB_ERR_HIP, "chub_policy: out of device memory");
+    pol->allocs.push_back(d);
+    if (hipMemset(d, 0, bytes) != hipSuccess) return fail(CHUB_ERR_HIP, "chub_policy: hipMemset failed");
+    *p = d;
+    return CHUB_OK;
+}
+#define policy_alloc(pol, p, count) policy_alloc_bytes((pol), (void **) (p), (size_t) (count) * sizeof(**(p)))
+
+static int policy_upload(chub_policy *pol, int l, const float *W, const float *b) {
+    const size_t nw = (size_t) pol->spec.width[l] * (size_t) pol->in_dim[l], nb = (size_t) pol->spec.width[l];
+    HIP_TRY(hipDeviceSynchronize());  // (the staging buffer is one; nothing may still be reading the layer either)
+    HIP_TRY(hipMemcpy(pol->d_stage, W, nw * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(pol->d_stage + nw, b, nb * sizeof(float), hipMemcpyHostToDevice));
+    launch_policy_relayout(pol->d_stage, pol->d_stage + nw, pol->d_w[l], pol->d_b[l], pol->spec.width[l], pol->in_dim[l], pol->pa.layer[l].k_pad,
+                           pol->pa.layer[l].tiles, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    return CHUB_OK;
+}
+
+int chub_policy_create(chub_env *e, const chub_policy_spec *spec, const float *const *W, const float *const *b, const float *mean,
+                       const float *inv_std, chub_policy **out) {
+    if (!e || !spec || !W || !b || !out) return fail(CHUB_ERR_ARG, "null argument");
+    *out = nullptr;
+    PolicyShape ps;
+    if (const int rc = policy_shape(e->hp.S, spec, ps)) return rc;
+    for (int l = 0; l < spec->n_layers; l++)
+        if (!W[l] || !b[l]) return fail(CHUB_ERR_ARG, "null argument");
+    if (spec->normalize && (!mean || !inv_std)) return fail(CHUB_ERR_ARG, "normalize needs mean and inv_std");
+    if (e->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_create between chub_graph_begin and chub_graph_end (it allocates and synchronises)");
+    bool feature_block = false;
+    for (int i = 0; i < spec->n_inputs; i++) feature_block |= spec->inputs[i].kind != CHUB_PIN_OBS;
+    if (e->tape_only && (feature_block || spec->head == CHUB_PHEAD_LOADS))
+        return fail(CHUB_ERR_UNSUPPORTED, "a policy that reads feature blocks or sets station loads is not supported on a tape handle "
+                                          "(chub_tape_register_soc rewrites the class tables)");
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+
+    chub_policy *pol = new chub_policy();
+    pol->env = e;
+    pol->spec = *spec;
+    pol->F = ps.F;
+    pol->A_out = ps.A_out;
+    e->policies.push_back(pol);
+    const size_t N = (size_t) e->hp.n_envs;
+    const int S = e->hp.S[0] + e->hp.S[1], Wd = (S + 63) / 64;
+    PolicyArgs &pa = pol->pa;
+    memset(&pa, 0, sizeof pa);
+    pa.n_envs = e->hp.n_envs;
+    pa.n_inputs = spec->n_inputs;
+    pa.n_layers = spec->n_layers;
+    pa.F = ps.F;
+    pa.f_pad = (ps.F + 1) & ~1;
+    pa.q_row0 = ps.p_rows;
+    pa.hidden_act = spec->hidden_act;
+    pa.squash = spec->squash;
+    pa.normalize = spec->normalize;
+    pa.head = spec->head;
+    pa.clip = spec->clip;
+    pa.S = S;
+    pa.A = S + 2;
+    pa.W = Wd;
+    int rc = CHUB_OK, max_tiles = 1;
+    size_t stage = 0;
+    for (int l = 0; l < spec->n_layers && !rc; l++) {
+        const int in = l ? spec->width[l - 1] : ps.F, width = spec->width[l];
+        int tiles = (width + kPolicyOutTile - 1) / kPolicyOutTile;
+        // the head's tiles cover every bit word in full: bits from S up are written as zeros, not left alone
+        if (l == spec->n_layers - 1 && spec->head == CHUB_PHEAD_PILES && tiles < 2 * Wd) tiles = 2 * Wd;
+        pol->in_dim[l] = in;
+        pa.layer[l].k_pad = (in + 1) & ~1;
+        pa.layer[l].tiles = tiles;
+        max_tiles = tiles > max_tiles ? tiles : max_tiles;
+        stage = std::max(stage, (size_t) width * (size_t) in + (size_t) width);
+        rc = policy_alloc(pol, &pol->d_w[l], (size_t) tiles * (size_t) pa.layer[l].k_pad * kPolicyOutTile);
+        if (!rc) rc = policy_alloc(pol, &pol->d_b[l], (size_t) tiles * kPolicyOutTile);
+        pa.layer[l].w = pol->d_w[l];
+        pa.layer[l].b = pol->d_b[l];
+    }
+    pol->waves = max_tiles < kPolicyMaxWaves ? max_tiles : kPolicyMaxWaves;
+    if (!rc) rc = policy_alloc(pol, &pol->d_stage, stage);
+    if (!rc) rc = policy_alloc(pol, &pol->d_norm, 2 * (size_t) ps.F);
+    for (int i = 0; i < spec->n_inputs && !rc; i++) {
+        pa.in[i].width = ps.width[i];
+        pa.in[i].ld = ps.width[i];
+        if (spec->inputs[i].kind != CHUB_PIN_OBS) {
+            rc = policy_alloc(pol, &pol->d_scratch[i], N * (size_t) ps.width[i]);
+            pa.in[i].p = pol->d_scratch[i];
+        }
+    }
+    if (!rc) rc = policy_alloc(pol, &pol->d_loads, 2 * N);
+    if (!rc) rc = policy_alloc(pol, &pol->d_tail, 2 * N);
+    if (!rc) rc = policy_alloc(pol, &pol->d_bits, N * (size_t) Wd);
+    if (!rc) rc = policy_alloc(pol, &pol->d_rows, N * (size_t) (S + 2));
+    if (!rc && spec->normalize) {
+        pa.mean = pol->d_norm;
+        pa.inv_std = pol->d_norm + ps.F;
+        if (hipMemcpy(pol->d_norm, mean, (size_t) ps.F * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(pol->d_norm + ps.F, inv_std, (size_t) ps.F * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+            rc = fail(CHUB_ERR_HIP, "chub_policy_create: mean / inv_std could not be copied to the device");
+    }
+    pa.loads = pol->d_loads;
+    for (int l = 0; l < spec->n_layers && !rc; l++) rc = policy_upload(pol, l, W[l], b[l]);
+    if (rc) {
+        const std::string msg = g_err;
+        policy_free(pol);
+        return fail(rc, msg);
+    }
+    *out = pol;
+    return CHUB_OK;
+}
+
+int chub_policy_destroy(chub_policy *pol) {
+    if (!pol) return CHUB_OK;
+    if (pol->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_destroy between chub_graph_begin and chub_graph_end (it synchronises and frees)");
+    policy_free(pol);
+    (void) hipGetLastError();
+    return CHUB_OK;
+}
+
+int chub_policy_set_weights(chub_policy *pol, int32_t layer, const float *W, const float *b) {
+    if (!pol || !W || !b) return fail(CHUB_ERR_ARG, "null argument");
+    if (layer < 0 || layer >= pol->spec.n_layers) return fail(CHUB_ERR_ARG, "layer: 0 .. n_layers - 1");
+    if (pol->env->capturing)
+        return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_set_weights between chub_graph_begin and chub_graph_end (it copies and synchronises: use "
+                                          "chub_policy_set_weights_device)");
+    HIP_TRY(hipSetDevice(pol->env->device));
+    (void) hipGetLastError();
+    return policy_upload(pol, layer, W, b);
+}
+
+int chub_policy_set_weights_device(chub_policy *pol, int32_t layer, const float *d_W, const float *d_b, void *stream) {
+    if (!pol || !d_W || !d_b) return fail(CHUB_ERR_ARG, "null argument");
+    if (layer < 0 || layer >= pol->spec.n_layers) return fail(CHUB_ERR_ARG, "layer: 0 .. n_layers - 1");
+    HIP_TRY(hipSetDevice(pol->env->device));
+    (void) hipGetLastError();
+    launch_policy_relayout(d_W, d_b, pol->d_w[layer], pol->d_b[layer], pol->spec.width[layer], pol->in_dim[layer], pol->pa.layer[layer].k_pad,
+                           pol->pa.layer[layer].tiles, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_policy_act_device(chub_env *e, chub_policy *pol, const float *d_obs, int64_t ld_obs, const uint8_t *d_mask, float *d_actions,
+                           uint64_t *d_pile_bits, float *d_tail, void *stream) {
+    if (!e || !pol) return fail(CHUB_ERR_ARG, "null argument");
+    if (pol->env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
+    const chub_policy_spec &sp = pol->spec;
+    bool obs_block = false, feature_block = false;
+    for (int i = 0; i < sp.n_inputs; i++) (sp.inputs[i].kind == CHUB_PIN_OBS ? obs_block : feature_block) = true;
+    if (obs_block && !d_obs) return fail(CHUB_ERR_ARG, "null argument");
+    if (obs_block && ld_obs < e->hp.obs_dim) return fail(CHUB_ERR_ARG, "ld_obs: at least the observation's " + std::to_string(e->hp.obs_dim) + " floats");
+    if (!d_actions && !d_pile_bits) return fail(CHUB_ERR_ARG, "chub_policy_act: give d_actions, d_pile_bits or both");
+    if (sp.head == CHUB_PHEAD_PILES && d_pile_bits && !d_tail) return fail(CHUB_ERR_ARG, "chub_policy_act: pile bits need d_tail (the two tail actions)");
+    if (e->tape_only && (feature_block || sp.head == CHUB_PHEAD_LOADS))
+        return fail(CHUB_ERR_UNSUPPORTED, "a policy that reads feature blocks or sets station loads is not supported on a tape handle "
+                                          "(chub_tape_register_soc rewrites the class tables)");
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    PolicyArgs pa = pol->pa;
+    for (int i = 0; i < sp.n_inputs; i++) {
+        const chub_policy_input &in = sp.inputs[i];
+        int rc = CHUB_OK;
+        switch (in.kind) {
+        case CHUB_PIN_OBS:
+            pa.in[i].p = d_obs;
+            pa.in[i].ld = ld_obs;
+            break;
+        case CHUB_PIN_PILE_OBS: rc = chub_pile_obs_device(e, (uint32_t) in.fields, d_mask, pol->d_scratch[i], stream); break;
+        case CHUB_PIN_STATION_PROFILE: rc = chub_station_profile_device(e, (uint32_t) in.fields, in.param, d_mask, pol->d_scratch[i], stream); break;
+        default: rc = chub_forecast_device(e, (uint32_t) in.fields, in.param, d_mask, pol->d_scratch[i], stream); break;
+        }
+        if (rc) return rc;
+    }
+    const bool loads = sp.head == CHUB_PHEAD_LOADS;
+    pa.mask = d_mask;
+    pa.actions = loads ? nullptr : d_actions;
+    pa.bits = loads ? nullptr : (uint32_t *) d_pile_bits;
+    pa.tail = d_tail ? d_tail : (loads ? pol->d_tail : nullptr);
+    launch_policy(pa, pol->waves, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    if (loads) return chub_load_dispatch_device(e, CHUB_LOAD_FRACTION, pol->d_loads, pa.tail, d_mask, d_actions, d_pile_bits, stream);
+    return CHUB_OK;
+}
+
+int chub_policy_act(chub_env *e, chub_policy *pol, const float *obs, float *actions) {
+    if (!e || !pol || !actions) return fail(CHUB_ERR_ARG, "null argument");
+    if (pol->env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
+    if (e->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_act between chub_graph_begin and chub_graph_end (it allocates and synchronises)");
+    bool obs_block = false;
+    for (int i = 0; i < pol->spec.n_inputs; i++) obs_block |= pol->spec.inputs[i].kind == CHUB_PIN_OBS;
+    if (obs_block && !obs) return fail(CHUB_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t N = (size_t) e->hp.n_envs, D = (size_t) e->hp.obs_dim, A = (size_t) e->hp.act_dim;
+    const size_t b_obs = N * D * sizeof(float), b_act = N * A * sizeof(float);
+    char *d = nullptr;  // obs | rows, one allocation
+    HIP_TRY(hipMalloc((void **) &d, b_obs + b_act));
+    float *d_obs = (float *) d, *d_act = (float *) (d + b_obs);
+    int rc = CHUB_OK;
+    if (obs_block && hipMemcpy(d_obs, obs, b_obs, hipMemcpyHostToDevice) != hipSuccess)
+        rc = fail(CHUB_ERR_HIP, "chub_policy_act: the observations could not be copied to the device");
+    if (!rc) rc = chub_policy_act_device(e, pol, d_obs, (int64_t) D, nullptr, d_act, nullptr, pol->d_tail, nullptr);
+    if (!rc && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(actions, d_act, b_act, hipMemcpyDeviceToHost) != hipSuccess))
+        rc = fail(CHUB_ERR_HIP, "chub_policy_act: the launch failed or its output could not be copied back");
+    (void) hipFree(d);
+    return rc;
+}
+
+// The closed loop: what a host loop of chub_reset_device / chub_policy_act_device / chub_step_bits_device_packed (or
+// chub_autoreset_step_device) calls does, with nothing on the host between the steps
+int chub_policy_run_steps(chub_env *e, chub_policy *pol, int mode, float *const *d_packed2, float *d_reset_obs, float *d_final_obs,
+                          int64_t first_step, int64_t n_steps, void *stream) {
+    if (!e || !pol || !d_packed2 || !d_packed2[0] || !d_packed2[1] || first_step < 0 || n_steps < 0) return fail(CHUB_ERR_ARG, "bad argument");
+    if (pol->env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
+    if (mode != CHUB_PRUN_LOCKSTEP && mode != CHUB_PRUN_AUTORESET) return fail(CHUB_ERR_ARG, "mode: CHUB_PRUN_LOCKSTEP or CHUB_PRUN_AUTORESET");
+    if (mode == CHUB_PRUN_LOCKSTEP && !d_reset_obs) return fail(CHUB_ERR_ARG, "bad argument");
+    if (e->hp.rng_mode == CHUB_RNG_COMPAT)
+        return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_run_steps runs the Philox modes: COMPAT steps take the caller's normals one by one");
+    if (mode == CHUB_PRUN_AUTORESET && e->tick == 0) return fail(CHUB_ERR_ARG, "step() before reset()");
+    const int D = e->hp.obs_dim;
+    for (int64_t i = first_step; i < first_step + n_steps; i++) {
+        int rc;
+        const float *obs = d_packed2[(i - 1) & 1];
+        int64_t ld = D + 2;
+        if (mode == CHUB_PRUN_LOCKSTEP) {
+            if (i % 96 == 0) {
+                if ((rc = chub_reset_device(e, nullptr, nullptr, d_reset_obs, stream))) return rc;
+                obs = d_reset_obs;
+                ld = D;
+            }
+            if ((rc = chub_policy_act_device(e, pol, obs, ld, nullptr, nullptr, pol->d_bits, pol->d_tail, stream))) return rc;
+            if ((rc = chub_step_bits_device_packed(e, pol->d_bits, pol->d_tail, nullptr, d_packed2[i & 1], stream))) return rc;
+        } else {
+            if (i == first_step && d_reset_obs) {
+                obs = d_reset_obs;
+                ld = D;
+            }
+            if ((rc = chub_policy_act_device(e, pol, obs, ld, nullptr, pol->d_rows, nullptr, nullptr, stream))) return rc;
+            if ((rc = chub_autoreset_step_device(e, pol->d_rows, nullptr, nullptr, nullptr, d_packed2[i & 1], d_final_obs, stream))) return rc;
+        }
+    }
+    return CHUB_OK;
+}
 
 }  // extern "C"

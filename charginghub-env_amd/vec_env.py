@@ -104,6 +104,98 @@ def summary_dict(raw):
     return out
 
 
+class DevicePolicy(object):
+    """An MLP actor on the device (chub_policy_*, include/chub.h "an actor on the device"): made by VecChargingHub.make_policy.  The
+    feature row (the observation and / or the feature calls' blocks) goes through the dense layers in ONE launch and comes out as action
+    rows or pile bits + tail, which every step form takes; run_steps is the closed loop issued from C.  Exact f32: every product rounded
+    once, f32 accumulation (an fmaf chain), the trainer's network up to summation order."""
+
+    def __init__(self, env, layers, inputs=("obs",), head="piles", hidden_act="tanh", squash="tanh", normalize=None):
+        self._env = env
+        self._lib = env._lib
+        layers = [(np.ascontiguousarray(W, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32).ravel()) for W, b in layers]
+        mean = inv_std = None
+        clip = 0.0
+        if normalize is not None:
+            mean, inv_std, clip = normalize
+            mean = np.ascontiguousarray(mean, dtype=np.float32).ravel()
+            inv_std = np.ascontiguousarray(inv_std, dtype=np.float32).ravel()
+        self.spec = _lib.policy_spec([W.shape[0] if W.ndim == 2 else -1 for W, _ in layers], inputs, head, hidden_act, squash,
+                                     normalize is not None, clip)
+        F, A = C.c_int32(), C.c_int32()
+        check(self._lib.chub_policy_input_width(C.byref(env.cfg), C.byref(self.spec), C.byref(F), C.byref(A)))
+        self.n_features, self.n_outputs = F.value, A.value
+        fan_in = self.n_features
+        for l, (W, b) in enumerate(layers):  # (the library sees pointers only: the shapes are checked here)
+            if W.shape != (self.spec.width[l], fan_in) or b.shape != (W.shape[0],):
+                raise ValueError("layer %d: W must have shape (%d, %d) and b (%d,), got %s and %s"
+                                 % (l, self.spec.width[l], fan_in, self.spec.width[l], W.shape, b.shape))
+            fan_in = W.shape[0]
+        if normalize is not None and (mean.shape != (self.n_features,) or inv_std.shape != (self.n_features,)):
+            raise ValueError("normalize: mean and inv_std must have %d entries (the feature row)" % self.n_features)
+        self.layer_shapes = [W.shape for W, _ in layers]
+        n = len(layers)
+        Wp = (C.c_void_p * n)(*[W.ctypes.data for W, _ in layers])
+        bp = (C.c_void_p * n)(*[b.ctypes.data for _, b in layers])
+        h = C.c_void_p()
+        check(self._lib.chub_policy_create(env._h, C.byref(self.spec), Wp, bp, _ptr(mean), _ptr(inv_std), C.byref(h)))
+        self._p = h
+
+    def act_device(self, d_obs=0, ld_obs=None, d_actions=0, d_pile_bits=0, d_tail=0, d_mask=0, stream=0):
+        """one evaluation on `stream`: d_obs [N] rows of obs_dim floats with row stride ld_obs floats (default obs_dim; a packed
+        [N, D + 2] block: D + 2) -> d_actions [N, A] f32 and / or d_pile_bits [N, bit_words] u64 with d_tail [N, 2] f32.  d_mask [N] u8 in
+        device memory: only the rows of the envs it names are written.  No synchronisation, nothing of the simulation changes,
+        recordable into a graph."""
+        ld = self._env.obs_dim if ld_obs is None else int(ld_obs)
+        check(self._lib.chub_policy_act_device(self._env._h, self._p, d_obs or None, ld, d_mask or None, d_actions or None, d_pile_bits or None,
+                                               d_tail or None, stream or None))
+
+    def act(self, obs=None):
+        """act_device through host memory: obs [N, D] -> float32 action rows [N, A] (the convenience form: it allocates, synchronises and
+        copies)"""
+        e = self._env
+        o = None if obs is None else np.ascontiguousarray(obs, dtype=np.float32)
+        if o is not None and o.shape != (e.n_envs, e.obs_dim):
+            raise AssertionError("obs must have shape (%d, %d)" % (e.n_envs, e.obs_dim))
+        actions = np.zeros((e.n_envs, e.act_dim), dtype=np.float32)
+        check(self._lib.chub_sync(e._h))  # (calls in flight on any stream write the state the feature blocks read)
+        check(self._lib.chub_policy_act(e._h, self._p, _ptr(o), _ptr(actions)))
+        return actions
+
+    def set_weights(self, layer, W, b):
+        """new weights of one layer from host arrays, W [out, in] (the nn.Linear layout) and b [out]; synchronises"""
+        W = np.ascontiguousarray(W, dtype=np.float32)
+        b = np.ascontiguousarray(b, dtype=np.float32).ravel()
+        if not 0 <= int(layer) < len(self.layer_shapes) or W.shape != self.layer_shapes[layer] or b.shape != (W.shape[0],):
+            raise ValueError("set_weights: layer %r takes W %s and b (%d,)" % (layer, self.layer_shapes[layer] if 0 <= int(layer) < len(self.layer_shapes) else "?", W.shape[0]))
+        check(self._lib.chub_policy_set_weights(self._p, int(layer), _ptr(W), _ptr(b)))
+
+    def set_weights_device(self, layer, d_W, d_b, stream=0):
+        """the same from device memory in the trainer's layout (e.g. a parameter's data_ptr()), as one re-layout launch on `stream`: a
+        captured graph's next replay evaluates the new weights"""
+        check(self._lib.chub_policy_set_weights_device(self._p, int(layer), d_W, d_b, stream or None))
+
+    def run_steps(self, d_packed2, n_steps, first_step=0, mode="lockstep", d_reset_obs=0, d_final_obs=0, stream=0):
+        """the closed loop issued from C (chub_policy_run_steps): d_packed2 = the addresses of two [N, D + 2] f32 blocks, step i writes block
+        i & 1.  mode "lockstep": a reset into d_reset_obs [N, D] before every step whose index is a multiple of 96, bits-form steps;
+        "autoreset": chub_autoreset_step_device per step, the first one acting on d_reset_obs (the observation the caller holds) if given.
+        Returns after enqueueing."""
+        blocks = (C.c_void_p * 2)(int(d_packed2[0]), int(d_packed2[1]))
+        check(self._lib.chub_policy_run_steps(self._env._h, self._p, _lib._enum_value(_lib.PRUN, mode, "run mode"), blocks, d_reset_obs or None,
+                                              d_final_obs or None, int(first_step), int(n_steps), stream or None))
+
+    def close(self):
+        if getattr(self, "_p", None) and getattr(self._env, "_h", None):
+            check(self._lib.chub_policy_destroy(self._p))
+        self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class VecChargingHub(object):
     def __init__(self, n_envs, station_list, station_type_list, seed=0, rng="philox", device=0, env_id0=0,
                  data_dir=None, slot_kernel="auto", no_arena=False, copy_outputs=True, fused_step="auto", tile="auto", walk_ahead="auto",
@@ -616,6 +708,15 @@ class VecChargingHub(object):
         check(self._lib.chub_load_dispatch(self._h, u, _ptr(ld), _ptr(t), _ptr(actions), _ptr(bits)))
         return actions, bits
 
+    # ---- an actor on the device (chub_policy_*): closed-loop rollouts with no host between the steps
+    def make_policy(self, layers, inputs=("obs",), head="piles", hidden_act="tanh", squash="tanh", normalize=None):
+        """an MLP actor bound to this handle -> DevicePolicy.  layers: [(W, b), ...] with W [out, in] (the nn.Linear layout), 1 .. 4 of them,
+        hidden widths 1 .. 256, the last one the head's: "piles" act_dim outputs (an action row), "loads" 4 (load0, load1, tail0, tail1;
+        the loads go through load_dispatch as fractions).  inputs: the blocks of the feature row in order -- "obs", or (kind, fields[,
+        param]) with kind "pile_obs" / "station_profile" / "forecast" and fields / param as those calls take them.  normalize: None or
+        (mean [F], inv_std [F], clip)."""
+        return DevicePolicy(self, layers, inputs, head, hidden_act, squash, normalize)
+
     def step_load_device(self, d_actions, d_obs, d_reward, d_done, d_exo_z=0, stream=0):
         """the device-pointer form of step_load (chub_step_load_device): d_actions [N, A] f32 in load_actions' layout"""
         check(self._lib.chub_step_load_device(self._h, d_actions, d_exo_z or None, d_obs, d_reward, d_done, stream or None))
@@ -782,4 +883,4 @@ class VecChargingHub(object):
             pass
 
 
-__all__ = ["VecChargingHub", "make_config", "ChubError", "split_env_params", "slice_env_kwargs"]
+__all__ = ["VecChargingHub", "DevicePolicy", "make_config", "ChubError", "split_env_params", "slice_env_kwargs"]

@@ -499,6 +499,89 @@ class TorchHubVecEnv(object):
         self.vec.step_bits_device_packed(pile_bits.data_ptr(), tail.data_ptr(), self._packed.data_ptr(), stream=self._stream())
         return self._after_step()
 
+    # ---- an actor on the device (chub_policy_*): the trained network evaluated by the hub itself, closed-loop rollouts issued from C
+    def load_policy(self, module_or_layers, inputs=("obs",), head=None, squash=None, normalize=None):
+        """A feed-forward actor -> DevicePolicy (VecChargingHub.make_policy).  module_or_layers: an ``nn.Sequential`` of ``Linear`` /
+        ``Tanh`` / ``ReLU`` (the activation between the Linears is the hidden one and must be the same throughout; a Tanh behind the last
+        Linear is the squash), or a list of ``(W, b)`` tensors / arrays in the nn.Linear layout.  head: "piles" or "loads" (default: what
+        ``control`` says); squash: "tanh" or "clip" (default: "tanh").  The weights are copied; after an optimiser step
+        ``policy.set_weights_device(l, linear.weight.data_ptr(), linear.bias.data_ptr(), stream)`` brings layer l up to date on the
+        device."""
+        torch = self.torch
+        hidden = None
+        if isinstance(module_or_layers, torch.nn.Module):
+            layers, acts = [], []
+            for m in module_or_layers.children():
+                if isinstance(m, torch.nn.Linear):
+                    if m.bias is None:
+                        raise ValueError("load_policy: every Linear needs a bias")
+                    layers.append((m.weight.detach().to("cpu", torch.float32).numpy(), m.bias.detach().to("cpu", torch.float32).numpy()))
+                    acts.append(None)
+                elif isinstance(m, (torch.nn.Tanh, torch.nn.ReLU)) and layers and acts[-1] is None:
+                    acts[-1] = "tanh" if isinstance(m, torch.nn.Tanh) else "relu"
+                else:
+                    raise ValueError("load_policy: an nn.Sequential of Linear / Tanh / ReLU, not %s here" % type(m).__name__)
+            if not layers:
+                raise ValueError("load_policy: no Linear layer")
+            if len(set(acts[:-1])) > 1 or None in acts[:-1]:
+                raise ValueError("load_policy: one activation, Tanh or ReLU, behind every hidden Linear")
+            hidden = acts[0] if len(acts) > 1 else None
+            if acts[-1] == "relu" or (acts[-1] == "tanh" and squash not in (None, "tanh")):
+                raise ValueError("load_policy: behind the last Linear only a Tanh (the squash) may follow")
+            squash = "tanh" if acts[-1] == "tanh" else squash
+        else:
+            layers = [(W.detach().to("cpu", torch.float32).numpy() if hasattr(W, "detach") else W,
+                       b.detach().to("cpu", torch.float32).numpy() if hasattr(b, "detach") else b) for W, b in module_or_layers]
+        if head is None:
+            head = "loads" if self.control == "station" else "piles"
+        return self.vec.make_policy(layers, inputs=inputs, head=head, hidden_act=hidden or "tanh", squash=squash or "tanh", normalize=normalize)
+
+    def rollout(self, policy, n_steps):
+        """n_steps closed-loop steps of `policy` from the current observation, issued from C on torch's current stream with nothing on the
+        host between them (chub_policy_run_steps), in the adapter's auto-reset mode: ``autoreset="per_env"`` every step is the auto-reset
+        step and ``last_obs`` keeps the terminal rows; ``autoreset=True`` the batch is reset where ``step`` would reset it, after the 96th
+        step of its day (``last_obs`` is set only for a day that ends with the rollout).  Returns (obs, reward, done, {}) of the LAST step as
+        views of its packed block, as ``step`` does."""
+        if not self.autoreset:
+            raise RuntimeError("rollout needs an auto-reset mode: construct with autoreset=True or 'per_env'")
+        if self._cur_obs is None:
+            raise RuntimeError("rollout() before reset()")
+        n_steps = int(n_steps)
+        if n_steps <= 0:
+            raise ValueError("n_steps must be positive")
+        if getattr(self, "_packed_alt", None) is None:
+            self._packed_alt = self.torch.empty_like(self._packed)
+        first = 0 if self.per_env else self._t
+        blocks = [None, None]  # step i writes block i & 1 and reads block (i - 1) & 1: the block that holds the current observation
+        blocks[(first - 1) & 1], blocks[first & 1] = self._packed, self._packed_alt
+        fresh = self._cur_obs is self._obs0  # the current observation is a reset's dense [N, D] block, not a packed one
+        if self.per_env:
+            policy.run_steps([b.data_ptr() for b in blocks], n_steps, first_step=first, mode="autoreset", d_reset_obs=self._obs0.data_ptr() if fresh else 0,
+                             d_final_obs=self.last_obs.data_ptr(), stream=self._stream())
+        else:
+            start, count = first, n_steps
+            if first % 96 == 0:  # the adapter has just reset (the observation is in _obs0): the run must not begin with a reset of its own
+                if getattr(self, "_pol_bits", None) is None:
+                    self._pol_bits = self.torch.zeros((self.num_envs, self.vec.bit_words), dtype=self.torch.int64, device=self.device)
+                    self._pol_tail = self.torch.zeros((self.num_envs, 2), dtype=self.torch.float32, device=self.device)
+                policy.act_device(self._obs0.data_ptr(), self.obs_dim, d_pile_bits=self._pol_bits.data_ptr(), d_tail=self._pol_tail.data_ptr(),
+                                  stream=self._stream())
+                self.vec.step_bits_device_packed(self._pol_bits.data_ptr(), self._pol_tail.data_ptr(), blocks[first & 1].data_ptr(),
+                                                 stream=self._stream())
+                start, count = first + 1, n_steps - 1
+            if count:
+                policy.run_steps([b.data_ptr() for b in blocks], count, first_step=start, mode="lockstep", d_reset_obs=self._obs0.data_ptr(),
+                                 stream=self._stream())
+            self._t += n_steps - 1  # (_after_step counts the last one)
+        last = blocks[(first + n_steps - 1) & 1]
+        if last is not self._packed:
+            self._packed, self._packed_alt = last, self._packed
+        if self.per_env:
+            D = self.obs_dim
+            self._cur_obs = self._packed[:, :D]
+            return self._cur_obs, self._packed[:, D], self._packed[:, D + 1] > 0.5, {}
+        return self._after_step()
+
     def copy_envs(self, src_idx, dst_idx, source=None):
         """env dst_idx[i] becomes a clone of env src_idx[i] of `source` (another TorchHubVecEnv; default: this one), on torch's current
         stream and without a host read: the indices are int64 CUDA tensors as torch.topk returns them (chub_copy_envs_device: distinct

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Three ways to drive the hub, smallest first (run from the repo root on a machine with an MI355X):
+"""Four ways to drive the hub, smallest first (run from the repo root on a machine with an MI355X):
 
     python examples/quickstart.py
 
 1. the drop-in single env (the reference's class and call pattern, test/env_test.py);
 2. the batched host-pointer API (numpy in / numpy out);
-3. the device-resident API (torch CUDA tensors in / out, no host copies) -- what an on-device learner should use.
+3. the device-resident API (torch CUDA tensors in / out, no host copies) -- what an on-device learner should use;
+4. a closed-loop day with an actor evaluated by the hub itself (numpy and ctypes only: no torch, no host between the steps).
 """
 import os
 import sys
@@ -122,7 +123,31 @@ def device_resident(n=65536):
     env.close()
 
 
+def closed_loop(n=4096):
+    import charginghub_env_amd as chub
+    from charginghub_env_amd import multi_gpu
+
+    hub = chub.VecChargingHub(n, seed=0, **HUB)
+    D, A = hub.obs_dim, hub.act_dim
+    rs = np.random.RandomState(0)
+    sizes = [D, 64, 64, A]                                   # a small random actor; a trained one hands over its nn.Linear weights
+    layers = [((rs.normal(size=(o, i)) / np.sqrt(i)).astype(np.float32), np.zeros(o, dtype=np.float32)) for i, o in zip(sizes[:-1], sizes[1:])]
+    policy = hub.make_policy(layers)                         # exact f32 on the matrix cores: the trainer's network up to summation order
+    packed = [multi_gpu.DeviceBuffer(n * (D + 2) * 4) for _ in range(2)]
+    reset_obs = multi_gpu.DeviceBuffer(n * D * 4)
+    t0 = time.perf_counter()
+    policy.run_steps([b.ptr for b in packed], 96, d_reset_obs=reset_obs.ptr)   # reset + 96 x (actor, step), issued from C
+    hub.sync()
+    dt = time.perf_counter() - t0
+    last = packed[95 & 1].to_host(np.float32, (n, D + 2))    # obs, reward, done of the day's last step
+    print("4. %d envs, a 13-64-64-47 actor on the device, one closed-loop day: %.1f M env-steps/s, mean reward %.4f, all done: %s"
+          % (n, n * 96 / dt / 1e6, last[:, D].mean(), bool((last[:, D + 1] > 0.5).all())))
+    policy.close()
+    hub.close()
+
+
 if __name__ == "__main__":
     single_env()
     batched_host()
     device_resident()
+    closed_loop()

@@ -738,6 +738,97 @@ int chub_load_dispatch_device(chub_env *env, int units, const float *d_loads /* 
                               uint64_t *d_pile_bits /* [N,W] or NULL */, void *stream);
 int chub_load_dispatch(chub_env *env, int units, const float *loads, const float *tail, float *actions, uint64_t *pile_bits);
 
+/* ---- an actor on the device: closed-loop rollouts with no host ------------------------------------------------------------------------
+ * Everything that surrounds a policy runs on the device (the step in every form, observations, profiles, forecasts, the dispatch); this
+ * section adds the policy itself, for the common case of a feed-forward actor: the env's feature row, through 1 .. 4 dense layers, to the
+ * action row or the pile bits the step already takes, as ONE launch on the caller's stream -- and chub_policy_run_steps, the closed loop
+ * issued from C, which a captured graph can hold.
+ *   Feature row: the spec's 1 .. 4 input blocks, concatenated in the order given into F floats per env:
+ *       CHUB_PIN_OBS             D floats: the env's observation row, supplied by the caller (d_obs) or by the run loop
+ *       CHUB_PIN_PILE_OBS        fields = a CHUB_PILE_* mask: C * S floats, chub_pile_obs_device's row of the env
+ *       CHUB_PIN_STATION_PROFILE fields = a CHUB_SP_* mask, param = buckets: chub_station_profile_size floats
+ *       CHUB_PIN_FORECAST        fields = a CHUB_FC_* mask, param = horizon: chub_forecast_size floats
+ *     With normalize = 1 every feature becomes x <- min(max((x - mean[f]) * inv_std[f], -clip), clip), the subtraction and the product each
+ *     rounded to f32 (no FMA).
+ *   Layers: h <- act(W[l] h + b[l]), W[l] [width[l]][inputs of layer l] row-major (the nn.Linear layout), hidden widths 1 .. 256, hidden_act
+ *     CHUB_PACT_TANH or CHUB_PACT_RELU on every layer but the last.  The last layer's width is fixed by the head, its outputs z are squashed to
+ *     a = tanhf(z) (CHUB_PSQ_TANH) or a = min(max(z, -1), 1) (CHUB_PSQ_CLIP):
+ *       CHUB_PHEAD_PILES  A = S + 2 outputs: an action row.  Outputs: d_actions [N, A] f32 and / or d_pile_bits [N, ceil(S / 64)] u64 with
+ *                         d_tail [N, 2] f32 -- chub_step_bits_device's layout, bits from S up zero.  Pile bit b is a[b] >= -2^-25 on the squashed
+ *                         f32 value: the step kernels' own predicate ((a + 1) / 2 >= 0.5 in f32), not the sign of z.  Stepping the bits and
+ *                         stepping the row therefore give the same state bit for bit.
+ *       CHUB_PHEAD_LOADS  4 outputs (load0, load1, tail0, tail1): the two loads go through chub_load_dispatch_device as CHUB_LOAD_FRACTION,
+ *                         which writes d_actions and / or d_pile_bits; d_tail (if given) receives the tail pair.
+ *   Numerics contract.  Every product is rounded once and accumulated in f32, as an fmaf chain (gfx950's v_mfma_f32_32x32x2_f32: f32 in, f32
+ *     accumulate); no wider and no narrower arithmetic is used.  The bias is the chain's initial value.  The order of a layer's terms is
+ *     unspecified but fixed: two calls on the same inputs give identical bits, whatever N, the mask or an env's place in the batch.  tanh is the
+ *     device library's tanhf.  So an evaluated policy is the trainer's f32 network up to summation order.
+ *   chub_policy_input_width: F and the head's output count for a hub shape and a spec, or the code and message chub_policy_create would give
+ *       for them.  It needs no device.
+ *   chub_policy_create: W[l] / b[l] host f32 as above (n_layers of each), mean / inv_std [F] host f32 (read when normalize = 1, else may be
+ *       NULL).  Everything is validated before any allocation.  The weights are copied to the device in the kernel's own layout; scratch for the
+ *       non-OBS blocks, the load / tail buffers and the run loop's action buffers are allocated here, all OUTSIDE the arena:
+ *       chub_state_size and snapshots are unchanged.  A policy is bound to its handle; chub_destroy destroys the handle's policies first.
+ *   chub_policy_set_weights: new W / b of one layer from host memory (it synchronises).  chub_policy_set_weights_device: the same from device
+ *       memory in the trainer's layout, as a re-layout launch on `stream` (no synchronisation; recordable).  The buffers the policy kernel reads
+ *       never move, so a captured graph's next replay evaluates the new weights.
+ *   chub_policy_act_device: d_obs [N] rows of at least D floats with row stride ld_obs floats (a packed [N, D + 2] block: ld_obs = D + 2; not
+ *       read, may be NULL, without a CHUB_PIN_OBS block).  The call enqueues the feature launches of the spec's non-OBS blocks into the policy's
+ *       scratch, with the same mask, then ONE policy launch, then (CHUB_PHEAD_LOADS) chub_load_dispatch_device.  With d_mask [N] u8 (device
+ *       memory) only the rows of the named envs are written.  Manners are chub_pile_obs_device's: no tick, no clock, no draw; no
+ *       synchronisation, allocation or staging copy; recordable between chub_graph_begin and chub_graph_end without counting towards the even
+ *       number of resets + steps; valid in all three RNG modes, on lock-step and per-env clocks, with per-env rows.  A policy's scratch is one
+ *       buffer: calls on one policy must be ordered against each other (the same stream, or an event).
+ *   chub_policy_act: the convenience form through host memory, every env: obs [N, D] -> actions [N, A].  Allocates, copies, synchronises.
+ *   chub_policy_run_steps: the closed loop issued from C, steps first_step .. first_step + n_steps - 1; returns after enqueueing.  Results are
+ *       exactly those of the same calls made one by one; inside a capture the whole run is recorded, under the step calls' own rules.
+ *       CHUB_PRUN_LOCKSTEP: before every step whose index is a multiple of 96 a chub_reset_device into d_reset_obs [N, D]; then per step i
+ *           chub_policy_act_device on the newest observation -- d_reset_obs right after a reset, else d_packed2[(i - 1) & 1] (so a run that
+ *           starts mid-day continues from the block its predecessor left) -- into the policy's own bits and tail, and
+ *           chub_step_bits_device_packed into d_packed2[i & 1] [N, D + 2].  16 bytes of action per env and word instead of a float row.
+ *       CHUB_PRUN_AUTORESET: per step chub_policy_act_device into the policy's own action rows and chub_autoreset_step_device into
+ *           d_packed2[i & 1] (d_final_obs [N, D] may be NULL).  The handle must have been reset.  The call's first step reads d_reset_obs [N, D]
+ *           (the observation the caller holds) if it is given, else d_packed2[(first_step - 1) & 1]; every later step the packed block before it.
+ *       Philox modes only: COMPAT needs the caller's normals per step (CHUB_ERR_UNSUPPORTED).
+ * Refusals, all with a message and before any device work.  CHUB_ERR_ARG: null arguments; n_inputs or n_layers outside 1 .. 4; an unknown
+ * kind, activation, head or squash; a feature block's own bad arguments (that call's message); widths outside
+ * 1 .. 256; a last width that is not the head's; clip <= 0 (or NaN) with normalize; a policy used with a handle it was not made for; no
+ * output asked for, or d_pile_bits without d_tail.  CHUB_ERR_UNSUPPORTED: chub_policy_create, chub_policy_destroy and the host form of
+ * set_weights between chub_graph_begin and chub_graph_end; a non-OBS block or the LOADS head on a tape handle (as the feature calls); a
+ * feature row and hidden layers that do not fit the kernel's 64 KiB of LDS (F rounded up to 2 and the widest odd hidden layer, plus the
+ * widest even hidden layer, each rounded up to 32: at most 512 rows together -- F <= 256 always fits).
+ * Out of scope: sampling and exploration noise, log-probabilities, a critic, bf16 / f16 weights, recurrent or convolutional actors, the
+ * multi-GPU hosts, COMPAT in chub_policy_run_steps. */
+enum { CHUB_PIN_OBS = 0, CHUB_PIN_PILE_OBS, CHUB_PIN_STATION_PROFILE, CHUB_PIN_FORECAST, CHUB_PIN_COUNT };
+enum { CHUB_PACT_TANH = 0, CHUB_PACT_RELU, CHUB_PACT_COUNT };
+enum { CHUB_PHEAD_PILES = 0, CHUB_PHEAD_LOADS, CHUB_PHEAD_COUNT };
+enum { CHUB_PSQ_TANH = 0, CHUB_PSQ_CLIP, CHUB_PSQ_COUNT };
+enum { CHUB_PRUN_LOCKSTEP = 0, CHUB_PRUN_AUTORESET, CHUB_PRUN_COUNT };
+typedef struct chub_policy chub_policy;
+typedef struct chub_policy_input { int32_t kind, fields, param; } chub_policy_input;
+typedef struct chub_policy_spec {
+    int32_t n_inputs;             /* 1 .. 4 blocks, concatenated in this order into one feature row of F floats */
+    chub_policy_input inputs[4];
+    int32_t n_layers;             /* 1 .. 4 dense layers, the last one the output layer */
+    int32_t width[4];             /* width[l] = outputs of layer l, hidden widths 1 .. 256; width[n_layers - 1] is fixed by head */
+    int32_t hidden_act;           /* CHUB_PACT_* */
+    int32_t head;                 /* CHUB_PHEAD_* */
+    int32_t squash;               /* CHUB_PSQ_* */
+    int32_t normalize;            /* 0 / 1 */
+    float clip;
+} chub_policy_spec;
+int chub_policy_input_width(const chub_config *cfg, const chub_policy_spec *spec, int32_t *F_out, int32_t *A_out);
+int chub_policy_create(chub_env *env, const chub_policy_spec *spec, const float *const *W, const float *const *b, const float *mean,
+                       const float *inv_std, chub_policy **out);
+int chub_policy_destroy(chub_policy *pol);
+int chub_policy_set_weights(chub_policy *pol, int32_t layer, const float *W, const float *b);
+int chub_policy_set_weights_device(chub_policy *pol, int32_t layer, const float *d_W, const float *d_b, void *stream);
+int chub_policy_act_device(chub_env *env, chub_policy *pol, const float *d_obs, int64_t ld_obs, const uint8_t *d_mask, float *d_actions,
+                           uint64_t *d_pile_bits, float *d_tail, void *stream);
+int chub_policy_act(chub_env *env, chub_policy *pol, const float *obs, float *actions);
+int chub_policy_run_steps(chub_env *env, chub_policy *pol, int mode, float *const *d_packed2, float *d_reset_obs, float *d_final_obs,
+                          int64_t first_step, int64_t n_steps, void *stream);
+
 /* The FCEV waiting list is unbounded as in the reference (HYD:264-265): the entries a list that still gets served can
  * hold are kept one by one, and once no prefix of it fits into 15 minutes any more (HYD:270-276: nobody is served again
  * until reset and the list only grows) its entries are folded into their count and running sums, which is all the

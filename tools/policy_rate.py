@@ -1,0 +1,127 @@
+#!/usr/bin/env python3
+"""The device actor (chub_policy_*) on a device-resident PHILOX handle, three measurements on ONE build in one process:
+  launch       us per chub_policy_act_device (bits + tail out), CALLS launches between two HIP events;
+  closed_loop  env-steps/s of chub_policy_run_steps (lock-step mode: reset, then per step the actor and the bits-form step) over ten days;
+  open_loop    the same for chub_run_steps with its open-loop random action batches.
+Every case is warmed up, then the cases alternate, ROUNDS times; median, best and worst round are reported with the build id.
+--open-loop-only measures the last case alone: with CHUB_LIB=<another build's libchub.so> that is the open-loop rate of a build without
+the actor (the parent commit), on the same device, for the comparison against run-to-run noise.
+    python tools/policy_rate.py [--shape 65536x20,25] [--hidden 64,64] [--rounds 7] [--calls 200] [--days 10] [--out profiles/policy_rate.json]"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import charginghub_env_amd as chub
+from charginghub_env_amd import multi_gpu
+from charginghub_env_amd._lib import check
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shape", default="65536x20,25")
+    ap.add_argument("--hidden", default="64,64")
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--days", type=int, default=10)
+    ap.add_argument("--open-loop-only", action="store_true")
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    n_s, piles_s = args.shape.split("x")
+    n, piles = int(n_s), [int(x) for x in piles_s.split(",")]
+    hidden = [int(x) for x in args.hidden.split(",") if x]
+    st = multi_gpu.Stream(0)
+    stream = st.ptr
+    lib = chub.load_library()
+    hip = ctypes.CDLL("libamdhip64.so")  # (the runtime libchub has loaded)
+    for name, argtypes in (("hipEventCreate", [ctypes.POINTER(ctypes.c_void_p)]), ("hipEventRecord", [ctypes.c_void_p, ctypes.c_void_p]),
+                           ("hipEventSynchronize", [ctypes.c_void_p]),
+                           ("hipEventElapsedTime", [ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p])):
+        getattr(hip, name).restype = ctypes.c_int
+        getattr(hip, name).argtypes = argtypes
+    ev = [ctypes.c_void_p(), ctypes.c_void_p()]
+    for e in ev:
+        assert hip.hipEventCreate(ctypes.byref(e)) == 0
+    build_id = lib.chub_build_id().decode()
+
+    v = chub.VecChargingHub(n, seed=1, rng="philox", station_list=piles, station_type_list=["fast", "slow"], hydro_prod_rate=100.0,
+                            hydro_store_vlt=25.0, init_soc=0.2, fc_max_power=100.0, fcev_permeate=0.01)
+    D, A = v.obs_dim, v.act_dim
+    acts = [multi_gpu.DeviceBuffer(n * A * 4) for _ in range(4)]
+    for b, a in enumerate(acts):
+        v.random_actions_device(a.ptr, 123, b, stream)
+    packed = [multi_gpu.DeviceBuffer(n * (D + 2) * 4) for _ in range(2)]
+    obs0 = multi_gpu.DeviceBuffer(n * D * 4)
+    bits, tail = multi_gpu.DeviceBuffer(n * v.bit_words * 8), multi_gpu.DeviceBuffer(n * 2 * 4)
+    c_acts = (ctypes.c_void_p * 4)(*[a.ptr for a in acts])
+    c_packed = (ctypes.c_void_p * 2)(packed[0].ptr, packed[1].ptr)
+    steps = 96 * args.days
+
+    def between_events(fn):
+        assert hip.hipEventRecord(ev[0], stream) == 0
+        fn()
+        assert hip.hipEventRecord(ev[1], stream) == 0
+        assert hip.hipEventSynchronize(ev[1]) == 0
+        ms = ctypes.c_float()
+        assert hip.hipEventElapsedTime(ctypes.byref(ms), ev[0], ev[1]) == 0
+        return ms.value
+
+    def open_loop():
+        st.sync()
+        t0 = time.perf_counter()
+        check(lib.chub_run_steps(v._h, None, c_acts, 4, c_packed, None, obs0.ptr, 0, steps, stream))
+        st.sync()
+        return n * steps / (time.perf_counter() - t0)
+
+    cases = {("open_loop", "chub_run_steps", "env_steps_per_s"): open_loop}
+    if not args.open_loop_only:
+        rs = np.random.RandomState(0)
+        sizes = [D] + hidden + [A]
+        layers = [((rs.normal(size=(o, i)) / np.sqrt(i)).astype(np.float32), (0.1 * rs.normal(size=o)).astype(np.float32))
+                  for i, o in zip(sizes[:-1], sizes[1:])]
+        pol = v.make_policy(layers)
+
+        def launch():
+            def many():
+                for _ in range(args.calls):
+                    pol.act_device(packed[1].ptr, D + 2, d_pile_bits=bits.ptr, d_tail=tail.ptr, stream=stream)
+            return between_events(many) * 1e3 / args.calls
+
+        def closed_loop():
+            st.sync()
+            t0 = time.perf_counter()
+            pol.run_steps([p.ptr for p in packed], steps, mode="lockstep", d_reset_obs=obs0.ptr, stream=stream)
+            st.sync()
+            return n * steps / (time.perf_counter() - t0)
+
+        cases[("launch", "chub_policy_act_device", "us_per_launch")] = launch
+        cases[("closed_loop", "chub_policy_run_steps", "env_steps_per_s")] = closed_loop
+
+    for fn in cases.values():  # warm-up (the open loop first: it leaves real observations in the packed blocks)
+        fn()
+    values = {c: [] for c in cases}
+    for _ in range(args.rounds):
+        for c, fn in cases.items():
+            values[c].append(fn())
+    rows = []
+    for (kind, route, unit), xs in values.items():
+        row = dict(shape=args.shape, n_envs=n, piles=piles, mode="philox", net=[D] + hidden + [A], kind=kind, route=route, unit=unit, rounds=len(xs),
+                   median=round(statistics.median(xs), 3), min=round(min(xs), 3), max=round(max(xs), 3), steps_per_round=steps,
+                   launches_per_round=args.calls, build_id=build_id, lib=os.environ.get("CHUB_LIB", ""))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    v.close()
+    st.destroy()
+    if args.out:
+        os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+        json.dump(rows, open(args.out, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()
