@@ -1784,6 +1784,9 @@ constexpr int kAccCopies = CHUB_ACC_COPIES;
 #ifndef CHUB_TAIL_PRE
 #define CHUB_TAIL_PRE 1  // 1: the tail actions packed_records hands over are requested with the workgroup's first loads; 0: where it stores them (A/B)
 #endif
+#ifndef CHUB_UNIT_DRAWS
+#define CHUB_UNIT_DRAWS 1  // 1: steps on the small tile take a unit's decoded draws and its admission count once, in the unit pass; 0: every lane of the unit (A/B)
+#endif
 #ifndef CHUB_EPI_ALL
 #define CHUB_EPI_ALL 1  // 1: every wave of the workgroup takes its share of the new cars (a third barrier: -0.2 us at C4); 0: the last wave alone
 #endif
@@ -1903,6 +1906,16 @@ __device__ __forceinline__ int slot_body_packed(const HubParams &hp, const StepA
     // comes out as vmcnt(0).  Two forms keep the slot-by-slot order: the large tile, whose streams come from HBM (state words first cost it
     // 1.4 % of the C5 step), and the one-launch kernels (FUSED: 0.4-1 % of the C2 step; they compile to what they were) -- docs/LAB_NOTEBOOK.md, Part I.
     constexpr bool STATE_FIRST = !RESET && !FUSED && BLOCK <= 256;
+    // The same forms take a unit's decoded draws ONCE: all S_k lanes of a unit used to ask for the same word and work the same
+    // assign / line out of it.  The lane that runs unit u in the unit pass behind barrier 1 (thread u; T <= 2 and epb <= BLOCK * T / 4: 2 epb <= BLOCK
+    // units, one pass) requests the word behind its wave's action rows, as the last wave requests its tail actions, and leaves the unit's
+    // admission count in s_uinfo -- where its empties were, which only that count needed -- and its record word in s_unit.  (A wait counts
+    // from the youngest request: a wave that makes such an extra request waits for one of its action rows with the state words, the others
+    // for the state words alone.  In front of the state words, where every wave's wait is exact, and on the last wave were measured and
+    // lost 0.1 % each -- docs/LAB_NOTEBOOK.md, Part I.)  A step's `want` is an unsigned byte of the decoded
+    // word (dk_make), so the count is 0 ... 64; the raw draws of a reset, which are negative on small fast stations, keep the per-lane form,
+    // as do the large tile, the one-launch kernels and stations of more than 64 piles.
+    constexpr bool UNIT_DRAWS = CHUB_UNIT_DRAWS && STATE_FIRST && !BIG && T <= 2;
     int e_[T], k_[T], slot[T];
     bool valid[T];
     uint32_t sidx[T];
@@ -1963,14 +1976,23 @@ __device__ __forceinline__ int slot_body_packed(const HubParams &hp, const StepA
             for (int j = 0; j < T; j++) served[j] = CHUB_AT(const uint8_t, pa.env_mask, envc[j]);
             asm volatile("" ::: "memory");
         }
+        if (!UNIT_DRAWS) {
 #pragma unroll
-        for (int j = 0; j < T; j++) pk_in[j] = CHUB_AT(const uint32_t, pa.pk, (valid[j] ? sidx[j] : (uint32_t) env_first) << 2);
-        asm volatile("" ::: "memory");
+            for (int j = 0; j < T; j++) pk_in[j] = CHUB_AT(const uint32_t, pa.pk, (valid[j] ? sidx[j] : (uint32_t) env_first) << 2);
+            asm volatile("" ::: "memory");
+        }
 #pragma unroll
         for (int j = 0; j < T; j++) {
             if (BITS) actw[j] = CHUB_AT(const u32x2, pa.actions, (envc[j] * (((uint32_t) St + 63u) >> 6) + (valid[j] ? (uint32_t) hs_[j] >> 6 : 0u)) << 3);
             else act[j] = CHUB_ACT_LOAD((CHUB_G(const float)) ((CHUB_G(const char)) pa.actions + (uint32_t) ((idx0 + vc[j] + 2u * envc[j]) << 2)));  // row stride S0 + S1 + 2
         }
+    }
+    uint32_t upk = 0u;  // UNIT_DRAWS: unit tid's decoded draws
+    if (UNIT_DRAWS) asm volatile("" : "=v"(upk));
+    if (UNIT_DRAWS && (tid & ~63) < 2 * epb) {  // (wave-uniform: the 22 units of a workgroup of the 20 + 25 hub are the first wave's alone)
+        asm volatile("" ::: "memory");
+        const int ue = tid >> 1, uenv = env_first + ue;
+        upk = CHUB_AT(const uint32_t, pa.pk, (ue < epb && uenv < N ? (uint32_t) ((tid & 1) ? N : 0) + (uint32_t) uenv : (uint32_t) env_first) << 2);
     }
     if (HOIST_TAIL) asm volatile("" : "=v"(tail_pre[0]), "=v"(tail_pre[1]));
     if (HOIST_TAIL && wave == WAVES - 1) {  // behind everything else: the other waves' wait for the state words then leaves them in flight as well
@@ -2043,7 +2065,7 @@ __device__ __forceinline__ int slot_body_packed(const HubParams &hp, const StepA
     CHUB_STAMP(4);  // barrier 1 passed
     // ---- every unit's empties, ONCE per unit: a lane per unit reads the ballots of the (at most two) virtual waves the unit lies in
     // and leaves, in one word, the empties in front of the unit inside its first wave, the unit's empties in that wave, its empties in
-    // all, and which wave that is.  (Rounds 2-3 had every LANE work its unit's 64-bit masks out for itself, two popcounts and an LDS
+    // all -- UNIT_DRAWS: how many of them take a car, with the unit's record word in s_unit -- and which wave that is.  (Rounds 2-3 had every LANE work its unit's 64-bit masks out for itself, two popcounts and an LDS
     // read each: a third of the kernel's vector instructions.)  Stations of more than 64 piles keep that form below.
     if (!BIG) {
         for (int u = tid; u < 2 * epb; u += BLOCK) {
@@ -2053,13 +2075,26 @@ __device__ __forceinline__ int slot_body_packed(const HubParams &hp, const StepA
             const int wv = U0 >> 6, lo = U0 & 63;
             const int hi0 = (U1 - (wv << 6)) < 64 ? (U1 - (wv << 6)) : 64;
             uint32_t info = (uint32_t) wv << 24;
+            int all = 0;  // the unit's empties
             if (Sk > 0) {
                 const uint64_t b0 = s_ball[wv];
                 const uint64_t below_lo = lo ? (~0ull >> (64 - lo)) : 0ull, below_hi = ~0ull >> (64 - hi0);
                 const int start_e = __popcll(b0 & below_lo), cnt0 = __popcll(b0 & below_hi & ~below_lo);
                 const int over = U1 - ((wv + 1) << 6);  // lanes of the unit in the next virtual wave
                 const int cnt1 = over > 0 ? __popcll(s_ball[wv + 1] & (~0ull >> (64 - over))) : 0;
-                info |= (uint32_t) start_e | ((uint32_t) cnt0 << 8) | ((uint32_t) (cnt0 + cnt1) << 16);
+                all = cnt0 + cnt1;
+                info |= (uint32_t) start_e | ((uint32_t) cnt0 << 8) | (UNIT_DRAWS ? 0u : (uint32_t) (cnt0 + cnt1) << 16);
+            }
+            if (UNIT_DRAWS) {
+                // assign_car (CHS.hpp:417-430), once per unit: the queue after the renege pass + the arrivals that stay, and flow_in, were decoded
+                // one launch ahead (dk_make).  The third byte carries how many of the unit's empties take a car instead of how many there are.
+                // (A unit past the batch's end or of an env the launch does not serve has no empties -- its lanes balloted none -- and so admits nobody.)
+                asm volatile("" : "+v"(upk));
+                const int want = dk_want(upk);
+                const int assign = want < all ? want : all;
+                const int ln = want - assign;
+                s_unit[u] = pkd_make(ln < kMaxLine ? ln : kMaxLine, dk_flow(upk), 0);
+                info |= (uint32_t) assign << 16;
             }
             s_uinfo[u] = info;
         }
@@ -2141,7 +2176,9 @@ __device__ __forceinline__ int slot_body_packed(const HubParams &hp, const StepA
         line[j] = 0;
         flow[j] = 0;
         int assign = 0;
-        if (valid[j]) {
+        if (UNIT_DRAWS) {
+            assign = empties;  // (the unit pass left min(want, empties) in that byte)
+        } else if (valid[j]) {
             const uint32_t pk = pk_in[j];
             int want;
             if (RESET) {
@@ -2176,7 +2213,7 @@ __device__ __forceinline__ int slot_body_packed(const HubParams &hp, const StepA
 #pragma unroll
     for (int j = 0; j < T; j++) {
         if (valid[j] && !adm[j]) CHUB_AT(uint32_t, pa.state, (idx0 + (uint32_t) (tid + j * BLOCK)) << 2) = w0n[j];
-        if (valid[j] && slot[j] == 0) s_unit[2 * e_[j] + k_[j]] = pkd_make(line[j], flow[j], 0);
+        if (!UNIT_DRAWS && valid[j] && slot[j] == 0) s_unit[2 * e_[j] + k_[j]] = pkd_make(line[j], flow[j], 0);
     }
     CHUB_STAMP(7);  // admission done, state stores issued
     __syncthreads();
@@ -2270,7 +2307,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK <= 256 ? 8 : 2048 / BLOCK)) void k_sl
     __shared__ uint64_t s_ball[BLOCK * T / 64 + 2];                   // [1 + virtual wave]: a unit's neighbouring wave may be "wave -1" or "wave WAVES"
     __shared__ __attribute__((aligned(16))) int s_acc[2 * BLOCK * T * kAccCopies];  // 2 epb <= BLOCK * T / 2 units x {min, charge, max power, cars} (BIG: as 64-bit sums, few units)
     __shared__ uint32_t s_unit[BLOCK * T / 2];                        // per unit: line | flow << 8
-    __shared__ uint32_t s_uinfo[BLOCK * T / 2];                       // per unit: where its empties are (the admission's unit pass)
+    __shared__ uint32_t s_uinfo[BLOCK * T / 2];                       // per unit: where its empties are and how many of them take a car (the admission's unit pass)
     if (RESET && MASKED && mask_is_empty(sa)) return;  // (a masked reset of nobody: chub_autoreset_step_device on most calls)
     // all kernel arguments this wave needs, requested in ONE batch of scalar loads at its very start (the single asm
     // statement makes every one of them live here), instead of in a chain of dependent loads in front of the first
