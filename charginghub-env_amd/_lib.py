@@ -196,6 +196,18 @@ class ChubPolicySpec(C.Structure):
                 ("hidden_act", C.c_int32), ("head", C.c_int32), ("squash", C.c_int32), ("normalize", C.c_int32), ("clip", C.c_float)]
 
 
+class ChubPolicySampleOut(C.Structure):
+    """chub_policy_sample_out of include/chub.h: device addresses, 0 / None = not asked for"""
+    _fields_ = [("d_actions", C.c_void_p), ("d_pile_bits", C.c_void_p), ("d_tail", C.c_void_p), ("d_u", C.c_void_p), ("d_logp", C.c_void_p),
+                ("d_features", C.c_void_p)]
+
+
+class ChubRollout(C.Structure):
+    """chub_rollout of include/chub.h: T and the device addresses of the [T][N][...] arrays"""
+    _fields_ = [("T", C.c_int64), ("d_packed", C.c_void_p), ("d_pile_bits", C.c_void_p), ("d_tail", C.c_void_p), ("d_u", C.c_void_p),
+                ("d_logp", C.c_void_p), ("d_features", C.c_void_p), ("d_final_obs", C.c_void_p)]
+
+
 def _enum_value(table, value, what):
     if isinstance(value, str):
         if value not in table:
@@ -381,6 +393,10 @@ def load_library():
         "chub_policy_set_weights": (I, [P, C.c_int32, P, P]), "chub_policy_set_weights_device": (I, [P, C.c_int32, P, P, P]),
         "chub_policy_act_device": (I, [P, P, P, L, P, P, P, P, P]), "chub_policy_act": (I, [P, P, P, P]),
         "chub_policy_run_steps": (I, [P, P, I, P, P, P, L, L, P]),
+        "chub_next_tick": (I, [P, C.POINTER(C.c_uint32)]), "chub_policy_set_exploration": (I, [P, C.c_uint64, P]),
+        "chub_policy_set_log_std_device": (I, [P, P, P]),
+        "chub_policy_sample_device": (I, [P, P, P, L, P, C.POINTER(ChubPolicySampleOut), P]),
+        "chub_policy_collect": (I, [P, P, I, C.POINTER(ChubRollout), P, L, P]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -416,7 +432,8 @@ EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "ch
             "chub_forecast_size", "chub_forecast_device", "chub_forecast",
             "chub_get_step_terms_size", "chub_get_step_terms_device", "chub_get_step_terms", "chub_set_step_terms", "chub_get_step_terms_attached",
             "chub_policy_input_width", "chub_policy_create", "chub_policy_destroy", "chub_policy_set_weights", "chub_policy_set_weights_device",
-            "chub_policy_act_device", "chub_policy_act", "chub_policy_run_steps"]
+            "chub_policy_act_device", "chub_policy_act", "chub_policy_run_steps",
+            "chub_next_tick", "chub_policy_set_exploration", "chub_policy_set_log_std_device", "chub_policy_sample_device", "chub_policy_collect"]
 
 
 def check(rc):

@@ -23,6 +23,11 @@ constexpr int kPolicyMaxWaves = 4;    // waves per workgroup at most (one output
 // The activations of a tile live in two LDS images, [row][32 envs] f32: P holds the feature row and the outputs of the odd layers, Q the
 // outputs of the even layers.  Together at most 512 rows (64 KiB, what a launch gets without asking for more).
 constexpr int kPolicyLdsRows = 512;
+// Sampling (include/chub.h, "sampling from the device actor"): the Philox site of the policy's noise (SITE_POLICY of chub_device.h) and the
+// LDS rows behind the two images in which the waves' log-probability partials meet, [wave][32 envs].  They count towards the same 512
+// rows: chub_policy_set_exploration refuses a policy whose images leave fewer (the deterministic fit rule is unchanged)
+constexpr uint32_t kPolicySite = 15u;
+constexpr int kPolicyLogpRows = kPolicyMaxWaves;
 
 // Device weight layout of one layer (built by k_policy_relayout from the trainer's row-major [out][in]): per tile of 32 outputs the
 // transposed block [k_pad][32], zero beyond `in` and `out` -- lane l of a wave reads element 64 s + l of a tile at k-step s, which is
@@ -42,6 +47,7 @@ struct PolicyBlock {
 };
 
 struct PolicyArgs {
+    static constexpr bool kSample = false;
     int64_t n_envs;
     PolicyBlock in[kPolicyMaxInputs];
     PolicyLayer layer[kPolicyMaxLayers];
@@ -58,7 +64,23 @@ struct PolicyArgs {
     int32_t S, A, W;              // piles, outputs of the head, u64 words per env
 };
 
+// what the sampled instantiation of k_policy takes on top: the noise's counter and key, the Gaussian scale, the normal tables of the handle
+// (chub_device.h: normal_icdf / normal_tail) and the outputs only a sampled call has
+struct PolicySampleArgs : PolicyArgs {
+    static constexpr bool kSample = true;
+    const uint32_t *tick_base;    // the handle's device-side tick offset: the launch's Philox tick is tick + *tick_base, as a step's
+    const float *log_std;         // [G], the policy's own buffer (never moves)
+    const float *normal_icdf, *normal_tail;  // [4097] each
+    float *u;                     // [N][G] or null: the pre-squash Gaussian samples
+    float *logp;                  // [N]
+    float *features;              // [N][F] or null: the raw feature row
+    uint32_t key[2], tick, gid0;  // the policy's key, the host tick of the handle's next launch, global id of env 0
+    int32_t G;                    // Gaussian outputs: 2 (PILES), 4 (LOADS)
+    int32_t r_row0;               // first of the kPolicyLogpRows LDS rows of the log-probability partials
+};
+
 void launch_policy(const PolicyArgs &a, int waves, hipStream_t stream);
+void launch_policy_sample(const PolicySampleArgs &a, int waves, hipStream_t stream);
 // W [out][in] row-major and b [out] in device memory -> the layout above
 void launch_policy_relayout(const float *d_W, const float *d_b, float *d_w, float *d_bias, int out, int in, int k_pad, int tiles, hipStream_t stream);
 

@@ -13,6 +13,14 @@
 // input index k = 0, 1, .. with the bias as the chain's initial value, for every env alike -- a column of the B operand never meets
 // another column, so an env's outputs do not depend on N, the mask or its place in the tile.  Rows and columns beyond a layer's real
 // size hold zeros (weights, biases and LDS rows), which add exactly nothing.
+//
+// Sampling (the header's "sampling from the device actor") is a compile-time parameter of the same kernel: the argument block's type.
+// k_policy<PolicyArgs> is the deterministic actor, instruction for instruction what it was before sampling existed;
+// k_policy<PolicySampleArgs> runs the same chain to the pre-squash outputs and then, in the head, draws each pile from its logit and each
+// Gaussian output around its mean with Philox noise under the policy's key and the tick of the handle's next launch.  A lane's sixteen
+// accumulator rows are four runs of four consecutive rows from a multiple of four, so one Philox block serves each run with every word
+// used.  The log-probability's terms are summed per lane, across the half-waves by a shuffle and across the waves through four LDS rows
+// behind the two images, in wave order: no atomics.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -29,7 +37,52 @@ constexpr float kPolicyOnThreshold = -2.98023223876953125e-8f;
 // accumulator register r of lane l holds output row (r & 3) + 8 (r >> 2) + 4 (l >> 5) of the tile, for env column l & 31
 __device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
-__global__ __launch_bounds__(64 * kPolicyMaxWaves) void k_policy(const PolicyArgs a) {
+// ---- sampling (include/chub.h, "sampling from the device actor").  Philox4x32-10 and the tabulated normal are chub_kernels.hip's own
+// (philox4x32_10, normal_from_word), restated here because the two files share no device header: the same rounds, the same tables.
+struct PolicyU4 {
+    uint32_t v[4];
+};
+
+__device__ __forceinline__ PolicyU4 policy_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int i = 0; i < 10; i++) {
+        const uint64_t p0 = (uint64_t) 0xD2511F53u * c0, p1 = (uint64_t) 0xCD9E8D57u * c2;
+        const uint32_t h0 = (uint32_t) (p0 >> 32), l0 = (uint32_t) p0, h1 = (uint32_t) (p1 >> 32), l1 = (uint32_t) p1;
+        const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
+        c0 = n0; c1 = l1; c2 = n2; c3 = l0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    PolicyU4 r;
+    r.v[0] = c0; r.v[1] = c1; r.v[2] = c2; r.v[3] = c3;
+    return r;
+}
+
+// N(0,1) from one 32-bit word: 4096 cells of the inverse CDF, linear inside a cell; the outer 16 cells on either side through the second
+// table with cells of 2^-20
+__device__ __forceinline__ float policy_normal_from_word(const float *tz, const float *tl, uint32_t w) {
+    const uint32_t cell = w >> 20;
+    const bool hi = cell >= 4096u - 16u, lo = cell < 16u;
+    const uint32_t m = hi ? ~w : w;
+    const bool tail = hi || lo;
+    const float *tab = tail ? tl : tz;
+    const uint32_t idx = tail ? (m >> 12) : cell;
+    const float frac = tail ? (float) (m & 0xFFFu) * (1.0f / 4096.0f) : (float) (w & 0xFFFFFu) * (1.0f / 1048576.0f);
+    const float a = tab[idx], b = tab[idx + 1];
+    const float z = __fadd_rn(a, __fmul_rn(__fsub_rn(b, a), frac));
+    return hi ? -z : z;
+}
+
+constexpr float kHalfLn2Pi = 0.918938533204672742f;  // 0.5 ln 2 pi
+
+// softplus(x) = max(x, 0) + log1pf(expf(-|x|))
+__device__ __forceinline__ float policy_softplus(float x) { return __fadd_rn(fmaxf(x, 0.0f), log1pf(expf(-fabsf(x)))); }
+
+// Args = PolicyArgs: the deterministic actor.  Args = PolicySampleArgs: the same chain to the pre-squash outputs z, then a draw from the
+// actor's distribution, its log-probability and (if asked for) the raw feature row.
+template <typename Args>
+__global__ __launch_bounds__(64 * kPolicyMaxWaves) void k_policy(const Args a) {
+    constexpr bool kSample = Args::kSample;
     extern __shared__ float lds[];
     const int tid = (int) threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = (int) (blockDim.x >> 6), nt = (int) blockDim.x;
     const int col = lane & 31, half = lane >> 5;
@@ -51,6 +104,9 @@ __global__ __launch_bounds__(64 * kPolicyMaxWaves) void k_policy(const PolicyArg
                 float x = 0.0f;  // (envs beyond N: zeros, never stored)
                 if (env < a.n_envs) {
                     x = p[env * ld + f];
+                    if constexpr (kSample) {
+                        if (a.features && (!a.mask || a.mask[env] != 0)) a.features[env * a.F + f0 + f] = x;
+                    }
                     if (a.normalize) {
                         x = __fmul_rn(__fsub_rn(x, a.mean[f0 + f]), a.inv_std[f0 + f]);
                         x = fminf(fmaxf(x, -a.clip), a.clip);
@@ -66,6 +122,7 @@ __global__ __launch_bounds__(64 * kPolicyMaxWaves) void k_policy(const PolicyArg
 
     const int64_t env = env0 + col;
     const bool store = env < a.n_envs && (!a.mask || a.mask[env] != 0);
+    [[maybe_unused]] float logp = 0.0f;  // (sampling) this lane's terms: its rows of its wave's tiles, in ascending tile order
 
 #pragma unroll
     for (int l = 0; l < kPolicyMaxLayers; l++) {
@@ -90,6 +147,55 @@ __global__ __launch_bounds__(64 * kPolicyMaxWaves) void k_policy(const PolicyArg
                         const float z = acc[r];
                         const float v = a.hidden_act == PACT_TANH ? tanhf(z) : fmaxf(z, 0.0f);
                         dst[(t * kPolicyOutTile + acc_row(r, half)) * kPolicyEnvTile + col] = v;
+                    }
+                } else if constexpr (kSample) {
+                    // counter (block, site << 16 | kind, tick, global env id) under the policy's key: nothing of N, the mask or the tile enters
+                    const uint32_t tick = a.tick + *a.tick_base, gid = a.gid0 + (uint32_t) env;
+                    const bool piles = a.head == PHEAD_PILES;
+                    const int g0 = piles ? a.S : 0;  // output g0 + i is Gaussian i
+                    uint32_t m = 0u;
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        // registers 4 q .. 4 q + 3 are four consecutive rows from a multiple of 4: the four words of one pile block
+                        const int n0 = t * kPolicyOutTile + 8 * q + 4 * half;
+                        PolicyU4 pb = {{0u, 0u, 0u, 0u}}, gb = {{0u, 0u, 0u, 0u}};
+                        if (piles && n0 < a.S) pb = policy_philox4x32_10((uint32_t) (n0 >> 2), kPolicySite << 16, tick, gid, a.key[0], a.key[1]);
+                        if (n0 + 3 >= g0 && n0 < g0 + a.G) gb = policy_philox4x32_10(0u, (kPolicySite << 16) | 1u, tick, gid, a.key[0], a.key[1]);
+#pragma unroll
+                        for (int j = 0; j < 4; j++) {
+                            const int n = n0 + j, i = n - g0;
+                            const float z = acc[4 * q + j];
+                            if (piles && n < a.S) {
+                                const float U = (float) (pb.v[j] >> 8) * 5.9604644775390625e-8f;  // 2^-24: exact
+                                const float p = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-z)));
+                                const bool on = U < p;
+                                logp = __fsub_rn(logp, policy_softplus(on ? -z : z));
+                                if (on) m |= 1u << (n & 31);
+                                if (store && a.actions) a.actions[env * a.A + n] = on ? 1.0f : -1.0f;
+                            } else if (i >= 0 && i < a.G) {
+                                const uint32_t w = i == 0 ? gb.v[0] : i == 1 ? gb.v[1] : i == 2 ? gb.v[2] : gb.v[3];
+                                const float eps = policy_normal_from_word(a.normal_icdf, a.normal_tail, w);
+                                const float ls = a.log_std[i];
+                                const float u = __fadd_rn(z, __fmul_rn(expf(ls), eps));
+                                const float v = a.squash == PSQ_TANH ? tanhf(u) : fminf(fmaxf(u, -1.0f), 1.0f);
+                                logp = __fadd_rn(logp, __fsub_rn(__fsub_rn(__fmul_rn(-0.5f, __fmul_rn(eps, eps)), ls), kHalfLn2Pi));
+                                if (store) {
+                                    if (a.u) a.u[env * a.G + i] = u;
+                                    if (piles) {
+                                        if (a.actions) a.actions[env * a.A + n] = v;
+                                        if (a.tail) a.tail[env * 2 + i] = v;
+                                    } else if (i < 2) {
+                                        a.loads[env * 2 + i] = v;
+                                    } else {
+                                        a.tail[env * 2 + (i - 2)] = v;
+                                    }
+                                }
+                            }
+                        }
+                    }
+                    if (piles && a.bits) {
+                        m |= (uint32_t) __shfl_xor((int) m, 32);
+                        if (store && half == 0 && t < 2 * a.W) a.bits[env * (int64_t) (2 * a.W) + t] = m;
                     }
                 } else {
                     uint32_t m = 0u;
@@ -118,15 +224,44 @@ __global__ __launch_bounds__(64 * kPolicyMaxWaves) void k_policy(const PolicyArg
             __syncthreads();
         }
     }
+
+    if constexpr (kSample) {
+        // an env's log-probability: the two half-waves by a shuffle, then the waves' partials in wave order through LDS.  No atomics: the
+        // order is the same for every env and every launch of this policy
+        logp = __fadd_rn(logp, __shfl_xor(logp, 32));
+        float *const R = lds + (size_t) a.r_row0 * kPolicyEnvTile;
+        if (half == 0) R[wave * kPolicyEnvTile + col] = logp;
+        __syncthreads();
+        if (tid < kPolicyEnvTile) {
+            float s = R[col];
+            for (int w = 1; w < nw; w++) s = __fadd_rn(s, R[w * kPolicyEnvTile + col]);
+            if (store) a.logp[env] = s;
+        }
+    }
+}
+
+// rows of the Q image: it ends where the widest even hidden layer does
+static int policy_q_rows(const PolicyArgs &a) {
+    int q_rows = 0;
+    for (int l = 0; l + 1 < a.n_layers; l += 2) q_rows = a.layer[l].tiles * kPolicyOutTile > q_rows ? a.layer[l].tiles * kPolicyOutTile : q_rows;
+    return q_rows;
 }
 
 void launch_policy(const PolicyArgs &a, int waves, hipStream_t stream) {
     if (a.n_envs <= 0) return;
     const int64_t nb = (a.n_envs + kPolicyEnvTile - 1) / kPolicyEnvTile;
-    int q_rows = 0;  // (the Q image ends where the widest even hidden layer does)
-    for (int l = 0; l + 1 < a.n_layers; l += 2) q_rows = a.layer[l].tiles * kPolicyOutTile > q_rows ? a.layer[l].tiles * kPolicyOutTile : q_rows;
-    const size_t lds_bytes = (size_t) (a.q_row0 + q_rows) * kPolicyEnvTile * sizeof(float);
-    hipLaunchKernelGGL(k_policy, dim3((unsigned) nb), dim3(64u * (unsigned) waves), lds_bytes, stream, a);
+    const size_t lds_bytes = (size_t) (a.q_row0 + policy_q_rows(a)) * kPolicyEnvTile * sizeof(float);
+    hipLaunchKernelGGL(k_policy<PolicyArgs>, dim3((unsigned) nb), dim3(64u * (unsigned) waves), lds_bytes, stream, a);
+}
+
+// the sampled launch: the same grid, kPolicyLogpRows more rows of LDS behind the two images (the caller has checked that they fit)
+void launch_policy_sample(const PolicySampleArgs &a, int waves, hipStream_t stream) {
+    if (a.n_envs <= 0) return;
+    const int64_t nb = (a.n_envs + kPolicyEnvTile - 1) / kPolicyEnvTile;
+    PolicySampleArgs s = a;
+    s.r_row0 = a.q_row0 + policy_q_rows(a);
+    const size_t lds_bytes = (size_t) (s.r_row0 + kPolicyLogpRows) * kPolicyEnvTile * sizeof(float);
+    hipLaunchKernelGGL(k_policy<PolicySampleArgs>, dim3((unsigned) nb), dim3(64u * (unsigned) waves), lds_bytes, stream, s);
 }
 
 // the trainer's layout (nn.Linear: W [out][in] row-major, b [out]) -> the kernel's (chub_policy.h), zeros beyond `out` and `in`

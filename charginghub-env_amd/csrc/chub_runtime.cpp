@@ -3445,6 +3445,11 @@ struct chub_policy {
     float *d_loads, *d_tail;                // [N][2] each: the LOADS head's outputs; the run loop's tail pair
     uint64_t *d_bits;                       // [N][W]: the run loop's pile bits
     float *d_rows;                          // [N][S + 2]: the run loop's action rows (CHUB_PRUN_AUTORESET)
+    // sampling (chub_policy_set_exploration): the key of the policy's noise and the Gaussian outputs' log_std [G] (allocated once, never moves)
+    int32_t lds_rows, G;                    // rows of the two LDS images; Gaussian outputs (2 PILES, 4 LOADS)
+    bool explore;
+    uint32_t key[2];
+    float *d_log_std;
     std::vector<void *> allocs;
 };
 
@@ -3575,6 +3580,8 @@ int chub_policy_create(chub_env *e, const chub_policy_spec *spec, const float *c
     pol->spec = *spec;
     pol->F = ps.F;
     pol->A_out = ps.A_out;
+    pol->lds_rows = ps.p_rows + ps.q_rows;
+    pol->G = spec->head == CHUB_PHEAD_PILES ? 2 : 4;
     e->policies.push_back(pol);
     const size_t N = (size_t) e->hp.n_envs;
     const int S = e->hp.S[0] + e->hp.S[1], Wd = (S + 63) / 64;
@@ -3674,23 +3681,27 @@ int chub_policy_set_weights_device(chub_policy *pol, int32_t layer, const float 
     return CHUB_OK;
 }
 
-int chub_policy_act_device(chub_env *e, chub_policy *pol, const float *d_obs, int64_t ld_obs, const uint8_t *d_mask, float *d_actions,
-                           uint64_t *d_pile_bits, float *d_tail, void *stream) {
-    if (!e || !pol) return fail(CHUB_ERR_ARG, "null argument");
-    if (pol->env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
-    const chub_policy_spec &sp = pol->spec;
-    bool obs_block = false, feature_block = false;
-    for (int i = 0; i < sp.n_inputs; i++) (sp.inputs[i].kind == CHUB_PIN_OBS ? obs_block : feature_block) = true;
+// what an evaluation asks of its observation argument, and of the handle (the tape rules of the feature calls)
+static int policy_check_obs(const chub_env *e, const chub_policy *pol, const float *d_obs, int64_t ld_obs) {
+    bool obs_block = false;
+    for (int i = 0; i < pol->spec.n_inputs; i++) obs_block |= pol->spec.inputs[i].kind == CHUB_PIN_OBS;
     if (obs_block && !d_obs) return fail(CHUB_ERR_ARG, "null argument");
     if (obs_block && ld_obs < e->hp.obs_dim) return fail(CHUB_ERR_ARG, "ld_obs: at least the observation's " + std::to_string(e->hp.obs_dim) + " floats");
-    if (!d_actions && !d_pile_bits) return fail(CHUB_ERR_ARG, "chub_policy_act: give d_actions, d_pile_bits or both");
-    if (sp.head == CHUB_PHEAD_PILES && d_pile_bits && !d_tail) return fail(CHUB_ERR_ARG, "chub_policy_act: pile bits need d_tail (the two tail actions)");
-    if (e->tape_only && (feature_block || sp.head == CHUB_PHEAD_LOADS))
+    return CHUB_OK;
+}
+
+static int policy_check_tape(const chub_env *e, const chub_policy *pol) {
+    bool feature_block = false;
+    for (int i = 0; i < pol->spec.n_inputs; i++) feature_block |= pol->spec.inputs[i].kind != CHUB_PIN_OBS;
+    if (e->tape_only && (feature_block || pol->spec.head == CHUB_PHEAD_LOADS))
         return fail(CHUB_ERR_UNSUPPORTED, "a policy that reads feature blocks or sets station loads is not supported on a tape handle "
                                           "(chub_tape_register_soc rewrites the class tables)");
-    HIP_TRY(hipSetDevice(e->device));
-    (void) hipGetLastError();
-    PolicyArgs pa = pol->pa;
+    return CHUB_OK;
+}
+
+// the feature launches of the spec's non-OBS blocks into the policy's scratch; the OBS blocks point at the caller's rows
+static int policy_feature_blocks(chub_env *e, chub_policy *pol, const float *d_obs, int64_t ld_obs, const uint8_t *d_mask, PolicyArgs &pa, void *stream) {
+    const chub_policy_spec &sp = pol->spec;
     for (int i = 0; i < sp.n_inputs; i++) {
         const chub_policy_input &in = sp.inputs[i];
         int rc = CHUB_OK;
@@ -3705,6 +3716,22 @@ int chub_policy_act_device(chub_env *e, chub_policy *pol, const float *d_obs, in
         }
         if (rc) return rc;
     }
+    return CHUB_OK;
+}
+
+int chub_policy_act_device(chub_env *e, chub_policy *pol, const float *d_obs, int64_t ld_obs, const uint8_t *d_mask, float *d_actions,
+                           uint64_t *d_pile_bits, float *d_tail, void *stream) {
+    if (!e || !pol) return fail(CHUB_ERR_ARG, "null argument");
+    if (pol->env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
+    const chub_policy_spec &sp = pol->spec;
+    if (const int rc = policy_check_obs(e, pol, d_obs, ld_obs)) return rc;
+    if (!d_actions && !d_pile_bits) return fail(CHUB_ERR_ARG, "chub_policy_act: give d_actions, d_pile_bits or both");
+    if (sp.head == CHUB_PHEAD_PILES && d_pile_bits && !d_tail) return fail(CHUB_ERR_ARG, "chub_policy_act: pile bits need d_tail (the two tail actions)");
+    if (const int rc = policy_check_tape(e, pol)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    PolicyArgs pa = pol->pa;
+    if (const int rc = policy_feature_blocks(e, pol, d_obs, ld_obs, d_mask, pa, stream)) return rc;
     const bool loads = sp.head == CHUB_PHEAD_LOADS;
     pa.mask = d_mask;
     pa.actions = loads ? nullptr : d_actions;
@@ -3772,6 +3799,135 @@ int chub_policy_run_steps(chub_env *e, chub_policy *pol, int mode, float *const 
             if ((rc = chub_policy_act_device(e, pol, obs, ld, nullptr, pol->d_rows, nullptr, nullptr, stream))) return rc;
             if ((rc = chub_autoreset_step_device(e, pol->d_rows, nullptr, nullptr, nullptr, d_packed2[i & 1], d_final_obs, stream))) return rc;
         }
+    }
+    return CHUB_OK;
+}
+
+// ---- sampling from the device actor (include/chub.h): exploration noise, log-probabilities, rollouts that keep the trajectory
+static_assert((uint32_t) SITE_POLICY == kPolicySite, "chub_policy.h restates SITE_POLICY of chub_device.h");
+
+int chub_next_tick(const chub_env *e, uint32_t *out) {
+    if (!e || !out) return fail(CHUB_ERR_ARG, "null argument");
+    *out = e->tick + 1u;
+    return CHUB_OK;
+}
+
+int chub_policy_set_exploration(chub_policy *pol, uint64_t key, const float *log_std) {
+    if (!pol || !log_std) return fail(CHUB_ERR_ARG, "null argument");
+    chub_env *e = pol->env;
+    for (int i = 0; i < pol->G; i++)
+        if (!std::isfinite(log_std[i])) return fail(CHUB_ERR_ARG, "log_std[" + std::to_string(i) + "] is not finite");
+    if (e->capturing)
+        return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_set_exploration between chub_graph_begin and chub_graph_end (it copies and synchronises: use "
+                                          "chub_policy_set_log_std_device)");
+    if (pol->lds_rows + kPolicyLogpRows > kPolicyLdsRows)
+        return fail(CHUB_ERR_UNSUPPORTED, "the sampled launch needs " + std::to_string(kPolicyLogpRows) + " rows of LDS behind this policy's " +
+                                              std::to_string(pol->lds_rows) + ": at most " + std::to_string(kPolicyLdsRows) + " together");
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipDeviceSynchronize());  // (a sampled launch in flight reads the buffer)
+    if (!pol->d_log_std)
+        if (const int rc = policy_alloc(pol, &pol->d_log_std, 4)) return rc;
+    HIP_TRY(hipMemcpy(pol->d_log_std, log_std, (size_t) pol->G * sizeof(float), hipMemcpyHostToDevice));
+    pol->key[0] = (uint32_t) key;  // (split as the env's seed is)
+    pol->key[1] = (uint32_t) (key >> 32);
+    pol->explore = true;
+    return CHUB_OK;
+}
+
+int chub_policy_set_log_std_device(chub_policy *pol, const float *d_log_std, void *stream) {
+    if (!pol || !d_log_std) return fail(CHUB_ERR_ARG, "null argument");
+    if (!pol->explore) return fail(CHUB_ERR_ARG, "chub_policy_set_exploration first (it makes the policy's log_std buffer)");
+    HIP_TRY(hipSetDevice(pol->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipMemcpyAsync(pol->d_log_std, d_log_std, (size_t) pol->G * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
+    return CHUB_OK;
+}
+
+// everything chub_policy_sample_device refuses for, with nothing enqueued yet
+static int policy_sample_check(chub_env *e, chub_policy *pol, const float *d_obs, int64_t ld_obs, const chub_policy_sample_out *out) {
+    if (!e || !pol || !out) return fail(CHUB_ERR_ARG, "null argument");
+    if (pol->env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
+    if (!pol->explore) return fail(CHUB_ERR_ARG, "chub_policy_sample: chub_policy_set_exploration first (the key and log_std)");
+    if (const int rc = policy_check_obs(e, pol, d_obs, ld_obs)) return rc;
+    if (!out->d_logp) return fail(CHUB_ERR_ARG, "chub_policy_sample: d_logp is required");
+    if (pol->spec.head == CHUB_PHEAD_PILES && out->d_pile_bits && !out->d_tail)
+        return fail(CHUB_ERR_ARG, "chub_policy_sample: pile bits need d_tail (the two tail actions)");
+    return policy_check_tape(e, pol);
+}
+
+int chub_policy_sample_device(chub_env *e, chub_policy *pol, const float *d_obs, int64_t ld_obs, const uint8_t *d_mask,
+                              const chub_policy_sample_out *out, void *stream) {
+    if (const int rc = policy_sample_check(e, pol, d_obs, ld_obs, out)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    PolicySampleArgs sa;
+    static_cast<PolicyArgs &>(sa) = pol->pa;
+    if (const int rc = policy_feature_blocks(e, pol, d_obs, ld_obs, d_mask, sa, stream)) return rc;
+    const bool loads = pol->spec.head == CHUB_PHEAD_LOADS;
+    sa.mask = d_mask;
+    sa.actions = loads ? nullptr : out->d_actions;
+    sa.bits = loads ? nullptr : (uint32_t *) out->d_pile_bits;
+    sa.tail = out->d_tail ? out->d_tail : (loads ? pol->d_tail : nullptr);
+    sa.tick_base = e->d_tick_base;
+    sa.log_std = pol->d_log_std;
+    sa.normal_icdf = (const float *) e->tb.normal_icdf;
+    sa.normal_tail = (const float *) e->tb.normal_tail;
+    sa.u = out->d_u;
+    sa.logp = out->d_logp;
+    sa.features = out->d_features;
+    sa.key[0] = pol->key[0];
+    sa.key[1] = pol->key[1];
+    sa.tick = e->tick + 1u - e->graph_base;  // the argument the handle's next launch carries: + *tick_base on the device (CHUB_TICK)
+    sa.gid0 = (uint32_t) e->hp.env_id0;
+    sa.G = pol->G;
+    sa.r_row0 = 0;
+    launch_policy_sample(sa, pol->waves, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    if (loads && (out->d_actions || out->d_pile_bits))
+        return chub_load_dispatch_device(e, CHUB_LOAD_FRACTION, pol->d_loads, sa.tail, d_mask, out->d_actions, out->d_pile_bits, stream);
+    return CHUB_OK;
+}
+
+// The closed loop that keeps what a trainer needs: a host loop of the calls the header lists, like chub_policy_run_steps
+int chub_policy_collect(chub_env *e, chub_policy *pol, int mode, const chub_rollout *r, float *d_obs0, int64_t first_step, void *stream) {
+    if (!e || !pol || !r || !d_obs0) return fail(CHUB_ERR_ARG, "null argument");
+    if (pol->env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
+    if (mode != CHUB_PRUN_LOCKSTEP && mode != CHUB_PRUN_AUTORESET) return fail(CHUB_ERR_ARG, "mode: CHUB_PRUN_LOCKSTEP or CHUB_PRUN_AUTORESET");
+    if (!r->d_packed || !r->d_pile_bits || !r->d_tail || !r->d_u || !r->d_logp)
+        return fail(CHUB_ERR_ARG, "chub_policy_collect: d_packed, d_pile_bits, d_tail, d_u and d_logp are required");
+    if (r->T <= 0 || first_step < 0) return fail(CHUB_ERR_ARG, "chub_policy_collect: T >= 1 steps from first_step >= 0");
+    if (mode == CHUB_PRUN_LOCKSTEP && first_step % 96 + r->T > 96)
+        return fail(CHUB_ERR_ARG, "chub_policy_collect: a lock-step rollout stays inside one day (first_step % 96 + T <= 96)");
+    if (mode == CHUB_PRUN_AUTORESET && r->T > 96)
+        return fail(CHUB_ERR_ARG, "chub_policy_collect: T <= 96 (an env finishes at most once, so a row of d_final_obs is written at most once)");
+    if (e->hp.rng_mode == CHUB_RNG_COMPAT)
+        return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_collect runs the Philox modes: COMPAT steps take the caller's normals one by one");
+    if (mode == CHUB_PRUN_AUTORESET && e->tick == 0) return fail(CHUB_ERR_ARG, "step() before reset()");
+    chub_policy_sample_out probe = {};
+    probe.d_logp = r->d_logp;
+    probe.d_pile_bits = r->d_pile_bits;
+    probe.d_tail = r->d_tail;
+    if (const int rc = policy_sample_check(e, pol, d_obs0, e->hp.obs_dim, &probe)) return rc;
+    const size_t N = (size_t) e->hp.n_envs, D = (size_t) e->hp.obs_dim, Wd = (size_t) ((e->hp.S[0] + e->hp.S[1] + 63) / 64);
+    int rc;
+    if (mode == CHUB_PRUN_LOCKSTEP && first_step % 96 == 0 && (rc = chub_reset_device(e, nullptr, nullptr, d_obs0, stream))) return rc;
+    for (int64_t t = 0; t < r->T; t++) {
+        const size_t k = (size_t) t;
+        const float *obs = t ? r->d_packed + (k - 1) * N * (D + 2) : d_obs0;
+        const int64_t ld = t ? (int64_t) D + 2 : (int64_t) D;
+        float *packed = r->d_packed + k * N * (D + 2);
+        chub_policy_sample_out o;
+        o.d_actions = mode == CHUB_PRUN_AUTORESET ? pol->d_rows : nullptr;
+        o.d_pile_bits = r->d_pile_bits + k * N * Wd;
+        o.d_tail = r->d_tail + k * N * 2;
+        o.d_u = r->d_u + k * N * (size_t) pol->G;
+        o.d_logp = r->d_logp + k * N;
+        o.d_features = r->d_features ? r->d_features + k * N * (size_t) pol->F : nullptr;
+        if ((rc = chub_policy_sample_device(e, pol, obs, ld, nullptr, &o, stream))) return rc;
+        if (mode == CHUB_PRUN_LOCKSTEP) rc = chub_step_bits_device_packed(e, o.d_pile_bits, o.d_tail, nullptr, packed, stream);
+        else rc = chub_autoreset_step_device(e, pol->d_rows, nullptr, nullptr, nullptr, packed, r->d_final_obs, stream);
+        if (rc) return rc;
     }
     return CHUB_OK;
 }

@@ -184,6 +184,40 @@ class DevicePolicy(object):
         check(self._lib.chub_policy_run_steps(self._env._h, self._p, _lib._enum_value(_lib.PRUN, mode, "run mode"), blocks, d_reset_obs or None,
                                               d_final_obs or None, int(first_step), int(n_steps), stream or None))
 
+    # ---- sampling (include/chub.h, "sampling from the device actor")
+    @property
+    def n_gaussians(self):
+        """G: the Gaussian outputs, 2 (the tail pair of the piles head) or 4 (the loads head)"""
+        return 2 if self.spec.head == _lib.PHEAD["piles"] else 4
+
+    def set_exploration(self, key, log_std):
+        """the key of the policy's noise (a uint64) and log_std [G] of its Gaussian outputs, from host values; synchronises.  Needed once
+        before sample_device / collect"""
+        ls = np.ascontiguousarray(np.broadcast_to(np.asarray(log_std, dtype=np.float32), (self.n_gaussians,)))
+        check(self._lib.chub_policy_set_exploration(self._p, int(key) & (2 ** 64 - 1), _ptr(ls)))
+
+    def set_log_std_device(self, d_log_std, stream=0):
+        """log_std [G] f32 from device memory (e.g. a parameter's data_ptr()) as a copy on `stream`: a captured graph's next replay
+        samples with it"""
+        check(self._lib.chub_policy_set_log_std_device(self._p, d_log_std, stream or None))
+
+    def sample_device(self, d_obs=0, ld_obs=None, d_logp=0, d_actions=0, d_pile_bits=0, d_tail=0, d_u=0, d_features=0, d_mask=0, stream=0):
+        """one SAMPLED evaluation on `stream` (chub_policy_sample_device): as act_device, with the action drawn from the actor's
+        distribution under the tick of the handle's next launch (VecChargingHub.next_tick), its log-probability in d_logp [N] f32 (required),
+        the pre-squash Gaussian samples in d_u [N, G] and the raw feature row in d_features [N, F].  No tick is consumed."""
+        ld = self._env.obs_dim if ld_obs is None else int(ld_obs)
+        out = _lib.ChubPolicySampleOut(d_actions or None, d_pile_bits or None, d_tail or None, d_u or None, d_logp or None, d_features or None)
+        check(self._lib.chub_policy_sample_device(self._env._h, self._p, d_obs or None, ld, d_mask or None, C.byref(out), stream or None))
+
+    def collect(self, n_steps, d_obs0, d_packed, d_pile_bits, d_tail, d_u, d_logp, d_features=0, d_final_obs=0, first_step=0, mode="lockstep",
+                stream=0):
+        """the closed loop that keeps the trajectory (chub_policy_collect): n_steps sampled steps into [T][N][...] arrays in device memory,
+        the actor reading d_obs0 [N, D] at the first step and the packed block before it afterwards.  Returns after enqueueing."""
+        r = _lib.ChubRollout(int(n_steps), d_packed or None, d_pile_bits or None, d_tail or None, d_u or None, d_logp or None, d_features or None,
+                             d_final_obs or None)
+        check(self._lib.chub_policy_collect(self._env._h, self._p, _lib._enum_value(_lib.PRUN, mode, "run mode"), C.byref(r), d_obs0 or None,
+                                            int(first_step), stream or None))
+
     def close(self):
         if getattr(self, "_p", None) and getattr(self._env, "_h", None):
             check(self._lib.chub_policy_destroy(self._p))
@@ -716,6 +750,13 @@ class VecChargingHub(object):
         param]) with kind "pile_obs" / "station_profile" / "forecast" and fields / param as those calls take them.  normalize: None or
         (mean [F], inv_std [F], clip)."""
         return DevicePolicy(self, layers, inputs, head, hidden_act, squash, normalize)
+
+    def next_tick(self):
+        """the Philox tick of this handle's next reset or step (chub_next_tick): the tick a sampled policy call made now draws its noise
+        under.  Host arithmetic only."""
+        t = C.c_uint32()
+        check(self._lib.chub_next_tick(self._h, C.byref(t)))
+        return t.value
 
     def step_load_device(self, d_actions, d_obs, d_reward, d_done, d_exo_z=0, stream=0):
         """the device-pointer form of step_load (chub_step_load_device): d_actions [N, A] f32 in load_actions' layout"""

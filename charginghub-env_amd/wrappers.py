@@ -249,6 +249,30 @@ class HubVectorEnv(_HubBatch):
             _HubBatch.close(self)
 
 
+def sampled_logp(z, bits_or_on, u, log_std):
+    """The log-probability of recorded actions under a network's outputs, in torch and differentiable in `z` and `log_std`: what a trainer
+    uses for the NEW policy's term of an importance ratio (include/chub.h, "sampling from the device actor"; the old policy's term is the
+    recorded ``logp``).  z [..., S + G]: the last layer's PRE-squash outputs (S pile logits, then the G Gaussian means; G = log_std's
+    length, S may be 0); bits_or_on: the pile decisions as a bool tensor [..., S] or as recorded bit words int64 [..., W]; u [..., G]: the
+    recorded pre-squash samples.  eps = (u - z_gauss) / exp(log_std);
+        logp = sum_b (on_b ? -softplus(-z_b) : -softplus(z_b)) + sum_i (-0.5 eps_i^2 - log_std_i - 0.5 ln 2 pi)
+    The Gaussian part is the density of the pre-squash sample: no tanh Jacobian, which cancels in every ratio."""
+    import math
+
+    import torch
+
+    G = log_std.shape[-1]
+    S = z.shape[-1] - G
+    on = bits_or_on
+    if on.dtype != torch.bool:
+        sh = torch.arange(64, device=on.device, dtype=torch.int64)
+        on = (((on.unsqueeze(-1) >> sh) & 1) != 0).flatten(-2)[..., :S]
+    zp, zg = z[..., :S], z[..., S:]
+    piles = -torch.nn.functional.softplus(torch.where(on, -zp, zp)).sum(dim=-1)
+    eps = (u - zg) / torch.exp(log_std)
+    return piles + (-0.5 * eps * eps - log_std - 0.5 * math.log(2.0 * math.pi)).sum(dim=-1)
+
+
 class TorchHubVecEnv(object):
     """The hub for an on-device learner: actions in and observations / rewards / dones out are torch CUDA tensors, the
     step runs through the device-pointer entry points on torch's current stream, and nothing is copied through the host
@@ -581,6 +605,53 @@ class TorchHubVecEnv(object):
             self._cur_obs = self._packed[:, :D]
             return self._cur_obs, self._packed[:, D], self._packed[:, D + 1] > 0.5, {}
         return self._after_step()
+
+    def collect(self, policy, n_steps):
+        """n_steps SAMPLED closed-loop steps of `policy` (after ``policy.set_exploration``) from the current observation, issued from C on
+        torch's current stream (chub_policy_collect), keeping the trajectory: a dict of CUDA tensors the next call with the same policy and
+        n_steps overwrites --
+            obs0 [N, D]: the observation the first step acted on; packed [T, N, D + 2]: step t's output block, whose observation the actor
+            of step t + 1 read; reward [T, N] and done [T, N] (1.0 / 0.0): views of packed; bits [T, N, W] int64 and tail [T, N, 2]: the
+            actions taken; u [T, N, G]: the pre-squash Gaussian samples; logp [T, N]; features [T, N, F]: the raw feature rows the actor saw.
+        ``sampled_logp`` of the trainer's own forward pass on ``features`` gives the new policy's term of the importance ratio.
+        ``autoreset="per_env"``: every step is the auto-reset step, ``last_obs`` keeps the terminal rows, n_steps <= 96.
+        ``autoreset=True``: the rollout stays inside the batch's day (n_steps <= 96 - steps taken today); one that begins a day begins with
+        the day's reset, made by the call itself (it replaces the one the adapter made), and one that ends a day is followed by the
+        adapter's reset as in ``step``."""
+        torch = self.torch
+        if not self.autoreset:
+            raise RuntimeError("collect needs an auto-reset mode: construct with autoreset=True or 'per_env'")
+        if self._cur_obs is None:
+            raise RuntimeError("collect() before reset()")
+        T = int(n_steps)
+        today = 0 if self.per_env else self._t % 96
+        if not 0 < T <= 96 - today:
+            raise ValueError("n_steps must be 1 .. %d here (a rollout stays inside one day)" % (96 - today))
+        N, D, W = self.num_envs, self.obs_dim, self.vec.bit_words
+        cache = getattr(self, "_rollouts", None)
+        if cache is None:
+            cache = self._rollouts = {}
+        ro = cache.get((id(policy), T))
+        if ro is None:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            ro = cache[(id(policy), T)] = {
+                "obs0": torch.zeros((N, D), **f32), "packed": torch.zeros((T, N, D + 2), **f32),
+                "bits": torch.zeros((T, N, W), dtype=torch.int64, device=self.device), "tail": torch.zeros((T, N, 2), **f32),
+                "u": torch.zeros((T, N, policy.n_gaussians), **f32), "logp": torch.zeros((T, N), **f32),
+                "features": torch.zeros((T, N, policy.n_features), **f32)}
+            ro["reward"], ro["done"] = ro["packed"][:, :, D], ro["packed"][:, :, D + 1]
+        ro["obs0"].copy_(self._cur_obs)
+        policy.collect(T, ro["obs0"].data_ptr(), ro["packed"].data_ptr(), ro["bits"].data_ptr(), ro["tail"].data_ptr(), ro["u"].data_ptr(),
+                       ro["logp"].data_ptr(), d_features=ro["features"].data_ptr(), d_final_obs=self.last_obs.data_ptr() if self.per_env else 0,
+                       first_step=today, mode="autoreset" if self.per_env else "lockstep", stream=self._stream())
+        self._packed.copy_(ro["packed"][T - 1])  # (the block `step` and `rollout` continue from)
+        self._cur_obs = self._packed[:, :D]
+        if not self.per_env:
+            self._t += T
+            if self._t % 96 == 0:
+                self.last_obs = self._cur_obs.clone()
+                self.reset()
+        return ro
 
     def copy_envs(self, src_idx, dst_idx, source=None):
         """env dst_idx[i] becomes a clone of env src_idx[i] of `source` (another TorchHubVecEnv; default: this one), on torch's current

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""Four ways to drive the hub, smallest first (run from the repo root on a machine with an MI355X):
+"""Five ways to drive the hub, smallest first (run from the repo root on a machine with an MI355X):
 
     python examples/quickstart.py
 
 1. the drop-in single env (the reference's class and call pattern, test/env_test.py);
 2. the batched host-pointer API (numpy in / numpy out);
 3. the device-resident API (torch CUDA tensors in / out, no host copies) -- what an on-device learner should use;
-4. a closed-loop day with an actor evaluated by the hub itself (numpy and ctypes only: no torch, no host between the steps).
+4. a closed-loop day with an actor evaluated by the hub itself (numpy and ctypes only: no torch, no host between the steps);
+5. on-policy training data: the hub samples from the actor, and keeps actions, log-probabilities and every step's block on the device.
 """
 import os
 import sys
@@ -146,8 +147,30 @@ def closed_loop(n=4096):
     hub.close()
 
 
+def on_policy_data(n=4096, steps=32):
+    import charginghub_env_amd as chub
+
+    if torch is None:
+        print("5. skipped: torch is not installed")
+        return
+    env = chub.TorchHubVecEnv(n, seed=0, autoreset="per_env", **HUB)
+    D, A = env.obs_dim, env.act_dim
+    net = torch.nn.Sequential(torch.nn.Linear(D, 64), torch.nn.Tanh(), torch.nn.Linear(64, A)).to("cuda")
+    log_std = torch.full((2,), -0.5, device="cuda")
+    policy = env.load_policy(net)
+    policy.set_exploration(key=7, log_std=log_std.cpu().numpy())   # the noise's key and the scale of the two tail actions
+    env.reset()
+    ro = env.collect(policy, steps)                           # sampled actions, their log-probabilities and every step's block, kept
+    new = chub.wrappers.sampled_logp(net(ro["features"]), ro["bits"], ro["u"], log_std)   # the new policy's term, differentiable
+    ratio = torch.exp(new - ro["logp"]).detach()              # (a loss would keep the graph: PPO's clipped surrogate is built on this)
+    print("5. %d envs x %d sampled steps kept on the device: mean reward %.4f, mean log-probability %.2f, importance ratio %.5f .. %.5f"
+          % (n, steps, float(ro["reward"].mean()), float(ro["logp"].mean()), float(ratio.min()), float(ratio.max())))
+    env.close()
+
+
 if __name__ == "__main__":
     single_env()
     batched_host()
     device_resident()
     closed_loop()
+    on_policy_data()

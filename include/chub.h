@@ -797,8 +797,8 @@ int chub_load_dispatch(chub_env *env, int units, const float *loads, const float
  * set_weights between chub_graph_begin and chub_graph_end; a non-OBS block or the LOADS head on a tape handle (as the feature calls); a
  * feature row and hidden layers that do not fit the kernel's 64 KiB of LDS (F rounded up to 2 and the widest odd hidden layer, plus the
  * widest even hidden layer, each rounded up to 32: at most 512 rows together -- F <= 256 always fits).
- * Out of scope: sampling and exploration noise, log-probabilities, a critic, bf16 / f16 weights, recurrent or convolutional actors, the
- * multi-GPU hosts, COMPAT in chub_policy_run_steps. */
+ * Out of scope: a critic (values of all recorded observations are one batched call of the trainer's afterwards: it does not belong in the
+ * loop), bf16 / f16 weights, recurrent or convolutional actors, the multi-GPU hosts, COMPAT in chub_policy_run_steps. */
 enum { CHUB_PIN_OBS = 0, CHUB_PIN_PILE_OBS, CHUB_PIN_STATION_PROFILE, CHUB_PIN_FORECAST, CHUB_PIN_COUNT };
 enum { CHUB_PACT_TANH = 0, CHUB_PACT_RELU, CHUB_PACT_COUNT };
 enum { CHUB_PHEAD_PILES = 0, CHUB_PHEAD_LOADS, CHUB_PHEAD_COUNT };
@@ -828,6 +828,79 @@ int chub_policy_act_device(chub_env *env, chub_policy *pol, const float *d_obs, 
 int chub_policy_act(chub_env *env, chub_policy *pol, const float *obs, float *actions);
 int chub_policy_run_steps(chub_env *env, chub_policy *pol, int mode, float *const *d_packed2, float *d_reset_obs, float *d_final_obs,
                           int64_t first_step, int64_t n_steps, void *stream);
+
+/* ---- sampling from the device actor: exploration noise, log-probabilities, rollouts that keep the trajectory --------------------------
+ * The actor above is deterministic and chub_policy_run_steps keeps nothing.  This section makes on-policy training data in the same
+ * launches: the action is DRAWN from the actor's distribution inside the actor launch, its log-probability is written beside it, and
+ * chub_policy_collect keeps every step's block, action and log-probability where the trainer reads them.  Nothing of a policy's spec
+ * changes: a policy made by chub_policy_create samples once chub_policy_set_exploration has given it a key and a scale.
+ *   The distribution.  z = the last layer's pre-squash outputs, computed exactly as the deterministic actor computes them (same chain, same
+ *     bits).  G = the number of Gaussian outputs:
+ *       CHUB_PHEAD_PILES  outputs 0 .. S-1 are pile LOGITS, outputs S, S+1 the means of the two tail actions: G = 2
+ *       CHUB_PHEAD_LOADS  all four outputs (load0, load1, tail0, tail1) are Gaussian means: G = 4
+ *     Noise is Philox4x32-10 under the POLICY's key (a uint64 split as the env's seed is), counter (block, 15 << 16 | kind, tick, global env
+ *     id): site 15 is no step's.  tick is the Philox tick of the handle's NEXT launch (chub_next_tick: host arithmetic, no device read),
+ *     formed in the kernel as the steps form theirs, so a captured graph's next replay draws new noise as its steps do.  The noise does not
+ *     depend on N, the mask, an env's place in the batch or sharding (env_id0).  Sampling consumes no tick: two sampled calls with no reset
+ *     or step between them give IDENTICAL bits.
+ *       pile b (kind 0): w = word b & 3 of block b >> 2; U = (float) (w >> 8) * 2^-24 (exact); p = 1 / (1 + expf(-z_b)) in f32; on iff U < p
+ *       Gaussian i (kind 1): eps_i = the handle's tabulated normal (the OU draws' function and tables) of word i of block 0;
+ *           u_i = z_i + sigma_i * eps_i, sigma_i = expf(log_std_i), the product and the sum each rounded to f32 (no FMA); action = squash(u_i)
+ *     Log-probability, one f32 per env:
+ *       logp = sum_b (on_b ? -softplus(-z_b) : -softplus(z_b)) + sum_i (-0.5 eps_i^2 - log_std_i - 0.5 ln 2 pi)
+ *     with softplus(x) = max(x, 0) + log1pf(expf(-|x|)).  The Gaussian part is the density of the PRE-squash u: no tanh Jacobian is applied,
+ *     since it is a function of u alone and cancels in every importance ratio.  The order of the sum is unspecified but fixed for a policy (no
+ *     atomics).  Every pile counts, whether it holds a car or not (counting only occupied piles: not done).
+ *     Outputs: action rows get pile entries exactly +1.0f / -1.0f (what the dispatch writes) and the squashed tail; pile bits are zero from bit
+ *     S up; CHUB_PHEAD_LOADS sends the squashed loads through chub_load_dispatch_device as fractions, as the deterministic call does.
+ *   chub_next_tick: the Philox tick of the handle's next reset or step, i.e. the tick a sampled call made now draws under.
+ *   chub_policy_set_exploration: key and log_std [G] from host memory (it copies and synchronises).  The buffer is the policy's, allocated once
+ *       outside the arena: snapshots are unchanged.  chub_policy_set_log_std_device: a copy on `stream` into that buffer: recordable, and a
+ *       captured graph's next replay samples with the new scale, as with chub_policy_set_weights_device.
+ *       The sampled launch needs 4 rows of LDS behind the deterministic launch's two images: a policy whose images leave fewer than 4 of the 512
+ *       rows is refused HERE with CHUB_ERR_UNSUPPORTED (the deterministic fit rule is unchanged, and such a policy still evaluates).
+ *   chub_policy_sample_device: the manners of chub_policy_act_device -- the same feature launches, the same mask semantics (only the named envs'
+ *       rows of EVERY output are written), no tick consumed, no clock, no synchronisation, no allocation; recordable without counting towards a
+ *       graph's even number of resets + steps.  d_logp is required, every other output optional (d_tail is required with d_pile_bits under
+ *       CHUB_PHEAD_PILES).  d_u [N, G] are the pre-squash samples, d_features [N, F] the RAW feature row (before normalisation): what the
+ *       trainer feeds its own network to reproduce z.
+ *   chub_policy_collect: a host loop of the calls below, like chub_policy_run_steps; returns after enqueueing; Philox modes only.  The actor
+ *       at step t reads d_obs0 [N, D] (ld = D) for t = 0 and block t - 1 of d_packed (ld = D + 2) afterwards: no copy.
+ *       CHUB_PRUN_LOCKSTEP: first_step % 96 + T <= 96.  If first_step % 96 == 0 it begins with chub_reset_device into d_obs0.  Per step
+ *           chub_policy_sample_device straight into the rollout's d_pile_bits[t], d_tail[t], d_u[t], d_logp[t], d_features[t], then
+ *           chub_step_bits_device_packed from those into d_packed[t].
+ *       CHUB_PRUN_AUTORESET: T <= 96 (an env finishes at most once, so each row of d_final_obs is written at most once); the handle must have
+ *           been reset.  Per step the sample goes into the policy's own action rows AND the rollout's bits, tail, u, logp and features, then
+ *           chub_autoreset_step_device into d_packed[t] with d_final_obs.
+ * Refusals, with a message and before any device work.  CHUB_ERR_ARG: null env, policy, out, d_logp, d_obs0 or required rollout arrays; T <= 0;
+ * the day and T rules above; a policy of another handle; sampling before chub_policy_set_exploration; a log_std that is not finite; the
+ * observation rules of chub_policy_act_device.  CHUB_ERR_UNSUPPORTED: chub_policy_set_exploration between chub_graph_begin and
+ * chub_graph_end; the LDS rule above; COMPAT in chub_policy_collect; the tape rules of chub_policy_act_device. */
+int chub_next_tick(const chub_env *env, uint32_t *out);
+int chub_policy_set_exploration(chub_policy *pol, uint64_t key, const float *log_std /* host [G] */);
+int chub_policy_set_log_std_device(chub_policy *pol, const float *d_log_std /* [G] */, void *stream);
+typedef struct chub_policy_sample_out {
+    float *d_actions;       /* [N][A] or NULL */
+    uint64_t *d_pile_bits;  /* [N][W] or NULL */
+    float *d_tail;          /* [N][2]: squashed tail pair; required with d_pile_bits */
+    float *d_u;             /* [N][G] or NULL: the pre-squash Gaussian samples */
+    float *d_logp;          /* [N], required */
+    float *d_features;      /* [N][F] or NULL: the RAW feature row, before normalisation */
+} chub_policy_sample_out;
+int chub_policy_sample_device(chub_env *env, chub_policy *pol, const float *d_obs, int64_t ld_obs, const uint8_t *d_mask,
+                              const chub_policy_sample_out *out, void *stream);
+typedef struct chub_rollout {
+    int64_t T;
+    float *d_packed;        /* [T][N][D + 2]: block t = the packed output of step t */
+    uint64_t *d_pile_bits;  /* [T][N][W] */
+    float *d_tail;          /* [T][N][2] */
+    float *d_u;             /* [T][N][G] */
+    float *d_logp;          /* [T][N] */
+    float *d_features;      /* [T][N][F] or NULL */
+    float *d_final_obs;     /* [N][D] or NULL (AUTORESET only) */
+} chub_rollout;
+int chub_policy_collect(chub_env *env, chub_policy *pol, int mode, const chub_rollout *r, float *d_obs0 /* [N][D] */,
+                        int64_t first_step, void *stream);
 
 /* The FCEV waiting list is unbounded as in the reference (HYD:264-265): the entries a list that still gets served can
  * hold are kept one by one, and once no prefix of it fits into 15 minutes any more (HYD:270-276: nobody is served again

@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
-"""The device actor (chub_policy_*) on a device-resident PHILOX handle, three measurements on ONE build in one process:
-  launch       us per chub_policy_act_device (bits + tail out), CALLS launches between two HIP events;
-  closed_loop  env-steps/s of chub_policy_run_steps (lock-step mode: reset, then per step the actor and the bits-form step) over ten days;
-  open_loop    the same for chub_run_steps with its open-loop random action batches.
+"""The device actor (chub_policy_*) on a device-resident PHILOX handle, five measurements on ONE build in one process:
+  launch          us per chub_policy_act_device (bits + tail out), CALLS launches between two HIP events;
+  closed_loop     env-steps/s of chub_policy_run_steps (lock-step mode: reset, then per step the actor and the bits-form step) over ten days;
+  open_loop       the same for chub_run_steps with its open-loop random action batches;
+  sampled_launch  us per chub_policy_sample_device (bits + tail + u + logp out), as `launch`;
+  collect         env-steps/s of chub_policy_collect in lock-step mode, ten calls of one day each, every step's block and action kept.
 Every case is warmed up, then the cases alternate, ROUNDS times; median, best and worst round are reported with the build id.
---open-loop-only measures the last case alone: with CHUB_LIB=<another build's libchub.so> that is the open-loop rate of a build without
-the actor (the parent commit), on the same device, for the comparison against run-to-run noise.
+--open-loop-only measures the open loop alone, --launch-only the open loop and the deterministic launch: with
+CHUB_LIB=<another build's libchub.so> those are the rates of a build without the newer entry points (the parent commit), on the same
+device; run in alternating processes with this build's they show what the run-to-run spread is.
     python tools/policy_rate.py [--shape 65536x20,25] [--hidden 64,64] [--rounds 7] [--calls 200] [--days 10] [--out profiles/policy_rate.json]"""
 import argparse
 import ctypes
@@ -31,6 +34,7 @@ def main():
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--days", type=int, default=10)
     ap.add_argument("--open-loop-only", action="store_true")
+    ap.add_argument("--launch-only", action="store_true")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     n_s, piles_s = args.shape.split("x")
@@ -101,7 +105,32 @@ def main():
             return n * steps / (time.perf_counter() - t0)
 
         cases[("launch", "chub_policy_act_device", "us_per_launch")] = launch
-        cases[("closed_loop", "chub_policy_run_steps", "env_steps_per_s")] = closed_loop
+        if not args.launch_only:
+            cases[("closed_loop", "chub_policy_run_steps", "env_steps_per_s")] = closed_loop
+            # the SAMPLED actor: one launch with bits + tail + u + logp out, and chub_policy_collect in lock-step mode, a day per call
+            pol.set_exploration(2024, np.array([-0.5, -0.5], dtype=np.float32))
+            W = v.bit_words
+            roll = dict(packed=multi_gpu.DeviceBuffer(96 * n * (D + 2) * 4), bits=multi_gpu.DeviceBuffer(96 * n * W * 8),
+                        tail=multi_gpu.DeviceBuffer(96 * n * 2 * 4), u=multi_gpu.DeviceBuffer(96 * n * 2 * 4), logp=multi_gpu.DeviceBuffer(96 * n * 4))
+
+            def sampled_launch():
+                def many():
+                    for _ in range(args.calls):
+                        pol.sample_device(packed[1].ptr, D + 2, d_logp=roll["logp"].ptr, d_pile_bits=bits.ptr, d_tail=tail.ptr, d_u=roll["u"].ptr,
+                                          stream=stream)
+                return between_events(many) * 1e3 / args.calls
+
+            def collect():
+                st.sync()
+                t0 = time.perf_counter()
+                for _ in range(args.days):
+                    pol.collect(96, obs0.ptr, roll["packed"].ptr, roll["bits"].ptr, roll["tail"].ptr, roll["u"].ptr, roll["logp"].ptr,
+                                mode="lockstep", stream=stream)
+                st.sync()
+                return n * steps / (time.perf_counter() - t0)
+
+            cases[("sampled_launch", "chub_policy_sample_device", "us_per_launch")] = sampled_launch
+            cases[("collect", "chub_policy_collect", "env_steps_per_s")] = collect
 
     for fn in cases.values():  # warm-up (the open loop first: it leaves real observations in the packed blocks)
         fn()
