@@ -208,6 +208,22 @@ class ChubRollout(C.Structure):
                 ("d_logp", C.c_void_p), ("d_features", C.c_void_p), ("d_final_obs", C.c_void_p)]
 
 
+class ChubGae(C.Structure):
+    """chub_gae of include/chub.h: T, the device addresses of a rollout's blocks and the values, the two factors, the outputs"""
+    _fields_ = [("T", C.c_int64), ("d_packed", C.c_void_p), ("d_values", C.c_void_p), ("d_final_values", C.c_void_p), ("d_mask", C.c_void_p),
+                ("gamma", C.c_float), ("lam", C.c_float), ("d_adv", C.c_void_p), ("d_ret", C.c_void_p), ("d_stats", C.c_void_p)]
+
+
+# pile sets (chub_pile_set_device): the CHUB_PSET_* enum of include/chub.h, in order
+PSET_NAMES = ("all", "occupied", "decidable")
+PSET = {name: i for i, name in enumerate(PSET_NAMES)}
+
+
+def pile_set(which):
+    """a pile set as its CHUB_PSET_* value: a name of PSET_NAMES, or the value itself (the library refuses an unknown one)"""
+    return _enum_value(PSET, which, "pile set")
+
+
 def _enum_value(table, value, what):
     if isinstance(value, str):
         if value not in table:
@@ -397,6 +413,10 @@ def load_library():
         "chub_policy_set_log_std_device": (I, [P, P, P]),
         "chub_policy_sample_device": (I, [P, P, P, L, P, C.POINTER(ChubPolicySampleOut), P]),
         "chub_policy_collect": (I, [P, P, I, C.POINTER(ChubRollout), P, L, P]),
+        "chub_pile_set_device": (I, [P, I, P, P, P]),
+        "chub_policy_sample_set_device": (I, [P, P, P, L, P, I, P, C.POINTER(ChubPolicySampleOut), P]),
+        "chub_policy_collect_set": (I, [P, P, I, I, C.POINTER(ChubRollout), P, P, L, P]),
+        "chub_rollout_gae_device": (I, [P, C.POINTER(ChubGae), P]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -433,7 +453,8 @@ EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "ch
             "chub_get_step_terms_size", "chub_get_step_terms_device", "chub_get_step_terms", "chub_set_step_terms", "chub_get_step_terms_attached",
             "chub_policy_input_width", "chub_policy_create", "chub_policy_destroy", "chub_policy_set_weights", "chub_policy_set_weights_device",
             "chub_policy_act_device", "chub_policy_act", "chub_policy_run_steps",
-            "chub_next_tick", "chub_policy_set_exploration", "chub_policy_set_log_std_device", "chub_policy_sample_device", "chub_policy_collect"]
+            "chub_next_tick", "chub_policy_set_exploration", "chub_policy_set_log_std_device", "chub_policy_sample_device", "chub_policy_collect",
+            "chub_pile_set_device", "chub_policy_sample_set_device", "chub_policy_collect_set", "chub_rollout_gae_device"]
 
 
 def check(rc):

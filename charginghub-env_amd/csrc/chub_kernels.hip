@@ -4658,6 +4658,65 @@ void launch_pile_obs(const HubParams &hp, const DevCtx *ctx, uint32_t fields, co
     }
 }
 
+// -------------------------------------------------------------------- pile sets (chub_pile_set_device)
+// Which piles' action bits can matter to the next step, as chub_step_bits' words: out[env][W] u64, bit b = hub slot b, bits from S up zero.
+// The values are pile_decode's, i.e. k_pile_obs' car and emergency columns: PSET_OCCUPIED asks it for the car alone (the state word),
+// PSET_DECIDABLE for the emergency too (judge_feasibility's own predicate, CHS:1404-1413: no car -> forced off, emergency >= 1.01 -> forced
+// on), PSET_ALL loads nothing.  A workgroup takes E = max(1, 256 / S) whole envs, one lane per pile (a station of more than 256 piles: the
+// lanes stride); the envs' words are assembled in LDS by atomicOr and stored whole, consecutive lanes on consecutive words: no global atomics.
+enum PileSet : int { PSET_ALL = 0, PSET_OCCUPIED, PSET_DECIDABLE, PSET_COUNT };
+constexpr int kPileSetLanes = 256;
+constexpr int kPileSetLdsWords = 2 * (kPileSetLanes + 4);  // u32 words of E envs: E * 2 W <= 2 (256 / S) (S / 64 + 1) <= 8 + 512 / S for S <= 256, 2 W <= 256 beyond
+struct PileSetArgs {
+    const DevCtx *ctx;
+    const uint8_t *mask;   // [N] or null: rows of envs whose byte is 0 are not written
+    uint32_t *out;         // [N][2 W] u32 = [N][W] u64, little-endian halves
+    int which;             // PileSet
+    int envs;              // E: envs per workgroup
+};
+template <int LAYOUT>
+__global__ __launch_bounds__(kPileSetLanes) void k_pile_set(const PileSetArgs a) {
+    __shared__ uint32_t words[kPileSetLdsWords];
+    const DevCtx *__restrict__ ctx = a.ctx;
+    const HubParams &hp = ctx->hp;
+    const Tables &tb = ctx->tb;
+    const int S0 = hp.S[0], S = S0 + hp.S[1], W2 = 2 * ((S + 63) >> 6), E = a.envs;
+    const int tid = (int) threadIdx.x;
+    const int64_t env0 = (int64_t) blockIdx.x * E;
+    const uint32_t fields = a.which == PSET_DECIDABLE ? (PF_CAR | PF_EMERGENCY) : PF_CAR;
+    for (int w = tid; w < E * W2; w += kPileSetLanes) words[w] = 0u;
+    __syncthreads();
+    for (int idx = tid; idx < E * S; idx += kPileSetLanes) {
+        const int j = idx / S, slot = idx - j * S;
+        const int64_t env = env0 + j;
+        if (env >= hp.n_envs || (a.mask && !a.mask[env])) continue;
+        bool in = true;
+        if (a.which != PSET_ALL) {
+            const PileVals p = pile_decode<LAYOUT>(ctx, nullptr, fields, env, slot, env * S + slot);
+            in = p.left > 0;
+            if (in && a.which == PSET_DECIDABLE) in = emergency_of(tb.ttab[slot >= S0 ? 1 : 0][p.lev], p.t_soc, p.left) < 1.01f;
+        }
+        if (in) atomicOr(&words[j * W2 + (slot >> 5)], 1u << (slot & 31));
+    }
+    __syncthreads();
+    for (int w = tid; w < E * W2; w += kPileSetLanes) {
+        const int64_t env = env0 + w / W2;
+        if (env < hp.n_envs && (!a.mask || a.mask[env])) a.out[env0 * W2 + w] = words[w];
+    }
+}
+void launch_pile_set(const HubParams &hp, const DevCtx *ctx, int which, const uint8_t *d_mask, uint64_t *d_bits, hipStream_t stream) {
+    const int S = hp.S[0] + hp.S[1];
+    if (hp.n_envs <= 0 || S <= 0) return;
+    const int E = S >= kPileSetLanes ? 1 : kPileSetLanes / S;
+    const int64_t nb = (hp.n_envs + E - 1) / E;
+    const PileSetArgs a = {ctx, d_mask, (uint32_t *) d_bits, which, E};
+    switch (slot_layout(hp)) {
+    case LAYOUT_COMPAT: hipLaunchKernelGGL(k_pile_set<LAYOUT_COMPAT>, dim3((unsigned) nb), dim3(kPileSetLanes), 0, stream, a); break;
+    case LAYOUT_CURVES: hipLaunchKernelGGL(k_pile_set<LAYOUT_CURVES>, dim3((unsigned) nb), dim3(kPileSetLanes), 0, stream, a); break;
+    default: hipLaunchKernelGGL(k_pile_set<LAYOUT_PHILOX>, dim3((unsigned) nb), dim3(kPileSetLanes), 0, stream, a); break;
+    }
+}
+
 // -------------------------------------------------------------------- exogenous look-ahead (chub_forecast_device)
 // What is deterministic about the next H slots of an env's day, as columns: out[env][column][h], the columns of the field mask in ascending
 // order (FcField), h = 0 the slot the env's next step simulates.  Lane = one float of the flat [N][C][H] range, so a wave stores runs of

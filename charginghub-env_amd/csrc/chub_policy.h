@@ -48,6 +48,7 @@ struct PolicyBlock {
 
 struct PolicyArgs {
     static constexpr bool kSample = false;
+    static constexpr bool kSet = false;
     int64_t n_envs;
     PolicyBlock in[kPolicyMaxInputs];
     PolicyLayer layer[kPolicyMaxLayers];
@@ -79,8 +80,32 @@ struct PolicySampleArgs : PolicyArgs {
     int32_t r_row0;               // first of the kPolicyLogpRows LDS rows of the log-probability partials
 };
 
+// the sampled instantiation whose log-probability counts a pile's Bernoulli term only where the pile's bit is in a set (include/chub.h,
+// "pile sets"): the u32 word t of an env's set is exactly the 32 outputs of accumulator tile t.  Everything else is PolicySampleArgs' launch
+struct PolicySampleSetArgs : PolicySampleArgs {
+    static constexpr bool kSet = true;
+    const uint32_t *set;          // [N][2 W] u32 = [N][W] u64, little-endian halves: chub_pile_set_device's words
+};
+
 void launch_policy(const PolicyArgs &a, int waves, hipStream_t stream);
 void launch_policy_sample(const PolicySampleArgs &a, int waves, hipStream_t stream);
+void launch_policy_sample_set(const PolicySampleSetArgs &a, int waves, hipStream_t stream);
+
+// generalised advantage estimation over a rollout's blocks (include/chub.h, chub_rollout_gae_device)
+struct GaeArgs {
+    int64_t n_envs, T;
+    int32_t D;                    // reward at column D, done at D + 1 of a packed row of D + 2
+    float gamma, gl;              // gl = gamma * lambda, formed once in f32
+    const float *packed;          // [T][N][D + 2]
+    const float *values;          // [T + 1][N]
+    const float *final_values;    // [N] or null
+    const uint8_t *mask;          // [N] or null
+    float *adv, *ret;             // [T][N]; ret may be null
+    double *partials;             // [blocks][3] or null: count, sum, sum of squares per workgroup
+    double *stats;                // [3] or null
+};
+constexpr int kGaeLanes = 256;
+void launch_gae(const GaeArgs &a, hipStream_t stream);
 // W [out][in] row-major and b [out] in device memory -> the layout above
 void launch_policy_relayout(const float *d_W, const float *d_b, float *d_w, float *d_bias, int out, int in, int k_pad, int tiles, hipStream_t stream);
 

@@ -79,10 +79,13 @@ constexpr float kHalfLn2Pi = 0.918938533204672742f;  // 0.5 ln 2 pi
 __device__ __forceinline__ float policy_softplus(float x) { return __fadd_rn(fmaxf(x, 0.0f), log1pf(expf(-fabsf(x)))); }
 
 // Args = PolicyArgs: the deterministic actor.  Args = PolicySampleArgs: the same chain to the pre-squash outputs z, then a draw from the
-// actor's distribution, its log-probability and (if asked for) the raw feature row.
+// actor's distribution, its log-probability and (if asked for) the raw feature row.  Args = PolicySampleSetArgs: the sampled launch with a
+// pile's Bernoulli term added to the log-probability only where the pile's bit is in the env's set (one u32 word per accumulator tile); the
+// draws, the outputs and the order of the terms that remain are the sampled launch's.
 template <typename Args>
 __global__ __launch_bounds__(64 * kPolicyMaxWaves) void k_policy(const Args a) {
     constexpr bool kSample = Args::kSample;
+    [[maybe_unused]] constexpr bool kSet = Args::kSet;
     extern __shared__ float lds[];
     const int tid = (int) threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = (int) (blockDim.x >> 6), nt = (int) blockDim.x;
     const int col = lane & 31, half = lane >> 5;
@@ -154,6 +157,10 @@ __global__ __launch_bounds__(64 * kPolicyMaxWaves) void k_policy(const Args a) {
                     const bool piles = a.head == PHEAD_PILES;
                     const int g0 = piles ? a.S : 0;  // output g0 + i is Gaussian i
                     uint32_t m = 0u;
+                    [[maybe_unused]] uint32_t in_set = 0u;  // (a pile set) the env's word of this tile: the piles whose terms count
+                    if constexpr (kSet) {
+                        if (piles && t < 2 * a.W && env < a.n_envs) in_set = a.set[env * (int64_t) (2 * a.W) + t];
+                    }
 #pragma unroll
                     for (int q = 0; q < 4; q++) {
                         // registers 4 q .. 4 q + 3 are four consecutive rows from a multiple of 4: the four words of one pile block
@@ -169,7 +176,11 @@ __global__ __launch_bounds__(64 * kPolicyMaxWaves) void k_policy(const Args a) {
                                 const float U = (float) (pb.v[j] >> 8) * 5.9604644775390625e-8f;  // 2^-24: exact
                                 const float p = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-z)));
                                 const bool on = U < p;
-                                logp = __fsub_rn(logp, policy_softplus(on ? -z : z));
+                                if constexpr (kSet) {
+                                    if ((in_set >> (n & 31)) & 1u) logp = __fsub_rn(logp, policy_softplus(on ? -z : z));
+                                } else {
+                                    logp = __fsub_rn(logp, policy_softplus(on ? -z : z));
+                                }
                                 if (on) m |= 1u << (n & 31);
                                 if (store && a.actions) a.actions[env * a.A + n] = on ? 1.0f : -1.0f;
                             } else if (i >= 0 && i < a.G) {
@@ -262,6 +273,108 @@ void launch_policy_sample(const PolicySampleArgs &a, int waves, hipStream_t stre
     s.r_row0 = a.q_row0 + policy_q_rows(a);
     const size_t lds_bytes = (size_t) (s.r_row0 + kPolicyLogpRows) * kPolicyEnvTile * sizeof(float);
     hipLaunchKernelGGL(k_policy<PolicySampleArgs>, dim3((unsigned) nb), dim3(64u * (unsigned) waves), lds_bytes, stream, s);
+}
+
+void launch_policy_sample_set(const PolicySampleSetArgs &a, int waves, hipStream_t stream) {
+    if (a.n_envs <= 0) return;
+    const int64_t nb = (a.n_envs + kPolicyEnvTile - 1) / kPolicyEnvTile;
+    PolicySampleSetArgs s = a;
+    s.r_row0 = a.q_row0 + policy_q_rows(a);
+    const size_t lds_bytes = (size_t) (s.r_row0 + kPolicyLogpRows) * kPolicyEnvTile * sizeof(float);
+    hipLaunchKernelGGL(k_policy<PolicySampleSetArgs>, dim3((unsigned) nb), dim3(64u * (unsigned) waves), lds_bytes, stream, s);
+}
+
+// ---- generalised advantage estimation over a rollout's blocks (include/chub.h, chub_rollout_gae_device).  One lane per env, consecutive
+// lanes on consecutive envs: V, adv and ret are coalesced rows of [t][N]; reward and done are the last two floats of a packed row, fetched as
+// one 8-byte load (4-byte aligned: a row is D + 2 floats).  Only the adv recurrence is serial in t, so the loads of kGaeAhead steps are
+// issued before the chain that consumes them.  Every operation is rounded once (no contraction): a numpy f32 restatement gives the same bits.
+// Statistics: a lane sums its env's advantages and their squares in f64 in the order it writes them, the workgroup's lanes meet in a fixed
+// LDS tree, the workgroups' partials are summed by ONE workgroup of a second launch in a fixed order: no atomics, the same bits every call.
+constexpr int kGaeAhead = 8;
+struct __attribute__((packed, aligned(4))) GaeRewardDone {
+    float r, d;
+};
+
+__device__ __forceinline__ void gae_block_sum(double (*red)[kGaeLanes], int tid, double &c, double &s, double &q) {
+    red[0][tid] = c; red[1][tid] = s; red[2][tid] = q;
+    __syncthreads();
+    for (int h = kGaeLanes / 2; h > 0; h >>= 1) {
+        if (tid < h) {
+#pragma unroll
+            for (int i = 0; i < 3; i++) red[i][tid] += red[i][tid + h];
+        }
+        __syncthreads();
+    }
+    c = red[0][0]; s = red[1][0]; q = red[2][0];
+}
+
+__global__ __launch_bounds__(kGaeLanes) void k_gae(const GaeArgs a) {
+    __shared__ double red[3][kGaeLanes];
+    const int tid = (int) threadIdx.x;
+    const int64_t e = (int64_t) blockIdx.x * kGaeLanes + tid, N = a.n_envs;
+    const bool live = e < N && (!a.mask || a.mask[e] != 0);
+    double cnt = 0.0, sum = 0.0, sq = 0.0;
+    if (live) {
+        const int64_t row = (int64_t) a.D + 2;
+        const float fin = a.final_values ? a.final_values[e] : 0.0f;
+        float v_next = a.values[a.T * N + e], adv = 0.0f;
+        for (int64_t t1 = a.T; t1 > 0; t1 -= kGaeAhead) {
+            float v[kGaeAhead];
+            GaeRewardDone rd[kGaeAhead];
+#pragma unroll
+            for (int k = 0; k < kGaeAhead; k++) {
+                const int64_t t = t1 - 1 - k;
+                if (t >= 0) {
+                    v[k] = a.values[t * N + e];
+                    rd[k] = *(const GaeRewardDone *) (a.packed + (t * N + e) * row + a.D);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < kGaeAhead; k++) {
+                const int64_t t = t1 - 1 - k;
+                if (t >= 0) {
+                    const bool done = rd[k].d != 0.0f;
+                    const float vn = done ? fin : v_next;
+                    const float delta = __fsub_rn(__fadd_rn(rd[k].r, __fmul_rn(a.gamma, vn)), v[k]);
+                    adv = __fadd_rn(delta, __fmul_rn(a.gl, done ? 0.0f : adv));
+                    a.adv[t * N + e] = adv;
+                    if (a.ret) a.ret[t * N + e] = __fadd_rn(adv, v[k]);
+                    sum += (double) adv;
+                    sq += (double) adv * (double) adv;
+                    v_next = v[k];
+                }
+            }
+        }
+        cnt = (double) a.T;
+    }
+    if (a.partials) {
+        gae_block_sum(red, tid, cnt, sum, sq);
+        if (tid == 0) {
+            double *p = a.partials + (size_t) blockIdx.x * 3;
+            p[0] = cnt; p[1] = sum; p[2] = sq;
+        }
+    }
+}
+
+// the workgroups' partials in ONE workgroup: lane l takes partials l, l + 256, .. in ascending order, then the same LDS tree
+__global__ __launch_bounds__(kGaeLanes) void k_gae_stats(const double *partials, int64_t blocks, double *stats) {
+    __shared__ double red[3][kGaeLanes];
+    const int tid = (int) threadIdx.x;
+    double c = 0.0, s = 0.0, q = 0.0;
+    for (int64_t b = tid; b < blocks; b += kGaeLanes) {
+        c += partials[b * 3]; s += partials[b * 3 + 1]; q += partials[b * 3 + 2];
+    }
+    gae_block_sum(red, tid, c, s, q);
+    if (tid == 0) {
+        stats[0] = c; stats[1] = s; stats[2] = q;
+    }
+}
+
+void launch_gae(const GaeArgs &a, hipStream_t stream) {
+    if (a.n_envs <= 0) return;
+    const int64_t nb = (a.n_envs + kGaeLanes - 1) / kGaeLanes;
+    hipLaunchKernelGGL(k_gae, dim3((unsigned) nb), dim3(kGaeLanes), 0, stream, a);
+    if (a.partials && a.stats) hipLaunchKernelGGL(k_gae_stats, dim3(1), dim3(kGaeLanes), 0, stream, (const double *) a.partials, nb, a.stats);
 }
 
 // the trainer's layout (nn.Linear: W [out][in] row-major, b [out]) -> the kernel's (chub_policy.h), zeros beyond `out` and `in`

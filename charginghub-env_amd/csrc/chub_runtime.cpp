@@ -27,6 +27,7 @@ void launch_check_ttab(const DevCtx *ctx, uint32_t *d_mismatch, hipStream_t stre
 void launch_build_cls_soc(const DevCtx *ctx, float *d_out, hipStream_t stream);
 void launch_pile_obs(const HubParams &hp, const DevCtx *ctx, uint32_t fields, const uint8_t *d_mask, const float *d_cls_soc, float *d_out,
                      hipStream_t stream);
+void launch_pile_set(const HubParams &hp, const DevCtx *ctx, int which, const uint8_t *d_mask, uint64_t *d_bits, hipStream_t stream);
 void launch_station_profile(const HubParams &hp, const DevCtx *ctx, uint32_t fields, int buckets, const uint8_t *d_mask, const float *d_cls_soc,
                             float *d_out, hipStream_t stream);
 void launch_load_dispatch(const HubParams &hp, const DevCtx *ctx, int units, const uint8_t *d_mask, const float *d_cls_soc, const float *d_loads,
@@ -173,6 +174,9 @@ struct chub_env {
     uint32_t st_fields = 0;
     // the actors made for this handle (chub_policy_create): destroyed before it.  Everything they own lies outside the arena
     std::vector<chub_policy *> policies;
+    // chub_rollout_gae_device's statistics: the workgroups' partials [ceil(N / 256)][3] f64, allocated at create outside the arena (derived
+    // scratch: no snapshot carries it).  One buffer: calls that ask for d_stats must be ordered against each other
+    double *d_gae_part = nullptr;
     double *d_ep_sum = nullptr;  // k_episode_summary's partials [kEpSumMaxBlocks][kEpSumWords], then the host form's result [kEpSumWords]
     int public_mode = 0;     // the rng_mode the handle was created with: CHUB_RNG_PHILOX_CURVES is hp.rng_mode = PHILOX + hp.soc_curves
     bool tape_only = false;  // ... and once there are any, the handle's class rows are the caller's: only tape resets / steps may admit cars
@@ -1039,6 +1043,10 @@ static int create_impl(const chub_config *cfg_in, const char *data_dir, int64_t 
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess)
             return bail(fail(CHUB_ERR_HIP, "the SoC table of the arrival classes could not be built on the device"));
     }
+    if (hipMalloc((void **) &e->d_gae_part, (size_t) ((n_envs + kGaeLanes - 1) / kGaeLanes) * 3 * sizeof(double)) != hipSuccess) {
+        e->d_gae_part = nullptr;
+        return bail(fail(CHUB_ERR_HIP, "hipMalloc failed"));
+    }
     *out = e;
     return CHUB_OK;
 }
@@ -1064,6 +1072,7 @@ int chub_destroy(chub_env *e) {
         if (e->d_cls_soc) (void) hipFree(e->d_cls_soc);
         if (e->fc.mean) (void) hipFree((void *) e->fc.mean);
         if (e->d_ep_sum) (void) hipFree(e->d_ep_sum);
+        if (e->d_gae_part) (void) hipFree(e->d_gae_part);
         if (e->h_bits) (void) hipHostFree(e->h_bits);  // h_tail / d_tail are the ends of the same blocks
         if (e->d_bits) (void) hipFree(e->d_bits);
         if (e->d_packed) (void) hipFree(e->d_packed);
@@ -2666,6 +2675,26 @@ int chub_pile_obs_device(chub_env *e, uint32_t fields, const uint8_t *d_mask, fl
     return CHUB_OK;
 }
 
+// ---- pile sets (include/chub.h): which piles' action bits the next step can see, as chub_step_bits' words
+static int pile_set_check(const chub_env *e, int which, const char *who) {
+    if (which < 0 || which >= CHUB_PSET_COUNT)
+        return fail(CHUB_ERR_ARG, std::string(who) + ": which is CHUB_PSET_ALL, CHUB_PSET_OCCUPIED or CHUB_PSET_DECIDABLE");
+    if (e->tape_only)
+        return fail(CHUB_ERR_UNSUPPORTED, std::string(who) + " is not supported on a tape handle (chub_tape_register_soc rewrites the class tables)");
+    return CHUB_OK;
+}
+
+int chub_pile_set_device(chub_env *e, int which, const uint8_t *d_mask, uint64_t *d_bits, void *stream) {
+    if (!e || !d_bits) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = pile_set_check(e, which, "chub_pile_set_device")) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    if (const int rc = sync_ctx(e, (hipStream_t) stream)) return rc;  // (nothing to do inside a capture: chub_graph_begin has done it)
+    launch_pile_set(e->hp, e->d_ctx, which, d_mask, d_bits, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
 int chub_station_profile_size(uint32_t fields, int32_t buckets) {
     if (fields == 0u || (fields >> CHUB_SP_COUNT) != 0u) return fail(CHUB_ERR_ARG, "fields: a non-empty mask over the CHUB_SP_* fields");
     if (buckets < 1 || buckets > 32) return fail(CHUB_ERR_ARG, "buckets: 1 .. 32");
@@ -3445,6 +3474,7 @@ struct chub_policy {
     float *d_loads, *d_tail;                // [N][2] each: the LOADS head's outputs; the run loop's tail pair
     uint64_t *d_bits;                       // [N][W]: the run loop's pile bits
     float *d_rows;                          // [N][S + 2]: the run loop's action rows (CHUB_PRUN_AUTORESET)
+    uint64_t *d_set;                        // [N][W]: the pile set of a set-aware sampled call that names no buffer of its own
     // sampling (chub_policy_set_exploration): the key of the policy's noise and the Gaussian outputs' log_std [G] (allocated once, never moves)
     int32_t lds_rows, G;                    // rows of the two LDS images; Gaussian outputs (2 PILES, 4 LOADS)
     bool explore;
@@ -3633,6 +3663,7 @@ int chub_policy_create(chub_env *e, const chub_policy_spec *spec, const float *c
     if (!rc) rc = policy_alloc(pol, &pol->d_tail, 2 * N);
     if (!rc) rc = policy_alloc(pol, &pol->d_bits, N * (size_t) Wd);
     if (!rc) rc = policy_alloc(pol, &pol->d_rows, N * (size_t) (S + 2));
+    if (!rc) rc = policy_alloc(pol, &pol->d_set, N * (size_t) Wd);
     if (!rc && spec->normalize) {
         pa.mean = pol->d_norm;
         pa.inv_std = pol->d_norm + ps.F;
@@ -3856,13 +3887,28 @@ static int policy_sample_check(chub_env *e, chub_policy *pol, const float *d_obs
     return policy_check_tape(e, pol);
 }
 
-int chub_policy_sample_device(chub_env *e, chub_policy *pol, const float *d_obs, int64_t ld_obs, const uint8_t *d_mask,
-                              const chub_policy_sample_out *out, void *stream) {
-    if (const int rc = policy_sample_check(e, pol, d_obs, ld_obs, out)) return rc;
+// what the set-aware calls refuse on top, with nothing enqueued yet (after policy_sample_check: pol and e are good)
+static int policy_set_check(const chub_env *e, const chub_policy *pol, int which, const char *who) {
+    if (const int rc = pile_set_check(e, which, who)) return rc;
+    if (which != CHUB_PSET_ALL && pol->spec.head == CHUB_PHEAD_LOADS)
+        return fail(CHUB_ERR_ARG, std::string(who) + ": under CHUB_PHEAD_LOADS the log-probability has no pile terms: which must be CHUB_PSET_ALL");
+    return CHUB_OK;
+}
+
+// one sampled evaluation, checked by the caller.  which < 0: chub_policy_sample_device's launches; else the pile set launch in front, with the
+// same mask, and the set-aware actor launch
+static int policy_sample_enqueue(chub_env *e, chub_policy *pol, const float *d_obs, int64_t ld_obs, const uint8_t *d_mask, int which,
+                                 uint64_t *d_set_bits, const chub_policy_sample_out *out, void *stream) {
     HIP_TRY(hipSetDevice(e->device));
     (void) hipGetLastError();
-    PolicySampleArgs sa;
+    PolicySampleSetArgs sa;
     static_cast<PolicyArgs &>(sa) = pol->pa;
+    sa.set = nullptr;
+    if (which >= 0) {
+        uint64_t *set = d_set_bits ? d_set_bits : pol->d_set;
+        if (const int rc = chub_pile_set_device(e, which, d_mask, set, stream)) return rc;
+        sa.set = (const uint32_t *) set;
+    }
     if (const int rc = policy_feature_blocks(e, pol, d_obs, ld_obs, d_mask, sa, stream)) return rc;
     const bool loads = pol->spec.head == CHUB_PHEAD_LOADS;
     sa.mask = d_mask;
@@ -3882,16 +3928,32 @@ int chub_policy_sample_device(chub_env *e, chub_policy *pol, const float *d_obs,
     sa.gid0 = (uint32_t) e->hp.env_id0;
     sa.G = pol->G;
     sa.r_row0 = 0;
-    launch_policy_sample(sa, pol->waves, (hipStream_t) stream);
+    if (which >= 0) launch_policy_sample_set(sa, pol->waves, (hipStream_t) stream);
+    else launch_policy_sample(sa, pol->waves, (hipStream_t) stream);
     HIP_TRY(hipGetLastError());
     if (loads && (out->d_actions || out->d_pile_bits))
         return chub_load_dispatch_device(e, CHUB_LOAD_FRACTION, pol->d_loads, sa.tail, d_mask, out->d_actions, out->d_pile_bits, stream);
     return CHUB_OK;
 }
 
-// The closed loop that keeps what a trainer needs: a host loop of the calls the header lists, like chub_policy_run_steps
-int chub_policy_collect(chub_env *e, chub_policy *pol, int mode, const chub_rollout *r, float *d_obs0, int64_t first_step, void *stream) {
-    if (!e || !pol || !r || !d_obs0) return fail(CHUB_ERR_ARG, "null argument");
+int chub_policy_sample_device(chub_env *e, chub_policy *pol, const float *d_obs, int64_t ld_obs, const uint8_t *d_mask,
+                              const chub_policy_sample_out *out, void *stream) {
+    if (const int rc = policy_sample_check(e, pol, d_obs, ld_obs, out)) return rc;
+    return policy_sample_enqueue(e, pol, d_obs, ld_obs, d_mask, -1, nullptr, out, stream);
+}
+
+int chub_policy_sample_set_device(chub_env *e, chub_policy *pol, const float *d_obs, int64_t ld_obs, const uint8_t *d_mask, int which,
+                                  uint64_t *d_set_bits, const chub_policy_sample_out *out, void *stream) {
+    if (const int rc = policy_sample_check(e, pol, d_obs, ld_obs, out)) return rc;
+    if (const int rc = policy_set_check(e, pol, which, "chub_policy_sample_set_device")) return rc;
+    return policy_sample_enqueue(e, pol, d_obs, ld_obs, d_mask, which, d_set_bits, out, stream);
+}
+
+// The closed loop that keeps what a trainer needs: a host loop of the calls the header lists, like chub_policy_run_steps.  which < 0:
+// chub_policy_collect; else chub_policy_collect_set, whose step t also leaves its pile set in d_set_bits[t]
+static int policy_collect(chub_env *e, chub_policy *pol, int mode, int which, const chub_rollout *r, uint64_t *d_set_bits, float *d_obs0,
+                          int64_t first_step, void *stream) {
+    if (!e || !pol || !r || !d_obs0 || (which >= 0 && !d_set_bits)) return fail(CHUB_ERR_ARG, "null argument");
     if (pol->env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
     if (mode != CHUB_PRUN_LOCKSTEP && mode != CHUB_PRUN_AUTORESET) return fail(CHUB_ERR_ARG, "mode: CHUB_PRUN_LOCKSTEP or CHUB_PRUN_AUTORESET");
     if (!r->d_packed || !r->d_pile_bits || !r->d_tail || !r->d_u || !r->d_logp)
@@ -3909,6 +3971,8 @@ int chub_policy_collect(chub_env *e, chub_policy *pol, int mode, const chub_roll
     probe.d_pile_bits = r->d_pile_bits;
     probe.d_tail = r->d_tail;
     if (const int rc = policy_sample_check(e, pol, d_obs0, e->hp.obs_dim, &probe)) return rc;
+    if (which >= 0)
+        if (const int rc = policy_set_check(e, pol, which, "chub_policy_collect_set")) return rc;
     const size_t N = (size_t) e->hp.n_envs, D = (size_t) e->hp.obs_dim, Wd = (size_t) ((e->hp.S[0] + e->hp.S[1] + 63) / 64);
     int rc;
     if (mode == CHUB_PRUN_LOCKSTEP && first_step % 96 == 0 && (rc = chub_reset_device(e, nullptr, nullptr, d_obs0, stream))) return rc;
@@ -3924,11 +3988,50 @@ int chub_policy_collect(chub_env *e, chub_policy *pol, int mode, const chub_roll
         o.d_u = r->d_u + k * N * (size_t) pol->G;
         o.d_logp = r->d_logp + k * N;
         o.d_features = r->d_features ? r->d_features + k * N * (size_t) pol->F : nullptr;
-        if ((rc = chub_policy_sample_device(e, pol, obs, ld, nullptr, &o, stream))) return rc;
+        if ((rc = policy_sample_enqueue(e, pol, obs, ld, nullptr, which, which >= 0 ? d_set_bits + k * N * Wd : nullptr, &o, stream))) return rc;
         if (mode == CHUB_PRUN_LOCKSTEP) rc = chub_step_bits_device_packed(e, o.d_pile_bits, o.d_tail, nullptr, packed, stream);
         else rc = chub_autoreset_step_device(e, pol->d_rows, nullptr, nullptr, nullptr, packed, r->d_final_obs, stream);
         if (rc) return rc;
     }
+    return CHUB_OK;
+}
+
+int chub_policy_collect(chub_env *e, chub_policy *pol, int mode, const chub_rollout *r, float *d_obs0, int64_t first_step, void *stream) {
+    return policy_collect(e, pol, mode, -1, r, nullptr, d_obs0, first_step, stream);
+}
+
+int chub_policy_collect_set(chub_env *e, chub_policy *pol, int mode, int which, const chub_rollout *r, uint64_t *d_set_bits, float *d_obs0,
+                            int64_t first_step, void *stream) {
+    if (which < 0 || which >= CHUB_PSET_COUNT)
+        return fail(CHUB_ERR_ARG, "chub_policy_collect_set: which is CHUB_PSET_ALL, CHUB_PSET_OCCUPIED or CHUB_PSET_DECIDABLE");
+    return policy_collect(e, pol, mode, which, r, d_set_bits, d_obs0, first_step, stream);
+}
+
+// ---- advantages (include/chub.h, chub_rollout_gae_device): the env supplies N and D and the partials of the statistics, nothing else
+int chub_rollout_gae_device(chub_env *e, const chub_gae *g, void *stream) {
+    if (!e || !g) return fail(CHUB_ERR_ARG, "null argument");
+    if (!g->d_packed || !g->d_values || !g->d_adv) return fail(CHUB_ERR_ARG, "chub_rollout_gae_device: d_packed, d_values and d_adv are required");
+    if (g->T <= 0) return fail(CHUB_ERR_ARG, "chub_rollout_gae_device: T >= 1");
+    if (!(g->gamma >= 0.0f && g->gamma <= 1.0f) || !(g->lambda >= 0.0f && g->lambda <= 1.0f))
+        return fail(CHUB_ERR_ARG, "chub_rollout_gae_device: gamma and lambda lie in [0, 1]");
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    GaeArgs a;
+    a.n_envs = e->hp.n_envs;
+    a.T = g->T;
+    a.D = e->hp.obs_dim;
+    a.gamma = g->gamma;
+    a.gl = g->gamma * g->lambda;
+    a.packed = g->d_packed;
+    a.values = g->d_values;
+    a.final_values = g->d_final_values;
+    a.mask = g->d_mask;
+    a.adv = g->d_adv;
+    a.ret = g->d_ret;
+    a.partials = g->d_stats ? e->d_gae_part : nullptr;
+    a.stats = g->d_stats;
+    launch_gae(a, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
     return CHUB_OK;
 }
 

@@ -201,22 +201,40 @@ class DevicePolicy(object):
         samples with it"""
         check(self._lib.chub_policy_set_log_std_device(self._p, d_log_std, stream or None))
 
-    def sample_device(self, d_obs=0, ld_obs=None, d_logp=0, d_actions=0, d_pile_bits=0, d_tail=0, d_u=0, d_features=0, d_mask=0, stream=0):
+    def sample_device(self, d_obs=0, ld_obs=None, d_logp=0, d_actions=0, d_pile_bits=0, d_tail=0, d_u=0, d_features=0, d_mask=0, stream=0,
+                      logp_piles=None, d_set_bits=0):
         """one SAMPLED evaluation on `stream` (chub_policy_sample_device): as act_device, with the action drawn from the actor's
         distribution under the tick of the handle's next launch (VecChargingHub.next_tick), its log-probability in d_logp [N] f32 (required),
-        the pre-squash Gaussian samples in d_u [N, G] and the raw feature row in d_features [N, F].  No tick is consumed."""
+        the pre-squash Gaussian samples in d_u [N, G] and the raw feature row in d_features [N, F].  No tick is consumed.
+        logp_piles="all" | "occupied" | "decidable" (chub_policy_sample_set_device): the same draws and outputs, with d_logp counting a
+        pile's term only where the pile is in that set of the current state (VecChargingHub.pile_set_device), which is also written to
+        d_set_bits [N, bit_words] u64 if given."""
         ld = self._env.obs_dim if ld_obs is None else int(ld_obs)
         out = _lib.ChubPolicySampleOut(d_actions or None, d_pile_bits or None, d_tail or None, d_u or None, d_logp or None, d_features or None)
-        check(self._lib.chub_policy_sample_device(self._env._h, self._p, d_obs or None, ld, d_mask or None, C.byref(out), stream or None))
+        if logp_piles is None:
+            if d_set_bits:
+                raise ValueError("d_set_bits needs logp_piles (the set to write)")
+            check(self._lib.chub_policy_sample_device(self._env._h, self._p, d_obs or None, ld, d_mask or None, C.byref(out), stream or None))
+        else:
+            check(self._lib.chub_policy_sample_set_device(self._env._h, self._p, d_obs or None, ld, d_mask or None, _lib.pile_set(logp_piles),
+                                                          d_set_bits or None, C.byref(out), stream or None))
 
     def collect(self, n_steps, d_obs0, d_packed, d_pile_bits, d_tail, d_u, d_logp, d_features=0, d_final_obs=0, first_step=0, mode="lockstep",
-                stream=0):
+                stream=0, logp_piles=None, d_set_bits=0):
         """the closed loop that keeps the trajectory (chub_policy_collect): n_steps sampled steps into [T][N][...] arrays in device memory,
-        the actor reading d_obs0 [N, D] at the first step and the packed block before it afterwards.  Returns after enqueueing."""
+        the actor reading d_obs0 [N, D] at the first step and the packed block before it afterwards.  Returns after enqueueing.
+        logp_piles="all" | "occupied" | "decidable" with d_set_bits [T, N, bit_words] u64 (chub_policy_collect_set): d_logp[t] counts the
+        piles of that set in the state step t acts on, and d_set_bits[t] keeps the set."""
         r = _lib.ChubRollout(int(n_steps), d_packed or None, d_pile_bits or None, d_tail or None, d_u or None, d_logp or None, d_features or None,
                              d_final_obs or None)
-        check(self._lib.chub_policy_collect(self._env._h, self._p, _lib._enum_value(_lib.PRUN, mode, "run mode"), C.byref(r), d_obs0 or None,
-                                            int(first_step), stream or None))
+        run = _lib._enum_value(_lib.PRUN, mode, "run mode")
+        if logp_piles is None:
+            if d_set_bits:
+                raise ValueError("d_set_bits needs logp_piles (the set to keep)")
+            check(self._lib.chub_policy_collect(self._env._h, self._p, run, C.byref(r), d_obs0 or None, int(first_step), stream or None))
+        else:
+            check(self._lib.chub_policy_collect_set(self._env._h, self._p, run, _lib.pile_set(logp_piles), C.byref(r), d_set_bits or None,
+                                                    d_obs0 or None, int(first_step), stream or None))
 
     def close(self):
         if getattr(self, "_p", None) and getattr(self._env, "_h", None):
@@ -644,6 +662,38 @@ class VecChargingHub(object):
         finally:
             self._lib.chub_free_device(self._device, d)
         return out
+
+    # ---- pile sets on the device (chub_pile_set_device): the piles whose action bit the next step can see
+    def pile_set_device(self, d_bits, which="decidable", d_mask=0, stream=0):
+        """a pile set of every env into device memory, d_bits [N, bit_words] u64 in step_bits' layout (bits from n_slots up zero): "all",
+        "occupied" (the pile holds a car) or "decidable" (it holds a car whose emergency is below 1.01: the step reads the pile's action bit).
+        d_mask [N] u8 in device memory: only the rows of the envs it names are written.  One launch on `stream`: no synchronisation, nothing
+        of the simulation changes, recordable into a graph."""
+        check(self._lib.chub_pile_set_device(self._h, _lib.pile_set(which), d_mask or None, d_bits, stream or None))
+
+    def pile_set(self, which="decidable"):
+        """pile_set_device into host memory, unpacked: bool [N, n_slots] (the convenience form: it allocates, synchronises and copies)"""
+        words = np.zeros((self.n_envs, self.bit_words), dtype=np.uint64)
+        d = C.c_void_p()
+        check(self._lib.chub_malloc_device(self._device, words.nbytes, C.byref(d)))
+        try:
+            check(self._lib.chub_sync(self._h))  # (calls in flight on any stream write the state)
+            check(self._lib.chub_pile_set_device(self._h, _lib.pile_set(which), None, d, None))
+            check(self._lib.chub_copy_to_host(self._device, _ptr(words), d, words.nbytes, None))
+        finally:
+            self._lib.chub_free_device(self._device, d)
+        return np.unpackbits(words.view(np.uint8), axis=1, bitorder="little")[:, :self.n_slots].astype(bool)
+
+    # ---- advantages on the device (chub_rollout_gae_device): GAE over a collected rollout's blocks
+    def gae_device(self, n_steps, d_packed, d_values, d_adv, d_ret=0, d_final_values=0, gamma=0.99, lam=0.95, d_mask=0, d_stats=0, stream=0):
+        """generalised advantage estimation over n_steps blocks: d_packed [T, N, D + 2] (a rollout's), d_values [T + 1, N] f32 (V of obs0,
+        then V of every block's observation), d_final_values [N] (V of the terminal observations; 0: an episode's end is worth 0) ->
+        d_adv, d_ret [T, N] f32 and d_stats [3] f64 (count, sum, sum of squares of the advantages).  Exact f32, every operation rounded
+        once; the statistics have the same bits every call.  One launch on `stream` (two with d_stats): no synchronisation, no simulation
+        state read, recordable into a graph."""
+        g = _lib.ChubGae(int(n_steps), d_packed or None, d_values or None, d_final_values or None, d_mask or None, float(gamma), float(lam),
+                         d_adv or None, d_ret or None, d_stats or None)
+        check(self._lib.chub_rollout_gae_device(self._h, C.byref(g), stream or None))
 
     # ---- per-station deadline profiles on the device (chub_station_profile_device): who is due by when
     def station_profile_device(self, d_out, fields=None, buckets=8, d_mask=0, stream=0):

@@ -249,28 +249,57 @@ class HubVectorEnv(_HubBatch):
             _HubBatch.close(self)
 
 
-def sampled_logp(z, bits_or_on, u, log_std):
+def _unpack_words(words, S):
+    """recorded bit words int64 [..., W] -> bool [..., S] (a bool tensor passes through)"""
+    import torch
+
+    if words.dtype == torch.bool:
+        return words
+    sh = torch.arange(64, device=words.device, dtype=torch.int64)
+    return (((words.unsqueeze(-1) >> sh) & 1) != 0).flatten(-2)[..., :S]
+
+
+def sampled_logp(z, bits_or_on, u, log_std, piles=None):
     """The log-probability of recorded actions under a network's outputs, in torch and differentiable in `z` and `log_std`: what a trainer
     uses for the NEW policy's term of an importance ratio (include/chub.h, "sampling from the device actor"; the old policy's term is the
     recorded ``logp``).  z [..., S + G]: the last layer's PRE-squash outputs (S pile logits, then the G Gaussian means; G = log_std's
     length, S may be 0); bits_or_on: the pile decisions as a bool tensor [..., S] or as recorded bit words int64 [..., W]; u [..., G]: the
     recorded pre-squash samples.  eps = (u - z_gauss) / exp(log_std);
         logp = sum_b (on_b ? -softplus(-z_b) : -softplus(z_b)) + sum_i (-0.5 eps_i^2 - log_std_i - 0.5 ln 2 pi)
-    The Gaussian part is the density of the pre-squash sample: no tanh Jacobian, which cancels in every ratio."""
+    The Gaussian part is the density of the pre-squash sample: no tanh Jacobian, which cancels in every ratio.
+    piles: a bool tensor [..., S] or recorded set words int64 [..., W] (a rollout's ``set_bits``): only the piles of the set count, as in
+    a ``logp`` recorded with ``logp_piles=``; None: every pile counts."""
     import math
 
     import torch
 
     G = log_std.shape[-1]
     S = z.shape[-1] - G
-    on = bits_or_on
-    if on.dtype != torch.bool:
-        sh = torch.arange(64, device=on.device, dtype=torch.int64)
-        on = (((on.unsqueeze(-1) >> sh) & 1) != 0).flatten(-2)[..., :S]
+    on = _unpack_words(bits_or_on, S)
     zp, zg = z[..., :S], z[..., S:]
-    piles = -torch.nn.functional.softplus(torch.where(on, -zp, zp)).sum(dim=-1)
+    terms = torch.nn.functional.softplus(torch.where(on, -zp, zp))
+    if piles is not None:
+        terms = torch.where(_unpack_words(piles, S), terms, torch.zeros_like(terms))
     eps = (u - zg) / torch.exp(log_std)
-    return piles + (-0.5 * eps * eps - log_std - 0.5 * math.log(2.0 * math.pi)).sum(dim=-1)
+    return -terms.sum(dim=-1) + (-0.5 * eps * eps - log_std - 0.5 * math.log(2.0 * math.pi)).sum(dim=-1)
+
+
+def sampled_entropy(z, log_std, piles=None):
+    """The entropy of the actor's distribution at outputs z [..., S + G], in torch and differentiable in `z` and `log_std` (an entropy
+    bonus): the Bernoulli entropy of the pile logits, H(p) = softplus(z) - z sigmoid(z), summed over the piles of `piles` (a bool tensor
+    [..., S] or recorded set words int64 [..., W]; None: all of them), plus the Gaussian entropy sum_i (0.5 + log_std_i + 0.5 ln 2 pi) of
+    the pre-squash samples."""
+    import math
+
+    import torch
+
+    G = log_std.shape[-1]
+    S = z.shape[-1] - G
+    zp = z[..., :S]
+    h = torch.nn.functional.softplus(zp) - zp * torch.sigmoid(zp)
+    if piles is not None:
+        h = torch.where(_unpack_words(piles, S), h, torch.zeros_like(h))
+    return h.sum(dim=-1) + (0.5 + log_std + 0.5 * math.log(2.0 * math.pi)).sum(dim=-1)
 
 
 class TorchHubVecEnv(object):
@@ -606,7 +635,7 @@ class TorchHubVecEnv(object):
             return self._cur_obs, self._packed[:, D], self._packed[:, D + 1] > 0.5, {}
         return self._after_step()
 
-    def collect(self, policy, n_steps):
+    def collect(self, policy, n_steps, logp_piles=None):
         """n_steps SAMPLED closed-loop steps of `policy` (after ``policy.set_exploration``) from the current observation, issued from C on
         torch's current stream (chub_policy_collect), keeping the trajectory: a dict of CUDA tensors the next call with the same policy and
         n_steps overwrites --
@@ -614,6 +643,9 @@ class TorchHubVecEnv(object):
             of step t + 1 read; reward [T, N] and done [T, N] (1.0 / 0.0): views of packed; bits [T, N, W] int64 and tail [T, N, 2]: the
             actions taken; u [T, N, G]: the pre-squash Gaussian samples; logp [T, N]; features [T, N, F]: the raw feature rows the actor saw.
         ``sampled_logp`` of the trainer's own forward pass on ``features`` gives the new policy's term of the importance ratio.
+        ``logp_piles="all" | "occupied" | "decidable"`` (chub_policy_collect_set): ``logp`` counts a pile's term only where the pile is in
+        that set of the state the step acted on, and the dict also holds set_bits [T, N, W] int64, the sets -- what
+        ``sampled_logp(..., piles=ro["set_bits"])`` and ``sampled_entropy`` take.  "decidable" are the piles whose bit the step reads.
         ``autoreset="per_env"``: every step is the auto-reset step, ``last_obs`` keeps the terminal rows, n_steps <= 96.
         ``autoreset=True``: the rollout stays inside the batch's day (n_steps <= 96 - steps taken today); one that begins a day begins with
         the day's reset, made by the call itself (it replaces the one the adapter made), and one that ends a day is followed by the
@@ -631,19 +663,24 @@ class TorchHubVecEnv(object):
         cache = getattr(self, "_rollouts", None)
         if cache is None:
             cache = self._rollouts = {}
-        ro = cache.get((id(policy), T))
+        if logp_piles is not None:
+            _lib.pile_set(logp_piles)  # (ValueError for an unknown name, before anything is allocated)
+        ro = cache.get((id(policy), T, logp_piles is not None))
         if ro is None:
             f32 = dict(dtype=torch.float32, device=self.device)
-            ro = cache[(id(policy), T)] = {
+            ro = cache[(id(policy), T, logp_piles is not None)] = {
                 "obs0": torch.zeros((N, D), **f32), "packed": torch.zeros((T, N, D + 2), **f32),
                 "bits": torch.zeros((T, N, W), dtype=torch.int64, device=self.device), "tail": torch.zeros((T, N, 2), **f32),
                 "u": torch.zeros((T, N, policy.n_gaussians), **f32), "logp": torch.zeros((T, N), **f32),
                 "features": torch.zeros((T, N, policy.n_features), **f32)}
             ro["reward"], ro["done"] = ro["packed"][:, :, D], ro["packed"][:, :, D + 1]
+            if logp_piles is not None:
+                ro["set_bits"] = torch.zeros((T, N, W), dtype=torch.int64, device=self.device)
         ro["obs0"].copy_(self._cur_obs)
+        extra = {} if logp_piles is None else dict(logp_piles=logp_piles, d_set_bits=ro["set_bits"].data_ptr())
         policy.collect(T, ro["obs0"].data_ptr(), ro["packed"].data_ptr(), ro["bits"].data_ptr(), ro["tail"].data_ptr(), ro["u"].data_ptr(),
                        ro["logp"].data_ptr(), d_features=ro["features"].data_ptr(), d_final_obs=self.last_obs.data_ptr() if self.per_env else 0,
-                       first_step=today, mode="autoreset" if self.per_env else "lockstep", stream=self._stream())
+                       first_step=today, mode="autoreset" if self.per_env else "lockstep", stream=self._stream(), **extra)
         self._packed.copy_(ro["packed"][T - 1])  # (the block `step` and `rollout` continue from)
         self._cur_obs = self._packed[:, :D]
         if not self.per_env:
@@ -652,6 +689,35 @@ class TorchHubVecEnv(object):
                 self.last_obs = self._cur_obs.clone()
                 self.reset()
         return ro
+
+    def advantages(self, rollout, values, final_values=None, gamma=0.99, lam=0.95, stats=False):
+        """Generalised advantage estimation over a ``collect`` rollout, on torch's current stream in one launch (chub_rollout_gae_device):
+        values [T + 1, N] float32 CUDA = the critic on ``rollout["obs0"]`` and then on every block's observation
+        (``rollout["packed"][:, :, :D]``); final_values [N] = the critic on ``last_obs`` (the terminal rows of ``autoreset="per_env"``),
+        read only where done fires; None: an episode's end is worth 0.  Returns (adv, ret), float32 [T, N] CUDA tensors the next call with
+        the same T overwrites; with stats=True (adv, ret, stats), stats a float64 [3] CUDA tensor: count, sum and sum of squares of the
+        advantages (mean and variance for normalisation with nothing read back).  Exact f32: delta = (r + gamma vn) - V,
+        adv = delta + (gamma lam) adv', every operation rounded once."""
+        torch = self.torch
+        packed = rollout["packed"]
+        T, N = int(packed.shape[0]), self.num_envs
+        ok = lambda t, shape: self._on_device(t) and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
+        if not ok(values, (T + 1, N)):
+            raise AssertionError("values must be a contiguous float32 tensor on %s of shape (%d, %d)" % (self.device, T + 1, N))
+        if final_values is not None and not ok(final_values, (N,)):
+            raise AssertionError("final_values must be a contiguous float32 tensor on %s of shape (%d,)" % (self.device, N))
+        cache = getattr(self, "_gae", None)
+        if cache is None:
+            cache = self._gae = {}
+        out = cache.get(T)
+        if out is None:
+            out = cache[T] = (torch.zeros((T, N), dtype=torch.float32, device=self.device), torch.zeros((T, N), dtype=torch.float32, device=self.device),
+                              torch.zeros((3,), dtype=torch.float64, device=self.device))
+        adv, ret, st = out
+        self.vec.gae_device(T, packed.data_ptr(), values.data_ptr(), adv.data_ptr(), d_ret=ret.data_ptr(),
+                            d_final_values=0 if final_values is None else final_values.data_ptr(), gamma=gamma, lam=lam,
+                            d_stats=st.data_ptr() if stats else 0, stream=self._stream())
+        return (adv, ret, st) if stats else (adv, ret)
 
     def copy_envs(self, src_idx, dst_idx, source=None):
         """env dst_idx[i] becomes a clone of env src_idx[i] of `source` (another TorchHubVecEnv; default: this one), on torch's current

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Five ways to drive the hub, smallest first (run from the repo root on a machine with an MI355X):
+"""Six ways to drive the hub, smallest first (run from the repo root on a machine with an MI355X):
 
     python examples/quickstart.py
 
@@ -7,7 +7,8 @@
 2. the batched host-pointer API (numpy in / numpy out);
 3. the device-resident API (torch CUDA tensors in / out, no host copies) -- what an on-device learner should use;
 4. a closed-loop day with an actor evaluated by the hub itself (numpy and ctypes only: no torch, no host between the steps);
-5. on-policy training data: the hub samples from the actor, and keeps actions, log-probabilities and every step's block on the device.
+5. on-policy training data: the hub samples from the actor, and keeps actions, log-probabilities and every step's block on the device;
+6. one PPO-shaped iteration on that data: log-probabilities over the piles the step can see, a torch critic, advantages on the device.
 """
 import os
 import sys
@@ -168,9 +169,54 @@ def on_policy_data(n=4096, steps=32):
     env.close()
 
 
+def ppo_iteration(n=4096, steps=64):
+    import charginghub_env_amd as chub
+
+    if torch is None:
+        print("6. skipped: torch is not installed")
+        return
+    env = chub.TorchHubVecEnv(n, seed=0, autoreset="per_env", **HUB)
+    D, A = env.obs_dim, env.act_dim
+    net = torch.nn.Sequential(torch.nn.Linear(D, 64), torch.nn.Tanh(), torch.nn.Linear(64, A)).to("cuda")
+    critic = torch.nn.Sequential(torch.nn.Linear(D, 64), torch.nn.Tanh(), torch.nn.Linear(64, 1)).to("cuda")
+    log_std = torch.full((2,), -0.5, device="cuda", requires_grad=True)
+    opt = torch.optim.Adam(list(net.parameters()) + list(critic.parameters()) + [log_std], lr=3e-4)
+    policy = env.load_policy(net)
+    policy.set_exploration(key=7, log_std=log_std.detach().cpu().numpy())
+    env.reset()
+    # the step ignores a pile's bit where the pile is empty or its car is forced on: only the decidable piles' terms enter logp
+    ro = env.collect(policy, steps, logp_piles="decidable")
+    with torch.no_grad():                                    # the critic on obs0 and on every block's observation: one batched call each
+        values = torch.cat([critic(ro["obs0"]).reshape(1, n), critic(ro["packed"][:, :, :D]).reshape(steps, n)]).contiguous()
+        final = critic(env.last_obs).reshape(n).contiguous()  # the terminal observations of the envs whose day ended in the rollout
+    adv, ret, stats = env.advantages(ro, values, final, gamma=0.99, lam=0.95, stats=True)   # one launch; count, sum, sum of squares beside
+    mean = stats[1] / stats[0]
+    std = (stats[2] / stats[0] - mean * mean).clamp_min(1e-12).sqrt()
+    a = ((adv - mean) / std).float()
+    z = net(ro["features"])
+    new = chub.wrappers.sampled_logp(z, ro["bits"], ro["u"], log_std, piles=ro["set_bits"])
+    ratio = torch.exp(new - ro["logp"])
+    surrogate = torch.min(ratio * a, ratio.clamp(0.8, 1.2) * a).mean()
+    entropy = chub.wrappers.sampled_entropy(z, log_std, piles=ro["set_bits"]).mean()
+    value_loss = (critic(ro["features"]).reshape(steps, n) - ret).pow(2).mean()
+    loss = -surrogate + 0.5 * value_loss - 0.01 * entropy
+    opt.zero_grad()
+    loss.backward()
+    opt.step()
+    sets = ro["set_bits"]
+    decidable = sum(((sets >> b) & 1).sum() for b in range(env.vec.n_slots)) / float(sets.shape[0] * n) if sets.shape[-1] == 1 else float("nan")
+    print("6. %d envs x %d steps, one PPO iteration: %.1f of %d piles decidable per step, importance ratio %.5f .. %.5f, advantage std %.3f, loss %.4f"
+          % (n, steps, float(decidable), env.vec.n_slots, float(ratio.min()), float(ratio.max()), float(std), float(loss.detach())))
+    for l, m in enumerate(x for x in net if isinstance(x, torch.nn.Linear)):   # the stepped weights, on the device, for the next collect
+        policy.set_weights_device(l, m.weight.data_ptr(), m.bias.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    policy.set_log_std_device(log_std.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    env.close()
+
+
 if __name__ == "__main__":
     single_env()
     batched_host()
     device_resident()
     closed_loop()
     on_policy_data()
+    ppo_iteration()

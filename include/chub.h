@@ -902,6 +902,64 @@ typedef struct chub_rollout {
 int chub_policy_collect(chub_env *env, chub_policy *pol, int mode, const chub_rollout *r, float *d_obs0 /* [N][D] */,
                         int64_t first_step, void *stream);
 
+/* ---- pile sets and advantages: log-probabilities over the piles a step can see, GAE over a collected rollout ---------------------------
+ * The step ignores a pile's action bit wherever the reference's judge_feasibility overrides it (CHS:1404-1413): a pile with no car at the
+ * start of the step is forced off, a pile whose car has emergency >= 1.01 is forced on, and a car that arrives during the step is not
+ * touched by that step's action.  The sampled actor above nevertheless counts all S Bernoulli terms.  This section names the piles that
+ * matter, lets the sampled launch count only those, and turns a collected rollout into advantages without leaving the device.
+ *   chub_pile_set_device: d_bits [N][W] u64 in chub_step_bits' layout, W = ceil(S / 64), bits from S up zero.  Bit b of env e:
+ *       CHUB_PSET_ALL        b < S
+ *       CHUB_PSET_OCCUPIED   chub_pile_obs_device's car column of the pile is non-zero
+ *       CHUB_PSET_DECIDABLE  occupied, and its emergency column is < 1.01f: the reference's predicate, on the values the columns hold
+ *     Manners are chub_pile_obs_device's: ONE launch on `stream`, read-only on simulation state (no tick, no clock, no draw), no
+ *     synchronisation, no allocation; with d_mask [N] u8 only the rows of the named envs are written; all three RNG modes and slot layouts,
+ *     every hub shape (a station of 0 piles, stations of 4096); valid wherever chub_pile_obs_device is; recordable between chub_graph_begin
+ *     and chub_graph_end without counting towards the even number of resets + steps.  OCCUPIED reads the state word alone, DECIDABLE adds
+ *     the pile's record (PHILOX: its class row).  A step whose bits differ only outside DECIDABLE computes the same state and outputs.
+ *   chub_policy_sample_set_device: chub_policy_sample_device with a set.  It enqueues chub_pile_set_device in front, with the same mask, into
+ *     d_set_bits [N][W] (NULL: a buffer of the policy's own), then the sampled actor launch with the set as one more input.  Every draw and
+ *     d_pile_bits, d_actions, d_tail, d_u and d_features are bit for bit what chub_policy_sample_device writes; only d_logp differs: a
+ *     pile's Bernoulli term is added iff its bit is in the set, in the same fixed order with the other terms left out.  The Gaussian terms
+ *     always count.  With CHUB_PSET_ALL d_logp too is chub_policy_sample_device's.  Under CHUB_PHEAD_LOADS the log-probability has no pile
+ *     terms: only CHUB_PSET_ALL is accepted.
+ *   chub_policy_collect_set: chub_policy_collect with the set launch and the set-aware sample per step; d_set_bits [T][N][W] (required),
+ *     block t = the set in the state step t acts on.  The same day, T and mode rules; Philox modes only.
+ *   chub_rollout_gae_device: generalised advantage estimation over a rollout's blocks, one launch (two with d_stats) on `stream`.  Per env,
+ *     for t = T-1 .. 0, in f32 with every operation rounded once and no contraction, gl = gamma * lambda formed once in f32:
+ *       d      = packed[t][D + 1] != 0
+ *       vn     = d ? (d_final_values ? d_final_values[e] : 0) : V[t + 1]
+ *       delta  = (packed[t][D] + gamma * vn) - V[t]
+ *       adv[t] = delta + gl * (d ? 0 : adv[t + 1]),  adv[T] = 0
+ *       ret[t] = adv[t] + V[t]
+ *     V[0] = V(d_obs0) and V[t + 1] = V(the observation in block t): on an auto-reset rollout the observation in block t of a finished env is
+ *     already the next episode's (the right V[t + 1] for step t + 1), and the terminal one is in d_final_obs, whose value d_final_values
+ *     carries (NULL: an episode's end is worth 0).  With d_mask only the named envs' columns of d_adv / d_ret are written and counted.
+ *     d_stats [3] f64: count, sum and sum of squares of the advantages written, reduced without atomics in an order fixed for (N, T): two
+ *     calls give identical bits.  The partials live in one buffer of the handle's: calls that ask for d_stats must be ordered against
+ *     each other.  `env` supplies N and D only: no simulation state is read, no tick, no synchronisation, no allocation; recordable.
+ * Refusals, with a message and before any device work.  CHUB_ERR_ARG: null env, d_bits, g, d_packed, d_values or d_adv; null d_set_bits in
+ * chub_policy_collect_set; an unknown `which`; which != CHUB_PSET_ALL under CHUB_PHEAD_LOADS; T <= 0; gamma or lambda outside [0, 1] or
+ * NaN; everything chub_policy_sample_device and chub_policy_collect refuse.  CHUB_ERR_UNSUPPORTED: tape handles, as for
+ * chub_pile_obs_device.  Out of scope: a critic on the device (values are the trainer's one batched call). */
+enum { CHUB_PSET_ALL = 0, CHUB_PSET_OCCUPIED, CHUB_PSET_DECIDABLE, CHUB_PSET_COUNT };
+int chub_pile_set_device(chub_env *env, int which, const uint8_t *d_mask, uint64_t *d_bits /* [N][W] */, void *stream);
+int chub_policy_sample_set_device(chub_env *env, chub_policy *pol, const float *d_obs, int64_t ld_obs, const uint8_t *d_mask, int which,
+                                  uint64_t *d_set_bits /* [N][W] out, or NULL: the policy's own scratch */,
+                                  const chub_policy_sample_out *out, void *stream);
+int chub_policy_collect_set(chub_env *env, chub_policy *pol, int mode, int which, const chub_rollout *r,
+                            uint64_t *d_set_bits /* [T][N][W], required */, float *d_obs0, int64_t first_step, void *stream);
+typedef struct chub_gae {
+    int64_t T;
+    const float *d_packed;        /* [T][N][D + 2]: reward at column D, done at D + 1 (a rollout's d_packed) */
+    const float *d_values;        /* [T + 1][N]: V[0] = V(d_obs0), V[t + 1] = V(the observation in block t) */
+    const float *d_final_values;  /* [N] or NULL: V(d_final_obs), read only where done fires (bootstrap through the day's end) */
+    const uint8_t *d_mask;        /* [N] or NULL */
+    float gamma, lambda;
+    float *d_adv, *d_ret;         /* [T][N] each; d_ret may be NULL */
+    double *d_stats;              /* [3] or NULL: count, sum and sum of squares of the advantages written */
+} chub_gae;
+int chub_rollout_gae_device(chub_env *env, const chub_gae *g, void *stream);
+
 /* The FCEV waiting list is unbounded as in the reference (HYD:264-265): the entries a list that still gets served can
  * hold are kept one by one, and once no prefix of it fits into 15 minutes any more (HYD:270-276: nobody is served again
  * until reset and the list only grows) its entries are folded into their count and running sums, which is all the

@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
-"""The device actor (chub_policy_*) on a device-resident PHILOX handle, five measurements on ONE build in one process:
+"""The device actor (chub_policy_*) on a device-resident PHILOX handle, measurements on ONE build in one process:
   launch          us per chub_policy_act_device (bits + tail out), CALLS launches between two HIP events;
   closed_loop     env-steps/s of chub_policy_run_steps (lock-step mode: reset, then per step the actor and the bits-form step) over ten days;
   open_loop       the same for chub_run_steps with its open-loop random action batches;
   sampled_launch  us per chub_policy_sample_device (bits + tail + u + logp out), as `launch`;
-  collect         env-steps/s of chub_policy_collect in lock-step mode, ten calls of one day each, every step's block and action kept.
+  collect         env-steps/s of chub_policy_collect in lock-step mode, ten calls of one day each, every step's block and action kept;
+  pile_set_*      us per chub_pile_set_device, one case per set (all, occupied, decidable), as `launch`;
+  sampled_set_launch  us per chub_policy_sample_set_device with the decidable set (the set launch and the set-aware actor launch), as `launch`;
+  collect_set     env-steps/s of chub_policy_collect_set with the decidable set, as `collect`;
+  gae             us per chub_rollout_gae_device over the collected day (T = 96, with d_ret, d_final_values and d_stats), with the bytes it
+                  asks for and the bytes of the lines it touches; with --torch-gae also gae_torch, the same recurrence as a torch loop over
+                  the same device memory in the same process (torch is then imported first, so that both share one HIP runtime).
 Every case is warmed up, then the cases alternate, ROUNDS times; median, best and worst round are reported with the build id.
---open-loop-only measures the open loop alone, --launch-only the open loop and the deterministic launch: with
-CHUB_LIB=<another build's libchub.so> those are the rates of a build without the newer entry points (the parent commit), on the same
+--open-loop-only measures the open loop alone, --launch-only the open loop and the deterministic launch, --no-sets the first five cases:
+with CHUB_LIB=<another build's libchub.so> those are the rates of a build without the newer entry points (the parent commit), on the same
 device; run in alternating processes with this build's they show what the run-to-run spread is.
     python tools/policy_rate.py [--shape 65536x20,25] [--hidden 64,64] [--rounds 7] [--calls 200] [--days 10] [--out profiles/policy_rate.json]"""
 import argparse
@@ -19,6 +25,9 @@ import sys
 import time
 
 import numpy as np
+
+if "--torch-gae" in sys.argv:
+    import torch  # before libchub is loaded: both must share one HIP runtime
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import charginghub_env_amd as chub
@@ -35,6 +44,8 @@ def main():
     ap.add_argument("--days", type=int, default=10)
     ap.add_argument("--open-loop-only", action="store_true")
     ap.add_argument("--launch-only", action="store_true")
+    ap.add_argument("--torch-gae", action="store_true")
+    ap.add_argument("--no-sets", action="store_true", help="the first five cases only: what a build without the pile set entry points can run")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     n_s, piles_s = args.shape.split("x")
@@ -132,6 +143,56 @@ def main():
             cases[("sampled_launch", "chub_policy_sample_device", "us_per_launch")] = sampled_launch
             cases[("collect", "chub_policy_collect", "env_steps_per_s")] = collect
 
+        if not args.launch_only and not args.no_sets:
+            # pile sets, the set-aware sampled launch and collect, and GAE over the collected day
+            roll["set"] = multi_gpu.DeviceBuffer(96 * n * W * 8)
+            T = 96
+            gae = dict(values=multi_gpu.DeviceBuffer((T + 1) * n * 4), final=multi_gpu.DeviceBuffer(n * 4), adv=multi_gpu.DeviceBuffer(T * n * 4),
+                       ret=multi_gpu.DeviceBuffer(T * n * 4), stats=multi_gpu.DeviceBuffer(24))
+            gae["values"].from_host(rs.normal(size=((T + 1) * n,)).astype(np.float32))
+            gae["final"].from_host(rs.normal(size=(n,)).astype(np.float32))
+
+            def pile_set(which):
+                def run():
+                    def many():
+                        for _ in range(args.calls):
+                            v.pile_set_device(roll["set"].ptr, which, stream=stream)
+                    return between_events(many) * 1e3 / args.calls
+                return run
+
+            def sampled_set_launch():
+                def many():
+                    for _ in range(args.calls):
+                        pol.sample_device(packed[1].ptr, D + 2, d_logp=roll["logp"].ptr, d_pile_bits=bits.ptr, d_tail=tail.ptr, d_u=roll["u"].ptr,
+                                          stream=stream, logp_piles="decidable", d_set_bits=roll["set"].ptr)
+                return between_events(many) * 1e3 / args.calls
+
+            def collect_set():
+                st.sync()
+                t0 = time.perf_counter()
+                for _ in range(args.days):
+                    pol.collect(96, obs0.ptr, roll["packed"].ptr, roll["bits"].ptr, roll["tail"].ptr, roll["u"].ptr, roll["logp"].ptr,
+                                mode="lockstep", stream=stream, logp_piles="decidable", d_set_bits=roll["set"].ptr)
+                st.sync()
+                return n * steps / (time.perf_counter() - t0)
+
+            gae_calls = max(1, args.calls // 10)
+
+            def gae_device():
+                def many():
+                    for _ in range(gae_calls):
+                        v.gae_device(T, roll["packed"].ptr, gae["values"].ptr, gae["adv"].ptr, d_ret=gae["ret"].ptr, d_final_values=gae["final"].ptr,
+                                     gamma=0.99, lam=0.95, d_stats=gae["stats"].ptr, stream=stream)
+                return between_events(many) * 1e3 / gae_calls
+
+            for which in ("all", "occupied", "decidable"):
+                cases[("pile_set_" + which, "chub_pile_set_device", "us_per_launch")] = pile_set(which)
+            cases[("sampled_set_launch", "chub_policy_sample_set_device", "us_per_launch")] = sampled_set_launch
+            cases[("collect_set", "chub_policy_collect_set", "env_steps_per_s")] = collect_set
+            cases[("gae", "chub_rollout_gae_device", "us_per_call")] = gae_device
+            if args.torch_gae:
+                cases[("gae_torch", "a torch loop over the same memory", "us_per_call")] = torch_gae_case(roll["packed"].ptr, gae, n, T, D, max(1, gae_calls // 4))
+
     for fn in cases.values():  # warm-up (the open loop first: it leaves real observations in the packed blocks)
         fn()
     values = {c: [] for c in cases}
@@ -143,6 +204,10 @@ def main():
         row = dict(shape=args.shape, n_envs=n, piles=piles, mode="philox", net=[D] + hidden + [A], kind=kind, route=route, unit=unit, rounds=len(xs),
                    median=round(statistics.median(xs), 3), min=round(min(xs), 3), max=round(max(xs), 3), steps_per_round=steps,
                    launches_per_round=args.calls, build_id=build_id, lib=os.environ.get("CHUB_LIB", ""))
+        if kind in ("gae", "gae_torch"):  # what the recurrence asks for (V, reward + done in; adv, ret out), and the lines that holds at a
+            useful = 96 * n * (4 + 8 + 4 + 4) + n * 8           # (D + 2) * 4-byte row stride: every line of the packed blocks
+            lines = 96 * n * ((D + 2) * 4 + 4 + 4 + 4) + n * 8
+            row.update(bytes_asked_for=useful, bytes_of_lines_touched=lines, gb_per_s_of_lines=round(lines / (row["median"] * 1e-6) / 1e9, 1))
         rows.append(row)
         print(json.dumps(row), flush=True)
     v.close()
@@ -150,6 +215,43 @@ def main():
     if args.out:
         os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
         json.dump(rows, open(args.out, "w"), indent=1)
+
+
+def torch_gae_case(packed_ptr, gae, n, T, D, calls):
+    """the same recurrence written the usual way, as a reverse torch loop of elementwise launches over the same device memory (torch's
+    current stream); timed with torch's own events"""
+    def view(ptr, shape):
+        count = int(np.prod(shape))
+        buf = (ctypes.c_float * count).from_address(0)  # (never read on the host: only the address and the shape are used)
+        iface = dict(shape=tuple(shape), typestr="<f4", data=(int(ptr), False), version=2)
+        holder = type("DeviceArray", (), {"__cuda_array_interface__": iface})()
+        del buf
+        return torch.as_tensor(holder, device="cuda")
+
+    packed, values, final = view(packed_ptr, (T, n, D + 2)), view(gae["values"].ptr, (T + 1, n)), view(gae["final"].ptr, (n,))
+    adv, ret = torch.empty((T, n), device="cuda"), torch.empty((T, n), device="cuda")
+
+    def once():
+        nxt = torch.zeros(n, device="cuda")
+        for t in range(T - 1, -1, -1):
+            r, d = packed[t, :, D], packed[t, :, D + 1] != 0
+            vn = torch.where(d, final, values[t + 1])
+            delta = r + 0.99 * vn - values[t]
+            nxt = delta + (0.99 * 0.95) * torch.where(d, torch.zeros_like(nxt), nxt)
+            adv[t] = nxt
+            ret[t] = nxt + values[t]
+        return adv.double().sum(), (adv.double() ** 2).sum()
+
+    def run():
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(calls):
+            once()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / calls
+    return run
 
 
 if __name__ == "__main__":
