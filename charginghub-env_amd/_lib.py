@@ -417,6 +417,12 @@ def load_library():
         "chub_policy_sample_set_device": (I, [P, P, P, L, P, I, P, C.POINTER(ChubPolicySampleOut), P]),
         "chub_policy_collect_set": (I, [P, P, I, I, C.POINTER(ChubRollout), P, P, L, P]),
         "chub_rollout_gae_device": (I, [P, C.POINTER(ChubGae), P]),
+        "chub_moments_create": (I, [P, C.c_int32, C.POINTER(P)]), "chub_moments_destroy": (I, [P]),
+        "chub_moments_update_device": (I, [P, P, L, L, P, P]), "chub_moments_reset_device": (I, [P, P]),
+        "chub_moments_get": (I, [P, C.POINTER(C.c_double), P, P]), "chub_moments_set": (I, [P, C.c_double, P, P]),
+        "chub_moments_state_device": (I, [P, C.POINTER(P)]),
+        "chub_policy_set_normalizer": (I, [P, P, P]), "chub_policy_set_normalizer_device": (I, [P, P, P, P]),
+        "chub_policy_get_normalizer_device": (I, [P, P, P, P]), "chub_policy_normalizer_from_moments_device": (I, [P, P, C.c_double, P]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -454,7 +460,10 @@ EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "ch
             "chub_policy_input_width", "chub_policy_create", "chub_policy_destroy", "chub_policy_set_weights", "chub_policy_set_weights_device",
             "chub_policy_act_device", "chub_policy_act", "chub_policy_run_steps",
             "chub_next_tick", "chub_policy_set_exploration", "chub_policy_set_log_std_device", "chub_policy_sample_device", "chub_policy_collect",
-            "chub_pile_set_device", "chub_policy_sample_set_device", "chub_policy_collect_set", "chub_rollout_gae_device"]
+            "chub_pile_set_device", "chub_policy_sample_set_device", "chub_policy_collect_set", "chub_rollout_gae_device",
+            "chub_moments_create", "chub_moments_destroy", "chub_moments_update_device", "chub_moments_reset_device", "chub_moments_get", "chub_moments_set",
+            "chub_moments_state_device", "chub_policy_set_normalizer", "chub_policy_set_normalizer_device", "chub_policy_get_normalizer_device",
+            "chub_policy_normalizer_from_moments_device"]
 
 
 def check(rc):

@@ -106,6 +106,25 @@ struct GaeArgs {
 };
 constexpr int kGaeLanes = 256;
 void launch_gae(const GaeArgs &a, hipStream_t stream);
+// running feature statistics (include/chub.h, chub_moments_update_device).  A workgroup's 256 lanes lie along the columns of a row: lane
+// r_in * L + c takes column c (and c + L where F > 256) of row r_in of the workgroup's pass, L = min(F, 256) lanes per row and
+// RW = 256 / L rows per pass.  Workgroup b takes passes b, b + blocks, b + 2 blocks, ..: the rows a workgroup sees depend on (R, F) only.
+struct MomentsArgs {
+    const float *x;               // [R] rows of F floats with row stride ld
+    int64_t ld, R, passes;        // passes = ceil(R / RW)
+    int64_t n_envs, e_step;       // (mask) row r belongs to env r % N; e_step = (blocks * RW) % N
+    const uint8_t *mask;          // [N] or null
+    const double *state;          // [1 + 2F]: n | mean[F] | M2[F]
+    double *partials;             // [blocks][1 + 2F]: count | S1[F] | S2[F] per workgroup
+    double *pivot;                // [1 + F]: the state's n and the pivots K[F] of this call, left by workgroup 0 for the merge
+    int32_t F, L, RW, blocks;
+};
+constexpr int kMomentsLanes = 256;
+constexpr int kMomentsAhead = 8;        // passes a lane has in flight (measured against 4 and 16: DESIGN.md 6.21)
+constexpr int kMomentsMergeCols = 32;   // columns per workgroup of the merge launch, kMomentsLanes / 32 groups of partials each
+void launch_moments(const MomentsArgs &a, double *state, hipStream_t stream);
+// the policy's normaliser from a moments state: mean32[f] = (float) mean[f], inv_std32[f] = (float) (1 / sqrt(M2[f] / n + eps)); n == 0: nothing
+void launch_normalizer_from_moments(const double *state, int F, double eps, float *mean32, float *inv_std32, hipStream_t stream);
 // W [out][in] row-major and b [out] in device memory -> the layout above
 void launch_policy_relayout(const float *d_W, const float *d_b, float *d_w, float *d_bias, int out, int in, int k_pad, int tiles, hipStream_t stream);
 

@@ -377,6 +377,175 @@ void launch_gae(const GaeArgs &a, hipStream_t stream) {
     if (a.partials && a.stats) hipLaunchKernelGGL(k_gae_stats, dim3(1), dim3(kGaeLanes), 0, stream, (const double *) a.partials, nb, a.stats);
 }
 
+// ---- running feature statistics (include/chub.h, "running feature statistics"; the lane layout is chub_policy.h's MomentsArgs).
+// Launch 1 streams the rows: consecutive lanes read consecutive floats of a row, a lane keeps kAhead passes in flight, converts to f64,
+// subtracts its column's pivot and adds d and d d to its own sums.  The loop has no branch around a load: a row that does not count (past
+// R, or of a masked-out env) is NOT read -- its lane reads row 0 instead, the pivot row every call reads, and a select drops the value -- so
+// every load of a pass is issued before the first is waited for.  (With the loads under per-row branches the compiler waited for each
+// before issuing the next: a third of the rate)  The lanes of a workgroup that share a column then meet in LDS as a
+// tree over the row index (row r + h joins row r, h = the power of two halving down: a fixed order), and the workgroup writes one row
+// of partials.  Launch 2 adds the partials and merges.  No atomics anywhere: every sum's order is a function of (R, F, the grid) alone.
+// kMask: a mask is given (the bytes of a pass are loaded first, the rows they admit next); kTwo: F > 256, two columns per lane.
+template <int kAhead, bool kMask, bool kTwo>
+__global__ __launch_bounds__(kMomentsLanes) void k_moments(const MomentsArgs a) {
+    __shared__ double red[3][kMomentsLanes];
+    const int tid = (int) threadIdx.x, L = a.L, RW = a.RW, F = a.F;
+    const int r_in = tid / L, c = tid - r_in * L;
+    const bool on = r_in < RW, two = kTwo && c + L < F;  // (two columns per lane only where F > 256: L = 256, RW = 1)
+    const double n0 = a.state[0];
+    double K0 = 0.0, K1 = 0.0;
+    if (on) {
+        K0 = n0 > 0.0 ? a.state[1 + c] : (double) a.x[c];
+        if (two) K1 = n0 > 0.0 ? a.state[1 + c + L] : (double) a.x[c + L];
+        if (blockIdx.x == 0 && r_in == 0) {
+            a.pivot[1 + c] = K0;
+            if (two) a.pivot[1 + c + L] = K1;
+            if (c == 0) a.pivot[0] = n0;
+        }
+    }
+    double s1a = 0.0, s2a = 0.0, s1b = 0.0, s2b = 0.0, cnt = 0.0;
+    if (on) {
+        const int64_t G = a.blocks, N = a.n_envs;
+        // the lane's row and its offset move by one grid of passes per load: additions only
+        const int64_t row_step = G * RW, q_step = row_step * a.ld;
+        const int c1 = two ? L : 0;  // (the second column's offset; a lane without one reads its first again)
+        int64_t row = (int64_t) blockIdx.x * RW + r_in, off = row * a.ld + c;
+        [[maybe_unused]] int64_t e = kMask ? row % N : 0;
+        for (int64_t p = blockIdx.x; p < a.passes; p += G * kAhead) {
+            bool ok[kAhead];
+            float va[kAhead];
+            [[maybe_unused]] float vb[kAhead];
+            [[maybe_unused]] uint8_t m[kAhead];
+#pragma unroll
+            for (int k = 0; k < kAhead; k++) {
+                ok[k] = row + k * row_step < a.R;
+                if constexpr (kMask) {
+                    m[k] = a.mask[e];  // (e < N whatever the row)
+                    e += a.e_step;
+                    if (e >= N) e -= N;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < kAhead; k++) {
+                if constexpr (kMask) ok[k] = ok[k] && m[k] != 0;
+                const float *q = a.x + (ok[k] ? off + k * q_step : (int64_t) c);
+                va[k] = q[0];
+                if constexpr (kTwo) vb[k] = q[c1];
+            }
+            row += kAhead * row_step;
+            off += kAhead * q_step;
+#pragma unroll
+            for (int k = 0; k < kAhead; k++) {
+                const double d = ok[k] ? (double) va[k] - K0 : 0.0;
+                s1a += d;
+                s2a += d * d;
+                if constexpr (kTwo) {
+                    const double d1 = ok[k] && two ? (double) vb[k] - K1 : 0.0;
+                    s1b += d1;
+                    s2b += d1 * d1;
+                }
+                cnt += ok[k] ? 1.0 : 0.0;
+            }
+        }
+    }
+    if (RW > 1) {  // (uniform) the lanes of a column, rows 0 .. RW - 1 of the pass: a tree over the row index
+        red[0][tid] = s1a; red[1][tid] = s2a; red[2][tid] = cnt;
+        __syncthreads();
+        int h = 1;
+        while (h < RW) h <<= 1;
+        for (h >>= 1; h > 0; h >>= 1) {
+            if (r_in < h && r_in + h < RW) {
+#pragma unroll
+                for (int i = 0; i < 3; i++) red[i][tid] += red[i][tid + h * L];
+            }
+            __syncthreads();
+        }
+        s1a = red[0][tid]; s2a = red[1][tid]; cnt = red[2][tid];
+    }
+    if (on && r_in == 0) {
+        double *p = a.partials + (size_t) blockIdx.x * (size_t) (1 + 2 * F);
+        p[1 + c] = s1a;
+        p[1 + F + c] = s2a;
+        if (two) {
+            p[1 + c + L] = s1b;
+            p[1 + F + c + L] = s2b;
+        }
+        if (c == 0) p[0] = cnt;
+    }
+}
+
+// the partials of `blocks` workgroups into the state: a workgroup takes kMomentsMergeCols columns; its lane group g adds the partials of
+// blocks [blocks g / 8, blocks (g + 1) / 8) in ascending order, the groups meet in LDS in ascending g, and group 0 merges (Chan et al.).
+// n and the pivots come from launch 1's copy: the lane that writes the state's n races nobody who reads it.
+__global__ __launch_bounds__(kMomentsLanes) void k_moments_merge(const double *partials, int blocks, const double *pivot, double *state, int F) {
+    constexpr int kGroups = kMomentsLanes / kMomentsMergeCols;
+    __shared__ double red[3][kGroups][kMomentsMergeCols];
+    const int tid = (int) threadIdx.x, cl = tid % kMomentsMergeCols, g = tid / kMomentsMergeCols;
+    const int col = (int) blockIdx.x * kMomentsMergeCols + cl;
+    const bool live = col < F;
+    const size_t stride = (size_t) (1 + 2 * F);
+    double c = 0.0, s1 = 0.0, s2 = 0.0;
+    if (live) {
+        const int b1 = (int) ((int64_t) blocks * (g + 1) / kGroups);
+#pragma unroll 8
+        for (int b = (int) ((int64_t) blocks * g / kGroups); b < b1; b++) {
+            const double *p = partials + (size_t) b * stride;
+            c += p[0];
+            s1 += p[1 + col];
+            s2 += p[1 + F + col];
+        }
+    }
+    red[0][g][cl] = c; red[1][g][cl] = s1; red[2][g][cl] = s2;
+    __syncthreads();
+    if (g != 0 || !live) return;
+    c = s1 = s2 = 0.0;
+#pragma unroll
+    for (int j = 0; j < kGroups; j++) {
+        c += red[0][j][cl]; s1 += red[1][j][cl]; s2 += red[2][j][cl];
+    }
+    if (!(c > 0.0)) return;  // nobody counted: the state is left alone
+    const double n = pivot[0], K = pivot[1 + col];
+    const double t = s2 - (s1 * s1) / c;
+    const double m2b = t < 0.0 ? 0.0 : t;  // (a NaN stays one)
+    const double n1 = n + c;
+    double mean, m2;
+    if (n > 0.0) {
+        const double db = s1 / c;
+        mean = K + s1 / n1;
+        m2 = (state[1 + F + col] + m2b) + (db * db) * ((n * c) / n1);
+    } else {
+        mean = K + s1 / c;
+        m2 = m2b;
+    }
+    state[1 + col] = mean;
+    state[1 + F + col] = m2;
+    if (col == 0) state[0] = n1;
+}
+
+void launch_moments(const MomentsArgs &a, double *state, hipStream_t stream) {
+    const dim3 grid((unsigned) a.blocks), block(kMomentsLanes);
+    constexpr int kA = kMomentsAhead;
+    if (a.mask && a.F > kMomentsLanes) hipLaunchKernelGGL((k_moments<kA, true, true>), grid, block, 0, stream, a);
+    else if (a.mask) hipLaunchKernelGGL((k_moments<kA, true, false>), grid, block, 0, stream, a);
+    else if (a.F > kMomentsLanes) hipLaunchKernelGGL((k_moments<kA, false, true>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((k_moments<kA, false, false>), grid, block, 0, stream, a);
+    hipLaunchKernelGGL(k_moments_merge, dim3((unsigned) ((a.F + kMomentsMergeCols - 1) / kMomentsMergeCols)), dim3(kMomentsLanes), 0, stream,
+                       (const double *) a.partials, (int) a.blocks, (const double *) a.pivot, state, (int) a.F);
+}
+
+// the policy's normaliser from a moments state, every f64 operation rounded once (IEEE division and square root); n == 0: nothing is written
+__global__ void k_normalizer_from_moments(const double *state, int F, double eps, float *mean32, float *inv_std32) {
+    const int f = (int) (blockIdx.x * blockDim.x + threadIdx.x);
+    const double n = state[0];
+    if (f >= F || !(n > 0.0)) return;
+    mean32[f] = (float) state[1 + f];
+    inv_std32[f] = (float) __ddiv_rn(1.0, __dsqrt_rn(__dadd_rn(__ddiv_rn(state[1 + F + f], n), eps)));
+}
+
+void launch_normalizer_from_moments(const double *state, int F, double eps, float *mean32, float *inv_std32, hipStream_t stream) {
+    hipLaunchKernelGGL(k_normalizer_from_moments, dim3((unsigned) ((F + 63) / 64)), dim3(64), 0, stream, state, F, eps, mean32, inv_std32);
+}
+
 // the trainer's layout (nn.Linear: W [out][in] row-major, b [out]) -> the kernel's (chub_policy.h), zeros beyond `out` and `in`
 __global__ void k_policy_relayout(const float *W, const float *b, float *w, float *bias, int out, int in, int k_pad, int tiles) {
     const int64_t total = (int64_t) tiles * k_pad * kPolicyOutTile;

@@ -174,6 +174,8 @@ struct chub_env {
     uint32_t st_fields = 0;
     // the actors made for this handle (chub_policy_create): destroyed before it.  Everything they own lies outside the arena
     std::vector<chub_policy *> policies;
+    // the running feature statistics made for this handle (chub_moments_create): destroyed before it, state and partials outside the arena
+    std::vector<chub_moments *> moments;
     // chub_rollout_gae_device's statistics: the workgroups' partials [ceil(N / 256)][3] f64, allocated at create outside the arena (derived
     // scratch: no snapshot carries it).  One buffer: calls that ask for d_stats must be ordered against each other
     double *d_gae_part = nullptr;
@@ -1052,10 +1054,12 @@ static int create_impl(const chub_config *cfg_in, const char *data_dir, int64_t 
 }
 
 static void policy_free(chub_policy *pol);
+static void moments_free(chub_moments *m);
 
 int chub_destroy(chub_env *e) {
     if (!e) return CHUB_OK;
-    while (!e->policies.empty()) policy_free(e->policies.back());  // (each takes itself off the list)
+    while (!e->moments.empty()) moments_free(e->moments.back());  // (each takes itself off the list)
+    while (!e->policies.empty()) policy_free(e->policies.back());
     if (!e->allocs.empty() || !e->prof_events.empty()) {  // a handle that never reached the device owns nothing there
         (void) hipSetDevice(e->device);
         (void) hipDeviceSynchronize();
@@ -4031,6 +4035,199 @@ int chub_rollout_gae_device(chub_env *e, const chub_gae *g, void *stream) {
     a.partials = g->d_stats ? e->d_gae_part : nullptr;
     a.stats = g->d_stats;
     launch_gae(a, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+}  // extern "C"
+
+// ---- running feature statistics (include/chub.h): the state [1 + 2F] f64 and the partials of the two launches, owned by the object, outside
+// the arena.  The kernels are chub_policy.hip's k_moments / k_moments_merge; here: validation, ownership and the launch shape.
+struct chub_moments {
+    chub_env *env;
+    int32_t F, L, RW;    // columns; lanes along a row and rows per workgroup pass (chub_policy.h, MomentsArgs)
+    int32_t grid;        // workgroups of launch 1 at most, chosen once at create from F and the device's CU count
+    double *d_state;     // [1 + 2F]: n | mean[F] | M2[F] (never moves)
+    double *d_part;      // [grid][1 + 2F], then the pivots [1 + F]
+};
+
+extern "C" {
+
+constexpr int kMomentsMaxF = 512;
+constexpr int kMomentsBlocksPerCu = 4;               // 4 workgroups x 256 lanes x kMomentsAhead loads: 32 KiB in flight per CU
+constexpr size_t kMomentsPartialBytes = 4u << 20;    // the partials stay at most this large
+
+static void moments_free(chub_moments *m) {
+    chub_env *e = m->env;
+    (void) hipSetDevice(e->device);
+    (void) hipDeviceSynchronize();  // (a launch still in flight reads and writes the buffers)
+    if (m->d_state) (void) hipFree(m->d_state);
+    if (m->d_part) (void) hipFree(m->d_part);
+    e->moments.erase(std::remove(e->moments.begin(), e->moments.end(), m), e->moments.end());
+    delete m;
+}
+
+int chub_moments_create(chub_env *e, int32_t F, chub_moments **out) {
+    if (!e || !out) return fail(CHUB_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (F < 1 || F > kMomentsMaxF) return fail(CHUB_ERR_ARG, "chub_moments_create: F is 1 .. " + std::to_string(kMomentsMaxF));
+    if (e->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_moments_create between chub_graph_begin and chub_graph_end (it allocates and synchronises)");
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device));
+    const size_t row = (size_t) (1 + 2 * F) * sizeof(double);
+    int64_t grid = (int64_t) kMomentsBlocksPerCu * (cus > 0 ? cus : 1);
+    if ((size_t) grid * row > kMomentsPartialBytes) grid = (int64_t) (kMomentsPartialBytes / row);
+    chub_moments *m = new chub_moments();
+    m->env = e;
+    m->F = F;
+    m->L = F < kMomentsLanes ? F : kMomentsLanes;
+    m->RW = kMomentsLanes / m->L;
+    m->grid = (int32_t) grid;
+    e->moments.push_back(m);
+    const size_t part = (size_t) grid * row + (size_t) (1 + F) * sizeof(double);
+    if (hipMalloc((void **) &m->d_state, row) != hipSuccess || hipMalloc((void **) &m->d_part, part) != hipSuccess ||
+        hipMemset(m->d_state, 0, row) != hipSuccess || hipMemset(m->d_part, 0, part) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        moments_free(m);
+        (void) hipGetLastError();
+        return fail(CHUB_ERR_HIP, "chub_moments_create: out of device memory");
+    }
+    *out = m;
+    return CHUB_OK;
+}
+
+int chub_moments_destroy(chub_moments *m) {
+    if (!m) return CHUB_OK;
+    if (m->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_moments_destroy between chub_graph_begin and chub_graph_end (it synchronises and frees)");
+    moments_free(m);
+    (void) hipGetLastError();
+    return CHUB_OK;
+}
+
+int chub_moments_update_device(chub_moments *m, const float *d_x, int64_t ld, int64_t R, const uint8_t *d_mask, void *stream) {
+    if (!m || !d_x) return fail(CHUB_ERR_ARG, "null argument");
+    if (ld < m->F) return fail(CHUB_ERR_ARG, "chub_moments_update_device: ld is at least F = " + std::to_string(m->F) + " floats");
+    if (R <= 0) return fail(CHUB_ERR_ARG, "chub_moments_update_device: R >= 1");
+    const int64_t N = m->env->hp.n_envs;
+    if (d_mask && R % N != 0)
+        return fail(CHUB_ERR_ARG, "chub_moments_update_device: with a mask R is a multiple of the handle's " + std::to_string(N) + " envs (row r belongs to env r % N)");
+    HIP_TRY(hipSetDevice(m->env->device));
+    (void) hipGetLastError();
+    MomentsArgs a;
+    a.x = d_x;
+    a.ld = ld;
+    a.R = R;
+    a.passes = (R + m->RW - 1) / m->RW;
+    a.F = m->F;
+    a.L = m->L;
+    a.RW = m->RW;
+    a.blocks = (int32_t) (a.passes < m->grid ? a.passes : m->grid);
+    a.n_envs = N;
+    a.e_step = ((int64_t) a.blocks * m->RW) % N;
+    a.mask = d_mask;
+    a.state = m->d_state;
+    a.partials = m->d_part;
+    a.pivot = m->d_part + (size_t) m->grid * (size_t) (1 + 2 * m->F);
+    launch_moments(a, m->d_state, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_moments_reset_device(chub_moments *m, void *stream) {
+    if (!m) return fail(CHUB_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(m->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipMemsetAsync(m->d_state, 0, (size_t) (1 + 2 * m->F) * sizeof(double), (hipStream_t) stream));
+    return CHUB_OK;
+}
+
+int chub_moments_get(chub_moments *m, double *count, double *mean, double *m2) {
+    if (!m || !count || !mean || !m2) return fail(CHUB_ERR_ARG, "null argument");
+    if (m->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_moments_get between chub_graph_begin and chub_graph_end (it synchronises)");
+    HIP_TRY(hipSetDevice(m->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<double> h((size_t) (1 + 2 * m->F));
+    HIP_TRY(hipMemcpy(h.data(), m->d_state, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    *count = h[0];
+    memcpy(mean, h.data() + 1, (size_t) m->F * sizeof(double));
+    memcpy(m2, h.data() + 1 + m->F, (size_t) m->F * sizeof(double));
+    return CHUB_OK;
+}
+
+int chub_moments_set(chub_moments *m, double count, const double *mean, const double *m2) {
+    if (!m || !mean || !m2) return fail(CHUB_ERR_ARG, "null argument");
+    if (!std::isfinite(count) || count < 0.0) return fail(CHUB_ERR_ARG, "chub_moments_set: count is finite and >= 0");
+    if (m->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_moments_set between chub_graph_begin and chub_graph_end (it copies and synchronises)");
+    HIP_TRY(hipSetDevice(m->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipDeviceSynchronize());  // (an update in flight reads and writes the state)
+    std::vector<double> h((size_t) (1 + 2 * m->F));
+    h[0] = count;
+    memcpy(h.data() + 1, mean, (size_t) m->F * sizeof(double));
+    memcpy(h.data() + 1 + m->F, m2, (size_t) m->F * sizeof(double));
+    HIP_TRY(hipMemcpy(m->d_state, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    return CHUB_OK;
+}
+
+int chub_moments_state_device(chub_moments *m, const double **d_state) {
+    if (!m || !d_state) return fail(CHUB_ERR_ARG, "null argument");
+    *d_state = m->d_state;
+    return CHUB_OK;
+}
+
+// ---- the policy's normaliser, written, read and derived (include/chub.h): all into / out of the policy's own d_norm, which never moves
+static int policy_needs_normalizer(const chub_policy *pol, const char *who) {
+    if (!pol->spec.normalize) return fail(CHUB_ERR_ARG, std::string(who) + ": the policy was created with normalize = 0 (its kernel reads no normaliser)");
+    return CHUB_OK;
+}
+
+int chub_policy_set_normalizer(chub_policy *pol, const float *mean, const float *inv_std) {
+    if (!pol || !mean || !inv_std) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = policy_needs_normalizer(pol, "chub_policy_set_normalizer")) return rc;
+    if (pol->env->capturing)
+        return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_set_normalizer between chub_graph_begin and chub_graph_end (it copies and synchronises: use "
+                                          "chub_policy_set_normalizer_device)");
+    HIP_TRY(hipSetDevice(pol->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipDeviceSynchronize());  // (a policy launch in flight reads the buffer)
+    HIP_TRY(hipMemcpy(pol->d_norm, mean, (size_t) pol->F * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(pol->d_norm + pol->F, inv_std, (size_t) pol->F * sizeof(float), hipMemcpyHostToDevice));
+    return CHUB_OK;
+}
+
+int chub_policy_set_normalizer_device(chub_policy *pol, const float *d_mean, const float *d_inv_std, void *stream) {
+    if (!pol || !d_mean || !d_inv_std) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = policy_needs_normalizer(pol, "chub_policy_set_normalizer_device")) return rc;
+    HIP_TRY(hipSetDevice(pol->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipMemcpyAsync(pol->d_norm, d_mean, (size_t) pol->F * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
+    HIP_TRY(hipMemcpyAsync(pol->d_norm + pol->F, d_inv_std, (size_t) pol->F * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
+    return CHUB_OK;
+}
+
+int chub_policy_get_normalizer_device(chub_policy *pol, float *d_mean, float *d_inv_std, void *stream) {
+    if (!pol || !d_mean || !d_inv_std) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = policy_needs_normalizer(pol, "chub_policy_get_normalizer_device")) return rc;
+    HIP_TRY(hipSetDevice(pol->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipMemcpyAsync(d_mean, pol->d_norm, (size_t) pol->F * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
+    HIP_TRY(hipMemcpyAsync(d_inv_std, pol->d_norm + pol->F, (size_t) pol->F * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
+    return CHUB_OK;
+}
+
+int chub_policy_normalizer_from_moments_device(chub_policy *pol, chub_moments *m, double eps, void *stream) {
+    if (!pol || !m) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = policy_needs_normalizer(pol, "chub_policy_normalizer_from_moments_device")) return rc;
+    if (m->env != pol->env) return fail(CHUB_ERR_ARG, "chub_policy_normalizer_from_moments_device: the policy and the moments were made for different handles");
+    if (m->F != pol->F)
+        return fail(CHUB_ERR_ARG, "chub_policy_normalizer_from_moments_device: the moments have F = " + std::to_string(m->F) + ", the policy's feature row " +
+                                      std::to_string(pol->F));
+    if (!(eps > 0.0) || !std::isfinite(eps)) return fail(CHUB_ERR_ARG, "chub_policy_normalizer_from_moments_device: eps is finite and > 0");
+    HIP_TRY(hipSetDevice(pol->env->device));
+    (void) hipGetLastError();
+    launch_normalizer_from_moments(m->d_state, pol->F, eps, pol->d_norm, pol->d_norm + pol->F, (hipStream_t) stream);
     HIP_TRY(hipGetLastError());
     return CHUB_OK;
 }

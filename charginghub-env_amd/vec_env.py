@@ -236,10 +236,116 @@ class DevicePolicy(object):
             check(self._lib.chub_policy_collect_set(self._env._h, self._p, run, _lib.pile_set(logp_piles), C.byref(r), d_set_bits or None,
                                                     d_obs0 or None, int(first_step), stream or None))
 
+    # ---- the normaliser, written, read and derived (include/chub.h, "running feature statistics"): policies made with normalize=
+    def _norm_pair(self, mean, inv_std):
+        mean = np.ascontiguousarray(mean, dtype=np.float32).ravel()
+        inv_std = np.ascontiguousarray(inv_std, dtype=np.float32).ravel()
+        if mean.shape != (self.n_features,) or inv_std.shape != (self.n_features,):
+            raise ValueError("mean and inv_std must have %d entries (the feature row)" % self.n_features)
+        return mean, inv_std
+
+    def set_normalizer(self, mean, inv_std):
+        """new mean / inv_std [F] from host arrays; synchronises"""
+        mean, inv_std = self._norm_pair(mean, inv_std)
+        check(self._lib.chub_policy_set_normalizer(self._p, _ptr(mean), _ptr(inv_std)))
+
+    def set_normalizer_device(self, d_mean, d_inv_std, stream=0):
+        """the same from device memory, [F] f32 each, as copies on `stream`: a captured graph's next replay evaluates the new normaliser"""
+        check(self._lib.chub_policy_set_normalizer_device(self._p, d_mean or None, d_inv_std or None, stream or None))
+
+    def get_normalizer_device(self, d_mean, d_inv_std, stream=0):
+        """the normaliser the policy evaluates with, copied on `stream` into d_mean / d_inv_std [F] f32 in device memory"""
+        check(self._lib.chub_policy_get_normalizer_device(self._p, d_mean or None, d_inv_std or None, stream or None))
+
+    def normalizer(self):
+        """(mean, inv_std) as float32 numpy arrays (the convenience form: it allocates, synchronises and copies)"""
+        e = self._env
+        out = np.zeros((2, self.n_features), dtype=np.float32)
+        d = C.c_void_p()
+        check(self._lib.chub_malloc_device(e._device, out.nbytes, C.byref(d)))
+        try:
+            check(self._lib.chub_sync(e._h))  # (calls in flight on any stream may write the normaliser)
+            check(self._lib.chub_policy_get_normalizer_device(self._p, d, C.c_void_p(d.value + out.nbytes // 2), None))
+            check(self._lib.chub_copy_to_host(e._device, _ptr(out), d, out.nbytes, None))
+        finally:
+            self._lib.chub_free_device(e._device, d)
+        return out[0].copy(), out[1].copy()
+
+    def normalizer_from_moments(self, m, eps=1e-8, stream=0):
+        """mean = (float) the moments' mean, inv_std = (float) (1 / sqrt(M2 / n + eps)) (the population variance), one launch on `stream`;
+        moments that have counted nothing leave the normaliser alone.  Recordable into a graph."""
+        check(self._lib.chub_policy_normalizer_from_moments_device(self._p, m._m, float(eps), stream or None))
+
     def close(self):
         if getattr(self, "_p", None) and getattr(self._env, "_h", None):
             check(self._lib.chub_policy_destroy(self._p))
         self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceMoments(object):
+    """Running count, mean and M2 per feature on the device (chub_moments_*, include/chub.h "running feature statistics"): made by
+    VecChargingHub.make_moments.  The state is [1 + 2 F] float64 in device memory (n | mean | M2); update_device adds a batch of rows in
+    two launches with every sum's order fixed (the same bits every call), pivoted so that a constant column has M2 == 0 exactly."""
+
+    def __init__(self, env, F):
+        self._env = env
+        self._lib = env._lib
+        self.n_features = int(F)
+        h = C.c_void_p()
+        check(self._lib.chub_moments_create(env._h, self.n_features, C.byref(h)))
+        self._m = h
+
+    def update_device(self, d_x, rows, ld=None, d_mask=0, stream=0):
+        """add `rows` rows of F float32 with row stride ld floats (default F) in device memory.  d_mask [N] u8 in device memory: row r
+        belongs to env r % N and only the rows of the envs it names count.  No synchronisation, recordable into a graph."""
+        ld = self.n_features if ld is None else int(ld)
+        check(self._lib.chub_moments_update_device(self._m, d_x or None, ld, int(rows), d_mask or None, stream or None))
+
+    def reset_device(self, stream=0):
+        """the state back to zeros, on `stream`"""
+        check(self._lib.chub_moments_reset_device(self._m, stream or None))
+
+    def get_raw(self):
+        """(count, mean [F], M2 [F]) as the state holds them, float64; synchronises"""
+        n = C.c_double()
+        mean = np.zeros((self.n_features,), dtype=np.float64)
+        m2 = np.zeros((self.n_features,), dtype=np.float64)
+        check(self._lib.chub_moments_get(self._m, C.byref(n), _ptr(mean), _ptr(m2)))
+        return n.value, mean, m2
+
+    def get(self):
+        """(count, mean [F], var [F]) with var = M2 / count, the population variance (zeros while nothing is counted); synchronises"""
+        n, mean, m2 = self.get_raw()
+        return n, mean, (m2 / n if n > 0 else np.zeros_like(m2))
+
+    def set(self, count, mean, var=None, m2=None):
+        """the state from host values (a checkpoint): count, mean [F] and either var [F] (M2 = var * count) or m2 [F] itself, which
+        get_raw() round-trips bit for bit; synchronises"""
+        if (var is None) == (m2 is None):
+            raise ValueError("set: exactly one of var and m2")
+        mean = np.ascontiguousarray(mean, dtype=np.float64).ravel()
+        m2 = np.ascontiguousarray(np.asarray(var, dtype=np.float64) * float(count) if m2 is None else m2, dtype=np.float64).ravel()
+        if mean.shape != (self.n_features,) or m2.shape != (self.n_features,):
+            raise ValueError("set: mean and var / m2 must have %d entries" % self.n_features)
+        check(self._lib.chub_moments_set(self._m, float(count), _ptr(mean), _ptr(m2)))
+
+    @property
+    def state_ptr(self):
+        """the device address of the state, [1 + 2 F] float64: n | mean | M2 (it never moves)"""
+        p = C.c_void_p()
+        check(self._lib.chub_moments_state_device(self._m, C.byref(p)))
+        return p.value
+
+    def close(self):
+        if getattr(self, "_m", None) and getattr(self._env, "_h", None):
+            check(self._lib.chub_moments_destroy(self._m))
+        self._m = None
 
     def __del__(self):
         try:
@@ -801,6 +907,11 @@ class VecChargingHub(object):
         (mean [F], inv_std [F], clip)."""
         return DevicePolicy(self, layers, inputs, head, hidden_act, squash, normalize)
 
+    def make_moments(self, F):
+        """running count / mean / M2 of F features on the device, bound to this handle -> DeviceMoments (chub_moments_create, 1 <= F <= 512):
+        what DevicePolicy.normalizer_from_moments turns into the policy's normaliser"""
+        return DeviceMoments(self, F)
+
     def next_tick(self):
         """the Philox tick of this handle's next reset or step (chub_next_tick): the tick a sampled policy call made now draws its noise
         under.  Host arithmetic only."""
@@ -974,4 +1085,4 @@ class VecChargingHub(object):
             pass
 
 
-__all__ = ["VecChargingHub", "DevicePolicy", "make_config", "ChubError", "split_env_params", "slice_env_kwargs"]
+__all__ = ["VecChargingHub", "DevicePolicy", "DeviceMoments", "make_config", "ChubError", "split_env_params", "slice_env_kwargs"]

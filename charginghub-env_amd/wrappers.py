@@ -302,6 +302,16 @@ def sampled_entropy(z, log_std, piles=None):
     return h.sum(dim=-1) + (0.5 + log_std + 0.5 * math.log(2.0 * math.pi)).sum(dim=-1)
 
 
+def normalize_features(features, mean, inv_std, clip):
+    """The device actor's input normalisation restated in torch (include/chub.h, "an actor on the device"): features [..., F] raw feature
+    rows (a rollout's ``features``), mean / inv_std [F] (``TorchHubVecEnv.policy_normalizer``), clip the policy's.  The subtraction, the
+    product and the clamp are three f32 operations, each rounded once, as in the kernel: for finite inputs the result is bit for bit what
+    the actor's first layer saw, so the trainer's own network on it reproduces z.  (A NaN feature stays NaN here; the kernel clamps it.)"""
+    import torch
+
+    return torch.clamp((features - mean) * inv_std, min=-float(clip), max=float(clip))
+
+
 class TorchHubVecEnv(object):
     """The hub for an on-device learner: actions in and observations / rewards / dones out are torch CUDA tensors, the
     step runs through the device-pointer entry points on torch's current stream, and nothing is copied through the host
@@ -718,6 +728,45 @@ class TorchHubVecEnv(object):
                             d_final_values=0 if final_values is None else final_values.data_ptr(), gamma=gamma, lam=lam,
                             d_stats=st.data_ptr() if stats else 0, stream=self._stream())
         return (adv, ret, st) if stats else (adv, ret)
+
+    # ---- a normaliser that follows the rollouts (chub_moments_*, chub_policy_normalizer_from_moments_device)
+    def update_normalizer(self, policy, rollout, moments=None, eps=1e-8, mask=None):
+        """Running observation statistics, VecNormalize-style, with nothing read back: add the raw feature rows of a ``collect`` rollout
+        (``rollout["features"]`` [T, N, F]) to `moments` (a DeviceMoments; None: one the adapter makes and keeps per policy), then set the
+        policy's normaliser from them, mean and 1 / sqrt(var + eps) -- three launches on torch's current stream.  mask: a uint8 / bool CUDA
+        tensor [N]; only the rows of the envs it names count.  The rollout's ``logp`` was recorded under the normaliser in force BEFORE this
+        call: take ``policy_normalizer(policy)`` first if the trainer is to reproduce z from ``features`` (``normalize_features``).  Returns
+        the moments object."""
+        torch = self.torch
+        feats = rollout["features"]
+        F = policy.n_features
+        if not (self._on_device(feats) and feats.dtype == torch.float32 and feats.is_contiguous() and feats.dim() == 3
+                and tuple(feats.shape[1:]) == (self.num_envs, F)):
+            raise AssertionError("rollout['features'] must be a contiguous float32 tensor on %s of shape (T, %d, %d)" % (self.device, self.num_envs, F))
+        if moments is None:
+            cache = getattr(self, "_moments", None)
+            if cache is None:
+                cache = self._moments = {}
+            moments = cache.get(id(policy))
+            if moments is None:
+                moments = cache[id(policy)] = self.vec.make_moments(F)
+        d_mask = 0
+        if mask is not None:
+            if not (self._on_device(mask) and mask.dtype in (torch.uint8, torch.bool) and mask.is_contiguous() and tuple(mask.shape) == (self.num_envs,)):
+                raise AssertionError("mask must be a contiguous uint8 or bool tensor on %s of shape (%d,)" % (self.device, self.num_envs))
+            d_mask = mask.data_ptr()
+        moments.update_device(feats.data_ptr(), int(feats.shape[0]) * self.num_envs, ld=F, d_mask=d_mask, stream=self._stream())
+        policy.normalizer_from_moments(moments, eps=eps, stream=self._stream())
+        return moments
+
+    def policy_normalizer(self, policy):
+        """(mean, inv_std): the normaliser `policy` evaluates with, as two new float32 [F] CUDA tensors filled on torch's current stream
+        (chub_policy_get_normalizer_device): no synchronisation"""
+        torch = self.torch
+        mean = torch.empty((policy.n_features,), dtype=torch.float32, device=self.device)
+        inv_std = torch.empty_like(mean)
+        policy.get_normalizer_device(mean.data_ptr(), inv_std.data_ptr(), stream=self._stream())
+        return mean, inv_std
 
     def copy_envs(self, src_idx, dst_idx, source=None):
         """env dst_idx[i] becomes a clone of env src_idx[i] of `source` (another TorchHubVecEnv; default: this one), on torch's current

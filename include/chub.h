@@ -960,6 +960,64 @@ typedef struct chub_gae {
 } chub_gae;
 int chub_rollout_gae_device(chub_env *env, const chub_gae *g, void *stream);
 
+/* ---- running feature statistics: a normaliser that follows the rollouts ----------------------------------------------------------------
+ * The actor's input normalisation x <- clip((x - mean[f]) * inv_std[f]) is given at chub_policy_create.  A trainer that keeps running
+ * observation statistics (stable-baselines' VecNormalize / RunningMeanStd) needs them computed where the rollout lies, and needs to hand them
+ * to the policy without destroying it.  This section adds both: a moments object that accumulates count, mean and M2 per feature on the
+ * device, and setters / a getter of a policy's normaliser, one of which derives it from the moments -- all in-stream and recordable.
+ *   The state.  [1 + 2F] f64 in device memory: n | mean[F] | M2[F] (M2 = the sum of squared deviations from the mean: the population
+ *     variance is M2 / n).  Zeros after create; it never moves.  State and partials are allocated at create, OUTSIDE the arena: chub_state_size
+ *     and snapshots are unchanged; chub_moments_get / chub_moments_set are how a checkpoint carries the state.  The object is bound to its
+ *     handle; chub_destroy destroys a handle's moments objects first, as it does its policies.
+ *   chub_moments_update_device: R rows of F floats with row stride ld >= F floats -- a rollout's d_features (R = T N, ld = F), or the
+ *     observations inside d_packed (F = D, ld = D + 2).  With d_mask [N] u8 in device memory row r belongs to env r % N (R a multiple of N) and
+ *     only the rows of envs with a non-zero byte count; the rows of other envs are not read.  Manners are chub_rollout_gae_device's: no
+ *     simulation state read, no tick, no synchronisation, no allocation; recordable between chub_graph_begin and chub_graph_end without
+ *     counting towards the even number of resets + steps.  The partials are one buffer of the object's: calls on one object must be ordered
+ *     against each other (the same stream, or an event).
+ *   Definition, per feature f, all in f64, every operation rounded once:
+ *       K     = n > 0 ? mean[f] : (double) x[0][f]       the pivot; row 0 serves whether it is masked or not
+ *       d     = (double) x - K
+ *       n_b   = the counted rows,  S1 = sum d,  S2 = sum d d  over them
+ *       M2_b  = max(S2 - S1 S1 / n_b, 0)
+ *       n'    = n + n_b
+ *       n > 0:   mean' = K + S1 / n',   M2' = (M2 + M2_b) + (S1 / n_b)^2 (n n_b / n')          (Chan et al.)
+ *       n == 0:  mean' = K + S1 / n_b,  M2' = M2_b
+ *     n_b == 0 leaves the state untouched: an all-zero mask writes nothing.  Non-finite inputs give a non-finite state; nothing is checked on
+ *     the device.  The pivot makes a constant column come out with M2 == 0 exactly and removes the cancellation of a raw sum of squares.  The
+ *     order of the sums is unspecified but fixed for (R, F, ld, N) on one device: two calls on the same data and state give identical bits.  No
+ *     atomics.  Two launches: the rows' sums per workgroup (the grid is chosen once at create from F and the device's compute units, so the
+ *     rows a workgroup takes depend on (R, F) only), then the partials' sum and the merge.
+ *   chub_moments_reset_device: the state back to zeros, as a memset on `stream`; recordable.
+ *   chub_moments_get / chub_moments_set: the state to / from host memory (count, mean [F], m2 [F]); both synchronise; identical bits round trip.
+ *   chub_moments_state_device: the address of the state, for a trainer that reads it in its own kernels.
+ *   The policy's normaliser.  All four calls need a policy created with normalize = 1 (a normalize = 0 policy keeps its null pointers, and the
+ *     kernel's argument block does not change).  chub_policy_set_normalizer: mean / inv_std [F] from host memory (it synchronises).  The device
+ *     forms are copies, or one tiny launch, on `stream` into / out of the policy's own buffer: recordable, no synchronisation.  The buffers
+ *     the policy kernel reads never move, so a captured graph's next replay evaluates the new normaliser.  chub_policy_get_normalizer_device
+ *     copies out, [F] each: what the trainer needs to reproduce z from a rollout's raw d_features.
+ *     chub_policy_normalizer_from_moments_device: in one launch mean32[f] = (float) mean[f] and
+ *     inv_std32[f] = (float) (1.0 / sqrt(M2[f] / n + eps)): the population variance, as RunningMeanStd uses; IEEE f64 division and square root,
+ *     every operation rounded once.  n == 0 leaves the normaliser as it is, decided on the device with no host read.
+ * Refusals, all with a message and before any device work.  CHUB_ERR_ARG: null arguments; F outside 1 .. 512; ld < F; R <= 0; a mask with
+ * R % N != 0; chub_moments_set with count < 0 or not finite; a normaliser call on a normalize = 0 policy; from_moments with objects of
+ * different F or different handles, or eps not finite and > 0.  CHUB_ERR_UNSUPPORTED: chub_moments_create / destroy / get / set and
+ * chub_policy_set_normalizer between chub_graph_begin and chub_graph_end.
+ * Out of scope: accumulating inside the sampled actor launch, reward / return scaling, the multi-GPU hosts (an all-reduce of [1 + 2F]
+ * doubles is the trainer's), anything in the snapshot. */
+typedef struct chub_moments chub_moments;
+int chub_moments_create(chub_env *env, int32_t F, chub_moments **out);   /* 1 <= F <= 512 */
+int chub_moments_destroy(chub_moments *m);
+int chub_moments_update_device(chub_moments *m, const float *d_x, int64_t ld, int64_t R, const uint8_t *d_mask /* [N] or NULL */, void *stream);
+int chub_moments_reset_device(chub_moments *m, void *stream);
+int chub_moments_get(chub_moments *m, double *count, double *mean /* [F] */, double *m2 /* [F] */);  /* synchronises */
+int chub_moments_set(chub_moments *m, double count, const double *mean, const double *m2);           /* synchronises */
+int chub_moments_state_device(chub_moments *m, const double **d_state);  /* [1 + 2F] f64: n | mean[F] | M2[F] */
+int chub_policy_set_normalizer(chub_policy *pol, const float *mean, const float *inv_std);               /* host; synchronises */
+int chub_policy_set_normalizer_device(chub_policy *pol, const float *d_mean, const float *d_inv_std, void *stream);
+int chub_policy_get_normalizer_device(chub_policy *pol, float *d_mean, float *d_inv_std, void *stream);  /* copies out, [F] each */
+int chub_policy_normalizer_from_moments_device(chub_policy *pol, chub_moments *m, double eps, void *stream);
+
 /* The FCEV waiting list is unbounded as in the reference (HYD:264-265): the entries a list that still gets served can
  * hold are kept one by one, and once no prefix of it fits into 15 minutes any more (HYD:270-276: nobody is served again
  * until reset and the list only grows) its entries are folded into their count and running sums, which is all the
