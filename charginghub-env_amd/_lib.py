@@ -423,6 +423,15 @@ def load_library():
         "chub_moments_state_device": (I, [P, C.POINTER(P)]),
         "chub_policy_set_normalizer": (I, [P, P, P]), "chub_policy_set_normalizer_device": (I, [P, P, P, P]),
         "chub_policy_get_normalizer_device": (I, [P, P, P, P]), "chub_policy_normalizer_from_moments_device": (I, [P, P, C.c_double, P]),
+        "chub_population_param_count": (I, [C.POINTER(ChubConfig), C.POINTER(ChubPolicySpec), C.POINTER(L)]),
+        "chub_population_create": (I, [P, C.c_int32, C.c_uint64, C.POINTER(P)]), "chub_population_destroy": (I, [P]),
+        "chub_population_perturb_device": (I, [P, P, P, C.c_float, C.c_uint32, P]),
+        "chub_population_set_member_device": (I, [P, C.c_int32, C.c_int32, P, P, P]),
+        "chub_population_get_member_device": (I, [P, C.c_int32, C.c_int32, P, P, P]),
+        "chub_population_set_member": (I, [P, C.c_int32, C.c_int32, P, P]), "chub_population_get_member": (I, [P, C.c_int32, C.c_int32, P, P]),
+        "chub_population_copy_members_device": (I, [P, P, P, C.c_int32, P]),
+        "chub_population_act_device": (I, [P, P, P, L, P, P, P, P, P]), "chub_population_run_steps": (I, [P, P, I, P, P, P, L, L, P]),
+        "chub_population_es_gradient_device": (I, [P, P, C.c_uint32, P, P, P]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -463,7 +472,10 @@ EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "ch
             "chub_pile_set_device", "chub_policy_sample_set_device", "chub_policy_collect_set", "chub_rollout_gae_device",
             "chub_moments_create", "chub_moments_destroy", "chub_moments_update_device", "chub_moments_reset_device", "chub_moments_get", "chub_moments_set",
             "chub_moments_state_device", "chub_policy_set_normalizer", "chub_policy_set_normalizer_device", "chub_policy_get_normalizer_device",
-            "chub_policy_normalizer_from_moments_device"]
+            "chub_policy_normalizer_from_moments_device",
+            "chub_population_param_count", "chub_population_create", "chub_population_destroy", "chub_population_perturb_device",
+            "chub_population_set_member_device", "chub_population_get_member_device", "chub_population_set_member", "chub_population_get_member",
+            "chub_population_copy_members_device", "chub_population_act_device", "chub_population_run_steps", "chub_population_es_gradient_device"]
 
 
 def check(rc):

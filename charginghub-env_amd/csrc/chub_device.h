@@ -76,7 +76,8 @@ enum Site : uint32_t {
     SITE_HVSOC = 9,   // index = FCEV arrival number; polar trials
     SITE_OU = 10,     // index = 0 pv, 1 wd, 2 price; polar trials
     SITE_DAY = 11,    // word 0 -> pv day, word 1 -> wd day (reset)
-    SITE_POLICY = 15  // index = 0 pile draws (block b >> 2, word b & 3), 1 Gaussian outputs (block 0, word i); under the POLICY's key (chub_policy.hip)
+    SITE_POLICY = 15, // index = 0 pile draws (block b >> 2, word b & 3), 1 Gaussian outputs (block 0, word i); under the POLICY's key (chub_policy.hip)
+    SITE_POPULATION = 16  // index = layer; block (row << 8 | k >> 2) of generation g and pair j, word k & 3; under the POPULATION's key (chub_policy.hip)
 };
 
 // StationRec::pkd, the integer part of a station record: bits 0-3 Station::line (<= max_line = 10), bits 4-15

@@ -28,6 +28,8 @@ constexpr int kPolicyLdsRows = 512;
 // rows: chub_policy_set_exploration refuses a policy whose images leave fewer (the deterministic fit rule is unchanged)
 constexpr uint32_t kPolicySite = 15u;
 constexpr int kPolicyLogpRows = kPolicyMaxWaves;
+// A population (include/chub.h, "a population of actors"): the Philox site of the perturbation noise (SITE_POPULATION of chub_device.h)
+constexpr uint32_t kPopulationSite = 16u;
 
 // Device weight layout of one layer (built by k_policy_relayout from the trainer's row-major [out][in]): per tile of 32 outputs the
 // transposed block [k_pad][32], zero beyond `in` and `out` -- lane l of a wave reads element 64 s + l of a tile at k-step s, which is
@@ -87,7 +89,19 @@ struct PolicySampleSetArgs : PolicySampleArgs {
     const uint32_t *set;          // [N][2 W] u32 = [N][W] u64, little-endian halves: chub_pile_set_device's words
 };
 
+// the deterministic launch over a population (include/chub.h, "a population of actors"): member m's weights serve the tiles of 32 envs
+// m tiles_per_member .. (m + 1) tiles_per_member - 1 -- a tile belongs to one member -- and lie m w_stride[l] / m b_stride[l] floats
+// behind layer[l].w / layer[l].b, which point at member 0.  Workgroup b takes tile xcd_order(b) (chub_kernels.hip): the workgroups of
+// one XCD take a contiguous eighth of the tiles, so a member's tiles share an L2.  Everything else is PolicyArgs' launch
+struct PolicyPopArgs : PolicyArgs {
+    static constexpr bool kPop = true;
+    int32_t tiles_per_member;     // E / 32
+    int32_t pad_;
+    int64_t w_stride[kPolicyMaxLayers], b_stride[kPolicyMaxLayers];
+};
+
 void launch_policy(const PolicyArgs &a, int waves, hipStream_t stream);
+void launch_policy_pop(const PolicyPopArgs &a, int waves, hipStream_t stream);
 void launch_policy_sample(const PolicySampleArgs &a, int waves, hipStream_t stream);
 void launch_policy_sample_set(const PolicySampleSetArgs &a, int waves, hipStream_t stream);
 
@@ -127,6 +141,33 @@ void launch_moments(const MomentsArgs &a, double *state, hipStream_t stream);
 void launch_normalizer_from_moments(const double *state, int F, double eps, float *mean32, float *inv_std32, hipStream_t stream);
 // W [out][in] row-major and b [out] in device memory -> the layout above
 void launch_policy_relayout(const float *d_W, const float *d_b, float *d_w, float *d_bias, int out, int in, int k_pad, int tiles, hipStream_t stream);
+
+
+// ---- a population's weights (include/chub.h, "a population of actors").  One layer of every member: member m's block of the layout above
+// lies m * stride floats behind w / bias.  Layer l is the augmented matrix [W | b], columns k = 0 .. in (column `in` the bias); a lane
+// owns (pair j, output row, column group k >> 2) and one Philox block: eps of column k is normal_from_word of word k & 3 of the block with
+// counter (row << 8 | k >> 2, 16 << 16 | l, generation, j) under the population's key
+struct PopLayerArgs {
+    float *w, *bias;              // member 0's [tiles][k_pad][32] and [tiles * 32]
+    int64_t stride;               // floats from a member's block to the next member's
+    int32_t out, in, k_pad, tiles, layer;
+    int32_t pairs;                // P / 2
+    uint32_t key[2], generation;
+    const float *normal_icdf, *normal_tail;  // [4097] each: the handle's tables
+};
+// theta + / - sigma eps into members 2j / 2j + 1, fused with the re-layout.  device_layout == 0: W [out][in], b [out] (the trainer's);
+// != 0: W = a [tiles][k_pad][32] block, b = [tiles * 32] (the centre policy's own weights)
+void launch_population_perturb(const PopLayerArgs &a, const float *W, const float *b, int device_layout, float sigma, hipStream_t stream);
+// partial[c][item][4] f64: the sum over the pairs j of chunk c, ascending, of (util[2j] - util[2j + 1]) eps; item = row * groups + k >> 2,
+// groups = in / 4 + 1.  Then g = (float) (the chunks' sum, ascending) in the trainer's layout
+void launch_population_es_gradient(const PopLayerArgs &a, const float *d_util, int chunk_pairs, int chunks, double *partials, float *gW, float *gb,
+                                   hipStream_t stream);
+// the kernel's layout of one member's layer -> W [out][in], b [out]
+void launch_policy_unlayout(const float *d_w, const float *d_bias, float *d_W, float *d_b, int out, int in, int k_pad, hipStream_t stream);
+// member dst[i] <- member src[i], i = 0 .. count - 1, all sources read (into `stage`, [count][member_floats]) before any destination is
+// written; a pair with an index outside 0 .. P - 1 is skipped; of two pairs with one destination the later wins
+void launch_population_copy(float *params, float *stage, int64_t member_floats, int P, const int32_t *d_src, const int32_t *d_dst, int count,
+                            hipStream_t stream);
 
 }  // namespace chub
 #endif

@@ -25,6 +25,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "chub_policy.h"
 
 namespace chub {
@@ -78,8 +80,20 @@ constexpr float kHalfLn2Pi = 0.918938533204672742f;  // 0.5 ln 2 pi
 // softplus(x) = max(x, 0) + log1pf(expf(-|x|))
 __device__ __forceinline__ float policy_softplus(float x) { return __fadd_rn(fmaxf(x, 0.0f), log1pf(expf(-fabsf(x)))); }
 
-// Args = PolicyArgs: the deterministic actor.  Args = PolicySampleArgs: the same chain to the pre-squash outputs z, then a draw from the
-// actor's distribution, its log-probability and (if asked for) the raw feature row.  Args = PolicySampleSetArgs: the sampled launch with a
+// whether an argument block is a population's (Args::kPop, PolicyPopArgs only: the other blocks do not name the flag)
+template <typename Args, typename = void>
+struct PolicyIsPop {
+    static constexpr bool value = false;
+};
+template <typename Args>
+struct PolicyIsPop<Args, std::enable_if_t<Args::kPop>> {
+    static constexpr bool value = true;
+};
+
+// Args = PolicyArgs: the deterministic actor.  Args = PolicyPopArgs: the same launch with the weights of the workgroup's member (a
+// population: the chain, the order and the squash are the deterministic launch's; what differs is where w and b point and which tile
+// of 32 envs a workgroup takes).  Args = PolicySampleArgs: the same chain to the pre-squash outputs z, then a draw from the actor's
+// distribution, its log-probability and (if asked for) the raw feature row.  Args = PolicySampleSetArgs: the sampled launch with a
 // pile's Bernoulli term added to the log-probability only where the pile's bit is in the env's set (one u32 word per accumulator tile); the
 // draws, the outputs and the order of the terms that remain are the sampled launch's.
 template <typename Args>
@@ -89,7 +103,14 @@ __global__ __launch_bounds__(64 * kPolicyMaxWaves) void k_policy(const Args a) {
     extern __shared__ float lds[];
     const int tid = (int) threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = (int) (blockDim.x >> 6), nt = (int) blockDim.x;
     const int col = lane & 31, half = lane >> 5;
-    const int64_t env0 = (int64_t) blockIdx.x * kPolicyEnvTile;
+    int64_t tile = (int64_t) blockIdx.x;
+    if constexpr (PolicyIsPop<Args>::value) {
+        // (a population) the dispatcher hands workgroup b to XCD b % 8, each with an L2 of its own: XCD x takes ONE contiguous eighth of
+        // the tiles (xcd_order of chub_kernels.hip), so a member's tiles meet in one L2 and an XCD reads an eighth of the weights
+        const uint32_t nb = gridDim.x, q = nb >> 3, r = nb & 7u, x = blockIdx.x & 7u;
+        tile = (int64_t) (x * q + (x < r ? x : r) + (blockIdx.x >> 3));
+    }
+    const int64_t env0 = tile * kPolicyEnvTile;
     float *const P = lds;
     float *const Q = lds + (size_t) a.q_row0 * kPolicyEnvTile;
 
@@ -125,6 +146,8 @@ __global__ __launch_bounds__(64 * kPolicyMaxWaves) void k_policy(const Args a) {
 
     const int64_t env = env0 + col;
     const bool store = env < a.n_envs && (!a.mask || a.mask[env] != 0);
+    [[maybe_unused]] int64_t member = 0;  // (a population) whose weights this workgroup's 32 envs are served with
+    if constexpr (PolicyIsPop<Args>::value) member = tile / a.tiles_per_member;
     [[maybe_unused]] float logp = 0.0f;  // (sampling) this lane's terms: its rows of its wave's tiles, in ascending tile order
 
 #pragma unroll
@@ -138,9 +161,11 @@ __global__ __launch_bounds__(64 * kPolicyMaxWaves) void k_policy(const Args a) {
             for (int t = wave; t < L.tiles; t += nw) {
                 f32x16 acc;
                 const float *bt = L.b + t * kPolicyOutTile + 4 * half;
+                if constexpr (PolicyIsPop<Args>::value) bt += member * a.b_stride[l];  // (a population: the block of the workgroup's member)
 #pragma unroll
                 for (int r = 0; r < 16; r++) acc[r] = bt[(r & 3) + 8 * (r >> 2)];
                 const float *wt = L.w + (size_t) t * (size_t) L.k_pad * kPolicyOutTile + lane;
+                if constexpr (PolicyIsPop<Args>::value) wt += member * a.w_stride[l];
                 const float *xs = src + lane;
                 for (int s = 0; s < ksteps; s++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wt[64 * s], xs[64 * s], acc, 0, 0, 0);
 
@@ -263,6 +288,14 @@ void launch_policy(const PolicyArgs &a, int waves, hipStream_t stream) {
     const int64_t nb = (a.n_envs + kPolicyEnvTile - 1) / kPolicyEnvTile;
     const size_t lds_bytes = (size_t) (a.q_row0 + policy_q_rows(a)) * kPolicyEnvTile * sizeof(float);
     hipLaunchKernelGGL(k_policy<PolicyArgs>, dim3((unsigned) nb), dim3(64u * (unsigned) waves), lds_bytes, stream, a);
+}
+
+// a population's launch: the deterministic launch's grid and LDS (the caller has checked that N = P tiles_per_member 32)
+void launch_policy_pop(const PolicyPopArgs &a, int waves, hipStream_t stream) {
+    if (a.n_envs <= 0) return;
+    const int64_t nb = (a.n_envs + kPolicyEnvTile - 1) / kPolicyEnvTile;
+    const size_t lds_bytes = (size_t) (a.q_row0 + policy_q_rows(a)) * kPolicyEnvTile * sizeof(float);
+    hipLaunchKernelGGL(k_policy<PolicyPopArgs>, dim3((unsigned) nb), dim3(64u * (unsigned) waves), lds_bytes, stream, a);
 }
 
 // the sampled launch: the same grid, kPolicyLogpRows more rows of LDS behind the two images (the caller has checked that they fit)
@@ -564,6 +597,143 @@ void launch_policy_relayout(const float *d_W, const float *d_b, float *d_w, floa
     int64_t nb = (total + 255) / 256;
     if (nb > 1024) nb = 1024;
     hipLaunchKernelGGL(k_policy_relayout, dim3((unsigned) nb), dim3(256), 0, stream, d_W, d_b, d_w, d_bias, out, in, k_pad, tiles);
+}
+
+// the way back: one layer in the kernel's layout -> W [out][in], b [out]; one lane per element of [W | b]
+__global__ void k_policy_unlayout(const float *w, const float *bias, float *W, float *b, int out, int in, int k_pad) {
+    const int64_t idx = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t) out * (in + 1)) return;
+    const int n = (int) (idx / (in + 1)), k = (int) (idx - (int64_t) n * (in + 1));
+    if (k < in) W[(int64_t) n * in + k] = w[((int64_t) (n >> 5) * k_pad + k) * kPolicyOutTile + (n & 31)];
+    else b[n] = bias[n];
+}
+
+void launch_policy_unlayout(const float *d_w, const float *d_bias, float *d_W, float *d_b, int out, int in, int k_pad, hipStream_t stream) {
+    const int64_t total = (int64_t) out * (in + 1);
+    hipLaunchKernelGGL(k_policy_unlayout, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, stream, d_w, d_bias, d_W, d_b, out, in, k_pad);
+}
+
+// ---- a population's weights (include/chub.h, "a population of actors"; the lane layout is chub_policy.h's PopLayerArgs)
+constexpr int kPopLanes = 256;
+
+__device__ __forceinline__ PolicyU4 population_block(const PopLayerArgs &a, int row, int group, uint32_t pair) {
+    return policy_philox4x32_10(((uint32_t) row << 8) | (uint32_t) group, (kPopulationSite << 16) | (uint32_t) a.layer, a.generation, pair, a.key[0],
+                                a.key[1]);
+}
+
+// Lane (pair j, tile t, column group g, row i of the tile), i fastest: consecutive lanes write consecutive words of [k][32].  ONE Philox
+// block gives the lane's four columns of both members of the pair; d = sigma eps is rounded once, theta + d and theta - d once each.
+// Rows beyond `out` and the column beyond `in` of an odd layer are written as zeros: noise there would act as extra hidden units
+__global__ __launch_bounds__(kPopLanes) void k_population_perturb(const PopLayerArgs a, const float *W, const float *b, int device_layout, float sigma) {
+    const int groups = a.in / 4 + 1;
+    const int64_t idx = (int64_t) blockIdx.x * kPopLanes + threadIdx.x;
+    if (idx >= (int64_t) a.pairs * a.tiles * groups * kPolicyOutTile) return;
+    const int i = (int) (idx & 31);
+    int64_t q = idx >> 5;
+    const int g = (int) (q % groups);
+    q /= groups;
+    const int t = (int) (q % a.tiles), j = (int) (q / a.tiles);
+    const int row = t * kPolicyOutTile + i;
+    const bool live = row < a.out;
+    PolicyU4 blk = {{0u, 0u, 0u, 0u}};
+    if (live) blk = population_block(a, row, g, (uint32_t) j);
+    float *const w0 = a.w + (int64_t) (2 * j) * a.stride + (int64_t) t * a.k_pad * kPolicyOutTile + i, *const w1 = w0 + a.stride;
+    float *const b0 = a.bias + (int64_t) (2 * j) * a.stride + row, *const b1 = b0 + a.stride;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const int k = 4 * g + c;
+        float plus = 0.0f, minus = 0.0f;
+        if (live && k <= a.in) {
+            float theta;
+            if (k == a.in) theta = b[row];
+            else theta = device_layout ? W[((int64_t) t * a.k_pad + k) * kPolicyOutTile + i] : W[(int64_t) row * a.in + k];
+            const float d = __fmul_rn(sigma, policy_normal_from_word(a.normal_icdf, a.normal_tail, blk.v[c]));
+            plus = __fadd_rn(theta, d);
+            minus = __fsub_rn(theta, d);
+        }
+        if (k < a.k_pad) {
+            w0[(int64_t) k * kPolicyOutTile] = k < a.in ? plus : 0.0f;
+            w1[(int64_t) k * kPolicyOutTile] = k < a.in ? minus : 0.0f;
+        }
+        if (k == a.in) {
+            *b0 = plus;
+            *b1 = minus;
+        }
+    }
+}
+
+void launch_population_perturb(const PopLayerArgs &a, const float *W, const float *b, int device_layout, float sigma, hipStream_t stream) {
+    const int64_t total = (int64_t) a.pairs * a.tiles * (a.in / 4 + 1) * kPolicyOutTile;
+    hipLaunchKernelGGL(k_population_perturb, dim3((unsigned) ((total + kPopLanes - 1) / kPopLanes)), dim3(kPopLanes), 0, stream, a, W, b, device_layout,
+                       sigma);
+}
+
+// The ES gradient estimate.  Launch 1: lane (chunk c = blockIdx.y, item = row groups + column group) regenerates the block of every pair
+// of its chunk in ascending j and adds du_j eps to four f64 sums, product and sum each rounded once.  Launch 2: one lane per parameter adds
+// the chunks' sums in ascending c, rounds once to f32 and stores in the trainer's layout.  No atomics: the order is a function of
+// (P, the layer's shape, the chunk size) alone
+__global__ __launch_bounds__(kPopLanes) void k_population_es_partial(const PopLayerArgs a, const float *util, int chunk_pairs, double *partials) {
+    const int groups = a.in / 4 + 1, items = a.out * groups;
+    const int item = (int) (blockIdx.x * kPopLanes + threadIdx.x), c = (int) blockIdx.y;
+    if (item >= items) return;
+    const int row = item / groups, g = item - row * groups;
+    const int j0 = c * chunk_pairs, j1 = j0 + chunk_pairs < a.pairs ? j0 + chunk_pairs : a.pairs;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int j = j0; j < j1; j++) {
+        const double du = __dsub_rn((double) util[2 * j], (double) util[2 * j + 1]);
+        const PolicyU4 blk = population_block(a, row, g, (uint32_t) j);
+#pragma unroll
+        for (int w = 0; w < 4; w++)
+            s[w] = __dadd_rn(s[w], __dmul_rn(du, (double) policy_normal_from_word(a.normal_icdf, a.normal_tail, blk.v[w])));
+    }
+    double *p = partials + ((int64_t) c * items + item) * 4;
+#pragma unroll
+    for (int w = 0; w < 4; w++) p[w] = s[w];
+}
+
+__global__ __launch_bounds__(kPopLanes) void k_population_es_merge(const double *partials, int chunks, float *gW, float *gb, int out, int in) {
+    const int64_t idx = (int64_t) blockIdx.x * kPopLanes + threadIdx.x;
+    if (idx >= (int64_t) out * (in + 1)) return;
+    const int groups = in / 4 + 1;
+    const int row = (int) (idx / (in + 1)), k = (int) (idx - (int64_t) row * (in + 1));
+    const int64_t items = (int64_t) out * groups, at = ((int64_t) row * groups + (k >> 2)) * 4 + (k & 3);
+    double s = 0.0;
+    for (int c = 0; c < chunks; c++) s = __dadd_rn(s, partials[(int64_t) c * items * 4 + at]);
+    if (k < in) gW[(int64_t) row * in + k] = (float) s;
+    else gb[row] = (float) s;
+}
+
+void launch_population_es_gradient(const PopLayerArgs &a, const float *d_util, int chunk_pairs, int chunks, double *partials, float *gW, float *gb,
+                                   hipStream_t stream) {
+    const int items = a.out * (a.in / 4 + 1);
+    hipLaunchKernelGGL(k_population_es_partial, dim3((unsigned) ((items + kPopLanes - 1) / kPopLanes), (unsigned) chunks), dim3(kPopLanes), 0, stream, a,
+                       d_util, chunk_pairs, partials);
+    const int64_t total = (int64_t) a.out * (a.in + 1);
+    hipLaunchKernelGGL(k_population_es_merge, dim3((unsigned) ((total + kPopLanes - 1) / kPopLanes)), dim3(kPopLanes), 0, stream,
+                       (const double *) partials, chunks, gW, gb, a.out, a.in);
+}
+
+// lane x takes float x of every member named: first every source into its column of the staging rows, then every destination from there.
+// A lane meets no other lane's floats, so one launch reads all sources before it writes any destination (a swap is a swap)
+__global__ __launch_bounds__(kPopLanes) void k_population_copy(float *params, float *stage, int64_t member_floats, int P, const int32_t *src,
+                                                               const int32_t *dst, int count) {
+    const int64_t x = (int64_t) blockIdx.x * kPopLanes + threadIdx.x;
+    if (x >= member_floats) return;
+    for (int i = 0; i < count; i++) {
+        const int32_t s = src[i], d = dst[i];
+        if (s >= 0 && s < P && d >= 0 && d < P) stage[(int64_t) i * member_floats + x] = params[(int64_t) s * member_floats + x];
+    }
+    for (int i = 0; i < count; i++) {
+        const int32_t s = src[i], d = dst[i];
+        if (s >= 0 && s < P && d >= 0 && d < P) params[(int64_t) d * member_floats + x] = stage[(int64_t) i * member_floats + x];
+    }
+}
+
+void launch_population_copy(float *params, float *stage, int64_t member_floats, int P, const int32_t *d_src, const int32_t *d_dst, int count,
+                            hipStream_t stream) {
+    if (count <= 0) return;
+    hipLaunchKernelGGL(k_population_copy, dim3((unsigned) ((member_floats + kPopLanes - 1) / kPopLanes)), dim3(kPopLanes), 0, stream, params, stage,
+                       member_floats, P, d_src, d_dst, count);
 }
 
 }  // namespace chub

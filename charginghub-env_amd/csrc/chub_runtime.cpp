@@ -3485,6 +3485,7 @@ struct chub_policy {
     uint32_t key[2];
     float *d_log_std;
     std::vector<void *> allocs;
+    std::vector<chub_population *> populations;  // made for this policy (chub_population_create): destroyed before it
 };
 
 extern "C" {
@@ -3559,8 +3560,11 @@ int chub_policy_input_width(const chub_config *cfg, const chub_policy_spec *spec
     return CHUB_OK;
 }
 
+static void population_free(chub_population *pop);
+
 static void policy_free(chub_policy *pol) {
     chub_env *e = pol->env;
+    while (!pol->populations.empty()) population_free(pol->populations.back());
     (void) hipSetDevice(e->device);
     (void) hipDeviceSynchronize();  // (a launch still in flight reads the weights and the scratch)
     for (void *p : pol->allocs) (void) hipFree(p);
@@ -3754,28 +3758,47 @@ static int policy_feature_blocks(chub_env *e, chub_policy *pol, const float *d_o
     return CHUB_OK;
 }
 
-int chub_policy_act_device(chub_env *e, chub_policy *pol, const float *d_obs, int64_t ld_obs, const uint8_t *d_mask, float *d_actions,
-                           uint64_t *d_pile_bits, float *d_tail, void *stream) {
-    if (!e || !pol) return fail(CHUB_ERR_ARG, "null argument");
+// everything a deterministic evaluation refuses for, with nothing enqueued yet
+static int policy_act_check(const chub_env *e, const chub_policy *pol, const float *d_obs, int64_t ld_obs, const float *d_actions,
+                            const uint64_t *d_pile_bits, const float *d_tail) {
     if (pol->env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
-    const chub_policy_spec &sp = pol->spec;
     if (const int rc = policy_check_obs(e, pol, d_obs, ld_obs)) return rc;
     if (!d_actions && !d_pile_bits) return fail(CHUB_ERR_ARG, "chub_policy_act: give d_actions, d_pile_bits or both");
-    if (sp.head == CHUB_PHEAD_PILES && d_pile_bits && !d_tail) return fail(CHUB_ERR_ARG, "chub_policy_act: pile bits need d_tail (the two tail actions)");
-    if (const int rc = policy_check_tape(e, pol)) return rc;
+    if (pol->spec.head == CHUB_PHEAD_PILES && d_pile_bits && !d_tail) return fail(CHUB_ERR_ARG, "chub_policy_act: pile bits need d_tail (the two tail actions)");
+    return policy_check_tape(e, pol);
+}
+
+// one deterministic evaluation, checked by the caller.  pop == nullptr: the policy's own weights (chub_policy_act_device); else the members
+// of a population of this policy, member m for envs [m E, (m + 1) E) (chub_population_act_device)
+static void population_args(const chub_population *pop, const PolicyArgs &pa, PolicyPopArgs &out);
+static int policy_act_enqueue(chub_env *e, chub_policy *pol, const chub_population *pop, const float *d_obs, int64_t ld_obs, const uint8_t *d_mask,
+                              float *d_actions, uint64_t *d_pile_bits, float *d_tail, void *stream) {
     HIP_TRY(hipSetDevice(e->device));
     (void) hipGetLastError();
     PolicyArgs pa = pol->pa;
     if (const int rc = policy_feature_blocks(e, pol, d_obs, ld_obs, d_mask, pa, stream)) return rc;
-    const bool loads = sp.head == CHUB_PHEAD_LOADS;
+    const bool loads = pol->spec.head == CHUB_PHEAD_LOADS;
     pa.mask = d_mask;
     pa.actions = loads ? nullptr : d_actions;
     pa.bits = loads ? nullptr : (uint32_t *) d_pile_bits;
     pa.tail = d_tail ? d_tail : (loads ? pol->d_tail : nullptr);
-    launch_policy(pa, pol->waves, (hipStream_t) stream);
+    if (pop) {
+        PolicyPopArgs pp;
+        population_args(pop, pa, pp);
+        launch_policy_pop(pp, pol->waves, (hipStream_t) stream);
+    } else {
+        launch_policy(pa, pol->waves, (hipStream_t) stream);
+    }
     HIP_TRY(hipGetLastError());
     if (loads) return chub_load_dispatch_device(e, CHUB_LOAD_FRACTION, pol->d_loads, pa.tail, d_mask, d_actions, d_pile_bits, stream);
     return CHUB_OK;
+}
+
+int chub_policy_act_device(chub_env *e, chub_policy *pol, const float *d_obs, int64_t ld_obs, const uint8_t *d_mask, float *d_actions,
+                           uint64_t *d_pile_bits, float *d_tail, void *stream) {
+    if (!e || !pol) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = policy_act_check(e, pol, d_obs, ld_obs, d_actions, d_pile_bits, d_tail)) return rc;
+    return policy_act_enqueue(e, pol, nullptr, d_obs, ld_obs, d_mask, d_actions, d_pile_bits, d_tail, stream);
 }
 
 int chub_policy_act(chub_env *e, chub_policy *pol, const float *obs, float *actions) {
@@ -3803,39 +3826,47 @@ int chub_policy_act(chub_env *e, chub_policy *pol, const float *obs, float *acti
 }
 
 // The closed loop: what a host loop of chub_reset_device / chub_policy_act_device / chub_step_bits_device_packed (or
-// chub_autoreset_step_device) calls does, with nothing on the host between the steps
-int chub_policy_run_steps(chub_env *e, chub_policy *pol, int mode, float *const *d_packed2, float *d_reset_obs, float *d_final_obs,
-                          int64_t first_step, int64_t n_steps, void *stream) {
+// chub_autoreset_step_device) calls does, with nothing on the host between the steps.  pop == nullptr: chub_policy_run_steps; else the
+// population's actor in the policy's place (chub_population_run_steps)
+static int policy_run(chub_env *e, chub_policy *pol, const chub_population *pop, int mode, float *const *d_packed2, float *d_reset_obs, float *d_final_obs,
+                      int64_t first_step, int64_t n_steps, void *stream) {
+    const char *who = pop ? "chub_population_run_steps" : "chub_policy_run_steps";
     if (!e || !pol || !d_packed2 || !d_packed2[0] || !d_packed2[1] || first_step < 0 || n_steps < 0) return fail(CHUB_ERR_ARG, "bad argument");
     if (pol->env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
     if (mode != CHUB_PRUN_LOCKSTEP && mode != CHUB_PRUN_AUTORESET) return fail(CHUB_ERR_ARG, "mode: CHUB_PRUN_LOCKSTEP or CHUB_PRUN_AUTORESET");
     if (mode == CHUB_PRUN_LOCKSTEP && !d_reset_obs) return fail(CHUB_ERR_ARG, "bad argument");
     if (e->hp.rng_mode == CHUB_RNG_COMPAT)
-        return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_run_steps runs the Philox modes: COMPAT steps take the caller's normals one by one");
+        return fail(CHUB_ERR_UNSUPPORTED, std::string(who) + " runs the Philox modes: COMPAT steps take the caller's normals one by one");
     if (mode == CHUB_PRUN_AUTORESET && e->tick == 0) return fail(CHUB_ERR_ARG, "step() before reset()");
     const int D = e->hp.obs_dim;
     for (int64_t i = first_step; i < first_step + n_steps; i++) {
         int rc;
         const float *obs = d_packed2[(i - 1) & 1];
         int64_t ld = D + 2;
-        if (mode == CHUB_PRUN_LOCKSTEP) {
-            if (i % 96 == 0) {
-                if ((rc = chub_reset_device(e, nullptr, nullptr, d_reset_obs, stream))) return rc;
-                obs = d_reset_obs;
-                ld = D;
-            }
-            if ((rc = chub_policy_act_device(e, pol, obs, ld, nullptr, nullptr, pol->d_bits, pol->d_tail, stream))) return rc;
-            if ((rc = chub_step_bits_device_packed(e, pol->d_bits, pol->d_tail, nullptr, d_packed2[i & 1], stream))) return rc;
-        } else {
-            if (i == first_step && d_reset_obs) {
-                obs = d_reset_obs;
-                ld = D;
-            }
-            if ((rc = chub_policy_act_device(e, pol, obs, ld, nullptr, pol->d_rows, nullptr, nullptr, stream))) return rc;
-            if ((rc = chub_autoreset_step_device(e, pol->d_rows, nullptr, nullptr, nullptr, d_packed2[i & 1], d_final_obs, stream))) return rc;
+        const bool lock = mode == CHUB_PRUN_LOCKSTEP;
+        if (lock && i % 96 == 0) {
+            if ((rc = chub_reset_device(e, nullptr, nullptr, d_reset_obs, stream))) return rc;
+            obs = d_reset_obs;
+            ld = D;
+        } else if (!lock && i == first_step && d_reset_obs) {
+            obs = d_reset_obs;
+            ld = D;
         }
+        float *rows = lock ? nullptr : pol->d_rows;
+        uint64_t *bits = lock ? pol->d_bits : nullptr;
+        float *tail = lock ? pol->d_tail : nullptr;
+        if ((rc = policy_act_check(e, pol, obs, ld, rows, bits, tail))) return rc;
+        if ((rc = policy_act_enqueue(e, pol, pop, obs, ld, nullptr, rows, bits, tail, stream))) return rc;
+        if (lock) rc = chub_step_bits_device_packed(e, pol->d_bits, pol->d_tail, nullptr, d_packed2[i & 1], stream);
+        else rc = chub_autoreset_step_device(e, pol->d_rows, nullptr, nullptr, nullptr, d_packed2[i & 1], d_final_obs, stream);
+        if (rc) return rc;
     }
     return CHUB_OK;
+}
+
+int chub_policy_run_steps(chub_env *e, chub_policy *pol, int mode, float *const *d_packed2, float *d_reset_obs, float *d_final_obs,
+                          int64_t first_step, int64_t n_steps, void *stream) {
+    return policy_run(e, pol, nullptr, mode, d_packed2, d_reset_obs, d_final_obs, first_step, n_steps, stream);
 }
 
 // ---- sampling from the device actor (include/chub.h): exploration noise, log-probabilities, rollouts that keep the trajectory
@@ -4228,6 +4259,287 @@ int chub_policy_normalizer_from_moments_device(chub_policy *pol, chub_moments *m
     HIP_TRY(hipSetDevice(pol->env->device));
     (void) hipGetLastError();
     launch_normalizer_from_moments(m->d_state, pol->F, eps, pol->d_norm, pol->d_norm + pol->F, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+}  // extern "C"
+
+// ---- a population of actors (include/chub.h): P members' weights in the kernel's layout, perturbed, evaluated and differentiated (ES) on the
+// device.  The kernels are chub_policy.hip's; here: validation, ownership and the calls' order.
+static_assert((uint32_t) SITE_POPULATION == kPopulationSite, "chub_policy.h restates SITE_POPULATION of chub_device.h");
+// the noise counter's first word is row << 8 | k >> 2: column k <= in <= 512 gives a group <= 128 < 2^8, row <= 8193 < 2^24
+static_assert(kPolicyLdsRows <= 512 && kPolicyMaxHidden <= 512, "a layer's inputs (the feature row or a hidden width) are at most 512");
+static_assert((512 >> 2) < (1 << 8) && (uint64_t) (2 * 4096 + 2 - 1) == 8193u && (8193ull << 8 | 0xFFull) <= 0xFFFFFFFFull,
+              "the fields of the population noise counter stay apart");
+
+struct chub_population {
+    chub_policy *pol;
+    int32_t P, E;
+    uint32_t key[2];
+    float *d_params;                         // [P][member_floats]: per member every layer's [tiles][k_pad][32] and [tiles * 32] (never moves)
+    float *d_stage;                          // [P][member_floats]: chub_population_copy_members_device reads every source into it first
+    int64_t member_floats;
+    int64_t off_w[kPolicyMaxLayers], off_b[kPolicyMaxLayers];  // a layer's blocks inside a member's
+    double *d_part;                          // [chunks][items of the largest layer][4]: the ES gradient's partial sums
+    int32_t chunk_pairs, chunks;             // pairs per chunk and chunks, fixed at create for (P, spec)
+};
+
+extern "C" {
+
+constexpr int kPopChunkPairs = 16;                  // pairs a lane of the gradient's first launch takes at least
+constexpr int kPopMaxChunks = 64;
+constexpr size_t kPopPartialBytes = 64u << 20;      // the partial sums stay at most this large (or one chunk)
+
+static void population_free(chub_population *pop) {
+    chub_policy *pol = pop->pol;
+    (void) hipSetDevice(pol->env->device);
+    (void) hipDeviceSynchronize();  // (a launch still in flight reads the weights)
+    if (pop->d_params) (void) hipFree(pop->d_params);
+    if (pop->d_stage) (void) hipFree(pop->d_stage);
+    if (pop->d_part) (void) hipFree(pop->d_part);
+    pol->populations.erase(std::remove(pol->populations.begin(), pol->populations.end(), pop), pol->populations.end());
+    delete pop;
+}
+
+static void population_args(const chub_population *pop, const PolicyArgs &pa, PolicyPopArgs &out) {
+    static_cast<PolicyArgs &>(out) = pa;
+    out.tiles_per_member = pop->E / kPolicyEnvTile;
+    out.pad_ = 0;
+    for (int l = 0; l < kPolicyMaxLayers; l++) {
+        out.w_stride[l] = out.b_stride[l] = pop->member_floats;
+        if (l < pa.n_layers) {
+            out.layer[l].w = pop->d_params + pop->off_w[l];
+            out.layer[l].b = pop->d_params + pop->off_b[l];
+        }
+    }
+}
+
+int chub_population_param_count(const chub_config *cfg, const chub_policy_spec *spec, int64_t *n_out) {
+    if (!cfg || !spec || !n_out) return fail(CHUB_ERR_ARG, "null argument");
+    PolicyShape ps;
+    if (const int rc = policy_shape(cfg->station_list, spec, ps)) return rc;
+    int64_t n = 0;
+    for (int l = 0; l < spec->n_layers; l++) n += (int64_t) spec->width[l] * ((l ? spec->width[l - 1] : ps.F) + 1);
+    *n_out = n;
+    return CHUB_OK;
+}
+
+// one layer of the population as the weight kernels take it
+static PopLayerArgs population_layer(const chub_population *pop, int l, uint32_t generation) {
+    const chub_policy *pol = pop->pol;
+    PopLayerArgs a;
+    a.w = pop->d_params + pop->off_w[l];
+    a.bias = pop->d_params + pop->off_b[l];
+    a.stride = pop->member_floats;
+    a.out = pol->spec.width[l];
+    a.in = pol->in_dim[l];
+    a.k_pad = pol->pa.layer[l].k_pad;
+    a.tiles = pol->pa.layer[l].tiles;
+    a.layer = l;
+    a.pairs = pop->P / 2;
+    a.key[0] = pop->key[0];
+    a.key[1] = pop->key[1];
+    a.generation = generation;
+    a.normal_icdf = (const float *) pol->env->tb.normal_icdf;
+    a.normal_tail = (const float *) pol->env->tb.normal_tail;
+    return a;
+}
+
+int chub_population_create(chub_policy *pol, int32_t P, uint64_t key, chub_population **out) {
+    if (!pol || !out) return fail(CHUB_ERR_ARG, "null argument");
+    *out = nullptr;
+    chub_env *e = pol->env;
+    const int64_t N = e->hp.n_envs;
+    if (P < 2 || (P & 1)) return fail(CHUB_ERR_ARG, "chub_population_create: P is even and at least 2 (members 2j and 2j + 1 are an antithetic pair)");
+    if (N % P != 0 || (N / P) % kPolicyEnvTile != 0)
+        return fail(CHUB_ERR_ARG, "chub_population_create: the handle's " + std::to_string(N) + " envs are not P = " + std::to_string(P) +
+                                      " blocks of a multiple of " + std::to_string(kPolicyEnvTile) + " envs (a workgroup's tile belongs to one member)");
+    if (e->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_population_create between chub_graph_begin and chub_graph_end (it allocates and synchronises)");
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    chub_population *pop = new chub_population();
+    pop->pol = pol;
+    pop->P = P;
+    pop->E = (int32_t) (N / P);
+    pop->key[0] = (uint32_t) key;  // (split as the policy's key is)
+    pop->key[1] = (uint32_t) (key >> 32);
+    int64_t at = 0, items = 0;
+    for (int l = 0; l < pol->spec.n_layers; l++) {
+        const PolicyLayer &L = pol->pa.layer[l];
+        pop->off_w[l] = at;
+        at += (int64_t) L.tiles * L.k_pad * kPolicyOutTile;
+        pop->off_b[l] = at;
+        at += (int64_t) L.tiles * kPolicyOutTile;
+        items = std::max(items, (int64_t) pol->spec.width[l] * (pol->in_dim[l] / 4 + 1));
+    }
+    pop->member_floats = at;
+    // the gradient's chunks of pairs: at least kPopChunkPairs pairs each, at most kPopMaxChunks chunks, the partials within kPopPartialBytes
+    const int pairs = P / 2;
+    const size_t chunk_bytes = (size_t) items * 4 * sizeof(double);
+    int64_t chunks = std::min<int64_t>((pairs + kPopChunkPairs - 1) / kPopChunkPairs, kPopMaxChunks);
+    chunks = std::max<int64_t>(1, std::min<int64_t>(chunks, (int64_t) (kPopPartialBytes / chunk_bytes)));
+    pop->chunk_pairs = (int32_t) ((pairs + chunks - 1) / chunks);
+    pop->chunks = (pairs + pop->chunk_pairs - 1) / pop->chunk_pairs;
+    pol->populations.push_back(pop);
+    const size_t bytes = (size_t) P * (size_t) at * sizeof(float), part = (size_t) pop->chunks * chunk_bytes;
+    bool ok = hipMalloc((void **) &pop->d_params, bytes) == hipSuccess && hipMalloc((void **) &pop->d_stage, bytes) == hipSuccess &&
+              hipMalloc((void **) &pop->d_part, part) == hipSuccess && hipMemset(pop->d_stage, 0, bytes) == hipSuccess &&
+              hipMemset(pop->d_part, 0, part) == hipSuccess;
+    // every member = the centre's current weights: its blocks are the member's layout already
+    for (int m = 0; m < P && ok; m++)
+        for (int l = 0; l < pol->spec.n_layers && ok; l++) {
+            const PolicyLayer &L = pol->pa.layer[l];
+            float *base = pop->d_params + (int64_t) m * at;
+            ok = hipMemcpyAsync(base + pop->off_w[l], pol->d_w[l], (size_t) L.tiles * L.k_pad * kPolicyOutTile * sizeof(float), hipMemcpyDeviceToDevice,
+                                nullptr) == hipSuccess &&
+                 hipMemcpyAsync(base + pop->off_b[l], pol->d_b[l], (size_t) L.tiles * kPolicyOutTile * sizeof(float), hipMemcpyDeviceToDevice, nullptr) ==
+                     hipSuccess;
+        }
+    if (!ok || hipDeviceSynchronize() != hipSuccess) {
+        population_free(pop);
+        (void) hipGetLastError();
+        return fail(CHUB_ERR_HIP, "chub_population_create: out of device memory");
+    }
+    *out = pop;
+    return CHUB_OK;
+}
+
+int chub_population_destroy(chub_population *pop) {
+    if (!pop) return CHUB_OK;
+    if (pop->pol->env->capturing)
+        return fail(CHUB_ERR_UNSUPPORTED, "chub_population_destroy between chub_graph_begin and chub_graph_end (it synchronises and frees)");
+    population_free(pop);
+    (void) hipGetLastError();
+    return CHUB_OK;
+}
+
+int chub_population_perturb_device(chub_population *pop, const float *const *d_W, const float *const *d_b, float sigma, uint32_t generation,
+                                   void *stream) {
+    if (!pop) return fail(CHUB_ERR_ARG, "null argument");
+    const chub_policy *pol = pop->pol;
+    if ((d_W == nullptr) != (d_b == nullptr)) return fail(CHUB_ERR_ARG, "chub_population_perturb_device: d_W and d_b are both given or both NULL (the centre's weights)");
+    if (d_W)
+        for (int l = 0; l < pol->spec.n_layers; l++)
+            if (!d_W[l] || !d_b[l]) return fail(CHUB_ERR_ARG, "null argument");
+    if (!std::isfinite(sigma) || sigma < 0.0f) return fail(CHUB_ERR_ARG, "chub_population_perturb_device: sigma is finite and >= 0");
+    HIP_TRY(hipSetDevice(pol->env->device));
+    (void) hipGetLastError();
+    for (int l = 0; l < pol->spec.n_layers; l++) {
+        const PopLayerArgs a = population_layer(pop, l, generation);
+        if (d_W) launch_population_perturb(a, d_W[l], d_b[l], 0, sigma, (hipStream_t) stream);
+        else launch_population_perturb(a, pol->d_w[l], pol->d_b[l], 1, sigma, (hipStream_t) stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+static int population_check_member(const chub_population *pop, int32_t m, int32_t layer) {
+    if (m < 0 || m >= pop->P) return fail(CHUB_ERR_ARG, "m: 0 .. P - 1");
+    if (layer < 0 || layer >= pop->pol->spec.n_layers) return fail(CHUB_ERR_ARG, "layer: 0 .. n_layers - 1");
+    return CHUB_OK;
+}
+
+int chub_population_set_member_device(chub_population *pop, int32_t m, int32_t layer, const float *d_W, const float *d_b, void *stream) {
+    if (!pop || !d_W || !d_b) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = population_check_member(pop, m, layer)) return rc;
+    const chub_policy *pol = pop->pol;
+    HIP_TRY(hipSetDevice(pol->env->device));
+    (void) hipGetLastError();
+    float *base = pop->d_params + (int64_t) m * pop->member_floats;
+    launch_policy_relayout(d_W, d_b, base + pop->off_w[layer], base + pop->off_b[layer], pol->spec.width[layer], pol->in_dim[layer],
+                           pol->pa.layer[layer].k_pad, pol->pa.layer[layer].tiles, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_population_get_member_device(chub_population *pop, int32_t m, int32_t layer, float *d_W, float *d_b, void *stream) {
+    if (!pop || !d_W || !d_b) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = population_check_member(pop, m, layer)) return rc;
+    const chub_policy *pol = pop->pol;
+    HIP_TRY(hipSetDevice(pol->env->device));
+    (void) hipGetLastError();
+    const float *base = pop->d_params + (int64_t) m * pop->member_floats;
+    launch_policy_unlayout(base + pop->off_w[layer], base + pop->off_b[layer], d_W, d_b, pol->spec.width[layer], pol->in_dim[layer],
+                           pol->pa.layer[layer].k_pad, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+// the host forms go through the policy's staging buffer (W | b of the largest layer, the trainer's layout), as chub_policy_set_weights does
+int chub_population_set_member(chub_population *pop, int32_t m, int32_t layer, const float *W, const float *b) {
+    if (!pop || !W || !b) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = population_check_member(pop, m, layer)) return rc;
+    chub_policy *pol = pop->pol;
+    if (pol->env->capturing)
+        return fail(CHUB_ERR_UNSUPPORTED, "chub_population_set_member between chub_graph_begin and chub_graph_end (it copies and synchronises: use "
+                                          "chub_population_set_member_device)");
+    const size_t nw = (size_t) pol->spec.width[layer] * (size_t) pol->in_dim[layer], nb = (size_t) pol->spec.width[layer];
+    HIP_TRY(hipSetDevice(pol->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipDeviceSynchronize());  // (the staging buffer is one; nothing may still be reading the layer either)
+    HIP_TRY(hipMemcpy(pol->d_stage, W, nw * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(pol->d_stage + nw, b, nb * sizeof(float), hipMemcpyHostToDevice));
+    if (const int rc = chub_population_set_member_device(pop, m, layer, pol->d_stage, pol->d_stage + nw, nullptr)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    return CHUB_OK;
+}
+
+int chub_population_get_member(chub_population *pop, int32_t m, int32_t layer, float *W, float *b) {
+    if (!pop || !W || !b) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = population_check_member(pop, m, layer)) return rc;
+    chub_policy *pol = pop->pol;
+    if (pol->env->capturing)
+        return fail(CHUB_ERR_UNSUPPORTED, "chub_population_get_member between chub_graph_begin and chub_graph_end (it copies and synchronises: use "
+                                          "chub_population_get_member_device)");
+    const size_t nw = (size_t) pol->spec.width[layer] * (size_t) pol->in_dim[layer], nb = (size_t) pol->spec.width[layer];
+    HIP_TRY(hipSetDevice(pol->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipDeviceSynchronize());
+    if (const int rc = chub_population_get_member_device(pop, m, layer, pol->d_stage, pol->d_stage + nw, nullptr)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(W, pol->d_stage, nw * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(b, pol->d_stage + nw, nb * sizeof(float), hipMemcpyDeviceToHost));
+    return CHUB_OK;
+}
+
+int chub_population_copy_members_device(chub_population *pop, const int32_t *d_src, const int32_t *d_dst, int32_t count, void *stream) {
+    if (!pop || !d_src || !d_dst) return fail(CHUB_ERR_ARG, "null argument");
+    if (count < 0 || count > pop->P)
+        return fail(CHUB_ERR_ARG, "chub_population_copy_members_device: count is 0 .. P (every source is staged before any destination is written)");
+    HIP_TRY(hipSetDevice(pop->pol->env->device));
+    (void) hipGetLastError();
+    launch_population_copy(pop->d_params, pop->d_stage, pop->member_floats, pop->P, d_src, d_dst, count, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_population_act_device(chub_env *e, chub_population *pop, const float *d_obs, int64_t ld_obs, const uint8_t *d_mask, float *d_actions,
+                               uint64_t *d_pile_bits, float *d_tail, void *stream) {
+    if (!e || !pop) return fail(CHUB_ERR_ARG, "null argument");
+    if (pop->pol->env != e) return fail(CHUB_ERR_ARG, "this population was made for another handle");
+    if (const int rc = policy_act_check(e, pop->pol, d_obs, ld_obs, d_actions, d_pile_bits, d_tail)) return rc;
+    return policy_act_enqueue(e, pop->pol, pop, d_obs, ld_obs, d_mask, d_actions, d_pile_bits, d_tail, stream);
+}
+
+int chub_population_run_steps(chub_env *e, chub_population *pop, int mode, float *const *d_packed2, float *d_reset_obs, float *d_final_obs,
+                              int64_t first_step, int64_t n_steps, void *stream) {
+    if (!e || !pop) return fail(CHUB_ERR_ARG, "null argument");
+    if (pop->pol->env != e) return fail(CHUB_ERR_ARG, "this population was made for another handle");
+    return policy_run(e, pop->pol, pop, mode, d_packed2, d_reset_obs, d_final_obs, first_step, n_steps, stream);
+}
+
+int chub_population_es_gradient_device(chub_population *pop, const float *d_util, uint32_t generation, float *const *d_gW, float *const *d_gb,
+                                       void *stream) {
+    if (!pop || !d_util || !d_gW || !d_gb) return fail(CHUB_ERR_ARG, "null argument");
+    const chub_policy *pol = pop->pol;
+    for (int l = 0; l < pol->spec.n_layers; l++)
+        if (!d_gW[l] || !d_gb[l]) return fail(CHUB_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(pol->env->device));
+    (void) hipGetLastError();
+    for (int l = 0; l < pol->spec.n_layers; l++)  // (one buffer of partials: the stream orders a layer's merge before the next layer's sums)
+        launch_population_es_gradient(population_layer(pop, l, generation), d_util, pop->chunk_pairs, pop->chunks, pop->d_part, d_gW[l], d_gb[l],
+                                      (hipStream_t) stream);
     HIP_TRY(hipGetLastError());
     return CHUB_OK;
 }

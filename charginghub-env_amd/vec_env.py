@@ -288,6 +288,164 @@ class DevicePolicy(object):
             pass
 
 
+class DevicePopulation(object):
+    """P actors on one handle (chub_population_*, include/chub.h "a population of actors"): made by VecChargingHub.make_population from a
+    DevicePolicy, the centre, whose spec, normaliser and buffers it shares.  Member m serves envs [m E, (m + 1) E), E = N / P a multiple
+    of 32, inside the same single actor launch per step.  perturb_device draws members 2j / 2j + 1 = theta +- sigma eps from counter-based
+    noise that is never stored; es_gradient_device regenerates it: g = sum_j (util[2j] - util[2j + 1]) eps_j."""
+
+    def __init__(self, env, policy, P, key):
+        self._env = env
+        self._lib = env._lib
+        self.policy = policy
+        self.n_members = int(P)
+        self.key = int(key) & (2 ** 64 - 1)
+        self.layer_shapes = list(policy.layer_shapes)
+        h = C.c_void_p()
+        check(self._lib.chub_population_create(policy._p, self.n_members, self.key, C.byref(h)))
+        self._q = h
+        self.envs_per_member = env.n_envs // self.n_members
+
+    @property
+    def n_params(self):
+        """parameters per member: the sum over layers of out * (in + 1) (chub_population_param_count)"""
+        n = C.c_int64()
+        check(self._lib.chub_population_param_count(C.byref(self._env.cfg), C.byref(self.policy.spec), C.byref(n)))
+        return n.value
+
+    def _ptr_arrays(self, d_W, d_b):
+        n = len(self.layer_shapes)
+        if len(d_W) != n or len(d_b) != n:
+            raise ValueError("one device address per layer: %d layers" % n)
+        return (C.c_void_p * n)(*[int(p) for p in d_W]), (C.c_void_p * n)(*[int(p) for p in d_b])
+
+    def perturb_device(self, sigma, generation, d_W=None, d_b=None, stream=0):
+        """every member from theta on `stream`: members 2j / 2j + 1 = theta + / - sigma eps(generation, j).  d_W / d_b: per layer the device
+        address of W [out, in] and b [out] float32 (the nn.Linear layout, e.g. data_ptr()); None: the centre policy's current weights.
+        sigma and generation are host values: a captured graph replays the same ones."""
+        if (d_W is None) != (d_b is None):
+            raise ValueError("perturb_device: d_W and d_b are both given or both None")
+        Wp, bp = (None, None) if d_W is None else self._ptr_arrays(d_W, d_b)
+        check(self._lib.chub_population_perturb_device(self._q, Wp, bp, float(sigma), int(generation) & 0xFFFFFFFF, stream or None))
+
+    def _host_layers(self, layers):
+        out = [(np.ascontiguousarray(W, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32).ravel()) for W, b in layers]
+        if [W.shape for W, _ in out] != self.layer_shapes or any(b.shape != (W.shape[0],) for W, b in out):
+            raise ValueError("layers must be (W, b) pairs of shapes %s" % (self.layer_shapes,))
+        return out
+
+    def perturb(self, sigma, generation, layers=None):
+        """perturb_device from host arrays, layers = [(W, b), ..] (None: the centre policy's weights); it allocates, copies and synchronises"""
+        e = self._env
+        if layers is None:
+            self.perturb_device(sigma, generation)
+            check(self._lib.chub_sync(e._h))
+            return
+        layers = self._host_layers(layers)
+        flat = np.concatenate([a.ravel() for W, b in layers for a in (W, b)])
+        d = C.c_void_p()
+        check(self._lib.chub_malloc_device(e._device, flat.nbytes, C.byref(d)))
+        try:
+            check(self._lib.chub_copy_to_device(e._device, d, _ptr(flat), flat.nbytes, None))
+            d_W, d_b, at = [], [], d.value
+            for W, b in layers:
+                d_W.append(at)
+                d_b.append(at + W.nbytes)
+                at += W.nbytes + b.nbytes
+            self.perturb_device(sigma, generation, d_W, d_b)
+            check(self._lib.chub_sync(e._h))
+        finally:
+            self._lib.chub_free_device(e._device, d)
+
+    def set_member(self, m, layer, W, b):
+        """member m's layer from host arrays, W [out, in] and b [out]; synchronises"""
+        W = np.ascontiguousarray(W, dtype=np.float32)
+        b = np.ascontiguousarray(b, dtype=np.float32).ravel()
+        if not 0 <= int(layer) < len(self.layer_shapes) or W.shape != self.layer_shapes[layer] or b.shape != (W.shape[0],):
+            raise ValueError("set_member: layer %r takes W %s and b of its rows" % (layer, self.layer_shapes[layer] if 0 <= int(layer) < len(self.layer_shapes) else "?"))
+        check(self._lib.chub_population_set_member(self._q, int(m), int(layer), _ptr(W), _ptr(b)))
+
+    def get_member(self, m, layer=None):
+        """member m's weights as float32 numpy arrays: (W, b) of one layer, or with layer=None the list over all layers; synchronises"""
+        if layer is None:
+            return [self.get_member(m, l) for l in range(len(self.layer_shapes))]
+        if not 0 <= int(layer) < len(self.layer_shapes):
+            raise ValueError("get_member: layer is 0 .. %d" % (len(self.layer_shapes) - 1))
+        W = np.zeros(self.layer_shapes[layer], dtype=np.float32)
+        b = np.zeros((W.shape[0],), dtype=np.float32)
+        check(self._lib.chub_population_get_member(self._q, int(m), int(layer), _ptr(W), _ptr(b)))
+        return W, b
+
+    def set_member_device(self, m, layer, d_W, d_b, stream=0):
+        """member m's layer from device memory in the trainer's layout, one launch on `stream`"""
+        check(self._lib.chub_population_set_member_device(self._q, int(m), int(layer), d_W or None, d_b or None, stream or None))
+
+    def get_member_device(self, m, layer, d_W, d_b, stream=0):
+        """member m's layer into device memory in the trainer's layout, one launch on `stream`"""
+        check(self._lib.chub_population_get_member_device(self._q, int(m), int(layer), d_W or None, d_b or None, stream or None))
+
+    def copy_members_device(self, d_src, d_dst, count, stream=0):
+        """member dst[i] becomes a copy of member src[i] (int32 indices in device memory, count <= P) in one launch on `stream`; every source
+        is read before any destination is written, so src = [0, 1], dst = [1, 0] swaps"""
+        check(self._lib.chub_population_copy_members_device(self._q, d_src or None, d_dst or None, int(count), stream or None))
+
+    def act_device(self, d_obs=0, ld_obs=None, d_actions=0, d_pile_bits=0, d_tail=0, d_mask=0, stream=0):
+        """DevicePolicy.act_device with member m's weights for envs [m E, (m + 1) E): bit for bit what a policy holding them writes"""
+        ld = self._env.obs_dim if ld_obs is None else int(ld_obs)
+        check(self._lib.chub_population_act_device(self._env._h, self._q, d_obs or None, ld, d_mask or None, d_actions or None, d_pile_bits or None,
+                                                   d_tail or None, stream or None))
+
+    def run_steps(self, d_packed2, n_steps, first_step=0, mode="lockstep", d_reset_obs=0, d_final_obs=0, stream=0):
+        """DevicePolicy.run_steps with the population's actor (chub_population_run_steps)"""
+        blocks = (C.c_void_p * 2)(int(d_packed2[0]), int(d_packed2[1]))
+        check(self._lib.chub_population_run_steps(self._env._h, self._q, _lib._enum_value(_lib.PRUN, mode, "run mode"), blocks, d_reset_obs or None,
+                                                  d_final_obs or None, int(first_step), int(n_steps), stream or None))
+
+    def es_gradient_device(self, d_util, generation, d_gW, d_gb, stream=0):
+        """g = sum over pairs j of (util[2j] - util[2j + 1]) eps(generation, j) in f64, rounded once to float32, into d_gW[l] [out, in] and
+        d_gb[l] [out] (device addresses per layer); d_util [P] float32 in device memory.  The same bits every call."""
+        Wp, bp = self._ptr_arrays(d_gW, d_gb)
+        check(self._lib.chub_population_es_gradient_device(self._q, d_util or None, int(generation) & 0xFFFFFFFF, Wp, bp, stream or None))
+
+    def es_gradient(self, util, generation):
+        """es_gradient_device through host memory: util [P] -> [(gW, gb), ..] float32 numpy arrays; it allocates, copies and synchronises"""
+        e = self._env
+        util = np.ascontiguousarray(util, dtype=np.float32).ravel()
+        if util.shape != (self.n_members,):
+            raise ValueError("util must have %d entries (one per member)" % self.n_members)
+        out = np.zeros((self.n_params,), dtype=np.float32)
+        d = C.c_void_p()
+        check(self._lib.chub_malloc_device(e._device, out.nbytes + util.nbytes, C.byref(d)))
+        try:
+            check(self._lib.chub_copy_to_device(e._device, C.c_void_p(d.value + out.nbytes), _ptr(util), util.nbytes, None))
+            d_gW, d_gb, at = [], [], d.value
+            for o, i in self.layer_shapes:
+                d_gW.append(at)
+                d_gb.append(at + 4 * o * i)
+                at += 4 * o * (i + 1)
+            self.es_gradient_device(d.value + out.nbytes, generation, d_gW, d_gb)
+            check(self._lib.chub_sync(e._h))
+            check(self._lib.chub_copy_to_host(e._device, _ptr(out), d, out.nbytes, None))
+        finally:
+            self._lib.chub_free_device(e._device, d)
+        res, at = [], 0
+        for o, i in self.layer_shapes:
+            res.append((out[at:at + o * i].reshape(o, i).copy(), out[at + o * i:at + o * (i + 1)].copy()))
+            at += o * (i + 1)
+        return res
+
+    def close(self):
+        if getattr(self, "_q", None) and getattr(self.policy, "_p", None) and getattr(self._env, "_h", None):
+            check(self._lib.chub_population_destroy(self._q))
+        self._q = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DeviceMoments(object):
     """Running count, mean and M2 per feature on the device (chub_moments_*, include/chub.h "running feature statistics"): made by
     VecChargingHub.make_moments.  The state is [1 + 2 F] float64 in device memory (n | mean | M2); update_device adds a batch of rows in
@@ -911,6 +1069,13 @@ class VecChargingHub(object):
         """running count / mean / M2 of F features on the device, bound to this handle -> DeviceMoments (chub_moments_create, 1 <= F <= 512):
         what DevicePolicy.normalizer_from_moments turns into the policy's normaliser"""
         return DeviceMoments(self, F)
+
+    def make_population(self, policy, P, key):
+        """P members around `policy` (a DevicePolicy of this handle, the centre) -> DevicePopulation (chub_population_create): P even, the
+        handle's envs P blocks of a multiple of 32; key: the uint64 key of the perturbation noise.  Every member starts as the centre."""
+        if policy._env is not self:
+            raise ValueError("make_population: the policy was made for another handle")
+        return DevicePopulation(self, policy, P, key)
 
     def next_tick(self):
         """the Philox tick of this handle's next reset or step (chub_next_tick): the tick a sampled policy call made now draws its noise

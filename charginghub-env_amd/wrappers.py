@@ -645,6 +645,38 @@ class TorchHubVecEnv(object):
             return self._cur_obs, self._packed[:, D], self._packed[:, D + 1] > 0.5, {}
         return self._after_step()
 
+    # ---- a population of actors (chub_population_*): the gradient-free route -- perturb, one closed-loop day, fitness, ES gradient
+    def load_population(self, policy, P, key):
+        """P members around `policy` (a DevicePolicy from ``load_policy``, the centre) -> DevicePopulation (VecChargingHub.make_population):
+        member m acts for envs [m E, (m + 1) E), E = num_envs / P a multiple of 32.  ``pop.perturb_device(sigma, generation, d_W, d_b,
+        stream)`` with the data_ptr()s of the centre's Linear layers draws the members on the device."""
+        return self.vec.make_population(policy, P, key)
+
+    def population_rollout(self, pop, n_steps):
+        """``rollout`` with the population's actor (chub_population_run_steps): n_steps closed-loop steps of all P members at once, member
+        m's weights for its block of envs; the same auto-reset modes, the same return value"""
+        return self.rollout(pop, n_steps)
+
+    def es_gradient(self, pop, utilities, generation):
+        """The ES gradient estimate of `pop`'s generation on torch's current stream (chub_population_es_gradient_device): utilities [P]
+        float32 CUDA (e.g. centred ranks of the members' fitness) -> a list of (gW, gb) float32 CUDA tensors in the nn.Linear shapes,
+        g = sum over pairs j of (u[2j] - u[2j + 1]) eps_j with the noise regenerated, not stored, accumulated in f64 in a fixed order.
+        sigma and 1 / (P sigma) are the caller's to apply.  The next call with the same population overwrites the tensors."""
+        torch = self.torch
+        u = utilities
+        if not (self._on_device(u) and u.dtype == torch.float32 and u.is_contiguous() and tuple(u.shape) == (pop.n_members,)):
+            raise AssertionError("utilities must be a contiguous float32 tensor on %s of shape (%d,)" % (self.device, pop.n_members))
+        cache = getattr(self, "_es_grads", None)
+        if cache is None:
+            cache = self._es_grads = {}
+        grads = cache.get(id(pop))
+        if grads is None:
+            grads = cache[id(pop)] = [(torch.zeros((o, i), dtype=torch.float32, device=self.device),
+                                       torch.zeros((o,), dtype=torch.float32, device=self.device)) for o, i in pop.layer_shapes]
+        pop.es_gradient_device(u.data_ptr(), generation, [gW.data_ptr() for gW, _ in grads], [gb.data_ptr() for _, gb in grads],
+                               stream=self._stream())
+        return grads
+
     def collect(self, policy, n_steps, logp_piles=None):
         """n_steps SAMPLED closed-loop steps of `policy` (after ``policy.set_exploration``) from the current observation, issued from C on
         torch's current stream (chub_policy_collect), keeping the trajectory: a dict of CUDA tensors the next call with the same policy and

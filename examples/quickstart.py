@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Six ways to drive the hub, smallest first (run from the repo root on a machine with an MI355X):
+"""Seven ways to drive the hub, smallest first (run from the repo root on a machine with an MI355X):
 
     python examples/quickstart.py
 
@@ -8,7 +8,9 @@
 3. the device-resident API (torch CUDA tensors in / out, no host copies) -- what an on-device learner should use;
 4. a closed-loop day with an actor evaluated by the hub itself (numpy and ctypes only: no torch, no host between the steps);
 5. on-policy training data: the hub samples from the actor, and keeps actions, log-probabilities and every step's block on the device;
-6. one PPO-shaped iteration on that data: log-probabilities over the piles the step can see, a torch critic, advantages on the device.
+6. one PPO-shaped iteration on that data: log-probabilities over the piles the step can see, a torch critic, advantages on the device;
+7. one evolution-strategies generation, no backward pass: a population of perturbed actors on one handle, a closed-loop day for all of
+   them at once, member fitness from the episode ledger, the ES gradient from regenerated noise, an SGD step on the centre.
 """
 import os
 import sys
@@ -213,6 +215,39 @@ def ppo_iteration(n=4096, steps=64):
     env.close()
 
 
+def es_generation(n=4096, members=64, sigma=0.05, lr=0.02, generation=0):
+    import charginghub_env_amd as chub
+
+    if torch is None:
+        print("7. skipped: torch is not installed")
+        return
+    env = chub.TorchHubVecEnv(n, seed=0, autoreset="per_env", episode_stats=True, **HUB)
+    D, A = env.obs_dim, env.act_dim
+    net = torch.nn.Sequential(torch.nn.Linear(D, 64), torch.nn.Tanh(), torch.nn.Linear(64, A), torch.nn.Tanh()).to("cuda")   # the centre
+    linears = [m for m in net if isinstance(m, torch.nn.Linear)]
+    policy = env.load_policy(net)
+    pop = env.load_population(policy, members, key=7)         # member m acts for envs [m E, (m + 1) E), E = n / members
+    stream = torch.cuda.current_stream().cuda_stream
+    # members 2j / 2j + 1 = theta + / - sigma eps_j, drawn on the device from the centre's own tensors; the noise is never stored
+    pop.perturb_device(sigma, generation, [m.weight.data_ptr() for m in linears], [m.bias.data_ptr() for m in linears], stream=stream)
+    env.reset()
+    env.population_rollout(pop, 96)                           # one closed-loop day, every member at once: one actor launch per step
+    fitness = env.episode_stats()["return"].view(members, -1).mean(dim=1)   # the day's return per env, viewed as [P][E]
+    ranks = fitness.argsort().argsort().float()
+    util = (ranks / (members - 1) - 0.5).contiguous()         # centred ranks: the trainer's choice of fitness shaping
+    grads = env.es_gradient(pop, util, generation)            # sum_j (u[2j] - u[2j + 1]) eps_j, the noise regenerated: nn.Linear shapes
+    with torch.no_grad():                                     # plain SGD ascent on the centre; 1 / (P sigma) is the estimator's scale
+        for m, (gW, gb) in zip(linears, grads):
+            m.weight.add_(lr / (members * sigma) * gW)
+            m.bias.add_(lr / (members * sigma) * gb)
+    for l, m in enumerate(linears):                           # the centre policy follows, for evaluation and the next generation
+        policy.set_weights_device(l, m.weight.data_ptr(), m.bias.data_ptr(), stream)
+    print("7. %d envs, %d members x %d envs, one ES generation of %d parameters: fitness %.3f .. %.3f, gradient norm %.3f"
+          % (n, members, n // members, pop.n_params, float(fitness.min()), float(fitness.max()),
+             float(torch.sqrt(sum((gW ** 2).sum() + (gb ** 2).sum() for gW, gb in grads)))))
+    env.close()
+
+
 if __name__ == "__main__":
     single_env()
     batched_host()
@@ -220,3 +255,4 @@ if __name__ == "__main__":
     closed_loop()
     on_policy_data()
     ppo_iteration()
+    es_generation()

@@ -1018,6 +1018,73 @@ int chub_policy_set_normalizer_device(chub_policy *pol, const float *d_mean, con
 int chub_policy_get_normalizer_device(chub_policy *pol, float *d_mean, float *d_inv_std, void *stream);  /* copies out, [F] each */
 int chub_policy_normalizer_from_moments_device(chub_policy *pol, chub_moments *m, double eps, void *stream);
 
+/* ---- a population of actors: perturb, act, run, ES gradient ---------------------------------------------------------------------------
+ * Evolution strategies, population-based training and plain evaluation of many candidate policies need no backward pass: they need P sets
+ * of weights evaluated on P blocks of envs.  A chub_population holds P members, each with its own weights, and evaluates all of them in the
+ * same single actor launch per step; its members are perturbed on the device from a centre with counter-based noise that is never stored,
+ * and utilities per member are turned into the ES gradient estimate by regenerating that noise.
+ *   Objects.  A population is bound to a chub_policy, "the centre": the policy's spec, normaliser, scratch, bits / tail / rows buffers and
+ *     handle are the population's.  The policy's own weights are never touched by a population call.  chub_population_create: P even,
+ *     2 <= P; N = P E with E a multiple of 32, so that a workgroup's tile of 32 envs belongs to exactly one member.  Member m serves envs
+ *     [m E, (m + 1) E).  At create every member equals the centre's current weights.  The members' weights live in the kernel's own device
+ *     layout, allocated once OUTSIDE the arena together with a staging block of the same size (chub_population_copy_members_device) and the
+ *     partial sums of the gradient; they never move.  chub_state_size and snapshots are unchanged.  chub_policy_destroy / chub_destroy
+ *     destroy a policy's populations first.  chub_population_param_count: host-only, no device: the sum over layers of out * (in + 1).
+ *   The noise, a pure function of (key, generation, pair, layer, row, column).  Layer l is the augmented matrix [W | b] with columns
+ *     k = 0 .. in (column `in` is the bias).  eps(g, j, l, row, k) is the handle's tabulated normal (normal_from_word: the OU draws'
+ *     function and tables) applied to word k & 3 of the Philox4x32-10 block with counter
+ *         (row << 8 | (k >> 2), 16 << 16 | l, g, j)
+ *     under the population's key, a uint64 split as the policy's key is (low word first).  in <= 512 and row <= 8193 keep the fields apart.
+ *     Nothing of P, N or the hub enters the noise.
+ *   The pairing.  Members 2j and 2j + 1 are an antithetic pair: with d = sigma * eps rounded once to f32, member 2j gets theta + d and
+ *     member 2j + 1 gets theta - d, each rounded once, no FMA.
+ *   Manners of the device calls: on the caller's stream, no synchronisation, no allocation, no tick; recordable between chub_graph_begin
+ *     and chub_graph_end without counting towards the even number of resets + steps.
+ *   chub_population_perturb_device: theta in the trainer's layout (d_W[l] [out][in] row-major, d_b[l] [out], device memory); both arrays
+ *     NULL: the centre policy's current weights.  One launch per layer writes every member's layer straight into the device layout (the
+ *     re-layout fused with the draw); everything beyond `in` and `out` in the padded layout stays zero.  sigma and generation are HOST
+ *     arguments: a captured graph replays the SAME generation and sigma -- record one graph per generation, or perturb between replays.
+ *   chub_population_set_member_device / get_member_device: one member's layer from / to the trainer's [out][in] / [out] layout, one launch.
+ *     chub_population_set_member / get_member: the same through host memory; they copy and synchronise.
+ *   chub_population_copy_members_device: member dst[i] becomes a copy of member src[i], i = 0 .. count - 1 with count <= P, in ONE launch: the
+ *     weight-side companion of chub_copy_envs_device.  ALL sources are read before any destination is written, so overlapping sets are
+ *     welcome: src = {0, 1}, dst = {1, 0} swaps the two.  The indices are device memory and cannot be checked by the host: a pair with an
+ *     index outside 0 .. P - 1 is skipped; of two pairs that name one destination the later wins.  Members not named are untouched.
+ *   chub_population_act_device: arguments, feature launches, mask semantics, refusals and the LOADS dispatch are chub_policy_act_device's.
+ *     CONTRACT: the outputs of member m's envs are bit for bit what chub_policy_act_device writes for a policy holding member m's
+ *     weights: the chain, the order and the squash are the same.
+ *   chub_population_run_steps: chub_policy_run_steps with the population's actor: both modes, Philox modes only, the same rules.
+ *   chub_population_es_gradient_device: per parameter
+ *         g[l][row][k] = sum over pairs j of ((double) util[2j] - (double) util[2j + 1]) * (double) eps(generation, j, l, row, k)
+ *     accumulated in f64 (product and sum each rounded once) in an order fixed for (P, spec), rounded once to f32 and written in the
+ *     trainer's layout (d_gW[l] [out][in], d_gb[l] [out]).  No atomics: two calls give identical bits.  The noise is regenerated, not read;
+ *     sigma and 1 / (P sigma) are the trainer's to apply.  Two launches per layer; the pairs' partial sums live in one buffer of the
+ *     population's: calls on one population must be ordered against each other.  d_util [P] f32 in device memory.
+ * Refusals, all with a message and before any device work.  CHUB_ERR_ARG: null arguments; P odd or < 2; N != P E or E no multiple of 32;
+ *     a population of another handle or policy; m or layer out of range; count < 0 or > P; sigma not finite or < 0; only one of d_W / d_b
+ *     NULL; everything chub_policy_act_device / chub_policy_run_steps refuse.  CHUB_ERR_UNSUPPORTED: create, destroy and the host forms
+ *     between chub_graph_begin and chub_graph_end; COMPAT in run_steps; the tape rules of chub_policy_act_device.
+ * Out of scope: sampling from a population (the sampled launches stay single-policy), per-member normalisers, non-antithetic noise, rank
+ *     shaping (fitness is chub_episode_stats_device's return column viewed as [P][E]; its reduction and ranking are the trainer's), the
+ *     multi-GPU hosts. */
+typedef struct chub_population chub_population;
+int chub_population_param_count(const chub_config *cfg, const chub_policy_spec *spec, int64_t *n_out);
+int chub_population_create(chub_policy *pol, int32_t P, uint64_t key, chub_population **out);
+int chub_population_destroy(chub_population *pop);
+int chub_population_perturb_device(chub_population *pop, const float *const *d_W, const float *const *d_b, float sigma, uint32_t generation,
+                                   void *stream);
+int chub_population_set_member_device(chub_population *pop, int32_t m, int32_t layer, const float *d_W, const float *d_b, void *stream);
+int chub_population_get_member_device(chub_population *pop, int32_t m, int32_t layer, float *d_W, float *d_b, void *stream);
+int chub_population_set_member(chub_population *pop, int32_t m, int32_t layer, const float *W, const float *b);  /* host; synchronises */
+int chub_population_get_member(chub_population *pop, int32_t m, int32_t layer, float *W, float *b);              /* host; synchronises */
+int chub_population_copy_members_device(chub_population *pop, const int32_t *d_src, const int32_t *d_dst, int32_t count, void *stream);
+int chub_population_act_device(chub_env *env, chub_population *pop, const float *d_obs, int64_t ld_obs, const uint8_t *d_mask, float *d_actions,
+                               uint64_t *d_pile_bits, float *d_tail, void *stream);
+int chub_population_run_steps(chub_env *env, chub_population *pop, int mode, float *const *d_packed2, float *d_reset_obs, float *d_final_obs,
+                              int64_t first_step, int64_t n_steps, void *stream);
+int chub_population_es_gradient_device(chub_population *pop, const float *d_util /* [P] */, uint32_t generation, float *const *d_gW,
+                                       float *const *d_gb, void *stream);
+
 /* The FCEV waiting list is unbounded as in the reference (HYD:264-265): the entries a list that still gets served can
  * hold are kept one by one, and once no prefix of it fits into 15 minutes any more (HYD:270-276: nobody is served again
  * until reset and the list only grows) its entries are folded into their count and running sums, which is all the

@@ -11,6 +11,11 @@
   gae             us per chub_rollout_gae_device over the collected day (T = 96, with d_ret, d_final_values and d_stats), with the bytes it
                   asks for and the bytes of the lines it touches; with --torch-gae also gae_torch, the same recurrence as a torch loop over
                   the same device memory in the same process (torch is then imported first, so that both share one HIP runtime).
+  --population    adds, around the same policy as the centre: pop_launch_P<P> us per chub_population_act_device at P = 2, 256 and 2048 members
+                  (as `launch`; at P = 2048 every workgroup reads its own member's weights), pop_closed_loop env-steps/s of
+                  chub_population_run_steps at P = 256 (as `closed_loop`), perturb_P<P> and es_gradient_P<P> us per
+                  chub_population_perturb_device / chub_population_es_gradient_device at P = 256 and 2048, with the Philox blocks a call
+                  computes; the sampled and set cases are left out.
 Every case is warmed up, then the cases alternate, ROUNDS times; median, best and worst round are reported with the build id.
 --open-loop-only measures the open loop alone, --launch-only the open loop and the deterministic launch, --no-sets the first five cases:
 with CHUB_LIB=<another build's libchub.so> those are the rates of a build without the newer entry points (the parent commit), on the same
@@ -46,6 +51,7 @@ def main():
     ap.add_argument("--launch-only", action="store_true")
     ap.add_argument("--torch-gae", action="store_true")
     ap.add_argument("--no-sets", action="store_true", help="the first five cases only: what a build without the pile set entry points can run")
+    ap.add_argument("--population", action="store_true", help="the open loop, the launch, the closed loop and the population cases")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     n_s, piles_s = args.shape.split("x")
@@ -95,6 +101,7 @@ def main():
         return n * steps / (time.perf_counter() - t0)
 
     cases = {("open_loop", "chub_run_steps", "env_steps_per_s"): open_loop}
+    notes = {}  # kind -> what a row of that case says on top
     if not args.open_loop_only:
         rs = np.random.RandomState(0)
         sizes = [D] + hidden + [A]
@@ -116,6 +123,10 @@ def main():
             return n * steps / (time.perf_counter() - t0)
 
         cases[("launch", "chub_policy_act_device", "us_per_launch")] = launch
+        if args.population:
+            cases[("closed_loop", "chub_policy_run_steps", "env_steps_per_s")] = closed_loop
+            population_cases(cases, notes, v, pol, sizes, packed, obs0, bits, tail, st, steps, args.calls, between_events)
+            args.launch_only = True  # (the sampled and set cases are not part of this run)
         if not args.launch_only:
             cases[("closed_loop", "chub_policy_run_steps", "env_steps_per_s")] = closed_loop
             # the SAMPLED actor: one launch with bits + tail + u + logp out, and chub_policy_collect in lock-step mode, a day per call
@@ -204,6 +215,7 @@ def main():
         row = dict(shape=args.shape, n_envs=n, piles=piles, mode="philox", net=[D] + hidden + [A], kind=kind, route=route, unit=unit, rounds=len(xs),
                    median=round(statistics.median(xs), 3), min=round(min(xs), 3), max=round(max(xs), 3), steps_per_round=steps,
                    launches_per_round=args.calls, build_id=build_id, lib=os.environ.get("CHUB_LIB", ""))
+        row.update(notes.get(kind, {}))
         if kind in ("gae", "gae_torch"):  # what the recurrence asks for (V, reward + done in; adv, ret out), and the lines that holds at a
             useful = 96 * n * (4 + 8 + 4 + 4) + n * 8           # (D + 2) * 4-byte row stride: every line of the packed blocks
             lines = 96 * n * ((D + 2) * 4 + 4 + 4 + 4) + n * 8
@@ -215,6 +227,62 @@ def main():
     if args.out:
         os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
         json.dump(rows, open(args.out, "w"), indent=1)
+
+
+def population_cases(cases, notes, v, pol, sizes, packed, obs0, bits, tail, st, steps, calls, between_events):
+    """the --population cases: populations of 2, 256 and 2048 members around `pol`, all perturbed from it once"""
+    n, D, stream = v.n_envs, v.obs_dim, st.ptr
+    shapes = list(zip(sizes[1:], sizes[:-1]))
+    pops = {P: v.make_population(pol, P, 77) for P in (2, 256, 2048)}
+    for q in pops.values():
+        q.perturb_device(0.05, 1, stream=stream)
+    util = multi_gpu.DeviceBuffer(2048 * 4)
+    util.from_host(np.random.RandomState(1).normal(size=2048).astype(np.float32))
+    gW, gb = [multi_gpu.DeviceBuffer(o * i * 4) for o, i in shapes], [multi_gpu.DeviceBuffer(o * 4) for o, _ in shapes]
+    few = max(1, calls // 10)
+
+    def pop_launch(q):
+        def run():
+            def many():
+                for _ in range(calls):
+                    q.act_device(packed[1].ptr, D + 2, d_pile_bits=bits.ptr, d_tail=tail.ptr, stream=stream)
+            return between_events(many) * 1e3 / calls
+        return run
+
+    def pop_closed_loop():
+        st.sync()
+        t0 = time.perf_counter()
+        pops[256].run_steps([p.ptr for p in packed], steps, mode="lockstep", d_reset_obs=obs0.ptr, stream=stream)
+        st.sync()
+        return n * steps / (time.perf_counter() - t0)
+
+    def perturb(q):
+        def run():
+            def many():
+                for g in range(few):
+                    q.perturb_device(0.05, g, stream=stream)
+            return between_events(many) * 1e3 / few
+        return run
+
+    def es_gradient(q):
+        def run():
+            def many():
+                for g in range(few):
+                    q.es_gradient_device(util.ptr, g, [x.ptr for x in gW], [x.ptr for x in gb], stream=stream)
+            return between_events(many) * 1e3 / few
+        return run
+
+    for P, q in pops.items():
+        cases[("pop_launch_P%d" % P, "chub_population_act_device", "us_per_launch")] = pop_launch(q)
+        notes["pop_launch_P%d" % P] = dict(members=P, weight_bytes_per_launch=(n // 32) * 4 * sum(
+            ((o + 31) // 32 * 32) * (((i + 1) & ~1) + 1) for o, i in shapes))
+    cases[("pop_closed_loop", "chub_population_run_steps", "env_steps_per_s")] = pop_closed_loop
+    notes["pop_closed_loop"] = dict(members=256)
+    for P in (256, 2048):
+        blocks = (P // 2) * sum(o * (i // 4 + 1) for o, i in shapes)  # one block per (pair, output row, group of four columns of [W | b])
+        cases[("perturb_P%d" % P, "chub_population_perturb_device", "us_per_call")] = perturb(pops[P])
+        cases[("es_gradient_P%d" % P, "chub_population_es_gradient_device", "us_per_call")] = es_gradient(pops[P])
+        notes["perturb_P%d" % P] = notes["es_gradient_P%d" % P] = dict(members=P, philox_blocks=blocks, launches_per_round=few)
 
 
 def torch_gae_case(packed_ptr, gae, n, T, D, calls):
