@@ -143,12 +143,14 @@ def test_perturb_equals_the_definition_bit_for_bit(piles):
 
 
 # ---- 2. act
-def act_equals_member_policies(v, pop, P, E, obs, make_member, what, lds):
-    """the population launch against one plain policy per member, in every output form; -> number of comparisons made"""
+def act_equals_member_policies(v, pop, P, E, obs, make_member, what, lds, mask=None):
+    """the population launch against one plain policy per member, in every output form; -> number of comparisons made.  mask: bool [N],
+    the rows the masked form names (None: the rows around the boundary between members 0 and 1, and the last row)"""
     n, D = v.n_envs, v.obs_dim
-    mask = np.zeros(n, bool)
-    mask[E - 5:E + 7] = True  # straddles the boundary between members 0 and 1
-    mask[n - 1] = True
+    if mask is None:
+        mask = np.zeros(n, bool)
+        mask[E - 5:E + 7] = True  # straddles the boundary between members 0 and 1
+        mask[n - 1] = True
     forms = (dict(), dict(bits=False, tail=False), dict(rows=False), dict(mask=mask))
     count = 0
     for ld in lds:
