@@ -214,6 +214,35 @@ class ChubGae(C.Structure):
                 ("gamma", C.c_float), ("lam", C.c_float), ("d_adv", C.c_void_p), ("d_ret", C.c_void_p), ("d_stats", C.c_void_p)]
 
 
+# actor gradients (chub_policy_grad_*): the CHUB_PLOSS_* enum of include/chub.h, in order
+PLOSS_NAMES = ("coef", "ppo_clip")
+PLOSS = {name: i for i, name in enumerate(PLOSS_NAMES)}
+
+
+def policy_loss(loss):
+    """a surrogate loss as its CHUB_PLOSS_* value: a name of PLOSS_NAMES, or the value itself (the library refuses an unknown one)"""
+    return _enum_value(PLOSS, loss, "policy loss")
+
+
+class ChubPolicyGradPlanOut(C.Structure):
+    """chub_policy_grad_plan_out of include/chub.h"""
+    _fields_ = [("n_params", C.c_int64), ("workspace_bytes", C.c_int64), ("workgroups", C.c_int32), ("lds_rows", C.c_int32),
+                ("lds_bytes", C.c_int32), ("in_registers", C.c_int32)]
+
+
+class ChubPolicyGradIn(C.Structure):
+    """chub_policy_grad_in of include/chub.h: device addresses, 0 / None = not given"""
+    _fields_ = [("R", C.c_int64), ("n_rows", C.c_int64), ("d_rows", C.c_void_p), ("d_features", C.c_void_p), ("ld_features", C.c_int64),
+                ("d_pile_bits", C.c_void_p), ("d_set_bits", C.c_void_p), ("d_u", C.c_void_p), ("d_logp_old", C.c_void_p), ("d_adv", C.c_void_p),
+                ("d_adv_stats", C.c_void_p), ("loss", C.c_int32), ("clip_eps", C.c_float), ("ent_coef", C.c_float), ("pad_", C.c_int32)]
+
+
+class ChubPolicyGradOut(C.Structure):
+    """chub_policy_grad_out of include/chub.h: device addresses, 0 / None = not asked for"""
+    _fields_ = [("d_gW", C.c_void_p * 4), ("d_gb", C.c_void_p * 4), ("d_glog_std", C.c_void_p), ("d_logp_new", C.c_void_p),
+                ("d_entropy", C.c_void_p), ("d_stats", C.c_void_p)]
+
+
 # pile sets (chub_pile_set_device): the CHUB_PSET_* enum of include/chub.h, in order
 PSET_NAMES = ("all", "occupied", "decidable")
 PSET = {name: i for i, name in enumerate(PSET_NAMES)}
@@ -432,6 +461,9 @@ def load_library():
         "chub_population_copy_members_device": (I, [P, P, P, C.c_int32, P]),
         "chub_population_act_device": (I, [P, P, P, L, P, P, P, P, P]), "chub_population_run_steps": (I, [P, P, I, P, P, P, L, L, P]),
         "chub_population_es_gradient_device": (I, [P, P, C.c_uint32, P, P, P]),
+        "chub_policy_grad_plan": (I, [C.POINTER(ChubConfig), C.POINTER(ChubPolicySpec), L, C.POINTER(ChubPolicyGradPlanOut)]),
+        "chub_policy_grad_create": (I, [P, L, C.POINTER(P)]), "chub_policy_grad_destroy": (I, [P]),
+        "chub_policy_grad_device": (I, [P, C.POINTER(ChubPolicyGradIn), C.POINTER(ChubPolicyGradOut), P]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -475,7 +507,8 @@ EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "ch
             "chub_policy_normalizer_from_moments_device",
             "chub_population_param_count", "chub_population_create", "chub_population_destroy", "chub_population_perturb_device",
             "chub_population_set_member_device", "chub_population_get_member_device", "chub_population_set_member", "chub_population_get_member",
-            "chub_population_copy_members_device", "chub_population_act_device", "chub_population_run_steps", "chub_population_es_gradient_device"]
+            "chub_population_copy_members_device", "chub_population_act_device", "chub_population_run_steps", "chub_population_es_gradient_device",
+            "chub_policy_grad_plan", "chub_policy_grad_create", "chub_policy_grad_destroy", "chub_policy_grad_device"]
 
 
 def check(rc):

@@ -169,5 +169,67 @@ void launch_policy_unlayout(const float *d_w, const float *d_bias, float *d_W, f
 void launch_population_copy(float *params, float *stage, int64_t member_floats, int P, const int32_t *d_src, const int32_t *d_dst, int count,
                             hipStream_t stream);
 
+// ---- actor gradients (include/chub.h, "actor gradients on the device").  A workgroup of four waves walks tiles of 32 rows b, b + blocks,
+// ..; every image of a tile lives in LDS as [row][kGradRowStride] f32: the feature rows X, the output of EVERY hidden layer, two delta
+// images and a few scratch rows.  The stride of 33 words keeps both read directions free of bank conflicts: across the 32 rows of the
+// tile at one feature (the forward's and W^T delta's B operand: consecutive words) and across 32 features at one row of the tile (both
+// operands of dW += delta h^T: word 33 i + e, every bank once).  No image is kept twice.
+constexpr int kGradLanes = 256;
+constexpr int kGradWaves = kGradLanes / 64;
+constexpr int kGradRowStride = 33;
+constexpr int kGradScratchRows = 16;     // [wave] logp partials, [wave] entropy partials, coefficient, entropy weight, [G] log_std terms, row indices
+constexpr int kGradLdsBytes = 160 * 1024;  // what a CU has; the launch asks for its rows through the function attribute
+constexpr int kGradMaxBlocks = 512;      // workgroups at most
+constexpr size_t kGradPartialBytes = 256u << 20;  // .. and fewer where their f32 partials would come to more than this
+constexpr int kGradRegSlots = 4;         // dW tiles of 32 x 32 a wave keeps in registers (else they live in the workgroup's partials)
+constexpr int kGradStats = 6, kGradPart64 = kGradStats + 4;  // f64 partials per workgroup: the stats, then the log_std sums
+enum PolicyLoss { PLOSS_COEF = 0, PLOSS_PPO_CLIP, PLOSS_COUNT };
+
+struct GradLayer {
+    const float *w, *b;   // the forward's layout (PolicyLayer)
+    const float *wrm;     // [32 ot][32 it] row-major, zeros beyond out / in: the A operand of delta_in = W^T delta_out (null for layer 0)
+    int32_t k_pad, in, out;
+    int32_t ot, it;       // tiles of 32 outputs / inputs
+    int32_t h_row0;       // first LDS row of the layer's output image (hidden layers)
+    int32_t pair0;        // the layer's first dW tile among the call's: tile (t, c) is pair0 + t * it + c
+    int32_t bias0;        // the layer's first float in the bias block of a workgroup's partials
+};
+
+struct PolicyGradArgs {
+    int64_t R, rows_total;
+    const int64_t *rows;          // [R] or null
+    const float *features;        // [.][F] raw, row stride ld
+    int64_t ld;
+    const uint32_t *pile_bits, *set_bits;  // [.][2 W] u32 (PILES); set_bits null: every pile
+    const float *u, *logp_old, *adv;
+    const double *adv_stats;      // [3] or null
+    const float *mean, *inv_std, *log_std;
+    GradLayer layer[kPolicyMaxLayers];
+    float *logp_new, *entropy;    // [R] or null
+    float *part;                  // [blocks][part_floats]: per pair [16 registers][64 lanes], then the bias block
+    double *part64;               // [blocks][kGradPart64]
+    float clip, clip_eps, ent_coef;
+    int32_t n_layers, F, x_rows, d_row0[2], s_row0;
+    int32_t hidden_act, normalize, head, S, A, W, G;
+    int32_t loss, backward, n_pairs, part_floats, bias_floats;
+};
+
+struct GradMergeArgs {
+    const float *part;
+    const double *part64;
+    float *gW[kPolicyMaxLayers], *gb[kPolicyMaxLayers], *glog_std;
+    double *stats;
+    int64_t R;
+    int64_t param0[kPolicyMaxLayers + 1];  // first flat parameter of layer l: out * (in + 1) each
+    int32_t in[kPolicyMaxLayers], out[kPolicyMaxLayers], it[kPolicyMaxLayers], pair0[kPolicyMaxLayers], bias0[kPolicyMaxLayers];
+    int32_t n_layers, blocks, part_floats, bias_base, G, backward;
+};
+
+// host-only: the largest dynamic LDS the gradient kernel may be launched with (set once per process and device)
+int policy_grad_prepare();
+// [launch 1, backward only] the row-major copies from the live device weights; [launch 2] k_policy_grad on `blocks` workgroups with
+// lds_rows rows of LDS; [launch 3] the merge
+void launch_policy_grad(const PolicyGradArgs &a, const GradMergeArgs &m, int blocks, int lds_rows, bool in_registers, hipStream_t stream);
+
 }  // namespace chub
 #endif

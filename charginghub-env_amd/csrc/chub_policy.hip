@@ -736,4 +736,383 @@ void launch_population_copy(float *params, float *stage, int64_t member_floats, 
                        member_floats, P, d_src, d_dst, count);
 }
 
+// ---- actor gradients (include/chub.h, "actor gradients on the device"; the images and the partials' layout are chub_policy.h's)
+//
+// Per tile of 32 rows: gather through d_rows and normalise into X; the forward as k_policy runs it (the same A operand from the same device
+// layout, the same k order from the bias), every hidden layer into an image of its own; the head's z into delta image 0 while each lane adds
+// its rows' log-probability and entropy terms (the waves meet in LDS in wave order, as in k_policy); 32 lanes form the rows' advantage,
+// ratio, loss term and the coefficient c = dL R / dlogp; the head's lanes turn z into delta z in place; then per layer, last to first,
+// dW += delta h^T and db += delta 1 over the tile's 32 rows and delta_in = (W^T delta) act'(h) into the other delta image.
+// One MFMA form serves all three products (v_mfma_f32_32x32x2_f32, lane l gives A[l & 31][l >> 5] and B[l >> 5][l & 31]):
+//   forward   C[out][row] : A = w[t][2 s + half][out]          B = h_in[2 s + half][row]      k = input
+//   W^T delta C[in][row]  : A = wrm[2 s + half][32 c + in]      B = delta[2 s + half][row]     k = output
+//   dW        C[out][in]  : A = delta[32 t + out][2 s + half]   B = h_in[32 c + in][2 s + half] k = row of the tile
+// kSlots > 0: a wave's dW tiles (pair p belongs to wave p % 4, slot p / 4) stay in registers for the whole walk; kSlots == 0: they are
+// read from and written to the workgroup's own slice of the partials around each tile's sixteen MFMAs, by the lane that owns them.
+__device__ __forceinline__ float grad_sigmoid(float z) { return __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-z))); }
+
+__global__ void k_policy_grad_wrm(const PolicyGradArgs a) {
+    for (int l = 1; l < a.n_layers; l++) {
+        const GradLayer L = a.layer[l];
+        const int ld = L.it * 32;
+        const int64_t total = (int64_t) L.ot * 32 * ld;
+        float *dst = const_cast<float *>(L.wrm);
+        for (int64_t idx = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t) gridDim.x * blockDim.x) {
+            const int n = (int) (idx / ld), k = (int) (idx - (int64_t) n * ld);
+            dst[idx] = (n < L.out && k < L.in) ? L.w[((int64_t) (n >> 5) * L.k_pad + k) * kPolicyOutTile + (n & 31)] : 0.0f;
+        }
+    }
+}
+
+__device__ __forceinline__ f32x16 grad_dw_tile(f32x16 acc, const float *delta, const float *hin, int t, int c, int col, int half) {
+    constexpr int RS = kGradRowStride;
+    const float *as = delta + (t * 32 + col) * RS + half, *bs = hin + (c * 32 + col) * RS + half;
+#pragma unroll
+    for (int s = 0; s < 16; s++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(as[2 * s], bs[2 * s], acc, 0, 0, 0);
+    return acc;
+}
+
+template <int kSlots>
+__global__ __launch_bounds__(kGradLanes) void k_policy_grad(const PolicyGradArgs a) {
+    constexpr int RS = kGradRowStride, nw = kGradWaves;
+    extern __shared__ float lds[];
+    const int tid = (int) threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
+    float *const X = lds;
+    float *const D0 = lds + a.d_row0[0] * RS, *const D1 = lds + a.d_row0[1] * RS;
+    float *const Sc = lds + a.s_row0 * RS;
+    int64_t *const rowi = (int64_t *) (Sc + (kGradScratchRows - 2) * RS);  // (the last two scratch rows; s_row0 is even: 8-byte aligned)
+    const int nl = a.n_layers;
+    const bool piles = a.head == PHEAD_PILES;
+    const int g0 = piles ? a.S : 0;
+    float *const mypart = a.part + (size_t) blockIdx.x * (size_t) a.part_floats;
+    float *const mybias = mypart + (size_t) a.n_pairs * 1024;
+
+    // the advantage's normaliser: mean and 1 / sqrt(var + 1e-8) in f64, every operation rounded once, each rounded once to f32
+    float m32 = 0.0f, s32 = 1.0f;
+    if (a.adv_stats) {
+        const double cnt = a.adv_stats[0], m = __ddiv_rn(a.adv_stats[1], cnt);
+        double var = __dsub_rn(__ddiv_rn(a.adv_stats[2], cnt), __dmul_rn(m, m));
+        var = var > 0.0 ? var : 0.0;
+        m32 = (float) m;
+        s32 = (float) __ddiv_rn(1.0, __dsqrt_rn(__dadd_rn(var, 1e-8)));
+    }
+    const float ratio_lo = __fsub_rn(1.0f, a.clip_eps), ratio_hi = __fadd_rn(1.0f, a.clip_eps);
+
+    f32x16 racc[kSlots > 0 ? kSlots : 1];
+#pragma unroll
+    for (int i = 0; i < (kSlots > 0 ? kSlots : 1); i++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) racc[i][r] = 0.0f;
+    if (a.backward) {
+        if constexpr (kSlots == 0) {
+            for (int p = wave; p < a.n_pairs; p += nw)
+#pragma unroll
+                for (int r = 0; r < 16; r++) mypart[((size_t) p * 16 + r) * 64 + lane] = 0.0f;
+        }
+        for (int l = 0; l < nl; l++)  // (the lane that zeroes a bias sum is the lane that adds to it)
+            for (int n = tid; n < a.layer[l].ot * 32; n += kGradLanes) mybias[a.layer[l].bias0 + n] = 0.0f;
+    }
+    double st[kGradStats] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, gls = 0.0;
+
+    const int64_t n_tiles = (a.R + 31) / 32;
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        // ---- the tile's 32 row indices, resolved once (-1: past R, or an index outside the arrays)
+        if (tid < 32) {
+            const int64_t r = tile * 32 + tid;
+            int64_t ri = -1;
+            if (r < a.R) ri = a.rows ? a.rows[r] : r;
+            rowi[tid] = (ri >= 0 && ri < a.rows_total) ? ri : -1;
+        }
+        __syncthreads();
+        // ---- the feature rows of the tile, normalised with the policy's current normaliser, as [feature][row]
+        for (int idx = tid; idx < 32 * a.F; idx += kGradLanes) {
+            const int j = idx / a.F, f = idx - j * a.F;
+            const int64_t ri = rowi[j];
+            float x = 0.0f;
+            if (ri >= 0) {
+                x = a.features[ri * a.ld + f];
+                if (a.normalize) {
+                    x = __fmul_rn(__fsub_rn(x, a.mean[f]), a.inv_std[f]);
+                    x = fminf(fmaxf(x, -a.clip), a.clip);
+                }
+            }
+            X[f * RS + j] = x;
+        }
+        for (int idx = tid; idx < (a.x_rows - a.F) * 32; idx += kGradLanes) X[(a.F + (idx >> 5)) * RS + (idx & 31)] = 0.0f;
+        const int64_t r_col = tile * 32 + col;
+        const int64_t ri = rowi[col];
+        const bool valid = ri >= 0;
+        __syncthreads();
+
+        // ---- the forward
+        float logp = 0.0f, ent = 0.0f;
+#pragma unroll
+        for (int l = 0; l < kPolicyMaxLayers; l++) {
+            if (l < nl) {
+                const GradLayer L = a.layer[l];
+                const bool last = l == nl - 1;
+                const float *src = l ? lds + a.layer[l ? l - 1 : 0].h_row0 * RS : X;
+                float *dst = last ? D0 : lds + L.h_row0 * RS;
+                const int ksteps = L.k_pad >> 1;
+                for (int t = wave; t < L.ot; t += nw) {
+                    f32x16 acc;
+                    const float *bt = L.b + t * kPolicyOutTile + 4 * half;
+#pragma unroll
+                    for (int r = 0; r < 16; r++) acc[r] = bt[(r & 3) + 8 * (r >> 2)];
+                    const float *wt = L.w + (size_t) t * (size_t) L.k_pad * kPolicyOutTile + lane;
+                    const float *xs = src + half * RS + col;
+                    for (int s = 0; s < ksteps; s++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wt[64 * s], xs[2 * RS * s], acc, 0, 0, 0);
+                    if (!last) {
+#pragma unroll
+                        for (int r = 0; r < 16; r++) {
+                            const float z = acc[r];
+                            dst[(t * 32 + acc_row(r, half)) * RS + col] = a.hidden_act == PACT_TANH ? tanhf(z) : fmaxf(z, 0.0f);
+                        }
+                    } else {
+                        uint32_t on_w = 0u, set_w = 0xFFFFFFFFu;
+                        if (piles && valid && t < 2 * a.W) {
+                            on_w = a.pile_bits[ri * (int64_t) (2 * a.W) + t];
+                            if (a.set_bits) set_w = a.set_bits[ri * (int64_t) (2 * a.W) + t];
+                        }
+#pragma unroll
+                        for (int r = 0; r < 16; r++) {
+                            const int n = t * 32 + acc_row(r, half), i = n - g0;
+                            const float z = acc[r];
+                            dst[n * RS + col] = z;
+                            if (!valid) continue;
+                            if (piles && n < a.S) {
+                                if ((set_w >> (n & 31)) & 1u) {
+                                    const bool on = (on_w >> (n & 31)) & 1u;
+                                    logp = __fsub_rn(logp, policy_softplus(on ? -z : z));
+                                    ent = __fadd_rn(ent, __fsub_rn(policy_softplus(z), __fmul_rn(z, grad_sigmoid(z))));
+                                }
+                            } else if (i >= 0 && i < a.G) {
+                                const float ls = a.log_std[i];
+                                const float eps = __fdiv_rn(__fsub_rn(a.u[ri * a.G + i], z), expf(ls));
+                                logp = __fadd_rn(logp, __fsub_rn(__fsub_rn(__fmul_rn(-0.5f, __fmul_rn(eps, eps)), ls), kHalfLn2Pi));
+                                ent = __fadd_rn(ent, __fadd_rn(__fadd_rn(0.5f, ls), kHalfLn2Pi));
+                            }
+                        }
+                    }
+                }
+                if (!last) __syncthreads();
+            }
+        }
+        // ---- a row's log-probability and entropy: the half-waves by a shuffle, the waves in wave order through LDS
+        logp = __fadd_rn(logp, __shfl_xor(logp, 32));
+        ent = __fadd_rn(ent, __shfl_xor(ent, 32));
+        if (half == 0) {
+            Sc[wave * RS + col] = logp;
+            Sc[(nw + wave) * RS + col] = ent;
+        }
+        __syncthreads();
+        if (tid < 32) {
+            float lp = Sc[col], en = Sc[nw * RS + col];
+            for (int w = 1; w < nw; w++) {
+                lp = __fadd_rn(lp, Sc[w * RS + col]);
+                en = __fadd_rn(en, Sc[(nw + w) * RS + col]);
+            }
+            float c = 0.0f;
+            if (valid) {
+                float A = a.adv[ri];
+                if (a.adv_stats) A = __fmul_rn(__fsub_rn(A, m32), s32);
+                float term;
+                if (a.loss == PLOSS_COEF) {
+                    c = -A;
+                    term = __fsub_rn(-__fmul_rn(A, lp), __fmul_rn(a.ent_coef, en));
+                } else {
+                    const float lo = a.logp_old[ri];
+                    const float ratio = expf(__fsub_rn(lp, lo));
+                    const float rc = fminf(fmaxf(ratio, ratio_lo), ratio_hi);
+                    const float surr = fminf(__fmul_rn(ratio, A), __fmul_rn(rc, A));
+                    term = __fsub_rn(-surr, __fmul_rn(a.ent_coef, en));
+                    // (A >= 0 and ratio < 1 + eps) or (A < 0 and ratio > 1 - eps), as two selects: written as the two-clause predicate the
+                    // compiler's gfx950 code zeroed c in every lane of the second clause; a NaN advantage is inactive
+                    const bool up = A >= 0.0f, inside = up ? ratio < ratio_hi : ratio > ratio_lo;
+                    const bool active = inside && A == A;
+                    const float nar = -__fmul_rn(A, ratio);
+                    c = active ? nar : 0.0f;
+                    st[3] += (double) lo - (double) lp;
+                    st[4] += active ? 0.0 : 1.0;
+                    st[5] += (double) ratio;
+                }
+                st[0] += 1.0;
+                st[1] += (double) term;
+                st[2] += (double) en;
+            }
+            if (r_col < a.R) {
+                if (a.logp_new) a.logp_new[r_col] = valid ? lp : 0.0f;
+                if (a.entropy) a.entropy[r_col] = valid ? en : 0.0f;
+            }
+            Sc[2 * nw * RS + col] = c;
+            Sc[(2 * nw + 1) * RS + col] = valid ? -a.ent_coef : 0.0f;
+        }
+        __syncthreads();
+        if (!a.backward) continue;
+
+        // ---- the head's delta z, in place of z
+        {
+            const GradLayer L = a.layer[nl - 1];
+            const float c = Sc[2 * nw * RS + col], ec = Sc[(2 * nw + 1) * RS + col];
+            for (int t = wave; t < L.ot; t += nw) {
+                uint32_t on_w = 0u, set_w = 0xFFFFFFFFu;
+                if (piles && valid && t < 2 * a.W) {
+                    on_w = a.pile_bits[ri * (int64_t) (2 * a.W) + t];
+                    if (a.set_bits) set_w = a.set_bits[ri * (int64_t) (2 * a.W) + t];
+                }
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int n = t * 32 + acc_row(r, half), i = n - g0;
+                    const float z = D0[n * RS + col];
+                    float d = 0.0f;
+                    if (valid && piles && n < a.S) {
+                        if ((set_w >> (n & 31)) & 1u) {
+                            const float sg = grad_sigmoid(z), on = ((on_w >> (n & 31)) & 1u) ? 1.0f : 0.0f;
+                            const float dh = -__fmul_rn(__fmul_rn(z, sg), __fsub_rn(1.0f, sg));
+                            d = __fadd_rn(__fmul_rn(c, __fsub_rn(on, sg)), __fmul_rn(ec, dh));
+                        }
+                    } else if (valid && i >= 0 && i < a.G) {
+                        const float sd = expf(a.log_std[i]);
+                        const float eps = __fdiv_rn(__fsub_rn(a.u[ri * a.G + i], z), sd);
+                        d = __fmul_rn(c, __fdiv_rn(eps, sd));
+                        Sc[(2 * nw + 2 + i) * RS + col] = __fadd_rn(__fmul_rn(c, __fsub_rn(__fmul_rn(eps, eps), 1.0f)), ec);
+                    } else if (!valid && i >= 0 && i < a.G) {
+                        Sc[(2 * nw + 2 + i) * RS + col] = 0.0f;
+                    }
+                    D0[n * RS + col] = d;
+                }
+            }
+        }
+        __syncthreads();
+        if (tid < a.G)
+            for (int e = 0; e < 32; e++) gls += (double) Sc[(2 * nw + 2 + tid) * RS + e];
+
+        // ---- the backward, last layer first
+        for (int l = nl - 1; l >= 0; l--) {
+            const GradLayer L = a.layer[l];
+            const float *Dc = ((nl - 1 - l) & 1) ? D1 : D0;
+            float *Dn = ((nl - 1 - l) & 1) ? D0 : D1;
+            const float *hin = l ? lds + a.layer[l ? l - 1 : 0].h_row0 * RS : X;
+            const int np = L.ot * L.it;
+            if constexpr (kSlots > 0) {
+#pragma unroll
+                for (int slot = 0; slot < kSlots; slot++) {
+                    const int pl = slot * nw + wave - L.pair0;
+                    if (pl >= 0 && pl < np) racc[slot] = grad_dw_tile(racc[slot], Dc, hin, pl / L.it, pl % L.it, col, half);
+                }
+            } else {
+                for (int p = L.pair0 + (((wave - L.pair0) % nw) + nw) % nw; p < L.pair0 + np; p += nw) {
+                    const int pl = p - L.pair0;
+                    float *q = mypart + (size_t) p * 1024 + lane;
+                    f32x16 acc;
+#pragma unroll
+                    for (int r = 0; r < 16; r++) acc[r] = q[r * 64];
+                    acc = grad_dw_tile(acc, Dc, hin, pl / L.it, pl % L.it, col, half);
+#pragma unroll
+                    for (int r = 0; r < 16; r++) q[r * 64] = acc[r];
+                }
+            }
+            for (int n = tid; n < L.ot * 32; n += kGradLanes) {
+                float s = 0.0f;
+                for (int e = 0; e < 32; e++) s = __fadd_rn(s, Dc[n * RS + e]);
+                mybias[L.bias0 + n] = __fadd_rn(mybias[L.bias0 + n], s);
+            }
+            if (l > 0) {
+                const int ld = L.it * 32, steps = (L.out + 1) >> 1;
+                const float *hp = hin;
+                for (int c = wave; c < L.it; c += nw) {
+                    f32x16 acc;
+#pragma unroll
+                    for (int r = 0; r < 16; r++) acc[r] = 0.0f;
+                    const float *wa = L.wrm + (size_t) half * ld + c * 32 + col;
+                    const float *bs = Dc + half * RS + col;
+                    for (int s = 0; s < steps; s++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[(size_t) 2 * s * ld], bs[2 * RS * s], acc, 0, 0, 0);
+#pragma unroll
+                    for (int r = 0; r < 16; r++) {
+                        const int k = c * 32 + acc_row(r, half);
+                        const float h = hp[k * RS + col];
+                        Dn[k * RS + col] = a.hidden_act == PACT_TANH ? __fmul_rn(acc[r], __fsub_rn(1.0f, __fmul_rn(h, h))) : (h > 0.0f ? acc[r] : 0.0f);
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+
+    // ---- the workgroup's partials: the dW tiles a wave kept, the stats of its 32 row lanes in lane order, the log_std sums
+    if constexpr (kSlots > 0) {
+        if (a.backward) {
+#pragma unroll
+            for (int slot = 0; slot < kSlots; slot++) {
+                const int p = slot * nw + wave;
+                if (p < a.n_pairs) {
+#pragma unroll
+                    for (int r = 0; r < 16; r++) mypart[((size_t) p * 16 + r) * 64 + lane] = racc[slot][r];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    double *const red = (double *) Sc;  // (s_row0 is even: 8-byte aligned)
+    if (tid < 32)
+#pragma unroll
+        for (int i = 0; i < kGradStats; i++) red[i * 32 + tid] = st[i];
+    __syncthreads();
+    double *const p64 = a.part64 + (size_t) blockIdx.x * kGradPart64;
+    if (tid < kGradStats) {
+        double s = 0.0;
+        for (int e = 0; e < 32; e++) s += red[tid * 32 + e];
+        p64[tid] = s;
+    }
+    if (tid < 4) p64[kGradStats + tid] = tid < a.G ? gls : 0.0;  // (lane i < G summed log_std term i)
+}
+
+// the workgroups' partials, summed in f64 in block order, times 1 / R, rounded once: one lane per parameter in the trainer's layout
+__global__ __launch_bounds__(256) void k_policy_grad_merge(const GradMergeArgs m) {
+    const int64_t idx = (int64_t) blockIdx.x * 256 + threadIdx.x;
+    const double R = (double) m.R;
+    if (blockIdx.x == 0 && threadIdx.x < kGradPart64) {
+        const int i = (int) threadIdx.x;
+        double s = 0.0;
+        for (int b = 0; b < m.blocks; b++) s += m.part64[(size_t) b * kGradPart64 + i];
+        if (i < kGradStats) {
+            if (m.stats) m.stats[i] = s;
+        } else if (m.backward && m.glog_std && i - kGradStats < m.G) {
+            m.glog_std[i - kGradStats] = (float) __ddiv_rn(s, R);
+        }
+    }
+    if (!m.backward || idx >= m.param0[m.n_layers]) return;
+    int l = 0;
+    while (l + 1 < m.n_layers && idx >= m.param0[l + 1]) l++;
+    const int64_t at = idx - m.param0[l];
+    const int in = m.in[l], n = (int) (at / (in + 1)), k = (int) (at - (int64_t) n * (in + 1));
+    float *dst = k < in ? (m.gW[l] ? m.gW[l] + (int64_t) n * in + k : nullptr) : (m.gb[l] ? m.gb[l] + n : nullptr);
+    if (!dst) return;
+    size_t off;
+    if (k < in) {
+        const int i = n & 31, r = (i & 3) + 4 * (i >> 3), hf = (i >> 2) & 1;
+        off = ((size_t) (m.pair0[l] + (n >> 5) * m.it[l] + (k >> 5)) * 16 + r) * 64 + (k & 31) + 32 * hf;
+    } else {
+        off = (size_t) m.bias_base + m.bias0[l] + n;
+    }
+    double s = 0.0;
+    for (int b = 0; b < m.blocks; b++) s += (double) m.part[(size_t) b * (size_t) m.part_floats + off];
+    *dst = (float) __ddiv_rn(s, R);
+}
+
+int policy_grad_prepare() {
+    if (hipFuncSetAttribute((const void *) k_policy_grad<0>, hipFuncAttributeMaxDynamicSharedMemorySize, kGradLdsBytes) != hipSuccess) return -1;
+    if (hipFuncSetAttribute((const void *) k_policy_grad<kGradRegSlots>, hipFuncAttributeMaxDynamicSharedMemorySize, kGradLdsBytes) != hipSuccess) return -1;
+    return 0;
+}
+
+void launch_policy_grad(const PolicyGradArgs &a, const GradMergeArgs &m, int blocks, int lds_rows, bool in_registers, hipStream_t stream) {
+    if (a.backward && a.n_layers > 1) hipLaunchKernelGGL(k_policy_grad_wrm, dim3(64), dim3(256), 0, stream, a);
+    const size_t lds_bytes = (size_t) lds_rows * kGradRowStride * sizeof(float);
+    if (in_registers) hipLaunchKernelGGL(k_policy_grad<kGradRegSlots>, dim3((unsigned) blocks), dim3(kGradLanes), lds_bytes, stream, a);
+    else hipLaunchKernelGGL(k_policy_grad<0>, dim3((unsigned) blocks), dim3(kGradLanes), lds_bytes, stream, a);
+    const int64_t total = a.backward ? m.param0[m.n_layers] : 1;
+    hipLaunchKernelGGL(k_policy_grad_merge, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, stream, m);
+}
+
 }  // namespace chub

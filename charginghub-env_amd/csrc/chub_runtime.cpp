@@ -3486,6 +3486,7 @@ struct chub_policy {
     float *d_log_std;
     std::vector<void *> allocs;
     std::vector<chub_population *> populations;  // made for this policy (chub_population_create): destroyed before it
+    std::vector<chub_policy_grad *> grads;       // made for this policy (chub_policy_grad_create): destroyed before it
 };
 
 extern "C" {
@@ -3561,10 +3562,12 @@ int chub_policy_input_width(const chub_config *cfg, const chub_policy_spec *spec
 }
 
 static void population_free(chub_population *pop);
+static void policy_grad_free(chub_policy_grad *g);
 
 static void policy_free(chub_policy *pol) {
     chub_env *e = pol->env;
     while (!pol->populations.empty()) population_free(pol->populations.back());
+    while (!pol->grads.empty()) policy_grad_free(pol->grads.back());
     (void) hipSetDevice(e->device);
     (void) hipDeviceSynchronize();  // (a launch still in flight reads the weights and the scratch)
     for (void *p : pol->allocs) (void) hipFree(p);
@@ -4540,6 +4543,259 @@ int chub_population_es_gradient_device(chub_population *pop, const float *d_util
     for (int l = 0; l < pol->spec.n_layers; l++)  // (one buffer of partials: the stream orders a layer's merge before the next layer's sums)
         launch_population_es_gradient(population_layer(pop, l, generation), d_util, pop->chunk_pairs, pop->chunks, pop->d_part, d_gW[l], d_gb[l],
                                       (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+// ---- actor gradients on the device (include/chub.h): the plan, the object, the call.  The kernels are chub_policy.hip's
+static_assert((int) CHUB_PLOSS_COUNT == PLOSS_COUNT && (int) CHUB_PLOSS_PPO_CLIP == PLOSS_PPO_CLIP, "chub_policy.h restates the CHUB_PLOSS_* enum");
+}  // extern "C"
+
+// what a spec comes to for the gradient launches: tiles, LDS rows, the partials' layout and the workgroups of a call of R rows
+struct GradPlan {
+    int64_t n_params, wrm_floats, wrm_off[kPolicyMaxLayers], param0[kPolicyMaxLayers + 1];
+    int32_t in[kPolicyMaxLayers], ot[kPolicyMaxLayers], it[kPolicyMaxLayers], h_row0[kPolicyMaxLayers], pair0[kPolicyMaxLayers], bias0[kPolicyMaxLayers];
+    int32_t x_rows, d_row0[2], s_row0, lds_rows, n_pairs, bias_floats, part_floats, in_registers;
+};
+
+static int grad_blocks(const GradPlan &gp, int64_t R) {
+    const int64_t tiles = (R + 31) / 32;
+    int64_t nb = std::min<int64_t>((tiles + 7) & ~(int64_t) 7, kGradMaxBlocks);
+    const int64_t by_bytes = std::max<int64_t>(8, (int64_t) (kGradPartialBytes / ((size_t) gp.part_floats * sizeof(float))) & ~(int64_t) 7);
+    return (int) std::min(nb, by_bytes);
+}
+
+static size_t grad_workspace(const GradPlan &gp, int blocks) {
+    return (size_t) gp.wrm_floats * sizeof(float) + (size_t) blocks * ((size_t) gp.part_floats * sizeof(float) + kGradPart64 * sizeof(double));
+}
+
+static int grad_plan(const chub_policy_spec *sp, const PolicyShape &ps, GradPlan &gp) {
+    memset(&gp, 0, sizeof gp);
+    const int nl = sp->n_layers;
+    int rows = (ps.F + 31) / 32 * 32, dmax = 0;
+    gp.x_rows = rows;
+    for (int l = 0; l < nl; l++) {
+        gp.in[l] = l ? sp->width[l - 1] : ps.F;
+        gp.ot[l] = (sp->width[l] + 31) / 32;
+        gp.it[l] = (gp.in[l] + 31) / 32;
+        gp.pair0[l] = gp.n_pairs;
+        gp.n_pairs += gp.ot[l] * gp.it[l];
+        gp.bias0[l] = gp.bias_floats;
+        gp.bias_floats += gp.ot[l] * 32;
+        gp.param0[l] = gp.n_params;
+        gp.n_params += (int64_t) sp->width[l] * (gp.in[l] + 1);
+        if (l) {
+            gp.wrm_off[l] = gp.wrm_floats;
+            gp.wrm_floats += (int64_t) gp.ot[l] * 32 * gp.it[l] * 32;
+        }
+        if (l + 1 < nl) {
+            gp.h_row0[l] = rows;
+            rows += gp.ot[l] * 32;
+        }
+        dmax = std::max(dmax, gp.ot[l] * 32);
+    }
+    gp.param0[nl] = gp.n_params;
+    gp.d_row0[0] = rows;
+    gp.d_row0[1] = rows + dmax;
+    gp.s_row0 = rows + 2 * dmax;
+    gp.lds_rows = gp.s_row0 + kGradScratchRows;
+    gp.part_floats = gp.n_pairs * 1024 + gp.bias_floats;
+    gp.in_registers = gp.n_pairs <= kGradRegSlots * kGradWaves ? 1 : 0;
+    if ((int64_t) gp.lds_rows * kGradRowStride * (int64_t) sizeof(float) > kGradLdsBytes)
+        return fail(CHUB_ERR_UNSUPPORTED, "the gradient launch keeps the feature rows, every hidden layer and two delta images in LDS: " +
+                                              std::to_string(gp.lds_rows) + " rows of " + std::to_string(kGradRowStride) + " floats, at most " +
+                                              std::to_string(kGradLdsBytes / (kGradRowStride * (int) sizeof(float))) + " (160 KiB); the policy still acts and samples");
+    return CHUB_OK;
+}
+
+struct chub_policy_grad {
+    chub_policy *pol;
+    int64_t max_rows;
+    GradPlan gp;
+    int32_t max_blocks;
+    float *d_wrm, *d_part;
+    double *d_part64;
+};
+
+extern "C" {
+
+static void policy_grad_free(chub_policy_grad *g) {
+    chub_policy *pol = g->pol;
+    (void) hipSetDevice(pol->env->device);
+    (void) hipDeviceSynchronize();  // (a launch still in flight reads the copies and writes the partials)
+    if (g->d_wrm) (void) hipFree(g->d_wrm);
+    if (g->d_part) (void) hipFree(g->d_part);
+    if (g->d_part64) (void) hipFree(g->d_part64);
+    pol->grads.erase(std::remove(pol->grads.begin(), pol->grads.end(), g), pol->grads.end());
+    delete g;
+}
+
+int chub_policy_grad_plan(const chub_config *cfg, const chub_policy_spec *spec, int64_t R, chub_policy_grad_plan_out *out) {
+    if (!cfg || !spec || !out) return fail(CHUB_ERR_ARG, "null argument");
+    if (R < 1) return fail(CHUB_ERR_ARG, "chub_policy_grad_plan: R is at least 1");
+    PolicyShape ps;
+    if (const int rc = policy_shape(cfg->station_list, spec, ps)) return rc;
+    GradPlan gp;
+    if (const int rc = grad_plan(spec, ps, gp)) return rc;
+    out->n_params = gp.n_params;
+    out->workgroups = grad_blocks(gp, R);
+    out->lds_rows = gp.lds_rows;
+    out->lds_bytes = gp.lds_rows * kGradRowStride * (int32_t) sizeof(float);
+    out->in_registers = gp.in_registers;
+    out->workspace_bytes = (int64_t) grad_workspace(gp, out->workgroups);
+    return CHUB_OK;
+}
+
+int chub_policy_grad_create(chub_policy *pol, int64_t max_rows, chub_policy_grad **out) {
+    if (!pol || !out) return fail(CHUB_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (max_rows < 1) return fail(CHUB_ERR_ARG, "chub_policy_grad_create: max_rows is at least 1");
+    chub_env *e = pol->env;
+    if (!pol->explore) return fail(CHUB_ERR_ARG, "chub_policy_grad_create: chub_policy_set_exploration first (the log-probability needs log_std)");
+    PolicyShape ps;
+    if (const int rc = policy_shape(e->hp.S, &pol->spec, ps)) return rc;
+    GradPlan gp;
+    if (const int rc = grad_plan(&pol->spec, ps, gp)) return rc;
+    if (e->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_grad_create between chub_graph_begin and chub_graph_end (it allocates and synchronises)");
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    if (policy_grad_prepare() != 0) {
+        (void) hipGetLastError();
+        return fail(CHUB_ERR_HIP, "chub_policy_grad_create: the gradient kernel's LDS limit could not be raised");
+    }
+    chub_policy_grad *g = new chub_policy_grad();
+    g->pol = pol;
+    g->max_rows = max_rows;
+    g->gp = gp;
+    g->max_blocks = grad_blocks(gp, max_rows);
+    g->d_wrm = g->d_part = nullptr;
+    g->d_part64 = nullptr;
+    pol->grads.push_back(g);
+    const size_t wrm = (size_t) std::max<int64_t>(gp.wrm_floats, 1) * sizeof(float), part = (size_t) g->max_blocks * (size_t) gp.part_floats * sizeof(float),
+                 p64 = (size_t) g->max_blocks * kGradPart64 * sizeof(double);
+    const bool ok = hipMalloc((void **) &g->d_wrm, wrm) == hipSuccess && hipMalloc((void **) &g->d_part, part) == hipSuccess &&
+                    hipMalloc((void **) &g->d_part64, p64) == hipSuccess && hipMemset(g->d_wrm, 0, wrm) == hipSuccess &&
+                    hipMemset(g->d_part, 0, part) == hipSuccess && hipMemset(g->d_part64, 0, p64) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) {
+        policy_grad_free(g);
+        (void) hipGetLastError();
+        return fail(CHUB_ERR_HIP, "chub_policy_grad_create: out of device memory");
+    }
+    *out = g;
+    return CHUB_OK;
+}
+
+int chub_policy_grad_destroy(chub_policy_grad *g) {
+    if (!g) return CHUB_OK;
+    if (g->pol->env->capturing)
+        return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_grad_destroy between chub_graph_begin and chub_graph_end (it synchronises and frees)");
+    policy_grad_free(g);
+    (void) hipGetLastError();
+    return CHUB_OK;
+}
+
+int chub_policy_grad_device(chub_policy_grad *g, const chub_policy_grad_in *in, const chub_policy_grad_out *out, void *stream) {
+    if (!g || !in || !out) return fail(CHUB_ERR_ARG, "null argument");
+    const chub_policy *pol = g->pol;
+    const bool piles = pol->spec.head == CHUB_PHEAD_PILES;
+    if (!in->d_features || !in->d_u || !in->d_adv || (piles && !in->d_pile_bits)) return fail(CHUB_ERR_ARG, "null argument");
+    if (in->R <= 0 || in->R > g->max_rows)
+        return fail(CHUB_ERR_ARG, "chub_policy_grad_device: R is 1 .. max_rows = " + std::to_string(g->max_rows));
+    if (in->n_rows < 1) return fail(CHUB_ERR_ARG, "chub_policy_grad_device: n_rows, the rows the arrays hold, is at least 1");
+    if (!in->d_rows && in->R > in->n_rows) return fail(CHUB_ERR_ARG, "chub_policy_grad_device: without d_rows the call reads rows 0 .. R - 1: R <= n_rows");
+    if (in->ld_features < pol->F) return fail(CHUB_ERR_ARG, "ld_features: at least the feature row's " + std::to_string(pol->F) + " floats");
+    if (in->loss != CHUB_PLOSS_COEF && in->loss != CHUB_PLOSS_PPO_CLIP) return fail(CHUB_ERR_ARG, "loss: CHUB_PLOSS_COEF or CHUB_PLOSS_PPO_CLIP");
+    if (in->loss == CHUB_PLOSS_PPO_CLIP) {
+        if (!(in->clip_eps > 0.0f && in->clip_eps < 1.0f)) return fail(CHUB_ERR_ARG, "clip_eps: inside (0, 1) under CHUB_PLOSS_PPO_CLIP");
+        if (!in->d_logp_old) return fail(CHUB_ERR_ARG, "null argument");
+    }
+    if (!std::isfinite(in->ent_coef)) return fail(CHUB_ERR_ARG, "ent_coef is not finite");
+    if (!piles && in->d_set_bits) return fail(CHUB_ERR_ARG, "chub_policy_grad_device: under CHUB_PHEAD_LOADS the log-probability has no pile terms: d_set_bits must be NULL");
+    if (!pol->explore) return fail(CHUB_ERR_ARG, "chub_policy_grad_device: chub_policy_set_exploration first (the log-probability needs log_std)");
+    HIP_TRY(hipSetDevice(pol->env->device));
+    (void) hipGetLastError();
+    const GradPlan &gp = g->gp;
+    const int nl = pol->spec.n_layers;
+    PolicyGradArgs a;
+    memset(&a, 0, sizeof a);
+    GradMergeArgs m;
+    memset(&m, 0, sizeof m);
+    bool backward = out->d_glog_std != nullptr;
+    for (int l = 0; l < nl; l++) backward |= out->d_gW[l] != nullptr || out->d_gb[l] != nullptr;
+    a.R = in->R;
+    a.rows_total = in->n_rows;
+    a.rows = in->d_rows;
+    a.features = in->d_features;
+    a.ld = in->ld_features;
+    a.pile_bits = (const uint32_t *) in->d_pile_bits;
+    a.set_bits = (const uint32_t *) in->d_set_bits;
+    a.u = in->d_u;
+    a.logp_old = in->d_logp_old;
+    a.adv = in->d_adv;
+    a.adv_stats = in->d_adv_stats;
+    a.mean = pol->pa.mean;
+    a.inv_std = pol->pa.inv_std;
+    a.log_std = pol->d_log_std;
+    a.logp_new = out->d_logp_new;
+    a.entropy = out->d_entropy;
+    a.part = g->d_part;
+    a.part64 = g->d_part64;
+    a.clip = pol->spec.clip;
+    a.clip_eps = in->clip_eps;
+    a.ent_coef = in->ent_coef;
+    a.n_layers = nl;
+    a.F = pol->F;
+    a.x_rows = gp.x_rows;
+    a.d_row0[0] = gp.d_row0[0];
+    a.d_row0[1] = gp.d_row0[1];
+    a.s_row0 = gp.s_row0;
+    a.hidden_act = pol->spec.hidden_act;
+    a.normalize = pol->spec.normalize;
+    a.head = pol->spec.head;
+    a.S = pol->pa.S;
+    a.A = pol->A_out;
+    a.W = pol->pa.W;
+    a.G = pol->G;
+    a.loss = in->loss;
+    a.backward = backward ? 1 : 0;
+    a.n_pairs = gp.n_pairs;
+    a.part_floats = gp.part_floats;
+    a.bias_floats = gp.bias_floats;
+    for (int l = 0; l < nl; l++) {
+        GradLayer &L = a.layer[l];
+        L.w = pol->d_w[l];
+        L.b = pol->d_b[l];
+        L.wrm = l ? g->d_wrm + gp.wrm_off[l] : nullptr;
+        L.k_pad = pol->pa.layer[l].k_pad;
+        L.in = gp.in[l];
+        L.out = pol->spec.width[l];
+        L.ot = gp.ot[l];
+        L.it = gp.it[l];
+        L.h_row0 = gp.h_row0[l];
+        L.pair0 = gp.pair0[l];
+        L.bias0 = gp.bias0[l];
+        m.gW[l] = out->d_gW[l];
+        m.gb[l] = out->d_gb[l];
+        m.in[l] = gp.in[l];
+        m.out[l] = pol->spec.width[l];
+        m.it[l] = gp.it[l];
+        m.pair0[l] = gp.pair0[l];
+        m.bias0[l] = gp.bias0[l];
+        m.param0[l] = gp.param0[l];
+    }
+    m.param0[nl] = gp.param0[nl];
+    m.part = g->d_part;
+    m.part64 = g->d_part64;
+    m.glog_std = out->d_glog_std;
+    m.stats = out->d_stats;
+    m.R = in->R;
+    m.n_layers = nl;
+    m.blocks = grad_blocks(gp, in->R);
+    m.part_floats = gp.part_floats;
+    m.bias_base = gp.n_pairs * 1024;
+    m.G = pol->G;
+    m.backward = a.backward;
+    launch_policy_grad(a, m, m.blocks, gp.lds_rows, gp.in_registers != 0, (hipStream_t) stream);
     HIP_TRY(hipGetLastError());
     return CHUB_OK;
 }

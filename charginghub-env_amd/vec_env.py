@@ -446,6 +446,130 @@ class DevicePopulation(object):
             pass
 
 
+class DevicePolicyGrad(object):
+    """Actor gradients on the device (chub_policy_grad_*, include/chub.h "actor gradients on the device"): made by
+    VecChargingHub.make_policy_grad from a DevicePolicy that has set_exploration.  grad_device differentiates a surrogate loss over rows of
+    a collected rollout through the policy's LIVE weights, normaliser and log_std and writes the gradient in the trainer's layout;
+    evaluate_device is the forward alone.  A handful of launches on the caller's stream, the same bits every call, no autograd."""
+
+    def __init__(self, env, policy, max_rows):
+        self._env = env
+        self._lib = env._lib
+        self.policy = policy
+        self.max_rows = int(max_rows)
+        self.layer_shapes = list(policy.layer_shapes)
+        self.n_params = sum(o * (i + 1) for o, i in self.layer_shapes)
+        h = C.c_void_p()
+        check(self._lib.chub_policy_grad_create(policy._p, self.max_rows, C.byref(h)))
+        self._g = h
+
+    def plan(self, R=None):
+        """chub_policy_grad_plan for a call of R rows (default max_rows) -> dict(n_params, workspace_bytes, workgroups, lds_rows, lds_bytes,
+        in_registers); host arithmetic only"""
+        out = _lib.ChubPolicyGradPlanOut()
+        check(self._lib.chub_policy_grad_plan(C.byref(self._env.cfg), C.byref(self.policy.spec), int(self.max_rows if R is None else R), C.byref(out)))
+        return {name: int(getattr(out, name)) for name, _ in out._fields_}
+
+    def grad_device(self, R, n_rows, d_features, d_u, d_adv, d_pile_bits=0, d_set_bits=0, d_logp_old=0, d_rows=0, d_adv_stats=0, ld_features=None,
+                    loss="ppo_clip", clip_eps=0.2, ent_coef=0.0, d_gW=None, d_gb=None, d_glog_std=0, d_logp_new=0, d_entropy=0, d_stats=0, stream=0):
+        """one call on `stream` (chub_policy_grad_device).  The per-row arrays hold n_rows rows: d_features [n_rows, F] raw (row stride
+        ld_features floats, default F), d_pile_bits / d_set_bits [n_rows, bit_words] u64, d_u [n_rows, G], d_logp_old, d_adv [n_rows];
+        d_rows [R] int64 picks the rows (0: rows 0 .. R - 1); d_adv_stats [3] f64 normalises the advantage.  Outputs, each optional:
+        d_gW[l] [out, in] / d_gb[l] [out] (device addresses per layer, the trainer's layout), d_glog_std [G], d_logp_new / d_entropy [R],
+        d_stats [6] f64.  With no gradient output the call is the forward alone.  No synchronisation; recordable into a graph."""
+        a = _lib.ChubPolicyGradIn(int(R), int(n_rows), d_rows or None, d_features or None,
+                                  self.policy.n_features if ld_features is None else int(ld_features), d_pile_bits or None, d_set_bits or None,
+                                  d_u or None, d_logp_old or None, d_adv or None, d_adv_stats or None, _lib.policy_loss(loss), float(clip_eps),
+                                  float(ent_coef), 0)
+        o = _lib.ChubPolicyGradOut()
+        for l in range(len(self.layer_shapes)):
+            o.d_gW[l] = (d_gW[l] or None) if d_gW else None
+            o.d_gb[l] = (d_gb[l] or None) if d_gb else None
+        o.d_glog_std, o.d_logp_new, o.d_entropy, o.d_stats = d_glog_std or None, d_logp_new or None, d_entropy or None, d_stats or None
+        check(self._lib.chub_policy_grad_device(self._g, C.byref(a), C.byref(o), stream or None))
+
+    def evaluate_device(self, R, n_rows, d_features, d_u, d_logp_new, d_entropy=0, d_pile_bits=0, d_set_bits=0, d_rows=0, ld_features=None, stream=0):
+        """the forward alone ("evaluate actions"): the current policy's log-probability of the recorded actions into d_logp_new [R] and the
+        entropy into d_entropy [R].  The advantage plays no part: d_u stands in for it"""
+        self.grad_device(R, n_rows, d_features, d_u, d_u, d_pile_bits, d_set_bits, 0, d_rows, 0, ld_features, "coef", 0.0, 0.0, None, None, 0,
+                         d_logp_new, d_entropy, 0, stream)
+
+    def grad(self, features, u, adv, pile_bits=None, set_bits=None, logp_old=None, rows=None, adv_stats=None, loss="ppo_clip", clip_eps=0.2,
+             ent_coef=0.0, backward=True):
+        """grad_device through host memory (the convenience form: it allocates, copies and synchronises): numpy arrays in, ->
+        dict(grads=[(gW, gb), ..], g_log_std [G], logp_new [R], entropy [R], stats [6]); backward=False: the forward alone, grads and
+        g_log_std are None"""
+        e, pol = self._env, self.policy
+        F, G = pol.n_features, pol.n_gaussians
+        features = np.ascontiguousarray(features, dtype=np.float32).reshape(-1, F)
+        n_rows = len(features)
+        ins = [("features", features), ("u", np.ascontiguousarray(u, dtype=np.float32).reshape(n_rows, G)),
+               ("adv", np.ascontiguousarray(adv, dtype=np.float32).reshape(n_rows))]
+        if pile_bits is not None:
+            ins.append(("pile_bits", np.ascontiguousarray(pile_bits, dtype=np.uint64).reshape(n_rows, -1)))
+        if set_bits is not None:
+            ins.append(("set_bits", np.ascontiguousarray(set_bits, dtype=np.uint64).reshape(n_rows, -1)))
+        if logp_old is not None:
+            ins.append(("logp_old", np.ascontiguousarray(logp_old, dtype=np.float32).reshape(n_rows)))
+        if rows is not None:
+            ins.append(("rows", np.ascontiguousarray(rows, dtype=np.int64).ravel()))
+        if adv_stats is not None:
+            ins.append(("adv_stats", np.ascontiguousarray(adv_stats, dtype=np.float64).reshape(3)))
+        R = n_rows if rows is None else len(dict(ins)["rows"])
+        outs = [("grads", np.zeros(self.n_params + G, dtype=np.float32)), ("logp_new", np.zeros(R, dtype=np.float32)),
+                ("entropy", np.zeros(R, dtype=np.float32)), ("stats", np.zeros(6, dtype=np.float64))]
+        at, off = 0, {}
+        for name, arr in ins + outs:
+            off[name] = at
+            at += (arr.nbytes + 15) & ~15
+        d = C.c_void_p()
+        check(self._lib.chub_malloc_device(e._device, max(at, 16), C.byref(d)))
+        try:
+            for name, arr in ins:
+                if arr.nbytes:
+                    check(self._lib.chub_copy_to_device(e._device, C.c_void_p(d.value + off[name]), _ptr(arr), arr.nbytes, None))
+            d_gW, d_gb, p = [], [], d.value + off["grads"]
+            for o, i in self.layer_shapes:
+                d_gW.append(p)
+                d_gb.append(p + 4 * o * i)
+                p += 4 * o * (i + 1)
+            addr = lambda name: d.value + off[name] if name in off else 0
+            check(self._lib.chub_sync(e._h))
+            self.grad_device(R, n_rows, addr("features"), addr("u"), addr("adv"), addr("pile_bits"), addr("set_bits"), addr("logp_old"), addr("rows"),
+                             addr("adv_stats"), None, loss, clip_eps, ent_coef, d_gW if backward else None, d_gb if backward else None,
+                             p if backward else 0, addr("logp_new"), addr("entropy"), addr("stats"))
+            check(self._lib.chub_sync(e._h))
+            for name, arr in outs:
+                check(self._lib.chub_copy_to_host(e._device, _ptr(arr), C.c_void_p(d.value + off[name]), arr.nbytes, None))
+        finally:
+            self._lib.chub_free_device(e._device, d)
+        res = dict(outs)
+        flat, grads, p = res.pop("grads"), [], 0
+        for o, i in self.layer_shapes:
+            grads.append((flat[p:p + o * i].reshape(o, i).copy(), flat[p + o * i:p + o * (i + 1)].copy()))
+            p += o * (i + 1)
+        res["grads"] = grads if backward else None
+        res["g_log_std"] = flat[p:p + G].copy() if backward else None
+        return res
+
+    def evaluate(self, features, u, pile_bits=None, set_bits=None, rows=None):
+        """evaluate_device through host memory -> (logp_new [R], entropy [R])"""
+        r = self.grad(features, u, np.zeros(len(np.asarray(u).reshape(-1, self.policy.n_gaussians)), dtype=np.float32), pile_bits, set_bits, None, rows,
+                      None, "coef", 0.0, 0.0, backward=False)
+        return r["logp_new"], r["entropy"]
+
+    def close(self):
+        if getattr(self, "_g", None) and getattr(self.policy, "_p", None) and getattr(self._env, "_h", None):
+            check(self._lib.chub_policy_grad_destroy(self._g))
+        self._g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DeviceMoments(object):
     """Running count, mean and M2 per feature on the device (chub_moments_*, include/chub.h "running feature statistics"): made by
     VecChargingHub.make_moments.  The state is [1 + 2 F] float64 in device memory (n | mean | M2); update_device adds a batch of rows in
@@ -1076,6 +1200,13 @@ class VecChargingHub(object):
         if policy._env is not self:
             raise ValueError("make_population: the policy was made for another handle")
         return DevicePopulation(self, policy, P, key)
+
+    def make_policy_grad(self, policy, max_rows):
+        """actor gradients for `policy` (a DevicePolicy of this handle with set_exploration) over calls of up to max_rows rows ->
+        DevicePolicyGrad (chub_policy_grad_create); refused where the policy's images do not fit the gradient launch's LDS"""
+        if policy._env is not self:
+            raise ValueError("make_policy_grad: the policy was made for another handle")
+        return DevicePolicyGrad(self, policy, max_rows)
 
     def next_tick(self):
         """the Philox tick of this handle's next reset or step (chub_next_tick): the tick a sampled policy call made now draws its noise

@@ -718,6 +718,8 @@ class TorchHubVecEnv(object):
             ro["reward"], ro["done"] = ro["packed"][:, :, D], ro["packed"][:, :, D + 1]
             if logp_piles is not None:
                 ro["set_bits"] = torch.zeros((T, N, W), dtype=torch.int64, device=self.device)
+        self._rollout_policy = getattr(self, "_rollout_policy", {})
+        self._rollout_policy[id(ro)] = policy  # (policy_gradient / evaluate_actions find the rollout's actor here)
         ro["obs0"].copy_(self._cur_obs)
         extra = {} if logp_piles is None else dict(logp_piles=logp_piles, d_set_bits=ro["set_bits"].data_ptr())
         policy.collect(T, ro["obs0"].data_ptr(), ro["packed"].data_ptr(), ro["bits"].data_ptr(), ro["tail"].data_ptr(), ro["u"].data_ptr(),
@@ -760,6 +762,67 @@ class TorchHubVecEnv(object):
                             d_final_values=0 if final_values is None else final_values.data_ptr(), gamma=gamma, lam=lam,
                             d_stats=st.data_ptr() if stats else 0, stream=self._stream())
         return (adv, ret, st) if stats else (adv, ret)
+
+    # ---- actor gradients on the device (chub_policy_grad_*): the policy-gradient step with no autograd for the actor
+    def _policy_grad_call(self, rollout, adv, rows, loss, clip_eps, ent_coef, adv_stats, backward):
+        torch = self.torch
+        policy = getattr(self, "_rollout_policy", {}).get(id(rollout))
+        if policy is None:
+            raise ValueError("rollout: a dict returned by this adapter's collect()")
+        feats = rollout["features"]
+        n_rows = int(feats.shape[0]) * int(feats.shape[1])
+        if rows is not None and not (self._on_device(rows) and rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_contiguous()):
+            raise AssertionError("rows must be a contiguous 1-d int64 tensor on %s" % (self.device,))
+        R = n_rows if rows is None else int(rows.numel())
+        if adv is not None and not (self._on_device(adv) and adv.dtype == torch.float32 and adv.is_contiguous() and adv.numel() == n_rows):
+            raise AssertionError("adv must be a contiguous float32 tensor on %s with one entry per (step, env)" % (self.device,))
+        if adv_stats is not None and not (self._on_device(adv_stats) and adv_stats.dtype == torch.float64 and adv_stats.is_contiguous()
+                                          and adv_stats.numel() == 3):
+            raise AssertionError("adv_stats must be a contiguous float64 tensor on %s of 3 entries (advantages(..., stats=True))" % (self.device,))
+        cache = getattr(self, "_pgrad", None)
+        if cache is None:
+            cache = self._pgrad = {}
+        ent = cache.get(id(policy))
+        if ent is None or ent["grad"].max_rows < R:
+            if ent is not None:
+                ent["grad"].close()
+            g = self.vec.make_policy_grad(policy, max(R, n_rows))
+            f32 = dict(dtype=torch.float32, device=self.device)
+            ent = cache[id(policy)] = {"grad": g, "grads": [(torch.zeros((o, i), **f32), torch.zeros((o,), **f32)) for o, i in g.layer_shapes],
+                                       "g_log_std": torch.zeros((policy.n_gaussians,), **f32),
+                                       "stats": torch.zeros((6,), dtype=torch.float64, device=self.device), "rows": {}}
+        out = ent["rows"].get(R)
+        if out is None:
+            out = ent["rows"][R] = (torch.zeros((R,), dtype=torch.float32, device=self.device), torch.zeros((R,), dtype=torch.float32, device=self.device))
+        piles = policy.spec.head == _lib.PHEAD["piles"]
+        sets = rollout.get("set_bits") if piles else None
+        ent["grad"].grad_device(R, n_rows, feats.data_ptr(), rollout["u"].data_ptr(), (adv if adv is not None else rollout["logp"]).data_ptr(),
+                                d_pile_bits=rollout["bits"].data_ptr() if piles else 0, d_set_bits=0 if sets is None else sets.data_ptr(),
+                                d_logp_old=rollout["logp"].data_ptr(), d_rows=0 if rows is None else rows.data_ptr(),
+                                d_adv_stats=0 if adv_stats is None else adv_stats.data_ptr(), loss=loss, clip_eps=clip_eps, ent_coef=ent_coef,
+                                d_gW=[gW.data_ptr() for gW, _ in ent["grads"]] if backward else None,
+                                d_gb=[gb.data_ptr() for _, gb in ent["grads"]] if backward else None,
+                                d_glog_std=ent["g_log_std"].data_ptr() if backward else 0, d_logp_new=out[0].data_ptr(), d_entropy=out[1].data_ptr(),
+                                d_stats=ent["stats"].data_ptr() if backward else 0, stream=self._stream())
+        return ent, out
+
+    def policy_gradient(self, rollout, adv, rows=None, loss="ppo_clip", clip_eps=0.2, ent_coef=0.0, adv_stats=None):
+        """The actor's gradient of a surrogate loss over a ``collect`` rollout, on torch's current stream with no autograd
+        (chub_policy_grad_device): the CURRENT weights, normaliser and log_std of the rollout's policy, the recorded actions, ``logp`` and
+        sets of `rollout`, adv [T, N] float32 CUDA (``advantages``), rows: an int64 CUDA tensor of flat (step, env) indices t * N + n (a
+        minibatch; None: every row), loss "ppo_clip" or "coef", adv_stats: the float64 [3] tensor of ``advantages(..., stats=True)`` to
+        normalise the advantage with.  Returns (grads, g_log_std, stats): grads a list of (gW, gb) in ``load_policy``'s layout, g_log_std
+        [G], stats float64 [6] (rows, sum of loss terms, sum of entropies, sum of logp_old - logp_new, rows clipped away, sum of ratios) --
+        CUDA tensors the next call with the same policy overwrites.  An optimiser step on them and ``policy.set_weights_device`` /
+        ``set_log_std_device`` close the loop."""
+        ent, _ = self._policy_grad_call(rollout, adv, rows, loss, clip_eps, ent_coef, adv_stats, True)
+        return ent["grads"], ent["g_log_std"], ent["stats"]
+
+    def evaluate_actions(self, rollout, rows=None):
+        """(logp_new, entropy) float32 [R] CUDA: the rollout's policy as it is NOW on the recorded actions of `rows` (None: every row, flat
+        [T * N]), the forward alone; the next call with the same R overwrites them"""
+        _, out = self._policy_grad_call(rollout, None, rows, "coef", 0.0, 0.0, None, False)
+        return out
 
     # ---- a normaliser that follows the rollouts (chub_moments_*, chub_policy_normalizer_from_moments_device)
     def update_normalizer(self, policy, rollout, moments=None, eps=1e-8, mask=None):

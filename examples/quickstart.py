@@ -248,6 +248,50 @@ def es_generation(n=4096, members=64, sigma=0.05, lr=0.02, generation=0):
     env.close()
 
 
+def ppo_on_device_gradients(n=4096, steps=64, minibatches=4):
+    import charginghub_env_amd as chub
+
+    if torch is None:
+        print("8. skipped: torch is not installed")
+        return
+    env = chub.TorchHubVecEnv(n, seed=0, autoreset="per_env", **HUB)
+    D, A = env.obs_dim, env.act_dim
+    net = torch.nn.Sequential(torch.nn.Linear(D, 64), torch.nn.Tanh(), torch.nn.Linear(64, A)).to("cuda")   # holds the weights; never run
+    linears = [m for m in net if isinstance(m, torch.nn.Linear)]
+    critic = torch.nn.Sequential(torch.nn.Linear(D, 64), torch.nn.Tanh(), torch.nn.Linear(64, 1)).to("cuda")
+    log_std = torch.full((2,), -0.5, device="cuda")
+    params = [p for m in linears for p in (m.weight, m.bias)] + [log_std]
+    opt = torch.optim.Adam(params, lr=3e-4)                    # the optimiser stays with the trainer; the actor needs no autograd
+    policy = env.load_policy(net)
+    policy.set_exploration(key=7, log_std=log_std.cpu().numpy())
+    stream = torch.cuda.current_stream().cuda_stream
+    env.reset()
+    ro = env.collect(policy, steps, logp_piles="decidable")
+    with torch.no_grad():
+        values = torch.cat([critic(ro["obs0"]).reshape(1, n), critic(ro["packed"][:, :, :D]).reshape(steps, n)]).contiguous()
+        final = critic(env.last_obs).reshape(n).contiguous()
+    adv, ret, adv_stats = env.advantages(ro, values, final, gamma=0.99, lam=0.95, stats=True)
+    perm = torch.randperm(steps * n, device="cuda")
+    clipped = 0.0
+    for rows in perm.chunk(minibatches):                     # a minibatch is a list of flat (step, env) indices into the rollout
+        # the CURRENT weights' log-probabilities of the recorded actions, the clipped surrogate and its gradient: a handful of launches
+        grads, g_log_std, stats = env.policy_gradient(ro, adv, rows=rows.contiguous(), loss="ppo_clip", clip_eps=0.2, ent_coef=0.01,
+                                                      adv_stats=adv_stats)
+        for m, (gW, gb) in zip(linears, grads):                # the returned tensors ARE the gradients, in nn.Linear's layout
+            m.weight.grad, m.bias.grad = gW, gb
+        log_std.grad = g_log_std
+        opt.step()
+        for l, m in enumerate(linears):                        # the stepped weights go straight back: the next minibatch differentiates them
+            policy.set_weights_device(l, m.weight.data_ptr(), m.bias.data_ptr(), stream)
+        policy.set_log_std_device(log_std.data_ptr(), stream)
+        clipped = clipped + stats[4] / stats[0]
+    logp_new, entropy = env.evaluate_actions(ro)              # the forward alone, under the weights as they are now
+    kl = float((ro["logp"].reshape(-1) - logp_new).mean())
+    print("8. %d envs x %d steps, one PPO epoch in %d minibatches with the actor's gradient from the device: clipped away %.3f of the rows, "
+          "approximate KL %.5f, mean entropy %.2f" % (n, steps, minibatches, float(clipped) / minibatches, kl, float(entropy.mean())))
+    env.close()
+
+
 if __name__ == "__main__":
     single_env()
     batched_host()
@@ -256,3 +300,4 @@ if __name__ == "__main__":
     on_policy_data()
     ppo_iteration()
     es_generation()
+    ppo_on_device_gradients()

@@ -1085,6 +1085,92 @@ int chub_population_run_steps(chub_env *env, chub_population *pop, int mode, flo
 int chub_population_es_gradient_device(chub_population *pop, const float *d_util /* [P] */, uint32_t generation, float *const *d_gW,
                                        float *const *d_gb, void *stream);
 
+/* ---- actor gradients on the device: log-probabilities, PPO-clip loss, backward pass ----------------------------------------------------
+ * The step of a policy-gradient update that used to leave the library: the CURRENT policy's log-probability of recorded actions and the
+ * gradient of a surrogate loss with respect to the actor's weights and log_std, through the actor's own chain.  A chub_policy_grad is
+ * bound to a chub_policy (its spec, live weights, normaliser and log_std); chub_policy_collect_set + chub_rollout_gae_device leave
+ * everything a call reads in device memory.
+ *   Rows.  A call works on R rows; a row is one (step, env) pair: R = T N over a rollout's [T][N][...] arrays taken flat.  d_rows [R]
+ *     int64 (NULL: rows 0 .. R - 1) indexes EVERY per-row array; the arrays hold n_rows rows, and an index outside 0 .. n_rows - 1 (device
+ *     memory: the host cannot check it) is skipped: it adds to nothing, stats[0] does not count it, its logp_new / entropy are 0.  A
+ *     repeated index counts as often as it is named.  Per row: d_features [.][F] the RAW feature row with row stride ld_features >= F;
+ *     d_pile_bits [.][W] (PILES); d_set_bits [.][W] or NULL for every pile (NULL under LOADS); d_u [.][G]; d_logp_old [.]; d_adv [.].
+ *   Forward.  x = clamp((feature - mean) * inv_std) with the policy's CURRENT normaliser exactly as the actor does (f32 subtraction, f32
+ *     product, clamp); the layers under the actor's numerics contract (every product rounded once, f32 accumulation from the bias in
+ *     ascending input order, the device library's tanhf): the pre-squash outputs z are the bits the actor's own launch forms.
+ *   logp_r: over the piles b of the set  -softplus(on_b ? -z_b : z_b)  with on_b the recorded bit, plus over the Gaussian outputs
+ *     -0.5 eps_i^2 - log_std_i - 0.5 ln 2 pi  with eps_i = (u_i - z_i) / expf(log_std_i) in f32.
+ *   H_r: over the same piles  softplus(z_b) - z_b sigmoid(z_b),  plus over the Gaussian outputs  0.5 + log_std_i + 0.5 ln 2 pi.
+ *   Advantage.  A_r = adv_r; with d_adv_stats [3] f64 (count, sum, sum of squares: chub_rollout_gae_device's d_stats)
+ *     A_r = (adv_r - m32) * s32, m = sum / count, s = 1 / sqrt(max(sumsq / count - m m, 0) + 1e-8), every f64 operation rounded once, m and
+ *     s each rounded once to f32, the subtraction and the product each rounded once.
+ *   Loss.  CHUB_PLOSS_COEF:      L = (1 / R) sum_r (-A_r logp_r - ent_coef H_r); d_logp_old is not read (it may be NULL).
+ *          CHUB_PLOSS_PPO_CLIP:  ratio_r = expf(logp_r - logp_old_r),
+ *                                L = (1 / R) sum_r (-min(ratio A, clamp(ratio, 1 - eps, 1 + eps) A) - ent_coef H_r);
+ *              the row's policy term has a gradient iff (A >= 0 and ratio < 1 + eps) or (A < 0 and ratio > 1 - eps) (1 -+ eps rounded to
+ *              f32), and there R dL/dlogp_r = -A ratio; elsewhere 0.  A ratio exactly on a bound is not defined beyond this predicate.
+ *   Gradients.  dlogp/dz_b = on_b - sigmoid(z_b) and dH/dz_b = -z_b sigmoid(z_b) (1 - sigmoid(z_b)) for piles of the set, 0 for the others;
+ *     dlogp/dz_i = eps_i / expf(log_std_i); dlogp/dlog_std_i = eps_i^2 - 1; dH/dlog_std_i = 1.  Hidden layers: tanh passes delta (1 - h^2),
+ *     relu delta [h > 0].  The normaliser is a constant.  The factor 1 / R is applied ONCE, to the summed gradient, in f64 (below).
+ *   Outputs, each optional: d_gW[l] [out][in] and d_gb[l] [out] in the TRAINER's layout (chub_policy_set_weights_device's), d_glog_std [G];
+ *     d_logp_new [R] and d_entropy [R], written at position r of the call (not at d_rows[r]); d_stats [6] f64: rows counted, sum of the
+ *     rows' loss terms, sum of entropies, sum of (logp_old - logp_new), rows whose policy term was clipped away, sum of ratios (the last
+ *     three are 0 under COEF).  With every gradient output NULL the call is the forward alone ("evaluate actions"): no backward launch.
+ *   Numerics of the gradient.  Products are rounded once and accumulated in f32 on the f32-input MFMA over the rows a workgroup walks
+ *     (32 rows per chain link, a workgroup's tiles in ascending order); the workgroups' partial sums are added in f64 in workgroup order,
+ *     divided by R in f64 and rounded once to f32.  The log_std sums and the stats are f64 from the row up.  No atomics: two calls on
+ *     the same inputs give identical bits, and the order is a function of (R, spec) alone.
+ *   Launches of one call, on the caller's stream: a small launch that rebuilds zero-padded row-major copies of layers 1.. from the
+ *     policy's LIVE device weights (they cannot go stale after chub_policy_set_weights_device, or inside a graph), the gradient launch,
+ *     the merge.  No allocation, no synchronisation, no tick; recordable.  The copies and the partials belong to the object: calls on
+ *     one object must be ordered against each other.
+ *   chub_policy_grad_plan: host-only, no device: the parameter count (sum of out * (in + 1)), the workgroups of a call of R rows
+ *     (ceil(R / 32) rounded up to 8, at most 512, fewer where the partials would pass 256 MiB), the LDS rows and bytes, whether the
+ *     dW tiles stay in registers (at most 16 tiles of 32 x 32 over all layers) and the workspace create allocates for max_rows = R --
+ *     or the refusal create would give.  The fit rule: LDS rows = F rounded up to 32 + every hidden width rounded up to 32 + twice the
+ *     widest layer output rounded up to 32 + 16, each row 33 floats (one of padding), at most 160 KiB.  13 -> 64 -> 64 -> 47 takes 304
+ *     rows, 64 -> 256 -> 256 -> 47 takes 1104 -- by THIS rule; a gradient object also needs chub_policy_set_exploration, whose own rule
+ *     (the policy's two images and 4 more rows within 512) refuses 64 -> 256 -> 256: for that actor the plan succeeds and no object
+ *     can be made.  64 -> 256 -> 224 -> 47 (1072 rows) is the widest of that shape that samples.  A policy that does not fit still acts
+ *     and samples.
+ *   chub_policy_grad_create allocates outside the arena: chub_state_size and snapshots are unchanged.  chub_policy_destroy / chub_destroy
+ *     destroy a policy's grad objects first.
+ * Refusals, all with a message and before any device work.  CHUB_ERR_ARG: null g / in / out, null d_features, d_u, d_adv, d_pile_bits
+ *     (PILES) or d_logp_old (PPO_CLIP); R <= 0, R > max_rows, n_rows < 1, ld_features < F; an unknown loss; eps outside (0, 1) under
+ *     PPO_CLIP; ent_coef not finite; d_set_bits under LOADS; a policy without chub_policy_set_exploration (no log_std); max_rows < 1.
+ *     CHUB_ERR_UNSUPPORTED: the fit rule; create / destroy between chub_graph_begin and chub_graph_end.
+ * Out of scope: a value loss or a critic on the device (the critic trains on `ret`, its own small regression, with the trainer), an
+ *     optimiser (Adam stays with the trainer or host), gradients with respect to the normaliser or through the tanh squash, bf16 weights,
+ *     populations, the multi-GPU hosts (an all-reduce of the returned gradients is the trainer's), COMPAT rollouts. */
+enum { CHUB_PLOSS_COEF = 0, CHUB_PLOSS_PPO_CLIP, CHUB_PLOSS_COUNT };
+typedef struct chub_policy_grad chub_policy_grad;
+typedef struct chub_policy_grad_plan_out {
+    int64_t n_params;             /* sum over layers of out * (in + 1); log_std's G come on top */
+    int64_t workspace_bytes;      /* what chub_policy_grad_create(max_rows = R) allocates */
+    int32_t workgroups, lds_rows, lds_bytes, in_registers;
+} chub_policy_grad_plan_out;
+typedef struct chub_policy_grad_in {
+    int64_t R, n_rows;            /* rows of this call; rows the per-row arrays hold */
+    const int64_t *d_rows;        /* [R] or NULL */
+    const float *d_features;      /* [n_rows][F], row stride ld_features */
+    int64_t ld_features;
+    const uint64_t *d_pile_bits, *d_set_bits;  /* [n_rows][W] */
+    const float *d_u, *d_logp_old, *d_adv;     /* [n_rows][G], [n_rows], [n_rows] */
+    const double *d_adv_stats;    /* [3] or NULL */
+    int32_t loss;                 /* CHUB_PLOSS_* */
+    float clip_eps, ent_coef;
+    int32_t pad_;
+} chub_policy_grad_in;
+typedef struct chub_policy_grad_out {
+    float *d_gW[4], *d_gb[4];
+    float *d_glog_std, *d_logp_new, *d_entropy;
+    double *d_stats;
+} chub_policy_grad_out;
+int chub_policy_grad_plan(const chub_config *cfg, const chub_policy_spec *spec, int64_t R, chub_policy_grad_plan_out *out);
+int chub_policy_grad_create(chub_policy *pol, int64_t max_rows, chub_policy_grad **out);
+int chub_policy_grad_destroy(chub_policy_grad *g);
+int chub_policy_grad_device(chub_policy_grad *g, const chub_policy_grad_in *in, const chub_policy_grad_out *out, void *stream);
+
 /* The FCEV waiting list is unbounded as in the reference (HYD:264-265): the entries a list that still gets served can
  * hold are kept one by one, and once no prefix of it fits into 15 minutes any more (HYD:270-276: nobody is served again
  * until reset and the list only grows) its entries are folded into their count and running sums, which is all the

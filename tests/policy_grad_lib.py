@@ -1,0 +1,485 @@
+"""The numpy f64 restatement of include/chub.h's "actor gradients on the device", and nothing else defines the expected values of
+tests/test_policy_grad_cpu.py and tests/test_gpu_policy_grad.py.  It is evaluated AT the f32 inputs: the normalisation, the advantage's
+normalisation and the bounds 1 -+ eps of the activity predicate are formed in f32 as the header says, everything else in f64.
+
+The bar is derived, not chosen.  policy_lib's forward bound gives err_h per hidden image and err_z; it is carried
+  - into logp (policy_sample_lib's per-term function errors and the chain's gamma), into ratio = exp(logp - logp_old) and the coefficient
+    c = -A ratio;
+  - into the head's delta z (sigmoid within bound_p's terms, every product rounded once);
+  - back through every layer: delta_in = (W^T delta) act'(h) is a chain of `out` products, gamma(out + 2) over the values held, the
+    incoming error through |W|, tanh's factor 1 - h^2 off by 2 |h| err_h + err_h^2, relu's mask undecided where |z| <= err_z;
+  - into dW = sum over rows of delta h: the input errors err_d (|h| + err_h) + |d| err_h, plus the accumulation: one rounding per product,
+    32 rows per MFMA chain and ceil(tiles / workgroups) tiles per workgroup in f32, one rounding of the f64 merge -- gamma(32 tpw + 3)
+    times the f64 matmul of absolute values |d|^T |h|.  All of it over R."""
+import ctypes as C
+
+import numpy as np
+
+import policy_lib as pl
+import policy_sample_lib as ps
+
+F32 = np.float32
+U, ULP, TINY = pl.U, ps.ULP, pl.TINY
+HALF_LN_2PI = ps.HALF_LN_2PI
+
+
+def sigmoid(z):
+    with np.errstate(over="ignore"):
+        return 1.0 / (1.0 + np.exp(-z))
+
+
+def adv_norm(adv, stats):
+    """(adv - m32) * s32, m and s from (count, sum, sumsq) in f64 operation by operation, each rounded once to f32"""
+    cnt, s1, s2 = (np.float64(v) for v in stats)
+    m = s1 / cnt
+    var = s2 / cnt - m * m
+    var = var if var > 0.0 else np.float64(0.0)
+    s = np.float64(1.0) / np.sqrt(var + np.float64(1e-8))
+    return ((np.asarray(adv, dtype=F32) - F32(m)).astype(F32) * F32(s)).astype(F32)
+
+
+class Case(object):
+    """everything one call reads.  layers [(W, b)] f32, log_std [G] f32, norm None or (mean, inv_std, clip), act "tanh" / "relu", head
+    "piles" / "loads", S piles; per-row arrays over n_rows rows: features [., F] f32, on bool [., S], sets bool [., S] or None, u [., G],
+    logp_old, adv f32; rows int64 [R] or None; adv_stats [3] f64 or None; loss "coef" / "ppo_clip"; clip_eps, ent_coef"""
+
+    def __init__(self, **kw):
+        self.norm = self.sets = self.rows = self.adv_stats = None
+        self.loss, self.clip_eps, self.ent_coef, self.name, self.inputs = "ppo_clip", 0.2, 0.0, "", ("obs",)
+        self.__dict__.update(kw)
+
+    def copy(self, **kw):
+        c = Case(**self.__dict__)
+        c.__dict__.update(kw)
+        return c
+
+    @property
+    def R(self):
+        return len(self.features) if self.rows is None else len(self.rows)
+
+    @property
+    def widths(self):
+        return [W.shape[0] for W, _ in self.layers]
+
+
+def restate(c, tpw=1, mistake=None):
+    """-> dict: gW, gb (lists, f64), gls [G], logp, ent [R], stats [6], coef [R], ratio [R], active [R], and the bars bar_W, bar_b,
+    bar_ls, bar_logp, bar_ent, bar_stats.  tpw: tiles of 32 rows a workgroup walks at most.  mistake: one of MISTAKES (a deliberately wrong
+    restatement; the bars are the right one's)"""
+    idx = np.arange(len(c.features)) if c.rows is None else np.asarray(c.rows, dtype=np.int64)
+    R = len(idx)
+    x = c.features[idx]
+    if c.norm is not None:
+        x = pl.normalise(x, *c.norm)
+    piles = c.head == "piles"
+    S = c.S if piles else 0
+    G = 2 if piles else 4
+    ls = np.asarray(c.log_std, dtype=F32).astype(np.float64)
+    sd = np.exp(ls)
+    on = c.on[idx][:, :S] if piles else np.zeros((R, 0), dtype=bool)
+    st = np.ones((R, S), dtype=bool) if (c.sets is None or not piles or mistake == "set_ignored") else c.sets[idx][:, :S]
+    u = c.u[idx].astype(np.float64)
+    if mistake == "gauss_shift":
+        u = np.roll(u, 1, axis=1)
+    A = np.asarray(c.adv, dtype=F32)
+    if c.adv_stats is not None:
+        A = adv_norm(A, c.adv_stats)
+    A = A[idx].astype(np.float64)
+
+    # ---- forward, with policy_lib.forward's bound per image
+    hs, errs, zs, ezs = [np.asarray(x, dtype=np.float64)], [np.zeros(x.shape)], [], []
+    L = len(c.layers)
+    for l, (W, b) in enumerate(c.layers):
+        W, b = np.asarray(W, dtype=np.float64), np.asarray(b, dtype=np.float64)
+        K = W.shape[1]
+        h, err = hs[-1], errs[-1]
+        z = h @ W.T + b
+        ez = pl.gamma(K + 2) * (np.abs(b) + (np.abs(h) + err) @ np.abs(W).T) + err @ np.abs(W).T + K * TINY
+        zs.append(z)
+        ezs.append(ez)
+        if l < L - 1:
+            if c.act == "tanh":
+                hs.append(np.tanh(z))
+                errs.append(ez + pl.TANH_ERR)
+            else:
+                hs.append(np.maximum(z, 0.0))
+                errs.append(ez)
+    z, ez = zs[-1], ezs[-1]
+    zp, ezp, zg, ezg = z[:, :S], ez[:, :S], z[:, S:S + G], ez[:, S:S + G]
+
+    # ---- logp, entropy and their bounds
+    xs = np.where(on, -zp, zp)
+    T = ps.softplus(xs)
+    e_ = np.exp(-np.abs(xs))
+    sp_err = lambda t, ezz, ee: ezz + ee * ps.EXP_ULP * ULP + np.log1p(ee) * ps.LOG1P_ULP * ULP + 1.001 * U * (t + ezz)
+    err_T = sp_err(T, ezp, e_)
+    eps = (u - zg) / sd
+    # eps on the device: the difference rounded once over the values held, expf within EXP_ULP ulp, the quotient rounded once
+    err_eps = (ezg + U * (np.abs(u - zg) + ezg)) / sd + np.abs(eps) * (ps.EXP_ULP * ULP + 2 * U) * 1.01 + TINY
+    g = -0.5 * eps * eps - ls - HALF_LN_2PI
+    err_g = np.abs(eps) * err_eps + 0.5 * err_eps ** 2 + 4.004 * U * (0.5 * (np.abs(eps) + err_eps) ** 2 + np.abs(ls) + HALF_LN_2PI)
+    logp = -(T * st).sum(axis=1) + g.sum(axis=1)
+    mag = (T * st).sum(axis=1) + np.abs(g).sum(axis=1) + (err_T * st).sum(axis=1) + err_g.sum(axis=1)
+    bar_logp = (err_T * st).sum(axis=1) + err_g.sum(axis=1) + pl.gamma(S + G + 8) * mag
+    sg = sigmoid(zp)
+    err_sg = ezp / 4 + sg * (1 - sg) * ps.EXP_ULP * ULP * 1.01 + sg * 2.01 * U + TINY
+    Hb = ps.softplus(zp) - zp * sg
+    err_Hb = sp_err(ps.softplus(zp), ezp, np.exp(-np.abs(zp))) + np.abs(zp) * err_sg + ezp * (sg + err_sg) + 2.002 * U * (np.abs(zp * sg) + ps.softplus(zp))
+    Hg = 0.5 + ls + HALF_LN_2PI
+    ent = (Hb * st).sum(axis=1) + Hg.sum()
+    mag_e = (np.abs(Hb) * st).sum(axis=1) + np.abs(Hg).sum() + (err_Hb * st).sum(axis=1)
+    bar_ent = (err_Hb * st).sum(axis=1) + 3.003 * U * np.abs(Hg).sum() + pl.gamma(S + G + 8) * mag_e
+
+    # ---- the coefficient c = R dL/dlogp, the loss terms
+    ecoef = float(F32(c.ent_coef))
+    if c.loss == "coef":
+        ratio, active = np.ones(R), np.ones(R, dtype=bool)
+        coef, err_c = -A, np.zeros(R)
+        term = -A * logp - ecoef * ent
+        bar_term = np.abs(A) * bar_logp + abs(ecoef) * bar_ent + 3.003 * U * (np.abs(A * logp) + abs(ecoef * ent))
+        dlp = np.zeros(R)
+        bar_dlp = np.zeros(R)
+        err_ratio = np.zeros(R)
+    else:
+        lo_ = c.logp_old[idx].astype(np.float64)
+        d = logp - lo_
+        ratio = np.exp(d)
+        err_d = bar_logp + U * (np.abs(d) + bar_logp)
+        err_ratio = ratio * (np.expm1(err_d) + ps.EXP_ULP * ULP * np.exp(err_d) * 1.01)
+        r_lo, r_hi = float(F32(1) - F32(c.clip_eps)), float(F32(1) + F32(c.clip_eps))
+        active = ((A >= 0) & (ratio < r_hi)) | ((A < 0) & (ratio > r_lo))
+        coef = np.where(active, -A * ratio, 0.0)
+        err_c = np.where(active, np.abs(A) * err_ratio + U * (np.abs(A) * (ratio + err_ratio)), 0.0)
+        surr = np.minimum(ratio * A, np.clip(ratio, r_lo, r_hi) * A)
+        term = -surr - ecoef * ent
+        bar_term = np.abs(A) * err_ratio + abs(ecoef) * bar_ent + 3.003 * U * (np.abs(surr) + abs(ecoef * ent)) + np.abs(A) * err_ratio * U
+        dlp = lo_ - logp
+        bar_dlp = bar_logp
+    count = float(R)
+    stats = np.array([count, term.sum(), ent.sum(), dlp.sum(), float((~active).sum()), ratio.sum() if c.loss != "coef" else 0.0])
+    bar_stats = np.array([0.0, bar_term.sum(), bar_ent.sum(), bar_dlp.sum(), 0.0, err_ratio.sum()]) * 1.001 + TINY
+
+    # ---- the head's delta z
+    cc, ec = coef[:, None], err_c[:, None]
+    dh = -zp * sg * (1 - sg)
+    err_dh = ezp + 2 * np.abs(zp) * err_sg + 4.004 * U * np.abs(dh) + TINY
+    t1 = cc * (on - sg)
+    dp = (t1 - ecoef * dh) * st
+    err_dp = (ec * (np.abs(on - sg) + err_sg + U) + np.abs(cc) * (err_sg + U * (np.abs(on - sg) + err_sg)) + U * np.abs(t1) + abs(ecoef) * (err_dh + U * np.abs(dh))
+              + U * (np.abs(t1) + abs(ecoef * dh))) * st
+    q = eps / sd
+    err_q = err_eps / sd + np.abs(q) * (ps.EXP_ULP * ULP + 2 * U) * 1.01
+    dg = cc * q
+    err_dg = ec * (np.abs(q) + err_q) + np.abs(cc) * err_q + U * np.abs(dg)
+    delta = np.concatenate([dp, dg], axis=1)
+    err_delta = np.concatenate([err_dp, err_dg], axis=1) * 1.001 + TINY
+    w = eps * eps - 1.0
+    err_w = 2 * np.abs(eps) * err_eps + err_eps ** 2 + U * (eps * eps + err_eps) + U * np.abs(w)
+    tls = cc * w - ecoef
+    err_tls = ec * (np.abs(w) + err_w) + np.abs(cc) * err_w + U * np.abs(cc * w) + U * np.abs(tls)
+    if mistake == "row_dropped":
+        delta = delta.copy()
+        delta[R // 2] = 0.0
+        tls = tls.copy()
+        tls[R // 2] = 0.0
+    div = 1.0 if mistake == "no_1_over_R" else float(R)  # (the sum divided by R, as the merge does)
+    gls = tls.sum(axis=0) / div
+    bar_ls = (err_tls.sum(axis=0) * 1.001 + U * np.abs(tls.sum(axis=0))) / R + TINY
+
+    # ---- backward
+    gam = pl.gamma(32 * int(tpw) + 3)
+    gW, gb, bar_W, bar_b = [None] * L, [None] * L, [None] * L, [None] * L
+    dl, edl = delta, err_delta
+    for l in range(L - 1, -1, -1):
+        W = np.asarray(c.layers[l][0], dtype=np.float64)
+        h, eh = hs[l], errs[l]
+        gW[l] = dl.T @ h / div
+        gb[l] = dl.sum(axis=0) / div
+        ad = np.abs(dl)
+        bar_W[l] = ((edl.T @ (np.abs(h) + eh) + ad.T @ eh) + gam * ((ad + edl).T @ (np.abs(h) + eh))) / R * 1.001 + TINY
+        bar_b[l] = (edl.sum(axis=0) + pl.gamma(32 * int(tpw) + 34) * (ad + edl).sum(axis=0)) / R * 1.001 + TINY
+        if l > 0:
+            pre = dl @ W
+            e_pre = edl @ np.abs(W) + pl.gamma(W.shape[0] + 2) * ((ad + edl) @ np.abs(W)) + W.shape[0] * TINY
+            if c.act == "tanh":
+                fac = 1.0 - h * h
+                e_fac = 2 * np.abs(h) * eh + eh * eh + 2.002 * U
+                nd = pre * fac
+                edl = e_pre * (np.abs(fac) + e_fac) + np.abs(pre) * e_fac + U * np.abs(nd)
+            else:
+                zl, ezl = zs[l - 1], ezs[l - 1]
+                nd = np.where(zl > 0, pre, 0.0)
+                edl = np.where(np.abs(zl) <= ezl, np.abs(pre) + e_pre, np.where(zl > 0, e_pre, 0.0))
+            dl = nd
+    if mistake == "head_rows_swapped":
+        t = gb[-1][:32]  # (two rows of the head's first tile: the ones whose bias gradients lie furthest apart)
+        i, j = int(t.argmax()), int(t.argmin())
+        gW[-1] = gW[-1].copy()
+        gW[-1][[i, j]] = gW[-1][[j, i]]
+        gb[-1] = gb[-1].copy()
+        gb[-1][[i, j]] = gb[-1][[j, i]]
+    return dict(gW=gW, gb=gb, gls=gls, logp=logp, ent=ent, stats=stats, coef=coef, ratio=ratio, active=active, A=A, bar_W=bar_W, bar_b=bar_b,
+                bar_ls=bar_ls, bar_logp=bar_logp, bar_ent=bar_ent, bar_stats=bar_stats, err_ratio=err_ratio, delta=delta, hs=hs,
+                eps=eps, u=u, zg=zg, sd=sd, ls=ls, terms_mag=(T * st).sum(axis=1) + np.abs(g).sum(axis=1))
+
+
+MISTAKES = ("row_dropped", "head_rows_swapped", "set_ignored", "gauss_shift", "no_1_over_R")
+
+
+def outside_bar(right, wrong):
+    """whether a wrong restatement leaves the right one's bar somewhere in gW, gb or g_log_std"""
+    out = any((np.abs(a - b) > bar).any() for a, b, bar in zip(right["gW"], wrong["gW"], right["bar_W"]))
+    out |= any((np.abs(a - b) > bar).any() for a, b, bar in zip(right["gb"], wrong["gb"], right["bar_b"]))
+    return bool(out | (np.abs(right["gls"] - wrong["gls"]) > right["bar_ls"]).any())
+
+
+def check_conditions(c, r):
+    """the conditions on a case's DATA under which the GPU comparison means something: the bar below 2^-8 of every layer's largest
+    gradient; under PPO_CLIP no ratio within 1e-3 of a bound, and no ratio's own error bound that large (no conforming device can decide the predicate otherwise)"""
+    for l in range(len(c.layers)):
+        assert r["bar_W"][l].max() < 2.0 ** -8 * np.abs(r["gW"][l]).max(), ("bar of gW", l, r["bar_W"][l].max(), np.abs(r["gW"][l]).max())
+        assert r["bar_b"][l].max() < 2.0 ** -8 * np.abs(r["gb"][l]).max(), ("bar of gb", l, r["bar_b"][l].max(), np.abs(r["gb"][l]).max())
+    assert r["bar_ls"].max() < 2.0 ** -8 * np.abs(r["gls"]).max(), ("bar of g_log_std", r["bar_ls"], r["gls"])
+    if c.loss == "ppo_clip":
+        lo, hi = float(F32(1) - F32(c.clip_eps)), float(F32(1) + F32(c.clip_eps))
+        gap = np.minimum(np.abs(r["ratio"] - lo), np.abs(r["ratio"] - hi))
+        assert gap.min() > 1e-3 and r["err_ratio"].max() < 1e-3, ("a ratio on a bound", gap.min(), r["err_ratio"].max())
+
+
+def rederivation_bound(r):
+    """Unchanged parameters: what |logp_new - logp| may be, per row, when the gradient launch and the sampled launch that recorded logp
+    form the SAME z bits and the same pile terms in the same order (include/chub.h: the forward is the actor's chain; a head tile
+    belongs to the same wave in both launches, since a sampled launch of fewer than four waves has no more head tiles than waves).
+    What differs is the G Gaussian terms: the sampled launch holds eps, the gradient launch re-derives it from the recorded
+    u = fl(z + fl(sigma eps)) as fl(fl(u - z) / sigma) with the same expf(log_std) bits.
+      eps:   the recorded sum and the product inside it were rounded once each, the difference and the quotient are rounded once each:
+             |eps' - eps| <= (u (|u| + |sigma eps|) + u |u - z|) / sigma + u |eps|, taken with |sigma eps| <= |u - z| (1 + 2 u)
+      term:  |eps| d + d^2 / 2, plus the three roundings of each launch's own term, 2 * 3 u (eps^2 / 2 + |log_std| + ln(2 pi) / 2)
+      sums:  the additions up to the first Gaussian term see identical operands; the G + 4 after it (the lane's remaining terms, the
+             half-wave shuffle, at most three waves' partials) are re-rounded in both launches: 2 gamma(G + 4) * the sum of the
+             terms' magnitudes
+    -> bound [R] f64; a ratio exp(logp_new - logp) then lies within expm1(bound) plus expf's 3 ulp of 1"""
+    eps, u, zg, sd, ls = r["eps"], r["u"], r["zg"], r["sd"], r["ls"]
+    G = eps.shape[1]
+    d = (U * (np.abs(u) + 2.01 * np.abs(u - zg)) / sd + U * np.abs(eps)) * 1.01 + TINY
+    term = np.abs(eps) * d + 0.5 * d * d + 2 * 3.003 * U * (0.5 * eps * eps + np.abs(ls) + HALF_LN_2PI)
+    return term.sum(axis=1) * 1.001 + 2 * pl.gamma(G + 4) * r["terms_mag"]
+
+
+def ratio_bound(bound):
+    """|exp(d) - 1| for |d| <= bound as expf forms it: the difference of two close f32 is exact, expf is within EXP_ULP ulp"""
+    return np.expm1(bound) + ps.EXP_ULP * ULP * 1.01 * np.exp(bound)
+
+
+def clipped_both_ways(c, r):
+    lo, hi = float(F32(1) - F32(c.clip_eps)), float(F32(1) + F32(c.clip_eps))
+    up = int(((r["A"] >= 0) & (r["ratio"] >= hi)).sum())
+    down = int(((r["A"] < 0) & (r["ratio"] <= lo)).sum())
+    return up, down
+
+
+# ---- the plan, through the C ABI (host-only: it needs no device)
+def plan(piles, widths, R, head="piles", act="tanh", inputs=("obs",), expect=0):
+    """chub_policy_grad_plan -> (rc, dict of the out struct, message)"""
+    import charginghub_env_amd as chub
+    from charginghub_env_amd import _lib
+
+    lib = chub.load_library()
+    cfg = _lib.ChubConfig()
+    cfg.station_list[0], cfg.station_list[1] = int(piles[0]), int(piles[1])
+    spec = _lib.policy_spec(widths, inputs, head, act, "tanh", False, 0.0)
+    out = _lib.ChubPolicyGradPlanOut()
+    rc = lib.chub_policy_grad_plan(C.byref(cfg), C.byref(spec), int(R), C.byref(out))
+    return rc, {name: int(getattr(out, name)) for name, _ in out._fields_}, lib.chub_last_error().decode()
+
+
+def tiles_per_workgroup(piles, widths, R, head="piles", act="tanh", inputs=("obs",)):
+    rc, p, msg = plan(piles, widths, R, head, act, inputs)
+    assert rc == 0, msg
+    tiles = (R + 31) // 32
+    return (tiles + p["workgroups"] - 1) // p["workgroups"]
+
+
+# ---- cases.  Made HERE so that the CPU test holds the conditions on the GPU test's own data
+ALIGN_HUBS = ([3, 2], [20, 25], [31, 31], [32, 31], [33, 32])
+BIG_HUB = [40, 37]  # 77 piles: two bit words, three head tiles
+R_LIST = (1, 31, 32, 33, 95)
+WIDTH_NETS = ((1,), (31,), (33,), (64, 64), (256, 33), (33, 256, 31), ())
+
+
+def weight_std(fan_in):
+    """1 / fan-in: a row's sum of |w| stays near 0.8, so the forward bound's worst case (absolute row sums, layer after layer) does not
+    grow with the depth and the bar stays small against the gradient"""
+    return 1.0 / fan_in
+
+
+def general_layers(rs, sizes):
+    return [((rs.normal(size=(o, i)) * weight_std(i)).astype(F32), (rs.normal(size=o) * 0.1).astype(F32)) for i, o in zip(sizes[:-1], sizes[1:])]
+
+
+WIDE_INPUTS = ("obs", ("pile_obs", ("car",)), ("forecast", ("price",), 6))  # 13 + 45 + 6 = 64 features on [20, 25]
+
+
+def synthetic_case(piles, hidden, act="tanh", head="piles", n_rows=95, loss="ppo_clip", sets=True, norm=False, seed=0, step=0.25, ent_coef=0.01,
+                   adv_stats=False, inputs=("obs",), F=None):
+    """a rollout made in numpy: actions drawn from the OLD weights' distribution, logp_old recorded in f32, then every weight moved by a
+    seeded step so that ratios spread over both bounds"""
+    S, D = sum(piles), (ps.obs_dim(piles) if F is None else F)  # (D: the feature row's width)
+    rs = np.random.RandomState(9000 + 131 * S + 17 * len(hidden) + sum(hidden) + 3 * n_rows + seed)
+    piles_head = head == "piles"
+    A_out, G, Sp = (S + 2, 2, S) if piles_head else (4, 4, 0)
+    old = general_layers(rs, [D] + list(hidden) + [A_out])
+    feats = (rs.normal(size=(n_rows, D)) + 0.3).astype(F32)
+    nrm = ((rs.normal(size=D) * 0.2).astype(F32), (1.0 + rs.rand(D)).astype(F32) * F32(0.5), 3.0) if norm else None
+    ls_old = np.array([-0.2, 0.1, -0.1, 0.3][:G], dtype=F32)
+    base = Case(layers=old, log_std=ls_old, norm=nrm, act=act, head=head, S=S, features=feats, on=np.zeros((n_rows, Sp), dtype=bool),
+                sets=None, u=np.zeros((n_rows, G), dtype=F32), logp_old=np.zeros(n_rows, dtype=F32), adv=np.zeros(n_rows, dtype=F32), loss="coef",
+                inputs=inputs)
+    z = _forward_z(base)
+    on = rs.rand(n_rows, Sp) < sigmoid(z[:, :Sp])
+    u = (z[:, Sp:] + np.exp(ls_old.astype(np.float64)) * rs.normal(size=(n_rows, G))).astype(F32)
+    st = (rs.rand(n_rows, Sp) < SET_RATE) if (sets and piles_head) else None
+    rec = base.copy(on=on, u=u, sets=st)
+    logp_old = restate(rec)["logp"].astype(F32)
+    adv = (rs.normal(size=n_rows) + 1.0).astype(F32)
+    new = perturbed(rs, old, step)
+    ls_new = (ls_old + F32(step) * rs.normal(size=G).astype(F32)).astype(F32)
+    stats = None
+    if adv_stats:
+        a64 = adv.astype(np.float64)
+        stats = np.array([float(n_rows), a64.sum(), (a64 * a64).sum()])
+    return rec.copy(layers=new, log_std=ls_new, logp_old=logp_old, adv=adv, loss=loss, ent_coef=ent_coef, adv_stats=stats,
+                    name="%s-%s-%s-%s-%d" % (ps_hub(piles), "x".join(map(str, hidden)) or "linear", act, head, n_rows), piles=list(piles), hidden=tuple(hidden))
+
+
+def perturbed(rs, layers, step):
+    """every weight moved by step * its layer's scale, every bias by step * its own (0.1): the update between collecting and differentiating"""
+    return [((W + step * weight_std(W.shape[1]) * rs.normal(size=W.shape)).astype(F32), (b + 0.1 * step * rs.normal(size=b.shape)).astype(F32)) for W, b in layers]
+
+
+def ps_hub(p):
+    return "%dx%d" % tuple(p)
+
+
+def _forward_z(c):
+    x = c.features if c.norm is None else pl.normalise(c.features, *c.norm)
+    h = np.asarray(x, dtype=np.float64)
+    for l, (W, b) in enumerate(c.layers):
+        h = h @ np.asarray(W, dtype=np.float64).T + np.asarray(b, dtype=np.float64)
+        if l < len(c.layers) - 1:
+            h = np.tanh(h) if c.act == "tanh" else np.maximum(h, 0.0)
+    return h
+
+
+def separate_ratios(c, tpw=1):
+    """drop nothing and move nothing: rows whose ratio lies within 1e-3 of a bound get their recorded logp_old moved by 4e-3 -- the
+    inputs avoid ties, as the definition leaves them open"""
+    if c.loss != "ppo_clip":
+        return c
+    r = restate(c, tpw)
+    lo, hi = float(F32(1) - F32(c.clip_eps)), float(F32(1) + F32(c.clip_eps))
+    idx = np.arange(len(c.features)) if c.rows is None else np.asarray(c.rows)
+    near = np.minimum(np.abs(r["ratio"] - lo), np.abs(r["ratio"] - hi)) <= 2e-3
+    if near.any():
+        lp = c.logp_old.copy()
+        lp[idx[near]] += F32(8e-3)
+        c = c.copy(logp_old=lp)
+    return c
+
+
+SET_RATE = 0.3  # a pile is in a synthetic row's set with this probability (few terms per row: a small logp bound, a small ratio bound)
+
+
+def gpu_general_cases():
+    """the synthetic twins of the GPU test's general cases (same nets, heads, activations, losses and R), for the CPU conditions.
+    Under PPO_CLIP the coefficient c = -A ratio carries the log-probability's whole bound, and the bar adds it over rows and outputs
+    in absolute value while the gradient cancels: the PPO cases are therefore the one-hidden-layer nets, the LOADS head and three deeper nets
+    whose data meet the condition; the other wide and deep nets are differentiated under COEF, whose coefficient is exact."""
+    out = []
+    for k, piles in enumerate(ALIGN_HUBS):
+        out.append(synthetic_case(piles, (33,), "tanh" if k % 2 == 0 else "relu", "piles", 95, "ppo_clip", True, k % 2 == 1, seed=k))
+    out.append(synthetic_case(BIG_HUB, (33,), "tanh", "piles", 95, "ppo_clip", True, False, seed=7))
+    out.append(synthetic_case([20, 25], (64, 64), "tanh", "loads", 95, "ppo_clip", False, True, seed=8))
+    out.append(synthetic_case([20, 25], (64, 64), "relu", "piles", 95, "coef", True, False, seed=9, adv_stats=True))
+    for k, hidden in enumerate(WIDTH_NETS):
+        loss = "ppo_clip" if len(hidden) < 2 and sum(hidden) < 64 else "coef"
+        out.append(synthetic_case([20, 25], hidden, "relu" if k % 2 else "tanh", "piles", 70, loss, True, False, seed=20 + k))
+    out.append(synthetic_case([3, 2], (31, 33, 64), "tanh", "piles", 70, "coef", True, False, seed=30))
+    # 64 -> 256 -> 224 -> 47: 1072 LDS rows, 141 KB -- the launch beyond 64 KiB of dynamic LDS, its dW tiles in the partials.  (64 -> 256
+    # -> 256 -> 47 fits the gradient's rule too, but chub_policy_set_exploration refuses it: 512 + 4 rows in the sampled launch)
+    out.append(synthetic_case([20, 25], (256, 224), "tanh", "piles", 70, "coef", True, False, seed=31, inputs=WIDE_INPUTS, F=64))
+    # PPO_CLIP through two and three hidden layers on the piles head, where the data keep the bar below 2^-8 of every layer's gradient
+    out.append(synthetic_case([3, 2], (64, 64), "tanh", "piles", 95, "ppo_clip", True, False, seed=52))
+    out.append(synthetic_case([20, 25], (33, 31), "relu", "piles", 70, "ppo_clip", True, False, seed=54))
+    out.append(synthetic_case([3, 2], (31, 33, 64), "tanh", "piles", 70, "ppo_clip", True, False, seed=55))
+    for R in R_LIST:
+        out.append(synthetic_case([20, 25], (33,), "tanh", "piles", R, "ppo_clip" if R > 1 else "coef", True, False, seed=40 + R))
+    return [separate_ratios(c) for c in out]
+
+
+# ---- the exact case: every product and every partial sum exact in f32, so the gradient equals the restatement BIT FOR BIT
+def exact_case(n_layers, n_rows, piles=(20, 25), hidden=(33, 64, 31)):
+    """LOADS head, relu, log_std = 0, features multiples of 1/2, weights in {-1, 0, 1} (three per output), integer biases, u multiples of
+    1/2, advantages +-2^k, COEF loss, ent_coef = 1/2"""
+    D = ps.obs_dim(piles)
+    rs = np.random.RandomState(77000 + n_layers + 7 * sum(hidden[:n_layers - 1]))  # (the net does not depend on R: one policy serves every R)
+    sizes = [D] + list(hidden[:n_layers - 1]) + [4]
+    layers = []
+    for fan_in, out in zip(sizes[:-1], sizes[1:]):
+        W = np.zeros((out, fan_in), dtype=F32)
+        for n in range(out):
+            cols = rs.choice(fan_in, size=min(3, fan_in), replace=False)
+            W[n, cols] = rs.choice([-1, 1], size=len(cols))
+        layers.append((W, rs.randint(-1, 2, size=out).astype(F32)))
+    rs = np.random.RandomState(78000 + 100 * n_layers + n_rows + 7 * sum(hidden[:n_layers - 1]))
+    feats = (rs.randint(-4, 5, size=(n_rows, D)) / 2.0).astype(F32)
+    u = (rs.randint(-8, 9, size=(n_rows, 4)) / 2.0).astype(F32)
+    adv = (rs.choice([-1.0, 1.0], size=n_rows) * 2.0 ** rs.randint(-2, 2, size=n_rows)).astype(F32)
+    c = Case(layers=layers, log_std=np.zeros(4, dtype=F32), act="relu", head="loads", S=sum(piles), features=feats, on=np.zeros((n_rows, 0), dtype=bool),
+             u=u, logp_old=np.zeros(n_rows, dtype=F32), adv=adv, loss="coef", ent_coef=0.5, name="exact-%d-%d" % (n_layers, n_rows), piles=list(piles),
+             hidden=tuple(hidden[:n_layers - 1]))
+    assert_exact(c)
+    return c
+
+
+EXACT_WIDE = (256, 64)  # 8 + 16 + 2 = 26 dW tiles of 32 x 32: more than the 16 a workgroup keeps in registers
+
+
+def assert_exact(c):
+    """every value and every product is a multiple of 2^-4 and every sum of absolute values stays below 2^23 quanta: any partial sum in
+    any order is exact in f32"""
+    q = 2.0 ** -4
+    r = restate(c)
+    h = np.asarray(c.features, dtype=np.float64)
+    for l, (W, b) in enumerate(c.layers):
+        W, b = np.asarray(W, dtype=np.float64), np.asarray(b, dtype=np.float64)
+        assert ((np.abs(h) @ np.abs(W).T + np.abs(b)).max()) / q < 2.0 ** 23
+        h = h @ W.T + b
+        if l < len(c.layers) - 1:
+            h = np.maximum(h, 0.0)
+        assert np.array_equal(h / q, np.round(h / q))
+    dl = r["delta"]
+    for l in range(len(c.layers) - 1, -1, -1):
+        W = np.asarray(c.layers[l][0], dtype=np.float64)
+        assert np.array_equal(dl / q, np.round(dl / q))
+        assert (np.abs(dl).T @ np.abs(r["hs"][l])).max() / q < 2.0 ** 23 and np.abs(dl).sum(axis=0).max() / q < 2.0 ** 23
+        if l > 0:
+            assert (np.abs(dl) @ np.abs(W)).max() / q < 2.0 ** 23
+            dl = np.where(r["hs"][l] > 0, dl @ W, 0.0)
+    return r
+
+
+def exact_expected(c):
+    """the f32 bits the device must give: the exact sums over R in f64, rounded once"""
+    r = restate(c)
+    return [g.astype(F32) for g in r["gW"]], [g.astype(F32) for g in r["gb"]], r["gls"].astype(F32)
+
+
+def pack_bits(on, S):
+    """bool [n, S] -> uint64 [n, ceil(S / 64)], bit b of word w = on[64 w + b]"""
+    on = np.asarray(on, dtype=bool)
+    W = max((S + 63) // 64, 1)
+    packed = np.packbits(on, axis=1, bitorder="little") if on.shape[1] else np.zeros((len(on), 0), dtype=np.uint8)
+    full = np.zeros((len(on), W * 8), dtype=np.uint8)
+    full[:, :packed.shape[1]] = packed
+    return np.ascontiguousarray(full).view("<u8").reshape(len(on), W)

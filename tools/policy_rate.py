@@ -16,6 +16,11 @@
                   chub_population_run_steps at P = 256 (as `closed_loop`), perturb_P<P> and es_gradient_P<P> us per
                   chub_population_perturb_device / chub_population_es_gradient_device at P = 256 and 2048, with the Philox blocks a call
                   computes; the sampled and set cases are left out.
+  --policy-grad   adds, after one collected day with decidable sets and raw feature rows: policy_grad us per chub_policy_grad_device over the
+                  whole day (R = 96 N rows, PPO_CLIP with the sets, every gradient output) and policy_eval us per forward-only call, with
+                  the algorithmic FLOP of each; with --torch-grad also policy_grad_torch, the same update as torch autograd over the same
+                  device memory in the same process (f32 network, wrappers.sampled_logp / sampled_entropy; torch is then imported first).
+                  The other sampled and set cases are left out.
 Every case is warmed up, then the cases alternate, ROUNDS times; median, best and worst round are reported with the build id.
 --open-loop-only measures the open loop alone, --launch-only the open loop and the deterministic launch, --no-sets the first five cases:
 with CHUB_LIB=<another build's libchub.so> those are the rates of a build without the newer entry points (the parent commit), on the same
@@ -31,7 +36,7 @@ import time
 
 import numpy as np
 
-if "--torch-gae" in sys.argv:
+if "--torch-gae" in sys.argv or "--torch-grad" in sys.argv:
     import torch  # before libchub is loaded: both must share one HIP runtime
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -52,6 +57,8 @@ def main():
     ap.add_argument("--torch-gae", action="store_true")
     ap.add_argument("--no-sets", action="store_true", help="the first five cases only: what a build without the pile set entry points can run")
     ap.add_argument("--population", action="store_true", help="the open loop, the launch, the closed loop and the population cases")
+    ap.add_argument("--policy-grad", action="store_true", help="the open loop, the launch and the actor-gradient cases")
+    ap.add_argument("--torch-grad", action="store_true")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     n_s, piles_s = args.shape.split("x")
@@ -127,6 +134,9 @@ def main():
             cases[("closed_loop", "chub_policy_run_steps", "env_steps_per_s")] = closed_loop
             population_cases(cases, notes, v, pol, sizes, packed, obs0, bits, tail, st, steps, args.calls, between_events)
             args.launch_only = True  # (the sampled and set cases are not part of this run)
+        if args.policy_grad:
+            policy_grad_cases(cases, notes, v, pol, layers, obs0, st, max(1, args.calls // 20), between_events, args.torch_grad)
+            args.launch_only = True
         if not args.launch_only:
             cases[("closed_loop", "chub_policy_run_steps", "env_steps_per_s")] = closed_loop
             # the SAMPLED actor: one launch with bits + tail + u + logp out, and chub_policy_collect in lock-step mode, a day per call
@@ -283,6 +293,84 @@ def population_cases(cases, notes, v, pol, sizes, packed, obs0, bits, tail, st, 
         cases[("perturb_P%d" % P, "chub_population_perturb_device", "us_per_call")] = perturb(pops[P])
         cases[("es_gradient_P%d" % P, "chub_population_es_gradient_device", "us_per_call")] = es_gradient(pops[P])
         notes["perturb_P%d" % P] = notes["es_gradient_P%d" % P] = dict(members=P, philox_blocks=blocks, launches_per_round=few)
+
+
+def device_view(ptr, shape, typestr="<f4"):
+    """a torch tensor over device memory this process owns (never read on the host: only the address and the shape are used)"""
+    iface = dict(shape=tuple(shape), typestr=typestr, data=(int(ptr), False), version=2)
+    return torch.as_tensor(type("DeviceArray", (), {"__cuda_array_interface__": iface})(), device="cuda")
+
+
+def policy_grad_cases(cases, notes, v, pol, layers, obs0, st, calls, between_events, with_torch):
+    """the --policy-grad cases: one collected day (lock-step, decidable sets, raw feature rows), then the whole day as ONE batch"""
+    n, D, W, T, stream = v.n_envs, v.obs_dim, v.bit_words, 96, st.ptr
+    R, F = T * n, pol.n_features
+    pol.set_exploration(2024, np.array([-0.5, -0.5], dtype=np.float32))
+    B = multi_gpu.DeviceBuffer
+    roll = dict(packed=B(R * (D + 2) * 4), bits=B(R * W * 8), tail=B(R * 8), u=B(R * 8), logp=B(R * 4), feat=B(R * F * 4), set=B(R * W * 8),
+                adv=B(R * 4), logp_new=B(R * 4), ent=B(R * 4), stats=B(48), gls=B(16))
+    pol.collect(T, obs0.ptr, roll["packed"].ptr, roll["bits"].ptr, roll["tail"].ptr, roll["u"].ptr, roll["logp"].ptr, d_features=roll["feat"].ptr,
+                mode="lockstep", stream=stream, logp_piles="decidable", d_set_bits=roll["set"].ptr)
+    roll["adv"].from_host(np.random.RandomState(2).normal(size=R).astype(np.float32))
+    shapes = [W_.shape for W_, _ in layers]
+    gW, gb = [B(o * i * 4) for o, i in shapes], [B(o * 4) for o, _ in shapes]
+    g = v.make_policy_grad(pol, R)
+    plan = g.plan()
+    # the update moves the weights a little, so that ratios are not all 1 (the work does not depend on it)
+    rs = np.random.RandomState(3)
+    moved = [((W_ + 0.02 * rs.normal(size=W_.shape) / np.sqrt(W_.shape[1])).astype(np.float32), b_) for W_, b_ in layers]
+    for l, (W_, b_) in enumerate(moved):
+        pol.set_weights(l, W_, b_)
+
+    def grad(backward):
+        def run():
+            def many():
+                for _ in range(calls):
+                    g.grad_device(R, R, roll["feat"].ptr, roll["u"].ptr, roll["adv"].ptr, roll["bits"].ptr, roll["set"].ptr, roll["logp"].ptr,
+                                  loss="ppo_clip", clip_eps=0.2, ent_coef=0.01, d_gW=[x.ptr for x in gW] if backward else None,
+                                  d_gb=[x.ptr for x in gb] if backward else None, d_glog_std=roll["gls"].ptr if backward else 0,
+                                  d_logp_new=roll["logp_new"].ptr, d_entropy=roll["ent"].ptr, d_stats=roll["stats"].ptr, stream=stream)
+            return between_events(many) * 1e3 / calls
+        return run
+
+    mac = sum(o * i for o, i in shapes)  # multiply-adds of one row's forward
+    cases[("policy_grad", "chub_policy_grad_device", "us_per_call")] = grad(True)
+    cases[("policy_eval", "chub_policy_grad_device, no gradient outputs", "us_per_call")] = grad(False)
+    notes["policy_grad"] = dict(rows=R, launches_per_round=calls, flop_per_row=3 * 2 * mac, gflop_per_call=round(3 * 2 * mac * R / 1e9, 1),
+                                workgroups=plan["workgroups"], lds_bytes=plan["lds_bytes"], in_registers=plan["in_registers"])
+    notes["policy_eval"] = dict(rows=R, launches_per_round=calls, flop_per_row=2 * mac, gflop_per_call=round(2 * mac * R / 1e9, 1))
+    if with_torch:
+        from charginghub_env_amd import wrappers
+        few = max(1, calls // 2)
+        S = v.n_slots
+        net = torch.nn.Sequential(*[m for k, (o, i) in enumerate(shapes) for m in ([torch.nn.Linear(i, o)] + ([torch.nn.Tanh()] if k < len(shapes) - 1 else []))]).to("cuda")
+        lin = [m for m in net if isinstance(m, torch.nn.Linear)]
+        with torch.no_grad():
+            for m, (W_, b_) in zip(lin, moved):
+                m.weight.copy_(torch.tensor(W_))
+                m.bias.copy_(torch.tensor(b_))
+        log_std = torch.tensor([-0.5, -0.5], device="cuda", requires_grad=True)
+        feat, u, lp_old, adv = device_view(roll["feat"].ptr, (R, F)), device_view(roll["u"].ptr, (R, 2)), device_view(roll["logp"].ptr, (R,)), device_view(roll["adv"].ptr, (R,))
+        bits, sets = device_view(roll["bits"].ptr, (R, W), "<i8"), device_view(roll["set"].ptr, (R, W), "<i8")
+
+        def torch_grad():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(few):
+                for prm in list(net.parameters()) + [log_std]:
+                    prm.grad = None
+                z = net(feat)
+                lp = wrappers.sampled_logp(z, bits, u, log_std, piles=sets)
+                en = wrappers.sampled_entropy(z, log_std, piles=sets)
+                ratio = torch.exp(lp - lp_old)
+                loss = (-torch.minimum(ratio * adv, torch.clamp(ratio, 0.8, 1.2) * adv) - 0.01 * en).mean()
+                loss.backward()
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1) * 1e3 / few
+        cases[("policy_grad_torch", "torch autograd over the same memory", "us_per_call")] = torch_grad
+        notes["policy_grad_torch"] = dict(rows=R, launches_per_round=few)
 
 
 def torch_gae_case(packed_ptr, gae, n, T, D, calls):
