@@ -243,6 +243,52 @@ class ChubPolicyGradOut(C.Structure):
                 ("d_entropy", C.c_void_p), ("d_stats", C.c_void_p)]
 
 
+# a critic on the device (chub_critic_*): the CHUB_VLOSS_* enum of include/chub.h, in order
+VLOSS_NAMES = ("mse", "clipped")
+VLOSS = {name: i for i, name in enumerate(VLOSS_NAMES)}
+
+
+def value_loss(loss):
+    """a value loss as its CHUB_VLOSS_* value: a name of VLOSS_NAMES, or the value itself (the library refuses an unknown one)"""
+    return _enum_value(VLOSS, loss, "value loss")
+
+
+class ChubCriticSpec(C.Structure):
+    """chub_critic_spec of include/chub.h"""
+    _fields_ = [("F", C.c_int32), ("n_layers", C.c_int32), ("width", C.c_int32 * 4), ("hidden_act", C.c_int32), ("normalize", C.c_int32),
+                ("clip", C.c_float)]
+
+
+def critic_spec(F, widths, hidden_act="tanh", normalize=False, clip=0.0):
+    """chub_critic_spec for rows of F floats and layers of these widths (the last is 1); nothing is checked here: the library refuses"""
+    spec = ChubCriticSpec()
+    spec.F = int(F)
+    spec.n_layers = len(widths)
+    for l, w in enumerate(list(widths)[:4]):
+        spec.width[l] = int(w)
+    spec.hidden_act = _enum_value(PACT, hidden_act, "hidden activation")
+    spec.normalize = 1 if normalize else 0
+    spec.clip = float(clip)
+    return spec
+
+
+class ChubCriticPlanOut(C.Structure):
+    """chub_critic_plan_out of include/chub.h"""
+    _fields_ = [("n_params", C.c_int64), ("workspace_bytes", C.c_int64), ("workgroups", C.c_int32), ("lds_rows", C.c_int32),
+                ("lds_bytes", C.c_int32), ("in_registers", C.c_int32)]
+
+
+class ChubCriticGradIn(C.Structure):
+    """chub_critic_grad_in of include/chub.h: device addresses, 0 / None = not given"""
+    _fields_ = [("R", C.c_int64), ("n_rows", C.c_int64), ("d_rows", C.c_void_p), ("d_x", C.c_void_p), ("ld", C.c_int64), ("d_ret", C.c_void_p),
+                ("d_v_old", C.c_void_p), ("loss", C.c_int32), ("clip_eps", C.c_float)]
+
+
+class ChubCriticGradOut(C.Structure):
+    """chub_critic_grad_out of include/chub.h: device addresses, 0 / None = not asked for"""
+    _fields_ = [("d_gW", C.c_void_p * 4), ("d_gb", C.c_void_p * 4), ("d_values", C.c_void_p), ("d_stats", C.c_void_p)]
+
+
 # pile sets (chub_pile_set_device): the CHUB_PSET_* enum of include/chub.h, in order
 PSET_NAMES = ("all", "occupied", "decidable")
 PSET = {name: i for i, name in enumerate(PSET_NAMES)}
@@ -347,7 +393,8 @@ def source_hash():
 
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
-    for name in ("chub_kernels.hip", "chub_policy.hip", "chub_runtime.cpp", "chub_comm.cpp", "chub_device.h", "chub_curves.h", "chub_plan.h", "chub_policy.h"):
+    for name in ("chub_kernels.hip", "chub_policy.hip", "chub_critic.hip", "chub_runtime.cpp", "chub_comm.cpp", "chub_device.h", "chub_curves.h", "chub_plan.h",
+                 "chub_policy.h", "chub_critic.h"):
         h.update(open(os.path.join(csrc, name), "rb").read())
     h.update(open(os.path.join(os.path.dirname(_HERE), "include", "chub.h"), "rb").read())
     return h.hexdigest()[:16]
@@ -464,6 +511,13 @@ def load_library():
         "chub_policy_grad_plan": (I, [C.POINTER(ChubConfig), C.POINTER(ChubPolicySpec), L, C.POINTER(ChubPolicyGradPlanOut)]),
         "chub_policy_grad_create": (I, [P, L, C.POINTER(P)]), "chub_policy_grad_destroy": (I, [P]),
         "chub_policy_grad_device": (I, [P, C.POINTER(ChubPolicyGradIn), C.POINTER(ChubPolicyGradOut), P]),
+        "chub_critic_plan": (I, [C.POINTER(ChubCriticSpec), L, C.POINTER(ChubCriticPlanOut)]),
+        "chub_critic_create": (I, [P, C.POINTER(ChubCriticSpec), P, P, P, P, L, C.POINTER(P)]), "chub_critic_destroy": (I, [P]),
+        "chub_critic_set_weights": (I, [P, C.c_int32, P, P]), "chub_critic_set_weights_device": (I, [P, C.c_int32, P, P, P]),
+        "chub_critic_set_normalizer": (I, [P, P, P]), "chub_critic_set_normalizer_device": (I, [P, P, P, P]),
+        "chub_critic_normalizer_from_moments_device": (I, [P, P, C.c_double, P]),
+        "chub_critic_values_device": (I, [P, P, L, L, P, L, P, P]),
+        "chub_critic_grad_device": (I, [P, C.POINTER(ChubCriticGradIn), C.POINTER(ChubCriticGradOut), P]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -508,7 +562,10 @@ EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "ch
             "chub_population_param_count", "chub_population_create", "chub_population_destroy", "chub_population_perturb_device",
             "chub_population_set_member_device", "chub_population_get_member_device", "chub_population_set_member", "chub_population_get_member",
             "chub_population_copy_members_device", "chub_population_act_device", "chub_population_run_steps", "chub_population_es_gradient_device",
-            "chub_policy_grad_plan", "chub_policy_grad_create", "chub_policy_grad_destroy", "chub_policy_grad_device"]
+            "chub_policy_grad_plan", "chub_policy_grad_create", "chub_policy_grad_destroy", "chub_policy_grad_device",
+            "chub_critic_plan", "chub_critic_create", "chub_critic_destroy", "chub_critic_set_weights", "chub_critic_set_weights_device",
+            "chub_critic_set_normalizer", "chub_critic_set_normalizer_device", "chub_critic_normalizer_from_moments_device",
+            "chub_critic_values_device", "chub_critic_grad_device"]
 
 
 def check(rc):

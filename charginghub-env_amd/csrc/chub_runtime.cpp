@@ -18,6 +18,7 @@
 #include "chub_device.h"
 #include "chub_plan.h"
 #include "chub_policy.h"
+#include "chub_critic.h"
 
 namespace chub {
 template <bool RESET>
@@ -176,6 +177,8 @@ struct chub_env {
     std::vector<chub_policy *> policies;
     // the running feature statistics made for this handle (chub_moments_create): destroyed before it, state and partials outside the arena
     std::vector<chub_moments *> moments;
+    // the critics made for this handle (chub_critic_create): destroyed before it, weights and workspace outside the arena
+    std::vector<chub_critic *> critics;
     // chub_rollout_gae_device's statistics: the workgroups' partials [ceil(N / 256)][3] f64, allocated at create outside the arena (derived
     // scratch: no snapshot carries it).  One buffer: calls that ask for d_stats must be ordered against each other
     double *d_gae_part = nullptr;
@@ -1055,11 +1058,13 @@ static int create_impl(const chub_config *cfg_in, const char *data_dir, int64_t 
 
 static void policy_free(chub_policy *pol);
 static void moments_free(chub_moments *m);
+static void critic_free(chub_critic *c);
 
 int chub_destroy(chub_env *e) {
     if (!e) return CHUB_OK;
     while (!e->moments.empty()) moments_free(e->moments.back());  // (each takes itself off the list)
     while (!e->policies.empty()) policy_free(e->policies.back());
+    while (!e->critics.empty()) critic_free(e->critics.back());
     if (!e->allocs.empty() || !e->prof_events.empty()) {  // a handle that never reached the device owns nothing there
         (void) hipSetDevice(e->device);
         (void) hipDeviceSynchronize();
@@ -4796,6 +4801,355 @@ int chub_policy_grad_device(chub_policy_grad *g, const chub_policy_grad_in *in, 
     m.G = pol->G;
     m.backward = a.backward;
     launch_policy_grad(a, m, m.blocks, gp.lds_rows, gp.in_registers != 0, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+// ---- a critic on the device (include/chub.h): the plan, the object, the calls.  The kernels are chub_critic.hip's; the weight layout, the
+// re-layout launch, the fit rule and the workgroup rule are the actor's and its gradient's (GradPlan above, the head one tile of 32)
+static_assert((int) CHUB_VLOSS_COUNT == VLOSS_COUNT && (int) CHUB_VLOSS_CLIPPED == VLOSS_CLIPPED, "chub_critic.h restates the CHUB_VLOSS_* enum");
+}  // extern "C"
+
+constexpr int kCriticMaxF = 512;  // the limit of chub_moments
+
+struct chub_critic {
+    chub_env *env;
+    chub_critic_spec spec;
+    int64_t max_rows;
+    GradPlan gp;
+    int32_t max_blocks;
+    int32_t in_dim[kPolicyMaxLayers], k_pad[kPolicyMaxLayers];
+    float *d_w[kPolicyMaxLayers], *d_b[kPolicyMaxLayers];  // the layers in the kernel's layout (never move)
+    float *d_norm;                          // mean [F] | inv_std [F]
+    float *d_stage;                         // the host form of set_weights: W | b of the largest layer, in the trainer's layout
+    float *d_wrm, *d_part;                  // the row-major copies of layers 1.., the workgroups' f32 partials
+    double *d_part64;
+    std::vector<void *> allocs;
+};
+
+static int critic_check_spec(const chub_critic_spec *sp) {
+    if (sp->F < 1 || sp->F > kCriticMaxF) return fail(CHUB_ERR_ARG, "F: 1 .. " + std::to_string(kCriticMaxF) + " floats per row");
+    if (sp->n_layers < 1 || sp->n_layers > kPolicyMaxLayers) return fail(CHUB_ERR_ARG, "n_layers: 1 .. 4");
+    for (int l = 0; l + 1 < sp->n_layers; l++)
+        if (sp->width[l] < 1 || sp->width[l] > kPolicyMaxHidden) return fail(CHUB_ERR_ARG, "width[" + std::to_string(l) + "]: hidden widths are 1 .. 256");
+    if (sp->width[sp->n_layers - 1] != 1) return fail(CHUB_ERR_ARG, "width[n_layers - 1] must be 1: the critic's head is one linear output");
+    if (sp->hidden_act < 0 || sp->hidden_act >= CHUB_PACT_COUNT) return fail(CHUB_ERR_ARG, "hidden_act: CHUB_PACT_TANH or CHUB_PACT_RELU");
+    if (sp->normalize != 0 && sp->normalize != 1) return fail(CHUB_ERR_ARG, "normalize: 0 or 1");
+    if (sp->normalize && !(sp->clip > 0.0f)) return fail(CHUB_ERR_ARG, "clip must be > 0 with normalize");
+    return CHUB_OK;
+}
+
+// the gradient's plan for the critic's layers: grad_plan reads n_layers, width and F only
+static int critic_plan(const chub_critic_spec *sp, GradPlan &gp) {
+    if (const int rc = critic_check_spec(sp)) return rc;
+    chub_policy_spec ps;
+    memset(&ps, 0, sizeof ps);
+    ps.n_layers = sp->n_layers;
+    for (int l = 0; l < sp->n_layers; l++) ps.width[l] = sp->width[l];
+    PolicyShape shape;
+    memset(&shape, 0, sizeof shape);
+    shape.F = sp->F;
+    if (grad_plan(&ps, shape, gp) != CHUB_OK)  // (its only refusal is the fit rule; said here in the critic's words)
+        return fail(CHUB_ERR_UNSUPPORTED, "the critic keeps its rows, every hidden layer and two delta images in LDS: " + std::to_string(gp.lds_rows) +
+                                              " rows of " + std::to_string(kGradRowStride) + " floats, at most " +
+                                              std::to_string(kGradLdsBytes / (kGradRowStride * (int) sizeof(float))) + " (160 KiB)");
+    return CHUB_OK;
+}
+
+extern "C" {
+
+static void critic_free(chub_critic *c) {
+    chub_env *e = c->env;
+    (void) hipSetDevice(e->device);
+    (void) hipDeviceSynchronize();  // (a launch still in flight reads the weights and writes the partials)
+    for (void *p : c->allocs) (void) hipFree(p);
+    e->critics.erase(std::remove(e->critics.begin(), e->critics.end(), c), e->critics.end());
+    delete c;
+}
+
+static int critic_alloc_bytes(chub_critic *c, void **p, size_t bytes) {
+    void *d = nullptr;
+    if (!bytes) bytes = 4;
+    if (hipMalloc(&d, bytes) != hipSuccess) return fail(CHUB_ERR_HIP, "chub_critic_create: out of device memory");
+    c->allocs.push_back(d);
+    if (hipMemset(d, 0, bytes) != hipSuccess) return fail(CHUB_ERR_HIP, "chub_critic_create: hipMemset failed");
+    *p = d;
+    return CHUB_OK;
+}
+#define critic_alloc(c, p, count) critic_alloc_bytes((c), (void **) (p), (size_t) (count) * sizeof(**(p)))
+
+static int critic_upload(chub_critic *c, int l, const float *W, const float *b) {
+    const size_t nw = (size_t) c->spec.width[l] * (size_t) c->in_dim[l], nb = (size_t) c->spec.width[l];
+    HIP_TRY(hipDeviceSynchronize());  // (the staging buffer is one; nothing may still be reading the layer either)
+    HIP_TRY(hipMemcpy(c->d_stage, W, nw * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d_stage + nw, b, nb * sizeof(float), hipMemcpyHostToDevice));
+    launch_policy_relayout(c->d_stage, c->d_stage + nw, c->d_w[l], c->d_b[l], c->spec.width[l], c->in_dim[l], c->k_pad[l], c->gp.ot[l], nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    return CHUB_OK;
+}
+
+int chub_critic_plan(const chub_critic_spec *spec, int64_t R, chub_critic_plan_out *out) {
+    if (!spec || !out) return fail(CHUB_ERR_ARG, "null argument");
+    if (R < 1) return fail(CHUB_ERR_ARG, "chub_critic_plan: R is at least 1");
+    GradPlan gp;
+    if (const int rc = critic_plan(spec, gp)) return rc;
+    out->n_params = gp.n_params;
+    out->workgroups = grad_blocks(gp, R);
+    out->lds_rows = gp.lds_rows;
+    out->lds_bytes = gp.lds_rows * kGradRowStride * (int32_t) sizeof(float);
+    out->in_registers = gp.in_registers;
+    out->workspace_bytes = (int64_t) ((size_t) gp.wrm_floats * sizeof(float) +
+                                      (size_t) out->workgroups * ((size_t) gp.part_floats * sizeof(float) + kCriticStats * sizeof(double)));
+    return CHUB_OK;
+}
+
+int chub_critic_create(chub_env *e, const chub_critic_spec *spec, const float *const *W, const float *const *b, const float *mean,
+                       const float *inv_std, int64_t max_rows, chub_critic **out) {
+    if (!e || !spec || !W || !b || !out) return fail(CHUB_ERR_ARG, "null argument");
+    *out = nullptr;
+    GradPlan gp;
+    if (const int rc = critic_plan(spec, gp)) return rc;
+    for (int l = 0; l < spec->n_layers; l++)
+        if (!W[l] || !b[l]) return fail(CHUB_ERR_ARG, "null argument");
+    if (spec->normalize && (!mean || !inv_std)) return fail(CHUB_ERR_ARG, "normalize needs mean and inv_std");
+    if (max_rows < 1) return fail(CHUB_ERR_ARG, "chub_critic_create: max_rows is at least 1");
+    if (e->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_critic_create between chub_graph_begin and chub_graph_end (it allocates and synchronises)");
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    if (critic_prepare() != 0) {
+        (void) hipGetLastError();
+        return fail(CHUB_ERR_HIP, "chub_critic_create: the critic kernel's LDS limit could not be raised");
+    }
+    chub_critic *c = new chub_critic();
+    c->env = e;
+    c->spec = *spec;
+    c->max_rows = max_rows;
+    c->gp = gp;
+    c->max_blocks = grad_blocks(gp, max_rows);
+    e->critics.push_back(c);
+    int rc = CHUB_OK;
+    size_t stage = 0;
+    for (int l = 0; l < spec->n_layers && !rc; l++) {
+        const int in = gp.in[l], width = spec->width[l];
+        c->in_dim[l] = in;
+        c->k_pad[l] = (in + 1) & ~1;
+        stage = std::max(stage, (size_t) width * (size_t) in + (size_t) width);
+        rc = critic_alloc(c, &c->d_w[l], (size_t) gp.ot[l] * (size_t) c->k_pad[l] * kPolicyOutTile);
+        if (!rc) rc = critic_alloc(c, &c->d_b[l], (size_t) gp.ot[l] * kPolicyOutTile);
+    }
+    if (!rc) rc = critic_alloc(c, &c->d_stage, stage);
+    if (!rc) rc = critic_alloc(c, &c->d_norm, 2 * (size_t) spec->F);
+    if (!rc) rc = critic_alloc(c, &c->d_wrm, (size_t) std::max<int64_t>(gp.wrm_floats, 1));
+    if (!rc) rc = critic_alloc(c, &c->d_part, (size_t) c->max_blocks * (size_t) gp.part_floats);
+    if (!rc) rc = critic_alloc(c, &c->d_part64, (size_t) c->max_blocks * kCriticStats);
+    if (!rc && spec->normalize) {
+        if (hipMemcpy(c->d_norm, mean, (size_t) spec->F * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(c->d_norm + spec->F, inv_std, (size_t) spec->F * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+            rc = fail(CHUB_ERR_HIP, "chub_critic_create: mean / inv_std could not be copied to the device");
+    }
+    for (int l = 0; l < spec->n_layers && !rc; l++) rc = critic_upload(c, l, W[l], b[l]);
+    if (rc) {
+        const std::string msg = g_err;
+        critic_free(c);
+        (void) hipGetLastError();
+        return fail(rc, msg);
+    }
+    *out = c;
+    return CHUB_OK;
+}
+
+int chub_critic_destroy(chub_critic *c) {
+    if (!c) return CHUB_OK;
+    if (c->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_critic_destroy between chub_graph_begin and chub_graph_end (it synchronises and frees)");
+    critic_free(c);
+    (void) hipGetLastError();
+    return CHUB_OK;
+}
+
+int chub_critic_set_weights(chub_critic *c, int32_t layer, const float *W, const float *b) {
+    if (!c || !W || !b) return fail(CHUB_ERR_ARG, "null argument");
+    if (layer < 0 || layer >= c->spec.n_layers) return fail(CHUB_ERR_ARG, "layer: 0 .. n_layers - 1");
+    if (c->env->capturing)
+        return fail(CHUB_ERR_UNSUPPORTED, "chub_critic_set_weights between chub_graph_begin and chub_graph_end (it copies and synchronises: use "
+                                          "chub_critic_set_weights_device)");
+    HIP_TRY(hipSetDevice(c->env->device));
+    (void) hipGetLastError();
+    return critic_upload(c, layer, W, b);
+}
+
+int chub_critic_set_weights_device(chub_critic *c, int32_t layer, const float *d_W, const float *d_b, void *stream) {
+    if (!c || !d_W || !d_b) return fail(CHUB_ERR_ARG, "null argument");
+    if (layer < 0 || layer >= c->spec.n_layers) return fail(CHUB_ERR_ARG, "layer: 0 .. n_layers - 1");
+    HIP_TRY(hipSetDevice(c->env->device));
+    (void) hipGetLastError();
+    launch_policy_relayout(d_W, d_b, c->d_w[layer], c->d_b[layer], c->spec.width[layer], c->in_dim[layer], c->k_pad[layer], c->gp.ot[layer],
+                           (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+static int critic_needs_normalizer(const chub_critic *c, const char *who) {
+    if (!c->spec.normalize) return fail(CHUB_ERR_ARG, std::string(who) + ": the critic was created with normalize = 0 (its kernel reads no normaliser)");
+    return CHUB_OK;
+}
+
+int chub_critic_set_normalizer(chub_critic *c, const float *mean, const float *inv_std) {
+    if (!c || !mean || !inv_std) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = critic_needs_normalizer(c, "chub_critic_set_normalizer")) return rc;
+    if (c->env->capturing)
+        return fail(CHUB_ERR_UNSUPPORTED, "chub_critic_set_normalizer between chub_graph_begin and chub_graph_end (it copies and synchronises: use "
+                                          "chub_critic_set_normalizer_device)");
+    HIP_TRY(hipSetDevice(c->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipDeviceSynchronize());  // (a critic launch in flight reads the buffer)
+    HIP_TRY(hipMemcpy(c->d_norm, mean, (size_t) c->spec.F * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d_norm + c->spec.F, inv_std, (size_t) c->spec.F * sizeof(float), hipMemcpyHostToDevice));
+    return CHUB_OK;
+}
+
+int chub_critic_set_normalizer_device(chub_critic *c, const float *d_mean, const float *d_inv_std, void *stream) {
+    if (!c || !d_mean || !d_inv_std) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = critic_needs_normalizer(c, "chub_critic_set_normalizer_device")) return rc;
+    HIP_TRY(hipSetDevice(c->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipMemcpyAsync(c->d_norm, d_mean, (size_t) c->spec.F * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
+    HIP_TRY(hipMemcpyAsync(c->d_norm + c->spec.F, d_inv_std, (size_t) c->spec.F * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
+    return CHUB_OK;
+}
+
+int chub_critic_normalizer_from_moments_device(chub_critic *c, chub_moments *m, double eps, void *stream) {
+    if (!c || !m) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = critic_needs_normalizer(c, "chub_critic_normalizer_from_moments_device")) return rc;
+    if (m->env != c->env) return fail(CHUB_ERR_ARG, "chub_critic_normalizer_from_moments_device: the critic and the moments were made for different handles");
+    if (m->F != c->spec.F)
+        return fail(CHUB_ERR_ARG, "chub_critic_normalizer_from_moments_device: the moments have F = " + std::to_string(m->F) + ", the critic's rows " +
+                                      std::to_string(c->spec.F));
+    if (!(eps > 0.0) || !std::isfinite(eps)) return fail(CHUB_ERR_ARG, "chub_critic_normalizer_from_moments_device: eps is finite and > 0");
+    HIP_TRY(hipSetDevice(c->env->device));
+    (void) hipGetLastError();
+    launch_normalizer_from_moments(m->d_state, c->spec.F, eps, c->d_norm, c->d_norm + c->spec.F, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+// what every critic call asks of its rows
+static int critic_check_rows(const chub_critic *c, const char *who, const float *d_x, int64_t ld, int64_t n_rows, const int64_t *d_rows, int64_t R) {
+    if (!d_x) return fail(CHUB_ERR_ARG, "null argument");
+    if (R <= 0 || R > c->max_rows) return fail(CHUB_ERR_ARG, std::string(who) + ": R is 1 .. max_rows = " + std::to_string(c->max_rows));
+    if (n_rows < 1) return fail(CHUB_ERR_ARG, std::string(who) + ": n_rows, the rows the arrays hold, is at least 1");
+    if (!d_rows && R > n_rows) return fail(CHUB_ERR_ARG, std::string(who) + ": without d_rows the call reads rows 0 .. R - 1: R <= n_rows");
+    if (ld < c->spec.F) return fail(CHUB_ERR_ARG, "ld: at least the row's " + std::to_string(c->spec.F) + " floats");
+    return CHUB_OK;
+}
+
+static void critic_args(const chub_critic *c, CriticArgs &a) {
+    const GradPlan &gp = c->gp;
+    memset(&a, 0, sizeof a);
+    a.mean = c->d_norm;
+    a.inv_std = c->d_norm + c->spec.F;
+    a.part = c->d_part;
+    a.part64 = c->d_part64;
+    a.clip = c->spec.clip;
+    a.n_layers = c->spec.n_layers;
+    a.F = c->spec.F;
+    a.x_rows = gp.x_rows;
+    a.d_row0[0] = gp.d_row0[0];
+    a.d_row0[1] = gp.d_row0[1];
+    a.s_row0 = gp.s_row0;
+    a.hidden_act = c->spec.hidden_act;
+    a.normalize = c->spec.normalize;
+    a.n_pairs = gp.n_pairs;
+    a.part_floats = gp.part_floats;
+    a.bias_floats = gp.bias_floats;
+    for (int l = 0; l < c->spec.n_layers; l++) {
+        GradLayer &L = a.layer[l];
+        L.w = c->d_w[l];
+        L.b = c->d_b[l];
+        L.wrm = l ? c->d_wrm + gp.wrm_off[l] : nullptr;
+        L.k_pad = c->k_pad[l];
+        L.in = gp.in[l];
+        L.out = c->spec.width[l];
+        L.ot = gp.ot[l];
+        L.it = gp.it[l];
+        L.h_row0 = gp.h_row0[l];
+        L.pair0 = gp.pair0[l];
+        L.bias0 = gp.bias0[l];
+    }
+}
+
+int chub_critic_values_device(chub_critic *c, const float *d_x, int64_t ld, int64_t n_rows, const int64_t *d_rows, int64_t R, float *d_values,
+                              void *stream) {
+    if (!c || !d_values) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = critic_check_rows(c, "chub_critic_values_device", d_x, ld, n_rows, d_rows, R)) return rc;
+    HIP_TRY(hipSetDevice(c->env->device));
+    (void) hipGetLastError();
+    CriticArgs a;
+    critic_args(c, a);
+    a.R = R;
+    a.rows_total = n_rows;
+    a.rows = d_rows;
+    a.x = d_x;
+    a.ld = ld;
+    a.values = d_values;
+    // (no partials to merge: as many workgroups as the tiles give, up to what 256 CUs hold of the 13-64-64-1 form, four each)
+    const int64_t tiles = (R + 31) / 32;
+    launch_critic_values(a, (int) std::min<int64_t>((tiles + 7) & ~(int64_t) 7, kCriticValueBlocks), c->gp.lds_rows, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_critic_grad_device(chub_critic *c, const chub_critic_grad_in *in, const chub_critic_grad_out *out, void *stream) {
+    if (!c || !in || !out) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = critic_check_rows(c, "chub_critic_grad_device", in->d_x, in->ld, in->n_rows, in->d_rows, in->R)) return rc;
+    if (!in->d_ret) return fail(CHUB_ERR_ARG, "null argument");
+    if (in->loss != CHUB_VLOSS_MSE && in->loss != CHUB_VLOSS_CLIPPED) return fail(CHUB_ERR_ARG, "loss: CHUB_VLOSS_MSE or CHUB_VLOSS_CLIPPED");
+    if (in->loss == CHUB_VLOSS_CLIPPED) {
+        if (!(in->clip_eps > 0.0f) || !std::isfinite(in->clip_eps)) return fail(CHUB_ERR_ARG, "clip_eps: finite and > 0 under CHUB_VLOSS_CLIPPED");
+        if (!in->d_v_old) return fail(CHUB_ERR_ARG, "null argument");
+    }
+    HIP_TRY(hipSetDevice(c->env->device));
+    (void) hipGetLastError();
+    const GradPlan &gp = c->gp;
+    const int nl = c->spec.n_layers;
+    CriticArgs a;
+    critic_args(c, a);
+    CriticMergeArgs m;
+    memset(&m, 0, sizeof m);
+    bool backward = false;
+    for (int l = 0; l < nl; l++) backward |= out->d_gW[l] != nullptr || out->d_gb[l] != nullptr;
+    a.R = in->R;
+    a.rows_total = in->n_rows;
+    a.rows = in->d_rows;
+    a.x = in->d_x;
+    a.ld = in->ld;
+    a.ret = in->d_ret;
+    a.v_old = in->d_v_old;
+    a.values = out->d_values;
+    a.clip_eps = in->clip_eps;
+    a.loss = in->loss;
+    a.stats = 1;
+    a.backward = backward ? 1 : 0;
+    for (int l = 0; l < nl; l++) {
+        m.gW[l] = out->d_gW[l];
+        m.gb[l] = out->d_gb[l];
+        m.in[l] = gp.in[l];
+        m.it[l] = gp.it[l];
+        m.pair0[l] = gp.pair0[l];
+        m.bias0[l] = gp.bias0[l];
+        m.param0[l] = gp.param0[l];
+    }
+    m.param0[nl] = gp.param0[nl];
+    m.part = c->d_part;
+    m.part64 = c->d_part64;
+    m.stats = out->d_stats;
+    m.R = in->R;
+    m.n_layers = nl;
+    m.blocks = grad_blocks(gp, in->R);
+    m.part_floats = gp.part_floats;
+    m.bias_base = gp.n_pairs * 1024;
+    m.backward = a.backward;
+    launch_critic_grad(a, m, m.blocks, gp.lds_rows, gp.in_registers != 0, (hipStream_t) stream);
     HIP_TRY(hipGetLastError());
     return CHUB_OK;
 }

@@ -570,6 +570,173 @@ class DevicePolicyGrad(object):
             pass
 
 
+class DeviceCritic(object):
+    """A value network on the device (chub_critic_*, include/chub.h "a critic on the device"): made by VecChargingHub.make_critic.  It
+    reads rows of F floats the caller points at (a rollout's features, observation blocks); values_device is the forward alone,
+    grad_device the value loss and its gradient through the critic's LIVE weights and normaliser in the trainer's layout.  The actor's
+    numerics, the same bits every call, no autograd."""
+
+    def __init__(self, env, layers, hidden_act="tanh", normalize=None, max_rows=None):
+        self._env = env
+        self._lib = env._lib
+        layers = [(np.ascontiguousarray(W, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32).ravel()) for W, b in layers]
+        if not layers or any(W.ndim != 2 for W, _ in layers):
+            raise ValueError("layers: a list of (W [out, in], b [out])")
+        mean = inv_std = None
+        clip = 0.0
+        if normalize is not None:
+            mean, inv_std, clip = normalize
+            mean = np.ascontiguousarray(mean, dtype=np.float32).ravel()
+            inv_std = np.ascontiguousarray(inv_std, dtype=np.float32).ravel()
+        self.n_features = int(layers[0][0].shape[1])
+        self.max_rows = int(env.n_envs if max_rows is None else max_rows)
+        self.spec = _lib.critic_spec(self.n_features, [W.shape[0] for W, _ in layers], hidden_act, normalize is not None, clip)
+        fan_in = self.n_features
+        for l, (W, b) in enumerate(layers):  # (the library sees pointers only: the shapes are checked here)
+            if W.shape[1] != fan_in or b.shape != (W.shape[0],):
+                raise ValueError("layer %d: W must have %d columns and b %d entries, got %s and %s" % (l, fan_in, W.shape[0], W.shape, b.shape))
+            fan_in = W.shape[0]
+        if normalize is not None and (mean.shape != (self.n_features,) or inv_std.shape != (self.n_features,)):
+            raise ValueError("normalize: mean and inv_std must have %d entries (the row)" % self.n_features)
+        self.layer_shapes = [W.shape for W, _ in layers]
+        self.n_params = sum(o * (i + 1) for o, i in self.layer_shapes)
+        n = len(layers)
+        Wp = (C.c_void_p * n)(*[W.ctypes.data for W, _ in layers])
+        bp = (C.c_void_p * n)(*[b.ctypes.data for _, b in layers])
+        h = C.c_void_p()
+        check(self._lib.chub_critic_create(env._h, C.byref(self.spec), Wp, bp, _ptr(mean), _ptr(inv_std), self.max_rows, C.byref(h)))
+        self._c = h
+
+    def plan(self, R=None):
+        """chub_critic_plan for a call of R rows (default max_rows) -> dict(n_params, workspace_bytes, workgroups, lds_rows, lds_bytes,
+        in_registers); host arithmetic only"""
+        out = _lib.ChubCriticPlanOut()
+        check(self._lib.chub_critic_plan(C.byref(self.spec), int(self.max_rows if R is None else R), C.byref(out)))
+        return {name: int(getattr(out, name)) for name, _ in out._fields_}
+
+    def values_device(self, R, n_rows, d_x, d_values, d_rows=0, ld=None, stream=0):
+        """the forward alone on `stream` (chub_critic_values_device): d_x holds n_rows rows of F floats with row stride ld floats (default
+        F), d_rows [R] int64 picks them (0: rows 0 .. R - 1), V goes to d_values [R] f32 at position r.  One launch, no synchronisation;
+        recordable into a graph."""
+        check(self._lib.chub_critic_values_device(self._c, d_x or None, self.n_features if ld is None else int(ld), int(n_rows), d_rows or None, int(R),
+                                                  d_values or None, stream or None))
+
+    def grad_device(self, R, n_rows, d_x, d_ret, d_v_old=0, d_rows=0, ld=None, loss="mse", clip_eps=0.2, d_gW=None, d_gb=None, d_values=0, d_stats=0,
+                    stream=0):
+        """one call on `stream` (chub_critic_grad_device): the value loss over rows of d_x against d_ret [n_rows] (and d_v_old [n_rows] under
+        loss="clipped").  Outputs, each optional: d_gW[l] [out, in] / d_gb[l] [out] (device addresses per layer, the trainer's layout),
+        d_values [R], d_stats [6] f64 (rows, loss terms, clipped rows, sum (ret - v)^2, sum ret, sum ret^2).  With no gradient output the
+        call is the forward plus stats.  No synchronisation; recordable into a graph."""
+        a = _lib.ChubCriticGradIn(int(R), int(n_rows), d_rows or None, d_x or None, self.n_features if ld is None else int(ld), d_ret or None,
+                                  d_v_old or None, _lib.value_loss(loss), float(clip_eps))
+        o = _lib.ChubCriticGradOut()
+        for l in range(len(self.layer_shapes)):
+            o.d_gW[l] = (d_gW[l] or None) if d_gW else None
+            o.d_gb[l] = (d_gb[l] or None) if d_gb else None
+        o.d_values, o.d_stats = d_values or None, d_stats or None
+        check(self._lib.chub_critic_grad_device(self._c, C.byref(a), C.byref(o), stream or None))
+
+    def _through_host(self, ins, outs, call):
+        """device memory for named numpy arrays, the inputs copied in, call(addr), the outputs copied back"""
+        e = self._env
+        at, off = 0, {}
+        for name, arr in ins + outs:
+            off[name] = at
+            at += (arr.nbytes + 15) & ~15
+        d = C.c_void_p()
+        check(self._lib.chub_malloc_device(e._device, max(at, 16), C.byref(d)))
+        try:
+            for name, arr in ins:
+                if arr.nbytes:
+                    check(self._lib.chub_copy_to_device(e._device, C.c_void_p(d.value + off[name]), _ptr(arr), arr.nbytes, None))
+            check(self._lib.chub_sync(e._h))
+            call(lambda name: d.value + off[name] if name in off else 0)
+            check(self._lib.chub_sync(e._h))
+            for name, arr in outs:
+                check(self._lib.chub_copy_to_host(e._device, _ptr(arr), C.c_void_p(d.value + off[name]), arr.nbytes, None))
+        finally:
+            self._lib.chub_free_device(e._device, d)
+
+    def values(self, x, rows=None):
+        """values_device through host memory (the convenience form: it allocates, copies and synchronises): x [n_rows, F] -> V [R] f32"""
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, self.n_features)
+        ins = [("x", x)]
+        if rows is not None:
+            ins.append(("rows", np.ascontiguousarray(rows, dtype=np.int64).ravel()))
+        R = len(x) if rows is None else len(ins[1][1])
+        v = np.zeros(R, dtype=np.float32)
+        self._through_host(ins, [("values", v)], lambda addr: self.values_device(R, len(x), addr("x"), addr("values"), addr("rows")))
+        return v
+
+    def grad(self, x, ret, v_old=None, rows=None, loss="mse", clip_eps=0.2, backward=True):
+        """grad_device through host memory -> dict(grads=[(gW, gb), ..] or None, values [R], stats [6])"""
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, self.n_features)
+        n_rows = len(x)
+        ins = [("x", x), ("ret", np.ascontiguousarray(ret, dtype=np.float32).reshape(n_rows))]
+        if v_old is not None:
+            ins.append(("v_old", np.ascontiguousarray(v_old, dtype=np.float32).reshape(n_rows)))
+        if rows is not None:
+            ins.append(("rows", np.ascontiguousarray(rows, dtype=np.int64).ravel()))
+        R = n_rows if rows is None else len(dict(ins)["rows"])
+        flat, v, stats = np.zeros(self.n_params, dtype=np.float32), np.zeros(R, dtype=np.float32), np.zeros(6, dtype=np.float64)
+
+        def call(addr):
+            d_gW, d_gb, p = [], [], addr("grads")
+            for o, i in self.layer_shapes:
+                d_gW.append(p)
+                d_gb.append(p + 4 * o * i)
+                p += 4 * o * (i + 1)
+            self.grad_device(R, n_rows, addr("x"), addr("ret"), addr("v_old"), addr("rows"), None, loss, clip_eps, d_gW if backward else None,
+                             d_gb if backward else None, addr("values"), addr("stats"))
+
+        self._through_host(ins, [("grads", flat), ("values", v), ("stats", stats)], call)
+        grads, p = [], 0
+        for o, i in self.layer_shapes:
+            grads.append((flat[p:p + o * i].reshape(o, i).copy(), flat[p + o * i:p + o * (i + 1)].copy()))
+            p += o * (i + 1)
+        return {"grads": grads if backward else None, "values": v, "stats": stats}
+
+    def set_weights(self, layer, W, b):
+        """new weights of one layer from host arrays, W [out, in] (the nn.Linear layout) and b [out]; synchronises"""
+        W = np.ascontiguousarray(W, dtype=np.float32)
+        b = np.ascontiguousarray(b, dtype=np.float32).ravel()
+        if not 0 <= int(layer) < len(self.layer_shapes) or W.shape != self.layer_shapes[layer] or b.shape != (W.shape[0],):
+            raise ValueError("set_weights: layer %r takes W %s and b (%d,)" % (layer, self.layer_shapes[layer] if 0 <= int(layer) < len(self.layer_shapes) else "?", W.shape[0]))
+        check(self._lib.chub_critic_set_weights(self._c, int(layer), _ptr(W), _ptr(b)))
+
+    def set_weights_device(self, layer, d_W, d_b, stream=0):
+        """the same from device memory in the trainer's layout (e.g. a parameter's data_ptr()), as one re-layout launch on `stream`: a
+        captured graph's next replay evaluates the new weights"""
+        check(self._lib.chub_critic_set_weights_device(self._c, int(layer), d_W or None, d_b or None, stream or None))
+
+    def set_normalizer(self, mean, inv_std):
+        """new mean / inv_std [F] from host arrays; synchronises"""
+        mean = np.ascontiguousarray(mean, dtype=np.float32).ravel()
+        inv_std = np.ascontiguousarray(inv_std, dtype=np.float32).ravel()
+        if mean.shape != (self.n_features,) or inv_std.shape != (self.n_features,):
+            raise ValueError("mean and inv_std must have %d entries (the row)" % self.n_features)
+        check(self._lib.chub_critic_set_normalizer(self._c, _ptr(mean), _ptr(inv_std)))
+
+    def set_normalizer_device(self, d_mean, d_inv_std, stream=0):
+        """the same from device memory, [F] f32 each, as copies on `stream`"""
+        check(self._lib.chub_critic_set_normalizer_device(self._c, d_mean or None, d_inv_std or None, stream or None))
+
+    def normalizer_from_moments(self, m, eps=1e-8, stream=0):
+        """mean = (float) the moments' mean, inv_std = (float) (1 / sqrt(M2 / n + eps)), one launch on `stream`, as the policy's; recordable"""
+        check(self._lib.chub_critic_normalizer_from_moments_device(self._c, m._m, float(eps), stream or None))
+
+    def close(self):
+        if getattr(self, "_c", None) and getattr(self._env, "_h", None):
+            check(self._lib.chub_critic_destroy(self._c))
+        self._c = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DeviceMoments(object):
     """Running count, mean and M2 per feature on the device (chub_moments_*, include/chub.h "running feature statistics"): made by
     VecChargingHub.make_moments.  The state is [1 + 2 F] float64 in device memory (n | mean | M2); update_device adds a batch of rows in
@@ -1207,6 +1374,12 @@ class VecChargingHub(object):
         if policy._env is not self:
             raise ValueError("make_policy_grad: the policy was made for another handle")
         return DevicePolicyGrad(self, policy, max_rows)
+
+    def make_critic(self, layers, hidden_act="tanh", normalize=None, max_rows=None):
+        """a value network bound to this handle -> DeviceCritic (chub_critic_create).  layers: [(W [out, in], b [out]), ...] float32 in the
+        nn.Linear layout, the last with one output; the rows it reads have layers[0][0].shape[1] floats.  normalize: None or (mean [F],
+        inv_std [F], clip), the critic's own.  max_rows: the most rows one call works on (default n_envs; T * n_envs for a rollout)."""
+        return DeviceCritic(self, layers, hidden_act, normalize, max_rows)
 
     def next_tick(self):
         """the Philox tick of this handle's next reset or step (chub_next_tick): the tick a sampled policy call made now draws its noise

@@ -391,7 +391,8 @@ class TorchHubVecEnv(object):
         self.device = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
         if self.device.type == "cuda":
             torch.cuda.set_device(self.device)
-        self.vec = VecChargingHub(n_envs, station_list, station_type_list, seed=seed, rng="philox", device=int(self.device.index or 0),
+        rng = hub_kwargs.pop("rng", "philox")  # ("philox_curves": PHILOX's draws with the charge curves evaluated on the device)
+        self.vec = VecChargingHub(n_envs, station_list, station_type_list, seed=seed, rng=rng, device=int(self.device.index or 0),
                                   **hub_kwargs)
         self.num_envs, self.obs_dim, self.act_dim = self.vec.n_envs, self.vec.obs_dim, self.vec.act_dim
         self._rows = None
@@ -823,6 +824,112 @@ class TorchHubVecEnv(object):
         [T * N]), the forward alone; the next call with the same R overwrites them"""
         _, out = self._policy_grad_call(rollout, None, rows, "coef", 0.0, 0.0, None, False)
         return out
+
+    # ---- a critic on the device (chub_critic_*): values for ``advantages`` and the value loss's gradient with no autograd
+    def load_critic(self, module_or_layers, normalize=None):
+        """A feed-forward value network -> DeviceCritic (VecChargingHub.make_critic), for calls of up to 96 * num_envs rows (a rollout).
+        module_or_layers: what ``load_policy`` accepts -- an ``nn.Sequential`` of ``Linear`` / ``Tanh`` / ``ReLU`` (one activation behind
+        every hidden Linear, nothing behind the last, which has one output), or a list of ``(W, b)`` tensors / arrays in the nn.Linear
+        layout (hidden activation tanh).  Its rows are the feature rows of the actor it is trained beside: ``Linear(F, ..)``.  normalize:
+        None or (mean [F], inv_std [F], clip), the critic's own.  The weights are copied; after an optimiser step
+        ``critic.set_weights_device(l, linear.weight.data_ptr(), linear.bias.data_ptr(), stream)`` brings layer l up to date."""
+        torch = self.torch
+        hidden = None
+        if isinstance(module_or_layers, torch.nn.Module):
+            layers, acts = [], []
+            for m in module_or_layers.children():
+                if isinstance(m, torch.nn.Linear):
+                    if m.bias is None:
+                        raise ValueError("load_critic: every Linear needs a bias")
+                    layers.append((m.weight.detach().to("cpu", torch.float32).numpy(), m.bias.detach().to("cpu", torch.float32).numpy()))
+                    acts.append(None)
+                elif isinstance(m, (torch.nn.Tanh, torch.nn.ReLU)) and layers and acts[-1] is None:
+                    acts[-1] = "tanh" if isinstance(m, torch.nn.Tanh) else "relu"
+                else:
+                    raise ValueError("load_critic: an nn.Sequential of Linear / Tanh / ReLU, not %s here" % type(m).__name__)
+            if not layers:
+                raise ValueError("load_critic: no Linear layer")
+            if len(set(acts[:-1])) > 1 or None in acts[:-1]:
+                raise ValueError("load_critic: one activation, Tanh or ReLU, behind every hidden Linear")
+            if acts[-1] is not None:
+                raise ValueError("load_critic: nothing may follow the last Linear (the value is a linear output)")
+            hidden = acts[0] if len(acts) > 1 else None
+        else:
+            layers = [(W.detach().to("cpu", torch.float32).numpy() if hasattr(W, "detach") else W,
+                       b.detach().to("cpu", torch.float32).numpy() if hasattr(b, "detach") else b) for W, b in module_or_layers]
+        return self.vec.make_critic(layers, hidden_act=hidden or "tanh", normalize=normalize, max_rows=96 * self.num_envs)
+
+    def _critic_rollout(self, critic, rollout, who):
+        policy = getattr(self, "_rollout_policy", {}).get(id(rollout))
+        if policy is None:
+            raise ValueError("rollout: a dict returned by this adapter's collect()")
+        feats = rollout["features"]
+        if critic.n_features != int(feats.shape[2]):
+            raise ValueError("%s: the critic reads rows of %d floats, the rollout's feature rows have %d" % (who, critic.n_features, int(feats.shape[2])))
+        cache = getattr(self, "_critics", None)
+        if cache is None:
+            cache = self._critics = {}
+        ent = cache.get(id(critic))
+        if ent is None:
+            f32 = dict(dtype=self.torch.float32, device=self.device)
+            ent = cache[id(critic)] = {"grads": [(self.torch.zeros((o, i), **f32), self.torch.zeros((o,), **f32)) for o, i in critic.layer_shapes],
+                                       "stats": self.torch.zeros((6,), dtype=self.torch.float64, device=self.device), "values": {}}
+        return policy, feats, ent
+
+    def values(self, critic, rollout):
+        """The critic over a ``collect`` rollout, on torch's current stream (chub_critic_values_device) -> (values [T + 1, N],
+        final_values [N] or None), float32 CUDA tensors ready for ``advantages`` that the next call with the same critic and T
+        overwrites.  values[t], t < T: the critic on ``rollout["features"][t]``, the rows the actor saw, in ONE launch over T * N rows.
+        values[T]: the critic on the feature row of the state NOW -- the last packed block for an actor that reads the observation alone;
+        otherwise the actor's feature launches fill a scratch row first (``sample_device(d_features=...)``, which consumes no tick).
+        final_values: the critic on ``last_obs`` under ``autoreset="per_env"`` with an observation-only actor; otherwise None: an
+        episode's end is worth 0 (the state behind a terminal feature row is gone)."""
+        torch = self.torch
+        policy, feats, ent = self._critic_rollout(critic, rollout, "values")
+        T, N, F, D = int(feats.shape[0]), self.num_envs, critic.n_features, self.obs_dim
+        out = ent["values"].get(T)
+        if out is None:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            out = ent["values"][T] = (torch.zeros((T + 1, N), **f32), torch.zeros((N,), **f32), torch.zeros((N, F), **f32), torch.zeros((N,), **f32))
+        vals, final, scratch, logp = out
+        st = self._stream()
+        critic.values_device(T * N, T * N, feats.data_ptr(), vals.data_ptr(), stream=st)
+        obs_only = all(policy.spec.inputs[i].kind == _lib.PIN["obs"] for i in range(policy.spec.n_inputs))
+        if obs_only:
+            critic.values_device(N, N, rollout["packed"][T - 1].data_ptr(), vals[T].data_ptr(), ld=D + 2, stream=st)
+        else:
+            fresh = self._cur_obs is self._obs0  # (a reset's dense [N, D] block, or the observation columns of the packed block)
+            policy.sample_device(self._obs0.data_ptr() if fresh else self._packed.data_ptr(), D if fresh else D + 2, d_logp=logp.data_ptr(),
+                                 d_features=scratch.data_ptr(), stream=st)
+            critic.values_device(N, N, scratch.data_ptr(), vals[T].data_ptr(), stream=st)
+        if not (self.per_env and obs_only):
+            return vals, None
+        critic.values_device(N, N, self.last_obs.data_ptr(), final.data_ptr(), ld=int(self.last_obs.stride(0)), stream=st)
+        return vals, final
+
+    def value_gradient(self, critic, rollout, ret, rows=None, loss="mse", clip_eps=0.2, v_old=None):
+        """The critic's gradient of the value loss over a ``collect`` rollout, on torch's current stream with no autograd
+        (chub_critic_grad_device): the critic's CURRENT weights and normaliser on ``rollout["features"]``, ret [T, N] float32 CUDA
+        (``advantages``), rows: an int64 CUDA tensor of flat (step, env) indices t * N + n (a minibatch; None: every row), loss "mse" or
+        "clipped" (PPO2's clipped value loss around v_old [T, N], e.g. ``values(...)[0][:T]`` as collected, within clip_eps).  Returns
+        (grads, stats): grads a list of (gW, gb) in ``load_critic``'s layout, stats float64 [6] (rows, sum of loss terms, rows clipped
+        away, sum of (ret - v)^2, sum of ret, sum of ret^2) -- CUDA tensors the next call with the same critic overwrites."""
+        torch = self.torch
+        policy, feats, ent = self._critic_rollout(critic, rollout, "value_gradient")
+        n_rows = int(feats.shape[0]) * int(feats.shape[1])
+        if rows is not None and not (self._on_device(rows) and rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_contiguous()):
+            raise AssertionError("rows must be a contiguous 1-d int64 tensor on %s" % (self.device,))
+        R = n_rows if rows is None else int(rows.numel())
+        per_row = lambda t: self._on_device(t) and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n_rows
+        if not per_row(ret):
+            raise AssertionError("ret must be a contiguous float32 tensor on %s with one entry per (step, env)" % (self.device,))
+        clipped = _lib.value_loss(loss) == _lib.VLOSS["clipped"]
+        if clipped and (v_old is None or not per_row(v_old)):
+            raise AssertionError("v_old must be a contiguous float32 tensor on %s with one entry per (step, env) under loss='clipped'" % (self.device,))
+        critic.grad_device(R, n_rows, feats.data_ptr(), ret.data_ptr(), d_v_old=v_old.data_ptr() if clipped else 0,
+                           d_rows=0 if rows is None else rows.data_ptr(), loss=loss, clip_eps=clip_eps, d_gW=[gW.data_ptr() for gW, _ in ent["grads"]],
+                           d_gb=[gb.data_ptr() for _, gb in ent["grads"]], d_stats=ent["stats"].data_ptr(), stream=self._stream())
+        return ent["grads"], ent["stats"]
 
     # ---- a normaliser that follows the rollouts (chub_moments_*, chub_policy_normalizer_from_moments_device)
     def update_normalizer(self, policy, rollout, moments=None, eps=1e-8, mask=None):

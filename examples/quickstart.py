@@ -10,7 +10,10 @@
 5. on-policy training data: the hub samples from the actor, and keeps actions, log-probabilities and every step's block on the device;
 6. one PPO-shaped iteration on that data: log-probabilities over the piles the step can see, a torch critic, advantages on the device;
 7. one evolution-strategies generation, no backward pass: a population of perturbed actors on one handle, a closed-loop day for all of
-   them at once, member fitness from the episode ledger, the ES gradient from regenerated noise, an SGD step on the centre.
+   them at once, member fitness from the episode ledger, the ES gradient from regenerated noise, an SGD step on the centre;
+8. one PPO epoch with the actor's gradient from the device (a torch critic beside it);
+9. one complete PPO iteration in which torch does nothing but the two optimiser steps: collect -> values -> advantages -> minibatches of
+   the actor's and the critic's gradients from the device -> the stepped weights of both networks straight back.
 """
 import os
 import sys
@@ -292,6 +295,56 @@ def ppo_on_device_gradients(n=4096, steps=64, minibatches=4):
     env.close()
 
 
+def ppo_all_on_device(n=4096, steps=64, minibatches=4):
+    import charginghub_env_amd as chub
+
+    if torch is None:
+        print("9. skipped: torch is not installed")
+        return
+    env = chub.TorchHubVecEnv(n, seed=0, autoreset="per_env", **HUB)
+    D, A = env.obs_dim, env.act_dim
+    net = torch.nn.Sequential(torch.nn.Linear(D, 64), torch.nn.Tanh(), torch.nn.Linear(64, A)).to("cuda")      # hold the weights; never run
+    vnet = torch.nn.Sequential(torch.nn.Linear(D, 64), torch.nn.Tanh(), torch.nn.Linear(64, 1)).to("cuda")
+    a_lin = [m for m in net if isinstance(m, torch.nn.Linear)]
+    c_lin = [m for m in vnet if isinstance(m, torch.nn.Linear)]
+    log_std = torch.full((2,), -0.5, device="cuda")
+    a_opt = torch.optim.Adam([p for m in a_lin for p in (m.weight, m.bias)] + [log_std], lr=3e-4)
+    c_opt = torch.optim.Adam([p for m in c_lin for p in (m.weight, m.bias)], lr=1e-3)
+    policy = env.load_policy(net)
+    policy.set_exploration(key=7, log_std=log_std.cpu().numpy())
+    critic = env.load_critic(vnet)                             # the same nn.Sequential forms; its rows are the actor's feature rows
+    stream = torch.cuda.current_stream().cuda_stream
+    env.reset()
+    ro = env.collect(policy, steps, logp_piles="decidable")
+    values, final = env.values(critic, ro)                     # V over the whole rollout in one launch, V of the state now, V of last_obs
+    adv, ret, adv_stats = env.advantages(ro, values, final, gamma=0.99, lam=0.95, stats=True)
+    v_old = values[:steps].clone()                             # the values as collected: the centre of the clipped value loss
+    clipped = v_clipped = 0.0
+    for rows in torch.randperm(steps * n, device="cuda").chunk(minibatches):
+        rows = rows.contiguous()
+        grads, g_log_std, stats = env.policy_gradient(ro, adv, rows=rows, loss="ppo_clip", clip_eps=0.2, ent_coef=0.01, adv_stats=adv_stats)
+        v_grads, v_stats = env.value_gradient(critic, ro, ret, rows=rows, loss="clipped", clip_eps=0.2, v_old=v_old)
+        for m, (gW, gb) in zip(a_lin, grads):                  # the returned tensors ARE the gradients, in nn.Linear's layout
+            m.weight.grad, m.bias.grad = gW, gb
+        log_std.grad = g_log_std
+        for m, (gW, gb) in zip(c_lin, v_grads):
+            m.weight.grad, m.bias.grad = gW, gb
+        a_opt.step()                                           # torch's whole part of the iteration: these two lines
+        c_opt.step()
+        for l, m in enumerate(a_lin):                          # the stepped weights go straight back, for both networks
+            policy.set_weights_device(l, m.weight.data_ptr(), m.bias.data_ptr(), stream)
+        policy.set_log_std_device(log_std.data_ptr(), stream)
+        for l, m in enumerate(c_lin):
+            critic.set_weights_device(l, m.weight.data_ptr(), m.bias.data_ptr(), stream)
+        clipped, v_clipped = clipped + stats[4] / stats[0], v_clipped + v_stats[2] / v_stats[0]
+    _, st = env.value_gradient(critic, ro, ret)                # explained variance from the call's own sums: 1 - E(ret - v)^2 / Var ret
+    ev = 1.0 - (st[3] / st[0]) / (st[5] / st[0] - (st[4] / st[0]) ** 2).clamp_min(1e-12)
+    print("9. %d envs x %d steps, one PPO iteration with both gradients from the device: clipped away %.3f of the actor's rows and %.3f of "
+          "the critic's, value loss %.4f, explained variance %.3f" % (n, steps, float(clipped) / minibatches, float(v_clipped) / minibatches,
+                                                                     float(st[1] / st[0]), float(ev)))
+    env.close()
+
+
 if __name__ == "__main__":
     single_env()
     batched_host()
@@ -301,3 +354,4 @@ if __name__ == "__main__":
     ppo_iteration()
     es_generation()
     ppo_on_device_gradients()
+    ppo_all_on_device()

@@ -797,8 +797,8 @@ int chub_load_dispatch(chub_env *env, int units, const float *loads, const float
  * set_weights between chub_graph_begin and chub_graph_end; a non-OBS block or the LOADS head on a tape handle (as the feature calls); a
  * feature row and hidden layers that do not fit the kernel's 64 KiB of LDS (F rounded up to 2 and the widest odd hidden layer, plus the
  * widest even hidden layer, each rounded up to 32: at most 512 rows together -- F <= 256 always fits).
- * Out of scope: a critic (values of all recorded observations are one batched call of the trainer's afterwards: it does not belong in the
- * loop), bf16 / f16 weights, recurrent or convolutional actors, the multi-GPU hosts, COMPAT in chub_policy_run_steps. */
+ * Out of scope: a critic IN the loop (values of all recorded observations are one batched call afterwards: "a critic on the device",
+ * below), bf16 / f16 weights, recurrent or convolutional actors, the multi-GPU hosts, COMPAT in chub_policy_run_steps. */
 enum { CHUB_PIN_OBS = 0, CHUB_PIN_PILE_OBS, CHUB_PIN_STATION_PROFILE, CHUB_PIN_FORECAST, CHUB_PIN_COUNT };
 enum { CHUB_PACT_TANH = 0, CHUB_PACT_RELU, CHUB_PACT_COUNT };
 enum { CHUB_PHEAD_PILES = 0, CHUB_PHEAD_LOADS, CHUB_PHEAD_COUNT };
@@ -940,7 +940,7 @@ int chub_policy_collect(chub_env *env, chub_policy *pol, int mode, const chub_ro
  * Refusals, with a message and before any device work.  CHUB_ERR_ARG: null env, d_bits, g, d_packed, d_values or d_adv; null d_set_bits in
  * chub_policy_collect_set; an unknown `which`; which != CHUB_PSET_ALL under CHUB_PHEAD_LOADS; T <= 0; gamma or lambda outside [0, 1] or
  * NaN; everything chub_policy_sample_device and chub_policy_collect refuse.  CHUB_ERR_UNSUPPORTED: tape handles, as for
- * chub_pile_obs_device.  Out of scope: a critic on the device (values are the trainer's one batched call). */
+ * chub_pile_obs_device.  Out of scope: a critic inside these calls (d_values comes from "a critic on the device", below, or from the trainer). */
 enum { CHUB_PSET_ALL = 0, CHUB_PSET_OCCUPIED, CHUB_PSET_DECIDABLE, CHUB_PSET_COUNT };
 int chub_pile_set_device(chub_env *env, int which, const uint8_t *d_mask, uint64_t *d_bits /* [N][W] */, void *stream);
 int chub_policy_sample_set_device(chub_env *env, chub_policy *pol, const float *d_obs, int64_t ld_obs, const uint8_t *d_mask, int which,
@@ -1139,7 +1139,7 @@ int chub_population_es_gradient_device(chub_population *pop, const float *d_util
  *     (PILES) or d_logp_old (PPO_CLIP); R <= 0, R > max_rows, n_rows < 1, ld_features < F; an unknown loss; eps outside (0, 1) under
  *     PPO_CLIP; ent_coef not finite; d_set_bits under LOADS; a policy without chub_policy_set_exploration (no log_std); max_rows < 1.
  *     CHUB_ERR_UNSUPPORTED: the fit rule; create / destroy between chub_graph_begin and chub_graph_end.
- * Out of scope: a value loss or a critic on the device (the critic trains on `ret`, its own small regression, with the trainer), an
+ * Out of scope: the value loss (the critic trains on `ret` through "a critic on the device", below: chub_critic_grad_device), an
  *     optimiser (Adam stays with the trainer or host), gradients with respect to the normaliser or through the tanh squash, bf16 weights,
  *     populations, the multi-GPU hosts (an all-reduce of the returned gradients is the trainer's), COMPAT rollouts. */
 enum { CHUB_PLOSS_COEF = 0, CHUB_PLOSS_PPO_CLIP, CHUB_PLOSS_COUNT };
@@ -1170,6 +1170,108 @@ int chub_policy_grad_plan(const chub_config *cfg, const chub_policy_spec *spec, 
 int chub_policy_grad_create(chub_policy *pol, int64_t max_rows, chub_policy_grad **out);
 int chub_policy_grad_destroy(chub_policy_grad *g);
 int chub_policy_grad_device(chub_policy_grad *g, const chub_policy_grad_in *in, const chub_policy_grad_out *out, void *stream);
+
+/* ---- a critic on the device: values, value loss and its gradient -----------------------------------------------------------------------
+ * The value function of a policy-gradient update: V over rows of a collected rollout (what chub_rollout_gae_device takes as d_values) and
+ * the gradient of a regression on `ret` with respect to the critic's weights.  A chub_critic is a feed-forward network over rows of F
+ * floats with ONE linear output; it is bound to a handle as a policy is, destroyed by chub_destroy before the handle, and allocated
+ * outside the arena: chub_state_size and snapshots are unchanged.
+ *   Spec.  1 .. 4 layers, hidden widths 1 .. 256, width[n_layers - 1] = 1, F = 1 .. 512 (the limit of chub_moments), hidden_act one of
+ *     CHUB_PACT_*.  The critic has no input blocks of its own: it reads rows the caller points at -- d_x with row stride ld >= F floats,
+ *     n_rows rows, and optionally d_rows [R] int64 picking them, exactly as chub_policy_grad_in does (an index outside 0 .. n_rows - 1 is
+ *     skipped: it adds to nothing, is not counted, and its value is written as 0; a repeated index counts as often as it is named).  The
+ *     rows it is meant for are a rollout's d_features [T][N][F], the raw rows the actor saw at each step; for an OBS-only actor they are
+ *     also d_obs0, the packed blocks (ld = D + 2) and d_final_obs.
+ *   Normaliser.  With normalize the critic has its own mean / inv_std [F], applied exactly as the actor applies its own:
+ *     x = clamp((row - mean) * inv_std, -clip, clip), f32 subtraction, f32 product, clamp.  chub_critic_set_normalizer (host memory; it
+ *     synchronises), chub_critic_set_normalizer_device (device memory, on `stream`) and chub_critic_normalizer_from_moments_device (from
+ *     a chub_moments of the same handle and F, as chub_policy_normalizer_from_moments_device) mirror the policy's three calls.
+ *   Forward.  The actor's numerics contract: every product is rounded once, accumulation is in f32 from the bias in ascending input
+ *     order on v_mfma_f32_32x32x2_f32, tanh is the device library's tanhf, relu is exact.  The head is a linear output v with no squash.
+ *     Two calls on the same inputs give identical bits whatever R, d_rows or a row's place in the call, and the value the forward-only
+ *     call writes and the v inside a gradient call are the same bits.  A PILES / CHUB_PSQ_CLIP actor whose hidden layers are the critic's
+ *     and whose head row S is the critic's head row forms the same bits in d_tail[.][0] wherever |v| < 1.
+ *   Weights.  chub_critic_set_weights is the host form (it copies and synchronises); chub_critic_set_weights_device takes W [out][in] and
+ *     b [out] in device memory in the trainer's layout and runs a re-layout launch on `stream` (recordable).  The buffers the kernel
+ *     reads never move.
+ *   chub_critic_values_device is the forward alone: V of rows d_rows[0 .. R - 1] (NULL: rows 0 .. R - 1) into d_values [R], at position r
+ *     of the call.  One launch; no backward, no allocation, no synchronisation, no tick; recordable.
+ *   chub_critic_grad_device.  in: R, n_rows, d_rows, d_x, ld, d_ret [n_rows], d_v_old [n_rows] (read under CLIPPED only), loss, clip_eps.
+ *     CHUB_VLOSS_MSE:      L = (1 / R) sum_r 0.5 (v - ret)^2; per row R dL/dv = v - ret, ONE f32 subtraction; the row's loss term in the
+ *                          stats is 0.5 times the f64 square of that f32 difference.
+ *     CHUB_VLOSS_CLIPPED:  PPO2's clipped value loss: d = v - v_old, v_c = v_old + clamp(d, -eps, eps), e1 = (v - ret)^2,
+ *                          e2 = (v_c - ret)^2, each operation rounded once in f32; L = (1 / R) sum_r 0.5 max(e1, e2) (the row's loss term
+ *                          is 0.5 times the f64 value of the f32 maximum).  A row is ACTIVE iff (d > -eps and d < eps) or e1 >= e2; there
+ *                          R dL/dv = v - ret, elsewhere 0.  A d exactly on a bound, or e1 == e2 outside the range, is not defined beyond
+ *                          this predicate.
+ *     Hidden layers pass delta as the actor's gradient does: tanh delta (1 - h^2), relu delta [h > 0].  The normaliser is a constant.
+ *     Products are rounded once and accumulated in f32 on the f32-input MFMA over the rows a workgroup walks (32 rows per chain link, a
+ *     workgroup's tiles in ascending order); 1 / R is applied ONCE, to the f64 sum of the workgroups' f32 partials in workgroup order,
+ *     and the result is rounded once to f32.  No atomics: two calls on the same inputs give identical bits, and the order is a function
+ *     of (R, spec) alone.
+ *     out, each optional: d_gW[l] [out][in] and d_gb[l] [out] in the TRAINER's layout; d_values [R], written at position r; d_stats [6]
+ *     f64: rows counted, sum of the rows' loss terms, rows whose gradient was clipped away (0 under MSE), sum of (ret - v)^2, sum of ret,
+ *     sum of ret^2 (the last three are the ingredients of explained variance), all f64 from the row up.  With every gradient output NULL
+ *     the call is the forward plus stats: no backward.  Launches of one call with a backward, on the caller's stream: a small launch
+ *     that rebuilds zero-padded row-major copies of layers 1.. from the critic's LIVE device weights, the forward/backward launch, the
+ *     merge.  No allocation, no synchronisation, no tick; recordable.  The copies and the partials belong to the critic: its gradient
+ *     calls must be ordered against each other.
+ *   chub_critic_plan: host-only, no device: the parameter count (sum of out * (in + 1)), the workgroups of a call of R rows, the LDS rows
+ *     and bytes, whether the dW tiles stay in registers, and the workspace chub_critic_create allocates for max_rows = R -- or the refusal
+ *     create would give.  The fit rule and the workgroup rule are chub_policy_grad_plan's with the head's single output rounded up to
+ *     one tile of 32: LDS rows = F rounded up to 32 + every hidden width rounded up to 32 + twice the widest layer output rounded up
+ *     to 32 + 16, each row 33 floats, at most 160 KiB; workgroups = ceil(R / 32) rounded up to 8, at most 512, fewer where the partials
+ *     would pass 256 MiB; in registers with at most 16 dW tiles of 32 x 32 over all layers.  13 -> 64 -> 64 -> 1 takes 304 rows.
+ * Refusals, all with a message and before any device work.  CHUB_ERR_ARG: null arguments; F, n_layers or widths out of range; last
+ *     width != 1; an unknown activation or loss; clip <= 0 or NaN with normalize; normalize without mean / inv_std; a normaliser call on a
+ *     critic made with normalize = 0; R <= 0, R > max_rows, n_rows < 1, R > n_rows without d_rows, ld < F; null d_x, or null d_ret in a
+ *     gradient call; null d_v_old or eps <= 0 or not finite under CLIPPED; null d_values in the values call; moments of another handle or
+ *     another F; max_rows < 1.  CHUB_ERR_UNSUPPORTED: the fit rule; create, destroy or a host set_* between chub_graph_begin and
+ *     chub_graph_end.
+ * Out of scope: a trunk shared with the actor, return normalisation, an optimiser, bf16, the multi-GPU hosts, and terminal values for
+ *     feature rows with non-OBS blocks: the state is gone by then, so d_final_values is NULL and an episode's end is worth 0 for such
+ *     critics. */
+enum { CHUB_VLOSS_MSE = 0, CHUB_VLOSS_CLIPPED, CHUB_VLOSS_COUNT };
+typedef struct chub_critic chub_critic;
+typedef struct chub_critic_spec {
+    int32_t F;
+    int32_t n_layers;
+    int32_t width[4];             /* outputs of layer l; width[n_layers - 1] = 1 */
+    int32_t hidden_act;           /* CHUB_PACT_* */
+    int32_t normalize;
+    float clip;
+} chub_critic_spec;
+typedef struct chub_critic_plan_out {
+    int64_t n_params;             /* sum over layers of out * (in + 1) */
+    int64_t workspace_bytes;      /* what chub_critic_create(max_rows = R) allocates beside the weights */
+    int32_t workgroups, lds_rows, lds_bytes, in_registers;
+} chub_critic_plan_out;
+typedef struct chub_critic_grad_in {
+    int64_t R, n_rows;            /* rows of this call; rows the per-row arrays hold */
+    const int64_t *d_rows;        /* [R] or NULL */
+    const float *d_x;             /* [n_rows][F], row stride ld */
+    int64_t ld;
+    const float *d_ret, *d_v_old; /* [n_rows] each; d_v_old is read under CHUB_VLOSS_CLIPPED only */
+    int32_t loss;                 /* CHUB_VLOSS_* */
+    float clip_eps;
+} chub_critic_grad_in;
+typedef struct chub_critic_grad_out {
+    float *d_gW[4], *d_gb[4];
+    float *d_values;              /* [R] */
+    double *d_stats;              /* [6] */
+} chub_critic_grad_out;
+int chub_critic_plan(const chub_critic_spec *spec, int64_t R, chub_critic_plan_out *out);
+int chub_critic_create(chub_env *env, const chub_critic_spec *spec, const float *const *W, const float *const *b, const float *mean,
+                       const float *inv_std, int64_t max_rows, chub_critic **out);
+int chub_critic_destroy(chub_critic *c);
+int chub_critic_set_weights(chub_critic *c, int32_t layer, const float *W, const float *b);
+int chub_critic_set_weights_device(chub_critic *c, int32_t layer, const float *d_W, const float *d_b, void *stream);
+int chub_critic_set_normalizer(chub_critic *c, const float *mean, const float *inv_std);
+int chub_critic_set_normalizer_device(chub_critic *c, const float *d_mean, const float *d_inv_std, void *stream);
+int chub_critic_normalizer_from_moments_device(chub_critic *c, chub_moments *m, double eps, void *stream);
+int chub_critic_values_device(chub_critic *c, const float *d_x, int64_t ld, int64_t n_rows, const int64_t *d_rows /* [R] or NULL */, int64_t R,
+                              float *d_values /* [R] */, void *stream);
+int chub_critic_grad_device(chub_critic *c, const chub_critic_grad_in *in, const chub_critic_grad_out *out, void *stream);
 
 /* The FCEV waiting list is unbounded as in the reference (HYD:264-265): the entries a list that still gets served can
  * hold are kept one by one, and once no prefix of it fits into 15 minutes any more (HYD:270-276: nobody is served again

@@ -21,6 +21,11 @@
                   the algorithmic FLOP of each; with --torch-grad also policy_grad_torch, the same update as torch autograd over the same
                   device memory in the same process (f32 network, wrappers.sampled_logp / sampled_entropy; torch is then imported first).
                   The other sampled and set cases are left out.
+  --critic        the --policy-grad cases and, over the same collected day's feature rows, a 13-64-64-1 critic (the actor's hidden widths):
+                  critic_values us per chub_critic_values_device over the R rows, critic_grad us per chub_critic_grad_device under CLIPPED
+                  with every output, critic_grad_mb4096 the same call over a minibatch of 4096 rows picked by d_rows, and critic_grad_large /
+                  critic_values_large for a 13-256-224-1 critic (dW tiles in the partials, 137 KB of LDS); with --torch-critic also
+                  critic_values_torch and critic_grad_torch, the same two as torch autograd over the same device memory.
 Every case is warmed up, then the cases alternate, ROUNDS times; median, best and worst round are reported with the build id.
 --open-loop-only measures the open loop alone, --launch-only the open loop and the deterministic launch, --no-sets the first five cases:
 with CHUB_LIB=<another build's libchub.so> those are the rates of a build without the newer entry points (the parent commit), on the same
@@ -36,7 +41,7 @@ import time
 
 import numpy as np
 
-if "--torch-gae" in sys.argv or "--torch-grad" in sys.argv:
+if "--torch-gae" in sys.argv or "--torch-grad" in sys.argv or "--torch-critic" in sys.argv:
     import torch  # before libchub is loaded: both must share one HIP runtime
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -59,6 +64,8 @@ def main():
     ap.add_argument("--population", action="store_true", help="the open loop, the launch, the closed loop and the population cases")
     ap.add_argument("--policy-grad", action="store_true", help="the open loop, the launch and the actor-gradient cases")
     ap.add_argument("--torch-grad", action="store_true")
+    ap.add_argument("--critic", action="store_true", help="the actor-gradient cases and the critic's, in one process")
+    ap.add_argument("--torch-critic", action="store_true")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     n_s, piles_s = args.shape.split("x")
@@ -134,8 +141,10 @@ def main():
             cases[("closed_loop", "chub_policy_run_steps", "env_steps_per_s")] = closed_loop
             population_cases(cases, notes, v, pol, sizes, packed, obs0, bits, tail, st, steps, args.calls, between_events)
             args.launch_only = True  # (the sampled and set cases are not part of this run)
-        if args.policy_grad:
-            policy_grad_cases(cases, notes, v, pol, layers, obs0, st, max(1, args.calls // 20), between_events, args.torch_grad)
+        if args.policy_grad or args.critic:
+            roll = policy_grad_cases(cases, notes, v, pol, layers, obs0, st, max(1, args.calls // 20), between_events, args.torch_grad)
+            if args.critic:
+                critic_cases(cases, notes, v, roll, hidden, st, max(1, args.calls // 20), between_events, args.torch_critic)
             args.launch_only = True
         if not args.launch_only:
             cases[("closed_loop", "chub_policy_run_steps", "env_steps_per_s")] = closed_loop
@@ -371,6 +380,108 @@ def policy_grad_cases(cases, notes, v, pol, layers, obs0, st, calls, between_eve
             return e0.elapsed_time(e1) * 1e3 / few
         cases[("policy_grad_torch", "torch autograd over the same memory", "us_per_call")] = torch_grad
         notes["policy_grad_torch"] = dict(rows=R, launches_per_round=few)
+    return roll
+
+
+def critic_cases(cases, notes, v, roll, hidden, st, calls, between_events, with_torch):
+    """the --critic cases: the collected day's raw feature rows as ONE batch, `ret` and `v_old` around the critic's own values"""
+    n, T, stream = v.n_envs, 96, st.ptr
+    R = T * n
+    F = roll["feat"].nbytes // (4 * R)  # (the actor's feature row: the critic reads the same rows)
+    B = multi_gpu.DeviceBuffer
+    buf = dict(values=B(R * 4), ret=B(R * 4), v_old=B(R * 4), stats=B(48), rows=B(4096 * 8))
+    buf["rows"].from_host(np.random.RandomState(5).permutation(R)[:4096].astype(np.int64))
+
+    def make(widths, seed):
+        rs = np.random.RandomState(seed)
+        sizes = [F] + list(widths) + [1]
+        layers = [((rs.normal(size=(o, i)) / np.sqrt(i)).astype(np.float32), (0.1 * rs.normal(size=o)).astype(np.float32)) for i, o in zip(sizes[:-1], sizes[1:])]
+        cr = v.make_critic(layers, max_rows=R)
+        shapes = [W_.shape for W_, _ in layers]
+        return cr, layers, shapes, [B(o * i * 4) for o, i in shapes], [B(o * 4) for o, _ in shapes]
+
+    cr, layers, shapes, gW, gb = make(hidden, 7)
+    # v_old: the critic's values; ret: beside them; then the weights move a little, so that rows fall on both sides of the predicate
+    cr.values_device(R, R, roll["feat"].ptr, buf["v_old"].ptr, stream=stream)
+    st.sync()
+    v0 = buf["v_old"].to_host(np.float32, (R,))
+    buf["ret"].from_host((v0 + 0.5 * np.random.RandomState(8).normal(size=R)).astype(np.float32))
+    rs = np.random.RandomState(9)
+    moved = [((W_ + 0.1 * rs.normal(size=W_.shape) / np.sqrt(W_.shape[1])).astype(np.float32), b_) for W_, b_ in layers]
+    for l, (W_, b_) in enumerate(moved):
+        cr.set_weights(l, W_, b_)
+
+    def values(c, k):
+        def run():
+            def many():
+                for _ in range(k):
+                    c.values_device(R, R, roll["feat"].ptr, buf["values"].ptr, stream=stream)
+            return between_events(many) * 1e3 / k
+        return run
+
+    def grad(c, w, b, k, rows=0, Rc=R):
+        def run():
+            def many():
+                for _ in range(k):
+                    c.grad_device(Rc, R, roll["feat"].ptr, buf["ret"].ptr, buf["v_old"].ptr, rows, None, "clipped", 0.2, [x.ptr for x in w],
+                                  [x.ptr for x in b], buf["values"].ptr, buf["stats"].ptr, stream)
+            return between_events(many) * 1e3 / k
+        return run
+
+    mac = sum(o * i for o, i in shapes)
+    plan = cr.plan()
+    cases[("critic_values", "chub_critic_values_device", "us_per_call")] = values(cr, calls)
+    cases[("critic_grad", "chub_critic_grad_device, CLIPPED, every output", "us_per_call")] = grad(cr, gW, gb, calls)
+    cases[("critic_grad_mb4096", "chub_critic_grad_device, 4096 rows by d_rows", "us_per_call")] = grad(cr, gW, gb, 10 * calls, buf["rows"].ptr, 4096)
+    notes["critic_values"] = dict(rows=R, launches_per_round=calls, flop_per_row=2 * mac, gflop_per_call=round(2 * mac * R / 1e9, 1),
+                                  workgroups=plan["workgroups"], lds_bytes=plan["lds_bytes"])
+    notes["critic_grad"] = dict(rows=R, launches_per_round=calls, flop_per_row=3 * 2 * mac, gflop_per_call=round(3 * 2 * mac * R / 1e9, 1),
+                                workgroups=plan["workgroups"], lds_bytes=plan["lds_bytes"], in_registers=plan["in_registers"])
+    notes["critic_grad_mb4096"] = dict(rows=4096, launches_per_round=10 * calls, workgroups=cr.plan(4096)["workgroups"])
+    big, _, bshapes, bW, bb = make((256, 224), 11)
+    bplan, bmac = big.plan(), sum(o * i for o, i in bshapes)
+    cases[("critic_values_large", "chub_critic_values_device, %d-256-224-1" % F, "us_per_call")] = values(big, 2)
+    cases[("critic_grad_large", "chub_critic_grad_device, %d-256-224-1" % F, "us_per_call")] = grad(big, bW, bb, 2)
+    notes["critic_grad_large"] = dict(rows=R, launches_per_round=2, flop_per_row=3 * 2 * bmac, gflop_per_call=round(3 * 2 * bmac * R / 1e9, 1),
+                                      workgroups=bplan["workgroups"], lds_bytes=bplan["lds_bytes"], in_registers=bplan["in_registers"])
+    notes["critic_values_large"] = dict(rows=R, launches_per_round=2, flop_per_row=2 * bmac, gflop_per_call=round(2 * bmac * R / 1e9, 1))
+    if with_torch:
+        few = max(1, calls // 2)
+        net = torch.nn.Sequential(*[m for k, (o, i) in enumerate(shapes) for m in ([torch.nn.Linear(i, o)] + ([torch.nn.Tanh()] if k < len(shapes) - 1 else []))]).to("cuda")
+        lin = [m for m in net if isinstance(m, torch.nn.Linear)]
+        with torch.no_grad():
+            for m, (W_, b_) in zip(lin, moved):
+                m.weight.copy_(torch.tensor(W_))
+                m.bias.copy_(torch.tensor(b_))
+        feat, ret, v_old = device_view(roll["feat"].ptr, (R, F)), device_view(buf["ret"].ptr, (R,)), device_view(buf["v_old"].ptr, (R,))
+
+        def timed(fn):
+            def run():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(few):
+                    fn()
+                e1.record()
+                e1.synchronize()
+                return e0.elapsed_time(e1) * 1e3 / few
+            return run
+
+        def torch_values():
+            with torch.no_grad():
+                return net(feat)[:, 0]
+
+        def torch_grad():
+            for prm in net.parameters():
+                prm.grad = None
+            val = net(feat)[:, 0]
+            v_c = v_old + torch.clamp(val - v_old, -0.2, 0.2)
+            (0.5 * torch.maximum((val - ret) ** 2, (v_c - ret) ** 2)).mean().backward()
+
+        cases[("critic_values_torch", "torch forward over the same memory", "us_per_call")] = timed(torch_values)
+        cases[("critic_grad_torch", "torch autograd over the same memory", "us_per_call")] = timed(torch_grad)
+        notes["critic_values_torch"] = dict(rows=R, launches_per_round=few)
+        notes["critic_grad_torch"] = dict(rows=R, launches_per_round=few)
 
 
 def torch_gae_case(packed_ptr, gae, n, T, D, calls):
