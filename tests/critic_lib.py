@@ -8,9 +8,11 @@ chain of `out` products, the incoming error through |W|, tanh's factor off by 2 
 |z| <= err_z) and into a parameter (the operands' errors, one rounding per product, 32 rows per MFMA chain and tpw = ceil(tiles /
 workgroups) tiles per workgroup in f32, one rounding after the f64 merge).  All of it over R."""
 import ctypes as C
+import functools
 
 import numpy as np
 
+import grid_pass_lib as gpl
 import policy_lib as pl
 
 F32 = np.float32
@@ -59,16 +61,18 @@ def clipped_parts(v32, v_old, ret, eps):
 
 MISTAKES_MSE = ("row_dropped", "ret_shifted", "no_1_over_R")
 MISTAKES = MISTAKES_MSE + ("clip_ignored", "v_old_ignored")  # (the last two change nothing under MSE: they are asked of the clipped cases)
+TRIP_MISTAKES = ("later_trips_dropped", "last_trip_only")  # whole tiles lost in a workgroup's walk: asked of the cases of more than one trip
 
 
 def mistakes_of(c):
     return MISTAKES if c.loss == "clipped" else MISTAKES_MSE
 
 
-def restate(c, tpw=1, mistake=None):
+def restate(c, tpw=1, mistake=None, blocks=None):
     """-> dict: gW, gb (lists, f64), values [R] f64 (0 at skipped positions), stats [6], coef, active, d, e1, e2 (over the valid rows) and
     the bars bar_W, bar_b, bar_v [R], bar_stats, err_e (the derived error of e1 - e2 per valid row).  tpw: tiles of 32 rows a workgroup
-    walks at most.  mistake: one of MISTAKES (a deliberately wrong restatement; the bars are the right one's)"""
+    walks at most.  mistake: one of MISTAKES or TRIP_MISTAKES (a deliberately wrong restatement; the bars are the right one's); blocks: the
+    call's workgroups, which the TRIP_MISTAKES need"""
     n_rows = len(c.x)
     idx_all = np.arange(n_rows) if c.rows is None else np.asarray(c.rows, dtype=np.int64)
     R = len(idx_all)
@@ -142,6 +146,10 @@ def restate(c, tpw=1, mistake=None):
     if mistake == "row_dropped":  # (the first row from the middle on that has a gradient to lose)
         live = np.flatnonzero(np.roll(delta[:, 0] != 0.0, -(n // 2)))
         delta[(live[0] + n // 2) % n if len(live) else 0] = 0.0
+    if mistake in TRIP_MISTAKES:  # (a workgroup walks the tiles b, b + blocks, ..: only its first tile counts / only its last one)
+        at = np.arange(R)[ok]
+        kept = at // 32 < blocks if mistake == "later_trips_dropped" else gpl.grad_last_trip(R, blocks)[at]
+        delta[~kept] = 0.0
     div = 1.0 if mistake == "no_1_over_R" else float(R)  # (the sum divided by R, as the merge does)
     gam = pl.gamma(32 * int(tpw) + 3)
     gW, gb, bar_W, bar_b = [None] * L, [None] * L, [None] * L, [None] * L
@@ -302,6 +310,51 @@ def gpu_general_cases():
     return out
 
 
+# ---- the cases of more than one trip of k_critic's walk (tests/test_gpu_grad_trips.py): tests/grid_pass_lib.py's R2 and R3
+TRIP_R = (gpl.GRAD_R2, gpl.GRAD_R3)
+TRIP_SHAPES = (
+    (13, (64, 64), "tanh", False, None, None),
+    (13, (33, 31), "relu", False, None, None),
+    (13, (), "tanh", False, None, 15),
+    (45, (33, 17), "tanh", True, "mixed", 47),
+)
+TRIP_WIDE = (64, (256, 224), "tanh", False, None, None)  # dW tiles in the partials; its f64 restatement is the slowest: R2 and MSE only
+
+
+def later_trips_mixed(c):
+    """a "mixed" case's row list with more of the same in the later trips: indices outside the arrays and a repeat in the first tiles of
+    the second (and third) trip and in the partial last tile.  Rows leave or count twice; none is new, so no row comes onto an edge"""
+    rows, n_rows = c.rows.copy(), len(c.x)
+    for t in range(1, (gpl.grad_tiles(c.R) - 1) // gpl.GRAD_MAX_BLOCKS + 1):
+        at = t * gpl.GRAD_MAX_BLOCKS * 32
+        rows[[at + 5, at + 32 + 31]] = [-7, n_rows + 1]
+        rows[at + 9] = rows[at + 8]
+    rows[c.R - 2] = 2 ** 35
+    return c.copy(rows=rows)
+
+
+@functools.lru_cache(maxsize=None)
+def trip_general_cases():
+    """-> [(case, tpw)]: TRIP_SHAPES under both losses at R2 and R3, TRIP_WIDE under MSE at R2; tpw: 2 and 3, from the plan"""
+    out = []
+    for R in TRIP_R:
+        for k, (F, hidden, act, norm, rows, ld) in enumerate(TRIP_SHAPES):
+            for loss in ("mse", "clipped"):
+                c = synthetic_case(F, hidden, act, R - 17 if rows == "mixed" else R, loss, norm, rows, ld, seed=60 + k)
+                out.append(later_trips_mixed(c) if rows == "mixed" else c)
+    F, hidden, act, norm, rows, ld = TRIP_WIDE
+    out.append(synthetic_case(F, hidden, act, gpl.GRAD_R2, "mse", norm, rows, ld, seed=70))
+    assert all(c.R in TRIP_R for c in out)
+    return [(c, tiles_per_workgroup(c)) for c in out]
+
+
+def trip_parts(c, blocks):
+    """the call over R rows cut by trip: -> [case], part t holding, through d_rows, the positions the workgroups meet in their trip t"""
+    base = np.arange(c.R, dtype=np.int64) if c.rows is None else np.asarray(c.rows, dtype=np.int64)
+    trips = -(-gpl.grad_tiles(c.R) // blocks)
+    return [c.copy(rows=base[gpl.grad_trip_positions(c.R, blocks, t)], name="%s-trip%d" % (c.name, t)) for t in range(trips)]
+
+
 # ---- the exact cases: every product and every partial sum exact in f32, so values, gradients and stats equal the restatement BIT FOR BIT
 EXACT_F, EXACT_HIDDEN = 13, (33, 64, 31)
 EXACT_WIDE = (256, 64)  # 8 + 16 + 2 = 26 dW tiles of 32 x 32: more than the 16 a workgroup keeps in registers
@@ -309,7 +362,7 @@ EXACT_R = (1, 31, 32, 33, 95, 300)
 EXACT_EPS = 0.75
 
 
-def exact_case(n_layers, n_rows, loss="mse", hidden=EXACT_HIDDEN, F=EXACT_F):
+def exact_case(n_layers, n_rows, loss="mse", hidden=EXACT_HIDDEN, F=EXACT_F, blocks=None):
     """relu, features multiples of 1/2, weights in {-1, 0, 1} (three per output), integer biases; ret = v + k / 2 and v_old = v + j / 2 with
     small integers k, j, eps = 3/4: d, v_c, e1 and e2 are multiples of 1/16, |v_c - ret| is an odd and |v - ret| an even multiple of 1/4
     outside the range (never e1 == e2), |d| is never eps"""
@@ -329,15 +382,28 @@ def exact_case(n_layers, n_rows, loss="mse", hidden=EXACT_HIDDEN, F=EXACT_F):
              name="exact-%d-%d-%s" % (n_layers, n_rows, loss))
     v = forward64(c)
     c = c.copy(ret=(v + rs.randint(-3, 5, size=n_rows) / 2.0).astype(F32), v_old=(v + rs.randint(-3, 4, size=n_rows) / 2.0).astype(F32))
-    assert_exact(c)
+    assert_exact(c, blocks)
     return c
 
 
-def assert_exact(c):
+def exact_sums(dl, h, blocks, q):
+    """the sums of a dW tile and of a bias: without `blocks` over all rows below 2^23 quanta; with it over each workgroup's own rows
+    (tiles b, b + blocks, ..: the only f32 chain there is) below 2^23 and over all rows below 2^53, which the f64 merge holds exactly"""
+    ad, ah = np.abs(dl), np.abs(h)
+    total = max((ad.T @ ah).max(), ad.sum(axis=0).max()) / q
+    if blocks is None:
+        return total < 2.0 ** 23
+    A, H = gpl.grad_by_workgroup(ad, blocks), gpl.grad_by_workgroup(ah, blocks)
+    own = max(np.matmul(A.transpose(0, 2, 1), H).max(), A.sum(axis=1).max()) / q
+    return own < 2.0 ** 23 and total < 2.0 ** 53
+
+
+def assert_exact(c, blocks=None):
     """every value and every product is a multiple of 2^-4 and every sum of absolute values stays below 2^23 quanta: any partial sum in
-    any order is exact in f32"""
+    any order is exact in f32.  blocks: the call's workgroups -- then the sums over rows are held per workgroup (exact_sums)"""
     q = 2.0 ** -4
     r = restate(c)
+    assert blocks is None or c.rows is None
     h = np.asarray(c.x, dtype=np.float64)
     for l, (W, b) in enumerate(c.layers):
         W, b = np.asarray(W, dtype=np.float64), np.asarray(b, dtype=np.float64)
@@ -355,14 +421,14 @@ def assert_exact(c):
     for l in range(len(c.layers) - 1, -1, -1):
         W = np.asarray(c.layers[l][0], dtype=np.float64)
         assert np.array_equal(dl / q, np.round(dl / q))
-        assert (np.abs(dl).T @ np.abs(r["hs"][l])).max() / q < 2.0 ** 23 and np.abs(dl).sum(axis=0).max() / q < 2.0 ** 23
+        assert exact_sums(dl, r["hs"][l], blocks, q)
         if l > 0:
             assert (np.abs(dl) @ np.abs(W)).max() / q < 2.0 ** 23
             dl = np.where(r["hs"][l] > 0, dl @ W, 0.0)
     return r
 
 
-def exact_expected(c):
+def exact_expected(c, r=None):
     """the bits the device must give: the exact sums in f64, divided by R, rounded once -> (gW, gb, values f32; stats f64)"""
-    r = restate(c)
+    r = r or restate(c)
     return [g.astype(F32) for g in r["gW"]], [g.astype(F32) for g in r["gb"]], r["values"].astype(F32), r["stats"]

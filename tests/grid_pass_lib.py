@@ -1,7 +1,8 @@
 """The cases of tests/test_gpu_grid_pass.py and the arithmetic that says they are the right ones (tests/test_grid_pass_cpu.py): plain Python
 restatements of three pieces of index arithmetic -- the population launch's tile order (k_policy<PolicyPopArgs>), the moments stream's
 launch shape and loop trips (chub_moments_create, chub_moments_update_device, k_moments) and the ES gradient's chunks of pairs
-(chub_population_create).  They choose and check cases; they are never the expected value of a kernel's output: those stay
+(chub_population_create) -- and, for tests/test_gpu_grad_trips.py and tests/test_grad_trips_cpu.py, of a fourth: the gradient kernels'
+workgroups and the tiles each of them walks (grad_blocks, k_policy_grad, k_critic).  They choose and check cases; they are never the expected value of a kernel's output: those stay
 tests/population_lib.py's and tests/normalizer_lib.py's.  No GPU needed."""
 import numpy as np
 
@@ -174,3 +175,73 @@ def es_chunks(P, items):
     chunks = max(1, min(chunks, POP_PARTIAL_BYTES // (items * 32)))
     chunk_pairs = -(-pairs // chunks)
     return chunk_pairs, -(-pairs // chunk_pairs)
+
+
+# ---- the gradient kernels' walk (k_policy_grad, k_critic: chub_runtime.cpp's grad_blocks, the loop `tile = b; tile < n_tiles; tile += blocks`)
+GRAD_TILE = 32                  # rows of one tile of the walk
+GRAD_MAX_BLOCKS = 512           # kGradMaxBlocks
+GRAD_PARTIAL_BYTES = 256 << 20  # kGradPartialBytes
+GRAD_REG_PAIRS = 16             # kGradRegSlots * kGradWaves: dW tiles a workgroup keeps in registers
+GRAD_LDS_ROWS = 160 * 1024 // (33 * 4)  # kGradLdsBytes / (kGradRowStride floats): 1241
+GRAD_SCRATCH_ROWS = 16          # kGradScratchRows
+VALUE_BLOCKS = 1024             # kCriticValueBlocks: workgroups of chub_critic_values_device at most
+GRAD_R2 = 512 * 32 + 2 * 32 + 7      # 16455: 515 tiles, workgroups 0 .. 2 walk two and the rest one; tile 514 has 7 rows
+GRAD_R3 = 2 * 512 * 32 + 3 * 32 + 7  # 32871: 1028 tiles, workgroups 0 .. 3 walk three and the rest two; tile 1027 has 7 rows
+
+
+def grad_tiles(R):
+    return -(-R // GRAD_TILE)
+
+
+def grad_shape(sizes):
+    """grad_plan for layer sizes [F, width 0, ..]: -> (lds_rows, n_pairs, part_floats) -- the feature image, every hidden image, two
+    delta images of the widest layer and the scratch rows; one dW tile per (output tile, input tile); the dW tiles and the bias sums"""
+    up = lambda n: -(-n // 32)
+    ot, it = [up(o) for o in sizes[1:]], [up(i) for i in sizes[:-1]]
+    rows = 32 * it[0] + 32 * sum(ot[:-1]) + 2 * 32 * max(ot) + GRAD_SCRATCH_ROWS
+    pairs = sum(o * i for o, i in zip(ot, it))
+    return rows, pairs, pairs * 1024 + 32 * sum(ot)
+
+
+def grad_blocks(R, part_floats=1):
+    """workgroups of a gradient call of R rows: the tiles rounded up to 8, at most 512, and no more than keep the f32 partials
+    (part_floats a workgroup) within 256 MiB"""
+    nb = min((grad_tiles(R) + 7) & ~7, GRAD_MAX_BLOCKS)
+    return min(nb, max(8, (GRAD_PARTIAL_BYTES // (4 * part_floats)) & ~7))
+
+
+def value_blocks(R):
+    return min((grad_tiles(R) + 7) & ~7, VALUE_BLOCKS)
+
+
+def grad_trips(R, blocks):
+    """int [blocks]: the tiles workgroup b walks (b, b + blocks, ..)"""
+    tiles = grad_tiles(R)
+    return np.array([len(range(b, tiles, blocks)) for b in range(blocks)])
+
+
+def grad_trip_of(R, blocks):
+    """-> (trip [R], workgroup [R]) of every position of the call's row list"""
+    tile = np.arange(R) // GRAD_TILE
+    return tile // blocks, tile % blocks
+
+
+def grad_last_trip(R, blocks):
+    """bool [R]: the positions in the last tile their workgroup walks"""
+    tile = np.arange(R) // GRAD_TILE
+    return tile + blocks >= grad_tiles(R)
+
+
+def grad_trip_positions(R, blocks, trip):
+    """the positions 0 .. R - 1 that the workgroups meet in their trip `trip`, ascending"""
+    return np.flatnonzero(grad_trip_of(R, blocks)[0] == trip).astype(np.int64)
+
+
+def grad_by_workgroup(a, blocks):
+    """a [R, n] over the call's positions -> [blocks, 32 trips, n]: the rows workgroup b meets in its walk, zeros where it walks no tile
+    or the tile ends early"""
+    a = np.asarray(a)
+    trips = -(-grad_tiles(len(a)) // blocks)
+    full = np.zeros((trips * blocks * GRAD_TILE, a.shape[1]), dtype=a.dtype)
+    full[:len(a)] = a
+    return full.reshape(trips, blocks, GRAD_TILE, a.shape[1]).transpose(1, 0, 2, 3).reshape(blocks, trips * GRAD_TILE, a.shape[1])

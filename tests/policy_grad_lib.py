@@ -12,9 +12,11 @@ The bar is derived, not chosen.  policy_lib's forward bound giv
     32 rows per MFMA chain and ceil(tiles / workgroups) tiles per workgroup in f32, one rounding of the f64 merge -- gamma(32 tpw + 3)
     times the f64 matmul of absolute values |d|^T |h|.  All of it over R."""
 import ctypes as C
+import functools
 
 import numpy as np
 
+import grid_pass_lib as gpl
 import policy_lib as pl
 import policy_sample_lib as ps
 
@@ -62,10 +64,10 @@ class Case(object):
         return [W.shape[0] for W, _ in self.layers]
 
 
-def restate(c, tpw=1, mistake=None):
+def restate(c, tpw=1, mistake=None, blocks=None):
     """-> dict: gW, gb (lists, f64), gls [G], logp, ent [R], stats [6], coef [R], ratio [R], active [R], and the bars bar_W, bar_b,
-    bar_ls, bar_logp, bar_ent, bar_stats.  tpw: tiles of 32 rows a workgroup walks at most.  mistake: one of MISTAKES (a deliberately wrong
-    restatement; the bars are the right one's)"""
+    bar_ls, bar_logp, bar_ent, bar_stats.  tpw: tiles of 32 rows a workgroup walks at most.  mistake: one of MISTAKES or TRIP_MISTAKES (a
+    deliberately wrong restatement; the bars are the right one's); blocks: the call's workgroups, which the TRIP_MISTAKES need"""
     idx = np.arange(len(c.features)) if c.rows is None else np.asarray(c.rows, dtype=np.int64)
     R = len(idx)
     x = c.features[idx]
@@ -182,6 +184,9 @@ def restate(c, tpw=1, mistake=None):
         delta[R // 2] = 0.0
         tls = tls.copy()
         tls[R // 2] = 0.0
+    if mistake in TRIP_MISTAKES:  # (a workgroup walks the tiles b, b + blocks, ..: only its first tile counts / only its last one)
+        kept = np.arange(R) // 32 < blocks if mistake == "later_trips_dropped" else gpl.grad_last_trip(R, blocks)
+        delta, tls = np.where(kept[:, None], delta, 0.0), np.where(kept[:, None], tls, 0.0)
     div = 1.0 if mistake == "no_1_over_R" else float(R)  # (the sum divided by R, as the merge does)
     gls = tls.sum(axis=0) / div
     bar_ls = (err_tls.sum(axis=0) * 1.001 + U * np.abs(tls.sum(axis=0))) / R + TINY
@@ -224,6 +229,7 @@ def restate(c, tpw=1, mistake=None):
 
 
 MISTAKES = ("row_dropped", "head_rows_swapped", "set_ignored", "gauss_shift", "no_1_over_R")
+TRIP_MISTAKES = ("later_trips_dropped", "last_trip_only")  # whole tiles lost in a workgroup's walk: asked of the cases of more than one trip
 
 
 def outside_bar(right, wrong):
@@ -417,8 +423,65 @@ def gpu_general_cases():
     return [separate_ratios(c) for c in out]
 
 
+# ---- the cases of more than one trip of k_policy_grad's walk (tests/test_gpu_grad_trips.py): tests/grid_pass_lib.py's R2 and R3
+TRIP_R = (gpl.GRAD_R2, gpl.GRAD_R3)
+TRIP_BASES = (
+    # piles, hidden, act, head, loss, sets, norm, seed, adv_stats: five of gpu_general_cases' R = 95 cases
+    ([20, 25], (33,), "tanh", "piles", "ppo_clip", True, False, 40 + 95, False),
+    (BIG_HUB, (33,), "tanh", "piles", "ppo_clip", True, False, 7, False),
+    ([3, 2], (64, 64), "tanh", "piles", "ppo_clip", True, False, 52, False),
+    ([20, 25], (64, 64), "relu", "piles", "coef", True, False, 9, True),
+    ([20, 25], (64, 64), "tanh", "loads", "ppo_clip", False, True, 8, False),
+)
+
+# the one accepted shape whose partials pass 256 MiB at 512 workgroups (tests/test_grad_trips_cpu.py sweeps the plans): a PILES head over
+# 350 piles reading a column per pile, 12 x 11 = 132 dW tiles -- 488 workgroups, of which at R2 the first 27 walk two tiles and the rest one
+TRIP_CAPPED = ([175, 175], (), "tanh", "piles", "coef", True, False, 11, False)
+CAPPED_INPUTS, CAPPED_F, CAPPED_BLOCKS = ("obs", ("pile_obs", ("car",))), 13 + 350, 488
+
+@functools.lru_cache(maxsize=None)
+def trip_general_cases():
+    """-> [(case, tpw)].  Rows drawn fresh at these R do not keep the bar below 2^-8 of the gradient: the gradient cancels over 33 k rows
+    while the bar adds absolute values.  So the 95 stored rows of a small case are visited through d_rows, each about 346 times and in
+    every trip: rows = a seeded permutation of arange(R) % 95.  The gradient and the bar over it then stay where they are at R = 95"""
+    out = []
+    for R in TRIP_R:
+        for k, (piles, hidden, act, head, loss, sets, norm, seed, adv_stats) in enumerate(TRIP_BASES):
+            c = synthetic_case(piles, hidden, act, head, 95, loss, sets, norm, seed=seed, adv_stats=adv_stats)
+            rows = np.random.RandomState(300 + k).permutation(np.arange(R) % 95).astype(np.int64)
+            c = c.copy(rows=rows, name="%s-%s-rows%d" % (c.name, loss, R))
+            tpw = tiles_per_workgroup(c.piles, list(c.hidden) + [c.layers[-1][0].shape[0]], R, c.head, c.act, c.inputs)
+            out.append((separate_ratios(c, tpw), tpw))
+    piles, hidden, act, head, loss, sets, norm, seed, adv_stats = TRIP_CAPPED
+    c = synthetic_case(piles, hidden, act, head, 95, loss, sets, norm, seed=seed, adv_stats=adv_stats, inputs=CAPPED_INPUTS, F=CAPPED_F)
+    rows = np.random.RandomState(399).permutation(np.arange(gpl.GRAD_R2) % 95).astype(np.int64)
+    c = c.copy(rows=rows, name="%s-%s-rows%d" % (c.name, loss, gpl.GRAD_R2))
+    out.append((c, tiles_per_workgroup(c.piles, [c.layers[-1][0].shape[0]], c.R, c.head, c.act, c.inputs)))
+    return out
+
+
+def blocks_of(c):
+    rc, p, msg = plan(c.piles, list(c.hidden) + [c.layers[-1][0].shape[0]], c.R, c.head, c.act, c.inputs)
+    assert rc == 0, msg
+    return p["workgroups"]
+
+
+def trip_parts_case(loss):
+    """-> (case, tpw): the first actor of TRIP_BASES at R3 under PPO_CLIP as it is, or differentiated under COEF"""
+    c, tpw = [(c, t) for c, t in trip_general_cases() if c.R == gpl.GRAD_R3][0]
+    assert c.loss == "ppo_clip" and tpw == 3
+    return (c if loss == "ppo_clip" else c.copy(loss="coef", name=c.name.replace("ppo_clip", "coef"))), tpw
+
+
+def trip_parts(c, blocks):
+    """the call over R rows cut by trip: -> [case], part t holding, through d_rows, the positions the workgroups meet in their trip t"""
+    base = np.arange(c.R, dtype=np.int64) if c.rows is None else np.asarray(c.rows, dtype=np.int64)
+    trips = -(-gpl.grad_tiles(c.R) // blocks)
+    return [c.copy(rows=base[gpl.grad_trip_positions(c.R, blocks, t)], name="%s-trip%d" % (c.name, t)) for t in range(trips)]
+
+
 # ---- the exact case: every product and every partial sum exact in f32, so the gradient equals the restatement BIT FOR BIT
-def exact_case(n_layers, n_rows, piles=(20, 25), hidden=(33, 64, 31)):
+def exact_case(n_layers, n_rows, piles=(20, 25), hidden=(33, 64, 31), blocks=None):
     """LOADS head, relu, log_std = 0, features multiples of 1/2, weights in {-1, 0, 1} (three per output), integer biases, u multiples of
     1/2, advantages +-2^k, COEF loss, ent_coef = 1/2"""
     D = ps.obs_dim(piles)
@@ -438,18 +501,31 @@ def exact_case(n_layers, n_rows, piles=(20, 25), hidden=(33, 64, 31)):
     c = Case(layers=layers, log_std=np.zeros(4, dtype=F32), act="relu", head="loads", S=sum(piles), features=feats, on=np.zeros((n_rows, 0), dtype=bool),
              u=u, logp_old=np.zeros(n_rows, dtype=F32), adv=adv, loss="coef", ent_coef=0.5, name="exact-%d-%d" % (n_layers, n_rows), piles=list(piles),
              hidden=tuple(hidden[:n_layers - 1]))
-    assert_exact(c)
+    assert_exact(c, blocks)
     return c
 
 
 EXACT_WIDE = (256, 64)  # 8 + 16 + 2 = 26 dW tiles of 32 x 32: more than the 16 a workgroup keeps in registers
 
 
-def assert_exact(c):
+def exact_sums(dl, h, blocks, q):
+    """the sums of a dW tile and of a bias: without `blocks` over all rows below 2^23 quanta; with it over each workgroup's own rows
+    (tiles b, b + blocks, ..: the only f32 chain there is) below 2^23 and over all rows below 2^53, which the f64 merge holds exactly"""
+    ad, ah = np.abs(dl), np.abs(h)
+    total = max((ad.T @ ah).max(), ad.sum(axis=0).max()) / q
+    if blocks is None:
+        return total < 2.0 ** 23
+    A, H = gpl.grad_by_workgroup(ad, blocks), gpl.grad_by_workgroup(ah, blocks)
+    own = max(np.matmul(A.transpose(0, 2, 1), H).max(), A.sum(axis=1).max()) / q
+    return own < 2.0 ** 23 and total < 2.0 ** 53
+
+
+def assert_exact(c, blocks=None):
     """every value and every product is a multiple of 2^-4 and every sum of absolute values stays below 2^23 quanta: any partial sum in
-    any order is exact in f32"""
+    any order is exact in f32.  blocks: the call's workgroups -- then the sums over rows are held per workgroup (exact_sums)"""
     q = 2.0 ** -4
     r = restate(c)
+    assert blocks is None or c.rows is None
     h = np.asarray(c.features, dtype=np.float64)
     for l, (W, b) in enumerate(c.layers):
         W, b = np.asarray(W, dtype=np.float64), np.asarray(b, dtype=np.float64)
@@ -462,17 +538,42 @@ def assert_exact(c):
     for l in range(len(c.layers) - 1, -1, -1):
         W = np.asarray(c.layers[l][0], dtype=np.float64)
         assert np.array_equal(dl / q, np.round(dl / q))
-        assert (np.abs(dl).T @ np.abs(r["hs"][l])).max() / q < 2.0 ** 23 and np.abs(dl).sum(axis=0).max() / q < 2.0 ** 23
+        assert exact_sums(dl, r["hs"][l], blocks, q)
         if l > 0:
             assert (np.abs(dl) @ np.abs(W)).max() / q < 2.0 ** 23
             dl = np.where(r["hs"][l] > 0, dl @ W, 0.0)
     return r
 
 
-def exact_expected(c):
+def exact_expected(c, r=None):
     """the f32 bits the device must give: the exact sums over R in f64, rounded once"""
-    r = restate(c)
+    r = r or restate(c)
     return [g.astype(F32) for g in r["gW"]], [g.astype(F32) for g in r["gb"]], r["gls"].astype(F32)
+
+
+def exact_forward(c, r=None):
+    """an exact case's logp_new, entropy (f32 bits) and stats (f64 bits).  z, u and so eps (log_std = 0: expf gives 1) are exact, and so
+    is -0.5 eps^2; 0.5 ln 2 pi is not dyadic, so every Gaussian term is rounded once where it is subtracted and the row's four terms
+    are added in f32 in ascending output order from 0 (one lane holds the head's outputs 0 .. 3; the other half-wave and the other waves
+    add zeros).  A = +-2^k and ent_coef = 1/2 make both products of the row's loss term exact, their difference is rounded once.  The
+    stats are f64 sums of f32 numbers that are multiples of 2^-24: exact in any order below 2^53 of them, which is asserted"""
+    r = r or restate(c)
+    assert c.head == "loads" and c.loss == "coef" and c.rows is None and c.adv_stats is None and not np.asarray(c.log_std).any()
+    K, R = F32(0.918938533204672742), c.R
+    eps = r["eps"].astype(F32)
+    assert np.array_equal(eps.astype(np.float64), r["eps"])
+    lp, en = np.zeros(R, dtype=F32), np.zeros(R, dtype=F32)
+    hg = F32(F32(0.5) + F32(0.0)) + K
+    for i in range(4):
+        lp = lp + ((F32(-0.5) * (eps[:, i] * eps[:, i])) - F32(0.0) - K)
+        en = en + hg
+    assert lp.dtype == F32 and en.dtype == F32
+    A = np.asarray(c.adv, dtype=F32)
+    term = (-(A * lp) - F32(c.ent_coef) * en).astype(F32)
+    t64, e64 = term.astype(np.float64), en.astype(np.float64)
+    for a in (t64, e64):
+        assert np.array_equal(a * 2.0 ** 24, np.round(a * 2.0 ** 24)) and np.abs(a).sum() * 2.0 ** 24 < 2.0 ** 53
+    return lp, en, np.array([float(R), t64.sum(), e64.sum(), 0.0, 0.0, 0.0])
 
 
 def pack_bits(on, S):

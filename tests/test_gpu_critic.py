@@ -36,11 +36,11 @@ def padded(c):
 
 
 class DevCase(object):
-    """a case's arrays in device memory and the outputs of a call"""
+    """a case's arrays in device memory and the outputs of a call; tail: positions the two values buffers hold past R (nothing may write them)"""
 
-    def __init__(self, c):
+    def __init__(self, c, tail=0):
         mg = buffers()
-        self.c = c
+        self.c, self.tail = c, tail
         self.shapes = [(W.shape, b.shape) for W, b in c.layers]
         self.buf = {}
         ins = dict(x=padded(c), ret=c.ret, v_old=c.v_old)
@@ -53,7 +53,7 @@ class DevCase(object):
         for l, (ws, bs) in enumerate(self.shapes):
             for k, s in (("gW%d" % l, ws), ("gb%d" % l, bs), ("W%d" % l, ws), ("b%d" % l, bs)):
                 self.buf[k] = mg.DeviceBuffer(int(np.prod(s)) * 4)
-        self.buf["values"], self.buf["values2"], self.buf["stats"] = mg.DeviceBuffer(4 * c.R), mg.DeviceBuffer(4 * c.R), mg.DeviceBuffer(48)
+        self.buf["values"], self.buf["values2"], self.buf["stats"] = mg.DeviceBuffer(4 * (c.R + tail)), mg.DeviceBuffer(4 * (c.R + tail)), mg.DeviceBuffer(48)
         self.clear()
 
     def p(self, k):
@@ -80,15 +80,18 @@ class DevCase(object):
             self.buf["gW%d" % l].from_host(np.full(ws, np.nan, dtype=F32))
             self.buf["gb%d" % l].from_host(np.full(bs, np.nan, dtype=F32))
         for k in ("values", "values2"):
-            self.buf[k].from_host(np.full(self.c.R, np.nan, dtype=F32))
+            self.buf[k].from_host(np.full(self.c.R + self.tail, np.nan, dtype=F32))
         self.buf["stats"].from_host(np.full(6, np.nan, dtype=np.float64))
 
     def out(self):
-        """-> dict(grads [(gW, gb)], values, values2, stats), f32 / f64"""
+        """-> dict(grads [(gW, gb)], values, values2, stats), f32 / f64; with a tail also past = the two buffers' positions from R on"""
         grads = [(f32(self.buf["gW%d" % l].to_host(np.uint32, ws)), f32(self.buf["gb%d" % l].to_host(np.uint32, bs))) for l, (ws, bs) in enumerate(self.shapes)]
         R = self.c.R
-        return dict(grads=grads, values=f32(self.buf["values"].to_host(np.uint32, (R,))), values2=f32(self.buf["values2"].to_host(np.uint32, (R,))),
-                    stats=self.buf["stats"].to_host(np.uint64, (6,)).view(np.float64))
+        val, val2 = (f32(self.buf[k].to_host(np.uint32, (R + self.tail,))) for k in ("values", "values2"))
+        res = dict(grads=grads, values=val[:R].copy(), values2=val2[:R].copy(), stats=self.buf["stats"].to_host(np.uint64, (6,)).view(np.float64))
+        if self.tail:
+            res["past"] = np.concatenate([val[R:], val2[R:]])
+        return res
 
     def free(self):
         for b in self.buf.values():
@@ -104,9 +107,9 @@ def same_bits(a, b):
         np.array_equal(bits(a["values"]), bits(b["values"])) and np.array_equal(bits(a["stats"]), bits(b["stats"]))
 
 
-def call(cr, c, backward=True):
+def call(cr, c, backward=True, tail=0):
     """one gradient call and the values call on the case, through device buffers of their own"""
-    d = DevCase(c)
+    d = DevCase(c, tail)
     d.run(cr, backward=backward)
     d.run_values(cr)
     cr._env.sync()

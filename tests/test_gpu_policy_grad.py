@@ -221,13 +221,19 @@ def test_minibatches_by_rows_add_up():
 
 # ---- 5. determinism, graphs, new weights between replays
 class DevCase(object):
-    """a case's arrays in device memory and the outputs of a call"""
+    """a case's arrays in device memory and the outputs of a call.  tail None: the buffers of the determinism test (no d_rows, no
+    advantage statistics, no entropy); a number: all of the case's inputs and every output, NaN over the outputs before a call, logp_new
+    and entropy `tail` positions longer than R (nothing may write those)"""
 
-    def __init__(self, c):
+    def __init__(self, c, tail=None):
         mg = buffers()
-        self.c = c
+        self.c, self.tail = c, tail
         piles = c.head == "piles"
         ins = dict(features=c.features, u=c.u, adv=c.adv, logp_old=c.logp_old)
+        if tail is not None and c.rows is not None:
+            ins["rows"] = np.asarray(c.rows, dtype=np.int64)
+        if tail is not None and c.adv_stats is not None:
+            ins["adv_stats"] = np.asarray(c.adv_stats, dtype=np.float64)
         if piles:
             ins["bits"] = pgl.pack_bits(c.on, c.S)
             if c.sets is not None:
@@ -241,16 +247,20 @@ class DevCase(object):
         for l, (ws, bs) in enumerate(self.shapes):
             for k, s in (("gW%d" % l, ws), ("gb%d" % l, bs), ("W%d" % l, ws), ("b%d" % l, bs)):
                 self.buf[k] = mg.DeviceBuffer(int(np.prod(s)) * 4)
-        self.buf["gls"], self.buf["logp_new"], self.buf["stats"] = mg.DeviceBuffer(16), mg.DeviceBuffer(4 * c.R), mg.DeviceBuffer(48)
+        self.buf["gls"], self.buf["logp_new"], self.buf["stats"] = mg.DeviceBuffer(16), mg.DeviceBuffer(4 * (c.R + (tail or 0))), mg.DeviceBuffer(48)
+        if tail is not None:
+            self.buf["entropy"] = mg.DeviceBuffer(4 * (c.R + tail))
+            self.clear(np.nan)
 
     def p(self, k):
         return self.buf[k].ptr if k in self.buf else 0
 
-    def run(self, g, stream=0):
+    def run(self, g, stream=0, backward=True):
         c, L = self.c, len(self.shapes)
         g.grad_device(c.R, len(c.features), self.p("features"), self.p("u"), self.p("adv"), self.p("bits"), self.p("sets"), self.p("logp_old"),
-                      loss=c.loss, clip_eps=c.clip_eps, ent_coef=c.ent_coef, d_gW=[self.p("gW%d" % l) for l in range(L)],
-                      d_gb=[self.p("gb%d" % l) for l in range(L)], d_glog_std=self.p("gls"), d_logp_new=self.p("logp_new"), d_stats=self.p("stats"),
+                      d_rows=self.p("rows"), d_adv_stats=self.p("adv_stats"), loss=c.loss, clip_eps=c.clip_eps, ent_coef=c.ent_coef,
+                      d_gW=[self.p("gW%d" % l) for l in range(L)] if backward else None, d_gb=[self.p("gb%d" % l) for l in range(L)] if backward else None,
+                      d_glog_std=self.p("gls") if backward else 0, d_logp_new=self.p("logp_new"), d_entropy=self.p("entropy"), d_stats=self.p("stats"),
                       stream=stream)
 
     def put_weights(self, layers):
@@ -258,20 +268,30 @@ class DevCase(object):
             self.buf["W%d" % l].from_host(np.ascontiguousarray(W, dtype=F32))
             self.buf["b%d" % l].from_host(np.ascontiguousarray(b, dtype=F32))
 
-    def clear(self):
-        """zeros over every output, so that what is read next was written by the call in between"""
+    def clear(self, fill=0.0):
+        """zeros (or `fill`) over every output, so that what is read next was written by the call in between"""
         for l, (ws, bs) in enumerate(self.shapes):
-            self.buf["gW%d" % l].from_host(np.zeros(ws, dtype=F32))
-            self.buf["gb%d" % l].from_host(np.zeros(bs, dtype=F32))
-        self.buf["gls"].from_host(np.zeros(4, dtype=F32))
-        self.buf["logp_new"].from_host(np.zeros(self.c.R, dtype=F32))
-        self.buf["stats"].from_host(np.zeros(6, dtype=np.float64))
+            self.buf["gW%d" % l].from_host(np.full(ws, fill, dtype=F32))
+            self.buf["gb%d" % l].from_host(np.full(bs, fill, dtype=F32))
+        self.buf["gls"].from_host(np.full(4, fill, dtype=F32))
+        for k in ("logp_new", "entropy") if "entropy" in self.buf else ("logp_new",):
+            self.buf[k].from_host(np.full(self.c.R + (self.tail or 0), fill, dtype=F32))
+        self.buf["stats"].from_host(np.full(6, fill, dtype=np.float64))
 
     def out(self):
         res = []
         for l, (ws, bs) in enumerate(self.shapes):
             res += [self.buf["gW%d" % l].to_host(np.uint32, ws), self.buf["gb%d" % l].to_host(np.uint32, bs)]
         return res + [self.buf["gls"].to_host(np.uint32, (4,))[:2], self.buf["logp_new"].to_host(np.uint32, (self.c.R,)), self.buf["stats"].to_host(np.uint64, (6,))]
+
+    def result(self):
+        """(a DevCase with a tail) -> what `call` returns, from these buffers: dict(grads [(gW, gb)], g_log_std, logp_new, entropy [R],
+        stats), and past = the positions of logp_new and entropy from R on"""
+        R, G = self.c.R, len(self.c.log_std)
+        grads = [(f32(self.buf["gW%d" % l].to_host(np.uint32, ws)), f32(self.buf["gb%d" % l].to_host(np.uint32, bs))) for l, (ws, bs) in enumerate(self.shapes)]
+        lp, en = (f32(self.buf[k].to_host(np.uint32, (R + self.tail,))) for k in ("logp_new", "entropy"))
+        return dict(grads=grads, g_log_std=f32(self.buf["gls"].to_host(np.uint32, (4,)))[:G].copy(), logp_new=lp[:R].copy(), entropy=en[:R].copy(),
+                    stats=self.buf["stats"].to_host(np.uint64, (6,)).view(np.float64), past=np.concatenate([lp[R:], en[R:]]))
 
     def free(self):
         for b in self.buf.values():
