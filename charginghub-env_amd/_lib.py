@@ -427,6 +427,7 @@ def load_library():
         "chub_obs_dim": (I, [P]), "chub_act_dim": (I, [P]), "chub_num_envs": (L, [P]), "chub_clock": (I, [P]), "chub_uses_packed_kernel": (I, [P]), "chub_uses_fused_step": (I, [P]), "chub_uses_xcd_order": (I, [P]),
         "chub_launch_plan": (I, [C.POINTER(ChubConfig), L, I, C.POINTER(ChubOptions), P]),
         "chub_launch_plan_params": (I, [C.POINTER(ChubConfig), L, I, C.POINTER(ChubOptions), P]),
+        "chub_pair_plan": (I, [C.POINTER(ChubConfig), L, I, C.POINTER(ChubOptions), I, C.c_uint32, I, L, P]), "chub_uses_pair_tails": (I, [P]),
         "chub_create_params": (I, [C.POINTER(ChubConfig), C.c_char_p, L, L, I, C.c_uint64, I, C.POINTER(ChubOptions), P, C.POINTER(P)]),
         "chub_set_env_params": (I, [P, P, P]), "chub_get_env_params": (I, [P, P]), "chub_has_env_params": (I, [P]),
         "chub_reset": (I, [P, P, P, P]),
@@ -535,7 +536,7 @@ def load_library():
     return lib
 
 
-EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "chub_act_dim", "chub_num_envs", "chub_clock", "chub_uses_packed_kernel", "chub_uses_fused_step", "chub_uses_xcd_order", "chub_launch_plan", "chub_launch_plan_params",
+EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "chub_act_dim", "chub_num_envs", "chub_clock", "chub_uses_packed_kernel", "chub_uses_fused_step", "chub_uses_xcd_order", "chub_launch_plan", "chub_launch_plan_params", "chub_pair_plan", "chub_uses_pair_tails",
             "chub_create_params", "chub_set_env_params", "chub_get_env_params", "chub_has_env_params", "chub_reset",
             "chub_step", "chub_host_actions", "chub_step_bits", "chub_host_bits", "chub_step_bits_device", "chub_step_bits_device_packed", "chub_reset_device", "chub_step_device", "chub_step_device_packed", "chub_step_load", "chub_step_load_device", "chub_step_load_envs", "chub_step_load_envs_device", "chub_reset_envs", "chub_step_envs", "chub_reset_envs_device", "chub_step_envs_device",
             "chub_env_clocks", "chub_clock_groups", "chub_dmask_reset_envs_device", "chub_dmask_step_envs_device", "chub_autoreset_step_device", "chub_call_plan", "chub_random_actions_device", "chub_sync", "chub_profile_begin", "chub_profile_end",

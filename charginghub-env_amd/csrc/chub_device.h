@@ -353,6 +353,16 @@ struct PackedPtrs {
     const double *sin96;      // host copy of Tables::sin96 (the tail gets its slot's value by value)
 };
 
+// host-side copies of what a pair of steps whose tails share one launch keeps apart from the handle's own arrays (k_env_pair in chub_kernels.hip);
+// scratch outside the arena: every chain of pairs fills what it reads, and leaves the handle's arrays as single steps would
+struct PairBufs {
+    uint32_t *rec_a;      // [2N][4] the records of a pair's first step
+    float *tail_act_a;    // [N][2]  ... and its tail actions
+    uint64_t *pkraw;      // [2N]    the raw station draws of a pair's second step
+    uint32_t *drw[2][2];  // [N][4]  env draws: two blocks (one read, one written by a pair's tail launch) of two steps each
+    uint8_t *cnt[2][2];   // [N]
+};
+
 struct StepArgs {
     int32_t t;               // clock of the slot being simulated (0..95)
     uint32_t tick;           // Philox tick (increments on every reset and step)

@@ -397,6 +397,57 @@ __device__ __forceinline__ uint32_t draw_decoded_levels(const HubParams &hp, con
     }
     return (uint32_t) (stay_q + flow) | ((uint32_t) flow << 8);
 }
+// The same draws left RAW -- the 64-bit form above -- for a step whose queue length is not known yet at draw time: the second step of a pair whose
+// tails share one launch (k_env_pair) is decoded by its own slot launch (dk_make in slot_body_packed's unit pass).  Same Philox sites and
+// counters, same tables, same comparisons as draw_decoded_levels, so dk_make of this word gives that function's word bit for bit.  Lazy in
+// the same way: the queue in front of that step holds at most qmax cars (the `want` of the step before it: line = min(want - assign,
+// max_line)), and dk_make looks at renege bits below the queue length and at the balk entry of the thinned queue only, so the words of
+// queue positions 4-9 are drawn only where some unit of the wave may queue that far, and the balk table is filled up to qmax.
+__device__ __forceinline__ uint64_t draw_raw_levels(const HubParams &hp, const Tables &tb, uint32_t tick, int t, int k, int64_t env, int qmax,
+                                                    bool fast) {
+    PhiloxCtx px{hp.key[0], hp.key[1], tick, (uint32_t) (hp.env_id0 + env)};
+    const U4 a0 = px.block(SITE_ARRIVE, (uint32_t) k, 0);
+    const U4 r0 = px.block(SITE_RENEGE, (uint32_t) k, 0);
+    int n_in = (int) tb.cnt[k][t * kLevels + (int) (a0.v[0] % 1000u)];
+    n_in = n_in > 9 ? 9 : n_in;
+    uint32_t rw[10] = {r0.v[0], r0.v[1], r0.v[2], r0.v[3], 0u, 0u, 0u, 0u, 0u, 0u};
+    if (__any(qmax > 4)) {
+        const U4 r1 = px.block(SITE_RENEGE, (uint32_t) k, 1), r2 = px.block(SITE_RENEGE, (uint32_t) k, 2);
+        rw[4] = r1.v[0]; rw[5] = r1.v[1]; rw[6] = r1.v[2]; rw[7] = r1.v[3]; rw[8] = r2.v[0]; rw[9] = r2.v[1];
+    }
+    uint32_t ren = 0u;
+#pragma unroll
+    for (int w = 0; w < kMaxLine; w++) ren |= ((int) (rw[w] % 1000u) >= (int) tb.thr_renege[w]) ? (1u << w) : 0u;
+    uint64_t pk = (uint64_t) (ren | ((uint32_t) n_in << 10));
+    if (!fast && __any(n_in > 0)) {
+        uint32_t bw[9] = {a0.v[1], a0.v[2], a0.v[3], 0u, 0u, 0u, 0u, 0u, 0u};
+        if (__any(n_in > 3)) {
+            const U4 a1 = px.block(SITE_ARRIVE, (uint32_t) k, 1), a2 = px.block(SITE_ARRIVE, (uint32_t) k, 2);
+            bw[3] = a1.v[0]; bw[4] = a1.v[1]; bw[5] = a1.v[2]; bw[6] = a1.v[3]; bw[7] = a2.v[0]; bw[8] = a2.v[1];
+        }
+        const int S = hp.S[k];
+        int top[9];  // arrival j stays iff the thinned queue holds at most top[j] cars (-1: never)
+#pragma unroll
+        for (int j = 0; j < 9; j++) top[j] = -1;
+#pragma unroll
+        for (int j = 0; j < 9; j++) {
+            if (j >= 3 && !__any(n_in > j)) break;
+            top[j] = (j < n_in && j <= S) ? (int) tb.inv_balk[bw[j] % 1000u] - j : -1;
+        }
+        const bool more3 = __any(n_in > 3);
+#pragma unroll
+        for (int l = 0; l <= kMaxLine; l++) {
+            if (l > 0 && !__any(qmax >= l)) break;
+            int c = (l <= top[0] ? 1 : 0) + (l <= top[1] ? 1 : 0) + (l <= top[2] ? 1 : 0);
+            if (more3) {
+#pragma unroll
+                for (int j = 3; j < 9; j++) c += l <= top[j] ? 1 : 0;
+            }
+            pk |= (uint64_t) c << (14 + 4 * l);
+        }
+    }
+    return pk;
+}
 __device__ __forceinline__ int dk_want(uint32_t dk) { return (int) (dk & 255u); }
 __device__ __forceinline__ int dk_flow(uint32_t dk) { return (int) ((dk >> 8) & 255u); }
 
@@ -1756,6 +1807,8 @@ struct PackedArgs {
                                      // launch's number of workgroups, here so that it arrives with the first batch of arguments (gridDim.x is a load of its own)
     CHUB_G(float) tail_act;          // [N][2] out: the env's two tail actions, for the tail kernel (StationArrays::tail_act)
     CHUB_G(uint8_t) stay8;           // [N][S0 + S1] out, per admitted car: its stay_time (introspection only)
+    CHUB_G(const uint32_t) rec_prev; // RAW (the second slot launch of a pair, k_env_pair): the records the pair's first slot launch left -- pk is then
+                                     // the units' raw 64-bit draws (the pk_tape layout at dk_make), decoded against the queue length kept there
 };
 
 typedef const uint32_t __attribute__((address_space(4))) *chub_sptr;  // constant address space: scalar loads
@@ -1793,7 +1846,7 @@ constexpr int kAccCopies = CHUB_ACC_COPIES;
 // The station records of a workgroup of the packed kernel, one lane of ONE wave per unit (the caller has passed the workgroup's last
 // barrier: every car's LDS atomics are in).  FUSED: also into s_rec, for the tails that follow in the same workgroup.
 #define CHUB_AT(T_, base, byte_off) (*(CHUB_G(T_)) ((CHUB_G(char)) (base) + (uint32_t) (byte_off)))
-template <int BLOCK, int T, bool RESET, bool BIG, bool MASKED, bool FUSED, bool BITS>
+template <int BLOCK, int T, bool RESET, bool BIG, bool MASKED, bool FUSED, bool BITS, bool RAW = false>
 __device__ __forceinline__ void packed_records(const PackedArgs &pa, const uint32_t block_local, int *s_acc, const uint32_t *s_unit, u32x4 *s_rec,
                                                const float *tail_pre = nullptr) {
     const int lane = threadIdx.x & 63;
@@ -1822,7 +1875,7 @@ __device__ __forceinline__ void packed_records(const PackedArgs &pa, const uint3
             CHUB_AT(f32x2_, pa.tail_act, (uint32_t) env << 3) = tv;
         }
         uint32_t lf = s_unit[i];
-        if ((k ? S1 : S0) == 0) {
+        if (!RAW && (k ? S1 : S0) == 0) {  // (RAW: the unit pass has decoded the raw draws and left exactly this word in s_unit)
             // a station without piles still queues, reneges and balks (receive_car runs on it as on any other, CHS.hpp:1272-1316 /
             // 1583-1627; nobody is ever admitted): its queue length and arrival count move on here, power sums and cars stay 0
             const uint32_t pk = CHUB_AT(const uint32_t, pa.pk, su << 2);
@@ -1875,7 +1928,9 @@ struct NoHook {
 // 8 bytes per env and word instead of 4 per pile (chub_step_bits; the tail kernel reads the two tail actions from their own array).
 // PIPED (k_steps_piped): the new cars are the business of the upper half of the workgroup's slot waves -- the lower half returns right behind the
 // third barrier and makes the next step's draws meanwhile.
-template <int BLOCK, int T, bool TAPE, bool RESET, bool BIG, bool MASKED, bool FUSED, typename Hook, bool BITS = false, bool PIPED = false>
+// RAW (the second slot launch of a pair of steps whose tails share one launch, k_env_pair): no tail launch has run since the step before, so
+// the unit's draws wait in their raw 64-bit form and the unit pass decodes them (dk_make) against the queue the step before left in its record.
+template <int BLOCK, int T, bool TAPE, bool RESET, bool BIG, bool MASKED, bool FUSED, typename Hook, bool BITS = false, bool PIPED = false, bool RAW = false>
 __device__ __forceinline__ int slot_body_packed(const HubParams &hp, const StepArgs &sa, PackedArgs &pa, const Tables &tb,
                                                 const uint32_t block_local, uint32_t *q_cnt, uint32_t *q_new,
                                                 uint64_t *s_ball, int *s_acc, uint32_t *s_unit, Hook &hook, u32x4 *s_rec, uint32_t *s_uinfo) {
@@ -1916,6 +1971,7 @@ __device__ __forceinline__ int slot_body_packed(const HubParams &hp, const StepA
     // word (dk_make), so the count is 0 ... 64; the raw draws of a reset, which are negative on small fast stations, keep the per-lane form,
     // as do the large tile, the one-launch kernels and stations of more than 64 piles.
     constexpr bool UNIT_DRAWS = CHUB_UNIT_DRAWS && STATE_FIRST && !BIG && T <= 2;
+    static_assert(!RAW || (UNIT_DRAWS && !MASKED && !BITS && !TAPE), "the raw draws are decoded in the unit pass of the lock-step small tile");
     int e_[T], k_[T], slot[T];
     bool valid[T];
     uint32_t sidx[T];
@@ -1988,11 +2044,20 @@ __device__ __forceinline__ int slot_body_packed(const HubParams &hp, const StepA
         }
     }
     uint32_t upk = 0u;  // UNIT_DRAWS: unit tid's decoded draws
+    u32x2 uraw = {0u, 0u};  // RAW: its raw draws, and
+    uint32_t uprev = 0u;    //      the fourth word of its record of the step before
     if (UNIT_DRAWS) asm volatile("" : "=v"(upk));
+    if (RAW) asm volatile("" : "=v"(uraw), "=v"(uprev));
     if (UNIT_DRAWS && (tid & ~63) < 2 * epb) {  // (wave-uniform: the 22 units of a workgroup of the 20 + 25 hub are the first wave's alone)
         asm volatile("" ::: "memory");
         const int ue = tid >> 1, uenv = env_first + ue;
-        upk = CHUB_AT(const uint32_t, pa.pk, (ue < epb && uenv < N ? (uint32_t) ((tid & 1) ? N : 0) + (uint32_t) uenv : (uint32_t) env_first) << 2);
+        const uint32_t ui = ue < epb && uenv < N ? (uint32_t) ((tid & 1) ? N : 0) + (uint32_t) uenv : (uint32_t) env_first;
+        if (RAW) {
+            uraw = CHUB_AT(const u32x2, pa.pk, ui << 3);
+            uprev = CHUB_AT(const uint32_t, pa.rec_prev, (ui << 4) + 12u);
+        } else {
+            upk = CHUB_AT(const uint32_t, pa.pk, ui << 2);
+        }
     }
     if (HOIST_TAIL) asm volatile("" : "=v"(tail_pre[0]), "=v"(tail_pre[1]));
     if (HOIST_TAIL && wave == WAVES - 1) {  // behind everything else: the other waves' wait for the state words then leaves them in flight as well
@@ -2089,7 +2154,12 @@ __device__ __forceinline__ int slot_body_packed(const HubParams &hp, const StepA
                 // assign_car (CHS.hpp:417-430), once per unit: the queue after the renege pass + the arrivals that stay, and flow_in, were decoded
                 // one launch ahead (dk_make).  The third byte carries how many of the unit's empties take a car instead of how many there are.
                 // (A unit past the batch's end or of an env the launch does not serve has no empties -- its lanes balloted none -- and so admits nobody.)
-                asm volatile("" : "+v"(upk));
+                if (RAW) {
+                    asm volatile("" : "+v"(uraw), "+v"(uprev));
+                    upk = dk_make((uint64_t) uraw.x | ((uint64_t) uraw.y << 32), pkd_line(uprev), (k ? pa.type[1] : pa.type[0]) == 0);
+                } else {
+                    asm volatile("" : "+v"(upk));
+                }
                 const int want = dk_want(upk);
                 const int assign = want < all ? want : all;
                 const int ln = want - assign;
@@ -2290,7 +2360,7 @@ __device__ __forceinline__ int slot_body_packed(const HubParams &hp, const StepA
 #endif
         if (wave != WAVES - 1) return 0;
     }
-    packed_records<BLOCK, T, RESET, BIG, MASKED, false, BITS>(pa, block_local, s_acc, s_unit, nullptr, tail_pre);
+    packed_records<BLOCK, T, RESET, BIG, MASKED, false, BITS, RAW>(pa, block_local, s_acc, s_unit, nullptr, tail_pre);
 #if CHUB_TRACE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     CHUB_STAMP(11);  // records stored: the workgroup is done
@@ -2300,7 +2370,7 @@ __device__ __forceinline__ int slot_body_packed(const HubParams &hp, const StepA
 #undef CHUB_AT
 }
 
-template <int BLOCK, int T, bool TAPE, bool RESET, bool BIG, bool MASKED, bool BITS = false>
+template <int BLOCK, int T, bool TAPE, bool RESET, bool BIG, bool MASKED, bool BITS = false, bool RAW = false>
 __global__ __launch_bounds__(BLOCK, (BLOCK <= 256 ? 8 : 2048 / BLOCK)) void k_slot_packed(const DevCtx *__restrict__ ctx, StepArgs sa, PackedArgs pa_in) {
     __shared__ uint32_t q_new[BLOCK * T];
     __shared__ uint32_t q_cnt[2];
@@ -2316,7 +2386,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK <= 256 ? 8 : 2048 / BLOCK)) void k_sl
     asm volatile("" : "+s"(pa.S[0]), "+s"(pa.S[1]), "+s"(pa.type[0]), "+s"(pa.type[1]), "+s"(pa.n_envs), "+s"(pa.epb), "+s"(pa.magic),
                       "+s"(pa.cls_delta), "+s"(pa.state), "+s"(pa.rec), "+s"(pa.pk), "+s"(pa.actions), "+s"(pa.cls0), "+s"(pa.ttab2));
     NoHook hook;
-    (void) slot_body_packed<BLOCK, T, TAPE, RESET, BIG, MASKED, false, NoHook, BITS>(ctx->hp, sa, pa, ctx->tb, xcd_order(blockIdx.x, pa.xcd, MASKED ? 0u : pa.xcd) + (MASKED ? pa.blk0 : 0u), q_cnt, q_new,
+    (void) slot_body_packed<BLOCK, T, TAPE, RESET, BIG, MASKED, false, NoHook, BITS, false, RAW>(ctx->hp, sa, pa, ctx->tb, xcd_order(blockIdx.x, pa.xcd, MASKED ? 0u : pa.xcd) + (MASKED ? pa.blk0 : 0u), q_cnt, q_new,
                                                                                      s_ball + 1, s_acc, s_unit, hook, nullptr, s_uinfo);
 }
 
@@ -3015,6 +3085,15 @@ __device__ __forceinline__ void tail_prefetch(TailIn &in, const TailArgs &ta, co
     }
 }
 
+// A pair of steps in one lane (k_env_pair): what the first step's tail hands to the second -- the env's carried state in registers, and the second
+// step's other inputs (its station records, tail actions, pre-drawn variates, its element of the next slot's table rows), requested with the
+// first step's load burst so that the launch pays one cold round trip
+struct TailNext {
+    TailIn in;
+    u32x4 r0, r1;
+    double st_pv, st_wd;
+};
+
 // FUSED (k_step_fused): one WAVE runs the tails of up to 64 envs of its workgroup right behind their station records: the table rows
 // are already in LDS (the caller's), the two records come from LDS (s_rec, [2 * local env + station]), `row` = the lane's place
 // among the wave's output rows, env0 = the env of row 0, and the only synchronisation is the wave's own.
@@ -3044,12 +3123,16 @@ __device__ __forceinline__ uint32_t hv_count_env(const EnvParamArrays &ep, uint3
 
 // EP (ENV_PARAMS, handles made by chub_create_params): the hydrogen, fuel-cell, fluctuation and FCEV constants are the env's own (DevCtx::ep, read
 // in the first load burst) and the electrolyser table is the env's row of EnvArrays::hy_env instead of the block's LDS copy
-template <bool RESET, int MODE, bool MULTI, bool FUSED = false, typename Mid = NoMid, int EB = kEnvBlock, bool TAPE = false, bool EP = false>
+// PAIR (k_env_pair): 1 = the first step of a pair: it also requests the second step's inputs (ta2: that step's arguments) and leaves them, with the
+// env's state as it stands behind this step, in nx; 2 = the second step: everything comes from nx (`pre` = nx->in), its table rows of "now" are the
+// first step's rows of "next" (the caller passes those LDS arrays) and only the next slot's rows are parked
+template <bool RESET, int MODE, bool MULTI, bool FUSED = false, typename Mid = NoMid, int EB = kEnvBlock, bool TAPE = false, bool EP = false, int PAIR = 0>
 __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const StepArgs &sa, const int env, const bool live,
                                          const double *s_pv, const double *s_wd, const double *s_pv_now, const double *s_wd_now,
                                          const double *s_hy, const uint8_t *s_hv, float *s_out, const int env_block, const TailArgs &ta,
                                          const u32x4 *s_rec, const int local_env, const int env0_fused, const int rows_fused,
-                                         const TailIn &pre, const bool use_pre, Mid &mid) {
+                                         const TailIn &pre, const bool use_pre, Mid &mid, TailNext *nx = nullptr, const TailArgs *ta2 = nullptr) {
+    static_assert(PAIR == 0 || (!RESET && MODE == MODE_PHILOX && !MULTI && !FUSED && !TAPE && !EP), "pairs: the lock-step PHILOX step of the stand-alone tail");
     const HubParams &hp = ctx->hp;
     const EnvArrays &ev = ctx->ev;
     const CompatRng &cr = ctx->cr;
@@ -3101,15 +3184,23 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
     const bool ep_on = (tel_word & 2) != 0;
     if (!FUSED) {
         const int i = threadIdx.x;
-        if (!multi) {  // lock-step: the rows of the launch's slot of the day
+        if (PAIR == 2) {  // requested by the pair's first step
+            st_pv = nx->st_pv;
+            st_wd = nx->st_wd;
+        } else if (!multi) {  // lock-step: the rows of the launch's slot of the day
             if (i < 100) st_pv = ta.pv_row[i];
             if (i < 150) st_wd = ta.wd_row[i];
             if (!RESET) {
                 if (i < 100) st_pv_now = ta.pv_row_now[i];
                 if (i < 150) st_wd_now = ta.wd_row_now[i];
             }
+            if (PAIR == 1) {
+                nx->st_pv = nx->st_wd = 0.0;
+                if (i < 100) nx->st_pv = ta2->pv_row[i];
+                if (i < 150) nx->st_wd = ta2->wd_row[i];
+            }
         }
-        if (!RESET) {
+        if (!RESET && PAIR != 2) {
             if (!EP && i < 102) st_hy = ta.hy_table[i];
             // (the split step's tail does not look the forecourt's arrivals up -- the walk did: no table row, and no hop through the context
             // pointer for its address in front of the per-env loads)
@@ -3129,7 +3220,7 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
     int pv_day = 0, wd_day = 0, q_len = 0, hv_line = 0, F0i = 0, F1i = 0, ln0 = 0, ln1 = 0, hv_lev = 0, hv_arrive = 0;
     u32x4 drw_raw = {0u, 0u, 0u, 0u};
     uint32_t drw_n = 0u, hvw0 = 0u, hvw1 = 0u;
-    const bool have_pre = FUSED && use_pre;  // the env's own state came in ahead of time (tail_prefetch)
+    const bool have_pre = (FUSED || PAIR == 2) && use_pre;  // the env's own state came in ahead of time (tail_prefetch; PAIR: from the step before)
     double p_v_h_max = 0.0, p_cells = 0.0, p_rc_cells = 0.0, p_cap_mass = 0.0, p_rc_cap_mass = 0.0, p_init_soc = 0.0, p_hydro_loss = 0.0;
     double p_fc_max_power = 0.0, p_renew_fluct1 = 0.0, p_price_fluct1 = 0.0;
     if (live) {
@@ -3157,7 +3248,11 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
             ou_price = ta.ou[2u * n32 + e32];
             in_price_noise = ta.price_noise[e32];
         }
-        if (!FUSED) {  // (FUSED: the records are read from LDS behind mid(), where this workgroup writes them)
+        if (PAIR == 2) {
+            const u32x4 v0 = nx->r0, v1 = nx->r1;
+            mn0 = __uint_as_float(v0.x); P0f = __uint_as_float(v0.y); mx0 = __uint_as_float(v0.z); ln0 = pkd_line(v0.w); F0i = pkd_flow(v0.w);
+            mn1 = __uint_as_float(v1.x); P1f = __uint_as_float(v1.y); mx1 = __uint_as_float(v1.z); ln1 = pkd_line(v1.w); F1i = pkd_flow(v1.w);
+        } else if (!FUSED) {  // (FUSED: the records are read from LDS behind mid(), where this workgroup writes them)
             const StationRec r0 = rec_load(ta.rec, e32), r1 = rec_load(ta.rec, n32 + e32);
             mn0 = r0.mn; P0f = r0.chg; mx0 = r0.mx; ln0 = pkd_line(r0.pkd); F0i = pkd_flow(r0.pkd);
             mn1 = r1.mn; P1f = r1.chg; mx1 = r1.mx; ln1 = pkd_line(r1.pkd); F1i = pkd_flow(r1.pkd);
@@ -3217,6 +3312,16 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
             z_wd = sa.exo_z[e32 * 3u + 1u];
             z_pr = sa.exo_z[e32 * 3u + 2u];
         }
+        if (PAIR == 1) {  // the second step's inputs, behind this step's own requests: its waits leave them in flight
+            typedef float f32x2_ __attribute__((ext_vector_type(2)));
+            nx->r0 = ((CHUB_G(const u32x4)) ta2->rec)[e32];
+            nx->r1 = ((CHUB_G(const u32x4)) ta2->rec)[n32 + e32];
+            const f32x2_ tv = ((CHUB_G(const f32x2_)) ta2->tail_act)[e32];
+            nx->in.a_el = tv.x;
+            nx->in.a_fc = tv.y;
+            nx->in.drw = ((CHUB_G(const u32x4)) ta2->drw)[e32];
+            nx->in.drw_n = ta2->drw_cnt[e32];
+        }
     }
 
 
@@ -3232,7 +3337,7 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
         const int i = threadIdx.x;
         if (i < 100) ((double *) s_pv)[i] = st_pv;
         if (i < 150) ((double *) s_wd)[i] = st_wd;
-        if (!RESET) {
+        if (!RESET && PAIR != 2) {
             if (i < 100) ((double *) s_pv_now)[i] = st_pv_now;
             if (i < 150) ((double *) s_wd_now)[i] = st_wd_now;
             if (!EP && i < 102) ((double *) s_hy)[i] = st_hy;
@@ -3452,6 +3557,10 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
             hv_line = 0;
         }
         total_mass_need = total_mass;
+        if (PAIR == 1) {
+            nx->in.q_len = q_len;
+            nx->in.hv_line = hv_line | (stuck ? 128 : 0);  // (the byte in memory: the line, and whether the list is stuck)
+        }
     }
     mid.at1();
 
@@ -3472,9 +3581,11 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
             price_next = ou_sample(ou_price, .1, 0.005, z_pr) * HP_E(price_fluct1, p_price_fluct1);
             ev.ou[2u * n32 + e32] = ou_price;
             ev.price_noise[e32] = price_next;
+            if (PAIR == 1) nx->in.price_noise = price_next;
             price_next += price_last;
         } else {
             price_next = price_last + in_price_noise;
+            if (PAIR == 1) nx->in.price_noise = in_price_noise;
         }
     }
     if (MODE == MODE_COMPAT && !RESET && !hv_walked) rs.store(cr, sa.rng_cur, env);
@@ -3641,6 +3752,14 @@ __device__ __forceinline__ void env_tail(const DevCtx *__restrict__ ctx, const S
     }
 
     ev.cap[e32] = cap;
+    if (PAIR == 1) {  // the env's state behind this step, for the pair's second step in this lane
+        nx->in.ou_pv = ou_pv;
+        nx->in.ou_wd = ou_wd;
+        nx->in.ou_price = ou_price;
+        nx->in.cap = cap;
+        nx->in.pv_day = pv_day;
+        nx->in.wd_day = wd_day;
+    }
 
     // state_norm (MGR:318-342) of what make_state (MGR:362-373) collects, written straight to the output row
     float *obs = s_out + (FUSED ? (int) (threadIdx.x & 63u) : (int) threadIdx.x) * row_w;
@@ -3810,6 +3929,132 @@ __global__ __launch_bounds__(kEnvBlock) void k_env(const DevCtx *__restrict__ ct
     NoMid nomid;
     env_tail<RESET, MODE, MULTI, false, NoMid, kEnvBlock, TAPE, EP>(ctx, sa, env, env < (int) ta.n_envs && (!MULTI || in_group(sa, env)), s_pv, s_wd, s_pv_now,
                                                                 s_wd_now, s_hy, s_hv, s_out, blk, ta, nullptr, 0, 0, 0, none, false, nomid);
+}
+
+// ---------------------------------------------------------------------------------------- k_env_pair: the tails of TWO steps in one launch
+// Large PHILOX batches inside chub_run_steps (the plan's pair rule, chub_plan.h): the launches of a pair of lock-step steps go slot(i), slot(i + 1),
+// tails(i and i + 1) -- nothing in a step's slot phases reads what the previous step's tail writes -- so the tail launch's fixed costs (kernel
+// boundary, the cold start of its load burst, the drain of its rows) are paid once per two steps.  What a pair keeps apart:
+//   * records and tail actions: the pair's first slot launch writes PairArgs::rec_a / tail_act_a, its second the handle's own arrays
+//     (StationArrays::rec / tail_act), so behind a pair the handle holds what a single step would have left;
+//   * station draws: the first step's are decoded ahead as ever (StationArrays::pk, against the records of the step before the pair); the
+//     second step's wait raw in PairArgs::pkraw and are decoded by its own slot launch (slot_body_packed<.., RAW>);
+//   * env draws: a pair reads PairArgs::drw_in[0 / 1] and (MORE) writes the next pair's into drw_out[0 / 1], the other block of two.
+// MORE: another pair follows at once (same day, same call).  Otherwise the launch leaves the handle where any other entry point can go on: the
+// next step's draws where a single step's tail launch leaves them (level_block), and in the other parity what it would have found there.
+struct PairArgs {
+    CHUB_G(const uint32_t) rec_a;     // [2N][4] the records of the pair's first step
+    CHUB_G(uint64_t) pkraw;           // [2N] raw station draws: in, the pair's second step's (not MORE: decoded into pk for whoever looks); out, the next pair's
+    CHUB_G(const uint32_t) drw_in[2]; // [N][4] the env draws of the pair's two steps, and
+    CHUB_G(const uint8_t) cnt_in[2];  // [N]   their FCEV arrival counts
+    CHUB_G(uint32_t) drw_out[2];      // MORE: the next pair's
+    CHUB_G(uint8_t) cnt_out[2];
+};
+
+// a step's state-independent env draws (level_block's, same Philox sites and counters): three OU normals and the first FCEV arrival, for slot t of the day
+__device__ __forceinline__ void draw_env_pre(const DevCtx *__restrict__ ctx, const uint32_t tick, const int t, const uint32_t e, CHUB_G(uint32_t) drw,
+                                             CHUB_G(uint8_t) cnt_out) {
+    const HubParams &hp = ctx->hp;
+    const Tables &tb = ctx->tb;
+    PhiloxCtx px{hp.key[0], hp.key[1], tick, (uint32_t) (hp.env_id0 + e)};
+    const U4 ow = px.block(SITE_OU, 0, 0);  // word 0 pv, 1 wind, 2 price
+    const uint32_t hv_lev = px.block(SITE_HV, 0, 0).v[0] % 1000u;
+    u32x4 d;
+    d.x = __float_as_uint(normal_from_word(tb.normal_icdf, tb.normal_tail, ow.v[0]));
+    d.y = __float_as_uint(normal_from_word(tb.normal_icdf, tb.normal_tail, ow.v[1]));
+    d.z = __float_as_uint(normal_from_word(tb.normal_icdf, tb.normal_tail, ow.v[2]));
+    const uint32_t cnt = (uint32_t) tb.cnt_hv[(uint32_t) t * (uint32_t) kLevels + hv_lev];
+    d.w = cnt != 0u ? __float_as_uint(soc_from_word(tb.soc_d_icdf, px.block(SITE_HVSOC, 0, 0).v[0])) : 0u;  // the first arrival's SoC
+    ((CHUB_G(u32x4)) drw)[e] = d;
+    cnt_out[e] = (uint8_t) cnt;
+}
+
+// lane u of the level workgroups of a launch ([0, 2N) units, [2N, 3N) envs) -> its place, in XCD-aware order where the launch divides evenly (k_env)
+__device__ __forceinline__ bool level_lane(const uint32_t jb, const uint32_t n32, const int nb_env, const uint32_t xcd, int64_t &u) {
+    const uint32_t per = n32 >> 3;
+    if (xcd && (n32 & 2047u) == 0u && ((uint32_t) nb_env & 7u) == 0u) {
+        const uint32_t x = jb & 7u, i = jb >> 3, wpx = per / kEnvBlock;
+        const uint32_t seg = i / wpx;
+        u = (int64_t) seg * n32 + (int64_t) (x * per + (i - seg * wpx) * kEnvBlock + threadIdx.x);
+        return seg < 3u;
+    }
+    u = (int64_t) jb * kEnvBlock + threadIdx.x;
+    return u < 3 * (int64_t) n32;
+}
+
+// In front of a chain of pairs: what no earlier launch has left -- the raw station draws of the first pair's second step and the env draws of
+// both its steps (sa: the pair's first step; its decoded station draws are in pk[tick & 1] already)
+__global__ __launch_bounds__(kEnvBlock) void k_pair_draws(const DevCtx *__restrict__ ctx, StepArgs sa, PairArgs pr, uint32_t xcd) {
+    const HubParams &hp = ctx->hp;
+    const uint32_t n32 = (uint32_t) hp.n_envs;
+    int64_t u;
+    if (!level_lane(blockIdx.x, n32, 8, xcd, u)) return;
+    const uint32_t tick1 = CHUB_TICK(hp, sa.tick + 1u);
+    if (u < 2 * (int64_t) n32) {
+        const int kk = u >= (int64_t) n32 ? 1 : 0;
+        const int want = dk_want(ctx->st.pk[sa.tick & 1u][u]);
+        pr.pkraw[u] = draw_raw_levels(hp, ctx->tb, tick1, sa.t + 1, kk, u - (int64_t) kk * n32, want, hp.type[kk] == 0);
+    } else {
+        const uint32_t e = (uint32_t) (u - 2 * (int64_t) n32);
+        draw_env_pre(ctx, tick1 - 1u, sa.t, e, pr.drw_out[0], pr.cnt_out[0]);
+        draw_env_pre(ctx, tick1, sa.t + 1, e, pr.drw_out[1], pr.cnt_out[1]);
+    }
+}
+
+template <bool MORE>
+__global__ __launch_bounds__(kEnvBlock) void k_env_pair(const DevCtx *__restrict__ ctx, StepArgs sa, StepArgs sb, TailArgs ta, TailArgs tb2, PairArgs pr,
+                                                        int nb_env) {
+    __shared__ double s_pv[100], s_wd[150], s_pv_now[100], s_wd_now[150], s_hy[102], s_pv2[100], s_wd2[150];
+    __shared__ __attribute__((aligned(16))) float s_out[2][kEnvBlock * 16];  // each step's output rows
+    if ((int) blockIdx.x >= nb_env) {
+        const HubParams &hp = ctx->hp;
+        const uint32_t n32 = (uint32_t) hp.n_envs;
+        int64_t u;
+        if (!level_lane(blockIdx.x - (uint32_t) nb_env, n32, nb_env, ta.xcd, u)) return;
+        if (!MORE) {
+            // what the tail launch of the pair's second step alone would leave for the step behind it ...
+            level_block<false, false>(ctx, sb, u);
+            // ... and what it would have found: that step's own draws, in the other parity
+            if (u < 2 * (int64_t) n32) {
+                const int kk = u >= (int64_t) n32 ? 1 : 0;
+                ctx->st.pk[sb.tick & 1u][u] = dk_make(pr.pkraw[u], pkd_line(pr.rec_a[4u * (uint32_t) u + 3u]), hp.type[kk] == 0);
+            } else {
+                const uint32_t e = (uint32_t) (u - 2 * (int64_t) n32);
+                ((CHUB_G(u32x4)) ctx->ev.drw[sb.tick & 1u])[e] = ((CHUB_G(const u32x4)) pr.drw_in[1])[e];
+                ctx->ev.drw_cnt[sb.tick & 1u][e] = pr.cnt_in[1][e];
+            }
+            return;
+        }
+        const uint32_t tick2 = CHUB_TICK(hp, sb.tick + 1u);  // the next pair's first step
+        if (u < 2 * (int64_t) n32) {
+            const int kk = u >= (int64_t) n32 ? 1 : 0;
+            const bool fast = hp.type[kk] == 0;
+            const int64_t env_ = u - (int64_t) kk * n32;
+            // its first step: drawn and decoded against the queue the pair's second slot launch has left, as ever
+            const int line_now = pkd_line(ctx->st.rec[4u * (uint32_t) u + 3u]);
+            const uint32_t dk = draw_decoded_levels(hp, ctx->tb, tick2, sb.t + 1, kk, env_, line_now, fast);
+            ctx->st.pk[(sb.tick + 1u) & 1u][u] = dk;
+            // its second step: raw, in the same lane -- the queue in front of it cannot exceed the first step's `want`
+            pr.pkraw[u] = draw_raw_levels(hp, ctx->tb, tick2 + 1u, sb.t + 2, kk, env_, dk_want(dk), fast);
+        } else {
+            const uint32_t e = (uint32_t) (u - 2 * (int64_t) n32);
+            draw_env_pre(ctx, tick2, sb.t + 1, e, pr.drw_out[0], pr.cnt_out[0]);
+            draw_env_pre(ctx, tick2 + 1u, sb.t + 2, e, pr.drw_out[1], pr.cnt_out[1]);
+        }
+        return;
+    }
+    const int blk = (int) xcd_order(blockIdx.x, (uint32_t) nb_env, ta.xcd);
+    const int env = blk * kEnvBlock + (int) threadIdx.x;
+    const bool live = env < (int) ta.n_envs;
+    TailIn none;
+    TailNext nx;
+    NoMid nomid;
+    env_tail<false, MODE_PHILOX, false, false, NoMid, kEnvBlock, false, false, 1>(ctx, sa, env, live, s_pv, s_wd, s_pv_now, s_wd_now, s_hy, nullptr, s_out[0], blk, ta,
+                                                                                  nullptr, 0, 0, 0, none, false, nomid, &nx, &tb2);
+    // the second step, same lane: the env's state from registers, its other inputs as the first step's burst brought them; its rows of "now" are
+    // the first step's rows of "next"
+    env_tail<false, MODE_PHILOX, false, false, NoMid, kEnvBlock, false, false, 2>(ctx, sb, env, live, s_pv2, s_wd2, s_pv, s_wd, s_hy, nullptr, s_out[1], blk, tb2,
+                                                                                  nullptr, 0, 0, 0, nx.in, true, nomid, &nx, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------- k_env_walk: COMPAT, the split step's second launch
@@ -5502,6 +5747,7 @@ static PackedArgs make_packed_args(const HubParams &hp, const StepArgs &sa, cons
     pa.xcd = hp.xcd ? (uint32_t) ((hp.n_envs + hp.epb - 1) / hp.epb) : 0u;  // (the grid of an unmasked launch: launch_slot)
     pa.tail_act = (CHUB_G(float)) pp.st->tail_act;
     pa.stay8 = (CHUB_G(uint8_t)) pp.stay8;
+    pa.rec_prev = nullptr;
     return pa;
 }
 
@@ -5617,6 +5863,57 @@ void launch_env_walk(const HubParams &hp, const DevCtx *ctx, const StepArgs &sa,
     const int nb_env = (int) ((hp.n_envs + kEnvBlock - 1) / kEnvBlock);
     const unsigned nb = (unsigned) nb_env + (unsigned) ((hp.n_envs + 255) / 256);
     CHUB_LAUNCH(k_env_walk, dim3(nb), dim3(kEnvBlock), stream, ev0, ev1, ctx, sa, ta, sw, nb_env);
+}
+
+// A pair of lock-step steps of every env whose tails share one launch (k_env_pair; PHILOX handles on the small tile of the packed slot kernel):
+// sa / sb: the pair's first and second step; chain_start: no pair ran right before this one (k_pair_draws first, behind the first step's own
+// station draws if that step is a fresh one); more: another pair follows at once; sel: which of the two blocks of env draws this pair reads
+void launch_pair(const HubParams &hp, const DevCtx *ctx, const StepArgs &sa_in, const StepArgs &sb_in, hipStream_t stream, const PackedPtrs &pp,
+                 const PairBufs &pb, int sel, bool chain_start, bool more) {
+    StepArgs sa = sa_in, sb = sb_in;
+    const int64_t N = hp.n_envs;
+    const int nb_env = (int) ((N + kEnvBlock - 1) / kEnvBlock);
+    const unsigned nb_lev = (unsigned) ((3 * N + kEnvBlock - 1) / kEnvBlock);
+    PairArgs pr;
+    pr.rec_a = (CHUB_G(const uint32_t)) pb.rec_a;
+    pr.pkraw = (CHUB_G(uint64_t)) pb.pkraw;
+    for (int q = 0; q < 2; q++) {
+        pr.drw_in[q] = (CHUB_G(const uint32_t)) pb.drw[sel][q];
+        pr.cnt_in[q] = (CHUB_G(const uint8_t)) pb.cnt[sel][q];
+        pr.drw_out[q] = (CHUB_G(uint32_t)) pb.drw[sel ^ 1][q];
+        pr.cnt_out[q] = (CHUB_G(uint8_t)) pb.cnt[sel ^ 1][q];
+    }
+    const uint32_t xcd = hp.xcd ? 1u : 0u;
+    if (chain_start) {
+        launch_levels(sa.fresh ? LEVELS_DRAW : LEVELS_NONE, ctx, sa, stream);
+        PairArgs p0 = pr;  // (the prologue fills the blocks this pair reads)
+        for (int q = 0; q < 2; q++) {
+            p0.drw_out[q] = (CHUB_G(uint32_t)) pb.drw[sel][q];
+            p0.cnt_out[q] = (CHUB_G(uint8_t)) pb.cnt[sel][q];
+        }
+        hipLaunchKernelGGL(k_pair_draws, dim3(nb_lev), dim3(kEnvBlock), 0, stream, ctx, sa, p0, xcd);
+    }
+    sa.fresh = 0;  // (every draw of both steps has been made ahead)
+    sb.fresh = 0;
+    const uint32_t nb = (uint32_t) ((N + hp.epb - 1) / hp.epb);
+    PackedArgs pa = make_packed_args(hp, sa, pp);
+    pa.rec = (CHUB_G(uint32_t)) pb.rec_a;
+    pa.tail_act = (CHUB_G(float)) pb.tail_act_a;
+    hipLaunchKernelGGL((k_slot_packed<kPackedBlock, kSlotsPerLane, false, false, false, false>), dim3(nb), dim3(kPackedBlock), 0, stream, ctx, sa, pa);
+    PackedArgs pa2 = make_packed_args(hp, sb, pp);
+    pa2.pk = (CHUB_G(const uint32_t)) (const void *) pb.pkraw;
+    pa2.rec_prev = (CHUB_G(const uint32_t)) pb.rec_a;
+    hipLaunchKernelGGL((k_slot_packed<kPackedBlock, kSlotsPerLane, false, false, false, false, false, true>), dim3(nb), dim3(kPackedBlock), 0, stream, ctx,
+                       sb, pa2);
+    TailArgs ta = make_tail_args(*pp.ev, *pp.st, hp, sa, pp, false), tb2 = make_tail_args(*pp.ev, *pp.st, hp, sb, pp, false);
+    ta.rec = (CHUB_G(uint32_t)) pb.rec_a;
+    ta.tail_act = (CHUB_G(const float)) pb.tail_act_a;
+    ta.drw = pr.drw_in[0];
+    ta.drw_cnt = pr.cnt_in[0];
+    tb2.drw = pr.drw_in[1];
+    tb2.drw_cnt = pr.cnt_in[1];
+    if (more) hipLaunchKernelGGL(k_env_pair<true>, dim3((unsigned) nb_env + nb_lev), dim3(kEnvBlock), 0, stream, ctx, sa, sb, ta, tb2, pr, nb_env);
+    else hipLaunchKernelGGL(k_env_pair<false>, dim3((unsigned) nb_env + nb_lev), dim3(kEnvBlock), 0, stream, ctx, sa, sb, ta, tb2, pr, nb_env);
 }
 
 __global__ void k_tick_advance(uint32_t *tick_base, uint32_t by) { *tick_base += by; }

@@ -20,6 +20,9 @@ namespace chub {
 #ifndef CHUB_SPLIT2
 #define CHUB_SPLIT2 1  // the split step's slot pass with two slots per lane (slot_body_split2); 0: slot_body_compat<.., SPLIT> for every step
 #endif
+#ifndef CHUB_PAIR_MIN_ENVS
+#define CHUB_PAIR_MIN_ENVS 8192
+#endif
 constexpr int64_t kBigTileSlots = (int64_t) 10 << 20;  // handles of at least this many charger slots take the second tile (chub_options.tile overrides)
 constexpr int64_t kXcdOrderSlots = (int64_t) 6 << 20;  // handles of at most this many charger slots (their streams live in the caches) run their
                                                        // step kernels in XCD-aware work order
@@ -34,6 +37,12 @@ constexpr int kSpanMaxBlocks = 384;           // chub_run_steps's spans of steps
 constexpr int kFusedMaxBlocks = 384;   // PHILOX lock-step steps of at most this many slot workgroups run as ONE launch (k_step_fused).  Measured, us per step
                                        // as graph replays, one launch vs two: 8.08 vs 8.82 at 128 workgroups (C2), 8.50 vs 9.30 at 256, 9.42 vs 9.79 at 373,
                                        // 10.79 vs 10.61 at 745, 11.71 vs 11.38 at 1024, 17.9 vs 13.1 at 1490
+// chub_run_steps on the two-launch PHILOX step: pairs of steps whose tails share ONE launch (k_env_pair: slot(i), slot(i + 1), tails(i and i + 1)) from
+// this many envs on (chub_options.span_steps overrides: 1 = never, 2 and more = at any size).  The tail launch's fixed costs -- kernel boundary, the cold start of its load burst,
+// the drain of its rows -- are then paid once per two steps.  Measured, us per step as graph replays of two days, every step two launches vs pairs
+// ([20, 25] hub): 8704 envs 10.35 vs 9.65; 16 384: 11.74 vs 11.40; 24 576: 14.42 vs 13.84; 32 768: 16.53 vs 15.95; 65 536: 24.62 vs 23.86 -- a gain
+// at every size at which that hub's step is two launches; smaller handles on the two-launch step were not measured and keep the per-step path.
+constexpr int64_t kPairMinEnvs = CHUB_PAIR_MIN_ENVS;
 // Envs per walk workgroup of k_slot_walk2 (one wave walks them): 64, or -- batches of at most kWalk2HalfMaxEnvs envs -- 32: twice the walking
 // waves, each with half the cars to evaluate (all 64 lanes still evaluate).  A small batch's launch lasts as long as its longest walk
 // (4096 envs: 27.0 -> 22.3 us, 16 384: 31.1 -> 26.8, 32 768: 37.7 -> 33.2, 40 000: 40.4 -> 39.7); a large one is bound by instruction issue,
@@ -189,6 +198,34 @@ inline int plan_params(LaunchPlan &p, int rng_mode, const char **msg) {
     p.span_size_ok = 0;
     p.span_piped = 0;
     return CHUB_OK;
+}
+
+// ---- pairs of steps whose tails share one launch (chub_run_steps; k_env_pair in chub_kernels.hip)
+// per handle: the form exists for it -- its slot launch decodes the second step's raw draws in the unit pass of the lock-step small tile, its tail
+// is the homogeneous PHILOX tail, its step is two launches (a handle on the one-launch step sends whole spans out as one launch) -- and is wanted:
+// chub_options.span_steps, which bounds the steps per tail launch here as it bounds the steps per launch there, is 0 (by size) or at least 2
+inline bool plan_pair_handle(const LaunchPlan &p, int64_t n_envs, const chub_options &opt, bool env_params) {
+    if (p.packed != PACKED_SMALL || p.one_launch != ONE_NONE || env_params || opt.span_steps == 1) return false;
+    return opt.span_steps >= 2 || n_envs >= kPairMinEnvs;
+}
+// per call of chub_run_steps: lock-step steps of every env into the packed blocks and nothing else that reads a step's tail before the next
+// step's slot launch, or between the two
+struct PairState {
+    bool comm;         // a communicator gathers every step's block
+    bool per_env;      // the handle runs on per-env clocks
+    bool tape;         // a tape handle
+    bool outputs;      // step terms, the episode ledger or telemetry are attached
+    bool profiling;    // the per-kernel profiler samples step launches
+};
+inline bool plan_pair_call(bool handle_pairs, const PairState &c) {
+    return handle_pairs && !c.comm && !c.per_env && !c.tape && !c.outputs && !c.profiling;
+}
+// how many of the next `left` steps of a call go out as pairs when the handle's clock shows slot t of the day: pairs never straddle the day's
+// end or the call's; an odd step out goes by the per-step path
+inline int64_t pair_steps(int t, int64_t left) {
+    const int64_t day = 96 - t;
+    const int64_t k = left < day ? left : day;
+    return k > 0 ? k & ~(int64_t) 1 : 0;
 }
 
 // ---- per call

@@ -58,6 +58,8 @@ void launch_slot_walk2(const LaunchPlan &lp, const HubParams &hp, const DevCtx *
                        hipEvent_t ev0, hipEvent_t ev1);
 void launch_env_walk(const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, const StepArgs &sw, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
                      const PackedPtrs &pp);
+void launch_pair(const HubParams &hp, const DevCtx *ctx, const StepArgs &sa, const StepArgs &sb, hipStream_t stream, const PackedPtrs &pp,
+                 const PairBufs &pb, int sel, bool chain_start, bool more);
 }  // namespace chub
 
 using namespace chub;
@@ -94,6 +96,11 @@ struct chub_env {
     Tables tb;
     int device;
     LaunchPlan plan;           // the launch forms of this handle (chub_plan.h)
+    // chub_run_steps sends pairs of steps out with one tail launch (plan_pair_handle): what a pair keeps apart from the handle's arrays, ONE block
+    // outside the arena -- scratch: every chain of pairs fills what it reads, no snapshot carries it, no copy moves it
+    bool pair_tails = false;
+    PairBufs pair = {};
+    char *d_pair = nullptr;
     int rng_cur = 0;           // COMPAT: which of CompatRng's three buffers holds the committed streams (moved on by every commit: chub_device.h)
     uint32_t walked_tick = 0;  // COMPAT split step: the tick whose stream walk has run already, beside the previous step's tails (0: none)
     uint32_t e2_tick = ~0u;    // ... and the tick of the pass after which StationArrays::empt2 holds every unit's count (what a walk two steps ahead needs)
@@ -541,6 +548,7 @@ static int create_impl(const chub_config *cfg_in, const char *data_dir, int64_t 
     e->cfg = *cfg_in;
     e->env_params = rows != nullptr;
     e->plan = plan;
+    e->pair_tails = plan_pair_handle(plan, n_envs, opt, rows != nullptr);
     e->public_mode = public_mode;
     e->device = device;
     e->t = 0;
@@ -1052,6 +1060,26 @@ static int create_impl(const chub_config *cfg_in, const char *data_dir, int64_t 
         e->d_gae_part = nullptr;
         return bail(fail(CHUB_ERR_HIP, "hipMalloc failed"));
     }
+    if (e->pair_tails) {  // records 32 N, tail actions 8 N, raw draws 16 N, env draws 4 x (16 N + N) bytes, each part 256-byte aligned
+        const size_t Np = (size_t) n_envs;
+        auto up = [](size_t b) { return (b + 255) & ~(size_t) 255; };
+        const size_t b_rec = up(32 * Np), b_act = up(8 * Np), b_raw = up(16 * Np), b_drw = up(16 * Np), b_cnt = up(Np);
+        const size_t total = b_rec + b_act + b_raw + 4 * (b_drw + b_cnt);
+        if (hipMalloc((void **) &e->d_pair, total) != hipSuccess) {
+            e->d_pair = nullptr;
+            return bail(fail(CHUB_ERR_HIP, "hipMalloc failed"));
+        }
+        if (hipMemset(e->d_pair, 0, total) != hipSuccess) return bail(fail(CHUB_ERR_HIP, "hipMemset failed"));
+        char *q = e->d_pair;
+        e->pair.rec_a = (uint32_t *) q; q += b_rec;
+        e->pair.tail_act_a = (float *) q; q += b_act;
+        e->pair.pkraw = (uint64_t *) q; q += b_raw;
+        for (int a = 0; a < 2; a++)
+            for (int b = 0; b < 2; b++) {
+                e->pair.drw[a][b] = (uint32_t *) q; q += b_drw;
+                e->pair.cnt[a][b] = (uint8_t *) q; q += b_cnt;
+            }
+    }
     *out = e;
     return CHUB_OK;
 }
@@ -1082,6 +1110,7 @@ int chub_destroy(chub_env *e) {
         if (e->fc.mean) (void) hipFree((void *) e->fc.mean);
         if (e->d_ep_sum) (void) hipFree(e->d_ep_sum);
         if (e->d_gae_part) (void) hipFree(e->d_gae_part);
+        if (e->d_pair) (void) hipFree(e->d_pair);
         if (e->h_bits) (void) hipHostFree(e->h_bits);  // h_tail / d_tail are the ends of the same blocks
         if (e->d_bits) (void) hipFree(e->d_bits);
         if (e->d_packed) (void) hipFree(e->d_packed);
@@ -1110,6 +1139,34 @@ int chub_uses_xcd_order(const chub_env *e) {  // (the single-launch step has one
     return e ? ((e->hp.packed && e->hp.xcd && e->plan.one_launch == ONE_NONE) ? 1 : 0) : CHUB_ERR_ARG;
 }
 int chub_uses_fused_step(const chub_env *e) { return e ? ((e->plan.one_launch != ONE_NONE || e->plan.compat_small) ? 1 : 0) : CHUB_ERR_ARG; }
+
+int chub_uses_pair_tails(const chub_env *e) { return e ? (e->pair_tails ? 1 : 0) : CHUB_ERR_ARG; }
+
+int chub_pair_plan(const chub_config *cfg, int64_t n_envs, int rng_mode, const chub_options *opt_in, int env_params, uint32_t flags, int t, int64_t left,
+                   int64_t *out) {
+    if (!cfg || !out) return fail(CHUB_ERR_ARG, "null argument");
+    if (t < 0 || t > 95 || left < 0) return fail(CHUB_ERR_ARG, "t must be 0 .. 95 and left >= 0");
+    chub_options opt;
+    memset(&opt, 0, sizeof opt);
+    if (opt_in) opt = *opt_in;
+    LaunchPlan p;
+    const char *msg = nullptr;
+    if (const int rc = plan_handle(cfg, n_envs, rng_mode, opt, p, &msg)) return fail(rc, msg);
+    if (env_params)
+        if (const int rc = plan_params(p, rng_mode, &msg)) return fail(rc, msg);
+    const bool handle = plan_pair_handle(p, n_envs, opt, env_params != 0);
+    PairState c;
+    c.comm = (flags & CHUB_PAIRF_COMM) != 0;
+    c.per_env = (flags & CHUB_PAIRF_PER_ENV) != 0;
+    c.tape = (flags & CHUB_PAIRF_TAPE) != 0;
+    c.outputs = (flags & CHUB_PAIRF_OUTPUTS) != 0;
+    c.profiling = (flags & CHUB_PAIRF_PROFILING) != 0;
+    const bool call = plan_pair_call(handle, c);
+    out[CHUB_PAIR_HANDLE] = handle ? 1 : 0;
+    out[CHUB_PAIR_CALL] = call ? 1 : 0;
+    out[CHUB_PAIR_STEPS] = call ? pair_steps(t, left) : 0;
+    return CHUB_OK;
+}
 
 int chub_launch_plan(const chub_config *cfg, int64_t n_envs, int rng_mode, const chub_options *opt_in, int32_t *out) {
     if (!cfg || !out) return fail(CHUB_ERR_ARG, "null argument");
@@ -1748,6 +1805,54 @@ static int run_span(chub_env *e, const float *const *batches, int n_batches, flo
     return note_served(e, nullptr, 2, s);
 }
 
+// chub_run_steps on a handle whose pairs of steps share one tail launch (plan_pair_handle / plan_pair_call): n_pairs pairs from step `first`, all
+// within the handle's day.  Every pair is slot(i), slot(i + 1), tails(i and i + 1); the first is preceded by the draws no earlier launch has
+// left, the last leaves the handle as single steps would (launch_pair).
+static bool pairs_ok(const chub_env *e, const chub_comm *comm) {
+    PairState c;
+    c.comm = comm != nullptr;
+    c.per_env = e->per_env;
+    c.tape = e->tape_only;
+    c.outputs = e->st_out != nullptr || e->es.on != 0 || e->hp.telemetry != 0;
+    c.profiling = e->prof_on;
+    return plan_pair_call(e->pair_tails, c) && e->tick != 0;
+}
+
+static int run_pairs(chub_env *e, const float *const *batches, int n_batches, float *const *packed2, int64_t first, int64_t n_pairs, hipStream_t s) {
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    const MaskView all = {nullptr, 0, e->hp.n_envs - 1};
+    int sel = 0;
+    for (int64_t p = 0; p < n_pairs; p++) {
+        const int64_t i = first + 2 * p;
+        const StepCall c1 = step_call(nullptr, batches[i % n_batches], nullptr, packed_out(e, packed2[i & 1]), 0);
+        const StepCall c2 = step_call(nullptr, batches[(i + 1) % n_batches], nullptr, packed_out(e, packed2[(i + 1) & 1]), 0);
+        StepArgs sa, sb;
+        if (const int rc = fill_args(e, c1, 2, all, e->tick + 1u, s, sa)) return rc;
+        {   // the second step's arguments: as the handle will stand behind the first
+            const int t0 = e->t, pc0 = e->price_count;
+            const bool pd0 = e->predrawn;
+            e->t = t0 + 1;
+            e->price_count = pc0 + 1;
+            e->predrawn = true;
+            const int rc = fill_args(e, c2, 2, all, e->tick + 2u, s, sb);
+            e->t = t0;
+            e->price_count = pc0;
+            e->predrawn = pd0;
+            if (rc) return rc;
+        }
+        launch_pair(e->hp, e->d_ctx, sa, sb, s, packed_ptrs(e), e->pair, sel, p == 0, p + 1 < n_pairs);
+        if (hipGetLastError() != hipSuccess) {
+            e->predrawn = false;
+            return fail(CHUB_ERR_HIP, "a pair of steps could not be launched");
+        }
+        e->tick += 2u;
+        advance_clocks(e, c1, 2, 2);
+        sel ^= 1;
+    }
+    return note_served(e, nullptr, 2, s);
+}
+
 // A run of steps issued from C: what a host loop of chub_reset_device / chub_step_device_packed / chub_step_gather calls does, without
 // a trip through the host language per step (multi-GPU shards of a few thousand envs are otherwise bound by the host's issue rate)
 int chub_run_steps(chub_env *e, chub_comm *comm, const float *const *d_action_batches, int n_batches, float *const *d_packed2,
@@ -1758,6 +1863,15 @@ int chub_run_steps(chub_env *e, chub_comm *comm, const float *const *d_action_ba
     for (int64_t i = first_step; i < first_step + n_steps; i++) {
         int rc;
         if (i % 96 == 0 && (rc = chub_reset_device(e, nullptr, nullptr, d_reset_obs, stream))) return rc;
+        // PAIRS of steps with one tail launch (k_env_pair) where the plan says so: up to the day's end or the call's, an odd step out by the paths below
+        if (pairs_ok(e, comm)) {
+            const int64_t k2 = pair_steps(e->t, std::min<int64_t>(first_step + n_steps - i, 96 - i % 96));
+            if (k2 >= 2) {
+                if ((rc = run_pairs(e, d_action_batches, n_batches, d_packed2, i, k2 / 2, (hipStream_t) stream))) return rc;
+                i += k2 - 1;
+                continue;
+            }
+        }
         // a SPAN of steps in ONE launch (k_steps_fused) where the handle runs the one-launch step anyway: up to the day's end or the call's
         if (!comm) {
             int64_t k = first_step + n_steps - i;

@@ -829,7 +829,7 @@ class VecChargingHub(object):
         opt.fused_step = _lib.FUSED_STEP[fused_step]  # "auto": one launch per step for small batches; "off" / "on" (parity cross-check)
         opt.tile = _lib.TILES[tile]  # packed slot kernel: "auto" (by working-set size), "small" (256 x 2) or "large" (512 x 4)
         opt.walk_ahead = _lib.WALK_AHEAD[walk_ahead]  # COMPAT batches: "auto" (step i + 1's stream walks beside step i's tails) or "off"
-        opt.span_steps = 0 if span_steps == "auto" else (1 if span_steps == "off" else int(span_steps))  # chub_run_steps: steps per launch (one-launch handles)
+        opt.span_steps = 0 if span_steps == "auto" else (1 if span_steps == "off" else int(span_steps))  # chub_run_steps: steps per launch (one-launch handles); two-launch handles: pairs of steps with ONE tail launch ("auto": large batches, "off", 2: always)
         opt.span_tails = {"auto": 0, "same_wave": 1, "own_wave": 2}[span_tails]  # ... and the wave a span's tails run on (own_wave: a step behind the slots)
         opt.work_order = _lib.WORK_ORDER[work_order]  # PHILOX packed kernels: "auto" (XCD-aware while the streams are cache-resident) or "dispatch"
         self._copy_outputs = bool(copy_outputs)
@@ -1156,6 +1156,11 @@ class VecChargingHub(object):
     @property
     def uses_fused_step(self):
         return bool(self._lib.chub_uses_fused_step(self._h))
+
+    @property
+    def uses_pair_tails(self):
+        """chub_run_steps sends pairs of lock-step steps out with one tail launch (chub_options.span_steps on the two-launch step)"""
+        return bool(self._lib.chub_uses_pair_tails(self._h))
 
     @property
     def uses_xcd_order(self):

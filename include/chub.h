@@ -117,7 +117,13 @@ typedef struct chub_options {
                              (k_steps_fused: each workgroup goes from step to step by itself, one workgroup barrier between steps; a span ends
                              at the day's end at the latest): 0 = as many steps as the call and the day allow (default), 1 = never (every step
                              a launch: the parity cross-check), n = at most n steps per launch.  Results are bit-identical.  Of a span's packed
-                             outputs the last two blocks remain (the policy is open loop over the span: the call's own action batches). */
+                             outputs the last two blocks remain (the policy is open loop over the span: the call's own action batches).
+                             On a PHILOX handle that runs the TWO-launch step on the small tile of the packed slot kernel (stations of at most 64 piles)
+                             the same option bounds the steps per TAIL launch: chub_run_steps sends PAIRS of lock-step steps out as three launches --
+                             slot(i), slot(i + 1), then the per-env tails of both steps in one launch (k_env_pair) -- instead of four: 0 = from 8192
+                             envs on (default), 1 = never, 2 and more = at any size.  Pairs never straddle a day's end or the call's; an odd step out
+                             goes by the per-step path.  Not with a communicator, on per-env clocks, on a tape handle, on a handle with per-env hub
+                             parameters, under the profiler or with step terms, episode statistics or telemetry attached.  Bit-identical as well. */
     int32_t span_tails;   /* ... and where a span's per-env tails run: 0 = by size (default: up to 256 workgroups -- one per CU -- as 2, beyond as 1), 1 = on the
                              workgroup's last slot wave, behind its slot phases (k_steps_fused), 2 = on a fifth wave of the workgroup, ONE STEP BEHIND
                              the slot waves (k_steps_piped: the slot phases of step s + 1 read nothing the tails of step s write, so the two chains of a
@@ -197,6 +203,14 @@ int chub_set_env_params(chub_env *env, const uint8_t *mask /* host, NULL = all *
 int chub_get_env_params(chub_env *env, chub_env_params *rows /* [N] */);
 int chub_has_env_params(const chub_env *env);
 int chub_launch_plan_params(const chub_config *cfg, int64_t n_envs, int rng_mode, const chub_options *opt /* NULL = defaults */, int32_t *out);
+/* The pair rule of chub_run_steps (chub_options.span_steps on a handle on the two-launch step) for this hub shape, batch, RNG mode and options, without a device:
+ * out[CHUB_PAIR_HANDLE] = 1 if a handle made this way runs pairs of steps with one tail launch at all, out[CHUB_PAIR_CALL] = 1 if a call in the
+ * state `flags` describes does, out[CHUB_PAIR_STEPS] = how many of the next `left` steps then go out as pairs when the clock shows slot t of the day. */
+enum { CHUB_PAIR_HANDLE = 0, CHUB_PAIR_CALL, CHUB_PAIR_STEPS, CHUB_PAIR_COUNT };
+enum { CHUB_PAIRF_COMM = 1, CHUB_PAIRF_PER_ENV = 2, CHUB_PAIRF_TAPE = 4, CHUB_PAIRF_OUTPUTS = 8, CHUB_PAIRF_PROFILING = 16 };
+int chub_pair_plan(const chub_config *cfg, int64_t n_envs, int rng_mode, const chub_options *opt /* NULL = defaults */, int env_params, uint32_t flags,
+                   int t, int64_t left, int64_t *out);
+int chub_uses_pair_tails(const chub_env *env); /* 1: chub_run_steps sends pairs of steps out with one tail launch (where the call allows) */
 
 int chub_obs_dim(const chub_env *env);  /* 2 + 4*(#stations with piles>0) + 3 (MGR:74-104) */
 int chub_act_dim(const chub_env *env);  /* S + 2 (MGR:108-113) */
