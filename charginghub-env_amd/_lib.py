@@ -289,6 +289,23 @@ class ChubCriticGradOut(C.Structure):
     _fields_ = [("d_gW", C.c_void_p * 4), ("d_gb", C.c_void_p * 4), ("d_values", C.c_void_p), ("d_stats", C.c_void_p)]
 
 
+class ChubAdamHyper(C.Structure):
+    """chub_adam_hyper of include/chub.h"""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("max_grad_norm", C.c_double)]
+
+
+def adam_hyper(lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=0.0):
+    """chub_adam_hyper from Python values; nothing is checked here: the library refuses"""
+    return ChubAdamHyper(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(max_grad_norm))
+
+
+class ChubAdamPlanOut(C.Structure):
+    """chub_adam_plan_out of include/chub.h"""
+    _fields_ = [("n", C.c_int64), ("state_bytes", C.c_int64), ("workspace_bytes", C.c_int64), ("norm_workgroups", C.c_int32),
+                ("step_workgroups", C.c_int32)]
+
+
 # pile sets (chub_pile_set_device): the CHUB_PSET_* enum of include/chub.h, in order
 PSET_NAMES = ("all", "occupied", "decidable")
 PSET = {name: i for i, name in enumerate(PSET_NAMES)}
@@ -393,8 +410,8 @@ def source_hash():
 
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
-    for name in ("chub_kernels.hip", "chub_policy.hip", "chub_critic.hip", "chub_runtime.cpp", "chub_comm.cpp", "chub_device.h", "chub_curves.h", "chub_plan.h",
-                 "chub_policy.h", "chub_critic.h"):
+    for name in ("chub_kernels.hip", "chub_policy.hip", "chub_critic.hip", "chub_adam.hip", "chub_runtime.cpp", "chub_comm.cpp", "chub_device.h", "chub_curves.h",
+                 "chub_plan.h", "chub_policy.h", "chub_critic.h", "chub_adam.h"):
         h.update(open(os.path.join(csrc, name), "rb").read())
     h.update(open(os.path.join(os.path.dirname(_HERE), "include", "chub.h"), "rb").read())
     return h.hexdigest()[:16]
@@ -519,6 +536,17 @@ def load_library():
         "chub_critic_normalizer_from_moments_device": (I, [P, P, C.c_double, P]),
         "chub_critic_values_device": (I, [P, P, L, L, P, L, P, P]),
         "chub_critic_grad_device": (I, [P, C.POINTER(ChubCriticGradIn), C.POINTER(ChubCriticGradOut), P]),
+        "chub_adam_plan": (I, [P, P, C.c_int32, C.c_int32, C.POINTER(ChubAdamPlanOut)]),
+        "chub_adam_create_policy": (I, [P, C.POINTER(ChubAdamHyper), C.POINTER(P)]),
+        "chub_adam_create_critic": (I, [P, C.POINTER(ChubAdamHyper), C.POINTER(P)]), "chub_adam_destroy": (I, [P]),
+        "chub_adam_set_hyper": (I, [P, C.POINTER(ChubAdamHyper)]), "chub_adam_set_lr_device": (I, [P, P, P]),
+        "chub_adam_grads": (I, [P, P, P, C.POINTER(P)]), "chub_adam_counter_device": (I, [P, C.POINTER(P)]),
+        "chub_adam_step_device": (I, [P, P, P, P, P, P]), "chub_adam_reset_device": (I, [P, P]),
+        "chub_adam_state_size": (I, [P, C.POINTER(L)]), "chub_adam_get_state": (I, [P, P]), "chub_adam_set_state": (I, [P, P]),
+        "chub_policy_get_weights_device": (I, [P, C.c_int32, P, P, P]), "chub_policy_get_weights": (I, [P, C.c_int32, P, P]),
+        "chub_policy_get_log_std_device": (I, [P, P, P]), "chub_policy_get_log_std": (I, [P, P]),
+        "chub_critic_get_weights_device": (I, [P, C.c_int32, P, P, P]), "chub_critic_get_weights": (I, [P, C.c_int32, P, P]),
+        "chub_shuffle_rows_device": (I, [P, C.c_uint64, P, L, L, P, P]), "chub_shuffle_rows": (I, [C.c_uint64, C.c_uint64, L, P]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -566,7 +594,12 @@ EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "ch
             "chub_policy_grad_plan", "chub_policy_grad_create", "chub_policy_grad_destroy", "chub_policy_grad_device",
             "chub_critic_plan", "chub_critic_create", "chub_critic_destroy", "chub_critic_set_weights", "chub_critic_set_weights_device",
             "chub_critic_set_normalizer", "chub_critic_set_normalizer_device", "chub_critic_normalizer_from_moments_device",
-            "chub_critic_values_device", "chub_critic_grad_device"]
+            "chub_critic_values_device", "chub_critic_grad_device",
+            "chub_adam_plan", "chub_adam_create_policy", "chub_adam_create_critic", "chub_adam_destroy", "chub_adam_set_hyper", "chub_adam_set_lr_device",
+            "chub_adam_grads", "chub_adam_counter_device", "chub_adam_step_device", "chub_adam_reset_device", "chub_adam_state_size",
+            "chub_adam_get_state", "chub_adam_set_state", "chub_policy_get_weights_device", "chub_policy_get_weights",
+            "chub_policy_get_log_std_device", "chub_policy_get_log_std", "chub_critic_get_weights_device", "chub_critic_get_weights",
+            "chub_shuffle_rows_device", "chub_shuffle_rows"]
 
 
 def check(rc):

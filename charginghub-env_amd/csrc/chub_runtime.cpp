@@ -19,6 +19,7 @@
 #include "chub_plan.h"
 #include "chub_policy.h"
 #include "chub_critic.h"
+#include "chub_adam.h"
 
 namespace chub {
 template <bool RESET>
@@ -3606,6 +3607,7 @@ struct chub_policy {
     std::vector<void *> allocs;
     std::vector<chub_population *> populations;  // made for this policy (chub_population_create): destroyed before it
     std::vector<chub_policy_grad *> grads;       // made for this policy (chub_policy_grad_create): destroyed before it
+    std::vector<chub_adam *> adams;              // made for this policy (chub_adam_create_policy): destroyed before it
 };
 
 extern "C" {
@@ -3682,11 +3684,13 @@ int chub_policy_input_width(const chub_config *cfg, const chub_policy_spec *spec
 
 static void population_free(chub_population *pop);
 static void policy_grad_free(chub_policy_grad *g);
+static void adam_free(chub_adam *a);
 
 static void policy_free(chub_policy *pol) {
     chub_env *e = pol->env;
     while (!pol->populations.empty()) population_free(pol->populations.back());
     while (!pol->grads.empty()) policy_grad_free(pol->grads.back());
+    while (!pol->adams.empty()) adam_free(pol->adams.back());
     (void) hipSetDevice(e->device);
     (void) hipDeviceSynchronize();  // (a launch still in flight reads the weights and the scratch)
     for (void *p : pol->allocs) (void) hipFree(p);
@@ -4939,6 +4943,7 @@ struct chub_critic {
     float *d_wrm, *d_part;                  // the row-major copies of layers 1.., the workgroups' f32 partials
     double *d_part64;
     std::vector<void *> allocs;
+    std::vector<chub_adam *> adams;         // made for this critic (chub_adam_create_critic): destroyed before it
 };
 
 static int critic_check_spec(const chub_critic_spec *sp) {
@@ -4974,6 +4979,7 @@ extern "C" {
 
 static void critic_free(chub_critic *c) {
     chub_env *e = c->env;
+    while (!c->adams.empty()) adam_free(c->adams.back());
     (void) hipSetDevice(e->device);
     (void) hipDeviceSynchronize();  // (a launch still in flight reads the weights and writes the partials)
     for (void *p : c->allocs) (void) hipFree(p);
@@ -5265,6 +5271,375 @@ int chub_critic_grad_device(chub_critic *c, const chub_critic_grad_in *in, const
     m.backward = a.backward;
     launch_critic_grad(a, m, m.blocks, gp.lds_rows, gp.in_registers != 0, (hipStream_t) stream);
     HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+// ---- reading weights back (include/chub.h): the kernels' layout -> the trainer's, the way a population's members go
+int chub_policy_get_weights_device(chub_policy *pol, int32_t layer, float *d_W, float *d_b, void *stream) {
+    if (!pol || !d_W || !d_b) return fail(CHUB_ERR_ARG, "null argument");
+    if (layer < 0 || layer >= pol->spec.n_layers) return fail(CHUB_ERR_ARG, "layer: 0 .. n_layers - 1");
+    HIP_TRY(hipSetDevice(pol->env->device));
+    (void) hipGetLastError();
+    launch_policy_unlayout(pol->d_w[layer], pol->d_b[layer], d_W, d_b, pol->spec.width[layer], pol->in_dim[layer], pol->pa.layer[layer].k_pad,
+                           (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_policy_get_weights(chub_policy *pol, int32_t layer, float *W, float *b) {
+    if (!pol || !W || !b) return fail(CHUB_ERR_ARG, "null argument");
+    if (layer < 0 || layer >= pol->spec.n_layers) return fail(CHUB_ERR_ARG, "layer: 0 .. n_layers - 1");
+    if (pol->env->capturing)
+        return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_get_weights between chub_graph_begin and chub_graph_end (it copies and synchronises: use "
+                                          "chub_policy_get_weights_device)");
+    const size_t nw = (size_t) pol->spec.width[layer] * (size_t) pol->in_dim[layer], nb = (size_t) pol->spec.width[layer];
+    HIP_TRY(hipSetDevice(pol->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipDeviceSynchronize());  // (the staging buffer is one)
+    if (const int rc = chub_policy_get_weights_device(pol, layer, pol->d_stage, pol->d_stage + nw, nullptr)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(W, pol->d_stage, nw * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(b, pol->d_stage + nw, nb * sizeof(float), hipMemcpyDeviceToHost));
+    return CHUB_OK;
+}
+
+int chub_policy_get_log_std_device(chub_policy *pol, float *d_log_std, void *stream) {
+    if (!pol || !d_log_std) return fail(CHUB_ERR_ARG, "null argument");
+    if (!pol->explore) return fail(CHUB_ERR_ARG, "chub_policy_set_exploration first (it makes the policy's log_std buffer)");
+    HIP_TRY(hipSetDevice(pol->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipMemcpyAsync(d_log_std, pol->d_log_std, (size_t) pol->G * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
+    return CHUB_OK;
+}
+
+int chub_policy_get_log_std(chub_policy *pol, float *log_std) {
+    if (!pol || !log_std) return fail(CHUB_ERR_ARG, "null argument");
+    if (!pol->explore) return fail(CHUB_ERR_ARG, "chub_policy_set_exploration first (it makes the policy's log_std buffer)");
+    if (pol->env->capturing)
+        return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_get_log_std between chub_graph_begin and chub_graph_end (it copies and synchronises: use "
+                                          "chub_policy_get_log_std_device)");
+    HIP_TRY(hipSetDevice(pol->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(log_std, pol->d_log_std, (size_t) pol->G * sizeof(float), hipMemcpyDeviceToHost));
+    return CHUB_OK;
+}
+
+int chub_critic_get_weights_device(chub_critic *c, int32_t layer, float *d_W, float *d_b, void *stream) {
+    if (!c || !d_W || !d_b) return fail(CHUB_ERR_ARG, "null argument");
+    if (layer < 0 || layer >= c->spec.n_layers) return fail(CHUB_ERR_ARG, "layer: 0 .. n_layers - 1");
+    HIP_TRY(hipSetDevice(c->env->device));
+    (void) hipGetLastError();
+    launch_policy_unlayout(c->d_w[layer], c->d_b[layer], d_W, d_b, c->spec.width[layer], c->in_dim[layer], c->k_pad[layer], (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_critic_get_weights(chub_critic *c, int32_t layer, float *W, float *b) {
+    if (!c || !W || !b) return fail(CHUB_ERR_ARG, "null argument");
+    if (layer < 0 || layer >= c->spec.n_layers) return fail(CHUB_ERR_ARG, "layer: 0 .. n_layers - 1");
+    if (c->env->capturing)
+        return fail(CHUB_ERR_UNSUPPORTED, "chub_critic_get_weights between chub_graph_begin and chub_graph_end (it copies and synchronises: use "
+                                          "chub_critic_get_weights_device)");
+    const size_t nw = (size_t) c->spec.width[layer] * (size_t) c->in_dim[layer], nb = (size_t) c->spec.width[layer];
+    HIP_TRY(hipSetDevice(c->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipDeviceSynchronize());  // (the staging buffer is one)
+    if (const int rc = chub_critic_get_weights_device(c, layer, c->d_stage, c->d_stage + nw, nullptr)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(W, c->d_stage, nw * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(b, c->d_stage + nw, nb * sizeof(float), hipMemcpyDeviceToHost));
+    return CHUB_OK;
+}
+
+}  // extern "C"
+
+// ---- an optimiser on the device (include/chub.h): the plan, the object, the calls.  The kernels are chub_adam.hip's; the parameters are
+// the target's live weights, so the object owns the moments, the scalars, a gradient buffer and the chunks' partials, and nothing else
+struct AdamPlan {
+    int64_t n, param0[kPolicyMaxLayers + 1];
+    int32_t chunks, blocks;
+};
+
+static void adam_plan(const int32_t *out_dims, const int32_t *in_dims, int n_layers, int G, AdamPlan &ap) {
+    int64_t n = 0;
+    for (int l = 0; l < n_layers; l++) {
+        ap.param0[l] = n;
+        n += (int64_t) out_dims[l] * ((int64_t) in_dims[l] + 1);
+    }
+    ap.param0[n_layers] = n;
+    ap.n = n + G;
+    ap.chunks = (int32_t) ((ap.n + kAdamChunk - 1) / kAdamChunk);
+    ap.blocks = ap.chunks < kAdamMaxBlocks ? ap.chunks : kAdamMaxBlocks;
+}
+
+constexpr size_t kAdamBlobHeader = 32;  // int64 t, double p1, double p2, int64 n
+
+struct chub_adam {
+    chub_env *env;
+    chub_policy *pol;   // one of the two
+    chub_critic *critic;
+    AdamPlan ap;
+    AdamArgs args;      // everything but the gradient pointers and the stats
+    int32_t n_layers, G;
+    float *d_m, *d_v, *d_g;
+    double *d_scalars, *d_partials;
+};
+
+static int adam_check_hyper(const chub_adam_hyper *h) {
+    const double nonneg[4] = {h->lr, h->eps, h->weight_decay, h->max_grad_norm};
+    static const char *const names[4] = {"lr", "eps", "weight_decay", "max_grad_norm"};
+    for (int i = 0; i < 4; i++)
+        if (!(nonneg[i] >= 0.0) || !std::isfinite(nonneg[i])) return fail(CHUB_ERR_ARG, std::string(names[i]) + ": finite and >= 0");
+    if (!(h->beta1 >= 0.0 && h->beta1 < 1.0) || !(h->beta2 >= 0.0 && h->beta2 < 1.0)) return fail(CHUB_ERR_ARG, "beta1, beta2: in [0, 1)");
+    return CHUB_OK;
+}
+
+extern "C" {
+
+static void adam_free(chub_adam *a) {
+    (void) hipSetDevice(a->env->device);
+    (void) hipDeviceSynchronize();  // (a launch still in flight reads and writes all of these)
+    if (a->d_m) (void) hipFree(a->d_m);
+    if (a->d_v) (void) hipFree(a->d_v);
+    if (a->d_g) (void) hipFree(a->d_g);
+    if (a->d_scalars) (void) hipFree(a->d_scalars);
+    if (a->d_partials) (void) hipFree(a->d_partials);
+    std::vector<chub_adam *> &list = a->pol ? a->pol->adams : a->critic->adams;
+    list.erase(std::remove(list.begin(), list.end(), a), list.end());
+    delete a;
+}
+
+int chub_adam_plan(const int32_t *out_dims, const int32_t *in_dims, int32_t n_layers, int32_t G, chub_adam_plan_out *out) {
+    if (!out_dims || !in_dims || !out) return fail(CHUB_ERR_ARG, "null argument");
+    if (n_layers < 1 || n_layers > kPolicyMaxLayers) return fail(CHUB_ERR_ARG, "n_layers: 1 .. 4");
+    if (G < 0 || G > 4) return fail(CHUB_ERR_ARG, "G: 0 (no log_std) .. 4");
+    for (int l = 0; l < n_layers; l++)
+        if (out_dims[l] < 1 || in_dims[l] < 1 || out_dims[l] > 65536 || in_dims[l] > 65536) return fail(CHUB_ERR_ARG, "out_dims, in_dims: 1 .. 65536 each");
+    AdamPlan ap;
+    adam_plan(out_dims, in_dims, n_layers, G, ap);
+    out->n = ap.n;
+    out->state_bytes = (int64_t) kAdamBlobHeader + 8 * ap.n;
+    out->workspace_bytes = 12 * ap.n + 8 * (int64_t) ap.chunks + 8 * (int64_t) ADAM_SCALARS;  // m, v, the gradient buffer; the partials; the scalars
+    out->norm_workgroups = ap.blocks;
+    out->step_workgroups = ap.blocks;
+    return CHUB_OK;
+}
+
+// the object for a target whose layers (live device pointers, dims) stand in a->args already
+static int adam_create(chub_adam *a, const chub_adam_hyper *h, std::vector<chub_adam *> &list, chub_adam **out) {
+    AdamArgs &g = a->args;
+    adam_plan(g.out, g.in, a->n_layers, a->G, a->ap);
+    const AdamPlan &ap = a->ap;
+    for (int l = 0; l <= a->n_layers; l++) g.param0[l] = ap.param0[l];
+    g.n = ap.n;
+    g.n_layers = a->n_layers;
+    g.chunks = ap.chunks;
+    a->d_m = a->d_v = a->d_g = nullptr;
+    a->d_scalars = a->d_partials = nullptr;
+    list.push_back(a);
+    const size_t nf = (size_t) ap.n * sizeof(float), ns = (size_t) ADAM_SCALARS * sizeof(double), np = (size_t) ap.chunks * sizeof(double);
+    double sc[ADAM_SCALARS] = {h->lr, h->beta1, h->beta2, h->eps, h->weight_decay, h->max_grad_norm, 0.0, 1.0, 1.0, 0.0, 1.0, 1.0};  // (t = 0 is all zero bits)
+    const bool ok = hipMalloc((void **) &a->d_m, nf) == hipSuccess && hipMalloc((void **) &a->d_v, nf) == hipSuccess &&
+                    hipMalloc((void **) &a->d_g, nf) == hipSuccess && hipMalloc((void **) &a->d_scalars, ns) == hipSuccess &&
+                    hipMalloc((void **) &a->d_partials, np) == hipSuccess && hipMemset(a->d_m, 0, nf) == hipSuccess &&
+                    hipMemset(a->d_v, 0, nf) == hipSuccess && hipMemset(a->d_g, 0, nf) == hipSuccess && hipMemset(a->d_partials, 0, np) == hipSuccess &&
+                    hipMemcpy(a->d_scalars, sc, ns, hipMemcpyHostToDevice) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) {
+        adam_free(a);
+        (void) hipGetLastError();
+        return fail(CHUB_ERR_HIP, "chub_adam_create: out of device memory");
+    }
+    g.m = a->d_m;
+    g.v = a->d_v;
+    g.scalars = a->d_scalars;
+    g.partials = a->d_partials;
+    *out = a;
+    return CHUB_OK;
+}
+
+int chub_adam_create_policy(chub_policy *pol, const chub_adam_hyper *h, chub_adam **out) {
+    if (!pol || !h || !out) return fail(CHUB_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (const int rc = adam_check_hyper(h)) return rc;
+    chub_env *e = pol->env;
+    if (e->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_adam_create_policy between chub_graph_begin and chub_graph_end (it allocates and synchronises)");
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    chub_adam *a = new chub_adam();
+    memset(&a->args, 0, sizeof a->args);
+    a->env = e;
+    a->pol = pol;
+    a->critic = nullptr;
+    a->n_layers = pol->spec.n_layers;
+    a->G = pol->explore ? pol->G : 0;
+    for (int l = 0; l < a->n_layers; l++) {
+        a->args.w[l] = pol->d_w[l];
+        a->args.b[l] = pol->d_b[l];
+        a->args.in[l] = pol->in_dim[l];
+        a->args.out[l] = pol->spec.width[l];
+        a->args.k_pad[l] = pol->pa.layer[l].k_pad;
+    }
+    a->args.log_std = pol->explore ? pol->d_log_std : nullptr;
+    return adam_create(a, h, pol->adams, out);
+}
+
+int chub_adam_create_critic(chub_critic *c, const chub_adam_hyper *h, chub_adam **out) {
+    if (!c || !h || !out) return fail(CHUB_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (const int rc = adam_check_hyper(h)) return rc;
+    chub_env *e = c->env;
+    if (e->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_adam_create_critic between chub_graph_begin and chub_graph_end (it allocates and synchronises)");
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    chub_adam *a = new chub_adam();
+    memset(&a->args, 0, sizeof a->args);
+    a->env = e;
+    a->pol = nullptr;
+    a->critic = c;
+    a->n_layers = c->spec.n_layers;
+    a->G = 0;
+    for (int l = 0; l < a->n_layers; l++) {
+        a->args.w[l] = c->d_w[l];
+        a->args.b[l] = c->d_b[l];
+        a->args.in[l] = c->in_dim[l];
+        a->args.out[l] = c->spec.width[l];
+        a->args.k_pad[l] = c->k_pad[l];
+    }
+    return adam_create(a, h, c->adams, out);
+}
+
+int chub_adam_destroy(chub_adam *a) {
+    if (!a) return CHUB_OK;
+    if (a->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_adam_destroy between chub_graph_begin and chub_graph_end (it synchronises and frees)");
+    adam_free(a);
+    (void) hipGetLastError();
+    return CHUB_OK;
+}
+
+int chub_adam_set_hyper(chub_adam *a, const chub_adam_hyper *h) {
+    if (!a || !h) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = adam_check_hyper(h)) return rc;
+    if (a->env->capturing)
+        return fail(CHUB_ERR_UNSUPPORTED, "chub_adam_set_hyper between chub_graph_begin and chub_graph_end (it copies and synchronises: use chub_adam_set_lr_device)");
+    HIP_TRY(hipSetDevice(a->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipDeviceSynchronize());
+    const double sc[6] = {h->lr, h->beta1, h->beta2, h->eps, h->weight_decay, h->max_grad_norm};
+    HIP_TRY(hipMemcpy(a->d_scalars, sc, sizeof sc, hipMemcpyHostToDevice));
+    return CHUB_OK;
+}
+
+int chub_adam_set_lr_device(chub_adam *a, const double *d_lr, void *stream) {
+    if (!a || !d_lr) return fail(CHUB_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipMemcpyAsync(a->d_scalars + ADAM_LR, d_lr, sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t) stream));
+    return CHUB_OK;
+}
+
+int chub_adam_grads(chub_adam *a, float **d_gW, float **d_gb, float **d_glog_std) {
+    if (!a || !d_gW || !d_gb || !d_glog_std) return fail(CHUB_ERR_ARG, "null argument");
+    for (int l = 0; l < kPolicyMaxLayers; l++) {
+        const bool has = l < a->n_layers;
+        d_gW[l] = has ? a->d_g + a->ap.param0[l] : nullptr;
+        d_gb[l] = has ? a->d_g + a->ap.param0[l] + (int64_t) a->args.out[l] * a->args.in[l] : nullptr;
+    }
+    *d_glog_std = a->G ? a->d_g + a->ap.param0[a->n_layers] : nullptr;
+    return CHUB_OK;
+}
+
+int chub_adam_counter_device(chub_adam *a, const int64_t **d_t) {
+    if (!a || !d_t) return fail(CHUB_ERR_ARG, "null argument");
+    *d_t = reinterpret_cast<const int64_t *>(a->d_scalars) + ADAM_T;
+    return CHUB_OK;
+}
+
+int chub_adam_step_device(chub_adam *a, const float *const *d_gW, const float *const *d_gb, const float *d_glog_std, double *d_stats, void *stream) {
+    if (!a || !d_gW || !d_gb) return fail(CHUB_ERR_ARG, "null argument");
+    for (int l = 0; l < a->n_layers; l++)
+        if (!d_gW[l] || !d_gb[l]) return fail(CHUB_ERR_ARG, "null argument: d_gW[" + std::to_string(l) + "] / d_gb[" + std::to_string(l) + "]");
+    if (a->G && !d_glog_std) return fail(CHUB_ERR_ARG, "null argument: d_glog_std (the parameter vector ends with the policy's log_std)");
+    if (!a->G && d_glog_std) return fail(CHUB_ERR_ARG, "d_glog_std: the parameter vector has no log_std (a critic, or a policy without chub_policy_set_exploration at create)");
+    HIP_TRY(hipSetDevice(a->env->device));
+    (void) hipGetLastError();
+    AdamArgs g = a->args;
+    for (int l = 0; l < a->n_layers; l++) {
+        g.gW[l] = d_gW[l];
+        g.gb[l] = d_gb[l];
+    }
+    g.glog_std = d_glog_std;
+    g.stats = d_stats;
+    launch_adam_step(g, a->ap.blocks, a->ap.blocks, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_adam_reset_device(chub_adam *a, void *stream) {
+    if (!a) return fail(CHUB_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->env->device));
+    (void) hipGetLastError();
+    launch_adam_reset(a->d_m, a->d_v, a->ap.n, a->d_scalars, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_adam_state_size(chub_adam *a, int64_t *bytes) {
+    if (!a || !bytes) return fail(CHUB_ERR_ARG, "null argument");
+    *bytes = (int64_t) kAdamBlobHeader + 8 * a->ap.n;
+    return CHUB_OK;
+}
+
+int chub_adam_get_state(chub_adam *a, void *blob) {
+    if (!a || !blob) return fail(CHUB_ERR_ARG, "null argument");
+    if (a->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_adam_get_state between chub_graph_begin and chub_graph_end (it copies and synchronises)");
+    HIP_TRY(hipSetDevice(a->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipDeviceSynchronize());
+    char *p = static_cast<char *>(blob);
+    const size_t nf = (size_t) a->ap.n * sizeof(float);
+    HIP_TRY(hipMemcpy(p, a->d_scalars + ADAM_T, 24, hipMemcpyDeviceToHost));
+    const int64_t n = a->ap.n;
+    memcpy(p + 24, &n, 8);
+    HIP_TRY(hipMemcpy(p + kAdamBlobHeader, a->d_m, nf, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(p + kAdamBlobHeader + nf, a->d_v, nf, hipMemcpyDeviceToHost));
+    return CHUB_OK;
+}
+
+int chub_adam_set_state(chub_adam *a, const void *blob) {
+    if (!a || !blob) return fail(CHUB_ERR_ARG, "null argument");
+    const char *p = static_cast<const char *>(blob);
+    int64_t n;
+    memcpy(&n, p + 24, 8);
+    if (n != a->ap.n)
+        return fail(CHUB_ERR_ARG, "chub_adam_set_state: the blob holds " + std::to_string(n) + " parameters, this optimiser " + std::to_string(a->ap.n));
+    if (a->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_adam_set_state between chub_graph_begin and chub_graph_end (it copies and synchronises)");
+    HIP_TRY(hipSetDevice(a->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t nf = (size_t) a->ap.n * sizeof(float);
+    HIP_TRY(hipMemcpy(a->d_scalars + ADAM_T, p, 24, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(a->d_m, p + kAdamBlobHeader, nf, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(a->d_v, p + kAdamBlobHeader + nf, nf, hipMemcpyHostToDevice));
+    return CHUB_OK;
+}
+
+// ---- minibatch indices (include/chub.h): the shuffle's definition is chub_adam.h's, shared by the kernel and the host form
+int chub_shuffle_rows_device(chub_env *e, uint64_t key, const int64_t *d_counter, int64_t offset, int64_t R, int64_t *d_rows, void *stream) {
+    if (!e || !d_rows) return fail(CHUB_ERR_ARG, "null argument");
+    if (R < 1 || R > ((int64_t) 1 << 40)) return fail(CHUB_ERR_ARG, "chub_shuffle_rows_device: R is 1 .. 2^40");
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    launch_shuffle_rows(key, d_counter, offset, R, d_rows, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_shuffle_rows(uint64_t key, uint64_t counter, int64_t R, int64_t *rows) {
+    if (!rows) return fail(CHUB_ERR_ARG, "null argument");
+    if (R < 1 || R > ((int64_t) 1 << 40)) return fail(CHUB_ERR_ARG, "chub_shuffle_rows: R is 1 .. 2^40");
+    const int nb = shuffle_bits(R);
+    for (int64_t r = 0; r < R; r++) rows[r] = shuffle_row(r, R, nb, key, counter);
     return CHUB_OK;
 }
 

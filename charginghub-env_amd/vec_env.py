@@ -175,6 +175,31 @@ class DevicePolicy(object):
         captured graph's next replay evaluates the new weights"""
         check(self._lib.chub_policy_set_weights_device(self._p, int(layer), d_W, d_b, stream or None))
 
+    def get_weights(self, layer=None):
+        """the LIVE weights as float32 numpy arrays in the nn.Linear layout: (W, b) of one layer, or with layer=None the list over all
+        layers; synchronises"""
+        if layer is None:
+            return [self.get_weights(l) for l in range(len(self.layer_shapes))]
+        if not 0 <= int(layer) < len(self.layer_shapes):
+            raise ValueError("get_weights: layer is 0 .. %d" % (len(self.layer_shapes) - 1))
+        W = np.zeros(self.layer_shapes[layer], dtype=np.float32)
+        b = np.zeros((W.shape[0],), dtype=np.float32)
+        check(self._lib.chub_policy_get_weights(self._p, int(layer), _ptr(W), _ptr(b)))
+        return W, b
+
+    def get_weights_device(self, layer, d_W, d_b, stream=0):
+        """one layer into device memory in the trainer's layout (e.g. a parameter's data_ptr()), one launch on `stream`"""
+        check(self._lib.chub_policy_get_weights_device(self._p, int(layer), d_W or None, d_b or None, stream or None))
+
+    def get_log_std(self, d_log_std=0, stream=0):
+        """log_std [G]: as a float32 numpy array (synchronises), or with d_log_std a copy into device memory on `stream`"""
+        if d_log_std:
+            check(self._lib.chub_policy_get_log_std_device(self._p, d_log_std, stream or None))
+            return None
+        ls = np.zeros((self.n_gaussians,), dtype=np.float32)
+        check(self._lib.chub_policy_get_log_std(self._p, _ptr(ls)))
+        return ls
+
     def run_steps(self, d_packed2, n_steps, first_step=0, mode="lockstep", d_reset_obs=0, d_final_obs=0, stream=0):
         """the closed loop issued from C (chub_policy_run_steps): d_packed2 = the addresses of two [N, D + 2] f32 blocks, step i writes block
         i & 1.  mode "lockstep": a reset into d_reset_obs [N, D] before every step whose index is a multiple of 96, bits-form steps;
@@ -195,6 +220,12 @@ class DevicePolicy(object):
         before sample_device / collect"""
         ls = np.ascontiguousarray(np.broadcast_to(np.asarray(log_std, dtype=np.float32), (self.n_gaussians,)))
         check(self._lib.chub_policy_set_exploration(self._p, int(key) & (2 ** 64 - 1), _ptr(ls)))
+        self._explores = True
+
+    @property
+    def has_exploration(self):
+        """whether set_exploration has made the policy's log_std (what get_log_std reads and an optimiser made from now on trains)"""
+        return getattr(self, "_explores", False)
 
     def set_log_std_device(self, d_log_std, stream=0):
         """log_std [G] f32 from device memory (e.g. a parameter's data_ptr()) as a copy on `stream`: a captured graph's next replay
@@ -709,6 +740,22 @@ class DeviceCritic(object):
         captured graph's next replay evaluates the new weights"""
         check(self._lib.chub_critic_set_weights_device(self._c, int(layer), d_W or None, d_b or None, stream or None))
 
+    def get_weights(self, layer=None):
+        """the LIVE weights as float32 numpy arrays in the nn.Linear layout: (W, b) of one layer, or with layer=None the list over all
+        layers; synchronises"""
+        if layer is None:
+            return [self.get_weights(l) for l in range(len(self.layer_shapes))]
+        if not 0 <= int(layer) < len(self.layer_shapes):
+            raise ValueError("get_weights: layer is 0 .. %d" % (len(self.layer_shapes) - 1))
+        W = np.zeros(self.layer_shapes[layer], dtype=np.float32)
+        b = np.zeros((W.shape[0],), dtype=np.float32)
+        check(self._lib.chub_critic_get_weights(self._c, int(layer), _ptr(W), _ptr(b)))
+        return W, b
+
+    def get_weights_device(self, layer, d_W, d_b, stream=0):
+        """one layer into device memory in the trainer's layout (e.g. a parameter's data_ptr()), one launch on `stream`"""
+        check(self._lib.chub_critic_get_weights_device(self._c, int(layer), d_W or None, d_b or None, stream or None))
+
     def set_normalizer(self, mean, inv_std):
         """new mean / inv_std [F] from host arrays; synchronises"""
         mean = np.ascontiguousarray(mean, dtype=np.float32).ravel()
@@ -729,6 +776,95 @@ class DeviceCritic(object):
         if getattr(self, "_c", None) and getattr(self._env, "_h", None):
             check(self._lib.chub_critic_destroy(self._c))
         self._c = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceAdam(object):
+    """Adam with gradient clipping on the device (chub_adam_*, include/chub.h "an optimiser on the device"): made by
+    VecChargingHub.make_adam for a DevicePolicy or a DeviceCritic.  The parameters are the target's LIVE device weights: a step reads
+    gradients in the trainer's layout and writes the new weights straight into the kernels' layout, two launches, the same bits every
+    time.  The flat parameter vector (and m, v) is W[0], b[0], W[1], b[1], .., then the policy's log_std."""
+
+    def __init__(self, env, target, hyper):
+        self._env = env
+        self._lib = env._lib
+        self.target = target
+        h = C.c_void_p()
+        if isinstance(target, DevicePolicy):
+            check(self._lib.chub_adam_create_policy(target._p, C.byref(hyper), C.byref(h)))
+        elif isinstance(target, DeviceCritic):
+            check(self._lib.chub_adam_create_critic(target._c, C.byref(hyper), C.byref(h)))
+        else:
+            raise TypeError("make_adam: a DevicePolicy or a DeviceCritic")
+        self._a = h
+        self.layer_shapes = list(target.layer_shapes)
+        size = C.c_int64()
+        check(self._lib.chub_adam_state_size(self._a, C.byref(size)))
+        self.state_bytes = size.value
+        self.n_params = (size.value - 32) // 8
+        gW, gb, gl = (C.c_void_p * 4)(), (C.c_void_p * 4)(), C.c_void_p()
+        check(self._lib.chub_adam_grads(self._a, gW, gb, C.byref(gl)))
+        n = len(self.layer_shapes)
+        self._grads = ([gW[l] or 0 for l in range(n)], [gb[l] or 0 for l in range(n)], gl.value or 0)
+        t = C.c_void_p()
+        check(self._lib.chub_adam_counter_device(self._a, C.byref(t)))
+        self.counter_address = t.value
+
+    @property
+    def has_log_std(self):
+        return self._grads[2] != 0
+
+    def grads(self):
+        """(d_gW [layers], d_gb [layers], d_glog_std or 0): device addresses into the optimiser's own gradient buffer, the trainer's
+        layout in the flat order -- what a gradient call writes there needs no allocation by the caller"""
+        return list(self._grads[0]), list(self._grads[1]), self._grads[2]
+
+    def step_device(self, d_gW=None, d_gb=None, d_glog_std=None, d_stats=0, stream=0):
+        """one step on `stream` (chub_adam_step_device) from gradients at these device addresses (default: the optimiser's own buffers);
+        d_stats [4] f64: t, the gradient's norm, the clip scale, 1 where the step was skipped (a norm that is not finite).  Two launches,
+        no synchronisation; recordable into a graph, whose replays advance t, the bias corrections and the moments by themselves."""
+        n = len(self.layer_shapes)
+        gW = self._grads[0] if d_gW is None else d_gW
+        gb = self._grads[1] if d_gb is None else d_gb
+        gl = self._grads[2] if d_glog_std is None else d_glog_std
+        Wp = (C.c_void_p * 4)(*[(gW[l] or None) for l in range(n)])
+        bp = (C.c_void_p * 4)(*[(gb[l] or None) for l in range(n)])
+        check(self._lib.chub_adam_step_device(self._a, Wp, bp, gl or None, d_stats or None, stream or None))
+
+    def set_hyper(self, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=0.0):
+        """new hyper-parameters from host values; synchronises"""
+        check(self._lib.chub_adam_set_hyper(self._a, C.byref(_lib.adam_hyper(lr, betas, eps, weight_decay, max_grad_norm))))
+
+    def set_lr_device(self, d_lr, stream=0):
+        """lr from one f64 in device memory, as a copy on `stream`: a schedule inside a graph"""
+        check(self._lib.chub_adam_set_lr_device(self._a, d_lr or None, stream or None))
+
+    def reset_device(self, stream=0):
+        """m = v = 0, t = 0, the bias corrections' products back to 1, on `stream`"""
+        check(self._lib.chub_adam_reset_device(self._a, stream or None))
+
+    def state(self):
+        """the state blob as bytes: int64 t, f64 p1, f64 p2, int64 n, m [n] f32, v [n] f32; synchronises"""
+        blob = np.zeros(self.state_bytes, dtype=np.uint8)
+        check(self._lib.chub_adam_get_state(self._a, _ptr(blob)))
+        return blob.tobytes()
+
+    def load_state(self, blob):
+        """a state() blob back (of an optimiser with as many parameters); synchronises"""
+        buf = np.frombuffer(bytes(blob), dtype=np.uint8)
+        if buf.size != self.state_bytes:
+            raise ValueError("load_state: a blob of %d bytes, this optimiser's has %d" % (buf.size, self.state_bytes))
+        check(self._lib.chub_adam_set_state(self._a, _ptr(buf)))
+
+    def close(self):
+        if getattr(self, "_a", None) and getattr(self._env, "_h", None) and (getattr(self.target, "_p", None) or getattr(self.target, "_c", None)):
+            check(self._lib.chub_adam_destroy(self._a))  # (a closed target has destroyed its optimisers already)
+        self._a = None
 
     def __del__(self):
         try:
@@ -1385,6 +1521,27 @@ class VecChargingHub(object):
         nn.Linear layout, the last with one output; the rows it reads have layers[0][0].shape[1] floats.  normalize: None or (mean [F],
         inv_std [F], clip), the critic's own.  max_rows: the most rows one call works on (default n_envs; T * n_envs for a rollout)."""
         return DeviceCritic(self, layers, hidden_act, normalize, max_rows)
+
+    def make_adam(self, target, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=0.0):
+        """Adam on the LIVE weights of `target`, a DevicePolicy or a DeviceCritic of this handle -> DeviceAdam (chub_adam_create_*).
+        A policy that has set_exploration by now trains its log_std too.  weight_decay is decoupled (AdamW's) and touches W only;
+        max_grad_norm > 0 clips the gradient's global norm (0: no clipping)."""
+        if getattr(target, "_env", None) is not self:
+            raise ValueError("make_adam: the target was made for another handle")
+        return DeviceAdam(self, target, _lib.adam_hyper(lr, betas, eps, weight_decay, max_grad_norm))
+
+    def shuffle_rows_device(self, d_rows, R, key, d_counter=0, offset=0, stream=0):
+        """a permutation of 0 .. R - 1 into d_rows [R] int64 on `stream` (chub_shuffle_rows_device): a pure function of (key, counter, R)
+        with counter = the int64 at d_counter (0: zero; a DeviceAdam's counter_address: its step count, so that every replay of a
+        captured epoch shuffles anew) + offset.  Slices of d_rows are the d_rows of the gradient calls.  One launch; recordable."""
+        check(self._lib.chub_shuffle_rows_device(self._h, int(key) & (2 ** 64 - 1), d_counter or None, int(offset), int(R), d_rows or None,
+                                                 stream or None))
+
+    def shuffle_rows(self, R, key, counter=0):
+        """the same permutation computed on the host (chub_shuffle_rows) -> int64 [R]; no device"""
+        rows = np.zeros(int(R), dtype=np.int64)
+        check(self._lib.chub_shuffle_rows(int(key) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1), int(R), _ptr(rows)))
+        return rows
 
     def next_tick(self):
         """the Philox tick of this handle's next reset or step (chub_next_tick): the tick a sampled policy call made now draws its noise

@@ -765,7 +765,7 @@ class TorchHubVecEnv(object):
         return (adv, ret, st) if stats else (adv, ret)
 
     # ---- actor gradients on the device (chub_policy_grad_*): the policy-gradient step with no autograd for the actor
-    def _policy_grad_call(self, rollout, adv, rows, loss, clip_eps, ent_coef, adv_stats, backward):
+    def _policy_grad_call(self, rollout, adv, rows, loss, clip_eps, ent_coef, adv_stats, backward, into=None):
         torch = self.torch
         policy = getattr(self, "_rollout_policy", {}).get(id(rollout))
         if policy is None:
@@ -797,17 +797,18 @@ class TorchHubVecEnv(object):
             out = ent["rows"][R] = (torch.zeros((R,), dtype=torch.float32, device=self.device), torch.zeros((R,), dtype=torch.float32, device=self.device))
         piles = policy.spec.head == _lib.PHEAD["piles"]
         sets = rollout.get("set_bits") if piles else None
+        dst = ent if into is None else self._into(into, policy, "policy_gradient")
         ent["grad"].grad_device(R, n_rows, feats.data_ptr(), rollout["u"].data_ptr(), (adv if adv is not None else rollout["logp"]).data_ptr(),
                                 d_pile_bits=rollout["bits"].data_ptr() if piles else 0, d_set_bits=0 if sets is None else sets.data_ptr(),
                                 d_logp_old=rollout["logp"].data_ptr(), d_rows=0 if rows is None else rows.data_ptr(),
                                 d_adv_stats=0 if adv_stats is None else adv_stats.data_ptr(), loss=loss, clip_eps=clip_eps, ent_coef=ent_coef,
-                                d_gW=[gW.data_ptr() for gW, _ in ent["grads"]] if backward else None,
-                                d_gb=[gb.data_ptr() for _, gb in ent["grads"]] if backward else None,
-                                d_glog_std=ent["g_log_std"].data_ptr() if backward else 0, d_logp_new=out[0].data_ptr(), d_entropy=out[1].data_ptr(),
+                                d_gW=[gW.data_ptr() for gW, _ in dst["grads"]] if backward else None,
+                                d_gb=[gb.data_ptr() for _, gb in dst["grads"]] if backward else None,
+                                d_glog_std=dst["g_log_std"].data_ptr() if backward else 0, d_logp_new=out[0].data_ptr(), d_entropy=out[1].data_ptr(),
                                 d_stats=ent["stats"].data_ptr() if backward else 0, stream=self._stream())
-        return ent, out
+        return (ent if into is None else dict(ent, grads=dst["grads"], g_log_std=dst["g_log_std"])), out
 
-    def policy_gradient(self, rollout, adv, rows=None, loss="ppo_clip", clip_eps=0.2, ent_coef=0.0, adv_stats=None):
+    def policy_gradient(self, rollout, adv, rows=None, loss="ppo_clip", clip_eps=0.2, ent_coef=0.0, adv_stats=None, into=None):
         """The actor's gradient of a surrogate loss over a ``collect`` rollout, on torch's current stream with no autograd
         (chub_policy_grad_device): the CURRENT weights, normaliser and log_std of the rollout's policy, the recorded actions, ``logp`` and
         sets of `rollout`, adv [T, N] float32 CUDA (``advantages``), rows: an int64 CUDA tensor of flat (step, env) indices t * N + n (a
@@ -815,8 +816,9 @@ class TorchHubVecEnv(object):
         normalise the advantage with.  Returns (grads, g_log_std, stats): grads a list of (gW, gb) in ``load_policy``'s layout, g_log_std
         [G], stats float64 [6] (rows, sum of loss terms, sum of entropies, sum of logp_old - logp_new, rows clipped away, sum of ratios) --
         CUDA tensors the next call with the same policy overwrites.  An optimiser step on them and ``policy.set_weights_device`` /
-        ``set_log_std_device`` close the loop."""
-        ent, _ = self._policy_grad_call(rollout, adv, rows, loss, clip_eps, ent_coef, adv_stats, True)
+        ``set_log_std_device`` close the loop.  into: an optimiser ``make_optimizer`` made for the rollout's policy -- the gradient is
+        written into ITS buffers, the returned grads and g_log_std are views of them, and ``optimizer_step`` closes the loop."""
+        ent, _ = self._policy_grad_call(rollout, adv, rows, loss, clip_eps, ent_coef, adv_stats, True, into)
         return ent["grads"], ent["g_log_std"], ent["stats"]
 
     def evaluate_actions(self, rollout, rows=None):
@@ -907,13 +909,14 @@ class TorchHubVecEnv(object):
         critic.values_device(N, N, self.last_obs.data_ptr(), final.data_ptr(), ld=int(self.last_obs.stride(0)), stream=st)
         return vals, final
 
-    def value_gradient(self, critic, rollout, ret, rows=None, loss="mse", clip_eps=0.2, v_old=None):
+    def value_gradient(self, critic, rollout, ret, rows=None, loss="mse", clip_eps=0.2, v_old=None, into=None):
         """The critic's gradient of the value loss over a ``collect`` rollout, on torch's current stream with no autograd
         (chub_critic_grad_device): the critic's CURRENT weights and normaliser on ``rollout["features"]``, ret [T, N] float32 CUDA
         (``advantages``), rows: an int64 CUDA tensor of flat (step, env) indices t * N + n (a minibatch; None: every row), loss "mse" or
         "clipped" (PPO2's clipped value loss around v_old [T, N], e.g. ``values(...)[0][:T]`` as collected, within clip_eps).  Returns
         (grads, stats): grads a list of (gW, gb) in ``load_critic``'s layout, stats float64 [6] (rows, sum of loss terms, rows clipped
-        away, sum of (ret - v)^2, sum of ret, sum of ret^2) -- CUDA tensors the next call with the same critic overwrites."""
+        away, sum of (ret - v)^2, sum of ret, sum of ret^2) -- CUDA tensors the next call with the same critic overwrites.  into: an
+        optimiser ``make_optimizer`` made for `critic` -- the gradient is written into ITS buffers and the returned grads are views of them."""
         torch = self.torch
         policy, feats, ent = self._critic_rollout(critic, rollout, "value_gradient")
         n_rows = int(feats.shape[0]) * int(feats.shape[1])
@@ -926,10 +929,77 @@ class TorchHubVecEnv(object):
         clipped = _lib.value_loss(loss) == _lib.VLOSS["clipped"]
         if clipped and (v_old is None or not per_row(v_old)):
             raise AssertionError("v_old must be a contiguous float32 tensor on %s with one entry per (step, env) under loss='clipped'" % (self.device,))
+        grads = ent["grads"] if into is None else self._into(into, critic, "value_gradient")["grads"]
         critic.grad_device(R, n_rows, feats.data_ptr(), ret.data_ptr(), d_v_old=v_old.data_ptr() if clipped else 0,
-                           d_rows=0 if rows is None else rows.data_ptr(), loss=loss, clip_eps=clip_eps, d_gW=[gW.data_ptr() for gW, _ in ent["grads"]],
-                           d_gb=[gb.data_ptr() for _, gb in ent["grads"]], d_stats=ent["stats"].data_ptr(), stream=self._stream())
-        return ent["grads"], ent["stats"]
+                           d_rows=0 if rows is None else rows.data_ptr(), loss=loss, clip_eps=clip_eps, d_gW=[gW.data_ptr() for gW, _ in grads],
+                           d_gb=[gb.data_ptr() for _, gb in grads], d_stats=ent["stats"].data_ptr(), stream=self._stream())
+        return grads, ent["stats"]
+
+    # ---- an optimiser on the device (chub_adam_*, chub_shuffle_rows_device): the update with no torch optimiser and no re-layout
+    def _device_view(self, ptr, shape, typestr="<f4"):
+        """a tensor over device memory the library owns (only the address and the shape are used)"""
+        iface = dict(shape=tuple(shape), typestr=typestr, data=(int(ptr), False), version=2)
+        return self.torch.as_tensor(type("DeviceArray", (), {"__cuda_array_interface__": iface})(), device=self.device)
+
+    def make_optimizer(self, policy_or_critic, **hyper):
+        """Adam with gradient clipping on the LIVE weights of a ``load_policy`` actor or a ``load_critic`` critic -> DeviceAdam
+        (VecChargingHub.make_adam; hyper: lr, betas, eps, weight_decay, max_grad_norm).  ``policy_gradient(..., into=opt)`` /
+        ``value_gradient(..., into=opt)`` write the gradient into its own buffers and ``optimizer_step(opt)`` steps from there: the
+        next act, sample, values or gradient call sees the new weights with no ``set_weights_device``."""
+        opt = self.vec.make_adam(policy_or_critic, **hyper)
+        gW, gb, gl = opt.grads()
+        opt._views = {"grads": [(self._device_view(gW[l], (o, i)), self._device_view(gb[l], (o,))) for l, (o, i) in enumerate(opt.layer_shapes)],
+                      "g_log_std": self._device_view(gl, (opt.target.n_gaussians,)) if gl else None,
+                      "stats": self.torch.zeros((4,), dtype=self.torch.float64, device=self.device)}
+        return opt
+
+    def _into(self, opt, target, who):
+        if opt.target is not target or getattr(opt, "_views", None) is None:
+            raise ValueError("%s: into= takes an optimiser this adapter's make_optimizer made for the same policy / critic" % who)
+        return opt._views
+
+    def optimizer_step(self, opt):
+        """One step of `opt` from the gradients in its own buffers, on torch's current stream (chub_adam_step_device) -> the float64 [4]
+        CUDA stats tensor (t, the gradient's norm, the clip scale, 1 where a norm that was not finite skipped the step) the next step of
+        `opt` overwrites."""
+        views = self._into(opt, opt.target, "optimizer_step")
+        opt.step_device(d_stats=views["stats"].data_ptr(), stream=self._stream())
+        return views["stats"]
+
+    def optimizer_stats(self, opt):
+        """the float64 [4] CUDA stats tensor the last ``optimizer_step(opt)`` wrote (zeros before the first)"""
+        return self._into(opt, opt.target, "optimizer_stats")["stats"]
+
+    def shuffle_rows(self, R, key, counter=None, offset=0):
+        """A permutation of 0 .. R - 1 as an int64 CUDA tensor, on torch's current stream (chub_shuffle_rows_device): a pure function
+        of (key, counter + offset, R).  counter: None (0), an optimiser (its step count, read on the device when the launch runs), or an
+        int64 CUDA tensor of one entry.  Slices of it are the ``rows`` of ``policy_gradient`` / ``value_gradient``."""
+        torch = self.torch
+        rows = torch.empty((int(R),), dtype=torch.int64, device=self.device)
+        d_counter = 0 if counter is None else counter.counter_address if hasattr(counter, "counter_address") else counter.data_ptr()
+        self.vec.shuffle_rows_device(rows.data_ptr(), R, key, d_counter=d_counter, offset=offset, stream=self._stream())
+        return rows
+
+    def _weights(self, target):
+        torch = self.torch
+        f32 = dict(dtype=torch.float32, device=self.device)
+        out = [(torch.empty((o, i), **f32), torch.empty((o,), **f32)) for o, i in target.layer_shapes]
+        for l, (W, b) in enumerate(out):
+            target.get_weights_device(l, W.data_ptr(), b.data_ptr(), stream=self._stream())
+        return out
+
+    def policy_weights(self, policy):
+        """The actor's LIVE weights -> ([(W, b), ..] in nn.Linear's layout, log_std [G] or None), new float32 CUDA tensors filled on
+        torch's current stream (chub_policy_get_weights_device)"""
+        log_std = None
+        if policy.has_exploration:
+            log_std = self.torch.empty((policy.n_gaussians,), dtype=self.torch.float32, device=self.device)
+            policy.get_log_std(log_std.data_ptr(), stream=self._stream())
+        return self._weights(policy), log_std
+
+    def critic_weights(self, critic):
+        """The critic's LIVE weights -> [(W, b), ..] in nn.Linear's layout, new float32 CUDA tensors filled on torch's current stream"""
+        return self._weights(critic)
 
     # ---- a normaliser that follows the rollouts (chub_moments_*, chub_policy_normalizer_from_moments_device)
     def update_normalizer(self, policy, rollout, moments=None, eps=1e-8, mask=None):

@@ -345,6 +345,62 @@ def ppo_all_on_device(n=4096, steps=64, minibatches=4):
     env.close()
 
 
+def ppo_epochs_on_device(n=4096, steps=64, minibatches=4, epochs=4):
+    import charginghub_env_amd as chub
+
+    if torch is None:
+        print("10. skipped: torch is not installed")
+        return
+    env = chub.TorchHubVecEnv(n, seed=0, autoreset="per_env", **HUB)
+    D, A = env.obs_dim, env.act_dim
+    net = torch.nn.Sequential(torch.nn.Linear(D, 64), torch.nn.Tanh(), torch.nn.Linear(64, A)).to("cuda")      # receive the weights at the end
+    vnet = torch.nn.Sequential(torch.nn.Linear(D, 64), torch.nn.Tanh(), torch.nn.Linear(64, 1)).to("cuda")
+    policy = env.load_policy(net)
+    policy.set_exploration(key=7, log_std=[-0.5, -0.5])
+    critic = env.load_critic(vnet)
+    a_opt = env.make_optimizer(policy, lr=3e-4, max_grad_norm=0.5)    # Adam on the LIVE device weights (and log_std): no torch optimiser,
+    c_opt = env.make_optimizer(critic, lr=1e-3, max_grad_norm=0.5)    # no set_weights_device after a step
+    env.reset()
+    ro = env.collect(policy, steps, logp_piles="decidable")
+    values, final = env.values(critic, ro)
+    adv, ret, adv_stats = env.advantages(ro, values, final, gamma=0.99, lam=0.95, stats=True)
+    v_old = values[:steps].clone()
+    R = steps * n
+    mb = R // minibatches
+
+    def epoch():
+        # a permutation of the rollout's rows that is never stored apart from its output; its counter is the actor optimiser's step
+        # count, read on the device when the launch runs, so that every epoch -- every replay -- shuffles anew
+        rows = env.shuffle_rows(R, key=11, counter=a_opt)
+        for i in range(minibatches):
+            r = rows[i * mb:(i + 1) * mb]
+            env.policy_gradient(ro, adv, rows=r, loss="ppo_clip", clip_eps=0.2, ent_coef=0.01, adv_stats=adv_stats, into=a_opt)
+            env.value_gradient(critic, ro, ret, rows=r, loss="clipped", clip_eps=0.2, v_old=v_old, into=c_opt)
+            env.optimizer_step(a_opt)                          # the gradients lie in the optimisers' own buffers: two launches each
+            env.optimizer_step(c_opt)
+
+    epoch()                                                    # once eagerly: every tensor the calls cache exists before the recording
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):                              # the M-minibatch epoch as one chain of launches, recorded once
+        epoch()
+    for _ in range(epochs - 1):                                # each replay continues from the weights, moments and counter of the last
+        graph.replay()
+    a_stats = env.optimizer_stats(a_opt)                       # of the last step: t, the gradient's norm, the clip scale, skipped
+    (layers, log_std), v_layers = env.policy_weights(policy), env.critic_weights(critic)
+    with torch.no_grad():                                      # the trained weights back into the nn.Sequentials, in nn.Linear's layout
+        for m, (W, b) in zip([m for m in net if isinstance(m, torch.nn.Linear)], layers):
+            m.weight.copy_(W), m.bias.copy_(b)
+        for m, (W, b) in zip([m for m in vnet if isinstance(m, torch.nn.Linear)], v_layers):
+            m.weight.copy_(W), m.bias.copy_(b)
+    logp_new, entropy = env.evaluate_actions(ro)
+    kl = float((ro["logp"].reshape(-1) - logp_new).mean())
+    print("10. %d envs x %d steps, %d PPO epochs of %d minibatches with no torch optimiser, the epoch recorded once and replayed: %d Adam steps, "
+          "last gradient norm %.3f (clip scale %.3f), approximate KL %.5f, log_std %s"
+          % (n, steps, epochs, minibatches, int(a_stats[0]), float(a_stats[1]), float(a_stats[2]), kl, [round(float(x), 4) for x in log_std]))
+    env.close()
+
+
 if __name__ == "__main__":
     single_env()
     batched_host()
@@ -355,3 +411,4 @@ if __name__ == "__main__":
     es_generation()
     ppo_on_device_gradients()
     ppo_all_on_device()
+    ppo_epochs_on_device()

@@ -1154,7 +1154,7 @@ int chub_population_es_gradient_device(chub_population *pop, const float *d_util
  *     PPO_CLIP; ent_coef not finite; d_set_bits under LOADS; a policy without chub_policy_set_exploration (no log_std); max_rows < 1.
  *     CHUB_ERR_UNSUPPORTED: the fit rule; create / destroy between chub_graph_begin and chub_graph_end.
  * Out of scope: the value loss (the critic trains on `ret` through "a critic on the device", below: chub_critic_grad_device), an
- *     optimiser (Adam stays with the trainer or host), gradients with respect to the normaliser or through the tanh squash, bf16 weights,
+ *     optimiser (see "an optimiser on the device", below: chub_adam_step_device), gradients with respect to the normaliser or through the tanh squash, bf16 weights,
  *     populations, the multi-GPU hosts (an all-reduce of the returned gradients is the trainer's), COMPAT rollouts. */
 enum { CHUB_PLOSS_COEF = 0, CHUB_PLOSS_PPO_CLIP, CHUB_PLOSS_COUNT };
 typedef struct chub_policy_grad chub_policy_grad;
@@ -1242,7 +1242,7 @@ int chub_policy_grad_device(chub_policy_grad *g, const chub_policy_grad_in *in, 
  *     gradient call; null d_v_old or eps <= 0 or not finite under CLIPPED; null d_values in the values call; moments of another handle or
  *     another F; max_rows < 1.  CHUB_ERR_UNSUPPORTED: the fit rule; create, destroy or a host set_* between chub_graph_begin and
  *     chub_graph_end.
- * Out of scope: a trunk shared with the actor, return normalisation, an optimiser, bf16, the multi-GPU hosts, and terminal values for
+ * Out of scope: a trunk shared with the actor, return normalisation, an optimiser (see "an optimiser on the device", below), bf16, the multi-GPU hosts, and terminal values for
  *     feature rows with non-OBS blocks: the state is gone by then, so d_final_values is NULL and an episode's end is worth 0 for such
  *     critics. */
 enum { CHUB_VLOSS_MSE = 0, CHUB_VLOSS_CLIPPED, CHUB_VLOSS_COUNT };
@@ -1286,6 +1286,93 @@ int chub_critic_normalizer_from_moments_device(chub_critic *c, chub_moments *m, 
 int chub_critic_values_device(chub_critic *c, const float *d_x, int64_t ld, int64_t n_rows, const int64_t *d_rows /* [R] or NULL */, int64_t R,
                               float *d_values /* [R] */, void *stream);
 int chub_critic_grad_device(chub_critic *c, const chub_critic_grad_in *in, const chub_critic_grad_out *out, void *stream);
+
+/* ---- an optimiser on the device: Adam, gradient clipping, minibatch shuffles, weights read back ------------------------------------------
+ * What closes a PPO epoch inside the library: an Adam step that reads gradients where chub_policy_grad_device / chub_critic_grad_device
+ * leave them and writes the new weights straight into the kernels' own layout, a counter-based row shuffle whose slices are the d_rows
+ * of the two gradient calls, and the calls that hand the trained weights back.  After them M minibatches of (shuffle slice, actor
+ * gradient, critic gradient, two steps) are a chain of launches with nothing on the host between them, capturable as one graph whose
+ * every replay continues from the weights, moments and counter the last one left.
+ *   The parameter vector.  Flat, in the trainer's (torch's state_dict) order: for each layer W[l] row-major [out][in], then b[l]; for a
+ *     policy that had chub_policy_set_exploration at create, log_std [G] last.  n is its length.  m and v are f32 [n] in that order.
+ *     chub_adam_grads gives pointers into a gradient buffer of the object's own in the same order (d_gW / d_gb of layers the target has
+ *     not: NULL; d_glog_std: NULL without log_std): what chub_policy_grad_out / chub_critic_grad_out is filled with there needs no
+ *     allocation by the caller.  chub_adam_step_device takes any device pointers, these included.
+ *   There is no master copy.  The parameters are the target's LIVE device weights (per tile of 32 outputs [k_pad][32], biases
+ *     [tiles * 32]) and the policy's log_std buffer.  A lane owns one real parameter: it finds that parameter's place in the layout,
+ *     reads it, writes it; the zero padding beyond `in` and `out` is never touched.  chub_*_set_weights* on the target between steps
+ *     cannot make anything stale (the next step starts from the new weights and the old moments), and the next act, sample, values or
+ *     gradient call in the stream sees the new weights without a re-layout launch.
+ *   One step.  Every operation is an f64 operation rounded once unless said otherwise; t (int64), p1, p2 (f64) and the hyper-parameters
+ *     live in device memory.
+ *       1. norm = sqrt(sum g^2) over all n entries.  The squares are exact in f64.  The order of the sum: chunk c is entries 1024 c ..;
+ *          lane j of 256 adds entries j, j + 256, j + 512, j + 768 of the chunk in that order from 0 (an entry past n adds +0); the
+ *          lanes meet in a tree, lane j += lane j + 128, then + 64, .. + 1; the chunks' sums are added in ascending order from 0.
+ *       2. norm not finite: the step is SKIPPED.  Weights, m, v, t, p1, p2 keep their bits; stats = {t, norm, 0, 1}.
+ *       3. scale = (float) min(1, max_grad_norm / (norm + 1e-6)); with max_grad_norm == 0 scale is exactly 1.
+ *       4. t += 1; p1 *= beta1; p2 *= beta2 (running products, not pow).
+ *       5. Per parameter: g' = (double) g * (double) scale (exact); m32 = (float) (beta1 * m + (1 - beta1) * g');
+ *          v32 = (float) (beta2 * v + (1 - beta2) * (g' * g')); from the STORED f32 values denom = sqrt(v32) / sqrt(1 - p2) + eps;
+ *          th = (double) theta; for entries of a W only, where weight_decay != 0: th = th * (1 - lr * weight_decay) (biases and log_std
+ *          are never decayed); th = th - (lr / (1 - p1)) * (m32 / denom); theta = (float) th.  1 - beta1 and 1 - beta2 are f64
+ *          differences formed once.
+ *       6. stats = {t, norm, scale, 0}.
+ *   Launches.  A step is TWO launches, whatever the layer count, on the caller's stream: the first writes the chunks' sums and copies
+ *     t, p1, p2 into a "previous" block; in the second every workgroup adds the sums, reads "previous", and lane 0 of workgroup 0 alone
+ *     writes the new scalars: a launch never reads what another of its workgroups writes.  Both launches run min(chunks, 64) workgroups
+ *     that take chunks b, b + 64, ..  No allocation, no synchronisation, no tick, no atomics: two objects fed the same gradients hold
+ *     identical bits.  Recordable between chub_graph_begin and chub_graph_end (it is no reset or step of the handle: the count of those
+ *     is not touched); a replayed graph advances t, p1, p2 by itself.  chub_adam_set_lr_device copies one f64 from device memory into
+ *     the object's lr on the stream: a schedule inside a graph.  chub_adam_counter_device gives the address of t.
+ *   chub_adam_plan: host-only, no device: n, the state blob's bytes, the device memory create allocates (m, v, the gradient buffer,
+ *     the chunks' sums, the scalars) and the workgroups of the two launches, for layers out_dims[l] x in_dims[l] and G log_std entries.
+ *   Ownership.  Allocated outside the arena: chub_state_size and snapshots are unchanged.  chub_policy_destroy, chub_critic_destroy and
+ *     chub_destroy destroy a target's optimisers first.  The state blob is {int64 t, double p1, double p2, int64 n}, m[n], v[n]:
+ *     32 + 8 n bytes; chub_adam_set_state refuses a blob whose n differs.  chub_adam_reset_device: m = v = 0, t = 0, p1 = p2 = 1.
+ *   Reading weights back.  chub_policy_get_weights_device / chub_critic_get_weights_device write W [out][in] and b [out] of one layer
+ *     in the trainer's layout (one launch on `stream`), chub_policy_get_log_std_device [G] (one copy); the forms without _device take
+ *     host memory and synchronise.
+ *   chub_shuffle_rows_device: d_rows[r], r = 0 .. R - 1, is a permutation of 0 .. R - 1, a pure function of (key, c, R) with
+ *     c = *d_counter + offset as uint64 (d_counter NULL: 0), read on the device.  nb is the bit length of R - 1, lo = nb >> 1,
+ *     hi = nb - lo; left = x >> lo has hi bits, right is the low lo bits.  E(x) is six rounds i = 0 .. 5: even i
+ *     left ^= F_i(right) & mask_hi, odd i right ^= F_i(left) & mask_lo, with F_i(val) word 0 of Philox4x32-10 at counter
+ *     (val, 17 << 16 | i, low word of c, high word of c) under key (low word first).  d_rows[r] is cycle-walked: y = E(r), and while
+ *     y >= R, y = E(y), at most 64 applications of E; an entry that has not landed by then is written as -1, which the gradient calls
+ *     skip.  R = 1 writes 0.  One launch, one lane per r (a lane takes r, r + 2^20, .. beyond 2^20 rows), no tick; recordable.  Pointing
+ *     d_counter at chub_adam_counter_device's t gives every replay of a captured epoch a new shuffle; `offset` tells several shuffles
+ *     apart within one graph.  chub_shuffle_rows is the same definition in host C, no device.
+ * Refusals, all with a message and before any device work.  CHUB_ERR_ARG: a null argument; lr, eps, weight_decay or max_grad_norm
+ *     negative or not finite; a beta outside [0, 1); a null d_gW[l] or d_gb[l] for a layer the target has; a null d_glog_std where the
+ *     vector has log_std, a non-null one where it has not; a blob of another n; a layer outside 0 .. n_layers - 1; log_std calls on a
+ *     policy without chub_policy_set_exploration; R < 1 or R > 2^40.  CHUB_ERR_UNSUPPORTED: create, destroy and the host forms between
+ *     chub_graph_begin and chub_graph_end.
+ * Out of scope: other optimisers, per-layer learning rates, a clamp on log_std, AMSGrad, populations, the multi-GPU hosts. */
+typedef struct chub_adam chub_adam;
+typedef struct chub_adam_hyper { double lr, beta1, beta2, eps, weight_decay, max_grad_norm; } chub_adam_hyper;
+typedef struct chub_adam_plan_out { int64_t n; int64_t state_bytes; int64_t workspace_bytes; int32_t norm_workgroups, step_workgroups; } chub_adam_plan_out;
+int chub_adam_plan(const int32_t *out_dims, const int32_t *in_dims, int32_t n_layers, int32_t G, chub_adam_plan_out *out);
+int chub_adam_create_policy(chub_policy *pol, const chub_adam_hyper *h, chub_adam **out);
+int chub_adam_create_critic(chub_critic *c, const chub_adam_hyper *h, chub_adam **out);
+int chub_adam_destroy(chub_adam *a);
+int chub_adam_set_hyper(chub_adam *a, const chub_adam_hyper *h);                       /* host; synchronises */
+int chub_adam_set_lr_device(chub_adam *a, const double *d_lr, void *stream);
+int chub_adam_grads(chub_adam *a, float **d_gW /* [4] */, float **d_gb /* [4] */, float **d_glog_std);
+int chub_adam_counter_device(chub_adam *a, const int64_t **d_t);
+int chub_adam_step_device(chub_adam *a, const float *const *d_gW, const float *const *d_gb, const float *d_glog_std, double *d_stats /* [4] or NULL */,
+                          void *stream);
+int chub_adam_reset_device(chub_adam *a, void *stream);
+int chub_adam_state_size(chub_adam *a, int64_t *bytes);
+int chub_adam_get_state(chub_adam *a, void *blob);                                     /* host; synchronises */
+int chub_adam_set_state(chub_adam *a, const void *blob);                               /* host; synchronises */
+int chub_policy_get_weights_device(chub_policy *pol, int32_t layer, float *d_W, float *d_b, void *stream);
+int chub_policy_get_weights(chub_policy *pol, int32_t layer, float *W, float *b);      /* host; synchronises */
+int chub_policy_get_log_std_device(chub_policy *pol, float *d_log_std /* [G] */, void *stream);
+int chub_policy_get_log_std(chub_policy *pol, float *log_std /* [G] */);               /* host; synchronises */
+int chub_critic_get_weights_device(chub_critic *c, int32_t layer, float *d_W, float *d_b, void *stream);
+int chub_critic_get_weights(chub_critic *c, int32_t layer, float *W, float *b);        /* host; synchronises */
+int chub_shuffle_rows_device(chub_env *env, uint64_t key, const int64_t *d_counter /* or NULL: 0 */, int64_t offset, int64_t R, int64_t *d_rows /* [R] */,
+                             void *stream);
+int chub_shuffle_rows(uint64_t key, uint64_t counter, int64_t R, int64_t *rows);       /* host-only restatement in C, no device */
 
 /* The FCEV waiting list is unbounded as in the reference (HYD:264-265): the entries a list that still gets served can
  * hold are kept one by one, and once no prefix of it fits into 15 minutes any more (HYD:270-276: nobody is served again

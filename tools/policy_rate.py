@@ -26,6 +26,13 @@
                   with every output, critic_grad_mb4096 the same call over a minibatch of 4096 rows picked by d_rows, and critic_grad_large /
                   critic_values_large for a 13-256-224-1 critic (dW tiles in the partials, 137 KB of LDS); with --torch-critic also
                   critic_values_torch and critic_grad_torch, the same two as torch autograd over the same device memory.
+  --adam          a case of its own (torch first, one process, TorchHubVecEnv; T = 96, actor 13-64-64-47 and critic 13-64-64-1): the UPDATE
+                  PART of one minibatch, everything between the two gradient calls and the next -- update_torch: torch Adam.step() on both
+                  networks plus the set_weights_device / set_log_std_device calls of quickstart part 9; update_device: two
+                  chub_adam_step_device -- and the whole epoch at minibatches of 4096 and of 65 536 rows: epoch_torch_mb<R> issued eagerly
+                  the parent's way (torch.randperm outside), epoch_device_mb<R> eagerly with the device shuffle and steps,
+                  epoch_graph_mb<R> the same chain recorded once and replayed; shuffle / shuffle_torch: chub_shuffle_rows_device against
+                  torch.randperm over the rollout's rows.  us per update, ms per epoch, us per shuffle, between two events.
 Every case is warmed up, then the cases alternate, ROUNDS times; median, best and worst round are reported with the build id.
 --open-loop-only measures the open loop alone, --launch-only the open loop and the deterministic launch, --no-sets the first five cases:
 with CHUB_LIB=<another build's libchub.so> those are the rates of a build without the newer entry points (the parent commit), on the same
@@ -41,7 +48,7 @@ import time
 
 import numpy as np
 
-if "--torch-gae" in sys.argv or "--torch-grad" in sys.argv or "--torch-critic" in sys.argv:
+if "--torch-gae" in sys.argv or "--torch-grad" in sys.argv or "--torch-critic" in sys.argv or "--adam" in sys.argv:
     import torch  # before libchub is loaded: both must share one HIP runtime
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -66,8 +73,11 @@ def main():
     ap.add_argument("--torch-grad", action="store_true")
     ap.add_argument("--critic", action="store_true", help="the actor-gradient cases and the critic's, in one process")
     ap.add_argument("--torch-critic", action="store_true")
+    ap.add_argument("--adam", action="store_true", help="the optimiser's cases alone (see the module's text)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    if args.adam:
+        return adam_cases(args)
     n_s, piles_s = args.shape.split("x")
     n, piles = int(n_s), [int(x) for x in piles_s.split(",")]
     hidden = [int(x) for x in args.hidden.split(",") if x]
@@ -519,6 +529,145 @@ def torch_gae_case(packed_ptr, gae, n, T, D, calls):
         e1.synchronize()
         return e0.elapsed_time(e1) * 1e3 / calls
     return run
+
+
+
+
+def adam_cases(args):
+    """--adam: the update part of a minibatch and the whole epoch, the parent's way and this build's, alternating in one process"""
+    n_s, piles_s = args.shape.split("x")
+    n, piles = int(n_s), [int(x) for x in piles_s.split(",")]
+    hidden = [int(x) for x in args.hidden.split(",") if x]
+    T = 96
+    env = chub.TorchHubVecEnv(n, piles, ["fast", "slow"], seed=1, rng="philox", autoreset="per_env", hydro_prod_rate=100.0, hydro_store_vlt=25.0,
+                              init_soc=0.2, fc_max_power=100.0, fcev_permeate=0.01)
+    build_id = chub.load_library().chub_build_id().decode()
+    D, A = env.obs_dim, env.act_dim
+    side = torch.cuda.Stream()
+    torch.cuda.set_stream(side)  # (a created stream: a recording needs one)
+
+    def mlp(sizes):
+        mods = []
+        for i, o in zip(sizes[:-1], sizes[1:]):
+            mods += [torch.nn.Linear(i, o), torch.nn.Tanh()]
+        return torch.nn.Sequential(*mods[:-1]).to("cuda")
+
+    def twin():
+        """a policy and a critic with their nn.Sequentials (the same initial weights every time)"""
+        torch.manual_seed(0)
+        net, vnet = mlp([D] + hidden + [A]), mlp([D] + hidden + [1])
+        pol = env.load_policy(net)
+        pol.set_exploration(7, [-0.5, -0.5])
+        return net, vnet, pol, env.load_critic(vnet)
+
+    net, vnet, pol_t, crit_t = twin()        # the parent's way: torch optimisers, weights pushed back after every step
+    _, _, pol_d, crit_d = twin()             # this build's way
+    a_lin, c_lin = [m for m in net if isinstance(m, torch.nn.Linear)], [m for m in vnet if isinstance(m, torch.nn.Linear)]
+    log_std = torch.full((2,), -0.5, device="cuda")
+    a_opt_t = torch.optim.Adam([p for m in a_lin for p in (m.weight, m.bias)] + [log_std], lr=3e-4)
+    c_opt_t = torch.optim.Adam([p for m in c_lin for p in (m.weight, m.bias)], lr=1e-3)
+    a_opt_d, c_opt_d = env.make_optimizer(pol_d, lr=3e-4), env.make_optimizer(crit_d, lr=1e-3)
+    env.reset()
+    ro = env.collect(pol_t, T, logp_piles="decidable")
+    env._rollout_policy[id(ro)] = pol_t
+    values, final = env.values(crit_t, ro)
+    adv, ret, adv_stats = env.advantages(ro, values, final, stats=True)
+    v_old = values[:T].clone()
+    R = T * n
+
+    def grads_torch(rows):
+        grads, gls, _ = env.policy_gradient(ro, adv, rows=rows, adv_stats=adv_stats)
+        vg, _ = env.value_gradient(crit_t, ro, ret, rows=rows, loss="clipped", v_old=v_old)
+        for m, (gW, gb) in zip(a_lin, grads):
+            m.weight.grad, m.bias.grad = gW, gb
+        log_std.grad = gls
+        for m, (gW, gb) in zip(c_lin, vg):
+            m.weight.grad, m.bias.grad = gW, gb
+
+    def update_torch():
+        st = torch.cuda.current_stream().cuda_stream
+        a_opt_t.step()
+        c_opt_t.step()
+        for l, m in enumerate(a_lin):
+            pol_t.set_weights_device(l, m.weight.data_ptr(), m.bias.data_ptr(), st)
+        pol_t.set_log_std_device(log_std.data_ptr(), st)
+        for l, m in enumerate(c_lin):
+            crit_t.set_weights_device(l, m.weight.data_ptr(), m.bias.data_ptr(), st)
+
+    def update_device():
+        env.optimizer_step(a_opt_d)
+        env.optimizer_step(c_opt_d)
+
+    ro_d = dict(ro)  # the same rollout, differentiated through the second policy
+    env._rollout_policy[id(ro_d)] = pol_d
+
+    def grads_device(rows):
+        env.policy_gradient(ro_d, adv, rows=rows, adv_stats=adv_stats, into=a_opt_d)
+        env.value_gradient(crit_d, ro_d, ret, rows=rows, loss="clipped", v_old=v_old, into=c_opt_d)
+
+    def epoch_torch(mb):
+        perm = torch.randperm(R, device="cuda")
+        for i in range(R // mb):
+            grads_torch(perm[i * mb:(i + 1) * mb])
+            update_torch()
+
+    def epoch_device(mb):
+        rows = env.shuffle_rows(R, 11, counter=a_opt_d)
+        for i in range(R // mb):
+            grads_device(rows[i * mb:(i + 1) * mb])
+            update_device()
+
+    def timed(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / reps  # ms
+
+    few = max(1, args.calls // 4)
+    cases, failed = {}, {}
+    grads_torch(None)
+    grads_device(None)
+    cases[("update_torch", "torch Adam.step() x 2 + 6 set_weights_device + set_log_std_device", "us_per_update")] = lambda: timed(update_torch, few) * 1e3
+    cases[("update_device", "chub_adam_step_device x 2", "us_per_update")] = lambda: timed(update_device, few) * 1e3
+    cases[("shuffle", "chub_shuffle_rows_device", "us_per_call")] = lambda: timed(lambda: env.shuffle_rows(R, 11, counter=a_opt_d), 20) * 1e3
+    cases[("shuffle_torch", "torch.randperm", "us_per_call")] = lambda: timed(lambda: torch.randperm(R, device="cuda"), 20) * 1e3
+    for mb in (4096, 65536):
+        if R % mb:
+            continue
+        cases[("epoch_torch_mb%d" % mb, "eager, the parent's way", "ms_per_epoch")] = lambda mb=mb: timed(lambda: epoch_torch(mb), 1)
+        cases[("epoch_device_mb%d" % mb, "eager, chub_adam_step_device and chub_shuffle_rows_device", "ms_per_epoch")] = lambda mb=mb: timed(lambda: epoch_device(mb), 1)
+        epoch_device(mb)  # (every tensor the calls cache exists before the recording)
+        torch.cuda.synchronize()
+        try:
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=side):
+                epoch_device(mb)
+            cases[("epoch_graph_mb%d" % mb, "one captured graph replayed", "ms_per_epoch")] = lambda graph=graph: timed(graph.replay, 1)
+        except Exception as e:  # the row then says so: NOT MEASURED
+            failed["epoch_graph_mb%d" % mb] = repr(e)[:300]
+    for fn in cases.values():
+        fn()
+    vals = {c: [] for c in cases}
+    for _ in range(args.rounds):
+        for c, fn in cases.items():
+            vals[c].append(fn())
+    rows = []
+    for (kind, route, unit), xs in vals.items():
+        rows.append(dict(shape=args.shape, n_envs=n, piles=piles, T=T, rows=R, actor=[D] + hidden + [A], critic=[D] + hidden + [1], kind=kind, route=route,
+                         unit=unit, rounds=len(xs), median=round(statistics.median(xs), 3), min=round(min(xs), 3), max=round(max(xs), 3), build_id=build_id))
+    for kind, why in failed.items():
+        rows.append(dict(shape=args.shape, kind=kind, unit="NOT MEASURED", error=why, build_id=build_id))
+    for row in rows:
+        print(json.dumps(row), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+        json.dump(rows, open(args.out, "w"), indent=1)
+    torch.cuda.synchronize()
+    env.close()
 
 
 if __name__ == "__main__":
