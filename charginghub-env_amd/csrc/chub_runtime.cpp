@@ -3585,15 +3585,210 @@ static_assert((int) CHUB_PIN_COUNT == PIN_COUNT && (int) CHUB_PIN_FORECAST == PI
               "chub_policy.h restates the CHUB_PIN_* / PACT / PHEAD / PSQ / PRUN enums");
 }  // extern "C"
 
-struct chub_policy {
+// ---- device memory that an object owns: allocate zeroed and remember, free all
+struct DeviceAllocs {
+    std::vector<void *> ptrs;
+    // *p = count zeroed elements (at least 4 bytes).  Returns nullptr, or what failed, for the owner's own error text
+    template <class T>
+    const char *zeroed(T **p, size_t count) {
+        size_t bytes = count * sizeof(T);
+        void *d = nullptr;
+        if (!bytes) bytes = 4;
+        if (hipMalloc(&d, bytes) != hipSuccess) return "out of device memory";
+        ptrs.push_back(d);
+        if (hipMemset(d, 0, bytes) != hipSuccess) return "hipMemset failed";
+        *p = (T *) d;
+        return nullptr;
+    }
+    void free_all() {
+        for (void *p : ptrs) (void) hipFree(p);
+        ptrs.clear();
+    }
+};
+
+// ---- one net's layers in the kernels' layout (chub_policy.h): what an actor and a critic both are on the host, and what a population, a
+// gradient call and an optimiser read of their target.  The entry points of chub_policy_* and chub_critic_* that write, read or normalise
+// weights are their own refusals and one net_* call with the caller's name.
+struct MlpNet {
     chub_env *env;
-    chub_policy_spec spec;
-    int32_t F, A_out, waves;
-    int32_t in_dim[kPolicyMaxLayers];       // inputs of layer l
-    PolicyArgs pa;                          // everything that does not change from call to call
+    const char *noun, *row_noun, *alloc_who;  // the error texts' "policy" / "critic", "feature row" / "rows", "chub_policy" / "chub_critic_create"
+    int32_t n_layers, F;
+    int32_t out[kPolicyMaxLayers], in[kPolicyMaxLayers], k_pad[kPolicyMaxLayers];
+    int32_t tiles[kPolicyMaxLayers];        // output tiles of 32 a layer's buffers hold: the owner's rule
     float *d_w[kPolicyMaxLayers], *d_b[kPolicyMaxLayers];  // the layers in the kernel's layout (never move)
     float *d_norm;                          // mean [F] | inv_std [F]
     float *d_stage;                         // the host form of set_weights: W | b of the largest layer, in the trainer's layout
+    bool normalize;
+    DeviceAllocs allocs;
+    std::vector<chub_adam *> adams;         // made for this net (chub_adam_create_policy / _critic): destroyed before it
+};
+
+static void adam_free(chub_adam *a);
+
+template <class T>
+static int net_alloc(MlpNet &n, T **p, size_t count) {
+    if (const char *what = n.allocs.zeroed(p, count)) return fail(CHUB_ERR_HIP, std::string(n.alloc_who) + ": " + what);
+    return CHUB_OK;
+}
+
+// the layers, the staging buffer and the normaliser, zeroed, for the out / in / tiles that stand in the net
+static int net_alloc_layers(MlpNet &n) {
+    size_t stage = 0;
+    for (int l = 0; l < n.n_layers; l++) {
+        n.k_pad[l] = (n.in[l] + 1) & ~1;
+        stage = std::max(stage, (size_t) n.out[l] * (size_t) n.in[l] + (size_t) n.out[l]);
+        if (const int rc = net_alloc(n, &n.d_w[l], (size_t) n.tiles[l] * (size_t) n.k_pad[l] * kPolicyOutTile)) return rc;
+        if (const int rc = net_alloc(n, &n.d_b[l], (size_t) n.tiles[l] * kPolicyOutTile)) return rc;
+    }
+    if (const int rc = net_alloc(n, &n.d_stage, stage)) return rc;
+    return net_alloc(n, &n.d_norm, 2 * (size_t) n.F);
+}
+
+// the optimisers first; then nothing in flight may still read what goes
+static void net_free(MlpNet &n) {
+    while (!n.adams.empty()) adam_free(n.adams.back());
+    (void) hipSetDevice(n.env->device);
+    (void) hipDeviceSynchronize();
+    n.allocs.free_all();
+}
+
+// what a call that enqueues starts with; and what a host form (it copies and synchronises) starts with
+static int net_begin(const MlpNet &n) {
+    HIP_TRY(hipSetDevice(n.env->device));
+    (void) hipGetLastError();
+    return CHUB_OK;
+}
+
+static int net_begin_host(const MlpNet &n, const char *who) {
+    if (n.env->capturing)
+        return fail(CHUB_ERR_UNSUPPORTED, std::string(who) + " between chub_graph_begin and chub_graph_end (it copies and synchronises: use " + who +
+                                              "_device)");
+    return net_begin(n);
+}
+
+static int net_check_layer(const MlpNet &n, int32_t layer) {
+    if (layer < 0 || layer >= n.n_layers) return fail(CHUB_ERR_ARG, "layer: 0 .. n_layers - 1");
+    return CHUB_OK;
+}
+
+// W [out][in], b [out] in device memory -> layer l's blocks at d_w / d_b (the net's own, or a population member's); and back
+static void net_relayout(const MlpNet &n, int l, const float *d_W, const float *d_b, float *d_w, float *d_bias, void *stream) {
+    launch_policy_relayout(d_W, d_b, d_w, d_bias, n.out[l], n.in[l], n.k_pad[l], n.tiles[l], (hipStream_t) stream);
+}
+
+static void net_unlayout(const MlpNet &n, int l, const float *d_w, const float *d_bias, float *d_W, float *d_b, void *stream) {
+    launch_policy_unlayout(d_w, d_bias, d_W, d_b, n.out[l], n.in[l], n.k_pad[l], (hipStream_t) stream);
+}
+
+// the staging buffer holds layer l as W | b: where b stands
+static float *net_stage_b(const MlpNet &n, int l) { return n.d_stage + (size_t) n.out[l] * (size_t) n.in[l]; }
+
+// host W | b of layer l into the staging buffer, and out of it
+static int net_stage_in(MlpNet &n, int l, const float *W, const float *b) {
+    const size_t nw = (size_t) n.out[l] * (size_t) n.in[l], nb = (size_t) n.out[l];
+    HIP_TRY(hipDeviceSynchronize());  // (the staging buffer is one; nothing may still be reading the layer either)
+    HIP_TRY(hipMemcpy(n.d_stage, W, nw * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(n.d_stage + nw, b, nb * sizeof(float), hipMemcpyHostToDevice));
+    return CHUB_OK;
+}
+
+static int net_stage_out(MlpNet &n, int l, float *W, float *b) {
+    const size_t nw = (size_t) n.out[l] * (size_t) n.in[l], nb = (size_t) n.out[l];
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(W, n.d_stage, nw * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(b, n.d_stage + nw, nb * sizeof(float), hipMemcpyDeviceToHost));
+    return CHUB_OK;
+}
+
+static int net_upload(MlpNet &n, int l, const float *W, const float *b) {
+    if (const int rc = net_stage_in(n, l, W, b)) return rc;
+    net_relayout(n, l, n.d_stage, net_stage_b(n, l), n.d_w[l], n.d_b[l], nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    return CHUB_OK;
+}
+
+static int net_set_weights(MlpNet &n, const char *who, int32_t layer, const float *W, const float *b) {
+    if (const int rc = net_check_layer(n, layer)) return rc;
+    if (const int rc = net_begin_host(n, who)) return rc;
+    return net_upload(n, layer, W, b);
+}
+
+static int net_set_weights_device(MlpNet &n, int32_t layer, const float *d_W, const float *d_b, void *stream) {
+    if (const int rc = net_check_layer(n, layer)) return rc;
+    if (const int rc = net_begin(n)) return rc;
+    net_relayout(n, layer, d_W, d_b, n.d_w[layer], n.d_b[layer], stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+// reading weights back: the kernels' layout -> the trainer's, the way a population's members go
+static int net_get_weights_device(MlpNet &n, int32_t layer, float *d_W, float *d_b, void *stream) {
+    if (const int rc = net_check_layer(n, layer)) return rc;
+    if (const int rc = net_begin(n)) return rc;
+    net_unlayout(n, layer, n.d_w[layer], n.d_b[layer], d_W, d_b, stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+static int net_get_weights(MlpNet &n, const char *who, int32_t layer, float *W, float *b) {
+    if (const int rc = net_check_layer(n, layer)) return rc;
+    if (const int rc = net_begin_host(n, who)) return rc;
+    HIP_TRY(hipDeviceSynchronize());  // (the staging buffer is one)
+    if (const int rc = net_get_weights_device(n, layer, n.d_stage, net_stage_b(n, layer), nullptr)) return rc;
+    return net_stage_out(n, layer, W, b);
+}
+
+// the normaliser, written, read and derived: all into / out of the net's own d_norm, which never moves
+static int net_needs_normalizer(const MlpNet &n, const char *who) {
+    if (!n.normalize)
+        return fail(CHUB_ERR_ARG, std::string(who) + ": the " + n.noun + " was created with normalize = 0 (its kernel reads no normaliser)");
+    return CHUB_OK;
+}
+
+static hipError_t net_copy_normalizer(MlpNet &n, const float *mean, const float *inv_std) {
+    const hipError_t rc = hipMemcpy(n.d_norm, mean, (size_t) n.F * sizeof(float), hipMemcpyHostToDevice);
+    return rc != hipSuccess ? rc : hipMemcpy(n.d_norm + n.F, inv_std, (size_t) n.F * sizeof(float), hipMemcpyHostToDevice);
+}
+
+static int net_set_normalizer(MlpNet &n, const char *who, const float *mean, const float *inv_std) {
+    if (const int rc = net_needs_normalizer(n, who)) return rc;
+    if (const int rc = net_begin_host(n, who)) return rc;
+    HIP_TRY(hipDeviceSynchronize());  // (a launch in flight reads the buffer)
+    HIP_TRY(net_copy_normalizer(n, mean, inv_std));
+    return CHUB_OK;
+}
+
+static int net_set_normalizer_device(MlpNet &n, const char *who, const float *d_mean, const float *d_inv_std, void *stream) {
+    if (const int rc = net_needs_normalizer(n, who)) return rc;
+    if (const int rc = net_begin(n)) return rc;
+    HIP_TRY(hipMemcpyAsync(n.d_norm, d_mean, (size_t) n.F * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
+    HIP_TRY(hipMemcpyAsync(n.d_norm + n.F, d_inv_std, (size_t) n.F * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
+    return CHUB_OK;
+}
+
+static int net_get_normalizer_device(MlpNet &n, const char *who, float *d_mean, float *d_inv_std, void *stream) {
+    if (const int rc = net_needs_normalizer(n, who)) return rc;
+    if (const int rc = net_begin(n)) return rc;
+    HIP_TRY(hipMemcpyAsync(d_mean, n.d_norm, (size_t) n.F * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
+    HIP_TRY(hipMemcpyAsync(d_inv_std, n.d_norm + n.F, (size_t) n.F * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
+    return CHUB_OK;
+}
+
+// the weights and the normaliser a create call was given, into a net whose buffers stand
+static int net_load(MlpNet &n, const char *who, const float *const *W, const float *const *b, const float *mean, const float *inv_std) {
+    if (n.normalize && net_copy_normalizer(n, mean, inv_std) != hipSuccess)
+        return fail(CHUB_ERR_HIP, std::string(who) + ": mean / inv_std could not be copied to the device");
+    for (int l = 0; l < n.n_layers; l++)
+        if (const int rc = net_upload(n, l, W[l], b[l])) return rc;
+    return CHUB_OK;
+}
+
+struct chub_policy {
+    MlpNet net;
+    chub_policy_spec spec;
+    int32_t A_out, waves;
+    PolicyArgs pa;                          // everything that does not change from call to call
     float *d_scratch[kPolicyMaxInputs];     // [N][width] of every non-OBS block
     float *d_loads, *d_tail;                // [N][2] each: the LOADS head's outputs; the run loop's tail pair
     uint64_t *d_bits;                       // [N][W]: the run loop's pile bits
@@ -3604,10 +3799,8 @@ struct chub_policy {
     bool explore;
     uint32_t key[2];
     float *d_log_std;
-    std::vector<void *> allocs;
     std::vector<chub_population *> populations;  // made for this policy (chub_population_create): destroyed before it
     std::vector<chub_policy_grad *> grads;       // made for this policy (chub_policy_grad_create): destroyed before it
-    std::vector<chub_adam *> adams;              // made for this policy (chub_adam_create_policy): destroyed before it
 };
 
 extern "C" {
@@ -3684,41 +3877,14 @@ int chub_policy_input_width(const chub_config *cfg, const chub_policy_spec *spec
 
 static void population_free(chub_population *pop);
 static void policy_grad_free(chub_policy_grad *g);
-static void adam_free(chub_adam *a);
 
 static void policy_free(chub_policy *pol) {
-    chub_env *e = pol->env;
+    chub_env *e = pol->net.env;
     while (!pol->populations.empty()) population_free(pol->populations.back());
     while (!pol->grads.empty()) policy_grad_free(pol->grads.back());
-    while (!pol->adams.empty()) adam_free(pol->adams.back());
-    (void) hipSetDevice(e->device);
-    (void) hipDeviceSynchronize();  // (a launch still in flight reads the weights and the scratch)
-    for (void *p : pol->allocs) (void) hipFree(p);
+    net_free(pol->net);  // (its synchronise also covers the scratch a launch in flight reads)
     e->policies.erase(std::remove(e->policies.begin(), e->policies.end(), pol), e->policies.end());
     delete pol;
-}
-
-static int policy_alloc_bytes(chub_policy *pol, void **p, size_t bytes) {
-    void *d = nullptr;
-    if (!bytes) bytes = 4;
-    if (hipMalloc(&d, bytes) != hipSuccess) return fail(CHUB_ERR_HIP, "chub_policy: out of device memory");
-    pol->allocs.push_back(d);
-    if (hipMemset(d, 0, bytes) != hipSuccess) return fail(CHUB_ERR_HIP, "chub_policy: hipMemset failed");
-    *p = d;
-    return CHUB_OK;
-}
-#define policy_alloc(pol, p, count) policy_alloc_bytes((pol), (void **) (p), (size_t) (count) * sizeof(**(p)))
-
-static int policy_upload(chub_policy *pol, int l, const float *W, const float *b) {
-    const size_t nw = (size_t) pol->spec.width[l] * (size_t) pol->in_dim[l], nb = (size_t) pol->spec.width[l];
-    HIP_TRY(hipDeviceSynchronize());  // (the staging buffer is one; nothing may still be reading the layer either)
-    HIP_TRY(hipMemcpy(pol->d_stage, W, nw * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(pol->d_stage + nw, b, nb * sizeof(float), hipMemcpyHostToDevice));
-    launch_policy_relayout(pol->d_stage, pol->d_stage + nw, pol->d_w[l], pol->d_b[l], pol->spec.width[l], pol->in_dim[l], pol->pa.layer[l].k_pad,
-                           pol->pa.layer[l].tiles, nullptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    return CHUB_OK;
 }
 
 int chub_policy_create(chub_env *e, const chub_policy_spec *spec, const float *const *W, const float *const *b, const float *mean,
@@ -3740,9 +3906,15 @@ int chub_policy_create(chub_env *e, const chub_policy_spec *spec, const float *c
     (void) hipGetLastError();
 
     chub_policy *pol = new chub_policy();
-    pol->env = e;
+    MlpNet &net = pol->net;
+    net.env = e;
+    net.noun = "policy";
+    net.row_noun = "feature row";
+    net.alloc_who = "chub_policy";
+    net.n_layers = spec->n_layers;
+    net.F = ps.F;
+    net.normalize = spec->normalize != 0;
     pol->spec = *spec;
-    pol->F = ps.F;
     pol->A_out = ps.A_out;
     pol->lds_rows = ps.p_rows + ps.q_rows;
     pol->G = spec->head == CHUB_PHEAD_PILES ? 2 : 4;
@@ -3765,48 +3937,37 @@ int chub_policy_create(chub_env *e, const chub_policy_spec *spec, const float *c
     pa.S = S;
     pa.A = S + 2;
     pa.W = Wd;
-    int rc = CHUB_OK, max_tiles = 1;
-    size_t stage = 0;
-    for (int l = 0; l < spec->n_layers && !rc; l++) {
-        const int in = l ? spec->width[l - 1] : ps.F, width = spec->width[l];
-        int tiles = (width + kPolicyOutTile - 1) / kPolicyOutTile;
+    int max_tiles = 1;
+    for (int l = 0; l < spec->n_layers; l++) {
+        net.in[l] = l ? spec->width[l - 1] : ps.F;
+        net.out[l] = spec->width[l];
+        net.tiles[l] = (spec->width[l] + kPolicyOutTile - 1) / kPolicyOutTile;
         // the head's tiles cover every bit word in full: bits from S up are written as zeros, not left alone
-        if (l == spec->n_layers - 1 && spec->head == CHUB_PHEAD_PILES && tiles < 2 * Wd) tiles = 2 * Wd;
-        pol->in_dim[l] = in;
-        pa.layer[l].k_pad = (in + 1) & ~1;
-        pa.layer[l].tiles = tiles;
-        max_tiles = tiles > max_tiles ? tiles : max_tiles;
-        stage = std::max(stage, (size_t) width * (size_t) in + (size_t) width);
-        rc = policy_alloc(pol, &pol->d_w[l], (size_t) tiles * (size_t) pa.layer[l].k_pad * kPolicyOutTile);
-        if (!rc) rc = policy_alloc(pol, &pol->d_b[l], (size_t) tiles * kPolicyOutTile);
-        pa.layer[l].w = pol->d_w[l];
-        pa.layer[l].b = pol->d_b[l];
+        if (l == spec->n_layers - 1 && spec->head == CHUB_PHEAD_PILES && net.tiles[l] < 2 * Wd) net.tiles[l] = 2 * Wd;
+        max_tiles = std::max(max_tiles, net.tiles[l]);
     }
     pol->waves = max_tiles < kPolicyMaxWaves ? max_tiles : kPolicyMaxWaves;
-    if (!rc) rc = policy_alloc(pol, &pol->d_stage, stage);
-    if (!rc) rc = policy_alloc(pol, &pol->d_norm, 2 * (size_t) ps.F);
+    int rc = net_alloc_layers(net);
+    for (int l = 0; l < spec->n_layers; l++) pa.layer[l] = {net.d_w[l], net.d_b[l], net.k_pad[l], net.tiles[l]};
     for (int i = 0; i < spec->n_inputs && !rc; i++) {
         pa.in[i].width = ps.width[i];
         pa.in[i].ld = ps.width[i];
         if (spec->inputs[i].kind != CHUB_PIN_OBS) {
-            rc = policy_alloc(pol, &pol->d_scratch[i], N * (size_t) ps.width[i]);
+            rc = net_alloc(net, &pol->d_scratch[i], N * (size_t) ps.width[i]);
             pa.in[i].p = pol->d_scratch[i];
         }
     }
-    if (!rc) rc = policy_alloc(pol, &pol->d_loads, 2 * N);
-    if (!rc) rc = policy_alloc(pol, &pol->d_tail, 2 * N);
-    if (!rc) rc = policy_alloc(pol, &pol->d_bits, N * (size_t) Wd);
-    if (!rc) rc = policy_alloc(pol, &pol->d_rows, N * (size_t) (S + 2));
-    if (!rc) rc = policy_alloc(pol, &pol->d_set, N * (size_t) Wd);
-    if (!rc && spec->normalize) {
-        pa.mean = pol->d_norm;
-        pa.inv_std = pol->d_norm + ps.F;
-        if (hipMemcpy(pol->d_norm, mean, (size_t) ps.F * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(pol->d_norm + ps.F, inv_std, (size_t) ps.F * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-            rc = fail(CHUB_ERR_HIP, "chub_policy_create: mean / inv_std could not be copied to the device");
+    if (!rc) rc = net_alloc(net, &pol->d_loads, 2 * N);
+    if (!rc) rc = net_alloc(net, &pol->d_tail, 2 * N);
+    if (!rc) rc = net_alloc(net, &pol->d_bits, N * (size_t) Wd);
+    if (!rc) rc = net_alloc(net, &pol->d_rows, N * (size_t) (S + 2));
+    if (!rc) rc = net_alloc(net, &pol->d_set, N * (size_t) Wd);
+    if (spec->normalize) {
+        pa.mean = net.d_norm;
+        pa.inv_std = net.d_norm + ps.F;
     }
     pa.loads = pol->d_loads;
-    for (int l = 0; l < spec->n_layers && !rc; l++) rc = policy_upload(pol, l, W[l], b[l]);
+    if (!rc) rc = net_load(net, "chub_policy_create", W, b, mean, inv_std);
     if (rc) {
         const std::string msg = g_err;
         policy_free(pol);
@@ -3818,7 +3979,7 @@ int chub_policy_create(chub_env *e, const chub_policy_spec *spec, const float *c
 
 int chub_policy_destroy(chub_policy *pol) {
     if (!pol) return CHUB_OK;
-    if (pol->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_destroy between chub_graph_begin and chub_graph_end (it synchronises and frees)");
+    if (pol->net.env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_destroy between chub_graph_begin and chub_graph_end (it synchronises and frees)");
     policy_free(pol);
     (void) hipGetLastError();
     return CHUB_OK;
@@ -3826,24 +3987,22 @@ int chub_policy_destroy(chub_policy *pol) {
 
 int chub_policy_set_weights(chub_policy *pol, int32_t layer, const float *W, const float *b) {
     if (!pol || !W || !b) return fail(CHUB_ERR_ARG, "null argument");
-    if (layer < 0 || layer >= pol->spec.n_layers) return fail(CHUB_ERR_ARG, "layer: 0 .. n_layers - 1");
-    if (pol->env->capturing)
-        return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_set_weights between chub_graph_begin and chub_graph_end (it copies and synchronises: use "
-                                          "chub_policy_set_weights_device)");
-    HIP_TRY(hipSetDevice(pol->env->device));
-    (void) hipGetLastError();
-    return policy_upload(pol, layer, W, b);
+    return net_set_weights(pol->net, "chub_policy_set_weights", layer, W, b);
 }
 
 int chub_policy_set_weights_device(chub_policy *pol, int32_t layer, const float *d_W, const float *d_b, void *stream) {
     if (!pol || !d_W || !d_b) return fail(CHUB_ERR_ARG, "null argument");
-    if (layer < 0 || layer >= pol->spec.n_layers) return fail(CHUB_ERR_ARG, "layer: 0 .. n_layers - 1");
-    HIP_TRY(hipSetDevice(pol->env->device));
-    (void) hipGetLastError();
-    launch_policy_relayout(d_W, d_b, pol->d_w[layer], pol->d_b[layer], pol->spec.width[layer], pol->in_dim[layer], pol->pa.layer[layer].k_pad,
-                           pol->pa.layer[layer].tiles, (hipStream_t) stream);
-    HIP_TRY(hipGetLastError());
-    return CHUB_OK;
+    return net_set_weights_device(pol->net, layer, d_W, d_b, stream);
+}
+
+int chub_policy_get_weights(chub_policy *pol, int32_t layer, float *W, float *b) {
+    if (!pol || !W || !b) return fail(CHUB_ERR_ARG, "null argument");
+    return net_get_weights(pol->net, "chub_policy_get_weights", layer, W, b);
+}
+
+int chub_policy_get_weights_device(chub_policy *pol, int32_t layer, float *d_W, float *d_b, void *stream) {
+    if (!pol || !d_W || !d_b) return fail(CHUB_ERR_ARG, "null argument");
+    return net_get_weights_device(pol->net, layer, d_W, d_b, stream);
 }
 
 // what an evaluation asks of its observation argument, and of the handle (the tape rules of the feature calls)
@@ -3887,7 +4046,7 @@ static int policy_feature_blocks(chub_env *e, chub_policy *pol, const float *d_o
 // everything a deterministic evaluation refuses for, with nothing enqueued yet
 static int policy_act_check(const chub_env *e, const chub_policy *pol, const float *d_obs, int64_t ld_obs, const float *d_actions,
                             const uint64_t *d_pile_bits, const float *d_tail) {
-    if (pol->env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
+    if (pol->net.env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
     if (const int rc = policy_check_obs(e, pol, d_obs, ld_obs)) return rc;
     if (!d_actions && !d_pile_bits) return fail(CHUB_ERR_ARG, "chub_policy_act: give d_actions, d_pile_bits or both");
     if (pol->spec.head == CHUB_PHEAD_PILES && d_pile_bits && !d_tail) return fail(CHUB_ERR_ARG, "chub_policy_act: pile bits need d_tail (the two tail actions)");
@@ -3929,7 +4088,7 @@ int chub_policy_act_device(chub_env *e, chub_policy *pol, const float *d_obs, in
 
 int chub_policy_act(chub_env *e, chub_policy *pol, const float *obs, float *actions) {
     if (!e || !pol || !actions) return fail(CHUB_ERR_ARG, "null argument");
-    if (pol->env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
+    if (pol->net.env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
     if (e->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_act between chub_graph_begin and chub_graph_end (it allocates and synchronises)");
     bool obs_block = false;
     for (int i = 0; i < pol->spec.n_inputs; i++) obs_block |= pol->spec.inputs[i].kind == CHUB_PIN_OBS;
@@ -3958,7 +4117,7 @@ static int policy_run(chub_env *e, chub_policy *pol, const chub_population *pop,
                       int64_t first_step, int64_t n_steps, void *stream) {
     const char *who = pop ? "chub_population_run_steps" : "chub_policy_run_steps";
     if (!e || !pol || !d_packed2 || !d_packed2[0] || !d_packed2[1] || first_step < 0 || n_steps < 0) return fail(CHUB_ERR_ARG, "bad argument");
-    if (pol->env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
+    if (pol->net.env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
     if (mode != CHUB_PRUN_LOCKSTEP && mode != CHUB_PRUN_AUTORESET) return fail(CHUB_ERR_ARG, "mode: CHUB_PRUN_LOCKSTEP or CHUB_PRUN_AUTORESET");
     if (mode == CHUB_PRUN_LOCKSTEP && !d_reset_obs) return fail(CHUB_ERR_ARG, "bad argument");
     if (e->hp.rng_mode == CHUB_RNG_COMPAT)
@@ -4006,7 +4165,7 @@ int chub_next_tick(const chub_env *e, uint32_t *out) {
 
 int chub_policy_set_exploration(chub_policy *pol, uint64_t key, const float *log_std) {
     if (!pol || !log_std) return fail(CHUB_ERR_ARG, "null argument");
-    chub_env *e = pol->env;
+    chub_env *e = pol->net.env;
     for (int i = 0; i < pol->G; i++)
         if (!std::isfinite(log_std[i])) return fail(CHUB_ERR_ARG, "log_std[" + std::to_string(i) + "] is not finite");
     if (e->capturing)
@@ -4019,7 +4178,7 @@ int chub_policy_set_exploration(chub_policy *pol, uint64_t key, const float *log
     (void) hipGetLastError();
     HIP_TRY(hipDeviceSynchronize());  // (a sampled launch in flight reads the buffer)
     if (!pol->d_log_std)
-        if (const int rc = policy_alloc(pol, &pol->d_log_std, 4)) return rc;
+        if (const int rc = net_alloc(pol->net, &pol->d_log_std, 4)) return rc;
     HIP_TRY(hipMemcpy(pol->d_log_std, log_std, (size_t) pol->G * sizeof(float), hipMemcpyHostToDevice));
     pol->key[0] = (uint32_t) key;  // (split as the env's seed is)
     pol->key[1] = (uint32_t) (key >> 32);
@@ -4030,7 +4189,7 @@ int chub_policy_set_exploration(chub_policy *pol, uint64_t key, const float *log
 int chub_policy_set_log_std_device(chub_policy *pol, const float *d_log_std, void *stream) {
     if (!pol || !d_log_std) return fail(CHUB_ERR_ARG, "null argument");
     if (!pol->explore) return fail(CHUB_ERR_ARG, "chub_policy_set_exploration first (it makes the policy's log_std buffer)");
-    HIP_TRY(hipSetDevice(pol->env->device));
+    HIP_TRY(hipSetDevice(pol->net.env->device));
     (void) hipGetLastError();
     HIP_TRY(hipMemcpyAsync(pol->d_log_std, d_log_std, (size_t) pol->G * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
     return CHUB_OK;
@@ -4039,7 +4198,7 @@ int chub_policy_set_log_std_device(chub_policy *pol, const float *d_log_std, voi
 // everything chub_policy_sample_device refuses for, with nothing enqueued yet
 static int policy_sample_check(chub_env *e, chub_policy *pol, const float *d_obs, int64_t ld_obs, const chub_policy_sample_out *out) {
     if (!e || !pol || !out) return fail(CHUB_ERR_ARG, "null argument");
-    if (pol->env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
+    if (pol->net.env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
     if (!pol->explore) return fail(CHUB_ERR_ARG, "chub_policy_sample: chub_policy_set_exploration first (the key and log_std)");
     if (const int rc = policy_check_obs(e, pol, d_obs, ld_obs)) return rc;
     if (!out->d_logp) return fail(CHUB_ERR_ARG, "chub_policy_sample: d_logp is required");
@@ -4115,7 +4274,7 @@ int chub_policy_sample_set_device(chub_env *e, chub_policy *pol, const float *d_
 static int policy_collect(chub_env *e, chub_policy *pol, int mode, int which, const chub_rollout *r, uint64_t *d_set_bits, float *d_obs0,
                           int64_t first_step, void *stream) {
     if (!e || !pol || !r || !d_obs0 || (which >= 0 && !d_set_bits)) return fail(CHUB_ERR_ARG, "null argument");
-    if (pol->env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
+    if (pol->net.env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
     if (mode != CHUB_PRUN_LOCKSTEP && mode != CHUB_PRUN_AUTORESET) return fail(CHUB_ERR_ARG, "mode: CHUB_PRUN_LOCKSTEP or CHUB_PRUN_AUTORESET");
     if (!r->d_packed || !r->d_pile_bits || !r->d_tail || !r->d_u || !r->d_logp)
         return fail(CHUB_ERR_ARG, "chub_policy_collect: d_packed, d_pile_bits, d_tail, d_u and d_logp are required");
@@ -4148,7 +4307,7 @@ static int policy_collect(chub_env *e, chub_policy *pol, int mode, int which, co
         o.d_tail = r->d_tail + k * N * 2;
         o.d_u = r->d_u + k * N * (size_t) pol->G;
         o.d_logp = r->d_logp + k * N;
-        o.d_features = r->d_features ? r->d_features + k * N * (size_t) pol->F : nullptr;
+        o.d_features = r->d_features ? r->d_features + k * N * (size_t) pol->net.F : nullptr;
         if ((rc = policy_sample_enqueue(e, pol, obs, ld, nullptr, which, which >= 0 ? d_set_bits + k * N * Wd : nullptr, &o, stream))) return rc;
         if (mode == CHUB_PRUN_LOCKSTEP) rc = chub_step_bits_device_packed(e, o.d_pile_bits, o.d_tail, nullptr, packed, stream);
         else rc = chub_autoreset_step_device(e, pol->d_rows, nullptr, nullptr, nullptr, packed, r->d_final_obs, stream);
@@ -4334,59 +4493,38 @@ int chub_moments_state_device(chub_moments *m, const double **d_state) {
     return CHUB_OK;
 }
 
-// ---- the policy's normaliser, written, read and derived (include/chub.h): all into / out of the policy's own d_norm, which never moves
-static int policy_needs_normalizer(const chub_policy *pol, const char *who) {
-    if (!pol->spec.normalize) return fail(CHUB_ERR_ARG, std::string(who) + ": the policy was created with normalize = 0 (its kernel reads no normaliser)");
+// ---- a net's normaliser derived from the moments; the policy's normaliser calls (include/chub.h)
+static int net_normalizer_from_moments(MlpNet &n, const char *who, chub_moments *m, double eps, void *stream) {
+    if (const int rc = net_needs_normalizer(n, who)) return rc;
+    if (m->env != n.env) return fail(CHUB_ERR_ARG, std::string(who) + ": the " + n.noun + " and the moments were made for different handles");
+    if (m->F != n.F)
+        return fail(CHUB_ERR_ARG, std::string(who) + ": the moments have F = " + std::to_string(m->F) + ", the " + n.noun + "'s " + n.row_noun + " " +
+                                      std::to_string(n.F));
+    if (!(eps > 0.0) || !std::isfinite(eps)) return fail(CHUB_ERR_ARG, std::string(who) + ": eps is finite and > 0");
+    if (const int rc = net_begin(n)) return rc;
+    launch_normalizer_from_moments(m->d_state, n.F, eps, n.d_norm, n.d_norm + n.F, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
     return CHUB_OK;
 }
 
 int chub_policy_set_normalizer(chub_policy *pol, const float *mean, const float *inv_std) {
     if (!pol || !mean || !inv_std) return fail(CHUB_ERR_ARG, "null argument");
-    if (const int rc = policy_needs_normalizer(pol, "chub_policy_set_normalizer")) return rc;
-    if (pol->env->capturing)
-        return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_set_normalizer between chub_graph_begin and chub_graph_end (it copies and synchronises: use "
-                                          "chub_policy_set_normalizer_device)");
-    HIP_TRY(hipSetDevice(pol->env->device));
-    (void) hipGetLastError();
-    HIP_TRY(hipDeviceSynchronize());  // (a policy launch in flight reads the buffer)
-    HIP_TRY(hipMemcpy(pol->d_norm, mean, (size_t) pol->F * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(pol->d_norm + pol->F, inv_std, (size_t) pol->F * sizeof(float), hipMemcpyHostToDevice));
-    return CHUB_OK;
+    return net_set_normalizer(pol->net, "chub_policy_set_normalizer", mean, inv_std);
 }
 
 int chub_policy_set_normalizer_device(chub_policy *pol, const float *d_mean, const float *d_inv_std, void *stream) {
     if (!pol || !d_mean || !d_inv_std) return fail(CHUB_ERR_ARG, "null argument");
-    if (const int rc = policy_needs_normalizer(pol, "chub_policy_set_normalizer_device")) return rc;
-    HIP_TRY(hipSetDevice(pol->env->device));
-    (void) hipGetLastError();
-    HIP_TRY(hipMemcpyAsync(pol->d_norm, d_mean, (size_t) pol->F * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
-    HIP_TRY(hipMemcpyAsync(pol->d_norm + pol->F, d_inv_std, (size_t) pol->F * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
-    return CHUB_OK;
+    return net_set_normalizer_device(pol->net, "chub_policy_set_normalizer_device", d_mean, d_inv_std, stream);
 }
 
 int chub_policy_get_normalizer_device(chub_policy *pol, float *d_mean, float *d_inv_std, void *stream) {
     if (!pol || !d_mean || !d_inv_std) return fail(CHUB_ERR_ARG, "null argument");
-    if (const int rc = policy_needs_normalizer(pol, "chub_policy_get_normalizer_device")) return rc;
-    HIP_TRY(hipSetDevice(pol->env->device));
-    (void) hipGetLastError();
-    HIP_TRY(hipMemcpyAsync(d_mean, pol->d_norm, (size_t) pol->F * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
-    HIP_TRY(hipMemcpyAsync(d_inv_std, pol->d_norm + pol->F, (size_t) pol->F * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
-    return CHUB_OK;
+    return net_get_normalizer_device(pol->net, "chub_policy_get_normalizer_device", d_mean, d_inv_std, stream);
 }
 
 int chub_policy_normalizer_from_moments_device(chub_policy *pol, chub_moments *m, double eps, void *stream) {
     if (!pol || !m) return fail(CHUB_ERR_ARG, "null argument");
-    if (const int rc = policy_needs_normalizer(pol, "chub_policy_normalizer_from_moments_device")) return rc;
-    if (m->env != pol->env) return fail(CHUB_ERR_ARG, "chub_policy_normalizer_from_moments_device: the policy and the moments were made for different handles");
-    if (m->F != pol->F)
-        return fail(CHUB_ERR_ARG, "chub_policy_normalizer_from_moments_device: the moments have F = " + std::to_string(m->F) + ", the policy's feature row " +
-                                      std::to_string(pol->F));
-    if (!(eps > 0.0) || !std::isfinite(eps)) return fail(CHUB_ERR_ARG, "chub_policy_normalizer_from_moments_device: eps is finite and > 0");
-    HIP_TRY(hipSetDevice(pol->env->device));
-    (void) hipGetLastError();
-    launch_normalizer_from_moments(m->d_state, pol->F, eps, pol->d_norm, pol->d_norm + pol->F, (hipStream_t) stream);
-    HIP_TRY(hipGetLastError());
-    return CHUB_OK;
+    return net_normalizer_from_moments(pol->net, "chub_policy_normalizer_from_moments_device", m, eps, stream);
 }
 
 }  // extern "C"
@@ -4409,6 +4547,7 @@ struct chub_population {
     int64_t off_w[kPolicyMaxLayers], off_b[kPolicyMaxLayers];  // a layer's blocks inside a member's
     double *d_part;                          // [chunks][items of the largest layer][4]: the ES gradient's partial sums
     int32_t chunk_pairs, chunks;             // pairs per chunk and chunks, fixed at create for (P, spec)
+    DeviceAllocs allocs;
 };
 
 extern "C" {
@@ -4419,11 +4558,9 @@ constexpr size_t kPopPartialBytes = 64u << 20;      // the partial sums stay at 
 
 static void population_free(chub_population *pop) {
     chub_policy *pol = pop->pol;
-    (void) hipSetDevice(pol->env->device);
+    (void) hipSetDevice(pol->net.env->device);
     (void) hipDeviceSynchronize();  // (a launch still in flight reads the weights)
-    if (pop->d_params) (void) hipFree(pop->d_params);
-    if (pop->d_stage) (void) hipFree(pop->d_stage);
-    if (pop->d_part) (void) hipFree(pop->d_part);
+    pop->allocs.free_all();
     pol->populations.erase(std::remove(pol->populations.begin(), pol->populations.end(), pop), pol->populations.end());
     delete pop;
 }
@@ -4453,29 +4590,29 @@ int chub_population_param_count(const chub_config *cfg, const chub_policy_spec *
 
 // one layer of the population as the weight kernels take it
 static PopLayerArgs population_layer(const chub_population *pop, int l, uint32_t generation) {
-    const chub_policy *pol = pop->pol;
+    const MlpNet &net = pop->pol->net;
     PopLayerArgs a;
     a.w = pop->d_params + pop->off_w[l];
     a.bias = pop->d_params + pop->off_b[l];
     a.stride = pop->member_floats;
-    a.out = pol->spec.width[l];
-    a.in = pol->in_dim[l];
-    a.k_pad = pol->pa.layer[l].k_pad;
-    a.tiles = pol->pa.layer[l].tiles;
+    a.out = net.out[l];
+    a.in = net.in[l];
+    a.k_pad = net.k_pad[l];
+    a.tiles = net.tiles[l];
     a.layer = l;
     a.pairs = pop->P / 2;
     a.key[0] = pop->key[0];
     a.key[1] = pop->key[1];
     a.generation = generation;
-    a.normal_icdf = (const float *) pol->env->tb.normal_icdf;
-    a.normal_tail = (const float *) pol->env->tb.normal_tail;
+    a.normal_icdf = (const float *) net.env->tb.normal_icdf;
+    a.normal_tail = (const float *) net.env->tb.normal_tail;
     return a;
 }
 
 int chub_population_create(chub_policy *pol, int32_t P, uint64_t key, chub_population **out) {
     if (!pol || !out) return fail(CHUB_ERR_ARG, "null argument");
     *out = nullptr;
-    chub_env *e = pol->env;
+    chub_env *e = pol->net.env;
     const int64_t N = e->hp.n_envs;
     if (P < 2 || (P & 1)) return fail(CHUB_ERR_ARG, "chub_population_create: P is even and at least 2 (members 2j and 2j + 1 are an antithetic pair)");
     if (N % P != 0 || (N / P) % kPolicyEnvTile != 0)
@@ -4490,14 +4627,14 @@ int chub_population_create(chub_policy *pol, int32_t P, uint64_t key, chub_popul
     pop->E = (int32_t) (N / P);
     pop->key[0] = (uint32_t) key;  // (split as the policy's key is)
     pop->key[1] = (uint32_t) (key >> 32);
+    const MlpNet &net = pol->net;
     int64_t at = 0, items = 0;
-    for (int l = 0; l < pol->spec.n_layers; l++) {
-        const PolicyLayer &L = pol->pa.layer[l];
+    for (int l = 0; l < net.n_layers; l++) {
         pop->off_w[l] = at;
-        at += (int64_t) L.tiles * L.k_pad * kPolicyOutTile;
+        at += (int64_t) net.tiles[l] * net.k_pad[l] * kPolicyOutTile;
         pop->off_b[l] = at;
-        at += (int64_t) L.tiles * kPolicyOutTile;
-        items = std::max(items, (int64_t) pol->spec.width[l] * (pol->in_dim[l] / 4 + 1));
+        at += (int64_t) net.tiles[l] * kPolicyOutTile;
+        items = std::max(items, (int64_t) net.out[l] * (net.in[l] / 4 + 1));
     }
     pop->member_floats = at;
     // the gradient's chunks of pairs: at least kPopChunkPairs pairs each, at most kPopMaxChunks chunks, the partials within kPopPartialBytes
@@ -4508,18 +4645,16 @@ int chub_population_create(chub_policy *pol, int32_t P, uint64_t key, chub_popul
     pop->chunk_pairs = (int32_t) ((pairs + chunks - 1) / chunks);
     pop->chunks = (pairs + pop->chunk_pairs - 1) / pop->chunk_pairs;
     pol->populations.push_back(pop);
-    const size_t bytes = (size_t) P * (size_t) at * sizeof(float), part = (size_t) pop->chunks * chunk_bytes;
-    bool ok = hipMalloc((void **) &pop->d_params, bytes) == hipSuccess && hipMalloc((void **) &pop->d_stage, bytes) == hipSuccess &&
-              hipMalloc((void **) &pop->d_part, part) == hipSuccess && hipMemset(pop->d_stage, 0, bytes) == hipSuccess &&
-              hipMemset(pop->d_part, 0, part) == hipSuccess;
+    const size_t floats = (size_t) P * (size_t) at;
+    bool ok = !pop->allocs.zeroed(&pop->d_params, floats) && !pop->allocs.zeroed(&pop->d_stage, floats) &&
+              !pop->allocs.zeroed(&pop->d_part, (size_t) pop->chunks * (size_t) items * 4);
     // every member = the centre's current weights: its blocks are the member's layout already
     for (int m = 0; m < P && ok; m++)
-        for (int l = 0; l < pol->spec.n_layers && ok; l++) {
-            const PolicyLayer &L = pol->pa.layer[l];
+        for (int l = 0; l < net.n_layers && ok; l++) {
             float *base = pop->d_params + (int64_t) m * at;
-            ok = hipMemcpyAsync(base + pop->off_w[l], pol->d_w[l], (size_t) L.tiles * L.k_pad * kPolicyOutTile * sizeof(float), hipMemcpyDeviceToDevice,
-                                nullptr) == hipSuccess &&
-                 hipMemcpyAsync(base + pop->off_b[l], pol->d_b[l], (size_t) L.tiles * kPolicyOutTile * sizeof(float), hipMemcpyDeviceToDevice, nullptr) ==
+            ok = hipMemcpyAsync(base + pop->off_w[l], net.d_w[l], (size_t) net.tiles[l] * net.k_pad[l] * kPolicyOutTile * sizeof(float),
+                                hipMemcpyDeviceToDevice, nullptr) == hipSuccess &&
+                 hipMemcpyAsync(base + pop->off_b[l], net.d_b[l], (size_t) net.tiles[l] * kPolicyOutTile * sizeof(float), hipMemcpyDeviceToDevice, nullptr) ==
                      hipSuccess;
         }
     if (!ok || hipDeviceSynchronize() != hipSuccess) {
@@ -4533,7 +4668,7 @@ int chub_population_create(chub_policy *pol, int32_t P, uint64_t key, chub_popul
 
 int chub_population_destroy(chub_population *pop) {
     if (!pop) return CHUB_OK;
-    if (pop->pol->env->capturing)
+    if (pop->pol->net.env->capturing)
         return fail(CHUB_ERR_UNSUPPORTED, "chub_population_destroy between chub_graph_begin and chub_graph_end (it synchronises and frees)");
     population_free(pop);
     (void) hipGetLastError();
@@ -4549,12 +4684,12 @@ int chub_population_perturb_device(chub_population *pop, const float *const *d_W
         for (int l = 0; l < pol->spec.n_layers; l++)
             if (!d_W[l] || !d_b[l]) return fail(CHUB_ERR_ARG, "null argument");
     if (!std::isfinite(sigma) || sigma < 0.0f) return fail(CHUB_ERR_ARG, "chub_population_perturb_device: sigma is finite and >= 0");
-    HIP_TRY(hipSetDevice(pol->env->device));
+    HIP_TRY(hipSetDevice(pol->net.env->device));
     (void) hipGetLastError();
     for (int l = 0; l < pol->spec.n_layers; l++) {
         const PopLayerArgs a = population_layer(pop, l, generation);
         if (d_W) launch_population_perturb(a, d_W[l], d_b[l], 0, sigma, (hipStream_t) stream);
-        else launch_population_perturb(a, pol->d_w[l], pol->d_b[l], 1, sigma, (hipStream_t) stream);
+        else launch_population_perturb(a, pol->net.d_w[l], pol->net.d_b[l], 1, sigma, (hipStream_t) stream);
     }
     HIP_TRY(hipGetLastError());
     return CHUB_OK;
@@ -4569,12 +4704,10 @@ static int population_check_member(const chub_population *pop, int32_t m, int32_
 int chub_population_set_member_device(chub_population *pop, int32_t m, int32_t layer, const float *d_W, const float *d_b, void *stream) {
     if (!pop || !d_W || !d_b) return fail(CHUB_ERR_ARG, "null argument");
     if (const int rc = population_check_member(pop, m, layer)) return rc;
-    const chub_policy *pol = pop->pol;
-    HIP_TRY(hipSetDevice(pol->env->device));
+    HIP_TRY(hipSetDevice(pop->pol->net.env->device));
     (void) hipGetLastError();
     float *base = pop->d_params + (int64_t) m * pop->member_floats;
-    launch_policy_relayout(d_W, d_b, base + pop->off_w[layer], base + pop->off_b[layer], pol->spec.width[layer], pol->in_dim[layer],
-                           pol->pa.layer[layer].k_pad, pol->pa.layer[layer].tiles, (hipStream_t) stream);
+    net_relayout(pop->pol->net, layer, d_W, d_b, base + pop->off_w[layer], base + pop->off_b[layer], stream);
     HIP_TRY(hipGetLastError());
     return CHUB_OK;
 }
@@ -4582,12 +4715,10 @@ int chub_population_set_member_device(chub_population *pop, int32_t m, int32_t l
 int chub_population_get_member_device(chub_population *pop, int32_t m, int32_t layer, float *d_W, float *d_b, void *stream) {
     if (!pop || !d_W || !d_b) return fail(CHUB_ERR_ARG, "null argument");
     if (const int rc = population_check_member(pop, m, layer)) return rc;
-    const chub_policy *pol = pop->pol;
-    HIP_TRY(hipSetDevice(pol->env->device));
+    HIP_TRY(hipSetDevice(pop->pol->net.env->device));
     (void) hipGetLastError();
     const float *base = pop->d_params + (int64_t) m * pop->member_floats;
-    launch_policy_unlayout(base + pop->off_w[layer], base + pop->off_b[layer], d_W, d_b, pol->spec.width[layer], pol->in_dim[layer],
-                           pol->pa.layer[layer].k_pad, (hipStream_t) stream);
+    net_unlayout(pop->pol->net, layer, base + pop->off_w[layer], base + pop->off_b[layer], d_W, d_b, stream);
     HIP_TRY(hipGetLastError());
     return CHUB_OK;
 }
@@ -4596,17 +4727,10 @@ int chub_population_get_member_device(chub_population *pop, int32_t m, int32_t l
 int chub_population_set_member(chub_population *pop, int32_t m, int32_t layer, const float *W, const float *b) {
     if (!pop || !W || !b) return fail(CHUB_ERR_ARG, "null argument");
     if (const int rc = population_check_member(pop, m, layer)) return rc;
-    chub_policy *pol = pop->pol;
-    if (pol->env->capturing)
-        return fail(CHUB_ERR_UNSUPPORTED, "chub_population_set_member between chub_graph_begin and chub_graph_end (it copies and synchronises: use "
-                                          "chub_population_set_member_device)");
-    const size_t nw = (size_t) pol->spec.width[layer] * (size_t) pol->in_dim[layer], nb = (size_t) pol->spec.width[layer];
-    HIP_TRY(hipSetDevice(pol->env->device));
-    (void) hipGetLastError();
-    HIP_TRY(hipDeviceSynchronize());  // (the staging buffer is one; nothing may still be reading the layer either)
-    HIP_TRY(hipMemcpy(pol->d_stage, W, nw * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(pol->d_stage + nw, b, nb * sizeof(float), hipMemcpyHostToDevice));
-    if (const int rc = chub_population_set_member_device(pop, m, layer, pol->d_stage, pol->d_stage + nw, nullptr)) return rc;
+    MlpNet &net = pop->pol->net;
+    if (const int rc = net_begin_host(net, "chub_population_set_member")) return rc;
+    if (const int rc = net_stage_in(net, layer, W, b)) return rc;
+    if (const int rc = chub_population_set_member_device(pop, m, layer, net.d_stage, net_stage_b(net, layer), nullptr)) return rc;
     HIP_TRY(hipDeviceSynchronize());
     return CHUB_OK;
 }
@@ -4614,26 +4738,18 @@ int chub_population_set_member(chub_population *pop, int32_t m, int32_t layer, c
 int chub_population_get_member(chub_population *pop, int32_t m, int32_t layer, float *W, float *b) {
     if (!pop || !W || !b) return fail(CHUB_ERR_ARG, "null argument");
     if (const int rc = population_check_member(pop, m, layer)) return rc;
-    chub_policy *pol = pop->pol;
-    if (pol->env->capturing)
-        return fail(CHUB_ERR_UNSUPPORTED, "chub_population_get_member between chub_graph_begin and chub_graph_end (it copies and synchronises: use "
-                                          "chub_population_get_member_device)");
-    const size_t nw = (size_t) pol->spec.width[layer] * (size_t) pol->in_dim[layer], nb = (size_t) pol->spec.width[layer];
-    HIP_TRY(hipSetDevice(pol->env->device));
-    (void) hipGetLastError();
+    MlpNet &net = pop->pol->net;
+    if (const int rc = net_begin_host(net, "chub_population_get_member")) return rc;
     HIP_TRY(hipDeviceSynchronize());
-    if (const int rc = chub_population_get_member_device(pop, m, layer, pol->d_stage, pol->d_stage + nw, nullptr)) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(W, pol->d_stage, nw * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(b, pol->d_stage + nw, nb * sizeof(float), hipMemcpyDeviceToHost));
-    return CHUB_OK;
+    if (const int rc = chub_population_get_member_device(pop, m, layer, net.d_stage, net_stage_b(net, layer), nullptr)) return rc;
+    return net_stage_out(net, layer, W, b);
 }
 
 int chub_population_copy_members_device(chub_population *pop, const int32_t *d_src, const int32_t *d_dst, int32_t count, void *stream) {
     if (!pop || !d_src || !d_dst) return fail(CHUB_ERR_ARG, "null argument");
     if (count < 0 || count > pop->P)
         return fail(CHUB_ERR_ARG, "chub_population_copy_members_device: count is 0 .. P (every source is staged before any destination is written)");
-    HIP_TRY(hipSetDevice(pop->pol->env->device));
+    HIP_TRY(hipSetDevice(pop->pol->net.env->device));
     (void) hipGetLastError();
     launch_population_copy(pop->d_params, pop->d_stage, pop->member_floats, pop->P, d_src, d_dst, count, (hipStream_t) stream);
     HIP_TRY(hipGetLastError());
@@ -4643,7 +4759,7 @@ int chub_population_copy_members_device(chub_population *pop, const int32_t *d_s
 int chub_population_act_device(chub_env *e, chub_population *pop, const float *d_obs, int64_t ld_obs, const uint8_t *d_mask, float *d_actions,
                                uint64_t *d_pile_bits, float *d_tail, void *stream) {
     if (!e || !pop) return fail(CHUB_ERR_ARG, "null argument");
-    if (pop->pol->env != e) return fail(CHUB_ERR_ARG, "this population was made for another handle");
+    if (pop->pol->net.env != e) return fail(CHUB_ERR_ARG, "this population was made for another handle");
     if (const int rc = policy_act_check(e, pop->pol, d_obs, ld_obs, d_actions, d_pile_bits, d_tail)) return rc;
     return policy_act_enqueue(e, pop->pol, pop, d_obs, ld_obs, d_mask, d_actions, d_pile_bits, d_tail, stream);
 }
@@ -4651,7 +4767,7 @@ int chub_population_act_device(chub_env *e, chub_population *pop, const float *d
 int chub_population_run_steps(chub_env *e, chub_population *pop, int mode, float *const *d_packed2, float *d_reset_obs, float *d_final_obs,
                               int64_t first_step, int64_t n_steps, void *stream) {
     if (!e || !pop) return fail(CHUB_ERR_ARG, "null argument");
-    if (pop->pol->env != e) return fail(CHUB_ERR_ARG, "this population was made for another handle");
+    if (pop->pol->net.env != e) return fail(CHUB_ERR_ARG, "this population was made for another handle");
     return policy_run(e, pop->pol, pop, mode, d_packed2, d_reset_obs, d_final_obs, first_step, n_steps, stream);
 }
 
@@ -4661,7 +4777,7 @@ int chub_population_es_gradient_device(chub_population *pop, const float *d_util
     const chub_policy *pol = pop->pol;
     for (int l = 0; l < pol->spec.n_layers; l++)
         if (!d_gW[l] || !d_gb[l]) return fail(CHUB_ERR_ARG, "null argument");
-    HIP_TRY(hipSetDevice(pol->env->device));
+    HIP_TRY(hipSetDevice(pol->net.env->device));
     (void) hipGetLastError();
     for (int l = 0; l < pol->spec.n_layers; l++)  // (one buffer of partials: the stream orders a layer's merge before the next layer's sums)
         launch_population_es_gradient(population_layer(pop, l, generation), d_util, pop->chunk_pairs, pop->chunks, pop->d_part, d_gW[l], d_gb[l],
@@ -4688,25 +4804,25 @@ static int grad_blocks(const GradPlan &gp, int64_t R) {
     return (int) std::min(nb, by_bytes);
 }
 
-static size_t grad_workspace(const GradPlan &gp, int blocks) {
-    return (size_t) gp.wrm_floats * sizeof(float) + (size_t) blocks * ((size_t) gp.part_floats * sizeof(float) + kGradPart64 * sizeof(double));
+// (stats: the f64 a workgroup leaves beside its f32 partials, kGradPart64 or kCriticStats)
+static size_t grad_workspace(const GradPlan &gp, int blocks, int stats) {
+    return (size_t) gp.wrm_floats * sizeof(float) + (size_t) blocks * ((size_t) gp.part_floats * sizeof(float) + (size_t) stats * sizeof(double));
 }
 
-static int grad_plan(const chub_policy_spec *sp, const PolicyShape &ps, GradPlan &gp) {
+static int grad_plan(int nl, const int32_t *width, int F, GradPlan &gp) {
     memset(&gp, 0, sizeof gp);
-    const int nl = sp->n_layers;
-    int rows = (ps.F + 31) / 32 * 32, dmax = 0;
+    int rows = (F + 31) / 32 * 32, dmax = 0;
     gp.x_rows = rows;
     for (int l = 0; l < nl; l++) {
-        gp.in[l] = l ? sp->width[l - 1] : ps.F;
-        gp.ot[l] = (sp->width[l] + 31) / 32;
+        gp.in[l] = l ? width[l - 1] : F;
+        gp.ot[l] = (width[l] + 31) / 32;
         gp.it[l] = (gp.in[l] + 31) / 32;
         gp.pair0[l] = gp.n_pairs;
         gp.n_pairs += gp.ot[l] * gp.it[l];
         gp.bias0[l] = gp.bias_floats;
         gp.bias_floats += gp.ot[l] * 32;
         gp.param0[l] = gp.n_params;
-        gp.n_params += (int64_t) sp->width[l] * (gp.in[l] + 1);
+        gp.n_params += (int64_t) width[l] * (gp.in[l] + 1);
         if (l) {
             gp.wrm_off[l] = gp.wrm_floats;
             gp.wrm_floats += (int64_t) gp.ot[l] * 32 * gp.it[l] * 32;
@@ -4731,24 +4847,120 @@ static int grad_plan(const chub_policy_spec *sp, const PolicyShape &ps, GradPlan
     return CHUB_OK;
 }
 
-struct chub_policy_grad {
-    chub_policy *pol;
-    int64_t max_rows;
+// the *_plan_out block of chub_policy_grad_plan and chub_critic_plan
+template <class PlanOut>
+static void grad_plan_out(const GradPlan &gp, int64_t R, int stats, PlanOut *out) {
+    out->n_params = gp.n_params;
+    out->workgroups = grad_blocks(gp, R);
+    out->lds_rows = gp.lds_rows;
+    out->lds_bytes = gp.lds_rows * kGradRowStride * (int32_t) sizeof(float);
+    out->in_registers = gp.in_registers;
+    out->workspace_bytes = (int64_t) grad_workspace(gp, out->workgroups, stats);
+}
+
+// what the gradient launches of one net keep between calls: the plan, the row-major copies of layers 1.., the workgroups' f32 and f64 partials
+struct GradWorkspace {
     GradPlan gp;
     int32_t max_blocks;
     float *d_wrm, *d_part;
     double *d_part64;
+    DeviceAllocs allocs;
+};
+
+// nullptr, or what failed (DeviceAllocs::zeroed); the owner frees ws.allocs
+static const char *grad_workspace_create(GradWorkspace &ws, const GradPlan &gp, int64_t max_rows, int stats) {
+    ws.gp = gp;
+    ws.max_blocks = grad_blocks(gp, max_rows);
+    if (const char *what = ws.allocs.zeroed(&ws.d_wrm, (size_t) gp.wrm_floats)) return what;
+    if (const char *what = ws.allocs.zeroed(&ws.d_part, (size_t) ws.max_blocks * (size_t) gp.part_floats)) return what;
+    return ws.allocs.zeroed(&ws.d_part64, (size_t) ws.max_blocks * (size_t) stats);
+}
+
+// what a gradient call asks of its rows; ld_text names the stride and the row in the caller's words
+static int grad_check_rows(const char *who, int64_t max_rows, int64_t R, int64_t n_rows, const int64_t *d_rows, int64_t ld, int F, const char *ld_text) {
+    if (R <= 0 || R > max_rows) return fail(CHUB_ERR_ARG, std::string(who) + ": R is 1 .. max_rows = " + std::to_string(max_rows));
+    if (n_rows < 1) return fail(CHUB_ERR_ARG, std::string(who) + ": n_rows, the rows the arrays hold, is at least 1");
+    if (!d_rows && R > n_rows) return fail(CHUB_ERR_ARG, std::string(who) + ": without d_rows the call reads rows 0 .. R - 1: R <= n_rows");
+    if (ld < F) return fail(CHUB_ERR_ARG, std::string(ld_text) + std::to_string(F) + " floats");
+    return CHUB_OK;
+}
+
+static void grad_layers(const MlpNet &n, const GradWorkspace &ws, GradLayer *layer) {
+    const GradPlan &gp = ws.gp;
+    for (int l = 0; l < n.n_layers; l++) {
+        GradLayer &L = layer[l];
+        L.w = n.d_w[l];
+        L.b = n.d_b[l];
+        L.wrm = l ? ws.d_wrm + gp.wrm_off[l] : nullptr;
+        L.k_pad = n.k_pad[l];
+        L.in = gp.in[l];
+        L.out = n.out[l];
+        L.ot = gp.ot[l];
+        L.it = gp.it[l];
+        L.h_row0 = gp.h_row0[l];
+        L.pair0 = gp.pair0[l];
+        L.bias0 = gp.bias0[l];
+    }
+}
+
+// what PolicyGradArgs and CriticArgs share: the layers, the partials and the plan's numbers (a is zeroed first)
+template <class Args>
+static void grad_args(const MlpNet &n, const GradWorkspace &ws, Args &a) {
+    const GradPlan &gp = ws.gp;
+    memset(&a, 0, sizeof a);
+    grad_layers(n, ws, a.layer);
+    a.part = ws.d_part;
+    a.part64 = ws.d_part64;
+    a.n_layers = n.n_layers;
+    a.F = n.F;
+    a.x_rows = gp.x_rows;
+    a.d_row0[0] = gp.d_row0[0];
+    a.d_row0[1] = gp.d_row0[1];
+    a.s_row0 = gp.s_row0;
+    a.n_pairs = gp.n_pairs;
+    a.part_floats = gp.part_floats;
+    a.bias_floats = gp.bias_floats;
+}
+
+// what GradMergeArgs and CriticMergeArgs share (m is zeroed first); backward: some layer's gradient is asked for
+template <class Merge, class Out>
+static void grad_merge_args(const MlpNet &n, const GradWorkspace &ws, int64_t R, const Out *out, Merge &m) {
+    const GradPlan &gp = ws.gp;
+    memset(&m, 0, sizeof m);
+    for (int l = 0; l < n.n_layers; l++) {
+        m.gW[l] = out->d_gW[l];
+        m.gb[l] = out->d_gb[l];
+        m.in[l] = gp.in[l];
+        m.it[l] = gp.it[l];
+        m.pair0[l] = gp.pair0[l];
+        m.bias0[l] = gp.bias0[l];
+        m.param0[l] = gp.param0[l];
+        m.backward |= out->d_gW[l] != nullptr || out->d_gb[l] != nullptr;
+    }
+    m.param0[n.n_layers] = gp.param0[n.n_layers];
+    m.part = ws.d_part;
+    m.part64 = ws.d_part64;
+    m.stats = out->d_stats;
+    m.R = R;
+    m.n_layers = n.n_layers;
+    m.blocks = grad_blocks(gp, R);
+    m.part_floats = gp.part_floats;
+    m.bias_base = gp.n_pairs * 1024;
+}
+
+struct chub_policy_grad {
+    chub_policy *pol;
+    int64_t max_rows;
+    GradWorkspace ws;
 };
 
 extern "C" {
 
 static void policy_grad_free(chub_policy_grad *g) {
     chub_policy *pol = g->pol;
-    (void) hipSetDevice(pol->env->device);
+    (void) hipSetDevice(pol->net.env->device);
     (void) hipDeviceSynchronize();  // (a launch still in flight reads the copies and writes the partials)
-    if (g->d_wrm) (void) hipFree(g->d_wrm);
-    if (g->d_part) (void) hipFree(g->d_part);
-    if (g->d_part64) (void) hipFree(g->d_part64);
+    g->ws.allocs.free_all();
     pol->grads.erase(std::remove(pol->grads.begin(), pol->grads.end(), g), pol->grads.end());
     delete g;
 }
@@ -4759,13 +4971,8 @@ int chub_policy_grad_plan(const chub_config *cfg, const chub_policy_spec *spec, 
     PolicyShape ps;
     if (const int rc = policy_shape(cfg->station_list, spec, ps)) return rc;
     GradPlan gp;
-    if (const int rc = grad_plan(spec, ps, gp)) return rc;
-    out->n_params = gp.n_params;
-    out->workgroups = grad_blocks(gp, R);
-    out->lds_rows = gp.lds_rows;
-    out->lds_bytes = gp.lds_rows * kGradRowStride * (int32_t) sizeof(float);
-    out->in_registers = gp.in_registers;
-    out->workspace_bytes = (int64_t) grad_workspace(gp, out->workgroups);
+    if (const int rc = grad_plan(spec->n_layers, spec->width, ps.F, gp)) return rc;
+    grad_plan_out(gp, R, kGradPart64, out);
     return CHUB_OK;
 }
 
@@ -4773,12 +4980,12 @@ int chub_policy_grad_create(chub_policy *pol, int64_t max_rows, chub_policy_grad
     if (!pol || !out) return fail(CHUB_ERR_ARG, "null argument");
     *out = nullptr;
     if (max_rows < 1) return fail(CHUB_ERR_ARG, "chub_policy_grad_create: max_rows is at least 1");
-    chub_env *e = pol->env;
+    chub_env *e = pol->net.env;
     if (!pol->explore) return fail(CHUB_ERR_ARG, "chub_policy_grad_create: chub_policy_set_exploration first (the log-probability needs log_std)");
     PolicyShape ps;
     if (const int rc = policy_shape(e->hp.S, &pol->spec, ps)) return rc;
     GradPlan gp;
-    if (const int rc = grad_plan(&pol->spec, ps, gp)) return rc;
+    if (const int rc = grad_plan(pol->spec.n_layers, pol->spec.width, ps.F, gp)) return rc;
     if (e->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_grad_create between chub_graph_begin and chub_graph_end (it allocates and synchronises)");
     HIP_TRY(hipSetDevice(e->device));
     (void) hipGetLastError();
@@ -4789,17 +4996,8 @@ int chub_policy_grad_create(chub_policy *pol, int64_t max_rows, chub_policy_grad
     chub_policy_grad *g = new chub_policy_grad();
     g->pol = pol;
     g->max_rows = max_rows;
-    g->gp = gp;
-    g->max_blocks = grad_blocks(gp, max_rows);
-    g->d_wrm = g->d_part = nullptr;
-    g->d_part64 = nullptr;
     pol->grads.push_back(g);
-    const size_t wrm = (size_t) std::max<int64_t>(gp.wrm_floats, 1) * sizeof(float), part = (size_t) g->max_blocks * (size_t) gp.part_floats * sizeof(float),
-                 p64 = (size_t) g->max_blocks * kGradPart64 * sizeof(double);
-    const bool ok = hipMalloc((void **) &g->d_wrm, wrm) == hipSuccess && hipMalloc((void **) &g->d_part, part) == hipSuccess &&
-                    hipMalloc((void **) &g->d_part64, p64) == hipSuccess && hipMemset(g->d_wrm, 0, wrm) == hipSuccess &&
-                    hipMemset(g->d_part, 0, part) == hipSuccess && hipMemset(g->d_part64, 0, p64) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
-    if (!ok) {
+    if (grad_workspace_create(g->ws, gp, max_rows, kGradPart64) || hipDeviceSynchronize() != hipSuccess) {
         policy_grad_free(g);
         (void) hipGetLastError();
         return fail(CHUB_ERR_HIP, "chub_policy_grad_create: out of device memory");
@@ -4810,7 +5008,7 @@ int chub_policy_grad_create(chub_policy *pol, int64_t max_rows, chub_policy_grad
 
 int chub_policy_grad_destroy(chub_policy_grad *g) {
     if (!g) return CHUB_OK;
-    if (g->pol->env->capturing)
+    if (g->pol->net.env->capturing)
         return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_grad_destroy between chub_graph_begin and chub_graph_end (it synchronises and frees)");
     policy_grad_free(g);
     (void) hipGetLastError();
@@ -4822,11 +5020,9 @@ int chub_policy_grad_device(chub_policy_grad *g, const chub_policy_grad_in *in, 
     const chub_policy *pol = g->pol;
     const bool piles = pol->spec.head == CHUB_PHEAD_PILES;
     if (!in->d_features || !in->d_u || !in->d_adv || (piles && !in->d_pile_bits)) return fail(CHUB_ERR_ARG, "null argument");
-    if (in->R <= 0 || in->R > g->max_rows)
-        return fail(CHUB_ERR_ARG, "chub_policy_grad_device: R is 1 .. max_rows = " + std::to_string(g->max_rows));
-    if (in->n_rows < 1) return fail(CHUB_ERR_ARG, "chub_policy_grad_device: n_rows, the rows the arrays hold, is at least 1");
-    if (!in->d_rows && in->R > in->n_rows) return fail(CHUB_ERR_ARG, "chub_policy_grad_device: without d_rows the call reads rows 0 .. R - 1: R <= n_rows");
-    if (in->ld_features < pol->F) return fail(CHUB_ERR_ARG, "ld_features: at least the feature row's " + std::to_string(pol->F) + " floats");
+    if (const int rc = grad_check_rows("chub_policy_grad_device", g->max_rows, in->R, in->n_rows, in->d_rows, in->ld_features, pol->net.F,
+                                       "ld_features: at least the feature row's "))
+        return rc;
     if (in->loss != CHUB_PLOSS_COEF && in->loss != CHUB_PLOSS_PPO_CLIP) return fail(CHUB_ERR_ARG, "loss: CHUB_PLOSS_COEF or CHUB_PLOSS_PPO_CLIP");
     if (in->loss == CHUB_PLOSS_PPO_CLIP) {
         if (!(in->clip_eps > 0.0f && in->clip_eps < 1.0f)) return fail(CHUB_ERR_ARG, "clip_eps: inside (0, 1) under CHUB_PLOSS_PPO_CLIP");
@@ -4835,16 +5031,17 @@ int chub_policy_grad_device(chub_policy_grad *g, const chub_policy_grad_in *in, 
     if (!std::isfinite(in->ent_coef)) return fail(CHUB_ERR_ARG, "ent_coef is not finite");
     if (!piles && in->d_set_bits) return fail(CHUB_ERR_ARG, "chub_policy_grad_device: under CHUB_PHEAD_LOADS the log-probability has no pile terms: d_set_bits must be NULL");
     if (!pol->explore) return fail(CHUB_ERR_ARG, "chub_policy_grad_device: chub_policy_set_exploration first (the log-probability needs log_std)");
-    HIP_TRY(hipSetDevice(pol->env->device));
+    HIP_TRY(hipSetDevice(pol->net.env->device));
     (void) hipGetLastError();
-    const GradPlan &gp = g->gp;
-    const int nl = pol->spec.n_layers;
+    const GradPlan &gp = g->ws.gp;
     PolicyGradArgs a;
-    memset(&a, 0, sizeof a);
+    grad_args(pol->net, g->ws, a);
     GradMergeArgs m;
-    memset(&m, 0, sizeof m);
-    bool backward = out->d_glog_std != nullptr;
-    for (int l = 0; l < nl; l++) backward |= out->d_gW[l] != nullptr || out->d_gb[l] != nullptr;
+    grad_merge_args(pol->net, g->ws, in->R, out, m);
+    for (int l = 0; l < pol->net.n_layers; l++) m.out[l] = pol->net.out[l];
+    m.glog_std = out->d_glog_std;
+    m.G = pol->G;
+    m.backward |= out->d_glog_std != nullptr;
     a.R = in->R;
     a.rows_total = in->n_rows;
     a.rows = in->d_rows;
@@ -4861,17 +5058,9 @@ int chub_policy_grad_device(chub_policy_grad *g, const chub_policy_grad_in *in, 
     a.log_std = pol->d_log_std;
     a.logp_new = out->d_logp_new;
     a.entropy = out->d_entropy;
-    a.part = g->d_part;
-    a.part64 = g->d_part64;
     a.clip = pol->spec.clip;
     a.clip_eps = in->clip_eps;
     a.ent_coef = in->ent_coef;
-    a.n_layers = nl;
-    a.F = pol->F;
-    a.x_rows = gp.x_rows;
-    a.d_row0[0] = gp.d_row0[0];
-    a.d_row0[1] = gp.d_row0[1];
-    a.s_row0 = gp.s_row0;
     a.hidden_act = pol->spec.hidden_act;
     a.normalize = pol->spec.normalize;
     a.head = pol->spec.head;
@@ -4880,44 +5069,7 @@ int chub_policy_grad_device(chub_policy_grad *g, const chub_policy_grad_in *in, 
     a.W = pol->pa.W;
     a.G = pol->G;
     a.loss = in->loss;
-    a.backward = backward ? 1 : 0;
-    a.n_pairs = gp.n_pairs;
-    a.part_floats = gp.part_floats;
-    a.bias_floats = gp.bias_floats;
-    for (int l = 0; l < nl; l++) {
-        GradLayer &L = a.layer[l];
-        L.w = pol->d_w[l];
-        L.b = pol->d_b[l];
-        L.wrm = l ? g->d_wrm + gp.wrm_off[l] : nullptr;
-        L.k_pad = pol->pa.layer[l].k_pad;
-        L.in = gp.in[l];
-        L.out = pol->spec.width[l];
-        L.ot = gp.ot[l];
-        L.it = gp.it[l];
-        L.h_row0 = gp.h_row0[l];
-        L.pair0 = gp.pair0[l];
-        L.bias0 = gp.bias0[l];
-        m.gW[l] = out->d_gW[l];
-        m.gb[l] = out->d_gb[l];
-        m.in[l] = gp.in[l];
-        m.out[l] = pol->spec.width[l];
-        m.it[l] = gp.it[l];
-        m.pair0[l] = gp.pair0[l];
-        m.bias0[l] = gp.bias0[l];
-        m.param0[l] = gp.param0[l];
-    }
-    m.param0[nl] = gp.param0[nl];
-    m.part = g->d_part;
-    m.part64 = g->d_part64;
-    m.glog_std = out->d_glog_std;
-    m.stats = out->d_stats;
-    m.R = in->R;
-    m.n_layers = nl;
-    m.blocks = grad_blocks(gp, in->R);
-    m.part_floats = gp.part_floats;
-    m.bias_base = gp.n_pairs * 1024;
-    m.G = pol->G;
-    m.backward = a.backward;
+    a.backward = m.backward;
     launch_policy_grad(a, m, m.blocks, gp.lds_rows, gp.in_registers != 0, (hipStream_t) stream);
     HIP_TRY(hipGetLastError());
     return CHUB_OK;
@@ -4931,19 +5083,10 @@ static_assert((int) CHUB_VLOSS_COUNT == VLOSS_COUNT && (int) CHUB_VLOSS_CLIPPED 
 constexpr int kCriticMaxF = 512;  // the limit of chub_moments
 
 struct chub_critic {
-    chub_env *env;
+    MlpNet net;
     chub_critic_spec spec;
     int64_t max_rows;
-    GradPlan gp;
-    int32_t max_blocks;
-    int32_t in_dim[kPolicyMaxLayers], k_pad[kPolicyMaxLayers];
-    float *d_w[kPolicyMaxLayers], *d_b[kPolicyMaxLayers];  // the layers in the kernel's layout (never move)
-    float *d_norm;                          // mean [F] | inv_std [F]
-    float *d_stage;                         // the host form of set_weights: W | b of the largest layer, in the trainer's layout
-    float *d_wrm, *d_part;                  // the row-major copies of layers 1.., the workgroups' f32 partials
-    double *d_part64;
-    std::vector<void *> allocs;
-    std::vector<chub_adam *> adams;         // made for this critic (chub_adam_create_critic): destroyed before it
+    GradWorkspace ws;
 };
 
 static int critic_check_spec(const chub_critic_spec *sp) {
@@ -4958,17 +5101,10 @@ static int critic_check_spec(const chub_critic_spec *sp) {
     return CHUB_OK;
 }
 
-// the gradient's plan for the critic's layers: grad_plan reads n_layers, width and F only
+// the gradient's plan for the critic's layers
 static int critic_plan(const chub_critic_spec *sp, GradPlan &gp) {
     if (const int rc = critic_check_spec(sp)) return rc;
-    chub_policy_spec ps;
-    memset(&ps, 0, sizeof ps);
-    ps.n_layers = sp->n_layers;
-    for (int l = 0; l < sp->n_layers; l++) ps.width[l] = sp->width[l];
-    PolicyShape shape;
-    memset(&shape, 0, sizeof shape);
-    shape.F = sp->F;
-    if (grad_plan(&ps, shape, gp) != CHUB_OK)  // (its only refusal is the fit rule; said here in the critic's words)
+    if (grad_plan(sp->n_layers, sp->width, sp->F, gp) != CHUB_OK)  // (its only refusal is the fit rule; said here in the critic's words)
         return fail(CHUB_ERR_UNSUPPORTED, "the critic keeps its rows, every hidden layer and two delta images in LDS: " + std::to_string(gp.lds_rows) +
                                               " rows of " + std::to_string(kGradRowStride) + " floats, at most " +
                                               std::to_string(kGradLdsBytes / (kGradRowStride * (int) sizeof(float))) + " (160 KiB)");
@@ -4978,35 +5114,11 @@ static int critic_plan(const chub_critic_spec *sp, GradPlan &gp) {
 extern "C" {
 
 static void critic_free(chub_critic *c) {
-    chub_env *e = c->env;
-    while (!c->adams.empty()) adam_free(c->adams.back());
-    (void) hipSetDevice(e->device);
-    (void) hipDeviceSynchronize();  // (a launch still in flight reads the weights and writes the partials)
-    for (void *p : c->allocs) (void) hipFree(p);
+    chub_env *e = c->net.env;
+    net_free(c->net);  // (its synchronise also covers the partials a launch in flight writes)
+    c->ws.allocs.free_all();
     e->critics.erase(std::remove(e->critics.begin(), e->critics.end(), c), e->critics.end());
     delete c;
-}
-
-static int critic_alloc_bytes(chub_critic *c, void **p, size_t bytes) {
-    void *d = nullptr;
-    if (!bytes) bytes = 4;
-    if (hipMalloc(&d, bytes) != hipSuccess) return fail(CHUB_ERR_HIP, "chub_critic_create: out of device memory");
-    c->allocs.push_back(d);
-    if (hipMemset(d, 0, bytes) != hipSuccess) return fail(CHUB_ERR_HIP, "chub_critic_create: hipMemset failed");
-    *p = d;
-    return CHUB_OK;
-}
-#define critic_alloc(c, p, count) critic_alloc_bytes((c), (void **) (p), (size_t) (count) * sizeof(**(p)))
-
-static int critic_upload(chub_critic *c, int l, const float *W, const float *b) {
-    const size_t nw = (size_t) c->spec.width[l] * (size_t) c->in_dim[l], nb = (size_t) c->spec.width[l];
-    HIP_TRY(hipDeviceSynchronize());  // (the staging buffer is one; nothing may still be reading the layer either)
-    HIP_TRY(hipMemcpy(c->d_stage, W, nw * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_stage + nw, b, nb * sizeof(float), hipMemcpyHostToDevice));
-    launch_policy_relayout(c->d_stage, c->d_stage + nw, c->d_w[l], c->d_b[l], c->spec.width[l], c->in_dim[l], c->k_pad[l], c->gp.ot[l], nullptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    return CHUB_OK;
 }
 
 int chub_critic_plan(const chub_critic_spec *spec, int64_t R, chub_critic_plan_out *out) {
@@ -5014,13 +5126,7 @@ int chub_critic_plan(const chub_critic_spec *spec, int64_t R, chub_critic_plan_o
     if (R < 1) return fail(CHUB_ERR_ARG, "chub_critic_plan: R is at least 1");
     GradPlan gp;
     if (const int rc = critic_plan(spec, gp)) return rc;
-    out->n_params = gp.n_params;
-    out->workgroups = grad_blocks(gp, R);
-    out->lds_rows = gp.lds_rows;
-    out->lds_bytes = gp.lds_rows * kGradRowStride * (int32_t) sizeof(float);
-    out->in_registers = gp.in_registers;
-    out->workspace_bytes = (int64_t) ((size_t) gp.wrm_floats * sizeof(float) +
-                                      (size_t) out->workgroups * ((size_t) gp.part_floats * sizeof(float) + kCriticStats * sizeof(double)));
+    grad_plan_out(gp, R, kCriticStats, out);
     return CHUB_OK;
 }
 
@@ -5042,33 +5148,26 @@ int chub_critic_create(chub_env *e, const chub_critic_spec *spec, const float *c
         return fail(CHUB_ERR_HIP, "chub_critic_create: the critic kernel's LDS limit could not be raised");
     }
     chub_critic *c = new chub_critic();
-    c->env = e;
+    MlpNet &net = c->net;
+    net.env = e;
+    net.noun = "critic";
+    net.row_noun = "rows";
+    net.alloc_who = "chub_critic_create";
+    net.n_layers = spec->n_layers;
+    net.F = spec->F;
+    net.normalize = spec->normalize != 0;
+    for (int l = 0; l < spec->n_layers; l++) {
+        net.in[l] = gp.in[l];
+        net.out[l] = spec->width[l];
+        net.tiles[l] = gp.ot[l];
+    }
     c->spec = *spec;
     c->max_rows = max_rows;
-    c->gp = gp;
-    c->max_blocks = grad_blocks(gp, max_rows);
     e->critics.push_back(c);
-    int rc = CHUB_OK;
-    size_t stage = 0;
-    for (int l = 0; l < spec->n_layers && !rc; l++) {
-        const int in = gp.in[l], width = spec->width[l];
-        c->in_dim[l] = in;
-        c->k_pad[l] = (in + 1) & ~1;
-        stage = std::max(stage, (size_t) width * (size_t) in + (size_t) width);
-        rc = critic_alloc(c, &c->d_w[l], (size_t) gp.ot[l] * (size_t) c->k_pad[l] * kPolicyOutTile);
-        if (!rc) rc = critic_alloc(c, &c->d_b[l], (size_t) gp.ot[l] * kPolicyOutTile);
-    }
-    if (!rc) rc = critic_alloc(c, &c->d_stage, stage);
-    if (!rc) rc = critic_alloc(c, &c->d_norm, 2 * (size_t) spec->F);
-    if (!rc) rc = critic_alloc(c, &c->d_wrm, (size_t) std::max<int64_t>(gp.wrm_floats, 1));
-    if (!rc) rc = critic_alloc(c, &c->d_part, (size_t) c->max_blocks * (size_t) gp.part_floats);
-    if (!rc) rc = critic_alloc(c, &c->d_part64, (size_t) c->max_blocks * kCriticStats);
-    if (!rc && spec->normalize) {
-        if (hipMemcpy(c->d_norm, mean, (size_t) spec->F * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(c->d_norm + spec->F, inv_std, (size_t) spec->F * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-            rc = fail(CHUB_ERR_HIP, "chub_critic_create: mean / inv_std could not be copied to the device");
-    }
-    for (int l = 0; l < spec->n_layers && !rc; l++) rc = critic_upload(c, l, W[l], b[l]);
+    int rc = net_alloc_layers(net);
+    if (!rc)
+        if (const char *what = grad_workspace_create(c->ws, gp, max_rows, kCriticStats)) rc = fail(CHUB_ERR_HIP, std::string(net.alloc_who) + ": " + what);
+    if (!rc) rc = net_load(net, "chub_critic_create", W, b, mean, inv_std);
     if (rc) {
         const std::string msg = g_err;
         critic_free(c);
@@ -5081,7 +5180,7 @@ int chub_critic_create(chub_env *e, const chub_critic_spec *spec, const float *c
 
 int chub_critic_destroy(chub_critic *c) {
     if (!c) return CHUB_OK;
-    if (c->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_critic_destroy between chub_graph_begin and chub_graph_end (it synchronises and frees)");
+    if (c->net.env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_critic_destroy between chub_graph_begin and chub_graph_end (it synchronises and frees)");
     critic_free(c);
     (void) hipGetLastError();
     return CHUB_OK;
@@ -5089,120 +5188,59 @@ int chub_critic_destroy(chub_critic *c) {
 
 int chub_critic_set_weights(chub_critic *c, int32_t layer, const float *W, const float *b) {
     if (!c || !W || !b) return fail(CHUB_ERR_ARG, "null argument");
-    if (layer < 0 || layer >= c->spec.n_layers) return fail(CHUB_ERR_ARG, "layer: 0 .. n_layers - 1");
-    if (c->env->capturing)
-        return fail(CHUB_ERR_UNSUPPORTED, "chub_critic_set_weights between chub_graph_begin and chub_graph_end (it copies and synchronises: use "
-                                          "chub_critic_set_weights_device)");
-    HIP_TRY(hipSetDevice(c->env->device));
-    (void) hipGetLastError();
-    return critic_upload(c, layer, W, b);
+    return net_set_weights(c->net, "chub_critic_set_weights", layer, W, b);
 }
 
 int chub_critic_set_weights_device(chub_critic *c, int32_t layer, const float *d_W, const float *d_b, void *stream) {
     if (!c || !d_W || !d_b) return fail(CHUB_ERR_ARG, "null argument");
-    if (layer < 0 || layer >= c->spec.n_layers) return fail(CHUB_ERR_ARG, "layer: 0 .. n_layers - 1");
-    HIP_TRY(hipSetDevice(c->env->device));
-    (void) hipGetLastError();
-    launch_policy_relayout(d_W, d_b, c->d_w[layer], c->d_b[layer], c->spec.width[layer], c->in_dim[layer], c->k_pad[layer], c->gp.ot[layer],
-                           (hipStream_t) stream);
-    HIP_TRY(hipGetLastError());
-    return CHUB_OK;
+    return net_set_weights_device(c->net, layer, d_W, d_b, stream);
 }
 
-static int critic_needs_normalizer(const chub_critic *c, const char *who) {
-    if (!c->spec.normalize) return fail(CHUB_ERR_ARG, std::string(who) + ": the critic was created with normalize = 0 (its kernel reads no normaliser)");
-    return CHUB_OK;
+int chub_critic_get_weights(chub_critic *c, int32_t layer, float *W, float *b) {
+    if (!c || !W || !b) return fail(CHUB_ERR_ARG, "null argument");
+    return net_get_weights(c->net, "chub_critic_get_weights", layer, W, b);
+}
+
+int chub_critic_get_weights_device(chub_critic *c, int32_t layer, float *d_W, float *d_b, void *stream) {
+    if (!c || !d_W || !d_b) return fail(CHUB_ERR_ARG, "null argument");
+    return net_get_weights_device(c->net, layer, d_W, d_b, stream);
 }
 
 int chub_critic_set_normalizer(chub_critic *c, const float *mean, const float *inv_std) {
     if (!c || !mean || !inv_std) return fail(CHUB_ERR_ARG, "null argument");
-    if (const int rc = critic_needs_normalizer(c, "chub_critic_set_normalizer")) return rc;
-    if (c->env->capturing)
-        return fail(CHUB_ERR_UNSUPPORTED, "chub_critic_set_normalizer between chub_graph_begin and chub_graph_end (it copies and synchronises: use "
-                                          "chub_critic_set_normalizer_device)");
-    HIP_TRY(hipSetDevice(c->env->device));
-    (void) hipGetLastError();
-    HIP_TRY(hipDeviceSynchronize());  // (a critic launch in flight reads the buffer)
-    HIP_TRY(hipMemcpy(c->d_norm, mean, (size_t) c->spec.F * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_norm + c->spec.F, inv_std, (size_t) c->spec.F * sizeof(float), hipMemcpyHostToDevice));
-    return CHUB_OK;
+    return net_set_normalizer(c->net, "chub_critic_set_normalizer", mean, inv_std);
 }
 
 int chub_critic_set_normalizer_device(chub_critic *c, const float *d_mean, const float *d_inv_std, void *stream) {
     if (!c || !d_mean || !d_inv_std) return fail(CHUB_ERR_ARG, "null argument");
-    if (const int rc = critic_needs_normalizer(c, "chub_critic_set_normalizer_device")) return rc;
-    HIP_TRY(hipSetDevice(c->env->device));
-    (void) hipGetLastError();
-    HIP_TRY(hipMemcpyAsync(c->d_norm, d_mean, (size_t) c->spec.F * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
-    HIP_TRY(hipMemcpyAsync(c->d_norm + c->spec.F, d_inv_std, (size_t) c->spec.F * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
-    return CHUB_OK;
+    return net_set_normalizer_device(c->net, "chub_critic_set_normalizer_device", d_mean, d_inv_std, stream);
 }
 
 int chub_critic_normalizer_from_moments_device(chub_critic *c, chub_moments *m, double eps, void *stream) {
     if (!c || !m) return fail(CHUB_ERR_ARG, "null argument");
-    if (const int rc = critic_needs_normalizer(c, "chub_critic_normalizer_from_moments_device")) return rc;
-    if (m->env != c->env) return fail(CHUB_ERR_ARG, "chub_critic_normalizer_from_moments_device: the critic and the moments were made for different handles");
-    if (m->F != c->spec.F)
-        return fail(CHUB_ERR_ARG, "chub_critic_normalizer_from_moments_device: the moments have F = " + std::to_string(m->F) + ", the critic's rows " +
-                                      std::to_string(c->spec.F));
-    if (!(eps > 0.0) || !std::isfinite(eps)) return fail(CHUB_ERR_ARG, "chub_critic_normalizer_from_moments_device: eps is finite and > 0");
-    HIP_TRY(hipSetDevice(c->env->device));
-    (void) hipGetLastError();
-    launch_normalizer_from_moments(m->d_state, c->spec.F, eps, c->d_norm, c->d_norm + c->spec.F, (hipStream_t) stream);
-    HIP_TRY(hipGetLastError());
-    return CHUB_OK;
+    return net_normalizer_from_moments(c->net, "chub_critic_normalizer_from_moments_device", m, eps, stream);
 }
 
 // what every critic call asks of its rows
 static int critic_check_rows(const chub_critic *c, const char *who, const float *d_x, int64_t ld, int64_t n_rows, const int64_t *d_rows, int64_t R) {
     if (!d_x) return fail(CHUB_ERR_ARG, "null argument");
-    if (R <= 0 || R > c->max_rows) return fail(CHUB_ERR_ARG, std::string(who) + ": R is 1 .. max_rows = " + std::to_string(c->max_rows));
-    if (n_rows < 1) return fail(CHUB_ERR_ARG, std::string(who) + ": n_rows, the rows the arrays hold, is at least 1");
-    if (!d_rows && R > n_rows) return fail(CHUB_ERR_ARG, std::string(who) + ": without d_rows the call reads rows 0 .. R - 1: R <= n_rows");
-    if (ld < c->spec.F) return fail(CHUB_ERR_ARG, "ld: at least the row's " + std::to_string(c->spec.F) + " floats");
-    return CHUB_OK;
+    return grad_check_rows(who, c->max_rows, R, n_rows, d_rows, ld, c->spec.F, "ld: at least the row's ");
 }
 
 static void critic_args(const chub_critic *c, CriticArgs &a) {
-    const GradPlan &gp = c->gp;
-    memset(&a, 0, sizeof a);
-    a.mean = c->d_norm;
-    a.inv_std = c->d_norm + c->spec.F;
-    a.part = c->d_part;
-    a.part64 = c->d_part64;
+    grad_args(c->net, c->ws, a);
+    a.mean = c->net.d_norm;
+    a.inv_std = c->net.d_norm + c->spec.F;
     a.clip = c->spec.clip;
-    a.n_layers = c->spec.n_layers;
-    a.F = c->spec.F;
-    a.x_rows = gp.x_rows;
-    a.d_row0[0] = gp.d_row0[0];
-    a.d_row0[1] = gp.d_row0[1];
-    a.s_row0 = gp.s_row0;
     a.hidden_act = c->spec.hidden_act;
     a.normalize = c->spec.normalize;
-    a.n_pairs = gp.n_pairs;
-    a.part_floats = gp.part_floats;
-    a.bias_floats = gp.bias_floats;
-    for (int l = 0; l < c->spec.n_layers; l++) {
-        GradLayer &L = a.layer[l];
-        L.w = c->d_w[l];
-        L.b = c->d_b[l];
-        L.wrm = l ? c->d_wrm + gp.wrm_off[l] : nullptr;
-        L.k_pad = c->k_pad[l];
-        L.in = gp.in[l];
-        L.out = c->spec.width[l];
-        L.ot = gp.ot[l];
-        L.it = gp.it[l];
-        L.h_row0 = gp.h_row0[l];
-        L.pair0 = gp.pair0[l];
-        L.bias0 = gp.bias0[l];
-    }
 }
 
 int chub_critic_values_device(chub_critic *c, const float *d_x, int64_t ld, int64_t n_rows, const int64_t *d_rows, int64_t R, float *d_values,
                               void *stream) {
     if (!c || !d_values) return fail(CHUB_ERR_ARG, "null argument");
     if (const int rc = critic_check_rows(c, "chub_critic_values_device", d_x, ld, n_rows, d_rows, R)) return rc;
-    HIP_TRY(hipSetDevice(c->env->device));
+    HIP_TRY(hipSetDevice(c->net.env->device));
     (void) hipGetLastError();
     CriticArgs a;
     critic_args(c, a);
@@ -5214,7 +5252,7 @@ int chub_critic_values_device(chub_critic *c, const float *d_x, int64_t ld, int6
     a.values = d_values;
     // (no partials to merge: as many workgroups as the tiles give, up to what 256 CUs hold of the 13-64-64-1 form, four each)
     const int64_t tiles = (R + 31) / 32;
-    launch_critic_values(a, (int) std::min<int64_t>((tiles + 7) & ~(int64_t) 7, kCriticValueBlocks), c->gp.lds_rows, (hipStream_t) stream);
+    launch_critic_values(a, (int) std::min<int64_t>((tiles + 7) & ~(int64_t) 7, kCriticValueBlocks), c->ws.gp.lds_rows, (hipStream_t) stream);
     HIP_TRY(hipGetLastError());
     return CHUB_OK;
 }
@@ -5228,16 +5266,13 @@ int chub_critic_grad_device(chub_critic *c, const chub_critic_grad_in *in, const
         if (!(in->clip_eps > 0.0f) || !std::isfinite(in->clip_eps)) return fail(CHUB_ERR_ARG, "clip_eps: finite and > 0 under CHUB_VLOSS_CLIPPED");
         if (!in->d_v_old) return fail(CHUB_ERR_ARG, "null argument");
     }
-    HIP_TRY(hipSetDevice(c->env->device));
+    HIP_TRY(hipSetDevice(c->net.env->device));
     (void) hipGetLastError();
-    const GradPlan &gp = c->gp;
-    const int nl = c->spec.n_layers;
+    const GradPlan &gp = c->ws.gp;
     CriticArgs a;
     critic_args(c, a);
     CriticMergeArgs m;
-    memset(&m, 0, sizeof m);
-    bool backward = false;
-    for (int l = 0; l < nl; l++) backward |= out->d_gW[l] != nullptr || out->d_gb[l] != nullptr;
+    grad_merge_args(c->net, c->ws, in->R, out, m);
     a.R = in->R;
     a.rows_total = in->n_rows;
     a.rows = in->d_rows;
@@ -5249,64 +5284,17 @@ int chub_critic_grad_device(chub_critic *c, const chub_critic_grad_in *in, const
     a.clip_eps = in->clip_eps;
     a.loss = in->loss;
     a.stats = 1;
-    a.backward = backward ? 1 : 0;
-    for (int l = 0; l < nl; l++) {
-        m.gW[l] = out->d_gW[l];
-        m.gb[l] = out->d_gb[l];
-        m.in[l] = gp.in[l];
-        m.it[l] = gp.it[l];
-        m.pair0[l] = gp.pair0[l];
-        m.bias0[l] = gp.bias0[l];
-        m.param0[l] = gp.param0[l];
-    }
-    m.param0[nl] = gp.param0[nl];
-    m.part = c->d_part;
-    m.part64 = c->d_part64;
-    m.stats = out->d_stats;
-    m.R = in->R;
-    m.n_layers = nl;
-    m.blocks = grad_blocks(gp, in->R);
-    m.part_floats = gp.part_floats;
-    m.bias_base = gp.n_pairs * 1024;
-    m.backward = a.backward;
+    a.backward = m.backward;
     launch_critic_grad(a, m, m.blocks, gp.lds_rows, gp.in_registers != 0, (hipStream_t) stream);
     HIP_TRY(hipGetLastError());
     return CHUB_OK;
 }
 
-// ---- reading weights back (include/chub.h): the kernels' layout -> the trainer's, the way a population's members go
-int chub_policy_get_weights_device(chub_policy *pol, int32_t layer, float *d_W, float *d_b, void *stream) {
-    if (!pol || !d_W || !d_b) return fail(CHUB_ERR_ARG, "null argument");
-    if (layer < 0 || layer >= pol->spec.n_layers) return fail(CHUB_ERR_ARG, "layer: 0 .. n_layers - 1");
-    HIP_TRY(hipSetDevice(pol->env->device));
-    (void) hipGetLastError();
-    launch_policy_unlayout(pol->d_w[layer], pol->d_b[layer], d_W, d_b, pol->spec.width[layer], pol->in_dim[layer], pol->pa.layer[layer].k_pad,
-                           (hipStream_t) stream);
-    HIP_TRY(hipGetLastError());
-    return CHUB_OK;
-}
-
-int chub_policy_get_weights(chub_policy *pol, int32_t layer, float *W, float *b) {
-    if (!pol || !W || !b) return fail(CHUB_ERR_ARG, "null argument");
-    if (layer < 0 || layer >= pol->spec.n_layers) return fail(CHUB_ERR_ARG, "layer: 0 .. n_layers - 1");
-    if (pol->env->capturing)
-        return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_get_weights between chub_graph_begin and chub_graph_end (it copies and synchronises: use "
-                                          "chub_policy_get_weights_device)");
-    const size_t nw = (size_t) pol->spec.width[layer] * (size_t) pol->in_dim[layer], nb = (size_t) pol->spec.width[layer];
-    HIP_TRY(hipSetDevice(pol->env->device));
-    (void) hipGetLastError();
-    HIP_TRY(hipDeviceSynchronize());  // (the staging buffer is one)
-    if (const int rc = chub_policy_get_weights_device(pol, layer, pol->d_stage, pol->d_stage + nw, nullptr)) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(W, pol->d_stage, nw * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(b, pol->d_stage + nw, nb * sizeof(float), hipMemcpyDeviceToHost));
-    return CHUB_OK;
-}
-
+// ---- reading log_std back (include/chub.h)
 int chub_policy_get_log_std_device(chub_policy *pol, float *d_log_std, void *stream) {
     if (!pol || !d_log_std) return fail(CHUB_ERR_ARG, "null argument");
     if (!pol->explore) return fail(CHUB_ERR_ARG, "chub_policy_set_exploration first (it makes the policy's log_std buffer)");
-    HIP_TRY(hipSetDevice(pol->env->device));
+    HIP_TRY(hipSetDevice(pol->net.env->device));
     (void) hipGetLastError();
     HIP_TRY(hipMemcpyAsync(d_log_std, pol->d_log_std, (size_t) pol->G * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
     return CHUB_OK;
@@ -5315,40 +5303,13 @@ int chub_policy_get_log_std_device(chub_policy *pol, float *d_log_std, void *str
 int chub_policy_get_log_std(chub_policy *pol, float *log_std) {
     if (!pol || !log_std) return fail(CHUB_ERR_ARG, "null argument");
     if (!pol->explore) return fail(CHUB_ERR_ARG, "chub_policy_set_exploration first (it makes the policy's log_std buffer)");
-    if (pol->env->capturing)
+    if (pol->net.env->capturing)
         return fail(CHUB_ERR_UNSUPPORTED, "chub_policy_get_log_std between chub_graph_begin and chub_graph_end (it copies and synchronises: use "
                                           "chub_policy_get_log_std_device)");
-    HIP_TRY(hipSetDevice(pol->env->device));
+    HIP_TRY(hipSetDevice(pol->net.env->device));
     (void) hipGetLastError();
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(log_std, pol->d_log_std, (size_t) pol->G * sizeof(float), hipMemcpyDeviceToHost));
-    return CHUB_OK;
-}
-
-int chub_critic_get_weights_device(chub_critic *c, int32_t layer, float *d_W, float *d_b, void *stream) {
-    if (!c || !d_W || !d_b) return fail(CHUB_ERR_ARG, "null argument");
-    if (layer < 0 || layer >= c->spec.n_layers) return fail(CHUB_ERR_ARG, "layer: 0 .. n_layers - 1");
-    HIP_TRY(hipSetDevice(c->env->device));
-    (void) hipGetLastError();
-    launch_policy_unlayout(c->d_w[layer], c->d_b[layer], d_W, d_b, c->spec.width[layer], c->in_dim[layer], c->k_pad[layer], (hipStream_t) stream);
-    HIP_TRY(hipGetLastError());
-    return CHUB_OK;
-}
-
-int chub_critic_get_weights(chub_critic *c, int32_t layer, float *W, float *b) {
-    if (!c || !W || !b) return fail(CHUB_ERR_ARG, "null argument");
-    if (layer < 0 || layer >= c->spec.n_layers) return fail(CHUB_ERR_ARG, "layer: 0 .. n_layers - 1");
-    if (c->env->capturing)
-        return fail(CHUB_ERR_UNSUPPORTED, "chub_critic_get_weights between chub_graph_begin and chub_graph_end (it copies and synchronises: use "
-                                          "chub_critic_get_weights_device)");
-    const size_t nw = (size_t) c->spec.width[layer] * (size_t) c->in_dim[layer], nb = (size_t) c->spec.width[layer];
-    HIP_TRY(hipSetDevice(c->env->device));
-    (void) hipGetLastError();
-    HIP_TRY(hipDeviceSynchronize());  // (the staging buffer is one)
-    if (const int rc = chub_critic_get_weights_device(c, layer, c->d_stage, c->d_stage + nw, nullptr)) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(W, c->d_stage, nw * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(b, c->d_stage + nw, nb * sizeof(float), hipMemcpyDeviceToHost));
     return CHUB_OK;
 }
 
@@ -5376,15 +5337,23 @@ static void adam_plan(const int32_t *out_dims, const int32_t *in_dims, int n_lay
 constexpr size_t kAdamBlobHeader = 32;  // int64 t, double p1, double p2, int64 n
 
 struct chub_adam {
-    chub_env *env;
-    chub_policy *pol;   // one of the two
-    chub_critic *critic;
+    MlpNet *net;        // the target's: a policy's or a critic's
     AdamPlan ap;
     AdamArgs args;      // everything but the gradient pointers and the stats
     int32_t n_layers, G;
     float *d_m, *d_v, *d_g;
     double *d_scalars, *d_partials;
+    DeviceAllocs allocs;
 };
+
+static void adam_free(chub_adam *a) {
+    (void) hipSetDevice(a->net->env->device);
+    (void) hipDeviceSynchronize();  // (a launch still in flight reads and writes all of these)
+    a->allocs.free_all();
+    std::vector<chub_adam *> &list = a->net->adams;
+    list.erase(std::remove(list.begin(), list.end(), a), list.end());
+    delete a;
+}
 
 static int adam_check_hyper(const chub_adam_hyper *h) {
     const double nonneg[4] = {h->lr, h->eps, h->weight_decay, h->max_grad_norm};
@@ -5396,19 +5365,6 @@ static int adam_check_hyper(const chub_adam_hyper *h) {
 }
 
 extern "C" {
-
-static void adam_free(chub_adam *a) {
-    (void) hipSetDevice(a->env->device);
-    (void) hipDeviceSynchronize();  // (a launch still in flight reads and writes all of these)
-    if (a->d_m) (void) hipFree(a->d_m);
-    if (a->d_v) (void) hipFree(a->d_v);
-    if (a->d_g) (void) hipFree(a->d_g);
-    if (a->d_scalars) (void) hipFree(a->d_scalars);
-    if (a->d_partials) (void) hipFree(a->d_partials);
-    std::vector<chub_adam *> &list = a->pol ? a->pol->adams : a->critic->adams;
-    list.erase(std::remove(list.begin(), list.end(), a), list.end());
-    delete a;
-}
 
 int chub_adam_plan(const int32_t *out_dims, const int32_t *in_dims, int32_t n_layers, int32_t G, chub_adam_plan_out *out) {
     if (!out_dims || !in_dims || !out) return fail(CHUB_ERR_ARG, "null argument");
@@ -5426,25 +5382,38 @@ int chub_adam_plan(const int32_t *out_dims, const int32_t *in_dims, int32_t n_la
     return CHUB_OK;
 }
 
-// the object for a target whose layers (live device pointers, dims) stand in a->args already
-static int adam_create(chub_adam *a, const chub_adam_hyper *h, std::vector<chub_adam *> &list, chub_adam **out) {
+// the object for a net's live layers and, with G > 0, the policy's log_std [G]
+static int adam_create_for(MlpNet &net, const char *who, int G, float *d_log_std, const chub_adam_hyper *h, chub_adam **out) {
+    if (const int rc = adam_check_hyper(h)) return rc;
+    if (net.env->capturing)
+        return fail(CHUB_ERR_UNSUPPORTED, std::string(who) + " between chub_graph_begin and chub_graph_end (it allocates and synchronises)");
+    HIP_TRY(hipSetDevice(net.env->device));
+    (void) hipGetLastError();
+    chub_adam *a = new chub_adam();
+    a->net = &net;
+    a->n_layers = net.n_layers;
+    a->G = G;
     AdamArgs &g = a->args;
+    for (int l = 0; l < net.n_layers; l++) {
+        g.w[l] = net.d_w[l];
+        g.b[l] = net.d_b[l];
+        g.in[l] = net.in[l];
+        g.out[l] = net.out[l];
+        g.k_pad[l] = net.k_pad[l];
+    }
+    g.log_std = d_log_std;
     adam_plan(g.out, g.in, a->n_layers, a->G, a->ap);
     const AdamPlan &ap = a->ap;
     for (int l = 0; l <= a->n_layers; l++) g.param0[l] = ap.param0[l];
     g.n = ap.n;
     g.n_layers = a->n_layers;
     g.chunks = ap.chunks;
-    a->d_m = a->d_v = a->d_g = nullptr;
-    a->d_scalars = a->d_partials = nullptr;
-    list.push_back(a);
-    const size_t nf = (size_t) ap.n * sizeof(float), ns = (size_t) ADAM_SCALARS * sizeof(double), np = (size_t) ap.chunks * sizeof(double);
+    net.adams.push_back(a);
+    const size_t n = (size_t) ap.n;
     double sc[ADAM_SCALARS] = {h->lr, h->beta1, h->beta2, h->eps, h->weight_decay, h->max_grad_norm, 0.0, 1.0, 1.0, 0.0, 1.0, 1.0};  // (t = 0 is all zero bits)
-    const bool ok = hipMalloc((void **) &a->d_m, nf) == hipSuccess && hipMalloc((void **) &a->d_v, nf) == hipSuccess &&
-                    hipMalloc((void **) &a->d_g, nf) == hipSuccess && hipMalloc((void **) &a->d_scalars, ns) == hipSuccess &&
-                    hipMalloc((void **) &a->d_partials, np) == hipSuccess && hipMemset(a->d_m, 0, nf) == hipSuccess &&
-                    hipMemset(a->d_v, 0, nf) == hipSuccess && hipMemset(a->d_g, 0, nf) == hipSuccess && hipMemset(a->d_partials, 0, np) == hipSuccess &&
-                    hipMemcpy(a->d_scalars, sc, ns, hipMemcpyHostToDevice) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    const bool ok = !a->allocs.zeroed(&a->d_m, n) && !a->allocs.zeroed(&a->d_v, n) && !a->allocs.zeroed(&a->d_g, n) &&
+                    !a->allocs.zeroed(&a->d_scalars, (size_t) ADAM_SCALARS) && !a->allocs.zeroed(&a->d_partials, (size_t) ap.chunks) &&
+                    hipMemcpy(a->d_scalars, sc, sizeof sc, hipMemcpyHostToDevice) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
     if (!ok) {
         adam_free(a);
         (void) hipGetLastError();
@@ -5461,57 +5430,18 @@ static int adam_create(chub_adam *a, const chub_adam_hyper *h, std::vector<chub_
 int chub_adam_create_policy(chub_policy *pol, const chub_adam_hyper *h, chub_adam **out) {
     if (!pol || !h || !out) return fail(CHUB_ERR_ARG, "null argument");
     *out = nullptr;
-    if (const int rc = adam_check_hyper(h)) return rc;
-    chub_env *e = pol->env;
-    if (e->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_adam_create_policy between chub_graph_begin and chub_graph_end (it allocates and synchronises)");
-    HIP_TRY(hipSetDevice(e->device));
-    (void) hipGetLastError();
-    chub_adam *a = new chub_adam();
-    memset(&a->args, 0, sizeof a->args);
-    a->env = e;
-    a->pol = pol;
-    a->critic = nullptr;
-    a->n_layers = pol->spec.n_layers;
-    a->G = pol->explore ? pol->G : 0;
-    for (int l = 0; l < a->n_layers; l++) {
-        a->args.w[l] = pol->d_w[l];
-        a->args.b[l] = pol->d_b[l];
-        a->args.in[l] = pol->in_dim[l];
-        a->args.out[l] = pol->spec.width[l];
-        a->args.k_pad[l] = pol->pa.layer[l].k_pad;
-    }
-    a->args.log_std = pol->explore ? pol->d_log_std : nullptr;
-    return adam_create(a, h, pol->adams, out);
+    return adam_create_for(pol->net, "chub_adam_create_policy", pol->explore ? pol->G : 0, pol->explore ? pol->d_log_std : nullptr, h, out);
 }
 
 int chub_adam_create_critic(chub_critic *c, const chub_adam_hyper *h, chub_adam **out) {
     if (!c || !h || !out) return fail(CHUB_ERR_ARG, "null argument");
     *out = nullptr;
-    if (const int rc = adam_check_hyper(h)) return rc;
-    chub_env *e = c->env;
-    if (e->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_adam_create_critic between chub_graph_begin and chub_graph_end (it allocates and synchronises)");
-    HIP_TRY(hipSetDevice(e->device));
-    (void) hipGetLastError();
-    chub_adam *a = new chub_adam();
-    memset(&a->args, 0, sizeof a->args);
-    a->env = e;
-    a->pol = nullptr;
-    a->critic = c;
-    a->n_layers = c->spec.n_layers;
-    a->G = 0;
-    for (int l = 0; l < a->n_layers; l++) {
-        a->args.w[l] = c->d_w[l];
-        a->args.b[l] = c->d_b[l];
-        a->args.in[l] = c->in_dim[l];
-        a->args.out[l] = c->spec.width[l];
-        a->args.k_pad[l] = c->k_pad[l];
-    }
-    return adam_create(a, h, c->adams, out);
+    return adam_create_for(c->net, "chub_adam_create_critic", 0, nullptr, h, out);
 }
 
 int chub_adam_destroy(chub_adam *a) {
     if (!a) return CHUB_OK;
-    if (a->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_adam_destroy between chub_graph_begin and chub_graph_end (it synchronises and frees)");
+    if (a->net->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_adam_destroy between chub_graph_begin and chub_graph_end (it synchronises and frees)");
     adam_free(a);
     (void) hipGetLastError();
     return CHUB_OK;
@@ -5520,9 +5450,9 @@ int chub_adam_destroy(chub_adam *a) {
 int chub_adam_set_hyper(chub_adam *a, const chub_adam_hyper *h) {
     if (!a || !h) return fail(CHUB_ERR_ARG, "null argument");
     if (const int rc = adam_check_hyper(h)) return rc;
-    if (a->env->capturing)
+    if (a->net->env->capturing)
         return fail(CHUB_ERR_UNSUPPORTED, "chub_adam_set_hyper between chub_graph_begin and chub_graph_end (it copies and synchronises: use chub_adam_set_lr_device)");
-    HIP_TRY(hipSetDevice(a->env->device));
+    HIP_TRY(hipSetDevice(a->net->env->device));
     (void) hipGetLastError();
     HIP_TRY(hipDeviceSynchronize());
     const double sc[6] = {h->lr, h->beta1, h->beta2, h->eps, h->weight_decay, h->max_grad_norm};
@@ -5532,7 +5462,7 @@ int chub_adam_set_hyper(chub_adam *a, const chub_adam_hyper *h) {
 
 int chub_adam_set_lr_device(chub_adam *a, const double *d_lr, void *stream) {
     if (!a || !d_lr) return fail(CHUB_ERR_ARG, "null argument");
-    HIP_TRY(hipSetDevice(a->env->device));
+    HIP_TRY(hipSetDevice(a->net->env->device));
     (void) hipGetLastError();
     HIP_TRY(hipMemcpyAsync(a->d_scalars + ADAM_LR, d_lr, sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t) stream));
     return CHUB_OK;
@@ -5561,7 +5491,7 @@ int chub_adam_step_device(chub_adam *a, const float *const *d_gW, const float *c
         if (!d_gW[l] || !d_gb[l]) return fail(CHUB_ERR_ARG, "null argument: d_gW[" + std::to_string(l) + "] / d_gb[" + std::to_string(l) + "]");
     if (a->G && !d_glog_std) return fail(CHUB_ERR_ARG, "null argument: d_glog_std (the parameter vector ends with the policy's log_std)");
     if (!a->G && d_glog_std) return fail(CHUB_ERR_ARG, "d_glog_std: the parameter vector has no log_std (a critic, or a policy without chub_policy_set_exploration at create)");
-    HIP_TRY(hipSetDevice(a->env->device));
+    HIP_TRY(hipSetDevice(a->net->env->device));
     (void) hipGetLastError();
     AdamArgs g = a->args;
     for (int l = 0; l < a->n_layers; l++) {
@@ -5577,7 +5507,7 @@ int chub_adam_step_device(chub_adam *a, const float *const *d_gW, const float *c
 
 int chub_adam_reset_device(chub_adam *a, void *stream) {
     if (!a) return fail(CHUB_ERR_ARG, "null argument");
-    HIP_TRY(hipSetDevice(a->env->device));
+    HIP_TRY(hipSetDevice(a->net->env->device));
     (void) hipGetLastError();
     launch_adam_reset(a->d_m, a->d_v, a->ap.n, a->d_scalars, (hipStream_t) stream);
     HIP_TRY(hipGetLastError());
@@ -5592,8 +5522,8 @@ int chub_adam_state_size(chub_adam *a, int64_t *bytes) {
 
 int chub_adam_get_state(chub_adam *a, void *blob) {
     if (!a || !blob) return fail(CHUB_ERR_ARG, "null argument");
-    if (a->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_adam_get_state between chub_graph_begin and chub_graph_end (it copies and synchronises)");
-    HIP_TRY(hipSetDevice(a->env->device));
+    if (a->net->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_adam_get_state between chub_graph_begin and chub_graph_end (it copies and synchronises)");
+    HIP_TRY(hipSetDevice(a->net->env->device));
     (void) hipGetLastError();
     HIP_TRY(hipDeviceSynchronize());
     char *p = static_cast<char *>(blob);
@@ -5613,8 +5543,8 @@ int chub_adam_set_state(chub_adam *a, const void *blob) {
     memcpy(&n, p + 24, 8);
     if (n != a->ap.n)
         return fail(CHUB_ERR_ARG, "chub_adam_set_state: the blob holds " + std::to_string(n) + " parameters, this optimiser " + std::to_string(a->ap.n));
-    if (a->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_adam_set_state between chub_graph_begin and chub_graph_end (it copies and synchronises)");
-    HIP_TRY(hipSetDevice(a->env->device));
+    if (a->net->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_adam_set_state between chub_graph_begin and chub_graph_end (it copies and synchronises)");
+    HIP_TRY(hipSetDevice(a->net->env->device));
     (void) hipGetLastError();
     HIP_TRY(hipDeviceSynchronize());
     const size_t nf = (size_t) a->ap.n * sizeof(float);

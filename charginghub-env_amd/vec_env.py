@@ -104,11 +104,79 @@ def summary_dict(raw):
     return out
 
 
-class DevicePolicy(object):
+class _DeviceNet(object):
+    """What DevicePolicy and DeviceCritic share, as chub_policy and chub_critic share MlpNet in csrc/chub_runtime.cpp: one net's weight and
+    normaliser calls.  A subclass names the C prefix (`_c_name`: the calls are chub_<_c_name>_*), the attribute that holds its handle
+    (`_h_name`) and what its messages call a row (`_row`)."""
+    _c_name = _h_name = _row = None
+
+    def _net(self, call, *args):
+        check(getattr(self._lib, "chub_%s_%s" % (self._c_name, call))(getattr(self, self._h_name), *args))
+
+    def set_weights(self, layer, W, b):
+        """new weights of one layer from host arrays, W [out, in] (the nn.Linear layout) and b [out]; synchronises"""
+        W = np.ascontiguousarray(W, dtype=np.float32)
+        b = np.ascontiguousarray(b, dtype=np.float32).ravel()
+        if not 0 <= int(layer) < len(self.layer_shapes) or W.shape != self.layer_shapes[layer] or b.shape != (W.shape[0],):
+            raise ValueError("set_weights: layer %r takes W %s and b (%d,)" % (layer, self.layer_shapes[layer] if 0 <= int(layer) < len(self.layer_shapes) else "?", W.shape[0]))
+        self._net("set_weights", int(layer), _ptr(W), _ptr(b))
+
+    def set_weights_device(self, layer, d_W, d_b, stream=0):
+        """the same from device memory in the trainer's layout (e.g. a parameter's data_ptr()), as one re-layout launch on `stream`: a
+        captured graph's next replay evaluates the new weights"""
+        self._net("set_weights_device", int(layer), d_W or None, d_b or None, stream or None)
+
+    def get_weights(self, layer=None):
+        """the LIVE weights as float32 numpy arrays in the nn.Linear layout: (W, b) of one layer, or with layer=None the list over all
+        layers; synchronises"""
+        if layer is None:
+            return [self.get_weights(l) for l in range(len(self.layer_shapes))]
+        if not 0 <= int(layer) < len(self.layer_shapes):
+            raise ValueError("get_weights: layer is 0 .. %d" % (len(self.layer_shapes) - 1))
+        W = np.zeros(self.layer_shapes[layer], dtype=np.float32)
+        b = np.zeros((W.shape[0],), dtype=np.float32)
+        self._net("get_weights", int(layer), _ptr(W), _ptr(b))
+        return W, b
+
+    def get_weights_device(self, layer, d_W, d_b, stream=0):
+        """one layer into device memory in the trainer's layout (e.g. a parameter's data_ptr()), one launch on `stream`"""
+        self._net("get_weights_device", int(layer), d_W or None, d_b or None, stream or None)
+
+    def set_normalizer(self, mean, inv_std):
+        """new mean / inv_std [F] from host arrays; synchronises"""
+        mean = np.ascontiguousarray(mean, dtype=np.float32).ravel()
+        inv_std = np.ascontiguousarray(inv_std, dtype=np.float32).ravel()
+        if mean.shape != (self.n_features,) or inv_std.shape != (self.n_features,):
+            raise ValueError("mean and inv_std must have %d entries (the %s)" % (self.n_features, self._row))
+        self._net("set_normalizer", _ptr(mean), _ptr(inv_std))
+
+    def set_normalizer_device(self, d_mean, d_inv_std, stream=0):
+        """the same from device memory, [F] f32 each, as copies on `stream`: a captured graph's next replay evaluates the new normaliser"""
+        self._net("set_normalizer_device", d_mean or None, d_inv_std or None, stream or None)
+
+    def normalizer_from_moments(self, m, eps=1e-8, stream=0):
+        """mean = (float) the moments' mean, inv_std = (float) (1 / sqrt(M2 / n + eps)) (the population variance), one launch on `stream`;
+        moments that have counted nothing leave the normaliser alone.  Recordable into a graph."""
+        self._net("normalizer_from_moments_device", m._m, float(eps), stream or None)
+
+    def close(self):
+        if getattr(self, self._h_name, None) and getattr(self._env, "_h", None):
+            self._net("destroy")
+        setattr(self, self._h_name, None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DevicePolicy(_DeviceNet):
     """An MLP actor on the device (chub_policy_*, include/chub.h "an actor on the device"): made by VecChargingHub.make_policy.  The
     feature row (the observation and / or the feature calls' blocks) goes through the dense layers in ONE launch and comes out as action
     rows or pile bits + tail, which every step form takes; run_steps is the closed loop issued from C.  Exact f32: every product rounded
     once, f32 accumulation (an fmaf chain), the trainer's network up to summation order."""
+    _c_name, _h_name, _row = "policy", "_p", "feature row"
 
     def __init__(self, env, layers, inputs=("obs",), head="piles", hidden_act="tanh", squash="tanh", normalize=None):
         self._env = env
@@ -161,35 +229,6 @@ class DevicePolicy(object):
         check(self._lib.chub_sync(e._h))  # (calls in flight on any stream write the state the feature blocks read)
         check(self._lib.chub_policy_act(e._h, self._p, _ptr(o), _ptr(actions)))
         return actions
-
-    def set_weights(self, layer, W, b):
-        """new weights of one layer from host arrays, W [out, in] (the nn.Linear layout) and b [out]; synchronises"""
-        W = np.ascontiguousarray(W, dtype=np.float32)
-        b = np.ascontiguousarray(b, dtype=np.float32).ravel()
-        if not 0 <= int(layer) < len(self.layer_shapes) or W.shape != self.layer_shapes[layer] or b.shape != (W.shape[0],):
-            raise ValueError("set_weights: layer %r takes W %s and b (%d,)" % (layer, self.layer_shapes[layer] if 0 <= int(layer) < len(self.layer_shapes) else "?", W.shape[0]))
-        check(self._lib.chub_policy_set_weights(self._p, int(layer), _ptr(W), _ptr(b)))
-
-    def set_weights_device(self, layer, d_W, d_b, stream=0):
-        """the same from device memory in the trainer's layout (e.g. a parameter's data_ptr()), as one re-layout launch on `stream`: a
-        captured graph's next replay evaluates the new weights"""
-        check(self._lib.chub_policy_set_weights_device(self._p, int(layer), d_W, d_b, stream or None))
-
-    def get_weights(self, layer=None):
-        """the LIVE weights as float32 numpy arrays in the nn.Linear layout: (W, b) of one layer, or with layer=None the list over all
-        layers; synchronises"""
-        if layer is None:
-            return [self.get_weights(l) for l in range(len(self.layer_shapes))]
-        if not 0 <= int(layer) < len(self.layer_shapes):
-            raise ValueError("get_weights: layer is 0 .. %d" % (len(self.layer_shapes) - 1))
-        W = np.zeros(self.layer_shapes[layer], dtype=np.float32)
-        b = np.zeros((W.shape[0],), dtype=np.float32)
-        check(self._lib.chub_policy_get_weights(self._p, int(layer), _ptr(W), _ptr(b)))
-        return W, b
-
-    def get_weights_device(self, layer, d_W, d_b, stream=0):
-        """one layer into device memory in the trainer's layout (e.g. a parameter's data_ptr()), one launch on `stream`"""
-        check(self._lib.chub_policy_get_weights_device(self._p, int(layer), d_W or None, d_b or None, stream or None))
 
     def get_log_std(self, d_log_std=0, stream=0):
         """log_std [G]: as a float32 numpy array (synchronises), or with d_log_std a copy into device memory on `stream`"""
@@ -267,23 +306,7 @@ class DevicePolicy(object):
             check(self._lib.chub_policy_collect_set(self._env._h, self._p, run, _lib.pile_set(logp_piles), C.byref(r), d_set_bits or None,
                                                     d_obs0 or None, int(first_step), stream or None))
 
-    # ---- the normaliser, written, read and derived (include/chub.h, "running feature statistics"): policies made with normalize=
-    def _norm_pair(self, mean, inv_std):
-        mean = np.ascontiguousarray(mean, dtype=np.float32).ravel()
-        inv_std = np.ascontiguousarray(inv_std, dtype=np.float32).ravel()
-        if mean.shape != (self.n_features,) or inv_std.shape != (self.n_features,):
-            raise ValueError("mean and inv_std must have %d entries (the feature row)" % self.n_features)
-        return mean, inv_std
-
-    def set_normalizer(self, mean, inv_std):
-        """new mean / inv_std [F] from host arrays; synchronises"""
-        mean, inv_std = self._norm_pair(mean, inv_std)
-        check(self._lib.chub_policy_set_normalizer(self._p, _ptr(mean), _ptr(inv_std)))
-
-    def set_normalizer_device(self, d_mean, d_inv_std, stream=0):
-        """the same from device memory, [F] f32 each, as copies on `stream`: a captured graph's next replay evaluates the new normaliser"""
-        check(self._lib.chub_policy_set_normalizer_device(self._p, d_mean or None, d_inv_std or None, stream or None))
-
+    # ---- the normaliser read back (include/chub.h, "running feature statistics"; written and derived: _DeviceNet): policies made with normalize=
     def get_normalizer_device(self, d_mean, d_inv_std, stream=0):
         """the normaliser the policy evaluates with, copied on `stream` into d_mean / d_inv_std [F] f32 in device memory"""
         check(self._lib.chub_policy_get_normalizer_device(self._p, d_mean or None, d_inv_std or None, stream or None))
@@ -301,22 +324,6 @@ class DevicePolicy(object):
         finally:
             self._lib.chub_free_device(e._device, d)
         return out[0].copy(), out[1].copy()
-
-    def normalizer_from_moments(self, m, eps=1e-8, stream=0):
-        """mean = (float) the moments' mean, inv_std = (float) (1 / sqrt(M2 / n + eps)) (the population variance), one launch on `stream`;
-        moments that have counted nothing leave the normaliser alone.  Recordable into a graph."""
-        check(self._lib.chub_policy_normalizer_from_moments_device(self._p, m._m, float(eps), stream or None))
-
-    def close(self):
-        if getattr(self, "_p", None) and getattr(self._env, "_h", None):
-            check(self._lib.chub_policy_destroy(self._p))
-        self._p = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class DevicePopulation(object):
@@ -601,11 +608,12 @@ class DevicePolicyGrad(object):
             pass
 
 
-class DeviceCritic(object):
+class DeviceCritic(_DeviceNet):
     """A value network on the device (chub_critic_*, include/chub.h "a critic on the device"): made by VecChargingHub.make_critic.  It
     reads rows of F floats the caller points at (a rollout's features, observation blocks); values_device is the forward alone,
     grad_device the value loss and its gradient through the critic's LIVE weights and normaliser in the trainer's layout.  The actor's
     numerics, the same bits every call, no autograd."""
+    _c_name, _h_name, _row = "critic", "_c", "row"
 
     def __init__(self, env, layers, hidden_act="tanh", normalize=None, max_rows=None):
         self._env = env
@@ -727,61 +735,13 @@ class DeviceCritic(object):
             p += o * (i + 1)
         return {"grads": grads if backward else None, "values": v, "stats": stats}
 
-    def set_weights(self, layer, W, b):
-        """new weights of one layer from host arrays, W [out, in] (the nn.Linear layout) and b [out]; synchronises"""
-        W = np.ascontiguousarray(W, dtype=np.float32)
-        b = np.ascontiguousarray(b, dtype=np.float32).ravel()
-        if not 0 <= int(layer) < len(self.layer_shapes) or W.shape != self.layer_shapes[layer] or b.shape != (W.shape[0],):
-            raise ValueError("set_weights: layer %r takes W %s and b (%d,)" % (layer, self.layer_shapes[layer] if 0 <= int(layer) < len(self.layer_shapes) else "?", W.shape[0]))
-        check(self._lib.chub_critic_set_weights(self._c, int(layer), _ptr(W), _ptr(b)))
-
-    def set_weights_device(self, layer, d_W, d_b, stream=0):
-        """the same from device memory in the trainer's layout (e.g. a parameter's data_ptr()), as one re-layout launch on `stream`: a
-        captured graph's next replay evaluates the new weights"""
-        check(self._lib.chub_critic_set_weights_device(self._c, int(layer), d_W or None, d_b or None, stream or None))
-
-    def get_weights(self, layer=None):
-        """the LIVE weights as float32 numpy arrays in the nn.Linear layout: (W, b) of one layer, or with layer=None the list over all
-        layers; synchronises"""
-        if layer is None:
-            return [self.get_weights(l) for l in range(len(self.layer_shapes))]
-        if not 0 <= int(layer) < len(self.layer_shapes):
-            raise ValueError("get_weights: layer is 0 .. %d" % (len(self.layer_shapes) - 1))
-        W = np.zeros(self.layer_shapes[layer], dtype=np.float32)
-        b = np.zeros((W.shape[0],), dtype=np.float32)
-        check(self._lib.chub_critic_get_weights(self._c, int(layer), _ptr(W), _ptr(b)))
-        return W, b
-
-    def get_weights_device(self, layer, d_W, d_b, stream=0):
-        """one layer into device memory in the trainer's layout (e.g. a parameter's data_ptr()), one launch on `stream`"""
-        check(self._lib.chub_critic_get_weights_device(self._c, int(layer), d_W or None, d_b or None, stream or None))
-
-    def set_normalizer(self, mean, inv_std):
-        """new mean / inv_std [F] from host arrays; synchronises"""
-        mean = np.ascontiguousarray(mean, dtype=np.float32).ravel()
-        inv_std = np.ascontiguousarray(inv_std, dtype=np.float32).ravel()
-        if mean.shape != (self.n_features,) or inv_std.shape != (self.n_features,):
-            raise ValueError("mean and inv_std must have %d entries (the row)" % self.n_features)
-        check(self._lib.chub_critic_set_normalizer(self._c, _ptr(mean), _ptr(inv_std)))
-
     def set_normalizer_device(self, d_mean, d_inv_std, stream=0):
         """the same from device memory, [F] f32 each, as copies on `stream`"""
-        check(self._lib.chub_critic_set_normalizer_device(self._c, d_mean or None, d_inv_std or None, stream or None))
+        _DeviceNet.set_normalizer_device(self, d_mean, d_inv_std, stream)
 
     def normalizer_from_moments(self, m, eps=1e-8, stream=0):
         """mean = (float) the moments' mean, inv_std = (float) (1 / sqrt(M2 / n + eps)), one launch on `stream`, as the policy's; recordable"""
-        check(self._lib.chub_critic_normalizer_from_moments_device(self._c, m._m, float(eps), stream or None))
-
-    def close(self):
-        if getattr(self, "_c", None) and getattr(self._env, "_h", None):
-            check(self._lib.chub_critic_destroy(self._c))
-        self._c = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        _DeviceNet.normalizer_from_moments(self, m, eps, stream)
 
 
 class DeviceAdam(object):

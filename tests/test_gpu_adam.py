@@ -528,6 +528,28 @@ def test_refusals_leave_the_state_untouched():
     v.close()
 
 
+def test_destroying_the_handle_takes_the_whole_family_with_it():
+    """the ownership path no other test walks: chub_destroy while a policy with a population, a gradient object and an optimiser, and a
+    critic with an optimiser, are all alive.  Every call returns CHUB_OK, and a fresh handle works afterwards."""
+    lib = _lib.load_library()
+    rs = np.random.RandomState(5)
+    v = make("philox", (2, 3), N_ENVS)
+    pol = v.make_policy(pgl.general_layers(rs, [13, 8, 7]))
+    pol.set_exploration(KEY, [-0.5, 0.25])
+    family = [pol, v.make_population(pol, 2, KEY), v.make_policy_grad(pol, N_ENVS), v.make_adam(pol, **PLAIN)]
+    critic = v.make_critic(pgl.general_layers(rs, [13, 8, 1]), max_rows=N_ENVS)
+    family += [critic, v.make_adam(critic, **PLAIN)]
+    assert lib.chub_destroy(v._h) == 0, lib.chub_last_error()
+    v._h = None  # (what v.close() does; the objects went with the handle, so their close() calls nothing)
+    close_all(*family)
+    w = make("philox", (2, 3), N_ENVS)
+    w.reset()
+    fresh = w.make_critic(pgl.general_layers(rs, [13, 8, 1]), max_rows=N_ENVS)
+    assert np.isfinite(fresh.values(rs.uniform(0, 1, size=(N_ENVS, 13)).astype(F32))).all()
+    close_all(fresh)
+    w.close()
+
+
 # ---- 7. torch: the independent reference and the adapter, in child processes that import torch first (as tests/test_gpu_torch_side.py does)
 TORCH_CHILD = r"""
 import os, sys
