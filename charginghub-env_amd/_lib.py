@@ -306,6 +306,30 @@ class ChubAdamPlanOut(C.Structure):
                 ("step_workgroups", C.c_int32)]
 
 
+# a training log and a KL stop on the device (chub_train_log_*): the CHUB_KL_* and CHUB_TLOG_* enums of include/chub.h
+KL_NAMES = ("k1", "k3")
+KL = {name: i for i, name in enumerate(KL_NAMES)}
+TLOG = {"counted": 0, "after_stop": 1, "stopped": 2, "stop_index": 3, "actor": 4, "kl_max": 10, "kl_last": 11, "critic": 12, "actor_opt": 18,
+        "critic_opt": 24}
+TLOG_WORDS = 30
+
+
+def kl_kind(kl):
+    """a KL estimator as its CHUB_KL_* value: a name of KL_NAMES, or the value itself (the library refuses an unknown one)"""
+    return _enum_value(KL, kl, "KL estimator")
+
+
+class ChubPpoUpdateArgs(C.Structure):
+    """chub_ppo_update_args of include/chub.h: handles and device addresses, 0 / None = not given"""
+    _fields_ = [("grad", C.c_void_p), ("critic", C.c_void_p), ("actor_opt", C.c_void_p), ("critic_opt", C.c_void_p), ("log", C.c_void_p),
+                ("n_rows", C.c_int64), ("d_features", C.c_void_p), ("ld_features", C.c_int64), ("d_pile_bits", C.c_void_p),
+                ("d_set_bits", C.c_void_p), ("d_u", C.c_void_p), ("d_logp_old", C.c_void_p), ("d_adv", C.c_void_p), ("d_adv_stats", C.c_void_p),
+                ("d_ret", C.c_void_p), ("d_v_old", C.c_void_p), ("policy_loss", C.c_int32), ("value_loss", C.c_int32),
+                ("policy_clip_eps", C.c_float), ("value_clip_eps", C.c_float), ("ent_coef", C.c_float), ("epochs", C.c_int32),
+                ("minibatch_rows", C.c_int64), ("key", C.c_uint64), ("d_rows", C.c_void_p), ("kl_kind", C.c_int32), ("pad_", C.c_int32),
+                ("kl_limit", C.c_double)]
+
+
 # pile sets (chub_pile_set_device): the CHUB_PSET_* enum of include/chub.h, in order
 PSET_NAMES = ("all", "occupied", "decidable")
 PSET = {name: i for i, name in enumerate(PSET_NAMES)}
@@ -410,8 +434,8 @@ def source_hash():
 
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
-    for name in ("chub_kernels.hip", "chub_policy.hip", "chub_critic.hip", "chub_adam.hip", "chub_runtime.cpp", "chub_comm.cpp", "chub_device.h", "chub_curves.h",
-                 "chub_plan.h", "chub_policy.h", "chub_critic.h", "chub_adam.h"):
+    for name in ("chub_kernels.hip", "chub_policy.hip", "chub_critic.hip", "chub_adam.hip", "chub_trainlog.hip", "chub_runtime.cpp", "chub_comm.cpp", "chub_device.h", "chub_curves.h",
+                 "chub_plan.h", "chub_policy.h", "chub_critic.h", "chub_adam.h", "chub_trainlog.h"):
         h.update(open(os.path.join(csrc, name), "rb").read())
     h.update(open(os.path.join(os.path.dirname(_HERE), "include", "chub.h"), "rb").read())
     return h.hexdigest()[:16]
@@ -547,6 +571,11 @@ def load_library():
         "chub_policy_get_log_std_device": (I, [P, P, P]), "chub_policy_get_log_std": (I, [P, P]),
         "chub_critic_get_weights_device": (I, [P, C.c_int32, P, P, P]), "chub_critic_get_weights": (I, [P, C.c_int32, P, P]),
         "chub_shuffle_rows_device": (I, [P, C.c_uint64, P, L, L, P, P]), "chub_shuffle_rows": (I, [C.c_uint64, C.c_uint64, L, P]),
+        "chub_train_log_create": (I, [P, C.POINTER(P)]), "chub_train_log_destroy": (I, [P]), "chub_train_log_begin_device": (I, [P, P]),
+        "chub_train_log_record_device": (I, [P, P, P, C.c_int32, C.c_double, P]), "chub_train_log_steps_device": (I, [P, P, P, P]),
+        "chub_train_log_device": (I, [P, C.POINTER(P), C.POINTER(P)]), "chub_train_log_read": (I, [P, P]),
+        "chub_train_log_fold": (I, [P, P, P, P, C.c_int32, C.c_double]), "chub_adam_set_gate": (I, [P, P]),
+        "chub_ppo_update_plan": (I, [L, L, C.POINTER(L), C.POINTER(L)]), "chub_ppo_update": (I, [C.POINTER(ChubPpoUpdateArgs), P]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -599,7 +628,10 @@ EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "ch
             "chub_adam_grads", "chub_adam_counter_device", "chub_adam_step_device", "chub_adam_reset_device", "chub_adam_state_size",
             "chub_adam_get_state", "chub_adam_set_state", "chub_policy_get_weights_device", "chub_policy_get_weights",
             "chub_policy_get_log_std_device", "chub_policy_get_log_std", "chub_critic_get_weights_device", "chub_critic_get_weights",
-            "chub_shuffle_rows_device", "chub_shuffle_rows"]
+            "chub_shuffle_rows_device", "chub_shuffle_rows",
+            "chub_train_log_create", "chub_train_log_destroy", "chub_train_log_begin_device", "chub_train_log_record_device",
+            "chub_train_log_steps_device", "chub_train_log_device", "chub_train_log_read", "chub_train_log_fold", "chub_adam_set_gate",
+            "chub_ppo_update_plan", "chub_ppo_update"]
 
 
 def check(rc):

@@ -22,7 +22,7 @@ enum AdamScalar {
     ADAM_PREV_T, ADAM_PREV_P1, ADAM_PREV_P2,  // their copy, made by the norm launch: what every workgroup of the step launch reads
     ADAM_SCALARS
 };
-constexpr int kAdamStats = 4;  // t, norm, scale, skipped
+constexpr int kAdamStats = 4;  // t, norm, scale, 0 taken / 1 skipped / 2 held back by the gate
 
 struct AdamArgs {
     float *w[kPolicyMaxLayers], *b[kPolicyMaxLayers];  // the target's live layers: [tiles][k_pad][32], [tiles * 32]
@@ -36,6 +36,7 @@ struct AdamArgs {
     double *scalars;                       // [ADAM_SCALARS]
     double *partials;                      // [chunks]: a chunk's sum of squares
     double *stats;                         // [kAdamStats] or null
+    const int64_t *gate;                   // null, or a word in device memory: not 0 holds the step back (stats[3] = 2)
 };
 
 // [launch 1] the chunks' sums of squares and the copy of t, p1, p2; [launch 2] the step

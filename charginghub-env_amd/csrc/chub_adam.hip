@@ -80,12 +80,13 @@ __global__ __launch_bounds__(kAdamLanes) void k_adam_step(const AdamArgs a) {
     const double *sc = a.scalars;
     const int64_t t0 = reinterpret_cast<const int64_t *>(sc)[ADAM_PREV_T];
     const bool first = blockIdx.x == 0 && threadIdx.x == 0;
-    if (!isfinite(norm)) {  // skipped: nothing but the stats is written
+    const bool held = a.gate != nullptr && *a.gate != 0;  // (every workgroup reads the word: all of them return, or none)
+    if (held || !isfinite(norm)) {  // held back or skipped: nothing but the stats is written
         if (first && a.stats) {
             a.stats[0] = (double) t0;
             a.stats[1] = norm;
             a.stats[2] = 0.0;
-            a.stats[3] = 1.0;
+            a.stats[3] = held ? 2.0 : 1.0;
         }
         return;
     }

@@ -20,6 +20,7 @@
 #include "chub_policy.h"
 #include "chub_critic.h"
 #include "chub_adam.h"
+#include "chub_trainlog.h"
 
 namespace chub {
 template <bool RESET>
@@ -187,6 +188,8 @@ struct chub_env {
     std::vector<chub_moments *> moments;
     // the critics made for this handle (chub_critic_create): destroyed before it, weights and workspace outside the arena
     std::vector<chub_critic *> critics;
+    // the training logs made for this handle (chub_train_log_create): destroyed before it, words, gate and stats blocks outside the arena
+    std::vector<chub_train_log *> train_logs;
     // chub_rollout_gae_device's statistics: the workgroups' partials [ceil(N / 256)][3] f64, allocated at create outside the arena (derived
     // scratch: no snapshot carries it).  One buffer: calls that ask for d_stats must be ordered against each other
     double *d_gae_part = nullptr;
@@ -1088,9 +1091,11 @@ static int create_impl(const chub_config *cfg_in, const char *data_dir, int64_t 
 static void policy_free(chub_policy *pol);
 static void moments_free(chub_moments *m);
 static void critic_free(chub_critic *c);
+static void train_log_free(chub_train_log *log);
 
 int chub_destroy(chub_env *e) {
     if (!e) return CHUB_OK;
+    while (!e->train_logs.empty()) train_log_free(e->train_logs.back());  // (first: it clears the gates of optimisers that still live)
     while (!e->moments.empty()) moments_free(e->moments.back());  // (each takes itself off the list)
     while (!e->policies.empty()) policy_free(e->policies.back());
     while (!e->critics.empty()) critic_free(e->critics.back());
@@ -5015,8 +5020,8 @@ int chub_policy_grad_destroy(chub_policy_grad *g) {
     return CHUB_OK;
 }
 
-int chub_policy_grad_device(chub_policy_grad *g, const chub_policy_grad_in *in, const chub_policy_grad_out *out, void *stream) {
-    if (!g || !in || !out) return fail(CHUB_ERR_ARG, "null argument");
+// what chub_policy_grad_device refuses of its input (chub_ppo_update asks the same before it enqueues anything)
+static int policy_grad_check(const chub_policy_grad *g, const chub_policy_grad_in *in) {
     const chub_policy *pol = g->pol;
     const bool piles = pol->spec.head == CHUB_PHEAD_PILES;
     if (!in->d_features || !in->d_u || !in->d_adv || (piles && !in->d_pile_bits)) return fail(CHUB_ERR_ARG, "null argument");
@@ -5031,6 +5036,13 @@ int chub_policy_grad_device(chub_policy_grad *g, const chub_policy_grad_in *in, 
     if (!std::isfinite(in->ent_coef)) return fail(CHUB_ERR_ARG, "ent_coef is not finite");
     if (!piles && in->d_set_bits) return fail(CHUB_ERR_ARG, "chub_policy_grad_device: under CHUB_PHEAD_LOADS the log-probability has no pile terms: d_set_bits must be NULL");
     if (!pol->explore) return fail(CHUB_ERR_ARG, "chub_policy_grad_device: chub_policy_set_exploration first (the log-probability needs log_std)");
+    return CHUB_OK;
+}
+
+int chub_policy_grad_device(chub_policy_grad *g, const chub_policy_grad_in *in, const chub_policy_grad_out *out, void *stream) {
+    if (!g || !in || !out) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = policy_grad_check(g, in)) return rc;
+    const chub_policy *pol = g->pol;
     HIP_TRY(hipSetDevice(pol->net.env->device));
     (void) hipGetLastError();
     const GradPlan &gp = g->ws.gp;
@@ -5257,8 +5269,8 @@ int chub_critic_values_device(chub_critic *c, const float *d_x, int64_t ld, int6
     return CHUB_OK;
 }
 
-int chub_critic_grad_device(chub_critic *c, const chub_critic_grad_in *in, const chub_critic_grad_out *out, void *stream) {
-    if (!c || !in || !out) return fail(CHUB_ERR_ARG, "null argument");
+// what chub_critic_grad_device refuses of its input (chub_ppo_update asks the same before it enqueues anything)
+static int critic_grad_check(const chub_critic *c, const chub_critic_grad_in *in) {
     if (const int rc = critic_check_rows(c, "chub_critic_grad_device", in->d_x, in->ld, in->n_rows, in->d_rows, in->R)) return rc;
     if (!in->d_ret) return fail(CHUB_ERR_ARG, "null argument");
     if (in->loss != CHUB_VLOSS_MSE && in->loss != CHUB_VLOSS_CLIPPED) return fail(CHUB_ERR_ARG, "loss: CHUB_VLOSS_MSE or CHUB_VLOSS_CLIPPED");
@@ -5266,6 +5278,12 @@ int chub_critic_grad_device(chub_critic *c, const chub_critic_grad_in *in, const
         if (!(in->clip_eps > 0.0f) || !std::isfinite(in->clip_eps)) return fail(CHUB_ERR_ARG, "clip_eps: finite and > 0 under CHUB_VLOSS_CLIPPED");
         if (!in->d_v_old) return fail(CHUB_ERR_ARG, "null argument");
     }
+    return CHUB_OK;
+}
+
+int chub_critic_grad_device(chub_critic *c, const chub_critic_grad_in *in, const chub_critic_grad_out *out, void *stream) {
+    if (!c || !in || !out) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = critic_grad_check(c, in)) return rc;
     HIP_TRY(hipSetDevice(c->net.env->device));
     (void) hipGetLastError();
     const GradPlan &gp = c->ws.gp;
@@ -5343,6 +5361,7 @@ struct chub_adam {
     int32_t n_layers, G;
     float *d_m, *d_v, *d_g;
     double *d_scalars, *d_partials;
+    double *d_own_stats;  // chub_ppo_update without a log: the target's gradient stats [6], then the step's [4]
     DeviceAllocs allocs;
 };
 
@@ -5413,6 +5432,7 @@ static int adam_create_for(MlpNet &net, const char *who, int G, float *d_log_std
     double sc[ADAM_SCALARS] = {h->lr, h->beta1, h->beta2, h->eps, h->weight_decay, h->max_grad_norm, 0.0, 1.0, 1.0, 0.0, 1.0, 1.0};  // (t = 0 is all zero bits)
     const bool ok = !a->allocs.zeroed(&a->d_m, n) && !a->allocs.zeroed(&a->d_v, n) && !a->allocs.zeroed(&a->d_g, n) &&
                     !a->allocs.zeroed(&a->d_scalars, (size_t) ADAM_SCALARS) && !a->allocs.zeroed(&a->d_partials, (size_t) ap.chunks) &&
+                    !a->allocs.zeroed(&a->d_own_stats, (size_t) (kTrainLogGradStats + kTrainLogStepStats)) &&
                     hipMemcpy(a->d_scalars, sc, sizeof sc, hipMemcpyHostToDevice) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
     if (!ok) {
         adam_free(a);
@@ -5571,6 +5591,242 @@ int chub_shuffle_rows(uint64_t key, uint64_t counter, int64_t R, int64_t *rows) 
     const int nb = shuffle_bits(R);
     for (int64_t r = 0; r < R; r++) rows[r] = shuffle_row(r, R, nb, key, counter);
     return CHUB_OK;
+}
+
+}  // extern "C"
+
+// ---- a training log and a KL stop on the device (include/chub.h): the object, the three launches, the host fold, the gate, the update as
+// one call.  The kernels are chub_trainlog.hip's, the fold's arithmetic chub_trainlog.h's
+static_assert((int) CHUB_TLOG_WORDS == TLOG_WORDS && (int) CHUB_TLOG_COUNTED == TLOG_COUNTED && (int) CHUB_TLOG_AFTER_STOP == TLOG_AFTER_STOP &&
+                  (int) CHUB_TLOG_STOPPED == TLOG_STOPPED && (int) CHUB_TLOG_STOP_INDEX == TLOG_STOP_INDEX && (int) CHUB_TLOG_ACTOR == TLOG_ACTOR &&
+                  (int) CHUB_TLOG_KL_MAX == TLOG_KL_MAX && (int) CHUB_TLOG_KL_LAST == TLOG_KL_LAST && (int) CHUB_TLOG_CRITIC == TLOG_CRITIC &&
+                  (int) CHUB_TLOG_ACTOR_OPT == TLOG_ACTOR_OPT && (int) CHUB_TLOG_CRITIC_OPT == TLOG_CRITIC_OPT && (int) CHUB_KL_K1 == KL_K1 &&
+                  (int) CHUB_KL_K3 == KL_K3 && (int) CHUB_KL_COUNT == KL_COUNT,
+              "chub_trainlog.h restates the CHUB_TLOG_* / CHUB_KL_* enums");
+static_assert(kTrainLogStepStats == kAdamStats, "the log reads the optimiser's stats block");
+
+struct chub_train_log {
+    chub_env *env;
+    double *d_block;   // the words [TLOG_WORDS], the gate (one int64 word), then chub_ppo_update's four stats blocks
+    double *d_words;
+    int64_t *d_gate;
+    double *d_pstats, *d_cstats, *d_astats_actor, *d_astats_critic;
+    DeviceAllocs allocs;
+};
+
+template <class F>
+static void for_each_adam(chub_env *e, F f) {
+    for (chub_policy *pol : e->policies)
+        for (chub_adam *a : pol->net.adams) f(a);
+    for (chub_critic *c : e->critics)
+        for (chub_adam *a : c->net.adams) f(a);
+}
+
+static void train_log_free(chub_train_log *log) {
+    chub_env *e = log->env;
+    (void) hipSetDevice(e->device);
+    (void) hipDeviceSynchronize();  // (a launch still in flight reads the gate and writes the words)
+    for_each_adam(e, [log](chub_adam *a) {
+        if (a->args.gate == log->d_gate) a->args.gate = nullptr;
+    });
+    log->allocs.free_all();
+    e->train_logs.erase(std::remove(e->train_logs.begin(), e->train_logs.end(), log), e->train_logs.end());
+    delete log;
+}
+
+static int train_log_check_kl(const char *who, int32_t kl_kind, double kl_limit) {
+    if (kl_kind != CHUB_KL_K1 && kl_kind != CHUB_KL_K3) return fail(CHUB_ERR_ARG, std::string(who) + ": kl_kind: CHUB_KL_K1 or CHUB_KL_K3");
+    if (!(kl_limit >= 0.0)) return fail(CHUB_ERR_ARG, std::string(who) + ": kl_limit: >= 0 (0: never stops)");
+    return CHUB_OK;
+}
+
+static int ppo_split(int64_t n_rows, int64_t minibatch_rows, int64_t *minibatches, int64_t *last_rows) {
+    if (n_rows < 1) return fail(CHUB_ERR_ARG, "chub_ppo_update: n_rows is at least 1");
+    if (minibatch_rows < 1) return fail(CHUB_ERR_ARG, "chub_ppo_update: minibatch_rows is at least 1");
+    const int64_t M = (n_rows + minibatch_rows - 1) / minibatch_rows;  // (n_rows <= 2^40 wherever it matters: no overflow below 2^62)
+    *minibatches = M;
+    *last_rows = n_rows - (M - 1) * minibatch_rows;
+    return CHUB_OK;
+}
+
+extern "C" {
+
+int chub_train_log_create(chub_env *e, chub_train_log **out) {
+    if (!e || !out) return fail(CHUB_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (e->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_train_log_create between chub_graph_begin and chub_graph_end (it allocates and synchronises)");
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    chub_train_log *log = new chub_train_log();
+    log->env = e;
+    e->train_logs.push_back(log);
+    constexpr size_t kWords = (size_t) TLOG_WORDS + 1 + 2 * kTrainLogGradStats + 2 * kTrainLogStepStats;
+    double h[kWords] = {0.0};
+    h[TLOG_STOP_INDEX] = -1.0;  // (what begin leaves)
+    if (log->allocs.zeroed(&log->d_block, kWords) || hipMemcpy(log->d_block, h, sizeof h, hipMemcpyHostToDevice) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {
+        train_log_free(log);
+        (void) hipGetLastError();
+        return fail(CHUB_ERR_HIP, "chub_train_log_create: out of device memory");
+    }
+    log->d_words = log->d_block;
+    log->d_gate = reinterpret_cast<int64_t *>(log->d_block + TLOG_WORDS);
+    log->d_pstats = log->d_block + TLOG_WORDS + 1;
+    log->d_cstats = log->d_pstats + kTrainLogGradStats;
+    log->d_astats_actor = log->d_cstats + kTrainLogGradStats;
+    log->d_astats_critic = log->d_astats_actor + kTrainLogStepStats;
+    *out = log;
+    return CHUB_OK;
+}
+
+int chub_train_log_destroy(chub_train_log *log) {
+    if (!log) return CHUB_OK;
+    if (log->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_train_log_destroy between chub_graph_begin and chub_graph_end (it synchronises and frees)");
+    train_log_free(log);
+    (void) hipGetLastError();
+    return CHUB_OK;
+}
+
+int chub_train_log_begin_device(chub_train_log *log, void *stream) {
+    if (!log) return fail(CHUB_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(log->env->device));
+    (void) hipGetLastError();
+    launch_trainlog_begin(log->d_words, log->d_gate, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_train_log_record_device(chub_train_log *log, const double *d_pstats, const double *d_cstats, int32_t kl_kind, double kl_limit, void *stream) {
+    if (!log) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = train_log_check_kl("chub_train_log_record_device", kl_kind, kl_limit)) return rc;
+    HIP_TRY(hipSetDevice(log->env->device));
+    (void) hipGetLastError();
+    launch_trainlog_record(log->d_words, log->d_gate, d_pstats, d_cstats, kl_kind, kl_limit, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_train_log_steps_device(chub_train_log *log, const double *d_astats_actor, const double *d_astats_critic, void *stream) {
+    if (!log) return fail(CHUB_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(log->env->device));
+    (void) hipGetLastError();
+    launch_trainlog_steps(log->d_words, d_astats_actor, d_astats_critic, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_train_log_device(chub_train_log *log, const double **d_words, const int64_t **d_gate) {
+    if (!log || !d_words || !d_gate) return fail(CHUB_ERR_ARG, "null argument");
+    *d_words = log->d_words;
+    *d_gate = log->d_gate;
+    return CHUB_OK;
+}
+
+int chub_train_log_read(chub_train_log *log, double *words) {
+    if (!log || !words) return fail(CHUB_ERR_ARG, "null argument");
+    if (log->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_train_log_read between chub_graph_begin and chub_graph_end (it copies and synchronises)");
+    HIP_TRY(hipSetDevice(log->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(words, log->d_words, (size_t) TLOG_WORDS * sizeof(double), hipMemcpyDeviceToHost));
+    return CHUB_OK;
+}
+
+int chub_train_log_fold(double *words, int64_t *gate, const double *pstats, const double *cstats, int32_t kl_kind, double kl_limit) {
+    if (!words || !gate) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = train_log_check_kl("chub_train_log_fold", kl_kind, kl_limit)) return rc;
+    trainlog_record(words, gate, pstats, cstats, kl_kind, kl_limit);
+    return CHUB_OK;
+}
+
+int chub_adam_set_gate(chub_adam *a, const int64_t *d_gate) {
+    if (!a) return fail(CHUB_ERR_ARG, "null argument");
+    a->args.gate = d_gate;
+    return CHUB_OK;
+}
+
+int chub_ppo_update_plan(int64_t n_rows, int64_t minibatch_rows, int64_t *minibatches, int64_t *last_rows) {
+    if (!minibatches || !last_rows) return fail(CHUB_ERR_ARG, "null argument");
+    return ppo_split(n_rows, minibatch_rows, minibatches, last_rows);
+}
+
+int chub_ppo_update(const chub_ppo_update_args *u, void *stream) {
+    if (!u) return fail(CHUB_ERR_ARG, "null argument");
+    if (!u->grad || !u->critic || !u->actor_opt || !u->critic_opt) return fail(CHUB_ERR_ARG, "chub_ppo_update: null grad, critic, actor_opt or critic_opt");
+    chub_policy *pol = u->grad->pol;
+    chub_env *e = pol->net.env;
+    if (u->critic->net.env != e || u->actor_opt->net->env != e || u->critic_opt->net->env != e || (u->log && u->log->env != e))
+        return fail(CHUB_ERR_ARG, "chub_ppo_update: the gradient object, the critic, the optimisers and the log belong to one handle");
+    if (u->actor_opt->net != &pol->net) return fail(CHUB_ERR_ARG, "chub_ppo_update: actor_opt is not an optimiser of the gradient object's policy");
+    if (u->critic_opt->net != &u->critic->net) return fail(CHUB_ERR_ARG, "chub_ppo_update: critic_opt is not an optimiser of the critic");
+    if (u->epochs < 1) return fail(CHUB_ERR_ARG, "chub_ppo_update: epochs is at least 1");
+    int64_t M, last;
+    if (const int rc = ppo_split(u->n_rows, u->minibatch_rows, &M, &last)) return rc;
+    if (u->minibatch_rows > u->grad->max_rows || u->minibatch_rows > u->critic->max_rows)
+        return fail(CHUB_ERR_ARG, "chub_ppo_update: minibatch_rows is at most the gradient object's max_rows = " + std::to_string(u->grad->max_rows) +
+                                      " and the critic's = " + std::to_string(u->critic->max_rows));
+    if (!u->d_rows) return fail(CHUB_ERR_ARG, "chub_ppo_update: null d_rows (the caller's [n_rows] int64 the shuffles are written to)");
+    if (const int rc = train_log_check_kl("chub_ppo_update", u->kl_kind, u->kl_limit)) return rc;
+    if (u->n_rows > ((int64_t) 1 << 40)) return fail(CHUB_ERR_ARG, "chub_ppo_update: chub_shuffle_rows_device: R is 1 .. 2^40");
+    // the constituents' own refusals, for both sizes of a minibatch, before anything is enqueued
+    chub_policy_grad_in pin = {};
+    pin.n_rows = u->n_rows;
+    pin.d_features = u->d_features;
+    pin.ld_features = u->ld_features;
+    pin.d_pile_bits = u->d_pile_bits;
+    pin.d_set_bits = u->d_set_bits;
+    pin.d_u = u->d_u;
+    pin.d_logp_old = u->d_logp_old;
+    pin.d_adv = u->d_adv;
+    pin.d_adv_stats = u->d_adv_stats;
+    pin.loss = u->policy_loss;
+    pin.clip_eps = u->policy_clip_eps;
+    pin.ent_coef = u->ent_coef;
+    chub_critic_grad_in cin = {};
+    cin.n_rows = u->n_rows;
+    cin.d_x = u->d_features;
+    cin.ld = u->ld_features;
+    cin.d_ret = u->d_ret;
+    cin.d_v_old = u->d_v_old;
+    cin.loss = u->value_loss;
+    cin.clip_eps = u->value_clip_eps;
+    const int64_t sizes[2] = {M > 1 ? u->minibatch_rows : last, last};
+    for (int k = 0; k < 2; k++) {
+        pin.R = cin.R = sizes[k];
+        pin.d_rows = cin.d_rows = u->d_rows;
+        if (const int rc = policy_grad_check(u->grad, &pin)) return fail(rc, "chub_ppo_update: chub_policy_grad_device: " + std::string(g_err));
+        if (const int rc = critic_grad_check(u->critic, &cin)) return fail(rc, "chub_ppo_update: chub_critic_grad_device: " + std::string(g_err));
+    }
+    chub_policy_grad_out pout = {};
+    chub_critic_grad_out cout_ = {};
+    float *unused = nullptr;
+    if (const int rc = chub_adam_grads(u->actor_opt, pout.d_gW, pout.d_gb, &pout.d_glog_std)) return rc;
+    if (const int rc = chub_adam_grads(u->critic_opt, cout_.d_gW, cout_.d_gb, &unused)) return rc;
+    chub_train_log *log = u->log;
+    double *astats_actor = log ? log->d_astats_actor : u->actor_opt->d_own_stats + kTrainLogGradStats;
+    double *astats_critic = log ? log->d_astats_critic : u->critic_opt->d_own_stats + kTrainLogGradStats;
+    pout.d_stats = log ? log->d_pstats : u->actor_opt->d_own_stats;
+    cout_.d_stats = log ? log->d_cstats : u->critic_opt->d_own_stats;
+    const int64_t *gate_a = u->actor_opt->args.gate, *gate_c = u->critic_opt->args.gate;
+    if (log) u->actor_opt->args.gate = u->critic_opt->args.gate = log->d_gate;
+    const int64_t *d_t = reinterpret_cast<const int64_t *>(u->actor_opt->d_scalars) + ADAM_T;
+    int rc = log ? chub_train_log_begin_device(log, stream) : CHUB_OK;
+    for (int32_t ep = 0; ep < u->epochs && !rc; ep++) {
+        rc = chub_shuffle_rows_device(e, u->key, d_t, ep, u->n_rows, u->d_rows, stream);
+        for (int64_t i = 0; i < M && !rc; i++) {
+            pin.R = cin.R = i + 1 < M ? u->minibatch_rows : last;
+            pin.d_rows = cin.d_rows = u->d_rows + i * u->minibatch_rows;
+            rc = chub_policy_grad_device(u->grad, &pin, &pout, stream);
+            if (!rc) rc = chub_critic_grad_device(u->critic, &cin, &cout_, stream);
+            if (!rc && log) rc = chub_train_log_record_device(log, pout.d_stats, cout_.d_stats, u->kl_kind, u->kl_limit, stream);
+            if (!rc) rc = chub_adam_step_device(u->actor_opt, pout.d_gW, pout.d_gb, pout.d_glog_std, astats_actor, stream);
+            if (!rc) rc = chub_adam_step_device(u->critic_opt, cout_.d_gW, cout_.d_gb, nullptr, astats_critic, stream);
+            if (!rc && log) rc = chub_train_log_steps_device(log, astats_actor, astats_critic, stream);
+        }
+    }
+    u->actor_opt->args.gate = gate_a;
+    u->critic_opt->args.gate = gate_c;
+    return rc;
 }
 
 }  // extern "C"

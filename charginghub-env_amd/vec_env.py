@@ -796,6 +796,11 @@ class DeviceAdam(object):
         bp = (C.c_void_p * 4)(*[(gb[l] or None) for l in range(n)])
         check(self._lib.chub_adam_step_device(self._a, Wp, bp, gl or None, d_stats or None, stream or None))
 
+    def set_gate(self, d_gate):
+        """point the optimiser at an int64 word in device memory (a DeviceTrainLog's gate_address), or 0 / None for none
+        (chub_adam_set_gate): where the word is not 0 a step keeps every bit of weights and state and writes stats [t, norm, 0, 2]"""
+        check(self._lib.chub_adam_set_gate(self._a, d_gate or None))
+
     def set_hyper(self, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=0.0):
         """new hyper-parameters from host values; synchronises"""
         check(self._lib.chub_adam_set_hyper(self._a, C.byref(_lib.adam_hyper(lr, betas, eps, weight_decay, max_grad_norm))))
@@ -831,6 +836,69 @@ class DeviceAdam(object):
             self.close()
         except Exception:
             pass
+
+
+class DeviceTrainLog(object):
+    """The numbers of a PPO update and its KL stop, kept on the device (chub_train_log_*, include/chub.h "a training log and a KL stop on
+    the device"): made by VecChargingHub.make_train_log.  begin, record and steps are one small launch each on the caller's stream,
+    recordable into a graph; read is the one synchronising copy.  gate_address is the word DeviceAdam.set_gate takes."""
+
+    def __init__(self, env):
+        self._env = env
+        self._lib = env._lib
+        h = C.c_void_p()
+        check(self._lib.chub_train_log_create(env._h, C.byref(h)))
+        self._t = h
+        w, g = C.c_void_p(), C.c_void_p()
+        check(self._lib.chub_train_log_device(self._t, C.byref(w), C.byref(g)))
+        self.words_address, self.gate_address = w.value, g.value
+
+    def begin(self, stream=0):
+        """every word 0, the stop index -1, the gate 0 (chub_train_log_begin_device)"""
+        check(self._lib.chub_train_log_begin_device(self._t, stream or None))
+
+    def record(self, d_pstats=0, d_cstats=0, kl="k3", kl_limit=0.0, stream=0):
+        """one minibatch, after its two gradient calls and before its steps (chub_train_log_record_device): d_pstats / d_cstats are the
+        stats blocks [6] f64 of DevicePolicyGrad.grad_device / DeviceCritic.grad_device (0: none).  kl_limit > 0 stops the update at the
+        first minibatch whose estimate is not <= kl_limit."""
+        check(self._lib.chub_train_log_record_device(self._t, d_pstats or None, d_cstats or None, _lib.kl_kind(kl), float(kl_limit), stream or None))
+
+    def steps(self, d_astats_actor=0, d_astats_critic=0, stream=0):
+        """after the minibatch's optimiser steps (chub_train_log_steps_device), on their stats blocks [4] f64 (0: none)"""
+        check(self._lib.chub_train_log_steps_device(self._t, d_astats_actor or None, d_astats_critic or None, stream or None))
+
+    def read(self):
+        """the words -> float64 [TLOG_WORDS] (the layout: _lib.TLOG); synchronises"""
+        words = np.zeros(_lib.TLOG_WORDS, dtype=np.float64)
+        check(self._lib.chub_train_log_read(self._t, _ptr(words)))
+        return words
+
+    def close(self):
+        if getattr(self, "_t", None) and getattr(self._env, "_h", None):
+            check(self._lib.chub_train_log_destroy(self._t))
+        self._t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def train_log_fold(words, gate, pstats=None, cstats=None, kl="k3", kl_limit=0.0):
+    """the record step on host memory (chub_train_log_fold; no device): words float64 [TLOG_WORDS] and gate int64 [1] are updated in place"""
+    assert words.dtype == np.float64 and words.size == _lib.TLOG_WORDS and gate.dtype == np.int64 and gate.size == 1
+    ps = None if pstats is None else np.ascontiguousarray(pstats, dtype=np.float64)
+    cs = None if cstats is None else np.ascontiguousarray(cstats, dtype=np.float64)
+    check(_lib.load_library().chub_train_log_fold(_ptr(words), _ptr(gate), None if ps is None else _ptr(ps), None if cs is None else _ptr(cs),
+                                                  _lib.kl_kind(kl), float(kl_limit)))
+
+
+def ppo_update_plan(n_rows, minibatch_rows):
+    """(minibatches per epoch, rows of the last one) of ppo_update's split (chub_ppo_update_plan; host arithmetic only)"""
+    m, last = C.c_int64(), C.c_int64()
+    check(_lib.load_library().chub_ppo_update_plan(int(n_rows), int(minibatch_rows), C.byref(m), C.byref(last)))
+    return m.value, last.value
 
 
 class DeviceMoments(object):
@@ -1489,6 +1557,30 @@ class VecChargingHub(object):
         if getattr(target, "_env", None) is not self:
             raise ValueError("make_adam: the target was made for another handle")
         return DeviceAdam(self, target, _lib.adam_hyper(lr, betas, eps, weight_decay, max_grad_norm))
+
+    def make_train_log(self):
+        """a training log with its gate word for this handle -> DeviceTrainLog (chub_train_log_create)"""
+        return DeviceTrainLog(self)
+
+    def ppo_update(self, grad, critic, actor_opt, critic_opt, n_rows, d_features, d_u, d_logp_old, d_adv, d_ret, d_rows, epochs, minibatch_rows, key,
+                   d_pile_bits=0, d_set_bits=0, d_adv_stats=0, d_v_old=0, ld_features=None, loss="ppo_clip", value_loss="mse", clip_eps=0.2,
+                   value_clip_eps=0.2, ent_coef=0.0, kl="k3", kl_limit=0.0, log=None, stream=0):
+        """a whole PPO update enqueued on `stream` by one call (chub_ppo_update): per epoch a shuffle of the n_rows rows into d_rows
+        [n_rows] int64 under the actor optimiser's step count, per minibatch the actor gradient, the critic gradient, log.record, the two
+        steps, log.steps.  grad: a DevicePolicyGrad; critic: a DeviceCritic; the optimisers are theirs.  With log (a DeviceTrainLog)
+        the update begins the log and both optimisers honour its gate: kl_limit > 0 stops stepping at the first minibatch whose KL
+        estimate (kl: "k1" or "k3") is not <= kl_limit.  No synchronisation; recordable into a graph."""
+        a = _lib.ChubPpoUpdateArgs()
+        a.grad, a.critic, a.actor_opt, a.critic_opt, a.log = grad._g, critic._c, actor_opt._a, critic_opt._a, (log._t if log is not None else None)
+        a.n_rows, a.d_features = int(n_rows), d_features or None
+        a.ld_features = grad.policy.n_features if ld_features is None else int(ld_features)
+        a.d_pile_bits, a.d_set_bits, a.d_u, a.d_logp_old, a.d_adv = d_pile_bits or None, d_set_bits or None, d_u or None, d_logp_old or None, d_adv or None
+        a.d_adv_stats, a.d_ret, a.d_v_old = d_adv_stats or None, d_ret or None, d_v_old or None
+        a.policy_loss, a.value_loss = _lib.policy_loss(loss), _lib.value_loss(value_loss)
+        a.policy_clip_eps, a.value_clip_eps, a.ent_coef = float(clip_eps), float(value_clip_eps), float(ent_coef)
+        a.epochs, a.minibatch_rows, a.key, a.d_rows = int(epochs), int(minibatch_rows), int(key) & (2 ** 64 - 1), d_rows or None
+        a.kl_kind, a.kl_limit = _lib.kl_kind(kl), float(kl_limit)
+        check(self._lib.chub_ppo_update(C.byref(a), stream or None))
 
     def shuffle_rows_device(self, d_rows, R, key, d_counter=0, offset=0, stream=0):
         """a permutation of 0 .. R - 1 into d_rows [R] int64 on `stream` (chub_shuffle_rows_device): a pure function of (key, counter, R)

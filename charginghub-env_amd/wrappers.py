@@ -312,6 +312,26 @@ def normalize_features(features, mean, inv_std, clip):
     return torch.clamp((features - mean) * inv_std, min=-float(clip), max=float(clip))
 
 
+def train_log_summary(words, kl="k3"):
+    """The words of a training log (DeviceTrainLog.read) -> a dict under stable-baselines3's names; the sums are the log's f64 sums, every
+    quotient is one f64 division.  A log that counted no minibatch gives NaN means."""
+    w = np.asarray(words, dtype=np.float64)
+    T = _lib.TLOG
+    a, c = w[T["actor"]:T["actor"] + 6], w[T["critic"]:T["critic"] + 6]
+    with np.errstate(all="ignore"):
+        k1 = a[3] / a[0]
+        out = {"n_minibatches": int(w[T["counted"]]), "stopped_at": None if w[T["stop_index"]] < 0 else int(w[T["stop_index"]]),
+               "approx_kl": float(k1 if _lib.kl_kind(kl) == _lib.KL["k1"] else (a[5] / a[0] - 1.0) + k1), "approx_kl_max": float(w[T["kl_max"]]),
+               "clip_fraction": float(a[4] / a[0]), "entropy": float(a[2] / a[0]), "policy_loss": float(a[1] / a[0]),
+               "value_loss": float(c[1] / c[0]), "value_clip_fraction": float(c[2] / c[0]),
+               "explained_variance": float(1.0 - (c[3] / c[0]) / max(c[5] / c[0] - (c[4] / c[0]) ** 2, 1e-12))}
+        for name, base in (("policy_opt", T["actor_opt"]), ("critic_opt", T["critic_opt"])):
+            o = w[base:base + 6]
+            out[name] = {"steps": int(o[0]), "skipped": int(o[1]), "held_back": int(o[2]), "grad_norm_mean": float(o[3] / (o[0] + o[2])),  # (a skipped step's norm is not finite and not in the sum)
+                         "grad_norm_max": float(o[4]), "clipped_steps": int(o[5])}
+    return out
+
+
 class TorchHubVecEnv(object):
     """The hub for an on-device learner: actions in and observations / rewards / dones out are torch CUDA tensors, the
     step runs through the device-pointer entry points on torch's current stream, and nothing is copied through the host
@@ -765,6 +785,23 @@ class TorchHubVecEnv(object):
         return (adv, ret, st) if stats else (adv, ret)
 
     # ---- actor gradients on the device (chub_policy_grad_*): the policy-gradient step with no autograd for the actor
+    def _policy_grad_entry(self, policy, R, n_rows):
+        """the policy's gradient object for calls of R rows over arrays of n_rows, with the tensors its calls fill (made on first use)"""
+        torch = self.torch
+        cache = getattr(self, "_pgrad", None)
+        if cache is None:
+            cache = self._pgrad = {}
+        ent = cache.get(id(policy))
+        if ent is None or ent["grad"].max_rows < R:
+            if ent is not None:
+                ent["grad"].close()
+            g = self.vec.make_policy_grad(policy, max(R, n_rows))
+            f32 = dict(dtype=torch.float32, device=self.device)
+            ent = cache[id(policy)] = {"grad": g, "grads": [(torch.zeros((o, i), **f32), torch.zeros((o,), **f32)) for o, i in g.layer_shapes],
+                                       "g_log_std": torch.zeros((policy.n_gaussians,), **f32),
+                                       "stats": torch.zeros((6,), dtype=torch.float64, device=self.device), "rows": {}}
+        return ent
+
     def _policy_grad_call(self, rollout, adv, rows, loss, clip_eps, ent_coef, adv_stats, backward, into=None):
         torch = self.torch
         policy = getattr(self, "_rollout_policy", {}).get(id(rollout))
@@ -780,18 +817,7 @@ class TorchHubVecEnv(object):
         if adv_stats is not None and not (self._on_device(adv_stats) and adv_stats.dtype == torch.float64 and adv_stats.is_contiguous()
                                           and adv_stats.numel() == 3):
             raise AssertionError("adv_stats must be a contiguous float64 tensor on %s of 3 entries (advantages(..., stats=True))" % (self.device,))
-        cache = getattr(self, "_pgrad", None)
-        if cache is None:
-            cache = self._pgrad = {}
-        ent = cache.get(id(policy))
-        if ent is None or ent["grad"].max_rows < R:
-            if ent is not None:
-                ent["grad"].close()
-            g = self.vec.make_policy_grad(policy, max(R, n_rows))
-            f32 = dict(dtype=torch.float32, device=self.device)
-            ent = cache[id(policy)] = {"grad": g, "grads": [(torch.zeros((o, i), **f32), torch.zeros((o,), **f32)) for o, i in g.layer_shapes],
-                                       "g_log_std": torch.zeros((policy.n_gaussians,), **f32),
-                                       "stats": torch.zeros((6,), dtype=torch.float64, device=self.device), "rows": {}}
+        ent = self._policy_grad_entry(policy, R, n_rows)
         out = ent["rows"].get(R)
         if out is None:
             out = ent["rows"][R] = (torch.zeros((R,), dtype=torch.float32, device=self.device), torch.zeros((R,), dtype=torch.float32, device=self.device))
@@ -969,6 +995,67 @@ class TorchHubVecEnv(object):
     def optimizer_stats(self, opt):
         """the float64 [4] CUDA stats tensor the last ``optimizer_step(opt)`` wrote (zeros before the first)"""
         return self._into(opt, opt.target, "optimizer_stats")["stats"]
+
+    # ---- a training log and a KL stop on the device (chub_train_log_*, chub_ppo_update): the update as one call, its numbers in one read
+    def make_train_log(self):
+        """The numbers of a PPO update and its KL stop, kept on the device -> DeviceTrainLog (VecChargingHub.make_train_log): what
+        ``ppo_update(..., log=log)`` fills and ``train_log_summary(log)`` reads."""
+        return self.vec.make_train_log()
+
+    def ppo_update(self, rollout, adv, ret, policy_opt, critic_opt, *, epochs, minibatch_rows, key, clip_eps, ent_coef, v_old=None,
+                   loss="ppo_clip", value_loss="clipped", adv_stats=None, target_kl=None, kl="k3", log=None):
+        """A whole PPO update over a ``collect`` rollout, enqueued on torch's current stream by ONE call (chub_ppo_update): `epochs` times a
+        shuffle of the rollout's T * N rows under `key` and policy_opt's step count, and per minibatch of minibatch_rows rows (the last of
+        an epoch takes the remainder) the actor gradient, the critic gradient, the two optimiser steps.  adv, ret [T, N] float32 CUDA
+        (``advantages``), v_old [T, N] under value_loss="clipped"; policy_opt / critic_opt: ``make_optimizer`` of the rollout's policy and of
+        the critic; clip_eps serves both losses.  log: a ``make_train_log`` log -- the update begins it, every minibatch is recorded into
+        it, and with target_kl the update stops stepping at the first minibatch whose approximate KL (kl: "k3", the mean of
+        (ratio - 1) - log ratio, or "k1", the mean of -log ratio) is not <= 1.5 * target_kl: stable-baselines3's rule, factor included.
+        target_kl needs a log.  Nothing is read back; the call may be recorded into a graph, whose replays each begin the log anew.  After
+        a stop the remaining gradient launches still run; their steps are held back."""
+        torch = self.torch
+        policy = getattr(self, "_rollout_policy", {}).get(id(rollout))
+        if policy is None:
+            raise ValueError("rollout: a dict returned by this adapter's collect()")
+        if policy_opt.target is not policy:
+            raise ValueError("ppo_update: policy_opt is not an optimiser of the rollout's policy")
+        critic = critic_opt.target
+        if target_kl is not None and log is None:
+            raise ValueError("ppo_update: target_kl needs log= (the stop is a word of the log)")
+        feats = rollout["features"]
+        n_rows = int(feats.shape[0]) * int(feats.shape[1])
+        per_row = lambda t: t is not None and self._on_device(t) and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n_rows
+        clipped = _lib.value_loss(value_loss) == _lib.VLOSS["clipped"]
+        if not per_row(adv) or not per_row(ret) or (clipped and not per_row(v_old)):
+            raise AssertionError("adv, ret (and v_old under value_loss='clipped') must be contiguous float32 tensors on %s with one entry per "
+                                 "(step, env)" % (self.device,))
+        if adv_stats is not None and not (self._on_device(adv_stats) and adv_stats.dtype == torch.float64 and adv_stats.is_contiguous()
+                                          and adv_stats.numel() == 3):
+            raise AssertionError("adv_stats must be a contiguous float64 tensor on %s of 3 entries (advantages(..., stats=True))" % (self.device,))
+        mb = min(int(minibatch_rows), n_rows)  # (one minibatch per epoch either way)
+        ent = self._policy_grad_entry(policy, n_rows, n_rows)
+        rows_cache = getattr(self, "_ppo_rows", None)
+        if rows_cache is None:
+            rows_cache = self._ppo_rows = {}
+        rows = rows_cache.get(n_rows)
+        if rows is None:
+            rows = rows_cache[n_rows] = torch.zeros((n_rows,), dtype=torch.int64, device=self.device)
+        piles = policy.spec.head == _lib.PHEAD["piles"]
+        sets = rollout.get("set_bits") if piles else None
+        self.vec.ppo_update(ent["grad"], critic, policy_opt, critic_opt, n_rows, feats.data_ptr(), rollout["u"].data_ptr(), rollout["logp"].data_ptr(),
+                            adv.data_ptr(), ret.data_ptr(), rows.data_ptr(), epochs, mb, key, d_pile_bits=rollout["bits"].data_ptr() if piles else 0,
+                            d_set_bits=0 if sets is None else sets.data_ptr(), d_adv_stats=0 if adv_stats is None else adv_stats.data_ptr(),
+                            d_v_old=v_old.data_ptr() if clipped else 0, loss=loss, value_loss=value_loss, clip_eps=clip_eps, value_clip_eps=clip_eps,
+                            ent_coef=ent_coef, kl=kl, kl_limit=0.0 if target_kl is None else 1.5 * float(target_kl), log=log, stream=self._stream())
+        return rows
+
+    def train_log_summary(self, log, kl="k3"):
+        """One synchronising read of `log` -> a dict under stable-baselines3's names.  Over the counted minibatches, weighted by rows:
+        approx_kl (kl: "k3" or "k1"), clip_fraction, entropy, policy_loss, value_loss, value_clip_fraction, explained_variance
+        (1 - E(ret - v)^2 / Var ret from the critic's sums); approx_kl_max, the largest single minibatch's estimate as recorded;
+        n_minibatches; stopped_at (None, or the index of the minibatch that set the stop); and per optimiser, under "policy_opt" and
+        "critic_opt": steps, skipped, held_back, grad_norm_mean, grad_norm_max, clipped_steps."""
+        return train_log_summary(log.read(), kl)
 
     def shuffle_rows(self, R, key, counter=None, offset=0):
         """A permutation of 0 .. R - 1 as an int64 CUDA tensor, on torch's current stream (chub_shuffle_rows_device): a pure function

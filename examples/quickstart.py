@@ -13,7 +13,9 @@
    them at once, member fitness from the episode ledger, the ES gradient from regenerated noise, an SGD step on the centre;
 8. one PPO epoch with the actor's gradient from the device (a torch critic beside it);
 9. one complete PPO iteration in which torch does nothing but the two optimiser steps: collect -> values -> advantages -> minibatches of
-   the actor's and the critic's gradients from the device -> the stepped weights of both networks straight back.
+   the actor's and the critic's gradients from the device -> the stepped weights of both networks straight back;
+10. PPO epochs with no torch optimiser: Adam and the minibatch shuffle on the device, the epoch recorded once and replayed;
+11. three PPO iterations whose update is ONE call with target_kl, and the numbers stable-baselines3 prints read once per iteration.
 """
 import os
 import sys
@@ -401,6 +403,41 @@ def ppo_epochs_on_device(n=4096, steps=64, minibatches=4, epochs=4):
     env.close()
 
 
+def ppo_with_log_and_target_kl(n=4096, steps=64, minibatches=4, epochs=4, iterations=3):
+    import charginghub_env_amd as chub
+
+    if torch is None:
+        print("11. skipped: torch is not installed")
+        return
+    env = chub.TorchHubVecEnv(n, seed=0, autoreset="per_env", **HUB)
+    D, A = env.obs_dim, env.act_dim
+    net = torch.nn.Sequential(torch.nn.Linear(D, 64), torch.nn.Tanh(), torch.nn.Linear(64, A)).to("cuda")
+    vnet = torch.nn.Sequential(torch.nn.Linear(D, 64), torch.nn.Tanh(), torch.nn.Linear(64, 1)).to("cuda")
+    policy = env.load_policy(net)
+    policy.set_exploration(key=7, log_std=[-0.5, -0.5])
+    critic = env.load_critic(vnet)
+    a_opt = env.make_optimizer(policy, lr=3e-4, max_grad_norm=0.5)
+    c_opt = env.make_optimizer(critic, lr=1e-3, max_grad_norm=0.5)
+    log = env.make_train_log()                                 # thirty f64 words and a gate word on the device
+    env.reset()
+    for it in range(iterations):
+        ro = env.collect(policy, steps, logp_piles="decidable")
+        values, final = env.values(critic, ro)
+        adv, ret, adv_stats = env.advantages(ro, values, final, gamma=0.99, lam=0.95, stats=True)
+        v_old = values[:steps].clone()
+        # the whole update in one call: per epoch a shuffle, per minibatch two gradients, the log's record, two steps, the log's steps.
+        # The first minibatch whose approximate KL passes 1.5 * target_kl (stable-baselines3's rule) closes the gate: no later step is taken
+        env.ppo_update(ro, adv, ret, a_opt, c_opt, epochs=epochs, minibatch_rows=steps * n // minibatches, key=11 + it, clip_eps=0.2,
+                       ent_coef=0.01, v_old=v_old, adv_stats=adv_stats, target_kl=0.02, log=log)
+        s = env.train_log_summary(log)                         # the iteration's one read-back
+        print("11. iteration %d: %d minibatches counted%s, approx_kl %.5f (max %.5f), clip_fraction %.3f, entropy %.3f, policy_loss %.4f, "
+              "value_loss %.4f, explained_variance %.3f, actor steps %d (held back %d, clipped %d), grad norm %.3f"
+              % (it, s["n_minibatches"], "" if s["stopped_at"] is None else ", stopped at %d" % s["stopped_at"], s["approx_kl"], s["approx_kl_max"],
+                 s["clip_fraction"], s["entropy"], s["policy_loss"], s["value_loss"], s["explained_variance"], s["policy_opt"]["steps"],
+                 s["policy_opt"]["held_back"], s["policy_opt"]["clipped_steps"], s["policy_opt"]["grad_norm_mean"]))
+    env.close()
+
+
 if __name__ == "__main__":
     single_env()
     batched_host()
@@ -412,3 +449,4 @@ if __name__ == "__main__":
     ppo_on_device_gradients()
     ppo_all_on_device()
     ppo_epochs_on_device()
+    ppo_with_log_and_target_kl()

@@ -1317,6 +1317,8 @@ int chub_critic_grad_device(chub_critic *c, const chub_critic_grad_in *in, const
  *          are never decayed); th = th - (lr / (1 - p1)) * (m32 / denom); theta = (float) th.  1 - beta1 and 1 - beta2 are f64
  *          differences formed once.
  *       6. stats = {t, norm, scale, 0}.
+ *       An optimiser with a gate (chub_adam_set_gate: "a training log and a KL stop on the device", below) whose word is not 0 is HELD
+ *       BACK after 1. exactly as 2. skips it, with stats = {t, norm, 0, 2}.
  *   Launches.  A step is TWO launches, whatever the layer count, on the caller's stream: the first writes the chunks' sums and copies
  *     t, p1, p2 into a "previous" block; in the second every workgroup adds the sums, reads "previous", and lane 0 of workgroup 0 alone
  *     writes the new scalars: a launch never reads what another of its workgroups writes.  Both launches run min(chunks, 64) workgroups
@@ -1373,6 +1375,98 @@ int chub_critic_get_weights(chub_critic *c, int32_t layer, float *W, float *b); 
 int chub_shuffle_rows_device(chub_env *env, uint64_t key, const int64_t *d_counter /* or NULL: 0 */, int64_t offset, int64_t R, int64_t *d_rows /* [R] */,
                              void *stream);
 int chub_shuffle_rows(uint64_t key, uint64_t counter, int64_t R, int64_t *rows);       /* host-only restatement in C, no device */
+
+/* ---- a training log and a KL stop on the device: the numbers of a recorded PPO update, target_kl, the update as one call ------------------
+ * A recorded epoch overwrites the stats blocks of its gradient calls and steps minibatch by minibatch, and nobody is on the host to break
+ * its loop.  A chub_train_log is one block of CHUB_TLOG_WORDS f64 words plus one int64 GATE word in device memory that three small
+ * launches keep: the sums a trainer prints after an update, and the stop that an approximate KL past its limit sets and that the
+ * optimiser steps honour.  It is bound to a handle, destroyed by chub_destroy before the handle, and allocated outside the arena:
+ * chub_state_size and snapshots are unchanged.
+ *   The words (CHUB_TLOG_*): COUNTED minibatches counted; AFTER_STOP minibatches recorded after the stop (they are not counted);
+ *     STOPPED 0 / 1; STOP_INDEX the record call that set the stop, counting the record calls since begin from 0, -1 if none;
+ *     ACTOR + 0 .. 5 the sums of chub_policy_grad_device's stats[0 .. 5] (rows, loss terms, entropies, logp_old - logp_new, rows clipped
+ *     away, ratios); KL_MAX, KL_LAST the largest and the last KL estimate over the counted minibatches (the first counted minibatch sets
+ *     KL_MAX whatever its sign; a NaN never replaces it); CRITIC + 0 .. 5 the sums of chub_critic_grad_device's stats[0 .. 5] (rows, loss
+ *     terms, rows clipped away, (ret - v)^2, ret, ret^2); ACTOR_OPT + 0 .. 5 and CRITIC_OPT + 0 .. 5 per optimiser: steps taken, steps
+ *     skipped by a norm that is not finite, steps held back by the gate, the sum of the norms, the largest norm, steps with scale < 1.
+ *   chub_train_log_begin_device: every word 0, STOP_INDEX -1, the gate 0.
+ *   chub_train_log_record_device runs after the two gradient calls of a minibatch and before its steps, on their stats blocks d_pstats [6]
+ *     and d_cstats [6] (either may be NULL).  With STOPPED set it adds 1 to AFTER_STOP and nothing else.  Otherwise, with n = pstats[0],
+ *     every f64 operation rounded once: CHUB_KL_K1 kl = pstats[3] / n; CHUB_KL_K3 kl = (pstats[5] / n - 1) + pstats[3] / n, the mean of
+ *     (ratio - 1) - log ratio; n == 0 or no d_pstats: kl = 0.  Both blocks are added into ACTOR.. and CRITIC.., one addition per word in
+ *     the order of the record calls; KL_MAX, KL_LAST and COUNTED follow.  With kl_limit > 0 and !(kl <= kl_limit) -- a NaN estimate
+ *     stops -- STOPPED and the gate become 1 and STOP_INDEX the call's index.  The minibatch that sets the stop IS counted and is not
+ *     stepped.  chub_train_log_fold is the same source run on host memory, no device.
+ *   chub_train_log_steps_device runs after the minibatch's steps, on the two stats blocks [4] of chub_adam_step_device (either may be
+ *     NULL).  By stats[3]: 0 taken, 1 skipped, 2 held back.  The norm's sum and maximum take every FINITE norm, whatever became of the
+ *     step; scale < 1 counts taken steps only.  It counts after the stop as before it.
+ *   The gate.  chub_adam_set_gate points an optimiser at an int64 in device memory (NULL clears).  Where that word is not 0 a step
+ *     returns as it does for a norm that is not finite: weights, m, v, t, p1, p2 keep their bits, and stats = {t, norm, 0, 2}; the norm
+ *     launch still runs.  Every workgroup of the step launch reads the word, which only an earlier launch writes.  Without a gate a step
+ *     is what it was.  chub_train_log_destroy clears the gate of every optimiser of the handle that points at the log's.
+ *   Launches.  begin, record and steps are ONE launch of one workgroup each; lane 0 folds (the fold is a chain through thirty words).
+ *     No launch reads a word another of its workgroups writes; no atomics; no allocation, no synchronisation, no tick.  Recordable
+ *     between chub_graph_begin and chub_graph_end (no reset or step of the handle: the count of those is not touched).
+ *     chub_train_log_device gives the addresses of the words and of the gate; chub_train_log_read copies the words to host memory and
+ *     synchronises.
+ *   chub_ppo_update is a host loop over existing calls, as chub_policy_collect is for the rollout; it returns after enqueueing.  With
+ *     M = ceil(n_rows / minibatch_rows) minibatches per epoch, the last of the remainder (chub_ppo_update_plan: host arithmetic only),
+ *     it issues: with a log, begin; per epoch e = 0 .. epochs - 1 chub_shuffle_rows_device(key, the ACTOR optimiser's t, offset e, n_rows)
+ *     into d_rows; per minibatch i on d_rows + i * minibatch_rows: the actor gradient into the actor optimiser's own buffers
+ *     (chub_adam_grads), the critic gradient likewise, record, the actor step, the critic step, steps.  With a log both optimisers have
+ *     the log's gate for the duration of the call (whatever gate they had is theirs again afterwards); without one record, steps and
+ *     begin are left out and the optimisers keep the gate they have.  The four stats blocks are the log's own; without a log each
+ *     optimiser owns a gradient block [6] and a step block [4] (80 bytes beside what chub_adam_plan counts).  d_rows [n_rows] int64 is
+ *     the caller's.  The critic reads the feature rows (d_features, ld_features).
+ * Refusals, all with a message and before any device work.  CHUB_ERR_ARG: a null argument; an unknown kl_kind; kl_limit negative or
+ *     NaN; for chub_ppo_update: epochs < 1; minibatch_rows < 1 or above the gradient object's or the critic's max_rows; a null d_rows;
+ *     objects of different handles; an optimiser whose target is not the given policy / critic; and whatever a constituent call
+ *     refuses, under that call's name.  CHUB_ERR_UNSUPPORTED: create, destroy and read between chub_graph_begin and chub_graph_end.
+ * Out of scope: after a stop the gradient launches of the remaining minibatches still run and are wasted (gating them would need the
+ *     word inside the gradient kernels; the host cannot know of the stop without a read); a log per epoch; the multi-GPU hosts. */
+enum {
+    CHUB_TLOG_COUNTED = 0, CHUB_TLOG_AFTER_STOP = 1, CHUB_TLOG_STOPPED = 2, CHUB_TLOG_STOP_INDEX = 3, CHUB_TLOG_ACTOR = 4,
+    CHUB_TLOG_KL_MAX = 10, CHUB_TLOG_KL_LAST = 11, CHUB_TLOG_CRITIC = 12, CHUB_TLOG_ACTOR_OPT = 18, CHUB_TLOG_CRITIC_OPT = 24,
+    CHUB_TLOG_WORDS = 30
+};
+enum { CHUB_KL_K1 = 0, CHUB_KL_K3, CHUB_KL_COUNT };
+typedef struct chub_train_log chub_train_log;
+typedef struct chub_ppo_update_args {
+    chub_policy_grad *grad;       /* the actor's gradient object (and through it the policy) */
+    chub_critic *critic;
+    chub_adam *actor_opt, *critic_opt;
+    chub_train_log *log;          /* or NULL */
+    int64_t n_rows;               /* rows the per-row arrays hold: all of them are shuffled */
+    const float *d_features;      /* [n_rows][F], row stride ld_features: the actor's and the critic's rows */
+    int64_t ld_features;
+    const uint64_t *d_pile_bits, *d_set_bits;
+    const float *d_u, *d_logp_old, *d_adv;
+    const double *d_adv_stats;    /* [3] or NULL */
+    const float *d_ret, *d_v_old;
+    int32_t policy_loss, value_loss;   /* CHUB_PLOSS_*, CHUB_VLOSS_* */
+    float policy_clip_eps, value_clip_eps, ent_coef;
+    int32_t epochs;
+    int64_t minibatch_rows;
+    uint64_t key;
+    int64_t *d_rows;              /* [n_rows], the caller's */
+    int32_t kl_kind;              /* CHUB_KL_* */
+    int32_t pad_;
+    double kl_limit;              /* 0: never stops */
+} chub_ppo_update_args;
+int chub_train_log_create(chub_env *env, chub_train_log **out);
+int chub_train_log_destroy(chub_train_log *log);
+int chub_train_log_begin_device(chub_train_log *log, void *stream);
+int chub_train_log_record_device(chub_train_log *log, const double *d_pstats /* [6] or NULL */, const double *d_cstats /* [6] or NULL */, int32_t kl_kind,
+                                 double kl_limit, void *stream);
+int chub_train_log_steps_device(chub_train_log *log, const double *d_astats_actor /* [4] or NULL */, const double *d_astats_critic /* [4] or NULL */,
+                                void *stream);
+int chub_train_log_device(chub_train_log *log, const double **d_words, const int64_t **d_gate);
+int chub_train_log_read(chub_train_log *log, double *words /* [CHUB_TLOG_WORDS] */);   /* host; synchronises */
+int chub_train_log_fold(double *words, int64_t *gate, const double *pstats, const double *cstats, int32_t kl_kind,
+                        double kl_limit);                                              /* host-only: the record step, no device */
+int chub_adam_set_gate(chub_adam *a, const int64_t *d_gate /* or NULL: none */);
+int chub_ppo_update_plan(int64_t n_rows, int64_t minibatch_rows, int64_t *minibatches, int64_t *last_rows);  /* host-only */
+int chub_ppo_update(const chub_ppo_update_args *args, void *stream);
 
 /* The FCEV waiting list is unbounded as in the reference (HYD:264-265): the entries a list that still gets served can
  * hold are kept one by one, and once no prefix of it fits into 15 minutes any more (HYD:270-276: nobody is served again

@@ -33,6 +33,10 @@
                   the parent's way (torch.randperm outside), epoch_device_mb<R> eagerly with the device shuffle and steps,
                   epoch_graph_mb<R> the same chain recorded once and replayed; shuffle / shuffle_torch: chub_shuffle_rows_device against
                   torch.randperm over the rollout's rows.  us per update, ms per epoch, us per shuffle, between two events.
+  --trainlog      a case of its own beside --adam's (the same rollout, nets and optimisers): the whole epoch at minibatches of 4096 and of
+                  65 536 rows as ONE chub_ppo_update -- epoch_update_mb<R> without a log, epoch_update_log_mb<R> with one (two more launches per
+                  minibatch, one more per update) -- each eagerly and as one captured graph replayed (.._graph_..), and beside them
+                  --adam's epoch_device_mb<R> / epoch_graph_mb<R>, the same chain issued call by call from Python.  ms per epoch.
 Every case is warmed up, then the cases alternate, ROUNDS times; median, best and worst round are reported with the build id.
 --open-loop-only measures the open loop alone, --launch-only the open loop and the deterministic launch, --no-sets the first five cases:
 with CHUB_LIB=<another build's libchub.so> those are the rates of a build without the newer entry points (the parent commit), on the same
@@ -48,7 +52,7 @@ import time
 
 import numpy as np
 
-if "--torch-gae" in sys.argv or "--torch-grad" in sys.argv or "--torch-critic" in sys.argv or "--adam" in sys.argv:
+if "--torch-gae" in sys.argv or "--torch-grad" in sys.argv or "--torch-critic" in sys.argv or "--adam" in sys.argv or "--trainlog" in sys.argv:
     import torch  # before libchub is loaded: both must share one HIP runtime
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -74,10 +78,13 @@ def main():
     ap.add_argument("--critic", action="store_true", help="the actor-gradient cases and the critic's, in one process")
     ap.add_argument("--torch-critic", action="store_true")
     ap.add_argument("--adam", action="store_true", help="the optimiser's cases alone (see the module's text)")
+    ap.add_argument("--trainlog", action="store_true", help="one chub_ppo_update per epoch, with and without a training log (see the module's text)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     if args.adam:
         return adam_cases(args)
+    if args.trainlog:
+        return trainlog_cases(args)
     n_s, piles_s = args.shape.split("x")
     n, piles = int(n_s), [int(x) for x in piles_s.split(",")]
     hidden = [int(x) for x in args.hidden.split(",") if x]
@@ -661,6 +668,103 @@ def adam_cases(args):
                          unit=unit, rounds=len(xs), median=round(statistics.median(xs), 3), min=round(min(xs), 3), max=round(max(xs), 3), build_id=build_id))
     for kind, why in failed.items():
         rows.append(dict(shape=args.shape, kind=kind, unit="NOT MEASURED", error=why, build_id=build_id))
+    for row in rows:
+        print(json.dumps(row), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+        json.dump(rows, open(args.out, "w"), indent=1)
+    torch.cuda.synchronize()
+    env.close()
+
+
+def trainlog_cases(args):
+    """--trainlog: the epoch as one chub_ppo_update, with and without a log, eager and replayed, beside --adam's call-by-call epoch"""
+    n_s, piles_s = args.shape.split("x")
+    n, piles = int(n_s), [int(x) for x in piles_s.split(",")]
+    hidden = [int(x) for x in args.hidden.split(",") if x]
+    T = 96
+    env = chub.TorchHubVecEnv(n, piles, ["fast", "slow"], seed=1, rng="philox", autoreset="per_env", hydro_prod_rate=100.0, hydro_store_vlt=25.0,
+                              init_soc=0.2, fc_max_power=100.0, fcev_permeate=0.01)
+    build_id = chub.load_library().chub_build_id().decode()
+    D, A = env.obs_dim, env.act_dim
+    side = torch.cuda.Stream()
+    torch.cuda.set_stream(side)  # (a created stream: a recording needs one)
+
+    def mlp(sizes):
+        mods = []
+        for i, o in zip(sizes[:-1], sizes[1:]):
+            mods += [torch.nn.Linear(i, o), torch.nn.Tanh()]
+        return torch.nn.Sequential(*mods[:-1]).to("cuda")
+
+    torch.manual_seed(0)
+    pol = env.load_policy(mlp([D] + hidden + [A]))
+    pol.set_exploration(7, [-0.5, -0.5])
+    crit = env.load_critic(mlp([D] + hidden + [1]))
+    a_opt, c_opt = env.make_optimizer(pol, lr=3e-4), env.make_optimizer(crit, lr=1e-3)
+    log = env.make_train_log()
+    env.reset()
+    ro = env.collect(pol, T, logp_piles="decidable")
+    values, final = env.values(crit, ro)
+    adv, ret, adv_stats = env.advantages(ro, values, final, stats=True)
+    v_old = values[:T].clone()
+    R = T * n
+
+    def epoch_calls(mb):  # (--adam's epoch_device: the chain issued call by call)
+        rows = env.shuffle_rows(R, 11, counter=a_opt)
+        for i in range(R // mb):
+            r = rows[i * mb:(i + 1) * mb]
+            env.policy_gradient(ro, adv, rows=r, adv_stats=adv_stats, into=a_opt)
+            env.value_gradient(crit, ro, ret, rows=r, loss="clipped", v_old=v_old, into=c_opt)
+            env.optimizer_step(a_opt)
+            env.optimizer_step(c_opt)
+
+    def epoch_update(mb, with_log):
+        env.ppo_update(ro, adv, ret, a_opt, c_opt, epochs=1, minibatch_rows=mb, key=11, clip_eps=0.2, ent_coef=0.0, v_old=v_old, adv_stats=adv_stats,
+                       log=log if with_log else None)
+
+    def timed(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / reps  # ms
+
+    cases, failed = {}, {}
+    for mb in (4096, 65536):
+        if R % mb:
+            continue
+        routes = {"epoch_device": ("the calls one by one from Python", lambda mb=mb: epoch_calls(mb)),
+                  "epoch_update": ("one chub_ppo_update, no log", lambda mb=mb: epoch_update(mb, False)),
+                  "epoch_update_log": ("one chub_ppo_update with a log", lambda mb=mb: epoch_update(mb, True))}
+        for name, (route, fn) in routes.items():
+            cases[("%s_mb%d" % (name, mb), "eager, " + route, "ms_per_epoch")] = lambda fn=fn: timed(fn, 1)
+            fn()  # (every tensor the calls cache exists before the recording)
+            torch.cuda.synchronize()
+            kind = "%s_mb%d" % (name.replace("epoch_device", "epoch_graph").replace("epoch_update", "epoch_update_graph"), mb)
+            try:
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, stream=side):
+                    fn()
+                cases[(kind, "one captured graph replayed, " + route, "ms_per_epoch")] = lambda graph=graph: timed(graph.replay, 1)
+            except Exception as e:  # the row then says so: NOT MEASURED
+                failed[kind] = repr(e)[:300]
+    for fn in cases.values():
+        fn()
+    vals = {c: [] for c in cases}
+    for _ in range(args.rounds):
+        for c, fn in cases.items():
+            vals[c].append(fn())
+    summary = env.train_log_summary(log)
+    rows = []
+    for (kind, route, unit), xs in vals.items():
+        rows.append(dict(shape=args.shape, n_envs=n, piles=piles, T=T, rows=R, actor=[D] + hidden + [A], critic=[D] + hidden + [1], kind=kind, route=route,
+                         unit=unit, rounds=len(xs), median=round(statistics.median(xs), 3), min=round(min(xs), 3), max=round(max(xs), 3), build_id=build_id))
+    for kind, why in failed.items():
+        rows.append(dict(shape=args.shape, kind=kind, unit="NOT MEASURED", error=why, build_id=build_id))
+    rows.append(dict(shape=args.shape, kind="last_log", summary=summary, build_id=build_id))
     for row in rows:
         print(json.dumps(row), flush=True)
     if args.out:
