@@ -142,17 +142,19 @@ FC_MAX = np.array([config_kwargs(config_of(i))["fc_max_power"] for i in range(N)
 
 
 class Trajectory(object):
-    """what the oracle leaves after every call of the script; steps are numbered over the whole run (PLAN[0] + PLAN[1])"""
+    """what the oracle leaves after every call of a script; steps are numbered over the whole run (sum(plan)).  The defaults are this
+    population's: N envs of HUB through PLAN."""
 
-    def __init__(self, steps):
-        self.reset_obs = np.zeros((len(PLAN), N, D))
-        self.reset_scalars = np.zeros((len(PLAN), N, 2, 8))
-        self.slots = [np.zeros((steps, N, 9, HUB["station_list"][k]), dtype=np.float32) for k in (0, 1)]
-        self.scalars = np.zeros((steps, N, 2, 8))
-        self.tel = np.zeros((steps, N, T_COUNT))
-        self.obs = np.zeros((steps, N, D))
-        self.reward = np.zeros((steps, N))
-        self.done = np.zeros((steps, N), dtype=bool)
+    def __init__(self, steps, n=N, piles=None, d=D, episodes=len(PLAN)):
+        piles = HUB["station_list"] if piles is None else piles
+        self.reset_obs = np.zeros((episodes, n, d))
+        self.reset_scalars = np.zeros((episodes, n, 2, 8))
+        self.slots = [np.zeros((steps, n, 9, piles[k]), dtype=np.float32) for k in (0, 1)]
+        self.scalars = np.zeros((steps, n, 2, 8))
+        self.tel = np.zeros((steps, n, T_COUNT))
+        self.obs = np.zeros((steps, n, d))
+        self.reward = np.zeros((steps, n))
+        self.done = np.zeros((steps, n), dtype=bool)
         self.q_overflow = 0
         self.flags = None
 
@@ -161,65 +163,72 @@ class Trajectory(object):
             a.setflags(write=False)
 
 
-def step_plan():
+def step_plan(plan=PLAN):
     """[(episode, step of the episode, step of the run)]"""
     out, i = [], 0
-    for ep, steps in enumerate(PLAN):
+    for ep, steps in enumerate(plan):
         for t in range(steps):
             out.append((ep, t, i))
             i += 1
     return out
 
 
-@functools.lru_cache(maxsize=None)
-def oracle_trajectory():
-    """Six oracle vecs (PHILOX back-end, 16 envs each at ENV_ID0 + 16 k) through reset + 96 steps + reset + 40 steps of the script.
-    Computed once per process and left unchanged."""
+def run_oracle(cfgs, batches, plan, block, env_id0, seed, fc_max):
+    """One oracle vec per entry of cfgs ([(name, hub shape + the eight scalars)], PHILOX back-end, `block` envs each at env_id0 + block * k)
+    through reset + plan[0] steps, reset + plan[1] steps, ...; step i of the run takes batches[i % len(batches)] ([.., block * len(cfgs), A]
+    f32).  Returns the frozen Trajectory, its flags classified with fc_max ([n])."""
     vecs = []
-    for k, (name, kw) in enumerate(configs()):
+    for k, (name, kw) in enumerate(cfgs):
         cfg = orclib.make_config(piles=kw["station_list"], types=kw["station_type_list"],
                                  **{f: kw[f] for f in kw if f not in ("station_list", "station_type_list")})
-        h = orc.orc_vec_create(C.byref(cfg), orclib.tables(), BLOCK, ENV_ID0 + BLOCK * k, orclib.PHILOX, SEED)
+        h = orc.orc_vec_create(C.byref(cfg), orclib.tables(), block, env_id0 + block * k, orclib.PHILOX, seed)
         assert h
         vecs.append((cfg, h))
-    tr = Trajectory(sum(PLAN))
-    o_obs, o_rew, o_done = np.zeros((BLOCK, D)), np.zeros(BLOCK), np.zeros(BLOCK, dtype=np.uint8)
+    piles = list(cfgs[0][1]["station_list"])
+    assert all(list(kw["station_list"]) == piles for _, kw in cfgs)
+    n, d, s = block * len(cfgs), orc.orc_env_obs_dim(C.byref(vecs[0][0])), sum(piles)
+    assert batches.shape[1:] == (n, s + 2) and batches.dtype == np.float32
+    tr = Trajectory(sum(plan), n, piles, d, len(plan))
+    o_obs, o_rew, o_done = np.zeros((block, d)), np.zeros(block), np.zeros(block, dtype=np.uint8)
 
     def records(dst_scalars):
         for k, (_, h) in enumerate(vecs):
-            for e in range(BLOCK):
-                env = orc.orc_vec_env(h, e)
-                for s in (0, 1):
-                    orc.orc_station_scalars(orc.orc_env_station(env, s), ptr(dst_scalars[k * BLOCK + e, s]))
-                tr.q_overflow += orc.orc_env_q_overflow(env)
+            orc.orc_vec_station_scalars(h, ptr(dst_scalars[k * block:(k + 1) * block]))
+            for e in range(block):
+                tr.q_overflow += orc.orc_env_q_overflow(orc.orc_vec_env(h, e))
 
     i = 0
-    for ep, steps in enumerate(PLAN):
+    for ep, steps in enumerate(plan):
         for k, (_, h) in enumerate(vecs):
             orc.orc_vec_reset(h, None, None, ptr(o_obs))
-            tr.reset_obs[ep, k * BLOCK:(k + 1) * BLOCK] = o_obs
+            tr.reset_obs[ep, k * block:(k + 1) * block] = o_obs
         records(tr.reset_scalars[ep])
         for t in range(steps):
-            act = actions(i)
+            act = batches[i % len(batches)]
             for k, (_, h) in enumerate(vecs):
-                sel = slice(k * BLOCK, (k + 1) * BLOCK)
+                sel = slice(k * block, (k + 1) * block)
                 a = np.ascontiguousarray(act[sel])
                 orc.orc_vec_step(h, ptr(a), None, ptr(o_obs), ptr(o_rew), ptr(o_done), 1)
                 tr.obs[i, sel], tr.reward[i, sel], tr.done[i, sel] = o_obs, o_rew, o_done.astype(bool)
-                for e in range(BLOCK):
-                    env = orc.orc_vec_env(h, e)
-                    for s in (0, 1):
-                        orc.orc_station_slots(orc.orc_env_station(env, s), ptr(tr.slots[s][i, k * BLOCK + e]))
-                    orc.orc_env_telemetry(env, ptr(tr.tel[i, k * BLOCK + e]))
+                for st in (0, 1):
+                    orc.orc_vec_slots(h, st, ptr(tr.slots[st][i, sel]))
+                orc.orc_vec_telemetry(h, ptr(tr.tel[i, sel]))
             records(tr.scalars[i])
             i += 1
     for _, h in vecs:
         orc.orc_vec_destroy(h)
-    a_el = np.stack([actions(j)[:, S] for j in range(i)])
-    a_fc = np.stack([actions(j)[:, S + 1] for j in range(i)])
-    tr.flags = classify(tr.tel, a_el, a_fc, FC_MAX[None, :])
+    a_el = np.stack([batches[j % len(batches)][:, s] for j in range(i)])
+    a_fc = np.stack([batches[j % len(batches)][:, s + 1] for j in range(i)])
+    tr.flags = classify(tr.tel, a_el, a_fc, np.asarray(fc_max)[None, :])
     tr.freeze()
     return tr
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_trajectory():
+    """Six oracle vecs (PHILOX back-end, 16 envs each at ENV_ID0 + 16 k) through reset + 96 steps + reset + 40 steps of the script.
+    Computed once per process and left unchanged."""
+    return run_oracle(configs(), action_batches(), PLAN, BLOCK, ENV_ID0, SEED, FC_MAX)
 
 
 def branch_counts(tr=None):
