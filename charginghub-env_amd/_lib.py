@@ -330,6 +330,30 @@ class ChubPpoUpdateArgs(C.Structure):
                 ("kl_limit", C.c_double)]
 
 
+# constrained PPO on the device (chub_lagrange_*): the CHUB_COST_* and CHUB_LAG_* enums of include/chub.h
+COST_KIND_NAMES = ("step", "done")
+COST_KIND = {name: i for i, name in enumerate(COST_KIND_NAMES)}
+LAG_MAX_K, LAG_STATS, LAG_WORDS = 4, 6, 3
+
+
+def cost_kind(kind):
+    """a cost kind as its CHUB_COST_* value: a name of COST_KIND_NAMES, or the value itself (the library refuses an unknown one)"""
+    return _enum_value(COST_KIND, kind, "cost kind")
+
+
+class ChubConstraint(C.Structure):
+    """chub_constraint of include/chub.h"""
+    _fields_ = [("column", C.c_int32), ("kind", C.c_int32), ("limit", C.c_double), ("lr", C.c_double), ("lambda0", C.c_double),
+                ("lambda_max", C.c_double)]
+
+
+class ChubCostGae(C.Structure):
+    """chub_cost_gae of include/chub.h: device addresses, 0 / None = not given"""
+    _fields_ = [("T", C.c_int64), ("C", C.c_int32), ("pad_", C.c_int32), ("d_terms", C.c_void_p), ("d_packed", C.c_void_p),
+                ("d_values", C.c_void_p * 4), ("d_final_values", C.c_void_p * 4), ("d_mask", C.c_void_p), ("gamma", C.c_float),
+                ("lam", C.c_float), ("d_adv", C.c_void_p * 4), ("d_ret", C.c_void_p * 4), ("d_ep_carry", C.c_void_p)]
+
+
 # pile sets (chub_pile_set_device): the CHUB_PSET_* enum of include/chub.h, in order
 PSET_NAMES = ("all", "occupied", "decidable")
 PSET = {name: i for i, name in enumerate(PSET_NAMES)}
@@ -434,8 +458,8 @@ def source_hash():
 
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
-    for name in ("chub_kernels.hip", "chub_policy.hip", "chub_critic.hip", "chub_adam.hip", "chub_trainlog.hip", "chub_runtime.cpp", "chub_comm.cpp", "chub_device.h", "chub_curves.h",
-                 "chub_plan.h", "chub_policy.h", "chub_critic.h", "chub_adam.h", "chub_trainlog.h"):
+    for name in ("chub_kernels.hip", "chub_policy.hip", "chub_critic.hip", "chub_adam.hip", "chub_trainlog.hip", "chub_lagrange.hip", "chub_runtime.cpp", "chub_comm.cpp", "chub_device.h", "chub_curves.h",
+                 "chub_plan.h", "chub_policy.h", "chub_critic.h", "chub_adam.h", "chub_trainlog.h", "chub_lagrange.h"):
         h.update(open(os.path.join(csrc, name), "rb").read())
     h.update(open(os.path.join(os.path.dirname(_HERE), "include", "chub.h"), "rb").read())
     return h.hexdigest()[:16]
@@ -576,6 +600,14 @@ def load_library():
         "chub_train_log_device": (I, [P, C.POINTER(P), C.POINTER(P)]), "chub_train_log_read": (I, [P, P]),
         "chub_train_log_fold": (I, [P, P, P, P, C.c_int32, C.c_double]), "chub_adam_set_gate": (I, [P, P]),
         "chub_ppo_update_plan": (I, [L, L, C.POINTER(L), C.POINTER(L)]), "chub_ppo_update": (I, [C.POINTER(ChubPpoUpdateArgs), P]),
+        "chub_policy_collect_terms": (I, [P, P, I, I, C.POINTER(ChubRollout), P, P, L, C.c_uint32, P, P]),
+        "chub_lagrange_create": (I, [P, C.c_int32, C.POINTER(ChubConstraint), C.POINTER(P)]), "chub_lagrange_destroy": (I, [P]),
+        "chub_lagrange_gae_device": (I, [P, C.POINTER(ChubCostGae), P]), "chub_lagrange_step_device": (I, [P, P]),
+        "chub_lagrange_combine_device": (I, [P, L, P, P, C.POINTER(P), P, P]),
+        "chub_lagrange_device": (I, [P, C.POINTER(P), C.POINTER(P)]), "chub_lagrange_read": (I, [P, P, P, P]),
+        "chub_lagrange_set_lambda_device": (I, [P, P, P]), "chub_lagrange_state_size": (I, [P, C.POINTER(L)]),
+        "chub_lagrange_get_state": (I, [P, P]), "chub_lagrange_set_state": (I, [P, P]),
+        "chub_lagrange_fold": (I, [C.POINTER(ChubConstraint), P, P, P]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -631,7 +663,10 @@ EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "ch
             "chub_shuffle_rows_device", "chub_shuffle_rows",
             "chub_train_log_create", "chub_train_log_destroy", "chub_train_log_begin_device", "chub_train_log_record_device",
             "chub_train_log_steps_device", "chub_train_log_device", "chub_train_log_read", "chub_train_log_fold", "chub_adam_set_gate",
-            "chub_ppo_update_plan", "chub_ppo_update"]
+            "chub_ppo_update_plan", "chub_ppo_update",
+            "chub_policy_collect_terms", "chub_lagrange_create", "chub_lagrange_destroy", "chub_lagrange_gae_device", "chub_lagrange_step_device",
+            "chub_lagrange_combine_device", "chub_lagrange_device", "chub_lagrange_read", "chub_lagrange_set_lambda_device",
+            "chub_lagrange_state_size", "chub_lagrange_get_state", "chub_lagrange_set_state", "chub_lagrange_fold"]
 
 
 def check(rc):

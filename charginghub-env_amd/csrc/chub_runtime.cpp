@@ -21,6 +21,7 @@
 #include "chub_critic.h"
 #include "chub_adam.h"
 #include "chub_trainlog.h"
+#include "chub_lagrange.h"
 
 namespace chub {
 template <bool RESET>
@@ -190,6 +191,8 @@ struct chub_env {
     std::vector<chub_critic *> critics;
     // the training logs made for this handle (chub_train_log_create): destroyed before it, words, gate and stats blocks outside the arena
     std::vector<chub_train_log *> train_logs;
+    // the constraint objects made for this handle (chub_lagrange_create): destroyed before it, multipliers, stats and partials outside the arena
+    std::vector<chub_lagrange *> lagranges;
     // chub_rollout_gae_device's statistics: the workgroups' partials [ceil(N / 256)][3] f64, allocated at create outside the arena (derived
     // scratch: no snapshot carries it).  One buffer: calls that ask for d_stats must be ordered against each other
     double *d_gae_part = nullptr;
@@ -1092,9 +1095,11 @@ static void policy_free(chub_policy *pol);
 static void moments_free(chub_moments *m);
 static void critic_free(chub_critic *c);
 static void train_log_free(chub_train_log *log);
+static void lagrange_free(chub_lagrange *lag);
 
 int chub_destroy(chub_env *e) {
     if (!e) return CHUB_OK;
+    while (!e->lagranges.empty()) lagrange_free(e->lagranges.back());
     while (!e->train_logs.empty()) train_log_free(e->train_logs.back());  // (first: it clears the gates of optimisers that still live)
     while (!e->moments.empty()) moments_free(e->moments.back());  // (each takes itself off the list)
     while (!e->policies.empty()) policy_free(e->policies.back());
@@ -4277,7 +4282,7 @@ int chub_policy_sample_set_device(chub_env *e, chub_policy *pol, const float *d_
 // The closed loop that keeps what a trainer needs: a host loop of the calls the header lists, like chub_policy_run_steps.  which < 0:
 // chub_policy_collect; else chub_policy_collect_set, whose step t also leaves its pile set in d_set_bits[t]
 static int policy_collect(chub_env *e, chub_policy *pol, int mode, int which, const chub_rollout *r, uint64_t *d_set_bits, float *d_obs0,
-                          int64_t first_step, void *stream) {
+                          int64_t first_step, void *stream, uint32_t fields = 0u, float *d_terms = nullptr) {
     if (!e || !pol || !r || !d_obs0 || (which >= 0 && !d_set_bits)) return fail(CHUB_ERR_ARG, "null argument");
     if (pol->net.env != e) return fail(CHUB_ERR_ARG, "this policy was made for another handle");
     if (mode != CHUB_PRUN_LOCKSTEP && mode != CHUB_PRUN_AUTORESET) return fail(CHUB_ERR_ARG, "mode: CHUB_PRUN_LOCKSTEP or CHUB_PRUN_AUTORESET");
@@ -4301,8 +4306,23 @@ static int policy_collect(chub_env *e, chub_policy *pol, int mode, int which, co
     const size_t N = (size_t) e->hp.n_envs, D = (size_t) e->hp.obs_dim, Wd = (size_t) ((e->hp.S[0] + e->hp.S[1] + 63) / 64);
     int rc;
     if (mode == CHUB_PRUN_LOCKSTEP && first_step % 96 == 0 && (rc = chub_reset_device(e, nullptr, nullptr, d_obs0, stream))) return rc;
+    // chub_policy_collect_terms: step t's terms go to block t of d_terms; the handle's own attachment is in force again on every way out
+    struct TermsGuard {
+        chub_env *e;
+        float *out;
+        uint32_t fields;
+        ~TermsGuard() {
+            e->st_out = out;
+            e->st_fields = fields;
+        }
+    } guard = {e, e->st_out, e->st_fields};
+    const size_t Ct = d_terms ? (size_t) __builtin_popcount(fields) : 0;
     for (int64_t t = 0; t < r->T; t++) {
         const size_t k = (size_t) t;
+        if (d_terms) {
+            e->st_out = d_terms + k * N * Ct;
+            e->st_fields = fields;
+        }
         const float *obs = t ? r->d_packed + (k - 1) * N * (D + 2) : d_obs0;
         const int64_t ld = t ? (int64_t) D + 2 : (int64_t) D;
         float *packed = r->d_packed + k * N * (D + 2);
@@ -4330,6 +4350,16 @@ int chub_policy_collect_set(chub_env *e, chub_policy *pol, int mode, int which, 
     if (which < 0 || which >= CHUB_PSET_COUNT)
         return fail(CHUB_ERR_ARG, "chub_policy_collect_set: which is CHUB_PSET_ALL, CHUB_PSET_OCCUPIED or CHUB_PSET_DECIDABLE");
     return policy_collect(e, pol, mode, which, r, d_set_bits, d_obs0, first_step, stream);
+}
+
+// chub_policy_collect(_set) that keeps every step's terms (include/chub.h, "constrained PPO on the device"): policy_collect is the loop; the
+// step forms read e->st_out / e->st_fields when they enqueue, so the per-step destination is a launch argument and nothing is attached
+int chub_policy_collect_terms(chub_env *e, chub_policy *pol, int mode, int which, const chub_rollout *r, uint64_t *d_set_bits, float *d_obs0,
+                              int64_t first_step, uint32_t fields, float *d_terms, void *stream) {
+    if (const int rc = check_step_terms(e, fields, d_terms)) return rc;
+    if (which >= CHUB_PSET_COUNT)
+        return fail(CHUB_ERR_ARG, "chub_policy_collect_terms: which is negative (chub_policy_collect), CHUB_PSET_ALL, CHUB_PSET_OCCUPIED or CHUB_PSET_DECIDABLE");
+    return policy_collect(e, pol, mode, which < 0 ? -1 : which, r, d_set_bits, d_obs0, first_step, stream, fields, d_terms);
 }
 
 // ---- advantages (include/chub.h, chub_rollout_gae_device): the env supplies N and D and the partials of the statistics, nothing else
@@ -5827,6 +5857,237 @@ int chub_ppo_update(const chub_ppo_update_args *u, void *stream) {
     u->actor_opt->args.gate = gate_a;
     u->critic_opt->args.gate = gate_c;
     return rc;
+}
+
+}  // extern "C"
+
+// ---- constrained PPO on the device (include/chub.h): the object, the three device calls, the state calls, the host fold.  The kernels are
+// chub_lagrange.hip's, the step rule's arithmetic chub_lagrange.h's
+static_assert((int) CHUB_COST_STEP == COST_STEP && (int) CHUB_COST_AT_DONE == COST_AT_DONE && (int) CHUB_COST_KIND_COUNT == COST_KIND_COUNT &&
+                  (int) CHUB_LAG_MAX_K == kLagMaxK && (int) CHUB_LAG_STATS == kLagStats && (int) CHUB_LAG_WORDS == kLagWords,
+              "chub_lagrange.h restates the CHUB_COST_* / CHUB_LAG_* enums");
+
+struct chub_lagrange {
+    chub_env *env;
+    int32_t K;
+    chub_constraint c[kLagMaxK];
+    double *d_block;     // lambda [K], the stats [K][6], the words [K][3]
+    double *d_lambda, *d_stats, *d_words;
+    double *d_partials;  // [ceil(N / 256)][K][6]
+    DeviceAllocs allocs;
+};
+
+static void lagrange_free(chub_lagrange *lag) {
+    chub_env *e = lag->env;
+    (void) hipSetDevice(e->device);
+    (void) hipDeviceSynchronize();  // (a launch still in flight reads and writes the block)
+    lag->allocs.free_all();
+    e->lagranges.erase(std::remove(e->lagranges.begin(), e->lagranges.end(), lag), e->lagranges.end());
+    delete lag;
+}
+
+static int lagrange_check_constraint(const char *who, const chub_constraint &c) {
+    const std::string w(who);
+    if (c.column < 0) return fail(CHUB_ERR_ARG, w + ": a constraint's column is at least 0");
+    if (c.kind != CHUB_COST_STEP && c.kind != CHUB_COST_AT_DONE) return fail(CHUB_ERR_ARG, w + ": kind: CHUB_COST_STEP or CHUB_COST_AT_DONE");
+    const double v[4] = {c.limit, c.lr, c.lambda0, c.lambda_max};
+    for (double x : v)
+        if (!(x >= 0.0) || !__builtin_isfinite(x)) return fail(CHUB_ERR_ARG, w + ": limit, lr, lambda0 and lambda_max are finite and not negative");
+    if (c.lambda_max != 0.0 && c.lambda0 > c.lambda_max) return fail(CHUB_ERR_ARG, w + ": lambda0 lies at or below a non-zero lambda_max");
+    return CHUB_OK;
+}
+
+extern "C" {
+
+int chub_lagrange_create(chub_env *e, int32_t K, const chub_constraint *c, chub_lagrange **out) {
+    if (!e || !c || !out) return fail(CHUB_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (K < 1 || K > kLagMaxK) return fail(CHUB_ERR_ARG, "chub_lagrange_create: K is 1 .. 4 constraints");
+    for (int32_t k = 0; k < K; k++)
+        if (const int rc = lagrange_check_constraint("chub_lagrange_create", c[k])) return rc;
+    if (e->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_lagrange_create between chub_graph_begin and chub_graph_end (it allocates and synchronises)");
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    chub_lagrange *lag = new chub_lagrange();
+    lag->env = e;
+    lag->K = K;
+    for (int32_t k = 0; k < K; k++) lag->c[k] = c[k];
+    e->lagranges.push_back(lag);
+    const size_t words = (size_t) K * (1 + kLagStats + kLagWords);
+    const size_t blocks = ((size_t) e->hp.n_envs + kLagLanes - 1) / kLagLanes;
+    double h[kLagMaxK] = {0.0};
+    for (int32_t k = 0; k < K; k++) h[k] = c[k].lambda0;
+    if (lag->allocs.zeroed(&lag->d_block, words) || lag->allocs.zeroed(&lag->d_partials, blocks * (size_t) K * kLagStats) ||
+        hipMemcpy(lag->d_block, h, (size_t) K * sizeof(double), hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        lagrange_free(lag);
+        (void) hipGetLastError();
+        return fail(CHUB_ERR_HIP, "chub_lagrange_create: out of device memory");
+    }
+    lag->d_lambda = lag->d_block;
+    lag->d_stats = lag->d_lambda + K;
+    lag->d_words = lag->d_stats + (size_t) K * kLagStats;
+    *out = lag;
+    return CHUB_OK;
+}
+
+int chub_lagrange_destroy(chub_lagrange *lag) {
+    if (!lag) return CHUB_OK;
+    if (lag->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_lagrange_destroy between chub_graph_begin and chub_graph_end (it synchronises and frees)");
+    lagrange_free(lag);
+    (void) hipGetLastError();
+    return CHUB_OK;
+}
+
+int chub_lagrange_gae_device(chub_lagrange *lag, const chub_cost_gae *g, void *stream) {
+    if (!lag || !g) return fail(CHUB_ERR_ARG, "null argument");
+    if (!g->d_terms || !g->d_packed) return fail(CHUB_ERR_ARG, "chub_lagrange_gae_device: d_terms and d_packed are required");
+    if (g->T <= 0) return fail(CHUB_ERR_ARG, "chub_lagrange_gae_device: T >= 1");
+    if (g->C < 1) return fail(CHUB_ERR_ARG, "chub_lagrange_gae_device: C >= 1 floats in a d_terms row");
+    if (!(g->gamma >= 0.0f && g->gamma <= 1.0f) || !(g->lambda >= 0.0f && g->lambda <= 1.0f))
+        return fail(CHUB_ERR_ARG, "chub_lagrange_gae_device: gamma and lambda lie in [0, 1]");
+    for (int32_t k = 0; k < lag->K; k++) {
+        if (lag->c[k].column >= g->C) return fail(CHUB_ERR_ARG, "chub_lagrange_gae_device: a constraint's column lies outside 0 .. C - 1");
+        if (!g->d_adv[k]) return fail(CHUB_ERR_ARG, "chub_lagrange_gae_device: d_adv[k] is required for every constraint");
+    }
+    const chub_env *e = lag->env;
+    if ((uint64_t) e->hp.n_envs * (uint64_t) std::max(e->hp.obs_dim + 2, g->C) * sizeof(float) > 0xffffffffull)
+        return fail(CHUB_ERR_UNSUPPORTED, "chub_lagrange_gae_device: one step's block of d_packed or d_terms is at most 4 GiB (the kernel's offsets are 32 bits)");
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    CostGaeArgs a = {};
+    a.n_envs = e->hp.n_envs;
+    a.T = g->T;
+    a.D = e->hp.obs_dim;
+    a.C = g->C;
+    a.K = lag->K;
+    a.gamma = g->gamma;
+    a.gl = g->gamma * g->lambda;
+    a.terms = g->d_terms;
+    a.packed = g->d_packed;
+    a.mask = g->d_mask;
+    a.carry = g->d_ep_carry;
+    a.partials = lag->d_partials;
+    a.stats = lag->d_stats;
+    for (int32_t k = 0; k < lag->K; k++) {
+        a.values[k] = g->d_values[k];
+        a.final_values[k] = g->d_final_values[k];
+        a.adv[k] = g->d_adv[k];
+        a.ret[k] = g->d_ret[k];
+        a.column[k] = lag->c[k].column;
+        a.kind[k] = lag->c[k].kind;
+    }
+    launch_cost_gae(a, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_lagrange_step_device(chub_lagrange *lag, void *stream) {
+    if (!lag) return fail(CHUB_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(lag->env->device));
+    (void) hipGetLastError();
+    LagrangeStepArgs a = {};
+    a.K = lag->K;
+    a.lambda = lag->d_lambda;
+    a.words = lag->d_words;
+    a.stats = lag->d_stats;
+    for (int32_t k = 0; k < lag->K; k++) {
+        a.limit[k] = lag->c[k].limit;
+        a.lr[k] = lag->c[k].lr;
+        a.lambda_max[k] = lag->c[k].lambda_max;
+    }
+    launch_lagrange_step(a, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_lagrange_combine_device(chub_lagrange *lag, int64_t n, const float *d_adv, const double *d_adv_stats, const float *const *d_adv_cost,
+                                 float *d_out, void *stream) {
+    if (!lag || !d_adv || !d_adv_cost || !d_out) return fail(CHUB_ERR_ARG, "null argument");
+    if (n < 1) return fail(CHUB_ERR_ARG, "chub_lagrange_combine_device: n >= 1 entries");
+    for (int32_t k = 0; k < lag->K; k++)
+        if (!d_adv_cost[k]) return fail(CHUB_ERR_ARG, "chub_lagrange_combine_device: d_adv_cost[k] is required for every constraint");
+    HIP_TRY(hipSetDevice(lag->env->device));
+    (void) hipGetLastError();
+    LagrangeCombineArgs a = {};
+    a.n = n;
+    a.K = lag->K;
+    a.adv = d_adv;
+    a.adv_stats = d_adv_stats;
+    a.lambda = lag->d_lambda;
+    a.stats = lag->d_stats;
+    for (int32_t k = 0; k < lag->K; k++) a.advc[k] = d_adv_cost[k];
+    a.out = d_out;
+    launch_lagrange_combine(a, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_lagrange_device(chub_lagrange *lag, const double **d_lambda, const double **d_stats) {
+    if (!lag || !d_lambda || !d_stats) return fail(CHUB_ERR_ARG, "null argument");
+    *d_lambda = lag->d_lambda;
+    *d_stats = lag->d_stats;
+    return CHUB_OK;
+}
+
+int chub_lagrange_read(chub_lagrange *lag, double *lambda, double *stats, double *words) {
+    if (!lag) return fail(CHUB_ERR_ARG, "null argument");
+    if (lag->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_lagrange_read between chub_graph_begin and chub_graph_end (it copies and synchronises)");
+    HIP_TRY(hipSetDevice(lag->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t K = (size_t) lag->K;
+    if (lambda) HIP_TRY(hipMemcpy(lambda, lag->d_lambda, K * sizeof(double), hipMemcpyDeviceToHost));
+    if (stats) HIP_TRY(hipMemcpy(stats, lag->d_stats, K * kLagStats * sizeof(double), hipMemcpyDeviceToHost));
+    if (words) HIP_TRY(hipMemcpy(words, lag->d_words, K * kLagWords * sizeof(double), hipMemcpyDeviceToHost));
+    return CHUB_OK;
+}
+
+int chub_lagrange_set_lambda_device(chub_lagrange *lag, const double *d_lambda, void *stream) {
+    if (!lag || !d_lambda) return fail(CHUB_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(lag->env->device));
+    (void) hipGetLastError();
+    launch_lagrange_set_lambda(lag->d_lambda, d_lambda, lag->K, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+// the checkpoint blob: K as an int64, lambda [K], the words [K][3]
+int chub_lagrange_state_size(chub_lagrange *lag, int64_t *bytes) {
+    if (!lag || !bytes) return fail(CHUB_ERR_ARG, "null argument");
+    *bytes = (int64_t) (sizeof(int64_t) + (size_t) lag->K * (1 + kLagWords) * sizeof(double));
+    return CHUB_OK;
+}
+
+int chub_lagrange_get_state(chub_lagrange *lag, void *blob) {
+    if (!lag || !blob) return fail(CHUB_ERR_ARG, "null argument");
+    if (lag->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_lagrange_get_state between chub_graph_begin and chub_graph_end (it copies and synchronises)");
+    const int64_t K = lag->K;
+    memcpy(blob, &K, sizeof K);
+    double *w = reinterpret_cast<double *>(static_cast<char *>(blob) + sizeof K);
+    return chub_lagrange_read(lag, w, nullptr, w + K);
+}
+
+int chub_lagrange_set_state(chub_lagrange *lag, const void *blob) {
+    if (!lag || !blob) return fail(CHUB_ERR_ARG, "null argument");
+    if (lag->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_lagrange_set_state between chub_graph_begin and chub_graph_end (it copies and synchronises)");
+    int64_t K;
+    memcpy(&K, blob, sizeof K);
+    if (K != lag->K) return fail(CHUB_ERR_ARG, "chub_lagrange_set_state: the blob was taken from an object of another K");
+    const double *w = reinterpret_cast<const double *>(static_cast<const char *>(blob) + sizeof K);
+    HIP_TRY(hipSetDevice(lag->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(lag->d_lambda, w, (size_t) K * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(lag->d_words, w + K, (size_t) K * kLagWords * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    return CHUB_OK;
+}
+
+int chub_lagrange_fold(const chub_constraint *c, double *lambda, double *words, const double *stats) {
+    if (!c || !lambda || !words || !stats) return fail(CHUB_ERR_ARG, "null argument");
+    if (const int rc = lagrange_check_constraint("chub_lagrange_fold", *c)) return rc;
+    lagrange_step(lambda, words, stats, c->limit, c->lr, c->lambda_max);
+    return CHUB_OK;
 }
 
 }  // extern "C"

@@ -290,15 +290,22 @@ class DevicePolicy(_DeviceNet):
                                                           d_set_bits or None, C.byref(out), stream or None))
 
     def collect(self, n_steps, d_obs0, d_packed, d_pile_bits, d_tail, d_u, d_logp, d_features=0, d_final_obs=0, first_step=0, mode="lockstep",
-                stream=0, logp_piles=None, d_set_bits=0):
+                stream=0, logp_piles=None, d_set_bits=0, d_terms=0, term_fields=None):
         """the closed loop that keeps the trajectory (chub_policy_collect): n_steps sampled steps into [T][N][...] arrays in device memory,
         the actor reading d_obs0 [N, D] at the first step and the packed block before it afterwards.  Returns after enqueueing.
         logp_piles="all" | "occupied" | "decidable" with d_set_bits [T, N, bit_words] u64 (chub_policy_collect_set): d_logp[t] counts the
-        piles of that set in the state step t acts on, and d_set_bits[t] keeps the set."""
+        piles of that set in the state step t acts on, and d_set_bits[t] keeps the set.  d_terms [T, N, C] f32 with term_fields (names
+        or a mask, as set_step_terms takes them): block t keeps step t's terms (chub_policy_collect_terms; telemetry must be on)."""
         r = _lib.ChubRollout(int(n_steps), d_packed or None, d_pile_bits or None, d_tail or None, d_u or None, d_logp or None, d_features or None,
                              d_final_obs or None)
         run = _lib._enum_value(_lib.PRUN, mode, "run mode")
-        if logp_piles is None:
+        if d_terms or term_fields is not None:
+            if logp_piles is None and d_set_bits:
+                raise ValueError("d_set_bits needs logp_piles (the set to keep)")
+            which = -1 if logp_piles is None else _lib.pile_set(logp_piles)
+            check(self._lib.chub_policy_collect_terms(self._env._h, self._p, run, which, C.byref(r), d_set_bits or None, d_obs0 or None,
+                                                      int(first_step), _lib.st_fields_mask(term_fields), d_terms or None, stream or None))
+        elif logp_piles is None:
             if d_set_bits:
                 raise ValueError("d_set_bits needs logp_piles (the set to keep)")
             check(self._lib.chub_policy_collect(self._env._h, self._p, run, C.byref(r), d_obs0 or None, int(first_step), stream or None))
@@ -892,6 +899,113 @@ def train_log_fold(words, gate, pstats=None, cstats=None, kl="k3", kl_limit=0.0)
     cs = None if cstats is None else np.ascontiguousarray(cstats, dtype=np.float64)
     check(_lib.load_library().chub_train_log_fold(_ptr(words), _ptr(gate), None if ps is None else _ptr(ps), None if cs is None else _ptr(cs),
                                                   _lib.kl_kind(kl), float(kl_limit)))
+
+
+class DeviceLagrange(object):
+    """K = 1 .. 4 constraints with their Lagrange multipliers on the device (chub_lagrange_*, include/chub.h "constrained PPO on the
+    device"): made by VecChargingHub.make_lagrange.  gae, step and combine enqueue on the caller's stream and are recordable into a
+    graph; read is the one synchronising copy.  constraints: dicts or tuples (column, kind, limit, lr, lambda0, lambda_max) with column
+    the index within the rows of the terms array gae is given and kind "step" | "done"."""
+
+    def __init__(self, env, constraints):
+        self._env = env
+        self._lib = env._lib
+        rows = [c if isinstance(c, dict) else dict(zip(("column", "kind", "limit", "lr", "lambda0", "lambda_max"), c)) for c in constraints]
+        self.K = len(rows)
+        arr = (_lib.ChubConstraint * max(self.K, 1))()
+        for k, c in enumerate(rows):
+            arr[k] = _lib.ChubConstraint(int(c["column"]), _lib.cost_kind(c.get("kind", "step")), float(c.get("limit", 0.0)), float(c.get("lr", 0.0)),
+                                         float(c.get("lambda0", 0.0)), float(c.get("lambda_max", 0.0)))
+        self.constraints = [dict(column=a.column, kind=a.kind, limit=a.limit, lr=a.lr, lambda0=a.lambda0, lambda_max=a.lambda_max) for a in arr[:self.K]]
+        h = C.c_void_p()
+        check(self._lib.chub_lagrange_create(env._h, self.K, arr, C.byref(h)))
+        self._g = h
+        lam, st = C.c_void_p(), C.c_void_p()
+        check(self._lib.chub_lagrange_device(self._g, C.byref(lam), C.byref(st)))
+        self.lambda_address, self.stats_address = lam.value, st.value
+
+    @staticmethod
+    def _four(addresses, K):
+        a = list(addresses) if addresses else []
+        if len(a) > K:
+            raise ValueError("%d addresses for %d constraints" % (len(a), K))
+        return (C.c_void_p * 4)(*[x or None for x in a + [0] * (4 - len(a))])
+
+    def gae(self, n_steps, n_columns, d_terms, d_packed, d_adv, d_ret=None, d_values=None, d_final_values=None, gamma=0.99, lam=0.95, d_mask=0,
+            d_ep_carry=0, stream=0):
+        """cost advantages, cost returns and episode costs of a collected rollout (chub_lagrange_gae_device): d_terms [T, N, n_columns]
+        f32, d_packed [T, N, D + 2] (only done is read); per constraint d_adv[k] [T, N] (required), d_ret[k] [T, N], d_values[k]
+        [T + 1, N] (none: V = 0) and d_final_values[k] [N] as sequences of device addresses; d_ep_carry [N, K] f64 carries the cost of
+        the episodes still open from call to call.  The stats block is written by the second of the two launches."""
+        g = _lib.ChubCostGae()
+        g.T, g.C, g.d_terms, g.d_packed, g.d_mask = int(n_steps), int(n_columns), d_terms or None, d_packed or None, d_mask or None
+        g.d_values, g.d_final_values = self._four(d_values, self.K), self._four(d_final_values, self.K)
+        g.d_adv, g.d_ret = self._four(d_adv, self.K), self._four(d_ret, self.K)
+        g.gamma, g.lam, g.d_ep_carry = float(gamma), float(lam), d_ep_carry or None
+        check(self._lib.chub_lagrange_gae_device(self._g, C.byref(g), stream or None))
+
+    def step(self, stream=0):
+        """projected dual ascent on every multiplier from the stats the last gae left (chub_lagrange_step_device): one launch"""
+        check(self._lib.chub_lagrange_step_device(self._g, stream or None))
+
+    def combine(self, n, d_adv, d_adv_cost, d_out, d_adv_stats=0, stream=0):
+        """d_out [n] = (normalised advantage - sum_k lambda_k (cost advantage_k - its mean)) / (1 + sum_k lambda_k)
+        (chub_lagrange_combine_device): what grad_device / ppo_update take as d_adv with no d_adv_stats.  d_out may be d_adv."""
+        if len(d_adv_cost) != self.K:
+            raise ValueError("%d cost advantages for %d constraints" % (len(d_adv_cost), self.K))
+        arr = (C.c_void_p * 4)(*[x or None for x in list(d_adv_cost) + [0] * (4 - self.K)])
+        check(self._lib.chub_lagrange_combine_device(self._g, int(n), d_adv or None, d_adv_stats or None, arr, d_out or None, stream or None))
+
+    def set_lambda_device(self, d_lambda, stream=0):
+        """the multipliers from K f64 words in device memory (chub_lagrange_set_lambda_device): one launch"""
+        check(self._lib.chub_lagrange_set_lambda_device(self._g, d_lambda or None, stream or None))
+
+    def read(self):
+        """(lambda [K], stats [K, 6], words [K, 3] = J_last, steps taken, steps skipped) as float64; synchronises"""
+        lam, st, w = np.zeros(self.K), np.zeros((self.K, _lib.LAG_STATS)), np.zeros((self.K, _lib.LAG_WORDS))
+        check(self._lib.chub_lagrange_read(self._g, _ptr(lam), _ptr(st), _ptr(w)))
+        return lam, st, w
+
+    def get_state(self):
+        """lambda and the counters as bytes, for a checkpoint (chub_lagrange_get_state); synchronises"""
+        n = C.c_int64()
+        check(self._lib.chub_lagrange_state_size(self._g, C.byref(n)))
+        blob = np.zeros(n.value, dtype=np.uint8)
+        check(self._lib.chub_lagrange_get_state(self._g, _ptr(blob)))
+        return blob.tobytes()
+
+    def set_state(self, blob):
+        """get_state's bytes back (chub_lagrange_set_state): a blob of another K is refused"""
+        n = C.c_int64()
+        check(self._lib.chub_lagrange_state_size(self._g, C.byref(n)))
+        b = np.frombuffer(bytes(blob), dtype=np.uint8).copy()
+        if b.size < 8:
+            raise ValueError("set_state: not a state blob (%d bytes)" % b.size)
+        if int(b[:8].view(np.int64)[0]) == self.K and b.size != n.value:  # (another K: the library refuses it, from the first word alone)
+            raise ValueError("set_state: %d bytes, this object's state has %d" % (b.size, n.value))
+        check(self._lib.chub_lagrange_set_state(self._g, _ptr(b)))
+
+    def close(self):
+        if getattr(self, "_g", None) and getattr(self._env, "_h", None):
+            check(self._lib.chub_lagrange_destroy(self._g))
+        self._g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def lagrange_fold(constraint, lam, words, stats):
+    """the multiplier's step on host memory for one constraint (chub_lagrange_fold; no device): lam float64 [1] and words float64 [3]
+    (J_last, taken, skipped) are updated in place from stats float64 [6]"""
+    assert lam.dtype == np.float64 and lam.size == 1 and words.dtype == np.float64 and words.size == 3
+    st = np.ascontiguousarray(stats, dtype=np.float64)
+    assert st.size == _lib.LAG_STATS
+    c = _lib.ChubConstraint(int(constraint.get("column", 0)), _lib.cost_kind(constraint.get("kind", "step")), float(constraint.get("limit", 0.0)),
+                            float(constraint.get("lr", 0.0)), float(constraint.get("lambda0", 0.0)), float(constraint.get("lambda_max", 0.0)))
+    check(_lib.load_library().chub_lagrange_fold(C.byref(c), _ptr(lam), _ptr(words), _ptr(st)))
 
 
 def ppo_update_plan(n_rows, minibatch_rows):
@@ -1561,6 +1675,11 @@ class VecChargingHub(object):
     def make_train_log(self):
         """a training log with its gate word for this handle -> DeviceTrainLog (chub_train_log_create)"""
         return DeviceTrainLog(self)
+
+    def make_lagrange(self, constraints):
+        """K = 1 .. 4 constraints with their multipliers for this handle -> DeviceLagrange (chub_lagrange_create).  constraints: dicts
+        with column (within the terms rows its gae will be given), kind "step" | "done", limit, lr, lambda0, lambda_max (0: no ceiling)"""
+        return DeviceLagrange(self, constraints)
 
     def ppo_update(self, grad, critic, actor_opt, critic_opt, n_rows, d_features, d_u, d_logp_old, d_adv, d_ret, d_rows, epochs, minibatch_rows, key,
                    d_pile_bits=0, d_set_bits=0, d_adv_stats=0, d_v_old=0, ld_features=None, loss="ppo_clip", value_loss="mse", clip_eps=0.2,

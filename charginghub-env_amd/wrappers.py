@@ -698,7 +698,7 @@ class TorchHubVecEnv(object):
                                stream=self._stream())
         return grads
 
-    def collect(self, policy, n_steps, logp_piles=None):
+    def collect(self, policy, n_steps, logp_piles=None, terms=None):
         """n_steps SAMPLED closed-loop steps of `policy` (after ``policy.set_exploration``) from the current observation, issued from C on
         torch's current stream (chub_policy_collect), keeping the trajectory: a dict of CUDA tensors the next call with the same policy and
         n_steps overwrites --
@@ -709,6 +709,9 @@ class TorchHubVecEnv(object):
         ``logp_piles="all" | "occupied" | "decidable"`` (chub_policy_collect_set): ``logp`` counts a pile's term only where the pile is in
         that set of the state the step acted on, and the dict also holds set_bits [T, N, W] int64, the sets -- what
         ``sampled_logp(..., piles=ro["set_bits"])`` and ``sampled_entropy`` take.  "decidable" are the piles whose bit the step reads.
+        ``terms=(names of _lib.ST_NAMES)`` (chub_policy_collect_terms): the dict gains terms [T, N, C], step t's terms in block t in the
+        order of ``rollout["terms_names"]`` (ascending field order) -- a finished env's row holds its terminal step's terms -- what
+        ``cost_advantages`` reads.  Telemetry is switched on by the first such call; a ``step_terms=`` buffer stays attached and unwritten.
         ``autoreset="per_env"``: every step is the auto-reset step, ``last_obs`` keeps the terminal rows, n_steps <= 96.
         ``autoreset=True``: the rollout stays inside the batch's day (n_steps <= 96 - steps taken today); one that begins a day begins with
         the day's reset, made by the call itself (it replaces the one the adapter made), and one that ends a day is followed by the
@@ -728,10 +731,12 @@ class TorchHubVecEnv(object):
             cache = self._rollouts = {}
         if logp_piles is not None:
             _lib.pile_set(logp_piles)  # (ValueError for an unknown name, before anything is allocated)
-        ro = cache.get((id(policy), T, logp_piles is not None))
+        st_mask = None if terms is None else _lib.st_fields_mask(terms)  # (ValueError for an unknown name, before anything is allocated)
+        key = (id(policy), T, logp_piles is not None) + (() if st_mask is None else (st_mask,))
+        ro = cache.get(key)
         if ro is None:
             f32 = dict(dtype=torch.float32, device=self.device)
-            ro = cache[(id(policy), T, logp_piles is not None)] = {
+            ro = cache[key] = {
                 "obs0": torch.zeros((N, D), **f32), "packed": torch.zeros((T, N, D + 2), **f32),
                 "bits": torch.zeros((T, N, W), dtype=torch.int64, device=self.device), "tail": torch.zeros((T, N, 2), **f32),
                 "u": torch.zeros((T, N, policy.n_gaussians), **f32), "logp": torch.zeros((T, N), **f32),
@@ -739,10 +744,16 @@ class TorchHubVecEnv(object):
             ro["reward"], ro["done"] = ro["packed"][:, :, D], ro["packed"][:, :, D + 1]
             if logp_piles is not None:
                 ro["set_bits"] = torch.zeros((T, N, W), dtype=torch.int64, device=self.device)
+            if st_mask is not None:
+                ro["terms_names"] = _lib.st_fields_names(st_mask)
+                ro["terms"] = torch.zeros((T, N, len(ro["terms_names"])), **f32)
+                self.vec.set_telemetry(True)
         self._rollout_policy = getattr(self, "_rollout_policy", {})
         self._rollout_policy[id(ro)] = policy  # (policy_gradient / evaluate_actions find the rollout's actor here)
         ro["obs0"].copy_(self._cur_obs)
         extra = {} if logp_piles is None else dict(logp_piles=logp_piles, d_set_bits=ro["set_bits"].data_ptr())
+        if st_mask is not None:
+            extra.update(d_terms=ro["terms"].data_ptr(), term_fields=st_mask)
         policy.collect(T, ro["obs0"].data_ptr(), ro["packed"].data_ptr(), ro["bits"].data_ptr(), ro["tail"].data_ptr(), ro["u"].data_ptr(),
                        ro["logp"].data_ptr(), d_features=ro["features"].data_ptr(), d_final_obs=self.last_obs.data_ptr() if self.per_env else 0,
                        first_step=today, mode="autoreset" if self.per_env else "lockstep", stream=self._stream(), **extra)
@@ -1048,6 +1059,102 @@ class TorchHubVecEnv(object):
                             d_v_old=v_old.data_ptr() if clipped else 0, loss=loss, value_loss=value_loss, clip_eps=clip_eps, value_clip_eps=clip_eps,
                             ent_coef=ent_coef, kl=kl, kl_limit=0.0 if target_kl is None else 1.5 * float(target_kl), log=log, stream=self._stream())
         return rows
+
+    # ---- constrained PPO on the device (chub_lagrange_*): cost advantages, multipliers, the combined advantage
+    def make_constraints(self, constraints):
+        """Constraints with their Lagrange multipliers on the device -> DeviceLagrange (VecChargingHub.make_lagrange).  constraints: up to
+        four dicts ``dict(term="grid_excess", kind="step", limit=.., lr=.., lambda0=0, lambda_max=0)``: term a name of _lib.ST_NAMES,
+        kind "step" (the term's value at every step) or "done" (its value where the episode ends, 0 elsewhere; on "soc_penalty" the
+        reference's test_penalty), limit the bound on an episode's mean cost, lr the multiplier's step, lambda_max 0 = no ceiling.  The
+        object's ``terms`` is the ``terms=`` tuple ``collect`` must be given: the distinct terms, so that a terms row holds nothing else."""
+        names = _lib.st_fields_names(_lib.st_fields_mask([c["term"] for c in constraints]))
+        rows = [dict(column=names.index(c["term"]), kind=c.get("kind", "step"), limit=c.get("limit", 0.0), lr=c.get("lr", 0.0),
+                     lambda0=c.get("lambda0", 0.0), lambda_max=c.get("lambda_max", 0.0)) for c in constraints]
+        lag = self.vec.make_lagrange(rows)
+        lag.terms = names
+        lag.term_of = tuple(c["term"] for c in constraints)
+        return lag
+
+    def _own_constraints(self, constraints, who):
+        if getattr(constraints, "_env", None) is not self.vec:
+            raise ValueError("%s: the constraints were made for another handle" % who)
+
+    def cost_advantages(self, rollout, constraints, cost_values=None, final_values=None, gamma=0.99, lam=0.95):
+        """Cost GAE over a ``collect(..., terms=constraints.terms)`` rollout for every constraint in one pass, on torch's current stream
+        (chub_lagrange_gae_device): cost_values, a sequence with per constraint a [T + 1, N] float32 CUDA tensor (the cost critic as
+        ``advantages`` takes the reward critic's values) or None (V = 0); final_values likewise [N].  Returns (advs, rets): per constraint
+        a float32 [T, N] CUDA tensor, overwritten by the next call with the same T.  The cost of episodes still running at the rollout's
+        end is carried to the next call in a [N, K] float64 tensor of the object's; the stats ``update_multipliers`` reads are left
+        in the object."""
+        torch = self.torch
+        self._own_constraints(constraints, "cost_advantages")
+        if "terms" not in rollout or tuple(rollout["terms_names"]) != tuple(constraints.terms):
+            raise ValueError("cost_advantages: the rollout must be collected with terms=constraints.terms %r" % (constraints.terms,))
+        T, N, K = int(rollout["packed"].shape[0]), self.num_envs, constraints.K
+        ok = lambda t, shape: self._on_device(t) and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
+        vals = list(cost_values) if cost_values is not None else [None] * K
+        fins = list(final_values) if final_values is not None else [None] * K
+        if len(vals) != K or len(fins) != K:
+            raise ValueError("cost_advantages: one entry per constraint (%d)" % K)
+        for v in vals:
+            if v is not None and not ok(v, (T + 1, N)):
+                raise AssertionError("cost_values[k] must be a contiguous float32 tensor on %s of shape (%d, %d)" % (self.device, T + 1, N))
+        for v in fins:
+            if v is not None and not ok(v, (N,)):
+                raise AssertionError("final_values[k] must be a contiguous float32 tensor on %s of shape (%d,)" % (self.device, N))
+        cache = constraints.__dict__.setdefault("_torch", {})
+        if "carry" not in cache:
+            cache["carry"] = torch.zeros((N, K), dtype=torch.float64, device=self.device)
+        out = cache.get(("gae", T))
+        if out is None:
+            out = cache[("gae", T)] = ([torch.zeros((T, N), dtype=torch.float32, device=self.device) for _ in range(K)],
+                                       [torch.zeros((T, N), dtype=torch.float32, device=self.device) for _ in range(K)])
+        advs, rets = out
+        constraints.gae(T, len(constraints.terms), rollout["terms"].data_ptr(), rollout["packed"].data_ptr(), [a.data_ptr() for a in advs],
+                        d_ret=[r.data_ptr() for r in rets], d_values=[0 if v is None else v.data_ptr() for v in vals],
+                        d_final_values=[0 if v is None else v.data_ptr() for v in fins], gamma=gamma, lam=lam,
+                        d_ep_carry=cache["carry"].data_ptr(), stream=self._stream())
+        return advs, rets
+
+    def update_multipliers(self, constraints):
+        """One step of projected dual ascent on every multiplier, from the episodes the last ``cost_advantages`` saw finish, on torch's
+        current stream (chub_lagrange_step_device).  A rollout in which no episode finished moves nothing and counts as skipped."""
+        self._own_constraints(constraints, "update_multipliers")
+        constraints.step(stream=self._stream())
+
+    def constrained_advantages(self, adv, adv_stats, cost_advs, constraints):
+        """The advantage a PPO-Lagrangian update ascends, in one streaming launch on torch's current stream (chub_lagrange_combine_device):
+        (A - sum_k lambda_k (A_k - mean A_k)) / (1 + sum_k lambda_k) with A the reward advantage, normalised by adv_stats where given
+        (``advantages(..., stats=True)``), and A_k the cost advantages of the last ``cost_advantages``.  Returns a float32 tensor of adv's
+        shape (overwritten by the next call of the same size): hand it to ``policy_gradient`` / ``ppo_update`` as adv with adv_stats=None."""
+        torch = self.torch
+        self._own_constraints(constraints, "constrained_advantages")
+        n = adv.numel()
+        flat = lambda t: self._on_device(t) and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+        if not flat(adv) or len(cost_advs) != constraints.K or not all(flat(c) for c in cost_advs):
+            raise AssertionError("adv and one cost advantage per constraint must be contiguous float32 tensors on %s of one size" % (self.device,))
+        if adv_stats is not None and not (self._on_device(adv_stats) and adv_stats.dtype == torch.float64 and adv_stats.is_contiguous()
+                                          and adv_stats.numel() == 3):
+            raise AssertionError("adv_stats must be a contiguous float64 tensor on %s of 3 entries (advantages(..., stats=True))" % (self.device,))
+        cache = constraints.__dict__.setdefault("_torch", {})
+        out = cache.get(("combined", tuple(adv.shape)))
+        if out is None:
+            out = cache[("combined", tuple(adv.shape))] = torch.zeros(tuple(adv.shape), dtype=torch.float32, device=self.device)
+        constraints.combine(n, adv.data_ptr(), [c.data_ptr() for c in cost_advs], out.data_ptr(),
+                            d_adv_stats=0 if adv_stats is None else adv_stats.data_ptr(), stream=self._stream())
+        return out
+
+    def constraint_summary(self, constraints):
+        """One synchronising read of the constraints -> a list with per constraint a dict: term, kind, limit, lambda, cost (J_last: the
+        mean episode cost the last taken step saw), episodes and episode_cost_mean of the last ``cost_advantages``, steps, skipped."""
+        self._own_constraints(constraints, "constraint_summary")
+        lam, st, w = constraints.read()
+        out = []
+        for k, c in enumerate(constraints.constraints):
+            out.append(dict(term=constraints.term_of[k] if hasattr(constraints, "term_of") else c["column"], kind=_lib.COST_KIND_NAMES[c["kind"]],
+                            limit=c["limit"], **{"lambda": float(lam[k])}, cost=float(w[k, 0]), episodes=int(st[k, 3]),
+                            episode_cost_mean=float(st[k, 4] / st[k, 3]) if st[k, 3] else float("nan"), steps=int(w[k, 1]), skipped=int(w[k, 2])))
+        return out
 
     def train_log_summary(self, log, kl="k3"):
         """One synchronising read of `log` -> a dict under stable-baselines3's names.  Over the counted minibatches, weighted by rows:

@@ -15,7 +15,9 @@
 9. one complete PPO iteration in which torch does nothing but the two optimiser steps: collect -> values -> advantages -> minibatches of
    the actor's and the critic's gradients from the device -> the stepped weights of both networks straight back;
 10. PPO epochs with no torch optimiser: Adam and the minibatch shuffle on the device, the epoch recorded once and replayed;
-11. three PPO iterations whose update is ONE call with target_kl, and the numbers stable-baselines3 prints read once per iteration.
+11. three PPO iterations whose update is ONE call with target_kl, and the numbers stable-baselines3 prints read once per iteration;
+12. three PPO-Lagrangian iterations: the grid draw over the limit and the tank's end-of-day penalty as constraints, their multipliers,
+    cost advantages and the combined advantage on the device, one cost critic per constraint.
 """
 import os
 import sys
@@ -438,6 +440,50 @@ def ppo_with_log_and_target_kl(n=4096, steps=64, minibatches=4, epochs=4, iterat
     env.close()
 
 
+def ppo_lagrangian(n=4096, steps=64, minibatches=4, epochs=2, iterations=3):
+    import charginghub_env_amd as chub
+
+    if torch is None:
+        print("12. skipped: torch is not installed")
+        return
+    env = chub.TorchHubVecEnv(n, seed=0, autoreset="per_env", **HUB)
+    D, A = env.obs_dim, env.act_dim
+    mlp = lambda out: torch.nn.Sequential(torch.nn.Linear(D, 64), torch.nn.Tanh(), torch.nn.Linear(64, out)).to("cuda")
+    policy = env.load_policy(mlp(A))
+    policy.set_exploration(key=7, log_std=[-0.5, -0.5])
+    critic = env.load_critic(mlp(1))
+    a_opt = env.make_optimizer(policy, lr=3e-4, max_grad_norm=0.5)
+    c_opt = env.make_optimizer(critic, lr=1e-3, max_grad_norm=0.5)
+    # two constraints on an episode's cost: the energy drawn over the grid limit, summed over the day, and the tank's end-of-day
+    # penalty (the reference's test_penalty).  Each has a multiplier on the device and a cost critic of its own
+    cons = env.make_constraints([dict(term="grid_excess", kind="step", limit=50.0, lr=1e-3),
+                                 dict(term="soc_penalty", kind="done", limit=0.5, lr=0.05, lambda_max=10.0)])
+    cost_critics = [env.load_critic(mlp(1)) for _ in range(cons.K)]
+    cost_opts = [env.make_optimizer(c, lr=1e-3, max_grad_norm=0.5) for c in cost_critics]
+    log = env.make_train_log()
+    env.reset()
+    for it in range(iterations):
+        ro = env.collect(policy, steps, logp_piles="decidable", terms=cons.terms)   # the rollout keeps the constrained step terms
+        values, final = env.values(critic, ro)
+        adv, ret, adv_stats = env.advantages(ro, values, final, gamma=0.99, lam=0.95, stats=True)
+        cost_vf = [tuple(t.clone() for t in env.values(c, ro)) for c in cost_critics]
+        cost_advs, cost_rets = env.cost_advantages(ro, cons, cost_values=[v for v, _ in cost_vf], final_values=[f for _, f in cost_vf],
+                                                   gamma=0.99, lam=0.95)          # every constraint in one pass, episode costs counted
+        env.update_multipliers(cons)                                              # lambda += lr (J - limit), kept in [0, lambda_max]
+        combined = env.constrained_advantages(adv, adv_stats, cost_advs, cons)    # (A - sum lambda_k A_k) / (1 + sum lambda_k)
+        for c, opt, c_ret in zip(cost_critics, cost_opts, cost_rets):             # the cost critics: existing calls on the cost returns
+            env.value_gradient(c, ro, c_ret, into=opt)
+            env.optimizer_step(opt)
+        env.ppo_update(ro, combined, ret, a_opt, c_opt, epochs=epochs, minibatch_rows=steps * n // minibatches, key=23 + it, clip_eps=0.2,
+                       ent_coef=0.01, v_old=values[:steps].clone(), adv_stats=None, log=log)
+        s = env.train_log_summary(log)
+        print("12. iteration %d: policy_loss %.4f, approx_kl %.5f; %s" % (it, s["policy_loss"], s["approx_kl"], "; ".join(
+            "%s (%s) lambda %.4f, episode cost %.3f over %d episodes against %.2f, steps %d, skipped %d"
+            % (c["term"], c["kind"], c["lambda"], c["episode_cost_mean"], c["episodes"], c["limit"], c["steps"], c["skipped"])
+            for c in env.constraint_summary(cons))))
+    env.close()
+
+
 if __name__ == "__main__":
     single_env()
     batched_host()
@@ -450,3 +496,4 @@ if __name__ == "__main__":
     ppo_all_on_device()
     ppo_epochs_on_device()
     ppo_with_log_and_target_kl()
+    ppo_lagrangian()

@@ -1468,6 +1468,104 @@ int chub_adam_set_gate(chub_adam *a, const int64_t *d_gate /* or NULL: none */);
 int chub_ppo_update_plan(int64_t n_rows, int64_t minibatch_rows, int64_t *minibatches, int64_t *last_rows);  /* host-only */
 int chub_ppo_update(const chub_ppo_update_args *args, void *stream);
 
+/* ---- constrained PPO on the device: step terms kept per step, cost advantages, Lagrange multipliers, the combined advantage ---------------
+ * PPO-Lagrangian on what the step terms expose (CHUB_ST_GRID_EXCESS, CHUB_ST_NOT_MEET, CHUB_ST_SOC_PENALTY, ..): the reference's constructor
+ * takes use_lagrange and its step() keeps the block commented out (MGR:275-297).  A chub_lagrange holds K = 1 .. CHUB_LAG_MAX_K constraints,
+ * their multipliers lambda [K] f64, a stats block [K][CHUB_LAG_STATS] f64, per constraint the words {J_last, steps taken, steps skipped}
+ * (f64) and the partials of the reduction, sized at create from N -- all in device memory outside the arena: chub_state_size and snapshots
+ * are unchanged.  It is bound to a handle and destroyed by chub_destroy before the handle.  Cost critics are chub_critic objects trained on
+ * d_ret[k] by the existing calls.
+ *   chub_policy_collect_terms: chub_policy_collect (which < 0) or chub_policy_collect_set (which >= 0; the same rules and refusals) that
+ *     also keeps every step's terms: block t of d_terms [T][N][C] f32, C = chub_get_step_terms_size(fields), is bit for bit what a buffer
+ *     attached with chub_set_step_terms(env, fields, ..) holds right after step t of the same loop; under CHUB_PRUN_AUTORESET a finished
+ *     env's row therefore holds its terminal step's terms.  Whatever attachment the handle had is in force again when the call returns,
+ *     and its buffer is not written by the call.  Recordable as chub_policy_collect is: the per-step destination is a launch argument.
+ *   A constraint: `column` is a column of the d_terms rows the object is given, `kind` how a step's cost c_t is read from it:
+ *     CHUB_COST_STEP the column's value; CHUB_COST_AT_DONE the column's value where packed[t][D + 1] != 0 and exactly +0.0f elsewhere
+ *     (on CHUB_ST_SOC_PENALTY: the reference's test_penalty as an end-of-day constraint).  J, the constrained quantity, is the mean cost
+ *     of a finished episode; `limit` is its bound, `lr` the multiplier's step, `lambda0` its start, `lambda_max` its ceiling (0: none).
+ *   chub_lagrange_gae_device: kernel k_cost_gae plus a one-workgroup merge on `stream`.  Per env, for every constraint, in one pass
+ *     t = T-1 .. 0:
+ *       Advantage: chub_rollout_gae_device's recurrence operation for operation with c_t in place of packed[t][D] (f32, every operation
+ *         rounded once, no contraction, gl formed once); d_values[k] NULL: V = 0 everywhere; d_final_values[k] NULL: an end is worth 0.
+ *       Episode cost, f64, with seg = 0 and open = true: at a step with done -- if open, carry_out = seg, else the segment is a finished
+ *         episode of cost seg; then seg = (double) c_t, open = false.  At a step without done seg = seg + (double) c_t.  After t = 0 with
+ *         carry_in = d_ep_carry[e][k] (0 without d_ep_carry): x = carry_in + seg; if open carry_out = x, else x is a finished episode.
+ *         d_ep_carry[e][k] = carry_out.  A finished episode of cost x adds (1, x, x x) to the env's three episode sums.
+ *       Stats [k][0 .. 5]: count, sum and sum of squares of the advantages written; episodes finished, the sum of their costs, the sum
+ *         of the costs' squares.
+ *       Reduction order (chub_rollout_gae_device's): a lane takes its env's sums in the order it writes (t descending; per step the
+ *         advantage, then an episode that step closes; the episode closed after t = 0 last); lanes are envs 256 b .. 256 b + 255 of
+ *         workgroup b and meet in the tree h = 128, 64, .. 1 (lane l += lane l + h); lane l of the merge workgroup takes partials l,
+ *         l + 256, .. ascending from 0, then the same tree.  No atomics: two calls give identical bits.
+ *       With d_mask the other envs are not read, not written and not counted, and their carry keeps its bits.
+ *     A cost load is 4 bytes at a stride of C floats: collect only the columns you constrain (C = K is the fast case).
+ *   chub_lagrange_step_device: one launch of one wave, lane k per constraint, f64, every operation rounded once: n = stats[k][3],
+ *     J = stats[k][4] / n.  n == 0 or J not finite: lambda keeps its bits, skipped += 1.  Else l = lambda + lr (J - limit);
+ *     l = l < 0 ? 0 : l; with lambda_max != 0, l = l > lambda_max ? lambda_max : l; a NaN l leaves lambda, taken and J_last as they are
+ *     and adds 1 to skipped; else lambda = l, taken += 1, J_last = J.  It reads only what an earlier launch wrote.
+ *     chub_lagrange_fold is the same source on host memory for one constraint, no device.
+ *   chub_lagrange_combine_device: one streaming launch over n = T N entries.  a = d_adv_stats ? (adv - m32) * s32 : adv with m32, s32
+ *     chub_policy_grad_device's "Advantage" paragraph; for k ascending with l32 = (float) lambda[k]: l32 == 0 performs NO operation (with
+ *     every lambda 0 the output has the normalised advantage's bits), else a = a - l32 * (advc_k - mc32_k), three operations each rounded
+ *     once, mc32_k = (float) (stats[k][1] / stats[k][0]) -- cost advantages are centred, not scaled; out = a * inv32,
+ *     inv32 = (float) (1 / (1 + sum_k (double) l32_k)), the sum ascending in f64 from 0.  d_out may be d_adv; it must not overlap a
+ *     d_adv_cost[k].  Hand d_out to chub_policy_grad_device / chub_ppo_update as d_adv with d_adv_stats = NULL.  The call presupposes a
+ *     chub_lagrange_gae_device call that counted at least one entry: with stats[k][0] == 0 (no gae yet, or every env masked out) and
+ *     lambda[k] != 0, mc32_k is 0 / 0 and the whole output is NaN.
+ *   chub_lagrange_device gives the addresses of lambda and the stats; chub_lagrange_read copies lambda [K], the stats [K][6] and the
+ *     words [K][3] to host memory (each may be NULL) and synchronises; chub_lagrange_set_lambda_device copies K f64 words from device
+ *     memory in one launch; chub_lagrange_get_state / _set_state move a blob of chub_lagrange_state_size bytes (K, lambda, the words)
+ *     for checkpoints: a blob of another K is refused.
+ *   Manners of the device calls: no tick, no simulation state read, no allocation, no synchronisation; recordable between
+ *     chub_graph_begin and chub_graph_end, not counted among its resets and steps.  Calls on one object must be ordered against each other.
+ * Refusals, all with a message and before any device work.  CHUB_ERR_ARG: a null argument; K outside 1 .. 4; a column below 0 (create) or
+ *     above C - 1 (gae); an unknown kind; lr, limit, lambda0 or lambda_max negative or not finite; lambda0 above a non-zero lambda_max;
+ *     T <= 0; gamma or lambda outside [0, 1] or NaN; a null d_terms, d_packed or d_adv[k]; n < 1; for chub_policy_collect_terms telemetry
+ *     off, a bad mask or a null d_terms, and whatever chub_policy_collect(_set) refuses.  No C call takes both a handle and an object:
+ *     the Python adapter refuses an object made for another handle.  CHUB_ERR_UNSUPPORTED: create, destroy, read and the state calls
+ *     between chub_graph_begin and chub_graph_end; a step's block of d_packed or d_terms beyond 4 GiB (the kernel's offsets are 32 bits).
+ * Out of scope: a multi-output critic (one chub_critic per constraint); PID or Adam on lambda; gating the policy update on feasibility;
+ *     populations; the multi-GPU hosts; COMPAT rollouts. */
+enum { CHUB_COST_STEP = 0, CHUB_COST_AT_DONE, CHUB_COST_KIND_COUNT };
+enum { CHUB_LAG_MAX_K = 4, CHUB_LAG_STATS = 6, CHUB_LAG_WORDS = 3 };
+typedef struct chub_lagrange chub_lagrange;
+typedef struct chub_constraint {
+    int32_t column;               /* within a d_terms row */
+    int32_t kind;                 /* CHUB_COST_* */
+    double limit, lr, lambda0, lambda_max;
+} chub_constraint;
+typedef struct chub_cost_gae {
+    int64_t T;
+    int32_t C;                    /* floats of a d_terms row */
+    int32_t pad_;
+    const float *d_terms;         /* [T][N][C] */
+    const float *d_packed;        /* [T][N][D + 2]: only done, at column D + 1, is read */
+    const float *d_values[4];     /* per constraint [T + 1][N], or NULL: V = 0 */
+    const float *d_final_values[4]; /* per constraint [N], or NULL: an end is worth 0 */
+    const uint8_t *d_mask;        /* [N] or NULL */
+    float gamma, lambda;
+    float *d_adv[4];              /* per constraint [T][N], required for k < K */
+    float *d_ret[4];              /* per constraint [T][N] or NULL */
+    double *d_ep_carry;           /* [N][K] f64, in and out, or NULL */
+} chub_cost_gae;
+int chub_policy_collect_terms(chub_env *env, chub_policy *pol, int mode, int which /* < 0: chub_policy_collect */, const chub_rollout *r,
+                              uint64_t *d_set_bits /* [T][N][W] where which >= 0 */, float *d_obs0, int64_t first_step, uint32_t fields,
+                              float *d_terms /* [T][N][C] */, void *stream);
+int chub_lagrange_create(chub_env *env, int32_t K, const chub_constraint *c /* [K] */, chub_lagrange **out);
+int chub_lagrange_destroy(chub_lagrange *lag);
+int chub_lagrange_gae_device(chub_lagrange *lag, const chub_cost_gae *g, void *stream);
+int chub_lagrange_step_device(chub_lagrange *lag, void *stream);
+int chub_lagrange_combine_device(chub_lagrange *lag, int64_t n, const float *d_adv, const double *d_adv_stats /* [3] or NULL */,
+                                 const float *const *d_adv_cost /* host array [K] of device addresses */, float *d_out, void *stream);
+int chub_lagrange_device(chub_lagrange *lag, const double **d_lambda, const double **d_stats);
+int chub_lagrange_read(chub_lagrange *lag, double *lambda /* [K] */, double *stats /* [K][6] */, double *words /* [K][3] */); /* host; synchronises */
+int chub_lagrange_set_lambda_device(chub_lagrange *lag, const double *d_lambda /* [K], device */, void *stream);
+int chub_lagrange_state_size(chub_lagrange *lag, int64_t *bytes);
+int chub_lagrange_get_state(chub_lagrange *lag, void *blob);
+int chub_lagrange_set_state(chub_lagrange *lag, const void *blob);
+int chub_lagrange_fold(const chub_constraint *c, double *lambda, double *words /* [3] */, const double *stats /* [6] */); /* host-only */
+
 /* The FCEV waiting list is unbounded as in the reference (HYD:264-265): the entries a list that still gets served can
  * hold are kept one by one, and once no prefix of it fits into 15 minutes any more (HYD:270-276: nobody is served again
  * until reset and the list only grows) its entries are folded into their count and running sums, which is all the

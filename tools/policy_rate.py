@@ -37,6 +37,13 @@
                   65 536 rows as ONE chub_ppo_update -- epoch_update_mb<R> without a log, epoch_update_log_mb<R> with one (two more launches per
                   minibatch, one more per update) -- each eagerly and as one captured graph replayed (.._graph_..), and beside them
                   --adam's epoch_device_mb<R> / epoch_graph_mb<R>, the same chain issued call by call from Python.  ms per epoch.
+  --lagrange      a case of its own (torch first, TorchHubVecEnv; T = 96): on one collected rollout with all 27 step terms kept,
+                  gae_reward: chub_rollout_gae_device (with ret and stats) as the parent commit has it; cost_gae_k<K>_c<C>:
+                  chub_lagrange_gae_device (values, returns and the episode carry for every constraint) at K = 1, 2, 4 with C = K terms
+                  columns and at K = 2 reading two columns of the 27; combine_k2 / combine_k2_torch: chub_lagrange_combine_device against
+                  the same arithmetic as one torch expression, combine_k2_rotating: the launch over four rotating sets of its arrays, more
+                  than the 256 MiB cache holds; lagrange_step: the multipliers' launch.  us per call between two events,
+                  with the bytes each call must move (bytes_useful) and the bytes its strided reads touch at 64-byte granularity (bytes_lines).
 Every case is warmed up, then the cases alternate, ROUNDS times; median, best and worst round are reported with the build id.
 --open-loop-only measures the open loop alone, --launch-only the open loop and the deterministic launch, --no-sets the first five cases:
 with CHUB_LIB=<another build's libchub.so> those are the rates of a build without the newer entry points (the parent commit), on the same
@@ -52,7 +59,7 @@ import time
 
 import numpy as np
 
-if "--torch-gae" in sys.argv or "--torch-grad" in sys.argv or "--torch-critic" in sys.argv or "--adam" in sys.argv or "--trainlog" in sys.argv:
+if "--torch-gae" in sys.argv or "--torch-grad" in sys.argv or "--torch-critic" in sys.argv or "--adam" in sys.argv or "--trainlog" in sys.argv or "--lagrange" in sys.argv:
     import torch  # before libchub is loaded: both must share one HIP runtime
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -79,8 +86,11 @@ def main():
     ap.add_argument("--torch-critic", action="store_true")
     ap.add_argument("--adam", action="store_true", help="the optimiser's cases alone (see the module's text)")
     ap.add_argument("--trainlog", action="store_true", help="one chub_ppo_update per epoch, with and without a training log (see the module's text)")
+    ap.add_argument("--lagrange", action="store_true", help="the cost GAE, the combine and the step launches beside the reward GAE (see the module's text)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    if args.lagrange:
+        return lagrange_cases(args)
     if args.adam:
         return adam_cases(args)
     if args.trainlog:
@@ -771,6 +781,114 @@ def trainlog_cases(args):
         os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
         json.dump(rows, open(args.out, "w"), indent=1)
     torch.cuda.synchronize()
+    env.close()
+
+
+def lagrange_cases(args):
+    """--lagrange: the constrained learner's launches beside the parent's reward GAE, on one collected rollout"""
+    n_s, piles_s = args.shape.split("x")
+    n, piles = int(n_s), [int(x) for x in piles_s.split(",")]
+    T = 96
+    env = chub.TorchHubVecEnv(n, piles, ["fast", "slow"], seed=1, rng="philox", autoreset="per_env", hydro_prod_rate=100.0, hydro_store_vlt=25.0,
+                              init_soc=0.2, fc_max_power=100.0, fcev_permeate=0.01)
+    build_id = chub.load_library().chub_build_id().decode()
+    D, A = env.obs_dim, env.act_dim
+    torch.manual_seed(0)
+    lin = lambda i, o: torch.nn.Sequential(torch.nn.Linear(i, 64), torch.nn.Tanh(), torch.nn.Linear(64, o)).to("cuda")
+    pol = env.load_policy(lin(D, A))
+    pol.set_exploration(7, [-0.5, -0.5])
+    crit = env.load_critic(lin(D, 1))
+    env.reset()
+    ro = env.collect(pol, T, logp_piles="decidable", terms=chub._lib.ST_NAMES)
+    values, final = env.values(crit, ro)
+    adv, ret, adv_stats = env.advantages(ro, values, final, stats=True)
+    R = T * n
+    f32 = dict(dtype=torch.float32, device=env.device)
+    stream = torch.cuda.current_stream().cuda_stream
+    row = (D + 2) * 4
+    lines = lambda stride, used: min(stride, 64 * ((used + 63) // 64 + (1 if stride % 64 else 0)))  # bytes of a strided row its reads touch, at most
+
+    def timed(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3  # us
+
+    cases, meta, keep = {}, {}, []
+    cases["gae_reward"] = lambda: env.advantages(ro, values, final, stats=True)
+    meta["gae_reward"] = dict(route="chub_rollout_gae_device with d_ret and d_stats", bytes_useful=R * (8 + 4 + 4 + 4), bytes_lines=R * (lines(row, 8) + 12))
+    names = ("grid_excess", "not_meet", "soc_penalty", "soc_deviation")
+    for K, C in ((1, 1), (2, 2), (4, 4), (2, 27)):
+        cols = [chub._lib.ST[x] for x in names[:K]] if C == 27 else list(range(K))
+        terms = ro["terms"] if C == 27 else ro["terms"][:, :, [chub._lib.ST[x] for x in names[:K]]].contiguous()
+        lag = env.vec.make_lagrange([dict(column=c, kind="done" if names[k] == "soc_penalty" else "step", limit=1.0, lr=1e-3) for k, c in enumerate(cols)])
+        advs, rets = [torch.zeros((T, n), **f32) for _ in range(K)], [torch.zeros((T, n), **f32) for _ in range(K)]
+        carry = torch.zeros((n, K), dtype=torch.float64, device=env.device)
+        keep.append((lag, terms, advs, rets, carry))
+        kind = "cost_gae_k%d_c%d" % (K, C)
+        cases[kind] = lambda lag=lag, terms=terms, advs=advs, rets=rets, carry=carry, K=K, C=C: lag.gae(
+            T, C, terms.data_ptr(), ro["packed"].data_ptr(), [a.data_ptr() for a in advs], d_ret=[r.data_ptr() for r in rets],
+            d_values=[values.data_ptr()] * K, d_final_values=[final.data_ptr()] * K, d_ep_carry=carry.data_ptr(), stream=stream)
+        meta[kind] = dict(route="chub_lagrange_gae_device: values, returns and carry for every constraint",
+                          bytes_useful=R * (4 + K * 16) + n * K * 16, bytes_lines=R * (lines(row, 4) + lines(4 * C, 4 * K) + K * 12) + n * K * 16)
+    lag2 = keep[1][0]
+    cadv = keep[1][2]
+    out = torch.zeros((T, n), **f32)
+    lam = torch.tensor([0.5, 2.0], dtype=torch.float64, device=env.device)
+    cases["cost_gae_k2_c2"]()
+    lag2.set_lambda_device(lam.data_ptr(), stream=stream)
+    cases["combine_k2"] = lambda: lag2.combine(R, adv.data_ptr(), [c.data_ptr() for c in cadv], out.data_ptr(), d_adv_stats=adv_stats.data_ptr(), stream=stream)
+    meta["combine_k2"] = dict(route="chub_lagrange_combine_device, two multipliers not 0", bytes_useful=R * 16, bytes_lines=R * 16)
+    torch.cuda.synchronize()
+    m = (adv_stats[1] / adv_stats[0]).float()
+    sdev = (1.0 / torch.sqrt((adv_stats[2] / adv_stats[0] - (adv_stats[1] / adv_stats[0]) ** 2).clamp_min(0.0) + 1e-8)).float()
+    mc = [c.mean() for c in cadv]
+    inv = float(1.0 / (1.0 + 0.5 + 2.0))
+
+    def combine_torch():
+        torch.mul(((adv - m) * sdev) - 0.5 * (cadv[0] - mc[0]) - 2.0 * (cadv[1] - mc[1]), inv, out=out)
+
+    cases["combine_k2_torch"] = combine_torch
+    meta["combine_k2_torch"] = dict(route="the same arithmetic as one eager torch expression (its temporaries included)", bytes_useful=R * 16, bytes_lines=R * 16)
+    # the same launch over four rotating sets of its arrays (4 x 101 MB, past the 256 MiB cache): the rate from HBM
+    sets = [(adv.clone(), [c.clone() for c in cadv], torch.zeros((T, n), **f32)) for _ in range(4)]
+    turn = [0]
+
+    def combine_rotating():
+        a, cs, o = sets[turn[0] % len(sets)]
+        turn[0] += 1
+        lag2.combine(R, a.data_ptr(), [c.data_ptr() for c in cs], o.data_ptr(), d_adv_stats=adv_stats.data_ptr(), stream=stream)
+
+    cases["combine_k2_rotating"] = combine_rotating
+    meta["combine_k2_rotating"] = dict(route="chub_lagrange_combine_device over four rotating sets of arrays (403 MB in all)", bytes_useful=R * 16, bytes_lines=R * 16)
+    cases["lagrange_step"] = lambda: lag2.step(stream=stream)
+    meta["lagrange_step"] = dict(route="chub_lagrange_step_device, K = 2", bytes_useful=2 * 11 * 8, bytes_lines=2 * 11 * 8)
+    reps = {"lagrange_step": max(args.calls, 1)}
+    for fn in cases.values():
+        fn()
+    torch.cuda.synchronize()
+    vals = {c: [] for c in cases}
+    for _ in range(args.rounds):
+        for c, fn in cases.items():
+            vals[c].append(timed(fn, reps.get(c, 10)))
+    rows = []
+    for kind, xs in vals.items():
+        med = statistics.median(xs)
+        rows.append(dict(shape=args.shape, n_envs=n, piles=piles, T=T, rows=R, kind=kind, unit="us_per_call", rounds=len(xs), median=round(med, 2),
+                         min=round(min(xs), 2), max=round(max(xs), 2), gb_per_s_useful=round(meta[kind]["bytes_useful"] / med / 1e3, 1),
+                         gb_per_s_lines=round(meta[kind]["bytes_lines"] / med / 1e3, 1), build_id=build_id, **meta[kind]))
+    for row_ in rows:
+        print(json.dumps(row_), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+        json.dump(rows, open(args.out, "w"), indent=1)
+    torch.cuda.synchronize()
+    for lag, *_ in keep:
+        lag.close()
     env.close()
 
 
