@@ -354,6 +354,16 @@ class ChubCostGae(C.Structure):
                 ("lam", C.c_float), ("d_adv", C.c_void_p * 4), ("d_ret", C.c_void_p * 4), ("d_ep_carry", C.c_void_p)]
 
 
+# reward scaling on the device (chub_return_norm_*)
+RETURN_NORM_MAGIC = 0x314d524e52424843  # CHUB_RETURN_NORM_MAGIC of include/chub.h: the first word of a state blob
+RETURN_NORM_BLOB_HEAD = 48              # magic, N, the state [3], scale32 and its padding; the carry [N] f32 follows
+
+
+class ChubReturnNormSpec(C.Structure):
+    """chub_return_norm_spec of include/chub.h"""
+    _fields_ = [("gamma", C.c_float), ("clip", C.c_float), ("eps", C.c_double)]
+
+
 # pile sets (chub_pile_set_device): the CHUB_PSET_* enum of include/chub.h, in order
 PSET_NAMES = ("all", "occupied", "decidable")
 PSET = {name: i for i, name in enumerate(PSET_NAMES)}
@@ -458,8 +468,8 @@ def source_hash():
 
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
-    for name in ("chub_kernels.hip", "chub_policy.hip", "chub_critic.hip", "chub_adam.hip", "chub_trainlog.hip", "chub_lagrange.hip", "chub_runtime.cpp", "chub_comm.cpp", "chub_device.h", "chub_curves.h",
-                 "chub_plan.h", "chub_policy.h", "chub_critic.h", "chub_adam.h", "chub_trainlog.h", "chub_lagrange.h"):
+    for name in ("chub_kernels.hip", "chub_policy.hip", "chub_critic.hip", "chub_adam.hip", "chub_trainlog.hip", "chub_lagrange.hip", "chub_retnorm.hip", "chub_runtime.cpp", "chub_comm.cpp", "chub_device.h", "chub_curves.h",
+                 "chub_plan.h", "chub_policy.h", "chub_critic.h", "chub_adam.h", "chub_trainlog.h", "chub_lagrange.h", "chub_retnorm.h"):
         h.update(open(os.path.join(csrc, name), "rb").read())
     h.update(open(os.path.join(os.path.dirname(_HERE), "include", "chub.h"), "rb").read())
     return h.hexdigest()[:16]
@@ -608,6 +618,12 @@ def load_library():
         "chub_lagrange_set_lambda_device": (I, [P, P, P]), "chub_lagrange_state_size": (I, [P, C.POINTER(L)]),
         "chub_lagrange_get_state": (I, [P, P]), "chub_lagrange_set_state": (I, [P, P]),
         "chub_lagrange_fold": (I, [C.POINTER(ChubConstraint), P, P, P]),
+        "chub_return_norm_create": (I, [P, C.POINTER(ChubReturnNormSpec), C.POINTER(P)]), "chub_return_norm_destroy": (I, [P]),
+        "chub_return_norm_update_device": (I, [P, P, L, P, P]), "chub_return_norm_gae_device": (I, [P, C.POINTER(ChubGae), P]),
+        "chub_return_norm_reset_carry_device": (I, [P, P, P]), "chub_return_norm_reset_device": (I, [P, P]),
+        "chub_return_norm_device": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P)]), "chub_return_norm_state_size": (I, [P, C.POINTER(L)]),
+        "chub_return_norm_get_state": (I, [P, P]), "chub_return_norm_set_state": (I, [P, P]),
+        "chub_return_norm_fold": (I, [P, P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -666,7 +682,10 @@ EXPORTED = ["chub_create", "chub_create_ex", "chub_destroy", "chub_obs_dim", "ch
             "chub_ppo_update_plan", "chub_ppo_update",
             "chub_policy_collect_terms", "chub_lagrange_create", "chub_lagrange_destroy", "chub_lagrange_gae_device", "chub_lagrange_step_device",
             "chub_lagrange_combine_device", "chub_lagrange_device", "chub_lagrange_read", "chub_lagrange_set_lambda_device",
-            "chub_lagrange_state_size", "chub_lagrange_get_state", "chub_lagrange_set_state", "chub_lagrange_fold"]
+            "chub_lagrange_state_size", "chub_lagrange_get_state", "chub_lagrange_set_state", "chub_lagrange_fold",
+            "chub_return_norm_create", "chub_return_norm_destroy", "chub_return_norm_update_device", "chub_return_norm_gae_device",
+            "chub_return_norm_reset_carry_device", "chub_return_norm_reset_device", "chub_return_norm_device", "chub_return_norm_state_size",
+            "chub_return_norm_get_state", "chub_return_norm_set_state", "chub_return_norm_fold"]
 
 
 def check(rc):

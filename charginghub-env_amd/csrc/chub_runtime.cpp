@@ -22,6 +22,7 @@
 #include "chub_adam.h"
 #include "chub_trainlog.h"
 #include "chub_lagrange.h"
+#include "chub_retnorm.h"
 
 namespace chub {
 template <bool RESET>
@@ -193,6 +194,8 @@ struct chub_env {
     std::vector<chub_train_log *> train_logs;
     // the constraint objects made for this handle (chub_lagrange_create): destroyed before it, multipliers, stats and partials outside the arena
     std::vector<chub_lagrange *> lagranges;
+    // the reward scalers made for this handle (chub_return_norm_create): destroyed before it, state, scale, carry and partials outside the arena
+    std::vector<chub_return_norm *> return_norms;
     // chub_rollout_gae_device's statistics: the workgroups' partials [ceil(N / 256)][3] f64, allocated at create outside the arena (derived
     // scratch: no snapshot carries it).  One buffer: calls that ask for d_stats must be ordered against each other
     double *d_gae_part = nullptr;
@@ -1096,9 +1099,11 @@ static void moments_free(chub_moments *m);
 static void critic_free(chub_critic *c);
 static void train_log_free(chub_train_log *log);
 static void lagrange_free(chub_lagrange *lag);
+static void return_norm_free(chub_return_norm *rn);
 
 int chub_destroy(chub_env *e) {
     if (!e) return CHUB_OK;
+    while (!e->return_norms.empty()) return_norm_free(e->return_norms.back());
     while (!e->lagranges.empty()) lagrange_free(e->lagranges.back());
     while (!e->train_logs.empty()) train_log_free(e->train_logs.back());  // (first: it clears the gates of optimisers that still live)
     while (!e->moments.empty()) moments_free(e->moments.back());  // (each takes itself off the list)
@@ -6087,6 +6092,214 @@ int chub_lagrange_fold(const chub_constraint *c, double *lambda, double *words, 
     if (!c || !lambda || !words || !stats) return fail(CHUB_ERR_ARG, "null argument");
     if (const int rc = lagrange_check_constraint("chub_lagrange_fold", *c)) return rc;
     lagrange_step(lambda, words, stats, c->limit, c->lr, c->lambda_max);
+    return CHUB_OK;
+}
+
+}  // extern "C"
+
+// ---- reward scaling on the device (include/chub.h): the object, the four device calls, the state calls, the host fold.  The kernels are
+// chub_retnorm.hip's, the merge's arithmetic chub_retnorm.h's
+struct chub_return_norm {
+    chub_env *env;
+    chub_return_norm_spec spec;
+    double *d_words;     // the state [3], then the pivot copy [2] (never move)
+    double *d_state, *d_pivot;
+    float *d_scale;      // [1]
+    float *d_carry;      // [N]
+    double *d_partials;  // [ceil(N / 256)][3]
+    DeviceAllocs allocs;
+};
+
+static void return_norm_free(chub_return_norm *rn) {
+    chub_env *e = rn->env;
+    (void) hipSetDevice(e->device);
+    (void) hipDeviceSynchronize();  // (a launch still in flight reads and writes the buffers)
+    rn->allocs.free_all();
+    e->return_norms.erase(std::remove(e->return_norms.begin(), e->return_norms.end(), rn), e->return_norms.end());
+    delete rn;
+}
+
+// what every call on an object checks first: the object, and that its handle has not become a tape handle
+static int return_norm_check(const chub_return_norm *rn, const char *who) {
+    if (!rn) return fail(CHUB_ERR_ARG, "null argument");
+    if (rn->env->tape_only) return fail(CHUB_ERR_UNSUPPORTED, std::string(who) + " is not supported on a tape handle (chub_tape_register_soc)");
+    return CHUB_OK;
+}
+
+struct ReturnNormBlobHead {
+    uint64_t magic;
+    int64_t n_envs;
+    double state[3];
+    float scale, pad_;
+};
+static_assert(sizeof(ReturnNormBlobHead) == 48, "the blob's head is 48 bytes");
+
+extern "C" {
+
+int chub_return_norm_create(chub_env *e, const chub_return_norm_spec *spec, chub_return_norm **out) {
+    if (!e || !spec || !out) return fail(CHUB_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (!(spec->gamma >= 0.0f && spec->gamma <= 1.0f)) return fail(CHUB_ERR_ARG, "chub_return_norm_create: gamma lies in [0, 1]");
+    if (!(spec->eps > 0.0) || !__builtin_isfinite(spec->eps)) return fail(CHUB_ERR_ARG, "chub_return_norm_create: eps is finite and above 0");
+    if (!(spec->clip >= 0.0f)) return fail(CHUB_ERR_ARG, "chub_return_norm_create: clip is at least 0 (0: none)");
+    if (e->tape_only) return fail(CHUB_ERR_UNSUPPORTED, "chub_return_norm_create is not supported on a tape handle (chub_tape_register_soc)");
+    if (e->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_return_norm_create between chub_graph_begin and chub_graph_end (it allocates and synchronises)");
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    chub_return_norm *rn = new chub_return_norm();
+    rn->env = e;
+    rn->spec = *spec;
+    e->return_norms.push_back(rn);
+    const size_t N = (size_t) e->hp.n_envs, blocks = (N + kRetLanes - 1) / kRetLanes;
+    const float one = 1.0f;
+    if (rn->allocs.zeroed(&rn->d_words, 5) || rn->allocs.zeroed(&rn->d_scale, 1) || rn->allocs.zeroed(&rn->d_carry, N) ||
+        rn->allocs.zeroed(&rn->d_partials, blocks * 3) || hipMemcpy(rn->d_scale, &one, sizeof one, hipMemcpyHostToDevice) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {
+        return_norm_free(rn);
+        (void) hipGetLastError();
+        return fail(CHUB_ERR_HIP, "chub_return_norm_create: out of device memory");
+    }
+    rn->d_state = rn->d_words;
+    rn->d_pivot = rn->d_words + 3;
+    *out = rn;
+    return CHUB_OK;
+}
+
+int chub_return_norm_destroy(chub_return_norm *rn) {
+    if (!rn) return CHUB_OK;
+    if (rn->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_return_norm_destroy between chub_graph_begin and chub_graph_end (it synchronises and frees)");
+    return_norm_free(rn);
+    (void) hipGetLastError();
+    return CHUB_OK;
+}
+
+int chub_return_norm_update_device(chub_return_norm *rn, const float *d_packed, int64_t T, const uint8_t *d_mask, void *stream) {
+    if (const int rc = return_norm_check(rn, "chub_return_norm_update_device")) return rc;
+    if (!d_packed) return fail(CHUB_ERR_ARG, "null argument");
+    if (T <= 0) return fail(CHUB_ERR_ARG, "chub_return_norm_update_device: T >= 1");
+    const chub_env *e = rn->env;
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    ReturnMomentsArgs a = {};
+    a.n_envs = e->hp.n_envs;
+    a.T = T;
+    a.D = e->hp.obs_dim;
+    a.gamma = rn->spec.gamma;
+    a.eps = rn->spec.eps;
+    a.packed = d_packed;
+    a.mask = d_mask;
+    a.carry = rn->d_carry;
+    a.partials = rn->d_partials;
+    a.pivot = rn->d_pivot;
+    a.state = rn->d_state;
+    a.scale = rn->d_scale;
+    launch_return_moments(a, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_return_norm_gae_device(chub_return_norm *rn, const chub_gae *g, void *stream) {
+    if (const int rc = return_norm_check(rn, "chub_return_norm_gae_device")) return rc;
+    if (!g) return fail(CHUB_ERR_ARG, "null argument");
+    if (!g->d_packed || !g->d_values || !g->d_adv) return fail(CHUB_ERR_ARG, "chub_return_norm_gae_device: d_packed, d_values and d_adv are required");
+    if (g->T <= 0) return fail(CHUB_ERR_ARG, "chub_return_norm_gae_device: T >= 1");
+    if (!(g->gamma >= 0.0f && g->gamma <= 1.0f) || !(g->lambda >= 0.0f && g->lambda <= 1.0f))
+        return fail(CHUB_ERR_ARG, "chub_return_norm_gae_device: gamma and lambda lie in [0, 1]");
+    chub_env *e = rn->env;
+    HIP_TRY(hipSetDevice(e->device));
+    (void) hipGetLastError();
+    ScaledGaeArgs a = {};
+    a.n_envs = e->hp.n_envs;
+    a.T = g->T;
+    a.D = e->hp.obs_dim;
+    a.gamma = g->gamma;
+    a.gl = g->gamma * g->lambda;
+    a.clip = rn->spec.clip;
+    a.scale = rn->d_scale;
+    a.packed = g->d_packed;
+    a.values = g->d_values;
+    a.final_values = g->d_final_values;
+    a.mask = g->d_mask;
+    a.adv = g->d_adv;
+    a.ret = g->d_ret;
+    a.partials = g->d_stats ? e->d_gae_part : nullptr;
+    a.stats = g->d_stats;
+    launch_gae_scaled(a, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_return_norm_reset_carry_device(chub_return_norm *rn, const uint8_t *d_mask, void *stream) {
+    if (const int rc = return_norm_check(rn, "chub_return_norm_reset_carry_device")) return rc;
+    HIP_TRY(hipSetDevice(rn->env->device));
+    (void) hipGetLastError();
+    launch_return_reset_carry(rn->d_carry, d_mask, rn->env->hp.n_envs, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_return_norm_reset_device(chub_return_norm *rn, void *stream) {
+    if (const int rc = return_norm_check(rn, "chub_return_norm_reset_device")) return rc;
+    HIP_TRY(hipSetDevice(rn->env->device));
+    (void) hipGetLastError();
+    launch_return_reset(rn->d_state, rn->d_scale, rn->d_carry, rn->env->hp.n_envs, (hipStream_t) stream);
+    HIP_TRY(hipGetLastError());
+    return CHUB_OK;
+}
+
+int chub_return_norm_device(chub_return_norm *rn, const double **d_state, const float **d_scale, const float **d_carry) {
+    if (!rn) return fail(CHUB_ERR_ARG, "null argument");
+    if (d_state) *d_state = rn->d_state;
+    if (d_scale) *d_scale = rn->d_scale;
+    if (d_carry) *d_carry = rn->d_carry;
+    return CHUB_OK;
+}
+
+int chub_return_norm_state_size(chub_return_norm *rn, int64_t *bytes) {
+    if (!rn || !bytes) return fail(CHUB_ERR_ARG, "null argument");
+    *bytes = (int64_t) (sizeof(ReturnNormBlobHead) + (size_t) rn->env->hp.n_envs * sizeof(float));
+    return CHUB_OK;
+}
+
+int chub_return_norm_get_state(chub_return_norm *rn, void *blob) {
+    if (const int rc = return_norm_check(rn, "chub_return_norm_get_state")) return rc;
+    if (!blob) return fail(CHUB_ERR_ARG, "null argument");
+    if (rn->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_return_norm_get_state between chub_graph_begin and chub_graph_end (it copies and synchronises)");
+    HIP_TRY(hipSetDevice(rn->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipDeviceSynchronize());
+    ReturnNormBlobHead h = {};
+    h.magic = CHUB_RETURN_NORM_MAGIC;
+    h.n_envs = rn->env->hp.n_envs;
+    HIP_TRY(hipMemcpy(h.state, rn->d_state, sizeof h.state, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&h.scale, rn->d_scale, sizeof h.scale, hipMemcpyDeviceToHost));
+    memcpy(blob, &h, sizeof h);
+    HIP_TRY(hipMemcpy(static_cast<char *>(blob) + sizeof h, rn->d_carry, (size_t) h.n_envs * sizeof(float), hipMemcpyDeviceToHost));
+    return CHUB_OK;
+}
+
+int chub_return_norm_set_state(chub_return_norm *rn, const void *blob) {
+    if (const int rc = return_norm_check(rn, "chub_return_norm_set_state")) return rc;
+    if (!blob) return fail(CHUB_ERR_ARG, "null argument");
+    if (rn->env->capturing) return fail(CHUB_ERR_UNSUPPORTED, "chub_return_norm_set_state between chub_graph_begin and chub_graph_end (it copies and synchronises)");
+    ReturnNormBlobHead h;
+    memcpy(&h, blob, sizeof h);
+    if (h.magic != CHUB_RETURN_NORM_MAGIC) return fail(CHUB_ERR_ARG, "chub_return_norm_set_state: not a return-norm state blob (the magic differs)");
+    if (h.n_envs != rn->env->hp.n_envs) return fail(CHUB_ERR_ARG, "chub_return_norm_set_state: the blob was taken from an object of another N");
+    HIP_TRY(hipSetDevice(rn->env->device));
+    (void) hipGetLastError();
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(rn->d_state, h.state, sizeof h.state, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(rn->d_scale, &h.scale, sizeof h.scale, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(rn->d_carry, static_cast<const char *>(blob) + sizeof h, (size_t) h.n_envs * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    return CHUB_OK;
+}
+
+int chub_return_norm_fold(double state[3], float *scale, double n_b, double K, double S1, double S2, double eps) {
+    if (!state || !scale) return fail(CHUB_ERR_ARG, "null argument");
+    if (!(eps > 0.0) || !__builtin_isfinite(eps)) return fail(CHUB_ERR_ARG, "chub_return_norm_fold: eps is finite and above 0");
+    return_norm_fold(state, scale, n_b, K, S1, S2, eps);
     return CHUB_OK;
 }
 

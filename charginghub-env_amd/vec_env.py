@@ -1008,6 +1008,98 @@ def lagrange_fold(constraint, lam, words, stats):
     check(_lib.load_library().chub_lagrange_fold(C.byref(c), _ptr(lam), _ptr(words), _ptr(st)))
 
 
+class DeviceReturnNorm(object):
+    """Reward scaling by the running spread of the discounted return (chub_return_norm_*, include/chub.h "reward scaling on the device";
+    stable-baselines' VecNormalize with norm_reward): made by VecChargingHub.make_return_norm.  update_device, gae_device and the two
+    resets enqueue on the caller's stream and are recordable into a graph; state, scale and get_state / set_state synchronise."""
+
+    def __init__(self, env, gamma=0.99, eps=1e-8, clip=10.0):
+        self._env = env
+        self._lib = env._lib
+        self.gamma, self.eps, self.clip = float(gamma), float(eps), float(clip)
+        spec = _lib.ChubReturnNormSpec(self.gamma, self.clip, self.eps)
+        h = C.c_void_p()
+        check(self._lib.chub_return_norm_create(env._h, C.byref(spec), C.byref(h)))
+        self._g = h
+        st, sc, ca = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(self._lib.chub_return_norm_device(self._g, C.byref(st), C.byref(sc), C.byref(ca)))
+        self.state_address, self.scale_address, self.carry_address = st.value, sc.value, ca.value
+
+    def update_device(self, n_steps, d_packed, d_mask=0, stream=0):
+        """a rollout's blocks d_packed [T, N, D + 2] into the running state, then the scale (chub_return_norm_update_device): two launches"""
+        check(self._lib.chub_return_norm_update_device(self._g, d_packed or None, int(n_steps), d_mask or None, stream or None))
+
+    def gae_device(self, n_steps, d_packed, d_values, d_adv, d_ret=0, d_final_values=0, gamma=0.99, lam=0.95, d_mask=0, d_stats=0, stream=0):
+        """VecChargingHub.rollout_gae with every reward multiplied by the object's scale word and clipped (chub_return_norm_gae_device)"""
+        g = _lib.ChubGae(int(n_steps), d_packed or None, d_values or None, d_final_values or None, d_mask or None, float(gamma), float(lam),
+                         d_adv or None, d_ret or None, d_stats or None)
+        check(self._lib.chub_return_norm_gae_device(self._g, C.byref(g), stream or None))
+
+    def reset_carry_device(self, d_mask=0, stream=0):
+        """the carried return of the named envs (none: all) back to 0 (chub_return_norm_reset_carry_device)"""
+        check(self._lib.chub_return_norm_reset_carry_device(self._g, d_mask or None, stream or None))
+
+    def reset_device(self, stream=0):
+        """state, scale and carry to empty (chub_return_norm_reset_device)"""
+        check(self._lib.chub_return_norm_reset_device(self._g, stream or None))
+
+    def get_state(self):
+        """the state, the scale and the carry as bytes, for a checkpoint (chub_return_norm_get_state); synchronises"""
+        n = C.c_int64()
+        check(self._lib.chub_return_norm_state_size(self._g, C.byref(n)))
+        blob = np.zeros(n.value, dtype=np.uint8)
+        check(self._lib.chub_return_norm_get_state(self._g, _ptr(blob)))
+        return blob.tobytes()
+
+    def set_state(self, blob):
+        """get_state's bytes back (chub_return_norm_set_state): a blob of another N is refused"""
+        n = C.c_int64()
+        check(self._lib.chub_return_norm_state_size(self._g, C.byref(n)))
+        b = np.frombuffer(bytes(blob), dtype=np.uint8).copy()
+        if b.size < _lib.RETURN_NORM_BLOB_HEAD:
+            raise ValueError("set_state: not a state blob (%d bytes)" % b.size)
+        N = int(b[8:16].view(np.int64)[0])
+        if int(b[:8].view(np.uint64)[0]) == _lib.RETURN_NORM_MAGIC and b.size != _lib.RETURN_NORM_BLOB_HEAD + 4 * max(N, 0):
+            raise ValueError("set_state: %d bytes, a blob of N = %d has %d" % (b.size, N, _lib.RETURN_NORM_BLOB_HEAD + 4 * max(N, 0)))
+        check(self._lib.chub_return_norm_set_state(self._g, _ptr(b)))  # (another magic or another N: the library refuses it, from the head alone)
+
+    def _head(self):
+        b = np.frombuffer(self.get_state(), dtype=np.uint8)
+        return b[16:40].view(np.float64).copy(), b[40:44].view(np.float32)[0], b[_lib.RETURN_NORM_BLOB_HEAD:].view(np.float32).copy()
+
+    def state(self):
+        """(n, mean, M2) as float64 [3]; synchronises"""
+        return self._head()[0]
+
+    def scale(self):
+        """scale32 as numpy float32; synchronises"""
+        return self._head()[1]
+
+    def carry(self):
+        """the carried return per env, float32 [N]; synchronises"""
+        return self._head()[2]
+
+    def close(self):
+        if getattr(self, "_g", None) and getattr(self._env, "_h", None):
+            check(self._lib.chub_return_norm_destroy(self._g))
+        self._g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def return_norm_fold(state, n_b, K, S1, S2, eps=1e-8):
+    """the merge of a call's sums into the running state and the scale that follows, on host memory (chub_return_norm_fold; no device):
+    state float64 [3] = (n, mean, M2) is updated in place; returns scale32, or None where n_b == 0 wrote nothing"""
+    assert state.dtype == np.float64 and state.size == 3 and state.flags.c_contiguous
+    sc = np.full(1, np.nan, dtype=np.float32)
+    check(_lib.load_library().chub_return_norm_fold(_ptr(state), _ptr(sc), float(n_b), float(K), float(S1), float(S2), float(eps)))
+    return None if not n_b > 0 else sc[0]
+
+
 def ppo_update_plan(n_rows, minibatch_rows):
     """(minibatches per epoch, rows of the last one) of ppo_update's split (chub_ppo_update_plan; host arithmetic only)"""
     m, last = C.c_int64(), C.c_int64()
@@ -1680,6 +1772,11 @@ class VecChargingHub(object):
         """K = 1 .. 4 constraints with their multipliers for this handle -> DeviceLagrange (chub_lagrange_create).  constraints: dicts
         with column (within the terms rows its gae will be given), kind "step" | "done", limit, lr, lambda0, lambda_max (0: no ceiling)"""
         return DeviceLagrange(self, constraints)
+
+    def make_return_norm(self, gamma=0.99, eps=1e-8, clip=10.0):
+        """running statistics of the discounted return and the reward scale they give, for this handle -> DeviceReturnNorm
+        (chub_return_norm_create): VecNormalize's norm_reward with its defaults; clip 0 = none"""
+        return DeviceReturnNorm(self, gamma=gamma, eps=eps, clip=clip)
 
     def ppo_update(self, grad, critic, actor_opt, critic_opt, n_rows, d_features, d_u, d_logp_old, d_adv, d_ret, d_rows, epochs, minibatch_rows, key,
                    d_pile_bits=0, d_set_bits=0, d_adv_stats=0, d_v_old=0, ld_features=None, loss="ppo_clip", value_loss="mse", clip_eps=0.2,

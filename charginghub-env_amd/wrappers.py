@@ -766,14 +766,16 @@ class TorchHubVecEnv(object):
                 self.reset()
         return ro
 
-    def advantages(self, rollout, values, final_values=None, gamma=0.99, lam=0.95, stats=False):
+    def advantages(self, rollout, values, final_values=None, gamma=0.99, lam=0.95, stats=False, reward_norm=None):
         """Generalised advantage estimation over a ``collect`` rollout, on torch's current stream in one launch (chub_rollout_gae_device):
         values [T + 1, N] float32 CUDA = the critic on ``rollout["obs0"]`` and then on every block's observation
         (``rollout["packed"][:, :, :D]``); final_values [N] = the critic on ``last_obs`` (the terminal rows of ``autoreset="per_env"``),
         read only where done fires; None: an episode's end is worth 0.  Returns (adv, ret), float32 [T, N] CUDA tensors the next call with
         the same T overwrites; with stats=True (adv, ret, stats), stats a float64 [3] CUDA tensor: count, sum and sum of squares of the
         advantages (mean and variance for normalisation with nothing read back).  Exact f32: delta = (r + gamma vn) - V,
-        adv = delta + (gamma lam) adv', every operation rounded once."""
+        adv = delta + (gamma lam) adv', every operation rounded once.  reward_norm: a ``make_reward_normalizer`` object
+        (chub_return_norm_gae_device) -- r is the rollout's reward times the object's scale word, clipped to its clip; the critic then
+        learns returns in scaled units.  None: the raw reward."""
         torch = self.torch
         packed = rollout["packed"]
         T, N = int(packed.shape[0]), self.num_envs
@@ -790,9 +792,12 @@ class TorchHubVecEnv(object):
             out = cache[T] = (torch.zeros((T, N), dtype=torch.float32, device=self.device), torch.zeros((T, N), dtype=torch.float32, device=self.device),
                               torch.zeros((3,), dtype=torch.float64, device=self.device))
         adv, ret, st = out
-        self.vec.gae_device(T, packed.data_ptr(), values.data_ptr(), adv.data_ptr(), d_ret=ret.data_ptr(),
-                            d_final_values=0 if final_values is None else final_values.data_ptr(), gamma=gamma, lam=lam,
-                            d_stats=st.data_ptr() if stats else 0, stream=self._stream())
+        if reward_norm is not None:
+            self._own_reward_norm(reward_norm, "advantages")
+        gae = self.vec.gae_device if reward_norm is None else reward_norm.gae_device
+        gae(T, packed.data_ptr(), values.data_ptr(), adv.data_ptr(), d_ret=ret.data_ptr(),
+            d_final_values=0 if final_values is None else final_values.data_ptr(), gamma=gamma, lam=lam,
+            d_stats=st.data_ptr() if stats else 0, stream=self._stream())
         return (adv, ret, st) if stats else (adv, ret)
 
     # ---- actor gradients on the device (chub_policy_grad_*): the policy-gradient step with no autograd for the actor
@@ -1194,6 +1199,43 @@ class TorchHubVecEnv(object):
     def critic_weights(self, critic):
         """The critic's LIVE weights -> [(W, b), ..] in nn.Linear's layout, new float32 CUDA tensors filled on torch's current stream"""
         return self._weights(critic)
+
+    # ---- reward scaling by running return statistics (chub_return_norm_*): VecNormalize's norm_reward with nothing read back
+    def make_reward_normalizer(self, gamma=0.99, eps=1e-8, clip=10.0):
+        """Running statistics of the discounted return, per env across rollouts, and the reward scale 1 / sqrt(var + eps) they give ->
+        DeviceReturnNorm (VecChargingHub.make_return_norm).  gamma is the discount of the tracked return (the trainer's), clip bounds
+        the scaled reward (0: none).  ``update_reward_normalizer`` then ``advantages(..., reward_norm=rn)`` per rollout, as VecNormalize
+        updates before it normalises.  Episode accounting (``episode_stats``) stays in raw units."""
+        return self.vec.make_return_norm(gamma=gamma, eps=eps, clip=clip)
+
+    def _own_reward_norm(self, rn, who):
+        if getattr(rn, "_env", None) is not self.vec:
+            raise ValueError("%s: the reward normaliser was made for another handle" % who)
+
+    def update_reward_normalizer(self, rollout, rn, mask=None):
+        """Add the discounted returns of a ``collect`` rollout to `rn` and set its scale from them, two launches on torch's current
+        stream (chub_return_norm_update_device).  The return of an env's running episode is carried to the next call.  mask: a uint8 /
+        bool CUDA tensor [N]; only the envs it names count or move their carry.  Returns rn."""
+        torch = self.torch
+        self._own_reward_norm(rn, "update_reward_normalizer")
+        packed = rollout["packed"]
+        if not (self._on_device(packed) and packed.dtype == torch.float32 and packed.is_contiguous() and packed.dim() == 3
+                and tuple(packed.shape[1:]) == (self.num_envs, self.obs_dim + 2)):
+            raise AssertionError("rollout['packed'] must be a contiguous float32 tensor on %s of shape (T, %d, %d)"
+                                 % (self.device, self.num_envs, self.obs_dim + 2))
+        d_mask = 0
+        if mask is not None:
+            if not (self._on_device(mask) and mask.dtype in (torch.uint8, torch.bool) and mask.is_contiguous() and tuple(mask.shape) == (self.num_envs,)):
+                raise AssertionError("mask must be a contiguous uint8 or bool tensor on %s of shape (%d,)" % (self.device, self.num_envs))
+            d_mask = mask.data_ptr()
+        rn.update_device(int(packed.shape[0]), packed.data_ptr(), d_mask=d_mask, stream=self._stream())
+        return rn
+
+    def reward_scale(self, rn):
+        """The scale `rn` multiplies rewards by, as a float32 [1] CUDA tensor over the object's own word: nothing is read or copied, and a
+        later update shows in it (clone it to keep a value)."""
+        self._own_reward_norm(rn, "reward_scale")
+        return self._device_view(rn.scale_address, (1,))
 
     # ---- a normaliser that follows the rollouts (chub_moments_*, chub_policy_normalizer_from_moments_device)
     def update_normalizer(self, policy, rollout, moments=None, eps=1e-8, mask=None):

@@ -17,7 +17,9 @@
 10. PPO epochs with no torch optimiser: Adam and the minibatch shuffle on the device, the epoch recorded once and replayed;
 11. three PPO iterations whose update is ONE call with target_kl, and the numbers stable-baselines3 prints read once per iteration;
 12. three PPO-Lagrangian iterations: the grid draw over the limit and the tank's end-of-day penalty as constraints, their multipliers,
-    cost advantages and the combined advantage on the device, one cost critic per constraint.
+    cost advantages and the combined advantage on the device, one cost critic per constraint;
+13. part 11's three iterations with the reward scaled by the running spread of the discounted return (VecNormalize's norm_reward): the
+    statistics, the scale and the scaled advantages stay on the device.
 """
 import os
 import sys
@@ -484,6 +486,39 @@ def ppo_lagrangian(n=4096, steps=64, minibatches=4, epochs=2, iterations=3):
     env.close()
 
 
+def ppo_with_reward_scaling(n=4096, steps=64, minibatches=4, epochs=4, iterations=3):
+    import charginghub_env_amd as chub
+
+    if torch is None:
+        print("13. skipped: torch is not installed")
+        return
+    env = chub.TorchHubVecEnv(n, seed=0, autoreset="per_env", **HUB)
+    D, A = env.obs_dim, env.act_dim
+    net = torch.nn.Sequential(torch.nn.Linear(D, 64), torch.nn.Tanh(), torch.nn.Linear(64, A)).to("cuda")
+    vnet = torch.nn.Sequential(torch.nn.Linear(D, 64), torch.nn.Tanh(), torch.nn.Linear(64, 1)).to("cuda")
+    policy = env.load_policy(net)
+    policy.set_exploration(key=7, log_std=[-0.5, -0.5])
+    critic = env.load_critic(vnet)
+    a_opt = env.make_optimizer(policy, lr=3e-4, max_grad_norm=0.5)
+    c_opt = env.make_optimizer(critic, lr=1e-3, max_grad_norm=0.5)
+    log = env.make_train_log()
+    rn = env.make_reward_normalizer(gamma=0.99, eps=1e-8, clip=10.0)   # the state [n, mean, M2], the scale and a carry per env, on the device
+    scale = env.reward_scale(rn)                                        # a tensor over the object's own word: no read until it is printed
+    env.reset()
+    for it in range(iterations):
+        ro = env.collect(policy, steps, logp_piles="decidable")
+        values, final = env.values(critic, ro)
+        env.update_reward_normalizer(ro, rn)                            # update first, then normalise, as VecNormalize does
+        adv, ret, adv_stats = env.advantages(ro, values, final, gamma=0.99, lam=0.95, stats=True, reward_norm=rn)
+        v_old = values[:steps].clone()
+        env.ppo_update(ro, adv, ret, a_opt, c_opt, epochs=epochs, minibatch_rows=steps * n // minibatches, key=11 + it, clip_eps=0.2,
+                       ent_coef=0.01, v_old=v_old, adv_stats=adv_stats, target_kl=0.02, log=log)
+        s = env.train_log_summary(log)
+        print("13. iteration %d: reward scale %.6g, value_loss %.4f, explained_variance %.3f, approx_kl %.5f, policy_loss %.4f"
+              % (it, float(scale[0]), s["value_loss"], s["explained_variance"], s["approx_kl"], s["policy_loss"]))
+    env.close()
+
+
 if __name__ == "__main__":
     single_env()
     batched_host()
@@ -497,3 +532,4 @@ if __name__ == "__main__":
     ppo_epochs_on_device()
     ppo_with_log_and_target_kl()
     ppo_lagrangian()
+    ppo_with_reward_scaling()

@@ -1566,6 +1566,76 @@ int chub_lagrange_get_state(chub_lagrange *lag, void *blob);
 int chub_lagrange_set_state(chub_lagrange *lag, const void *blob);
 int chub_lagrange_fold(const chub_constraint *c, double *lambda, double *words /* [3] */, const double *stats /* [6] */); /* host-only */
 
+/* ---- reward scaling on the device: running statistics of the discounted return, a GAE that divides by their spread -----------------------
+ * The reward side of stable-baselines' VecNormalize (norm_reward): rewards are divided by the running standard deviation of the
+ * discounted return and clipped; no mean is subtracted.  The reward here is money and its scale moves with the hub's shape; everything
+ * from chub_rollout_gae_device on reads it raw.  A chub_return_norm is bound to a handle and holds gamma (f32), eps (f64) and clip (f32,
+ * 0 = none); in device memory, outside the arena, the state [n, mean, M2] f64, the word scale32 (f32), a carry g[N] f32 and the partials
+ * of the reduction.  chub_state_size and snapshots are unchanged, no simulation state is read and no tick is consumed; chub_destroy frees
+ * a handle's objects first, as it does its moments objects.  After create: state zeros, scale32 = 1.0f, carry zeros.
+ *   chub_return_norm_update_device: the rollout's blocks d_packed [T][N][D + 2] into the state, two launches on `stream`.  Per counted env
+ *     e, forward in t, in f32 with every operation rounded once and no contraction, g starting at carry[e]:
+ *       g = gamma * g + packed[t][e][D]              (two operations)
+ *       g is counted
+ *       if packed[t][e][D + 1] != 0:  g = 0          (after counting: stable-baselines' order)
+ *     and carry[e] = g after t = T - 1.  With d_mask [N] u8 an env not named is not read, not counted and its carry keeps its bits.  The
+ *     n_b = T (counted envs) values join the state by the pivoted form of "running feature statistics", all in f64, every operation
+ *     rounded once:
+ *       K     = n > 0 ? mean : (double) packed[0][0][D]       (row 0 serves whether env 0 is masked or not)
+ *       d     = (double) g - K,   S1 = sum d,   S2 = sum d d
+ *       M2_b  = t < 0 ? 0 : t  with  t = S2 - S1 S1 / n_b     (a NaN stays a NaN)
+ *       n'    = n + n_b
+ *       n > 0:   mean' = K + S1 / n',   M2' = (M2 + M2_b) + (S1 / n_b)^2 (n n_b / n')
+ *       n == 0:  mean' = K + S1 / n_b,  M2' = M2_b
+ *       scale32 = n' == 0 ? 1.0f : (float) (1 / sqrt(M2' / n' + eps))      (the population variance; IEEE f64 division and square root)
+ *     n_b == 0 writes nothing: state and scale32 keep their bits.  Order of the sums: a lane takes its env's values t ascending; lanes are
+ *     envs 256 b .. 256 b + 255 of workgroup b and meet in the tree h = 128, 64, .. 1 (lane l += lane l + h); lane l of the one merge
+ *     workgroup takes partials l, l + 256, .. ascending from 0, then the same tree.  No atomics: two calls give identical bits.
+ *     chub_return_norm_fold is the merge and the scale as host code, compiled from the function the merge kernel runs: state [3] and
+ *     *scale are updated from (n_b, K, S1, S2); it needs no device.
+ *   chub_return_norm_gae_device: chub_rollout_gae_device's recurrence, operation for operation, reduction and d_stats included, with
+ *     packed[t][D] replaced by
+ *       r' = packed[t][D] * scale32                             (one f32 operation)
+ *       if clip != 0:  r' = r' > clip ? clip : (r' < -clip ? -clip : r')     (selects: a NaN stays a NaN)
+ *     scale32 is loaded from the object's device word inside the kernel: a replayed graph uses the scale its own update launch left.
+ *     chub_gae is shared unchanged.  With scale32 == 1 and clip == 0 every output has chub_rollout_gae_device's bits.  The statistics'
+ *     partials are the handle's one buffer: calls that ask for d_stats are ordered as chub_rollout_gae_device's are.
+ *   chub_return_norm_reset_carry_device: carry[e] = 0 for the named envs (d_mask NULL: all), for lock-step trainers that reset between
+ *     rollouts; chub_return_norm_reset_device: state zeros, scale32 = 1.0f, carry zeros.  One launch each.
+ *   chub_return_norm_device gives the addresses of the state [3], scale32 and the carry [N] (each may be NULL); they never move.
+ *   chub_return_norm_get_state / _set_state move a blob of chub_return_norm_state_size bytes for checkpoints; both synchronise.  The blob:
+ *     a magic (u64), N (i64), the state [3] f64, scale32 with four bytes of padding, the carry [N] f32.  set_state installs scale32 as
+ *     the blob gives it.  A blob with another magic or of another N is refused.
+ *   Manners of the device calls: no synchronisation, no allocation, no atomics, the same bits on every call; recordable between
+ *     chub_graph_begin and chub_graph_end, not counted among its resets and steps.  Calls on one object must be ordered against each other.
+ * Refusals, all with a message and before any device work.  CHUB_ERR_ARG: a null argument (rn, spec, out, d_packed, g, its d_packed,
+ *     d_values or d_adv, a blob); T <= 0; gamma (the spec's, the call's) or lambda outside [0, 1] or NaN; eps <= 0 or not finite; clip < 0
+ *     or NaN; a blob of another N.  No C call takes both a handle and an object: the Python adapter refuses an object made for another
+ *     handle.  The kernels address with 64 bits: no block size is refused.  CHUB_ERR_UNSUPPORTED: tape handles; create, destroy and the
+ *     state calls between chub_graph_begin and chub_graph_end.
+ * Out of scope: scaling cost returns (chub_lagrange limits stay in raw units); statistics per step inside a rollout (one scale per
+ *     rollout: the critic's targets share a scale within a batch); writing the scaled rewards out; subtracting a mean (VecNormalize does
+ *     not either); episode accounting, which stays in raw units as Monitor under VecNormalize does. */
+typedef struct chub_return_norm chub_return_norm;
+typedef struct chub_return_norm_spec {
+    float gamma;                  /* [0, 1]: the discount of the return whose spread is tracked */
+    float clip;                   /* >= 0; 0: none */
+    double eps;                   /* > 0, finite */
+} chub_return_norm_spec;
+#define CHUB_RETURN_NORM_MAGIC 0x314d524e52424843ull   /* "CHBRNRM1" */
+int chub_return_norm_create(chub_env *env, const chub_return_norm_spec *spec, chub_return_norm **out);
+int chub_return_norm_destroy(chub_return_norm *rn);
+int chub_return_norm_update_device(chub_return_norm *rn, const float *d_packed /* [T][N][D + 2] */, int64_t T,
+                                   const uint8_t *d_mask /* [N] or NULL */, void *stream);
+int chub_return_norm_gae_device(chub_return_norm *rn, const chub_gae *g, void *stream);
+int chub_return_norm_reset_carry_device(chub_return_norm *rn, const uint8_t *d_mask /* [N] or NULL */, void *stream);
+int chub_return_norm_reset_device(chub_return_norm *rn, void *stream);
+int chub_return_norm_device(chub_return_norm *rn, const double **d_state /* [3] */, const float **d_scale /* [1] */, const float **d_carry /* [N] */);
+int chub_return_norm_state_size(chub_return_norm *rn, int64_t *bytes);
+int chub_return_norm_get_state(chub_return_norm *rn, void *blob);        /* host; synchronises */
+int chub_return_norm_set_state(chub_return_norm *rn, const void *blob);  /* host; synchronises */
+int chub_return_norm_fold(double state[3], float *scale, double n_b, double K, double S1, double S2, double eps);  /* host-only */
+
 /* The FCEV waiting list is unbounded as in the reference (HYD:264-265): the entries a list that still gets served can
  * hold are kept one by one, and once no prefix of it fits into 15 minutes any more (HYD:270-276: nobody is served again
  * until reset and the list only grows) its entries are folded into their count and running sums, which is all the

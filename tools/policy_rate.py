@@ -44,6 +44,12 @@
                   the same arithmetic as one torch expression, combine_k2_rotating: the launch over four rotating sets of its arrays, more
                   than the 256 MiB cache holds; lagrange_step: the multipliers' launch.  us per call between two events,
                   with the bytes each call must move (bytes_useful) and the bytes its strided reads touch at 64-byte granularity (bytes_lines).
+  --return-norm   a case of its own (torch first, TorchHubVecEnv; T = 96): on one collected rollout, gae_reward: chub_rollout_gae_device
+                  (with ret and stats) as the parent commit has it; gae_scaled: chub_return_norm_gae_device on the same arrays;
+                  return_norm_update: chub_return_norm_update_device (two launches); return_norm_torch: the same arithmetic as eager
+                  torch (a forward loop for g, var, the scaled and clipped reward).  us per call between two events, with bytes_useful
+                  and bytes_lines as --lagrange counts them.  With CHUB_LIB=<the parent's libchub.so> only gae_reward runs: the
+                  unscaled call on the parent's library, for the process-to-process spread.
 Every case is warmed up, then the cases alternate, ROUNDS times; median, best and worst round are reported with the build id.
 --open-loop-only measures the open loop alone, --launch-only the open loop and the deterministic launch, --no-sets the first five cases:
 with CHUB_LIB=<another build's libchub.so> those are the rates of a build without the newer entry points (the parent commit), on the same
@@ -59,7 +65,7 @@ import time
 
 import numpy as np
 
-if "--torch-gae" in sys.argv or "--torch-grad" in sys.argv or "--torch-critic" in sys.argv or "--adam" in sys.argv or "--trainlog" in sys.argv or "--lagrange" in sys.argv:
+if "--torch-gae" in sys.argv or "--torch-grad" in sys.argv or "--torch-critic" in sys.argv or "--adam" in sys.argv or "--trainlog" in sys.argv or "--lagrange" in sys.argv or "--return-norm" in sys.argv:
     import torch  # before libchub is loaded: both must share one HIP runtime
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -87,10 +93,13 @@ def main():
     ap.add_argument("--adam", action="store_true", help="the optimiser's cases alone (see the module's text)")
     ap.add_argument("--trainlog", action="store_true", help="one chub_ppo_update per epoch, with and without a training log (see the module's text)")
     ap.add_argument("--lagrange", action="store_true", help="the cost GAE, the combine and the step launches beside the reward GAE (see the module's text)")
+    ap.add_argument("--return-norm", action="store_true", help="the return statistics' update and the scaled GAE beside the reward GAE (see the module's text)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     if args.lagrange:
         return lagrange_cases(args)
+    if args.return_norm:
+        return return_norm_cases(args)
     if args.adam:
         return adam_cases(args)
     if args.trainlog:
@@ -889,6 +898,98 @@ def lagrange_cases(args):
     torch.cuda.synchronize()
     for lag, *_ in keep:
         lag.close()
+    env.close()
+
+
+def return_norm_cases(args):
+    """--return-norm: the reward scaling's launches beside the parent's reward GAE, on one collected rollout"""
+    n_s, piles_s = args.shape.split("x")
+    n, piles = int(n_s), [int(x) for x in piles_s.split(",")]
+    T = 96
+    env = chub.TorchHubVecEnv(n, piles, ["fast", "slow"], seed=1, rng="philox", autoreset="per_env", hydro_prod_rate=100.0, hydro_store_vlt=25.0,
+                              init_soc=0.2, fc_max_power=100.0, fcev_permeate=0.01)
+    build_id = chub.load_library().chub_build_id().decode()
+    D, A = env.obs_dim, env.act_dim
+    torch.manual_seed(0)
+    lin = lambda i, o: torch.nn.Sequential(torch.nn.Linear(i, 64), torch.nn.Tanh(), torch.nn.Linear(64, o)).to("cuda")
+    pol = env.load_policy(lin(D, A))
+    pol.set_exploration(7, [-0.5, -0.5])
+    crit = env.load_critic(lin(D, 1))
+    env.reset()
+    ro = env.collect(pol, T, logp_piles="decidable")
+    values, final = env.values(crit, ro)
+    R = T * n
+    row = (D + 2) * 4
+    lines = lambda stride, used: min(stride, 64 * ((used + 63) // 64 + (1 if stride % 64 else 0)))  # bytes of a strided row its reads touch, at most
+
+    def timed(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3  # us
+
+    cases, meta = {}, {}
+    gae_bytes = dict(bytes_useful=R * (8 + 4 + 4 + 4), bytes_lines=R * (lines(row, 8) + 12))
+    cases["gae_reward"] = lambda: env.advantages(ro, values, final, stats=True)
+    meta["gae_reward"] = dict(route="chub_rollout_gae_device with d_ret and d_stats", **gae_bytes)
+    rn = None
+    if os.environ.get("CHUB_LIB"):
+        try:
+            rn = env.make_reward_normalizer()
+        except chub._lib.ChubError:  # (the parent's library: the unscaled call alone)
+            rn = None
+    else:
+        rn = env.make_reward_normalizer()
+    if rn is not None:
+        cases["gae_scaled"] = lambda: env.advantages(ro, values, final, stats=True, reward_norm=rn)
+        meta["gae_scaled"] = dict(route="chub_return_norm_gae_device with d_ret and d_stats", **gae_bytes)
+        cases["return_norm_update"] = lambda: env.update_reward_normalizer(ro, rn)
+        meta["return_norm_update"] = dict(route="chub_return_norm_update_device: the moments launch and its merge", bytes_useful=R * 8 + n * 8,
+                                          bytes_lines=R * lines(row, 8) + n * 8)
+        reward, done = ro["reward"], ro["done"]
+        carry = torch.zeros((n,), dtype=torch.float32, device=env.device)
+        gs = torch.zeros((T, n), dtype=torch.float32, device=env.device)
+        zero = torch.zeros((), dtype=torch.float32, device=env.device)
+
+        def same_in_torch():
+            g = carry
+            for t in range(T):
+                g = 0.99 * g + reward[t]
+                gs[t] = g
+                g = torch.where(done[t] != 0, zero, g)
+            carry.copy_(g)
+            var = gs.double().var(unbiased=False)
+            return torch.clamp(reward * (1.0 / torch.sqrt(var + 1e-8)).float(), -10.0, 10.0)
+
+        cases["return_norm_torch"] = same_in_torch
+        meta["return_norm_torch"] = dict(route="the update's arithmetic and the scaled, clipped reward as eager torch (its temporaries included)",
+                                         bytes_useful=R * 8 + n * 8 + R * 4, bytes_lines=R * lines(row, 8) + n * 8 + R * 4)
+    for fn in cases.values():
+        fn()
+    torch.cuda.synchronize()
+    vals = {c: [] for c in cases}
+    for _ in range(args.rounds):
+        for c, fn in cases.items():
+            vals[c].append(timed(fn, 2 if c == "return_norm_torch" else 10))
+    rows = []
+    for kind, xs in vals.items():
+        med = statistics.median(xs)
+        rows.append(dict(shape=args.shape, n_envs=n, piles=piles, T=T, rows=R, kind=kind, unit="us_per_call", rounds=len(xs), median=round(med, 2),
+                         min=round(min(xs), 2), max=round(max(xs), 2), gb_per_s_useful=round(meta[kind]["bytes_useful"] / med / 1e3, 1),
+                         gb_per_s_lines=round(meta[kind]["bytes_lines"] / med / 1e3, 1), build_id=build_id, lib=os.environ.get("CHUB_LIB", ""),
+                         **meta[kind]))
+    for row_ in rows:
+        print(json.dumps(row_), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+        json.dump(rows, open(args.out, "w"), indent=1)
+    torch.cuda.synchronize()
+    if rn is not None:
+        rn.close()
     env.close()
 
 
