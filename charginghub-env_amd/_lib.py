@@ -468,8 +468,8 @@ def source_hash():
 
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
-    for name in ("chub_kernels.hip", "chub_policy.hip", "chub_critic.hip", "chub_adam.hip", "chub_trainlog.hip", "chub_lagrange.hip", "chub_retnorm.hip", "chub_runtime.cpp", "chub_comm.cpp", "chub_device.h", "chub_curves.h",
-                 "chub_plan.h", "chub_policy.h", "chub_critic.h", "chub_adam.h", "chub_trainlog.h", "chub_lagrange.h", "chub_retnorm.h"):
+    for name in ("chub_kernels.hip", "chub_policy.hip", "chub_gae.hip", "chub_critic.hip", "chub_adam.hip", "chub_trainlog.hip", "chub_lagrange.hip", "chub_retnorm.hip", "chub_runtime.cpp", "chub_comm.cpp", "chub_device.h", "chub_curves.h",
+                 "chub_plan.h", "chub_policy.h", "chub_gae.h", "chub_critic.h", "chub_adam.h", "chub_trainlog.h", "chub_lagrange.h", "chub_retnorm.h"):
         h.update(open(os.path.join(csrc, name), "rb").read())
     h.update(open(os.path.join(os.path.dirname(_HERE), "include", "chub.h"), "rb").read())
     return h.hexdigest()[:16]

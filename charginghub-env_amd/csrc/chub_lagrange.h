@@ -15,7 +15,6 @@ constexpr int kLagMaxK = 4;     // constraints of one object
 constexpr int kLagStats = 6;    // per constraint: count, sum, sum of squares of the advantages; episodes, sum and sum of squares of their costs
 constexpr int kLagWords = 3;    // per constraint: J_last, steps taken, steps skipped
 constexpr int kLagLanes = 256;  // a workgroup of k_cost_gae, of its merge and of k_lagrange_combine
-constexpr int kLagAhead = 8;    // steps whose loads are in flight before the serial chain consumes them (k_gae's kGaeAhead)
 constexpr int kLagCombineBlocks = 2048;  // the streaming launch's grid cap: a lane takes entries i, i + 2048 * 256, ..
 
 // the step rule on one constraint: lambda, its three words, its six stats

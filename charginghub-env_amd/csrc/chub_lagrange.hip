@@ -1,27 +1,15 @@
 // chub_lagrange.hip -- constrained PPO on the device (include/chub.h): the cost advantages and episode costs of a collected rollout
 // (k_cost_gae and its one-workgroup merge), the multipliers' projected ascent (k_lagrange_step) and the combined advantage
-// (k_lagrange_combine).  The launch arguments and the step rule are chub_lagrange.h's.  No atomics anywhere: two calls give the same bits.
+// (k_lagrange_combine).  The launch arguments and the step rule are chub_lagrange.h's; the recurrence's step and the reductions are
+// chub_gae.h's, shared with the reward's GAE.  No atomics anywhere: two calls give the same bits.
 // Built with -ffp-contract=off; where an operation's rounding is part of the definition it is written as the _rn intrinsic.
 #include "chub_lagrange.h"
 
+#include "chub_gae.h"
+
 namespace chub {
 
-// the tree k_gae's statistics take (chub_policy.hip, gae_block_sum), over six words
-__device__ __forceinline__ void lag_block_sum(double (*red)[kLagLanes], int tid, double (&w)[kLagStats]) {
-#pragma unroll
-    for (int i = 0; i < kLagStats; i++) red[i][tid] = w[i];
-    __syncthreads();
-    for (int h = kLagLanes / 2; h > 0; h >>= 1) {
-        if (tid < h) {
-#pragma unroll
-            for (int i = 0; i < kLagStats; i++) red[i][tid] += red[i][tid + h];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < kLagStats; i++) w[i] = red[i][0];
-    __syncthreads();  // (the next constraint's words overwrite red)
-}
+static_assert(kLagLanes == kGaeLanes, "the cost advantages' statistics take the tree the reward advantages' take");
 
 // a wave-uniform base plus a lane's 32-bit byte offset: the lane keeps one offset per array, not a 64-bit address per load in flight
 template <class T>
@@ -31,7 +19,7 @@ __device__ __forceinline__ T *lag_at(T *base, uint32_t byte_offset) {
 
 // ---- cost advantages and episode costs.  One lane per env, consecutive lanes on consecutive envs: done, V, adv and ret are read and written
 // as k_gae reads and writes them; a cost is ONE float of a terms row, so a wave's cost load touches 64 rows C floats apart (callers collect
-// only the columns they constrain).  Only the recurrences are serial in t: the loads of kLagAhead steps -- done once, a cost and a value per
+// only the columns they constrain).  Only the recurrences are serial in t: the loads of kGaeAhead steps -- done once, a cost and a value per
 // constraint -- are issued before the chain that consumes them, with no branch around a load (a step before t = 0 reads step 0 again and a
 // select drops it).  All K constraints share the pass over done.  K is a template argument: every per-constraint array is indexed by
 // constants and stays in registers.
@@ -62,10 +50,10 @@ __global__ __launch_bounds__(kLagLanes) void k_cost_gae(const CostGaeArgs a) {
             seg[c] = 0.0;
             carry_out[c] = 0.0;
         }
-        for (int64_t t1 = a.T; t1 > 0; t1 -= kLagAhead) {
-            float d[kLagAhead], cost[kLagAhead][K], v[kLagAhead][K];
+        for (int64_t t1 = a.T; t1 > 0; t1 -= kGaeAhead) {
+            float d[kGaeAhead], cost[kGaeAhead][K], v[kGaeAhead][K];
 #pragma unroll
-            for (int k = 0; k < kLagAhead; k++) {
+            for (int k = 0; k < kGaeAhead; k++) {
                 const int64_t t = t1 - 1 - k, tt = t < 0 ? 0 : t;
                 d[k] = *lag_at(a.packed + tt * N * row, o_done);  // (a uniform base and the lane's 32-bit offset: one address register per array)
 #pragma unroll
@@ -75,18 +63,17 @@ __global__ __launch_bounds__(kLagLanes) void k_cost_gae(const CostGaeArgs a) {
                 }
             }
 #pragma unroll
-            for (int k = 0; k < kLagAhead; k++) {
+            for (int k = 0; k < kGaeAhead; k++) {
                 const int64_t t = t1 - 1 - k;
                 if (t >= 0) {
                     const bool done = d[k] != 0.0f;
 #pragma unroll
                     for (int c = 0; c < K; c++) {
                         const float ct = a.kind[c] == COST_AT_DONE && !done ? 0.0f : cost[k][c];
-                        const float vn = done ? fin[c] : v_next[c];
-                        const float delta = __fsub_rn(__fadd_rn(ct, __fmul_rn(a.gamma, vn)), v[k][c]);
-                        adv[c] = __fadd_rn(delta, __fmul_rn(a.gl, done ? 0.0f : adv[c]));
+                        const GaeStep s = gae_step<const float *>(ct, done, v[k][c], &fin[c], a.gamma, a.gl, &v_next[c], &adv[c]);
+                        adv[c] = s.adv;
                         *lag_at(a.adv[c] + t * N, o_env) = adv[c];
-                        if (a.ret[c]) *lag_at(a.ret[c] + t * N, o_env) = __fadd_rn(adv[c], v[k][c]);
+                        if (a.ret[c]) *lag_at(a.ret[c] + t * N, o_env) = s.ret;
                         w[c][1] += (double) adv[c];
                         w[c][2] += __dmul_rn((double) adv[c], (double) adv[c]);
                         v_next[c] = v[k][c];
@@ -123,7 +110,8 @@ __global__ __launch_bounds__(kLagLanes) void k_cost_gae(const CostGaeArgs a) {
     }
 #pragma unroll
     for (int c = 0; c < K; c++) {
-        lag_block_sum(red, tid, w[c]);
+        block_sum(red, tid, w[c]);
+        __syncthreads();  // (the next constraint's words overwrite red)
         if (tid == 0) {
             double *p = a.partials + ((size_t) blockIdx.x * K + c) * kLagStats;
 #pragma unroll
@@ -132,20 +120,14 @@ __global__ __launch_bounds__(kLagLanes) void k_cost_gae(const CostGaeArgs a) {
     }
 }
 
-// the workgroups' partials in ONE workgroup: lane l takes partials l, l + 256, .. in ascending order, then the same tree, constraint by constraint
+// the workgroups' partials in ONE workgroup (chub_gae.h, partials_sum), constraint by constraint
 __global__ __launch_bounds__(kLagLanes) void k_cost_gae_merge(const double *partials, int64_t blocks, int K, double *stats) {
     __shared__ double red[kLagStats][kLagLanes];
     const int tid = (int) threadIdx.x;
     for (int c = 0; c < K; c++) {
         double w[kLagStats];
-#pragma unroll
-        for (int i = 0; i < kLagStats; i++) w[i] = 0.0;
-        for (int64_t b = tid; b < blocks; b += kLagLanes) {
-            const double *p = partials + ((size_t) b * K + c) * kLagStats;
-#pragma unroll
-            for (int i = 0; i < kLagStats; i++) w[i] += p[i];
-        }
-        lag_block_sum(red, tid, w);
+        partials_sum(red, tid, partials + c * kLagStats, blocks, (int64_t) K * kLagStats, w);
+        __syncthreads();  // (the next constraint's words overwrite red)
         if (tid == 0) {
 #pragma unroll
             for (int i = 0; i < kLagStats; i++) stats[c * kLagStats + i] = w[i];

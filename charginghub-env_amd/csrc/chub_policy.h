@@ -105,21 +105,6 @@ void launch_policy_pop(const PolicyPopArgs &a, int waves, hipStream_t stream);
 void launch_policy_sample(const PolicySampleArgs &a, int waves, hipStream_t stream);
 void launch_policy_sample_set(const PolicySampleSetArgs &a, int waves, hipStream_t stream);
 
-// generalised advantage estimation over a rollout's blocks (include/chub.h, chub_rollout_gae_device)
-struct GaeArgs {
-    int64_t n_envs, T;
-    int32_t D;                    // reward at column D, done at D + 1 of a packed row of D + 2
-    float gamma, gl;              // gl = gamma * lambda, formed once in f32
-    const float *packed;          // [T][N][D + 2]
-    const float *values;          // [T + 1][N]
-    const float *final_values;    // [N] or null
-    const uint8_t *mask;          // [N] or null
-    float *adv, *ret;             // [T][N]; ret may be null
-    double *partials;             // [blocks][3] or null: count, sum, sum of squares per workgroup
-    double *stats;                // [3] or null
-};
-constexpr int kGaeLanes = 256;
-void launch_gae(const GaeArgs &a, hipStream_t stream);
 // running feature statistics (include/chub.h, chub_moments_update_device).  A workgroup's 256 lanes lie along the columns of a row: lane
 // r_in * L + c takes column c (and c + L where F > 256) of row r_in of the workgroup's pass, L = min(F, 256) lanes per row and
 // RW = 256 / L rows per pass.  Workgroup b takes passes b, b + blocks, b + 2 blocks, ..: the rows a workgroup sees depend on (R, F) only.

@@ -317,99 +317,6 @@ void launch_policy_sample_set(const PolicySampleSetArgs &a, int waves, hipStream
     hipLaunchKernelGGL(k_policy<PolicySampleSetArgs>, dim3((unsigned) nb), dim3(64u * (unsigned) waves), lds_bytes, stream, s);
 }
 
-// ---- generalised advantage estimation over a rollout's blocks (include/chub.h, chub_rollout_gae_device).  One lane per env, consecutive
-// lanes on consecutive envs: V, adv and ret are coalesced rows of [t][N]; reward and done are the last two floats of a packed row, fetched as
-// one 8-byte load (4-byte aligned: a row is D + 2 floats).  Only the adv recurrence is serial in t, so the loads of kGaeAhead steps are
-// issued before the chain that consumes them.  Every operation is rounded once (no contraction): a numpy f32 restatement gives the same bits.
-// Statistics: a lane sums its env's advantages and their squares in f64 in the order it writes them, the workgroup's lanes meet in a fixed
-// LDS tree, the workgroups' partials are summed by ONE workgroup of a second launch in a fixed order: no atomics, the same bits every call.
-constexpr int kGaeAhead = 8;
-struct __attribute__((packed, aligned(4))) GaeRewardDone {
-    float r, d;
-};
-
-__device__ __forceinline__ void gae_block_sum(double (*red)[kGaeLanes], int tid, double &c, double &s, double &q) {
-    red[0][tid] = c; red[1][tid] = s; red[2][tid] = q;
-    __syncthreads();
-    for (int h = kGaeLanes / 2; h > 0; h >>= 1) {
-        if (tid < h) {
-#pragma unroll
-            for (int i = 0; i < 3; i++) red[i][tid] += red[i][tid + h];
-        }
-        __syncthreads();
-    }
-    c = red[0][0]; s = red[1][0]; q = red[2][0];
-}
-
-__global__ __launch_bounds__(kGaeLanes) void k_gae(const GaeArgs a) {
-    __shared__ double red[3][kGaeLanes];
-    const int tid = (int) threadIdx.x;
-    const int64_t e = (int64_t) blockIdx.x * kGaeLanes + tid, N = a.n_envs;
-    const bool live = e < N && (!a.mask || a.mask[e] != 0);
-    double cnt = 0.0, sum = 0.0, sq = 0.0;
-    if (live) {
-        const int64_t row = (int64_t) a.D + 2;
-        const float fin = a.final_values ? a.final_values[e] : 0.0f;
-        float v_next = a.values[a.T * N + e], adv = 0.0f;
-        for (int64_t t1 = a.T; t1 > 0; t1 -= kGaeAhead) {
-            float v[kGaeAhead];
-            GaeRewardDone rd[kGaeAhead];
-#pragma unroll
-            for (int k = 0; k < kGaeAhead; k++) {
-                const int64_t t = t1 - 1 - k;
-                if (t >= 0) {
-                    v[k] = a.values[t * N + e];
-                    rd[k] = *(const GaeRewardDone *) (a.packed + (t * N + e) * row + a.D);
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < kGaeAhead; k++) {
-                const int64_t t = t1 - 1 - k;
-                if (t >= 0) {
-                    const bool done = rd[k].d != 0.0f;
-                    const float vn = done ? fin : v_next;
-                    const float delta = __fsub_rn(__fadd_rn(rd[k].r, __fmul_rn(a.gamma, vn)), v[k]);
-                    adv = __fadd_rn(delta, __fmul_rn(a.gl, done ? 0.0f : adv));
-                    a.adv[t * N + e] = adv;
-                    if (a.ret) a.ret[t * N + e] = __fadd_rn(adv, v[k]);
-                    sum += (double) adv;
-                    sq += (double) adv * (double) adv;
-                    v_next = v[k];
-                }
-            }
-        }
-        cnt = (double) a.T;
-    }
-    if (a.partials) {
-        gae_block_sum(red, tid, cnt, sum, sq);
-        if (tid == 0) {
-            double *p = a.partials + (size_t) blockIdx.x * 3;
-            p[0] = cnt; p[1] = sum; p[2] = sq;
-        }
-    }
-}
-
-// the workgroups' partials in ONE workgroup: lane l takes partials l, l + 256, .. in ascending order, then the same LDS tree
-__global__ __launch_bounds__(kGaeLanes) void k_gae_stats(const double *partials, int64_t blocks, double *stats) {
-    __shared__ double red[3][kGaeLanes];
-    const int tid = (int) threadIdx.x;
-    double c = 0.0, s = 0.0, q = 0.0;
-    for (int64_t b = tid; b < blocks; b += kGaeLanes) {
-        c += partials[b * 3]; s += partials[b * 3 + 1]; q += partials[b * 3 + 2];
-    }
-    gae_block_sum(red, tid, c, s, q);
-    if (tid == 0) {
-        stats[0] = c; stats[1] = s; stats[2] = q;
-    }
-}
-
-void launch_gae(const GaeArgs &a, hipStream_t stream) {
-    if (a.n_envs <= 0) return;
-    const int64_t nb = (a.n_envs + kGaeLanes - 1) / kGaeLanes;
-    hipLaunchKernelGGL(k_gae, dim3((unsigned) nb), dim3(kGaeLanes), 0, stream, a);
-    if (a.partials && a.stats) hipLaunchKernelGGL(k_gae_stats, dim3(1), dim3(kGaeLanes), 0, stream, (const double *) a.partials, nb, a.stats);
-}
-
 // ---- running feature statistics (include/chub.h, "running feature statistics"; the lane layout is chub_policy.h's MomentsArgs).
 // Launch 1 streams the rows: consecutive lanes read consecutive floats of a row, a lane keeps kAhead passes in flight, converts to f64,
 // subtracts its column's pivot and adds d and d d to its own sums.  The loop has no branch around a load: a row that does not count (past

@@ -14,7 +14,7 @@
 namespace chub {
 
 constexpr int kRetLanes = 256;  // a workgroup of every kernel of the unit
-constexpr int kRetAhead = 8;    // steps whose loads are in flight before the serial chain consumes them (k_gae's kGaeAhead)
+constexpr int kRetAhead = 8;    // steps of k_return_moments whose loads are in flight before the serial chain consumes them
 constexpr int kRetStreamBlocks = 1024;  // the reset kernels' grid cap: a lane takes entries i, i + 1024 * 256, ..
 
 __host__ __device__ inline double retnorm_div(double a, double b) {
@@ -76,20 +76,7 @@ struct ReturnMomentsArgs {
     float *scale;              // [1]
 };
 
-// k_gae_scaled: chub_policy.h's GaeArgs with the object's scale word and clip
-struct ScaledGaeArgs {
-    int64_t n_envs, T;
-    int32_t D;
-    float gamma, gl, clip;
-    const float *scale;        // [1], read inside the kernel
-    const float *packed, *values, *final_values;
-    const uint8_t *mask;
-    float *adv, *ret;
-    double *partials, *stats;  // both null, or [blocks][3] and [3]
-};
-
 void launch_return_moments(const ReturnMomentsArgs &a, hipStream_t stream);
-void launch_gae_scaled(const ScaledGaeArgs &a, hipStream_t stream);
 void launch_return_reset_carry(float *carry, const uint8_t *mask, int64_t n_envs, hipStream_t stream);
 void launch_return_reset(double *state, float *scale, float *carry, int64_t n_envs, hipStream_t stream);
 

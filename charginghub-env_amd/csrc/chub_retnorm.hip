@@ -1,29 +1,14 @@
 // chub_retnorm.hip -- reward scaling on the device (include/chub.h): the running variance of the discounted return over a rollout's blocks
-// (k_return_moments and its one-workgroup merge), the GAE that multiplies every reward by the scale that state gives (k_gae_scaled) and
-// the two reset streams.  The launch arguments and the merge's arithmetic are chub_retnorm.h's.  No atomics anywhere: two calls give the
-// same bits.  Built with -ffp-contract=off; where an operation's rounding is part of the definition it is written as the _rn intrinsic.
+// (k_return_moments and its one-workgroup merge) and the two reset streams.  The GAE that multiplies every reward by the scale that state
+// gives is chub_gae.hip's k_gae<true>.  The launch arguments and the merge's arithmetic are chub_retnorm.h's; the (reward, done) pair and
+// the reductions are chub_gae.h's.  No atomics anywhere: two calls give the same bits.  Built with -ffp-contract=off; where an operation's rounding is part of the definition it is written as the _rn intrinsic.
 #include "chub_retnorm.h"
+
+#include "chub_gae.h"
 
 namespace chub {
 
-// reward and done: the last two floats of a packed row as one 8-byte load (4-byte aligned: a row is D + 2 floats), as k_gae fetches them
-struct __attribute__((packed, aligned(4))) RetRewardDone {
-    float r, d;
-};
-
-// the tree k_gae's statistics take (chub_policy.hip, gae_block_sum): lane l takes lane l + h, h = 128 .. 1
-__device__ __forceinline__ void ret_block_sum(double (*red)[kRetLanes], int tid, double &c, double &s, double &q) {
-    red[0][tid] = c; red[1][tid] = s; red[2][tid] = q;
-    __syncthreads();
-    for (int h = kRetLanes / 2; h > 0; h >>= 1) {
-        if (tid < h) {
-#pragma unroll
-            for (int i = 0; i < 3; i++) red[i][tid] += red[i][tid + h];
-        }
-        __syncthreads();
-    }
-    c = red[0][0]; s = red[1][0]; q = red[2][0];
-}
+static_assert(kRetLanes == kGaeLanes, "the return's sums meet in the tree the GAE's statistics take");
 
 // ---- the discounted return's sums.  One lane per env, consecutive lanes on consecutive envs, forward in t.  Only g is serial in t: the
 // (reward, done) loads of kRetAhead steps are issued before the chain that consumes them, with NO branch around a load -- a step past
@@ -41,123 +26,51 @@ __global__ __launch_bounds__(kRetLanes) void k_return_moments(const ReturnMoment
         a.pivot[1] = K;
     }
     const bool live = e < N && (!a.mask || a.mask[e] != 0);
-    double cnt = 0.0, s1 = 0.0, s2 = 0.0;
+    double w[3] = {0.0, 0.0, 0.0};  // n_b, S1, S2
     if (live) {
         const int64_t row = (int64_t) a.D + 2, step = N * row, last = a.T - 1;
         const float *p = a.packed + e * row + a.D;  // (step t's pair lies at p + t * step)
         float g = a.carry[e];
         for (int64_t t0 = 0; t0 < a.T; t0 += kRetAhead) {
-            RetRewardDone rd[kRetAhead];
+            GaeRewardDone rd[kRetAhead];
 #pragma unroll
             for (int k = 0; k < kRetAhead; k++) {
                 const int64_t t = t0 + k;
-                rd[k] = *(const RetRewardDone *) (p + (t > last ? last : t) * step);
+                rd[k] = *(const GaeRewardDone *) (p + (t > last ? last : t) * step);
             }
 #pragma unroll
             for (int k = 0; k < kRetAhead; k++) {
                 const bool ok = t0 + k <= last;
                 const float gn = __fadd_rn(__fmul_rn(a.gamma, g), rd[k].r);
                 const double d = __dsub_rn((double) gn, K);
-                s1 = ok ? __dadd_rn(s1, d) : s1;
-                s2 = ok ? __dadd_rn(s2, __dmul_rn(d, d)) : s2;
+                w[1] = ok ? __dadd_rn(w[1], d) : w[1];
+                w[2] = ok ? __dadd_rn(w[2], __dmul_rn(d, d)) : w[2];
                 g = ok ? (rd[k].d != 0.0f ? 0.0f : gn) : g;  // (zeroed AFTER it was counted: VecNormalize's order)
             }
         }
         a.carry[e] = g;
-        cnt = (double) a.T;
+        w[0] = (double) a.T;
     }
-    ret_block_sum(red, tid, cnt, s1, s2);
+    block_sum(red, tid, w);
     if (tid == 0) {
         double *q = a.partials + (size_t) blockIdx.x * 3;
-        q[0] = cnt; q[1] = s1; q[2] = s2;
+        q[0] = w[0]; q[1] = w[1]; q[2] = w[2];
     }
 }
 
-// the workgroups' partials in ONE workgroup: lane l takes partials l, l + 256, .. in ascending order, then the same tree; lane 0 merges
-// into the state and writes the scale.  n and K are launch 1's copies
+// the workgroups' partials in ONE workgroup (chub_gae.h, partials_sum); lane 0 merges into the state and writes the scale.  n and K are launch 1's copies
 __global__ __launch_bounds__(kRetLanes) void k_return_merge(const double *partials, int64_t blocks, const double *pivot, double *state, float *scale,
                                                             double eps) {
     __shared__ double red[3][kRetLanes];
     const int tid = (int) threadIdx.x;
-    double c = 0.0, s1 = 0.0, s2 = 0.0;
-    for (int64_t b = tid; b < blocks; b += kRetLanes) {
-        c += partials[b * 3]; s1 += partials[b * 3 + 1]; s2 += partials[b * 3 + 2];
-    }
-    ret_block_sum(red, tid, c, s1, s2);
-    if (tid == 0 && c > 0.0) {
+    double w[3];
+    partials_sum(red, tid, partials, blocks, 3, w);
+    if (tid == 0 && w[0] > 0.0) {
         double st[3] = {pivot[0], state[1], state[2]};
         float sc = 1.0f;
-        return_norm_fold(st, &sc, c, pivot[1], s1, s2, eps);
+        return_norm_fold(st, &sc, w[0], pivot[1], w[1], w[2], eps);
         state[0] = st[0]; state[1] = st[1]; state[2] = st[2];
         *scale = sc;
-    }
-}
-
-// ---- the scaled GAE: k_gae (chub_policy.hip) restated, its layout, its recurrence operation for operation and its reduction, with the
-// reward replaced by r' = r * scale32, clipped by selects (a NaN stays a NaN).  scale32 is ONE uniform load from the object's word: a
-// replayed graph multiplies by what the update launched before it left there.
-__global__ __launch_bounds__(kRetLanes) void k_gae_scaled(const ScaledGaeArgs a) {
-    __shared__ double red[3][kRetLanes];
-    const int tid = (int) threadIdx.x;
-    const int64_t e = (int64_t) blockIdx.x * kRetLanes + tid, N = a.n_envs;
-    const bool live = e < N && (!a.mask || a.mask[e] != 0);
-    const float scale = *a.scale, clip = a.clip, nclip = -a.clip;
-    double cnt = 0.0, sum = 0.0, sq = 0.0;
-    if (live) {
-        const int64_t row = (int64_t) a.D + 2;
-        const float fin = a.final_values ? a.final_values[e] : 0.0f;
-        float v_next = a.values[a.T * N + e], adv = 0.0f;
-        for (int64_t t1 = a.T; t1 > 0; t1 -= kRetAhead) {
-            float v[kRetAhead];
-            RetRewardDone rd[kRetAhead];
-#pragma unroll
-            for (int k = 0; k < kRetAhead; k++) {
-                const int64_t t = t1 - 1 - k;
-                if (t >= 0) {
-                    v[k] = a.values[t * N + e];
-                    rd[k] = *(const RetRewardDone *) (a.packed + (t * N + e) * row + a.D);
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < kRetAhead; k++) {
-                const int64_t t = t1 - 1 - k;
-                if (t >= 0) {
-                    const bool done = rd[k].d != 0.0f;
-                    float r = __fmul_rn(rd[k].r, scale);
-                    if (clip != 0.0f) r = r > clip ? clip : (r < nclip ? nclip : r);
-                    const float vn = done ? fin : v_next;
-                    const float delta = __fsub_rn(__fadd_rn(r, __fmul_rn(a.gamma, vn)), v[k]);
-                    adv = __fadd_rn(delta, __fmul_rn(a.gl, done ? 0.0f : adv));
-                    a.adv[t * N + e] = adv;
-                    if (a.ret) a.ret[t * N + e] = __fadd_rn(adv, v[k]);
-                    sum += (double) adv;
-                    sq += (double) adv * (double) adv;
-                    v_next = v[k];
-                }
-            }
-        }
-        cnt = (double) a.T;
-    }
-    if (a.partials) {
-        ret_block_sum(red, tid, cnt, sum, sq);
-        if (tid == 0) {
-            double *p = a.partials + (size_t) blockIdx.x * 3;
-            p[0] = cnt; p[1] = sum; p[2] = sq;
-        }
-    }
-}
-
-// k_gae_stats restated: the workgroups' partials in one workgroup, the same order
-__global__ __launch_bounds__(kRetLanes) void k_gae_scaled_stats(const double *partials, int64_t blocks, double *stats) {
-    __shared__ double red[3][kRetLanes];
-    const int tid = (int) threadIdx.x;
-    double c = 0.0, s = 0.0, q = 0.0;
-    for (int64_t b = tid; b < blocks; b += kRetLanes) {
-        c += partials[b * 3]; s += partials[b * 3 + 1]; q += partials[b * 3 + 2];
-    }
-    ret_block_sum(red, tid, c, s, q);
-    if (tid == 0) {
-        stats[0] = c; stats[1] = s; stats[2] = q;
     }
 }
 
@@ -188,14 +101,6 @@ void launch_return_moments(const ReturnMomentsArgs &a, hipStream_t stream) {
     hipLaunchKernelGGL(k_return_moments, dim3((unsigned) nb), dim3(kRetLanes), 0, stream, a);
     hipLaunchKernelGGL(k_return_merge, dim3(1), dim3(kRetLanes), 0, stream, (const double *) a.partials, nb, (const double *) a.pivot, a.state, a.scale,
                        a.eps);
-}
-
-void launch_gae_scaled(const ScaledGaeArgs &a, hipStream_t stream) {
-    if (a.n_envs <= 0) return;
-    const int64_t nb = (a.n_envs + kRetLanes - 1) / kRetLanes;
-    hipLaunchKernelGGL(k_gae_scaled, dim3((unsigned) nb), dim3(kRetLanes), 0, stream, a);
-    if (a.partials && a.stats)
-        hipLaunchKernelGGL(k_gae_scaled_stats, dim3(1), dim3(kRetLanes), 0, stream, (const double *) a.partials, nb, a.stats);
 }
 
 void launch_return_reset_carry(float *carry, const uint8_t *mask, int64_t n_envs, hipStream_t stream) {

@@ -18,6 +18,7 @@
 #include "chub_device.h"
 #include "chub_plan.h"
 #include "chub_policy.h"
+#include "chub_gae.h"
 #include "chub_critic.h"
 #include "chub_adam.h"
 #include "chub_trainlog.h"
@@ -4367,29 +4368,47 @@ int chub_policy_collect_terms(chub_env *e, chub_policy *pol, int mode, int which
     return policy_collect(e, pol, mode, which < 0 ? -1 : which, r, d_set_bits, d_obs0, first_step, stream, fields, d_terms);
 }
 
-// ---- advantages (include/chub.h, chub_rollout_gae_device): the env supplies N and D and the partials of the statistics, nothing else
-int chub_rollout_gae_device(chub_env *e, const chub_gae *g, void *stream) {
-    if (!e || !g) return fail(CHUB_ERR_ARG, "null argument");
-    if (!g->d_packed || !g->d_values || !g->d_adv) return fail(CHUB_ERR_ARG, "chub_rollout_gae_device: d_packed, d_values and d_adv are required");
-    if (g->T <= 0) return fail(CHUB_ERR_ARG, "chub_rollout_gae_device: T >= 1");
-    if (!(g->gamma >= 0.0f && g->gamma <= 1.0f) || !(g->lambda >= 0.0f && g->lambda <= 1.0f))
-        return fail(CHUB_ERR_ARG, "chub_rollout_gae_device: gamma and lambda lie in [0, 1]");
+// ---- advantages (include/chub.h, chub_rollout_gae_device): the env supplies N and D and the partials of the statistics, nothing else.
+// The horizon and the discounts of every GAE call, refused in the caller's name
+static int gae_check_T(const char *who, int64_t T) {
+    return T <= 0 ? fail(CHUB_ERR_ARG, std::string(who) + ": T >= 1") : CHUB_OK;
+}
+
+static int gae_check_discounts(const char *who, float gamma, float lambda) {
+    if (!(gamma >= 0.0f && gamma <= 1.0f) || !(lambda >= 0.0f && lambda <= 1.0f))
+        return fail(CHUB_ERR_ARG, std::string(who) + ": gamma and lambda lie in [0, 1]");
+    return CHUB_OK;
+}
+
+// a chub_gae checked and, on the env's device, stated as the unscaled launch's arguments
+static int gae_args(GaeArgs *a, const char *who, chub_env *e, const chub_gae *g) {
+    if (!g->d_packed || !g->d_values || !g->d_adv) return fail(CHUB_ERR_ARG, std::string(who) + ": d_packed, d_values and d_adv are required");
+    if (const int rc = gae_check_T(who, g->T)) return rc;
+    if (const int rc = gae_check_discounts(who, g->gamma, g->lambda)) return rc;
     HIP_TRY(hipSetDevice(e->device));
     (void) hipGetLastError();
+    a->n_envs = e->hp.n_envs;
+    a->T = g->T;
+    a->D = e->hp.obs_dim;
+    a->gamma = g->gamma;
+    a->gl = g->gamma * g->lambda;
+    a->clip = 0.0f;
+    a->scale = nullptr;
+    a->packed = g->d_packed;
+    a->values = g->d_values;
+    a->final_values = g->d_final_values;
+    a->mask = g->d_mask;
+    a->adv = g->d_adv;
+    a->ret = g->d_ret;
+    a->partials = g->d_stats ? e->d_gae_part : nullptr;
+    a->stats = g->d_stats;
+    return CHUB_OK;
+}
+
+int chub_rollout_gae_device(chub_env *e, const chub_gae *g, void *stream) {
+    if (!e || !g) return fail(CHUB_ERR_ARG, "null argument");
     GaeArgs a;
-    a.n_envs = e->hp.n_envs;
-    a.T = g->T;
-    a.D = e->hp.obs_dim;
-    a.gamma = g->gamma;
-    a.gl = g->gamma * g->lambda;
-    a.packed = g->d_packed;
-    a.values = g->d_values;
-    a.final_values = g->d_final_values;
-    a.mask = g->d_mask;
-    a.adv = g->d_adv;
-    a.ret = g->d_ret;
-    a.partials = g->d_stats ? e->d_gae_part : nullptr;
-    a.stats = g->d_stats;
+    if (const int rc = gae_args(&a, "chub_rollout_gae_device", e, g)) return rc;
     launch_gae(a, (hipStream_t) stream);
     HIP_TRY(hipGetLastError());
     return CHUB_OK;
@@ -5946,10 +5965,9 @@ int chub_lagrange_destroy(chub_lagrange *lag) {
 int chub_lagrange_gae_device(chub_lagrange *lag, const chub_cost_gae *g, void *stream) {
     if (!lag || !g) return fail(CHUB_ERR_ARG, "null argument");
     if (!g->d_terms || !g->d_packed) return fail(CHUB_ERR_ARG, "chub_lagrange_gae_device: d_terms and d_packed are required");
-    if (g->T <= 0) return fail(CHUB_ERR_ARG, "chub_lagrange_gae_device: T >= 1");
+    if (const int rc = gae_check_T("chub_lagrange_gae_device", g->T)) return rc;
     if (g->C < 1) return fail(CHUB_ERR_ARG, "chub_lagrange_gae_device: C >= 1 floats in a d_terms row");
-    if (!(g->gamma >= 0.0f && g->gamma <= 1.0f) || !(g->lambda >= 0.0f && g->lambda <= 1.0f))
-        return fail(CHUB_ERR_ARG, "chub_lagrange_gae_device: gamma and lambda lie in [0, 1]");
+    if (const int rc = gae_check_discounts("chub_lagrange_gae_device", g->gamma, g->lambda)) return rc;
     for (int32_t k = 0; k < lag->K; k++) {
         if (lag->c[k].column >= g->C) return fail(CHUB_ERR_ARG, "chub_lagrange_gae_device: a constraint's column lies outside 0 .. C - 1");
         if (!g->d_adv[k]) return fail(CHUB_ERR_ARG, "chub_lagrange_gae_device: d_adv[k] is required for every constraint");
@@ -6201,30 +6219,11 @@ int chub_return_norm_update_device(chub_return_norm *rn, const float *d_packed, 
 int chub_return_norm_gae_device(chub_return_norm *rn, const chub_gae *g, void *stream) {
     if (const int rc = return_norm_check(rn, "chub_return_norm_gae_device")) return rc;
     if (!g) return fail(CHUB_ERR_ARG, "null argument");
-    if (!g->d_packed || !g->d_values || !g->d_adv) return fail(CHUB_ERR_ARG, "chub_return_norm_gae_device: d_packed, d_values and d_adv are required");
-    if (g->T <= 0) return fail(CHUB_ERR_ARG, "chub_return_norm_gae_device: T >= 1");
-    if (!(g->gamma >= 0.0f && g->gamma <= 1.0f) || !(g->lambda >= 0.0f && g->lambda <= 1.0f))
-        return fail(CHUB_ERR_ARG, "chub_return_norm_gae_device: gamma and lambda lie in [0, 1]");
-    chub_env *e = rn->env;
-    HIP_TRY(hipSetDevice(e->device));
-    (void) hipGetLastError();
-    ScaledGaeArgs a = {};
-    a.n_envs = e->hp.n_envs;
-    a.T = g->T;
-    a.D = e->hp.obs_dim;
-    a.gamma = g->gamma;
-    a.gl = g->gamma * g->lambda;
+    GaeArgs a;
+    if (const int rc = gae_args(&a, "chub_return_norm_gae_device", rn->env, g)) return rc;
     a.clip = rn->spec.clip;
     a.scale = rn->d_scale;
-    a.packed = g->d_packed;
-    a.values = g->d_values;
-    a.final_values = g->d_final_values;
-    a.mask = g->d_mask;
-    a.adv = g->d_adv;
-    a.ret = g->d_ret;
-    a.partials = g->d_stats ? e->d_gae_part : nullptr;
-    a.stats = g->d_stats;
-    launch_gae_scaled(a, (hipStream_t) stream);
+    launch_gae(a, (hipStream_t) stream);
     HIP_TRY(hipGetLastError());
     return CHUB_OK;
 }

@@ -1,6 +1,6 @@
 """Constrained PPO on the device (include/chub.h, "constrained PPO on the device"), bit for bit against tests/lagrange_lib.py unless said
 otherwise: (1) k_cost_gae and its merge on made data over lagrange_lib.GAE_CASES (workgroup edges, look-ahead edges, K, C, columns, done
-patterns, kinds, values, masks, carries), a repeated call, two calls against the concatenation; (2) the step launch against the fold;
+patterns, kinds, values, masks, carries), a repeated call, two calls against the concatenation, chub_rollout_gae_device on the same data; (2) the step launch against the fold;
 (3) the combine launch, and a gradient call fed its output; (4) chub_policy_collect_terms against a twin's attached buffer, step by step;
 (5) one recorded iteration replayed three times against three eager ones; (6) the torch adapter's methods in a child process;
 (7) refusals and ownership."""
@@ -175,6 +175,41 @@ def test_two_calls_with_the_carry_equal_one_call_on_the_concatenation(name):
     assert g["stats"][:, 3].min() > 0
     for m in (first, second, whole):
         m.free()
+
+
+def test_the_reward_and_the_cost_entry_points_run_one_recurrence():
+    """chub_rollout_gae_device against chub_lagrange_gae_device (K = 1, CHUB_COST_STEP, C = 1) fed the same rewards as its terms: adv, ret
+    and the first three stats words bit for bit.  N = 257 is a full workgroup and one lane, T = 9 a full chunk of eight steps and a partial
+    one; an episode ends at t = 7 in env 0 and at t = 8 in env 256; every other env is masked out and keeps its canaries"""
+    N, T = 257, 9
+    v = handle(N)
+    D = v.obs_dim
+    rs = np.random.RandomState(41)
+    done = rs.uniform(size=(T, N)) < 1.0 / 9.0
+    done[7, 0] = done[8, 256] = True
+    mask = (np.arange(N) % 2 == 0).astype(np.uint8)
+    packed = rs.normal(size=(T, N, D + 2)).astype(F32)
+    packed[:, :, D + 1] = done
+    reward = np.ascontiguousarray(packed[:, :, D])
+    lag = v.make_lagrange([dict(column=0, kind="step", limit=1.0, lr=0.1)])
+    d_packed, d_terms, d_mask = dbuf(packed), dbuf(reward.reshape(T, N, 1)), dbuf(mask)
+    d_values, d_final = dbuf(rs.normal(size=(T + 1, N)).astype(F32)), dbuf(rs.normal(size=N).astype(F32))
+    out = [dbuf(np.full((T, N), CANARY, dtype=np.uint32)) for _ in range(4)]
+    d_stats = dbuf(np.full(3, CANARY_F64, dtype=np.uint64))
+    v.gae_device(T, d_packed.ptr, d_values.ptr, out[0].ptr, d_ret=out[1].ptr, d_final_values=d_final.ptr, gamma=ll.GAMMA, lam=ll.LAM, d_mask=d_mask.ptr,
+                 d_stats=d_stats.ptr)
+    lag.gae(T, 1, d_terms.ptr, d_packed.ptr, [out[2].ptr], d_ret=[out[3].ptr], d_values=[d_values.ptr], d_final_values=[d_final.ptr], gamma=ll.GAMMA,
+            lam=ll.LAM, d_mask=d_mask.ptr)
+    v.sync()
+    adv, ret, cadv, cret = [b.to_host(np.uint32, (T, N)) for b in out]
+    live = mask != 0
+    assert np.array_equal(adv, cadv) and np.array_equal(ret, cret)
+    assert not (adv[:, live] == CANARY).any() and not (ret[:, live] == CANARY).any()
+    for a in (adv, ret, cadv, cret):
+        assert (a[:, ~live] == CANARY).all(), "a masked-out env's column was written"
+    stats = d_stats.to_host(np.uint64, (3,))
+    assert np.array_equal(stats, ll.bits(lag.read()[1])[0, :3]) and stats.view(F64)[0] == T * live.sum()
+    close_all(lag, d_packed, d_terms, d_mask, d_values, d_final, d_stats, *out)
 
 
 # ---- 2. the step on the device against the fold

@@ -54,13 +54,14 @@ def test_header_device_header_and_binding_agree():
     assert _lib.COST_KIND == {"step": ll.STEP, "done": ll.AT_DONE} and (ll.STEP, ll.AT_DONE) == (0, 1)
     sizes = dict(re.findall(r"CHUB_LAG_(\w+) = (\d+)", hdr))
     assert (int(sizes["MAX_K"]), int(sizes["STATS"]), int(sizes["WORDS"])) == (_lib.LAG_MAX_K, _lib.LAG_STATS, _lib.LAG_WORDS) == (4, 6, 3)
-    for name, want in (("kLagMaxK", 4), ("kLagStats", 6), ("kLagWords", 3), ("kLagLanes", ll.LANES), ("kLagAhead", ll.AHEAD),
-                       ("kLagCombineBlocks", ll.COMBINE_BLOCKS)):
+    for name, want in (("kLagMaxK", 4), ("kLagStats", 6), ("kLagWords", 3), ("kLagLanes", ll.LANES), ("kLagCombineBlocks", ll.COMBINE_BLOCKS)):
         assert int(re.search(r"constexpr int %s = (\d+);" % name, dev).group(1)) == want, name
-    # the look-ahead and the workgroup are k_gae's
-    pol = open(os.path.join(ROOT, "charginghub-env_amd", "csrc", "chub_policy.hip")).read() + \
-        open(os.path.join(ROOT, "charginghub-env_amd", "csrc", "chub_policy.h")).read()
-    assert "constexpr int kGaeAhead = %d;" % ll.AHEAD in pol and "constexpr int kGaeLanes = %d;" % ll.LANES in pol
+    # the look-ahead is k_gae's own constant, defined once in chub_gae.h, and the workgroup equals k_gae's
+    gae = open(os.path.join(ROOT, "charginghub-env_amd", "csrc", "chub_gae.h")).read()
+    for name, want in (("kGaeLanes", ll.LANES), ("kGaeAhead", ll.AHEAD)):
+        assert [int(x) for x in re.findall(r"constexpr int %s = (\d+);" % name, gae)] == [want], name
+    kern = open(os.path.join(ROOT, "charginghub-env_amd", "csrc", "chub_lagrange.hip")).read()
+    assert "t1 -= kGaeAhead" in kern and "kLagAhead" not in kern + dev
     names = [n for n, _ in _lib.ChubConstraint._fields_]
     assert struct_fields(hdr, "chub_constraint") == names and C.sizeof(_lib.ChubConstraint) == 40
     names = ["lambda" if n == "lam" else n for n, _ in _lib.ChubCostGae._fields_]

@@ -75,6 +75,7 @@ def test_the_new_source_file_is_part_of_the_build_id():
     srcs = re.search(r"^SRCS := (.*)$", mk, flags=re.M).group(1).split()
     objs = re.search(r"^OBJS := (.*)$", mk, flags=re.M).group(1).split()
     assert "chub_policy.hip" in srcs and "chub_policy.h" in srcs and "chub_policy.o" in objs
+    assert "chub_gae.hip" in srcs and "chub_gae.h" in srcs and "chub_gae.o" in objs
     import inspect
     hashed = re.findall(r'"(chub_\w+\.(?:hip|cpp|h))"', inspect.getsource(_lib.source_hash))
     assert sorted(hashed + ["../../include/chub.h"]) == sorted(srcs)

@@ -59,9 +59,10 @@ def test_header_device_header_and_binding_agree():
     assert rl.MAGIC.to_bytes(8, "little") == b"CHBRNRM1" and _lib.RETURN_NORM_BLOB_HEAD == rl.BLOB_HEAD
     for name, want in (("kRetLanes", rl.LANES), ("kRetAhead", rl.AHEAD)):
         assert int(re.search(r"constexpr int %s = (\d+);" % name, dev).group(1)) == want, name
-    pol = open(os.path.join(ROOT, "charginghub-env_amd", "csrc", "chub_policy.hip")).read() + \
-        open(os.path.join(ROOT, "charginghub-env_amd", "csrc", "chub_policy.h")).read()
-    assert "constexpr int kGaeAhead = %d;" % rl.AHEAD in pol and "constexpr int kGaeLanes = %d;" % rl.LANES in pol
+    # the scaled GAE is k_gae itself: its look-ahead and workgroup are defined once, in chub_gae.h
+    gae = open(os.path.join(ROOT, "charginghub-env_amd", "csrc", "chub_gae.h")).read()
+    for name, want in (("kGaeLanes", rl.LANES), ("kGaeAhead", rl.AHEAD)):
+        assert [int(x) for x in re.findall(r"constexpr int %s = (\d+);" % name, gae)] == [want], name
     # the scaled call shares chub_gae unchanged
     assert re.search(r"int chub_return_norm_gae_device\(chub_return_norm \*rn, const chub_gae \*g, void \*stream\);", hdr)
 
